@@ -28,6 +28,13 @@ holds it against the guide's measured 6.3 TB/s.  `roofline.pipes`: per step, the
 HBM) would need alone, from the committed instruction-mix profile of the same kernel sources (which one binds the family).
 `--io pipelined` (any N): every rank also feeds its frames from pinned host memory through mars_hip_pipe_* and reports
 the I/O-inclusive rate (MAX over ranks), the first thing an 8-GPU run is bound by.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) is lean: set-up, W warm-up steps, the K timed steps (with the
+roofline's HIP events in the last of them, as always), `--dump-outputs` if asked, the line.  Everything else above -- the
+sustained leg, the pipelined-I/O, PCIe-inclusive, graph-only and batch-1 legs, the CPU baselines and their parity checks,
+the copy-rate probe with `roofline.pipes`, and the other BASELINE configs (`configs`) -- runs only with `--full`.  Legs asked
+for by name (`--io pipelined|camera`, `--sustain-s S`) run either way.
+`--dump-outputs DIR`: what the timed path computed in its last step, as float32 .npy files (dump_outputs() lists them).
 """
 import hashlib
 import argparse
@@ -257,6 +264,47 @@ def compare_frame(model, runner, tensors, out_ids, frame, f32, every_tensor):
             ok += int(e)
             worst = max(worst, w)
     return n, ok, worst
+
+
+DUMP_BUDGET = 64 * 10 ** 6  # bytes, all files of one --dump-outputs together
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(model, tensors, out_ids, detect, outdir):
+    """--dump-outputs DIR: what a caller of the timed path receives for its last step, as float32 .npy files --
+    output<i>.npy: graph output i (the head tensor bytes as int8, or float32 for a float graph) of the frames in frames.npy,
+    [frames, values]; every frame when the budget allows, else a sample of frames drawn with a fixed seed (if not even one
+    frame fits: a seeded sample of each output's values of frame 0, their indices in output<i>_index.npy);
+    detections.npy (tail on): the kept boxes of every frame, rows (frame, x, y, w, h, conf, cls) in the library's order.
+    Inputs and the sample depend only on the arguments, so two builds can be compared file for file."""
+    os.makedirs(outdir, exist_ok=True)
+    model.download()
+    batch = model.batch
+    files = {}
+    if detect:
+        dets = model.detect(outputs=tuple(range(len(out_ids))), thresh=0.45)
+        rows = [np.column_stack([np.full(len(d), f, np.float32)] + [d[k].astype(np.float32) for k in ("x", "y", "w", "h", "conf", "cls")])
+                for f, d in enumerate(dets) if len(d)]
+        files["detections"] = np.concatenate(rows) if rows else np.zeros((0, 7), np.float32)
+    heads = [model.output_view(i).view(np.float32 if tensors[ti]["dtype"] == 0 else np.int8) for i, ti in enumerate(out_ids)]
+    left = DUMP_BUDGET - sum(a.nbytes for a in files.values()) - 4096
+    per_frame = sum(h.shape[1] for h in heads) * 4
+    rng = np.random.default_rng(DUMP_SEED)
+    keep = min(batch, left // per_frame) if per_frame else batch
+    if keep >= 1:
+        frames = np.arange(batch) if keep == batch else np.sort(rng.choice(batch, keep, replace=False))
+        for i, h in enumerate(heads):
+            files["output%d" % i] = h[frames].astype(np.float32)
+    else:
+        frames = np.zeros(1, np.int64)
+        for i, h in enumerate(heads):
+            n = min(h.shape[1], max(1, left * h.shape[1] * 4 // per_frame // 12))  # value (float32) + index (float64): 12 bytes
+            idx = np.sort(rng.choice(h.shape[1], n, replace=False))
+            files["output%d" % i] = h[0, idx].astype(np.float32)[None]
+            files["output%d_index" % i] = idx.astype(np.float64)
+    files["frames"] = frames.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def short_leg(M, name, model_bytes, batch, steps, warmup, tail, f32_mode=None, cpu_frames=1, file_model=False, what=""):
@@ -517,7 +565,14 @@ def main():
                          "the default run measures this anyway.  camera (N=1): additionally the reference demo's whole loop "
                          "(src/mars/mars_yolo_test.c:132-214) -- uint8 RGB 1280x720 frames in pinned host memory -> letterbox / px-128 on "
                          "the device -> graph -> decode + NMS -> detections back, pipelined (mars_hip_pipe_* in camera mode): `camera_io`")
-    ap.add_argument("--sustain-s", type=float, default=3.0, help="seconds of back-to-back steps of the sustained leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed steps (sustained, I/O, batch-1, CPU baselines and parity, copy-rate "
+                         "probe, the other BASELINE configs); a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (graph outputs of a seeded sample of frames, "
+                         "every frame's detections) to DIR/<name>.npy as float32, 64 MB at most")
+    ap.add_argument("--sustain-s", type=float, default=None,
+                    help="seconds of back-to-back steps of the sustained leg (0 = skip; default 3 with --full, else 0)")
     ap.add_argument("--ops", type=str, default="", help="write a per-launch table (last timed step) to this file")
     ap.add_argument("--autotune", action="store_true",
                     help="time the launch variants of every convolution once before the warmup and pin the fastest "
@@ -531,6 +586,10 @@ def main():
                     help="start the --gpus N ranks as child processes of this one even at N=1 (what `--gpus N` with N>1 does "
                          "by itself when no launcher has set WORLD_SIZE): rehearses the N>1 entry point on one GPU")
     args = ap.parse_args()
+    if args.sustain_s is None:
+        args.sustain_s = 3.0 if args.full else 0.0
+    # the legs behind --full; --timed-only (profiling passes) skips them even there
+    extras = args.full and not args.timed_only
 
     # ---- N ranks: either a launcher started us (torch.distributed.run sets WORLD_SIZE; it must equal --gpus), or this
     # process -- which has not imported torch nor made a HIP call -- starts one fresh child per GPU and relays rank 0's line
@@ -679,6 +738,8 @@ def main():
     model.set_profiling(False)
     if dist is not None:
         dt = D.max_over_ranks(dist, dt, device="cuda")
+    if args.dump_outputs and rank == 0:  # before any further leg: the last timed step's results, as a caller would read them
+        dump_outputs(model, tensors, out_ids, not args.no_tail, args.dump_outputs)
 
     # ---- sustained leg (every rank): the timed region above is a burst of K steps after an idle device; a camera pipeline
     # runs for hours.  Back-to-back steps for >= --sustain-s seconds, the shader clock sampled while they run
@@ -720,7 +781,7 @@ def main():
     # every batch (mars_hip_pipe_*: upload k+1 / graph k / tail k / download k-1 on their own streams), detections (or the
     # raw head tensors too) go back.  The staging buffers are filled once (a camera would DMA into them).
     pipe_rates = {}
-    want_pipe = not f32 and not args.no_tail and not args.timed_only and (world == 1 or args.io == "pipelined")
+    want_pipe = not f32 and not args.no_tail and not args.timed_only and ((extras and world == 1) or args.io == "pipelined")
     if want_pipe:
         stacked = np.stack(frames)
         modes = (("detections", False), ("raw_outputs", True)) if world == 1 else (("detections", False),)
@@ -914,7 +975,7 @@ def main():
             result["camera_io"] = camera
         if multi:
             result["config"]["rccl"] = rccl_info
-        if world == 1 and not args.timed_only:
+        if world == 1 and extras:
             # not the headline value: the same batch INCLUDING host->HBM input copies and HBM->host
             # output copies through the reference API's mars_run() (pinned staging, one stream)
             M.lib().mars_hip_sync()
@@ -949,7 +1010,7 @@ def main():
                     model.run_device(sync=False)
                 M.lib().mars_hip_sync()
                 result["graph_only_images_per_s"] = 10 * args.batch / (time.perf_counter() - t1)
-        if world == 1 and not args.timed_only:
+        if world == 1 and extras:
             # the reference's real call pattern (mars_test.c:33-148): ONE frame per mars_run.  Latency of the graph alone
             # (input resident) and through mars_run() (H2D + graph + D2H), median of 20
             m1 = M.Model(model_bytes, batch=1)
@@ -974,7 +1035,7 @@ def main():
             lat["launches"] = len(m1.ops())
             result["latency_batch1"] = lat
             m1.close()
-        if world == 1 and not args.no_cpu_baseline and not args.timed_only:
+        if world == 1 and not args.no_cpu_baseline and extras:
             model.download()
             every = {"tensors_compared": 0, "tensors_equal": 0}
 
@@ -1033,7 +1094,7 @@ def main():
             result["cpu_baseline"] = base
             # the fair node-level figure -- frames are independent, one frame per thread on every core
             result["cpu_baseline_all_cores"] = cpu_baseline_parallel(model_bytes, frames, out_ids, args.cpu_threads, ref_outs, f32, bool(args.model))
-    if rank == 0 and world == 1 and not args.timed_only and not f32:
+    if rank == 0 and world == 1 and extras and not f32:
         # (last of all legs: after a 2 GiB allocate / copy / free the raw-heads mars_run leg ran at 9.4k instead of 15.9k img/s)
         # What a plain copy reaches on THIS box: `peak` stays the guide's 8 TB/s, but no kernel that reads and writes HBM
         # gets there -- a 1 GiB device-to-device copy (read + write bytes over its time) is the practical ceiling the
@@ -1054,7 +1115,7 @@ def main():
         clk = (sustained or {}).get("shader_clock_mhz", {}).get("median") if sustained else None
         result["roofline"]["pipes"] = pipe_times(args, result["roofline"]["algorithmic_bytes"], copy_gbs, clk)
     model.close()
-    if rank == 0 and world == 1 and not multi and not args.timed_only and not args.no_extra_configs and not args.model and not f32 and not args.vary_scales:
+    if rank == 0 and world == 1 and not multi and extras and not args.no_extra_configs and not args.model and not f32 and not args.vary_scales:
         # every BASELINE config under the same clock as the headline -- separate model instances, after the headline's
         # timed region and all its legs (the headline's numbers are final by now)
         t1 = time.perf_counter()

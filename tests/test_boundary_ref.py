@@ -1,5 +1,5 @@
-"""The drop-in boundary, pinned by the reference's OWN callers and headers (CPU, build container only: skipped where
-/root/reference is absent, e.g. on the GPU box).
+"""The drop-in boundary, pinned by the reference's OWN callers and headers (CPU).  The tests that compile the reference's
+sources skip where its tree is absent; the layout test then holds our headers to the digest of the probe's output it recorded.
 
 * The reference's programs that drive this path -- src/mars/mars_test.c, src/mars/mars_yolo_test.c, examples/test_init.c,
   examples/test_inference.c -- are compiled UNCHANGED, from where they lie, against this repo's include/ and linked with
@@ -8,6 +8,7 @@
 * A layout probe generated from THIS repo's headers (every struct's size, every field's offset and size, every
   enumerator's value) is compiled once per header set; the two outputs must be identical.
 """
+import hashlib
 import os
 import re
 import subprocess
@@ -19,11 +20,15 @@ INC = os.path.join(ROOT, "include")
 REF = "/root/reference"
 LIB = os.path.join(ROOT, "thingino-accel_amd", "lib")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "mars")), reason="reference tree absent")
+HAVE_REF = os.path.isdir(os.path.join(REF, "src", "mars"))
+needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference tree absent")
+# sha256 (first 24 hex digits) of what the layout probe prints when compiled against the reference's headers
+LAYOUT_SHA = "37a5075488c994502ab7a429"
 
 CALLERS = ["src/mars/mars_test.c", "src/mars/mars_yolo_test.c", "examples/test_init.c", "examples/test_inference.c"]
 
 
+@needs_ref
 @pytest.mark.parametrize("rel", CALLERS)
 def test_reference_caller_builds_and_links_unchanged(rel, tmp_path):
     exe = tmp_path / os.path.basename(rel)[:-2]
@@ -112,18 +117,24 @@ def _probe_source():
 
 
 def test_struct_layouts_and_enums_equal_the_reference_headers(tmp_path):
+    """the probe built with our headers prints what it prints built with the reference's: compiled live where the reference
+    tree is present (whose output must then still have the recorded digest), else by that digest"""
     src = tmp_path / "probe.c"
     src.write_text(_probe_source())
     outs = []
-    for inc in (INC, os.path.join(REF, "include")):
+    for inc in (INC, os.path.join(REF, "include")) if HAVE_REF else (INC,):
         exe = tmp_path / ("probe_" + ("ours" if inc == INC else "ref"))
         r = subprocess.run(["gcc", "-std=gnu11", "-w", "-I", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
         assert r.returncode == 0, "%s: %s" % (inc, r.stderr[-3000:])
         outs.append(subprocess.check_output([str(exe)], text=True))
-    assert outs[0] == outs[1]
+    if HAVE_REF:
+        assert hashlib.sha256(outs[1].encode()).hexdigest()[:24] == LAYOUT_SHA, "LAYOUT_SHA is not what the reference's headers give"
+        assert outs[0] == outs[1]
+    assert hashlib.sha256(outs[0].encode()).hexdigest()[:24] == LAYOUT_SHA
     assert "mars_header_t 76\n" in outs[0] and "mars_tensor_t 124\n" in outs[0] and "mars_layer_t 112\n" in outs[0]
 
 
+@needs_ref
 def test_function_prototypes_equal_the_reference_headers(tmp_path):
     """every function the reference's public headers for this path declare is declared here with the same type: a TU that
     includes OUR header and then re-declares each function with the REFERENCE's prototype text must compile (C rejects

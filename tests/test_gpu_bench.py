@@ -5,15 +5,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*extra, env=None):
+def run_bench(*extra, env=None, full=True):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--batch", "4", "--hw", "160", "--width", "4"] + list(extra), capture_output=True, text=True, timeout=600,
+                          "--batch", "4", "--hw", "160", "--width", "4"] + (["--full"] if full else []) + list(extra),
+                         capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, **(env or {})))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -131,7 +133,7 @@ def test_bench_starts_its_own_ranks():
     child runs the whole multi-process path and the line's rank count is the RCCL group's."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--steps", "3", "--warmup", "1",
-                          "--batch", "4", "--hw", "160", "--width", "4", "--no-cpu-baseline", "--sustain-s", "0"],
+                          "--batch", "4", "--hw", "160", "--width", "4", "--full", "--no-cpu-baseline", "--sustain-s", "0"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.count("\n") == 1 and out.stdout.startswith("{")
@@ -152,3 +154,23 @@ def test_bench_camera_leg():
     assert c["images_per_s"] > 0 and "1280x720" in c["frame"] and c["host_to_device_bytes_per_batch"] == 4 * 1280 * 720 * 3
     k = c["preproc_kernel"]
     assert k["ms_per_batch"] > 0 and k["achieved_gbs"] > 0 and 0 < k["frac_of_hbm_peak"] < 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """without --full the line carries the headline and its roofline but no further leg; --dump-outputs writes the last timed
+    step's head tensors and detections, identical from run to run"""
+    dumps = []
+    for k in range(2):
+        d = run_bench("--dump-outputs", str(tmp_path / str(k)), full=False)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "int8"
+        assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"] and d["roofline"]["bound"] in ("hbm", "mfma")
+        for k2 in ("cpu_baseline", "cpu_baseline_all_cores", "sustained", "pipelined_io", "latency_batch1", "configs", "graph_only_images_per_s"):
+            assert k2 not in d, k2
+        dumps.append({f.stem: np.load(f) for f in (tmp_path / str(k)).iterdir()})
+    a, b = dumps
+    assert set(a) == set(b) and {"output0", "output1", "output2", "detections", "frames"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    assert a["frames"].tolist() == [0, 1, 2, 3] and a["output0"].shape[0] == 4 and a["detections"].shape[1] == 7
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name

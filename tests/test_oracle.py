@@ -1,6 +1,11 @@
 """The CPU restatement (oracle/restate) against (a) the reference compiled in place
 (oracle/_ref; only where it was built) and (b) the committed golden vectors the
-reference produced (everywhere).  No GPU involved."""
+reference produced (everywhere).  No GPU involved.
+
+The *_vs_reference tests run the reference live where oracle/_ref was built; elsewhere they
+hold the restatement against what the reference gave for the same inputs, recorded in
+golden.json "vs_reference" (record_vs_reference(), called by tests/golden/make_golden.py)."""
+import hashlib
 import json
 import os
 
@@ -86,31 +91,70 @@ def test_trunc_x86(orc):
     assert orc.trunc_x86(2147483520.0) == 2147483520 and orc.trunc_x86(-2147483648.0) == -2147483648
 
 
-# ---------------------------------------------------------------- live reference (build container only)
-@pytest.mark.parametrize("name,kw", cases.SYNTH, ids=lambda v: v if isinstance(v, str) else "")
-def test_restatement_vs_reference_synthetic(orc, ref, marsrt, name, kw):
-    d = marsrt.synth_model(**kw)
+# ---------------------------------------------------------------- the live reference, or what it recorded
+def sig(a):
+    """dtype, shape and bytes of an array, as one comparable string"""
+    a = np.asarray(a)
+    return "%s%s:%s" % (a.dtype.str, list(a.shape), cases.digest(a))
+
+
+def graph_of(impl):
+    return impl.Graph if hasattr(impl, "Graph") else impl.O2Model  # orcbind / refbind
+
+
+def fold(obs):
+    """one digest of a whole observation (the form golden.json "vs_reference" keeps)"""
+    return hashlib.sha256(json.dumps(obs, sort_keys=True).encode()).hexdigest()[:24]
+
+
+@pytest.fixture(scope="module")
+def witness():
+    """witness(key, got, observe): got (the restatement's observation) equals observe(refbind) -- run live where oracle/_ref
+    was built (which must then also match the record, so the record stays the reference's), else as golden.json
+    "vs_reference" recorded it"""
+    import refbind
+    live = refbind if refbind.available() else None
+    rec = GOLD["vs_reference"]
+
+    def check(key, got, observe):
+        if live is None:
+            assert fold(got) == rec[key], "%s differs from what the reference gave" % key
+            return
+        want = observe(live)
+        assert key not in rec or fold(want) == rec[key], "golden.json vs_reference[%r] is not what the reference gives" % key
+        assert got == want
+    return check
+
+
+def obs_synthetic(impl, d):
     hdr, tensors, _ = marsfile.parse(d)
-    tin = tensors[hdr["inputs"][0]]
-    x = model_input(tin, "lcg")
-    g, m = orc.Graph(d, slack_mult=2), ref.O2Model(d, slack_mult=2)
+    x = model_input(tensors[hdr["inputs"][0]], "lcg")
+    g = graph_of(impl)(d, slack_mult=2)
     g.set_input(0, x.tobytes())
-    m.set_input(0, x.tobytes())
-    assert g.run() == 0 and m.run() == 0
+    out = {"rc": g.run()}
     for ti in range(len(tensors)):
         if tensors[ti]["size"] == 0:
-            assert np.array_equal(g.tensor(ti), m.tensor(ti)), "tensor %d" % ti
+            out["t%d" % ti] = sig(g.tensor(ti))
+    out["distinct_out"] = len(np.unique(g.tensor(hdr["outputs"][0])))
+    g.close()
+    return out
+
+
+@pytest.mark.parametrize("name,kw", cases.SYNTH, ids=lambda v: v if isinstance(v, str) else "")
+def test_restatement_vs_reference_synthetic(orc, witness, marsrt, name, kw):
+    d = marsrt.synth_model(**kw)
+    got = obs_synthetic(orc, d)
+    assert got["rc"] == 0
+    witness("synthetic/" + name, got, lambda R: obs_synthetic(R, d))
     # the synthetic graphs are hazard- and overrun-free: outputs are not degenerate
-    out = g.tensor(hdr["outputs"][0])
-    assert len(np.unique(out)) > 16
+    assert got["distinct_out"] > 16
 
 
 @pytest.mark.parametrize("seed", [2, 3])
 @pytest.mark.parametrize("case", cases.CONV_I8_CASES, ids=lambda c: c[0])
-def test_conv_i8_vs_reference(orc, ref, case, seed):
-    a = cases.conv_i8_call(orc.conv2d_int8, case, seed)
-    b = cases.conv_i8_call(ref.conv2d_int8, case, seed)
-    assert np.array_equal(a, b)
+def test_conv_i8_vs_reference(orc, witness, case, seed):
+    a = sig(cases.conv_i8_call(orc.conv2d_int8, case, seed))
+    witness("conv_i8/%s/%d" % (case[0], seed), a, lambda R: sig(cases.conv_i8_call(R.conv2d_int8, case, seed)))
 
 
 @pytest.mark.parametrize("fam", ["split", "patch", "stem"])
@@ -124,21 +168,21 @@ def test_conv_f32_family_golden(orc, fam):
         assert got == GOLD["conv_f32_family"][f32shapes.shape_id(fam, shape)], shape
 
 
-@pytest.mark.parametrize("fam", sorted(cases.CONV_I8_FAMILIES))
-def test_conv_i8_family_vs_reference(orc, ref, fam):
-    """... and element-wise against the live reference, at a second seed the goldens do not hold"""
+def obs_conv_i8_family(impl, fam):
     seed, cs = cases.family_cases(fam)
-    for c in cs:
-        a = cases.conv_i8_call(orc.conv2d_int8, c, seed + 100)
-        b = cases.conv_i8_call(ref.conv2d_int8, c, seed + 100)
-        assert np.array_equal(a, b), c[0]
+    return {c[0]: sig(cases.conv_i8_call(impl.conv2d_int8, c, seed + 100)) for c in cs}
+
+
+@pytest.mark.parametrize("fam", sorted(cases.CONV_I8_FAMILIES))
+def test_conv_i8_family_vs_reference(orc, witness, fam):
+    """... and element-wise against the reference, at a second seed the goldens do not hold"""
+    witness("conv_i8_family/" + fam, obs_conv_i8_family(orc, fam), lambda R: obs_conv_i8_family(R, fam))
 
 
 @pytest.mark.parametrize("case", cases.CONV_F32_CASES, ids=lambda c: c[0])
-def test_conv_f32_vs_reference(orc, ref, case):
-    a = cases.conv_f32_call(orc.conv2d_f32, case, 5)
-    b = cases.conv_f32_call(ref.conv2d_f32, case, 5)
-    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))  # bit-identical, not just close
+def test_conv_f32_vs_reference(orc, witness, case):
+    a = sig(cases.conv_f32_call(orc.conv2d_f32, case, 5))  # the bytes: bit-identical, not just close
+    witness("conv_f32/" + case[0], a, lambda R: sig(cases.conv_f32_call(R.conv2d_f32, case, 5)))
 
 
 def _layer_graph(kind):
@@ -244,29 +288,34 @@ LAYER_KINDS = ["sigmoid", "relu", "relu6", "leaky", "mul", "add", "mul_const", "
                "missing_tensor", "conv_relu_valid"]
 
 
-@pytest.mark.parametrize("kind", LAYER_KINDS)
-def test_layers_vs_reference(orc, ref, kind):
+def obs_layers(impl, kind):
     d = _layer_graph(kind)
     hdr, tensors, _ = marsfile.parse(d)
-    tin = tensors[hdr["inputs"][0]]
-    x = model_input(tin, "lcg")
-    g, m = orc.Graph(d), ref.O2Model(d)
+    x = model_input(tensors[hdr["inputs"][0]], "lcg")
+    g = graph_of(impl)(d)
     g.set_input(0, x.tobytes())
-    m.set_input(0, x.tobytes())
-    assert g.run() == m.run()
+    out = {"rc": g.run()}
     for ti in range(len(tensors)):
         if tensors[ti]["size"] == 0:
-            ext = marsfile.tensor_nbytes(tensors[ti]) + 64
-            assert np.array_equal(g.tensor(ti, extent=ext), m.tensor(ti, extent=ext)), "tensor %d" % ti
+            out["t%d" % ti] = sig(g.tensor(ti, extent=marsfile.tensor_nbytes(tensors[ti]) + 64))
+    g.close()
+    return out
+
+
+@pytest.mark.parametrize("kind", LAYER_KINDS)
+def test_layers_vs_reference(orc, witness, kind):
+    witness("layers/" + kind, obs_layers(orc, kind), lambda R: obs_layers(R, kind))
+
+
+def obs_yolo(impl, case):
+    pred, npred, scale = cases.yolo_pred(case)
+    raw = impl.parse_output(pred, npred, scale)
+    return {"raw": sig(raw), "nms_0.45": sig(impl.nms(raw, 0.45)), "nms_0.1": sig(impl.nms(raw, 0.1))}
 
 
 @pytest.mark.parametrize("case", cases.YOLO_CASES, ids=lambda c: c[0])
-def test_yolo_vs_reference(orc, ref, case):
-    pred, npred, scale = cases.yolo_pred(case)
-    a, b = orc.parse_output(pred, npred, scale), ref.parse_output(pred, npred, scale)
-    assert a.tobytes() == b.tobytes()
-    assert orc.nms(a, 0.45).tobytes() == ref.nms(b, 0.45).tobytes()
-    assert orc.nms(a, 0.1).tobytes() == ref.nms(b, 0.1).tobytes()
+def test_yolo_vs_reference(orc, witness, case):
+    witness("yolo/" + case[0], obs_yolo(orc, case), lambda R: obs_yolo(R, case))
 
 
 def test_run_frames_threads(orc, marsrt):
@@ -293,9 +342,11 @@ def test_letterbox_vs_golden(orc, case):
     assert (out == -17).any() or case[1] * case[4] == case[2] * case[3]  # padding present unless aspect ratios match
 
 
-def test_letterbox_vs_reference_sweep(orc, ref):
+def obs_letterbox_sweep(impl):
     """many geometries (growing, shrinking, identical, extreme aspect ratios, odd sizes), both layouts"""
+    fn = impl.letterbox if hasattr(impl, "letterbox") else impl.load_image
     rng = np.random.default_rng(5)
+    out = []
     for i in range(40):
         w, h = int(rng.integers(5, 300)), int(rng.integers(5, 300))
         tw, th = int(rng.integers(8, 200)), int(rng.integers(8, 200))
@@ -303,6 +354,31 @@ def test_letterbox_vs_reference_sweep(orc, ref):
         if min(int(w * min(tw / w, th / h)), int(h * min(tw / w, th / h))) < 1:
             continue
         nhwc = i & 1
-        a = ref.load_image(img, tw, th, nhwc)
-        b = orc.letterbox(img, tw, th, nhwc)
-        assert np.array_equal(a, b), (w, h, tw, th, nhwc, int((a != b).sum()))
+        out.append(["%dx%d->%dx%d nhwc=%d" % (w, h, tw, th, nhwc), sig(fn(img, tw, th, nhwc))])
+    return out
+
+
+def test_letterbox_vs_reference_sweep(orc, witness):
+    got = obs_letterbox_sweep(orc)
+    assert len(got) > 30
+    witness("letterbox_sweep", got, obs_letterbox_sweep)
+
+
+def record_vs_reference(R, marsrt):
+    """golden.json "vs_reference": what the reference (R = refbind) gives for every *_vs_reference comparison above"""
+    rec = {}
+    for name, kw in cases.SYNTH:
+        rec["synthetic/" + name] = obs_synthetic(R, marsrt.synth_model(**kw))
+    for case in cases.CONV_I8_CASES:
+        for seed in (2, 3):
+            rec["conv_i8/%s/%d" % (case[0], seed)] = sig(cases.conv_i8_call(R.conv2d_int8, case, seed))
+    for fam in sorted(cases.CONV_I8_FAMILIES):
+        rec["conv_i8_family/" + fam] = obs_conv_i8_family(R, fam)
+    for case in cases.CONV_F32_CASES:
+        rec["conv_f32/" + case[0]] = sig(cases.conv_f32_call(R.conv2d_f32, case, 5))
+    for kind in LAYER_KINDS:
+        rec["layers/" + kind] = obs_layers(R, kind)
+    for case in cases.YOLO_CASES:
+        rec["yolo/" + case[0]] = obs_yolo(R, case)
+    rec["letterbox_sweep"] = obs_letterbox_sweep(R)
+    return {k: fold(v) for k, v in rec.items()}
