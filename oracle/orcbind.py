@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "liboracle.so")
 _lib = None
 
+E_BOUNDS = -100  # ORC_E_BOUNDS (orc.h): a layer would have reached outside a tensor's allocation; it was not run
+
 DET_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"),
                       ("conf", "<f4"), ("cls", "<i4")])
 

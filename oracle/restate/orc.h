@@ -79,6 +79,10 @@ int orc_parse_output(const int8_t *pred, int npred, float scale, orc_det_t *dets
 int orc_nms(orc_det_t *d, int n, float thresh);
 
 /* ---- whole graph, O2 memory semantics */
+/* orc_graph_run's code for a layer that would read or write outside a tensor's allocation (its shapes reach past
+ * the slack the graph was opened with): the layer is not run, nothing outside an allocation is touched.  Not a
+ * mars_error_t: the reference has no such check and would read whatever lies there. */
+#define ORC_E_BOUNDS (-100)
 typedef struct orc_graph orc_graph_t;
 /* returns NULL on malformed file; *err gets a mars_error_t-compatible code */
 orc_graph_t *orc_graph_open(const void *file, size_t size, size_t slack_mult, size_t slack_add, int *err);

@@ -9,6 +9,11 @@
  *             :1092-1158 batchnorm
  * Memory:     oracle O2 -- one zero-initialised buffer per activation tensor
  *             (no round-robin arena), weight blob followed by zeros.
+ * Bounds:     before a layer runs, the byte range each of its kernel calls
+ *             touches in every tensor is checked against that tensor's
+ *             allocation (the slack it was opened with); a layer that would
+ *             reach outside one returns ORC_E_BOUNDS unrun.  The reference has
+ *             no such check: there such a layer reads whatever lies behind.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -164,6 +169,37 @@ static otensor_t *by_id(orc_graph_t *g, uint32_t id) {
 
 static size_t numel_of(const otensor_t *t) { return shape_numel(&t->d); }
 
+/* ---- bounds guard.  A span is the byte range [lo, hi) that one kernel call touches in one tensor: an access of `width` bytes at
+ * base + k1 s1 + k2 s2 + k3 s3, k_i in [0, n_i).  Kept in double: exact for every extent an allocation can have, and a product of
+ * int32 dimensions cannot wrap. */
+typedef struct { double lo, hi; } span_t; /* hi <= lo: nothing touched */
+
+static span_t span3(double base, double width, double n1, double s1, double n2, double s2, double n3, double s3) {
+    span_t r = {base, base + width};
+    if (n1 <= 0 || n2 <= 0 || n3 <= 0 || width <= 0) { r.hi = r.lo; return r; }
+    const double n[3] = {n1, n2, n3}, st[3] = {s1, s2, s3};
+    for (int i = 0; i < 3; i++) {
+        const double d = (n[i] - 1) * st[i];
+        if (d > 0) r.hi += d; else r.lo += d;
+    }
+    return r;
+}
+
+static span_t flat(double bytes) { return span3(0, bytes, 1, 0, 1, 0, 1, 0); }
+
+static int fits(const otensor_t *t, span_t s) { return s.hi <= s.lo || (t && t->ptr && s.lo >= 0 && s.hi <= (double)t->alloc); }
+
+/* the rows (or columns) a max-pool window reads: v = o * stride + k for o in [0, n_out), k in [0, k_n), cut at v >= n_in (:919-957 break) */
+static void pool_range(int n_out, int stride, int k_n, int n_in, double *lo, double *cnt) {
+    const double a = (double)(n_out - 1) * stride;
+    const double v_lo = a < 0 ? a : 0, v_hi = (a > 0 ? a : 0) + k_n - 1;
+    *lo = v_lo;
+    *cnt = (v_hi < n_in - 1 ? v_hi : n_in - 1) - v_lo + 1;
+}
+
+/* the source row of an output row of UPSAMPLE: min(o / scale, n_in - 1), monotone in o for a fixed sign of scale */
+static int up_src(int o, int scale, int n_in) { const int v = o / scale; return v >= n_in ? n_in - 1 : v; }
+
 static int run_conv(orc_graph_t *g, const mars_layer_t *L) {
     const mars_conv_params_t *cp = &L->params.conv;
     otensor_t *in = by_id(g, L->input_tensor_ids[0]);
@@ -189,6 +225,13 @@ static int run_conv(orc_graph_t *g, const mars_layer_t *L) {
         q.pad_left = pw / 2;
     }
     if (q.in_h < 0 || q.in_w < 0 || q.in_c < 0 || q.out_h < 0 || q.out_w < 0 || q.out_c < 0) return E_TENSOR;
+    { /* taps outside the image are skipped, so the input is read within in_h x in_w x in_c elements */
+        const double e = in->d.dtype == MARS_DTYPE_FLOAT32 ? 4 : 1, outs = (double)q.out_h * q.out_w;
+        if (!fits(in, flat(outs > 0 ? (double)q.in_h * q.in_w * q.in_c * e : 0)) ||
+            !fits(w, flat(outs > 0 ? (double)q.out_c * q.kh * q.kw * q.in_c * e : 0)) ||
+            (b && b->ptr && !fits(b, flat(outs > 0 ? (double)q.out_c * 4 : 0))) || !fits(out, flat(outs * q.out_c * e)))
+            return ORC_E_BOUNDS;
+    }
 
     if (in->d.dtype == MARS_DTYPE_FLOAT32) {
         orc_conv_f32_nchw((const float *)in->ptr, (const float *)w->ptr,
@@ -215,6 +258,8 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
             otensor_t *a = by_id(g, L->input_tensor_ids[0]), *o = by_id(g, L->output_tensor_ids[0]);
             if (!a || !o || !a->ptr || !o->ptr) return E_TENSOR;
             size_t n = numel_of(a);
+            const span_t sp = flat((double)n * (a->d.dtype == MARS_DTYPE_FLOAT32 ? 4 : 1));
+            if (!fits(a, sp) || !fits(o, sp)) return ORC_E_BOUNDS;
             if (a->d.dtype == MARS_DTYPE_FLOAT32) orc_sigmoid_f32((const float *)a->ptr, (float *)o->ptr, n);
             else orc_sigmoid_i8((const int8_t *)a->ptr, (int8_t *)o->ptr, n, a->d.scale, o->d.scale);
             return E_OK;
@@ -225,6 +270,8 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
             otensor_t *o = by_id(g, L->output_tensor_ids[0]);
             if (!a || !b || !o || !a->ptr || !b->ptr || !o->ptr) return E_TENSOR;
             size_t n = numel_of(a); /* extent comes from the FIRST operand only */
+            const span_t sp = flat((double)n * (a->d.dtype == MARS_DTYPE_FLOAT32 ? 4 : 1));
+            if (!fits(a, sp) || !fits(b, sp) || !fits(o, sp)) return ORC_E_BOUNDS;
             int mul = L->type == MARS_LAYER_MUL;
             if (a->d.dtype == MARS_DTYPE_FLOAT32)
                 orc_binary_f32(mul, (const float *)a->ptr, (const float *)b->ptr, (float *)o->ptr, n);
@@ -239,6 +286,8 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
             otensor_t *a = by_id(g, L->input_tensor_ids[0]), *o = by_id(g, L->output_tensor_ids[0]);
             if (!a || !o || !a->ptr || !o->ptr) return E_TENSOR;
             size_t n = numel_of(a);
+            const span_t sp = flat((double)n * (a->d.dtype == MARS_DTYPE_FLOAT32 ? 4 : 1));
+            if (!fits(a, sp) || !fits(o, sp)) return ORC_E_BOUNDS;
             int leaky = L->type == MARS_LAYER_LEAKY_RELU;
             if (a->d.dtype == MARS_DTYPE_FLOAT32) orc_relu_f32((const float *)a->ptr, (float *)o->ptr, n, leaky);
             else orc_relu_i8((const int8_t *)a->ptr, (int8_t *)o->ptr, n, leaky);
@@ -249,6 +298,17 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
             otensor_t *a = by_id(g, L->input_tensor_ids[0]), *o = by_id(g, L->output_tensor_ids[0]);
             if (!a || !o || !a->ptr || !o->ptr) return E_TENSOR;
             /* shape[1..3] read as H,W,C whatever the layout tag; int8 bytes whatever the dtype */
+            {
+                const int in_h = a->d.shape[1], in_w = a->d.shape[2], ch = a->d.shape[3], out_h = o->d.shape[1], out_w = o->d.shape[2];
+                const int kh = (int)pp->kernel_h, kw = (int)pp->kernel_w;
+                double y0, ny, x0, nx;
+                pool_range(out_h, (int)pp->stride_h, kh, in_h, &y0, &ny);
+                pool_range(out_w, (int)pp->stride_w, kw, in_w, &x0, &nx);
+                const int any = out_h > 0 && out_w > 0 && kh > 0 && kw > 0;
+                if ((any && !fits(a, span3((y0 * in_w + x0) * ch, 1, ny, (double)in_w * ch, nx, ch, ch, 1))) ||
+                    !fits(o, span3(0, 1, out_h, (double)out_w * ch, out_w, ch, ch, 1)))
+                    return ORC_E_BOUNDS;
+            }
             orc_maxpool_i8((const int8_t *)a->ptr, (int8_t *)o->ptr, a->d.shape[1], a->d.shape[2],
                            a->d.shape[3], o->d.shape[1], o->d.shape[2], (int)pp->kernel_h,
                            (int)pp->kernel_w, (int)pp->stride_h, (int)pp->stride_w);
@@ -257,7 +317,18 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
         case MARS_LAYER_CONCAT: {
             otensor_t *o = by_id(g, L->output_tensor_ids[0]);
             if (!o || !o->ptr) return E_TENSOR;
+            const int oh = o->d.shape[1], ow = o->d.shape[2], oc = o->d.shape[3];
             int off = 0;
+            for (uint32_t k = 0; k < L->num_inputs && k < 4; k++) { /* (every slice checked before the first one is copied) */
+                otensor_t *a = by_id(g, L->input_tensor_ids[k]);
+                if (!a || !a->ptr) continue;
+                const int in_c = a->d.shape[3];
+                if (!fits(a, span3(0, 1, oh, (double)ow * in_c, ow, in_c, in_c, 1)) ||
+                    !fits(o, span3(off, 1, oh, (double)ow * oc, ow, oc, in_c, 1)))
+                    return ORC_E_BOUNDS;
+                off += in_c;
+            }
+            off = 0;
             for (uint32_t k = 0; k < L->num_inputs && k < 4; k++) {
                 otensor_t *a = by_id(g, L->input_tensor_ids[k]);
                 if (!a || !a->ptr) continue; /* silently skipped (:980) */
@@ -278,6 +349,14 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
             int sh = up->scale_h > 0 ? (int)up->scale_h : out_h / in_h;
             int sw = up->scale_w > 0 ? (int)up->scale_w : out_w / in_w;
             if (sh == 0 || sw == 0) return E_TENSOR; /* the reference would divide by zero */
+            if (out_h > 0 && out_w > 0) {
+                if (ch < 0) return ORC_E_BOUNDS; /* (a negative run length: memcpy of nearly 2^64 bytes) */
+                const int ya = up_src(0, sh, in_h), yb = up_src(out_h - 1, sh, in_h), xa = up_src(0, sw, in_w), xb = up_src(out_w - 1, sw, in_w);
+                const int y0 = ya < yb ? ya : yb, y1 = ya < yb ? yb : ya, x0 = xa < xb ? xa : xb, x1 = xa < xb ? xb : xa;
+                if (!fits(a, span3(((double)y0 * in_w + x0) * ch, ch, y1 - y0 + 1, (double)in_w * ch, x1 - x0 + 1, ch, 1, 0)) ||
+                    !fits(o, span3(0, ch, out_h, (double)out_w * ch, out_w, ch, 1, 0)))
+                    return ORC_E_BOUNDS;
+            }
             orc_upsample_i8((const int8_t *)a->ptr, (int8_t *)o->ptr, in_h, in_w, ch, out_h, out_w, sh, sw);
             return E_OK;
         }
@@ -287,6 +366,11 @@ static int run_layer(orc_graph_t *g, const mars_layer_t *L) {
             if (!a || !o || !a->ptr || !o->ptr) return E_TENSOR;
             int n = a->d.shape[0] > 0 ? a->d.shape[0] : 1, c = a->d.shape[1] > 0 ? a->d.shape[1] : 1;
             int h = a->d.shape[2] > 0 ? a->d.shape[2] : 1, w = a->d.shape[3] > 0 ? a->d.shape[3] : 1;
+            {
+                const span_t v = flat((double)n * c * h * w * (a->d.dtype == MARS_DTYPE_FLOAT32 ? 4 : 1));
+                if (!fits(a, v) || !fits(o, v) || (s && s->ptr && !fits(s, flat(4.0 * c))) || (b && b->ptr && !fits(b, flat(4.0 * c))))
+                    return ORC_E_BOUNDS;
+            }
             const float *sp = s && s->ptr ? (const float *)s->ptr : NULL;
             const float *bp = b && b->ptr ? (const float *)b->ptr : NULL;
             if (a->d.dtype == MARS_DTYPE_FLOAT32)

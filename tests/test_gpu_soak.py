@@ -19,6 +19,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
     ("fuzz_graphs.py", ["20268", "40"], {"FUZZ_NCHW": "1"}),  # every graph NCHW-tagged: nhwc_internal, the byte-wise layers on the internal layout, virtual_concat_q
     ("fuzz_graphs_f32.py", ["20264", "25"], {}),
     ("fuzz_vcat_f32.py", ["20269", "25"], {}),  # float concats read through a view of their last input (virtual_concat_f32), modes 3 / 4
+    ("fuzz_graphs.py", ["20271", "30"], {"FUZZ_NCHW": "1", "FUZZ_CHAIN": "1", "FUZZ_INTERIOR": "1"}),  # concat_q chains; graph outputs other layers read
+    ("fuzz_pipe.py", ["20270", "30"], {}),  # the pipelined path (per-slot I/O buffers) on graphs whose outputs sit inside the graph
     ("fuzz_tail.py", ["20265", "60"], {}),
     ("fuzz_api_states.py", ["20266", "60"], {}),
 ], ids=lambda v: v if isinstance(v, str) else ("-".join(v) if isinstance(v, list) else "+".join(sorted(v)) or "default"))

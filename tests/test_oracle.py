@@ -364,6 +364,84 @@ def test_letterbox_vs_reference_sweep(orc, witness):
     witness("letterbox_sweep", got, obs_letterbox_sweep)
 
 
+# ---------------------------------------------------------------- random graphs (tests/graphgen.py): the soak scripts' checker, pinned
+GENERATED = [  # (key, generator, options, seed): 8 graphs each, both new options included
+    ("int8", "int8_graph", {}, 5101),
+    ("int8_nchw", "int8_graph", dict(nchw=True), 5102),
+    ("int8_nchw_chain_interior", "int8_graph", dict(nchw=True, concat_chain=True, interior_outputs=True), 5103),
+    ("int8_interior", "int8_graph", dict(nchw=False, interior_outputs=True), 5104),
+    ("f32", "f32_graph", {}, 5105),
+    ("f32_interior", "f32_graph", dict(interior_outputs=True), 5106),
+    ("vcat_f32", "vcat_f32_graph", {}, 5107),
+    ("vcat_f32_interior", "vcat_f32_graph", dict(interior_outputs=True), 5108),
+]
+PAST_END = 4096  # bytes compared behind every activation tensor: what the byte-wise layers spill there is read by later layers
+
+
+def generated_graphs(gen, opts, seed, n=8):
+    import graphgen
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < n:
+        r = getattr(graphgen, gen)(rng, **opts)
+        if r is not None:
+            out.append(r[0])
+    return out
+
+
+def obs_generated(impl, graphs):
+    """every activation tensor of every graph (and PAST_END bytes behind it) after one run at the default slack"""
+    obs = []
+    for d in graphs:
+        hdr, tensors, _ = marsfile.parse(d)
+        g = graph_of(impl)(d)
+        g.set_input(0, model_input(tensors[hdr["inputs"][0]], "lcg").tobytes())
+        o = {"rc": g.run()}
+        for ti in range(len(tensors)):
+            if tensors[ti]["size"] == 0:
+                o["t%d" % ti] = sig(g.tensor(ti, extent=marsfile.tensor_nbytes(tensors[ti]) + PAST_END))
+        g.close()
+        obs.append(o)
+    return obs
+
+
+@pytest.mark.parametrize("key,gen,opts,seed", GENERATED, ids=[g[0] for g in GENERATED])
+def test_generated_graphs_vs_reference(orc, witness, key, gen, opts, seed):
+    """the random graphs the GPU soak compares against the restatement (NCHW byte-wise concat / pool / upsample, SPPF / C3 motifs, float
+    concats read through views, graph outputs inside the graph): the restatement equals the reference on every tensor, and past its end"""
+    graphs = generated_graphs(gen, opts, seed)
+    got = obs_generated(orc, graphs)
+    assert all(o["rc"] == 0 for o in got)
+    witness("generated/" + key, got, lambda R: obs_generated(R, graphs))
+
+
+def spilling_graph():
+    """fuzz_graphs.py's generator, seed 1, NCHW-tagged, graph 73: upsampling -> SPPF -> upsampling -> C3 -- byte-wise concats of
+    [1, N C, H, W] that read N - 1 inputs' worth past the end of their last input"""
+    import graphgen
+    rng = np.random.default_rng(1)
+    for it in range(74):
+        r = graphgen.int8_graph(rng, nchw=True)
+        if r is not None:
+            d, desc = r
+            rng.integers(1, 4)  # (the soak script's batch draw)
+    assert [q[0] for q in desc] == ["nchw", "c3", "concat", "conv", "up", "sppf", "up", "conv", "c3"]
+    return d
+
+
+def test_restatement_stops_at_its_allocations(orc):
+    """with less slack behind every tensor (slack_mult 2) the concats of spilling_graph() reach past their inputs' allocations: the run stops
+    with ORC_E_BOUNDS before that layer instead of reading the heap (the same graph at the default slack runs clean)"""
+    d = spilling_graph()
+    hdr, tensors, _ = marsfile.parse(d)
+    x = model_input(tensors[hdr["inputs"][0]], "lcg").tobytes()
+    for slack, want in ((2, orc.E_BOUNDS), (8, 0)):
+        g = orc.Graph(d, slack_mult=slack)
+        g.set_input(0, x)
+        assert g.run() == want, slack
+        g.close()
+
+
 def record_vs_reference(R, marsrt):
     """golden.json "vs_reference": what the reference (R = refbind) gives for every *_vs_reference comparison above"""
     rec = {}
@@ -381,4 +459,6 @@ def record_vs_reference(R, marsrt):
     for case in cases.YOLO_CASES:
         rec["yolo/" + case[0]] = obs_yolo(R, case)
     rec["letterbox_sweep"] = obs_letterbox_sweep(R)
+    for key, gen, opts, seed in GENERATED:
+        rec["generated/" + key] = obs_generated(R, generated_graphs(gen, opts, seed))
     return {k: fold(v) for k, v in rec.items()}

@@ -1,6 +1,7 @@
 """CPU AddressSanitizer / UBSan build of the host side (loader, planner, tensor and memory shims) driven by
 tests/c/fuzz_loader.c over the shipped and synthetic models plus the two crafted files ADVICE (round 1) reported:
-an in_c that wrapped kw*in_c inside the weight packer, and an out_c that made the arena doubling loop spin."""
+an in_c that wrapped kw*in_c inside the weight packer, and an out_c that made the arena doubling loop spin.
+Also the checker itself (oracle/restate, driven by tests/c/orc_bounds.c) over random graphs at too little slack."""
 import os
 import struct
 import subprocess
@@ -105,3 +106,44 @@ def test_compile_step_under_sanitizers(tmp_path):
     err = r.stderr.decode(errors="replace")
     assert r.returncode == 0, r.stdout.decode()[-2000:] + err[-4000:]
     assert "ERROR: AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-4000:]
+
+
+def test_restatement_under_sanitizers(tmp_path):
+    """the restatement over random graphs (tests/graphgen.py) whose byte-wise concats reach N - 1 inputs past their last input's end: at
+    slack_mult 2 some of them need more than their allocation holds and stop with ORC_E_BOUNDS, at slack_mult 8 all run -- and at neither
+    does a read or write leave an allocation"""
+    import numpy as np
+    import graphgen
+    import marsfile
+    import orcbind
+    from conftest import lcg_frame
+    out = tmp_path / "orc_bounds"
+    rs = os.path.join(ROOT, "oracle", "restate")
+    cmd = ["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + rs, os.path.join(ROOT, "tests", "c", "orc_bounds.c")] + \
+        [os.path.join(rs, f) for f in sorted(os.listdir(rs)) if f.endswith(".c")] + ["-lm", "-lpthread", "-o", str(out)]
+    subprocess.check_call(cmd)
+    args = []
+    for gen, opts, seed, n in (("int8_graph", dict(nchw=True), 1, 10), ("int8_graph", dict(nchw=True, concat_chain=True, interior_outputs=True), 2, 6),
+                               ("int8_graph", {}, 3, 6), ("vcat_f32_graph", {}, 4, 6), ("f32_graph", {}, 5, 6)):
+        rng = np.random.default_rng(seed)
+        for i in range(n):
+            r = getattr(graphgen, gen)(rng, **opts)
+            if r is None:
+                continue
+            rng.integers(1, 4)  # (fuzz_graphs.py's batch draw: the first seed's graphs are the soak's, two of them spill past slack 2)
+            hdr, tensors, _ = marsfile.parse(r[0])
+            p = tmp_path / ("%s_%d_%d" % (gen, seed, i))
+            p.with_suffix(".mars").write_bytes(r[0])
+            p.with_suffix(".bin").write_bytes(lcg_frame(seed * 100 + i, marsfile.tensor_nbytes(tensors[hdr["inputs"][0]])).tobytes())
+            args += [str(p.with_suffix(".mars")), str(p.with_suffix(".bin"))]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    rcs = {}
+    for slack in (2, 8):
+        r = subprocess.run([str(out), str(slack)] + args, env=env, capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+        rcs[slack] = [int(l.split()[1]) for l in r.stdout.splitlines()]
+        assert len(rcs[slack]) == len(args) // 2
+    assert set(rcs[8]) == {0}
+    assert set(rcs[2]) == {0, orcbind.E_BOUNDS}

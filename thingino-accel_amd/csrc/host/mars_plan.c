@@ -1712,7 +1712,7 @@ void virtual_concat_f32(mars_model_ext_t *m) {
         if (Wb <= 0 || (Wb & 3) || last->out_c != Wb || last->ch_off != (N - 1) * Wb || last->out_pix_stride || last->out_h <= 0 || last->out_w <= 0) continue;
         const int TL = last->t_in[0];
         const size_t Lb = (size_t)last->out_h * last->out_w * (size_t)Wb, sB = (size_t)(N - 1) * (size_t)Wb;
-        if (TL < 0 || TL == T || m->mt[TL].is_weight || m->mt[TL].io_in /* (a pipeline may hand the graph input over in a buffer of its own: nothing mapped in front) */ || m->mt[TL].rec_c || m->mt[TL].nhwc_c || m->mt[TL].pix_stride || m->mt[TL].bytes < Lb ||
+        if (TL < 0 || TL == T || m->mt[TL].is_weight || m->mt[TL].io_in || m->mt[TL].io_out /* (a pipeline hands every graph input and output over in a buffer of its own: nothing mapped in front) */ || m->mt[TL].rec_c || m->mt[TL].nhwc_c || m->mt[TL].pix_stride || m->mt[TL].bytes < Lb ||
             m->pub.tensors[TL].desc.dtype != MARS_DTYPE_FLOAT32 || sB > 256)
             continue;
         int ok = 1, firsts[3] = {-1, -1, -1};
