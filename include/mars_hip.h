@@ -163,6 +163,45 @@ mars_error_t mars_hip_detect(mars_model_t *model, const int *output_indices, int
 mars_error_t mars_hip_detect_device(mars_model_t *model, const int *output_indices, int n_outputs,
                                     float nms_thresh);
 
+/* ------------------------------------------- anchor-based YOLOv5 Detect heads */
+/* mars_hip_detect reads its outputs as rows of 85 values already decoded (the reference demo's parse_output).  A YOLOv5 graph
+ * as exported ends in raw Detect-head convolutions instead: [3 * (5 + nc)] channels per grid cell, the box and score logits of
+ * three anchors.  These calls decode such heads on the device into boxes in input pixels (or, through the letterbox of
+ * mars_hip_preprocess, in source-image pixels), for any class count nc >= 1:
+ *   prediction order: head (as listed; mars_yolo_find_heads lists them by ascending stride), anchor a, cell row gy, column gx;
+ *   sig(q) = 1 / (1 + expf(-q * scale)) of the head's int8 byte q and its own scale;
+ *   obj = sig(q4); best = first class of largest byte; conf = obj * sig(q_best); both obj and conf >= conf_thresh;
+ *   cx = ((2 sig(q0) - 0.5) + gx) * stride, w = (2 sig(q2))^2 * anchor_w (cy, h alike); float32, no fused multiply-add;
+ *   the first MARS_YOLO_MAX_DET candidates are kept, then the sort + class-wise NMS of mars_hip_detect; then, with src_w > 0,
+ *   x' = (cx - px) * (src_w / nw), w' = w * (src_w / nw) (y, h alike) for the letterbox (nw, nh, px, py) of src_w x src_h frames.
+ * Out of scope: the anchor-free DFL head (yolov5nu / YOLOv8 style: 64 box + nc class channels); no tensor of it counts as a head. */
+
+/* The heads of a .mars file, found on the host (no device needed), sorted by stride: int8 outputs of CONV2D layers with
+ * 3 * (5 + nc) channels (nc >= 1) that only no-op layers read (or that are graph outputs), whose grid divides the graph input
+ * by the same factor on both axes (the stride).  Writes up to cap entries (tensor indices, strides, class counts; any array
+ * may be NULL) and returns the number found: 0 = none, -1 = a file the loader rejects. */
+int mars_yolo_find_heads(const void *data, size_t size, int *tensor_ids, int *strides, int *num_classes, int cap);
+
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int n_heads;             /* 0: mars_yolo_find_heads on the loaded file */
+    int head_tensors[4];     /* TENSOR indices (not output indices) */
+    int strides[4];          /* 0: input height / head height */
+    float anchors[4][3][2];  /* pixels; all zero: YOLOv5 P3-P5 defaults (10,13 16,30 33,23 | 30,61 62,45 59,119 | 116,90 156,198 373,326) */
+    float conf_thresh;       /* 0: 0.25 */
+    float nms_thresh;        /* 0: 0.45 */
+    int src_w, src_h;        /* > 0: map boxes back through the letterbox of mars_hip_preprocess for frames of this size */
+} mars_yolo_heads_t;
+/* Decode + NMS over the model's current batch.  dets: host [batch][MARS_YOLO_MAX_DET]; counts: [batch].  heads may be NULL (all
+ * defaults).  MARS_ERR_INVALID_TENSOR: no heads, or a head that is not int8, is only partly written, has no device buffer, has
+ * scale <= 0 or a channel count that is not 3 * (5 + nc). */
+mars_error_t mars_hip_detect_heads(mars_model_t *model, const mars_yolo_heads_t *heads, mars_det_t *dets, int *counts);
+/* Same, results stay in HBM; runs on the auxiliary stream behind the graph, and the next run's head-writing layers wait for it
+ * (as mars_hip_detect_device).  mars_hip_detect_results fetches them. */
+mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_heads_t *heads);
+/* The detections the last mars_hip_detect_device / mars_hip_detect_heads_device call left in HBM (waits for them). */
+mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int *counts);
+
 /* ------------------------------------------------------- pipelined host I/O */
 /* mars_run() pays host->HBM copy, graph and HBM->host copy one after the other.  With an open pipe up to three batches are
  * in flight: batch k+1 uploads and batch k-1 downloads (on their own streams, from / into their own buffers) while batch k
@@ -187,6 +226,8 @@ typedef struct {
                              * three batches in flight.  0 / 0: the graph inputs themselves are uploaded (as before).
                              * The struct has grown by these two fields (round 5): callers zero-initialise it (`= {0}` / memset) before
                              * setting what they use, so that a build against an older header still means "no camera" (ADVICE r5). */
+    const mars_yolo_heads_t *heads; /* detect: non-NULL = decode these raw heads (mars_hip_detect_heads) instead of det_outputs; copied at
+                             * open.  In camera mode a zero src_w / src_h means camera_w / camera_h: boxes come back in camera pixels */
 } mars_hip_pipe_opts_t;
 mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t *opts);
 /* pinned host buffer ([batch][frame bytes]) to fill for the NEXT submit; changes after every submit */

@@ -17,6 +17,8 @@
 //    reproducing the permutation exactly, ties included;
 //  * suppression: the pair relation is evaluated in parallel, 64 rows at a time, into an LDS bit
 //    matrix with the reference's float expression order, then applied greedily.
+// Beside it (end of file): the decode of raw anchor-based YOLOv5 Detect heads into real boxes
+// (heads_decode_kernel), which feeds the same sort + suppression.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -410,4 +412,157 @@ extern "C" int mhip_detect(const mhip_detect_t *p) {
 extern "C" int mhip_nms_only(void *dets_dev, int *count_dev, int n, float thresh) {
     if (!dets_dev || !count_dev || n < 0 || n > MAXD) return -1;
     return launch_sort_nms((det_rec *)dets_dev, count_dev, 1, thresh);
+}
+
+// ------------------------------------------------------------ anchor heads
+// The raw Detect-head convolutions of an anchor-based YOLOv5 graph decoded as the exported model's Detect layer would
+// (mars_hip_detect_heads): prediction (head k, anchor a, cell gy, gx) reads channels a * (5 + nc) + 0 .. 4 + nc of the cell;
+// with sig[q] = 1 / (1 + expf(-q * scale)) tabulated on the host per head (libm, the decode's own expression):
+//   obj = sig[q4] (dropped below conf), best = first class of largest q (the table is strictly increasing for scale > 0, so
+//   q decides), c = obj * sig[q_best] (dropped below conf), cx = ((2 sig[q0] - 0.5) + gx) * stride, w = (2 sig[q2])^2 * anchor_w.
+// Every float operation is rounded on its own (explicit _rn intrinsics: no FMA contraction whatever the flags).  The first
+// 1000 candidates in prediction order are kept -- t377's row order of the shipped file -- and sort_nms_kernel takes over.
+// One 256-thread workgroup per frame walks the predictions 2048 at a time, each thread 8 consecutive cells: their objectness
+// bytes are loaded first (8 loads in flight per thread), the class bytes only for the cells that pass, and one block-wide
+// scan gives every candidate its slot.
+#define HEADS_THREADS 256
+#define HEADS_CELLS 8 // consecutive cells per thread and step
+
+__global__ __launch_bounds__(HEADS_THREADS) void heads_decode_kernel(const mhip_heads_t p) {
+    __shared__ float sig_s[4][256];
+    __shared__ int wave_sum[HEADS_THREADS / 64];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int i = tid; i < p.nheads * 256; i += HEADS_THREADS) sig_s[i >> 8][i & 255] = p.sig[i];
+    __syncthreads();
+    det_rec *dets = (det_rec *)p.dets + (size_t)f * MAXD;
+    const float conf = p.conf;
+    int total = 0;
+    for (int hd = 0; hd < p.nheads && total < MAXD; hd++) {
+        const int8_t *hb = p.base[hd] + (size_t)f * p.frame_stride[hd];
+        const int W = p.w[hd], npix = p.h[hd] * W, nc = p.nc[hd], R = 5 + nc, ps = p.pix_step[hd], cs = p.ch_step[hd];
+        const float *sg = sig_s[hd];
+        const float fstride = (float)p.stride[hd];
+        const bool fast80 = nc == 80 && cs == 1;
+        for (int a = 0; a < 3 && total < MAXD; a++) {
+            const int8_t *ab = hb + (size_t)a * R * cs; // channel a * R of cell 0
+            const float aw = p.anchors[hd][a][0], ah = p.anchors[hd][a][1];
+            for (int base = 0; base < npix && total < MAXD; base += HEADS_THREADS * HEADS_CELLS) {
+                const int c0 = base + tid * HEADS_CELLS;
+                int qo[HEADS_CELLS];
+#pragma unroll
+                for (int k = 0; k < HEADS_CELLS; k++) qo[k] = c0 + k < npix ? ab[(size_t)(c0 + k) * ps + 4 * cs] : 0;
+                unsigned cand = 0;
+                int best[HEADS_CELLS];
+                float cf[HEADS_CELLS];
+#pragma unroll
+                for (int k = 0; k < HEADS_CELLS; k++) {
+                    best[k] = 0;
+                    cf[k] = 0.f;
+                    if (c0 + k >= npix) continue;
+                    const float obj = sg[qo[k] + 128];
+                    if (obj < conf) continue;
+                    const int8_t *row = ab + (size_t)(c0 + k) * ps;
+                    int arg = 0, bq = -129;
+                    if (fast80) {
+                        // the 80 class bytes as five 16-byte loads (any alignment is served), compared as integers
+                        v4i w[5];
+#pragma unroll
+                        for (int j = 0; j < 5; j++) __builtin_memcpy(&w[j], row + 5 + 16 * j, 16);
+#pragma unroll
+                        for (int j = 0; j < 20; j++) {
+                            const int d = w[j >> 2][j & 3];
+#pragma unroll
+                            for (int b = 0; b < 4; b++) {
+                                const int q = (d << (24 - 8 * b)) >> 24;
+                                const bool gt = q > bq;
+                                bq = gt ? q : bq;
+                                arg = gt ? 4 * j + b : arg;
+                            }
+                        }
+                    } else {
+                        for (int c = 0; c < nc; c++) {
+                            const int q = row[(size_t)(5 + c) * cs];
+                            if (q > bq) { bq = q; arg = c; }
+                        }
+                    }
+                    const float c = __fmul_rn(obj, sg[bq + 128]);
+                    if (c < conf) continue;
+                    cand |= 1u << k;
+                    best[k] = arg;
+                    cf[k] = c;
+                }
+                // slots: block-wide exclusive scan of the per-thread candidate counts (thread order = prediction order)
+                const int n_t = __popc(cand);
+                int incl = n_t;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int v = __shfl_up(incl, o);
+                    if (lane >= o) incl += v;
+                }
+                if (lane == 63) wave_sum[wv] = incl;
+                __syncthreads();
+                int slot = total, step = 0;
+#pragma unroll
+                for (int w = 0; w < HEADS_THREADS / 64; w++) {
+                    if (w < wv) slot += wave_sum[w];
+                    step += wave_sum[w];
+                }
+                slot += incl - n_t;
+#pragma unroll
+                for (int k = 0; k < HEADS_CELLS; k++) {
+                    if (!((cand >> k) & 1u)) continue;
+                    if (slot < MAXD) {
+                        const int cell = c0 + k, gy = cell / W, gx = cell - gy * W;
+                        const int8_t *row = ab + (size_t)cell * ps;
+                        const float s0 = sg[row[0] + 128], s1 = sg[row[cs] + 128];
+                        const float s2 = __fmul_rn(sg[row[2 * cs] + 128], 2.0f), s3 = __fmul_rn(sg[row[3 * cs] + 128], 2.0f);
+                        det_rec d;
+                        d.x = __fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(s0, 2.0f), 0.5f), (float)gx), fstride);
+                        d.y = __fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(s1, 2.0f), 0.5f), (float)gy), fstride);
+                        d.w = __fmul_rn(__fmul_rn(s2, s2), aw);
+                        d.h = __fmul_rn(__fmul_rn(s3, s3), ah);
+                        d.conf = cf[k];
+                        d.cls = best[k];
+                        dets[slot] = d;
+                    }
+                    slot++;
+                }
+                total += step;
+                __syncthreads(); // wave_sum is rewritten by the next step
+            }
+        }
+    }
+    if (total > MAXD) total = MAXD;
+    if (tid == 0) {
+        if (p.raw_counts) p.raw_counts[f] = total;
+        p.counts[f] = total;
+    }
+}
+
+// the kept boxes back through the letterbox of the image front-end (after NMS: suppression sees the network's coordinates)
+__global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int *counts, float px, float py, float rx, float ry) {
+    det_rec *d = all + (size_t)blockIdx.x * MAXD;
+    int n = counts[blockIdx.x];
+    if (n > MAXD) n = MAXD;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        det_rec r = d[i];
+        r.x = __fmul_rn(__fsub_rn(r.x, px), rx);
+        r.y = __fmul_rn(__fsub_rn(r.y, py), ry);
+        r.w = __fmul_rn(r.w, rx);
+        r.h = __fmul_rn(r.h, ry);
+        d[i] = r;
+    }
+}
+
+extern "C" int mhip_detect_heads(const mhip_heads_t *p) {
+    if (!p || p->nheads <= 0 || p->nheads > 4 || p->frames <= 0 || !p->dets || !p->counts || !p->sig) return -1;
+    for (int k = 0; k < p->nheads; k++)
+        if (!p->base[k] || p->h[k] <= 0 || p->w[k] <= 0 || p->nc[k] < 1 || p->pix_step[k] <= 0 || p->ch_step[k] <= 0) return -1;
+    hipLaunchKernelGGL(heads_decode_kernel, dim3(p->frames), dim3(HEADS_THREADS), 0, mhip_stream_native(), *p);
+    int rc = mhip_check(hipGetLastError(), "decode heads");
+    if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
+    if (rc || !p->map) return rc;
+    hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,
+                       (float)p->py, p->rx, p->ry);
+    return mhip_check(hipGetLastError(), "letterbox mapping");
 }

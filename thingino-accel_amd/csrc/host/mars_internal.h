@@ -53,6 +53,7 @@ typedef struct {
     size_t zero_from;      /* != 0: bytes from this offset on are never written by any layer (zero_tail_f32 relies on it): mars_hip_write_tensor refuses non-zero bytes there */
     int partial;           /* only part of the tensor is ever written (virtual_concat_q keeps the first rows of a concat): not readable through mars_hip_read_tensor */
     int nhwc_pitch;        /* ... bytes between its pixels (0 = nhwc_c; a write-only 255-channel head is kept at 256) */
+    int tail_read;         /* a raw-head decode (mars_hip_detect_heads_device) reads it: a pending tail holds back its writer like a graph output's */
 } mtensor_t;
 
 typedef struct {
@@ -134,6 +135,9 @@ typedef struct mars_model_ext {
     float det_lut_scale[4]; /* scales the uploaded decode LUTs were built for */
     int det_lut_n;
     int det_lut_mono[4];    /* value table of that segment strictly increasing (mhip_detect_t.mono) */
+    float *heads_lut_dev;   /* raw-head decode: [head][256] sigmoid tables (mhip_heads_t.sig) */
+    float heads_lut_scale[4];
+    int heads_lut_n;
     void *ev_graph_done, *ev_tail_done; /* main->aux and aux->main hand-offs */
     int tail_pending;
     int frame0, run_frames; /* frame range the launches being enqueued cover (a large batch runs as two halves on two streams) */
@@ -146,6 +150,7 @@ typedef struct mars_model_ext {
     struct { char key[28]; int value, saved; } tune[MARS_MAX_MODEL_TUNE]; /* launch-policy overrides of this model */
     int n_tune, tune_depth;
     int plan_f32_mode; /* the f32_mfma mode build_plan ran under (weight images, record pairs): replan_for_f32_mode */
+    unsigned char *layer_noop; /* [num_layers]: plan_layer emitted no launch for it (the runtime treats it as a no-op; mars_yolo_find_heads) */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -199,6 +204,20 @@ MARS_INTERNAL void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op
 mars_error_t mars_detect_prepare(mars_model_ext_t *m, const int *output_indices, int n_outputs);
 int mars_detect_launch(mars_model_ext_t *m, const int *output_indices, int n_outputs, float nms_thresh, void *dets_dev,
                        int *counts_dev);
+
+/* raw anchor-based heads (mars_yolo.c): a mars_yolo_heads_t resolved against the loaded plan */
+typedef struct {
+    int n, ti[4], stride[4], nc[4], h[4], w[4], pix_step[4], ch_step[4];
+    float anchors[4][3][2];
+    float conf, nms;
+    int map, px, py;
+    float rx, ry;
+    int internal; /* some head is not a graph output: one buffer for every batch in flight */
+} mars_heads_cfg_t;
+MARS_INTERNAL int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, int *strides, int *num_classes, int cap);
+MARS_INTERNAL mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h, mars_heads_cfg_t *c);
+MARS_INTERNAL mars_error_t mars_heads_prepare(mars_model_ext_t *m, const mars_heads_cfg_t *c); /* sigmoid tables up; synchronises if they change */
+MARS_INTERNAL int mars_heads_launch(mars_model_ext_t *m, const mars_heads_cfg_t *c, void *dets_dev, int *counts_dev); /* current stream */
 
 /* shared host helpers (mars_model.c) */
 int32_t mars_trunc_x86(float x);

@@ -139,6 +139,7 @@ void mars_free(mars_model_t *model) {
     free_ops(m);
     if (m->arena_dev) mhip_free(m->arena_dev);
     if (m->det_lut_dev) mhip_free(m->det_lut_dev);
+    if (m->heads_lut_dev) mhip_free(m->heads_lut_dev);
     if (m->ev_graph_done) mhip_event_destroy(m->ev_graph_done);
     if (m->ev_tail_done) mhip_event_destroy(m->ev_tail_done);
     if (m->ev_fork) mhip_event_destroy(m->ev_fork);
@@ -148,6 +149,7 @@ void mars_free(mars_model_t *model) {
         for (int c = 0; c < 8; c++)
             if (m->ev_chunk[k][c]) mhip_event_destroy(m->ev_chunk[k][c]);
     free(m->arena_host);
+    free(m->layer_noop);
     free(m->mt);
     free(m->pub.weights);
     free(m->pub.layers);
@@ -171,7 +173,11 @@ mars_error_t build_plan(mars_model_ext_t *m) {
     }
     /* slot 0 of the arena: mirror of the raw blob (element-wise layers may read weight
      * tensors directly); sized after planning, so reserve generously now */
-    for (uint32_t i = 0; i < nl && m->plan_err == MARS_OK; i++) plan_layer(m, (int)i);
+    for (uint32_t i = 0; i < nl && m->plan_err == MARS_OK; i++) {
+        const int n0 = m->n_ops;
+        plan_layer(m, (int)i);
+        m->layer_noop[i] = m->n_ops == n0;
+    }
     if (m->plan_err != MARS_OK) return (mars_error_t)m->plan_err;
     if (m->fusion >= 1) {
         fuse_silu(m);
@@ -365,7 +371,8 @@ static mars_error_t load_host(const void *data, size_t size, unsigned flags, mar
     m->pub.tensors = (mars_runtime_tensor_t *)calloc(h.num_tensors ? h.num_tensors : 1, sizeof(mars_runtime_tensor_t));
     m->pub.layers = (mars_runtime_layer_t *)calloc(h.num_layers ? h.num_layers : 1, sizeof(mars_runtime_layer_t));
     m->mt = (mtensor_t *)calloc(h.num_tensors ? h.num_tensors : 1, sizeof(mtensor_t));
-    if (!m->pub.tensors || !m->pub.layers || !m->mt) { mars_free(&m->pub); return MARS_ERR_ALLOC_FAILED; }
+    m->layer_noop = (unsigned char *)calloc(h.num_layers ? h.num_layers : 1, 1);
+    if (!m->pub.tensors || !m->pub.layers || !m->mt || !m->layer_noop) { mars_free(&m->pub); return MARS_ERR_ALLOC_FAILED; }
     const uint8_t *q = p + sizeof(h);
     for (uint32_t i = 0; i < h.num_tensors; i++, q += sizeof(mars_tensor_t)) memcpy(&m->pub.tensors[i].desc, q, sizeof(mars_tensor_t));
     for (uint32_t i = 0; i < h.num_layers; i++, q += sizeof(mars_layer_t)) memcpy(&m->pub.layers[i].desc, q, sizeof(mars_layer_t));
@@ -461,6 +468,15 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
     }
 #undef EMIT
     if (out && cap) out[n < cap ? n : cap - 1] = 0;
+    mars_free(&m->pub);
+    return n;
+}
+
+/* anchor-based YOLOv5 heads of a file, host only: the loader's parse and plan (which layers are no-ops), then mars_find_heads */
+int mars_yolo_find_heads(const void *data, size_t size, int *tensor_ids, int *strides, int *num_classes, int cap) {
+    mars_model_ext_t *m = NULL;
+    if (load_host(data, size, 0, &m) != MARS_OK) return -1;
+    const int n = mars_find_heads(m, tensor_ids, strides, num_classes, cap);
     mars_free(&m->pub);
     return n;
 }

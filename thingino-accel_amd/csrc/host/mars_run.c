@@ -347,9 +347,10 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             return (mars_error_t)op->err;
         }
         mars_op_t *mate = op->pair_next && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
-        if (wait_tail && ((op->t_out >= 0 && m->mt[op->t_out].io_out) || (mate && mate->t_out >= 0 && m->mt[mate->t_out].io_out))) {
+        if (wait_tail && ((op->t_out >= 0 && (m->mt[op->t_out].io_out || m->mt[op->t_out].tail_read)) ||
+                          (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)))) {
             /* the previous batch's detection tail (auxiliary stream) still reads the graph
-             * outputs: order this launch behind it */
+             * outputs (or the raw heads it decodes): order this launch behind it */
             mhip_stream_wait(sid, m->ev_tail_done);
             wait_tail = 0;
         }

@@ -200,3 +200,223 @@ int mars_yolo_nms(mars_det_t *dets, int n, float thresh) {
     mhip_free(d);
     return kept;
 }
+
+/* ---- raw anchor-based YOLOv5 Detect heads (include/mars_hip.h: mars_hip_detect_heads) */
+static int tensor_by_id(const mars_model_ext_t *m, uint32_t id) {
+    if (id == NO_TENSOR) return -1;
+    for (uint32_t i = 0; i < m->pub.header.num_tensors; i++)
+        if (m->pub.tensors[i].desc.id == id) return (int)i;
+    return -1;
+}
+
+/* channels and grid of a 4-D [1, C, H, W] / [1, H, W, C] (NHWC tag) tensor; -1 if it is not one */
+static int tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w) {
+    if (d->ndims != 4 || d->shape[0] != 1) return -1;
+    if (d->format == MARS_FORMAT_NHWC) { *h = d->shape[1]; *w = d->shape[2]; *c = d->shape[3]; }
+    else { *c = d->shape[1]; *h = d->shape[2]; *w = d->shape[3]; }
+    return *c > 0 && *h > 0 && *w > 0 ? 0 : -1;
+}
+
+/* graph input 0's grid (what the strides divide) */
+static int input_hw(const mars_model_ext_t *m, int *h, int *w) {
+    int c;
+    if (m->pub.header.num_inputs < 1 || m->pub.header.input_tensor_ids[0] >= m->pub.header.num_tensors) return -1;
+    return tensor_chw(&m->pub.tensors[m->pub.header.input_tensor_ids[0]].desc, &c, h, w);
+}
+
+int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, int *strides, int *num_classes, int cap) {
+    const uint32_t nl = m->pub.header.num_layers;
+    int ih, iw, n = 0, ti[4], st[4], nc[4];
+    if (input_hw(m, &ih, &iw)) return 0;
+    for (uint32_t li = 0; li < nl; li++) {
+        const mars_layer_t *L = &m->pub.layers[li].desc;
+        if (L->type != MARS_LAYER_CONV2D || L->num_outputs < 1 || m->layer_noop[li]) continue;
+        const int T = tensor_by_id(m, L->output_tensor_ids[0]);
+        if (T < 0 || m->mt[T].is_weight) continue;
+        const mars_tensor_t *d = &m->pub.tensors[T].desc;
+        int c, h, w;
+        if (d->dtype != MARS_DTYPE_INT8 || tensor_chw(d, &c, &h, &w) || c % 3 || c / 3 - 5 < 1) continue;
+        if (ih % h || iw % w || ih / h != iw / w) continue;
+        int read = 0; /* by a layer that does something */
+        for (uint32_t lj = 0; lj < nl && !read && !m->mt[T].io_out; lj++) {
+            const mars_layer_t *R = &m->pub.layers[lj].desc;
+            for (uint32_t k = 0; k < R->num_inputs && k < 4; k++)
+                if (R->input_tensor_ids[k] == d->id && !m->layer_noop[lj]) read = 1;
+        }
+        if (read) continue;
+        if (n < 4) { ti[n] = T; st[n] = ih / h; nc[n] = c / 3 - 5; }
+        n++;
+    }
+    const int kept = n < 4 ? n : 4;
+    for (int i = 1; i < kept; i++) /* by stride, stable */
+        for (int j = i; j > 0 && st[j - 1] > st[j]; j--) {
+            int t;
+            t = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = t;
+            t = st[j]; st[j] = st[j - 1]; st[j - 1] = t;
+            t = nc[j]; nc[j] = nc[j - 1]; nc[j - 1] = t;
+        }
+    for (int i = 0; i < kept && i < cap; i++) {
+        if (tensor_ids) tensor_ids[i] = ti[i];
+        if (strides) strides[i] = st[i];
+        if (num_classes) num_classes[i] = nc[i];
+    }
+    return n;
+}
+
+static const float k_default_anchors[3][3][2] = {{{10, 13}, {16, 30}, {33, 23}}, {{30, 61}, {62, 45}, {59, 119}}, {{116, 90}, {156, 198}, {373, 326}}};
+
+mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h, mars_heads_cfg_t *c) {
+    mars_yolo_heads_t zero;
+    memset(&zero, 0, sizeof(zero));
+    if (!h) h = &zero;
+    memset(c, 0, sizeof(*c));
+    int ih, iw;
+    if (h->n_heads < 0 || h->n_heads > 4 || input_hw(m, &ih, &iw)) return MARS_ERR_INVALID_TENSOR;
+    int n = h->n_heads;
+    if (n == 0) {
+        n = mars_find_heads(m, c->ti, NULL, NULL, 4);
+        if (n <= 0 || n > 4) return MARS_ERR_INVALID_TENSOR;
+    } else {
+        memcpy(c->ti, h->head_tensors, sizeof(c->ti));
+    }
+    c->n = n;
+    for (int k = 0; k < n; k++) {
+        const int T = c->ti[k];
+        if (T < 0 || (uint32_t)T >= m->pub.header.num_tensors) return MARS_ERR_INVALID_TENSOR;
+        const mtensor_t *t = &m->mt[T];
+        const mars_tensor_t *d = &m->pub.tensors[T].desc;
+        int ch, hh, ww;
+        if (t->is_weight || t->partial || !t->dev || d->dtype != MARS_DTYPE_INT8 || !(d->scale > 0) || tensor_chw(d, &ch, &hh, &ww) ||
+            ch % 3 || ch / 3 - 5 < 1)
+            return MARS_ERR_INVALID_TENSOR;
+        /* the device layout is what the writing convolution stores: planes [C][H][W], or pixel rows at its pitch (NHWC tensors, the
+         * padded rows of graph outputs, NCHW-tagged tensors held pixels x channels) */
+        const mars_op_t *wr = NULL;
+        for (int i = 0; i < m->n_ops && !wr; i++)
+            if (m->ops[i].kind == OP_CONV_I8 && m->ops[i].t_out == T) wr = &m->ops[i];
+        if (!wr || wr->out_ch_off || wr->out_byte_off || wr->out_c != ch || wr->out_h != hh || wr->out_w != ww) return MARS_ERR_INVALID_TENSOR;
+        if (wr->out_nchw) { c->pix_step[k] = 1; c->ch_step[k] = hh * ww; }
+        else { c->pix_step[k] = wr->out_pix_stride ? wr->out_pix_stride : ch; c->ch_step[k] = 1; }
+        c->h[k] = hh; c->w[k] = ww; c->nc[k] = ch / 3 - 5;
+        c->stride[k] = h->strides[k] > 0 ? h->strides[k] : ih / hh;
+        if (h->strides[k] < 0 || c->stride[k] <= 0) return MARS_ERR_INVALID_TENSOR;
+        if (!t->io_out) c->internal = 1;
+    }
+    int any = 0;
+    for (int k = 0; k < 4; k++)
+        for (int a = 0; a < 3; a++) any |= h->anchors[k][a][0] != 0 || h->anchors[k][a][1] != 0;
+    if (any) memcpy(c->anchors, h->anchors, sizeof(c->anchors));
+    else if (n <= 3) memcpy(c->anchors, k_default_anchors, (size_t)n * sizeof(k_default_anchors[0]));
+    else return MARS_ERR_INVALID_TENSOR; /* no default anchors for a fourth head */
+    c->conf = h->conf_thresh != 0 ? h->conf_thresh : 0.25f;
+    c->nms = h->nms_thresh != 0 ? h->nms_thresh : 0.45f;
+    if (h->src_w || h->src_h) {
+        if (h->src_w <= 0 || h->src_h <= 0) return MARS_ERR_INVALID_TENSOR;
+        /* the letterbox of mars_preproc.c (the reference's load_image, mars_yolo_test.c:47-49) for the graph input's size */
+        const int w = h->src_w, hs = h->src_h, tw = iw, th = ih;
+        const float scale = fminf((float)tw / w, (float)th / hs);
+        const int nw = (int)(w * scale), nh = (int)(hs * scale);
+        if (nw <= 0 || nh <= 0) return MARS_ERR_INVALID_TENSOR;
+        c->map = 1;
+        c->px = (tw - nw) / 2;
+        c->py = (th - nh) / 2;
+        c->rx = (float)w / (float)nw;
+        c->ry = (float)hs / (float)nh;
+    }
+    return MARS_OK;
+}
+
+/* sigmoid tables of the heads (they depend only on the heads' scales): built and uploaded once.  Synchronises when they change. */
+mars_error_t mars_heads_prepare(mars_model_ext_t *m, const mars_heads_cfg_t *c) {
+    if (!m->heads_lut_dev) m->heads_lut_dev = (float *)mhip_malloc(4 * 256 * sizeof(float));
+    if (!m->heads_lut_dev) return MARS_ERR_ALLOC_FAILED;
+    int stale = m->heads_lut_n != c->n;
+    for (int k = 0; k < c->n; k++)
+        if (memcmp(&m->heads_lut_scale[k], &m->pub.tensors[c->ti[k]].desc.scale, sizeof(float)) != 0) stale = 1;
+    if (!stale) return MARS_OK;
+    float lut[4 * 256], tab[768];
+    for (int k = 0; k < c->n; k++) {
+        const float sc = m->pub.tensors[c->ti[k]].desc.scale;
+        build_decode_lut(sc, tab); /* its obj(q) = 1 / (1 + expf(-q * scale)): the sigmoid of every head byte */
+        memcpy(lut + k * 256, tab + 256, 256 * sizeof(float));
+        m->heads_lut_scale[k] = sc;
+    }
+    if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
+    if (mhip_h2d_async(m->heads_lut_dev, lut, (size_t)c->n * 256 * sizeof(float)) || mhip_sync())
+        return MARS_ERR_LAYER_FAILED; /* `lut` is on this stack frame */
+    m->heads_lut_n = c->n;
+    return MARS_OK;
+}
+
+int mars_heads_launch(mars_model_ext_t *m, const mars_heads_cfg_t *c, void *dets_dev, int *counts_dev) {
+    mhip_heads_t p;
+    memset(&p, 0, sizeof(p));
+    for (int k = 0; k < c->n; k++) {
+        const mtensor_t *t = &m->mt[c->ti[k]];
+        if (!t->dev) return -1;
+        p.base[k] = (const int8_t *)t->dev;
+        p.frame_stride[k] = t->stride;
+        p.h[k] = c->h[k]; p.w[k] = c->w[k]; p.nc[k] = c->nc[k];
+        p.pix_step[k] = c->pix_step[k]; p.ch_step[k] = c->ch_step[k];
+        p.stride[k] = c->stride[k];
+    }
+    memcpy(p.anchors, c->anchors, sizeof(p.anchors));
+    p.sig = m->heads_lut_dev;
+    p.nheads = c->n;
+    p.frames = m->batch;
+    p.conf = c->conf;
+    p.nms_thresh = c->nms;
+    p.dets = dets_dev;
+    p.counts = counts_dev;
+    p.raw_counts = counts_dev + m->batch;
+    p.map = c->map; p.px = c->px; p.py = c->py; p.rx = c->rx; p.ry = c->ry;
+    return mhip_detect_heads(&p);
+}
+
+mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_heads_t *heads) {
+    if (!model) return MARS_ERR_INVALID_TENSOR;
+    mars_model_ext_t *m = (mars_model_ext_t *)model;
+    mars_heads_cfg_t c;
+    mars_error_t e = mars_heads_resolve(m, heads, &c);
+    if (e != MARS_OK) return e;
+    if (m->det_cap < m->batch || !m->det_dev) {
+        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
+        if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
+        m->det_lut_n = 0;
+    }
+    e = mars_heads_prepare(m, &c);
+    if (e != MARS_OK) return e;
+    /* as mars_hip_detect_device: the decode runs on the auxiliary stream behind the graph, and the next run's layers that write a head
+     * wait for it (tail_read) -- the heads of the shipped files are internal tensors, not graph outputs */
+    for (int k = 0; k < c.n; k++) m->mt[c.ti[k]].tail_read = 1;
+    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
+    if (!m->ev_tail_done) m->ev_tail_done = mhip_event_create_sync();
+    if (!m->ev_graph_done || !m->ev_tail_done) return MARS_ERR_ALLOC_FAILED;
+    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
+    mhip_select_aux(1);
+    int rc = mhip_stream_wait(1, m->ev_graph_done);
+    if (!rc) rc = mars_heads_launch(m, &c, m->det_dev, m->det_counts_dev);
+    if (!rc) rc = mhip_event_record(m->ev_tail_done);
+    mhip_select_aux(0);
+    if (rc) return MARS_ERR_LAYER_FAILED;
+    m->tail_pending = 1;
+    return MARS_OK;
+}
+
+mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int *counts) {
+    if (!model || !dets || !counts) return MARS_ERR_INVALID_TENSOR;
+    mars_model_ext_t *m = (mars_model_ext_t *)model;
+    if (!m->det_dev || m->det_cap < m->batch) return MARS_ERR_INVALID_TENSOR;
+    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
+    m->tail_pending = 0;
+    if (mhip_d2h_async(dets, m->det_dev, (size_t)m->batch * MARS_YOLO_MAX_DET * sizeof(mars_det_t)) ||
+        mhip_d2h_async(counts, m->det_counts_dev, (size_t)m->batch * sizeof(int)) || mhip_sync())
+        return MARS_ERR_LAYER_FAILED;
+    return MARS_OK;
+}
+
+mars_error_t mars_hip_detect_heads(mars_model_t *model, const mars_yolo_heads_t *heads, mars_det_t *dets, int *counts) {
+    if (!dets || !counts) return MARS_ERR_INVALID_TENSOR;
+    mars_error_t e = mars_hip_detect_heads_device(model, heads);
+    return e != MARS_OK ? e : mars_hip_detect_results(model, dets, counts);
+}

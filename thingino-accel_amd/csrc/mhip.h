@@ -268,7 +268,7 @@ int mhip_upsample_i8(const int8_t *in, size_t in_stride, int8_t *out, size_t out
 int mhip_nchw_to_nhwc_pad(const int8_t *in, size_t in_stride, int8_t *out, size_t out_stride,
                           int frames, int c, int hw, int c_pad);
 
-/* ---- detection tail (yolo_tail.hip) */
+/* ---- detection tails (yolo_tail.hip) */
 typedef struct {
     const int8_t *pred[4]; size_t stride[4]; int npred[4];
     int pix_c[4], pix_stride[4]; /* pix_stride != 0: every pix_c prediction bytes sit at the start of a pix_stride-byte pixel row */
@@ -284,6 +284,24 @@ typedef struct {
 } mhip_detect_t;
 int mhip_detect(const mhip_detect_t *p);
 int mhip_nms_only(void *dets_dev, int *count_dev, int n, float thresh);
+/* raw anchor-based YOLOv5 Detect heads (yolo_tail.hip: heads_decode_kernel), decoded in prediction order (head, anchor, gy, gx),
+ * then the same sort + NMS as mhip_detect, then (map) the letterbox mapping x' = (x - px) * rx, w' = w * rx (y, h alike) */
+typedef struct {
+    const int8_t *base[4]; size_t frame_stride[4]; /* head k of frame f starts at base[k] + f * frame_stride[k] */
+    int h[4], w[4], nc[4];  /* grid and classes: 3 * (5 + nc) channels */
+    int pix_step[4], ch_step[4]; /* byte of (pixel p = gy * w + gx, channel c) = p * pix_step + c * ch_step */
+    int stride[4];
+    float anchors[4][3][2]; /* pixels */
+    const float *sig;       /* device [head][256]: 1 / (1 + expf(-q * scale)) at q + 128, the head's own scale */
+    int nheads, frames;
+    float conf, nms_thresh;
+    void *dets;             /* device [frames][1000] records of 24 bytes */
+    int *counts;            /* device [frames] kept */
+    int *raw_counts;        /* device [frames] candidates before NMS (or NULL) */
+    int map, px, py;        /* map != 0: boxes mapped back through a letterbox at (px, py) with factors rx, ry */
+    float rx, ry;
+} mhip_heads_t;
+int mhip_detect_heads(const mhip_heads_t *p);
 
 /* ---- image front-end (preproc.hip): letterbox resize + (px - 128); tables from csrc/host/mars_preproc.c */
 typedef struct {

@@ -80,9 +80,14 @@ class SynthOpts(C.Structure):
                 ("nchw_int8", C.c_int), ("seed", C.c_uint), ("tiny", C.c_int), ("vary_scales", C.c_int)]
 
 
+class YoloHeads(C.Structure):  # mars_yolo_heads_t: zero = default in every field
+    _fields_ = [("n_heads", C.c_int), ("head_tensors", C.c_int * 4), ("strides", C.c_int * 4), ("anchors", C.c_float * 24),
+                ("conf_thresh", C.c_float), ("nms_thresh", C.c_float), ("src_w", C.c_int), ("src_h", C.c_int)]
+
+
 class PipeOpts(C.Structure):
     _fields_ = [("download_outputs", C.c_int), ("detect", C.c_int), ("det_outputs", C.c_int * 4), ("n_det_outputs", C.c_int),
-                ("nms_thresh", C.c_float), ("camera_w", C.c_int), ("camera_h", C.c_int)]
+                ("nms_thresh", C.c_float), ("camera_w", C.c_int), ("camera_h", C.c_int), ("heads", C.POINTER(YoloHeads))]
 
 
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
@@ -116,7 +121,8 @@ EXPORTS = {
                    "mars_hip_detect", "mars_hip_detect_device", "mars_synth_model", "mars_hip_set_tuning", "mars_hip_autotune", "mars_yolo_letterbox",
                    "mars_hip_preprocess", "mars_hip_preprocess_device", "mars_hip_tensor_frame_bytes", "mars_hip_tensor_byte_size", "mars_hip_pipe_open",
                    "mars_hip_pipe_input", "mars_hip_pipe_submit", "mars_hip_pipe_wait", "mars_hip_pipe_close", "mars_hip_pipe_camera_ms", "mars_hip_set_output_mode",
-                   "mars_hip_get_tuning", "mars_hip_model_set_tuning", "mars_hip_model_get_tuning"],
+                   "mars_hip_get_tuning", "mars_hip_model_set_tuning", "mars_hip_model_get_tuning", "mars_yolo_find_heads",
+                   "mars_hip_detect_heads", "mars_hip_detect_heads_device", "mars_hip_detect_results"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -205,6 +211,10 @@ def lib():
     L.mars_yolo_nms.argtypes = [C.c_void_p, C.c_int, C.c_float]
     L.mars_hip_detect.argtypes = [P(MarsModel), P(C.c_int), C.c_int, C.c_float, C.c_void_p, P(C.c_int)]
     L.mars_hip_detect_device.argtypes = [P(MarsModel), P(C.c_int), C.c_int, C.c_float]
+    L.mars_yolo_find_heads.argtypes = [C.c_void_p, C.c_size_t, P(C.c_int), P(C.c_int), P(C.c_int), C.c_int]
+    L.mars_hip_detect_heads.argtypes = [P(MarsModel), P(YoloHeads), C.c_void_p, P(C.c_int)]
+    L.mars_hip_detect_heads_device.argtypes = [P(MarsModel), P(YoloHeads)]
+    L.mars_hip_detect_results.argtypes = [P(MarsModel), C.c_void_p, P(C.c_int)]
     L.mars_compile_onnx.restype = C.c_size_t
     L.mars_compile_onnx.argtypes = [C.c_char_p, C.c_size_t, P(CompileOpts), C.c_void_p, C.c_size_t]
     L.mars_compile_file.argtypes = [C.c_char_p, C.c_char_p, P(CompileOpts)]
@@ -277,6 +287,35 @@ def describe_plan(file_bytes, flags=0):
     buf = C.create_string_buffer(n + 1)
     lib().mars_hip_describe_plan(b, len(b), flags, buf, n + 1)
     return buf.value.decode().splitlines()
+
+
+def find_yolo_heads(file_bytes):
+    """anchor-based YOLOv5 Detect heads of a .mars file (mars_yolo_find_heads; host only: works without a GPU), by stride:
+    a list of (tensor index, stride, classes).  ValueError if the loader rejects the file."""
+    b = bytes(file_bytes)
+    ti, st, nc = (C.c_int * 4)(), (C.c_int * 4)(), (C.c_int * 4)()
+    n = lib().mars_yolo_find_heads(b, len(b), ti, st, nc, 4)
+    if n < 0:
+        raise ValueError("the loader rejects the file")
+    return [(ti[k], st[k], nc[k]) for k in range(min(n, 4))]
+
+
+def yolo_heads(heads=None, anchors=None, conf=0.25, thresh=0.45, src=None):
+    """mars_yolo_heads_t.  heads: None (found on the loaded file) or a list of tensor indices / (tensor index, stride) pairs;
+    anchors: None (YOLOv5 P3-P5 defaults) or [head][3][2] pixels; src = (w, h): boxes mapped back through the letterbox of
+    frames of that size"""
+    h = YoloHeads()
+    for k, e in enumerate(heads or ()):
+        ti, st = e if isinstance(e, (tuple, list)) else (e, 0)
+        h.head_tensors[k], h.strides[k] = int(ti), int(st)
+    h.n_heads = len(heads or ())
+    if anchors is not None:
+        for i, v in enumerate(np.asarray(anchors, dtype=np.float32).reshape(-1)):
+            h.anchors[i] = float(v)
+    h.conf_thresh, h.nms_thresh = conf, thresh
+    if src is not None:
+        h.src_w, h.src_h = int(src[0]), int(src[1])
+    return h
 
 
 def compile_onnx(onnx_bytes, float32=False, nhwc=False, verbose=False):
@@ -445,12 +484,42 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_detect_device")
 
+    def detect_heads(self, heads=None, anchors=None, conf=0.25, thresh=0.45, src=None):
+        """decode + NMS of raw YOLOv5 Detect heads (mars_hip_detect_heads): a record array per frame, as detect().  Arguments
+        as for yolo_heads()."""
+        h = yolo_heads(heads, anchors, conf, thresh, src)
+        dets = np.zeros((self.batch, MAX_DET), dtype=DET_DTYPE)
+        counts = np.zeros(self.batch, dtype=np.int32)
+        rc = lib().mars_hip_detect_heads(self.p, C.byref(h), dets.ctypes.data, counts.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_heads")
+        return [dets[f, :counts[f]].copy() for f in range(self.batch)]
+
+    def detect_heads_device(self, heads=None, anchors=None, conf=0.25, thresh=0.45, src=None):
+        rc = lib().mars_hip_detect_heads_device(self.p, C.byref(yolo_heads(heads, anchors, conf, thresh, src)))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_heads_device")
+
+    def detect_results(self):
+        """the detections the last detect_device / detect_heads_device left in HBM (mars_hip_detect_results)"""
+        dets = np.zeros((self.batch, MAX_DET), dtype=DET_DTYPE)
+        counts = np.zeros(self.batch, dtype=np.int32)
+        rc = lib().mars_hip_detect_results(self.p, dets.ctypes.data, counts.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_results")
+        return [dets[f, :counts[f]].copy() for f in range(self.batch)]
+
     # -- pipelined host I/O (mars_hip_pipe_*)
-    def pipe_open(self, download_outputs=True, detect=False, det_outputs=(0,), thresh=0.45, camera=None):
-        """camera = (w, h): input 0 is fed from uint8 RGB camera frames, the letterbox front-end runs on the device behind the upload"""
+    def pipe_open(self, download_outputs=True, detect=False, det_outputs=(0,), thresh=0.45, camera=None, heads=None):
+        """camera = (w, h): input 0 is fed from uint8 RGB camera frames, the letterbox front-end runs on the device behind the upload.
+        heads (with detect): True (found on the file), a list as for detect_heads() or a YoloHeads -- the tail decodes those raw
+        heads instead of det_outputs; in camera mode their boxes come back in camera pixels"""
         cw, ch = camera if camera else (0, 0)
         o = PipeOpts(int(download_outputs), int(detect), (C.c_int * 4)(*(list(det_outputs) + [0] * (4 - len(det_outputs)))),
                      len(det_outputs) if detect else 0, thresh, int(cw), int(ch))
+        if heads is not None and heads is not False:
+            h = heads if isinstance(heads, YoloHeads) else yolo_heads(None if heads is True else heads, thresh=thresh)
+            o.heads = C.pointer(h)  # copied by mars_hip_pipe_open
         rc = lib().mars_hip_pipe_open(self.p, C.byref(o))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_pipe_open")
