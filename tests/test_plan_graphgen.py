@@ -27,11 +27,34 @@ def _graphs(gen, seed, n=N, **opt):
     return out
 
 
+# what every test below draws: name -> (generator, seed, options, f32_mfma modes it is planned under).  tools/plan_corpus.py dumps the plans of
+# exactly these graphs
+CORPUS = {}
+for _nchw in (None, True):
+    for _int in (False, True):
+        CORPUS["int8", _nchw, _int] = (graphgen.int8_graph, 4100 + 2 * bool(_nchw) + _int, dict(nchw=_nchw, interior_outputs=_int), (None,))
+for _int in (False, True):
+    CORPUS["int8_chain", _int] = (graphgen.int8_graph, 4110 + _int, dict(nchw=True, interior_outputs=_int, concat_chain=True), (None,))
+    CORPUS["f32", _int] = (graphgen.f32_graph, 4120 + _int, dict(interior_outputs=_int), (1, 3, 4))
+    CORPUS["vcat_f32", _int] = (graphgen.vcat_f32_graph, 4130 + _int, dict(interior_outputs=_int), (1, 3, 4))
+
+
+def corpus_graphs(key):
+    gen, seed, opt, _ = CORPUS[key]
+    return _graphs(gen, seed, **opt)
+
+
+def strip_full(lines):
+    """a MARS_HIP_DESCRIBE_FULL dump without what the flag adds: the lines that start with '+', and everything from ' |' on in the others"""
+    return [l.split(" |")[0] for l in lines if not l.startswith("+")]
+
+
 def plan_violations(marsrt, d):
     """-> the plan lines that break the I/O invariants, plus a note if the descriptor-only plan differs"""
     hdr = marsfile.parse(d)[0]
     io = set(hdr["inputs"]) | set(hdr["outputs"])
     L = marsrt.describe_plan(d)
+    assert L, "empty plan"  # (a plan the planner's own check rejects fails the load: it must not pass for a plan without violations)
     bad = []
     for l in L:
         if l.startswith("op ") and " view=-" in l:
@@ -73,12 +96,12 @@ def _plain_env(monkeypatch):
 @pytest.mark.parametrize("nchw", [None, True])
 @pytest.mark.parametrize("interior", [False, True])
 def test_int8_graphs(marsrt, monkeypatch, nchw, interior):
-    check_plans(marsrt, monkeypatch, _graphs(graphgen.int8_graph, 4100 + 2 * bool(nchw) + interior, nchw=nchw, interior_outputs=interior))
+    check_plans(marsrt, monkeypatch, corpus_graphs(("int8", nchw, interior)))
 
 
 @pytest.mark.parametrize("interior", [False, True])
 def test_int8_concat_chain_graphs(marsrt, monkeypatch, interior):
-    gs = _graphs(graphgen.int8_graph, 4110 + interior, nchw=True, interior_outputs=interior, concat_chain=True)
+    gs = corpus_graphs(("int8_chain", interior))
     check_plans(marsrt, monkeypatch, gs)
     if not interior:  # the chain is there, and its three concats stay pixels x channels (concat_q) when no graph output pins them
         monkeypatch.setenv("MARS_HIP_FUSION", "1")
@@ -87,18 +110,40 @@ def test_int8_concat_chain_graphs(marsrt, monkeypatch, interior):
 
 @pytest.mark.parametrize("interior", [False, True])
 def test_f32_graphs(marsrt, monkeypatch, interior):
-    check_plans(marsrt, monkeypatch, _graphs(graphgen.f32_graph, 4120 + interior, interior_outputs=interior), f32_modes=(1, 3, 4))
+    check_plans(marsrt, monkeypatch, corpus_graphs(("f32", interior)), f32_modes=CORPUS["f32", interior][3])
 
 
 @pytest.mark.parametrize("interior", [False, True])
 def test_vcat_f32_graphs(marsrt, monkeypatch, interior):
-    gs = _graphs(graphgen.vcat_f32_graph, 4130 + interior, interior_outputs=interior)
-    check_plans(marsrt, monkeypatch, gs, f32_modes=(1, 3, 4))
+    gs = corpus_graphs(("vcat_f32", interior))
+    check_plans(marsrt, monkeypatch, gs, f32_modes=CORPUS["vcat_f32", interior][3])
     # (the pass still runs on these graphs: some concats are read through a view -- rarely where graph outputs sit inside the motif)
     saved = marsrt.get_tuning("f32_mfma")
     try:
         marsrt.set_tuning("f32_mfma", 3)
         assert sum(any(" view=-" in l for l in marsrt.describe_plan(d)) for d in gs) >= (1 if interior else N // 2)
+    finally:
+        marsrt.set_tuning("f32_mfma", saved)
+
+
+@pytest.mark.parametrize("key", sorted(CORPUS, key=str), ids=lambda k: "-".join(str(v) for v in k))
+def test_full_dump_only_adds(marsrt, monkeypatch, key):
+    """MARS_HIP_DESCRIBE_FULL (flags=2) adds fields and lines and alters nothing: stripped of them, the full dump of every graph of the corpus is the
+    default dump, line for line, at every fusion level and float mode -- and it does add (every op line grows, the totals line is there)"""
+    gs, modes = corpus_graphs(key), CORPUS[key][3]
+    saved = marsrt.get_tuning("f32_mfma")
+    try:
+        for mode in modes:
+            if mode is not None:
+                marsrt.set_tuning("f32_mfma", mode)
+            for level in (0, 1, 2):
+                monkeypatch.setenv("MARS_HIP_FUSION", str(level))
+                for gi, d in enumerate(gs):
+                    for defer in (0, 1):
+                        short, full = marsrt.describe_plan(d, flags=defer), marsrt.describe_plan(d, flags=defer | 2)
+                        assert strip_full(full) == short, "graph %d mode %s level %d" % (gi, mode, level)
+                        assert full[-1].startswith("+plan n_ops %d " % sum(l.startswith("op ") for l in short))
+                        assert all(" | err " in l for l in full if l.startswith("op "))
     finally:
         marsrt.set_tuning("f32_mfma", saved)
 

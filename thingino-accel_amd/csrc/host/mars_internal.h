@@ -56,6 +56,11 @@ typedef struct {
     int tail_read;         /* a raw-head decode (mars_hip_detect_heads_device) reads it: a pending tail holds back its writer like a graph output's */
 } mtensor_t;
 
+/* One launch.  The operand model every planner pass and the run path rely on (plan_check enforces it on every plan):
+ *   - a launch READS exactly the tensors t_in[0 .. n_in): add_t - 1, seg_t[0 .. nseg) and vc_t[0 .. vc_n) say which ROLE an entry of t_in
+ *     plays (the folded Add's operand, the segments of a virtual concat, the first inputs of a float one), they name no further operand;
+ *   - a launch WRITES t_out and chain_out[0 .. chain_n), where chain_n != 0 implies t_out == chain_out[chain_n - 1].
+ * Ask through op_reads() / op_writes(); a new operand field must be mirrored into t_in, not scanned for. */
 typedef struct {
     int kind, layer, err;
     int t_in[4], n_in, t_out; /* tensor indices, -1 if none */
@@ -103,9 +108,22 @@ typedef struct {
     void *ev_start; /* profiling: the event that marks this launch's start = the previous launch's ev1 (own ev0 for the first) */
 } mars_op_t;
 
+/* Every environment switch the planner and alloc_batch obey, read in ONE place (plan_switches_read, mars_model.c): a plan is a function of
+ * (file, batch, f32_mfma mode, this record).  build_plan and alloc_batch refresh it when they start; `fusion` is read at load only
+ * (mars_hip_set_fusion changes it afterwards). */
+typedef struct {
+    int fusion; /* MARS_HIP_FUSION, default 1 */
+    unsigned no_fuse_lut : 1, no_nhwc_internal : 1, no_vconcat_q : 1, no_pair_f32 : 1, no_rec : 1, no_zero_tail : 1, no_vconcat_f32 : 1,
+        no_rowpad : 1; /* MARS_HIP_NO_*: set = that pass is off */
+    size_t rec_limit;        /* MARS_HIP_REC_LIMIT: bytes all frames of a tensor may span under 32-bit offsets (rec_pairs, virtual_concat_f32) */
+    size_t vconcat_limit;    /* MARS_HIP_VCONCAT_LIMIT: ... the output of a segmented convolution (alloc_batch) */
+    size_t bottleneck_limit; /* MARS_HIP_BOTTLENECK_LIMIT: largest batch that keeps fused bottlenecks, 0 = no limit (alloc_batch) */
+} plan_switches_t;
+
 typedef struct mars_model_ext {
     mars_model_t pub; /* MUST stay first */
-    int batch, fusion, profiling, deferred;
+    plan_switches_t sw;
+    int batch, profiling, deferred;
     int plan_err;   /* first allocation failure while planning (build_plan returns it; 0 = none) */
     int no_vconcat; /* virtual concat switched off (a batch too large for 32-bit buffer offsets) */
     int no_download; /* mars_hip_set_output_mode(MARS_HIP_OUTPUT_ON_DEVICE): mars_run leaves the graph outputs in HBM */
@@ -167,6 +185,7 @@ MARS_INTERNAL int mars_verbose(void);
 /* mars_model.c */
 MARS_INTERNAL void drop_graph(mars_model_ext_t *m);
 MARS_INTERNAL mars_model_ext_t *mars_live_models(void);
+MARS_INTERNAL void plan_switches_read(plan_switches_t *sw, int at_load);
 MARS_INTERNAL mars_error_t build_plan(mars_model_ext_t *m);
 MARS_INTERNAL mars_error_t upload_params(mars_model_ext_t *m);
 MARS_INTERNAL mars_error_t alloc_batch(mars_model_ext_t *m, int n);
@@ -176,29 +195,35 @@ MARS_INTERNAL size_t shape_numel(const mars_tensor_t *d);
 MARS_INTERNAL size_t reference_buffer_size(const mars_model_ext_t *m);
 MARS_INTERNAL size_t arena_reserve(mars_model_ext_t *m, size_t bytes);
 MARS_INTERNAL void blob_read(const mars_model_ext_t *m, size_t off, size_t n, void *dst);
+MARS_INTERNAL int op_reads(const mars_op_t *o, int t);  /* t is one of t_in[0 .. n_in) */
+MARS_INTERNAL int op_writes(const mars_op_t *o, int t); /* t is t_out or one of chain_out[0 .. chain_n) */
+MARS_INTERNAL size_t planned_stride(const mtensor_t *t);
+MARS_INTERNAL void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p);
+MARS_INTERNAL int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t out_stride);
+/* ... the passes, in the order build_plan calls them (f32: 0 = the int8 form, 1 = the float32 form) */
 MARS_INTERNAL void plan_layer(mars_model_ext_t *m, int li);
-MARS_INTERNAL void nhwc_internal(mars_model_ext_t *m);
-MARS_INTERNAL void virtual_concat_q(mars_model_ext_t *m);
-MARS_INTERNAL void zero_tail_f32(mars_model_ext_t *m);
-MARS_INTERNAL void virtual_concat_f32(mars_model_ext_t *m);
-MARS_INTERNAL void fuse_silu(mars_model_ext_t *m);
+MARS_INTERNAL void fold_silu(mars_model_ext_t *m, int f32);
 MARS_INTERNAL void fuse_lut(mars_model_ext_t *m);
-MARS_INTERNAL void fuse_silu_f32(mars_model_ext_t *m);
-MARS_INTERNAL void elide_concat(mars_model_ext_t *m);
-MARS_INTERNAL void fuse_add(mars_model_ext_t *m);
-MARS_INTERNAL void fuse_add_f32(mars_model_ext_t *m);
-MARS_INTERNAL void rec_pairs(mars_model_ext_t *m);
-MARS_INTERNAL void pair_convs_f32(mars_model_ext_t *m);
-MARS_INTERNAL void trim_concat(mars_model_ext_t *m);
-MARS_INTERNAL int mars_preproc_prepare(int w, int h, int tw, int th); /* mars_preproc.c: gather tables of a letterbox geometry, cached */
-MARS_INTERNAL void fuse_bottleneck(mars_model_ext_t *m);
+MARS_INTERNAL void nhwc_internal(mars_model_ext_t *m);
+MARS_INTERNAL void fold_add(mars_model_ext_t *m, int f32);
 MARS_INTERNAL void virtual_concat(mars_model_ext_t *m);
-MARS_INTERNAL void pair_convs(mars_model_ext_t *m);
+MARS_INTERNAL void elide_concat(mars_model_ext_t *m);
+MARS_INTERNAL void trim_concat(mars_model_ext_t *m);
 MARS_INTERNAL void fuse_pool_chains(mars_model_ext_t *m);
+MARS_INTERNAL void pair_convs(mars_model_ext_t *m);
+MARS_INTERNAL void fuse_bottleneck(mars_model_ext_t *m);
+MARS_INTERNAL void pad_output_rows(mars_model_ext_t *m);
+MARS_INTERNAL void virtual_concat_q(mars_model_ext_t *m);
 MARS_INTERNAL void f32_policy(mars_model_ext_t *m);
+MARS_INTERNAL void zero_tail_f32(mars_model_ext_t *m);
+MARS_INTERNAL void pair_convs_f32(mars_model_ext_t *m);
 MARS_INTERNAL void rec_pairs(mars_model_ext_t *m);
+MARS_INTERNAL void virtual_concat_f32(mars_model_ext_t *m);
+MARS_INTERNAL void plan_check(mars_model_ext_t *m);
 /* mars_run.c */
 MARS_INTERNAL void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8_t *p);
+/* mars_preproc.c */
+MARS_INTERNAL int mars_preproc_prepare(int w, int h, int tw, int th); /* gather tables of a letterbox geometry, cached */
 
 /* detection tail pieces shared with the pipelined I/O (mars_yolo.c) */
 mars_error_t mars_detect_prepare(mars_model_ext_t *m, const int *output_indices, int n_outputs);

@@ -20,6 +20,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/types.h>
 #include <time.h>
 
 #include "mars_internal.h"
@@ -30,6 +31,24 @@ int mars_verbose(void) {
     static int v = -1;
     if (v < 0) v = getenv("MARS_VERBOSE") ? 1 : 0;
     return v;
+}
+
+/* every environment switch of the planner and of alloc_batch, with its default (plan_switches_t) */
+void plan_switches_read(plan_switches_t *sw, int at_load) {
+    const char *e;
+    if (at_load) sw->fusion = (e = getenv("MARS_HIP_FUSION")) ? atoi(e) : 1;
+    sw->no_fuse_lut = getenv("MARS_HIP_NO_FUSE_LUT") != NULL;
+    sw->no_nhwc_internal = getenv("MARS_HIP_NO_NHWC_INTERNAL") != NULL;
+    sw->no_vconcat_q = getenv("MARS_HIP_NO_VCONCAT_Q") != NULL;
+    sw->no_pair_f32 = getenv("MARS_HIP_NO_PAIR_F32") != NULL;
+    sw->no_rec = getenv("MARS_HIP_NO_REC") != NULL;
+    sw->no_zero_tail = getenv("MARS_HIP_NO_ZERO_TAIL") != NULL;
+    sw->no_vconcat_f32 = getenv("MARS_HIP_NO_VCONCAT_F32") != NULL;
+    sw->no_rowpad = getenv("MARS_HIP_NO_ROWPAD") != NULL;
+    /* (tests lower the limits to see the per-batch decisions with small tensors) */
+    sw->rec_limit = (e = getenv("MARS_HIP_REC_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0xfffffff0u;
+    sw->vconcat_limit = (e = getenv("MARS_HIP_VCONCAT_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0x7fffffffu;
+    sw->bottleneck_limit = (e = getenv("MARS_HIP_BOTTLENECK_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : 0;
 }
 
 void drop_graph(mars_model_ext_t *m) {
@@ -55,44 +74,6 @@ const char *mars_get_error_string(mars_error_t err) {
 }
 
 /* ------------------------------------------------------------------- load */
-/* Ragged pixel rows of graph outputs (the 255-channel YOLO heads) are kept at a 16-byte-aligned pitch on the device:
- * the producing convolution then takes the aligned epilogue (16-byte stores straight from registers, every launch
- * form) instead of the LDS-staged copy-out with 8+4+2+1-byte row tails.  Only tensors nothing in the graph reads:
- * their readers are the detection tail (told the pitch) and the download / read entry points (2-D copies), so hosts
- * still see the reference's dense [H][W][C] bytes.  The pad channels carry zero weights; their bytes are never read. */
-static void pad_output_rows(mars_model_ext_t *m) {
-    for (uint32_t i = 0; i < m->pub.header.num_tensors; i++) m->mt[i].pix_c = m->mt[i].pix_stride = 0;
-    if (getenv("MARS_HIP_NO_ROWPAD")) return;
-    for (int i = 0; i < m->n_ops; i++) {
-        mars_op_t *o = &m->ops[i];
-        if (o->kind != OP_CONV_I8 || o->out_nchw || o->out_pix_stride || o->out_ch_off || o->add_t || o->t_out < 0 ||
-            (o->out_c & 15) == 0 || (o->in_c & 15) != 0)
-            continue;
-        mtensor_t *t = &m->mt[o->t_out];
-        const int P = (o->out_c + 15) & ~15;
-        const size_t px = (size_t)o->out_h * o->out_w;
-        if (!t->io_out || t->io_in || P > o->oc_pad || t->bytes != px * (size_t)o->out_c || (px * P) % 256 != 0) continue;
-        int other = 0; /* any other op touching the tensor keeps it dense */
-        for (int j = 0; j < m->n_ops && !other; j++) {
-            if (j == i) continue;
-            if (m->ops[j].t_out == o->t_out) other = 1;
-            for (int k = 0; k < m->ops[j].n_in; k++)
-                if (m->ops[j].t_in[k] == o->t_out) other = 1;
-            for (int k = 0; k < m->ops[j].nseg; k++)
-                if (m->ops[j].seg_t[k] == o->t_out) other = 1;
-            if (m->ops[j].add_t - 1 == o->t_out) other = 1;
-            for (int k = 0; k < m->ops[j].chain_n; k++)
-                if (m->ops[j].chain_out[k] == o->t_out) other = 1;
-        }
-        if (other) continue;
-        o->out_pix_stride = P;
-        o->store_c = P;
-        t->pix_c = o->out_c;
-        t->pix_stride = P;
-        if (px * P > t->extent) t->extent = px * P;
-    }
-}
-
 static void free_device_state(mars_model_ext_t *m) {
     drop_graph(m);
     if (m->act_dev) mhip_free(m->act_dev);
@@ -159,12 +140,13 @@ void mars_free(mars_model_t *model) {
 
 mars_error_t build_plan(mars_model_ext_t *m) {
     const uint32_t nt = m->pub.header.num_tensors, nl = m->pub.header.num_layers;
+    plan_switches_read(&m->sw, 0);
     free_ops(m);
     m->arena_size = 0;
     if (m->arena_host) memset(m->arena_host, 0, m->arena_cap); /* re-plans must not see stale bytes */
     m->scratch_per_frame = 0;
     m->plan_err = MARS_OK;
-    m->plan_f32_mode = mhip_conv_f32_mode(-1);
+    m->plan_f32_mode = mhip_conv_f32_mode(-1); /* (the passes read the stored value) */
     m->blob_mirror_bytes = m->pub.weights_size;
     for (uint32_t i = 0; i < nt; i++) {
         m->mt[i].extent = m->mt[i].bytes;
@@ -179,28 +161,31 @@ mars_error_t build_plan(mars_model_ext_t *m) {
         m->layer_noop[i] = m->n_ops == n0;
     }
     if (m->plan_err != MARS_OK) return (mars_error_t)m->plan_err;
-    if (m->fusion >= 1) {
-        fuse_silu(m);
-        fuse_lut(m); /* (after the SiLU chains: a lone activation layer behind a convolution) */
-        fuse_silu_f32(m);
-        nhwc_internal(m); /* (after the SiLU fold: its intermediates are gone; before Add folding / pairing: they then see NHWC convolutions) */
-        fuse_add(m);
-        fuse_add_f32(m);
+    /* the passes, in order; why each stands where it stands is said here and nowhere else */
+    if (m->sw.fusion >= 1) {
+        fold_silu(m, 0);
+        fuse_lut(m);      /* after the SiLU chains: a SIGMOID that feeds a MUL belongs to them, a lone activation layer is what is left */
+        fold_silu(m, 1);
+        nhwc_internal(m); /* after the SiLU fold: its intermediates are gone; before Add folding / pairing: they then see NHWC convolutions */
+        fold_add(m, 0);
+        fold_add(m, 1);
         if (!m->no_vconcat) virtual_concat(m);
-        elide_concat(m);
+        elide_concat(m);  /* after virtual_concat: only the concats that stay materialised get producers that write slices */
         trim_concat(m);
-        fuse_pool_chains(m);
+        fuse_pool_chains(m); /* the first pass that sets chain_out: from here on op_writes() is more than t_out */
         pair_convs(m);
-        if (m->fusion >= 2 && !m->no_bottleneck) fuse_bottleneck(m); /* opt-in (level 2); after pairing: a paired launch stays a pair */
+        if (m->sw.fusion >= 2 && !m->no_bottleneck) fuse_bottleneck(m); /* opt-in (level 2); after pairing: a paired launch stays a pair */
         pad_output_rows(m);
-        virtual_concat_q(m); /* (last: it splits a convolution in two launches over one output tensor) */
+        virtual_concat_q(m); /* last of the int8 passes: it splits a convolution in two launches over one output tensor */
+    } else {
+        nhwc_internal(m); /* only resets what a plan at another level left in the tensors */
     }
-    if (m->fusion < 1) nhwc_internal(m); /* (resets the tensors' flags) */
     f32_policy(m);
-    zero_tail_f32(m); /* (before pairing: a pair shares its input, hence its limit; resets the flags at fusion level 0) */
-    if (m->fusion >= 1) pair_convs_f32(m); /* (after f32_policy: a pair shares one kernel choice) */
-    rec_pairs(m); /* (fusion >= 1 only; resets the tensors' record flags in any case) */
-    virtual_concat_f32(m); /* (last: it replaces launches; shares rec_pairs' per-batch decision) */
+    zero_tail_f32(m); /* before pairing: a pair shares its input, hence its limit; resets its flags at fusion level 0 */
+    if (m->sw.fusion >= 1) pair_convs_f32(m); /* after f32_policy: a pair shares one kernel choice */
+    rec_pairs(m);          /* fusion >= 1 only; resets the tensors' record flags in any case */
+    virtual_concat_f32(m); /* last: it replaces launches; shares rec_pairs' per-batch decision */
+    if (m->plan_err == MARS_OK) plan_check(m);
     return (mars_error_t)m->plan_err;
 }
 
@@ -228,9 +213,10 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
     const uint32_t nt = m->pub.header.num_tensors;
     if (m->pipe) mars_hip_pipe_close(&m->pub); /* its slots were sized for the old batch */
     if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
-    /* tests exercise the two fall-backs below with a small batch: limits from the environment, read once per call */
-    const char *env_v = getenv("MARS_HIP_VCONCAT_LIMIT"), *env_b = getenv("MARS_HIP_BOTTLENECK_LIMIT");
-    const size_t vlim = env_v ? (size_t)strtoull(env_v, NULL, 0) : (size_t)0x7fffffffu, blim = env_b ? (size_t)strtoull(env_b, NULL, 0) : 0;
+    plan_switches_read(&m->sw, 0);
+    /* tests exercise the two fall-backs below with a small batch: their limits are the ones read just now (a re-plan below reads the record
+     * again, these two stay) */
+    const size_t vlim = m->sw.vconcat_limit, blim = m->sw.bottleneck_limit;
     /* the two batch-dependent fall-backs are decided afresh for every batch (they used to stick once a large
      * batch had switched them on): plan again with the fusions allowed, the checks below take them back if need be */
     /* (record-format pairs, rec_pairs: chosen per batch too -- plan again when a chosen pair would not fit this batch, or one left
@@ -249,9 +235,7 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
         for (int i = 0; i < m->n_ops; i++) {
             const mars_op_t *op = &m->ops[i];
             if (op->kind != OP_CONV_I8 || op->nseg < 2 || op->t_out < 0) continue;
-            const mtensor_t *t = &m->mt[op->t_out];
-            const size_t stride = ALIGN_UP(t->extent > t->bytes ? t->extent : t->bytes, 256);
-            if (stride * (size_t)n > vlim) {
+            if (planned_stride(&m->mt[op->t_out]) * (size_t)n > vlim) {
                 m->no_vconcat = 1;
                 mars_error_t e = build_plan(m);
                 if (e == MARS_OK) e = upload_params(m);
@@ -262,22 +246,12 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
     /* fused bottlenecks were accepted on geometry alone (one frame, no strides): the launcher's limits also depend on the
      * batch (32-bit output offsets, tile count).  The 1x1 has left the plan, so a launch that fails would have no
      * fallback: check every fused launch against THIS batch and plan again without the fusion if one does not fit */
-    if (m->fusion >= 2 && !m->no_bottleneck)
+    if (m->sw.fusion >= 2 && !m->no_bottleneck)
         for (int i = 0; i < m->n_ops; i++) {
             const mars_op_t *op = &m->ops[i];
             if (op->kind != OP_CONV_I8 || !op->pre || op->t_out < 0) continue;
-            const mtensor_t *t = &m->mt[op->t_out];
-            mhip_conv_i8_t p;
-            memset(&p, 0, sizeof(p));
-            p.frames = n; p.in_c = op->in_c; p.in_h = op->in_h; p.in_w = op->in_w; p.out_h = op->out_h; p.out_w = op->out_w;
-            p.out_c = op->store_c ? op->store_c : op->out_c; p.kh = op->kh; p.kw = op->kw; p.stride_h = op->sh; p.stride_w = op->sw;
-            p.pad_top = op->pt; p.pad_left = op->pl; p.row_pad = op->row_pad; p.oc_pad = op->oc_pad; p.safe = op->safe;
-            p.out_pix_stride = op->out_pix_stride; p.out_ch_off = op->out_ch_off;
-            p.out_stride = ALIGN_UP(t->extent > t->bytes ? t->extent : t->bytes, 256);
-            p.in_stride = op->t_in[0] >= 0 ? ALIGN_UP(m->mt[op->t_in[0]].extent > m->mt[op->t_in[0]].bytes ? m->mt[op->t_in[0]].extent : m->mt[op->t_in[0]].bytes, 256) : 0;
-            p.pre_w = (const int8_t *)m; p.pre_bias = (const int32_t *)m; p.pre_lut2 = (const uint8_t *)m; p.lut2 = (const uint8_t *)m;
-            p.lut = (const uint8_t *)m;
-            if (!mhip_conv_i8_pre_ok(&p) || (blim && (size_t)n > blim)) {
+            const size_t in_stride = op->t_in[0] >= 0 ? planned_stride(&m->mt[op->t_in[0]]) : 0;
+            if (!conv_i8_pre_fits(op, n, in_stride, planned_stride(&m->mt[op->t_out])) || (blim && (size_t)n > blim)) {
                 m->no_bottleneck = 1;
                 mars_error_t e = build_plan(m);
                 if (e == MARS_OK) e = upload_params(m);
@@ -290,8 +264,7 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
     for (uint32_t i = 0; i < nt; i++) {
         mtensor_t *t = &m->mt[i];
         if (t->is_weight || !t->needed) continue;
-        t->stride = ALIGN_UP(t->extent > t->bytes ? t->extent : t->bytes, 256);
-        if (t->stride == 0) t->stride = 256;
+        t->stride = planned_stride(t);
         per_frame += t->stride;
     }
     m->act_bytes = per_frame * (size_t)n;
@@ -366,7 +339,7 @@ static mars_error_t load_host(const void *data, size_t size, unsigned flags, mar
     mars_model_ext_t *m = (mars_model_ext_t *)calloc(1, sizeof(*m));
     if (!m) return MARS_ERR_ALLOC_FAILED;
     m->pub.header = h;
-    m->fusion = getenv("MARS_HIP_FUSION") ? atoi(getenv("MARS_HIP_FUSION")) : 1;
+    plan_switches_read(&m->sw, 1);
     m->deferred = deferred;
     m->pub.tensors = (mars_runtime_tensor_t *)calloc(h.num_tensors ? h.num_tensors : 1, sizeof(mars_runtime_tensor_t));
     m->pub.layers = (mars_runtime_layer_t *)calloc(h.num_layers ? h.num_layers : 1, sizeof(mars_runtime_layer_t));
@@ -431,16 +404,43 @@ mars_error_t mars_hip_load_memory_ex(const void *data, size_t size, unsigned fla
     return MARS_OK;
 }
 
+/* MARS_HIP_DESCRIBE_FULL: every scalar field of a launch that the run path reads, appended to its line at k (pointers, events and timings are not plan) */
+static int describe_op_full(const mars_op_t *o, char *line, size_t cap, int k) {
+#define ADD(...) k += snprintf(line + k, cap - (size_t)k, __VA_ARGS__)
+    ADD(" | err %d in %dx%dx%d out %dx%dx%d k %dx%d s %dx%d p %d,%d", o->err, o->in_h, o->in_w, o->in_c, o->out_h, o->out_w, o->out_c, o->kh, o->kw, o->sh, o->sw, o->pt, o->pl);
+    ADD(" nchw %d out_nchw %d relu %d is_mul %d is_f32 %d leaky %d safe %d silu %d f32_exact %d variant %d", o->nchw, o->out_nchw, o->relu, o->is_mul, o->is_f32, o->leaky,
+        o->safe, o->silu_f32, o->f32_exact, o->variant);
+    ADD(" row_pad %d oc_pad %d c_pad %d store_c %d ch_off %d out_ch_off %d out_pix_stride %d in_byte_off %zu out_byte_off %zu scale %dx%d bn_n %d n %zu", o->row_pad,
+        o->oc_pad, o->c_pad, o->store_c, o->ch_off, o->out_ch_off, o->out_pix_stride, o->in_byte_off, o->out_byte_off, o->scale_h, o->scale_w, o->bn_n, o->n);
+    ADD(" k_limit %d rows_only %d pair_next %d in_rec %d out_rec %d vc %d,%d,%d:", o->k_limit, o->rows_only, o->pair_next, o->in_rec, o->out_rec, o->vc_n, o->vc_run, o->vc_shift);
+    for (int q = 0; q < o->vc_n && q < 3; q++) ADD(" %d", o->vc_t[q]);
+    ADD(" add %d %a %a %a seg %d up %d:", o->add_t, (double)o->add_s_conv, (double)o->add_s_other, (double)o->add_inv, o->nseg, o->seg_up);
+    for (int q = 0; q < o->nseg && q < 4; q++) ADD(" %d/%d", o->seg_t[q], o->seg_c[q]);
+    ADD(" chain %d:", o->chain_n);
+    for (int q = 0; q < o->chain_n && q < 3; q++) ADD(" %d", o->chain_out[q]);
+    ADD(" cs %a f %a %a %a", (double)o->cs, (double)o->f0, (double)o->f1, (double)o->f2);
+    ADD(" w_off %zd b_off %zd lut_off %zd lut2_off %zd s_off %zd w2_off %zd rows %d planes %d w3_off %zd stem %d blob %zd %zd", (ssize_t)o->w_off, (ssize_t)o->b_off,
+        (ssize_t)o->lut_off, (ssize_t)o->lut2_off, (ssize_t)o->s_off, (ssize_t)o->w2_off, o->w2_rows, o->w2_planes, (ssize_t)o->w3_off, o->w3_stem, (ssize_t)o->w_blob_off[0],
+        (ssize_t)o->w_blob_off[1]);
+    ADD(" pre %d", o->pre);
+    if (o->pre) ADD(" %zd %zd %zd %a", (ssize_t)o->pre_w_off, (ssize_t)o->pre_b_off, (ssize_t)o->pre_lut2_off, (double)o->pre_cs);
+    ADD(" macs %a bytes %a prof_kind %d", o->macs, o->bytes, o->prof_kind);
+#undef ADD
+    return k;
+}
+
 /* The plan of a file as text, WITHOUT a device (tests of the planner on the CPU: which layers fuse, which tensors are kept pixels x channels,
  * which K loops are cut ...): one line per launch -- "op I layer L KIND in T.. out T" + the flags that are set -- and one per tensor that is not
- * held as tagged.  Returns the length needed (the text is cut at cap); 0 on a file the loader rejects. */
+ * held as tagged.  Returns the length needed (the text is cut at cap); 0 on a file the loader rejects.
+ * MARS_HIP_DESCRIBE_FULL adds, and alters nothing: " | ..." behind those lines and whole lines that start with "+" (include/mars_hip.h). */
 size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, char *out, size_t cap) {
     static const char *const kinds[] = {"conv_i8", "conv_f32", "relu_bytes", "lut_i8", "binary_i8", "sigmoid_f32", "binary_f32", "relu_f32", "bn",
                                         "maxpool", "concat_slice", "upsample", "upsample_q", "maxpool_q", "concat_q", "conv_f32_vhead", "fail"};
     mars_model_ext_t *m = NULL;
-    if (load_host(data, size, flags, &m) != MARS_OK) return 0;
+    const int full = (flags & MARS_HIP_DESCRIBE_FULL) != 0;
+    if (load_host(data, size, flags & ~MARS_HIP_DESCRIBE_FULL, &m) != MARS_OK) return 0;
     size_t n = 0;
-    char line[512];
+    char line[4096];
 #define EMIT() do { const size_t l = strlen(line); if (out && n < cap) memcpy(out + n, line, n + l <= cap ? l : cap - n); n += l; } while (0)
     for (int i = 0; i < m->n_ops; i++) {
         const mars_op_t *o = &m->ops[i];
@@ -456,14 +456,30 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
         FLAG(o->rows_only, " rows_only=%d", o->rows_only); FLAG(o->out_byte_off, " out_off=%zu", o->out_byte_off); FLAG(o->chain_n, " chain=%d", o->chain_n);
         FLAG(o->out_pix_stride, " pix_stride=%d", o->out_pix_stride); FLAG(o->kind == OP_FAIL, " err=%d", o->err);
 #undef FLAG
+        if (full) k = describe_op_full(o, line, sizeof line, k);
         snprintf(line + k, sizeof line - (size_t)k, "\n");
         EMIT();
     }
     for (uint32_t t = 0; t < m->pub.header.num_tensors; t++) {
         const mtensor_t *mt = &m->mt[t];
-        if (!mt->nhwc_c && !mt->partial && !mt->zero_from && !mt->rec_c && !mt->pix_stride) continue;
-        snprintf(line, sizeof line, "tensor %u nhwc_c %d pitch %d partial %d zero_from %zu rec_c %d pix_stride %d\n", t, mt->nhwc_c, mt->nhwc_pitch, mt->partial,
-                 mt->zero_from, mt->rec_c, mt->pix_stride);
+        const int listed = mt->nhwc_c || mt->partial || mt->zero_from || mt->rec_c || mt->pix_stride;
+        if (!listed && !(full && mt->needed)) continue;
+        int k = listed ? snprintf(line, sizeof line, "tensor %u nhwc_c %d pitch %d partial %d zero_from %zu rec_c %d pix_stride %d", t, mt->nhwc_c, mt->nhwc_pitch,
+                                  mt->partial, mt->zero_from, mt->rec_c, mt->pix_stride)
+                       : snprintf(line, sizeof line, "+tensor %u", t);
+        if (full)
+            k += snprintf(line + k, sizeof line - (size_t)k, " | bytes %zu extent %zu needed %d tail_read %d weight %d io %d,%d pix_c %d rec_hw %d nhwc_hw %d", mt->bytes,
+                          mt->extent, mt->needed, mt->tail_read, mt->is_weight, mt->io_in, mt->io_out, mt->pix_c, mt->rec_hw, mt->nhwc_hw);
+        snprintf(line + k, sizeof line - (size_t)k, "\n");
+        EMIT();
+    }
+    if (full) {
+        const plan_switches_t *w = &m->sw;
+        snprintf(line, sizeof line, "+plan n_ops %d arena_size %zu scratch_per_frame %zu blob_mirror_bytes %zu rec_max_frames %zu rec_skipped %d f32_mode %d | fusion %d"
+                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d rec_limit %zu"
+                 " vconcat_limit %zu bottleneck_limit %zu\n", m->n_ops, m->arena_size, m->scratch_per_frame, m->blob_mirror_bytes, m->rec_max_frames, m->rec_skipped,
+                 m->plan_f32_mode, w->fusion, w->no_fuse_lut, w->no_nhwc_internal, w->no_vconcat_q, w->no_pair_f32, w->no_rec, w->no_zero_tail, w->no_vconcat_f32,
+                 w->no_rowpad, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
         EMIT();
     }
 #undef EMIT

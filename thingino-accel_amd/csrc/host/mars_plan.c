@@ -3,6 +3,8 @@
  * mirrors: src/mars/mars_runtime.c:511-1224), the host arithmetic they share, the parameter arena, and the fusion passes
  * (SiLU tables, residual Adds, virtual / zero-copy concats, paired launches, pool chains, the float32 policy).
  * Split out of mars_model.c in round 4; loader: mars_model.c, run paths: mars_run.c.
+ * The passes ask who reads and writes a tensor through ONE layer of helpers (use-def helpers below), on the operand model stated at
+ * mars_op_t (mars_internal.h) and checked by plan_check; the environment switches they obey are m->sw (plan_switches_t).
  */
 #include <math.h>
 #include <stdio.h>
@@ -270,7 +272,7 @@ static void plan_conv(mars_model_ext_t *m, int li) {
          * planes for conv_f32_split; mode 4 = three planes for conv_f32_split; modes 0 - 2 read neither (no dead planes in
          * the arena, its upload and its multi-GPU broadcast). */
         {
-            const int mode = mhip_conv_f32_mode(-1);
+            const int mode = m->plan_f32_mode;
             size_t n3 = 0;
             int stem = 0;
             if (mode == 3 && sh == sw && pt == pl) {
@@ -580,117 +582,193 @@ void plan_layer(mars_model_ext_t *m, int li) {
     }
 }
 
+/* ---------------------------------------------------------- use-def helpers
+ * The operand model (mars_op_t): a launch reads t_in[0 .. n_in) and writes t_out + chain_out[0 .. chain_n).  Two facts let every pass use
+ * the same helpers, whatever arrays its hand-written loops used to scan:
+ *  (1) seg_t / add_t / vc_t name entries of t_in once more (plan_check), so scanning them next to t_in finds nothing new;
+ *  (2) chain_n == 0 in every op until fuse_pool_chains has run, so before it `o->t_out == t` and op_writes(o, t) agree. */
+int op_reads(const mars_op_t *o, int t) {
+    for (int k = 0; k < o->n_in; k++)
+        if (o->t_in[k] == t) return 1;
+    return 0;
+}
+int op_writes(const mars_op_t *o, int t) {
+    if (o->t_out == t) return 1;
+    for (int k = 0; k < o->chain_n; k++)
+        if (o->chain_out[k] == t) return 1;
+    return 0;
+}
+
+/* readers[t] = operand slots that read tensor t (an op that reads it twice counts twice), writers[t] = ops that write it; both for the caller to
+ * free (one allocation: free(readers)).  A pass that rewrites ops keeps the counts it still needs current itself.  0 = out of memory. */
+static int use_counts(const mars_model_ext_t *m, int **readers, int **writers) {
+    const size_t nt = (size_t)m->pub.header.num_tensors + 1;
+    int *c = (int *)calloc(2 * nt, sizeof(int));
+    if (!c) return 0;
+    for (int i = 0; i < m->n_ops; i++) {
+        const mars_op_t *o = &m->ops[i];
+        for (int k = 0; k < o->n_in; k++)
+            if (o->t_in[k] >= 0) c[o->t_in[k]]++;
+        if (o->t_out >= 0) c[nt + (size_t)o->t_out]++;
+        for (int k = 0; k < o->chain_n; k++) /* (the chain's last stage is t_out: counted above) */
+            if (o->chain_out[k] >= 0 && o->chain_out[k] != o->t_out) c[nt + (size_t)o->chain_out[k]]++;
+    }
+    *readers = c;
+    *writers = c + nt;
+    return 1;
+}
+
+/* the last op in front of op `before` whose t_out is t (THE writer where writers[t] == 1), or -1 */
+static int writer_before(const mars_model_ext_t *m, int t, int before) {
+    for (int k = before - 1; k >= 0; k--)
+        if (m->ops[k].t_out == t) return k;
+    return -1;
+}
+
+enum { USE_READ = 1, USE_WRITE = 2 };
+/* does an op in [lo, hi) read / write tensor t?  (ops a pass has marked dead, kind -1, count like any other) */
+static int touched_between(const mars_model_ext_t *m, int lo, int hi, int t, int how) {
+    for (int k = lo < 0 ? 0 : lo; k < hi && k < m->n_ops; k++)
+        if (((how & USE_READ) && op_reads(&m->ops[k], t)) || ((how & USE_WRITE) && op_writes(&m->ops[k], t))) return 1;
+    return 0;
+}
+/* does an op outside [lo, hi] read or write tensor t? */
+static int touched_by_other(const mars_model_ext_t *m, int t, int lo, int hi) {
+    return touched_between(m, 0, lo, t, USE_READ | USE_WRITE) || touched_between(m, hi + 1, m->n_ops, t, USE_READ | USE_WRITE);
+}
+
+/* closes a pass that marked ops dead (kind = -1) */
+static void drop_dead_ops(mars_model_ext_t *m) {
+    int w = 0;
+    for (int i = 0; i < m->n_ops; i++)
+        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
+    m->n_ops = w;
+}
+
+/* device bytes per frame a tensor will get (alloc_batch).  Every tensor a launch touches has extent > 0, so the 256 of an empty one only shows for
+ * a graph input / output that no layer uses. */
+size_t planned_stride(const mtensor_t *t) {
+    size_t s = ALIGN_UP(t->extent > t->bytes ? t->extent : t->bytes, 256);
+    return s ? s : 256;
+}
+
+/* the half-step form of a convolution's fused 256-entry table, where its scale allows it: index k = trunc(2 * acc * cs) in [-256, 255] determines
+ * round-half-away(acc * cs) = (k >= 0 ? (k+1)>>1 : -((1-k)>>1)) exactly (conv_i8.hip, requant_pack FAST); the ReLU clamp folds in.
+ * (tab may point into the arena: it is read before the arena can move) */
+static void lut2_from_lut(mars_model_ext_t *m, mars_op_t *c, const int8_t *tab) {
+    if (!mhip_conv_i8_lut2_ok(c->cs)) return;
+    int8_t tab2[512];
+    for (int k = -256; k < 256; k++) {
+        int r = k >= 0 ? (k + 1) >> 1 : -((1 - k) >> 1);
+        const int lo = c->relu ? 0 : -128;
+        r = r < lo ? lo : (r > 127 ? 127 : r);
+        tab2[k + 256] = tab[r + 128];
+    }
+    c->lut2_off = arena_reserve(m, 512);
+    if (c->lut2_off != NO_OFF) memcpy(m->arena_host + c->lut2_off, tab2, 512);
+}
+
+/* the geometry half of a conv_i8 launch record (conv_i8_params adds addresses, strides and the epilogue's operands) */
+void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p) {
+    memset(p, 0, sizeof(*p));
+    p->frames = frames;
+    p->in_c = op->in_c; p->in_h = op->in_h; p->in_w = op->in_w;
+    p->out_h = op->out_h; p->out_w = op->out_w; p->out_c = op->store_c ? op->store_c : op->out_c;
+    p->kh = op->kh; p->kw = op->kw; p->stride_h = op->sh; p->stride_w = op->sw; p->pad_top = op->pt; p->pad_left = op->pl;
+    p->row_pad = op->row_pad; p->oc_pad = op->oc_pad; p->safe = op->safe;
+    p->out_pix_stride = op->out_pix_stride; p->out_ch_off = op->out_ch_off;
+}
+/* does the device code take convolution `op` with a 1 x 1 + SiLU folded in front of it (fuse_bottleneck), at this batch and these frame strides?
+ * It decides on geometry: the operands only need to be non-null */
+int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t out_stride) {
+    mhip_conv_i8_t p;
+    conv_i8_geometry(op, frames, &p);
+    p.in_stride = in_stride; p.out_stride = out_stride;
+    p.pre_w = (const int8_t *)op; p.pre_bias = (const int32_t *)op; p.pre_lut2 = (const uint8_t *)op; p.lut2 = (const uint8_t *)op;
+    p.lut = (const uint8_t *)op;
+    return mhip_conv_i8_pre_ok(&p);
+}
+
 /* ------------------------------------------------------------------ fusion
  * conv -> sigmoid -> mul (SiLU as exported to ONNX) collapses into the conv
  * epilogue: every value of the chain is a function of the conv's int8 result
  * q1 alone, so lut[q1] = mul(q1, sigmoid(q1)) computed on the host with the
  * reference's own float steps is bit-identical.
- * Only done when q1 and sigmoid(q1) have no other reader and are not outputs. */
-void fuse_silu(mars_model_ext_t *m) {
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
-        if (m->ops[i].t_out >= 0) writers[m->ops[i].t_out]++;
-    }
+ * Only done when q1 and sigmoid(q1) have no other reader and are not outputs.
+ * match_silu: ops i .. i + 2 are such a chain, int8 or float32 -> q = {q1, q2, q3}, fwd = the MUL's operand order. */
+static int match_silu(const mars_model_ext_t *m, int i, int f32, const int *readers, const int *writers, int q[3], int *fwd) {
+    const mars_op_t *c = &m->ops[i], *s = c + 1, *mu = c + 2;
+    if (c->kind != (f32 ? OP_CONV_F32 : OP_CONV_I8) || s->kind != (f32 ? OP_SIGMOID_F32 : OP_LUT_I8) || mu->kind != (f32 ? OP_BINARY_F32 : OP_BINARY_I8) || !mu->is_mul)
+        return 0;
+    if (!f32 && m->pub.layers[s->layer].desc.type != MARS_LAYER_SIGMOID) return 0;
+    const int q1 = q[0] = c->t_out, q2 = q[1] = s->t_out, q3 = q[2] = mu->t_out;
+    if (s->t_in[0] != q1 || q1 == q2 || q2 == q3 || q1 == q3) return 0;
+    *fwd = mu->t_in[0] == q1 && mu->t_in[1] == q2;
+    if (!*fwd && !(mu->t_in[0] == q2 && mu->t_in[1] == q1)) return 0;
+    /* redirecting the result onto one of the convolution's own inputs would make a parallel launch run in place */
+    if (f32 ? q3 == c->t_in[0] || m->mt[q3].is_weight : op_reads(c, q3)) return 0;
+    if (readers[q1] != 2 || readers[q2] != 1 || writers[q1] != 1 || writers[q2] != 1 || writers[q3] != 1) return 0;
+    if (m->mt[q1].io_out || m->mt[q2].io_out || m->mt[q1].io_in || m->mt[q2].io_in) return 0;
+    const size_t n1 = (size_t)c->out_h * c->out_w * c->out_c;
+    return s->n == n1 && mu->n == n1; /* the chain must cover exactly the conv's result */
+}
+
+/* float32 form of the same chain: conv_f32 -> SIGMOID (float, :742-749) -> MUL (float, :807-816).  The epilogue evaluates
+ * s = 1.0f / (1.0f + expf(-v)), out = v * s with the reference's roundings and this image's libm expf (expf_exact.h), so
+ * the fused result is the same float bit for bit; the two intermediates are never written (5 of the 7 float passes over
+ * the tensor disappear: the element-wise layers were 36 % of the float32 graph's time). */
+void fold_silu(mars_model_ext_t *m, int f32) {
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
     for (int i = 0; i + 2 < m->n_ops; i++) {
-        mars_op_t *c = &m->ops[i], *s = &m->ops[i + 1], *mu = &m->ops[i + 2];
-        if (c->kind != OP_CONV_I8 || s->kind != OP_LUT_I8 || mu->kind != OP_BINARY_I8 || !mu->is_mul) continue;
-        if (m->pub.layers[s->layer].desc.type != MARS_LAYER_SIGMOID) continue;
-        const int q1 = c->t_out, q2 = s->t_out, q3 = mu->t_out;
-        if (s->t_in[0] != q1) continue;
-        const int fwd = mu->t_in[0] == q1 && mu->t_in[1] == q2, rev = mu->t_in[0] == q2 && mu->t_in[1] == q1;
-        if (!fwd && !rev) continue;
-        if (q1 == q2 || q2 == q3 || q1 == q3) continue;
-        { /* redirecting the result onto one of the convolution's own inputs would make a parallel launch run in place */
-            int inplace = 0;
-            for (int k = 0; k < c->n_in; k++)
-                if (c->t_in[k] == q3) inplace = 1;
-            if (inplace) continue;
-        }
-        if (readers[q1] != 2 || readers[q2] != 1 || writers[q1] != 1 || writers[q2] != 1 || writers[q3] != 1) continue;
-        if (m->mt[q1].io_out || m->mt[q2].io_out || m->mt[q1].io_in || m->mt[q2].io_in) continue;
+        mars_op_t *c = &m->ops[i];
+        int q[3], fwd;
+        if (!match_silu(m, i, f32, readers, writers, q, &fwd)) continue;
         const size_t n1 = (size_t)c->out_h * c->out_w * c->out_c;
-        if (s->n != n1 || mu->n != n1) continue; /* the chain must cover exactly the conv's result */
-        const mars_tensor_t *d1 = &m->pub.tensors[q1].desc, *d2 = &m->pub.tensors[q2].desc, *d3 = &m->pub.tensors[q3].desc;
-        int8_t tab[256];
-        for (int q = -128; q < 128; q++) {
-            int sg = sigmoid_q(q, d1->scale, d2->scale);
-            tab[q + 128] = (int8_t)(fwd ? binary_q(1, q, sg, d1->scale, d2->scale, d3->scale)
-                                        : binary_q(1, sg, q, d2->scale, d1->scale, d3->scale));
-        }
-        c->lut_off = lut_i8(m, tab);
-        if (mhip_conv_i8_lut2_ok(c->cs)) {
-            /* half-step form: index k = trunc(2 * acc * cs) in [-256, 255] determines round-half-away(acc * cs) =
-             * (k >= 0 ? (k+1)>>1 : -((1-k)>>1)) exactly (conv_i8.hip, requant_pack FAST); the ReLU clamp folds in */
-            int8_t tab2[512];
-            for (int k = -256; k < 256; k++) {
-                int r = k >= 0 ? (k + 1) >> 1 : -((1 - k) >> 1);
-                const int lo = c->relu ? 0 : -128;
-                r = r < lo ? lo : (r > 127 ? 127 : r);
-                tab2[k + 256] = tab[r + 128];
+        if (f32) {
+            c->silu_f32 = 1;
+        } else {
+            const mars_tensor_t *d1 = &m->pub.tensors[q[0]].desc, *d2 = &m->pub.tensors[q[1]].desc, *d3 = &m->pub.tensors[q[2]].desc;
+            int8_t tab[256];
+            for (int v = -128; v < 128; v++) {
+                int sg = sigmoid_q(v, d1->scale, d2->scale);
+                tab[v + 128] = (int8_t)(fwd ? binary_q(1, v, sg, d1->scale, d2->scale, d3->scale)
+                                            : binary_q(1, sg, v, d2->scale, d1->scale, d3->scale));
             }
-            c->lut2_off = arena_reserve(m, 512);
-            if (c->lut2_off != NO_OFF) memcpy(m->arena_host + c->lut2_off, tab2, 512);
+            c->lut_off = lut_i8(m, tab);
+            lut2_from_lut(m, c, tab);
         }
-        c->t_out = q3;
-        c->bytes += 0; /* same bytes written, to q3 instead of q1 */
-        touch(m, q3, n1);
-        m->mt[q1].needed = 0;
-        m->mt[q2].needed = 0;
+        c->t_out = q[2]; /* same bytes written, to q3 instead of q1 */
+        touch(m, q[2], n1 * (f32 ? 4 : 1));
+        m->mt[q[0]].needed = 0;
+        m->mt[q[1]].needed = 0;
         /* drop the two element-wise ops */
         memmove(&m->ops[i + 1], &m->ops[i + 3], (size_t)(m->n_ops - i - 3) * sizeof(mars_op_t));
         m->n_ops -= 2;
     }
     free(readers);
-    free(writers);
 }
 
 /* A single int8 activation layer behind a convolution (RELU / RELU6 / LEAKY_RELU / SIGMOID as their own layers: the shipped tiny_160_int8.mars,
  * any exporter that does not fold them): the layer is a 256-entry map of the convolution's int8 result (plan_unary builds it), which is what the
- * convolution's fused table applies in its epilogue -- the same bytes, one launch and two passes over the tensor less.  Runs after fuse_silu (a
- * SIGMOID that feeds a MUL belongs to that chain).  Conditions as there: the convolution's result has no other reader and is no graph tensor. */
+ * convolution's fused table applies in its epilogue -- the same bytes, one launch and two passes over the tensor less.
+ * Conditions as for the SiLU chain: the convolution's result has no other reader and is no graph tensor. */
 void fuse_lut(mars_model_ext_t *m) {
-    if (getenv("MARS_HIP_NO_FUSE_LUT")) return;
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
-        if (m->ops[i].t_out >= 0) writers[m->ops[i].t_out]++;
-    }
+    if (m->sw.no_fuse_lut) return;
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
     for (int i = 0; i + 1 < m->n_ops; i++) {
         mars_op_t *c = &m->ops[i], *s = &m->ops[i + 1];
         if (c->kind != OP_CONV_I8 || s->kind != OP_LUT_I8 || c->lut_off != NO_OFF || s->lut_off == NO_OFF) continue;
         const int q1 = c->t_out, q2 = s->t_out;
         if (q1 < 0 || q2 < 0 || s->t_in[0] != q1 || q1 == q2) continue;
-        int inplace = 0; /* redirecting the result onto one of the convolution's own inputs would make a parallel launch run in place */
-        for (int k = 0; k < c->n_in; k++)
-            if (c->t_in[k] == q2) inplace = 1;
-        if (inplace) continue;
+        if (op_reads(c, q2)) continue; /* redirecting the result onto one of the convolution's own inputs would make a parallel launch run in place */
         if (readers[q1] != 1 || writers[q1] != 1 || writers[q2] != 1 || m->mt[q1].io_out || m->mt[q1].io_in || m->mt[q1].is_weight || m->mt[q2].is_weight) continue;
         const size_t n1 = (size_t)c->out_h * c->out_w * c->out_c;
         if (s->n != n1 || m->mt[q2].bytes < n1) continue; /* the layer must cover exactly the convolution's result */
         if (m->pub.tensors[q1].desc.dtype != MARS_DTYPE_INT8 || m->pub.tensors[q2].desc.dtype != MARS_DTYPE_INT8) continue;
-        const int8_t *tab = (const int8_t *)(m->arena_host + s->lut_off);
         c->lut_off = s->lut_off;
-        if (mhip_conv_i8_lut2_ok(c->cs)) { /* the half-step form, as fuse_silu builds it (the ReLU clamp folds in) */
-            int8_t tab2[512];
-            for (int k = -256; k < 256; k++) {
-                int r = k >= 0 ? (k + 1) >> 1 : -((1 - k) >> 1);
-                const int lo = c->relu ? 0 : -128;
-                r = r < lo ? lo : (r > 127 ? 127 : r);
-                tab2[k + 256] = tab[r + 128];
-            }
-            c->lut2_off = arena_reserve(m, 512);
-            if (c->lut2_off != NO_OFF) memcpy(m->arena_host + c->lut2_off, tab2, 512);
-            c = &m->ops[i]; /* (arena_reserve may move the host image, not the ops) */
-        }
+        lut2_from_lut(m, c, (const int8_t *)(m->arena_host + s->lut_off));
         c->t_out = q2;
         touch(m, q2, n1);
         m->mt[q1].needed = 0;
@@ -698,43 +776,6 @@ void fuse_lut(mars_model_ext_t *m) {
         m->n_ops -= 1;
     }
     free(readers);
-    free(writers);
-}
-
-/* float32 form of the same chain: conv_f32 -> SIGMOID (float, :742-749) -> MUL (float, :807-816).  The epilogue evaluates
- * s = 1.0f / (1.0f + expf(-v)), out = v * s with the reference's roundings and this image's libm expf (expf_exact.h), so
- * the fused result is the same float bit for bit; the two intermediates are never written (5 of the 7 float passes over
- * the tensor disappear: the element-wise layers were 36 % of the float32 graph's time). */
-void fuse_silu_f32(mars_model_ext_t *m) {
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
-        if (m->ops[i].t_out >= 0) writers[m->ops[i].t_out]++;
-    }
-    for (int i = 0; i + 2 < m->n_ops; i++) {
-        mars_op_t *c = &m->ops[i], *s = &m->ops[i + 1], *mu = &m->ops[i + 2];
-        if (c->kind != OP_CONV_F32 || s->kind != OP_SIGMOID_F32 || mu->kind != OP_BINARY_F32 || !mu->is_mul) continue;
-        const int q1 = c->t_out, q2 = s->t_out, q3 = mu->t_out;
-        if (s->t_in[0] != q1 || q1 == q2 || q2 == q3 || q1 == q3 || q3 == c->t_in[0]) continue;
-        if (!((mu->t_in[0] == q1 && mu->t_in[1] == q2) || (mu->t_in[0] == q2 && mu->t_in[1] == q1))) continue;
-        if (readers[q1] != 2 || readers[q2] != 1 || writers[q1] != 1 || writers[q2] != 1 || writers[q3] != 1) continue;
-        if (m->mt[q1].io_out || m->mt[q2].io_out || m->mt[q1].io_in || m->mt[q2].io_in || m->mt[q3].is_weight) continue;
-        const size_t n1 = (size_t)c->out_h * c->out_w * c->out_c;
-        if (s->n != n1 || mu->n != n1) continue; /* the chain must cover exactly the conv's result */
-        c->silu_f32 = 1;
-        c->t_out = q3;
-        touch(m, q3, n1 * 4);
-        m->mt[q1].needed = 0;
-        m->mt[q2].needed = 0;
-        memmove(&m->ops[i + 1], &m->ops[i + 3], (size_t)(m->n_ops - i - 3) * sizeof(mars_op_t));
-        m->n_ops -= 2;
-    }
-    free(readers);
-    free(writers);
 }
 
 /* ------------------------------------------------------------- zero-copy concat
@@ -744,24 +785,15 @@ void fuse_silu_f32(mars_model_ext_t *m) {
  * producer gets (pixel stride = concat channels, channel offset) and the copy launch disappears.
  * Same bytes end up in the concat output; the intermediate tensor is never materialised. */
 void elide_concat(mars_model_ext_t *m) {
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
-        if (m->ops[i].t_out >= 0) writers[m->ops[i].t_out]++;
-    }
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
     for (int i = 0; i < m->n_ops; i++) {
         mars_op_t *cs = &m->ops[i];
         if (cs->kind != OP_CONCAT_SLICE) continue;
         const int ti = cs->t_in[0], to = cs->t_out;
         const mtensor_t *mt = &m->mt[ti];
         if (mt->is_weight || mt->io_in || mt->io_out || readers[ti] != 1 || writers[ti] != 1) continue;
-        int j = -1;
-        for (int k = 0; k < i; k++)
-            if (m->ops[k].t_out == ti) j = k;
+        const int j = writer_before(m, ti, i);
         if (j < 0) continue;
         mars_op_t *pr = &m->ops[j];
         if (pr->out_pix_stride || pr->add_t) continue; /* a folded Add needs its other operand laid out like the output */
@@ -771,14 +803,13 @@ void elide_concat(mars_model_ext_t *m) {
         else if (pr->kind == OP_BINARY_I8) ok = pr->n == npix * (size_t)cs->in_c;
         else if (pr->kind == OP_MAXPOOL || pr->kind == OP_UPSAMPLE) ok = (size_t)pr->out_h * pr->out_w == npix && pr->in_c == cs->in_c;
         if (!ok || cs->ch_off + cs->in_c > cs->out_c) continue;
-        /* nothing between producer and the copy may touch the concat output except its other slices */
+        /* nothing between producer and the copy may touch the concat output except its other slices (own loop: those are allowed writers,
+         * and a slice copy already elided is skipped) */
         int clash = 0;
         for (int k = j; k < i && !clash; k++) {
             const mars_op_t *o = &m->ops[k];
-            if (o->kind == -1) continue; /* a slice copy already elided */
-            for (int q = 0; q < o->n_in; q++)
-                if (o->t_in[q] == to) clash = 1;
-            if (o->t_out == to && o->kind != OP_CONCAT_SLICE && !o->out_pix_stride) clash = 1;
+            if (o->kind == -1) continue;
+            if (op_reads(o, to) || (o->t_out == to && o->kind != OP_CONCAT_SLICE && !o->out_pix_stride)) clash = 1;
         }
         if (clash) continue;
         pr->t_out = to;
@@ -787,14 +818,10 @@ void elide_concat(mars_model_ext_t *m) {
         if (pr->kind == OP_BINARY_I8) pr->in_c = cs->in_c; /* channel run of the slice */
         pr->bytes += 0;
         m->mt[ti].needed = 0;
-        cs->kind = -1; /* dropped below */
+        cs->kind = -1;
     }
-    int w = 0;
-    for (int i = 0; i < m->n_ops; i++)
-        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-    m->n_ops = w;
+    drop_dead_ops(m);
     free(readers);
-    free(writers);
 }
 
 /* Dead stores of a CONCAT.  The reference copies input k's "pixels" (runs of shape[3] BYTES, whatever the dtype) to byte
@@ -836,7 +863,7 @@ void trim_concat(mars_model_ext_t *m) {
 void nhwc_internal(mars_model_ext_t *m) {
     const int nt = (int)m->pub.header.num_tensors;
     for (int i = 0; i < nt; i++) m->mt[i].nhwc_c = m->mt[i].nhwc_hw = m->mt[i].nhwc_pitch = m->mt[i].partial = 0;
-    if (m->fusion < 1 || getenv("MARS_HIP_NO_NHWC_INTERNAL")) return;
+    if (m->sw.fusion < 1 || m->sw.no_nhwc_internal) return;
     unsigned char *el = (unsigned char *)calloc((size_t)nt + 1, 1);
     if (!el) return;
     for (int t = 0; t < nt; t++) { /* candidates: dense [1, C, H, W] int8 activations, C a multiple of 16 (16-byte pixel rows), not NHWC-tagged */
@@ -956,12 +983,7 @@ void nhwc_internal(mars_model_ext_t *m) {
         if (o->n_in >= 1 && o->t_in[0] >= 0 && el[o->t_in[0]]) o->nchw = 0;
         if (o->t_out >= 0 && el[o->t_out]) o->out_nchw = 0;
     }
-    {
-        int w = 0;
-        for (int i = 0; i < m->n_ops; i++)
-            if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-        m->n_ops = w;
-    }
+    drop_dead_ops(m);
     free(grp);
     for (int t = 0; t < nt; t++)
         if (el[t]) {
@@ -989,18 +1011,7 @@ void nhwc_internal(mars_model_ext_t *m) {
             d->shape[1] != o->out_c || d->shape[2] != o->out_h || d->shape[3] != o->out_w || P > o->oc_pad ||
             mt->bytes != (size_t)o->out_c * o->out_h * o->out_w || mt->extent != mt->bytes)
             continue;
-        int touched = 0; /* any other op that reads or writes it keeps it as tagged */
-        for (int j = 0; j < m->n_ops && !touched; j++) {
-            const mars_op_t *q = &m->ops[j];
-            if (j != i && q->t_out == T) touched = 1;
-            for (int k = 0; k < q->n_in && k < 4; k++)
-                if (q->t_in[k] == T) touched = 1;
-            for (int k = 0; k < q->nseg && k < 4; k++)
-                if (q->seg_t[k] == T) touched = 1;
-            for (int k = 0; k < q->chain_n && k < 3; k++)
-                if (q->chain_out[k] == T) touched = 1;
-        }
-        if (touched) continue;
+        if (touched_by_other(m, T, i, i)) continue; /* any other op that reads or writes it keeps it as tagged (op i itself: no convolution reads its own result) */
         o->out_nchw = 0;
         o->out_pix_stride = P;
         o->store_c = P;
@@ -1012,8 +1023,6 @@ void nhwc_internal(mars_model_ext_t *m) {
     free(el);
 }
 
-static int op_writes(const mars_op_t *o, int t);
-
 /* The reference's CONCAT on NCHW-tagged maps of equal size is a shift of its LAST input by N - 1 map rows (move.hip: concat_nchwq_kernel):
  *   out(c, h, w) = in_last(c, h - (N - 1), w)  for h >= N - 1 and c < C_last,   0 for c >= C_last;   the first N - 1 rows are irregular.
  * When its only reader is a plain 1 x 1 convolution X (C3's cv3, SPPF's cv2 in the shipped files), X over rows h >= N - 1 is the SAME
@@ -1022,9 +1031,9 @@ static int op_writes(const mars_op_t *o, int t);
  *   - X is split in two launches: rows 0 .. N - 2 from those rows (all channels, the original weights), rows N - 1 .. H - 1 straight from
  *     in_last (a second weight image: the first C_last input channels).
  * The concat's copy of the whole map and the zero half (or three quarters) of X's K loop go.  Same bytes out: every output row is the sum
- * the reference computes, over exactly the non-zero terms.  Runs last of the fusion passes. */
+ * the reference computes, over exactly the non-zero terms. */
 void virtual_concat_q(mars_model_ext_t *m) {
-    if (m->fusion < 1 || getenv("MARS_HIP_NO_VCONCAT_Q")) return;
+    if (m->sw.fusion < 1 || m->sw.no_vconcat_q) return;
     for (int i = 0; i < m->n_ops; i++) {
         mars_op_t *cq = &m->ops[i];
         if (cq->kind != OP_CONCAT_Q || cq->n_in < 2 || cq->rows_only) continue;
@@ -1035,10 +1044,8 @@ void virtual_concat_q(mars_model_ext_t *m) {
         int r = -1, nr = 0, bad = 0;
         for (int j = 0; j < m->n_ops; j++) {
             const mars_op_t *o = &m->ops[j];
-            for (int k = 0; k < o->n_in && k < 4; k++)
+            for (int k = 0; k < o->n_in; k++)
                 if (o->t_in[k] == T) { nr++; if (r < 0) r = j; }
-            for (int k = 0; k < o->nseg && k < 4; k++)
-                if (o->seg_t[k] == T) bad = 1;
             if (j != i && op_writes(o, T)) bad = 1;
         }
         if (bad || r <= i || nr < 1 || nr > 2) continue;
@@ -1055,10 +1062,7 @@ void virtual_concat_q(mars_model_ext_t *m) {
                 ok = 0;
         }
         if (!ok) continue;
-        int clash = 0; /* in_last must still hold at the readers what it held at the concat */
-        for (int j = i + 1; j < r + np && !clash; j++)
-            if (op_writes(&m->ops[j], TL)) clash = 1;
-        if (clash) continue;
+        if (touched_between(m, i + 1, r + np, TL, USE_WRITE)) continue; /* in_last must still hold at the readers what it held at the concat */
         /* the second weight images: input channels [0, C_last) of every output channel (1 x 1: OIHW and OHWI coincide) */
         size_t w_off2[2] = {NO_OFF, NO_OFF};
         int row_pad2 = 0;
@@ -1122,130 +1126,50 @@ void virtual_concat_q(mars_model_ext_t *m) {
  * (mars_runtime.c ADD branch: (a*sa + b*sb) * (1/so) + 0.5f, truncated, saturated), reading x where the output
  * goes.  Saves writing the convolution result and reading it back.  Conditions: the convolution result has no
  * other reader, x and the Add output have the same dense layout and frame stride, nothing touches them in
- * between, and the scales keep the float -> int conversion in range (so no x86 fix-up is needed). */
-static size_t planned_stride(const mtensor_t *t) {
-    size_t s = ALIGN_UP(t->extent > t->bytes ? t->extent : t->bytes, 256);
-    return s ? s : 256;
-}
-void fuse_add(mars_model_ext_t *m) {
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
-        if (m->ops[i].t_out >= 0) writers[m->ops[i].t_out]++;
-    }
-    for (int j = 0; j < m->n_ops; j++) {
-        mars_op_t *ad = &m->ops[j];
-        if (ad->kind != OP_BINARY_I8 || ad->is_mul || ad->n_in != 2 || ad->out_pix_stride) continue;
-        for (int side = 0; side < 2; side++) {
-            const int A = ad->t_in[side], X = ad->t_in[1 - side], O = ad->t_out;
-            if (A < 0 || X < 0 || O < 0 || A == X || O == X || O == A) continue;
-            if (readers[A] != 1 || writers[A] != 1 || m->mt[A].io_in || m->mt[A].io_out || m->mt[A].is_weight) continue;
-            if (m->mt[X].is_weight || m->mt[O].is_weight || writers[O] != 1) continue;
-            int i = -1;
-            for (int k = 0; k < j; k++)
-                if (m->ops[k].t_out == A) i = k;
-            if (i < 0) continue;
-            mars_op_t *c = &m->ops[i];
-            if (c->kind != OP_CONV_I8 || c->out_nchw || !c->safe || c->out_pix_stride || (c->out_c & 15) || (c->in_c & 15) ||
-                c->nseg || c->add_t || c->n_in != 1)
-                continue;
-            if (ad->n != (size_t)c->out_h * c->out_w * c->out_c) continue;
-            if (c->t_in[0] == O) continue; /* add(conv(X), Y) -> X: sequential in the reference, a race when fused */
-            if (planned_stride(&m->mt[X]) != planned_stride(&m->mt[O])) continue;
-            const float s_conv = side == 0 ? ad->f0 : ad->f1, s_other = side == 0 ? ad->f1 : ad->f0, inv = ad->f2;
-            const double bound = 128.0 * (fabs((double)s_conv) + fabs((double)s_other)) * fabs((double)inv) + 1.0;
-            if (!(bound < 2147483000.0)) continue; /* also rejects NaN / inf */
-            int clash = 0;
-            for (int k = i; k <= j && !clash; k++) {
-                const mars_op_t *o = &m->ops[k];
-                if (o->t_out == X) clash = 1; /* x must be complete before the convolution runs */
-                if (k > i && k < j) {
-                    if (o->t_out == O) clash = 1;
-                    for (int q = 0; q < o->n_in; q++)
-                        if (o->t_in[q] == O) clash = 1;
-                }
-            }
-            if (clash) continue;
-            c->t_out = O;
-            c->add_t = X + 1;
-            c->add_s_conv = s_conv; c->add_s_other = s_other; c->add_inv = inv;
-            c->t_in[c->n_in++] = X;
-            c->bytes += (double)ad->n;
-            m->mt[A].needed = 0;
-            ad->kind = -1;
-            readers[A] = 0;
-            break;
-        }
-    }
-    int w = 0;
-    for (int i = 0; i < m->n_ops; i++)
-        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-    m->n_ops = w;
-    free(readers);
-    free(writers);
-}
-
-/* The float32 form: Add(conv_f32 result, x) (reference mars_runtime.c:807-816: out[i] = a[i] + b[i]) evaluated where the
+ * between, and the scales keep the float -> int conversion in range (so no x86 fix-up is needed).
+ * The float32 form: Add(conv_f32 result, x) (reference mars_runtime.c:807-816: out[i] = a[i] + b[i]) evaluated where the
  * convolution stores -- one float add behind the (fused) SiLU, the same float the separate layer computes from the same two
  * floats, so every kernel form stays what it was (the exact-order kernel bit-identical).  Saves a write and two reads of
- * the tensor per bottleneck (7 launches, 7 % of the float32 twin's step). */
-void fuse_add_f32(mars_model_ext_t *m) {
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
-        if (m->ops[i].t_out >= 0) writers[m->ops[i].t_out]++;
-    }
+ * the tensor per bottleneck (7 launches, 7 % of the float32 twin's step).  It needs none of the int8 form's layout conditions. */
+void fold_add(mars_model_ext_t *m, int f32) {
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
     for (int j = 0; j < m->n_ops; j++) {
         mars_op_t *ad = &m->ops[j];
-        if (ad->kind != OP_BINARY_F32 || ad->is_mul || ad->n_in != 2) continue;
+        if (ad->kind != (f32 ? OP_BINARY_F32 : OP_BINARY_I8) || ad->is_mul || ad->n_in != 2 || (!f32 && ad->out_pix_stride)) continue;
         for (int side = 0; side < 2; side++) {
             const int A = ad->t_in[side], X = ad->t_in[1 - side], O = ad->t_out;
             if (A < 0 || X < 0 || O < 0 || A == X || O == X || O == A) continue;
             if (readers[A] != 1 || writers[A] != 1 || m->mt[A].io_in || m->mt[A].io_out || m->mt[A].is_weight) continue;
             if (m->mt[X].is_weight || m->mt[O].is_weight || writers[O] != 1) continue;
-            int i = -1;
-            for (int k = 0; k < j; k++)
-                if (m->ops[k].t_out == A) i = k;
+            const int i = writer_before(m, A, j);
             if (i < 0) continue;
             mars_op_t *c = &m->ops[i];
-            if (c->kind != OP_CONV_F32 || c->add_t || c->n_in != 1) continue;
+            if (c->kind != (f32 ? OP_CONV_F32 : OP_CONV_I8) || c->add_t || c->n_in != 1) continue;
+            if (!f32 && (c->out_nchw || !c->safe || c->out_pix_stride || (c->out_c & 15) || (c->in_c & 15) || c->nseg)) continue;
             if (ad->n != (size_t)c->out_h * c->out_w * c->out_c) continue;
             if (c->t_in[0] == O) continue; /* add(conv(X), Y) -> X: sequential in the reference, a race when fused */
-            int clash = 0;
-            for (int k = i; k <= j && !clash; k++) {
-                const mars_op_t *o = &m->ops[k];
-                if (o->t_out == X) clash = 1; /* x must be complete before the convolution runs */
-                if (k > i && k < j) {
-                    if (o->t_out == O) clash = 1;
-                    for (int q = 0; q < o->n_in; q++)
-                        if (o->t_in[q] == O) clash = 1;
-                }
+            const float s_conv = side == 0 ? ad->f0 : ad->f1, s_other = side == 0 ? ad->f1 : ad->f0, inv = ad->f2;
+            if (!f32) { /* the int8 epilogue reads x where the output goes, and converts float -> int without the x86 fix-up */
+                if (planned_stride(&m->mt[X]) != planned_stride(&m->mt[O])) continue;
+                const double bound = 128.0 * (fabs((double)s_conv) + fabs((double)s_other)) * fabs((double)inv) + 1.0;
+                if (!(bound < 2147483000.0)) continue; /* also rejects NaN / inf */
             }
-            if (clash) continue;
+            /* x must be complete before the convolution runs, and nothing in between may touch the Add's output */
+            if (touched_between(m, i, j + 1, X, USE_WRITE) || touched_between(m, i + 1, j, O, USE_READ | USE_WRITE)) continue;
             c->t_out = O;
             c->add_t = X + 1;
+            if (!f32) { c->add_s_conv = s_conv; c->add_s_other = s_other; c->add_inv = inv; }
             c->t_in[c->n_in++] = X;
-            c->bytes += 4.0 * (double)ad->n;
+            c->bytes += (f32 ? 4.0 : 1.0) * (double)ad->n;
             m->mt[A].needed = 0;
             ad->kind = -1;
             readers[A] = 0;
             break;
         }
     }
-    int w = 0;
-    for (int i = 0; i < m->n_ops; i++)
-        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-    m->n_ops = w;
+    drop_dead_ops(m);
     free(readers);
-    free(writers);
 }
 
 /* Fused C3 bottleneck: conv1x1 + SiLU (A) whose only reader is the k x k convolution B right behind it (B usually
@@ -1257,12 +1181,8 @@ void fuse_add_f32(mars_model_ext_t *m) {
  * nothing at batch 256 -- these 32 / 64-channel layers are bound by the requantisation's vector instructions, not by
  * the bytes the fusion saves, and the halo makes the fused kernel requantise 1.3x the pixels. */
 void fuse_bottleneck(mars_model_ext_t *m) {
-    const int nt = (int)m->pub.header.num_tensors;
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers) return;
-    for (int i = 0; i < m->n_ops; i++)
-        for (int k = 0; k < m->ops[i].n_in; k++)
-            if (m->ops[i].t_in[k] >= 0) readers[m->ops[i].t_in[k]]++;
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
     for (int i = 0; i + 1 < m->n_ops; i++) {
         mars_op_t *a = &m->ops[i], *b = &m->ops[i + 1];
         if (a->kind != OP_CONV_I8 || b->kind != OP_CONV_I8 || a->pre || b->pre) continue;
@@ -1276,19 +1196,7 @@ void fuse_bottleneck(mars_model_ext_t *m) {
             continue;
         const int X = a->t_in[0];
         if (X < 0 || X == b->t_out || m->mt[X].is_weight) continue;
-        /* the device side decides on geometry: describe B with A folded in (pointers only need to be non-null here) */
-        mars_op_t trial = *b;
-        trial.pre = 1;
-        trial.t_in[0] = X;
-        mhip_conv_i8_t p;
-        memset(&p, 0, sizeof(p));
-        p.frames = 1; p.in_c = trial.in_c; p.in_h = trial.in_h; p.in_w = trial.in_w; p.out_h = trial.out_h; p.out_w = trial.out_w;
-        p.out_c = trial.store_c ? trial.store_c : trial.out_c; p.kh = trial.kh; p.kw = trial.kw; p.stride_h = trial.sh; p.stride_w = trial.sw;
-        p.pad_top = trial.pt; p.pad_left = trial.pl; p.row_pad = trial.row_pad; p.oc_pad = trial.oc_pad; p.safe = trial.safe;
-        p.out_pix_stride = trial.out_pix_stride; p.out_ch_off = trial.out_ch_off;
-        p.pre_w = (const int8_t *)m; p.pre_bias = (const int32_t *)m; p.pre_lut2 = (const uint8_t *)m; p.lut2 = (const uint8_t *)m;
-        p.lut = (const uint8_t *)m;
-        if (!mhip_conv_i8_pre_ok(&p)) continue;
+        if (!conv_i8_pre_fits(b, 1, 0, 0)) continue; /* one frame, no strides: alloc_batch asks again for its batch */
         b->pre = 1;
         b->pre_w_off = a->w_off; b->pre_b_off = a->b_off; b->pre_lut2_off = a->lut2_off; b->pre_cs = a->cs;
         b->t_in[0] = X;
@@ -1297,11 +1205,34 @@ void fuse_bottleneck(mars_model_ext_t *m) {
         readers[T] = 0;
         a->kind = -1;
     }
-    int w = 0;
-    for (int i = 0; i < m->n_ops; i++)
-        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-    m->n_ops = w;
+    drop_dead_ops(m);
     free(readers);
+}
+
+/* Ragged pixel rows of graph outputs (the 255-channel YOLO heads) are kept at a 16-byte-aligned pitch on the device:
+ * the producing convolution then takes the aligned epilogue (16-byte stores straight from registers, every launch
+ * form) instead of the LDS-staged copy-out with 8+4+2+1-byte row tails.  Only tensors nothing in the graph reads:
+ * their readers are the detection tail (told the pitch) and the download / read entry points (2-D copies), so hosts
+ * still see the reference's dense [H][W][C] bytes.  The pad channels carry zero weights; their bytes are never read. */
+void pad_output_rows(mars_model_ext_t *m) {
+    for (uint32_t i = 0; i < m->pub.header.num_tensors; i++) m->mt[i].pix_c = m->mt[i].pix_stride = 0;
+    if (m->sw.no_rowpad) return;
+    for (int i = 0; i < m->n_ops; i++) {
+        mars_op_t *o = &m->ops[i];
+        if (o->kind != OP_CONV_I8 || o->out_nchw || o->out_pix_stride || o->out_ch_off || o->add_t || o->t_out < 0 ||
+            (o->out_c & 15) == 0 || (o->in_c & 15) != 0)
+            continue;
+        mtensor_t *t = &m->mt[o->t_out];
+        const int P = (o->out_c + 15) & ~15;
+        const size_t px = (size_t)o->out_h * o->out_w;
+        if (!t->io_out || t->io_in || P > o->oc_pad || t->bytes != px * (size_t)o->out_c || (px * P) % 256 != 0) continue;
+        if (touched_by_other(m, o->t_out, i, i)) continue; /* any other op touching the tensor keeps it dense */
+        o->out_pix_stride = P;
+        o->store_c = P;
+        t->pix_c = o->out_c;
+        t->pix_stride = P;
+        if (px * P > t->extent) t->extent = px * P;
+    }
 }
 
 /* Virtual concat: when every reader of a Concat output is a plain 1x1 convolution, the concat tensor is never
@@ -1347,8 +1278,7 @@ void virtual_concat(mars_model_ext_t *m) {
                 bad = 1;
             c += o->in_c;
             /* the input must still hold at the last reader what it held where the copy stood */
-            for (int i = sl[a] + 1; i <= last_reader && !bad; i++)
-                if (m->ops[i].t_out == o->t_in[0]) bad = 1;
+            if (!bad && touched_between(m, sl[a] + 1, last_reader + 1, o->t_in[0], USE_WRITE)) bad = 1;
         }
         if (bad || c != s0->out_c) continue;
         for (int i = 0; i < m->n_ops && !bad; i++) {
@@ -1406,10 +1336,7 @@ void virtual_concat(mars_model_ext_t *m) {
             m->mt[S].needed = 0;
         }
     }
-    int w = 0;
-    for (int i = 0; i < m->n_ops; i++)
-        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-    m->n_ops = w;
+    drop_dead_ops(m);
 }
 
 /* Two convolutions that read the same input with the same geometry (C3's cv1 and cv2, which the exporter emits
@@ -1432,11 +1359,18 @@ static int pairable(const mars_op_t *o) {
     return o->kind == OP_CONV_I8 && !o->nchw && !o->out_nchw && !o->add_t && !o->nseg && o->safe && o->lut_off != NO_OFF && !o->pair_next &&
            (o->in_c & 15) == 0 && o->in_c > 4 && (o->out_c & 15) == 0 && !o->out_pix_stride;
 }
-static int op_writes(const mars_op_t *o, int t) {
-    if (o->t_out == t) return 1;
-    for (int k = 0; k < o->chain_n; k++)
-        if (o->chain_out[k] == t) return 1;
-    return 0;
+/* the step both pairing passes share: op j becomes op i's mate (moved up right behind it) unless an op between them touches j's output or
+ * writes one of j's inputs */
+static int pair_up(mars_model_ext_t *m, int i, int j) {
+    const mars_op_t *b = &m->ops[j];
+    if (touched_between(m, i + 1, j, b->t_out, USE_READ | USE_WRITE)) return 0;
+    for (int k = 0; k < b->n_in; k++)
+        if (touched_between(m, i + 1, j, b->t_in[k], USE_WRITE)) return 0;
+    const mars_op_t moved = *b;
+    memmove(&m->ops[i + 2], &m->ops[i + 1], sizeof(mars_op_t) * (size_t)(j - i - 1));
+    m->ops[i + 1] = moved;
+    m->ops[i].pair_next = 1;
+    return 1;
 }
 void pair_convs(mars_model_ext_t *m) {
     for (int i = 0; i + 1 < m->n_ops; i++) {
@@ -1445,23 +1379,8 @@ void pair_convs(mars_model_ext_t *m) {
         for (int j = i + 1; j < m->n_ops && j <= i + 48; j++) {
             mars_op_t *b = &m->ops[j];
             if (!pairable(b) || !same_conv_input(a, b) || b->t_out == a->t_out) continue;
-            int ok = 1;
-            for (int k = 0; k < b->n_in; k++)
-                if (b->t_in[k] == b->t_out || b->t_in[k] == a->t_out) ok = 0;
-            for (int q = i + 1; q < j && ok; q++) {
-                const mars_op_t *o = &m->ops[q];
-                if (op_writes(o, b->t_out)) ok = 0;
-                for (int k = 0; k < o->n_in; k++)
-                    if (o->t_in[k] == b->t_out) ok = 0;
-                for (int k = 0; k < b->n_in; k++)
-                    if (op_writes(o, b->t_in[k])) ok = 0;
-            }
-            if (!ok) continue;
-            mars_op_t moved = *b;
-            memmove(&m->ops[i + 2], &m->ops[i + 1], sizeof(mars_op_t) * (size_t)(j - i - 1));
-            m->ops[i + 1] = moved;
-            m->ops[i].pair_next = 1;
-            break;
+            if (op_reads(b, b->t_out) || op_reads(b, a->t_out)) continue;
+            if (pair_up(m, i, j)) break;
         }
     }
 }
@@ -1475,7 +1394,7 @@ static int pairable_f32(const mars_op_t *o) {
            o->kh == 1 && o->kw == 1;
 }
 void pair_convs_f32(mars_model_ext_t *m) {
-    if (getenv("MARS_HIP_NO_PAIR_F32")) return;
+    if (m->sw.no_pair_f32) return;
     for (int i = 0; i + 1 < m->n_ops; i++) {
         mars_op_t *a = &m->ops[i];
         if (!pairable_f32(a) || (i > 0 && m->ops[i - 1].pair_next)) continue;
@@ -1488,19 +1407,9 @@ void pair_convs_f32(mars_model_ext_t *m) {
             if (planned_stride(&m->mt[a->t_out]) != planned_stride(&m->mt[b->t_out])) continue;
             if (a->w2_planes != b->w2_planes) continue;
             int ok = b->t_in[0] != b->t_out && b->t_in[0] != a->t_out;
-            for (int q = i + 1; q < j && ok; q++) {
-                const mars_op_t *o = &m->ops[q];
-                if (op_writes(o, b->t_out) || op_writes(o, b->t_in[0])) ok = 0;
-                for (int k = 0; k < o->n_in; k++)
-                    if (o->t_in[k] == b->t_out) ok = 0;
-                if (o->pair_next) ok = 0; /* (a pair stays adjacent) */
-            }
-            if (!ok) continue;
-            mars_op_t moved = *b;
-            memmove(&m->ops[i + 2], &m->ops[i + 1], sizeof(mars_op_t) * (size_t)(j - i - 1));
-            m->ops[i + 1] = moved;
-            m->ops[i].pair_next = 1;
-            break;
+            for (int q = i + 1; q < j && ok; q++)
+                if (m->ops[q].pair_next) ok = 0; /* (this pass does not move an op past a pair; pair_convs does: kept as it was) */
+            if (ok && pair_up(m, i, j)) break;
         }
     }
 }
@@ -1533,10 +1442,7 @@ void fuse_pool_chains(mars_model_ext_t *m) {
         }
         a->t_out = a->chain_out[n - 1];
     }
-    int w = 0;
-    for (int i = 0; i < m->n_ops; i++)
-        if (m->ops[i].kind != -1) m->ops[w++] = m->ops[i];
-    m->n_ops = w;
+    drop_dead_ops(m);
 }
 
 /* float32 graphs: which convolutions may take the f32 matrix cores (fused rounding per tap, inside the 1e-4 tolerance)?
@@ -1558,32 +1464,17 @@ void rec_pairs(mars_model_ext_t *m) {
     for (int i = 0; i < nt; i++) m->mt[i].rec_c = m->mt[i].rec_hw = 0;
     m->rec_skipped = 0;
     m->rec_max_frames = (size_t)-1;
-    if (m->fusion < 1 || getenv("MARS_HIP_NO_REC") || mhip_conv_f32_mode(-1) != 3) return;
-    const char *lim_env = getenv("MARS_HIP_REC_LIMIT"); /* (tests lower it to see the per-batch decision with small tensors) */
-    const size_t frames = m->rec_frames > 0 ? (size_t)m->rec_frames : 1, lim = lim_env ? (size_t)strtoull(lim_env, NULL, 0) : (size_t)0xfffffff0u; /* 32-bit byte offsets over all frames of a tensor */
-    int *readers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    int *writers = (int *)calloc((size_t)nt + 1, sizeof(int));
-    if (!readers || !writers) { free(readers); free(writers); return; }
-    for (int i = 0; i < m->n_ops; i++) {
-        const mars_op_t *o = &m->ops[i];
-        for (int k = 0; k < o->n_in && k < 4; k++)
-            if (o->t_in[k] >= 0) readers[o->t_in[k]]++;
-        /* (the operand of a folded Add is one of t_in[]: fuse_add_f32) */
-        for (int k = 0; k < o->nseg && k < 4; k++)
-            if (o->seg_t[k] >= 0) readers[o->seg_t[k]]++;
-        if (o->t_out >= 0) writers[o->t_out]++;
-        for (int k = 0; k < o->chain_n && k < 3; k++)
-            if (o->chain_out[k] >= 0) writers[o->chain_out[k]]++;
-    }
+    if (m->sw.fusion < 1 || m->sw.no_rec || m->plan_f32_mode != 3) return;
+    const size_t frames = m->rec_frames > 0 ? (size_t)m->rec_frames : 1, lim = m->sw.rec_limit; /* 32-bit byte offsets over all frames of a tensor */
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
     for (int j = 0; j < m->n_ops; j++) {
         mars_op_t *x = &m->ops[j];
         if (x->kind != OP_CONV_F32 || x->w3_off == NO_OFF || x->w3_stem || x->n_in != (x->add_t ? 2 : 1) || x->in_rec) continue;
         const int T = x->t_in[0];
         if (T < 0 || readers[T] != 1 || writers[T] != 1 || m->mt[T].io_in || m->mt[T].io_out || m->mt[T].is_weight) continue;
         if (x->add_t && x->add_t - 1 == T) continue;
-        int i = -1;
-        for (int k = 0; k < j; k++)
-            if (m->ops[k].t_out == T) i = k;
+        const int i = writer_before(m, T, j);
         if (i < 0) continue;
         mars_op_t *pr = &m->ops[i];
         if (pr->kind != OP_CONV_F32 || pr->add_t || pr->out_rec || (pr->out_c & 7) || pr->kh > 32 || pr->kw > 32) continue;
@@ -1607,11 +1498,7 @@ void rec_pairs(mars_model_ext_t *m) {
             const int tt[3] = {pr->t_in[0], T, x->t_out};
             size_t worst = 0;
             for (int q = 0; q < 3; q++)
-                if (tt[q] >= 0) {
-                    const mtensor_t *u = &m->mt[tt[q]];
-                    const size_t st = ALIGN_UP(u->extent > u->bytes ? u->extent : u->bytes, 256);
-                    if (st > worst) worst = st;
-                }
+                if (tt[q] >= 0 && planned_stride(&m->mt[tt[q]]) > worst) worst = planned_stride(&m->mt[tt[q]]);
             if (worst && worst * frames > lim) {
                 m->rec_skipped = 1;
                 continue;
@@ -1627,7 +1514,6 @@ void rec_pairs(mars_model_ext_t *m) {
         m->mt[T].rec_hw = x->in_h * x->in_w;
     }
     free(readers);
-    free(writers);
 }
 
 /* Exact zeros the reference's byte-wise CONCAT leaves in float tensors (round 6).  The concat copies runs of shape[3] BYTES whatever the dtype
@@ -1642,7 +1528,7 @@ void zero_tail_f32(mars_model_ext_t *m) {
     const int nt = (int)m->pub.header.num_tensors;
     for (int i = 0; i < nt; i++) m->mt[i].zero_from = 0;
     for (int i = 0; i < m->n_ops; i++) m->ops[i].k_limit = 0;
-    if (m->fusion < 1 || getenv("MARS_HIP_NO_ZERO_TAIL")) return;
+    if (m->sw.fusion < 1 || m->sw.no_zero_tail) return;
     for (int j = 0; j < m->n_ops; j++) {
         mars_op_t *x = &m->ops[j];
         if (x->kind != OP_CONV_F32 || x->kh != 1 || x->kw != 1 || x->sh != 1 || x->sw != 1 || x->pt || x->pl || x->in_rec || x->w2_off == NO_OFF) continue;
@@ -1653,10 +1539,8 @@ void zero_tail_f32(mars_model_ext_t *m) {
         int ok = 1, nw = 0;
         for (int q = 0; q < m->n_ops && ok; q++) {
             const mars_op_t *o = &m->ops[q];
-            for (int k = 0; k < o->chain_n && k < 3; k++)
-                if (o->chain_out[k] == T) ok = 0;
-            if (o->t_out != T) continue;
-            if (o->kind != OP_CONCAT_SLICE || o->out_pix_stride) { ok = 0; break; }
+            if (!op_writes(o, T)) continue;
+            if (o->kind != OP_CONCAT_SLICE || o->out_pix_stride) { ok = 0; break; } /* (a pool chain that writes it is no slice either) */
             nw++;
             const size_t npix = (size_t)o->out_h * o->out_w;
             if (npix && o->in_c > 0) {
@@ -1693,12 +1577,10 @@ void zero_tail_f32(mars_model_ext_t *m) {
  * the concat IS the convolution over the address (last input - sB) with L / plane input planes: it runs on that view (vc_shift, k_limit required),
  * and a second, tiny launch (OP_CONV_F32_VHEAD) recomputes the first sB / 4 pixels of every output plane from their true operands.  The copies
  * (two passes over a quarter of the concat tensor) and the tensor itself go.  Same tolerance class as the launch it replaces (split-bf16 modes only).
- * Batch-dependent like rec_pairs (32-bit offsets over all frames): shares its per-batch re-planning.  Runs last. */
+ * Batch-dependent like rec_pairs (32-bit offsets over all frames): shares its per-batch re-planning. */
 void virtual_concat_f32(mars_model_ext_t *m) {
-    const int mode = mhip_conv_f32_mode(-1);
-    if (m->fusion < 1 || getenv("MARS_HIP_NO_VCONCAT_F32") || (mode != 3 && mode != 4)) return;
-    const char *lim_env = getenv("MARS_HIP_REC_LIMIT");
-    const size_t frames = m->rec_frames > 0 ? (size_t)m->rec_frames : 1, lim = lim_env ? (size_t)strtoull(lim_env, NULL, 0) : (size_t)0xfffffff0u;
+    if (m->sw.fusion < 1 || m->sw.no_vconcat_f32 || (m->plan_f32_mode != 3 && m->plan_f32_mode != 4)) return;
+    const size_t frames = m->rec_frames > 0 ? (size_t)m->rec_frames : 1, lim = m->sw.rec_limit;
     for (int i = 0; i < m->n_ops; i++) {
         if (m->ops[i].kind != OP_CONCAT_SLICE) continue;
         const int T = m->ops[i].t_out, layer = m->ops[i].layer;
@@ -1731,9 +1613,7 @@ void virtual_concat_f32(mars_model_ext_t *m) {
             const mars_op_t *o = &m->ops[j];
             if (j >= first_op && j <= e) continue;
             if (op_writes(o, T)) ok = 0;
-            for (int k = 0; k < o->nseg && k < 4; k++)
-                if (o->seg_t[k] == T) ok = 0;
-            for (int k = 0; k < o->n_in && k < 4; k++)
+            for (int k = 0; k < o->n_in; k++)
                 if (o->t_in[k] == T) {
                     if (k != 0 || j <= e) ok = 0;
                     if (r1 < 0) r1 = j;
@@ -1760,11 +1640,8 @@ void virtual_concat_f32(mars_model_ext_t *m) {
             if (st > worst) worst = st;
         }
         if (!ok) continue;
-        for (int j = e + 1; j <= rl && ok; j++) { /* the operands must still hold at the readers what they held at the concat */
-            if (op_writes(&m->ops[j], TL)) ok = 0;
-            for (int k = 0; k < N - 1; k++)
-                if (op_writes(&m->ops[j], firsts[k])) ok = 0;
-        }
+        ok = !touched_between(m, e + 1, rl + 1, TL, USE_WRITE); /* the operands must still hold at the readers what they held at the concat */
+        for (int k = 0; k < N - 1 && ok; k++) ok = !touched_between(m, e + 1, rl + 1, firsts[k], USE_WRITE);
         if (!ok) continue;
         if (planned_stride(&m->mt[TL]) > worst) worst = planned_stride(&m->mt[TL]);
         /* (the main launch's buffer range is the CONCAT tensor's size over the last input's frame stride: at most 3 strides more than frames of it) */
@@ -1858,3 +1735,24 @@ void f32_policy(mars_model_ext_t *m) {
     free(hot);
 }
 
+/* The operand model every pass above relies on (mars_op_t), checked once per plan: a violation is a planner bug, fails the plan with
+ * MARS_ERR_LAYER_FAILED and names the op under MARS_VERBOSE. */
+void plan_check(mars_model_ext_t *m) {
+    for (int i = 0; i < m->n_ops; i++) {
+        const mars_op_t *o = &m->ops[i];
+        const char *why = NULL;
+        if (o->kind == -1) why = "a dead op is left";
+        else if (o->n_in < 0 || o->n_in > 4 || o->nseg < 0 || o->nseg > 4 || o->chain_n < 0 || o->chain_n > 3 || o->vc_n < 0 || o->vc_n > 3) why = "an operand count is out of range";
+        else if (o->add_t && !op_reads(o, o->add_t - 1)) why = "add_t is not among t_in";
+        else if (o->chain_n && o->t_out != o->chain_out[o->chain_n - 1]) why = "t_out is not the chain's last stage";
+        else if (o->pair_next && (i + 1 >= m->n_ops || m->ops[i + 1].kind != o->kind)) why = "pair_next without a mate of its kind";
+        for (int k = 0; !why && k < o->nseg; k++)
+            if (!op_reads(o, o->seg_t[k])) why = "a seg_t is not among t_in";
+        for (int k = 0; !why && k < o->vc_n; k++)
+            if (!op_reads(o, o->vc_t[k])) why = "a vc_t is not among t_in";
+        if (!why) continue;
+        VLOG("plan_check: op %d (layer %d, kind %d): %s\n", i, o->layer, o->kind, why);
+        m->plan_err = MARS_ERR_LAYER_FAILED;
+        return;
+    }
+}

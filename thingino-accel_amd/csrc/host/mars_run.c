@@ -44,9 +44,8 @@ static size_t tstride(const mars_model_ext_t *m, int ti) { return ti >= 0 ? m->m
 
 void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8_t *p) {
     uint8_t *A = m->arena_dev;
-    memset(p, 0, sizeof(*p));
+    conv_i8_geometry(op, m->run_frames, p);
     p->in = (const int8_t *)tdev(m, op->t_in[0]); p->in_stride = tstride(m, op->t_in[0]);
-    p->in_c = op->in_c;
     p->out = (int8_t *)tdev(m, op->t_out); p->out_stride = tstride(m, op->t_out);
     if (p->in) p->in += op->in_byte_off;   /* (a row range of the tensors: virtual_concat_q) */
     if (p->out) p->out += op->out_byte_off;
@@ -62,13 +61,7 @@ void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8
         p->pre_lut2 = A + op->pre_lut2_off;
         p->pre_cs = op->pre_cs;
     }
-    p->frames = m->run_frames;
-    p->in_h = op->in_h; p->in_w = op->in_w;
-    p->out_h = op->out_h; p->out_w = op->out_w; p->out_c = op->store_c ? op->store_c : op->out_c;
-    p->kh = op->kh; p->kw = op->kw; p->stride_h = op->sh; p->stride_w = op->sw; p->pad_top = op->pt; p->pad_left = op->pl;
-    p->row_pad = op->row_pad; p->oc_pad = op->oc_pad; p->cs = op->cs; p->relu = op->relu; p->out_nchw = op->out_nchw;
-    p->safe = op->safe;
-    p->out_pix_stride = op->out_pix_stride; p->out_ch_off = op->out_ch_off;
+    p->cs = op->cs; p->relu = op->relu; p->out_nchw = op->out_nchw;
     p->variant = op->variant;
     if (op->add_t && tstride(m, op->add_t - 1) == p->out_stride) {
         p->add = (const int8_t *)tdev(m, op->add_t - 1);
@@ -390,11 +383,7 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
         { /* the relayout scratch's copy of a tensor dies with any write to that tensor */
             const mars_op_t *w2[2] = {op, mate};
             for (int q = 0; q < 2; q++)
-                if (w2[q]) {
-                    if (w2[q]->t_out == m->scratch_t) m->scratch_t = -1;
-                    for (int k = 0; k < w2[q]->chain_n; k++)
-                        if (w2[q]->chain_out[k] == m->scratch_t) m->scratch_t = -1;
-                }
+                if (w2[q] && op_writes(w2[q], m->scratch_t)) m->scratch_t = -1;
         }
         if (m->profiling) { /* level 2: one event per run of launches of the same kind (their sum lands on the last one) */
             const int nx = i + 1;
@@ -652,7 +641,7 @@ mars_error_t mars_hip_set_fusion(mars_model_t *model, int level) {
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     if (m->deferred) return MARS_ERR_INVALID_FILE;
     mhip_sync();
-    m->fusion = level;
+    m->sw.fusion = level;
     mars_error_t e = build_plan(m);
     if (e == MARS_OK) e = upload_params(m);
     if (e == MARS_OK) e = alloc_batch(m, m->batch > 0 ? m->batch : 1);

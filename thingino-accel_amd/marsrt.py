@@ -278,8 +278,14 @@ def synth_model(width_x16=8, depth_x3=1, input_hw=640, float32=False, nchw_int8=
     return bytes(buf)
 
 
+DESCRIBE_FULL = 2  # MARS_HIP_DESCRIBE_FULL
+
+
 def describe_plan(file_bytes, flags=0):
-    """the launch plan of a .mars file as a list of text lines (mars_hip_describe_plan; host only: works without a GPU)"""
+    """the launch plan of a .mars file as a list of text lines (mars_hip_describe_plan; host only: works without a GPU).
+    flags: 1 (MARS_HIP_LOAD_DEFER_WEIGHTS) plans from the descriptors alone, as a rank without the weight blob does; DESCRIBE_FULL (2) adds, behind
+    " |", every field of each launch that the run path reads and each tensor's sizes, and lines that start with "+": the needed tensors the short
+    form leaves out, and the plan's totals with the environment switches it was built under.  The short form is a prefix of the full one."""
     b = bytes(file_bytes)
     n = lib().mars_hip_describe_plan(b, len(b), flags, None, 0)
     if n == 0:
