@@ -179,7 +179,8 @@ mars_error_t mars_hip_detect_device(mars_model_t *model, const int *output_indic
  *   cx = ((2 sig(q0) - 0.5) + gx) * stride, w = (2 sig(q2))^2 * anchor_w (cy, h alike); float32, no fused multiply-add;
  *   the first MARS_YOLO_MAX_DET candidates are kept, then the sort + class-wise NMS of mars_hip_detect; then, with src_w > 0,
  *   x' = (cx - px) * (src_w / nw), w' = w * (src_w / nw) (y, h alike) for the letterbox (nw, nh, px, py) of src_w x src_h frames.
- * Out of scope: the anchor-free DFL head (yolov5nu / YOLOv8 style: 64 box + nc class channels); no tensor of it counts as a head. */
+ * The anchor-free DFL head (yolov5nu / YOLOv8 style: 64 box + nc class channels) has its own calls: "anchor-free DFL heads" below; no
+ * tensor of it counts as a head here. */
 
 /* The heads of a .mars file, found on the host (no device needed), sorted by stride: int8 outputs of CONV2D layers with
  * 3 * (5 + nc) channels (nc >= 1) that only no-op layers read (or that are graph outputs), whose grid divides the graph input
@@ -204,8 +205,48 @@ mars_error_t mars_hip_detect_heads(mars_model_t *model, const mars_yolo_heads_t 
 /* Same, results stay in HBM; runs on the auxiliary stream behind the graph, and the next run's head-writing layers wait for it
  * (as mars_hip_detect_device).  mars_hip_detect_results fetches them. */
 mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_heads_t *heads);
-/* The detections the last mars_hip_detect_device / mars_hip_detect_heads_device call left in HBM (waits for them). */
+/* The detections the last mars_hip_detect_device / mars_hip_detect_heads_device / mars_hip_detect_dfl_device call left in HBM (waits for them). */
 mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int *counts);
+
+/* -------------------------------------------------------- anchor-free DFL heads */
+/* The Ultralytics "u" / YOLOv8 Detect head (Distribution Focal Loss): per scale a BOX convolution of 4 * R channels -- R = reg_max bins
+ * for each of the sides left, top, right, bottom -- and a CLASS convolution of nc channels on the same grid, concatenated.  The exported
+ * softmax / DFL-conv / dist2bbox chain behind the concats is not executed (the shipped yolov5nu.mars carries it with all-zero shapes);
+ * these calls decode the two convolutions' int8 bytes themselves, one prediction per cell, float32, every operation rounded on its own:
+ *   prediction order: head (as listed; mars_yolo_find_dfl_heads lists them by ascending stride), cell row gy, column gx;
+ *   best = first class of largest byte q_b; conf = 1 / (1 + expf(-q_b * class scale)); kept iff conf >= conf_thresh (no objectness);
+ *   side k: m = largest of the bytes of channels [k R, (k + 1) R), e_i = expf(-((m - q_i) * box scale)),
+ *           dist_k = (0 e_0 + 1 e_1 + ... + (R - 1) e_{R-1}) / (e_0 + ... + e_{R-1}), both sums left to right;
+ *   x1 = (gx + 0.5) - dist_l, x2 = (gx + 0.5) + dist_r; cx = ((x1 + x2) * 0.5) * stride, w = (x2 - x1) * stride (y1, y2, cy, h alike);
+ *   the first MARS_YOLO_MAX_DET candidates are kept; then sort, class-wise NMS and the letterbox mapping as for the anchor heads.
+ * The bytes are read where the plan left them (planes, pixel rows, a channel slice of the concat's buffer): no plan changes. */
+
+/* The DFL heads of a .mars file, found on the host (no device needed), sorted by stride.  A head is a CONCAT layer that does something,
+ * of exactly two inputs A, B: int8 activations written by CONV2D layers, of equal H x W that divides the graph input by the same factor
+ * on both axes (the stride), read by nothing that does something but this CONCAT, whose own output is a graph output or is read only by
+ * no-op layers; A has 4 R channels, 2 <= R <= 32 (the box tensor, reg_max = R), B has nc >= 1 (the class tensor).  Writes up to cap
+ * entries per array (at most 4; box / class tensor indices, strides, class counts, reg_max; any array may be NULL) and returns the number
+ * found: 0 = none, -1 = a file the loader rejects.  (The decode wants one reg_max for all heads it is given.) */
+int mars_yolo_find_dfl_heads(const void *data, size_t size, int *box_ids, int *cls_ids, int *strides, int *num_classes, int *reg_max, int cap);
+
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int n_heads;                       /* 0: mars_yolo_find_dfl_heads on the loaded file */
+    int box_tensors[4], cls_tensors[4]; /* TENSOR indices */
+    int strides[4];                    /* 0: input height / grid height */
+    int reg_max;                       /* 0: box channels / 4 */
+    float box_scales[4], cls_scales[4]; /* 0: the tensor's own desc.scale (the shipped yolov5nu.mars carries 1.0 everywhere) */
+    float conf_thresh;                 /* 0: 0.25 */
+    float nms_thresh;                  /* 0: 0.45 */
+    int src_w, src_h;                  /* > 0: map boxes back through the letterbox of mars_hip_preprocess for frames of this size */
+} mars_yolo_dfl_heads_t;
+/* Decode + NMS over the model's current batch.  dets: host [batch][MARS_YOLO_MAX_DET]; counts: [batch].  heads may be NULL (all defaults).
+ * MARS_ERR_INVALID_TENSOR: no heads; a head tensor that is not int8, is only partly written or has no addressable bytes; an effective
+ * scale <= 0; box channels that are not 4 * reg_max with reg_max in 2 .. 32; box and class grids that differ. */
+mars_error_t mars_hip_detect_dfl(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, mars_det_t *dets, int *counts);
+/* Same, results stay in HBM for mars_hip_detect_results; streams and events as mars_hip_detect_heads_device (the next run's layers that
+ * write a box or class tensor wait for the decode). */
+mars_error_t mars_hip_detect_dfl_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads);
 
 /* ------------------------------------------------------- pipelined host I/O */
 /* mars_run() pays host->HBM copy, graph and HBM->host copy one after the other.  With an open pipe up to three batches are
@@ -233,6 +274,8 @@ typedef struct {
                              * setting what they use, so that a build against an older header still means "no camera" (ADVICE r5). */
     const mars_yolo_heads_t *heads; /* detect: non-NULL = decode these raw heads (mars_hip_detect_heads) instead of det_outputs; copied at
                              * open.  In camera mode a zero src_w / src_h means camera_w / camera_h: boxes come back in camera pixels */
+    const mars_yolo_dfl_heads_t *dfl_heads; /* detect: non-NULL = decode these DFL heads (mars_hip_detect_dfl) instead; copied at open, camera mode as
+                             * for heads.  Setting both heads and dfl_heads is an error (MARS_ERR_INVALID_TENSOR) */
 } mars_hip_pipe_opts_t;
 mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t *opts);
 /* pinned host buffer ([batch][frame bytes]) to fill for the NEXT submit; changes after every submit */
@@ -268,6 +311,13 @@ typedef struct {
 } mars_synth_opts_t;
 /* returns the file size; writes at most cap bytes (call with cap 0 to size) */
 size_t mars_synth_model(const mars_synth_opts_t *opts, void *buf, size_t cap);
+/* The same graphs with a chosen Detect head.  MARS_SYNTH_HEAD_ANCHOR: mars_synth_model's files byte for byte.  MARS_SYNTH_HEAD_DFL (int8
+ * only, not tiny): per scale a box branch (conv3x3 + SiLU, conv3x3 + SiLU, conv1x1; 64 channels wide, 64 = 4 x 16 outputs) and a class
+ * branch (the same, max(P3 channels, 80) wide, 80 outputs), concatenated; the three concats are the graph outputs.  The class
+ * convolution's bias and scale put a few cells per frame, not hundreds, above a confidence of 0.25.  0 = options it rejects. */
+#define MARS_SYNTH_HEAD_ANCHOR 0
+#define MARS_SYNTH_HEAD_DFL 1
+size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap);
 
 /* ------------------------------------------------------- image front-end */
 /* The reference's load_image() (src/mars/mars_yolo_test.c:40-77) after the file decode, on the GPU: letterbox

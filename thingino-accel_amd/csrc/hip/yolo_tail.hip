@@ -18,7 +18,7 @@
 //  * suppression: the pair relation is evaluated in parallel, 64 rows at a time, into an LDS bit
 //    matrix with the reference's float expression order, then applied greedily.
 // Beside it (end of file): the decode of raw anchor-based YOLOv5 Detect heads into real boxes
-// (heads_decode_kernel), which feeds the same sort + suppression.
+// (heads_decode_kernel) and of anchor-free DFL heads (dfl_decode_kernel), which feed the same sort + suppression.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -554,12 +554,208 @@ __global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int 
     }
 }
 
+// ---------------------------------------------------------------- DFL heads
+// The anchor-free head of the Ultralytics "u" / YOLOv8 models (mars_hip_detect_dfl): per scale a box convolution of 4 * R channels
+// (R = reg_max bins for each of left, top, right, bottom) and a class convolution of nc channels on the same grid, one prediction per
+// cell in the order (head, gy, gx).  With the host's tables per head, sg[q] = 1 / (1 + expf(-q * class scale)) and
+// E[d] = expf(-(d * box scale)), d = 0 .. 255:
+//   best = first class of largest byte, conf = sg[q_best], kept iff conf >= the threshold (no objectness);
+//   side k: m = largest of its R bytes, e_i = E[m - q_i], dist_k = (sum of i * e_i) / (sum of e_i), both sums left to right;
+//   x1 = (gx + 0.5) - dist_l, x2 = (gx + 0.5) + dist_r, cx = ((x1 + x2) * 0.5) * stride, w = (x2 - x1) * stride (y, h alike).
+// Every float operation is rounded on its own (_rn intrinsics).  There is no objectness byte to filter on, so EVERY class byte of every
+// cell is read: one 256-thread workgroup per frame walks the cells 1024 at a time, thread t the cells t, 256 + t, 512 + t, 768 + t of
+// the step -- consecutive lanes take consecutive cells, so plane reads coalesce -- and issues the loads of its four cells before the
+// first compare; pixel rows (ch_step 1) come as 16-byte loads and are compared as integers.  Box bytes are read only for the cells
+// that pass.  Slots come from one ordered block-wide count per step, and the walk ends once 1000 candidates are reached.
+#define DFL_THREADS 256
+#define DFL_CELLS 4
+
+// the first maximum of 16 int8 bytes (classes c0 .. c0 + 15) folded into (bq, arg)
+__device__ __forceinline__ void dfl_argmax16(const v4i w, const int c0, int &bq, int &arg) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int d = w[j];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int q = (d << (24 - 8 * b)) >> 24;
+            const bool gt = q > bq;
+            bq = gt ? q : bq;
+            arg = gt ? c0 + 4 * j + b : arg;
+        }
+    }
+}
+
+// one box side from its R bytes at q[i * cs]
+__device__ __forceinline__ float dfl_side(const int8_t *q, const int R, const int cs, const float *E) {
+    int m = -128;
+    for (int i = 0; i < R; i++) m = max(m, (int)q[(size_t)i * cs]);
+    float den = E[m - q[0]], num = 0.0f; // 0 * e_0 adds nothing to 0.0f
+    for (int i = 1; i < R; i++) {
+        const float e = E[m - q[(size_t)i * cs]];
+        den = __fadd_rn(den, e);
+        num = __fadd_rn(num, __fmul_rn((float)i, e));
+    }
+    return __fdiv_rn(num, den);
+}
+
+// ... reg_max 16 in a pixel row: the side is one 16-byte load
+__device__ __forceinline__ float dfl_side16(const int8_t *q, const float *E) {
+    v4i w;
+    __builtin_memcpy(&w, q, 16);
+    int b[16], m = -128;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        b[i] = (w[i >> 2] << (24 - 8 * (i & 3))) >> 24;
+        m = max(m, b[i]);
+    }
+    float den = E[m - b[0]], num = 0.0f;
+#pragma unroll
+    for (int i = 1; i < 16; i++) {
+        const float e = E[m - b[i]];
+        den = __fadd_rn(den, e);
+        num = __fadd_rn(num, __fmul_rn((float)i, e));
+    }
+    return __fdiv_rn(num, den);
+}
+
+__global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_heads_t p) {
+    __shared__ float tab_s[4][512];
+    __shared__ int wave_cnt[DFL_CELLS][DFL_THREADS / 64];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int i = tid; i < p.nheads * 512; i += DFL_THREADS) tab_s[i >> 9][i & 511] = p.tab[i];
+    __syncthreads();
+    det_rec *dets = (det_rec *)p.dets + (size_t)f * MAXD;
+    const float conf = p.conf;
+    const int R = p.reg_max;
+    int total = 0;
+    for (int hd = 0; hd < p.nheads && total < MAXD; hd++) {
+        const int8_t *cb = p.cls[hd] + (size_t)f * p.cls_frame_stride[hd];
+        const int8_t *bb = p.box[hd] + (size_t)f * p.box_frame_stride[hd];
+        const int W = p.w[hd], npix = p.h[hd] * W, nc = p.nc[hd];
+        const int cps = p.cls_pix_step[hd], ccs = p.cls_ch_step[hd], bps = p.box_pix_step[hd], bcs = p.box_ch_step[hd];
+        const float *E = tab_s[hd], *sg = E + 256;
+        const float fstride = (float)p.stride[hd];
+        for (int base = 0; base < npix && total < MAXD; base += DFL_THREADS * DFL_CELLS) {
+            int bq[DFL_CELLS], arg[DFL_CELLS];
+            const int8_t *row[DFL_CELLS]; // a cell past the end reads the last cell's bytes and is dropped below
+#pragma unroll
+            for (int k = 0; k < DFL_CELLS; k++) {
+                bq[k] = -129;
+                arg[k] = 0;
+                row[k] = cb + (size_t)min(base + k * DFL_THREADS + tid, npix - 1) * cps;
+            }
+            if (ccs == 1 && nc == 80) {
+                v4i w[DFL_CELLS][5]; // 20 loads of 16 bytes in flight (any alignment is served)
+#pragma unroll
+                for (int k = 0; k < DFL_CELLS; k++)
+#pragma unroll
+                    for (int j = 0; j < 5; j++) __builtin_memcpy(&w[k][j], row[k] + 16 * j, 16);
+#pragma unroll
+                for (int k = 0; k < DFL_CELLS; k++)
+#pragma unroll
+                    for (int j = 0; j < 5; j++) dfl_argmax16(w[k][j], 16 * j, bq[k], arg[k]);
+            } else if (ccs == 1) {
+                const int n16 = nc >> 4; // whole 16-byte runs inside the row, then its last bytes one by one
+                for (int j = 0; j < n16; j++) {
+                    v4i w[DFL_CELLS];
+#pragma unroll
+                    for (int k = 0; k < DFL_CELLS; k++) __builtin_memcpy(&w[k], row[k] + 16 * j, 16);
+#pragma unroll
+                    for (int k = 0; k < DFL_CELLS; k++) dfl_argmax16(w[k], 16 * j, bq[k], arg[k]);
+                }
+                for (int c = n16 << 4; c < nc; c++) {
+                    int q[DFL_CELLS];
+#pragma unroll
+                    for (int k = 0; k < DFL_CELLS; k++) q[k] = row[k][c];
+#pragma unroll
+                    for (int k = 0; k < DFL_CELLS; k++)
+                        if (q[k] > bq[k]) { bq[k] = q[k]; arg[k] = c; }
+                }
+            } else {
+#pragma unroll 4
+                for (int c = 0; c < nc; c++) { // planes: a wave reads 64 consecutive bytes of plane c per load
+                    int q[DFL_CELLS];
+#pragma unroll
+                    for (int k = 0; k < DFL_CELLS; k++) q[k] = row[k][(size_t)c * ccs];
+#pragma unroll
+                    for (int k = 0; k < DFL_CELLS; k++)
+                        if (q[k] > bq[k]) { bq[k] = q[k]; arg[k] = c; }
+                }
+            }
+            // slots: candidates are numbered in cell order = (k, thread); one count per (k, wave)
+            bool cand[DFL_CELLS];
+            float cf[DFL_CELLS];
+            int before[DFL_CELLS];
+#pragma unroll
+            for (int k = 0; k < DFL_CELLS; k++) {
+                cf[k] = sg[bq[k] + 128];
+                cand[k] = base + k * DFL_THREADS + tid < npix && cf[k] >= conf;
+                const unsigned long long m = __ballot(cand[k]);
+                before[k] = __popcll(m & ((1ull << lane) - 1ull));
+                if (lane == 0) wave_cnt[k][wv] = __popcll(m);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < DFL_CELLS; k++) {
+                int slot = total + before[k];
+#pragma unroll
+                for (int w = 0; w < DFL_THREADS / 64; w++) {
+                    const int c = wave_cnt[k][w];
+                    if (w < wv) slot += c;
+                    total += c;
+                }
+                if (!cand[k] || slot >= MAXD) continue;
+                const int cell = base + k * DFL_THREADS + tid, gy = cell / W, gx = cell - gy * W;
+                const int8_t *q = bb + (size_t)cell * bps;
+                float dist[4];
+                if (R == 16 && bcs == 1) {
+#pragma unroll
+                    for (int s = 0; s < 4; s++) dist[s] = dfl_side16(q + 16 * s, E);
+                } else {
+                    for (int s = 0; s < 4; s++) dist[s] = dfl_side(q + (size_t)s * R * bcs, R, bcs, E);
+                }
+                const float ax = __fadd_rn((float)gx, 0.5f), ay = __fadd_rn((float)gy, 0.5f);
+                const float x1 = __fsub_rn(ax, dist[0]), y1 = __fsub_rn(ay, dist[1]), x2 = __fadd_rn(ax, dist[2]), y2 = __fadd_rn(ay, dist[3]);
+                det_rec d;
+                d.x = __fmul_rn(__fmul_rn(__fadd_rn(x1, x2), 0.5f), fstride);
+                d.y = __fmul_rn(__fmul_rn(__fadd_rn(y1, y2), 0.5f), fstride);
+                d.w = __fmul_rn(__fsub_rn(x2, x1), fstride);
+                d.h = __fmul_rn(__fsub_rn(y2, y1), fstride);
+                d.conf = cf[k];
+                d.cls = arg[k];
+                dets[slot] = d;
+            }
+            __syncthreads(); // wave_cnt is rewritten by the next step
+        }
+    }
+    if (total > MAXD) total = MAXD;
+    if (tid == 0) {
+        if (p.raw_counts) p.raw_counts[f] = total;
+        p.counts[f] = total;
+    }
+}
+
 extern "C" int mhip_detect_heads(const mhip_heads_t *p) {
     if (!p || p->nheads <= 0 || p->nheads > 4 || p->frames <= 0 || !p->dets || !p->counts || !p->sig) return -1;
     for (int k = 0; k < p->nheads; k++)
         if (!p->base[k] || p->h[k] <= 0 || p->w[k] <= 0 || p->nc[k] < 1 || p->pix_step[k] <= 0 || p->ch_step[k] <= 0) return -1;
     hipLaunchKernelGGL(heads_decode_kernel, dim3(p->frames), dim3(HEADS_THREADS), 0, mhip_stream_native(), *p);
     int rc = mhip_check(hipGetLastError(), "decode heads");
+    if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
+    if (rc || !p->map) return rc;
+    hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,
+                       (float)p->py, p->rx, p->ry);
+    return mhip_check(hipGetLastError(), "letterbox mapping");
+}
+
+extern "C" int mhip_detect_dfl(const mhip_dfl_heads_t *p) {
+    if (!p || p->nheads <= 0 || p->nheads > 4 || p->frames <= 0 || !p->dets || !p->counts || !p->tab || p->reg_max < 2 || p->reg_max > 32) return -1;
+    for (int k = 0; k < p->nheads; k++)
+        if (!p->box[k] || !p->cls[k] || p->h[k] <= 0 || p->w[k] <= 0 || p->nc[k] < 1 || p->box_pix_step[k] <= 0 || p->box_ch_step[k] <= 0 ||
+            p->cls_pix_step[k] <= 0 || p->cls_ch_step[k] <= 0)
+            return -1;
+    hipLaunchKernelGGL(dfl_decode_kernel, dim3(p->frames), dim3(DFL_THREADS), 0, mhip_stream_native(), *p);
+    int rc = mhip_check(hipGetLastError(), "decode DFL heads");
     if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
     if (rc || !p->map) return rc;
     hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,

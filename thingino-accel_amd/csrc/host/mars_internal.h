@@ -53,7 +53,7 @@ typedef struct {
     size_t zero_from;      /* != 0: bytes from this offset on are never written by any layer (zero_tail_f32 relies on it): mars_hip_write_tensor refuses non-zero bytes there */
     int partial;           /* only part of the tensor is ever written (virtual_concat_q keeps the first rows of a concat): not readable through mars_hip_read_tensor */
     int nhwc_pitch;        /* ... bytes between its pixels (0 = nhwc_c; a write-only 255-channel head is kept at 256) */
-    int tail_read;         /* a raw-head decode (mars_hip_detect_heads_device) reads it: a pending tail holds back its writer like a graph output's */
+    int tail_read;         /* a raw-head decode (mars_hip_detect_heads_device / _dfl_device) reads it: a pending tail holds back its writer like a graph output's */
 } mtensor_t;
 
 /* One launch.  The operand model every planner pass and the run path rely on (plan_check enforces it on every plan):
@@ -156,6 +156,9 @@ typedef struct mars_model_ext {
     float *heads_lut_dev;   /* raw-head decode: [head][256] sigmoid tables (mhip_heads_t.sig) */
     float heads_lut_scale[4];
     int heads_lut_n;
+    float *dfl_lut_dev;     /* DFL decode: [head][512] tables (mhip_dfl_heads_t.tab) */
+    float dfl_lut_scale[4][2]; /* effective (box, class) scales they were built for */
+    int dfl_lut_n;
     void *ev_graph_done, *ev_tail_done; /* main->aux and aux->main hand-offs */
     int tail_pending;
     int frame0, run_frames; /* frame range the launches being enqueued cover (a large batch runs as two halves on two streams) */
@@ -243,6 +246,24 @@ MARS_INTERNAL int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, in
 MARS_INTERNAL mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h, mars_heads_cfg_t *c);
 MARS_INTERNAL mars_error_t mars_heads_prepare(mars_model_ext_t *m, const mars_heads_cfg_t *c); /* sigmoid tables up; synchronises if they change */
 MARS_INTERNAL int mars_heads_launch(mars_model_ext_t *m, const mars_heads_cfg_t *c, void *dets_dev, int *counts_dev); /* current stream */
+
+/* raw anchor-free DFL heads (mars_yolo.c): a mars_yolo_dfl_heads_t resolved against the loaded plan.  A head tensor's bytes live in its own
+ * buffer or, where the zero-copy concat made its convolution write a channel slice, inside the concat output's: buf = the tensor that owns
+ * the buffer (the one the writing launch names, so the one tail_read goes on), off = the slice's first byte in it */
+typedef struct {
+    int n, reg_max, stride[4], nc[4], h[4], w[4];
+    int box_t[4], cls_t[4], box_buf[4], cls_buf[4], box_off[4], cls_off[4];
+    int box_pix_step[4], box_ch_step[4], cls_pix_step[4], cls_ch_step[4];
+    float box_scale[4], cls_scale[4]; /* effective: the override, or the tensor's own */
+    float conf, nms;
+    int map, px, py;
+    float rx, ry;
+    int internal; /* some buffer is not a graph output's: one buffer for every batch in flight */
+} mars_dfl_cfg_t;
+MARS_INTERNAL int mars_find_dfl_heads(const mars_model_ext_t *m, int *box_ids, int *cls_ids, int *strides, int *num_classes, int *reg_max, int cap);
+MARS_INTERNAL mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *h, mars_dfl_cfg_t *c);
+MARS_INTERNAL mars_error_t mars_dfl_prepare(mars_model_ext_t *m, const mars_dfl_cfg_t *c); /* tables up; synchronises if they change */
+MARS_INTERNAL int mars_dfl_launch(mars_model_ext_t *m, const mars_dfl_cfg_t *c, void *dets_dev, int *counts_dev); /* current stream */
 
 /* shared host helpers (mars_model.c) */
 int32_t mars_trunc_x86(float x);

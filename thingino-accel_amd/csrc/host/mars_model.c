@@ -121,6 +121,7 @@ void mars_free(mars_model_t *model) {
     if (m->arena_dev) mhip_free(m->arena_dev);
     if (m->det_lut_dev) mhip_free(m->det_lut_dev);
     if (m->heads_lut_dev) mhip_free(m->heads_lut_dev);
+    if (m->dfl_lut_dev) mhip_free(m->dfl_lut_dev);
     if (m->ev_graph_done) mhip_event_destroy(m->ev_graph_done);
     if (m->ev_tail_done) mhip_event_destroy(m->ev_tail_done);
     if (m->ev_fork) mhip_event_destroy(m->ev_fork);
@@ -493,6 +494,15 @@ int mars_yolo_find_heads(const void *data, size_t size, int *tensor_ids, int *st
     mars_model_ext_t *m = NULL;
     if (load_host(data, size, 0, &m) != MARS_OK) return -1;
     const int n = mars_find_heads(m, tensor_ids, strides, num_classes, cap);
+    mars_free(&m->pub);
+    return n;
+}
+
+/* ... and its anchor-free DFL heads (mars_find_dfl_heads) */
+int mars_yolo_find_dfl_heads(const void *data, size_t size, int *box_ids, int *cls_ids, int *strides, int *num_classes, int *reg_max, int cap) {
+    mars_model_ext_t *m = NULL;
+    if (load_host(data, size, 0, &m) != MARS_OK) return -1;
+    const int n = mars_find_dfl_heads(m, box_ids, cls_ids, strides, num_classes, reg_max, cap);
     mars_free(&m->pub);
     return n;
 }

@@ -51,7 +51,8 @@ typedef struct mars_pipe {
     int head, tail, inflight;
     uint8_t *saved_in[MARS_MAX_IO], *saved_out[MARS_MAX_IO]; /* the model's own I/O tensor buffers */
     int batch;
-    mars_heads_cfg_t heads; /* opts.heads resolved at open (heads.n == 0: the tail decodes det_outputs) */
+    mars_heads_cfg_t heads; /* opts.heads resolved at open (heads.n == 0 and dfl.n == 0: the tail decodes det_outputs) */
+    mars_dfl_cfg_t dfl;     /* opts.dfl_heads resolved at open (dfl.n == 0: none) */
     int heads_queued;       /* a raw-head decode has been queued: the next graph's head-writing layers wait for it (ev_tail_done) */
 } mars_pipe_t;
 
@@ -113,7 +114,8 @@ mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t 
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     if (!m->act_dev || !m->arena_dev) return MARS_ERR_NNA_INIT_FAILED;
     if (!opts->download_outputs && !opts->detect) return MARS_ERR_INVALID_LAYER; /* nothing would come back */
-    if (opts->detect && !opts->heads && (opts->n_det_outputs <= 0 || opts->n_det_outputs > 4)) return MARS_ERR_INVALID_TENSOR;
+    if (opts->detect && opts->heads && opts->dfl_heads) return MARS_ERR_INVALID_TENSOR; /* one kind of raw head */
+    if (opts->detect && !opts->heads && !opts->dfl_heads && (opts->n_det_outputs <= 0 || opts->n_det_outputs > 4)) return MARS_ERR_INVALID_TENSOR;
     const int camera = opts->camera_w > 0 && opts->camera_h > 0;
     if ((opts->camera_w > 0) != (opts->camera_h > 0) || opts->camera_w < 0 || opts->camera_h < 0) return MARS_ERR_INVALID_FILE;
     if (model->header.num_inputs > MARS_MAX_IO || model->header.num_outputs > MARS_MAX_IO) return MARS_ERR_INVALID_FILE;
@@ -122,6 +124,7 @@ mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t 
     mars_pipe_t *pp = (mars_pipe_t *)calloc(1, sizeof(*pp));
     if (!pp) return MARS_ERR_ALLOC_FAILED;
     pp->opts = *opts;
+    pp->opts.dfl_heads = NULL; /* (resolved below; the caller's struct need not outlive the call) */
     pp->batch = m->batch;
     m->pipe = pp;
     const size_t B = (size_t)m->batch;
@@ -199,6 +202,13 @@ mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t 
         if (err == MARS_OK) err = mars_heads_prepare(m, &pp->heads);
         if (err == MARS_OK && !m->ev_tail_done && !(m->ev_tail_done = mhip_event_create_sync())) err = MARS_ERR_ALLOC_FAILED;
         for (int k = 0; err == MARS_OK && k < pp->heads.n; k++) m->mt[pp->heads.ti[k]].tail_read = 1;
+    } else if (err == MARS_OK && opts->detect && opts->dfl_heads) { /* DFL heads: likewise */
+        mars_yolo_dfl_heads_t h = *opts->dfl_heads;
+        if (camera && h.src_w == 0 && h.src_h == 0) { h.src_w = opts->camera_w; h.src_h = opts->camera_h; }
+        err = mars_dfl_resolve(m, &h, &pp->dfl);
+        if (err == MARS_OK) err = mars_dfl_prepare(m, &pp->dfl);
+        if (err == MARS_OK && !m->ev_tail_done && !(m->ev_tail_done = mhip_event_create_sync())) err = MARS_ERR_ALLOC_FAILED;
+        for (int k = 0; err == MARS_OK && k < pp->dfl.n; k++) m->mt[pp->dfl.box_buf[k]].tail_read = m->mt[pp->dfl.cls_buf[k]].tail_read = 1;
     } else if (err == MARS_OK && opts->detect) /* decode tables: built and uploaded once, before anything is in flight */
         err = mars_detect_prepare(m, opts->det_outputs, opts->n_det_outputs);
     if (err == MARS_OK && mhip_sync()) err = MARS_ERR_LAYER_FAILED;
@@ -262,7 +272,8 @@ mars_error_t mars_hip_pipe_submit(mars_model_t *model) {
     m->tail_pending = 0; /* ordering is by the slot events here, not by the single-buffer hand-off of mars_hip_detect */
     /* ... except for raw heads that are internal tensors: every slot's graph writes the same buffers, so this graph's head-writing
      * layers wait for the previous batch's decode (the rest of the graph still overlaps it) */
-    if (pp->heads.n && pp->heads.internal && pp->heads_queued) m->tail_pending = 1;
+    const int raw_internal = (pp->heads.n && pp->heads.internal) || (pp->dfl.n && pp->dfl.internal);
+    if (raw_internal && pp->heads_queued) m->tail_pending = 1;
     mars_error_t e = mars_hip_run_device_async(model);
     if (e != MARS_OK) return e;
     if (pp->opts.download_outputs)
@@ -277,9 +288,10 @@ mars_error_t mars_hip_pipe_submit(mars_model_t *model) {
         mhip_select_stream(1);
         rc = mhip_stream_wait(1, sl->ev_graph);
         if (!rc && pp->heads.n) rc = mars_heads_launch(m, &pp->heads, sl->det_dev, sl->cnt_dev);
+        else if (!rc && pp->dfl.n) rc = mars_dfl_launch(m, &pp->dfl, sl->det_dev, sl->cnt_dev);
         else if (!rc) rc = mars_detect_launch(m, pp->opts.det_outputs, pp->opts.n_det_outputs, pp->opts.nms_thresh, sl->det_dev, sl->cnt_dev);
         if (!rc) rc = mhip_event_record(sl->ev_tail);
-        if (!rc && pp->heads.n && pp->heads.internal) {
+        if (!rc && raw_internal) {
             rc = mhip_event_record(m->ev_tail_done);
             pp->heads_queued = 1;
         }

@@ -46,6 +46,15 @@ struct Builder {
     static constexpr float kActScale = 4.0f / 127.0f; // SiLU output
     static constexpr float kHeadScale = 0.05f;
     static constexpr float kInScale = 1.0f / 64.0f;
+    // DFL head (build_yolov5, head == MARS_SYNTH_HEAD_DFL).  Box logits: the usual int8 spread at kHeadScale, peaked distributions over the
+    // 16 bins.  Class logits: aimed at int8 mean -90 (the strongly negative class bias of a trained detector) and sigma 24, and a scale
+    // that puts the 0.25 confidence line (logit -1.0986) at the int8 value where, on the CPU oracle, the width_x16 4 / seed 1 twins give
+    // 10 - 20 candidates per 320 x 320 frame and 60 - 170 per 640 x 640 one (tests/test_yolo_dfl_cpu.py): -35 under NHWC tags, -62
+    // under NCHW tags, whose byte-wise concats leave the heads little besides their biases.  Other seeds and widths are not calibrated.
+    static constexpr float kDflClsScaleNhwc = 0.031f;
+    static constexpr float kDflClsScaleNchw = 0.0176f;
+    static constexpr float kDflClsSigma = 24.0f;
+    static constexpr float kDflClsMean = -90.0f;
 
     bool vary = false; // per-convolution scales (x0.75 .. x1.35 of the nominal ones): every fused table differs
     float jit() { return vary ? 0.75f + 0.6f * rng.unit() : 1.0f; }
@@ -98,7 +107,8 @@ struct Builder {
     float scale_of(const T &t) const { return tensors[t.id].scale; }
 
     // conv (+ optional SiLU as Sigmoid+Mul).  relu: fused ReLU activation instead.
-    T conv(const T &x, int cout, int k, int s, bool silu, bool relu, float out_scale_override = 0.f) {
+    // sigma_q / mean_q: spread and mean of the int8 result (the defaults draw the same bytes as ever)
+    T conv(const T &x, int cout, int k, int s, bool silu, bool relu, float out_scale_override = 0.f, float sigma_q = 48.0f, float mean_q = 0.f) {
         const int K = k * k * x.c;
         const int oh = (x.h + s - 1) / s, ow = (x.w + s - 1) / s;
         const std::string base = "conv" + std::to_string(layers.size());
@@ -118,13 +128,14 @@ struct Builder {
         } else {
             std::vector<int8_t> w((size_t)cout * K);
             for (auto &v : w) v = (int8_t)rng.range(-127, 127);
-            // sigma(acc) = 73.3 * sqrt(K) * rms_in; aim the int8 result at sigma 48
+            // sigma(acc) = 73.3 * sqrt(K) * rms_in; aim the int8 result at sigma 48 (sigma_q)
             const float sigma_acc = 73.3f * std::sqrt((float)K) * x.rms;
-            const float cs = 48.0f / sigma_acc;
+            const float cs = sigma_q / sigma_acc;
             w_scale = cs * out_scale / scale_of(x);
             std::vector<int32_t> b(cout);
             const int half = (int)(sigma_acc * 0.5f) + 1;
-            for (auto &v : b) v = rng.range(-half, half);
+            const int shift = (int)(mean_q / cs);
+            for (auto &v : b) v = rng.range(-half, half) + shift;
             if (nchw)
                 wid = add_tensor(base + ".w", MARS_DTYPE_INT8, MARS_FORMAT_OIHW, {cout, x.c, k, k}, w_scale,
                                  w.data(), w.size());
@@ -255,7 +266,7 @@ size_t build_tiny(const mars_synth_opts_t &o, void *buf, size_t cap) {
     return b.serialise({x.id}, {y.id}, buf, cap);
 }
 
-size_t build_yolov5(const mars_synth_opts_t &o, void *buf, size_t cap) {
+size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap) {
     Builder b(o.float32 != 0, o.nchw_int8 != 0, o.seed);
     b.vary = o.vary_scales != 0;
     const int hw = o.input_hw > 0 ? o.input_hw : 640;
@@ -285,6 +296,19 @@ size_t build_yolov5(const mars_synth_opts_t &o, void *buf, size_t cap) {
     T h20 = b.c3(b.concat({h18, h14}), ch(512), dep(3), false);
     T h21 = b.conv(h20, ch(512), 3, 2, true, false);
     T h23 = b.c3(b.concat({h21, h10}), ch(1024), dep(3), false);
+    if (head == MARS_SYNTH_HEAD_DFL) {
+        // anchor-free Detect: per scale a box branch and a class branch (conv3x3 + SiLU twice, then a plain 1x1), concatenated; the three
+        // concats are the graph outputs (the exported softmax / dist2bbox chain behind them is what mars_hip_detect_dfl computes)
+        const int c2 = 64, c3 = h17.c > 80 ? h17.c : 80;
+        std::vector<int> outs;
+        for (const T &p : {h17, h20, h23}) {
+            T bx = b.conv(b.conv(b.conv(p, c2, 3, 1, true, false), c2, 3, 1, true, false), 64, 1, 1, false, false, Builder::kHeadScale);
+            T cl = b.conv(b.conv(b.conv(p, c3, 3, 1, true, false), c3, 3, 1, true, false), 80, 1, 1, false, false, b.nchw ? Builder::kDflClsScaleNchw : Builder::kDflClsScaleNhwc,
+                          Builder::kDflClsSigma, Builder::kDflClsMean);
+            outs.push_back(b.concat({bx, cl}).id);
+        }
+        return b.serialise({x.id}, outs, buf, cap);
+    }
     // detect: one 1x1 conv per scale, 3 anchors x 85 = 255 channels, shared output scale
     T d0 = b.conv(h17, 255, 1, 1, false, false, Builder::kHeadScale);
     T d1 = b.conv(h20, 255, 1, 1, false, false, Builder::kHeadScale);
@@ -300,8 +324,13 @@ size_t build_yolov5(const mars_synth_opts_t &o, void *buf, size_t cap) {
 
 } // namespace
 
-extern "C" size_t mars_synth_model(const mars_synth_opts_t *opts, void *buf, size_t cap) {
-    if (!opts) return 0;
+extern "C" size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap) {
+    if (!opts || (head != MARS_SYNTH_HEAD_ANCHOR && head != MARS_SYNTH_HEAD_DFL)) return 0;
     if (opts->input_hw < 0 || (opts->tiny == 0 && opts->input_hw % 32 != 0)) return 0;
-    return opts->tiny ? build_tiny(*opts, buf, cap) : build_yolov5(*opts, buf, cap);
+    if (head == MARS_SYNTH_HEAD_DFL && (opts->tiny || opts->float32)) return 0;
+    return opts->tiny ? build_tiny(*opts, buf, cap) : build_yolov5(*opts, head, buf, cap);
+}
+
+extern "C" size_t mars_synth_model(const mars_synth_opts_t *opts, void *buf, size_t cap) {
+    return mars_synth_model_head(opts, MARS_SYNTH_HEAD_ANCHOR, buf, cap);
 }

@@ -263,6 +263,21 @@ int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, int *strides, in
     return n;
 }
 
+/* the letterbox of mars_preproc.c (the reference's load_image, mars_yolo_test.c:47-49) of w x hs frames for a tw x th graph input, as
+ * the mapping of the kept boxes back into the frame */
+static mars_error_t letterbox_of(int w, int hs, int tw, int th, int *map, int *px, int *py, float *rx, float *ry) {
+    if (w <= 0 || hs <= 0) return MARS_ERR_INVALID_TENSOR;
+    const float scale = fminf((float)tw / w, (float)th / hs);
+    const int nw = (int)(w * scale), nh = (int)(hs * scale);
+    if (nw <= 0 || nh <= 0) return MARS_ERR_INVALID_TENSOR;
+    *map = 1;
+    *px = (tw - nw) / 2;
+    *py = (th - nh) / 2;
+    *rx = (float)w / (float)nw;
+    *ry = (float)hs / (float)nh;
+    return MARS_OK;
+}
+
 static const float k_default_anchors[3][3][2] = {{{10, 13}, {16, 30}, {33, 23}}, {{30, 61}, {62, 45}, {59, 119}}, {{116, 90}, {156, 198}, {373, 326}}};
 
 mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h, mars_heads_cfg_t *c) {
@@ -310,19 +325,7 @@ mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h,
     else return MARS_ERR_INVALID_TENSOR; /* no default anchors for a fourth head */
     c->conf = h->conf_thresh != 0 ? h->conf_thresh : 0.25f;
     c->nms = h->nms_thresh != 0 ? h->nms_thresh : 0.45f;
-    if (h->src_w || h->src_h) {
-        if (h->src_w <= 0 || h->src_h <= 0) return MARS_ERR_INVALID_TENSOR;
-        /* the letterbox of mars_preproc.c (the reference's load_image, mars_yolo_test.c:47-49) for the graph input's size */
-        const int w = h->src_w, hs = h->src_h, tw = iw, th = ih;
-        const float scale = fminf((float)tw / w, (float)th / hs);
-        const int nw = (int)(w * scale), nh = (int)(hs * scale);
-        if (nw <= 0 || nh <= 0) return MARS_ERR_INVALID_TENSOR;
-        c->map = 1;
-        c->px = (tw - nw) / 2;
-        c->py = (th - nh) / 2;
-        c->rx = (float)w / (float)nw;
-        c->ry = (float)hs / (float)nh;
-    }
+    if (h->src_w || h->src_h) return letterbox_of(h->src_w, h->src_h, iw, ih, &c->map, &c->px, &c->py, &c->rx, &c->ry);
     return MARS_OK;
 }
 
@@ -373,34 +376,47 @@ int mars_heads_launch(mars_model_ext_t *m, const mars_heads_cfg_t *c, void *dets
     return mhip_detect_heads(&p);
 }
 
-mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_heads_t *heads) {
-    if (!model) return MARS_ERR_INVALID_TENSOR;
-    mars_model_ext_t *m = (mars_model_ext_t *)model;
-    mars_heads_cfg_t c;
-    mars_error_t e = mars_heads_resolve(m, heads, &c);
-    if (e != MARS_OK) return e;
-    if (m->det_cap < m->batch || !m->det_dev) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
-        if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
-        m->det_lut_n = 0;
-    }
-    e = mars_heads_prepare(m, &c);
-    if (e != MARS_OK) return e;
-    /* as mars_hip_detect_device: the decode runs on the auxiliary stream behind the graph, and the next run's layers that write a head
-     * wait for it (tail_read) -- the heads of the shipped files are internal tensors, not graph outputs */
-    for (int k = 0; k < c.n; k++) m->mt[c.ti[k]].tail_read = 1;
+/* the model's own detection buffers, large enough for the current batch */
+static mars_error_t own_det_buffers(mars_model_ext_t *m) {
+    if (m->det_cap >= m->batch && m->det_dev) return MARS_OK;
+    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
+    if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
+    m->det_lut_n = 0;
+    return MARS_OK;
+}
+
+/* as mars_hip_detect_device: a raw-head decode (launch(m, cfg, dets, counts) on the current stream) runs on the auxiliary stream behind the
+ * graph, and the next run's layers that write a tensor it reads wait for it (tail_read, set by the caller) -- the heads of the shipped
+ * files are internal tensors, not graph outputs */
+static mars_error_t tail_on_aux(mars_model_ext_t *m, int (*launch)(mars_model_ext_t *, const void *, void *, int *), const void *cfg) {
     if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
     if (!m->ev_tail_done) m->ev_tail_done = mhip_event_create_sync();
     if (!m->ev_graph_done || !m->ev_tail_done) return MARS_ERR_ALLOC_FAILED;
     if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
     mhip_select_aux(1);
     int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc) rc = mars_heads_launch(m, &c, m->det_dev, m->det_counts_dev);
+    if (!rc) rc = launch(m, cfg, m->det_dev, m->det_counts_dev);
     if (!rc) rc = mhip_event_record(m->ev_tail_done);
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;
     m->tail_pending = 1;
     return MARS_OK;
+}
+
+static int heads_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, int *counts_dev) {
+    return mars_heads_launch(m, (const mars_heads_cfg_t *)cfg, dets_dev, counts_dev);
+}
+
+mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_heads_t *heads) {
+    if (!model) return MARS_ERR_INVALID_TENSOR;
+    mars_model_ext_t *m = (mars_model_ext_t *)model;
+    mars_heads_cfg_t c;
+    mars_error_t e = mars_heads_resolve(m, heads, &c);
+    if (e == MARS_OK) e = own_det_buffers(m);
+    if (e == MARS_OK) e = mars_heads_prepare(m, &c);
+    if (e != MARS_OK) return e;
+    for (int k = 0; k < c.n; k++) m->mt[c.ti[k]].tail_read = 1;
+    return tail_on_aux(m, heads_launch_cb, &c);
 }
 
 mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int *counts) {
@@ -418,5 +434,221 @@ mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int 
 mars_error_t mars_hip_detect_heads(mars_model_t *model, const mars_yolo_heads_t *heads, mars_det_t *dets, int *counts) {
     if (!dets || !counts) return MARS_ERR_INVALID_TENSOR;
     mars_error_t e = mars_hip_detect_heads_device(model, heads);
+    return e != MARS_OK ? e : mars_hip_detect_results(model, dets, counts);
+}
+
+/* ---- raw anchor-free DFL heads (include/mars_hip.h: mars_hip_detect_dfl) */
+/* index of the CONV2D layer that does something and writes tensor T, or -1 */
+static int conv_layer_of(const mars_model_ext_t *m, int T) {
+    const uint32_t id = m->pub.tensors[T].desc.id;
+    for (uint32_t li = 0; li < m->pub.header.num_layers; li++) {
+        const mars_layer_t *L = &m->pub.layers[li].desc;
+        if (L->type == MARS_LAYER_CONV2D && L->num_outputs >= 1 && !m->layer_noop[li] && L->output_tensor_ids[0] == id) return (int)li;
+    }
+    return -1;
+}
+
+/* layers that do something and read tensor T, `except` not counted */
+static int real_readers(const mars_model_ext_t *m, int T, uint32_t except) {
+    const uint32_t id = m->pub.tensors[T].desc.id;
+    int n = 0;
+    for (uint32_t lj = 0; lj < m->pub.header.num_layers; lj++) {
+        const mars_layer_t *R = &m->pub.layers[lj].desc;
+        if (lj == except || m->layer_noop[lj]) continue;
+        for (uint32_t k = 0; k < R->num_inputs && k < 4; k++)
+            if (R->input_tensor_ids[k] == id) { n++; break; }
+    }
+    return n;
+}
+
+int mars_find_dfl_heads(const mars_model_ext_t *m, int *box_ids, int *cls_ids, int *strides, int *num_classes, int *reg_max, int cap) {
+    const uint32_t nl = m->pub.header.num_layers;
+    int ih, iw, n = 0, bt[4], ct[4], st[4], nc[4], rm[4];
+    if (input_hw(m, &ih, &iw)) return 0;
+    for (uint32_t li = 0; li < nl; li++) {
+        const mars_layer_t *L = &m->pub.layers[li].desc;
+        if (L->type != MARS_LAYER_CONCAT || L->num_inputs != 2 || L->num_outputs < 1 || m->layer_noop[li]) continue;
+        const int A = tensor_by_id(m, L->input_tensor_ids[0]), B = tensor_by_id(m, L->input_tensor_ids[1]), O = tensor_by_id(m, L->output_tensor_ids[0]);
+        if (A < 0 || B < 0 || O < 0 || A == B) continue;
+        int ca, ha, wa, cb, hb, wb, ok = 1;
+        for (int q = 0; q < 2 && ok; q++) { /* int8 activations out of convolutions, read by this CONCAT alone */
+            const int T = q ? B : A;
+            ok = !m->mt[T].is_weight && m->pub.tensors[T].desc.dtype == MARS_DTYPE_INT8 && conv_layer_of(m, T) >= 0 && !real_readers(m, T, li);
+        }
+        if (!ok || tensor_chw(&m->pub.tensors[A].desc, &ca, &ha, &wa) || tensor_chw(&m->pub.tensors[B].desc, &cb, &hb, &wb)) continue;
+        if (ha != hb || wa != wb || ih % ha || iw % wa || ih / ha != iw / wa) continue;
+        if (ca % 4 || ca / 4 < 2 || ca / 4 > 32) continue;
+        if (!m->mt[O].io_out && real_readers(m, O, nl)) continue;
+        if (n < 4) { bt[n] = A; ct[n] = B; st[n] = ih / ha; nc[n] = cb; rm[n] = ca / 4; }
+        n++;
+    }
+    const int kept = n < 4 ? n : 4;
+    for (int i = 1; i < kept; i++) /* by stride, stable */
+        for (int j = i; j > 0 && st[j - 1] > st[j]; j--) {
+            int t;
+#define SWAP(a) t = a[j]; a[j] = a[j - 1]; a[j - 1] = t
+            SWAP(bt); SWAP(ct); SWAP(st); SWAP(nc); SWAP(rm);
+#undef SWAP
+        }
+    for (int i = 0; i < kept && i < cap; i++) {
+        if (box_ids) box_ids[i] = bt[i];
+        if (cls_ids) cls_ids[i] = ct[i];
+        if (strides) strides[i] = st[i];
+        if (num_classes) num_classes[i] = nc[i];
+        if (reg_max) reg_max[i] = rm[i];
+    }
+    return n;
+}
+
+/* Where the plan left the int8 bytes of head tensor T ([ch] channels on an hh x ww grid): its own buffer -- planes [C][H][W], or pixel rows
+ * at the writing convolution's pitch (NHWC tensors, NCHW-tagged ones held pixels x channels) -- or, where the zero-copy concat redirected
+ * that convolution, a channel slice of the concat output's pixel rows.  0, or -1 if there are no such bytes. */
+static int dfl_locate(const mars_model_ext_t *m, int T, int ch, int hh, int ww, int *buf, int *off, int *pix_step, int *ch_step) {
+    const mtensor_t *t = &m->mt[T];
+    const mars_op_t *wr = NULL;
+    if (t->is_weight || t->partial) return -1;
+    for (int i = 0; i < m->n_ops && !wr; i++)
+        if (m->ops[i].kind == OP_CONV_I8 && m->ops[i].t_out == T) wr = &m->ops[i];
+    if (wr) {
+        if (!t->dev || wr->out_ch_off || wr->out_byte_off || wr->out_c != ch || wr->out_h != hh || wr->out_w != ww) return -1;
+        *buf = T;
+        *off = 0;
+        if (wr->out_nchw) { *pix_step = 1; *ch_step = hh * ww; }
+        else { *pix_step = wr->out_pix_stride ? wr->out_pix_stride : ch; *ch_step = 1; }
+        return 0;
+    }
+    const int li = conv_layer_of(m, T);
+    for (int i = 0; i < m->n_ops && li >= 0; i++) {
+        const mars_op_t *o = &m->ops[i];
+        if (o->kind != OP_CONV_I8 || o->layer != li) continue;
+        /* a plain convolution (no folded table or Add: the slice then holds T's bytes) writing rows of a wider tensor */
+        if (o->t_out < 0 || o->t_out == T || o->out_nchw || o->out_byte_off || o->lut_off != NO_OFF || o->add_t || o->out_pix_stride <= 0 ||
+            o->out_ch_off < 0 || o->out_ch_off + ch > o->out_pix_stride || o->out_c != ch || o->out_h != hh || o->out_w != ww ||
+            !m->mt[o->t_out].dev || m->mt[o->t_out].partial)
+            return -1;
+        *buf = o->t_out;
+        *off = o->out_ch_off;
+        *pix_step = o->out_pix_stride;
+        *ch_step = 1;
+        return 0;
+    }
+    return -1;
+}
+
+mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *h, mars_dfl_cfg_t *c) {
+    mars_yolo_dfl_heads_t zero;
+    memset(&zero, 0, sizeof(zero));
+    if (!h) h = &zero;
+    memset(c, 0, sizeof(*c));
+    int ih, iw;
+    if (h->n_heads < 0 || h->n_heads > 4 || h->reg_max < 0 || input_hw(m, &ih, &iw)) return MARS_ERR_INVALID_TENSOR;
+    int n = h->n_heads;
+    if (n == 0) {
+        n = mars_find_dfl_heads(m, c->box_t, c->cls_t, NULL, NULL, NULL, 4);
+        if (n <= 0 || n > 4) return MARS_ERR_INVALID_TENSOR;
+    } else {
+        memcpy(c->box_t, h->box_tensors, sizeof(c->box_t));
+        memcpy(c->cls_t, h->cls_tensors, sizeof(c->cls_t));
+    }
+    c->n = n;
+    for (int k = 0; k < n; k++) {
+        const int A = c->box_t[k], B = c->cls_t[k];
+        if (A < 0 || B < 0 || (uint32_t)A >= m->pub.header.num_tensors || (uint32_t)B >= m->pub.header.num_tensors) return MARS_ERR_INVALID_TENSOR;
+        const mars_tensor_t *da = &m->pub.tensors[A].desc, *db = &m->pub.tensors[B].desc;
+        int ca, ha, wa, cb, hb, wb;
+        if (da->dtype != MARS_DTYPE_INT8 || db->dtype != MARS_DTYPE_INT8 || tensor_chw(da, &ca, &ha, &wa) || tensor_chw(db, &cb, &hb, &wb) ||
+            ha != hb || wa != wb)
+            return MARS_ERR_INVALID_TENSOR;
+        const int R = h->reg_max ? h->reg_max : ca / 4;
+        if (ca != 4 * R || R < 2 || R > 32 || (k && R != c->reg_max)) return MARS_ERR_INVALID_TENSOR;
+        c->reg_max = R;
+        if (dfl_locate(m, A, ca, ha, wa, &c->box_buf[k], &c->box_off[k], &c->box_pix_step[k], &c->box_ch_step[k]) ||
+            dfl_locate(m, B, cb, hb, wb, &c->cls_buf[k], &c->cls_off[k], &c->cls_pix_step[k], &c->cls_ch_step[k]))
+            return MARS_ERR_INVALID_TENSOR;
+        c->box_scale[k] = h->box_scales[k] != 0 ? h->box_scales[k] : da->scale;
+        c->cls_scale[k] = h->cls_scales[k] != 0 ? h->cls_scales[k] : db->scale;
+        if (!(c->box_scale[k] > 0) || !(c->cls_scale[k] > 0)) return MARS_ERR_INVALID_TENSOR;
+        c->h[k] = ha; c->w[k] = wa; c->nc[k] = cb;
+        c->stride[k] = h->strides[k] > 0 ? h->strides[k] : ih / ha;
+        if (h->strides[k] < 0 || c->stride[k] <= 0) return MARS_ERR_INVALID_TENSOR;
+        if (!m->mt[c->box_buf[k]].io_out || !m->mt[c->cls_buf[k]].io_out) c->internal = 1;
+    }
+    c->conf = h->conf_thresh != 0 ? h->conf_thresh : 0.25f;
+    c->nms = h->nms_thresh != 0 ? h->nms_thresh : 0.45f;
+    if (h->src_w || h->src_h) return letterbox_of(h->src_w, h->src_h, iw, ih, &c->map, &c->px, &c->py, &c->rx, &c->ry);
+    return MARS_OK;
+}
+
+/* per head E[d] = expf(-(d * box scale)), d = 0 .. 255, and the class sigmoid (the anchor path's table, by the same expression); they depend
+ * only on the effective scales: built and uploaded once.  Synchronises when they change. */
+mars_error_t mars_dfl_prepare(mars_model_ext_t *m, const mars_dfl_cfg_t *c) {
+    if (!m->dfl_lut_dev) m->dfl_lut_dev = (float *)mhip_malloc(4 * 512 * sizeof(float));
+    if (!m->dfl_lut_dev) return MARS_ERR_ALLOC_FAILED;
+    int stale = m->dfl_lut_n != c->n;
+    for (int k = 0; k < c->n; k++)
+        if (memcmp(&m->dfl_lut_scale[k][0], &c->box_scale[k], sizeof(float)) != 0 || memcmp(&m->dfl_lut_scale[k][1], &c->cls_scale[k], sizeof(float)) != 0)
+            stale = 1;
+    if (!stale) return MARS_OK;
+    float lut[4 * 512], tab[768];
+    for (int k = 0; k < c->n; k++) {
+        for (int d = 0; d < 256; d++) lut[k * 512 + d] = expf(-((float)d * c->box_scale[k]));
+        build_decode_lut(c->cls_scale[k], tab);
+        memcpy(lut + k * 512 + 256, tab + 256, 256 * sizeof(float));
+    }
+    if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
+    m->dfl_lut_n = 0; /* (until the new tables are up) */
+    if (mhip_h2d_async(m->dfl_lut_dev, lut, (size_t)c->n * 512 * sizeof(float)) || mhip_sync())
+        return MARS_ERR_LAYER_FAILED; /* `lut` is on this stack frame */
+    for (int k = 0; k < c->n; k++) { m->dfl_lut_scale[k][0] = c->box_scale[k]; m->dfl_lut_scale[k][1] = c->cls_scale[k]; }
+    m->dfl_lut_n = c->n;
+    return MARS_OK;
+}
+
+int mars_dfl_launch(mars_model_ext_t *m, const mars_dfl_cfg_t *c, void *dets_dev, int *counts_dev) {
+    mhip_dfl_heads_t p;
+    memset(&p, 0, sizeof(p));
+    for (int k = 0; k < c->n; k++) {
+        const mtensor_t *tb = &m->mt[c->box_buf[k]], *tc = &m->mt[c->cls_buf[k]];
+        if (!tb->dev || !tc->dev) return -1;
+        p.box[k] = (const int8_t *)tb->dev + c->box_off[k];
+        p.cls[k] = (const int8_t *)tc->dev + c->cls_off[k];
+        p.box_frame_stride[k] = tb->stride; p.cls_frame_stride[k] = tc->stride;
+        p.h[k] = c->h[k]; p.w[k] = c->w[k]; p.nc[k] = c->nc[k];
+        p.box_pix_step[k] = c->box_pix_step[k]; p.box_ch_step[k] = c->box_ch_step[k];
+        p.cls_pix_step[k] = c->cls_pix_step[k]; p.cls_ch_step[k] = c->cls_ch_step[k];
+        p.stride[k] = c->stride[k];
+    }
+    p.reg_max = c->reg_max;
+    p.tab = m->dfl_lut_dev;
+    p.nheads = c->n;
+    p.frames = m->batch;
+    p.conf = c->conf;
+    p.nms_thresh = c->nms;
+    p.dets = dets_dev;
+    p.counts = counts_dev;
+    p.raw_counts = counts_dev + m->batch;
+    p.map = c->map; p.px = c->px; p.py = c->py; p.rx = c->rx; p.ry = c->ry;
+    return mhip_detect_dfl(&p);
+}
+
+static int dfl_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, int *counts_dev) {
+    return mars_dfl_launch(m, (const mars_dfl_cfg_t *)cfg, dets_dev, counts_dev);
+}
+
+mars_error_t mars_hip_detect_dfl_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads) {
+    if (!model) return MARS_ERR_INVALID_TENSOR;
+    mars_model_ext_t *m = (mars_model_ext_t *)model;
+    mars_dfl_cfg_t c;
+    mars_error_t e = mars_dfl_resolve(m, heads, &c);
+    if (e == MARS_OK) e = own_det_buffers(m);
+    if (e == MARS_OK) e = mars_dfl_prepare(m, &c);
+    if (e != MARS_OK) return e;
+    for (int k = 0; k < c.n; k++) m->mt[c.box_buf[k]].tail_read = m->mt[c.cls_buf[k]].tail_read = 1;
+    return tail_on_aux(m, dfl_launch_cb, &c);
+}
+
+mars_error_t mars_hip_detect_dfl(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, mars_det_t *dets, int *counts) {
+    if (!dets || !counts) return MARS_ERR_INVALID_TENSOR;
+    mars_error_t e = mars_hip_detect_dfl_device(model, heads);
     return e != MARS_OK ? e : mars_hip_detect_results(model, dets, counts);
 }

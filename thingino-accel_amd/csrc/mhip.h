@@ -302,6 +302,24 @@ typedef struct {
     float rx, ry;
 } mhip_heads_t;
 int mhip_detect_heads(const mhip_heads_t *p);
+/* raw anchor-free DFL heads (yolo_tail.hip: dfl_decode_kernel): per head a box tensor of 4 * reg_max channels and a class tensor of nc
+ * channels on the same grid, decoded in prediction order (head, gy, gx); then sort + NMS and the letterbox mapping as mhip_detect_heads */
+typedef struct {
+    const int8_t *box[4], *cls[4]; size_t box_frame_stride[4], cls_frame_stride[4]; /* tensor X of head k, frame f: X[k] + f * X_frame_stride[k] */
+    int h[4], w[4], nc[4];
+    int box_pix_step[4], box_ch_step[4], cls_pix_step[4], cls_ch_step[4]; /* byte of (pixel p, channel c) = p * pix_step + c * ch_step */
+    int stride[4];
+    int reg_max;            /* bins per box side, 2 .. 32 */
+    const float *tab;       /* device [head][512]: E[d] = expf(-(d * box scale)) at d = 0 .. 255, then 1 / (1 + expf(-q * class scale)) at 256 + q + 128 */
+    int nheads, frames;
+    float conf, nms_thresh;
+    void *dets;             /* device [frames][1000] records of 24 bytes */
+    int *counts;            /* device [frames] kept */
+    int *raw_counts;        /* device [frames] candidates before NMS (or NULL) */
+    int map, px, py;
+    float rx, ry;
+} mhip_dfl_heads_t;
+int mhip_detect_dfl(const mhip_dfl_heads_t *p);
 
 /* ---- image front-end (preproc.hip): letterbox resize + (px - 128); tables from csrc/host/mars_preproc.c */
 typedef struct {

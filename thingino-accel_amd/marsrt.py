@@ -85,9 +85,16 @@ class YoloHeads(C.Structure):  # mars_yolo_heads_t: zero = default in every fiel
                 ("conf_thresh", C.c_float), ("nms_thresh", C.c_float), ("src_w", C.c_int), ("src_h", C.c_int)]
 
 
+class YoloDflHeads(C.Structure):  # mars_yolo_dfl_heads_t: zero = default in every field
+    _fields_ = [("n_heads", C.c_int), ("box_tensors", C.c_int * 4), ("cls_tensors", C.c_int * 4), ("strides", C.c_int * 4),
+                ("reg_max", C.c_int), ("box_scales", C.c_float * 4), ("cls_scales", C.c_float * 4), ("conf_thresh", C.c_float),
+                ("nms_thresh", C.c_float), ("src_w", C.c_int), ("src_h", C.c_int)]
+
+
 class PipeOpts(C.Structure):
     _fields_ = [("download_outputs", C.c_int), ("detect", C.c_int), ("det_outputs", C.c_int * 4), ("n_det_outputs", C.c_int),
-                ("nms_thresh", C.c_float), ("camera_w", C.c_int), ("camera_h", C.c_int), ("heads", C.POINTER(YoloHeads))]
+                ("nms_thresh", C.c_float), ("camera_w", C.c_int), ("camera_h", C.c_int), ("heads", C.POINTER(YoloHeads)),
+                ("dfl_heads", C.POINTER(YoloDflHeads))]
 
 
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
@@ -122,7 +129,8 @@ EXPORTS = {
                    "mars_hip_preprocess", "mars_hip_preprocess_device", "mars_hip_tensor_frame_bytes", "mars_hip_tensor_byte_size", "mars_hip_pipe_open",
                    "mars_hip_pipe_input", "mars_hip_pipe_submit", "mars_hip_pipe_wait", "mars_hip_pipe_close", "mars_hip_pipe_camera_ms", "mars_hip_set_output_mode",
                    "mars_hip_get_tuning", "mars_hip_model_set_tuning", "mars_hip_model_get_tuning", "mars_yolo_find_heads",
-                   "mars_hip_detect_heads", "mars_hip_detect_heads_device", "mars_hip_detect_results"],
+                   "mars_hip_detect_heads", "mars_hip_detect_heads_device", "mars_hip_detect_results", "mars_yolo_find_dfl_heads",
+                   "mars_hip_detect_dfl", "mars_hip_detect_dfl_device", "mars_synth_model_head"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -215,12 +223,17 @@ def lib():
     L.mars_hip_detect_heads.argtypes = [P(MarsModel), P(YoloHeads), C.c_void_p, P(C.c_int)]
     L.mars_hip_detect_heads_device.argtypes = [P(MarsModel), P(YoloHeads)]
     L.mars_hip_detect_results.argtypes = [P(MarsModel), C.c_void_p, P(C.c_int)]
+    L.mars_yolo_find_dfl_heads.argtypes = [C.c_void_p, C.c_size_t, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), C.c_int]
+    L.mars_hip_detect_dfl.argtypes = [P(MarsModel), P(YoloDflHeads), C.c_void_p, P(C.c_int)]
+    L.mars_hip_detect_dfl_device.argtypes = [P(MarsModel), P(YoloDflHeads)]
     L.mars_compile_onnx.restype = C.c_size_t
     L.mars_compile_onnx.argtypes = [C.c_char_p, C.c_size_t, P(CompileOpts), C.c_void_p, C.c_size_t]
     L.mars_compile_file.argtypes = [C.c_char_p, C.c_char_p, P(CompileOpts)]
     L.mars_compile_last_error.restype = C.c_char_p
     L.mars_synth_model.restype = C.c_size_t
     L.mars_synth_model.argtypes = [P(SynthOpts), C.c_void_p, C.c_size_t]
+    L.mars_synth_model_head.restype = C.c_size_t
+    L.mars_synth_model_head.argtypes = [P(SynthOpts), C.c_int, C.c_void_p, C.c_size_t]
     conv_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                  C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     for n in ("conv2d_int8_mxu", "conv2d_int8_nhwc_mxu"):
@@ -267,14 +280,23 @@ def letterbox(rgb, tw, th, nhwc=True):
     return out
 
 
-def synth_model(width_x16=8, depth_x3=1, input_hw=640, float32=False, nchw_int8=False, seed=1, tiny=False, vary_scales=False):
-    """Bytes of a synthetic well-formed .mars graph (mars_synth_model)."""
+SYNTH_HEADS = {"anchor": 0, "dfl": 1}  # MARS_SYNTH_HEAD_*
+
+
+def synth_model(width_x16=8, depth_x3=1, input_hw=640, float32=False, nchw_int8=False, seed=1, tiny=False, vary_scales=False, head="anchor"):
+    """Bytes of a synthetic well-formed .mars graph (mars_synth_model; head="dfl": mars_synth_model_head with the anchor-free DFL
+    Detect head, int8 only)."""
     o = SynthOpts(width_x16, depth_x3, input_hw, int(float32), int(nchw_int8), seed, int(tiny), int(vary_scales))
-    n = lib().mars_synth_model(C.byref(o), None, 0)
+    if head == "anchor":
+        make = lib().mars_synth_model
+    else:
+        hd = SYNTH_HEADS[head]
+        make = lambda opts, buf, cap: lib().mars_synth_model_head(opts, hd, buf, cap)  # noqa: E731
+    n = make(C.byref(o), None, 0)
     if n == 0:
         raise ValueError("mars_synth_model rejected the options")
     buf = (C.c_uint8 * n)()
-    assert lib().mars_synth_model(C.byref(o), buf, n) == n
+    assert make(C.byref(o), buf, n) == n
     return bytes(buf)
 
 
@@ -318,6 +340,38 @@ def yolo_heads(heads=None, anchors=None, conf=0.25, thresh=0.45, src=None):
     if anchors is not None:
         for i, v in enumerate(np.asarray(anchors, dtype=np.float32).reshape(-1)):
             h.anchors[i] = float(v)
+    h.conf_thresh, h.nms_thresh = conf, thresh
+    if src is not None:
+        h.src_w, h.src_h = int(src[0]), int(src[1])
+    return h
+
+
+def find_yolo_dfl_heads(file_bytes):
+    """anchor-free DFL heads of a .mars file (mars_yolo_find_dfl_heads; host only: works without a GPU), by stride:
+    ([(box tensor index, class tensor index, stride)], classes, reg_max) -- classes and reg_max of the first head, 0 if there is none.
+    ValueError if the loader rejects the file."""
+    b = bytes(file_bytes)
+    bt, ct, st, nc, rm = ((C.c_int * 4)() for _ in range(5))
+    n = lib().mars_yolo_find_dfl_heads(b, len(b), bt, ct, st, nc, rm, 4)
+    if n < 0:
+        raise ValueError("the loader rejects the file")
+    return [(bt[k], ct[k], st[k]) for k in range(min(n, 4))], nc[0] if n else 0, rm[0] if n else 0
+
+
+def yolo_dfl_heads(heads=None, reg_max=0, box_scales=None, cls_scales=None, conf=0.25, thresh=0.45, src=None):
+    """mars_yolo_dfl_heads_t.  heads: None (found on the loaded file) or a list of (box tensor, class tensor[, stride]); box_scales /
+    cls_scales: None (the tensors' own), one number for every head or a list; src = (w, h): boxes mapped back through the letterbox
+    of frames of that size"""
+    h = YoloDflHeads()
+    for k, e in enumerate(heads or ()):
+        h.box_tensors[k], h.cls_tensors[k] = int(e[0]), int(e[1])
+        h.strides[k] = int(e[2]) if len(e) > 2 else 0
+    h.n_heads = len(heads or ())
+    h.reg_max = int(reg_max)
+    for dst, v in ((h.box_scales, box_scales), (h.cls_scales, cls_scales)):
+        if v is not None:
+            for k, x in enumerate(v if isinstance(v, (tuple, list)) else [v] * 4):
+                dst[k] = float(x)
     h.conf_thresh, h.nms_thresh = conf, thresh
     if src is not None:
         h.src_w, h.src_h = int(src[0]), int(src[1])
@@ -506,8 +560,24 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_detect_heads_device")
 
+    def detect_dfl(self, heads=None, **kw):
+        """decode + NMS of raw anchor-free DFL heads (mars_hip_detect_dfl): a record array per frame, as detect().  Arguments as for
+        yolo_dfl_heads()."""
+        h = yolo_dfl_heads(heads, **kw)
+        dets = np.zeros((self.batch, MAX_DET), dtype=DET_DTYPE)
+        counts = np.zeros(self.batch, dtype=np.int32)
+        rc = lib().mars_hip_detect_dfl(self.p, C.byref(h), dets.ctypes.data, counts.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_dfl")
+        return [dets[f, :counts[f]].copy() for f in range(self.batch)]
+
+    def detect_dfl_device(self, heads=None, **kw):
+        rc = lib().mars_hip_detect_dfl_device(self.p, C.byref(yolo_dfl_heads(heads, **kw)))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_dfl_device")
+
     def detect_results(self):
-        """the detections the last detect_device / detect_heads_device left in HBM (mars_hip_detect_results)"""
+        """the detections the last detect_device / detect_heads_device / detect_dfl_device left in HBM (mars_hip_detect_results)"""
         dets = np.zeros((self.batch, MAX_DET), dtype=DET_DTYPE)
         counts = np.zeros(self.batch, dtype=np.int32)
         rc = lib().mars_hip_detect_results(self.p, dets.ctypes.data, counts.ctypes.data_as(C.POINTER(C.c_int)))
@@ -516,16 +586,20 @@ class Model:
         return [dets[f, :counts[f]].copy() for f in range(self.batch)]
 
     # -- pipelined host I/O (mars_hip_pipe_*)
-    def pipe_open(self, download_outputs=True, detect=False, det_outputs=(0,), thresh=0.45, camera=None, heads=None):
+    def pipe_open(self, download_outputs=True, detect=False, det_outputs=(0,), thresh=0.45, camera=None, heads=None, dfl_heads=None):
         """camera = (w, h): input 0 is fed from uint8 RGB camera frames, the letterbox front-end runs on the device behind the upload.
         heads (with detect): True (found on the file), a list as for detect_heads() or a YoloHeads -- the tail decodes those raw
-        heads instead of det_outputs; in camera mode their boxes come back in camera pixels"""
+        heads instead of det_outputs; in camera mode their boxes come back in camera pixels.  dfl_heads: the same for anchor-free DFL
+        heads (True, a list as for detect_dfl() or a YoloDflHeads); not both"""
         cw, ch = camera if camera else (0, 0)
         o = PipeOpts(int(download_outputs), int(detect), (C.c_int * 4)(*(list(det_outputs) + [0] * (4 - len(det_outputs)))),
                      len(det_outputs) if detect else 0, thresh, int(cw), int(ch))
         if heads is not None and heads is not False:
             h = heads if isinstance(heads, YoloHeads) else yolo_heads(None if heads is True else heads, thresh=thresh)
             o.heads = C.pointer(h)  # copied by mars_hip_pipe_open
+        if dfl_heads is not None and dfl_heads is not False:
+            dh = dfl_heads if isinstance(dfl_heads, YoloDflHeads) else yolo_dfl_heads(None if dfl_heads is True else dfl_heads, thresh=thresh)
+            o.dfl_heads = C.pointer(dh)
         rc = lib().mars_hip_pipe_open(self.p, C.byref(o))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_pipe_open")
