@@ -276,7 +276,14 @@ typedef struct {
                              * open.  In camera mode a zero src_w / src_h means camera_w / camera_h: boxes come back in camera pixels */
     const mars_yolo_dfl_heads_t *dfl_heads; /* detect: non-NULL = decode these DFL heads (mars_hip_detect_dfl) instead; copied at open, camera mode as
                              * for heads.  Setting both heads and dfl_heads is an error (MARS_ERR_INVALID_TENSOR) */
+    int camera_format;      /* camera mode: MARS_HIP_CAMERA_RGB (0, as before) or MARS_HIP_CAMERA_NV12: the frames are NV12 ("NV12 camera frames" below;
+                             * camera_w and camera_h even), mars_hip_pipe_input(model, 0) is [batch][camera_w * camera_h * 3 / 2] bytes, the slot's
+                             * device buffer and its upload are that small, and the submit runs mars_hip_preprocess_nv12_device where the RGB
+                             * front-end runs.  Anything else: MARS_ERR_INVALID_FILE.  Not looked at outside camera mode */
+    unsigned camera_flags;  /* camera mode, NV12: MARS_NV12_* bits; an unknown bit: MARS_ERR_INVALID_FILE */
 } mars_hip_pipe_opts_t;
+#define MARS_HIP_CAMERA_RGB 0
+#define MARS_HIP_CAMERA_NV12 1
 mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t *opts);
 /* pinned host buffer ([batch][frame bytes]) to fill for the NEXT submit; changes after every submit */
 void *mars_hip_pipe_input(mars_model_t *model, int input_index);
@@ -334,6 +341,37 @@ mars_error_t mars_hip_preprocess(mars_model_t *model, int input_index, const uns
  * rgb_dev = frames x [h][w][3] bytes, contiguous; enqueued on the library's current stream, no synchronisation. */
 mars_error_t mars_hip_preprocess_device(mars_model_t *model, int input_index, const void *rgb_dev, int w, int h,
                                         int first_frame, int frames);
+
+/* ------------------------------------------------------ NV12 camera frames */
+/* The reference's cameras deliver NNA_FORMAT_NV12 (include/nna_types.h), the ISP's 4:2:0 output, not RGB.  The calls below take such frames
+ * as they are -- half the bytes of RGB on the way to the device -- and convert on the GPU, inside the front-end.
+ * A frame is w * h * 3 / 2 bytes, densely packed (no row pitch): the Y plane [h][w], directly behind it the chroma plane [h / 2][w / 2][2],
+ * interleaved U, V.  w and h are even.  Pixel (x, y) takes the chroma pair at (x >> 1, y >> 1): nearest, no chroma interpolation.
+ * Integer arithmetic, >> an arithmetic shift (floor), results clamped to [0, 255]; d = U - 128, e = V - 128:
+ *   default, BT.601 limited range, c = Y - 16:   R = (298 c + 409 e + 128) >> 8
+ *                                                G = (298 c - 100 d - 208 e + 128) >> 8
+ *                                                B = (298 c + 516 d + 128) >> 8
+ *   MARS_NV12_FULL_RANGE, BT.601 full range:     R = (256 Y + 359 e + 128) >> 8
+ *                                                G = (256 Y - 88 d - 183 e + 128) >> 8
+ *                                                B = (256 Y + 454 d + 128) >> 8
+ *   MARS_NV12_VU: the chroma pairs are stored V, U (NV21).
+ * The uint8 RGB image is then letterboxed exactly as by the RGB calls above: every call here writes, bit for bit, what its RGB counterpart
+ * writes for the converted frame.  Odd sizes and unknown flag bits are refused before any device work (-1 / MARS_ERR_INVALID_FILE); the other
+ * checks and error codes are those of the RGB calls. */
+#define MARS_NV12_FULL_RANGE 1u
+#define MARS_NV12_VU 2u
+/* Bytes of one NV12 frame; 0 for odd or non-positive sizes.  Host only. */
+size_t mars_hip_nv12_frame_bytes(int w, int h);
+/* One frame -> uint8 RGB [h][w][3].  Host pointers, runs on the GPU; 0 = ok, -1 = failure. */
+int mars_yolo_nv12_to_rgb(const unsigned char *nv12, int w, int h, unsigned flags, unsigned char *rgb);
+/* mars_yolo_letterbox of one NV12 frame. */
+int mars_yolo_letterbox_nv12(const unsigned char *nv12, int w, int h, int tw, int th, int nhwc, unsigned flags, signed char *out);
+/* mars_hip_preprocess / mars_hip_preprocess_device of `frames` NV12 frames (contiguous, w * h * 3 / 2 bytes apart).  The device form keeps
+ * one scratch buffer for geometries whose frames are converted before the resize: enqueue it on one stream. */
+mars_error_t mars_hip_preprocess_nv12(mars_model_t *model, int input_index, const unsigned char *nv12_frames, int w, int h, unsigned flags,
+                                      int first_frame, int frames);
+mars_error_t mars_hip_preprocess_nv12_device(mars_model_t *model, int input_index, const void *nv12_dev, int w, int h, unsigned flags,
+                                             int first_frame, int frames);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,8 @@
 //   out          = (uint8)(int)((double)(clamp(v, 0, 1) * 255.0f) + 0.5)  - 128, pad = -17
 // One thread per output pixel and frame; the horizontal sums are recomputed for every output row that uses them
 // (at most 4/scale rows): bit-identical by construction and far below the cost of reading the frame.
+// NV12 camera frames (4:2:0, the reference ISP's NNA_FORMAT_NV12) enter through the strip kernel's NV12 instantiation or through
+// nv12_to_rgb_kernel + the RGB kernels: integer BT.601, then exactly the resize above (see "NV12 source" below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -178,8 +180,44 @@ __global__ __launch_bounds__(256) void letterbox_tiled_kernel(const mhip_letterb
 // (strips outside the resized image) are filled without touching the source.
 #define LB_R 8
 #define LB_YT 64 // entries per output row of the staged vertical lists (longer lists: the launcher takes another form)
-template <int NC>
-__global__ __launch_bounds__(256) void letterbox_strip_kernel(const mhip_letterbox_t p, const int n_xtaps) {
+//
+// NV12 source (FMT = 1).  p.rgb then points at 4:2:0 frames: the Y plane [h][w], directly behind it the chroma plane [h / 2][w / 2][2].  Only
+// the step "source row -> float row" differs: for source row s a thread fetches its dwords of Y row s and, at the SAME byte offset, of chroma
+// row s >> 1 (dword i of the Y row = pixels 4 i .. 4 i + 3, chroma bytes 4 i .. 4 i + 3 = the two pairs those four pixels use), converts to
+// R, G, B in integer registers (nv12_coef_t: include/mars_hip.h gives the formulas) and writes the same [w * 3] float row through the same
+// /255 table.  The twelve floats of dword i leave as three float4 writes at float 12 i: ds_write_b128 is served in groups of 8 consecutive
+// lanes with bank = dword address mod 32, the eight lanes of a group start at dwords 12 l mod 32 = {0, 12, 24, 4, 16, 28, 8, 20} -- eight
+// disjoint 4-bank slots, so each of the three writes is conflict-free (what the 64-byte stride above is not).  Everything behind the float row
+// is the RGB code; the RGB instantiation (FMT = 0) compiles to what it was before the parameter existed.
+struct nv12_coef_t {
+    int cy, yoff, crv, cgu, cgv, cbu, vu;
+};
+__device__ __forceinline__ nv12_coef_t nv12_coef(const unsigned flags) {
+    nv12_coef_t k;
+    const bool full = flags & 1u; // MARS_NV12_FULL_RANGE
+    k.cy = full ? 256 : 298; k.yoff = full ? 0 : 16;
+    k.crv = full ? 359 : 409; k.cgu = full ? -88 : -100; k.cgv = full ? -183 : -208; k.cbu = full ? 454 : 516;
+    k.vu = (flags >> 1) & 1u;     // MARS_NV12_VU
+    return k;
+}
+// four pixels: yv = their Y bytes, cv = the two chroma pairs (bytes 0, 1: pixels 0, 1; bytes 2, 3: pixels 2, 3) -> rgb[pixel][channel], 0 .. 255
+__device__ __forceinline__ void nv12_quad(const nv12_coef_t k, const unsigned yv, const unsigned cv, int rgb[4][3]) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int c0 = (int)((cv >> (16 * q)) & 255u), c1 = (int)((cv >> (16 * q + 8)) & 255u);
+        const int d = (k.vu ? c1 : c0) - 128, e = (k.vu ? c0 : c1) - 128;
+        const int rr = k.crv * e + 128, gg = k.cgu * d + k.cgv * e + 128, bb = k.cbu * d + 128;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const int c = k.cy * ((int)((yv >> (8 * (2 * q + t))) & 255u) - k.yoff);
+            rgb[2 * q + t][0] = min(max((c + rr) >> 8, 0), 255); // (>> of a negative int: arithmetic, i.e. floor)
+            rgb[2 * q + t][1] = min(max((c + gg) >> 8, 0), 255);
+            rgb[2 * q + t][2] = min(max((c + bb) >> 8, 0), 255);
+        }
+    }
+}
+template <int NC, int FMT>
+__global__ __launch_bounds__(256) void letterbox_strip_kernel(const mhip_letterbox_t p, const int n_xtaps, const unsigned nv12) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int tid = threadIdx.x;
     const int row_f = ((p.w * 3 + 15) & ~15);                 // floats per staged source row (the last dword's tail lands here too)
@@ -243,19 +281,38 @@ __global__ __launch_bounds__(256) void letterbox_strip_kernel(const mhip_letterb
     // belongs to thread d % 256, so that a wave reads 256 contiguous bytes and -- converted -- writes 64 consecutive float4s (lane-linear:
     // no bank conflicts; 16 bytes per thread put the lanes' float4s 64 bytes apart, a 4-way conflict on every write).  A ragged last dword
     // is put together from single bytes: nothing is read beyond the row
-    const int rb = p.w * 3, nld = (rb + 3) >> 2; // dwords per row (at most 8 per thread: the launcher checks)
+    // (NV12: a row is w Y bytes, nld dwords of them and as many of the chroma row, at most 3 + 3 per thread: ld[0 .. 2] and ld[3 .. 5])
+    const int rb = FMT ? p.w : p.w * 3, nld = (rb + 3) >> 2; // dwords per row (at most 8 per thread: the launcher checks)
     unsigned ld[8];
     auto fetch = [&](int s) __attribute__((always_inline)) {
+        if constexpr (FMT != 0) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int i = tid + 256 * k;
-            if (i < nld) {
-                const uint8_t *g = src + (size_t)s * rb + (size_t)i * 4;
-                if (i * 4 + 4 <= rb) __builtin_memcpy(&ld[k], g, 4);
-                else {
-                    unsigned v = 0u;
-                    for (int b = 0; b < rb - i * 4; b++) v |= (unsigned)g[b] << (8 * b);
-                    ld[k] = v;
+            for (int k = 0; k < 3; k++) {
+                const int i = tid + 256 * k;
+                if (i < nld) {
+                    const uint8_t *gy = src + (size_t)s * rb + (size_t)i * 4;
+                    const uint8_t *gc = src + ((size_t)p.h + (size_t)(s >> 1)) * rb + (size_t)i * 4; // chroma row s >> 1: w bytes too
+                    if (i * 4 + 4 <= rb) {
+                        __builtin_memcpy(&ld[k], gy, 4);
+                        __builtin_memcpy(&ld[3 + k], gc, 4);
+                    } else { // w % 4 == 2: the last two pixels and their one chroma pair; nothing is read beyond either row
+                        ld[k] = (unsigned)gy[0] | (unsigned)gy[1] << 8;
+                        ld[3 + k] = (unsigned)gc[0] | (unsigned)gc[1] << 8;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int i = tid + 256 * k;
+                if (i < nld) {
+                    const uint8_t *g = src + (size_t)s * rb + (size_t)i * 4;
+                    if (i * 4 + 4 <= rb) __builtin_memcpy(&ld[k], g, 4);
+                    else {
+                        unsigned v = 0u;
+                        for (int b = 0; b < rb - i * 4; b++) v |= (unsigned)g[b] << (8 * b);
+                        ld[k] = v;
+                    }
                 }
             }
         }
@@ -263,12 +320,28 @@ __global__ __launch_bounds__(256) void letterbox_strip_kernel(const mhip_letterb
     if (s1 >= s0) fetch(s0);
     for (int s = s0; s <= s1; s++) {
         float *rf = rowf;
+        if constexpr (FMT != 0) { // Y + chroma -> R, G, B -> floats, once per pixel (a ragged last dword writes two pixels of padding: the row has room)
+            const nv12_coef_t kc = nv12_coef(nv12);
 #pragma unroll
-        for (int k = 0; k < 8; k++) { // bytes -> floats, once per byte
-            const int i = tid + 256 * k;
-            if (i < nld) {
-                const unsigned v = ld[k];
-                *(float4 *)(rf + i * 4) = make_float4(dec[v & 255u], dec[(v >> 8) & 255u], dec[(v >> 16) & 255u], dec[v >> 24]);
+            for (int k = 0; k < 3; k++) {
+                const int i = tid + 256 * k;
+                if (i < nld) {
+                    int c[4][3];
+                    nv12_quad(kc, ld[k], ld[3 + k], c);
+                    float *o = rf + i * 12;
+                    *(float4 *)(o) = make_float4(dec[c[0][0]], dec[c[0][1]], dec[c[0][2]], dec[c[1][0]]);
+                    *(float4 *)(o + 4) = make_float4(dec[c[1][1]], dec[c[1][2]], dec[c[2][0]], dec[c[2][1]]);
+                    *(float4 *)(o + 8) = make_float4(dec[c[2][2]], dec[c[3][0]], dec[c[3][1]], dec[c[3][2]]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) { // bytes -> floats, once per byte
+                const int i = tid + 256 * k;
+                if (i < nld) {
+                    const unsigned v = ld[k];
+                    *(float4 *)(rf + i * 4) = make_float4(dec[v & 255u], dec[(v >> 8) & 255u], dec[(v >> 16) & 255u], dec[v >> 24]);
+                }
             }
         }
         if (s < s1) fetch(s + 1);
@@ -377,40 +450,119 @@ __global__ __launch_bounds__(256) void letterbox_strip_kernel(const mhip_letterb
     }
 }
 
-static size_t strip_lds(const mhip_letterbox_t *p) {
-    const size_t row_f = ((size_t)p->w * 3 + 15) & ~(size_t)15;
-    return 1024 + (((size_t)p->nw + 1 + 3) & ~(size_t)3) * 4 + (((size_t)p->n_xtaps + 1) & ~(size_t)1) * 8 + (size_t)LB_R * LB_YT * 8 + row_f * 4;
+// Standalone conversion: NV12 frames -> uint8 RGB [h][w][3], the arithmetic of the fused form above (nv12_quad).  A thread owns 16 pixels of
+// one row: 16 Y bytes and the 16 chroma bytes at the same offset of chroma row y >> 1 in, 48 RGB bytes out -- three 16-byte stores where
+// the address allows, else twelve dwords, else bytes (frames and rows start at any byte offset).  Row ends (w % 16 != 0) go pixel by pixel.
+__global__ __launch_bounds__(256) void nv12_to_rgb_kernel(const uint8_t *nv12, const size_t nv12_stride, uint8_t *rgb, const size_t rgb_stride,
+                                                           const int w, const int h, const unsigned flags) {
+    const int gpr = (w + 15) >> 4; // 16-pixel groups per row
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)gpr * h) return;
+    const int y = (int)(t / gpr), x0 = (int)(t - (long long)y * gpr) * 16;
+    const uint8_t *src = nv12 + (size_t)blockIdx.y * nv12_stride;
+    const uint8_t *gy = src + (size_t)y * w + x0, *gc = src + ((size_t)h + (size_t)(y >> 1)) * w + x0;
+    uint8_t *o = rgb + (size_t)blockIdx.y * rgb_stride + ((size_t)y * w + x0) * 3;
+    const nv12_coef_t kc = nv12_coef(flags);
+    if (x0 + 16 <= w) {
+        unsigned yv[4], cv[4], out[12];
+        __builtin_memcpy(yv, gy, 16);
+        __builtin_memcpy(cv, gc, 16);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { // four pixels = 12 bytes = three dwords
+            int c[4][3];
+            nv12_quad(kc, yv[j], cv[j], c);
+            out[3 * j] = (unsigned)c[0][0] | (unsigned)c[0][1] << 8 | (unsigned)c[0][2] << 16 | (unsigned)c[1][0] << 24;
+            out[3 * j + 1] = (unsigned)c[1][1] | (unsigned)c[1][2] << 8 | (unsigned)c[2][0] << 16 | (unsigned)c[2][1] << 24;
+            out[3 * j + 2] = (unsigned)c[2][2] | (unsigned)c[3][0] << 8 | (unsigned)c[3][1] << 16 | (unsigned)c[3][2] << 24;
+        }
+        if (((uintptr_t)o & 15) == 0) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) ((uint4 *)o)[j] = make_uint4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
+        } else if (((uintptr_t)o & 3) == 0) {
+#pragma unroll
+            for (int j = 0; j < 12; j++) ((unsigned *)o)[j] = out[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 48; j++) o[j] = (uint8_t)(out[j >> 2] >> (8 * (j & 3)));
+        }
+    } else { // the row's last, partial group: w - x0 pixels (even), two at a time
+        for (int x = 0; x0 + x < w; x += 2) {
+            int c[4][3];
+            nv12_quad(kc, (unsigned)gy[x] | (unsigned)gy[x + 1] << 8, (unsigned)gc[x] | (unsigned)gc[x + 1] << 8, c);
+#pragma unroll
+            for (int j = 0; j < 6; j++) o[x * 3 + j] = (uint8_t)c[j / 3][j % 3];
+        }
+    }
+}
+
+extern "C" int mhip_nv12_to_rgb(const uint8_t *nv12, size_t nv12_stride, uint8_t *rgb, size_t rgb_stride, int frames, int w, int h, unsigned flags) {
+    if (!nv12 || !rgb || w <= 0 || h <= 0 || (w & 1) || (h & 1) || frames <= 0 || frames > 65535 || (flags & ~3u)) return -1;
+    const long long groups = (long long)((w + 15) >> 4) * h;
+    if ((groups + 255) / 256 > 0x7fffffffLL) return -1;
+    hipLaunchKernelGGL(nv12_to_rgb_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)frames), dim3(256), 0, mhip_stream_native(), nv12, nv12_stride,
+                       rgb, rgb_stride, w, h, flags);
+    return mhip_check(hipGetLastError(), "nv12 -> rgb");
+}
+
+// floats of the strip kernel's staged source row: w * 3, rounded up to 16; an NV12 row is written four pixels at a time, so its last dword may
+// add two pixels of padding
+static size_t strip_row_f(const mhip_letterbox_t *p, int nv12) {
+    const size_t px = nv12 ? (((size_t)p->w + 3) & ~(size_t)3) : (size_t)p->w;
+    return (px * 3 + 15) & ~(size_t)15;
+}
+
+static size_t strip_lds(const mhip_letterbox_t *p, int nv12) {
+    return 1024 + (((size_t)p->nw + 1 + 3) & ~(size_t)3) * 4 + (((size_t)p->n_xtaps + 1) & ~(size_t)1) * 8 + (size_t)LB_R * LB_YT * 8 + strip_row_f(p, nv12) * 4;
+}
+
+static bool letterbox_args_ok(const mhip_letterbox_t *p) {
+    if (!p || !p->rgb || !p->out || !p->xstart || !p->xsrc || !p->xw || !p->ystart || !p->ysrc || !p->yw) return false;
+    if (p->frames <= 0 || p->w <= 0 || p->h <= 0 || p->tw <= 0 || p->th <= 0 || p->nw <= 0 || p->nh <= 0 || p->px < 0 ||
+        p->py < 0 || p->px + p->nw > p->tw || p->py + p->nh > p->th || p->frames > 65535)
+        return false;
+    return true;
+}
+
+// strip form: the gather list and the float row fit LDS, a source row is at most 8 dwords per thread (NV12: 3 of the Y row and 3 of the chroma
+// row), at most 4 columns per thread, and the strip's output bytes fit where the float row was
+static bool strip_fits(const mhip_letterbox_t *p, int nv12) {
+    return p->n_xtaps > 0 && p->max_ytaps > 0 && p->max_ytaps < LB_YT && p->form != 1 && p->form != 2 && p->nw <= 1024 &&
+           (nv12 ? (p->w + 3) / 4 <= 768 : (p->w * 3 + 3) / 4 <= 2048) && (p->tw * 3) % 4 == 0 && strip_lds(p, nv12) <= 80 * 1024 &&
+           (size_t)LB_R * p->tw * 3 <= strip_row_f(p, nv12) * 4;
+}
+
+static int launch_strips(const mhip_letterbox_t *p, int nv12, unsigned flags) {
+    const dim3 g((unsigned)((p->th + LB_R - 1) / LB_R), (unsigned)p->frames);
+    const size_t lds = strip_lds(p, nv12);
+    const int nc = (p->nw + 255) / 256;
+#define LB_LAUNCH(NC, FMT)                                                                                                                \
+    do {                                                                                                                                  \
+        static bool attr_##NC##_##FMT = false;                                                                                            \
+        if (!attr_##NC##_##FMT) {                                                                                                         \
+            if (hipFuncSetAttribute((const void *)letterbox_strip_kernel<NC, FMT>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) \
+                return mhip_check(hipErrorUnknown, "letterbox (strips) attribute");                                                       \
+            attr_##NC##_##FMT = true;                                                                                                     \
+        }                                                                                                                                 \
+        hipLaunchKernelGGL((letterbox_strip_kernel<NC, FMT>), g, dim3(256), lds, mhip_stream_native(), *p, p->n_xtaps, flags);            \
+    } while (0)
+    if (nv12) {
+        if (nc <= 1) LB_LAUNCH(1, 1);
+        else if (nc == 2) LB_LAUNCH(2, 1);
+        else if (nc == 3) LB_LAUNCH(3, 1);
+        else LB_LAUNCH(4, 1);
+    } else {
+        if (nc <= 1) LB_LAUNCH(1, 0);
+        else if (nc == 2) LB_LAUNCH(2, 0);
+        else if (nc == 3) LB_LAUNCH(3, 0);
+        else LB_LAUNCH(4, 0);
+    }
+#undef LB_LAUNCH
+    return mhip_check(hipGetLastError(), nv12 ? "letterbox (strips, nv12)" : "letterbox (strips)");
 }
 
 extern "C" int mhip_letterbox(const mhip_letterbox_t *p) {
-    if (!p || !p->rgb || !p->out || !p->xstart || !p->xsrc || !p->xw || !p->ystart || !p->ysrc || !p->yw) return -1;
-    if (p->frames <= 0 || p->w <= 0 || p->h <= 0 || p->tw <= 0 || p->th <= 0 || p->nw <= 0 || p->nh <= 0 || p->px < 0 ||
-        p->py < 0 || p->px + p->nw > p->tw || p->py + p->nh > p->th || p->frames > 65535)
-        return -1;
-    // strip form: the gather list and two float rows fit LDS, a source row is at most 512 16-byte pieces, at most 4 columns per thread,
-    // and the strip's output bytes fit where the float rows were
-    if (p->n_xtaps > 0 && p->max_ytaps > 0 && p->max_ytaps < LB_YT && p->form != 1 && p->form != 2 && p->nw <= 1024 && (p->w * 3 + 3) / 4 <= 2048 && (p->tw * 3) % 4 == 0 && strip_lds(p) <= 80 * 1024 &&
-        (size_t)LB_R * p->tw * 3 <= ((((size_t)p->w * 3 + 15) & ~(size_t)15) * 4)) {
-        const dim3 g((unsigned)((p->th + LB_R - 1) / LB_R), (unsigned)p->frames);
-        const size_t lds = strip_lds(p);
-        const int nc = (p->nw + 255) / 256;
-#define LB_LAUNCH(NC)                                                                                                                     \
-    do {                                                                                                                                  \
-        static bool attr_##NC = false;                                                                                                    \
-        if (!attr_##NC) {                                                                                                                 \
-            if (hipFuncSetAttribute((const void *)letterbox_strip_kernel<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) \
-                return mhip_check(hipErrorUnknown, "letterbox (strips) attribute");                                                       \
-            attr_##NC = true;                                                                                                             \
-        }                                                                                                                                 \
-        hipLaunchKernelGGL(letterbox_strip_kernel<NC>, g, dim3(256), lds, mhip_stream_native(), *p, p->n_xtaps);                          \
-    } while (0)
-        if (nc <= 1) LB_LAUNCH(1);
-        else if (nc == 2) LB_LAUNCH(2);
-        else if (nc == 3) LB_LAUNCH(3);
-        else LB_LAUNCH(4);
-#undef LB_LAUNCH
-        return mhip_check(hipGetLastError(), "letterbox (strips)");
-    }
+    if (!letterbox_args_ok(p)) return -1;
+    if (strip_fits(p, 0)) return launch_strips(p, 0, 0u);
     dim3 grid((unsigned)((p->tw + 15) / 16), (unsigned)((p->th + 15) / 16), (unsigned)p->frames);
     if (p->max_cols > 0 && p->max_rows > 0 && p->form != 2) {
         const size_t lds = 1024 + (size_t)p->max_rows * 48 * 4 + (size_t)p->max_rows * (((size_t)p->max_cols * 3 + 3) & ~(size_t)3);
@@ -421,4 +573,21 @@ extern "C" int mhip_letterbox(const mhip_letterbox_t *p) {
     }
     hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, mhip_stream_native(), *p);
     return mhip_check(hipGetLastError(), "letterbox");
+}
+
+// NV12 frames (p->rgb / p->rgb_stride: the frames and their distance, w * h * 3 / 2 when packed): 1 = mhip_letterbox_nv12 takes the fused
+// strip form for this geometry and needs no scratch buffer, 0 = it converts first
+extern "C" int mhip_letterbox_nv12_fused(const mhip_letterbox_t *p) { return letterbox_args_ok(p) && !(p->w & 1) && !(p->h & 1) && strip_fits(p, 1); }
+
+// the letterbox of NV12 frames: fused where the strip form is offered; everywhere else (and under a forced form) the frames are converted into
+// `scratch` (frames x [h][w][3] bytes on the device) and the RGB kernels above run on that, unchanged.  The same bytes either way
+extern "C" int mhip_letterbox_nv12(const mhip_letterbox_t *p, unsigned flags, uint8_t *scratch) {
+    if (!letterbox_args_ok(p) || (p->w & 1) || (p->h & 1) || (flags & ~3u)) return -1;
+    if (strip_fits(p, 1)) return launch_strips(p, 1, flags);
+    if (!scratch) return -1;
+    mhip_letterbox_t q = *p;
+    q.rgb = scratch;
+    q.rgb_stride = (size_t)p->w * p->h * 3;
+    const int rc = mhip_nv12_to_rgb(p->rgb, p->rgb_stride, scratch, q.rgb_stride, p->frames, p->w, p->h, flags);
+    return rc ? rc : mhip_letterbox(&q);
 }

@@ -227,6 +227,7 @@ MARS_INTERNAL void plan_check(mars_model_ext_t *m);
 MARS_INTERNAL void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8_t *p);
 /* mars_preproc.c */
 MARS_INTERNAL int mars_preproc_prepare(int w, int h, int tw, int th); /* gather tables of a letterbox geometry, cached */
+MARS_INTERNAL int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int frames); /* the same + the conversion scratch, where NV12 frames need one */
 
 /* detection tail pieces shared with the pipelined I/O (mars_yolo.c) */
 mars_error_t mars_detect_prepare(mars_model_ext_t *m, const int *output_indices, int n_outputs);

@@ -14,7 +14,8 @@
  *     download stream  D2H(k-1)
  *
  * Camera mode (opts.camera_w / camera_h): what is uploaded for input 0 is the camera's uint8 RGB frames, and the image front-end
- * (letterbox resize + px - 128, mars_preproc.c) runs behind the copy on the upload stream: the reference demo's whole loop.
+ * (letterbox resize + px - 128, mars_preproc.c) runs behind the copy, ahead of the graph: the reference demo's whole loop.  With
+ * opts.camera_format = MARS_HIP_CAMERA_NV12 the frames are the ISP's 4:2:0 output, half the bytes on the link, converted inside the front-end.
  *
  * What travels back is the caller's choice: the raw graph outputs (as mars_run leaves them), the detections of the
  * decode + NMS tail (24 KB per frame at most instead of 2.1 MB of head tensors), or both.
@@ -35,7 +36,7 @@
 typedef struct {
     uint8_t *in_host[MARS_MAX_IO], *in_dev[MARS_MAX_IO];
     uint8_t *out_host[MARS_MAX_IO], *out_dev[MARS_MAX_IO], *out_dense[MARS_MAX_IO];
-    uint8_t *rgb_dev; /* camera mode: the uploaded RGB frames of input 0 (in_host[0] is their pinned source) */
+    uint8_t *rgb_dev; /* camera mode: the uploaded RGB (or NV12) frames of input 0 (in_host[0] is their pinned source) */
     mars_det_t *det_host;
     int *cnt_host;
     void *det_dev;
@@ -62,6 +63,12 @@ static mtensor_t *io_tensor(mars_model_ext_t *m, int is_out, int i) {
     const uint32_t tid = is_out ? m->pub.header.output_tensor_ids[i] : m->pub.header.input_tensor_ids[i];
     if (tid >= m->pub.header.num_tensors || m->mt[tid].is_weight || !m->mt[tid].dev) return NULL;
     return &m->mt[tid];
+}
+
+/* camera mode: bytes of one uploaded frame of input 0 */
+static size_t camera_frame_bytes(const mars_hip_pipe_opts_t *o) {
+    if (o->camera_format == MARS_HIP_CAMERA_NV12) return mars_hip_nv12_frame_bytes(o->camera_w, o->camera_h);
+    return (size_t)o->camera_w * o->camera_h * 3;
 }
 
 static void slot_free(pipe_slot_t *s) {
@@ -118,6 +125,11 @@ mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t 
     if (opts->detect && !opts->heads && !opts->dfl_heads && (opts->n_det_outputs <= 0 || opts->n_det_outputs > 4)) return MARS_ERR_INVALID_TENSOR;
     const int camera = opts->camera_w > 0 && opts->camera_h > 0;
     if ((opts->camera_w > 0) != (opts->camera_h > 0) || opts->camera_w < 0 || opts->camera_h < 0) return MARS_ERR_INVALID_FILE;
+    if (camera && ((opts->camera_format != MARS_HIP_CAMERA_RGB && opts->camera_format != MARS_HIP_CAMERA_NV12) ||
+                   (opts->camera_flags & ~(unsigned)(MARS_NV12_FULL_RANGE | MARS_NV12_VU)))) /* (outside camera mode the two fields are not looked at) */
+        return MARS_ERR_INVALID_FILE;
+    const int nv12 = camera && opts->camera_format == MARS_HIP_CAMERA_NV12;
+    if (nv12 && !mars_hip_nv12_frame_bytes(opts->camera_w, opts->camera_h)) return MARS_ERR_INVALID_FILE; /* odd sizes */
     if (model->header.num_inputs > MARS_MAX_IO || model->header.num_outputs > MARS_MAX_IO) return MARS_ERR_INVALID_FILE;
     mars_hip_pipe_close(model);
     if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
@@ -142,7 +154,7 @@ mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t 
         for (uint32_t i = 0; i < model->header.num_inputs && err == MARS_OK; i++) {
             mtensor_t *t = io_tensor(m, 0, (int)i);
             if (!t) continue;
-            const size_t cam_b = (i == 0 && camera) ? (size_t)opts->camera_w * opts->camera_h * 3 * B : 0;
+            const size_t cam_b = (i == 0 && camera) ? camera_frame_bytes(opts) * B : 0;
             const size_t host_b = cam_b ? cam_b : (t->bytes > 0 ? t->bytes * B : 64);
             sl->in_host[i] = (uint8_t *)mhip_host_alloc(host_b);
             sl->in_dev[i] = (uint8_t *)mhip_malloc(t->stride * B + 256);
@@ -191,7 +203,9 @@ mars_error_t mars_hip_pipe_open(mars_model_t *model, const mars_hip_pipe_opts_t 
             const mars_tensor_t *d0 = &model->tensors[model->header.input_tensor_ids[0]].desc;
             const int nhwc = d0->format == MARS_FORMAT_NHWC;
             const int th = nhwc ? d0->shape[1] : d0->shape[2], tw = nhwc ? d0->shape[2] : d0->shape[3], ch = nhwc ? d0->shape[3] : d0->shape[1];
-            if (ch != 3 || d0->dtype != MARS_DTYPE_INT8 || mars_preproc_prepare(opts->camera_w, opts->camera_h, tw, th)) err = MARS_ERR_INVALID_TENSOR;
+            if (ch != 3 || d0->dtype != MARS_DTYPE_INT8 ||
+                (nv12 ? mars_preproc_prepare_nv12(opts->camera_w, opts->camera_h, tw, th, m->batch) : mars_preproc_prepare(opts->camera_w, opts->camera_h, tw, th)))
+                err = MARS_ERR_INVALID_TENSOR;
         }
     }
     if (err == MARS_OK && opts->detect && opts->heads) { /* raw heads: resolved against the plan and their tables uploaded once */
@@ -241,7 +255,7 @@ mars_error_t mars_hip_pipe_submit(mars_model_t *model) {
         if (!t || !t->bytes) continue;
         if (i == 0 && camera) { /* RGB frames up; the front-end runs on the MAIN stream ahead of the graph (below): on this stream it stood between
                                  * batch k's copy and batch k + 1's, and the link idled while it ran (17.7 ms per batch = copy + kernel) */
-            rc = mhip_h2d_async(sl->rgb_dev, sl->in_host[0], (size_t)pp->opts.camera_w * pp->opts.camera_h * 3 * B);
+            rc = mhip_h2d_async(sl->rgb_dev, sl->in_host[0], camera_frame_bytes(&pp->opts) * B);
             continue;
         }
         rc = mhip_h2d_2d_async(sl->in_dev[i], t->stride, sl->in_host[i], t->bytes, t->bytes, B);
@@ -265,7 +279,9 @@ mars_error_t mars_hip_pipe_submit(mars_model_t *model) {
     }
     if (camera) { /* letterbox / px - 128 into this slot's graph input (now the input tensor's device buffer), then the graph behind it */
         rc = mhip_event_record(sl->ev_pre0);
-        if (!rc && mars_hip_preprocess_device(model, 0, sl->rgb_dev, pp->opts.camera_w, pp->opts.camera_h, 0, (int)B) != MARS_OK) rc = -1;
+        if (!rc && pp->opts.camera_format == MARS_HIP_CAMERA_NV12) {
+            if (mars_hip_preprocess_nv12_device(model, 0, sl->rgb_dev, pp->opts.camera_w, pp->opts.camera_h, pp->opts.camera_flags, 0, (int)B) != MARS_OK) rc = -1;
+        } else if (!rc && mars_hip_preprocess_device(model, 0, sl->rgb_dev, pp->opts.camera_w, pp->opts.camera_h, 0, (int)B) != MARS_OK) rc = -1;
         if (!rc) rc = mhip_event_record(sl->ev_pre1);
         if (rc) return MARS_ERR_LAYER_FAILED;
     }

@@ -260,8 +260,8 @@ static int geometry(int w, int h, int tw, int th, geom_t **out) {
     return 0;
 }
 
-static int run_letterbox(const geom_t *g, const uint8_t *rgb_dev, size_t rgb_stride, int8_t *out_dev, size_t out_stride,
-                         int frames, int nhwc) {
+static void letterbox_params(const geom_t *g, const uint8_t *rgb_dev, size_t rgb_stride, int8_t *out_dev, size_t out_stride, int frames,
+                             int nhwc, mhip_letterbox_t *pp) {
     mhip_letterbox_t p;
     memset(&p, 0, sizeof(p));
     p.rgb = rgb_dev; p.rgb_stride = rgb_stride;
@@ -277,7 +277,86 @@ static int run_letterbox(const geom_t *g, const uint8_t *rgb_dev, size_t rgb_str
     const char *b = (const char *)g->dev;
     p.xstart = (const int *)(b + g->off[0]); p.xsrc = (const int *)(b + g->off[1]); p.xw = (const float *)(b + g->off[2]);
     p.ystart = (const int *)(b + g->off[3]); p.ysrc = (const int *)(b + g->off[4]); p.yw = (const float *)(b + g->off[5]);
+    *pp = p;
+}
+
+static int run_letterbox(const geom_t *g, const uint8_t *rgb_dev, size_t rgb_stride, int8_t *out_dev, size_t out_stride,
+                         int frames, int nhwc) {
+    mhip_letterbox_t p;
+    letterbox_params(g, rgb_dev, rgb_stride, out_dev, out_stride, frames, nhwc, &p);
     return mhip_letterbox(&p);
+}
+
+/* ---- NV12 camera frames (include/mars_hip.h: "NV12 camera frames"): Y plane, then interleaved chroma at half resolution, w * h * 3 / 2 bytes */
+#define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
+
+size_t mars_hip_nv12_frame_bytes(int w, int h) {
+    if (w <= 0 || h <= 0 || (w & 1) || (h & 1)) return 0;
+    return (size_t)w * (size_t)h / 2 * 3;
+}
+
+/* the RGB frames of the two-pass route (mhip_letterbox_nv12 converts into them where the strip kernel is not offered): bytes needed, 0 = none */
+static size_t nv12_scratch_bytes(const geom_t *g, int frames) {
+    mhip_letterbox_t p;
+    uint8_t dummy = 0; /* (only the geometry and the form are looked at) */
+    letterbox_params(g, &dummy, 0, (int8_t *)&dummy, 0, frames, 1, &p);
+    return mhip_letterbox_nv12_fused(&p) ? 0 : (size_t)g->w * g->h * 3 * (size_t)frames;
+}
+
+static int run_letterbox_nv12(const geom_t *g, const uint8_t *nv12_dev, unsigned flags, uint8_t *scratch, int8_t *out_dev, size_t out_stride,
+                              int frames, int nhwc) {
+    mhip_letterbox_t p;
+    letterbox_params(g, nv12_dev, mars_hip_nv12_frame_bytes(g->w, g->h), out_dev, out_stride, frames, nhwc, &p);
+    return mhip_letterbox_nv12(&p, flags, scratch);
+}
+
+/* scratch of the device-pointer form, which returns before its kernels ran: kept, and only ever grown.  Work that uses it is ordered by the one
+ * stream the caller enqueues on (the pipe: its main stream) */
+static uint8_t *g_nv12_scratch;
+static size_t g_nv12_scratch_b;
+static uint8_t *nv12_scratch(size_t bytes) {
+    if (bytes <= g_nv12_scratch_b) return g_nv12_scratch;
+    if (g_nv12_scratch) {
+        if (mhip_sync()) return NULL; /* kernels queued earlier may still read the old one */
+        mhip_free(g_nv12_scratch);
+    }
+    g_nv12_scratch = (uint8_t *)mhip_malloc(bytes);
+    g_nv12_scratch_b = g_nv12_scratch ? bytes : 0;
+    return g_nv12_scratch;
+}
+
+/* one NV12 frame -> uint8 RGB [h][w][3]; host pointers, runs on the GPU */
+int mars_yolo_nv12_to_rgb(const unsigned char *nv12, int w, int h, unsigned flags, unsigned char *rgb) {
+    const size_t in_b = mars_hip_nv12_frame_bytes(w, h), out_b = in_b * 2;
+    if (!nv12 || !rgb || !in_b || (flags & ~NV12_FLAGS) || !mhip_ready()) return -1;
+    const size_t in_pad = (in_b + 255) & ~(size_t)255;
+    uint8_t *d = (uint8_t *)mhip_malloc(in_pad + out_b);
+    if (!d) return -1;
+    int rc = mhip_h2d_async(d, nv12, in_b);
+    if (!rc) rc = mhip_nv12_to_rgb(d, in_b, d + in_pad, out_b, 1, w, h, flags);
+    if (!rc) rc = mhip_d2h_async(rgb, d + in_pad, out_b);
+    if (mhip_sync()) rc = -1;
+    mhip_free(d);
+    return rc ? -1 : 0;
+}
+
+/* mars_yolo_letterbox on one NV12 frame */
+int mars_yolo_letterbox_nv12(const unsigned char *nv12, int w, int h, int tw, int th, int nhwc, unsigned flags, signed char *out) {
+    const size_t in_b = mars_hip_nv12_frame_bytes(w, h);
+    if (!nv12 || !out || !in_b || tw <= 0 || th <= 0 || (flags & ~NV12_FLAGS) || !mhip_ready()) return -1;
+    geom_t *g;
+    if (geometry(w, h, tw, th, &g)) return -1;
+    const size_t in_pad = (in_b + 255) & ~(size_t)255, out_b = (size_t)tw * th * 3, out_pad = (out_b + 255) & ~(size_t)255;
+    const size_t scr_b = nv12_scratch_bytes(g, 1);
+    uint8_t *d = (uint8_t *)mhip_malloc(in_pad + out_pad + scr_b);
+    if (!d) return -1;
+    int8_t *dout = (int8_t *)(d + in_pad);
+    int rc = mhip_h2d_async(d, nv12, in_b);
+    if (!rc) rc = run_letterbox_nv12(g, d, flags, scr_b ? d + in_pad + out_pad : NULL, dout, out_b, 1, nhwc);
+    if (!rc) rc = mhip_d2h_async(out, dout, out_b);
+    if (mhip_sync()) rc = -1;
+    mhip_free(d);
+    return rc ? -1 : 0;
 }
 
 /* host pointers in and out, one frame: the reference's load_image() on an already decoded image */
@@ -301,6 +380,15 @@ int mars_yolo_letterbox(const unsigned char *rgb, int w, int h, int tw, int th, 
 int mars_preproc_prepare(int w, int h, int tw, int th) {
     geom_t *g;
     return geometry(w, h, tw, th, &g);
+}
+
+/* the same for NV12 frames, `frames` at a time through mars_hip_preprocess_nv12_device: also the scratch frames of the two-pass route, if this
+ * geometry takes it */
+int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int frames) {
+    geom_t *g;
+    if (!mars_hip_nv12_frame_bytes(w, h) || frames <= 0 || geometry(w, h, tw, th, &g)) return -1;
+    const size_t scr_b = nv12_scratch_bytes(g, frames);
+    return scr_b && !nv12_scratch(scr_b) ? -1 : 0;
 }
 
 /* geometry + target checks shared by the host and the device form */
@@ -362,4 +450,40 @@ mars_error_t mars_hip_preprocess_device(mars_model_t *model, int input_index, co
     const mars_error_t e = preproc_target(model, input_index, w, h, first_frame, frames, &g, &dst, &dst_stride, &nhwc);
     if (e != MARS_OK) return e;
     return run_letterbox(g, (const uint8_t *)rgb_dev, (size_t)w * h * 3, dst, dst_stride, frames, nhwc) ? MARS_ERR_LAYER_FAILED : MARS_OK;
+}
+
+/* ---- the same two calls for NV12 frames: same checks and error codes; odd sizes and unknown flag bits are refused before any device work */
+mars_error_t mars_hip_preprocess_nv12(mars_model_t *model, int input_index, const unsigned char *nv12_frames, int w, int h, unsigned flags,
+                                      int first_frame, int frames) {
+    if (!nv12_frames || (flags & ~NV12_FLAGS) || (w > 0 && h > 0 && !mars_hip_nv12_frame_bytes(w, h))) return MARS_ERR_INVALID_FILE;
+    geom_t *g;
+    int8_t *dst;
+    size_t dst_stride;
+    int nhwc;
+    const mars_error_t e = preproc_target(model, input_index, w, h, first_frame, frames, &g, &dst, &dst_stride, &nhwc);
+    if (e != MARS_OK) return e;
+    const size_t in_b = mars_hip_nv12_frame_bytes(w, h) * (size_t)frames, in_pad = (in_b + 255) & ~(size_t)255;
+    const size_t scr_b = nv12_scratch_bytes(g, frames);
+    uint8_t *d = (uint8_t *)mhip_malloc(in_pad + scr_b);
+    if (!d) return MARS_ERR_ALLOC_FAILED;
+    int rc = mhip_h2d_async(d, nv12_frames, in_b);
+    if (!rc) rc = run_letterbox_nv12(g, d, flags, scr_b ? d + in_pad : NULL, dst, dst_stride, frames, nhwc);
+    if (mhip_sync()) rc = -1;
+    mhip_free(d);
+    return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
+}
+
+mars_error_t mars_hip_preprocess_nv12_device(mars_model_t *model, int input_index, const void *nv12_dev, int w, int h, unsigned flags,
+                                             int first_frame, int frames) {
+    if (!nv12_dev || (flags & ~NV12_FLAGS) || (w > 0 && h > 0 && !mars_hip_nv12_frame_bytes(w, h))) return MARS_ERR_INVALID_FILE;
+    geom_t *g;
+    int8_t *dst;
+    size_t dst_stride;
+    int nhwc;
+    const mars_error_t e = preproc_target(model, input_index, w, h, first_frame, frames, &g, &dst, &dst_stride, &nhwc);
+    if (e != MARS_OK) return e;
+    const size_t scr_b = nv12_scratch_bytes(g, frames);
+    uint8_t *scr = scr_b ? nv12_scratch(scr_b) : NULL;
+    if (scr_b && !scr) return MARS_ERR_ALLOC_FAILED;
+    return run_letterbox_nv12(g, (const uint8_t *)nv12_dev, flags, scr, dst, dst_stride, frames, nhwc) ? MARS_ERR_LAYER_FAILED : MARS_OK;
 }

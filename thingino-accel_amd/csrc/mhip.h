@@ -323,7 +323,7 @@ int mhip_detect_dfl(const mhip_dfl_heads_t *p);
 
 /* ---- image front-end (preproc.hip): letterbox resize + (px - 128); tables from csrc/host/mars_preproc.c */
 typedef struct {
-    const uint8_t *rgb; size_t rgb_stride;   /* [frames][h][w][3] uint8 on the device */
+    const uint8_t *rgb; size_t rgb_stride;   /* [frames][h][w][3] uint8 on the device (mhip_letterbox_nv12: [frames] NV12 frames) */
     int8_t *out;        size_t out_stride;   /* [frames] x (tw*th*3) int8: [th][tw][3] (nhwc) or [3][th][tw] */
     int frames, w, h, tw, th, nhwc;
     int nw, nh, px, py;                      /* resized size and its offset inside the target */
@@ -335,6 +335,13 @@ typedef struct {
     int form;                                /* 0: the launcher's choice (strips where they fit, else 16 x 16 tiles, else one thread per pixel); 1 / 2: tiles / per-pixel forced (tests) */
 } mhip_letterbox_t;
 int mhip_letterbox(const mhip_letterbox_t *p);
+/* NV12 camera frames (Y plane [h][w], behind it the chroma plane [h/2][w/2][2]; w, h even; flags = MARS_NV12_* of include/mars_hip.h).
+ * mhip_nv12_to_rgb: frames x NV12 -> frames x uint8 RGB [h][w][3] (strides in bytes between frames).
+ * mhip_letterbox_nv12: mhip_letterbox with p->rgb / p->rgb_stride naming NV12 frames; the strip form converts while it stages a source row,
+ * every other form converts into `scratch` (frames x w * h * 3 bytes on the device) first; mhip_letterbox_nv12_fused says which (1: no scratch needed) */
+int mhip_nv12_to_rgb(const uint8_t *nv12, size_t nv12_stride, uint8_t *rgb, size_t rgb_stride, int frames, int w, int h, unsigned flags);
+int mhip_letterbox_nv12_fused(const mhip_letterbox_t *p);
+int mhip_letterbox_nv12(const mhip_letterbox_t *p, unsigned flags, uint8_t *scratch);
 
 #ifdef __cplusplus
 }

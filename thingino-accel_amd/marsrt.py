@@ -94,7 +94,11 @@ class YoloDflHeads(C.Structure):  # mars_yolo_dfl_heads_t: zero = default in eve
 class PipeOpts(C.Structure):
     _fields_ = [("download_outputs", C.c_int), ("detect", C.c_int), ("det_outputs", C.c_int * 4), ("n_det_outputs", C.c_int),
                 ("nms_thresh", C.c_float), ("camera_w", C.c_int), ("camera_h", C.c_int), ("heads", C.POINTER(YoloHeads)),
-                ("dfl_heads", C.POINTER(YoloDflHeads))]
+                ("dfl_heads", C.POINTER(YoloDflHeads)), ("camera_format", C.c_int), ("camera_flags", C.c_uint)]
+
+
+CAMERA_RGB, CAMERA_NV12 = 0, 1        # MARS_HIP_CAMERA_*
+NV12_FULL_RANGE, NV12_VU = 1, 2       # MARS_NV12_*
 
 
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
@@ -130,7 +134,8 @@ EXPORTS = {
                    "mars_hip_pipe_input", "mars_hip_pipe_submit", "mars_hip_pipe_wait", "mars_hip_pipe_close", "mars_hip_pipe_camera_ms", "mars_hip_set_output_mode",
                    "mars_hip_get_tuning", "mars_hip_model_set_tuning", "mars_hip_model_get_tuning", "mars_yolo_find_heads",
                    "mars_hip_detect_heads", "mars_hip_detect_heads_device", "mars_hip_detect_results", "mars_yolo_find_dfl_heads",
-                   "mars_hip_detect_dfl", "mars_hip_detect_dfl_device", "mars_synth_model_head"],
+                   "mars_hip_detect_dfl", "mars_hip_detect_dfl_device", "mars_synth_model_head", "mars_hip_nv12_frame_bytes",
+                   "mars_yolo_nv12_to_rgb", "mars_yolo_letterbox_nv12", "mars_hip_preprocess_nv12", "mars_hip_preprocess_nv12_device"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -203,6 +208,12 @@ def lib():
     L.mars_yolo_letterbox.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.mars_hip_preprocess.argtypes = [P(MarsModel), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
     L.mars_hip_preprocess_device.argtypes = [P(MarsModel), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mars_hip_nv12_frame_bytes.restype = C.c_size_t
+    L.mars_hip_nv12_frame_bytes.argtypes = [C.c_int, C.c_int]
+    L.mars_yolo_nv12_to_rgb.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p]
+    L.mars_yolo_letterbox_nv12.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p]
+    L.mars_hip_preprocess_nv12.argtypes = [P(MarsModel), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
+    L.mars_hip_preprocess_nv12_device.argtypes = [P(MarsModel), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -277,6 +288,36 @@ def letterbox(rgb, tw, th, nhwc=True):
     out = np.zeros(tw * th * 3, dtype=np.int8)
     if lib().mars_yolo_letterbox(rgb.ctypes.data, w, h, tw, th, int(bool(nhwc)), out.ctypes.data) != 0:
         raise RuntimeError("mars_yolo_letterbox failed")
+    return out
+
+
+def _nv12_frames(nv12, w, h, batched):
+    """NV12 bytes as a contiguous uint8 array of [n, w * h * 3 / 2] (batched) or [w * h * 3 / 2]; the size must fit (odd sizes: the
+    library refuses them, so whatever arrives is passed on)"""
+    a = np.ascontiguousarray(nv12, dtype=np.uint8)
+    fb = lib().mars_hip_nv12_frame_bytes(int(w), int(h))
+    if fb:
+        a = a.reshape(-1, fb) if batched else a.reshape(-1)
+        if not batched and a.size != fb:
+            raise ValueError("an NV12 frame of %d x %d is %d bytes, got %d" % (w, h, fb, a.size))
+    return a
+
+
+def nv12_to_rgb(nv12, w, h, flags=0):
+    """mars_yolo_nv12_to_rgb: one NV12 frame (w * h * 3 / 2 bytes: Y plane, then interleaved chroma) -> uint8 RGB [h][w][3], on the GPU."""
+    a = _nv12_frames(nv12, w, h, False)
+    out = np.zeros((max(int(h), 0), max(int(w), 0), 3), dtype=np.uint8)
+    if lib().mars_yolo_nv12_to_rgb(a.ctypes.data, int(w), int(h), int(flags), out.ctypes.data) != 0:
+        raise RuntimeError("mars_yolo_nv12_to_rgb failed")
+    return out
+
+
+def letterbox_nv12(nv12, w, h, tw, th, nhwc=True, flags=0):
+    """mars_yolo_letterbox_nv12: one NV12 frame -> int8 letterboxed frame, on the GPU (what letterbox() gives for nv12_to_rgb() of it)."""
+    a = _nv12_frames(nv12, w, h, False)
+    out = np.zeros(tw * th * 3, dtype=np.int8)
+    if lib().mars_yolo_letterbox_nv12(a.ctypes.data, int(w), int(h), tw, th, int(bool(nhwc)), int(flags), out.ctypes.data) != 0:
+        raise RuntimeError("mars_yolo_letterbox_nv12 failed")
     return out
 
 
@@ -497,6 +538,14 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_preprocess")
 
+    def preprocess_nv12(self, nv12_frames, w, h, flags=0, first_frame=0, input_index=0):
+        """NV12 frames [n][w * h * 3 / 2] -> letterboxed int8 frames of the graph input, in HBM (mars_hip_preprocess_nv12)"""
+        a = _nv12_frames(nv12_frames, w, h, True)
+        n = a.shape[0] if a.ndim > 1 else 1
+        rc = lib().mars_hip_preprocess_nv12(self.p, input_index, a.ctypes.data, int(w), int(h), int(flags), first_frame, n)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_preprocess_nv12")
+
     def set_tuning(self, key, value):
         """per-model override of a launch-policy knob (mars_hip_model_set_tuning)"""
         if lib().mars_hip_model_set_tuning(self.p, key.encode(), int(value)) != 0:
@@ -586,8 +635,10 @@ class Model:
         return [dets[f, :counts[f]].copy() for f in range(self.batch)]
 
     # -- pipelined host I/O (mars_hip_pipe_*)
-    def pipe_open(self, download_outputs=True, detect=False, det_outputs=(0,), thresh=0.45, camera=None, heads=None, dfl_heads=None):
+    def pipe_open(self, download_outputs=True, detect=False, det_outputs=(0,), thresh=0.45, camera=None, heads=None, dfl_heads=None,
+                  camera_format=CAMERA_RGB, camera_flags=0):
         """camera = (w, h): input 0 is fed from uint8 RGB camera frames, the letterbox front-end runs on the device behind the upload.
+        camera_format = CAMERA_NV12: the frames are NV12 (w * h * 3 / 2 bytes each; camera_flags: NV12_FULL_RANGE | NV12_VU).
         heads (with detect): True (found on the file), a list as for detect_heads() or a YoloHeads -- the tail decodes those raw
         heads instead of det_outputs; in camera mode their boxes come back in camera pixels.  dfl_heads: the same for anchor-free DFL
         heads (True, a list as for detect_dfl() or a YoloDflHeads); not both"""
@@ -600,18 +651,22 @@ class Model:
         if dfl_heads is not None and dfl_heads is not False:
             dh = dfl_heads if isinstance(dfl_heads, YoloDflHeads) else yolo_dfl_heads(None if dfl_heads is True else dfl_heads, thresh=thresh)
             o.dfl_heads = C.pointer(dh)
+        o.camera_format, o.camera_flags = int(camera_format), int(camera_flags)
         rc = lib().mars_hip_pipe_open(self.p, C.byref(o))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_pipe_open")
         self._pipe = (bool(download_outputs), bool(detect))
         self._pipe_camera = (int(cw), int(ch)) if camera else None
+        self._pipe_camera_nv12 = bool(camera) and int(camera_format) == CAMERA_NV12
 
     def pipe_input_view(self, i=0):
         """uint8 view [batch, frame_bytes] of the staging buffer the NEXT pipe_submit() uploads (camera mode, input 0:
-        [batch, h * w * 3] RGB bytes)"""
+        [batch, h * w * 3] RGB bytes, or [batch, h * w * 3 / 2] NV12 bytes)"""
         ptr = lib().mars_hip_pipe_input(self.p, i)
         if i == 0 and getattr(self, "_pipe_camera", None):
             n = self._pipe_camera[0] * self._pipe_camera[1] * 3 * self.batch
+            if self._pipe_camera_nv12:
+                n = lib().mars_hip_nv12_frame_bytes(*self._pipe_camera) * self.batch
         else:
             n = lib().mars_hip_tensor_frame_bytes(self.p, self.header.input_tensor_ids[i]) * self.batch
         return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n,)).reshape(self.batch, -1)
