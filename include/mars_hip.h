@@ -373,6 +373,68 @@ mars_error_t mars_hip_preprocess_nv12(mars_model_t *model, int input_index, cons
 mars_error_t mars_hip_preprocess_nv12_device(mars_model_t *model, int input_index, const void *nv12_dev, int w, int h, unsigned flags,
                                              int first_frame, int frames);
 
+/* --------------------------------------------------------------- ROI crops */
+/* The second stage of a camera deployment: every detected person, face or plate is cut out of its frame, resized and handed to a small
+ * classifier or embedder (the reference ships such a shape: tiny_160_int8.mars, 3 x 160 x 160 int8).  The frames, the detections
+ * (mars_hip_detect_*_device) and the second model's input are all in HBM; the calls below connect them on the device.  Everything that
+ * touches a pixel is integer arithmetic, so the bytes are defined exactly:
+ *
+ * Box -> source rectangle.  A mars_det_t in source-frame pixels (centre x, y, size w, h), frames of W x H.  float32, every operation
+ *   rounded on its own, no fused multiply-add:
+ *     hw = (w * expand) * 0.5f;  x0f = max(x - hw, 0);  x1f = min(x + hw, (float)W);  x0 = (int)floorf(x0f);  x1 = (int)ceilf(x1f)
+ *   (y alike with h, H);  cw = x1 - x0, ch = y1 - y0.  The box is SKIPPED when a float field is not finite, w <= 0, h <= 0, cw < min_size or
+ *   ch < min_size.  expand == 0 means 1.0, min_size == 0 means 2.  (Before the conversions x0f is limited to W + 1 and x1f to -1, so that
+ *   they are defined for boxes far outside the frame; such a box has cw < 0 either way.)
+ * Target geometry for a tw x th input.  Stretch (default): nw = tw, nh = th, px = py = 0.  MARS_ROI_KEEP_ASPECT, integers only:
+ *     cw * th >= ch * tw:  nw = tw, nh = max(1, (ch * tw + cw / 2) / cw);   otherwise:  nh = th, nw = max(1, (cw * th + ch / 2) / ch);
+ *     px = (tw - nw) / 2, py = (th - nh) / 2.
+ *   Pixels outside [px, px + nw) x [py, py + nh) are -17, the reference's grey, as in the letterbox.
+ * Resize.  Bilinear, half-pixel centres, 8 fractional bits.  Output column i of [0, nw) (64-bit intermediates, / is floor: the
+ *   numerator is not negative):
+ *     pos = ((2 i + 1) * cw * 256) / (2 * nw) - 128, clamped to [0, (cw - 1) * 256];  i0 = pos >> 8, fx = pos & 255, i1 = min(i0 + 1, cw - 1)
+ *   rows alike with ch, nh: j0, j1, fy.  Per channel, a, b = the crop's pixels (i0, j0), (i1, j0), c, d = (i0, j1), (i1, j1), each 0 .. 255:
+ *     top = a * (256 - fx) + b * fx;  bot = c * (256 - fx) + d * fx;  v = (top * (256 - fy) + bot * fy + 32768) >> 16;  out = (int8)(v - 128)
+ *   The output layout is the one the destination's format tag asks for ([th][tw][3] or [3][th][tw]), as mars_hip_preprocess decides it.
+ * NV12 source.  The four taps are converted with the integer BT.601 formulas of "NV12 camera frames" above, the chroma pair taken at
+ *   (x >> 1, y >> 1) in FRAME coordinates, all MARS_NV12_* flags apply; then the blend.  An NV12 crop equals the RGB crop of
+ *   mars_yolo_nv12_to_rgb of that frame, bit for bit.
+ * Selection (the detection forms).  Boxes are visited by ascending frame, inside a frame in the order the tail left them.  A box is kept when
+ *   conf >= min_conf, cls_count == 0 or cls_first <= cls < cls_first + cls_count, the rectangle rule does not skip it, and fewer than
+ *   max_per_frame boxes of its frame are kept already (0: no limit).  Kept boxes fill the destination's frames 0, 1, ... in visiting
+ *   order up to its current batch; the boxes beyond are counted as dropped.  Destination frames behind the last crop are filled with -17. */
+typedef struct { int frame, det, x0, y0, x1, y1; } mars_roi_t; /* 24 bytes; det = index inside its frame's list (-1: a caller's box) */
+#define MARS_ROI_KEEP_ASPECT 1u
+/* Zero-initialise; zero means default in every field but the frame size. */
+typedef struct {
+    int src_w, src_h, src_format; unsigned src_flags; /* frames: MARS_HIP_CAMERA_RGB / _NV12, MARS_NV12_* (NV12 only) */
+    float expand, min_conf; int min_size;
+    int cls_first, cls_count, max_per_frame;
+    unsigned flags;                                    /* MARS_ROI_KEEP_ASPECT */
+} mars_hip_roi_opts_t;
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL pointer, a non-positive size, an unknown
+ * format or flag bit, odd NV12 sizes, a negative or non-finite expand / min_conf / min_size / cls_count / max_per_frame, frames or targets
+ * too wide for the crop kernel's on-chip buffers (about 5000 pixels).  MARS_ERR_INVALID_TENSOR: det_model == dst_model, a destination input
+ * that is not int8 with 3 channels, no detections in HBM, a model with an open pipe. */
+/* The mars_yolo_letterbox of this feature: host pointers in and out, runs on the GPU.  `frames` = n_frames frames of opts->src_w x src_h,
+ * densely packed; box i lies in frame frame_of_box[i].  Only the rectangle rule applies.  out = [n_boxes][tw * th * 3] int8 ([th][tw][3] with
+ * nhwc != 0, else [3][th][tw]), a skipped box's crop is all -17 and rois[i].x1 == rois[i].x0 marks it (rois may be NULL). */
+mars_error_t mars_yolo_crop_boxes(const unsigned char *frames, int n_frames, const mars_det_t *boxes, const int *frame_of_box, int n_boxes,
+                                  const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc, signed char *out, mars_roi_t *rois);
+/* The device-only chain.  Reads the detections the last mars_hip_detect_device / _heads_device / _dfl_device of det_model left in HBM (as
+ * mars_hip_detect_results would; they must be in source-frame pixels already, i.e. decoded with src_w / src_h set) and det_model's batch of
+ * frames at frames_dev (densely packed, as for mars_hip_preprocess[_nv12]_device), selects, and writes the crops into input `input_index`
+ * of dst_model, one per frame of its batch.  Enqueues only: the work goes on the library's main stream behind the event the detection tail
+ * records (the one the next run's head-writing layers wait for), so it is ordered behind the tail, behind any earlier run of dst_model and
+ * ahead of its next mars_hip_run_device[_async]. */
+mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
+                                             const mars_hip_roi_opts_t *opts);
+/* The same with the frames in host memory: uploads them, crops, waits. */
+mars_error_t mars_hip_crop_detections(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
+                                      const mars_hip_roi_opts_t *opts);
+/* The ROI table of the last crop call into dst_model (waits for it): rois[k] = where frame k of the input came from, for the first
+ * min(kept, cap) frames (rois may be NULL with cap 0); *n_kept crops were written, *n_dropped selected boxes found no frame. */
+mars_error_t mars_hip_roi_results(mars_model_t *dst_model, mars_roi_t *rois, int cap, int *n_kept, int *n_dropped);
+
 #ifdef __cplusplus
 }
 #endif

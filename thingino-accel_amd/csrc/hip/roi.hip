@@ -1,0 +1,318 @@
+// roi.hip -- ROI crops on gfx950: detected boxes -> source rectangles -> bilinear crops written straight into a second model's input.
+//
+// include/mars_hip.h ("ROI crops") states the arithmetic; everything that touches a pixel is integer, so the bytes are defined exactly.  The
+// reference has no such step (its demo stops at the boxes, src/mars/mars_yolo_test.c:132-214); the frames, the detections and the second
+// model's input all live in HBM here, and these kernels are the link between them:
+//   roi_select_kernel<0 / 1>  the selection rules over the detection lists a tail left in HBM: per-frame kept counts by wave ballots in list
+//                             order, slot offsets by a sum over the frames in front, the ROI table and the kept / dropped counters;
+//   roi_rects_kernel          the rectangle rule alone over a caller's boxes (mars_yolo_crop_boxes), box i -> slot i;
+//   roi_crop_kernel<FMT>      a workgroup owns ROI_R output rows of one destination slot.  The geometry differs per box and only the device
+//                             knows it: the kernel reads the kept count and its rectangle from device memory, builds the column table in
+//                             LDS, stages the source-row segments its rows touch in LDS (NV12: converted once per pixel while staging),
+//                             blends from LDS, puts the strip's bytes together in LDS and stores contiguous runs 16 bytes at a time.
+// Nothing here uses atomics: a slot number is a function of the lists alone.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../mhip.h"
+#include "nv12.hpp"
+
+extern "C" hipStream_t mhip_stream_native(void);
+extern "C" int mhip_check(hipError_t e, const char *what);
+
+struct roi_rec_t { int frame, det, x0, y0, x1, y1; };   // mars_roi_t
+struct roi_det_t { float x, y, w, h, conf; int cls; };  // mars_det_t
+
+// box -> source rectangle; false = skipped (the rectangle is then all zeros).  float32, every operation rounded on its own (-ffp-contract=off).
+// The two clamps in front of the conversions keep far-away boxes inside the int range and change no decision: x0f > W + 1 means x0 > x1 anyway
+__device__ __forceinline__ bool roi_rect(const roi_det_t d, const float expand, const int min_size, const int W, const int H, int &x0, int &y0,
+                                         int &x1, int &y1) {
+    x0 = y0 = x1 = y1 = 0;
+    if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf))) return false;
+    if (!(d.w > 0.0f) || !(d.h > 0.0f)) return false;
+    const float hw = (d.w * expand) * 0.5f, hh = (d.h * expand) * 0.5f;
+    float x0f = fmaxf(d.x - hw, 0.0f), x1f = fminf(d.x + hw, (float)W);
+    float y0f = fmaxf(d.y - hh, 0.0f), y1f = fminf(d.y + hh, (float)H);
+    x0f = fminf(x0f, (float)(W + 1)); x1f = fmaxf(x1f, -1.0f);
+    y0f = fminf(y0f, (float)(H + 1)); y1f = fmaxf(y1f, -1.0f);
+    const int ax0 = (int)floorf(x0f), ax1 = (int)ceilf(x1f), ay0 = (int)floorf(y0f), ay1 = (int)ceilf(y1f);
+    if (ax1 - ax0 < min_size || ay1 - ay0 < min_size) return false;
+    x0 = ax0; y0 = ay0; x1 = ax1; y1 = ay1;
+    return true;
+}
+
+// One wave per frame.  PHASE 0 counts the frame's kept boxes into frame_kept[f]; PHASE 1 (a second launch: it needs every frame's count) sums
+// the counts of the frames in front into the frame's first slot, walks the list again the same way and writes the table.  A box's rank inside
+// its frame = kept boxes in front of it in the list: the ballot of the 64 boxes in flight, masked below the lane, plus the chunks before.
+template <int PHASE>
+__global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
+    const int f = blockIdx.x, lane = threadIdx.x;
+    int base = 0;
+    if (PHASE == 1) {
+        int before = 0, all = 0;
+        for (int i = lane; i < p.n_frames; i += 64) {
+            const int k = p.frame_kept[i];
+            all += k;
+            if (i < f) before += k;
+        }
+        for (int s = 32; s > 0; s >>= 1) {
+            before += __shfl_xor(before, s, 64);
+            all += __shfl_xor(all, s, 64);
+        }
+        base = before;
+        if (f == 0 && lane == 0) {
+            const int kept = min(all, p.slots);
+            p.n_out[0] = kept;
+            p.n_out[1] = all - kept;
+        }
+    }
+    const int n = min(max(p.counts[f], 0), p.det_cap);
+    const roi_det_t *dets = (const roi_det_t *)p.dets + (size_t)f * p.det_cap;
+    roi_rec_t *rois = (roi_rec_t *)p.rois;
+    int kept = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        bool ok = false;
+        int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+        if (i < n) {
+            const roi_det_t d = dets[i];
+            ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
+                 roi_rect(d, p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
+        }
+        const unsigned long long mask = __ballot(ok);
+        const int rank = kept + __popcll(mask & ((1ull << lane) - 1ull));
+        if (p.max_per_frame > 0 && rank >= p.max_per_frame) ok = false;
+        if (PHASE == 1 && ok && base + rank < p.slots) {
+            roi_rec_t r;
+            r.frame = f; r.det = i; r.x0 = x0; r.y0 = y0; r.x1 = x1; r.y1 = y1;
+            rois[base + rank] = r;
+        }
+        kept += __popcll(mask);
+        if (p.max_per_frame > 0 && kept >= p.max_per_frame) {
+            kept = p.max_per_frame;
+            break;
+        }
+    }
+    if (PHASE == 0 && lane == 0) p.frame_kept[f] = kept;
+}
+
+__global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) {
+        p.n_out[0] = min(p.n_boxes, p.slots);
+        p.n_out[1] = 0;
+    }
+    if (i >= p.n_boxes || i >= p.slots) return;
+    roi_rec_t r;
+    r.frame = p.frame_of_box[i];
+    r.det = -1;
+    const bool ok = r.frame >= 0 && r.frame < p.n_frames;
+    const roi_det_t d = ((const roi_det_t *)p.boxes)[i];
+    r.x0 = r.y0 = r.x1 = r.y1 = 0;
+    if (ok) roi_rect(d, p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
+    ((roi_rec_t *)p.rois)[i] = r;
+}
+
+#define ROI_R 8 // output rows of a strip
+
+// n bytes of -17 at o, any alignment: bytes up to the first 16-byte boundary, 16-byte stores, bytes behind the last one
+__device__ __forceinline__ void roi_fill_run(int8_t *o, const int n, const int tid) {
+    const int head = min(n, (int)((16u - (unsigned)((uintptr_t)o & 15)) & 15u)), body = (n - head) & ~15;
+    const unsigned g = 0xefefefefu; // (int8) -17
+    for (int i = tid; i < head; i += 256) o[i] = (int8_t)-17;
+    for (int i = tid * 16; i < body; i += 256 * 16) *(uint4 *)(o + head + i) = make_uint4(g, g, g, g);
+    for (int i = head + body + tid; i < n; i += 256) o[i] = (int8_t)-17;
+}
+// n bytes from LDS to o; l and o are congruent mod 16, so the 16-byte runs are aligned on both sides
+__device__ __forceinline__ void roi_store_run(int8_t *o, const int8_t *l, const int n, const int tid) {
+    const int head = min(n, (int)((16u - (unsigned)((uintptr_t)o & 15)) & 15u)), body = (n - head) & ~15;
+    for (int i = tid; i < head; i += 256) o[i] = l[i];
+    for (int i = tid * 16; i < body; i += 256 * 16) *(uint4 *)(o + head + i) = *(const uint4 *)(l + head + i);
+    for (int i = head + body + tid; i < n; i += 256) o[i] = l[i];
+}
+
+// position of output sample i of n_out over n_in source samples, half-pixel centres, 8 fractional bits, clamped to the source
+__device__ __forceinline__ int roi_pos(const int i, const int n_in, const int n_out) {
+    long long pos = ((long long)(2 * i + 1) * n_in * 256) / (2LL * n_out) - 128;
+    pos = pos < 0 ? 0 : pos;
+    const long long top = (long long)(n_in - 1) * 256;
+    return (int)(pos > top ? top : pos);
+}
+
+static size_t roi_r16(size_t x) { return (x + 15) & ~(size_t)15; }
+// LDS of the crop kernel: [column table][group record][strip bytes][source rows]
+static size_t roi_lds_col(int tw) { return roi_r16((size_t)tw * 8); }
+#define ROI_META 256
+static size_t roi_lds_stage(int tw) { return 3 * (roi_r16((size_t)ROI_R * tw) + 16); } // per channel: a strip's rows + the offset inside a 16-byte line
+static size_t roi_pitch_max(int w, int fmt) { return fmt ? roi_r16((((size_t)w + 3) & ~(size_t)3) * 3) : roi_r16((size_t)w * 3); }
+static size_t roi_rowbuf(int w, int fmt) {
+    const size_t pm = roi_pitch_max(w, fmt), all = 2 * ROI_R * pm;
+    return all < 32 * 1024 ? all : (2 * pm > 32 * 1024 ? 2 * pm : 32 * 1024);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const int off_meta, const int off_stage, const int off_rows, const int rowbuf_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    const int tid = threadIdx.x;
+    const int slot = blockIdx.y, ys = blockIdx.x * ROI_R;
+    const int rows = min(ROI_R, p.th - ys), row_b = p.tw * 3;
+    int8_t *dst = p.out + (size_t)slot * p.out_stride;
+    // this slot's geometry, from device memory
+    bool live = slot < p.n_out[0];
+    roi_rec_t r = {0, 0, 0, 0, 0, 0};
+    if (live) r = ((const roi_rec_t *)p.rois)[slot];
+    const int cw = r.x1 - r.x0, ch = r.y1 - r.y0;
+    live = live && cw > 0 && ch > 0 && r.frame >= 0 && r.frame < p.n_frames && r.x0 >= 0 && r.y0 >= 0 && r.x1 <= p.w && r.y1 <= p.h;
+    int nw = p.tw, nh = p.th;
+    if (live && p.keep_aspect) {
+        if ((long long)cw * p.th >= (long long)ch * p.tw) nh = max(1, (int)(((long long)ch * p.tw + cw / 2) / cw));
+        else nw = max(1, (int)(((long long)cw * p.th + ch / 2) / ch));
+    }
+    const int px = (p.tw - nw) / 2, py = (p.th - nh) / 2;
+    const int r_lo = max(py - ys, 0), r_hi = min(py + nh - ys, rows); // the strip's rows inside the resized crop
+    if (!live || r_hi <= r_lo) { // an empty slot, a skipped box or a pad band: grey, the source is not touched
+        if (p.nhwc) roi_fill_run(dst + (size_t)ys * row_b, rows * row_b, tid);
+        else
+            for (int c = 0; c < 3; c++) roi_fill_run(dst + ((size_t)c * p.th + ys) * p.tw, rows * p.tw, tid);
+        return;
+    }
+    int2 *coltab = (int2 *)sm;                       // [nw] {byte offset of the left tap in a staged row, fx | (distance to the right tap) << 8}
+    int *meta = (int *)(sm + off_meta);              // [0] end of the group of rows, [1] staged source rows; [4 ..) their numbers; [32 ..) per strip row {slot a, slot b, fy, -}
+    int8_t *stage = (int8_t *)(sm + off_stage);
+    unsigned char *rowbuf = sm + off_rows;
+    const uint8_t *frame = p.frames + (size_t)r.frame * p.frame_stride;
+    // a staged row holds the pixels [xe, x1) of a source row as RGB bytes; NV12 rows are converted four pixels at a time from an even column
+    const int xe = FMT ? (r.x0 & ~1) : r.x0;
+    const int units = FMT ? (r.x1 - xe + 3) >> 2 : (cw * 3 + 15) >> 4; // quads of pixels / 16-byte pieces per staged row
+    const int pitch = FMT ? (units * 12 + 15) & ~15 : units * 16;
+    const int cap_rows = rowbuf_bytes / pitch; // >= 2: the launcher sized the buffer for the widest box
+    for (int i = tid; i < nw; i += 256) {
+        const int pos = roi_pos(i, cw, nw), i0 = pos >> 8, i1 = min(i0 + 1, cw - 1);
+        coltab[i] = make_int2((i0 + r.x0 - xe) * 3, (pos & 255) | ((i1 - i0) * 3) << 8);
+    }
+    // the strip's bytes: grey first (bands left / right of the crop, rows outside it).  The strip (planar: each channel's rows) is one contiguous
+    // run of the destination; its LDS image starts at the same offset inside a 16-byte line as the run does in memory
+    int8_t *st[3];
+    const int chan = ((ROI_R * p.tw + 15) & ~15) + 16; // bytes per channel region: a multiple of 16, so every region starts on a 16-byte line
+    if (p.nhwc) st[0] = st[1] = st[2] = stage + ((uintptr_t)(dst + (size_t)ys * row_b) & 15);
+    else
+        for (int c = 0; c < 3; c++) st[c] = stage + c * chan + ((uintptr_t)(dst + ((size_t)c * p.th + ys) * p.tw) & 15);
+    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
+    const nv12_coef_t kc = nv12_coef(p.nv12_flags);
+    int r_cur = r_lo;
+    while (r_cur < r_hi) {
+        // the next group of rows: as many as the row buffer holds source rows for.  Source rows only grow along the strip, so a row that is
+        // already staged is one of the last two
+        if (tid == 0) {
+            int n_st = 0, rr = r_cur;
+            for (; rr < r_hi; rr++) {
+                const int pos = roi_pos(ys + rr - py, ch, nh), j0 = pos >> 8, j1 = min(j0 + 1, ch - 1);
+                int a = -1, b = -1;
+                for (int k = max(n_st - 2, 0); k < n_st; k++) {
+                    if (meta[4 + k] == j0) a = k;
+                    if (meta[4 + k] == j1) b = k;
+                }
+                const int need = (a < 0) + (j1 != j0 && b < 0);
+                if (n_st + need > cap_rows) break;
+                if (a < 0) { a = n_st; meta[4 + n_st++] = j0; }
+                if (j1 == j0) b = a;
+                else if (b < 0) { b = n_st; meta[4 + n_st++] = j1; }
+                meta[32 + 4 * rr] = a; meta[32 + 4 * rr + 1] = b; meta[32 + 4 * rr + 2] = pos & 255;
+            }
+            meta[0] = rr; meta[1] = n_st;
+        }
+        __syncthreads(); // (the first time round also: the column table and the grey strip)
+        const int r_end = meta[0], n_st = meta[1];
+        for (int it = tid; it < n_st * units; it += 256) {
+            const int s = it / units, u = it - s * units;
+            const int sy = r.y0 + meta[4 + s];
+            if (FMT) { // Y bytes of pixels xe + 4 u .. + 3 and, at the same byte offset of chroma row sy >> 1, their two chroma pairs
+                const int x = xe + 4 * u;
+                const uint8_t *gy = frame + (size_t)sy * p.w + x, *gc = frame + ((size_t)p.h + (size_t)(sy >> 1)) * p.w + x;
+                unsigned yv, cv;
+                if (x + 4 <= p.w) {
+                    __builtin_memcpy(&yv, gy, 4);
+                    __builtin_memcpy(&cv, gc, 4);
+                } else { // w % 4 == 2: the row's last two pixels and their one pair; nothing is read beyond either row
+                    yv = (unsigned)gy[0] | (unsigned)gy[1] << 8;
+                    cv = (unsigned)gc[0] | (unsigned)gc[1] << 8;
+                }
+                int c[4][3];
+                nv12_quad(kc, yv, cv, c);
+                unsigned *o = (unsigned *)(rowbuf + s * pitch + u * 12);
+                o[0] = (unsigned)c[0][0] | (unsigned)c[0][1] << 8 | (unsigned)c[0][2] << 16 | (unsigned)c[1][0] << 24;
+                o[1] = (unsigned)c[1][1] | (unsigned)c[1][2] << 8 | (unsigned)c[2][0] << 16 | (unsigned)c[2][1] << 24;
+                o[2] = (unsigned)c[2][2] | (unsigned)c[3][0] << 8 | (unsigned)c[3][1] << 16 | (unsigned)c[3][2] << 24;
+            } else { // 16 bytes of the segment [x0 * 3, x1 * 3) of the row; the last piece byte by byte: nothing is read beyond the segment
+                const uint8_t *g = frame + ((size_t)sy * p.w + r.x0) * 3 + (size_t)u * 16;
+                unsigned v[4] = {0u, 0u, 0u, 0u};
+                const int left = cw * 3 - u * 16;
+                if (left >= 16) __builtin_memcpy(v, g, 16);
+                else {
+#pragma unroll
+                    for (int b = 0; b < 15; b++) // (register indices fixed by the unrolling)
+                        if (b < left) v[b >> 2] |= (unsigned)g[b] << (8 * (b & 3));
+                }
+                *(uint4 *)(rowbuf + s * pitch + u * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        __syncthreads();
+        const int npix = (r_end - r_cur) * nw;
+        for (int idx = tid; idx < npix; idx += 256) {
+            const int rr = idx / nw, i = idx - rr * nw, row = r_cur + rr;
+            const int4 rt = *(const int4 *)(meta + 32 + 4 * row);
+            const unsigned char *ra = rowbuf + rt.x * pitch, *rb = rowbuf + rt.y * pitch;
+            const int2 ct = coltab[i];
+            const int o0 = ct.x, o1 = ct.x + (ct.y >> 8), fx = ct.y & 255, fy = rt.z;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const int top = (int)ra[o0 + c] * (256 - fx) + (int)ra[o1 + c] * fx;
+                const int bot = (int)rb[o0 + c] * (256 - fx) + (int)rb[o1 + c] * fx;
+                const int v = (top * (256 - fy) + bot * fy + 32768) >> 16;
+                const int8_t q = (int8_t)(v - 128);
+                if (p.nhwc) st[0][row * row_b + (px + i) * 3 + c] = q;
+                else st[c][row * p.tw + px + i] = q;
+            }
+        }
+        __syncthreads(); // the rows and the group record may be overwritten
+        r_cur = r_end;
+    }
+    if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
+    else
+        for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
+}
+
+static bool roi_common_ok(const mhip_roi_t *p) {
+    return p && p->rois && p->n_out && p->w > 0 && p->h > 0 && p->n_frames > 0 && p->slots > 0 && p->expand > 0 && p->min_size >= 1 &&
+           (p->fmt == 0 || (p->fmt == 1 && !(p->w & 1) && !(p->h & 1) && !(p->nv12_flags & ~3u)));
+}
+
+extern "C" int mhip_roi_select(const mhip_roi_t *p) {
+    if (!roi_common_ok(p) || !p->dets || !p->counts || !p->frame_kept || p->det_cap <= 0 || p->cls_count < 0 || p->max_per_frame < 0) return -1;
+    hipLaunchKernelGGL(roi_select_kernel<0>, dim3((unsigned)p->n_frames), dim3(64), 0, mhip_stream_native(), *p);
+    hipLaunchKernelGGL(roi_select_kernel<1>, dim3((unsigned)p->n_frames), dim3(64), 0, mhip_stream_native(), *p);
+    return mhip_check(hipGetLastError(), "roi select");
+}
+
+extern "C" int mhip_roi_rects(const mhip_roi_t *p) {
+    if (!roi_common_ok(p) || !p->boxes || !p->frame_of_box || p->n_boxes <= 0 || p->n_boxes > p->slots) return -1;
+    hipLaunchKernelGGL(roi_rects_kernel, dim3((unsigned)((p->n_boxes + 255) / 256)), dim3(256), 0, mhip_stream_native(), *p);
+    return mhip_check(hipGetLastError(), "roi rects");
+}
+
+extern "C" int mhip_roi_fits(int w, int tw, int fmt) {
+    if (w <= 0 || tw <= 0) return 0;
+    return roi_lds_col(tw) + ROI_META + roi_lds_stage(tw) + roi_rowbuf(w, fmt) <= 64 * 1024;
+}
+
+extern "C" int mhip_roi_crop(const mhip_roi_t *p) {
+    if (!roi_common_ok(p) || !p->frames || !p->out || p->tw <= 0 || p->th <= 0 || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 ||
+        !mhip_roi_fits(p->w, p->tw, p->fmt))
+        return -1;
+    const int off_meta = (int)roi_lds_col(p->tw), off_stage = off_meta + ROI_META, off_rows = off_stage + (int)roi_lds_stage(p->tw);
+    const int rowbuf = (int)roi_rowbuf(p->w, p->fmt);
+    const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);
+    if (p->fmt) hipLaunchKernelGGL(roi_crop_kernel<1>, g, dim3(256), (size_t)off_rows + rowbuf, mhip_stream_native(), *p, off_meta, off_stage, off_rows, rowbuf);
+    else hipLaunchKernelGGL(roi_crop_kernel<0>, g, dim3(256), (size_t)off_rows + rowbuf, mhip_stream_native(), *p, off_meta, off_stage, off_rows, rowbuf);
+    return mhip_check(hipGetLastError(), p->fmt ? "roi crop (nv12)" : "roi crop");
+}

@@ -172,6 +172,9 @@ typedef struct mars_model_ext {
     int n_tune, tune_depth;
     int plan_f32_mode; /* the f32_mfma mode build_plan ran under (weight images, record pairs): replan_for_f32_mode */
     unsigned char *layer_noop; /* [num_layers]: plan_layer emitted no launch for it (the runtime treats it as a no-op; mars_yolo_find_heads) */
+    void *roi_dev;      /* ROI crops INTO this model (mars_roi.c): [kept, dropped, -, -][roi_cap_slots] x mars_roi_t[roi_cap_frames] x int, on the device */
+    int roi_cap_slots, roi_cap_frames;
+    int roi_slots;      /* slots of the last crop call (its batch then); 0 = there was none */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -228,6 +231,9 @@ MARS_INTERNAL void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op
 /* mars_preproc.c */
 MARS_INTERNAL int mars_preproc_prepare(int w, int h, int tw, int th); /* gather tables of a letterbox geometry, cached */
 MARS_INTERNAL int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int frames); /* the same + the conversion scratch, where NV12 frames need one */
+
+/* mars_roi.c */
+MARS_INTERNAL void mars_roi_release(mars_model_ext_t *m); /* the ROI table of a model whose device state goes away */
 
 /* detection tail pieces shared with the pipelined I/O (mars_yolo.c) */
 mars_error_t mars_detect_prepare(mars_model_ext_t *m, const int *output_indices, int n_outputs);

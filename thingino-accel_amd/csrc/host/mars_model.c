@@ -92,6 +92,7 @@ static void free_device_state(mars_model_ext_t *m) {
     m->det_counts_dev = NULL;
     m->det_cap = 0;
     m->tail_pending = 0;
+    mars_roi_release(m);
 }
 
 static void free_ops(mars_model_ext_t *m) {

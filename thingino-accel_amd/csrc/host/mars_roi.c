@@ -1,0 +1,167 @@
+/*
+ * mars_roi.c -- host side of the ROI crops (include/mars_hip.h, "ROI crops"): argument checks, the ROI table hung on the destination
+ * model, stream ordering, and the launches of csrc/hip/roi.hip.  The reference stops at the boxes (src/mars/mars_yolo_test.c:132-214);
+ * a second stage there would cut crops on the host.  There is no CPU pixel path here: without the device every entry point fails.
+ */
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../mhip.h"
+#include "mars_hip.h"
+#include "mars_internal.h"
+
+#define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
+
+/* the checks that need no device and no model, and the defaults resolved into the launch record */
+static mars_error_t roi_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_roi_t *p) {
+    memset(p, 0, sizeof(*p));
+    if (!o || o->src_w <= 0 || o->src_h <= 0 || tw <= 0 || th <= 0) return MARS_ERR_INVALID_FILE;
+    if (o->src_format != MARS_HIP_CAMERA_RGB && o->src_format != MARS_HIP_CAMERA_NV12) return MARS_ERR_INVALID_FILE;
+    if (o->src_format == MARS_HIP_CAMERA_NV12 ? ((o->src_flags & ~NV12_FLAGS) || !mars_hip_nv12_frame_bytes(o->src_w, o->src_h)) : o->src_flags != 0)
+        return MARS_ERR_INVALID_FILE;
+    if (o->flags & ~MARS_ROI_KEEP_ASPECT) return MARS_ERR_INVALID_FILE;
+    if (!isfinite(o->expand) || o->expand < 0 || !isfinite(o->min_conf) || o->min_size < 0 || o->cls_count < 0 || o->max_per_frame < 0)
+        return MARS_ERR_INVALID_FILE;
+    if (!mhip_roi_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
+    p->w = o->src_w; p->h = o->src_h; p->fmt = o->src_format; p->nv12_flags = o->src_flags;
+    p->frame_stride = p->fmt ? mars_hip_nv12_frame_bytes(p->w, p->h) : (size_t)p->w * p->h * 3;
+    p->expand = o->expand != 0 ? o->expand : 1.0f;
+    p->min_conf = o->min_conf;
+    p->min_size = o->min_size ? o->min_size : 2;
+    p->cls_first = o->cls_first; p->cls_count = o->cls_count; p->max_per_frame = o->max_per_frame;
+    p->keep_aspect = (o->flags & MARS_ROI_KEEP_ASPECT) != 0;
+    p->tw = tw; p->th = th;
+    return MARS_OK;
+}
+
+mars_error_t mars_yolo_crop_boxes(const unsigned char *frames, int n_frames, const mars_det_t *boxes, const int *frame_of_box, int n_boxes,
+                                  const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc, signed char *out, mars_roi_t *rois) {
+    mhip_roi_t p;
+    const mars_error_t e = roi_opts(opts, tw, th, &p);
+    if (e != MARS_OK) return e;
+    if (!frames || !boxes || !frame_of_box || !out || n_frames <= 0 || n_boxes <= 0 || n_boxes > 65535) return MARS_ERR_INVALID_FILE;
+    if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
+    const size_t in_b = p.frame_stride * (size_t)n_frames, out_b = (size_t)tw * th * 3;
+    /* one device block: [frames][boxes][frame_of_box][counters][rois][out] */
+    size_t off[6], total = 0;
+    const size_t sz[6] = {in_b, (size_t)n_boxes * sizeof(mars_det_t), (size_t)n_boxes * sizeof(int), 16, (size_t)n_boxes * sizeof(mars_roi_t),
+                          out_b * (size_t)n_boxes};
+    for (int i = 0; i < 6; i++) {
+        off[i] = total;
+        total += ALIGN_UP(sz[i], 256);
+    }
+    uint8_t *d = (uint8_t *)mhip_malloc(total);
+    if (!d) return MARS_ERR_ALLOC_FAILED;
+    p.frames = d; p.n_frames = n_frames;
+    p.boxes = d + off[1]; p.frame_of_box = (const int *)(d + off[2]); p.n_boxes = n_boxes;
+    p.n_out = (int *)(d + off[3]); p.rois = d + off[4];
+    p.out = (int8_t *)(d + off[5]); p.out_stride = out_b; p.slots = n_boxes; p.nhwc = nhwc != 0;
+    int rc = mhip_h2d_async(d, frames, in_b);
+    if (!rc) rc = mhip_h2d_async(d + off[1], boxes, sz[1]);
+    if (!rc) rc = mhip_h2d_async(d + off[2], frame_of_box, sz[2]);
+    if (!rc) rc = mhip_roi_rects(&p);
+    if (!rc) rc = mhip_roi_crop(&p);
+    if (!rc) rc = mhip_d2h_async(out, p.out, sz[5]);
+    if (!rc && rois) rc = mhip_d2h_async(rois, p.rois, sz[4]);
+    if (mhip_sync()) rc = -1;
+    mhip_free(d);
+    return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
+}
+
+void mars_roi_release(mars_model_ext_t *m) {
+    if (m->roi_dev) mhip_free(m->roi_dev);
+    m->roi_dev = NULL;
+    m->roi_cap_slots = m->roi_cap_frames = m->roi_slots = 0;
+}
+
+/* the table of `slots` crops out of `frames` source frames, on the destination model; only ever grown */
+static int roi_table(mars_model_ext_t *m, int slots, int frames) {
+    if (m->roi_dev && m->roi_cap_slots >= slots && m->roi_cap_frames >= frames) return 0;
+    if (m->roi_dev && mhip_sync()) return -1; /* kernels queued earlier may still use the old one */
+    const int cs = slots > m->roi_cap_slots ? slots : m->roi_cap_slots, cf = frames > m->roi_cap_frames ? frames : m->roi_cap_frames;
+    mars_roi_release(m);
+    m->roi_dev = mhip_malloc(16 + (size_t)cs * sizeof(mars_roi_t) + (size_t)cf * sizeof(int));
+    if (!m->roi_dev) return -1;
+    m->roi_cap_slots = cs; m->roi_cap_frames = cf;
+    return 0;
+}
+
+mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
+                                             const mars_hip_roi_opts_t *opts) {
+    if (!det_model || !dst_model || !frames_dev || !opts) return MARS_ERR_INVALID_FILE;
+    { /* what can be said without looking at either model */
+        mhip_roi_t q;
+        const mars_error_t e = roi_opts(opts, 1, 1, &q);
+        if (e != MARS_OK) return e;
+    }
+    if (det_model == dst_model) return MARS_ERR_INVALID_TENSOR;
+    mars_model_ext_t *det = (mars_model_ext_t *)det_model, *m = (mars_model_ext_t *)dst_model;
+    if (!m->act_dev || !det->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
+    if (m->pipe || det->pipe) return MARS_ERR_INVALID_TENSOR; /* a pipe's slots own their buffers */
+    if (input_index < 0 || (uint32_t)input_index >= dst_model->header.num_inputs) return MARS_ERR_INVALID_TENSOR;
+    const uint32_t tid = dst_model->header.input_tensor_ids[input_index];
+    if (tid >= dst_model->header.num_tensors) return MARS_ERR_INVALID_TENSOR;
+    const mars_tensor_t *t = &dst_model->tensors[tid].desc;
+    const int nhwc = t->format == MARS_FORMAT_NHWC;
+    const int th = nhwc ? t->shape[1] : t->shape[2], tw = nhwc ? t->shape[2] : t->shape[3], ch = nhwc ? t->shape[3] : t->shape[1];
+    if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0 || !m->mt[tid].dev || m->mt[tid].stride < (size_t)tw * th * 3)
+        return MARS_ERR_INVALID_TENSOR;
+    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    mhip_roi_t p;
+    const mars_error_t e = roi_opts(opts, tw, th, &p);
+    if (e != MARS_OK) return e;
+    if (m->batch > 65535) return MARS_ERR_INVALID_TENSOR;
+    if (roi_table(m, m->batch, det->batch)) return MARS_ERR_ALLOC_FAILED;
+    p.frames = (const uint8_t *)frames_dev; p.n_frames = det->batch;
+    p.dets = det->det_dev; p.counts = det->det_counts_dev; p.det_cap = MARS_YOLO_MAX_DET;
+    p.n_out = (int *)m->roi_dev;
+    p.rois = (uint8_t *)m->roi_dev + 16;
+    p.frame_kept = (int *)((uint8_t *)m->roi_dev + 16 + (size_t)m->roi_cap_slots * sizeof(mars_roi_t));
+    p.out = (int8_t *)m->mt[tid].dev; p.out_stride = m->mt[tid].stride; p.slots = m->batch; p.nhwc = nhwc;
+    /* The main stream.  It carries every run of dst_model (the parts of a large batch join it again), so the crops come behind an earlier
+     * graph that still reads the input and ahead of the next one.  The detections come from the auxiliary stream: wait for the event the
+     * tail recorded there -- the one the next run's head-writing layers of det_model wait for */
+    mhip_select_stream(0);
+    if (det->ev_tail_done && mhip_stream_wait(0, det->ev_tail_done)) return MARS_ERR_LAYER_FAILED;
+    if (mhip_roi_select(&p) || mhip_roi_crop(&p)) return MARS_ERR_LAYER_FAILED;
+    m->roi_slots = m->batch;
+    return MARS_OK;
+}
+
+mars_error_t mars_hip_crop_detections(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
+                                      const mars_hip_roi_opts_t *opts) {
+    if (!det_model || !dst_model || !frames || !opts) return MARS_ERR_INVALID_FILE;
+    mhip_roi_t q;
+    mars_error_t e = roi_opts(opts, 1, 1, &q);
+    if (e != MARS_OK) return e;
+    if (det_model == dst_model) return MARS_ERR_INVALID_TENSOR;
+    if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
+    const int n = mars_hip_get_batch(det_model);
+    if (n <= 0) return MARS_ERR_INVALID_TENSOR;
+    const size_t in_b = q.frame_stride * (size_t)n;
+    uint8_t *d = (uint8_t *)mhip_malloc(in_b);
+    if (!d) return MARS_ERR_ALLOC_FAILED;
+    mhip_select_stream(0);
+    if (mhip_h2d_async(d, frames, in_b)) e = MARS_ERR_LAYER_FAILED;
+    if (e == MARS_OK) e = mars_hip_crop_detections_device(det_model, d, dst_model, input_index, opts);
+    if (mhip_sync() && e == MARS_OK) e = MARS_ERR_LAYER_FAILED;
+    mhip_free(d);
+    return e;
+}
+
+mars_error_t mars_hip_roi_results(mars_model_t *dst_model, mars_roi_t *rois, int cap, int *n_kept, int *n_dropped) {
+    if (!dst_model || cap < 0 || (cap > 0 && !rois)) return MARS_ERR_INVALID_FILE;
+    mars_model_ext_t *m = (mars_model_ext_t *)dst_model;
+    if (!m->roi_dev || m->roi_slots <= 0) return MARS_ERR_INVALID_TENSOR; /* no crop call yet */
+    int n[2] = {0, 0};
+    if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
+    if (mhip_d2h_async(n, m->roi_dev, sizeof(n)) || mhip_sync()) return MARS_ERR_LAYER_FAILED;
+    int k = n[0] < cap ? n[0] : cap;
+    if (k > m->roi_slots) k = m->roi_slots;
+    if (k > 0 && (mhip_d2h_async(rois, (uint8_t *)m->roi_dev + 16, (size_t)k * sizeof(mars_roi_t)) || mhip_sync())) return MARS_ERR_LAYER_FAILED;
+    if (n_kept) *n_kept = n[0];
+    if (n_dropped) *n_dropped = n[1];
+    return MARS_OK;
+}

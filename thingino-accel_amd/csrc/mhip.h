@@ -343,6 +343,28 @@ int mhip_nv12_to_rgb(const uint8_t *nv12, size_t nv12_stride, uint8_t *rgb, size
 int mhip_letterbox_nv12_fused(const mhip_letterbox_t *p);
 int mhip_letterbox_nv12(const mhip_letterbox_t *p, unsigned flags, uint8_t *scratch);
 
+/* ---- ROI crops (roi.hip): boxes -> source rectangles -> bilinear crops into a second model's input; include/mars_hip.h "ROI crops" states
+ * the arithmetic.  Every pointer is device memory.  Geometry travels through device memory: the select / rectangle kernels write `rois`
+ * ([slots] records of 24 bytes: frame, det, x0, y0, x1, y1) and `n_out` ([0] kept, [1] dropped), the crop kernel reads them */
+typedef struct {
+    const uint8_t *frames; size_t frame_stride; /* [n_frames] RGB [h][w][3] (fmt 0) or NV12 (fmt 1) frames */
+    int n_frames, w, h, fmt;
+    unsigned nv12_flags;                        /* MARS_NV12_* */
+    const void *dets; const int *counts; int det_cap; /* mhip_roi_select: [n_frames][det_cap] records of 24 bytes + [n_frames] list lengths */
+    const void *boxes; const int *frame_of_box; int n_boxes; /* mhip_roi_rects: the caller's boxes, box i -> slot i */
+    float expand, min_conf;                     /* resolved: expand > 0 */
+    int min_size, cls_first, cls_count, max_per_frame; /* resolved: min_size >= 1 */
+    int keep_aspect;
+    int8_t *out; size_t out_stride;             /* [slots] x (tw * th * 3) int8: [th][tw][3] (nhwc) or [3][th][tw] */
+    int slots, tw, th, nhwc;
+    void *rois; int *n_out;
+    int *frame_kept;                            /* mhip_roi_select: scratch, [n_frames] */
+} mhip_roi_t;
+int mhip_roi_select(const mhip_roi_t *p); /* the selection rules over the detection lists, frame-major, list order; two launches */
+int mhip_roi_rects(const mhip_roi_t *p);  /* the rectangle rule alone: slot i = box i (x1 == x0: skipped), n_out = {n_boxes, 0} */
+int mhip_roi_crop(const mhip_roi_t *p);   /* slots >= n_out[0], skipped slots and pad bands are filled with -17 */
+int mhip_roi_fits(int w, int tw, int fmt); /* 1: the crop kernel's LDS holds two source rows of such frames and a strip of such a target */
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,14 @@ class PipeOpts(C.Structure):
 
 CAMERA_RGB, CAMERA_NV12 = 0, 1        # MARS_HIP_CAMERA_*
 NV12_FULL_RANGE, NV12_VU = 1, 2       # MARS_NV12_*
+ROI_KEEP_ASPECT = 1                   # MARS_ROI_*
+ROI_DTYPE = np.dtype([("frame", "<i4"), ("det", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4")])  # mars_roi_t
+
+
+class RoiOpts(C.Structure):  # mars_hip_roi_opts_t: zero = default in every field but the frame size
+    _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("src_format", C.c_int), ("src_flags", C.c_uint), ("expand", C.c_float),
+                ("min_conf", C.c_float), ("min_size", C.c_int), ("cls_first", C.c_int), ("cls_count", C.c_int), ("max_per_frame", C.c_int),
+                ("flags", C.c_uint)]
 
 
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
@@ -135,7 +143,8 @@ EXPORTS = {
                    "mars_hip_get_tuning", "mars_hip_model_set_tuning", "mars_hip_model_get_tuning", "mars_yolo_find_heads",
                    "mars_hip_detect_heads", "mars_hip_detect_heads_device", "mars_hip_detect_results", "mars_yolo_find_dfl_heads",
                    "mars_hip_detect_dfl", "mars_hip_detect_dfl_device", "mars_synth_model_head", "mars_hip_nv12_frame_bytes",
-                   "mars_yolo_nv12_to_rgb", "mars_yolo_letterbox_nv12", "mars_hip_preprocess_nv12", "mars_hip_preprocess_nv12_device"],
+                   "mars_yolo_nv12_to_rgb", "mars_yolo_letterbox_nv12", "mars_hip_preprocess_nv12", "mars_hip_preprocess_nv12_device",
+                   "mars_yolo_crop_boxes", "mars_hip_crop_detections_device", "mars_hip_crop_detections", "mars_hip_roi_results"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -214,6 +223,10 @@ def lib():
     L.mars_yolo_letterbox_nv12.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p]
     L.mars_hip_preprocess_nv12.argtypes = [P(MarsModel), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
     L.mars_hip_preprocess_nv12_device.argtypes = [P(MarsModel), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
+    L.mars_yolo_crop_boxes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, P(RoiOpts), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.mars_hip_crop_detections_device.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
+    L.mars_hip_crop_detections.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
+    L.mars_hip_roi_results.argtypes = [P(MarsModel), C.c_void_p, C.c_int, P(C.c_int), P(C.c_int)]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -319,6 +332,64 @@ def letterbox_nv12(nv12, w, h, tw, th, nhwc=True, flags=0):
     if lib().mars_yolo_letterbox_nv12(a.ctypes.data, int(w), int(h), tw, th, int(bool(nhwc)), int(flags), out.ctypes.data) != 0:
         raise RuntimeError("mars_yolo_letterbox_nv12 failed")
     return out
+
+
+def roi_opts(w, h, fmt=CAMERA_RGB, src_flags=0, expand=0.0, min_conf=0.0, min_size=0, classes=None, max_per_frame=0, keep_aspect=False):
+    """mars_hip_roi_opts_t for frames of w x h.  classes = (first, count): the class window; zero means default everywhere else"""
+    o = RoiOpts(int(w), int(h), int(fmt), int(src_flags), float(expand), float(min_conf), int(min_size))
+    if classes is not None:
+        o.cls_first, o.cls_count = int(classes[0]), int(classes[1])
+    o.max_per_frame = int(max_per_frame)
+    o.flags = ROI_KEEP_ASPECT if keep_aspect else 0
+    return o
+
+
+def crop_boxes(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
+    """mars_yolo_crop_boxes: frames (uint8, [n] frames of opts.src_w x opts.src_h, RGB or NV12) and boxes (DET_DTYPE records, box i in frame
+    frame_of_box[i]) -> (int8 crops [n_boxes][tw * th * 3], ROI_DTYPE records [n_boxes]; x1 == x0: skipped, its crop is all -17), on the GPU"""
+    a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    fb = opts.src_w * opts.src_h * 3 // (2 if opts.src_format == CAMERA_NV12 else 1)
+    if fb <= 0 or a.size % fb:
+        raise ValueError("frames of %d x %d are %d bytes each, got %d" % (opts.src_w, opts.src_h, fb, a.size))
+    b = np.ascontiguousarray(boxes, dtype=DET_DTYPE).reshape(-1)
+    fo = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
+    if fo.size != b.size:
+        raise ValueError("one frame index per box")
+    out = np.zeros((b.size, tw * th * 3), dtype=np.int8)
+    rois = np.zeros(b.size, dtype=ROI_DTYPE)
+    rc = lib().mars_yolo_crop_boxes(a.ctypes.data, a.size // fb, b.ctypes.data, fo.ctypes.data, b.size, C.byref(opts), tw, th, int(bool(nhwc)),
+                                    out.ctypes.data, rois.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_crop_boxes")
+    return out, rois
+
+
+class DeviceBuffer:
+    """bytes in HBM for the *_device calls (a stand-in for a capture card that writes there): hipMalloc + a blocking copy through the HIP runtime
+    the library itself is linked against.  .ptr is the device address"""
+
+    def __init__(self, data):
+        a = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        lib()  # the runtime is loaded with the library
+        self._hip = C.CDLL("libamdhip64.so", mode=os.RTLD_GLOBAL)
+        p = C.c_void_p()
+        if self._hip.hipMalloc(C.byref(p), C.c_size_t(max(a.size, 1))) != 0:
+            raise MemoryError("hipMalloc of %d bytes" % a.size)
+        self.ptr, self.size = p.value, a.size
+        if self._hip.hipMemcpy(C.c_void_p(self.ptr), C.c_void_p(a.ctypes.data), C.c_size_t(a.size), 1) != 0:  # hipMemcpyHostToDevice
+            self.free()
+            raise RuntimeError("hipMemcpy to the device")
+
+    def free(self):
+        if self.ptr:
+            self._hip.hipFree(C.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 SYNTH_HEADS = {"anchor": 0, "dfl": 1}  # MARS_SYNTH_HEAD_*
@@ -545,6 +616,47 @@ class Model:
         rc = lib().mars_hip_preprocess_nv12(self.p, input_index, a.ctypes.data, int(w), int(h), int(flags), first_frame, n)
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_preprocess_nv12")
+
+    def preprocess_device(self, dev_ptr, w, h, frames, first_frame=0, input_index=0):
+        """mars_hip_preprocess_device: RGB frames already in device memory (DeviceBuffer.ptr); enqueues only"""
+        rc = lib().mars_hip_preprocess_device(self.p, input_index, C.c_void_p(dev_ptr), int(w), int(h), first_frame, int(frames))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_preprocess_device")
+
+    def preprocess_nv12_device(self, dev_ptr, w, h, frames, flags=0, first_frame=0, input_index=0):
+        """mars_hip_preprocess_nv12_device: NV12 frames already in device memory; enqueues only"""
+        rc = lib().mars_hip_preprocess_nv12_device(self.p, input_index, C.c_void_p(dev_ptr), int(w), int(h), int(flags), first_frame, int(frames))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_preprocess_nv12_device")
+
+    def crop_detections(self, det_model, frames, opts, input_index=0, device=False):
+        """the second stage: the detections det_model's last detect_*_device left in HBM -> crops of its frames in THIS model's input
+        `input_index`, one per frame of this model's batch.  device=False: frames = uint8 host array, uploaded, the call waits
+        (mars_hip_crop_detections); device=True: frames = a device address (DeviceBuffer.ptr), enqueues only
+        (mars_hip_crop_detections_device)"""
+        if device:
+            rc = lib().mars_hip_crop_detections_device(det_model.p, C.c_void_p(frames), self.p, input_index, C.byref(opts))
+        else:
+            a = np.ascontiguousarray(frames, dtype=np.uint8)
+            rc = lib().mars_hip_crop_detections(det_model.p, a.ctypes.data, self.p, input_index, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_crop_detections")
+
+    def roi_results(self):
+        """-> (ROI_DTYPE records of the crops the last crop_detections() wrote, frame k of the input <- rois[k]; boxes dropped for want of a frame)"""
+        rois = np.zeros(self.batch, dtype=ROI_DTYPE)
+        kept, dropped = C.c_int(0), C.c_int(0)
+        rc = lib().mars_hip_roi_results(self.p, rois.ctypes.data, self.batch, C.byref(kept), C.byref(dropped))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_roi_results")
+        return rois[:min(kept.value, self.batch)].copy(), dropped.value
+
+    def write_tensor(self, idx, data, frame=0):
+        """mars_hip_write_tensor: one frame of an activation tensor from host memory"""
+        a = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        rc = lib().mars_hip_write_tensor(self.p, idx, frame, a.ctypes.data, a.size)
+        if rc != MARS_OK:
+            raise MarsError(rc, "write_tensor %d" % idx)
 
     def set_tuning(self, key, value):
         """per-model override of a launch-policy knob (mars_hip_model_set_tuning)"""
