@@ -435,6 +435,65 @@ mars_error_t mars_hip_crop_detections(mars_model_t *det_model, const unsigned ch
  * min(kept, cap) frames (rois may be NULL with cap 0); *n_kept crops were written, *n_dropped selected boxes found no frame. */
 mars_error_t mars_hip_roi_results(mars_model_t *dst_model, mars_roi_t *rois, int cap, int *n_kept, int *n_dropped);
 
+/* ---------------------------------------------------- Second-stage labels */
+/* What a deployment wants from the second stage is a label or an embedding per box, not a feature map: tiny_160_int8.mars leaves a
+ * 64 x 154 x 154 map, 1.5 MB per crop, to read back.  The graph cannot reduce it (GLOBAL_AVGPOOL and FC fail a run with
+ * MARS_ERR_INVALID_LAYER, SOFTMAX is accepted and not executed: the reference's behaviour, kept).  The calls below are the classifier head
+ * as a tail call outside the graph, like the Detect heads: a backbone, a 1 x 1 convolution to nc channels, then -- here -- the global
+ * average pool, the ranking and the scores, on the device, defined to the bit.  The pooled sums alone are what an embedder returns.
+ *
+ * Feature tensor.  An int8 activation tensor T of the model, C channels on an H x W grid ([1, C, H, W], or [1, H, W, C] under the NHWC
+ *   tag), 1 <= C <= 4096, 1 <= H * W <= 2^24; a graph output (output_index) or any TENSOR index (tensor > 0).  It is read where the plan
+ *   left its bytes -- planes, pixel rows at the writing convolution's pitch, a channel slice of a concat's rows -- for every frame of the
+ *   current batch; no plan changes.
+ * Pooling.  sum[c] = the int32 sum of the H * W bytes of channel c.  Exact; it cannot overflow inside the limits above.
+ * Ranking.  Channels by descending sum[c], ties to the lower channel; the first top_k are kept, 1 <= top_k <= MARS_CLS_MAX_TOPK
+ *   (top_k == 0 means 1).  With C < top_k the entries behind the last channel are {cls = -1, score = 0}.
+ * Score.  float32, every operation rounded on its own, no fused multiply-add:
+ *     logit[c] = ((float)sum[c] / (float)(H * W)) * scale          scale == 0 in the options: the tensor's own desc.scale
+ *   default:           score = logit[c]
+ *   MARS_CLS_SOFTMAX:  e[c] = expf(logit[c] - logit[best]) with the host libm's expf (csrc/expf_exact.h restates it), best = the top-1 channel;
+ *                      den = e[0] + e[1] + ... + e[C - 1], added left to right;  score = e[c] / den
+ * Join.  Frame k of the second model is crop k of its ROI table (mars_hip_roi_results).  labels[roi.frame][roi.det] = the top-1 entry of
+ *   crop k for k < kept; every other entry of the [batch][MARS_YOLO_MAX_DET] array is {-1, 0}.
+ * Not covered: float32 feature tensors; pooling only the un-padded part of a MARS_ROI_KEEP_ASPECT crop; a fully-connected layer behind the
+ *   pool; matching against a gallery; the pipelined mars_hip_pipe_* path. */
+#define MARS_CLS_MAX_TOPK 8
+#define MARS_CLS_SOFTMAX 1u
+typedef struct { int cls; float score; } mars_cls_t; /* 8 bytes */
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int output_index;   /* graph output to pool ... */
+    int tensor;         /* ... or, when > 0, this TENSOR index instead */
+    int top_k;          /* 0: 1 */
+    float scale;        /* 0: the tensor's desc.scale */
+    unsigned flags;     /* MARS_CLS_SOFTMAX */
+} mars_hip_cls_opts_t;
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL pointer where one is needed, top_k
+ * outside 0 .. 8, an unknown flag bit, a negative or non-finite scale, non-positive n, c, h or w.  MARS_ERR_INVALID_TENSOR: an index out
+ * of range; a tensor that is not int8, is a weight, a graph input, only partly written or without addressable bytes (one a fusion pass
+ * elided); C or H * W beyond the limits (more than 65535 maps or frames); an effective scale <= 0; *_results with nothing pending;
+ * det_model == cls_model; no crop call into cls_model out of this det_model, no classify results on cls_model, no detections in HBM on
+ * det_model; a model with an open pipe. */
+/* The mars_yolo_crop_boxes of this feature: host pointers in and out, runs on the GPU.  maps = n dense maps, [h][w][c] (nhwc != 0) or
+ * [c][h][w]; `scale` stands where a tensor's desc.scale would; top = [n][top_k]; sums = [n][c] or NULL. */
+mars_error_t mars_yolo_classify_maps(const signed char *maps, int n, int c, int h, int w, int nhwc, float scale, const mars_hip_cls_opts_t *opts,
+                                     mars_cls_t *top, int *sums);
+/* The model's current batch; the results stay in HBM.  Enqueues only: the kernels run on the auxiliary stream behind the graph launches
+ * enqueued so far (the hand-off of mars_hip_detect_*_device); of the next mars_hip_run_device[_async] only the layers that write T wait
+ * for them. */
+mars_error_t mars_hip_classify_device(mars_model_t *model, const mars_hip_cls_opts_t *opts);
+/* Waits.  top = [batch][top_k], sums = [batch][C] or NULL, *channels = C (may be NULL), all as of the last mars_hip_classify_device. */
+mars_error_t mars_hip_classify_results(mars_model_t *model, mars_cls_t *top, int *sums, int *channels);
+/* mars_hip_classify_device + mars_hip_classify_results. */
+mars_error_t mars_hip_classify(mars_model_t *model, const mars_hip_cls_opts_t *opts, mars_cls_t *top, int *sums);
+/* Scatters cls_model's top-1 entries through its ROI table onto det_model's detection lists.  Enqueues only: ordered behind cls_model's
+ * classify tail, det_model's detection tail and the crop call, and ahead of whatever next overwrites what it reads or writes -- the next
+ * crop call into cls_model, the next classify call on it, the next detect call of det_model. */
+mars_error_t mars_hip_label_detections_device(mars_model_t *det_model, mars_model_t *cls_model);
+/* Waits.  labels = [batch of det_model][MARS_YOLO_MAX_DET]; entry i of frame f belongs to dets[f][i] of mars_hip_detect_results. */
+mars_error_t mars_hip_label_results(mars_model_t *det_model, mars_cls_t *labels);
+
 #ifdef __cplusplus
 }
 #endif

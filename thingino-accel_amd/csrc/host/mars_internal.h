@@ -175,6 +175,15 @@ typedef struct mars_model_ext {
     void *roi_dev;      /* ROI crops INTO this model (mars_roi.c): [kept, dropped, -, -][roi_cap_slots] x mars_roi_t[roi_cap_frames] x int, on the device */
     int roi_cap_slots, roi_cap_frames;
     int roi_slots;      /* slots of the last crop call (its batch then); 0 = there was none */
+    struct mars_model_ext *roi_from; /* ... whose detections they were (compared, never followed: mars_free clears it) */
+    /* second-stage labels (mars_classify.c) */
+    void *cls_dev;      /* pooled results of THIS model, one block on the device: [cls_frames][nsplit][C] partial sums, [cls_frames][C] sums, [cls_frames][top_k] entries */
+    size_t cls_bytes, cls_sums_off, cls_top_off;
+    int cls_frames, cls_c, cls_top_k; /* of the last classify call; cls_frames == 0: there was none */
+    void *ev_label_done; /* a label scatter (auxiliary stream) has read this model's ROI table and entries: the next crop call into it waits */
+    int label_pending;
+    void *label_dev;    /* labels of THIS model's detections: [label_cap][MARS_YOLO_MAX_DET] x mars_cls_t on the device */
+    int label_cap, label_frames; /* label_frames == 0: no scatter yet */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -234,6 +243,15 @@ MARS_INTERNAL int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int fr
 
 /* mars_roi.c */
 MARS_INTERNAL void mars_roi_release(mars_model_ext_t *m); /* the ROI table of a model whose device state goes away */
+
+/* mars_classify.c */
+MARS_INTERNAL void mars_cls_release(mars_model_ext_t *m); /* the pooled results and labels of a model whose device state goes away */
+
+/* mars_yolo.c, shared with mars_classify.c */
+MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);
+MARS_INTERNAL int mars_locate_i8(const mars_model_ext_t *m, int T, int ch, int hh, int ww, int any_writer, int *buf, int *off, int *pix_step, int *ch_step);
+/* a tail (launch(m, cfg, m->det_dev, m->det_counts_dev) on the current stream) on the auxiliary stream behind the graph; sets tail_pending */
+MARS_INTERNAL mars_error_t mars_tail_on_aux(mars_model_ext_t *m, int (*launch)(struct mars_model_ext *, const void *, void *, int *), const void *cfg);
 
 /* detection tail pieces shared with the pipelined I/O (mars_yolo.c) */
 mars_error_t mars_detect_prepare(mars_model_ext_t *m, const int *output_indices, int n_outputs);

@@ -93,6 +93,7 @@ static void free_device_state(mars_model_ext_t *m) {
     m->det_cap = 0;
     m->tail_pending = 0;
     mars_roi_release(m);
+    mars_cls_release(m);
 }
 
 static void free_ops(mars_model_ext_t *m) {
@@ -115,6 +116,8 @@ void mars_free(mars_model_t *model) {
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     for (mars_model_ext_t **pp = &g_live_models; *pp; pp = &(*pp)->live_next)
         if (*pp == m) { *pp = m->live_next; break; }
+    for (mars_model_ext_t *x = g_live_models; x; x = x->live_next)
+        if (x->roi_from == m) x->roi_from = NULL;
     if (m->pipe) mars_hip_pipe_close(model);
     if (mhip_ready()) mhip_sync();
     free_device_state(m);
@@ -125,6 +128,7 @@ void mars_free(mars_model_t *model) {
     if (m->dfl_lut_dev) mhip_free(m->dfl_lut_dev);
     if (m->ev_graph_done) mhip_event_destroy(m->ev_graph_done);
     if (m->ev_tail_done) mhip_event_destroy(m->ev_tail_done);
+    if (m->ev_label_done) mhip_event_destroy(m->ev_label_done);
     if (m->ev_fork) mhip_event_destroy(m->ev_fork);
     for (int k = 0; k < 3; k++)
         if (m->ev_join[k]) mhip_event_destroy(m->ev_join[k]);

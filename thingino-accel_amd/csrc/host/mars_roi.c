@@ -74,6 +74,7 @@ void mars_roi_release(mars_model_ext_t *m) {
     if (m->roi_dev) mhip_free(m->roi_dev);
     m->roi_dev = NULL;
     m->roi_cap_slots = m->roi_cap_frames = m->roi_slots = 0;
+    m->roi_from = NULL;
 }
 
 /* the table of `slots` crops out of `frames` source frames, on the destination model; only ever grown */
@@ -125,8 +126,13 @@ mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void
      * tail recorded there -- the one the next run's head-writing layers of det_model wait for */
     mhip_select_stream(0);
     if (det->ev_tail_done && mhip_stream_wait(0, det->ev_tail_done)) return MARS_ERR_LAYER_FAILED;
+    if (m->label_pending) { /* a label scatter (mars_hip_label_detections_device, auxiliary stream) still reads the table this call rewrites */
+        if (mhip_stream_wait(0, m->ev_label_done)) return MARS_ERR_LAYER_FAILED;
+        m->label_pending = 0;
+    }
     if (mhip_roi_select(&p) || mhip_roi_crop(&p)) return MARS_ERR_LAYER_FAILED;
     m->roi_slots = m->batch;
+    m->roi_from = det;
     return MARS_OK;
 }
 

@@ -210,7 +210,7 @@ static int tensor_by_id(const mars_model_ext_t *m, uint32_t id) {
 }
 
 /* channels and grid of a 4-D [1, C, H, W] / [1, H, W, C] (NHWC tag) tensor; -1 if it is not one */
-static int tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w) {
+int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w) {
     if (d->ndims != 4 || d->shape[0] != 1) return -1;
     if (d->format == MARS_FORMAT_NHWC) { *h = d->shape[1]; *w = d->shape[2]; *c = d->shape[3]; }
     else { *c = d->shape[1]; *h = d->shape[2]; *w = d->shape[3]; }
@@ -221,7 +221,7 @@ static int tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w) {
 static int input_hw(const mars_model_ext_t *m, int *h, int *w) {
     int c;
     if (m->pub.header.num_inputs < 1 || m->pub.header.input_tensor_ids[0] >= m->pub.header.num_tensors) return -1;
-    return tensor_chw(&m->pub.tensors[m->pub.header.input_tensor_ids[0]].desc, &c, h, w);
+    return mars_tensor_chw(&m->pub.tensors[m->pub.header.input_tensor_ids[0]].desc, &c, h, w);
 }
 
 int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, int *strides, int *num_classes, int cap) {
@@ -235,7 +235,7 @@ int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, int *strides, in
         if (T < 0 || m->mt[T].is_weight) continue;
         const mars_tensor_t *d = &m->pub.tensors[T].desc;
         int c, h, w;
-        if (d->dtype != MARS_DTYPE_INT8 || tensor_chw(d, &c, &h, &w) || c % 3 || c / 3 - 5 < 1) continue;
+        if (d->dtype != MARS_DTYPE_INT8 || mars_tensor_chw(d, &c, &h, &w) || c % 3 || c / 3 - 5 < 1) continue;
         if (ih % h || iw % w || ih / h != iw / w) continue;
         int read = 0; /* by a layer that does something */
         for (uint32_t lj = 0; lj < nl && !read && !m->mt[T].io_out; lj++) {
@@ -301,7 +301,7 @@ mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h,
         const mtensor_t *t = &m->mt[T];
         const mars_tensor_t *d = &m->pub.tensors[T].desc;
         int ch, hh, ww;
-        if (t->is_weight || t->partial || !t->dev || d->dtype != MARS_DTYPE_INT8 || !(d->scale > 0) || tensor_chw(d, &ch, &hh, &ww) ||
+        if (t->is_weight || t->partial || !t->dev || d->dtype != MARS_DTYPE_INT8 || !(d->scale > 0) || mars_tensor_chw(d, &ch, &hh, &ww) ||
             ch % 3 || ch / 3 - 5 < 1)
             return MARS_ERR_INVALID_TENSOR;
         /* the device layout is what the writing convolution stores: planes [C][H][W], or pixel rows at its pitch (NHWC tensors, the
@@ -388,7 +388,7 @@ static mars_error_t own_det_buffers(mars_model_ext_t *m) {
 /* as mars_hip_detect_device: a raw-head decode (launch(m, cfg, dets, counts) on the current stream) runs on the auxiliary stream behind the
  * graph, and the next run's layers that write a tensor it reads wait for it (tail_read, set by the caller) -- the heads of the shipped
  * files are internal tensors, not graph outputs */
-static mars_error_t tail_on_aux(mars_model_ext_t *m, int (*launch)(mars_model_ext_t *, const void *, void *, int *), const void *cfg) {
+mars_error_t mars_tail_on_aux(mars_model_ext_t *m, int (*launch)(mars_model_ext_t *, const void *, void *, int *), const void *cfg) {
     if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
     if (!m->ev_tail_done) m->ev_tail_done = mhip_event_create_sync();
     if (!m->ev_graph_done || !m->ev_tail_done) return MARS_ERR_ALLOC_FAILED;
@@ -416,7 +416,7 @@ mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_h
     if (e == MARS_OK) e = mars_heads_prepare(m, &c);
     if (e != MARS_OK) return e;
     for (int k = 0; k < c.n; k++) m->mt[c.ti[k]].tail_read = 1;
-    return tail_on_aux(m, heads_launch_cb, &c);
+    return mars_tail_on_aux(m, heads_launch_cb, &c);
 }
 
 mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int *counts) {
@@ -475,7 +475,7 @@ int mars_find_dfl_heads(const mars_model_ext_t *m, int *box_ids, int *cls_ids, i
             const int T = q ? B : A;
             ok = !m->mt[T].is_weight && m->pub.tensors[T].desc.dtype == MARS_DTYPE_INT8 && conv_layer_of(m, T) >= 0 && !real_readers(m, T, li);
         }
-        if (!ok || tensor_chw(&m->pub.tensors[A].desc, &ca, &ha, &wa) || tensor_chw(&m->pub.tensors[B].desc, &cb, &hb, &wb)) continue;
+        if (!ok || mars_tensor_chw(&m->pub.tensors[A].desc, &ca, &ha, &wa) || mars_tensor_chw(&m->pub.tensors[B].desc, &cb, &hb, &wb)) continue;
         if (ha != hb || wa != wb || ih % ha || iw % wa || ih / ha != iw / wa) continue;
         if (ca % 4 || ca / 4 < 2 || ca / 4 > 32) continue;
         if (!m->mt[O].io_out && real_readers(m, O, nl)) continue;
@@ -500,10 +500,12 @@ int mars_find_dfl_heads(const mars_model_ext_t *m, int *box_ids, int *cls_ids, i
     return n;
 }
 
-/* Where the plan left the int8 bytes of head tensor T ([ch] channels on an hh x ww grid): its own buffer -- planes [C][H][W], or pixel rows
- * at the writing convolution's pitch (NHWC tensors, NCHW-tagged ones held pixels x channels) -- or, where the zero-copy concat redirected
- * that convolution, a channel slice of the concat output's pixel rows.  0, or -1 if there are no such bytes. */
-static int dfl_locate(const mars_model_ext_t *m, int T, int ch, int hh, int ww, int *buf, int *off, int *pix_step, int *ch_step) {
+/* Where the plan left the int8 bytes of activation tensor T ([ch] channels on an hh x ww grid): its own buffer -- planes [C][H][W], or pixel
+ * rows at the writing convolution's pitch (NHWC tensors, NCHW-tagged ones held pixels x channels, the padded rows of graph outputs) -- or,
+ * where the zero-copy concat redirected that convolution, a channel slice of the concat output's pixel rows.  any_writer = 0: only what a
+ * convolution wrote (the Detect heads); != 0: a tensor some other launch writes (a LUT map, an Add, a pool), or a graph input, too, laid
+ * out as mars_hip_read_tensor finds it.  0, or -1 if there are no such bytes. */
+int mars_locate_i8(const mars_model_ext_t *m, int T, int ch, int hh, int ww, int any_writer, int *buf, int *off, int *pix_step, int *ch_step) {
     const mtensor_t *t = &m->mt[T];
     const mars_op_t *wr = NULL;
     if (t->is_weight || t->partial) return -1;
@@ -532,7 +534,26 @@ static int dfl_locate(const mars_model_ext_t *m, int T, int ch, int hh, int ww, 
         *ch_step = 1;
         return 0;
     }
-    return -1;
+    if (!any_writer || !t->dev || t->rec_c) return -1;
+    const size_t hw = (size_t)hh * ww;
+    *buf = T;
+    *off = 0;
+    *ch_step = 1;
+    if (t->nhwc_c) { /* pixels x channels (nhwc_internal) */
+        if (t->nhwc_c != ch || (size_t)t->nhwc_hw != hw) return -1;
+        *pix_step = t->nhwc_pitch ? t->nhwc_pitch : ch;
+    } else if (t->pix_stride) { /* padded pixel rows (pad_output_rows) */
+        if (t->pix_c != ch || t->bytes != hw * (size_t)ch) return -1;
+        *pix_step = t->pix_stride;
+    } else if (t->bytes != hw * (size_t)ch) {
+        return -1;
+    } else if (m->pub.tensors[T].desc.format == MARS_FORMAT_NHWC) {
+        *pix_step = ch;
+    } else {
+        *pix_step = 1;
+        *ch_step = hh * ww;
+    }
+    return 0;
 }
 
 mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *h, mars_dfl_cfg_t *c) {
@@ -556,14 +577,14 @@ mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *
         if (A < 0 || B < 0 || (uint32_t)A >= m->pub.header.num_tensors || (uint32_t)B >= m->pub.header.num_tensors) return MARS_ERR_INVALID_TENSOR;
         const mars_tensor_t *da = &m->pub.tensors[A].desc, *db = &m->pub.tensors[B].desc;
         int ca, ha, wa, cb, hb, wb;
-        if (da->dtype != MARS_DTYPE_INT8 || db->dtype != MARS_DTYPE_INT8 || tensor_chw(da, &ca, &ha, &wa) || tensor_chw(db, &cb, &hb, &wb) ||
+        if (da->dtype != MARS_DTYPE_INT8 || db->dtype != MARS_DTYPE_INT8 || mars_tensor_chw(da, &ca, &ha, &wa) || mars_tensor_chw(db, &cb, &hb, &wb) ||
             ha != hb || wa != wb)
             return MARS_ERR_INVALID_TENSOR;
         const int R = h->reg_max ? h->reg_max : ca / 4;
         if (ca != 4 * R || R < 2 || R > 32 || (k && R != c->reg_max)) return MARS_ERR_INVALID_TENSOR;
         c->reg_max = R;
-        if (dfl_locate(m, A, ca, ha, wa, &c->box_buf[k], &c->box_off[k], &c->box_pix_step[k], &c->box_ch_step[k]) ||
-            dfl_locate(m, B, cb, hb, wb, &c->cls_buf[k], &c->cls_off[k], &c->cls_pix_step[k], &c->cls_ch_step[k]))
+        if (mars_locate_i8(m, A, ca, ha, wa, 0, &c->box_buf[k], &c->box_off[k], &c->box_pix_step[k], &c->box_ch_step[k]) ||
+            mars_locate_i8(m, B, cb, hb, wb, 0, &c->cls_buf[k], &c->cls_off[k], &c->cls_pix_step[k], &c->cls_ch_step[k]))
             return MARS_ERR_INVALID_TENSOR;
         c->box_scale[k] = h->box_scales[k] != 0 ? h->box_scales[k] : da->scale;
         c->cls_scale[k] = h->cls_scales[k] != 0 ? h->cls_scales[k] : db->scale;
@@ -644,7 +665,7 @@ mars_error_t mars_hip_detect_dfl_device(mars_model_t *model, const mars_yolo_dfl
     if (e == MARS_OK) e = mars_dfl_prepare(m, &c);
     if (e != MARS_OK) return e;
     for (int k = 0; k < c.n; k++) m->mt[c.box_buf[k]].tail_read = m->mt[c.cls_buf[k]].tail_read = 1;
-    return tail_on_aux(m, dfl_launch_cb, &c);
+    return mars_tail_on_aux(m, dfl_launch_cb, &c);
 }
 
 mars_error_t mars_hip_detect_dfl(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, mars_det_t *dets, int *counts) {

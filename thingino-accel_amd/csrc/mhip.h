@@ -365,6 +365,27 @@ int mhip_roi_rects(const mhip_roi_t *p);  /* the rectangle rule alone: slot i = 
 int mhip_roi_crop(const mhip_roi_t *p);   /* slots >= n_out[0], skipped slots and pad bands are filled with -17 */
 int mhip_roi_fits(int w, int tw, int fmt); /* 1: the crop kernel's LDS holds two source rows of such frames and a strip of such a target */
 
+/* ---- second-stage labels (classify.hip): int8 feature maps -> per-channel int32 sums -> ranked top-K entries; include/mars_hip.h
+ * "Second-stage labels" states the arithmetic.  Every pointer is device memory. */
+#define MHIP_CLS_MAX_C 4096
+#define MHIP_CLS_MAX_TOPK 8
+typedef struct {
+    const int8_t *base; size_t frame_stride; /* frame f starts at base + f * frame_stride */
+    int frames, c, hw;
+    int pix_step, ch_step;  /* byte of (pixel p, channel ch) = p * pix_step + ch * ch_step: planes (1, hw) or pixel rows (pitch, 1) */
+    int row_room;           /* pixel rows: bytes from channel 0 to the end of its pixel row that belong to the buffer (>= c) */
+    int nsplit;             /* parts a frame's pixels are cut into (mhip_classify_split) */
+    int *partial;           /* [frames][nsplit][c]: written by the pooling launch, summed by the finishing one */
+    int *sums;              /* [frames][c] */
+    void *top;              /* [frames][top_k] records of 8 bytes {int cls, float score} */
+    int top_k, softmax;
+    float scale;
+} mhip_classify_t;
+int mhip_classify_split(const mhip_classify_t *p); /* the nsplit the launcher wants for such a tensor (>= 1; looks at the layout fields only); 0: not a layout it reads */
+int mhip_classify(const mhip_classify_t *p); /* two launches: pool into `partial`, then sum, rank and score (one wavefront per frame) */
+/* labels [det_frames][det_cap] records of 8 bytes: every entry {-1, 0}, then entry (roi.frame, roi.det) of crop k < min(n_out[0], slots) = top[k][0] */
+int mhip_label_scatter(const void *rois, const int *n_out, int slots, const void *top, int top_k, void *labels, int det_frames, int det_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,14 @@ class RoiOpts(C.Structure):  # mars_hip_roi_opts_t: zero = default in every fiel
                 ("flags", C.c_uint)]
 
 
+CLS_MAX_TOPK, CLS_SOFTMAX = 8, 1       # MARS_CLS_*
+CLS_DTYPE = np.dtype([("cls", "<i4"), ("score", "<f4")])  # mars_cls_t
+
+
+class ClsOpts(C.Structure):  # mars_hip_cls_opts_t: zero = default in every field
+    _fields_ = [("output_index", C.c_int), ("tensor", C.c_int), ("top_k", C.c_int), ("scale", C.c_float), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
 
 
@@ -144,7 +152,9 @@ EXPORTS = {
                    "mars_hip_detect_heads", "mars_hip_detect_heads_device", "mars_hip_detect_results", "mars_yolo_find_dfl_heads",
                    "mars_hip_detect_dfl", "mars_hip_detect_dfl_device", "mars_synth_model_head", "mars_hip_nv12_frame_bytes",
                    "mars_yolo_nv12_to_rgb", "mars_yolo_letterbox_nv12", "mars_hip_preprocess_nv12", "mars_hip_preprocess_nv12_device",
-                   "mars_yolo_crop_boxes", "mars_hip_crop_detections_device", "mars_hip_crop_detections", "mars_hip_roi_results"],
+                   "mars_yolo_crop_boxes", "mars_hip_crop_detections_device", "mars_hip_crop_detections", "mars_hip_roi_results",
+                   "mars_yolo_classify_maps", "mars_hip_classify_device", "mars_hip_classify_results", "mars_hip_classify",
+                   "mars_hip_label_detections_device", "mars_hip_label_results"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -227,6 +237,12 @@ def lib():
     L.mars_hip_crop_detections_device.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
     L.mars_hip_crop_detections.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
     L.mars_hip_roi_results.argtypes = [P(MarsModel), C.c_void_p, C.c_int, P(C.c_int), P(C.c_int)]
+    L.mars_yolo_classify_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P(ClsOpts), C.c_void_p, C.c_void_p]
+    L.mars_hip_classify_device.argtypes = [P(MarsModel), P(ClsOpts)]
+    L.mars_hip_classify_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int)]
+    L.mars_hip_classify.argtypes = [P(MarsModel), P(ClsOpts), C.c_void_p, C.c_void_p]
+    L.mars_hip_label_detections_device.argtypes = [P(MarsModel), P(MarsModel)]
+    L.mars_hip_label_results.argtypes = [P(MarsModel), C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -362,6 +378,29 @@ def crop_boxes(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_crop_boxes")
     return out, rois
+
+
+def cls_opts(output_index=0, tensor=0, top_k=0, scale=0.0, softmax=False):
+    """mars_hip_cls_opts_t: pool graph output `output_index`, or TENSOR index `tensor` when > 0; zero means default everywhere"""
+    return ClsOpts(int(output_index), int(tensor), int(top_k), float(scale), CLS_SOFTMAX if softmax else 0)
+
+
+def classify_maps(maps, c, h, w, nhwc=True, scale=1.0, opts=None, want_sums=True):
+    """mars_yolo_classify_maps: int8 maps, [n] dense maps of [h][w][c] (nhwc) or [c][h][w] -> (CLS_DTYPE entries [n][top_k], int32 sums
+    [n][c] or None), on the GPU"""
+    a = np.ascontiguousarray(maps).view(np.int8).reshape(-1)
+    per = int(c) * int(h) * int(w)
+    if per <= 0 or a.size % per or a.size == 0:
+        raise ValueError("maps of %d x %d x %d are %d bytes each, got %d" % (c, h, w, per, a.size))
+    o = opts if opts is not None else cls_opts()
+    n, k = a.size // per, o.top_k if 0 < o.top_k <= CLS_MAX_TOPK else 1
+    top = np.zeros((n, k), dtype=CLS_DTYPE)
+    sums = np.zeros((n, int(c)), dtype=np.int32) if want_sums else None
+    rc = lib().mars_yolo_classify_maps(a.ctypes.data, n, int(c), int(h), int(w), int(bool(nhwc)), float(scale), C.byref(o), top.ctypes.data,
+                                       sums.ctypes.data if want_sums else None)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_classify_maps")
+    return top, sums
 
 
 class DeviceBuffer:
@@ -650,6 +689,46 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_roi_results")
         return rois[:min(kept.value, self.batch)].copy(), dropped.value
+
+    def classify_device(self, opts=None, **kw):
+        """the classifier head of this model's current batch, on the device (mars_hip_classify_device): pools the feature tensor, ranks,
+        scores; enqueues only.  opts = cls_opts(...), or its keywords"""
+        o = opts if opts is not None else cls_opts(**kw)
+        rc = lib().mars_hip_classify_device(self.p, C.byref(o))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_classify_device")
+
+    def classify_results(self, top_k, want_sums=True):
+        """-> (CLS_DTYPE entries [batch][top_k], int32 sums [batch][C] or None) of the last classify_device(); top_k as given there.  Waits"""
+        n = self.batch
+        top = np.zeros((n, max(int(top_k), 1)), dtype=CLS_DTYPE)
+        sums = np.zeros((n, 4096), dtype=np.int32) if want_sums else None
+        ch = C.c_int(0)
+        rc = lib().mars_hip_classify_results(self.p, top.ctypes.data, sums.ctypes.data if want_sums else None, C.byref(ch))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_classify_results")
+        return top, (sums.reshape(-1)[:n * ch.value].reshape(n, ch.value).copy() if want_sums else None)
+
+    def classify(self, opts=None, want_sums=True, **kw):
+        """classify_device + classify_results (mars_hip_classify's work, through the two calls: the channel count is only known afterwards)"""
+        o = opts if opts is not None else cls_opts(**kw)
+        self.classify_device(o)
+        return self.classify_results(o.top_k if o.top_k else 1, want_sums)
+
+    def label_detections(self, cls_model):
+        """THIS model is the detector: cls_model's top-1 entries go through its ROI table onto this model's detection lists, on the device
+        (mars_hip_label_detections_device); enqueues only"""
+        rc = lib().mars_hip_label_detections_device(self.p, cls_model.p)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_label_detections_device")
+
+    def label_results(self):
+        """-> CLS_DTYPE [batch][MAX_DET]: entry i of frame f belongs to detect_results()[f][i]; {-1, 0} where no crop was cut.  Waits"""
+        labels = np.zeros((self.batch, MAX_DET), dtype=CLS_DTYPE)
+        rc = lib().mars_hip_label_results(self.p, labels.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_label_results")
+        return labels
 
     def write_tensor(self, idx, data, frame=0):
         """mars_hip_write_tensor: one frame of an activation tensor from host memory"""
