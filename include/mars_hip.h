@@ -457,7 +457,7 @@ mars_error_t mars_hip_roi_results(mars_model_t *dst_model, mars_roi_t *rois, int
  * Join.  Frame k of the second model is crop k of its ROI table (mars_hip_roi_results).  labels[roi.frame][roi.det] = the top-1 entry of
  *   crop k for k < kept; every other entry of the [batch][MARS_YOLO_MAX_DET] array is {-1, 0}.
  * Not covered: float32 feature tensors; pooling only the un-padded part of a MARS_ROI_KEEP_ASPECT crop; a fully-connected layer behind the
- *   pool; matching against a gallery; the pipelined mars_hip_pipe_* path. */
+ *   pool; the pipelined mars_hip_pipe_* path.  (Matching the pooled sums against a gallery: "Gallery match" below.) */
 #define MARS_CLS_MAX_TOPK 8
 #define MARS_CLS_SOFTMAX 1u
 typedef struct { int cls; float score; } mars_cls_t; /* 8 bytes */
@@ -493,6 +493,75 @@ mars_error_t mars_hip_classify(mars_model_t *model, const mars_hip_cls_opts_t *o
 mars_error_t mars_hip_label_detections_device(mars_model_t *det_model, mars_model_t *cls_model);
 /* Waits.  labels = [batch of det_model][MARS_YOLO_MAX_DET]; entry i of frame f belongs to dets[f][i] of mars_hip_detect_results. */
 mars_error_t mars_hip_label_results(mars_model_t *det_model, mars_cls_t *labels);
+
+/* ----------------------------------------------------------- Gallery match */
+/* The step behind an embedder: whose face, which plate.  A gallery holds enrolled embeddings with an id each; a query embedding -- the
+ * pooled sums mars_hip_classify_device left in HBM, or a caller's vector -- is compared with every row by cosine similarity and the best
+ * top_k rows come back as {id, score}.  The products run on the int8 matrix unit; everything is defined to the bit:
+ *
+ * Quantisation.  An embedding is C int32 values, 1 <= C <= 4096 (any int32, INT32_MIN included: magnitudes are taken in 64 bits).
+ *   Integers only: m = max_c |v[c]|.  m == 0: the vector is NULL (it has no direction).  Otherwise
+ *     q[c] = sign(v[c]) * ((|v[c]| * 127 + m / 2) / m)          64-bit product, / is floor (the numerator is not negative)
+ *   so q[c] lies in [-127, 127] and the largest magnitude maps to +-127;  qq = sum_c q[c]^2 <= 127^2 * 4096 = 66 064 384 fits an int32.
+ *   The same rule quantises gallery rows on the host and queries on the device (mars_yolo_embed_quantise states it on the host).
+ * Gallery row r.  g_r[0 .. C) int8, an id id_r >= 0 and ginv_r = 1.0f / sqrtf((float)gg_r), gg_r the row's qq, computed on the host when
+ *   the row is added.  A null vector cannot be added.
+ * Dot.  dot_r = sum_c q[c] * g_r[c], an exact int32, |dot_r| <= 66 064 384.
+ * Key and rank.  float32, every operation rounded on its own, no fused multiply-add:  key_r = (float)dot_r * ginv_r  (the conversion rounds
+ *   to nearest-even: values above 2^24 do not fit).  Rows by descending key_r, ties to the lower row index; the first top_k are kept,
+ *   1 <= top_k <= MARS_CLS_MAX_TOPK (top_k == 0 means 1).  (key, row) is a total order: the result does not depend on how the launcher
+ *   cuts the gallery into chunks.
+ * Score.  qinv = 1.0f / sqrtf((float)qq);  score_r = key_r * qinv: the cosine.  It may exceed 1 by an ulp and is not clamped.  An entry is
+ *   {cls = id_r, score} in a mars_cls_t, the row index r beside it.  Entries with score < min_score are EMPTY: {-1, 0}, row -1
+ *   (min_score == 0: no threshold, negative scores are entries too).  With fewer than top_k rows in the gallery the entries behind the
+ *   last row are empty; for a null query all entries are empty.
+ * Join.  As the label join: idents[roi.frame][roi.det] = the top-1 entry of crop k for k < kept; every other entry is {-1, 0}.
+ * Not covered: enrolling rows straight from device results (enrol via mars_hip_classify_results -> mars_hip_gallery_add); centring or
+ *   whitening of embeddings; de-duplicating ids inside a top-K (several rows may share an id); removing single rows; float32 embeddings;
+ *   the pipelined mars_hip_pipe_* path; tracking across frames. */
+typedef struct mars_hip_gallery mars_hip_gallery_t; /* opaque */
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int top_k;          /* 0: 1 */
+    float min_score;    /* 0: no threshold */
+    unsigned flags;     /* none yet: must be 0 */
+} mars_hip_match_opts_t;
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL pointer where one is needed, a
+ * non-positive channels, capacity or n, a negative id, top_k outside 0 .. 8, a negative or non-finite min_score, any flag bit.
+ * MARS_ERR_INVALID_TENSOR: channels above 4096, a capacity above 2^24, more rows than the capacity holds, a null vector given to
+ * mars_hip_gallery_add, more than 65535 queries, an empty gallery, a gallery whose channels differ from the classify results' C, no
+ * classify / match results pending, det_model == cls_model, no crop call into cls_model out of this det_model, no detections in HBM, a
+ * model with an open pipe. */
+/* The rule on the host, no device needed: vectors = [n][c] int32 -> q = [n][c] int8, qq = [n] (may be NULL; 0 marks a null vector). */
+mars_error_t mars_yolo_embed_quantise(const int *vectors, int n, int c, signed char *q, int *qq);
+/* A gallery of up to `capacity` rows (1 .. 2^24) of `channels` values.  Its device image: int8 rows padded with zeros to a multiple of 64
+ * channels, the ginv array and the id array. */
+mars_error_t mars_hip_gallery_create(int channels, int capacity, mars_hip_gallery_t **out);
+/* Quantises n vectors ([n][channels] int32) on the host and appends them with their ids (all or none).  Ordered behind every match enqueued
+ * so far: it waits for the device. */
+mars_error_t mars_hip_gallery_add(mars_hip_gallery_t *g, const int *vectors, const int *ids, int n);
+int mars_hip_gallery_count(const mars_hip_gallery_t *g);      /* rows held; -1 without a gallery */
+mars_error_t mars_hip_gallery_clear(mars_hip_gallery_t *g);   /* forgets every row; the capacity stays */
+void mars_hip_gallery_free(mars_hip_gallery_t *g);            /* waits for the device first */
+/* Gallery rows one workgroup of the match kernel walks for a gallery of `rows` rows (a function of `rows` alone): for tests that want row
+ * counts around the cut.  0: rows out of range. */
+int mars_hip_match_chunk(int rows);
+/* The mars_yolo_classify_maps of this feature: host pointers in and out, runs on the GPU and waits.  vectors = [n][channels] int32;
+ * top = [n][top_k]; rows = [n][top_k] row indices or NULL. */
+mars_error_t mars_yolo_match_vectors(mars_hip_gallery_t *g, const int *vectors, int n, const mars_hip_match_opts_t *opts, mars_cls_t *top, int *rows);
+/* Matches the [frames][C] sums the last mars_hip_classify_device of cls_model left in HBM; the results stay there.  Enqueues only, on the
+ * auxiliary stream behind that classify tail and ahead of the next one. */
+mars_error_t mars_hip_match_device(mars_model_t *cls_model, mars_hip_gallery_t *g, const mars_hip_match_opts_t *opts);
+/* Waits.  top = [batch][top_k], rows = [batch][top_k] or NULL, as of the last mars_hip_match_device. */
+mars_error_t mars_hip_match_results(mars_model_t *cls_model, mars_cls_t *top, int *rows);
+/* mars_hip_match_device + mars_hip_match_results. */
+mars_error_t mars_hip_match(mars_model_t *cls_model, mars_hip_gallery_t *g, const mars_hip_match_opts_t *opts, mars_cls_t *top, int *rows);
+/* mars_hip_label_detections_device / mars_hip_label_results with cls_model's top-1 MATCH entries, into an array of their own: labels and
+ * identities coexist.  Enqueues only, with the label scatter's ordering: behind cls_model's match, det_model's detection tail and the crop
+ * call, ahead of the next crop call into cls_model, the next classify or match call on it and the next detect call of det_model. */
+mars_error_t mars_hip_identify_detections_device(mars_model_t *det_model, mars_model_t *cls_model);
+/* Waits.  idents = [batch of det_model][MARS_YOLO_MAX_DET]; entry i of frame f belongs to dets[f][i] of mars_hip_detect_results. */
+mars_error_t mars_hip_identity_results(mars_model_t *det_model, mars_cls_t *idents);
 
 #ifdef __cplusplus
 }

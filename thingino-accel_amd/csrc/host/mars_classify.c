@@ -72,6 +72,7 @@ void mars_cls_release(mars_model_ext_t *m) {
     m->cls_dev = m->label_dev = NULL;
     m->cls_bytes = 0;
     m->cls_frames = m->cls_c = m->cls_top_k = m->label_cap = m->label_frames = m->label_pending = 0;
+    mars_match_release(m);
 }
 
 static int cls_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, int *counts_dev) {

@@ -184,6 +184,12 @@ typedef struct mars_model_ext {
     int label_pending;
     void *label_dev;    /* labels of THIS model's detections: [label_cap][MARS_YOLO_MAX_DET] x mars_cls_t on the device */
     int label_cap, label_frames; /* label_frames == 0: no scatter yet */
+    /* gallery match (mars_gallery.c) */
+    void *match_dev;    /* match results of THIS model, one block on the device: quantised queries, qq, qinv, the chunks' lists, [match_frames][top_k] entries, their rows */
+    size_t match_bytes, match_top_off, match_row_off;
+    int match_frames, match_top_k; /* of the last match call; match_frames == 0: there was none */
+    void *ident_dev;    /* identities of THIS model's detections: [ident_cap][MARS_YOLO_MAX_DET] x mars_cls_t on the device */
+    int ident_cap, ident_frames; /* ident_frames == 0: no scatter yet */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -246,6 +252,9 @@ MARS_INTERNAL void mars_roi_release(mars_model_ext_t *m); /* the ROI table of a 
 
 /* mars_classify.c */
 MARS_INTERNAL void mars_cls_release(mars_model_ext_t *m); /* the pooled results and labels of a model whose device state goes away */
+
+/* mars_gallery.c */
+MARS_INTERNAL void mars_match_release(mars_model_ext_t *m); /* the match results and identities of a model whose device state goes away (mars_cls_release calls it) */
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

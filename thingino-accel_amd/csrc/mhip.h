@@ -386,6 +386,29 @@ int mhip_classify(const mhip_classify_t *p); /* two launches: pool into `partial
 /* labels [det_frames][det_cap] records of 8 bytes: every entry {-1, 0}, then entry (roi.frame, roi.det) of crop k < min(n_out[0], slots) = top[k][0] */
 int mhip_label_scatter(const void *rois, const int *n_out, int slots, const void *top, int top_k, void *labels, int det_frames, int det_cap);
 
+/* ---- gallery match (gallery.hip): int32 embeddings -> int8 rows (the exact rule of include/mars_hip.h, "Gallery match") -> int8 MFMA dot
+ * products against the gallery's rows -> ranked (key, row) lists -> {id, score} entries.  Every pointer is device memory. */
+#define MHIP_MATCH_MAX_C 4096
+#define MHIP_MATCH_KEEP 8           /* entries of a partial list: MHIP_CLS_MAX_TOPK, whatever top_k asks for */
+#define MHIP_MATCH_MAX_ROWS (1 << 24)
+typedef struct {
+    const int *vec;         /* [queries][c] int32 embeddings */
+    int queries, c, cp;     /* cp = c rounded up to a multiple of 64: the pitch of every int8 row */
+    int8_t *q;              /* [queries rounded up to 64][cp]: the quantised queries, pad channels and pad rows zero */
+    int *qq; float *qinv;   /* [queries]; qq == 0: a null query */
+    const int8_t *rows; const float *ginv; const int *ids; /* the gallery: [rows][cp], [rows], [rows]; rows and ginv are READ up to n_rows
+                                                            * rounded up to 16: the arrays are that long (mars_gallery.c allocates multiples of 64) */
+    int n_rows, chunk;      /* chunk = mhip_match_chunk(n_rows) */
+    unsigned long long *part; /* [queries][chunks][MHIP_MATCH_KEEP] rank words (gallery.hip: gm_ord), chunks = ceil(n_rows / chunk): written by
+                               * the match launch, read by the merge */
+    void *top; int *top_row; /* [queries][top_k] records of 8 bytes {int id, float score}, and the row index of each (-1: empty) */
+    int top_k;
+    float min_score;        /* 0: no threshold */
+} mhip_match_t;
+int mhip_match_chunk(int n_rows); /* gallery rows per workgroup the launcher wants for such a gallery (a multiple of 64; a function of n_rows alone); 0: n_rows out of range */
+int mhip_match(const mhip_match_t *p); /* three launches: quantise, match (one partial list per query and chunk), merge */
+/* (the identity scatter is mhip_label_scatter of classify.hip with another source and destination) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,10 @@ class ClsOpts(C.Structure):  # mars_hip_cls_opts_t: zero = default in every fiel
     _fields_ = [("output_index", C.c_int), ("tensor", C.c_int), ("top_k", C.c_int), ("scale", C.c_float), ("flags", C.c_uint)]
 
 
+class MatchOpts(C.Structure):  # mars_hip_match_opts_t: zero = default in every field
+    _fields_ = [("top_k", C.c_int), ("min_score", C.c_float), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
 
 
@@ -154,7 +158,11 @@ EXPORTS = {
                    "mars_yolo_nv12_to_rgb", "mars_yolo_letterbox_nv12", "mars_hip_preprocess_nv12", "mars_hip_preprocess_nv12_device",
                    "mars_yolo_crop_boxes", "mars_hip_crop_detections_device", "mars_hip_crop_detections", "mars_hip_roi_results",
                    "mars_yolo_classify_maps", "mars_hip_classify_device", "mars_hip_classify_results", "mars_hip_classify",
-                   "mars_hip_label_detections_device", "mars_hip_label_results"],
+                   "mars_hip_label_detections_device", "mars_hip_label_results",
+                   "mars_yolo_embed_quantise", "mars_hip_gallery_create", "mars_hip_gallery_add", "mars_hip_gallery_count",
+                   "mars_hip_gallery_clear", "mars_hip_gallery_free", "mars_hip_match_chunk", "mars_yolo_match_vectors",
+                   "mars_hip_match_device", "mars_hip_match_results", "mars_hip_match", "mars_hip_identify_detections_device",
+                   "mars_hip_identity_results"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -243,6 +251,20 @@ def lib():
     L.mars_hip_classify.argtypes = [P(MarsModel), P(ClsOpts), C.c_void_p, C.c_void_p]
     L.mars_hip_label_detections_device.argtypes = [P(MarsModel), P(MarsModel)]
     L.mars_hip_label_results.argtypes = [P(MarsModel), C.c_void_p]
+    L.mars_yolo_embed_quantise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.mars_hip_gallery_create.argtypes = [C.c_int, C.c_int, P(C.c_void_p)]
+    L.mars_hip_gallery_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mars_hip_gallery_count.argtypes = [C.c_void_p]
+    L.mars_hip_gallery_clear.argtypes = [C.c_void_p]
+    L.mars_hip_gallery_free.argtypes = [C.c_void_p]
+    L.mars_hip_gallery_free.restype = None
+    L.mars_hip_match_chunk.argtypes = [C.c_int]
+    L.mars_yolo_match_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, P(MatchOpts), C.c_void_p, C.c_void_p]
+    L.mars_hip_match_device.argtypes = [P(MarsModel), C.c_void_p, P(MatchOpts)]
+    L.mars_hip_match_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p]
+    L.mars_hip_match.argtypes = [P(MarsModel), C.c_void_p, P(MatchOpts), C.c_void_p, C.c_void_p]
+    L.mars_hip_identify_detections_device.argtypes = [P(MarsModel), P(MarsModel)]
+    L.mars_hip_identity_results.argtypes = [P(MarsModel), C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -401,6 +423,82 @@ def classify_maps(maps, c, h, w, nhwc=True, scale=1.0, opts=None, want_sums=True
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_classify_maps")
     return top, sums
+
+
+def embed_quantise(vectors, c):
+    """mars_yolo_embed_quantise: int32 embeddings [n][c] -> (int8 q [n][c], int32 qq [n]; qq == 0 marks a null vector).  Host only"""
+    v = np.ascontiguousarray(vectors, dtype=np.int32).reshape(-1)
+    if int(c) <= 0 or v.size == 0 or v.size % int(c):
+        raise ValueError("embeddings of %d values, got %d values" % (c, v.size))
+    n = v.size // int(c)
+    q = np.zeros((n, int(c)), dtype=np.int8)
+    qq = np.zeros(n, dtype=np.int32)
+    rc = lib().mars_yolo_embed_quantise(v.ctypes.data, n, int(c), q.ctypes.data, qq.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_embed_quantise")
+    return q, qq
+
+
+def match_opts(top_k=0, min_score=0.0):
+    """mars_hip_match_opts_t; zero means default everywhere (top_k 1, no threshold)"""
+    return MatchOpts(int(top_k), float(min_score), 0)
+
+
+def match_chunk(rows):
+    """mars_hip_match_chunk: gallery rows per workgroup of the match kernel for a gallery of `rows` rows"""
+    return int(lib().mars_hip_match_chunk(int(rows)))
+
+
+class Gallery:
+    """mars_hip_gallery_t: enrolled embeddings of `channels` int32 values with an id each, quantised on the host, held on the device"""
+
+    def __init__(self, channels, capacity):
+        self.channels = int(channels)
+        self.p = C.c_void_p()
+        rc = lib().mars_hip_gallery_create(self.channels, int(capacity), C.byref(self.p))
+        if rc != MARS_OK:
+            self.p = C.c_void_p()
+            raise MarsError(rc, "mars_hip_gallery_create")
+
+    def add(self, vectors, ids):
+        """int32 vectors [n][channels] with ids [n] (>= 0): all are appended or none"""
+        v = np.ascontiguousarray(vectors, dtype=np.int32).reshape(-1)
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if i.size == 0 or v.size != i.size * self.channels:
+            raise ValueError("%d ids need %d values, got %d" % (i.size, i.size * self.channels, v.size))
+        rc = lib().mars_hip_gallery_add(self.p, v.ctypes.data, i.ctypes.data, int(i.size))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_gallery_add")
+
+    def count(self):
+        return int(lib().mars_hip_gallery_count(self.p))
+
+    def clear(self):
+        rc = lib().mars_hip_gallery_clear(self.p)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_gallery_clear")
+
+    def close(self):
+        if self.p:
+            lib().mars_hip_gallery_free(self.p)
+            self.p = C.c_void_p()
+
+
+def match_vectors(gallery, vectors, opts=None, want_rows=True):
+    """mars_yolo_match_vectors: int32 embeddings [n][channels] against the gallery -> (CLS_DTYPE entries [n][top_k] with cls = id, int32 row
+    indices [n][top_k] or None), on the GPU"""
+    v = np.ascontiguousarray(vectors, dtype=np.int32).reshape(-1)
+    c = gallery.channels
+    if v.size == 0 or v.size % c:
+        raise ValueError("embeddings of %d values, got %d values" % (c, v.size))
+    o = opts if opts is not None else match_opts()
+    n, k = v.size // c, o.top_k if 0 < o.top_k <= CLS_MAX_TOPK else 1
+    top = np.zeros((n, k), dtype=CLS_DTYPE)
+    rows = np.zeros((n, k), dtype=np.int32) if want_rows else None
+    rc = lib().mars_yolo_match_vectors(gallery.p, v.ctypes.data, n, C.byref(o), top.ctypes.data, rows.ctypes.data if want_rows else None)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_match_vectors")
+    return top, rows
 
 
 class DeviceBuffer:
@@ -699,7 +797,8 @@ class Model:
             raise MarsError(rc, "mars_hip_classify_device")
 
     def classify_results(self, top_k, want_sums=True):
-        """-> (CLS_DTYPE entries [batch][top_k], int32 sums [batch][C] or None) of the last classify_device(); top_k as given there.  Waits"""
+        """-> (CLS_DTYPE entries [batch][top_k], int32 sums [batch][C] or None) of the last classify_device().  top_k MUST be the one
+        given there: the library copies batch x that many entries, and a smaller top_k here makes the array too short for them.  Waits"""
         n = self.batch
         top = np.zeros((n, max(int(top_k), 1)), dtype=CLS_DTYPE)
         sums = np.zeros((n, 4096), dtype=np.int32) if want_sums else None
@@ -729,6 +828,59 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_label_results")
         return labels
+
+    def match_device(self, gallery, opts=None, **kw):
+        """the pooled sums of the last classify_device() against the gallery, on the device (mars_hip_match_device); enqueues only.
+        opts = match_opts(...), or its keywords"""
+        o = opts if opts is not None else match_opts(**kw)
+        rc = lib().mars_hip_match_device(self.p, gallery.p, C.byref(o))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_match_device")
+        self._match_top_k = o.top_k if o.top_k else 1
+
+    def match_results(self, top_k=None, want_rows=True):
+        """-> (CLS_DTYPE entries [batch][top_k] with cls = id, int32 rows [batch][top_k] or None) of the last match_device().  The arrays
+        are sized by the top_k that call enqueued (the library copies that many entries per frame); a top_k given here must equal it.
+        Waits"""
+        k = getattr(self, "_match_top_k", 0)
+        if not k:  # no match call yet: the library refuses below
+            k = max(int(top_k or 1), 1)
+        elif top_k is not None and max(int(top_k), 1) != k:
+            raise ValueError("match_results(top_k=%d) after match_device(top_k=%d)" % (top_k, k))
+        top = np.zeros((self.batch, k), dtype=CLS_DTYPE)
+        rows = np.zeros((self.batch, k), dtype=np.int32) if want_rows else None
+        rc = lib().mars_hip_match_results(self.p, top.ctypes.data, rows.ctypes.data if want_rows else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_match_results")
+        return top, rows
+
+    def match(self, gallery, opts=None, want_rows=True, **kw):
+        """match_device + match_results (mars_hip_match)"""
+        o = opts if opts is not None else match_opts(**kw)
+        k = o.top_k if o.top_k else 1
+        top = np.zeros((self.batch, max(k, 1)), dtype=CLS_DTYPE)
+        rows = np.zeros((self.batch, max(k, 1)), dtype=np.int32) if want_rows else None
+        rc = lib().mars_hip_match(self.p, gallery.p, C.byref(o), top.ctypes.data, rows.ctypes.data if want_rows else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_match")
+        self._match_top_k = k
+        return top, rows
+
+    def identify_detections(self, cls_model):
+        """THIS model is the detector: cls_model's top-1 match entries go through its ROI table onto this model's detection lists, on the
+        device (mars_hip_identify_detections_device), into an array beside the labels; enqueues only"""
+        rc = lib().mars_hip_identify_detections_device(self.p, cls_model.p)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_identify_detections_device")
+
+    def identity_results(self):
+        """-> CLS_DTYPE [batch][MAX_DET] with cls = id: entry i of frame f belongs to detect_results()[f][i]; {-1, 0} where no crop was cut
+        or nothing matched.  Waits"""
+        idents = np.zeros((self.batch, MAX_DET), dtype=CLS_DTYPE)
+        rc = lib().mars_hip_identity_results(self.p, idents.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_identity_results")
+        return idents
 
     def write_tensor(self, idx, data, frame=0):
         """mars_hip_write_tensor: one frame of an activation tensor from host memory"""
