@@ -518,7 +518,7 @@ mars_error_t mars_hip_label_results(mars_model_t *det_model, mars_cls_t *labels)
  * Join.  As the label join: idents[roi.frame][roi.det] = the top-1 entry of crop k for k < kept; every other entry is {-1, 0}.
  * Not covered: enrolling rows straight from device results (enrol via mars_hip_classify_results -> mars_hip_gallery_add); centring or
  *   whitening of embeddings; de-duplicating ids inside a top-K (several rows may share an id); removing single rows; float32 embeddings;
- *   the pipelined mars_hip_pipe_* path; tracking across frames. */
+ *   the pipelined mars_hip_pipe_* path.  (Tracking across frames: "Tracking" below.) */
 typedef struct mars_hip_gallery mars_hip_gallery_t; /* opaque */
 /* Zero-initialise; zero means default in every field. */
 typedef struct {
@@ -562,6 +562,84 @@ mars_error_t mars_hip_match(mars_model_t *cls_model, mars_hip_gallery_t *g, cons
 mars_error_t mars_hip_identify_detections_device(mars_model_t *det_model, mars_model_t *cls_model);
 /* Waits.  idents = [batch of det_model][MARS_YOLO_MAX_DET]; entry i of frame f belongs to dets[f][i] of mars_hip_detect_results. */
 mars_error_t mars_hip_identity_results(mars_model_t *det_model, mars_cls_t *idents);
+
+/* ---------------------------------------------------------------- Tracking */
+/* The step that connects frame t to frame t + 1.  A tracker holds the track tables of S camera streams in HBM, MARS_TRACK_SLOTS slots each.
+ * A tail call associates every frame's detections with its stream's tracks and hangs a stable track id on each detection; optionally the
+ * track also carries the best identity seen on it so far.  All arithmetic is float32, every operation rounded on its own, no fused
+ * multiply-add; everything is defined to the bit:
+ *
+ * Frames -> streams.  A call over F frames and a tracker of S streams needs F % S == 0.  Default: frame f is stream f % S, step f / S.
+ *   MARS_TRACK_STREAM_MAJOR: stream f / (F / S), step f % (F / S).  A stream's steps are processed in ascending order; streams are
+ *   independent.  State persists between calls: one call over 2 T steps leaves exactly the state and outputs of two calls over T steps each.
+ * Candidates of a frame with list d[0 .. n).  d[i] is VALID when all five float fields are finite, w > 0, h > 0, and cls_count == 0 or
+ *   cls_first <= cls < cls_first + cls_count.  H = the valid detections with conf >= min_conf.  L exists only when low_conf > 0: the valid
+ *   detections with low_conf <= conf < min_conf.  The first MARS_TRACK_MAX_CAND members of each set, by index, take part (in the matching and,
+ *   for H, in the births); the rest add to the `overflow` counter.
+ * Predict.  For every live track: px = x + vx, py = y + vy.
+ * IoU(track, det).  The expression of the NMS kernel, a = (px, py, w, h) of the track, b = the detection: corners c -+ s / 2;
+ *   x1 = fmaxf(ax1, bx1), y1 alike, x2 = fminf(ax2, bx2), y2 alike;  iw = fmaxf(0, x2 - x1), ih alike;  inter = iw * ih;
+ *   uni = ((wa * ha + wb * hb) - inter) + 1e-6f;  iou = inter / uni.
+ * Association.  A pair (slot s, detection i) is ELIGIBLE when the classes are equal or MARS_TRACK_ANY_CLASS is set, and iou >= thresh (a
+ *   NaN fails the comparison: never eligible).  Eligible pairs are visited by (iou descending, slot ascending, detection index ascending);
+ *   a pair is taken when both its track and its detection are still free: greedy matching on a strict total order.  Pass 1: all live
+ *   tracks, the set H, iou_thresh.  Pass 2, only with low_conf > 0: the tracks pass 1 left unmatched, the set L, iou_thresh_low.
+ * Update, in this order.
+ *   Matched slot, with detection i:  dx = d.x - x, dy = d.y - y (x, y: the stored state, not the prediction);
+ *     vx = hits == 1 ? dx : (vx + dx) * 0.5f, vy alike;  x, y, w, h, cls = the detection's;  hits += 1, miss = 0.  With
+ *     MARS_TRACK_CARRY_IDENTITY: if idents[f][i].cls >= 0 and (ident.cls < 0 or idents[f][i].score >= ident.score) then ident = idents[f][i].
+ *   Unmatched live slot:  x = px, y = py, miss += 1;  freed when miss > max_miss, and `deaths` grows by one.
+ *   Births, after the deaths.  Each member of H that no pair took, by ascending index, is born into the lowest free slot (slots freed in
+ *     this step count as free):  id = next_id++ (per stream, starts at 1, an int32), the state from the detection, vx = vy = 0, hits = 1,
+ *     miss = 0, ident = that detection's entry under MARS_TRACK_CARRY_IDENTITY and {-1, 0} otherwise;  `births` grows by one.  With no
+ *     free slot `dropped` grows by one (and no id is used).
+ *   Output.  out[f][i] = {id, hits}, the values after the update, for every matched or born detection; every other entry up to the array's
+ *     width is {-1, 0}.
+ * Not covered: the pipelined mars_hip_pipe_* path; optimal (Hungarian) assignment; Kalman covariance (the motion model is the velocity
+ *   average above); an appearance cost in the association (the identity rides on the track, it does not steer it); more than
+ *   MARS_TRACK_SLOTS tracks per stream. */
+#define MARS_TRACK_SLOTS 256          /* tracks per stream */
+#define MARS_TRACK_MAX_CAND 256       /* candidates per frame and pass */
+typedef struct { int id, hits; } mars_track_t;                       /* 8 bytes; {-1, 0}: no track */
+typedef struct { int id, cls, hits, miss; float x, y, w, h, vx, vy; mars_cls_t ident; } mars_track_state_t; /* 48 bytes */
+#define MARS_TRACK_ANY_CLASS 1u
+#define MARS_TRACK_CARRY_IDENTITY 2u
+#define MARS_TRACK_STREAM_MAJOR 4u
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    float min_conf;        /* 0: 0.5  (high set) */
+    float low_conf;        /* 0: no second pass */
+    float iou_thresh;      /* 0: 0.3  (pass 1) */
+    float iou_thresh_low;  /* 0: 0.5  (pass 2) */
+    int max_miss;          /* 0: 30 */
+    int cls_first, cls_count;
+    unsigned flags;
+} mars_hip_track_opts_t;
+typedef struct mars_hip_tracker mars_hip_tracker_t; /* opaque */
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL pointer where one is needed (idents
+ * under MARS_TRACK_CARRY_IDENTITY among them), non-positive streams, frames or max_det, a negative cap, a negative or non-finite option, a
+ * threshold (min_conf, low_conf, iou_thresh, iou_thresh_low) above 1, low_conf >= the effective min_conf, an unknown flag bit.
+ * MARS_ERR_INVALID_TENSOR: streams above 65535, max_det above MARS_YOLO_MAX_DET, F % S != 0, a stream index out of range, no detections in
+ * HBM, MARS_TRACK_CARRY_IDENTITY without identity results on det_model, *_results with nothing pending, a model with an open pipe. */
+mars_error_t mars_hip_tracker_create(int streams, mars_hip_tracker_t **out);      /* 1 .. 65535 */
+mars_error_t mars_hip_tracker_reset(mars_hip_tracker_t *t);                       /* all tables empty, next id 1, counters 0; waits */
+void         mars_hip_tracker_free(mars_hip_tracker_t *t);                        /* waits for the device first */
+/* Waits.  The live tracks of one stream by ascending slot into states[0 .. cap) (states may be NULL with cap 0); *n_live = their number,
+ * also where it exceeds cap; counters = births, deaths, overflow, dropped of that stream since the last reset.  n_live and counters may be NULL. */
+mars_error_t mars_hip_tracker_read(mars_hip_tracker_t *t, int stream, mars_track_state_t *states, int cap, int *n_live, long long counters[4]);
+/* The mars_yolo_match_vectors of this feature: host pointers in and out, runs the same kernel on the GPU and waits.  dets and out are
+ * [frames][max_det], 1 <= max_det <= MARS_YOLO_MAX_DET; counts = [frames] (clamped to 0 .. max_det); idents = NULL or [frames][max_det]. */
+mars_error_t mars_yolo_track_lists(mars_hip_tracker_t *t, const mars_det_t *dets, const int *counts, const mars_cls_t *idents,
+                                   int frames, int max_det, const mars_hip_track_opts_t *opts, mars_track_t *out);
+/* Tracks the detections the last mars_hip_detect_*_device call of det_model left in HBM (F = its batch) and, with
+ * MARS_TRACK_CARRY_IDENTITY, reads the array mars_hip_identify_detections_device left.  Enqueues only, on the auxiliary stream with the label
+ * scatter's ordering: behind the detection tail and the identity scatter, ahead of det_model's next detect call.  The result array lives on
+ * det_model beside the labels and identities and is freed with the model. */
+mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts);
+/* Waits.  tracks = [batch of det_model][MARS_YOLO_MAX_DET]; entry i of frame f belongs to dets[f][i] of mars_hip_detect_results. */
+mars_error_t mars_hip_track_results(mars_model_t *det_model, mars_track_t *tracks);
+/* mars_hip_track_device + mars_hip_track_results. */
+mars_error_t mars_hip_track(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts, mars_track_t *tracks);
 
 #ifdef __cplusplus
 }

@@ -190,6 +190,9 @@ typedef struct mars_model_ext {
     int match_frames, match_top_k; /* of the last match call; match_frames == 0: there was none */
     void *ident_dev;    /* identities of THIS model's detections: [ident_cap][MARS_YOLO_MAX_DET] x mars_cls_t on the device */
     int ident_cap, ident_frames; /* ident_frames == 0: no scatter yet */
+    /* tracking (mars_track.c) */
+    void *track_dev;    /* track ids of THIS model's detections: [track_cap][MARS_YOLO_MAX_DET] x mars_track_t on the device */
+    int track_cap, track_frames; /* track_frames == 0: no track call yet */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -255,6 +258,9 @@ MARS_INTERNAL void mars_cls_release(mars_model_ext_t *m); /* the pooled results 
 
 /* mars_gallery.c */
 MARS_INTERNAL void mars_match_release(mars_model_ext_t *m); /* the match results and identities of a model whose device state goes away (mars_cls_release calls it) */
+
+/* mars_track.c */
+MARS_INTERNAL void mars_track_release(mars_model_ext_t *m); /* the track results of a model whose device state goes away */
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

@@ -94,6 +94,7 @@ static void free_device_state(mars_model_ext_t *m) {
     m->tail_pending = 0;
     mars_roi_release(m);
     mars_cls_release(m);
+    mars_track_release(m);
 }
 
 static void free_ops(mars_model_ext_t *m) {

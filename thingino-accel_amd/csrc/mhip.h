@@ -409,6 +409,27 @@ int mhip_match_chunk(int n_rows); /* gallery rows per workgroup the launcher wan
 int mhip_match(const mhip_match_t *p); /* three launches: quantise, match (one partial list per query and chunk), merge */
 /* (the identity scatter is mhip_label_scatter of classify.hip with another source and destination) */
 
+/* ---- tracking (track.hip): detection lists of `frames` frames -> a track id per detection, by the exact rule of include/mars_hip.h
+ * ("Tracking").  One workgroup per stream walks that stream's `steps` frames in order with the stream's table on chip.  Every pointer is
+ * device memory. */
+#define MHIP_TRACK_SLOTS 256
+#define MHIP_TRACK_CAND 256
+typedef struct { long long counters[4]; int next_id, pad; } mhip_track_hdr_t; /* births, deaths, overflow, dropped; the id the next birth gets - 1 */
+typedef struct {
+    int streams, steps;     /* frames = streams * steps */
+    int max_det;            /* row length of dets, idents and out: 1 .. 1000 */
+    int stream_major;       /* frame of (stream b, step t): b * steps + t; otherwise t * streams + b */
+    const void *dets;       /* [frames][max_det] records of 24 bytes {float x, y, w, h, conf; int cls} */
+    const int *counts;      /* [frames]; clamped to 0 .. max_det */
+    const void *idents;     /* [frames][max_det] records of 8 bytes {int cls, float score}, or NULL: no identity is carried */
+    void *out;              /* [frames][max_det] records of 8 bytes {int id, hits} */
+    void *states;           /* [streams][MHIP_TRACK_SLOTS] records of 48 bytes (mars_track_state_t); hits == 0: a free slot */
+    mhip_track_hdr_t *hdr;  /* [streams] */
+    float min_conf, low_conf, iou, iou_low; /* resolved: low_conf == 0 means no second pass, the others are never 0 */
+    int max_miss, cls_first, cls_count, any_class;
+} mhip_track_t;
+int mhip_track(const mhip_track_t *p); /* one launch */
+
 #ifdef __cplusplus
 }
 #endif

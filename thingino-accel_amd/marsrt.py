@@ -121,7 +121,33 @@ class MatchOpts(C.Structure):  # mars_hip_match_opts_t: zero = default in every 
     _fields_ = [("top_k", C.c_int), ("min_score", C.c_float), ("flags", C.c_uint)]
 
 
+TRACK_SLOTS, TRACK_MAX_CAND = 256, 256                                   # MARS_TRACK_*
+TRACK_ANY_CLASS, TRACK_CARRY_IDENTITY, TRACK_STREAM_MAJOR = 1, 2, 4
+TRACK_DTYPE = np.dtype([("id", "<i4"), ("hits", "<i4")])                 # mars_track_t
+TRACK_STATE_DTYPE = np.dtype([("id", "<i4"), ("cls", "<i4"), ("hits", "<i4"), ("miss", "<i4"), ("x", "<f4"), ("y", "<f4"), ("w", "<f4"),
+                              ("h", "<f4"), ("vx", "<f4"), ("vy", "<f4"), ("ident", CLS_DTYPE)])  # mars_track_state_t
+
+
+class TrackRec(C.Structure):  # mars_track_t
+    _fields_ = [("id", C.c_int), ("hits", C.c_int)]
+
+
+class ClsRec(C.Structure):  # mars_cls_t
+    _fields_ = [("cls", C.c_int), ("score", C.c_float)]
+
+
+class TrackState(C.Structure):  # mars_track_state_t
+    _fields_ = [("id", C.c_int), ("cls", C.c_int), ("hits", C.c_int), ("miss", C.c_int), ("x", C.c_float), ("y", C.c_float), ("w", C.c_float),
+                ("h", C.c_float), ("vx", C.c_float), ("vy", C.c_float), ("ident", ClsRec)]
+
+
+class TrackOpts(C.Structure):  # mars_hip_track_opts_t: zero = default in every field
+    _fields_ = [("min_conf", C.c_float), ("low_conf", C.c_float), ("iou_thresh", C.c_float), ("iou_thresh_low", C.c_float),
+                ("max_miss", C.c_int), ("cls_first", C.c_int), ("cls_count", C.c_int), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert C.sizeof(TrackRec) == TRACK_DTYPE.itemsize == 8 and C.sizeof(TrackState) == TRACK_STATE_DTYPE.itemsize == 48
 
 
 class CompileOpts(C.Structure):  # mars_compile_opts_t (include/mars_compile.h)
@@ -162,7 +188,9 @@ EXPORTS = {
                    "mars_yolo_embed_quantise", "mars_hip_gallery_create", "mars_hip_gallery_add", "mars_hip_gallery_count",
                    "mars_hip_gallery_clear", "mars_hip_gallery_free", "mars_hip_match_chunk", "mars_yolo_match_vectors",
                    "mars_hip_match_device", "mars_hip_match_results", "mars_hip_match", "mars_hip_identify_detections_device",
-                   "mars_hip_identity_results"],
+                   "mars_hip_identity_results",
+                   "mars_hip_tracker_create", "mars_hip_tracker_reset", "mars_hip_tracker_free", "mars_hip_tracker_read",
+                   "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -265,6 +293,15 @@ def lib():
     L.mars_hip_match.argtypes = [P(MarsModel), C.c_void_p, P(MatchOpts), C.c_void_p, C.c_void_p]
     L.mars_hip_identify_detections_device.argtypes = [P(MarsModel), P(MarsModel)]
     L.mars_hip_identity_results.argtypes = [P(MarsModel), C.c_void_p]
+    L.mars_hip_tracker_create.argtypes = [C.c_int, P(C.c_void_p)]
+    L.mars_hip_tracker_reset.argtypes = [C.c_void_p]
+    L.mars_hip_tracker_free.argtypes = [C.c_void_p]
+    L.mars_hip_tracker_free.restype = None
+    L.mars_hip_tracker_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_int), C.c_void_p]
+    L.mars_yolo_track_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(TrackOpts), C.c_void_p]
+    L.mars_hip_track_device.argtypes = [P(MarsModel), C.c_void_p, P(TrackOpts)]
+    L.mars_hip_track_results.argtypes = [P(MarsModel), C.c_void_p]
+    L.mars_hip_track.argtypes = [P(MarsModel), C.c_void_p, P(TrackOpts), C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -499,6 +536,69 @@ def match_vectors(gallery, vectors, opts=None, want_rows=True):
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_match_vectors")
     return top, rows
+
+
+def track_opts(min_conf=0.0, low_conf=0.0, iou_thresh=0.0, iou_thresh_low=0.0, max_miss=0, classes=None, any_class=False,
+               carry_identity=False, stream_major=False):
+    """mars_hip_track_opts_t; zero means default everywhere (min_conf 0.5, no second pass, IoU 0.3 / 0.5, max_miss 30, every class).
+    classes = (first, count)"""
+    first, count = classes if classes else (0, 0)
+    flags = (TRACK_ANY_CLASS if any_class else 0) | (TRACK_CARRY_IDENTITY if carry_identity else 0) | (TRACK_STREAM_MAJOR if stream_major else 0)
+    return TrackOpts(float(min_conf), float(low_conf), float(iou_thresh), float(iou_thresh_low), int(max_miss), int(first), int(count), flags)
+
+
+class Tracker:
+    """mars_hip_tracker_t: the track tables of `streams` camera streams, TRACK_SLOTS slots each, held on the device between calls"""
+
+    def __init__(self, streams):
+        self.streams = int(streams)
+        self.p = C.c_void_p()
+        rc = lib().mars_hip_tracker_create(self.streams, C.byref(self.p))
+        if rc != MARS_OK:
+            self.p = C.c_void_p()
+            raise MarsError(rc, "mars_hip_tracker_create")
+
+    def reset(self):
+        """every table empty, the next id 1, the counters 0"""
+        rc = lib().mars_hip_tracker_reset(self.p)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_tracker_reset")
+
+    def read(self, stream):
+        """-> (TRACK_STATE_DTYPE records of the live tracks of one stream by ascending slot, int64 [births, deaths, overflow, dropped]).  Waits"""
+        states = np.zeros(TRACK_SLOTS, dtype=TRACK_STATE_DTYPE)
+        n = C.c_int(0)
+        counters = np.zeros(4, dtype=np.int64)
+        rc = lib().mars_hip_tracker_read(self.p, int(stream), states.ctypes.data, TRACK_SLOTS, C.byref(n), counters.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_tracker_read")
+        return states[:n.value].copy(), counters
+
+    def close(self):
+        if self.p:
+            lib().mars_hip_tracker_free(self.p)
+            self.p = C.c_void_p()
+
+
+def track_lists(tracker, dets, counts, opts=None, idents=None):
+    """mars_yolo_track_lists: dets = DET_DTYPE [frames][max_det], counts = [frames], idents = None or CLS_DTYPE [frames][max_det] ->
+    TRACK_DTYPE [frames][max_det], on the GPU; the tracker's tables move on by these frames"""
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if d.ndim != 2 or d.shape[0] != c.size:
+        raise ValueError("dets must be [frames][max_det] with one count per frame")
+    i = None
+    if idents is not None:
+        i = np.ascontiguousarray(idents, dtype=CLS_DTYPE)
+        if i.shape != d.shape:
+            raise ValueError("idents must have the shape of dets")
+    o = opts if opts is not None else track_opts()
+    out = np.zeros(d.shape, dtype=TRACK_DTYPE)
+    rc = lib().mars_yolo_track_lists(tracker.p, d.ctypes.data, c.ctypes.data, i.ctypes.data if i is not None else None, d.shape[0], d.shape[1],
+                                     C.byref(o), out.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_track_lists")
+    return out
 
 
 class DeviceBuffer:
@@ -881,6 +981,32 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_identity_results")
         return idents
+
+    def track_device(self, tracker, opts=None, **kw):
+        """THIS model is the detector: the detections its last detect_*_device call left in HBM (and, with carry_identity, the identities
+        of identify_detections) go through the tracker, on the device (mars_hip_track_device); enqueues only.  opts = track_opts(...), or
+        its keywords"""
+        o = opts if opts is not None else track_opts(**kw)
+        rc = lib().mars_hip_track_device(self.p, tracker.p, C.byref(o))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_track_device")
+
+    def track_results(self):
+        """-> TRACK_DTYPE [batch][MAX_DET]: entry i of frame f belongs to detect_results()[f][i]; {-1, 0} where no track took the box.  Waits"""
+        tracks = np.zeros((self.batch, MAX_DET), dtype=TRACK_DTYPE)
+        rc = lib().mars_hip_track_results(self.p, tracks.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_track_results")
+        return tracks
+
+    def track(self, tracker, opts=None, **kw):
+        """track_device + track_results (mars_hip_track)"""
+        o = opts if opts is not None else track_opts(**kw)
+        tracks = np.zeros((self.batch, MAX_DET), dtype=TRACK_DTYPE)
+        rc = lib().mars_hip_track(self.p, tracker.p, C.byref(o), tracks.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_track")
+        return tracks
 
     def write_tensor(self, idx, data, frame=0):
         """mars_hip_write_tensor: one frame of an activation tensor from host memory"""
