@@ -324,6 +324,11 @@ size_t mars_synth_model(const mars_synth_opts_t *opts, void *buf, size_t cap);
  * convolution's bias and scale put a few cells per frame, not hundreds, above a confidence of 0.25.  0 = options it rejects. */
 #define MARS_SYNTH_HEAD_ANCHOR 0
 #define MARS_SYNTH_HEAD_DFL 1
+/* MARS_SYNTH_HEAD_SEG (int8 only, not tiny): the DFL twin plus, per scale, a coefficient branch (conv3x3 + SiLU, conv3x3 + SiLU, conv1x1 ->
+ * 32 channels) and one prototype branch from the P3 feature (conv3x3 + SiLU, a 2x nearest upsample, conv3x3 + SiLU, conv1x1 -> 32 channels
+ * at input / 4).  The file header has four output slots: graph outputs 0 - 2 are the concats and 3 the prototypes; the coefficient tensors
+ * are internal tensors named "seg.coef0", "seg.coef1", "seg.coef2" (the prototype tensor: "seg.proto"), each read by one no-op RESHAPE. */
+#define MARS_SYNTH_HEAD_SEG 2
 size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap);
 
 /* ------------------------------------------------------- image front-end */
@@ -640,6 +645,66 @@ mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *
 mars_error_t mars_hip_track_results(mars_model_t *det_model, mars_track_t *tracks);
 /* mars_hip_track_device + mars_hip_track_results. */
 mars_error_t mars_hip_track(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts, mars_track_t *tracks);
+
+/* ---------------------------------------------------------- Instance masks */
+/* The "-seg" sibling of the anchor-free DFL head (YOLOv8-seg style): beside the box and class convolutions every scale has a COEFFICIENT
+ * convolution of nm channels on the same grid, and the graph has one PROTOTYPE tensor of nm channels at PH x PW (a quarter of the input in
+ * the stock exports, nm = 32).  A detection's mask is sigmoid(coefficients . prototypes) > 0.5 cut to its box.  These calls run the DFL decode
+ * + NMS with the origin of every kept detection recorded, and then compute the masks of the first detections of every frame on the device,
+ * at the prototype tensor's size.  Integer dots, one float32 product and one compare: everything is defined to the bit.
+ *
+ * Setup for kept detection i of frame f.  Its origin is (head k, cell p = gy * W_k + gx), the prediction the decode made it from.
+ *   a[c] = the byte of channel c of head k's coefficient tensor at cell p, c < nm;  P[c][y][x] = the prototype tensor's bytes of frame f.
+ * Dot.        dot(x, y) = sum over c of a[c] * P[c][y][x], int32 (exact: |dot| <= 64 * 2^14).
+ * Scale.      s = coef_scale[k] * proto_scale, ONE float32 product.  A scale of 0 in the options means the tensor's own desc.scale; an
+ *             effective scale <= 0 (or not finite) is refused.
+ * Bit.        bit = ((float)dot * s > logit_min).  logit_min defaults to 0: dot > 0, i.e. sigmoid > 0.5.  (The conversion is exact.)
+ * Rectangle.  From the box (cx, cy, w, h) in GRAPH-INPUT pixels -- the record before any src_w / src_h letterbox mapping -- in float32, every
+ *             operation rounded on its own, no fused multiply-add:  fx = (float)PW / (float)in_w;
+ *               x0 = clamp((int)floorf((cx - w * 0.5f) * fx), 0, PW);  x1 = clamp((int)ceilf((cx + w * 0.5f) * fx), 0, PW);
+ *             y0, y1 alike with fy = (float)PH / (float)in_h.  (A value beyond the int range lands on the bound it passed, a NaN on 0.)
+ * Cut.        Pixel (x, y) is inside iff x0 <= x < x1 and y0 <= y < y1; bits outside are 0.  An empty rectangle: an all-zero mask, area 0.
+ * Selection.  Frame by frame, in the order of the kept list: the detections with conf >= min_conf (default 0: all) until max_per_frame are
+ *             taken.  max_per_frame defaults to 16; 1 .. MARS_SEG_MAX_PER_FRAME.  A function of the lists alone.
+ * Output.     Per frame max_per_frame slots; slot j holds a mars_mask_t {det, x0, y0, x1, y1, area} -- det = the index in the frame's list,
+ *             area = the number of set bits -- and PH rows of pitch = (PW + 31) / 32 uint32 words: pixel x is bit x & 31 of word x >> 5,
+ *             padding bits are 0.  Unused slots: {-1, 0, 0, 0, 0, 0} and all-zero words.
+ * Limits.     1 <= nm <= MARS_SEG_MAX_NM.  Coefficient tensors: int8, nm channels, on the grid of their head's box tensor.  Prototype tensor:
+ *             int8, nm channels.  All of them tensors whose bytes are addressable after a run, as the DFL heads' (read where the plan left
+ *             them: planes, pixel rows, a channel slice; no plan changes).  Anything else: MARS_ERR_INVALID_TENSOR.
+ * Not covered: a file-level finder for seg heads (no shipped file has one: callers name the tensors); masks at input or camera resolution
+ *   (upsampling); masks inside mars_hip_pipe_*; masks in the crop or track stages; nm > 64; float32 tensors; anchor-based seg heads. */
+#define MARS_SEG_MAX_PER_FRAME 64
+#define MARS_SEG_MAX_NM 64
+typedef struct { int det, x0, y0, x1, y1, area; } mars_mask_t; /* 24 bytes */
+/* Zero-initialise; zero means default in every field but the tensor indices. */
+typedef struct {
+    int coef_tensors[4];       /* TENSOR index per DFL head, in the heads' order */
+    int proto_tensor;
+    float coef_scales[4], proto_scale; /* 0: the tensor's own desc.scale */
+    float logit_min, min_conf;
+    int max_per_frame;         /* 0: 16 */
+} mars_hip_seg_opts_t;
+/* DFL decode + NMS of the model's current batch (mars_hip_detect_dfl_device with the same heads: mars_hip_detect_results returns the same
+ * bytes, under src_w / src_h too), then the masks.  Enqueues only, on the auxiliary stream behind the graph; the next run's layers that write
+ * a box, class, coefficient or prototype tensor wait for it on the device.  MARS_ERR_INVALID_TENSOR: what mars_hip_detect_dfl refuses, no
+ * options, a condition of "Limits" or "Scale" above, a logit_min or min_conf that is not finite, max_per_frame outside 0 .. 64, a
+ * coefficient grid that differs from its head's, a model with an open pipe. */
+mars_error_t mars_hip_detect_seg_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_seg_opts_t *seg);
+/* Waits.  recs = [batch][max_per_frame]; words = [batch][max_per_frame][PH][pitch]; any pointer may be NULL.  MARS_ERR_INVALID_TENSOR before
+ * any seg call on this model. */
+mars_error_t mars_hip_mask_results(mars_model_t *model, mars_mask_t *recs, uint32_t *words, int *ph, int *pw, int *pitch_words);
+/* mars_hip_detect_seg_device + mars_hip_detect_results + mars_hip_mask_results. */
+mars_error_t mars_hip_detect_seg(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_seg_opts_t *seg,
+                                 mars_det_t *dets, int *counts, mars_mask_t *recs, uint32_t *words);
+/* Device time (ms) of the mask stage alone (selection + masks) of the last mars_hip_detect_seg_device call, from events on the auxiliary
+ * stream; waits for it.  < 0: not available. */
+float mars_hip_mask_ms(mars_model_t *model);
+/* Host pointers in and out, one frame, the same kernels on the GPU; waits.  coefs = [n][nm] rows, one per box, 0 <= n <= 64 (every box is
+ * taken: slot i = box i); proto = [nm][ph][pw]; boxes in pixels of an in_w x in_h input; s = the product scale (> 0).  recs = [n], words =
+ * [n][ph][(pw + 31) / 32].  0, or -1: an argument out of range, no device, or a failed launch. */
+int mars_yolo_masks(const int8_t *coefs, int n, int nm, const int8_t *proto, int ph, int pw, const mars_det_t *boxes, int in_w, int in_h,
+                    float s, float logit_min, mars_mask_t *recs, uint32_t *words);
 
 #ifdef __cplusplus
 }

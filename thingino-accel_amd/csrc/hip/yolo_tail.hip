@@ -170,7 +170,10 @@ __global__ __launch_bounds__(256) void decode_kernel(const mhip_detect_t p) {
 #define NMS_SUBS (NMS_THREADS / NMS_CHUNK) // threads that share a row's bucket
 #define NMS_CHUNK 64
 #define NMS_BUCKETS 128
-__global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int *counts, float thresh) {
+// cand_pred / kept_pred (both or neither; NULL = nothing is written): the origin of every record.  cand_pred[f][r] is the prediction index
+// of candidate r as the decode wrote it; the compaction writes kept_pred[f][slot] = cand_pred[f][sperm[j]] for survivor j of the sorted
+// order -- sperm[] is final on every path of the sort (bitonic, tie-queue replay, the NaN loop) and nothing overwrites it afterwards.
+__global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int *counts, float thresh, const int *cand_pred, int *kept_pred) {
     __shared__ float bx[1024], by[1024], bw[1024], bh[1024], bconf[1024];
     __shared__ int bc[1024];
     __shared__ unsigned short blist[1024];              // box indices grouped by class bucket
@@ -386,6 +389,7 @@ __global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int
             det_rec k;
             k.x = bx[idx]; k.y = by[idx]; k.w = bw[idx]; k.h = bh[idx]; k.conf = bconf[idx]; k.cls = bc[idx];
             dets[slot] = k;
+            if (kept_pred) kept_pred[(size_t)f * MAXD + slot] = cand_pred[(size_t)f * MAXD + sperm[idx]];
         }
         for (int w = 0; w < NMS_THREADS / 64; w++) total += wave_cnt[w];
         __syncthreads();
@@ -394,8 +398,9 @@ __global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int
 }
 
 extern "C" void mhip_tail_release(void) {} // (the systolic sort's permutation buffer lived here until round 3)
-static int launch_sort_nms(det_rec *dets, int *counts, int frames, float thresh) {
-    hipLaunchKernelGGL(sort_nms_kernel, dim3(frames), dim3(NMS_THREADS), 0, mhip_stream_native(), dets, counts, thresh);
+static int launch_sort_nms(det_rec *dets, int *counts, int frames, float thresh, const int *cand_pred = nullptr, int *kept_pred = nullptr) {
+    if (!cand_pred || !kept_pred) cand_pred = nullptr, kept_pred = nullptr;
+    hipLaunchKernelGGL(sort_nms_kernel, dim3(frames), dim3(NMS_THREADS), 0, mhip_stream_native(), dets, counts, thresh, cand_pred, kept_pred);
     return mhip_check(hipGetLastError(), "sort + nms");
 }
 
@@ -540,12 +545,14 @@ __global__ __launch_bounds__(HEADS_THREADS) void heads_decode_kernel(const mhip_
 }
 
 // the kept boxes back through the letterbox of the image front-end (after NMS: suppression sees the network's coordinates)
-__global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int *counts, float px, float py, float rx, float ry) {
+// pre != NULL: the records as they were before the mapping (graph-input pixels) are kept in pre[frame][i] (the mask stage cuts by them)
+__global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int *counts, float px, float py, float rx, float ry, det_rec *pre) {
     det_rec *d = all + (size_t)blockIdx.x * MAXD;
     int n = counts[blockIdx.x];
     if (n > MAXD) n = MAXD;
     for (int i = threadIdx.x; i < n; i += 256) {
         det_rec r = d[i];
+        if (pre) pre[(size_t)blockIdx.x * MAXD + i] = r;
         r.x = __fmul_rn(__fsub_rn(r.x, px), rx);
         r.y = __fmul_rn(__fsub_rn(r.y, py), ry);
         r.w = __fmul_rn(r.w, rx);
@@ -567,6 +574,8 @@ __global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int 
 // the step -- consecutive lanes take consecutive cells, so plane reads coalesce -- and issues the loads of its four cells before the
 // first compare; pixel rows (ch_step 1) come as 16-byte loads and are compared as integers.  Box bytes are read only for the cells
 // that pass.  Slots come from one ordered block-wide count per step, and the walk ends once 1000 candidates are reached.
+// With cand_pred / kept_pred set the decode also writes each candidate's prediction index (cells of the heads before it + its cell) and
+// the sort carries it to the kept list (mhip_dfl_heads_t); the records and counts are the same bytes either way.
 #define DFL_THREADS 256
 #define DFL_CELLS 4
 
@@ -627,8 +636,8 @@ __global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_
     det_rec *dets = (det_rec *)p.dets + (size_t)f * MAXD;
     const float conf = p.conf;
     const int R = p.reg_max;
-    int total = 0;
-    for (int hd = 0; hd < p.nheads && total < MAXD; hd++) {
+    int total = 0, pred0 = 0; // pred0: the prediction index of this head's cell 0
+    for (int hd = 0; hd < p.nheads && total < MAXD; pred0 += p.h[hd] * p.w[hd], hd++) {
         const int8_t *cb = p.cls[hd] + (size_t)f * p.cls_frame_stride[hd];
         const int8_t *bb = p.box[hd] + (size_t)f * p.box_frame_stride[hd];
         const int W = p.w[hd], npix = p.h[hd] * W, nc = p.nc[hd];
@@ -724,6 +733,7 @@ __global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_
                 d.conf = cf[k];
                 d.cls = arg[k];
                 dets[slot] = d;
+                if (p.cand_pred) p.cand_pred[(size_t)f * MAXD + slot] = pred0 + cell;
             }
             __syncthreads(); // wave_cnt is rewritten by the next step
         }
@@ -744,7 +754,7 @@ extern "C" int mhip_detect_heads(const mhip_heads_t *p) {
     if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
     if (rc || !p->map) return rc;
     hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,
-                       (float)p->py, p->rx, p->ry);
+                       (float)p->py, p->rx, p->ry, (det_rec *)nullptr);
     return mhip_check(hipGetLastError(), "letterbox mapping");
 }
 
@@ -754,11 +764,13 @@ extern "C" int mhip_detect_dfl(const mhip_dfl_heads_t *p) {
         if (!p->box[k] || !p->cls[k] || p->h[k] <= 0 || p->w[k] <= 0 || p->nc[k] < 1 || p->box_pix_step[k] <= 0 || p->box_ch_step[k] <= 0 ||
             p->cls_pix_step[k] <= 0 || p->cls_ch_step[k] <= 0)
             return -1;
-    hipLaunchKernelGGL(dfl_decode_kernel, dim3(p->frames), dim3(DFL_THREADS), 0, mhip_stream_native(), *p);
+    mhip_dfl_heads_t q = *p;
+    if (!q.cand_pred || !q.kept_pred) q.cand_pred = q.kept_pred = nullptr; // both or neither
+    hipLaunchKernelGGL(dfl_decode_kernel, dim3(p->frames), dim3(DFL_THREADS), 0, mhip_stream_native(), q);
     int rc = mhip_check(hipGetLastError(), "decode DFL heads");
-    if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
+    if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh, p->cand_pred, p->kept_pred);
     if (rc || !p->map) return rc;
     hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,
-                       (float)p->py, p->rx, p->ry);
+                       (float)p->py, p->rx, p->ry, (det_rec *)p->premap);
     return mhip_check(hipGetLastError(), "letterbox mapping");
 }

@@ -193,6 +193,12 @@ typedef struct mars_model_ext {
     /* tracking (mars_track.c) */
     void *track_dev;    /* track ids of THIS model's detections: [track_cap][MARS_YOLO_MAX_DET] x mars_track_t on the device */
     int track_cap, track_frames; /* track_frames == 0: no track call yet */
+    /* instance masks (mars_seg.c) */
+    void *seg_dev;      /* one block on the device: candidate / kept prediction indices [frames][MARS_YOLO_MAX_DET] x int each, the kept boxes before the
+                         * letterbox mapping, [frames][seg_max] x mars_mask_t, [frames][seg_max][seg_ph][pitch] x uint32 */
+    size_t seg_bytes, seg_rec_off, seg_word_off;
+    int seg_frames, seg_max, seg_ph, seg_pw; /* of the last seg call; seg_frames == 0: there was none */
+    void *ev_seg[2];    /* timing events around the mask stage's launches on the auxiliary stream */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -262,10 +268,14 @@ MARS_INTERNAL void mars_match_release(mars_model_ext_t *m); /* the match results
 /* mars_track.c */
 MARS_INTERNAL void mars_track_release(mars_model_ext_t *m); /* the track results of a model whose device state goes away */
 
+/* mars_seg.c */
+MARS_INTERNAL void mars_seg_release(mars_model_ext_t *m); /* the mask results of a model whose device state goes away */
+
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);
 MARS_INTERNAL int mars_locate_i8(const mars_model_ext_t *m, int T, int ch, int hh, int ww, int any_writer, int *buf, int *off, int *pix_step, int *ch_step);
 /* a tail (launch(m, cfg, m->det_dev, m->det_counts_dev) on the current stream) on the auxiliary stream behind the graph; sets tail_pending */
+MARS_INTERNAL mars_error_t mars_own_det_buffers(mars_model_ext_t *m); /* the model's own detection buffers, large enough for the current batch */
 MARS_INTERNAL mars_error_t mars_tail_on_aux(mars_model_ext_t *m, int (*launch)(struct mars_model_ext *, const void *, void *, int *), const void *cfg);
 
 /* detection tail pieces shared with the pipelined I/O (mars_yolo.c) */
@@ -299,6 +309,8 @@ typedef struct {
     int map, px, py;
     float rx, ry;
     int internal; /* some buffer is not a graph output's: one buffer for every batch in flight */
+    int *cand_pred, *kept_pred; /* device, or NULL (mars_dfl_resolve leaves NULL): mhip_dfl_heads_t's origin arrays */
+    void *premap;               /* device, or NULL: mhip_dfl_heads_t.premap */
 } mars_dfl_cfg_t;
 MARS_INTERNAL int mars_find_dfl_heads(const mars_model_ext_t *m, int *box_ids, int *cls_ids, int *strides, int *num_classes, int *reg_max, int cap);
 MARS_INTERNAL mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *h, mars_dfl_cfg_t *c);

@@ -296,7 +296,7 @@ size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap)
     T h20 = b.c3(b.concat({h18, h14}), ch(512), dep(3), false);
     T h21 = b.conv(h20, ch(512), 3, 2, true, false);
     T h23 = b.c3(b.concat({h21, h10}), ch(1024), dep(3), false);
-    if (head == MARS_SYNTH_HEAD_DFL) {
+    if (head == MARS_SYNTH_HEAD_DFL || head == MARS_SYNTH_HEAD_SEG) {
         // anchor-free Detect: per scale a box branch and a class branch (conv3x3 + SiLU twice, then a plain 1x1), concatenated; the three
         // concats are the graph outputs (the exported softmax / dist2bbox chain behind them is what mars_hip_detect_dfl computes)
         const int c2 = 64, c3 = h17.c > 80 ? h17.c : 80;
@@ -306,6 +306,22 @@ size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap)
             T cl = b.conv(b.conv(b.conv(p, c3, 3, 1, true, false), c3, 3, 1, true, false), 80, 1, 1, false, false, b.nchw ? Builder::kDflClsScaleNchw : Builder::kDflClsScaleNhwc,
                           Builder::kDflClsSigma, Builder::kDflClsMean);
             outs.push_back(b.concat({bx, cl}).id);
+        }
+        if (head == MARS_SYNTH_HEAD_SEG) {
+            // Segment: per scale a coefficient branch of nm = 32 outputs, and one prototype branch from the P3 feature that ends at input / 4.
+            // The header has four output slots: the prototypes take the fourth, the coefficient tensors stay internal (named, each read by
+            // one RESHAPE the executor ignores, as the anchor twin keeps one behind its last head)
+            const int nm = 32, c4 = h17.c / 4 > nm ? h17.c / 4 : nm, cp = h17.c > nm ? h17.c : nm;
+            int k = 0;
+            for (const T &p : {h17, h20, h23}) {
+                T cf = b.conv(b.conv(b.conv(p, c4, 3, 1, true, false), c4, 3, 1, true, false), nm, 1, 1, false, false, Builder::kHeadScale);
+                std::snprintf(b.tensors[cf.id].name, sizeof(b.tensors[cf.id].name), "seg.coef%d", k++);
+                T r = b.act("seg.coef_flat", nm, cf.h * cf.w, 1, Builder::kHeadScale, 1.f);
+                b.layer(MARS_LAYER_RESHAPE, {cf.id}, r.id);
+            }
+            T pr = b.conv(b.conv(b.upsample(b.conv(h17, cp, 3, 1, true, false)), cp, 3, 1, true, false), nm, 1, 1, false, false, Builder::kHeadScale);
+            std::snprintf(b.tensors[pr.id].name, sizeof(b.tensors[pr.id].name), "seg.proto");
+            outs.push_back(pr.id);
         }
         return b.serialise({x.id}, outs, buf, cap);
     }
@@ -325,9 +341,9 @@ size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap)
 } // namespace
 
 extern "C" size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap) {
-    if (!opts || (head != MARS_SYNTH_HEAD_ANCHOR && head != MARS_SYNTH_HEAD_DFL)) return 0;
+    if (!opts || (head != MARS_SYNTH_HEAD_ANCHOR && head != MARS_SYNTH_HEAD_DFL && head != MARS_SYNTH_HEAD_SEG)) return 0;
     if (opts->input_hw < 0 || (opts->tiny == 0 && opts->input_hw % 32 != 0)) return 0;
-    if (head == MARS_SYNTH_HEAD_DFL && (opts->tiny || opts->float32)) return 0;
+    if (head != MARS_SYNTH_HEAD_ANCHOR && (opts->tiny || opts->float32)) return 0;
     return opts->tiny ? build_tiny(*opts, buf, cap) : build_yolov5(*opts, head, buf, cap);
 }
 

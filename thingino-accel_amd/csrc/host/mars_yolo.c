@@ -385,6 +385,8 @@ static mars_error_t own_det_buffers(mars_model_ext_t *m) {
     return MARS_OK;
 }
 
+mars_error_t mars_own_det_buffers(mars_model_ext_t *m) { return own_det_buffers(m); }
+
 /* as mars_hip_detect_device: a raw-head decode (launch(m, cfg, dets, counts) on the current stream) runs on the auxiliary stream behind the
  * graph, and the next run's layers that write a tensor it reads wait for it (tail_read, set by the caller) -- the heads of the shipped
  * files are internal tensors, not graph outputs */
@@ -649,6 +651,7 @@ int mars_dfl_launch(mars_model_ext_t *m, const mars_dfl_cfg_t *c, void *dets_dev
     p.counts = counts_dev;
     p.raw_counts = counts_dev + m->batch;
     p.map = c->map; p.px = c->px; p.py = c->py; p.rx = c->rx; p.ry = c->ry;
+    p.cand_pred = c->cand_pred; p.kept_pred = c->kept_pred; p.premap = c->premap;
     return mhip_detect_dfl(&p);
 }
 

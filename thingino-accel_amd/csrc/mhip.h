@@ -318,6 +318,11 @@ typedef struct {
     int *raw_counts;        /* device [frames] candidates before NMS (or NULL) */
     int map, px, py;
     float rx, ry;
+    /* optional, both or neither (NULL: nothing is written, nothing else changes): the origin of every record as a prediction index --
+     * cells of the heads before its head + its cell.  cand_pred [frames][1000]: of candidate r as the decode wrote it (scratch of the
+     * sort); kept_pred [frames][1000]: of kept record `slot` */
+    int *cand_pred, *kept_pred;
+    void *premap;           /* optional, looked at only with map != 0: device [frames][1000] records, the kept boxes BEFORE the letterbox mapping */
 } mhip_dfl_heads_t;
 int mhip_detect_dfl(const mhip_dfl_heads_t *p);
 
@@ -429,6 +434,32 @@ typedef struct {
     int max_miss, cls_first, cls_count, any_class;
 } mhip_track_t;
 int mhip_track(const mhip_track_t *p); /* one launch */
+
+/* ---- instance masks (seg.hip): kept detections + their prediction indices -> per frame up to max_per_frame records and bit masks at the
+ * prototype tensor's size, by the exact rule of include/mars_hip.h ("Instance masks").  Every pointer is device memory.  Two launches: the
+ * selection (records, rectangles), then the masks (int8 MFMA of the selected cells' coefficient rows against the prototype pixels). */
+#define MHIP_SEG_MAX_PER_FRAME 64
+#define MHIP_SEG_MAX_NM 64
+typedef struct {
+    const int8_t *coef[4]; size_t coef_frame_stride[4]; /* coefficient tensor of head k, frame f: coef[k] + f * coef_frame_stride[k] */
+    int coef_pix_step[4], coef_ch_step[4];              /* byte of (cell p, channel c) = p * pix_step + c * ch_step */
+    int cells[4];                                       /* h * w of head k: prediction index = cells of the heads before + cell */
+    float scale[4];                                     /* coefficient scale of head k * prototype scale, one float32 product */
+    int nheads;
+    const int8_t *proto; size_t proto_frame_stride; int proto_pix_step, proto_ch_step;
+    int nm, ph, pw, in_w, in_h;
+    int frames;
+    const void *boxes;      /* [frames][det_cap] records of 24 bytes, graph-input pixels */
+    const int *counts;      /* [frames] list lengths (clamped to 0 .. det_cap) */
+    const int *pred;        /* [frames][det_cap] prediction index of every listed record */
+    int det_cap;
+    float logit_min, min_conf;
+    int select_all;         /* != 0: every listed record is taken whatever its confidence (the host-pointer form) */
+    int max_per_frame;      /* 1 .. MHIP_SEG_MAX_PER_FRAME */
+    void *recs;             /* [frames][max_per_frame] records of 24 bytes {det, x0, y0, x1, y1, area} */
+    uint32_t *words;        /* [frames][max_per_frame][ph][(pw + 31) / 32] */
+} mhip_seg_t;
+int mhip_seg(const mhip_seg_t *p);
 
 #ifdef __cplusplus
 }

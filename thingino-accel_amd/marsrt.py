@@ -146,7 +146,21 @@ class TrackOpts(C.Structure):  # mars_hip_track_opts_t: zero = default in every 
                 ("max_miss", C.c_int), ("cls_first", C.c_int), ("cls_count", C.c_int), ("flags", C.c_uint)]
 
 
+SEG_MAX_PER_FRAME, SEG_MAX_NM = 64, 64                                  # MARS_SEG_*
+MASK_DTYPE = np.dtype([("det", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("area", "<i4")])  # mars_mask_t
+
+
+class MaskRec(C.Structure):  # mars_mask_t
+    _fields_ = [("det", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("area", C.c_int)]
+
+
+class SegOpts(C.Structure):  # mars_hip_seg_opts_t: zero = default in every field but the tensor indices
+    _fields_ = [("coef_tensors", C.c_int * 4), ("proto_tensor", C.c_int), ("coef_scales", C.c_float * 4), ("proto_scale", C.c_float),
+                ("logit_min", C.c_float), ("min_conf", C.c_float), ("max_per_frame", C.c_int)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert C.sizeof(MaskRec) == MASK_DTYPE.itemsize == 24 and C.sizeof(SegOpts) == 52
 assert C.sizeof(TrackRec) == TRACK_DTYPE.itemsize == 8 and C.sizeof(TrackState) == TRACK_STATE_DTYPE.itemsize == 48
 
 
@@ -190,7 +204,8 @@ EXPORTS = {
                    "mars_hip_match_device", "mars_hip_match_results", "mars_hip_match", "mars_hip_identify_detections_device",
                    "mars_hip_identity_results",
                    "mars_hip_tracker_create", "mars_hip_tracker_reset", "mars_hip_tracker_free", "mars_hip_tracker_read",
-                   "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track"],
+                   "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track",
+                   "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -302,6 +317,13 @@ def lib():
     L.mars_hip_track_device.argtypes = [P(MarsModel), C.c_void_p, P(TrackOpts)]
     L.mars_hip_track_results.argtypes = [P(MarsModel), C.c_void_p]
     L.mars_hip_track.argtypes = [P(MarsModel), C.c_void_p, P(TrackOpts), C.c_void_p]
+    L.mars_hip_detect_seg_device.argtypes = [P(MarsModel), P(YoloDflHeads), P(SegOpts)]
+    L.mars_hip_mask_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int)]
+    L.mars_hip_detect_seg.argtypes = [P(MarsModel), P(YoloDflHeads), P(SegOpts), C.c_void_p, P(C.c_int), C.c_void_p, C.c_void_p]
+    L.mars_hip_mask_ms.restype = C.c_float
+    L.mars_hip_mask_ms.argtypes = [P(MarsModel)]
+    L.mars_yolo_masks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                  C.c_void_p, C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -629,12 +651,12 @@ class DeviceBuffer:
             pass
 
 
-SYNTH_HEADS = {"anchor": 0, "dfl": 1}  # MARS_SYNTH_HEAD_*
+SYNTH_HEADS = {"anchor": 0, "dfl": 1, "seg": 2}  # MARS_SYNTH_HEAD_*
 
 
 def synth_model(width_x16=8, depth_x3=1, input_hw=640, float32=False, nchw_int8=False, seed=1, tiny=False, vary_scales=False, head="anchor"):
     """Bytes of a synthetic well-formed .mars graph (mars_synth_model; head="dfl": mars_synth_model_head with the anchor-free DFL
-    Detect head, int8 only)."""
+    Detect head, int8 only; head="seg": that head plus mask coefficients and prototypes, see seg_twin_tensors)."""
     o = SynthOpts(width_x16, depth_x3, input_hw, int(float32), int(nchw_int8), seed, int(tiny), int(vary_scales))
     if head == "anchor":
         make = lib().mars_synth_model
@@ -725,6 +747,57 @@ def yolo_dfl_heads(heads=None, reg_max=0, box_scales=None, cls_scales=None, conf
     if src is not None:
         h.src_w, h.src_h = int(src[0]), int(src[1])
     return h
+
+
+def seg_twin_tensors(file_bytes):
+    """the mask tensors of a synth_model(head="seg") file, found by the names the writer gives them (host only):
+    ([coefficient tensor index per head, by stride], prototype tensor index).  KeyError if the file has no such tensors."""
+    b = bytes(file_bytes)
+    hdr = MarsHeader.from_buffer_copy(b[:C.sizeof(MarsHeader)])
+    names = {}
+    for i in range(hdr.num_tensors):
+        o = 76 + 124 * i
+        names[b[o + 4:o + 64].split(b"\0")[0].decode()] = i
+    return [names["seg.coef%d" % k] for k in range(3)], names["seg.proto"]
+
+
+def seg_opts(coefs, proto, coef_scales=None, proto_scale=0.0, logit_min=0.0, min_conf=0.0, max_per_frame=0):
+    """mars_hip_seg_opts_t.  coefs: the coefficient tensor index of every DFL head, in the heads' order; proto: the prototype tensor index;
+    coef_scales: None (the tensors' own), one number for every head or a list"""
+    o = SegOpts()
+    for k, t in enumerate(coefs):
+        o.coef_tensors[k] = int(t)
+    o.proto_tensor = int(proto)
+    if coef_scales is not None:
+        for k, x in enumerate(coef_scales if isinstance(coef_scales, (tuple, list)) else [coef_scales] * 4):
+            o.coef_scales[k] = float(x)
+    o.proto_scale, o.logit_min, o.min_conf, o.max_per_frame = float(proto_scale), float(logit_min), float(min_conf), int(max_per_frame)
+    return o
+
+
+def masks(coefs, proto, boxes, in_w, in_h, s, logit_min=0.0):
+    """mars_yolo_masks: coefs int8 [n][nm] (one row per box), proto int8 [nm][ph][pw], boxes DET_DTYPE [n] in pixels of an in_w x in_h
+    input -> (records MASK_DTYPE [n], words uint32 [n][ph][pitch]); host arrays in and out, runs on the GPU"""
+    a = np.ascontiguousarray(coefs, dtype=np.int8)
+    pr = np.ascontiguousarray(proto, dtype=np.int8)
+    bx = np.ascontiguousarray(boxes, dtype=DET_DTYPE)
+    nm, ph, pw = pr.shape
+    n = len(bx)
+    assert a.shape == (n, nm) or (n == 0 and a.size == 0)
+    recs = np.zeros(n, dtype=MASK_DTYPE)
+    words = np.zeros((n, ph, (pw + 31) // 32), dtype=np.uint32)
+    rc = lib().mars_yolo_masks(a.ctypes.data, n, nm, pr.ctypes.data, ph, pw, bx.ctypes.data, int(in_w), int(in_h), float(s), float(logit_min),
+                               recs.ctypes.data, words.ctypes.data)
+    if rc != 0:
+        raise ValueError("mars_yolo_masks refused its arguments or failed (%d)" % rc)
+    return recs, words
+
+
+def unpack_masks(words, pw):
+    """uint32 [..., PH, pitch] mask words -> bool [..., PH, pw]: pixel x is bit x & 31 of word x >> 5"""
+    w = np.ascontiguousarray(words, dtype="<u4")
+    bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[:-1] + (w.shape[-1] * 4,)), axis=-1, bitorder="little")
+    return bits[..., :pw].astype(bool)
 
 
 def compile_onnx(onnx_bytes, float32=False, nhwc=False, verbose=False):
@@ -1093,6 +1166,33 @@ class Model:
         rc = lib().mars_hip_detect_dfl_device(self.p, C.byref(yolo_dfl_heads(heads, **kw)))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_detect_dfl_device")
+
+    def detect_seg_device(self, seg, heads=None, **kw):
+        """DFL decode + NMS + instance masks, results stay in HBM (mars_hip_detect_seg_device).  seg: seg_opts(); heads and the keywords
+        as for yolo_dfl_heads()"""
+        rc = lib().mars_hip_detect_seg_device(self.p, C.byref(yolo_dfl_heads(heads, **kw)), C.byref(seg) if seg is not None else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_seg_device")
+        self._seg_max = seg.max_per_frame or 16
+
+    def mask_results(self):
+        """the masks the last detect_seg_device left in HBM (mars_hip_mask_results): (records MASK_DTYPE [batch][max_per_frame],
+        words uint32 [batch][max_per_frame][PH][pitch], PW); unpack_masks(words, PW) gives the pixels"""
+        ph, pw, pitch = C.c_int(), C.c_int(), C.c_int()
+        rc = lib().mars_hip_mask_results(self.p, None, None, C.byref(ph), C.byref(pw), C.byref(pitch))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_mask_results")
+        recs = np.zeros((self.batch, self._seg_max), dtype=MASK_DTYPE)
+        words = np.zeros((self.batch, self._seg_max, ph.value, pitch.value), dtype=np.uint32)
+        rc = lib().mars_hip_mask_results(self.p, recs.ctypes.data, words.ctypes.data, None, None, None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_mask_results")
+        return recs, words, pw.value
+
+    def detect_seg(self, seg, heads=None, **kw):
+        """detect_seg_device + detect_results + mask_results (mars_hip_detect_seg): (a record array per frame, records, words, PW)"""
+        self.detect_seg_device(seg, heads, **kw)
+        return (self.detect_results(),) + self.mask_results()
 
     def detect_results(self):
         """the detections the last detect_device / detect_heads_device / detect_dfl_device left in HBM (mars_hip_detect_results)"""
