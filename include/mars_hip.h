@@ -329,6 +329,10 @@ size_t mars_synth_model(const mars_synth_opts_t *opts, void *buf, size_t cap);
  * at input / 4).  The file header has four output slots: graph outputs 0 - 2 are the concats and 3 the prototypes; the coefficient tensors
  * are internal tensors named "seg.coef0", "seg.coef1", "seg.coef2" (the prototype tensor: "seg.proto"), each read by one no-op RESHAPE. */
 #define MARS_SYNTH_HEAD_SEG 2
+/* MARS_SYNTH_HEAD_POSE (int8 only, not tiny): the DFL twin plus, per scale, a keypoint branch (conv3x3 + SiLU, conv3x3 + SiLU, conv1x1 -> 17 x 3
+ * = 51 channels), built behind every box and class branch: the three graph outputs and the detections are the DFL twin's.  The keypoint
+ * tensors are internal tensors named "pose.kpt0", "pose.kpt1", "pose.kpt2", each read by one no-op RESHAPE. */
+#define MARS_SYNTH_HEAD_POSE 3
 size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap);
 
 /* ------------------------------------------------------- image front-end */
@@ -705,6 +709,67 @@ float mars_hip_mask_ms(mars_model_t *model);
  * [n][ph][(pw + 31) / 32].  0, or -1: an argument out of range, no device, or a failed launch. */
 int mars_yolo_masks(const int8_t *coefs, int n, int nm, const int8_t *proto, int ph, int pw, const mars_det_t *boxes, int in_w, int in_h,
                     float s, float logit_min, mars_mask_t *recs, uint32_t *words);
+
+/* ----------------------------------------------------------- Pose keypoints */
+/* The "-pose" sibling of the anchor-free DFL head (YOLOv8-pose style): beside the box and class convolutions every scale has a KEYPOINT
+ * convolution of K * D channels on the same grid (K keypoints of D = 2 or 3 numbers; 17 x 3 in the stock export).  A detection's keypoints
+ * are the channels of the cell it was made from.  These calls run the DFL decode + NMS with the origin of every kept detection recorded, and
+ * then gather and decode the keypoints of the first detections of every frame on the device.  float32, every operation rounded on its own,
+ * no fused multiply-add: everything is defined to the bit.
+ *
+ * Origin.     For kept detection i of frame f: (head k, cell p = gy * W_k + gx), the prediction the decode made it from, as in "Instance
+ *             masks".
+ * Bytes.      q[c] = the byte of channel c of head k's keypoint tensor at cell p, c < K * D.  Keypoint j owns channels D * j (x), D * j + 1 (y)
+ *             and, with D == 3, D * j + 2 (visibility).
+ * Scale.      s_k = the head's keypoint scale.  A scale of 0 in the options means the tensor's own desc.scale; an effective scale <= 0 (or
+ *             not finite) is refused.
+ * Point.      ax = (float)q_x * s_k;  x = ((ax * 2.0f) + (float)gx) * (float)stride_k;  y alike from q_y and gy.  (Ultralytics'
+ *             (a * 2 + (anchor - 0.5)) * stride with anchor = g + 0.5.)  Graph-input pixels.
+ * Visibility. D == 3: v = 1.0f / (1.0f + expf((-(float)q_v) * s_k)), the function of (byte, scale) the DFL class confidence is, by the same
+ *             expf (the host's, tabulated per head).  D == 2: v = 1.0f.
+ * Mapping.    With src_w > 0 in the DFL options the keypoints go through the boxes' letterbox rule: x' = (x - px) * (src_w / nw), y' = (y - py) *
+ *             (src_h / nh), the factors and paddings those of the boxes.  Without it they stay in graph-input pixels.  v is never mapped.
+ * Selection.  Frame by frame, in the order of the kept list: the detections with conf >= min_conf (default 0: all) until max_per_frame are
+ *             taken.  max_per_frame defaults to 32; 1 .. MARS_POSE_MAX_PER_FRAME.  A function of the lists alone.
+ * Output.     Per frame max_per_frame slots; slot t holds a mars_pose_t {det, head, cell} -- det = the index in the frame's list -- and K
+ *             records mars_kpt_t {x, y, v}.  Unused slots: {-1, -1, -1} and all-zero keypoints.
+ * Limits.     1 <= K <= MARS_POSE_MAX_KPT, D = 2 or 3.  Keypoint tensors: int8, exactly K * D channels, on the grid of their head's box
+ *             tensor, tensors whose bytes are addressable after a run as the DFL heads' (read where the plan left them: planes, pixel rows,
+ *             a channel slice; no plan changes).  Anything else: MARS_ERR_INVALID_TENSOR.
+ * Not covered: a file-level finder for pose heads (callers name the tensors); keypoints inside mars_hip_pipe_*; keypoints in the crop or
+ *   track stages; OKS-based suppression (the boxes' NMS decides); float32 tensors; anchor-based pose heads. */
+#define MARS_POSE_MAX_PER_FRAME 256
+#define MARS_POSE_MAX_KPT 32
+typedef struct { int det, head, cell; } mars_pose_t; /* 12 bytes */
+typedef struct { float x, y, v; } mars_kpt_t;        /* 12 bytes */
+/* Zero-initialise; zero means default in every field but the tensor indices and num_kpt. */
+typedef struct {
+    int kpt_tensors[4];     /* TENSOR index per DFL head, in the heads' order */
+    int num_kpt, kpt_dim;   /* K; D (0: 3) */
+    float kpt_scales[4];    /* 0: the tensor's own desc.scale */
+    float min_conf;
+    int max_per_frame;      /* 0: 32 */
+} mars_hip_pose_opts_t;
+/* DFL decode + NMS of the model's current batch (mars_hip_detect_dfl_device with the same heads: mars_hip_detect_results returns the same
+ * bytes, under src_w / src_h too), then the keypoints.  Enqueues only, on the auxiliary stream behind the graph; the next run's layers that
+ * write a box, class or keypoint tensor wait for it on the device.  Its results live in a block of their own: a mask call on the same model
+ * leaves them alone (each call runs its own tail, the detections are those of the last one).  MARS_ERR_INVALID_TENSOR: what
+ * mars_hip_detect_dfl refuses, no options, a condition of "Limits" or "Scale" above, a min_conf that is not finite, max_per_frame outside
+ * 0 .. 256, K * D that is not the tensors' channel count, a keypoint grid that differs from its head's, a model with an open pipe. */
+mars_error_t mars_hip_detect_pose_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_pose_opts_t *pose);
+/* Waits.  recs = [batch][max_per_frame]; kpts = [batch][max_per_frame][K]; any pointer may be NULL; *num_kpt = K.  MARS_ERR_INVALID_TENSOR
+ * before any pose call on this model. */
+mars_error_t mars_hip_pose_results(mars_model_t *model, mars_pose_t *recs, mars_kpt_t *kpts, int *num_kpt);
+/* mars_hip_detect_pose_device + mars_hip_detect_results + mars_hip_pose_results. */
+mars_error_t mars_hip_detect_pose(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_pose_opts_t *pose,
+                                  mars_det_t *dets, int *counts, mars_pose_t *recs, mars_kpt_t *kpts);
+/* Device time (ms) of the keypoint stage alone (selection + gather) of the last mars_hip_detect_pose_device call, from events on the
+ * auxiliary stream; waits for it.  < 0: not available. */
+float mars_hip_pose_ms(mars_model_t *model);
+/* Host pointers in and out, one frame, the same kernels on the GPU; waits.  rows = [n][K * D] bytes, one row per detection, 0 <= n <= 256
+ * (every row is taken: slot i = row i); gx, gy, stride = [n], the cell and stride of every row; s = the keypoint scale (> 0); no mapping.
+ * kpts = [n][K].  0, or -1: an argument out of range, no device, or a failed launch. */
+int mars_yolo_keypoints(const int8_t *rows, int n, int K, int D, const int *gx, const int *gy, const int *stride, float s, mars_kpt_t *kpts);
 
 #ifdef __cplusplus
 }

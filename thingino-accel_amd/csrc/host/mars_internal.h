@@ -199,6 +199,14 @@ typedef struct mars_model_ext {
     size_t seg_bytes, seg_rec_off, seg_word_off;
     int seg_frames, seg_max, seg_ph, seg_pw; /* of the last seg call; seg_frames == 0: there was none */
     void *ev_seg[2];    /* timing events around the mask stage's launches on the auxiliary stream */
+    /* pose keypoints (mars_pose.c) */
+    void *pose_dev;     /* one block on the device: the visibility tables [4][256] x float, candidate / kept prediction indices
+                         * [frames][MARS_YOLO_MAX_DET] x int each, [frames][pose_max] x mars_pose_t, [frames][pose_max][pose_k] x mars_kpt_t */
+    size_t pose_bytes, pose_rec_off, pose_kpt_off;
+    int pose_frames, pose_max, pose_k; /* of the last pose call; pose_frames == 0: there was none */
+    float pose_lut_scale[4];           /* the scales the block's visibility tables were built from */
+    int pose_lut_n;                    /* tables that are up (0: none) */
+    void *ev_pose[2];   /* timing events around the keypoint stage's launches on the auxiliary stream */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -270,6 +278,9 @@ MARS_INTERNAL void mars_track_release(mars_model_ext_t *m); /* the track results
 
 /* mars_seg.c */
 MARS_INTERNAL void mars_seg_release(mars_model_ext_t *m); /* the mask results of a model whose device state goes away */
+
+/* mars_pose.c */
+MARS_INTERNAL void mars_pose_release(mars_model_ext_t *m); /* the keypoint results of a model whose device state goes away */
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

@@ -461,6 +461,35 @@ typedef struct {
 } mhip_seg_t;
 int mhip_seg(const mhip_seg_t *p);
 
+/* ---- pose keypoints (pose.hip): kept detections + their prediction indices -> per frame up to max_per_frame records {det, head, cell} and K
+ * keypoints {x, y, v} each, gathered from the origin cell of the heads' keypoint tensors by the exact rule of include/mars_hip.h ("Pose
+ * keypoints").  Every pointer is device memory.  Two launches: the selection (records), then the gather + decode. */
+#define MHIP_POSE_MAX_PER_FRAME 256
+#define MHIP_POSE_MAX_KPT 32
+typedef struct {
+    const int8_t *kpt[4]; size_t kpt_frame_stride[4]; /* keypoint tensor of head k, frame f: kpt[k] + f * kpt_frame_stride[k] */
+    int kpt_pix_step[4], kpt_ch_step[4];              /* byte of (cell p, channel c) = p * pix_step + c * ch_step */
+    int cells[4], w[4], stride[4];                    /* h * w, grid width and stride of head k: prediction index = cells of the heads before + cell */
+    float scale[4];                                   /* keypoint scale of head k */
+    int nheads;
+    const float *vis;       /* [nheads][256] visibility of byte q at [q + 128] (the host's 1 / (1 + expf(-q * scale))); looked at only with dim == 3 */
+    int num_kpt, dim;       /* K: 1 .. MHIP_POSE_MAX_KPT; D: 2 or 3 */
+    int frames;
+    const void *dets;       /* [frames][det_cap] records of 24 bytes: only conf is read (select_all: may be NULL) */
+    const int *counts;      /* [frames] list lengths (clamped to 0 .. det_cap) */
+    const int *pred;        /* [frames][det_cap] prediction index of every listed record */
+    const int *grid;        /* NULL, or [frames][det_cap][3] = (gx, gy, stride) of listed record i in place of its cell's (the host-pointer form) */
+    int det_cap;
+    float min_conf;
+    int select_all;         /* != 0: every listed record is taken whatever its confidence (the host-pointer form) */
+    int max_per_frame;      /* 1 .. MHIP_POSE_MAX_PER_FRAME */
+    int map, px, py;        /* map != 0: x' = (x - px) * rx, y' = (y - py) * ry */
+    float rx, ry;
+    void *recs;             /* [frames][max_per_frame] records of 12 bytes {det, head, cell} */
+    void *kpts;             /* [frames][max_per_frame][num_kpt] records of 12 bytes {x, y, v} */
+} mhip_pose_t;
+int mhip_pose(const mhip_pose_t *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,7 +159,18 @@ class SegOpts(C.Structure):  # mars_hip_seg_opts_t: zero = default in every fiel
                 ("logit_min", C.c_float), ("min_conf", C.c_float), ("max_per_frame", C.c_int)]
 
 
+POSE_MAX_PER_FRAME, POSE_MAX_KPT = 256, 32                              # MARS_POSE_*
+POSE_DTYPE = np.dtype([("det", "<i4"), ("head", "<i4"), ("cell", "<i4")])  # mars_pose_t
+KPT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("v", "<f4")])          # mars_kpt_t
+
+
+class PoseOpts(C.Structure):  # mars_hip_pose_opts_t: zero = default in every field but the tensor indices and num_kpt
+    _fields_ = [("kpt_tensors", C.c_int * 4), ("num_kpt", C.c_int), ("kpt_dim", C.c_int), ("kpt_scales", C.c_float * 4),
+                ("min_conf", C.c_float), ("max_per_frame", C.c_int)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
 assert C.sizeof(MaskRec) == MASK_DTYPE.itemsize == 24 and C.sizeof(SegOpts) == 52
 assert C.sizeof(TrackRec) == TRACK_DTYPE.itemsize == 8 and C.sizeof(TrackState) == TRACK_STATE_DTYPE.itemsize == 48
 
@@ -205,7 +216,8 @@ EXPORTS = {
                    "mars_hip_identity_results",
                    "mars_hip_tracker_create", "mars_hip_tracker_reset", "mars_hip_tracker_free", "mars_hip_tracker_read",
                    "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track",
-                   "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks"],
+                   "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks",
+                   "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -324,6 +336,12 @@ def lib():
     L.mars_hip_mask_ms.argtypes = [P(MarsModel)]
     L.mars_yolo_masks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
                                   C.c_void_p, C.c_void_p]
+    L.mars_hip_detect_pose_device.argtypes = [P(MarsModel), P(YoloDflHeads), P(PoseOpts)]
+    L.mars_hip_pose_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int)]
+    L.mars_hip_detect_pose.argtypes = [P(MarsModel), P(YoloDflHeads), P(PoseOpts), C.c_void_p, P(C.c_int), C.c_void_p, C.c_void_p]
+    L.mars_hip_pose_ms.restype = C.c_float
+    L.mars_hip_pose_ms.argtypes = [P(MarsModel)]
+    L.mars_yolo_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -651,12 +669,13 @@ class DeviceBuffer:
             pass
 
 
-SYNTH_HEADS = {"anchor": 0, "dfl": 1, "seg": 2}  # MARS_SYNTH_HEAD_*
+SYNTH_HEADS = {"anchor": 0, "dfl": 1, "seg": 2, "pose": 3}  # MARS_SYNTH_HEAD_*
 
 
 def synth_model(width_x16=8, depth_x3=1, input_hw=640, float32=False, nchw_int8=False, seed=1, tiny=False, vary_scales=False, head="anchor"):
     """Bytes of a synthetic well-formed .mars graph (mars_synth_model; head="dfl": mars_synth_model_head with the anchor-free DFL
-    Detect head, int8 only; head="seg": that head plus mask coefficients and prototypes, see seg_twin_tensors)."""
+    Detect head, int8 only; head="seg": that head plus mask coefficients and prototypes, see seg_twin_tensors; head="pose": the DFL head
+    plus keypoint tensors of 17 x 3 channels, see pose_twin_tensors)."""
     o = SynthOpts(width_x16, depth_x3, input_hw, int(float32), int(nchw_int8), seed, int(tiny), int(vary_scales))
     if head == "anchor":
         make = lib().mars_synth_model
@@ -798,6 +817,46 @@ def unpack_masks(words, pw):
     w = np.ascontiguousarray(words, dtype="<u4")
     bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[:-1] + (w.shape[-1] * 4,)), axis=-1, bitorder="little")
     return bits[..., :pw].astype(bool)
+
+
+def pose_twin_tensors(file_bytes):
+    """the keypoint tensors of a synth_model(head="pose") file, found by the names the writer gives them (host only): the tensor index per
+    head, by stride.  KeyError if the file has no such tensors."""
+    b = bytes(file_bytes)
+    hdr = MarsHeader.from_buffer_copy(b[:C.sizeof(MarsHeader)])
+    names = {}
+    for i in range(hdr.num_tensors):
+        o = 76 + 124 * i
+        names[b[o + 4:o + 64].split(b"\0")[0].decode()] = i
+    return [names["pose.kpt%d" % k] for k in range(3)]
+
+
+def pose_opts(kpts, num_kpt=17, kpt_dim=0, kpt_scales=None, min_conf=0.0, max_per_frame=0):
+    """mars_hip_pose_opts_t.  kpts: the keypoint tensor index of every DFL head, in the heads' order; num_kpt, kpt_dim: K and D (0: 3);
+    kpt_scales: None (the tensors' own), one number for every head or a list"""
+    o = PoseOpts()
+    for k, t in enumerate(kpts):
+        o.kpt_tensors[k] = int(t)
+    o.num_kpt, o.kpt_dim = int(num_kpt), int(kpt_dim)
+    if kpt_scales is not None:
+        for k, x in enumerate(kpt_scales if isinstance(kpt_scales, (tuple, list)) else [kpt_scales] * 4):
+            o.kpt_scales[k] = float(x)
+    o.min_conf, o.max_per_frame = float(min_conf), int(max_per_frame)
+    return o
+
+
+def keypoints(rows, K, D, gx, gy, stride, s):
+    """mars_yolo_keypoints: rows int8 [n][K * D] (one row per detection), gx, gy, stride int [n] (every row's cell and stride), s the
+    keypoint scale -> KPT_DTYPE [n][K]; host arrays in and out, runs on the GPU"""
+    a = np.ascontiguousarray(rows, dtype=np.int8)
+    n = len(a)
+    g = [np.ascontiguousarray(v, dtype=np.int32) for v in (gx, gy, stride)]
+    assert (a.shape == (n, K * D) or (n == 0 and a.size == 0)) and all(v.shape == (n,) for v in g)
+    kp = np.zeros((n, K), dtype=KPT_DTYPE)
+    rc = lib().mars_yolo_keypoints(a.ctypes.data, n, int(K), int(D), g[0].ctypes.data, g[1].ctypes.data, g[2].ctypes.data, float(s), kp.ctypes.data)
+    if rc != 0:
+        raise ValueError("mars_yolo_keypoints refused its arguments or failed (%d)" % rc)
+    return kp
 
 
 def compile_onnx(onnx_bytes, float32=False, nhwc=False, verbose=False):
@@ -1193,6 +1252,37 @@ class Model:
         """detect_seg_device + detect_results + mask_results (mars_hip_detect_seg): (a record array per frame, records, words, PW)"""
         self.detect_seg_device(seg, heads, **kw)
         return (self.detect_results(),) + self.mask_results()
+
+    def detect_pose_device(self, pose, heads=None, **kw):
+        """DFL decode + NMS + pose keypoints, results stay in HBM (mars_hip_detect_pose_device).  pose: pose_opts(); heads and the keywords
+        as for yolo_dfl_heads()"""
+        rc = lib().mars_hip_detect_pose_device(self.p, C.byref(yolo_dfl_heads(heads, **kw)), C.byref(pose) if pose is not None else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_pose_device")
+        self._pose_max = pose.max_per_frame or 32
+
+    def pose_results(self):
+        """the keypoints the last detect_pose_device left in HBM (mars_hip_pose_results): (records POSE_DTYPE [batch][max_per_frame],
+        keypoints KPT_DTYPE [batch][max_per_frame][K])"""
+        k = C.c_int()
+        rc = lib().mars_hip_pose_results(self.p, None, None, C.byref(k))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_pose_results")
+        recs = np.zeros((self.batch, self._pose_max), dtype=POSE_DTYPE)
+        kpts = np.zeros((self.batch, self._pose_max, k.value), dtype=KPT_DTYPE)
+        rc = lib().mars_hip_pose_results(self.p, recs.ctypes.data, kpts.ctypes.data, None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_pose_results")
+        return recs, kpts
+
+    def detect_pose(self, pose, heads=None, **kw):
+        """detect_pose_device + detect_results + pose_results (mars_hip_detect_pose): (a record array per frame, records, keypoints)"""
+        self.detect_pose_device(pose, heads, **kw)
+        return (self.detect_results(),) + self.pose_results()
+
+    def pose_ms(self):
+        """device time (ms) of the keypoint stage of the last detect_pose_device (mars_hip_pose_ms); < 0: not available"""
+        return float(lib().mars_hip_pose_ms(self.p))
 
     def detect_results(self):
         """the detections the last detect_device / detect_heads_device / detect_dfl_device left in HBM (mars_hip_detect_results)"""
