@@ -494,6 +494,7 @@ static inline bool conv_i8_direct_rows(const mhip_conv_i8_t *p) { // NHWC rows s
 bool conv_i8_patch_ok(const mhip_conv_i8_t *p, int th, int *ring);
 int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th); // -1: not eligible
 int conv_i8_pre_tile_rows(const mhip_conv_i8_t *p);                 // fused bottleneck: tallest tile that fits, 0 = none
+int conv_i8_post_tile_rows(const mhip_conv_i8_t *p);                // fused cv3 (post_* fields): likewise
 // conv_i8_rows.hip: whole-row tiles, patch-staged input, streamed weights, one persistent workgroup per CU (variant 20)
 bool conv_i8_rows_ok(const mhip_conv_i8_t *p);
 int conv_i8_launch_rows(const mhip_conv_i8_t *p); // -1: not eligible

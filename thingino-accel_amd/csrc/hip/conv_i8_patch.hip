@@ -77,7 +77,20 @@ __device__ __forceinline__ void barrier_lds() {
 // included, zero where the pixel lies outside the image (the k x k convolution's SAME padding applies to t) -- into a
 // second patch buffer, and the K loop reads that one: t never goes to HBM.  The 1x1's weights ([in_c][64], K padded
 // with zeros) and its half-step table (LDS bytes 512..1023) stay resident like the main weights.
-template <int TH, int BN, bool HAS_LUT, bool PRE = false>
+//
+// POST (C3's cv3 inside the 3x3 that feeds it, stride 1, out_c = BN = 32 / 64): the tile's result u is the first half of the
+// never-materialised concat({u, y2}) that only cv3, a 1x1 over 2 * BN channels, reads.  After a tile row's requant_pack the lane
+// (pixel frow, group g) holds the 4 * WOC consecutive channels g * 4 * WOC .. of u as packed dwords: for BN 64 that is the
+// 16-byte B-operand chunk g of cv3's first K step, and the same pixel's 16 bytes of y2 are chunk g of the second; for BN 32 the
+// lane's 8 bytes of u and its 8 bytes of y2 together are chunk g of cv3's only K step (the host lays cv3's weights out in that
+// K order: mhip_conv_i8_post_pack).  No halo: exactly the values the two launches requantise.  cv3's weights ([K steps][2 * BN
+// rows][64], rows permuted so that a lane's results are consecutive channels), its bias rows and its half-step table (LDS
+// bytes 512..1023, the slot PRE uses) stay resident; u itself is never stored.
+// y2 travels like the residual operand (wave-private LDS-DMA rows in the SAME staging area): without an Add it is requested
+// at the tile's start; with one, after the Add's rows have been read back into registers -- it is then the youngest
+// vector-memory operation when the wave needs it, so that wait is a full one, at the END of the tile (the next patch was
+// issued before the K loop and is due at the next tile's start anyway; no patch is drained before a tile's first MFMA).
+template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false>
 __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p, const int k64, const int tiles_x,
                                                           const int tiles_y, const unsigned ntiles_all, const int PH,
                                                           const int PW, const int PWP, const int PWH, const int nblk,
@@ -92,12 +105,15 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     uint8_t *slut = (uint8_t *)dynlds; // LDS byte address 0 (requant_pack LUT0)
     lds_base_must_be_zero(dynlds);
     const int nks = k64 / BK;
-    constexpr int LB = LUTB + (PRE ? 512 : 0);             // PRE: the 1x1's table behind the main one
+    constexpr int NPO = 2 * BN;                            // POST: cv3's input and output channels
+    constexpr int LB = LUTB + ((PRE || POST) ? 512 : 0);   // PRE / POST: the 1x1's table behind the main one
     int *dutab = (int *)(dynlds + LB);                     // [nks][4] unit offsets of the K chunks
     int8_t *wl = dynlds + LB + ((nks * 16 + 255) & ~255);   // [nks][BN][64], swizzled like the ring tiles
     const int patch_bytes = nblk * 1024;                   // whole 1 KB blocks (one wave-instruction of LDS-DMA each)
     int8_t *w1l = wl + nks * BN * BK;                      // PRE: [in_c][64] weights of the 1x1
-    int8_t *patch0 = w1l + (PRE ? p.in_c * BK : 0);
+    int8_t *pwl = w1l;                                     // POST: [NPO / 64][NPO][64] weights of cv3, then its NPO bias rows
+    const int *pbl = (const int *)(pwl + NPO * NPO);
+    int8_t *patch0 = w1l + (PRE ? p.in_c * BK : 0) + (POST ? NPO * NPO + NPO * 4 : 0);
     int8_t *tpatch = patch0 + ring * patch_bytes;          // PRE: the patch of t
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -121,6 +137,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
         else if (tid < 64) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.lut)[tid];
     }
     if (PRE && tid >= 128) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.pre_lut2)[tid - 128]; // LDS 512..1023
+    if (POST) {
+        if (tid >= 128) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.post_lut2)[tid - 128];
+        if (tid < NPO) ((int *)(pwl + NPO * NPO))[tid] = ((const int *)(p.post_w + NPO * NPO))[tid];
+    }
     // K chunk table: chunk (ks, f) -> kernel row ky, column kx, channel chunk
     const int rowbytes = p.kw * C, kbytes = p.kh * rowbytes;
     for (int i = tid; i < nks * 4; i += NTHREADS) {
@@ -146,6 +166,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
         }
         if (PRE)
             for (int g = wv; g < C / 16; g += 4) glds16(p.pre_w + (size_t)(g * 16 + (lane >> 2)) * BK + schunk * 16, w1l + g * 16 * BK);
+        if (POST) // the host's image is the LDS layout: a straight copy, 1 KB per instruction
+            for (int i = wv; i < NPO * NPO / 1024; i += 4) glds16(p.post_w + i * 1024 + lane * 16, pwl + i * 1024);
     }
     // this lane's units of the patch DMA: instruction n of wave wv fills the 1 KB block n*4 + wv = physical units
     // (n*4+wv)*64 + lane; blocks at or beyond nblk do not exist (that instruction is not issued)
@@ -210,16 +232,37 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
             }
     };
 
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)out_bytes, 0x00020000);
+    // (POST: the stores go to cv3's output, out_bytes is its extent)
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(POST ? p.post_out : p.out, 0, (int)out_bytes, 0x00020000);
     // the residual operand of a fused Add has the output's layout: same offsets, same extent
     const bool has_add = p.add != nullptr;
     // residual staging: per wave WPX rows of 64 lanes x 16 bytes (BN 64) or 2 x 64 lanes x 4 bytes (BN 32), behind the patches
     constexpr int RROW = WOC == 4 ? 1024 : 512;
     constexpr int NRI = WOC == 4 ? WPX : 2 * WPX;   // LDS-DMA instructions per wave and tile for it
     int8_t *rstage = patch0 + (ring + (PRE ? 1 : 0)) * patch_bytes + wv * (WPX * RROW);
-    const int NR = has_add ? NRI : 0;
     const int frow = lane & 15, fchunk = lane >> 4;
     const int chan = (lane >> 4) * (4 * WOC);
+    const int NR = has_add || POST ? NRI : 0;
+    // vector-memory operations of a tile behind its patch request: the stores (POST: cv3's, 16 bytes each), and y2's rows where an Add
+    // went through the staging area first
+    const int ntail = POST ? (has_add ? NRI : 0) + WPX * (NPO / 64) : NST;
+    const int ppstride = p.post_out_pix_stride ? p.post_out_pix_stride : NPO;
+    // POST: one staging row per tile row from a dense NHWC tensor of BN channels (the Add's operand, y2): this lane's 4 * WOC bytes
+    auto issue_rows = [&](const int8_t *base, size_t fstride, int tx, int ty, unsigned f) {
+#pragma unroll
+        for (int u = 0; u < WPX; u++) {
+            const int oy = ty * TH + wv * WPX + u, ox = tx * PT_TW + frow;
+            const int8_t *src = oy < p.out_h && ox < p.out_w ? base + (size_t)f * fstride + ((size_t)(oy * p.out_w + ox) * BN + (size_t)chan) : zeros;
+            if (WOC == 4) {
+                glds16(src, rstage + u * RROW);
+            } else {
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                                 (__attribute__((address_space(3))) void *)(rstage + u * RROW), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 4),
+                                                 (__attribute__((address_space(3))) void *)(rstage + u * RROW + 256), 4, 0, 0);
+            }
+        }
+    };
     const int pstride = p.out_pix_stride ? p.out_pix_stride : p.out_c;
     const int lo = p.relu ? 0 : -128;
     const uint8_t *lut128 = slut + 128;
@@ -273,7 +316,18 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
 #pragma unroll
             for (int q = 0; q < WOC; q++) xw[u][q] = 0;
         }
-        if (has_add) {
+        if (POST) {
+            // voffs: cv3's output (this lane's NPO / 4 consecutive channels of its pixel); u is not stored
+#pragma unroll
+            for (int u = 0; u < WPX; u++) {
+                const int oy = ty * TH + wv * WPX + u, ox = tx * PT_TW + frow;
+                const unsigned off = f * (unsigned)p.post_out_stride + (unsigned)(oy * p.out_w + ox) * (unsigned)ppstride +
+                                     (unsigned)(p.post_out_ch_off + (lane >> 4) * (NPO / 4));
+                voffs[u] = oy < p.out_h && ox < p.out_w ? (int)off : -1;
+            }
+            if (has_add) issue_rows(p.add, p.out_stride, tx, ty, f);
+            else issue_rows(p.post_in, p.post_in_stride, tx, ty, f);
+        } else if (has_add) {
 #pragma unroll
             for (int u = 0; u < WPX; u++) {
                 const int8_t *src = voffs[u] >= 0 ? p.add + (unsigned)voffs[u] : zeros;
@@ -302,12 +356,12 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 pn = npw;
             }
             // book-keeping for the NEXT tile: its patch is the second oldest now
-            const int after = NR + pn + NST;
+            const int after = NR + pn + ntail;
             yg0 = yg1 + after;
             yg1 = yg2 + after;
-            yg2 = NST; // the patch issued just now (if any): only this tile's stores follow it
-            if (D == 1) yg0 = NST;
-            if (D == 2) yg1 = NST;
+            yg2 = ntail; // the patch issued just now (if any): only this tile's stores (POST with an Add: and y2's rows) follow it
+            if (D == 1) yg0 = ntail;
+            if (D == 2) yg1 = ntail;
             pn_last = pn;
         } else {
             // one patch buffer: every wave must be past its reads of the previous tile before the buffer is refilled
@@ -438,6 +492,16 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 }
             }
         }
+        uint32_t pku[POST ? WPX : 1][WOC]; // POST: the packed rows of u, cv3's first operand
+        if (POST && has_add) {
+            // the Add's rows are in registers (the wait threads them: no read is left in flight): the staging area takes y2's
+#pragma unroll
+            for (int u = 0; u < WPX; u++) {
+                if constexpr (WOC == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[u][0]), "+v"(xw[u][1]), "+v"(xw[u][2]), "+v"(xw[u][3])::"memory");
+                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[u][0]), "+v"(xw[u][1])::"memory");
+            }
+            issue_rows(p.post_in, p.post_in_stride, tx, ty, f);
+        }
 #pragma unroll
         for (int u = 0; u < WPX; u++) {
             uint32_t pk[WOC];
@@ -455,11 +519,49 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 if (fast) requant_pack<WOC * 4, HAS_LUT, true, true, false, true>(a, p.cs, lo, lut128, pk);
                 else requant_pack<WOC * 4, HAS_LUT, true, true>(a, p.cs, lo, lut128, pk);
             }
+            if (POST) {
+#pragma unroll
+                for (int q = 0; q < WOC; q++) pku[POST ? u : 0][q] = pk[q];
+                continue;
+            }
             const int voff = voffs[u];
             if (WOC == 4)
                 __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]}, orsrc, voff, 0, 0);
             else if (WOC == 2)
                 __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk[0], (int)pk[WOC > 1 ? 1 : 0]}, orsrc, voff, 0, 0);
+        }
+        if (POST) {
+            // y2's rows: requested at the tile's start and waited for above (no Add: they took the Add's place), or just now
+            if (has_add) wait_vmcnt<0>();
+            else if (D > 0) wait_vmcnt_upto<15>(pn_last);
+#pragma unroll
+            for (int u = 0; u < WPX; u++) {
+                v4i b0, b1 = {0, 0, 0, 0};
+                if (WOC == 4) {
+                    b0 = (v4i){(int)pku[POST ? u : 0][0], (int)pku[POST ? u : 0][1], (int)pku[POST ? u : 0][WOC > 2 ? 2 : 0], (int)pku[POST ? u : 0][WOC > 3 ? 3 : 0]};
+                    b1 = *(const v4i *)(rstage + u * RROW + lane * 16);
+                } else {
+                    b0 = (v4i){(int)pku[POST ? u : 0][0], (int)pku[POST ? u : 0][WOC > 1 ? 1 : 0], *(const int *)(rstage + u * RROW + lane * 4),
+                               *(const int *)(rstage + u * RROW + 256 + lane * 4)};
+                }
+#pragma unroll
+                for (int h = 0; h < NPO / 64; h++) { // 16 consecutive output channels of this lane per round
+                    int a[16];
+#pragma unroll
+                    for (int s4 = 0; s4 < 4; s4++) {
+                        const int row = (h * 4 + s4) * 16;
+                        v4i c = *(const v4i *)(pbl + row + fchunk * 4);
+                        c = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const v4i *)(pwl + lds_off(row + frow, fchunk)), b0, c, 0, 0, 0);
+                        if (WOC == 4) c = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const v4i *)(pwl + NPO * BK + lds_off(row + frow, fchunk)), b1, c, 0, 0, 0);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) a[s4 * 4 + e] = c[e];
+                    }
+                    uint32_t pk4[4];
+                    requant_pack_pre<16>(a, p.post_cs, pk4);
+                    const int voff = voffs[u] >= 0 ? voffs[u] + h * 16 : -1;
+                    __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)pk4[0], (int)pk4[1], (int)pk4[2], (int)pk4[3]}, orsrc, voff, 0, 0);
+                }
+            }
         }
 #ifdef PATCH_STAMPS
         STAMP(st4);
@@ -518,10 +620,21 @@ static bool patch_geom(const mhip_conv_i8_t *p, int th, patch_geom_t *g) {
     if (g->nblk > 4 * PT_NIMAX) return false;
     const bool pre = p->pre_w != nullptr; // + the 1x1's table, its weights and the patch of its output
     if (pre && (s != 1 || (C != 32 && C != 64) || !p->pre_bias || !p->pre_lut2 || !p->lut2)) return false;
+    // a following 1x1 (C3's cv3): + its table, its weights and bias rows; y2's rows share the residual staging rows.  The whole result is one
+    // channel tile, dense; cv3 writes 2 * bn channels per pixel, 16-byte aligned, within 31-bit offsets
+    const bool post = p->post_w != nullptr;
+    if (post) {
+        const long ppstride = p->post_out_pix_stride ? p->post_out_pix_stride : 2 * g->bn;
+        if (pre || s != 1 || p->out_c != g->bn || p->oc_pad != g->bn || p->out_pix_stride || p->out_ch_off || !p->lut2 || !p->post_lut2 || !p->post_in ||
+            !p->post_out || ((p->post_out_pix_stride | p->post_out_ch_off) & 15) || p->post_out_pix_stride < 0 || p->post_out_ch_off < 0 ||
+            ppstride < p->post_out_ch_off + 2 * g->bn ||
+            (long)(p->frames - 1) * (long)p->post_out_stride + (long)p->out_h * p->out_w * ppstride > 0x7fffffffL)
+            return false;
+    }
     const size_t pb = (size_t)g->nblk * 1024;
-    const size_t radd = p->add ? (size_t)4 * (th / 4) * (g->bn == 64 ? 1024 : 512) : 0; // residual staging rows of the 4 waves
-    const size_t fixed = LUTB + (pre ? 512 + (size_t)C * BK + pb : 0) + (((size_t)g->nks * 16 + 255) & ~(size_t)255) +
-                         (size_t)g->nks * g->bn * BK + radd;
+    const size_t radd = p->add || post ? (size_t)4 * (th / 4) * (g->bn == 64 ? 1024 : 512) : 0; // residual staging rows of the 4 waves
+    const size_t fixed = LUTB + (pre ? 512 + (size_t)C * BK + pb : 0) + (post ? 512 + (size_t)4 * g->bn * g->bn + (size_t)8 * g->bn : 0) +
+                         (((size_t)g->nks * 16 + 255) & ~(size_t)255) + (size_t)g->nks * g->bn * BK + radd;
     const size_t budget = patch_lds_budget(g->bn);
     if (fixed + pb > budget) return false;
     // as many patch buffers as the budget holds, at most 4 (three patches in flight behind the one being computed);
@@ -537,9 +650,13 @@ static bool patch_geom(const mhip_conv_i8_t *p, int th, patch_geom_t *g) {
     return true;
 }
 
-template <int TH, int BN, bool HAS_LUT, bool PRE = false>
+static inline long post_out_bytes(const mhip_conv_i8_t *p) { // bytes from p->post_out to the end of the last pixel row cv3 can write
+    const long ppstride = p->post_out_pix_stride ? p->post_out_pix_stride : 2 * p->out_c;
+    return (long)(p->frames - 1) * (long)p->post_out_stride + (long)p->out_h * p->out_w * ppstride;
+}
+template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false>
 static int launch_patch_t(const mhip_conv_i8_t *p, int k64, const patch_geom_t &g) {
-    auto kern = conv_i8_patch<TH, BN, HAS_LUT, PRE>;
+    auto kern = conv_i8_patch<TH, BN, HAS_LUT, PRE, POST>;
     // workgroups the device holds at once at THIS layer's LDS size (small patches fit 3-4 per CU), cached per size
     static int cus = 0;
     static size_t slots_lds[8];
@@ -583,7 +700,7 @@ static int launch_patch_t(const mhip_conv_i8_t *p, int k64, const patch_geom_t &
     hipLaunchKernelGGL(kern, dim3(gx, noc), dim3(NTHREADS), g.lds, mhip_stream_native(), *p, k64,
                        g.tiles_x, g.tiles_y, ntiles, g.PH, g.PW, g.PWP, g.PWH, g.nblk, (const int8_t *)mhip_zero_page(),
                        make_fastdiv((unsigned)g.tiles_x), make_fastdiv((unsigned)g.tiles_y), make_fastdiv((unsigned)g.PWP),
-                       (unsigned)persist_out_bytes(p), g.ring, xmap,
+                       (unsigned)(POST ? post_out_bytes(p) : persist_out_bytes(p)), g.ring, xmap,
                        in_extent_bytes(p) <= 0x7fffffffL ? (unsigned)in_extent_bytes(p) : 0u);
     return mhip_check(hipGetLastError(), "conv_i8_patch launch");
 }
@@ -599,8 +716,9 @@ int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th) {
     patch_geom_t g;
     if (!patch_geom(p, th, &g)) return -1;
 #define PATCH(T, B)                                                                       \
-    (p->pre_w ? launch_patch_t<T, B, true, true>(p, k64, g)                               \
-              : (p->lut ? launch_patch_t<T, B, true>(p, k64, g) : launch_patch_t<T, B, false>(p, k64, g)))
+    (p->post_w ? launch_patch_t<T, B, true, false, true>(p, k64, g)                       \
+     : p->pre_w ? launch_patch_t<T, B, true, true>(p, k64, g)                             \
+                : (p->lut ? launch_patch_t<T, B, true>(p, k64, g) : launch_patch_t<T, B, false>(p, k64, g)))
     if (th == 16) return g.bn == 64 ? PATCH(16, 64) : PATCH(16, 32);
     if (th == 8) return g.bn == 64 ? PATCH(8, 64) : PATCH(8, 32);
     return g.bn == 64 ? PATCH(4, 64) : PATCH(4, 32);
@@ -617,4 +735,40 @@ int conv_i8_pre_tile_rows(const mhip_conv_i8_t *p) {
 extern "C" int mhip_conv_i8_pre_ok(const mhip_conv_i8_t *p) {
     if (!p || !p->pre_w || p->nseg > 1 || p->out_nchw) return 0;
     return conv_i8_pre_tile_rows(p) != 0;
+}
+
+// fused cv3 (post_* fields): only the patch-staged kernel evaluates it, and the launch has no other form: the tallest tile that fits
+int conv_i8_post_tile_rows(const mhip_conv_i8_t *p) {
+    patch_geom_t g;
+    for (int th : {16, 8, 4})
+        if (patch_geom(p, th, &g)) return th;
+    return 0;
+}
+extern "C" int mhip_conv_i8_post_ok(const mhip_conv_i8_t *p) {
+    if (!p || !p->post_w || p->pre_w || p->nseg > 1 || p->out_nchw) return 0;
+    return conv_i8_post_tile_rows(p) != 0;
+}
+extern "C" int mhip_conv_i8_post_k(int c, int k) {
+    if (c == 64) return k;
+    return k < 32 ? (k >> 3) * 16 + (k & 7) : ((k - 32) >> 3) * 16 + 8 + (k & 7);
+}
+extern "C" int mhip_conv_i8_post_row(int c, int oc) {
+    const int per = c / 2, g = oc / per, rem = oc - g * per; // a lane group's 2c / 4 consecutive channels
+    return (rem >> 2) * 16 + g * 4 + (rem & 3);
+}
+extern "C" size_t mhip_conv_i8_post_pack(int c, const int8_t *packed, const int32_t *bias, int8_t *out) {
+    if (c != 32 && c != 64) return 0;
+    const int n = 2 * c;
+    const size_t bytes = (size_t)n * n + (size_t)n * 4;
+    if (!packed || !out) return bytes;
+    memset(out, 0, bytes);
+    for (int oc = 0; oc < n; oc++) {
+        const int R = mhip_conv_i8_post_row(c, oc), src = mhip_conv_i8_oc_row(oc, n);
+        for (int k = 0; k < n; k++) {
+            const int pos = mhip_conv_i8_post_k(c, k), ks = pos >> 6, chunk = (pos & 63) >> 4;
+            out[(size_t)(ks * n + R) * BK + (((chunk ^ ((R >> 1) & 2))) << 4) + (pos & 15)] = packed[(size_t)src * n + k];
+        }
+        ((int32_t *)(out + (size_t)n * n))[R] = bias ? bias[src] : 0;
+    }
+    return bytes;
 }

@@ -45,6 +45,7 @@ void plan_switches_read(plan_switches_t *sw, int at_load) {
     sw->no_zero_tail = getenv("MARS_HIP_NO_ZERO_TAIL") != NULL;
     sw->no_vconcat_f32 = getenv("MARS_HIP_NO_VCONCAT_F32") != NULL;
     sw->no_rowpad = getenv("MARS_HIP_NO_ROWPAD") != NULL;
+    sw->no_post = getenv("MARS_HIP_NO_POST") != NULL;
     /* (tests lower the limits to see the per-batch decisions with small tensors) */
     sw->rec_limit = (e = getenv("MARS_HIP_REC_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0xfffffff0u;
     sw->vconcat_limit = (e = getenv("MARS_HIP_VCONCAT_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0x7fffffffu;
@@ -184,6 +185,7 @@ mars_error_t build_plan(mars_model_ext_t *m) {
         fuse_pool_chains(m); /* the first pass that sets chain_out: from here on op_writes() is more than t_out */
         pair_convs(m);
         if (m->sw.fusion >= 2 && !m->no_bottleneck) fuse_bottleneck(m); /* opt-in (level 2); after pairing: a paired launch stays a pair */
+        fuse_post(m);     /* after both: a paired launch stays a pair, an op carrying `pre` never takes `post` (level 2 keeps its plans) */
         pad_output_rows(m);
         virtual_concat_q(m); /* last of the int8 passes: it splits a convolution in two launches over one output tensor */
     } else {
@@ -232,8 +234,8 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
      * alone at a larger batch may fit now) */
     const int rec_replan = (size_t)n > m->rec_max_frames || (m->rec_skipped && n < m->rec_frames);
     m->rec_frames = n;
-    if (m->no_vconcat || m->no_bottleneck || rec_replan) {
-        m->no_vconcat = m->no_bottleneck = 0;
+    if (m->no_vconcat || m->no_bottleneck || m->no_post || rec_replan) {
+        m->no_vconcat = m->no_bottleneck = m->no_post = 0;
         mars_error_t e = build_plan(m);
         if (e == MARS_OK) e = upload_params(m);
         if (e != MARS_OK) return e;
@@ -262,6 +264,20 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
             const size_t in_stride = op->t_in[0] >= 0 ? planned_stride(&m->mt[op->t_in[0]]) : 0;
             if (!conv_i8_pre_fits(op, n, in_stride, planned_stride(&m->mt[op->t_out])) || (blim && (size_t)n > blim)) {
                 m->no_bottleneck = 1;
+                mars_error_t e = build_plan(m);
+                if (e == MARS_OK) e = upload_params(m);
+                if (e != MARS_OK) return e;
+                break;
+            }
+        }
+    /* fused cv3 launches were accepted for one frame: cv3's output is addressed with 31-bit offsets, and the 1x1 is not launched on its own, so a
+     * launch that fails would have no fallback: check every one against THIS batch and plan again without the fusion if one does not fit */
+    if (!m->no_post)
+        for (int i = 0; i + 1 < m->n_ops; i++) {
+            const mars_op_t *op = &m->ops[i];
+            if (op->kind != OP_CONV_I8 || !op->post_next) continue;
+            if (!conv_i8_post_fits(m, op, op + 1, n)) {
+                m->no_post = 1;
                 mars_error_t e = build_plan(m);
                 if (e == MARS_OK) e = upload_params(m);
                 if (e != MARS_OK) return e;
@@ -431,6 +447,8 @@ static int describe_op_full(const mars_op_t *o, char *line, size_t cap, int k) {
     ADD(" w_off %zd b_off %zd lut_off %zd lut2_off %zd s_off %zd w2_off %zd rows %d planes %d w3_off %zd stem %d blob %zd %zd", (ssize_t)o->w_off, (ssize_t)o->b_off,
         (ssize_t)o->lut_off, (ssize_t)o->lut2_off, (ssize_t)o->s_off, (ssize_t)o->w2_off, o->w2_rows, o->w2_planes, (ssize_t)o->w3_off, o->w3_stem, (ssize_t)o->w_blob_off[0],
         (ssize_t)o->w_blob_off[1]);
+    ADD(" post_next %d", o->post_next);
+    if (o->post_next) ADD(" %zd", (ssize_t)o->post_w_off);
     ADD(" pre %d", o->pre);
     if (o->pre) ADD(" %zd %zd %zd %a", (ssize_t)o->pre_w_off, (ssize_t)o->pre_b_off, (ssize_t)o->pre_lut2_off, (double)o->pre_cs);
     ADD(" macs %a bytes %a prof_kind %d", o->macs, o->bytes, o->prof_kind);
@@ -459,7 +477,7 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
 #define FLAG(cond, ...) if (cond) k += snprintf(line + k, sizeof line - (size_t)k, __VA_ARGS__)
         FLAG(o->kind == OP_CONV_I8 || o->kind == OP_CONV_F32 || o->kind == OP_CONV_F32_VHEAD, " k%dx%d s%d c%d->%d", o->kh, o->kw, o->sw, o->in_c, o->out_c);
         FLAG(o->nchw, " relayout"); FLAG(o->out_nchw, " planar_store"); FLAG(o->lut_off != NO_OFF, " lut"); FLAG(o->add_t, " add=%d", o->add_t - 1);
-        FLAG(o->nseg, " seg=%d", o->nseg); FLAG(o->pair_next, " pair_next"); FLAG(o->pre, " pre"); FLAG(o->silu_f32, " silu");
+        FLAG(o->nseg, " seg=%d", o->nseg); FLAG(o->pair_next, " pair_next"); FLAG(o->post_next, " post_next"); FLAG(o->pre, " pre"); FLAG(o->silu_f32, " silu");
         FLAG(o->k_limit, " k_limit=%d", o->k_limit); FLAG(o->in_rec, " in_rec=%d", o->in_rec); FLAG(o->out_rec, " out_rec");
         FLAG(o->vc_shift, " view=-%d", o->vc_shift); FLAG(o->vc_n, " vcat=%dx%d", o->vc_n, o->vc_run);
         FLAG(o->rows_only, " rows_only=%d", o->rows_only); FLAG(o->out_byte_off, " out_off=%zu", o->out_byte_off); FLAG(o->chain_n, " chain=%d", o->chain_n);
@@ -485,10 +503,10 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
     if (full) {
         const plan_switches_t *w = &m->sw;
         snprintf(line, sizeof line, "+plan n_ops %d arena_size %zu scratch_per_frame %zu blob_mirror_bytes %zu rec_max_frames %zu rec_skipped %d f32_mode %d | fusion %d"
-                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d rec_limit %zu"
+                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d no_post %d rec_limit %zu"
                  " vconcat_limit %zu bottleneck_limit %zu\n", m->n_ops, m->arena_size, m->scratch_per_frame, m->blob_mirror_bytes, m->rec_max_frames, m->rec_skipped,
                  m->plan_f32_mode, w->fusion, w->no_fuse_lut, w->no_nhwc_internal, w->no_vconcat_q, w->no_pair_f32, w->no_rec, w->no_zero_tail, w->no_vconcat_f32,
-                 w->no_rowpad, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
+                 w->no_rowpad, w->no_post, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
         EMIT();
     }
 #undef EMIT

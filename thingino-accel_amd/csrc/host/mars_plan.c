@@ -689,6 +689,21 @@ int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t o
     return mhip_conv_i8_pre_ok(&p);
 }
 
+/* does the device code take convolution `a` with the 1 x 1 `b` behind it evaluated in the same launch (fuse_post), at this batch?  Geometry and
+ * the planned frame strides only: the operands only need to be non-null */
+int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames) {
+    mhip_conv_i8_t p;
+    if (a->t_in[0] < 0 || a->t_out < 0 || b->t_out < 0) return 0;
+    conv_i8_geometry(a, frames, &p);
+    p.in_stride = planned_stride(&m->mt[a->t_in[0]]); p.out_stride = planned_stride(&m->mt[a->t_out]);
+    p.lut = p.lut2 = p.post_lut2 = (const uint8_t *)a;
+    p.post_w = p.post_in = (const int8_t *)a; p.post_out = (int8_t *)m;
+    if (a->add_t) p.add = (const int8_t *)a;
+    p.post_out_stride = planned_stride(&m->mt[b->t_out]);
+    p.post_out_pix_stride = b->out_pix_stride; p.post_out_ch_off = b->out_ch_off;
+    return mhip_conv_i8_post_ok(&p);
+}
+
 /* ------------------------------------------------------------------ fusion
  * conv -> sigmoid -> mul (SiLU as exported to ONNX) collapses into the conv
  * epilogue: every value of the chain is a function of the conv's int8 result
@@ -1206,6 +1221,54 @@ void fuse_bottleneck(mars_model_ext_t *m) {
         a->kind = -1;
     }
     drop_dead_ops(m);
+    free(readers);
+}
+
+/* C3's cv3 inside the k x k convolution that feeds it: A = the last bottleneck's k x k convolution (with its folded residual Add where there is
+ * one), whose result u only B reads, B = the 1 x 1 right behind it over the virtual concat {u, y2}.  A's launch (conv_i8_patch<POST>) holds a
+ * tile row of u as the B operand of B's first K part the moment it is requantised, reads the same pixels of y2, and stores B's result: u is
+ * never written nor read back, and one launch goes.  Same bytes: B sees exactly the int8 values A would have stored, no halo is involved.
+ * Both ops stay in the plan (as a pair's do): A carries post_next and is launched, B is skipped.  Only where the device code takes it
+ * (mhip_conv_i8_post_ok: 32 / 64 channels in one channel tile, mostly full tiles); a decision on shapes alone -- alloc_batch takes it back for
+ * a batch whose output offsets leave 31 bits (m->no_post). */
+void fuse_post(mars_model_ext_t *m) {
+    if (m->sw.no_post || m->no_post) return;
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
+    for (int i = 0; i + 1 < m->n_ops; i++) {
+        mars_op_t *a = &m->ops[i], *b = &m->ops[i + 1];
+        if (a->kind != OP_CONV_I8 || b->kind != OP_CONV_I8 || a->pre || b->pre || a->post_next || b->post_next || a->pair_next || b->pair_next ||
+            (i > 0 && (m->ops[i - 1].pair_next || m->ops[i - 1].post_next)))
+            continue;
+        const int c = a->out_c, T = a->t_out, O = b->t_out;
+        if ((c != 32 && c != 64) || a->oc_pad != c || a->kh * a->kw < 2 || a->sh != 1 || a->sw != 1 || !a->safe || a->nchw || a->out_nchw || a->nseg ||
+            a->out_pix_stride || a->out_ch_off || a->store_c || a->chain_n || a->in_byte_off || a->out_byte_off || a->lut_off == NO_OFF ||
+            a->lut2_off == NO_OFF || a->n_in >= 4)
+            continue;
+        if (b->kh != 1 || b->kw != 1 || b->sh != 1 || b->sw != 1 || b->pt || b->pl || !b->safe || b->nchw || b->out_nchw || b->add_t || b->chain_n ||
+            b->store_c || b->in_byte_off || b->lut_off == NO_OFF || b->lut2_off == NO_OFF || b->nseg != 2 || b->seg_up || b->seg_t[0] != T ||
+            b->seg_c[0] != c || b->seg_c[1] != c || b->in_c != 2 * c || b->out_c != 2 * c || b->oc_pad != 2 * c || b->row_pad != 2 * c ||
+            b->in_h != a->out_h || b->in_w != a->out_w || b->out_h != a->out_h || b->out_w != a->out_w)
+            continue;
+        const int Y = b->seg_t[1];
+        if (T < 0 || O < 0 || Y < 0 || Y == T || O == T || O == Y || readers[T] != 1 || writers[T] != 1 || m->mt[T].io_in || m->mt[T].io_out ||
+            m->mt[T].is_weight || m->mt[T].tail_read || m->mt[Y].is_weight || m->mt[Y].pix_stride ||
+            m->mt[Y].bytes != (size_t)a->out_h * a->out_w * c || op_reads(a, O) || op_reads(a, Y))
+            continue;
+        if (!conv_i8_post_fits(m, a, b, 1)) continue; /* one frame: alloc_batch asks again for its batch */
+        const size_t bytes = mhip_conv_i8_post_pack(c, NULL, NULL, NULL);
+        const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
+        if (off == NO_OFF) break;
+        mhip_conv_i8_post_pack(c, (const int8_t *)(m->arena_host + b->w_off), b->b_off != NO_OFF ? (const int32_t *)(m->arena_host + b->b_off) : NULL,
+                               (int8_t *)(m->arena_host + off));
+        a->post_next = 1;
+        a->post_w_off = off;
+        a->t_in[a->n_in++] = Y; /* (operand model: the launch reads y2) */
+        m->mt[T].needed = 0;
+        readers[T] = 0;
+        readers[Y]++;
+        i++; /* B is taken */
+    }
     free(readers);
 }
 
@@ -1746,6 +1809,9 @@ void plan_check(mars_model_ext_t *m) {
         else if (o->add_t && !op_reads(o, o->add_t - 1)) why = "add_t is not among t_in";
         else if (o->chain_n && o->t_out != o->chain_out[o->chain_n - 1]) why = "t_out is not the chain's last stage";
         else if (o->pair_next && (i + 1 >= m->n_ops || m->ops[i + 1].kind != o->kind)) why = "pair_next without a mate of its kind";
+        else if (o->post_next && (o->kind != OP_CONV_I8 || i + 1 >= m->n_ops || m->ops[i + 1].kind != OP_CONV_I8 || m->ops[i + 1].nseg != 2 ||
+                                  m->ops[i + 1].seg_t[0] != o->t_out || !op_reads(o, m->ops[i + 1].seg_t[1])))
+            why = "post_next without its 1x1 behind it, or y2 is not among t_in";
         for (int k = 0; !why && k < o->nseg; k++)
             if (!op_reads(o, o->seg_t[k])) why = "a seg_t is not among t_in";
         for (int k = 0; !why && k < o->vc_n; k++)

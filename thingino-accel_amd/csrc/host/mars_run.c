@@ -63,6 +63,7 @@ void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8
     }
     p->cs = op->cs; p->relu = op->relu; p->out_nchw = op->out_nchw;
     p->variant = op->variant;
+    if (op->post_next && op->t_out >= 0) p->out_stride = planned_stride(&m->mt[op->t_out]); /* (never written, so never allocated: the Add's operand has its layout) */
     if (op->add_t && tstride(m, op->add_t - 1) == p->out_stride) {
         p->add = (const int8_t *)tdev(m, op->add_t - 1);
         p->add_s_conv = op->add_s_conv; p->add_s_other = op->add_s_other; p->add_inv = op->add_inv;
@@ -81,6 +82,19 @@ void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8
         }
     }
     if (op->nseg > 1) p->in = p->seg_in[0];
+}
+
+/* a launch that carries post_next: its own record + the 1x1 behind it (fuse_post) */
+static void conv_i8_post_params(const mars_model_ext_t *m, const mars_op_t *op, const mars_op_t *cv3, mhip_conv_i8_t *p) {
+    uint8_t *A = m->arena_dev;
+    conv_i8_params(m, op, p);
+    p->post_w = (const int8_t *)(A + op->post_w_off);
+    p->post_lut2 = A + cv3->lut2_off;
+    p->post_cs = cv3->cs;
+    p->post_in = (const int8_t *)tdev(m, cv3->seg_t[1]); p->post_in_stride = tstride(m, cv3->seg_t[1]);
+    p->post_out = (int8_t *)tdev(m, cv3->t_out); p->post_out_stride = tstride(m, cv3->t_out);
+    if (p->post_out) p->post_out += cv3->out_byte_off;
+    p->post_out_pix_stride = cv3->out_pix_stride; p->post_out_ch_off = cv3->out_ch_off;
 }
 
 static void conv_f32_params(mars_model_ext_t *m, mars_op_t *op, mhip_conv_f32_t *p) {
@@ -339,7 +353,7 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             fprintf(stderr, "Mars: Layer %d execution failed\n", op->layer);
             return (mars_error_t)op->err;
         }
-        mars_op_t *mate = op->pair_next && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
+        mars_op_t *mate = (op->pair_next || op->post_next) && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
         if (wait_tail && ((op->t_out >= 0 && (m->mt[op->t_out].io_out || m->mt[op->t_out].tail_read)) ||
                           (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)))) {
             /* the previous batch's detection tail (auxiliary stream) still reads the graph
@@ -357,7 +371,12 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             op->ev_start = prof_last;
         }
         int rc;
-        if (mate && op->kind == OP_CONV_F32) { /* one grid for both (conv_f32_split's pair form); -2: one after the other */
+        if (mate && op->post_next) { /* cv3 inside this launch (conv_i8_patch<POST>): the plan holds it only where this form runs */
+            mhip_conv_i8_t pa;
+            conv_i8_post_params(m, op, mate, &pa);
+            rc = mhip_conv_i8(&pa);
+            i++; /* the mate has run */
+        } else if (mate && op->kind == OP_CONV_F32) { /* one grid for both (conv_f32_split's pair form); -2: one after the other */
             mhip_conv_f32_t pa, pb;
             conv_f32_params(m, op, &pa);
             conv_f32_params(m, mate, &pb);
@@ -760,6 +779,7 @@ static mars_error_t autotune_model(mars_model_t *model, int reps) {
         mars_op_t *op = &m->ops[i];
         if (op->kind != OP_CONV_I8 || op->nchw) continue;
         if (op->pair_next || (i > 0 && m->ops[i - 1].pair_next)) continue; /* paired launches have one form */
+        if (op->post_next || (i > 0 && m->ops[i - 1].post_next)) continue; /* ... and a fused cv3 goes with the launch its policy picks */
         mhip_conv_i8_t p;
         conv_i8_params(m, op, &p);
         int codes[32];

@@ -103,7 +103,28 @@ typedef struct {
     size_t seg_stride[4];
     int seg_c[4], seg_c0[4];
     int seg_up;                 /* bit k: segment k is read through a 2x2 nearest upsample (its tensor is out_h/2 x out_w/2) */
+    /* optional: a 1x1 stride-1 convolution with a fused SiLU table evaluated on this convolution's RESULT tile while it is still
+     * in registers (C3: cv3 over concat({this result, post_in}), patch-staged kernel only; out_c = c in {32, 64}, the 1x1 maps
+     * 2c -> 2c channels).  The result of this convolution itself is NOT stored (`out` may be NULL; out_stride still is the frame
+     * stride of `add`).  post_w = the image of mhip_conv_i8_post_pack (weights in the kernel's K and row order, then the bias rows);
+     * post_in = the concat's second half, a dense NHWC tensor of c channels; post_out / post_out_* as out / out_* of the 1x1 */
+    const int8_t *post_w;
+    const uint8_t *post_lut2;
+    float post_cs;
+    const int8_t *post_in;  size_t post_in_stride;
+    int8_t *post_out;       size_t post_out_stride;
+    int post_out_pix_stride, post_out_ch_off;
 } mhip_conv_i8_t;
+/* can the convolution described by *p take a following 1x1 (post_* fields) in its launch?  (geometry only, at some tile height) */
+int mhip_conv_i8_post_ok(const mhip_conv_i8_t *p);
+/* Bytes of, and (packed, out != NULL) the content of, the 1x1's image for a fused launch of c = 32 / 64 channels: `packed` / `bias` = the
+ * 1x1's packed weights [oc_pad = 2c][k64 = 2c] and bias rows as every conv_i8 launch reads them (bias NULL = zeros).  Weights: K steps of
+ * 64 bytes x 2c rows x 64 bytes in the kernel's LDS layout (chunk swizzle applied); row s * 16 + g * 4 + r carries output channel
+ * g * (2c / 4) + s * 4 + r; K order: c = 64 natural ({result, post_in}), c = 32 chunk g = [result 8g..8g+7 | post_in 8g..8g+7].
+ * mhip_conv_i8_post_k / _row say where input channel k / output channel oc went (tests).  0 = not such a shape */
+size_t mhip_conv_i8_post_pack(int c, const int8_t *packed, const int32_t *bias, int8_t *out);
+int mhip_conv_i8_post_k(int c, int k);
+int mhip_conv_i8_post_row(int c, int oc);
 /* row of the packed weights / bias that holds output channel oc (channels are permuted so that a lane's
  * results are consecutive channels) */
 int mhip_conv_i8_oc_row(int oc, int oc_pad);
