@@ -333,6 +333,10 @@ size_t mars_synth_model(const mars_synth_opts_t *opts, void *buf, size_t cap);
  * = 51 channels), built behind every box and class branch: the three graph outputs and the detections are the DFL twin's.  The keypoint
  * tensors are internal tensors named "pose.kpt0", "pose.kpt1", "pose.kpt2", each read by one no-op RESHAPE. */
 #define MARS_SYNTH_HEAD_POSE 3
+/* MARS_SYNTH_HEAD_OBB (int8 only, not tiny): the DFL twin plus, per scale, an angle branch (conv3x3 + SiLU, conv3x3 + SiLU, conv1x1 -> 1
+ * channel), built behind every box and class branch: the three graph outputs are the DFL twin's.  The angle tensors are internal tensors
+ * named "obb.ang0", "obb.ang1", "obb.ang2", each read by one no-op RESHAPE. */
+#define MARS_SYNTH_HEAD_OBB 4
 size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap);
 
 /* ------------------------------------------------------- image front-end */
@@ -770,6 +774,83 @@ float mars_hip_pose_ms(mars_model_t *model);
  * (every row is taken: slot i = row i); gx, gy, stride = [n], the cell and stride of every row; s = the keypoint scale (> 0); no mapping.
  * kpts = [n][K].  0, or -1: an argument out of range, no device, or a failed launch. */
 int mars_yolo_keypoints(const int8_t *rows, int n, int K, int D, const int *gx, const int *gy, const int *stride, float s, mars_kpt_t *kpts);
+
+/* ----------------------------------------------------------- Oriented boxes */
+/* The "-obb" sibling of the anchor-free DFL head (YOLOv8-obb style): beside the box and class convolutions every scale has an ANGLE
+ * convolution of 1 channel on the same grid, and rotated rectangles suppress each other by ProbIoU.  These calls decode, sort and suppress
+ * on the device.  float32, every operation rounded on its own (parentheses below give the order), no fused multiply-add, division and
+ * square root correctly rounded: everything is defined to the bit.  The reference has no such head, so nothing here restates it.
+ *
+ * Tables.     Per head, from the angle scale s (the tensor's own desc.scale, or the override; <= 0 or not finite is refused), built on the
+ *             host with its libm and uploaded; for q = -128 .. 127:
+ *               sg[q] = 1.0f / (1.0f + expf((-(float)q) * s));   ang[q] = (sg[q] - 0.25f) * 3.14159265f   (Ultralytics' rule: [-pi/4, 3pi/4))
+ *               cs[q] = cosf(ang[q]);   sn[q] = sinf(ang[q])
+ * Decode.     Prediction order, best class, conf and the side distances dist_l, dist_t, dist_r, dist_b: "anchor-free DFL heads" above.
+ *             With q = the angle byte of the cell:
+ *               xf = (dist_r - dist_l) * 0.5f;   yf = (dist_b - dist_t) * 0.5f
+ *               cx = (((xf * cs) - (yf * sn)) + ((float)gx + 0.5f)) * (float)stride
+ *               cy = (((xf * sn) + (yf * cs)) + ((float)gy + 0.5f)) * (float)stride
+ *               w = (dist_l + dist_r) * (float)stride;   h = (dist_t + dist_b) * (float)stride;   angle = ang[q]
+ *             The first MARS_YOLO_MAX_DET candidates in prediction order are kept.
+ * Order.      Confidence descending, then prediction index ascending (for mars_yolo_obb_nms: position in the caller's list ascending): a
+ *             plain stable order.  The reference demo's unstable exchange sort, which the upright tails reproduce, is NOT part of this
+ *             contract -- the reference has no oriented head.  Confidences are >= 0 and never NaN here (a table of a finite positive scale
+ *             holds none); mars_yolo_obb_nms refuses a list that holds a confidence that is NaN or negative (-0 included).
+ * Covariance. Per box, with cs, sn its angle's cosine and sine (the tables' entries; for mars_yolo_obb_nms cosf(angle), sinf(angle) on the host):
+ *               A = (w * w) / 12.0f;   B = (h * h) / 12.0f
+ *               a = (A * (cs * cs)) + (B * (sn * sn));   b = (A * (sn * sn)) + (B * (cs * cs));   c = (A - B) * (cs * sn)
+ *               v = (a * b) - (c * c);   d = v > 0 ? v : 0.0f          (a NaN v gives 0)
+ * Pair.       For sorted boxes i < j of one class (of any class under MARS_OBB_AGNOSTIC), ProbIoU without a log or a second exp:
+ *               sa = a_i + a_j;  sb = b_i + b_j;  sc = c_i + c_j;  dx = x_i - x_j;  dy = y_i - y_j
+ *               den = (sa * sb) - (sc * sc)
+ *               t1 = (((sa * (dy * dy)) + (sb * (dx * dx))) / den) * 0.25f
+ *               t2 = (((sc * (-dx)) * dy) / den) * 0.5f
+ *               X = den / (4.0f * sqrtf(d_i * d_j))
+ *             i suppresses j iff  expf(-(t1 + t2)) > E * sqrtf(X),  E = (float)(1.0 - (1.0 - (double)T) * (1.0 - (double)T)) from
+ *             nms_thresh T, computed once on the host.  This is 1 - sqrt(1 - exp(-(t1 + t2 + 0.5 log X))) > T rearranged.  expf is the host
+ *             libm's, bit for bit (csrc/expf_exact.h on the device).  A comparison with a NaN operand is false: zero-area boxes suppress
+ *             nothing and are not suppressed.
+ * Greedy.     In sorted order; suppressed boxes suppress nothing.
+ * Letterbox.  With src_w > 0 in the DFL options, after NMS: x' = (cx - px) * rx, y' = (cy - py) * ry (the boxes' rule and numbers);
+ *             w' = w * rx and h' = h * rx -- BOTH by rx, they lie along the box's own axes; the angle is unchanged.
+ * Result.     mars_obb_t per kept box, in sorted order; pred = its prediction index (cells of the heads before its head + its cell).
+ * Detections. The model's ordinary detection list is filled too, index-aligned with the obb records, so mars_hip_detect_results and the
+ *             crop, label and track stages work unchanged: entry i = the ENCLOSING UPRIGHT RECTANGLE of obb record i -- same x, y, conf,
+ *             cls;  w_e = (w * |cs|) + (h * |sn|);  h_e = (w * |sn|) + (h * |cs|), from the mapped w, h.
+ * Not covered: the pipelined mars_hip_pipe_* path; rotated crops (the crop stage gets the enclosing rectangle); an exact polygon IoU; a
+ *   file-level finder (callers name the angle tensors); float32 tensors; anchor-based obb heads. */
+typedef struct { float x, y, w, h, conf; int cls; float angle; int pred; } mars_obb_t; /* 32 bytes */
+#define MARS_OBB_AGNOSTIC 1u /* boxes of different classes suppress each other too */
+/* Zero-initialise; zero means default in every field but the tensor indices. */
+typedef struct {
+    int angle_tensors[4];   /* TENSOR index per DFL head, in the heads' order: int8, 1 channel, on the grid of its head's box tensor */
+    float angle_scales[4];  /* 0: the tensor's own desc.scale */
+    unsigned flags;         /* MARS_OBB_AGNOSTIC */
+} mars_hip_obb_opts_t;
+/* Oriented decode + sort + rotated NMS of the model's current batch; results stay in HBM.  Enqueues only: streams and events as
+ * mars_hip_detect_dfl_device (the auxiliary stream behind the graph; the next run's layers that write a box, class or angle tensor wait for
+ * the decode).  The obb records live in a block of their own: a mask or pose call on the same model leaves them alone and the reverse (the
+ * detections are those of the last call).  MARS_ERR_INVALID_TENSOR: what mars_hip_detect_dfl refuses; no options; an angle tensor that is
+ * not int8, has not exactly 1 channel, whose grid differs from its head's, that is only partly written or has no addressable bytes; an
+ * effective angle scale <= 0 or not finite; unknown flag bits; a model with an open pipe. */
+mars_error_t mars_hip_detect_obb_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_obb_opts_t *obb);
+/* Waits.  boxes = [batch][MARS_YOLO_MAX_DET], counts = [batch]; either may be NULL.  MARS_ERR_INVALID_TENSOR before any obb call on this model. */
+mars_error_t mars_hip_obb_results(mars_model_t *model, mars_obb_t *boxes, int *counts);
+/* mars_hip_detect_obb_device + mars_hip_detect_results (dets, counts: the enclosing rectangles) + mars_hip_obb_results (boxes). */
+mars_error_t mars_hip_detect_obb(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_obb_opts_t *obb, mars_det_t *dets,
+                                 int *counts, mars_obb_t *boxes);
+/* Device time (ms) of the whole stage (decode + sort + NMS) of the last mars_hip_detect_obb_device call, from events on the auxiliary
+ * stream; waits for it.  < 0: not available. */
+float mars_hip_obb_ms(mars_model_t *model);
+/* Host pointers in and out, the same sort + suppression kernel on the GPU; waits.  boxes = [n], 0 <= n <= MARS_YOLO_MAX_DET; cs, sn =
+ * cosf(angle), sinf(angle) on the host; thresh = T (0: 0.45); no mapping; pred is carried.  The kept boxes are written back in order; returns
+ * their number, or -1: an argument out of range, unknown flag bits, a confidence that is NaN or negative, no device, or a failed launch. */
+int mars_yolo_obb_nms(mars_obb_t *boxes, int n, float thresh, unsigned flags);
+/* Pure host code: the four corners of a box, xy = {x0, y0, .. x3, y3}, float32, one rounding per operation, cs = cosf(angle), sn = sinf(angle):
+ *   ux = (w * 0.5f) * cs;  uy = (w * 0.5f) * sn;  vx = (h * 0.5f) * sn;  vy = (h * 0.5f) * cs
+ *   corner 0 = (x - ux + vx, y - uy - vy);  1 = (x + ux + vx, y + uy - vy);  2 = (x + ux - vx, y + uy + vy);  3 = (x - ux - vx, y - uy + vy),
+ * each sum left to right. */
+void mars_yolo_obb_corners(const mars_obb_t *box, float xy[8]);
 
 #ifdef __cplusplus
 }

@@ -211,6 +211,14 @@ typedef struct mars_model_ext {
     float pose_lut_scale[4];           /* the scales the block's visibility tables were built from */
     int pose_lut_n;                    /* tables that are up (0: none) */
     void *ev_pose[2];   /* timing events around the keypoint stage's launches on the auxiliary stream */
+    /* oriented boxes (mars_obb.c) */
+    void *obb_dev;      /* one block on the device: the angle tables [4][768] x float, kept and candidate counts [frames] x int each, candidate
+                         * records [frames][MARS_YOLO_MAX_DET] x mars_obb_t, their (cos, sin) pairs, kept records [frames][MARS_YOLO_MAX_DET] x mars_obb_t */
+    size_t obb_bytes, obb_cnt_off, obb_out_off;
+    int obb_frames;                   /* of the last obb call; 0: there was none */
+    float obb_lut_scale[4];           /* the scales the block's angle tables were built from */
+    int obb_lut_n;                    /* tables that are up (0: none) */
+    void *ev_obb[2];    /* timing events around the oriented stage's launches on the auxiliary stream */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -287,6 +295,9 @@ MARS_INTERNAL void mars_seg_release(mars_model_ext_t *m); /* the mask results of
 
 /* mars_pose.c */
 MARS_INTERNAL void mars_pose_release(mars_model_ext_t *m); /* the keypoint results of a model whose device state goes away */
+
+/* mars_obb.c */
+MARS_INTERNAL void mars_obb_release(mars_model_ext_t *m); /* the oriented results of a model whose device state goes away */
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

@@ -98,6 +98,7 @@ static void free_device_state(mars_model_ext_t *m) {
     mars_track_release(m);
     mars_seg_release(m);
     mars_pose_release(m);
+    mars_obb_release(m);
 }
 
 static void free_ops(mars_model_ext_t *m) {

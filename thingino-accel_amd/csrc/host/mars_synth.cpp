@@ -296,7 +296,7 @@ size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap)
     T h20 = b.c3(b.concat({h18, h14}), ch(512), dep(3), false);
     T h21 = b.conv(h20, ch(512), 3, 2, true, false);
     T h23 = b.c3(b.concat({h21, h10}), ch(1024), dep(3), false);
-    if (head == MARS_SYNTH_HEAD_DFL || head == MARS_SYNTH_HEAD_SEG || head == MARS_SYNTH_HEAD_POSE) {
+    if (head == MARS_SYNTH_HEAD_DFL || head == MARS_SYNTH_HEAD_SEG || head == MARS_SYNTH_HEAD_POSE || head == MARS_SYNTH_HEAD_OBB) {
         // anchor-free Detect: per scale a box branch and a class branch (conv3x3 + SiLU twice, then a plain 1x1), concatenated; the three
         // concats are the graph outputs (the exported softmax / dist2bbox chain behind them is what mars_hip_detect_dfl computes)
         const int c2 = 64, c3 = h17.c > 80 ? h17.c : 80;
@@ -335,6 +335,18 @@ size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap)
                 b.layer(MARS_LAYER_RESHAPE, {kp.id}, r.id);
             }
         }
+        if (head == MARS_SYNTH_HEAD_OBB) {
+            // Oriented boxes: per scale an angle branch of 1 output, built after every box and class branch (the graph outputs are the DFL
+            // twin's); the angle tensors stay internal, named, each read by one RESHAPE the executor ignores
+            const int c4 = h17.c / 4 > 16 ? h17.c / 4 : 16;
+            int k = 0;
+            for (const T &p : {h17, h20, h23}) {
+                T an = b.conv(b.conv(b.conv(p, c4, 3, 1, true, false), c4, 3, 1, true, false), 1, 1, 1, false, false, Builder::kHeadScale);
+                std::snprintf(b.tensors[an.id].name, sizeof(b.tensors[an.id].name), "obb.ang%d", k++);
+                T r = b.act("obb.ang_flat", 1, an.h * an.w, 1, Builder::kHeadScale, 1.f);
+                b.layer(MARS_LAYER_RESHAPE, {an.id}, r.id);
+            }
+        }
         return b.serialise({x.id}, outs, buf, cap);
     }
     // detect: one 1x1 conv per scale, 3 anchors x 85 = 255 channels, shared output scale
@@ -353,7 +365,9 @@ size_t build_yolov5(const mars_synth_opts_t &o, int head, void *buf, size_t cap)
 } // namespace
 
 extern "C" size_t mars_synth_model_head(const mars_synth_opts_t *opts, int head, void *buf, size_t cap) {
-    if (!opts || (head != MARS_SYNTH_HEAD_ANCHOR && head != MARS_SYNTH_HEAD_DFL && head != MARS_SYNTH_HEAD_SEG && head != MARS_SYNTH_HEAD_POSE)) return 0;
+    if (!opts || (head != MARS_SYNTH_HEAD_ANCHOR && head != MARS_SYNTH_HEAD_DFL && head != MARS_SYNTH_HEAD_SEG && head != MARS_SYNTH_HEAD_POSE &&
+                  head != MARS_SYNTH_HEAD_OBB))
+        return 0;
     if (opts->input_hw < 0 || (opts->tiny == 0 && opts->input_hw % 32 != 0)) return 0;
     if (head != MARS_SYNTH_HEAD_ANCHOR && (opts->tiny || opts->float32)) return 0;
     return opts->tiny ? build_tiny(*opts, buf, cap) : build_yolov5(*opts, head, buf, cap);

@@ -511,6 +511,36 @@ typedef struct {
 } mhip_pose_t;
 int mhip_pose(const mhip_pose_t *p);
 
+/* ---- oriented boxes (obb.hip): the DFL heads plus a 1-channel angle tensor per head -> rotated candidates, then sort + ProbIoU suppression
+ * by the exact rule of include/mars_hip.h ("Oriented boxes").  Every pointer is device memory.  Records are 32 bytes {x, y, w, h, conf, cls,
+ * angle, pred}.  mhip_obb: the decode, then the sort + suppression.  mhip_obb_nms: the sort + suppression alone on cand / csn / cand_counts
+ * as a caller filled them (ang, box, cls, tab are not looked at). */
+typedef struct {
+    const int8_t *box[4], *cls[4], *ang[4]; size_t box_frame_stride[4], cls_frame_stride[4], ang_frame_stride[4];
+    int h[4], w[4], nc[4];
+    int box_pix_step[4], box_ch_step[4], cls_pix_step[4], cls_ch_step[4], ang_pix_step[4]; /* byte of (pixel p, channel c) = p * pix_step + c * ch_step */
+    int stride[4];
+    int reg_max;            /* bins per box side, 2 .. 32 */
+    const float *tab;       /* [head][512]: mhip_dfl_heads_t.tab */
+    const float *atab;      /* [head][768]: ang[q], cs[q], sn[q] at q + 128, + 256, + 512 */
+    int nheads, frames;
+    float conf;
+    float e_thresh;         /* E = (float)(1 - (1 - T)^2) */
+    int agnostic;           /* != 0: every pair is evaluated, whatever the classes */
+    void *cand;             /* [frames][1000] records: the candidates in prediction order; the sort leaves them in sorted order */
+    float *csn;             /* [frames][1000][2]: cos, sin of every candidate's angle (permuted with the records) */
+    int *cand_counts;       /* [frames] candidates (the decode writes it; clamped to 0 .. 1000) */
+    void *out;              /* [frames][1000] records: the kept boxes, mapped */
+    int *out_counts;        /* [frames] kept */
+    void *dets;             /* NULL, or [frames][1000] records of 24 bytes: the enclosing upright rectangles, index-aligned with out */
+    int *counts;            /* NULL, or [frames] kept (the detection list's) */
+    int *raw_counts;        /* NULL, or [frames] candidates before NMS */
+    int map, px, py;        /* map != 0: x' = (x - px) * rx, y' = (y - py) * ry, w' = w * rx, h' = h * rx */
+    float rx, ry;
+} mhip_obb_t;
+int mhip_obb(const mhip_obb_t *p);
+int mhip_obb_nms(const mhip_obb_t *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,7 +169,17 @@ class PoseOpts(C.Structure):  # mars_hip_pose_opts_t: zero = default in every fi
                 ("min_conf", C.c_float), ("max_per_frame", C.c_int)]
 
 
+OBB_AGNOSTIC = 1                                                        # MARS_OBB_AGNOSTIC
+OBB_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("conf", "<f4"), ("cls", "<i4"), ("angle", "<f4"),
+                      ("pred", "<i4")])                                  # mars_obb_t
+
+
+class ObbOpts(C.Structure):  # mars_hip_obb_opts_t: zero = default in every field but the tensor indices
+    _fields_ = [("angle_tensors", C.c_int * 4), ("angle_scales", C.c_float * 4), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
 assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
 assert C.sizeof(MaskRec) == MASK_DTYPE.itemsize == 24 and C.sizeof(SegOpts) == 52
 assert C.sizeof(TrackRec) == TRACK_DTYPE.itemsize == 8 and C.sizeof(TrackState) == TRACK_STATE_DTYPE.itemsize == 48
@@ -217,7 +227,9 @@ EXPORTS = {
                    "mars_hip_tracker_create", "mars_hip_tracker_reset", "mars_hip_tracker_free", "mars_hip_tracker_read",
                    "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track",
                    "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks",
-                   "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints"],
+                   "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints",
+                   "mars_hip_detect_obb_device", "mars_hip_obb_results", "mars_hip_detect_obb", "mars_hip_obb_ms", "mars_yolo_obb_nms",
+                   "mars_yolo_obb_corners"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -342,6 +354,14 @@ def lib():
     L.mars_hip_pose_ms.restype = C.c_float
     L.mars_hip_pose_ms.argtypes = [P(MarsModel)]
     L.mars_yolo_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    L.mars_hip_detect_obb_device.argtypes = [P(MarsModel), P(YoloDflHeads), P(ObbOpts)]
+    L.mars_hip_obb_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p]
+    L.mars_hip_detect_obb.argtypes = [P(MarsModel), P(YoloDflHeads), P(ObbOpts), C.c_void_p, P(C.c_int), C.c_void_p]
+    L.mars_hip_obb_ms.restype = C.c_float
+    L.mars_hip_obb_ms.argtypes = [P(MarsModel)]
+    L.mars_yolo_obb_nms.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint]
+    L.mars_yolo_obb_corners.argtypes = [C.c_void_p, C.c_void_p]
+    L.mars_yolo_obb_corners.restype = None
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -669,13 +689,14 @@ class DeviceBuffer:
             pass
 
 
-SYNTH_HEADS = {"anchor": 0, "dfl": 1, "seg": 2, "pose": 3}  # MARS_SYNTH_HEAD_*
+SYNTH_HEADS = {"anchor": 0, "dfl": 1, "seg": 2, "pose": 3, "obb": 4}  # MARS_SYNTH_HEAD_*
 
 
 def synth_model(width_x16=8, depth_x3=1, input_hw=640, float32=False, nchw_int8=False, seed=1, tiny=False, vary_scales=False, head="anchor"):
     """Bytes of a synthetic well-formed .mars graph (mars_synth_model; head="dfl": mars_synth_model_head with the anchor-free DFL
     Detect head, int8 only; head="seg": that head plus mask coefficients and prototypes, see seg_twin_tensors; head="pose": the DFL head
-    plus keypoint tensors of 17 x 3 channels, see pose_twin_tensors)."""
+    plus keypoint tensors of 17 x 3 channels, see pose_twin_tensors; head="obb": the DFL head plus 1-channel angle tensors, see
+    obb_twin_tensors)."""
     o = SynthOpts(width_x16, depth_x3, input_hw, int(float32), int(nchw_int8), seed, int(tiny), int(vary_scales))
     if head == "anchor":
         make = lib().mars_synth_model
@@ -857,6 +878,50 @@ def keypoints(rows, K, D, gx, gy, stride, s):
     if rc != 0:
         raise ValueError("mars_yolo_keypoints refused its arguments or failed (%d)" % rc)
     return kp
+
+
+def obb_twin_tensors(file_bytes):
+    """the angle tensors of a synth_model(head="obb") file, found by the names the writer gives them (host only): the tensor index per
+    head, by stride.  KeyError if the file has no such tensors."""
+    b = bytes(file_bytes)
+    hdr = MarsHeader.from_buffer_copy(b[:C.sizeof(MarsHeader)])
+    names = {}
+    for i in range(hdr.num_tensors):
+        o = 76 + 124 * i
+        names[b[o + 4:o + 64].split(b"\0")[0].decode()] = i
+    return [names["obb.ang%d" % k] for k in range(3)]
+
+
+def obb_opts(angles, angle_scales=None, agnostic=False, flags=0):
+    """mars_hip_obb_opts_t.  angles: the angle tensor index of every DFL head, in the heads' order; angle_scales: None (the tensors' own),
+    one number for every head or a list; agnostic: MARS_OBB_AGNOSTIC; flags: further bits, as given"""
+    o = ObbOpts()
+    for k, t in enumerate(angles):
+        o.angle_tensors[k] = int(t)
+    if angle_scales is not None:
+        for k, x in enumerate(angle_scales if isinstance(angle_scales, (tuple, list)) else [angle_scales] * 4):
+            o.angle_scales[k] = float(x)
+    o.flags = int(flags) | (OBB_AGNOSTIC if agnostic else 0)
+    return o
+
+
+def obb_nms(boxes, thresh=0.45, agnostic=False, flags=0):
+    """mars_yolo_obb_nms: OBB_DTYPE [n] -> the kept boxes in order (confidence descending, position ascending; ProbIoU suppression); host
+    arrays in and out, runs on the GPU"""
+    a = np.array(boxes, dtype=OBB_DTYPE, copy=True).reshape(-1)
+    n = lib().mars_yolo_obb_nms(a.ctypes.data, len(a), float(thresh), int(flags) | (OBB_AGNOSTIC if agnostic else 0))
+    if n < 0:
+        raise ValueError("mars_yolo_obb_nms refused its arguments or failed (%d)" % n)
+    return a[:n]
+
+
+def obb_corners(boxes):
+    """mars_yolo_obb_corners of every box: OBB_DTYPE [n] -> float32 [n][4][2] (host only)"""
+    a = np.ascontiguousarray(np.atleast_1d(boxes), dtype=OBB_DTYPE)
+    out = np.zeros((len(a), 4, 2), dtype=np.float32)
+    for i in range(len(a)):
+        lib().mars_yolo_obb_corners(a[i:i + 1].ctypes.data, out[i].ctypes.data)
+    return out
 
 
 def compile_onnx(onnx_bytes, float32=False, nhwc=False, verbose=False):
@@ -1283,6 +1348,32 @@ class Model:
     def pose_ms(self):
         """device time (ms) of the keypoint stage of the last detect_pose_device (mars_hip_pose_ms); < 0: not available"""
         return float(lib().mars_hip_pose_ms(self.p))
+
+    def detect_obb_device(self, obb, heads=None, **kw):
+        """oriented decode + sort + rotated NMS, results stay in HBM (mars_hip_detect_obb_device).  obb: obb_opts(); heads and the keywords
+        as for yolo_dfl_heads()"""
+        rc = lib().mars_hip_detect_obb_device(self.p, C.byref(yolo_dfl_heads(heads, **kw)), C.byref(obb) if obb is not None else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_obb_device")
+
+    def obb_results(self):
+        """the oriented boxes the last detect_obb_device left in HBM (mars_hip_obb_results): an OBB_DTYPE array per frame"""
+        boxes = np.zeros((self.batch, MAX_DET), dtype=OBB_DTYPE)
+        counts = np.zeros(self.batch, dtype=np.int32)
+        rc = lib().mars_hip_obb_results(self.p, boxes.ctypes.data, counts.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_obb_results")
+        return [boxes[f, :counts[f]].copy() for f in range(self.batch)]
+
+    def detect_obb(self, obb, heads=None, **kw):
+        """detect_obb_device + detect_results + obb_results: (the enclosing upright rectangles, a record array per frame; the oriented boxes,
+        an OBB_DTYPE array per frame, index-aligned)"""
+        self.detect_obb_device(obb, heads, **kw)
+        return self.detect_results(), self.obb_results()
+
+    def obb_ms(self):
+        """device time (ms) of the oriented stage (decode + sort + NMS) of the last detect_obb_device (mars_hip_obb_ms); < 0: not available"""
+        return float(lib().mars_hip_obb_ms(self.p))
 
     def detect_results(self):
         """the detections the last detect_device / detect_heads_device / detect_dfl_device left in HBM (mars_hip_detect_results)"""
