@@ -1302,6 +1302,11 @@ extern "C" int mhip_conv_i8_variants(const mhip_conv_i8_t *p, int *codes, int ma
             if (n < max && conv_i8_patch_ok(p, th, nullptr)) codes[n++] = th == 16 ? 10 : (th == 8 ? 9 : 11);
         return n;
     }
+    if (p->split_w) { // fused cv1 + cv2 pair: likewise
+        for (int th : {16, 8, 4})
+            if (n < max && conv_i8_patch_ok(p, th, nullptr)) codes[n++] = th == 16 ? 10 : (th == 8 ? 9 : 11);
+        return n;
+    }
     if (p->nseg > 1) { // the tile walker only: plain, or with resident weights where they fit
         const int bn = p->oc_pad % 128 == 0 ? 128 : (p->oc_pad % 64 == 0 ? 64 : 32);
         const variant_t dv = default_variant(p, nks);
@@ -1345,7 +1350,7 @@ static int launch_generic(const mhip_conv_i8_t *p, long total_pix, int k64) {
 
 extern "C" int mhip_conv_i8(const mhip_conv_i8_t *p) {
     // host-side shape checks: the kernels trust these (a faulting kernel can reset the node)
-    if (!p || !p->in || (!p->out && !(p->post_w && p->post_out)) || !p->w) return -1;
+    if (!p || !p->in || (!p->out && !(p->post_w && p->post_out) && !(p->split_w && p->split_out[0] && p->split_out[1])) || !p->w) return -1;
     if (p->out_pix_stride < 0 || p->out_ch_off < 0 || (p->out_nchw && (p->out_pix_stride || p->out_ch_off)) ||
         (p->out_pix_stride && p->out_pix_stride < p->out_ch_off + p->out_c))
         return -1;
@@ -1394,6 +1399,19 @@ extern "C" int mhip_conv_i8(const mhip_conv_i8_t *p) {
     if (p->post_w) { // fused cv3: the patch-staged kernel at the tallest tile that fits (4 rows for few workgroups); no other form runs it
         if (!mhip_zero_page() || (p->in_c % 16) != 0 || !mhip_conv_i8_post_ok(p)) return -1;
         int th = conv_i8_post_tile_rows(p);
+        const int code = p->variant ? p->variant : tune().variant;
+        if (code >= 9 && code <= 11) { // forced (tests): that height if it fits
+            const int want = code == 10 ? 16 : (code == 9 ? 8 : 4);
+            if (conv_i8_patch_ok(p, want, nullptr)) th = want;
+        } else if (tune().small_batch && conv_i8_patch_ok(p, 4, nullptr) &&
+                   ((long)p->frames * p->out_h * p->out_w + 255) / 256 * ((p->oc_pad + 127) / 128) < tune().few_wgs) {
+            th = 4;
+        }
+        return conv_i8_launch_patch(p, k64, th);
+    }
+    if (p->split_w) { // fused cv1 + cv2 pair: the same policy, the same single form
+        if (!mhip_zero_page() || (p->in_c % 16) != 0 || !mhip_conv_i8_split_ok(p)) return -1;
+        int th = conv_i8_split_tile_rows(p);
         const int code = p->variant ? p->variant : tune().variant;
         if (code >= 9 && code <= 11) { // forced (tests): that height if it fits
             const int want = code == 10 ? 16 : (code == 9 ? 8 : 4);

@@ -204,6 +204,35 @@ __device__ __forceinline__ void requant_pack_pre(const int (&a)[NV], float cs, u
 #pragma unroll
     for (int g = 0; g < NV / 4; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
+// ... of TWO results of 8 values each (the sides of a fused cv1 + cv2 pair): a[0..7] with cs0 through the table at LDS bytes 512..1023,
+// a[8..15] with cs1 through a third table at 1024..1535; one wait for all sixteen reads
+__device__ __forceinline__ void requant_pack_two(const int (&a)[16], float cs0, float cs1, uint32_t (&pk)[4]) {
+    const float c0 = cs0 * 2.0f, c1 = cs1 * 2.0f;
+    const int klo = -256, khi = 255;
+    int q[16], v[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int k = (int)((float)a[i] * (i < 8 ? c0 : c1));
+        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(q[i]) : "v"(k), "v"(klo), "v"(khi));
+    }
+#pragma unroll
+    for (int g = 0; g < 2; g++)
+        asm volatile("ds_read_i8 %0, %4 offset:768\n\tds_read_i8 %1, %5 offset:768\n\t"
+                     "ds_read_i8 %2, %6 offset:768\n\tds_read_i8 %3, %7 offset:768"
+                     : "=&v"(v[4 * g]), "=&v"(v[4 * g + 1]), "=&v"(v[4 * g + 2]), "=&v"(v[4 * g + 3])
+                     : "v"(q[4 * g]), "v"(q[4 * g + 1]), "v"(q[4 * g + 2]), "v"(q[4 * g + 3])
+                     : "memory");
+#pragma unroll
+    for (int g = 2; g < 4; g++)
+        asm volatile("ds_read_i8 %0, %4 offset:1280\n\tds_read_i8 %1, %5 offset:1280\n\t"
+                     "ds_read_i8 %2, %6 offset:1280\n\tds_read_i8 %3, %7 offset:1280"
+                     : "=&v"(v[4 * g]), "=&v"(v[4 * g + 1]), "=&v"(v[4 * g + 2]), "=&v"(v[4 * g + 3])
+                     : "v"(q[4 * g]), "v"(q[4 * g + 1]), "v"(q[4 * g + 2]), "v"(q[4 * g + 3])
+                     : "memory");
+    wait_lds_values<16>(v);
+#pragma unroll
+    for (int g = 0; g < 4; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+}
 template <int NV, bool HAS_LUT, bool SAFE, bool LUT0, bool ADD = false, bool FAST = false>
 __device__ __forceinline__ void requant_pack(const int (&a)[NV], float cs, int lo, const uint8_t *lut128, uint32_t (&pk)[NV / 4],
                                              const uint32_t *xw = nullptr, const add_args_t *ga = nullptr) {
@@ -495,6 +524,7 @@ bool conv_i8_patch_ok(const mhip_conv_i8_t *p, int th, int *ring);
 int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th); // -1: not eligible
 int conv_i8_pre_tile_rows(const mhip_conv_i8_t *p);                 // fused bottleneck: tallest tile that fits, 0 = none
 int conv_i8_post_tile_rows(const mhip_conv_i8_t *p);                // fused cv3 (post_* fields): likewise
+int conv_i8_split_tile_rows(const mhip_conv_i8_t *p);               // fused cv1 + cv2 pair (split_* fields): likewise
 // conv_i8_rows.hip: whole-row tiles, patch-staged input, streamed weights, one persistent workgroup per CU (variant 20)
 bool conv_i8_rows_ok(const mhip_conv_i8_t *p);
 int conv_i8_launch_rows(const mhip_conv_i8_t *p); // -1: not eligible

@@ -90,7 +90,18 @@ __device__ __forceinline__ void barrier_lds() {
 // at the tile's start; with one, after the Add's rows have been read back into registers -- it is then the youngest
 // vector-memory operation when the wave needs it, so that wait is a full one, at the END of the tile (the next patch was
 // issued before the K loop and is due at the next tile's start anyway; no patch is drained before a tile's first MFMA).
-template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false>
+//
+// SPLIT (C3's cv1 + cv2 inside the k x k convolution that feeds them, stride 1 / 2, out_c = BN = 64, no Add): the tile's result is read
+// by those two 1x1s (64 -> 32 channels each) and by nothing else.  After a tile row's requant_pack the lane's 16 bytes are B-operand
+// chunk g of the ONLY K step of both.  One round per side: two MFMAs over that side's 32 weight rows leave the lane with 8 consecutive
+// channels of that side, requantised with that side's scale through that side's half-step table (LDS bytes 512..1023 and 1024..1535)
+// and stored with one 8-byte buffer store into that side's tensor -- scale, table and buffer resource are wave-uniform.  There is no
+// second operand to wait for and no staging row.  The wave first packs all its tile rows, reads the image's four fragments and bias
+// rows ONCE per tile, issues the rows' MFMAs back to back (they are independent) and then requantises row by row with one LDS wait
+// for both sides' table reads: row by row in one pass, every row paid the fragment reads and two table round trips of its own (measured
+// slower).  The image (mhip_conv_i8_split_pack: 64 rows x 64 bytes, then 64 bias rows) stays resident where POST keeps cv3's; the
+// k x k result itself is never stored.
+template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false, bool SPLIT = false>
 __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p, const int k64, const int tiles_x,
                                                           const int tiles_y, const unsigned ntiles_all, const int PH,
                                                           const int PW, const int PWP, const int PWH, const int nblk,
@@ -106,14 +117,17 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     lds_base_must_be_zero(dynlds);
     const int nks = k64 / BK;
     constexpr int NPO = 2 * BN;                            // POST: cv3's input and output channels
-    constexpr int LB = LUTB + ((PRE || POST) ? 512 : 0);   // PRE / POST: the 1x1's table behind the main one
+    static_assert(!SPLIT || (BN == 64 && HAS_LUT && !PRE && !POST), "SPLIT: one 64-channel tile, no other stage");
+    constexpr int LB = LUTB + ((PRE || POST) ? 512 : 0) + (SPLIT ? 1024 : 0); // PRE / POST: the 1x1's table behind the main one; SPLIT: two
     int *dutab = (int *)(dynlds + LB);                     // [nks][4] unit offsets of the K chunks
     int8_t *wl = dynlds + LB + ((nks * 16 + 255) & ~255);   // [nks][BN][64], swizzled like the ring tiles
     const int patch_bytes = nblk * 1024;                   // whole 1 KB blocks (one wave-instruction of LDS-DMA each)
     int8_t *w1l = wl + nks * BN * BK;                      // PRE: [in_c][64] weights of the 1x1
     int8_t *pwl = w1l;                                     // POST: [NPO / 64][NPO][64] weights of cv3, then its NPO bias rows
     const int *pbl = (const int *)(pwl + NPO * NPO);
-    int8_t *patch0 = w1l + (PRE ? p.in_c * BK : 0) + (POST ? NPO * NPO + NPO * 4 : 0);
+    int8_t *swl = w1l;                                     // SPLIT: [64 rows: side, 32 channels][64] weights of cv1 and cv2, then their 64 bias rows
+    const int *sbl = (const int *)(swl + 64 * BK);
+    int8_t *patch0 = w1l + (PRE ? p.in_c * BK : 0) + (POST ? NPO * NPO + NPO * 4 : 0) + (SPLIT ? 64 * BK + 64 * 4 : 0);
     int8_t *tpatch = patch0 + ring * patch_bytes;          // PRE: the patch of t
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -140,6 +154,13 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     if (POST) {
         if (tid >= 128) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.post_lut2)[tid - 128];
         if (tid < NPO) ((int *)(pwl + NPO * NPO))[tid] = ((const int *)(p.post_w + NPO * NPO))[tid];
+    }
+    if (SPLIT) { // LDS 512..1023: side 0's table, 1024..1535: side 1's
+        if (tid >= 128) {
+            ((uint32_t *)slut)[tid] = ((const uint32_t *)p.split_lut2[0])[tid - 128];
+            ((uint32_t *)slut)[tid + 128] = ((const uint32_t *)p.split_lut2[1])[tid - 128];
+        }
+        if (tid < 64) ((int *)(swl + 64 * BK))[tid] = ((const int *)(p.split_w + 64 * BK))[tid];
     }
     // K chunk table: chunk (ks, f) -> kernel row ky, column kx, channel chunk
     const int rowbytes = p.kw * C, kbytes = p.kh * rowbytes;
@@ -168,6 +189,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
             for (int g = wv; g < C / 16; g += 4) glds16(p.pre_w + (size_t)(g * 16 + (lane >> 2)) * BK + schunk * 16, w1l + g * 16 * BK);
         if (POST) // the host's image is the LDS layout: a straight copy, 1 KB per instruction
             for (int i = wv; i < NPO * NPO / 1024; i += 4) glds16(p.post_w + i * 1024 + lane * 16, pwl + i * 1024);
+        if (SPLIT) // likewise: 4 KB, one instruction per wave
+            glds16(p.split_w + wv * 1024 + lane * 16, swl + wv * 1024);
     }
     // this lane's units of the patch DMA: instruction n of wave wv fills the 1 KB block n*4 + wv = physical units
     // (n*4+wv)*64 + lane; blocks at or beyond nblk do not exist (that instruction is not issued)
@@ -233,9 +256,12 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     };
 
     // (POST: the stores go to cv3's output, out_bytes is its extent)
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(POST ? p.post_out : p.out, 0, (int)out_bytes, 0x00020000);
+    // (SPLIT: side 0's tensor, out_bytes is its extent; side 1 has a resource of its own)
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? p.split_out[0] : (POST ? p.post_out : p.out), 0, (int)out_bytes, 0x00020000);
+    const unsigned out_bytes1 = SPLIT ? (unsigned)(p.frames - 1) * (unsigned)p.split_out_stride[1] + (unsigned)(p.out_h * p.out_w) * 32u : 0u;
+    const __amdgpu_buffer_rsrc_t orsrc1 = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? p.split_out[1] : p.out, 0, (int)out_bytes1, 0x00020000);
     // the residual operand of a fused Add has the output's layout: same offsets, same extent
-    const bool has_add = p.add != nullptr;
+    const bool has_add = !SPLIT && p.add != nullptr;
     // residual staging: per wave WPX rows of 64 lanes x 16 bytes (BN 64) or 2 x 64 lanes x 4 bytes (BN 32), behind the patches
     constexpr int RROW = WOC == 4 ? 1024 : 512;
     constexpr int NRI = WOC == 4 ? WPX : 2 * WPX;   // LDS-DMA instructions per wave and tile for it
@@ -245,7 +271,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     const int NR = has_add || POST ? NRI : 0;
     // vector-memory operations of a tile behind its patch request: the stores (POST: cv3's, 16 bytes each), and y2's rows where an Add
     // went through the staging area first
-    const int ntail = POST ? (has_add ? NRI : 0) + WPX * (NPO / 64) : NST;
+    // (SPLIT: no rows, two 8-byte stores per tile row -- one per side -- all behind the patch request like the plain form's)
+    const int ntail = POST ? (has_add ? NRI : 0) + WPX * (NPO / 64) : (SPLIT ? 2 * WPX : NST);
     const int ppstride = p.post_out_pix_stride ? p.post_out_pix_stride : NPO;
     // POST: one staging row per tile row from a dense NHWC tensor of BN channels (the Add's operand, y2): this lane's 4 * WOC bytes
     auto issue_rows = [&](const int8_t *base, size_t fstride, int tx, int ty, unsigned f) {
@@ -327,6 +354,13 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
             }
             if (has_add) issue_rows(p.add, p.out_stride, tx, ty, f);
             else issue_rows(p.post_in, p.post_in_stride, tx, ty, f);
+        } else if (SPLIT) {
+            // voffs: this lane's 8 consecutive channels of its pixel inside a frame of either side (32 channels, dense); the frame is added per side
+#pragma unroll
+            for (int u = 0; u < WPX; u++) {
+                const int oy = ty * TH + wv * WPX + u, ox = tx * PT_TW + frow;
+                voffs[u] = oy < p.out_h && ox < p.out_w ? (oy * p.out_w + ox) * 32 + (lane >> 4) * 8 : -1;
+            }
         } else if (has_add) {
 #pragma unroll
             for (int u = 0; u < WPX; u++) {
@@ -492,7 +526,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 }
             }
         }
-        uint32_t pku[POST ? WPX : 1][WOC]; // POST: the packed rows of u, cv3's first operand
+        uint32_t pku[POST || SPLIT ? WPX : 1][WOC]; // POST: the packed rows of u, cv3's first operand; SPLIT: the packed rows, both 1x1s' operand
         if (POST && has_add) {
             // the Add's rows are in registers (the wait threads them: no read is left in flight): the staging area takes y2's
 #pragma unroll
@@ -524,11 +558,47 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 for (int q = 0; q < WOC; q++) pku[POST ? u : 0][q] = pk[q];
                 continue;
             }
+            if (SPLIT) {
+#pragma unroll
+                for (int q = 0; q < WOC; q++) pku[SPLIT ? u : 0][q] = pk[q];
+                continue;
+            }
             const int voff = voffs[u];
             if (WOC == 4)
                 __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]}, orsrc, voff, 0, 0);
             else if (WOC == 2)
                 __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk[0], (int)pk[WOC > 1 ? 1 : 0]}, orsrc, voff, 0, 0);
+        }
+        if (SPLIT) {
+            // the image's fragments once per tile (rows sd * 32 + s4 * 16 .., side sd: this lane's channels (lane >> 4) * 8 + s4 * 4 .. + 3), then every
+            // row's four MFMAs -- independent of one another -- and per row ONE wait for both sides' table reads
+            v4i sw4[4], sb4[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                sw4[r] = *(const v4i *)(swl + lds_off(r * 16 + frow, fchunk));
+                sb4[r] = *(const v4i *)(sbl + r * 16 + fchunk * 4);
+            }
+            v4i sc[WPX][4];
+#pragma unroll
+            for (int u = 0; u < WPX; u++) {
+                const v4i b0 = {(int)pku[SPLIT ? u : 0][0], (int)pku[SPLIT ? u : 0][1], (int)pku[SPLIT ? u : 0][WOC > 2 ? 2 : 0], (int)pku[SPLIT ? u : 0][WOC > 3 ? 3 : 0]};
+#pragma unroll
+                for (int r = 0; r < 4; r++) sc[u][r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(sw4[r], b0, sb4[r], 0, 0, 0);
+            }
+            const unsigned fo0 = f * (unsigned)p.split_out_stride[0], fo1 = f * (unsigned)p.split_out_stride[1];
+#pragma unroll
+            for (int u = 0; u < WPX; u++) {
+                int a2[16];
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) a2[r * 4 + e] = sc[u][r][e];
+                uint32_t pk4[4];
+                requant_pack_two(a2, p.split_cs[0], p.split_cs[1], pk4);
+                const int voff0 = voffs[u] >= 0 ? voffs[u] + (int)fo0 : -1, voff1 = voffs[u] >= 0 ? voffs[u] + (int)fo1 : -1;
+                __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk4[0], (int)pk4[1]}, orsrc, voff0, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk4[2], (int)pk4[3]}, orsrc1, voff1, 0, 0);
+            }
         }
         if (POST) {
             // y2's rows: requested at the tile's start and waited for above (no Add: they took the Add's place), or just now
@@ -631,9 +701,20 @@ static bool patch_geom(const mhip_conv_i8_t *p, int th, patch_geom_t *g) {
             (long)(p->frames - 1) * (long)p->post_out_stride + (long)p->out_h * p->out_w * ppstride > 0x7fffffffL)
             return false;
     }
+    // the pair of 1x1s behind it (C3's cv1 + cv2): + their two tables, their weights and bias rows.  One 64-channel tile, dense, no Add; either side
+    // writes 32 channels per pixel, dense, within 31-bit offsets
+    const bool split = p->split_w != nullptr;
+    if (split) {
+        if (pre || post || p->add || g->bn != 64 || p->out_c != 64 || p->oc_pad != 64 || p->out_pix_stride || p->out_ch_off || !p->lut2 || !p->split_lut2[0] ||
+            !p->split_lut2[1] || !p->split_out[0] || !p->split_out[1])
+            return false;
+        for (int i = 0; i < 2; i++)
+            if ((long)(p->frames - 1) * (long)p->split_out_stride[i] + (long)p->out_h * p->out_w * 32 > 0x7fffffffL) return false;
+    }
     const size_t pb = (size_t)g->nblk * 1024;
     const size_t radd = p->add || post ? (size_t)4 * (th / 4) * (g->bn == 64 ? 1024 : 512) : 0; // residual staging rows of the 4 waves
     const size_t fixed = LUTB + (pre ? 512 + (size_t)C * BK + pb : 0) + (post ? 512 + (size_t)4 * g->bn * g->bn + (size_t)8 * g->bn : 0) +
+                         (split ? 1024 + (size_t)64 * BK + 64 * 4 : 0) +
                          (((size_t)g->nks * 16 + 255) & ~(size_t)255) + (size_t)g->nks * g->bn * BK + radd;
     const size_t budget = patch_lds_budget(g->bn);
     if (fixed + pb > budget) return false;
@@ -654,9 +735,12 @@ static inline long post_out_bytes(const mhip_conv_i8_t *p) { // bytes from p->po
     const long ppstride = p->post_out_pix_stride ? p->post_out_pix_stride : 2 * p->out_c;
     return (long)(p->frames - 1) * (long)p->post_out_stride + (long)p->out_h * p->out_w * ppstride;
 }
-template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false>
+static inline long split_out_bytes(const mhip_conv_i8_t *p, int side) { // ... of the pair's side
+    return (long)(p->frames - 1) * (long)p->split_out_stride[side] + (long)p->out_h * p->out_w * 32;
+}
+template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false, bool SPLIT = false>
 static int launch_patch_t(const mhip_conv_i8_t *p, int k64, const patch_geom_t &g) {
-    auto kern = conv_i8_patch<TH, BN, HAS_LUT, PRE, POST>;
+    auto kern = conv_i8_patch<TH, BN, HAS_LUT, PRE, POST, SPLIT>;
     // workgroups the device holds at once at THIS layer's LDS size (small patches fit 3-4 per CU), cached per size
     static int cus = 0;
     static size_t slots_lds[8];
@@ -700,7 +784,7 @@ static int launch_patch_t(const mhip_conv_i8_t *p, int k64, const patch_geom_t &
     hipLaunchKernelGGL(kern, dim3(gx, noc), dim3(NTHREADS), g.lds, mhip_stream_native(), *p, k64,
                        g.tiles_x, g.tiles_y, ntiles, g.PH, g.PW, g.PWP, g.PWH, g.nblk, (const int8_t *)mhip_zero_page(),
                        make_fastdiv((unsigned)g.tiles_x), make_fastdiv((unsigned)g.tiles_y), make_fastdiv((unsigned)g.PWP),
-                       (unsigned)(POST ? post_out_bytes(p) : persist_out_bytes(p)), g.ring, xmap,
+                       (unsigned)(SPLIT ? split_out_bytes(p, 0) : (POST ? post_out_bytes(p) : persist_out_bytes(p))), g.ring, xmap,
                        in_extent_bytes(p) <= 0x7fffffffL ? (unsigned)in_extent_bytes(p) : 0u);
     return mhip_check(hipGetLastError(), "conv_i8_patch launch");
 }
@@ -719,6 +803,11 @@ int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th) {
     (p->post_w ? launch_patch_t<T, B, true, false, true>(p, k64, g)                       \
      : p->pre_w ? launch_patch_t<T, B, true, true>(p, k64, g)                             \
                 : (p->lut ? launch_patch_t<T, B, true>(p, k64, g) : launch_patch_t<T, B, false>(p, k64, g)))
+    if (p->split_w) { // (patch_geom: one 64-channel tile)
+        if (th == 16) return launch_patch_t<16, 64, true, false, false, true>(p, k64, g);
+        if (th == 8) return launch_patch_t<8, 64, true, false, false, true>(p, k64, g);
+        return launch_patch_t<4, 64, true, false, false, true>(p, k64, g);
+    }
     if (th == 16) return g.bn == 64 ? PATCH(16, 64) : PATCH(16, 32);
     if (th == 8) return g.bn == 64 ? PATCH(8, 64) : PATCH(8, 32);
     return g.bn == 64 ? PATCH(4, 64) : PATCH(4, 32);
@@ -769,6 +858,37 @@ extern "C" size_t mhip_conv_i8_post_pack(int c, const int8_t *packed, const int3
             out[(size_t)(ks * n + R) * BK + (((chunk ^ ((R >> 1) & 2))) << 4) + (pos & 15)] = packed[(size_t)src * n + k];
         }
         ((int32_t *)(out + (size_t)n * n))[R] = bias ? bias[src] : 0;
+    }
+    return bytes;
+}
+
+// fused cv1 + cv2 pair (split_* fields): only the patch-staged kernel evaluates it, and the launch has no other form: the tallest tile that fits
+int conv_i8_split_tile_rows(const mhip_conv_i8_t *p) {
+    patch_geom_t g;
+    for (int th : {16, 8, 4})
+        if (patch_geom(p, th, &g)) return th;
+    return 0;
+}
+extern "C" int mhip_conv_i8_split_ok(const mhip_conv_i8_t *p) {
+    if (!p || !p->split_w || p->pre_w || p->post_w || p->add || p->nseg > 1 || p->out_nchw) return 0;
+    return conv_i8_split_tile_rows(p) != 0;
+}
+extern "C" int mhip_conv_i8_split_row(int side, int oc) {
+    const int g = oc >> 3, rem = oc & 7; // a lane group's 8 consecutive channels of one side
+    return side * 32 + (rem >> 2) * 16 + g * 4 + (rem & 3);
+}
+extern "C" size_t mhip_conv_i8_split_pack(const int8_t *packed0, const int32_t *bias0, const int8_t *packed1, const int32_t *bias1, int8_t *out) {
+    const size_t bytes = (size_t)64 * BK + (size_t)64 * 4;
+    if (!packed0 || !packed1 || !out) return bytes;
+    memset(out, 0, bytes);
+    for (int side = 0; side < 2; side++) {
+        const int8_t *packed = side ? packed1 : packed0;
+        const int32_t *bias = side ? bias1 : bias0;
+        for (int oc = 0; oc < 32; oc++) {
+            const int R = mhip_conv_i8_split_row(side, oc), src = mhip_conv_i8_oc_row(oc, 32);
+            for (int k = 0; k < 64; k++) out[(size_t)R * BK + ((((k >> 4) ^ ((R >> 1) & 2))) << 4) + (k & 15)] = packed[(size_t)src * 64 + k];
+            ((int32_t *)(out + (size_t)64 * BK))[R] = bias ? bias[src] : 0;
+        }
     }
     return bytes;
 }

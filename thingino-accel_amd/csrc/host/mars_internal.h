@@ -94,6 +94,9 @@ typedef struct {
     int post_next;   /* fused cv3: the NEXT op, a 1x1 over concat({this result, y2}), is evaluated on this convolution's result tile in the same launch
                         (fuse_post; conv_i8_patch<POST>); t_out is never written, y2's tensor is mirrored into t_in; the mate stays in the plan, is not launched */
     size_t post_w_off; /* ... its weights and bias rows as that kernel keeps them in LDS (mhip_conv_i8_post_pack) */
+    int split_next;  /* fused cv1 + cv2: the NEXT TWO ops, a paired launch of 1x1s that alone read this convolution's result, are evaluated on its result
+                        tile in the same launch (fuse_split; conv_i8_patch<SPLIT>); t_out is never written; both mates stay in the plan, are not launched */
+    size_t split_w_off; /* ... their weights and bias rows as that kernel keeps them in LDS (mhip_conv_i8_split_pack) */
     size_t w2_off;   /* a second image of the weights, or NO_OFF: the RGB stem's as conv_i8_rgb keeps them in LDS
                         (mhip_conv_i8_rgb_pack), or (w2_rows) a deep 3x3 layer's as conv_i8_rows streams them (mhip_conv_i8_rows_pack) */
     int w2_rows;
@@ -117,7 +120,7 @@ typedef struct {
 typedef struct {
     int fusion; /* MARS_HIP_FUSION, default 1 */
     unsigned no_fuse_lut : 1, no_nhwc_internal : 1, no_vconcat_q : 1, no_pair_f32 : 1, no_rec : 1, no_zero_tail : 1, no_vconcat_f32 : 1,
-        no_rowpad : 1, no_post : 1; /* MARS_HIP_NO_*: set = that pass is off */
+        no_rowpad : 1, no_post : 1, no_split : 1; /* MARS_HIP_NO_*: set = that pass is off */
     size_t rec_limit;        /* MARS_HIP_REC_LIMIT: bytes all frames of a tensor may span under 32-bit offsets (rec_pairs, virtual_concat_f32) */
     size_t vconcat_limit;    /* MARS_HIP_VCONCAT_LIMIT: ... the output of a segmented convolution (alloc_batch) */
     size_t bottleneck_limit; /* MARS_HIP_BOTTLENECK_LIMIT: largest batch that keeps fused bottlenecks, 0 = no limit (alloc_batch) */
@@ -132,6 +135,7 @@ typedef struct mars_model_ext {
     int no_download; /* mars_hip_set_output_mode(MARS_HIP_OUTPUT_ON_DEVICE): mars_run leaves the graph outputs in HBM */
     int no_bottleneck; /* fused bottlenecks (fusion level 2) switched off: one of them cannot launch at this batch */
     int no_post;       /* fused cv3 launches (fuse_post) switched off: one of them cannot launch at this batch (32-bit output offsets) */
+    int no_split;      /* fused cv1 + cv2 launches (fuse_split) switched off: likewise */
     int rec_frames;    /* rec_pairs: the batch the record-format pairs were chosen for (0 = one frame); a pair whose tensors reach 4 GiB at that batch is left alone */
     int rec_skipped;   /* ... some pair was left alone for that reason (a smaller batch may take it) */
     size_t rec_max_frames; /* ... the largest batch every chosen pair still fits */
@@ -251,6 +255,7 @@ MARS_INTERNAL size_t planned_stride(const mtensor_t *t);
 MARS_INTERNAL void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p);
 MARS_INTERNAL int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t out_stride);
 MARS_INTERNAL int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames);
+MARS_INTERNAL int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames);
 /* ... the passes, in the order build_plan calls them (f32: 0 = the int8 form, 1 = the float32 form) */
 MARS_INTERNAL void plan_layer(mars_model_ext_t *m, int li);
 MARS_INTERNAL void fold_silu(mars_model_ext_t *m, int f32);
@@ -264,6 +269,7 @@ MARS_INTERNAL void fuse_pool_chains(mars_model_ext_t *m);
 MARS_INTERNAL void pair_convs(mars_model_ext_t *m);
 MARS_INTERNAL void fuse_bottleneck(mars_model_ext_t *m);
 MARS_INTERNAL void fuse_post(mars_model_ext_t *m);
+MARS_INTERNAL void fuse_split(mars_model_ext_t *m);
 MARS_INTERNAL void pad_output_rows(mars_model_ext_t *m);
 MARS_INTERNAL void virtual_concat_q(mars_model_ext_t *m);
 MARS_INTERNAL void f32_policy(mars_model_ext_t *m);

@@ -704,6 +704,18 @@ int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_
     return mhip_conv_i8_post_ok(&p);
 }
 
+/* does the device code take convolution `a` with the paired 1 x 1s `b` and `c` behind it evaluated in the same launch (fuse_split), at this batch? */
+int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames) {
+    mhip_conv_i8_t p;
+    if (a->t_in[0] < 0 || a->t_out < 0 || b->t_out < 0 || c->t_out < 0) return 0;
+    conv_i8_geometry(a, frames, &p);
+    p.in_stride = planned_stride(&m->mt[a->t_in[0]]); p.out_stride = planned_stride(&m->mt[a->t_out]);
+    p.lut = p.lut2 = p.split_lut2[0] = p.split_lut2[1] = (const uint8_t *)a;
+    p.split_w = (const int8_t *)a; p.split_out[0] = p.split_out[1] = (int8_t *)m;
+    p.split_out_stride[0] = planned_stride(&m->mt[b->t_out]); p.split_out_stride[1] = planned_stride(&m->mt[c->t_out]);
+    return mhip_conv_i8_split_ok(&p);
+}
+
 /* ------------------------------------------------------------------ fusion
  * conv -> sigmoid -> mul (SiLU as exported to ONNX) collapses into the conv
  * epilogue: every value of the chain is a function of the conv's int8 result
@@ -1272,6 +1284,53 @@ void fuse_post(mars_model_ext_t *m) {
     free(readers);
 }
 
+/* C3's cv1 + cv2 inside the k x k convolution that feeds them: A = a k x k convolution (stride 1 or 2) to 64 channels whose result T only the
+ * two members B, C of the paired launch right behind it read (1 x 1, 64 -> 32 channels each).  A's launch (conv_i8_patch<SPLIT>) holds a tile
+ * row of T as the B operand of both 1 x 1s' only K step the moment it is requantised and stores their results: T is never written nor read
+ * back, and the pair launch goes.  Same bytes: B and C see exactly the int8 values A would have stored.  All three ops stay in the plan: A
+ * carries split_next and is launched, B (which keeps pair_next) and C are skipped.  B and C write dense tensors: pair_convs forms no pair that
+ * writes a channel slice, and one that has been given a byte offset or padded rows is declined here.  Only where the device code takes it
+ * (mhip_conv_i8_split_ok); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_split). */
+static int split_mate_ok(const mars_op_t *b, const mars_op_t *a, int T) {
+    return b->kind == OP_CONV_I8 && b->kh == 1 && b->kw == 1 && b->sh == 1 && b->sw == 1 && !b->pt && !b->pl && b->safe && !b->nchw && !b->out_nchw && !b->add_t &&
+           !b->chain_n && !b->store_c && !b->in_byte_off && !b->out_byte_off && !b->out_pix_stride && !b->out_ch_off && b->lut_off != NO_OFF &&
+           b->lut2_off != NO_OFF && !b->nseg && !b->pre && !b->post_next && !b->split_next && b->n_in == 1 && b->t_in[0] == T && b->in_c == 64 &&
+           b->out_c == 32 && b->oc_pad == 32 && b->row_pad == 64 && b->in_h == a->out_h && b->in_w == a->out_w && b->out_h == a->out_h && b->out_w == a->out_w;
+}
+void fuse_split(mars_model_ext_t *m) {
+    if (m->sw.no_split || m->no_split) return;
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
+    for (int i = 0; i + 2 < m->n_ops; i++) {
+        mars_op_t *a = &m->ops[i], *b = &m->ops[i + 1], *c = &m->ops[i + 2];
+        if (a->kind != OP_CONV_I8 || a->pre || a->post_next || a->split_next || a->pair_next || !b->pair_next || c->pair_next ||
+            (i > 0 && (m->ops[i - 1].pair_next || m->ops[i - 1].post_next)))
+            continue;
+        const int T = a->t_out;
+        if (a->out_c != 64 || a->oc_pad != 64 || a->kh * a->kw < 2 || (a->sh != 1 && a->sh != 2) || a->sw != a->sh || !a->safe || a->nchw || a->out_nchw ||
+            a->nseg || a->out_pix_stride || a->out_ch_off || a->store_c || a->chain_n || a->in_byte_off || a->out_byte_off || a->add_t ||
+            a->lut_off == NO_OFF || a->lut2_off == NO_OFF || a->n_in != 1)
+            continue;
+        if (T < 0 || !split_mate_ok(b, a, T) || !split_mate_ok(c, a, T)) continue;
+        const int O0 = b->t_out, O1 = c->t_out;
+        if (O0 < 0 || O1 < 0 || O0 == O1 || O0 == T || O1 == T || readers[T] != 2 || writers[T] != 1 || m->mt[T].io_in || m->mt[T].io_out ||
+            m->mt[T].is_weight || m->mt[T].tail_read || m->mt[O0].pix_stride || m->mt[O1].pix_stride || op_reads(a, O0) || op_reads(a, O1))
+            continue;
+        if (!conv_i8_split_fits(m, a, b, c, 1)) continue; /* one frame: alloc_batch asks again for its batch */
+        const size_t bytes = mhip_conv_i8_split_pack(NULL, NULL, NULL, NULL, NULL);
+        const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
+        if (off == NO_OFF) break;
+        mhip_conv_i8_split_pack((const int8_t *)(m->arena_host + b->w_off), b->b_off != NO_OFF ? (const int32_t *)(m->arena_host + b->b_off) : NULL,
+                                (const int8_t *)(m->arena_host + c->w_off), c->b_off != NO_OFF ? (const int32_t *)(m->arena_host + c->b_off) : NULL,
+                                (int8_t *)(m->arena_host + off));
+        a->split_next = 1;
+        a->split_w_off = off;
+        m->mt[T].needed = 0;
+        i += 2; /* B and C are taken */
+    }
+    free(readers);
+}
+
 /* Ragged pixel rows of graph outputs (the 255-channel YOLO heads) are kept at a 16-byte-aligned pitch on the device:
  * the producing convolution then takes the aligned epilogue (16-byte stores straight from registers, every launch
  * form) instead of the LDS-staged copy-out with 8+4+2+1-byte row tails.  Only tensors nothing in the graph reads:
@@ -1812,6 +1871,10 @@ void plan_check(mars_model_ext_t *m) {
         else if (o->post_next && (o->kind != OP_CONV_I8 || i + 1 >= m->n_ops || m->ops[i + 1].kind != OP_CONV_I8 || m->ops[i + 1].nseg != 2 ||
                                   m->ops[i + 1].seg_t[0] != o->t_out || !op_reads(o, m->ops[i + 1].seg_t[1])))
             why = "post_next without its 1x1 behind it, or y2 is not among t_in";
+        else if (o->split_next && (o->kind != OP_CONV_I8 || i + 2 >= m->n_ops || m->ops[i + 1].kind != OP_CONV_I8 || m->ops[i + 2].kind != OP_CONV_I8 ||
+                                   !m->ops[i + 1].pair_next || m->ops[i + 2].pair_next || m->ops[i + 1].n_in != 1 || m->ops[i + 2].n_in != 1 ||
+                                   m->ops[i + 1].t_in[0] != o->t_out || m->ops[i + 2].t_in[0] != o->t_out || o->post_next || o->pair_next || o->pre || o->add_t))
+            why = "split_next without its pair of 1x1s behind it";
         for (int k = 0; !why && k < o->nseg; k++)
             if (!op_reads(o, o->seg_t[k])) why = "a seg_t is not among t_in";
         for (int k = 0; !why && k < o->vc_n; k++)

@@ -63,7 +63,7 @@ void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8
     }
     p->cs = op->cs; p->relu = op->relu; p->out_nchw = op->out_nchw;
     p->variant = op->variant;
-    if (op->post_next && op->t_out >= 0) p->out_stride = planned_stride(&m->mt[op->t_out]); /* (never written, so never allocated: the Add's operand has its layout) */
+    if ((op->post_next || op->split_next) && op->t_out >= 0) p->out_stride = planned_stride(&m->mt[op->t_out]); /* (never written, so never allocated: the Add's operand has its layout) */
     if (op->add_t && tstride(m, op->add_t - 1) == p->out_stride) {
         p->add = (const int8_t *)tdev(m, op->add_t - 1);
         p->add_s_conv = op->add_s_conv; p->add_s_other = op->add_s_other; p->add_inv = op->add_inv;
@@ -95,6 +95,19 @@ static void conv_i8_post_params(const mars_model_ext_t *m, const mars_op_t *op, 
     p->post_out = (int8_t *)tdev(m, cv3->t_out); p->post_out_stride = tstride(m, cv3->t_out);
     if (p->post_out) p->post_out += cv3->out_byte_off;
     p->post_out_pix_stride = cv3->out_pix_stride; p->post_out_ch_off = cv3->out_ch_off;
+}
+
+/* a launch that carries split_next: its own record + the pair of 1x1s behind it (fuse_split) */
+static void conv_i8_split_params(const mars_model_ext_t *m, const mars_op_t *op, const mars_op_t *cv1, const mars_op_t *cv2, mhip_conv_i8_t *p) {
+    uint8_t *A = m->arena_dev;
+    const mars_op_t *side[2] = {cv1, cv2};
+    conv_i8_params(m, op, p);
+    p->split_w = (const int8_t *)(A + op->split_w_off);
+    for (int k = 0; k < 2; k++) {
+        p->split_lut2[k] = A + side[k]->lut2_off;
+        p->split_cs[k] = side[k]->cs;
+        p->split_out[k] = (int8_t *)tdev(m, side[k]->t_out); p->split_out_stride[k] = tstride(m, side[k]->t_out);
+    }
 }
 
 static void conv_f32_params(mars_model_ext_t *m, mars_op_t *op, mhip_conv_f32_t *p) {
@@ -353,9 +366,11 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             fprintf(stderr, "Mars: Layer %d execution failed\n", op->layer);
             return (mars_error_t)op->err;
         }
-        mars_op_t *mate = (op->pair_next || op->post_next) && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
+        mars_op_t *mate = (op->pair_next || op->post_next || op->split_next) && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
+        mars_op_t *mate2 = op->split_next && i + 2 < m->n_ops ? &m->ops[i + 2] : NULL; /* (a fused pair: both mates' outputs are this launch's) */
         if (wait_tail && ((op->t_out >= 0 && (m->mt[op->t_out].io_out || m->mt[op->t_out].tail_read)) ||
-                          (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)))) {
+                          (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)) ||
+                          (mate2 && mate2->t_out >= 0 && (m->mt[mate2->t_out].io_out || m->mt[mate2->t_out].tail_read)))) {
             /* the previous batch's detection tail (auxiliary stream) still reads the graph
              * outputs (or the raw heads it decodes): order this launch behind it */
             mhip_stream_wait(sid, m->ev_tail_done);
@@ -371,7 +386,15 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             op->ev_start = prof_last;
         }
         int rc;
-        if (mate && op->post_next) { /* cv3 inside this launch (conv_i8_patch<POST>): the plan holds it only where this form runs */
+        if (op->split_next) { /* cv1 + cv2 inside this launch (conv_i8_patch<SPLIT>): the plan holds them only where this form runs */
+            mhip_conv_i8_t pa;
+            rc = -1;
+            if (mate && mate2) {
+                conv_i8_split_params(m, op, mate, mate2, &pa);
+                rc = mhip_conv_i8(&pa);
+            }
+            i += 2; /* both mates have run */
+        } else if (mate && op->post_next) { /* cv3 inside this launch (conv_i8_patch<POST>): the plan holds it only where this form runs */
             mhip_conv_i8_t pa;
             conv_i8_post_params(m, op, mate, &pa);
             rc = mhip_conv_i8(&pa);
@@ -400,8 +423,8 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             rc = launch_op(m, op);
         }
         { /* the relayout scratch's copy of a tensor dies with any write to that tensor */
-            const mars_op_t *w2[2] = {op, mate};
-            for (int q = 0; q < 2; q++)
+            const mars_op_t *w2[3] = {op, mate, mate2};
+            for (int q = 0; q < 3; q++)
                 if (w2[q] && op_writes(w2[q], m->scratch_t)) m->scratch_t = -1;
         }
         if (m->profiling) { /* level 2: one event per run of launches of the same kind (their sum lands on the last one) */
@@ -780,6 +803,7 @@ static mars_error_t autotune_model(mars_model_t *model, int reps) {
         if (op->kind != OP_CONV_I8 || op->nchw) continue;
         if (op->pair_next || (i > 0 && m->ops[i - 1].pair_next)) continue; /* paired launches have one form */
         if (op->post_next || (i > 0 && m->ops[i - 1].post_next)) continue; /* ... and a fused cv3 goes with the launch its policy picks */
+        if (op->split_next) continue;                                      /* ... as does a fused pair (its mates are a pair: skipped above) */
         mhip_conv_i8_t p;
         conv_i8_params(m, op, &p);
         int codes[32];

@@ -114,7 +114,24 @@ typedef struct {
     const int8_t *post_in;  size_t post_in_stride;
     int8_t *post_out;       size_t post_out_stride;
     int post_out_pix_stride, post_out_ch_off;
+    /* optional: TWO 1x1 stride-1 convolutions with fused SiLU tables (C3's cv1 and cv2, 64 -> 32 channels each) evaluated on this
+     * convolution's RESULT tile while it is still in registers (patch-staged kernel only; out_c = oc_pad = 64, stride 1 or 2, no Add).
+     * The result of this convolution itself is NOT stored (`out` may be NULL).  split_w = the image of mhip_conv_i8_split_pack (both
+     * sides' weights in the kernel's row order, then the bias rows); side i has its own half-step table, combined scale and output:
+     * a dense NHWC tensor of 32 channels */
+    const int8_t *split_w;
+    const uint8_t *split_lut2[2];
+    float split_cs[2];
+    int8_t *split_out[2];   size_t split_out_stride[2];
 } mhip_conv_i8_t;
+/* can the convolution described by *p take the pair of 1x1s behind it (split_* fields) in its launch?  (geometry only, at some tile height) */
+int mhip_conv_i8_split_ok(const mhip_conv_i8_t *p);
+/* Bytes of, and (packed0, packed1, out != NULL) the content of, the pair's image: packed_i / bias_i = side i's packed weights
+ * [oc_pad = 32][k64 = 64] and bias rows as every conv_i8 launch reads them (bias NULL = zeros).  64 rows x 64 bytes in the kernel's LDS
+ * layout (chunk swizzle applied), K in natural order, then 64 bias rows; row side * 32 + s * 16 + g * 4 + r carries output channel
+ * g * 8 + s * 4 + r of that side (mhip_conv_i8_split_row; tests) */
+size_t mhip_conv_i8_split_pack(const int8_t *packed0, const int32_t *bias0, const int8_t *packed1, const int32_t *bias1, int8_t *out);
+int mhip_conv_i8_split_row(int side, int oc);
 /* can the convolution described by *p take a following 1x1 (post_* fields) in its launch?  (geometry only, at some tile height) */
 int mhip_conv_i8_post_ok(const mhip_conv_i8_t *p);
 /* Bytes of, and (packed, out != NULL) the content of, the 1x1's image for a fused launch of c = 32 / 64 channels: `packed` / `bias` = the
