@@ -852,6 +852,108 @@ int mars_yolo_obb_nms(mars_obb_t *boxes, int n, float thresh, unsigned flags);
  * each sum left to right. */
 void mars_yolo_obb_corners(const mars_obb_t *box, float xy[8]);
 
+/* --------------------------------------------------------- Tiled inference */
+/* Sliced inference for frames much larger than the graph input: a camera frame is cut into overlapping tiles, every tile is one frame of the
+ * batch, and the per-tile detection lists are mapped back and merged on the device.  A batch of B frames with T = n_tiles needs B % T == 0;
+ * it holds C = B / T camera frames, and model frame c * T + t is tile t of camera frame c.  The reference has no batch and no such step, so
+ * nothing here restates it.  The merge is float32, every operation rounded on its own, no fused multiply-add, division correctly rounded:
+ * everything is defined to the bit.
+ *
+ * Grid.       mars_tile_grid, per axis, with step = tile - overlap: the starts are k * step for every k >= 0 with k * step + tile < W, then one
+ *             final start W - tile; a tile at least as large as the axis gives the single span [0, W).  Tiles are listed row-major, y outer
+ *             and x inner.  1920 x 1080, 640 x 640 tiles, overlap 128: x-starts 0, 512, 1024, 1280, y-starts 0, 440: 8 tiles.  The calls take
+ *             a TABLE, not a grid: a caller may append any other rectangle, typically the whole frame, so that objects larger than a tile
+ *             are still seen.
+ * Front-end.  Tile t of camera frame c is written into model frame c * T + t by the rules of "ROI crops" above: the crop rectangle is the
+ *             tile's rectangle (no box arithmetic); the target geometry is stretch, or MARS_TILE_KEEP_ASPECT with the integer nw, nh, px, py
+ *             rule and -17 bands; the "Resize" and "NV12 source" paragraphs apply; the layout is the one the input's format tag asks for.
+ *             A tile whose size equals the input's gives pos = i * 256: an exact copy, pixel - 128.
+ * Quota.      Tile t contributes the first q entries of its list, q = max_per_tile, or by default min(MARS_YOLO_MAX_DET,
+ *             MARS_TILE_MAX_CAND / n_tiles); n_tiles * q <= MARS_TILE_MAX_CAND.  The entries beyond q are counted in `overflow`.
+ * Validity.   An entry is dropped, and counted in `invalid`, when one of x, y, w, h, conf is not finite, or w <= 0, or h <= 0.
+ * Map.        For a tile {x0, y0, x1, y1}: cw = x1 - x0, ch = y1 - y0, and nw, nh, px, py of the front-end's target geometry for the tw x th input:
+ *               rx = (float)cw / (float)nw;   X = ((x - (float)px) * rx) + (float)x0;   Wd = w * rx;      Y, Hd alike with ry = (float)ch / (float)nh
+ * Edge rule.  Only with edge_margin > 0.  l = X - (Wd * 0.5f), r = X + (Wd * 0.5f); tp, bt alike.  A side of the tile is interior when it is not
+ *             on the frame border: x0 > 0, x1 < src_w, y0 > 0, y1 < src_h.  The entry is dropped, and counted in `edge`, when
+ *             l - (float)x0 < edge_margin at an interior left side, (float)x1 - r < edge_margin at an interior right side, tp - (float)y0 <
+ *             edge_margin at an interior top, or (float)y1 - bt < edge_margin at an interior bottom: a box cut by a tile edge is left to
+ *             the neighbour that sees all of it.
+ * Candidates. The remaining entries, numbered k = 0, 1, ... by ascending tile, then list index; each carries its tile t and list index i.
+ *             `candidates` is their number.
+ * Order.      Confidence descending, then k ascending: a strict total order.  Confidences compare as their float32 values, except that -0
+ *             stands below +0 (the IEEE total order on finite values; detectors give none below their threshold).  This is deliberately NOT the
+ *             reference demo's exchange-sort permutation, which the upright tails reproduce: no reference defines this step.
+ * Suppression. Greedy in that order: a kept candidate a removes every later b with tile(a) != tile(b), equal classes (or any classes under
+ *             MARS_TILE_AGNOSTIC) and m(a, b) > merge_thresh.  Candidates of one tile never remove each other: the tile's own NMS has decided
+ *             those pairs.  With the mapped boxes, as in the detection tail (mars_yolo_nms):
+ *               x1 = max(Xa - Wa / 2, Xb - Wb / 2);  y1 alike;  x2 = min(Xa + Wa / 2, Xb + Wb / 2);  y2 alike
+ *               inter = max(0, x2 - x1) * max(0, y2 - y1)
+ *               m = inter / ((((Wa * Ha) + (Wb * Hb)) - inter) + 1e-6f)                     (IoU, the default)
+ *               m = inter / (fminf(Wa * Ha, Wb * Hb) + 1e-6f)                               (MARS_TILE_MATCH_IOS: intersection over the smaller)
+ *             IOS catches a box cut by a tile edge that lies inside its full version.  A removed candidate removes nothing.  `suppressed`
+ *             is the number removed.
+ * Output.     The survivors in sorted order, the first MARS_YOLO_MAX_DET of them; the rest are counted in `truncated`.  Each gives a
+ *             mars_det_t {X, Y, Wd, Hd, conf, cls} in camera pixels and an origin mars_tile_src_t {tile, det}.  Slots behind the last survivor
+ *             are all-zero bytes.
+ * Not covered: the mars_hip_pipe_* path; crop, label, identify, track, seg, pose and obb stages on merged lists (the host-list forms
+ *   mars_yolo_crop_boxes and mars_yolo_track_lists take the merged lists); box fusion by averaging (WBF); per-camera-frame tile tables; more
+ *   than MARS_TILE_MAX_CAND candidates per camera frame; float32 heads. */
+typedef struct { int x0, y0, x1, y1; } mars_tile_t;   /* source pixels, half-open; 16 bytes */
+typedef struct { int tile, det; } mars_tile_src_t;    /* 8 bytes: tile t, index inside that tile's list */
+typedef struct { int candidates, overflow, invalid, edge, suppressed, truncated; } mars_tile_stats_t; /* 24 bytes */
+#define MARS_TILE_MAX_TILES 64
+#define MARS_TILE_MAX_CAND 2048
+#define MARS_TILE_KEEP_ASPECT 1u
+#define MARS_TILE_MATCH_IOS 2u
+#define MARS_TILE_AGNOSTIC 4u
+/* Pure host code.  Writes the first min(count, cap) tiles (tiles may be NULL with cap 0) and returns the count, also when it exceeds cap;
+ * -1: a non-positive size, a negative overlap, or overlap >= tile. */
+int mars_tile_grid(int W, int H, int tile_w, int tile_h, int overlap_x, int overlap_y, mars_tile_t *tiles, int cap);
+/* Zero-initialise; zero means default in every field but the frame size and the table. */
+typedef struct {
+    int src_w, src_h, src_format; unsigned src_flags;   /* camera frames, as mars_hip_roi_opts_t */
+    int n_tiles; const mars_tile_t *tiles;              /* per camera frame, 1 .. MARS_TILE_MAX_TILES; copied by every call */
+    unsigned flags;                                     /* MARS_TILE_KEEP_ASPECT | MARS_TILE_MATCH_IOS | MARS_TILE_AGNOSTIC */
+    float merge_thresh;                                 /* 0: 0.5 */
+    float edge_margin;                                  /* source pixels; 0: no edge rule */
+    int max_per_tile;                                   /* 0: min(MARS_YOLO_MAX_DET, MARS_TILE_MAX_CAND / n_tiles) */
+} mars_hip_tile_opts_t;
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL table or pointer; n_tiles outside
+ * 1 .. MARS_TILE_MAX_TILES; a tile that is empty or not inside [0, src_w) x [0, src_h); a non-positive frame or input size, an unknown format
+ * or flag bit, odd NV12 sizes; a negative or non-finite merge_thresh or edge_margin, merge_thresh > 1; a negative max_per_tile, or n_tiles *
+ * max_per_tile > MARS_TILE_MAX_CAND; (front-end) a frame or target too wide for the crop kernel; (host-pointer forms) a non-positive n_frames,
+ * n_frames * n_tiles > 65535, max_det outside 1 .. MARS_YOLO_MAX_DET.  MARS_ERR_INVALID_TENSOR: a batch that is no
+ * multiple of n_tiles; an input that is not int8 with 3 channels; no detections in HBM; lists mapped with src_w > 0; *_results before any
+ * merge; a model with an open pipe. */
+/* Front-end.  `frames_dev` = C = batch / n_tiles camera frames of src_w x src_h, densely packed in HBM (RGB [h][w][3] or NV12).  Enqueues on
+ * the library's current stream, like mars_hip_preprocess_device: behind an earlier run of the model, ahead of its next one. */
+mars_error_t mars_hip_preprocess_tiles_device(mars_model_t *model, int input_index, const void *frames_dev, const mars_hip_tile_opts_t *opts);
+/* The same with the frames in host memory: uploads them, runs, waits. */
+mars_error_t mars_hip_preprocess_tiles(mars_model_t *model, int input_index, const unsigned char *frames, const mars_hip_tile_opts_t *opts);
+/* Merge.  Reads the lists the last mars_hip_detect_device / _heads_device / _dfl_device of the model left in HBM; they must be in graph-input
+ * pixels (the model records whether that tail ran with src_w > 0 and such lists are refused).  tw x th = the size of graph input 0.  Enqueues
+ * only, on the auxiliary stream with the ordering of mars_hip_track_device: behind the tail, ahead of the model's next detect call.  The
+ * merged arrays are the model's own: mars_hip_detect_results still returns the per-tile lists, byte for byte. */
+mars_error_t mars_hip_merge_tiles_device(mars_model_t *model, const mars_hip_tile_opts_t *opts);
+/* Waits.  dets = [C][MARS_YOLO_MAX_DET], counts = [C], origins = [C][MARS_YOLO_MAX_DET], stats = [C] of the last merge; any pointer may be NULL. */
+mars_error_t mars_hip_tile_results(mars_model_t *model, mars_det_t *dets, int *counts, mars_tile_src_t *origins, mars_tile_stats_t *stats);
+/* Camera frames C of the last merge on this model, the row count of what mars_hip_tile_results copies; 0: no merge yet (or no model). */
+int mars_hip_tile_frames(mars_model_t *model);
+/* mars_hip_merge_tiles_device + mars_hip_tile_results. */
+mars_error_t mars_hip_merge_tiles(mars_model_t *model, const mars_hip_tile_opts_t *opts, mars_det_t *dets, int *counts, mars_tile_src_t *origins,
+                                  mars_tile_stats_t *stats);
+/* Device time (ms) of the last mars_hip_merge_tiles_device call's kernel, from events on the auxiliary stream; waits for it.  < 0: not available. */
+float mars_hip_tile_ms(mars_model_t *model);
+/* Host pointers in and out, the same kernels on the GPU without a model; they wait.  frames = n_frames camera frames, out = [n_frames * T]
+ * [tw * th * 3] int8 ([th][tw][3] with nhwc != 0, else [3][th][tw]). */
+mars_error_t mars_yolo_tile_frames(const unsigned char *frames, int n_frames, const mars_hip_tile_opts_t *opts, int tw, int th, int nhwc,
+                                   signed char *out);
+/* dets = [n_frames * T][max_det] in pixels of a tw x th input, 1 <= max_det <= MARS_YOLO_MAX_DET; counts = [n_frames * T], clamped to
+ * 0 .. max_det.  out = [n_frames][MARS_YOLO_MAX_DET], out_counts = [n_frames], origins = [n_frames][MARS_YOLO_MAX_DET], stats = [n_frames];
+ * origins and stats may be NULL. */
+mars_error_t mars_yolo_merge_tiles(const mars_det_t *dets, const int *counts, int n_frames, int max_det, const mars_hip_tile_opts_t *opts,
+                                   int tw, int th, mars_det_t *out, int *out_counts, mars_tile_src_t *origins, mars_tile_stats_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

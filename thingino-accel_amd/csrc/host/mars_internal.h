@@ -223,6 +223,14 @@ typedef struct mars_model_ext {
     float obb_lut_scale[4];           /* the scales the block's angle tables were built from */
     int obb_lut_n;                    /* tables that are up (0: none) */
     void *ev_obb[2];    /* timing events around the oriented stage's launches on the auxiliary stream */
+    /* tiled inference (mars_tile.c) */
+    int det_mapped;     /* the last detection tail of THIS model mapped its lists into source-frame pixels (src_w > 0): the tile merge refuses them */
+    void *tile_roi_dev; /* tiles INTO this model: [slots, 0, ...] in 256 bytes, then [tile_roi_cap] x mars_roi_t, on the device */
+    int tile_roi_cap;
+    void *tile_dev;     /* merged lists of THIS model's detections, one block on the device: [tile_cap][MARS_YOLO_MAX_DET] x mars_det_t, the same of
+                         * mars_tile_src_t, [tile_cap] x int, [tile_cap] x mars_tile_stats_t */
+    int tile_cap, tile_cams; /* tile_cams == 0: no merge yet */
+    void *ev_tile[2];   /* timing events around the merge launch on the auxiliary stream */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -304,6 +312,9 @@ MARS_INTERNAL void mars_pose_release(mars_model_ext_t *m); /* the keypoint resul
 
 /* mars_obb.c */
 MARS_INTERNAL void mars_obb_release(mars_model_ext_t *m); /* the oriented results of a model whose device state goes away */
+
+/* mars_tile.c */
+MARS_INTERNAL void mars_tile_release(mars_model_ext_t *m); /* the tile table and merged lists of a model whose device state goes away */
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

@@ -100,6 +100,7 @@ static void free_device_state(mars_model_ext_t *m) {
     mars_seg_release(m);
     mars_pose_release(m);
     mars_obb_release(m);
+    mars_tile_release(m);
 }
 
 static void free_ops(mars_model_ext_t *m) {

@@ -162,6 +162,7 @@ mars_error_t mars_hip_detect_obb_device(mars_model_t *model, const mars_yolo_dfl
     m->obb_frames = 0;
     e = mars_tail_on_aux(m, obb_launch_cb, &c);
     if (e != MARS_OK) return e;
+    m->det_mapped = c.dfl.map;
     m->obb_cnt_off = cnt_off; m->obb_out_off = out_off;
     m->obb_frames = m->batch;
     return MARS_OK;

@@ -154,6 +154,7 @@ mars_error_t mars_hip_detect_pose_device(mars_model_t *model, const mars_yolo_df
     m->pose_frames = 0;
     e = mars_tail_on_aux(m, pose_launch_cb, &c);
     if (e != MARS_OK) return e;
+    m->det_mapped = c.dfl.map;
     m->pose_rec_off = rec_off; m->pose_kpt_off = kpt_off;
     m->pose_frames = m->batch; m->pose_max = p->max_per_frame; m->pose_k = K;
     return MARS_OK;

@@ -138,6 +138,7 @@ mars_error_t mars_hip_detect_seg_device(mars_model_t *model, const mars_yolo_dfl
     m->seg_frames = 0;
     e = mars_tail_on_aux(m, seg_launch_cb, &c);
     if (e != MARS_OK) return e;
+    m->det_mapped = c.dfl.map;
     m->seg_rec_off = rec_off; m->seg_word_off = word_off;
     m->seg_frames = m->batch; m->seg_max = p->max_per_frame; m->seg_ph = p->ph; m->seg_pw = p->pw;
     return MARS_OK;

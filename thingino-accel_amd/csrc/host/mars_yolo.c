@@ -128,6 +128,7 @@ mars_error_t mars_hip_detect_device(mars_model_t *model, const int *output_indic
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;
     m->tail_pending = 1;
+    m->det_mapped = 0;
     return MARS_OK;
 }
 
@@ -418,7 +419,9 @@ mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_h
     if (e == MARS_OK) e = mars_heads_prepare(m, &c);
     if (e != MARS_OK) return e;
     for (int k = 0; k < c.n; k++) m->mt[c.ti[k]].tail_read = 1;
-    return mars_tail_on_aux(m, heads_launch_cb, &c);
+    e = mars_tail_on_aux(m, heads_launch_cb, &c);
+    if (e == MARS_OK) m->det_mapped = c.map;
+    return e;
 }
 
 mars_error_t mars_hip_detect_results(mars_model_t *model, mars_det_t *dets, int *counts) {
@@ -668,7 +671,9 @@ mars_error_t mars_hip_detect_dfl_device(mars_model_t *model, const mars_yolo_dfl
     if (e == MARS_OK) e = mars_dfl_prepare(m, &c);
     if (e != MARS_OK) return e;
     for (int k = 0; k < c.n; k++) m->mt[c.box_buf[k]].tail_read = m->mt[c.cls_buf[k]].tail_read = 1;
-    return mars_tail_on_aux(m, dfl_launch_cb, &c);
+    e = mars_tail_on_aux(m, dfl_launch_cb, &c);
+    if (e == MARS_OK) m->det_mapped = c.map;
+    return e;
 }
 
 mars_error_t mars_hip_detect_dfl(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, mars_det_t *dets, int *counts) {

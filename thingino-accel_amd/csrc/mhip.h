@@ -558,6 +558,31 @@ typedef struct {
 int mhip_obb(const mhip_obb_t *p);
 int mhip_obb_nms(const mhip_obb_t *p);
 
+/* ---- tiled inference (tile.hip): the tile table -> the ROI table the crop kernel of roi.hip reads (tile t of camera frame c = slot c * T + t);
+ * T per-tile detection lists -> one list per camera frame in camera pixels, by the exact rule of include/mars_hip.h ("Tiled inference").
+ * The table travels by value in the launch record (at most 64 tiles); every pointer is device memory. */
+#define MHIP_TILE_MAX_TILES 64
+#define MHIP_TILE_MAX_CAND 2048
+typedef struct { int x0, y0, x1, y1; float px, py, rx, ry; } mhip_tile_geom_t; /* the rectangle; (float)px, (float)py and the factors of the map */
+typedef struct {
+    mhip_tile_geom_t tiles[MHIP_TILE_MAX_TILES];
+    int n_tiles, cams;      /* T, C: model frames = C * T */
+    int src_w, src_h;
+    int max_det;            /* row length of dets: 1 .. 1000 */
+    int quota;              /* entries a tile contributes: n_tiles * quota <= MHIP_TILE_MAX_CAND */
+    int ios, agnostic;
+    float thresh, edge_margin; /* edge_margin == 0: no edge rule */
+    const void *dets;       /* [C * T][max_det] records of 24 bytes {float x, y, w, h, conf; int cls} */
+    const int *counts;      /* [C * T]; clamped to 0 .. max_det */
+    void *out;              /* [C][1000] records of 24 bytes; slots behind the last survivor are zeroed */
+    int *out_counts;        /* [C] */
+    void *origins;          /* [C][1000] records of 8 bytes {int tile, det} */
+    void *stats;            /* [C] records of 24 bytes {candidates, overflow, invalid, edge, suppressed, truncated} */
+    void *rois; int *n_out; /* mhip_tile_rois: [C * T] records of 24 bytes (mhip_roi_t.rois) and {C * T, 0} (mhip_roi_t.n_out) */
+} mhip_tile_t;
+int mhip_tile_rois(const mhip_tile_t *p);  /* one launch: the ROI table of C camera frames */
+int mhip_tile_merge(const mhip_tile_t *p); /* one launch, one workgroup per camera frame */
+
 #ifdef __cplusplus
 }
 #endif

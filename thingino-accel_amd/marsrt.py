@@ -178,7 +178,21 @@ class ObbOpts(C.Structure):  # mars_hip_obb_opts_t: zero = default in every fiel
     _fields_ = [("angle_tensors", C.c_int * 4), ("angle_scales", C.c_float * 4), ("flags", C.c_uint)]
 
 
+TILE_MAX_TILES, TILE_MAX_CAND = 64, 2048                                 # MARS_TILE_*
+TILE_KEEP_ASPECT, TILE_MATCH_IOS, TILE_AGNOSTIC = 1, 2, 4
+TILE_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4")])  # mars_tile_t
+TILE_SRC_DTYPE = np.dtype([("tile", "<i4"), ("det", "<i4")])              # mars_tile_src_t
+TILE_STATS_DTYPE = np.dtype([("candidates", "<i4"), ("overflow", "<i4"), ("invalid", "<i4"), ("edge", "<i4"), ("suppressed", "<i4"),
+                             ("truncated", "<i4")])                        # mars_tile_stats_t
+
+
+class TileOpts(C.Structure):  # mars_hip_tile_opts_t: zero = default in every field but the frame size and the table
+    _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("src_format", C.c_int), ("src_flags", C.c_uint), ("n_tiles", C.c_int),
+                ("tiles", C.c_void_p), ("flags", C.c_uint), ("merge_thresh", C.c_float), ("edge_margin", C.c_float), ("max_per_tile", C.c_int)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert TILE_DTYPE.itemsize == 16 and TILE_SRC_DTYPE.itemsize == 8 and TILE_STATS_DTYPE.itemsize == 24 and C.sizeof(TileOpts) == 48
 assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
 assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
 assert C.sizeof(MaskRec) == MASK_DTYPE.itemsize == 24 and C.sizeof(SegOpts) == 52
@@ -229,7 +243,9 @@ EXPORTS = {
                    "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks",
                    "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints",
                    "mars_hip_detect_obb_device", "mars_hip_obb_results", "mars_hip_detect_obb", "mars_hip_obb_ms", "mars_yolo_obb_nms",
-                   "mars_yolo_obb_corners"],
+                   "mars_yolo_obb_corners",
+                   "mars_tile_grid", "mars_hip_preprocess_tiles_device", "mars_hip_preprocess_tiles", "mars_hip_merge_tiles_device",
+                   "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -362,6 +378,18 @@ def lib():
     L.mars_yolo_obb_nms.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint]
     L.mars_yolo_obb_corners.argtypes = [C.c_void_p, C.c_void_p]
     L.mars_yolo_obb_corners.restype = None
+    L.mars_tile_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.mars_hip_preprocess_tiles_device.argtypes = [P(MarsModel), C.c_int, C.c_void_p, P(TileOpts)]
+    L.mars_hip_preprocess_tiles.argtypes = [P(MarsModel), C.c_int, C.c_void_p, P(TileOpts)]
+    L.mars_hip_merge_tiles_device.argtypes = [P(MarsModel), P(TileOpts)]
+    L.mars_hip_tile_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_merge_tiles.argtypes = [P(MarsModel), P(TileOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_tile_frames.argtypes = [P(MarsModel)]
+    L.mars_hip_tile_ms.restype = C.c_float
+    L.mars_hip_tile_ms.argtypes = [P(MarsModel)]
+    L.mars_yolo_tile_frames.argtypes = [C.c_void_p, C.c_int, P(TileOpts), C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.mars_yolo_merge_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(TileOpts), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -497,6 +525,69 @@ def crop_boxes(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_crop_boxes")
     return out, rois
+
+
+def tile_grid(W, H, tile_w, tile_h, overlap_x=0, overlap_y=0):
+    """mars_tile_grid: the tile table (TILE_DTYPE records, row-major) of a W x H frame; ValueError where the library returns -1"""
+    n = lib().mars_tile_grid(int(W), int(H), int(tile_w), int(tile_h), int(overlap_x), int(overlap_y), None, 0)
+    if n < 0:
+        raise ValueError("mars_tile_grid refuses these sizes")
+    tiles = np.zeros(n, dtype=TILE_DTYPE)
+    if lib().mars_tile_grid(int(W), int(H), int(tile_w), int(tile_h), int(overlap_x), int(overlap_y), tiles.ctypes.data, n) != n:
+        raise RuntimeError("mars_tile_grid changed its mind")
+    return tiles
+
+
+def tile_opts(w, h, tiles, fmt=CAMERA_RGB, src_flags=0, keep_aspect=False, ios=False, agnostic=False, merge_thresh=0.0, edge_margin=0.0,
+              max_per_tile=0, flags=0):
+    """mars_hip_tile_opts_t for camera frames of w x h cut by `tiles` (TILE_DTYPE records, or rows of x0, y0, x1, y1); zero means default
+    everywhere else.  The table is copied and kept alive by the returned object"""
+    t = np.ascontiguousarray(tiles)
+    if t.dtype != TILE_DTYPE:
+        t = np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 4)).view(TILE_DTYPE).reshape(-1)
+    t = t.reshape(-1).copy()
+    f = int(flags) | (TILE_KEEP_ASPECT if keep_aspect else 0) | (TILE_MATCH_IOS if ios else 0) | (TILE_AGNOSTIC if agnostic else 0)
+    o = TileOpts(int(w), int(h), int(fmt), int(src_flags), int(t.size), t.ctypes.data, f, float(merge_thresh), float(edge_margin), int(max_per_tile))
+    o._table = t
+    return o
+
+
+def _tile_frame_bytes(opts):
+    return opts.src_w * opts.src_h * 3 // (2 if opts.src_format == CAMERA_NV12 else 1)
+
+
+def tile_frames(frames, opts, tw, th, nhwc=True):
+    """mars_yolo_tile_frames: camera frames (uint8, [n] frames of opts.src_w x opts.src_h, RGB or NV12) -> int8 tiles
+    [n * n_tiles][tw * th * 3], on the GPU"""
+    a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    fb = _tile_frame_bytes(opts)
+    if fb <= 0 or a.size % fb:
+        raise ValueError("frames of %d x %d are %d bytes each, got %d" % (opts.src_w, opts.src_h, fb, a.size))
+    n = a.size // fb
+    out = np.zeros((n * max(opts.n_tiles, 0), tw * th * 3), dtype=np.int8)
+    rc = lib().mars_yolo_tile_frames(a.ctypes.data, n, C.byref(opts), int(tw), int(th), int(bool(nhwc)), out.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_tile_frames")
+    return out
+
+
+def merge_tiles(dets, counts, opts, tw, th):
+    """mars_yolo_merge_tiles: dets (DET_DTYPE [n * n_tiles][max_det], pixels of a tw x th input) and counts [n * n_tiles] ->
+    (DET_DTYPE [n][MAX_DET] in camera pixels, counts [n], TILE_SRC_DTYPE [n][MAX_DET], TILE_STATS_DTYPE [n]), on the GPU"""
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if d.ndim != 2 or d.shape[0] != c.size or opts.n_tiles <= 0 or c.size % opts.n_tiles:
+        raise ValueError("dets is [n * n_tiles][max_det], counts [n * n_tiles]")
+    n = c.size // opts.n_tiles
+    out = np.zeros((n, MAX_DET), dtype=DET_DTYPE)
+    oc = np.zeros(n, dtype=np.int32)
+    org = np.zeros((n, MAX_DET), dtype=TILE_SRC_DTYPE)
+    st = np.zeros(n, dtype=TILE_STATS_DTYPE)
+    rc = lib().mars_yolo_merge_tiles(d.ctypes.data, c.ctypes.data, n, d.shape[1], C.byref(opts), int(tw), int(th), out.ctypes.data, oc.ctypes.data,
+                                     org.ctypes.data, st.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_merge_tiles")
+    return out, oc, org, st
 
 
 def cls_opts(output_index=0, tensor=0, top_k=0, scale=0.0, softmax=False):
@@ -1062,6 +1153,44 @@ class Model:
         rc = lib().mars_hip_preprocess_nv12_device(self.p, input_index, C.c_void_p(dev_ptr), int(w), int(h), int(flags), first_frame, int(frames))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_preprocess_nv12_device")
+
+    def preprocess_tiles(self, frames, opts, input_index=0, device=False):
+        """tiled inference, the front-end: batch / opts.n_tiles camera frames -> their tiles in graph input `input_index`, model frame
+        c * n_tiles + t = tile t of camera frame c.  device=False: frames = uint8 host array, uploaded, the call waits
+        (mars_hip_preprocess_tiles); device=True: frames = a device address (DeviceBuffer.ptr), enqueues only"""
+        if device:
+            rc = lib().mars_hip_preprocess_tiles_device(self.p, input_index, C.c_void_p(frames), C.byref(opts))
+        else:
+            a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+            fb = _tile_frame_bytes(opts)
+            if opts.n_tiles > 0 and self.batch % opts.n_tiles == 0 and fb > 0 and a.size != fb * (self.batch // opts.n_tiles):
+                raise ValueError("%d camera frames of %d bytes each, got %d bytes" % (self.batch // opts.n_tiles, fb, a.size))
+            rc = lib().mars_hip_preprocess_tiles(self.p, input_index, a.ctypes.data, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_preprocess_tiles")
+
+    def merge_tiles(self, opts):
+        """tiled inference, the merge: the per-tile lists the last detect_*_device left in HBM (graph-input pixels) -> one list per camera
+        frame in camera pixels, on the device (mars_hip_merge_tiles_device); enqueues only, tile_results() waits"""
+        rc = lib().mars_hip_merge_tiles_device(self.p, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_merge_tiles_device")
+
+    def tile_results(self):
+        """-> (DET_DTYPE [C][MAX_DET], counts [C], TILE_SRC_DTYPE [C][MAX_DET], TILE_STATS_DTYPE [C]) of the last merge_tiles(); waits"""
+        n = max(lib().mars_hip_tile_frames(self.p), 1)  # the library's own count; before any merge it is 0 and the call below refuses
+        out = np.zeros((n, MAX_DET), dtype=DET_DTYPE)
+        oc = np.zeros(n, dtype=np.int32)
+        org = np.zeros((n, MAX_DET), dtype=TILE_SRC_DTYPE)
+        st = np.zeros(n, dtype=TILE_STATS_DTYPE)
+        rc = lib().mars_hip_tile_results(self.p, out.ctypes.data, oc.ctypes.data, org.ctypes.data, st.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_tile_results")
+        return out, oc, org, st
+
+    def tile_ms(self):
+        """device time (ms) of the last merge_tiles() kernel (mars_hip_tile_ms); < 0: not available"""
+        return float(lib().mars_hip_tile_ms(self.p))
 
     def crop_detections(self, det_model, frames, opts, input_index=0, device=False):
         """the second stage: the detections det_model's last detect_*_device left in HBM -> crops of its frames in THIS model's input
