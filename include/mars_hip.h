@@ -137,7 +137,11 @@ void *mars_hip_stream(void); /* hipStream_t of the library, as void* */
  * With MARS_HIP_DESCRIBE_FULL in `flags` the text only grows: behind " |" every op line carries every scalar field of the launch that the run path
  * reads (geometry, paddings, offsets into tensors and into the parameter arena, segment / chain / concat-view operands, work counts, scales as hex
  * floats) and every tensor line its sizes; lines that begin with "+" are extra: one per needed tensor the short form does not list, and a last one
- * with the plan's totals and the environment switches it was built under.  Two loads that print the same full text launch the same work. */
+ * with the plan's totals and the environment switches it was built under.  Two loads that print the same full text launch the same work.
+ * Only the full form shows the 1x1 chained to a fused cv1 + cv2 launch (the bottleneck's m.cv1 evaluated inside the launch that carries
+ * split_next): "split_chain S" behind "split_next", S = 0 for none, 1 / 2 for the side of the pair it reads, then the arena offset of its weight
+ * image; the chained op keeps its own line and is not launched.  MARS_HIP_NO_CHAIN=1 in the environment switches that pass off ("no_chain" in the
+ * last line); MARS_HIP_NO_SPLIT=1 and fusion level 0 switch it off together with the fused pair. */
 size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, char *out, size_t cap);
 mars_error_t mars_hip_load_memory_ex(const void *data, size_t size, unsigned flags,
                                      mars_model_t **model);

@@ -233,6 +233,27 @@ __device__ __forceinline__ void requant_pack_two(const int (&a)[16], float cs0, 
 #pragma unroll
     for (int g = 0; g < 4; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
+// ... of the 8 values of the 1x1 chained to one side of that pair, through a fourth table at LDS bytes 1536..2047
+__device__ __forceinline__ void requant_pack_chain(const int (&a)[8], float cs, uint32_t (&pk)[2]) {
+    const float cs2 = cs * 2.0f;
+    const int klo = -256, khi = 255;
+    int q[8], v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int k = (int)((float)a[i] * cs2);
+        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(q[i]) : "v"(k), "v"(klo), "v"(khi));
+    }
+#pragma unroll
+    for (int g = 0; g < 2; g++)
+        asm volatile("ds_read_i8 %0, %4 offset:1792\n\tds_read_i8 %1, %5 offset:1792\n\t"
+                     "ds_read_i8 %2, %6 offset:1792\n\tds_read_i8 %3, %7 offset:1792"
+                     : "=&v"(v[4 * g]), "=&v"(v[4 * g + 1]), "=&v"(v[4 * g + 2]), "=&v"(v[4 * g + 3])
+                     : "v"(q[4 * g]), "v"(q[4 * g + 1]), "v"(q[4 * g + 2]), "v"(q[4 * g + 3])
+                     : "memory");
+    wait_lds_values<8>(v);
+#pragma unroll
+    for (int g = 0; g < 2; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+}
 template <int NV, bool HAS_LUT, bool SAFE, bool LUT0, bool ADD = false, bool FAST = false>
 __device__ __forceinline__ void requant_pack(const int (&a)[NV], float cs, int lo, const uint8_t *lut128, uint32_t (&pk)[NV / 4],
                                              const uint32_t *xw = nullptr, const add_args_t *ga = nullptr) {

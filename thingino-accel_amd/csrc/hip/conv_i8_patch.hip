@@ -101,7 +101,15 @@ __device__ __forceinline__ void barrier_lds() {
 // for both sides' table reads: row by row in one pass, every row paid the fragment reads and two table round trips of its own (measured
 // slower).  The image (mhip_conv_i8_split_pack: 64 rows x 64 bytes, then 64 bias rows) stays resident where POST keeps cv3's; the
 // k x k result itself is never stored.
-template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false, bool SPLIT = false>
+//
+// CHAIN (SPLIT only: the bottleneck's m.cv1, a 1x1 from 32 to 32 channels that reads one side of the pair): after requant_pack_two the lane's
+// two packed words of that side are 8 consecutive input channels of m.cv1 -- B-operand chunk g = {w0, w1, 0, 0} of its ONLY K step, against an
+// image (mhip_conv_i8_chain_pack: 32 rows x 64 bytes, then 32 bias rows, behind the pair's) whose K order has input channel c at byte
+// (c >> 3) * 16 + (c & 7) and zeros in every chunk's upper half.  Both sides are stored as before (cv1 is also the bottleneck's shortcut); the
+// chained words of all rows are kept, then the stage repeats the pair's shape: fragments and bias rows once per tile, all rows' two MFMAs back
+// to back, and row by row a requantisation with m.cv1's scale through its table (LDS bytes 1536..2047), one wait and one 8-byte store into
+// m.cv1's tensor.  By then the pair's accumulators are dead: the form needs no more registers than the plain one.  The side is wave-uniform.
+template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false, bool SPLIT = false, bool CHAIN = false>
 __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p, const int k64, const int tiles_x,
                                                           const int tiles_y, const unsigned ntiles_all, const int PH,
                                                           const int PW, const int PWP, const int PWH, const int nblk,
@@ -118,7 +126,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     const int nks = k64 / BK;
     constexpr int NPO = 2 * BN;                            // POST: cv3's input and output channels
     static_assert(!SPLIT || (BN == 64 && HAS_LUT && !PRE && !POST), "SPLIT: one 64-channel tile, no other stage");
-    constexpr int LB = LUTB + ((PRE || POST) ? 512 : 0) + (SPLIT ? 1024 : 0); // PRE / POST: the 1x1's table behind the main one; SPLIT: two
+    static_assert(!CHAIN || SPLIT, "CHAIN: a stage of the SPLIT form");
+    constexpr int LB = LUTB + ((PRE || POST) ? 512 : 0) + (SPLIT ? 1024 : 0) + (CHAIN ? 512 : 0); // PRE / POST: the 1x1's table behind the main one; SPLIT: two; CHAIN: a third
     int *dutab = (int *)(dynlds + LB);                     // [nks][4] unit offsets of the K chunks
     int8_t *wl = dynlds + LB + ((nks * 16 + 255) & ~255);   // [nks][BN][64], swizzled like the ring tiles
     const int patch_bytes = nblk * 1024;                   // whole 1 KB blocks (one wave-instruction of LDS-DMA each)
@@ -127,7 +136,9 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     const int *pbl = (const int *)(pwl + NPO * NPO);
     int8_t *swl = w1l;                                     // SPLIT: [64 rows: side, 32 channels][64] weights of cv1 and cv2, then their 64 bias rows
     const int *sbl = (const int *)(swl + 64 * BK);
-    int8_t *patch0 = w1l + (PRE ? p.in_c * BK : 0) + (POST ? NPO * NPO + NPO * 4 : 0) + (SPLIT ? 64 * BK + 64 * 4 : 0);
+    int8_t *cwl = swl + 64 * BK + 64 * 4;                  // CHAIN: [32 rows][64] weights of m.cv1, then its 32 bias rows
+    const int *cbl = (const int *)(cwl + 32 * BK);
+    int8_t *patch0 = w1l + (PRE ? p.in_c * BK : 0) + (POST ? NPO * NPO + NPO * 4 : 0) + (SPLIT ? 64 * BK + 64 * 4 : 0) + (CHAIN ? 32 * BK + 32 * 4 : 0);
     int8_t *tpatch = patch0 + ring * patch_bytes;          // PRE: the patch of t
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -162,6 +173,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
         }
         if (tid < 64) ((int *)(swl + 64 * BK))[tid] = ((const int *)(p.split_w + 64 * BK))[tid];
     }
+    if (CHAIN) { // LDS 1536..2047: m.cv1's table
+        if (tid >= 128) ((uint32_t *)slut)[tid + 256] = ((const uint32_t *)p.chain_lut2)[tid - 128];
+        if (tid >= 64 && tid < 96) ((int *)(cwl + 32 * BK))[tid - 64] = ((const int *)(p.chain_w + 32 * BK))[tid - 64];
+    }
     // K chunk table: chunk (ks, f) -> kernel row ky, column kx, channel chunk
     const int rowbytes = p.kw * C, kbytes = p.kh * rowbytes;
     for (int i = tid; i < nks * 4; i += NTHREADS) {
@@ -191,6 +206,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
             for (int i = wv; i < NPO * NPO / 1024; i += 4) glds16(p.post_w + i * 1024 + lane * 16, pwl + i * 1024);
         if (SPLIT) // likewise: 4 KB, one instruction per wave
             glds16(p.split_w + wv * 1024 + lane * 16, swl + wv * 1024);
+        if (CHAIN && wv < 2) // 2 KB
+            glds16(p.chain_w + wv * 1024 + lane * 16, cwl + wv * 1024);
     }
     // this lane's units of the patch DMA: instruction n of wave wv fills the 1 KB block n*4 + wv = physical units
     // (n*4+wv)*64 + lane; blocks at or beyond nblk do not exist (that instruction is not issued)
@@ -260,6 +277,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? p.split_out[0] : (POST ? p.post_out : p.out), 0, (int)out_bytes, 0x00020000);
     const unsigned out_bytes1 = SPLIT ? (unsigned)(p.frames - 1) * (unsigned)p.split_out_stride[1] + (unsigned)(p.out_h * p.out_w) * 32u : 0u;
     const __amdgpu_buffer_rsrc_t orsrc1 = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? p.split_out[1] : p.out, 0, (int)out_bytes1, 0x00020000);
+    // (CHAIN: m.cv1's tensor, a resource and an extent of its own)
+    const unsigned out_bytes2 = CHAIN ? (unsigned)(p.frames - 1) * (unsigned)p.chain_out_stride + (unsigned)(p.out_h * p.out_w) * 32u : 0u;
+    const __amdgpu_buffer_rsrc_t orsrc2 = __builtin_amdgcn_make_buffer_rsrc(CHAIN ? p.chain_out : p.out, 0, (int)out_bytes2, 0x00020000);
+    const bool cside1 = CHAIN && p.chain_side == 2; // the chained 1x1 reads side 1 (cv2's)
     // the residual operand of a fused Add has the output's layout: same offsets, same extent
     const bool has_add = !SPLIT && p.add != nullptr;
     // residual staging: per wave WPX rows of 64 lanes x 16 bytes (BN 64) or 2 x 64 lanes x 4 bytes (BN 32), behind the patches
@@ -271,8 +292,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
     const int NR = has_add || POST ? NRI : 0;
     // vector-memory operations of a tile behind its patch request: the stores (POST: cv3's, 16 bytes each), and y2's rows where an Add
     // went through the staging area first
-    // (SPLIT: no rows, two 8-byte stores per tile row -- one per side -- all behind the patch request like the plain form's)
-    const int ntail = POST ? (has_add ? NRI : 0) + WPX * (NPO / 64) : (SPLIT ? 2 * WPX : NST);
+    // (SPLIT: no rows, two 8-byte stores per tile row -- one per side -- all behind the patch request like the plain form's; CHAIN: a third)
+    const int ntail = POST ? (has_add ? NRI : 0) + WPX * (NPO / 64) : (SPLIT ? (CHAIN ? 3 : 2) * WPX : NST);
     const int ppstride = p.post_out_pix_stride ? p.post_out_pix_stride : NPO;
     // POST: one staging row per tile row from a dense NHWC tensor of BN channels (the Add's operand, y2): this lane's 4 * WOC bytes
     auto issue_rows = [&](const int8_t *base, size_t fstride, int tx, int ty, unsigned f) {
@@ -586,6 +607,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 for (int r = 0; r < 4; r++) sc[u][r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(sw4[r], b0, sb4[r], 0, 0, 0);
             }
             const unsigned fo0 = f * (unsigned)p.split_out_stride[0], fo1 = f * (unsigned)p.split_out_stride[1];
+            uint32_t ck[CHAIN ? WPX : 1][2]; // CHAIN: the chained side's packed words of every row, m.cv1's operand
 #pragma unroll
             for (int u = 0; u < WPX; u++) {
                 int a2[16];
@@ -598,6 +620,40 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_patch(const mhip_conv_i8_t p
                 const int voff0 = voffs[u] >= 0 ? voffs[u] + (int)fo0 : -1, voff1 = voffs[u] >= 0 ? voffs[u] + (int)fo1 : -1;
                 __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk4[0], (int)pk4[1]}, orsrc, voff0, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk4[2], (int)pk4[3]}, orsrc1, voff1, 0, 0);
+                if (CHAIN) {
+                    ck[CHAIN ? u : 0][0] = cside1 ? pk4[2] : pk4[0];
+                    ck[CHAIN ? u : 0][1] = cside1 ? pk4[3] : pk4[1];
+                }
+            }
+            if (CHAIN) {
+                // m.cv1's fragments once per tile (rows s4 * 16 ..: this lane's channels (lane >> 4) * 8 + s4 * 4 .. + 3), every row's two MFMAs,
+                // then per row one wait for its eight table reads
+                v4i cw4[2], cb4[2];
+#pragma unroll
+                for (int r = 0; r < 2; r++) {
+                    cw4[r] = *(const v4i *)(cwl + lds_off(r * 16 + frow, fchunk));
+                    cb4[r] = *(const v4i *)(cbl + r * 16 + fchunk * 4);
+                }
+                v4i cc[WPX][2];
+#pragma unroll
+                for (int u = 0; u < WPX; u++) {
+                    const v4i b0 = {(int)ck[CHAIN ? u : 0][0], (int)ck[CHAIN ? u : 0][1], 0, 0};
+#pragma unroll
+                    for (int r = 0; r < 2; r++) cc[u][r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(cw4[r], b0, cb4[r], 0, 0, 0);
+                }
+                const unsigned fo2 = f * (unsigned)p.chain_out_stride;
+#pragma unroll
+                for (int u = 0; u < WPX; u++) {
+                    int a1[8];
+#pragma unroll
+                    for (int r = 0; r < 2; r++)
+#pragma unroll
+                        for (int e = 0; e < 4; e++) a1[r * 4 + e] = cc[u][r][e];
+                    uint32_t pk2[2];
+                    requant_pack_chain(a1, p.chain_cs, pk2);
+                    const int voff2 = voffs[u] >= 0 ? voffs[u] + (int)fo2 : -1;
+                    __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk2[0], (int)pk2[1]}, orsrc2, voff2, 0, 0);
+                }
             }
         }
         if (POST) {
@@ -711,10 +767,18 @@ static bool patch_geom(const mhip_conv_i8_t *p, int th, patch_geom_t *g) {
         for (int i = 0; i < 2; i++)
             if ((long)(p->frames - 1) * (long)p->split_out_stride[i] + (long)p->out_h * p->out_w * 32 > 0x7fffffffL) return false;
     }
+    // the 1x1 chained to one side of the pair (the bottleneck's m.cv1): + its table, its weights and bias rows; 32 channels per pixel, dense, within
+    // 31-bit offsets, in a tensor that is neither side's
+    const bool chain = p->chain_side != 0;
+    if (chain) {
+        if (!split || (p->chain_side != 1 && p->chain_side != 2) || !p->chain_w || !p->chain_lut2 || !p->chain_out || p->chain_out == p->split_out[0] ||
+            p->chain_out == p->split_out[1] || (long)(p->frames - 1) * (long)p->chain_out_stride + (long)p->out_h * p->out_w * 32 > 0x7fffffffL)
+            return false;
+    }
     const size_t pb = (size_t)g->nblk * 1024;
     const size_t radd = p->add || post ? (size_t)4 * (th / 4) * (g->bn == 64 ? 1024 : 512) : 0; // residual staging rows of the 4 waves
     const size_t fixed = LUTB + (pre ? 512 + (size_t)C * BK + pb : 0) + (post ? 512 + (size_t)4 * g->bn * g->bn + (size_t)8 * g->bn : 0) +
-                         (split ? 1024 + (size_t)64 * BK + 64 * 4 : 0) +
+                         (split ? 1024 + (size_t)64 * BK + 64 * 4 : 0) + (chain ? 512 + (size_t)32 * BK + 32 * 4 : 0) +
                          (((size_t)g->nks * 16 + 255) & ~(size_t)255) + (size_t)g->nks * g->bn * BK + radd;
     const size_t budget = patch_lds_budget(g->bn);
     if (fixed + pb > budget) return false;
@@ -738,9 +802,9 @@ static inline long post_out_bytes(const mhip_conv_i8_t *p) { // bytes from p->po
 static inline long split_out_bytes(const mhip_conv_i8_t *p, int side) { // ... of the pair's side
     return (long)(p->frames - 1) * (long)p->split_out_stride[side] + (long)p->out_h * p->out_w * 32;
 }
-template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false, bool SPLIT = false>
+template <int TH, int BN, bool HAS_LUT, bool PRE = false, bool POST = false, bool SPLIT = false, bool CHAIN = false>
 static int launch_patch_t(const mhip_conv_i8_t *p, int k64, const patch_geom_t &g) {
-    auto kern = conv_i8_patch<TH, BN, HAS_LUT, PRE, POST, SPLIT>;
+    auto kern = conv_i8_patch<TH, BN, HAS_LUT, PRE, POST, SPLIT, CHAIN>;
     // workgroups the device holds at once at THIS layer's LDS size (small patches fit 3-4 per CU), cached per size
     static int cus = 0;
     static size_t slots_lds[8];
@@ -803,6 +867,11 @@ int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th) {
     (p->post_w ? launch_patch_t<T, B, true, false, true>(p, k64, g)                       \
      : p->pre_w ? launch_patch_t<T, B, true, true>(p, k64, g)                             \
                 : (p->lut ? launch_patch_t<T, B, true>(p, k64, g) : launch_patch_t<T, B, false>(p, k64, g)))
+    if (p->split_w && p->chain_side) { // (patch_geom: only with the pair)
+        if (th == 16) return launch_patch_t<16, 64, true, false, false, true, true>(p, k64, g);
+        if (th == 8) return launch_patch_t<8, 64, true, false, false, true, true>(p, k64, g);
+        return launch_patch_t<4, 64, true, false, false, true, true>(p, k64, g);
+    }
     if (p->split_w) { // (patch_geom: one 64-channel tile)
         if (th == 16) return launch_patch_t<16, 64, true, false, false, true>(p, k64, g);
         if (th == 8) return launch_patch_t<8, 64, true, false, false, true>(p, k64, g);
@@ -889,6 +958,23 @@ extern "C" size_t mhip_conv_i8_split_pack(const int8_t *packed0, const int32_t *
             for (int k = 0; k < 64; k++) out[(size_t)R * BK + ((((k >> 4) ^ ((R >> 1) & 2))) << 4) + (k & 15)] = packed[(size_t)src * 64 + k];
             ((int32_t *)(out + (size_t)64 * BK))[R] = bias ? bias[src] : 0;
         }
+    }
+    return bytes;
+}
+
+// the 1x1 chained to one side of the fused pair (chain_* fields): K position of input channel c, and the image
+extern "C" int mhip_conv_i8_chain_k(int c) { return (c >> 3) * 16 + (c & 7); }
+extern "C" size_t mhip_conv_i8_chain_pack(const int8_t *packed, const int32_t *bias, int8_t *out) {
+    const size_t bytes = (size_t)32 * BK + (size_t)32 * 4;
+    if (!packed || !out) return bytes;
+    memset(out, 0, bytes);
+    for (int oc = 0; oc < 32; oc++) {
+        const int R = mhip_conv_i8_split_row(0, oc), src = mhip_conv_i8_oc_row(oc, 32);
+        for (int c = 0; c < 32; c++) {
+            const int k = mhip_conv_i8_chain_k(c);
+            out[(size_t)R * BK + ((((k >> 4) ^ ((R >> 1) & 2))) << 4) + (k & 15)] = packed[(size_t)src * 64 + c];
+        }
+        ((int32_t *)(out + (size_t)32 * BK))[R] = bias ? bias[src] : 0;
     }
     return bytes;
 }

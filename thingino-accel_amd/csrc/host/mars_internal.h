@@ -97,6 +97,10 @@ typedef struct {
     int split_next;  /* fused cv1 + cv2: the NEXT TWO ops, a paired launch of 1x1s that alone read this convolution's result, are evaluated on its result
                         tile in the same launch (fuse_split; conv_i8_patch<SPLIT>); t_out is never written; both mates stay in the plan, are not launched */
     size_t split_w_off; /* ... their weights and bias rows as that kernel keeps them in LDS (mhip_conv_i8_split_pack) */
+    int split_chain; /* ... and the op behind them, a 1x1 from 32 to 32 channels that reads side split_chain - 1 of the pair (1 or 2, 0 = none: the
+                        bottleneck's m.cv1), is evaluated on that side's tile row in the same launch (fuse_split_chain; conv_i8_patch<CHAIN>); both
+                        sides are still written; that op stays in the plan too, is not launched */
+    size_t chain_w_off; /* ... its weights and bias rows as that kernel keeps them in LDS (mhip_conv_i8_chain_pack) */
     size_t w2_off;   /* a second image of the weights, or NO_OFF: the RGB stem's as conv_i8_rgb keeps them in LDS
                         (mhip_conv_i8_rgb_pack), or (w2_rows) a deep 3x3 layer's as conv_i8_rows streams them (mhip_conv_i8_rows_pack) */
     int w2_rows;
@@ -120,7 +124,7 @@ typedef struct {
 typedef struct {
     int fusion; /* MARS_HIP_FUSION, default 1 */
     unsigned no_fuse_lut : 1, no_nhwc_internal : 1, no_vconcat_q : 1, no_pair_f32 : 1, no_rec : 1, no_zero_tail : 1, no_vconcat_f32 : 1,
-        no_rowpad : 1, no_post : 1, no_split : 1; /* MARS_HIP_NO_*: set = that pass is off */
+        no_rowpad : 1, no_post : 1, no_split : 1, no_chain : 1; /* MARS_HIP_NO_*: set = that pass is off */
     size_t rec_limit;        /* MARS_HIP_REC_LIMIT: bytes all frames of a tensor may span under 32-bit offsets (rec_pairs, virtual_concat_f32) */
     size_t vconcat_limit;    /* MARS_HIP_VCONCAT_LIMIT: ... the output of a segmented convolution (alloc_batch) */
     size_t bottleneck_limit; /* MARS_HIP_BOTTLENECK_LIMIT: largest batch that keeps fused bottlenecks, 0 = no limit (alloc_batch) */
@@ -136,6 +140,7 @@ typedef struct mars_model_ext {
     int no_bottleneck; /* fused bottlenecks (fusion level 2) switched off: one of them cannot launch at this batch */
     int no_post;       /* fused cv3 launches (fuse_post) switched off: one of them cannot launch at this batch (32-bit output offsets) */
     int no_split;      /* fused cv1 + cv2 launches (fuse_split) switched off: likewise */
+    int no_chain;      /* the 1x1 chained to such a launch (fuse_split_chain) switched off: likewise */
     int rec_frames;    /* rec_pairs: the batch the record-format pairs were chosen for (0 = one frame); a pair whose tensors reach 4 GiB at that batch is left alone */
     int rec_skipped;   /* ... some pair was left alone for that reason (a smaller batch may take it) */
     size_t rec_max_frames; /* ... the largest batch every chosen pair still fits */
@@ -264,6 +269,7 @@ MARS_INTERNAL void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i
 MARS_INTERNAL int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t out_stride);
 MARS_INTERNAL int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames);
 MARS_INTERNAL int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames);
+MARS_INTERNAL int conv_i8_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, const mars_op_t *d, int side, int frames);
 /* ... the passes, in the order build_plan calls them (f32: 0 = the int8 form, 1 = the float32 form) */
 MARS_INTERNAL void plan_layer(mars_model_ext_t *m, int li);
 MARS_INTERNAL void fold_silu(mars_model_ext_t *m, int f32);
@@ -278,6 +284,7 @@ MARS_INTERNAL void pair_convs(mars_model_ext_t *m);
 MARS_INTERNAL void fuse_bottleneck(mars_model_ext_t *m);
 MARS_INTERNAL void fuse_post(mars_model_ext_t *m);
 MARS_INTERNAL void fuse_split(mars_model_ext_t *m);
+MARS_INTERNAL void fuse_split_chain(mars_model_ext_t *m);
 MARS_INTERNAL void pad_output_rows(mars_model_ext_t *m);
 MARS_INTERNAL void virtual_concat_q(mars_model_ext_t *m);
 MARS_INTERNAL void f32_policy(mars_model_ext_t *m);

@@ -47,6 +47,7 @@ void plan_switches_read(plan_switches_t *sw, int at_load) {
     sw->no_rowpad = getenv("MARS_HIP_NO_ROWPAD") != NULL;
     sw->no_post = getenv("MARS_HIP_NO_POST") != NULL;
     sw->no_split = getenv("MARS_HIP_NO_SPLIT") != NULL;
+    sw->no_chain = getenv("MARS_HIP_NO_CHAIN") != NULL;
     /* (tests lower the limits to see the per-batch decisions with small tensors) */
     sw->rec_limit = (e = getenv("MARS_HIP_REC_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0xfffffff0u;
     sw->vconcat_limit = (e = getenv("MARS_HIP_VCONCAT_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0x7fffffffu;
@@ -190,6 +191,7 @@ mars_error_t build_plan(mars_model_ext_t *m) {
         if (m->sw.fusion >= 2 && !m->no_bottleneck) fuse_bottleneck(m); /* opt-in (level 2); after pairing: a paired launch stays a pair */
         fuse_post(m);     /* after both: a paired launch stays a pair, an op carrying `pre` never takes `post` (level 2 keeps its plans) */
         fuse_split(m);    /* after pairing: it takes whole pairs; an op carrying `pre` or `post_next` is left alone */
+        fuse_split_chain(m); /* after fuse_split: it extends its launches; after fuse_bottleneck: a 1x1 folded into a 3x3 as `pre` is no op any more */
         pad_output_rows(m);
         virtual_concat_q(m); /* last of the int8 passes: it splits a convolution in two launches over one output tensor */
     } else {
@@ -238,8 +240,8 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
      * alone at a larger batch may fit now) */
     const int rec_replan = (size_t)n > m->rec_max_frames || (m->rec_skipped && n < m->rec_frames);
     m->rec_frames = n;
-    if (m->no_vconcat || m->no_bottleneck || m->no_post || m->no_split || rec_replan) {
-        m->no_vconcat = m->no_bottleneck = m->no_post = m->no_split = 0;
+    if (m->no_vconcat || m->no_bottleneck || m->no_post || m->no_split || m->no_chain || rec_replan) {
+        m->no_vconcat = m->no_bottleneck = m->no_post = m->no_split = m->no_chain = 0;
         mars_error_t e = build_plan(m);
         if (e == MARS_OK) e = upload_params(m);
         if (e != MARS_OK) return e;
@@ -282,6 +284,19 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
             if (op->kind != OP_CONV_I8 || !op->post_next) continue;
             if (!conv_i8_post_fits(m, op, op + 1, n)) {
                 m->no_post = 1;
+                mars_error_t e = build_plan(m);
+                if (e == MARS_OK) e = upload_params(m);
+                if (e != MARS_OK) return e;
+                break;
+            }
+        }
+    /* the 1x1 chained to a fused cv1 + cv2 launch likewise (its output's 31-bit offsets); asked first: without it the pair may still fit */
+    if (!m->no_chain)
+        for (int i = 0; i + 3 < m->n_ops; i++) {
+            const mars_op_t *op = &m->ops[i];
+            if (op->kind != OP_CONV_I8 || !op->split_next || !op->split_chain) continue;
+            if (!conv_i8_chain_fits(m, op, op + 1, op + 2, op + 3, op->split_chain, n)) {
+                m->no_chain = 1;
                 mars_error_t e = build_plan(m);
                 if (e == MARS_OK) e = upload_params(m);
                 if (e != MARS_OK) return e;
@@ -468,6 +483,8 @@ static int describe_op_full(const mars_op_t *o, char *line, size_t cap, int k) {
     if (o->post_next) ADD(" %zd", (ssize_t)o->post_w_off);
     ADD(" split_next %d", o->split_next);
     if (o->split_next) ADD(" %zd", (ssize_t)o->split_w_off);
+    ADD(" split_chain %d", o->split_chain);
+    if (o->split_chain) ADD(" %zd", (ssize_t)o->chain_w_off);
     ADD(" pre %d", o->pre);
     if (o->pre) ADD(" %zd %zd %zd %a", (ssize_t)o->pre_w_off, (ssize_t)o->pre_b_off, (ssize_t)o->pre_lut2_off, (double)o->pre_cs);
     ADD(" macs %a bytes %a prof_kind %d", o->macs, o->bytes, o->prof_kind);
@@ -522,10 +539,10 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
     if (full) {
         const plan_switches_t *w = &m->sw;
         snprintf(line, sizeof line, "+plan n_ops %d arena_size %zu scratch_per_frame %zu blob_mirror_bytes %zu rec_max_frames %zu rec_skipped %d f32_mode %d | fusion %d"
-                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d no_post %d no_split %d rec_limit %zu"
+                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d no_post %d no_split %d no_chain %d rec_limit %zu"
                  " vconcat_limit %zu bottleneck_limit %zu\n", m->n_ops, m->arena_size, m->scratch_per_frame, m->blob_mirror_bytes, m->rec_max_frames, m->rec_skipped,
                  m->plan_f32_mode, w->fusion, w->no_fuse_lut, w->no_nhwc_internal, w->no_vconcat_q, w->no_pair_f32, w->no_rec, w->no_zero_tail, w->no_vconcat_f32,
-                 w->no_rowpad, w->no_post, w->no_split, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
+                 w->no_rowpad, w->no_post, w->no_split, w->no_chain, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
         EMIT();
     }
 #undef EMIT

@@ -716,6 +716,20 @@ int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars
     return mhip_conv_i8_split_ok(&p);
 }
 
+/* ... and with the 1 x 1 `d` behind them, which reads side `side` - 1 of the pair, chained into that launch as well (fuse_split_chain)? */
+int conv_i8_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, const mars_op_t *d, int side, int frames) {
+    mhip_conv_i8_t p;
+    if (a->t_in[0] < 0 || a->t_out < 0 || b->t_out < 0 || c->t_out < 0 || d->t_out < 0 || (side != 1 && side != 2)) return 0;
+    conv_i8_geometry(a, frames, &p);
+    p.in_stride = planned_stride(&m->mt[a->t_in[0]]); p.out_stride = planned_stride(&m->mt[a->t_out]);
+    p.lut = p.lut2 = p.split_lut2[0] = p.split_lut2[1] = p.chain_lut2 = (const uint8_t *)a;
+    p.split_w = p.chain_w = (const int8_t *)a;
+    p.split_out[0] = (int8_t *)m; p.split_out[1] = (int8_t *)m + 1; p.chain_out = (int8_t *)m + 2; /* (three tensors: any three addresses) */
+    p.split_out_stride[0] = planned_stride(&m->mt[b->t_out]); p.split_out_stride[1] = planned_stride(&m->mt[c->t_out]);
+    p.chain_side = side; p.chain_out_stride = planned_stride(&m->mt[d->t_out]);
+    return mhip_conv_i8_split_ok(&p);
+}
+
 /* ------------------------------------------------------------------ fusion
  * conv -> sigmoid -> mul (SiLU as exported to ONNX) collapses into the conv
  * epilogue: every value of the chain is a function of the conv's int8 result
@@ -1331,6 +1345,57 @@ void fuse_split(mars_model_ext_t *m) {
     free(readers);
 }
 
+/* The bottleneck's m.cv1 inside the launch that already runs cv1 + cv2: A carries split_next with mates B and C; D = a 1 x 1 SiLU convolution from 32
+ * to 32 channels that reads exactly B's or C's output over the same map.  A's launch (conv_i8_patch<CHAIN>) holds that side's requantised tile row
+ * in registers the moment it stores it: it is the B operand of D's only K step.  D's input is still written (other ops read it: cv1's tensor is the
+ * bottleneck's shortcut), only D's read of it and D's launch go.  Same bytes: D sees exactly the int8 values its input tensor holds.  All four ops
+ * stay in the plan: A records the side (split_chain = 1 for B's, 2 for C's) and the image, D is skipped by the run loop like B and C.  D is moved up
+ * behind C under pair_up's rule (nothing in between touches its output or writes its input); the first op that qualifies is taken.  Only where the
+ * device code takes it (conv_i8_chain_fits); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_chain). */
+static int chain_mate_ok(const mars_op_t *d, const mars_op_t *a) {
+    return d->kind == OP_CONV_I8 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && !d->pt && !d->pl && d->safe && !d->nchw && !d->out_nchw && !d->add_t &&
+           !d->chain_n && !d->store_c && !d->in_byte_off && !d->out_byte_off && !d->out_pix_stride && !d->out_ch_off && d->lut_off != NO_OFF &&
+           d->lut2_off != NO_OFF && !d->nseg && !d->pre && !d->pair_next && !d->post_next && !d->split_next && d->n_in == 1 && d->in_c == 32 && d->out_c == 32 &&
+           d->oc_pad == 32 && d->row_pad == 32 && d->in_h == a->out_h && d->in_w == a->out_w && d->out_h == a->out_h && d->out_w == a->out_w;
+}
+void fuse_split_chain(mars_model_ext_t *m) {
+    if (m->sw.no_chain || m->no_chain || m->sw.no_split || m->no_split) return;
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
+    for (int i = 0; i + 3 < m->n_ops; i++) {
+        mars_op_t *a = &m->ops[i];
+        if (a->kind != OP_CONV_I8 || !a->split_next || a->split_chain) continue;
+        const int O0 = a[1].t_out, O1 = a[2].t_out;
+        for (int j = i + 3; j < m->n_ops && j <= i + 48; j++) {
+            const mars_op_t *d = &m->ops[j];
+            if (!chain_mate_ok(d, a) || m->ops[j - 1].pair_next || m->ops[j - 1].post_next || m->ops[j - 1].split_next ||
+                (j >= 2 && m->ops[j - 2].split_next))
+                continue; /* (a mate of another launch is not D) */
+            const int side = d->t_in[0] == O0 ? 1 : (d->t_in[0] == O1 ? 2 : 0), O = d->t_out;
+            if (!side || O < 0 || O == O0 || O == O1 || O == a->t_out || writers[O] != 1 || m->mt[O].io_in || m->mt[O].is_weight || m->mt[O].pix_stride ||
+                op_reads(a, O) || op_reads(d, O))
+                continue;
+            if (touched_between(m, i + 3, j, O, USE_READ | USE_WRITE) || touched_between(m, i + 3, j, d->t_in[0], USE_WRITE)) continue;
+            if (!conv_i8_chain_fits(m, a, a + 1, a + 2, d, side, 1)) continue; /* one frame: alloc_batch asks again for its batch */
+            const size_t bytes = mhip_conv_i8_chain_pack(NULL, NULL, NULL);
+            const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
+            if (off == NO_OFF) { free(readers); return; }
+            mhip_conv_i8_chain_pack((const int8_t *)(m->arena_host + d->w_off), d->b_off != NO_OFF ? (const int32_t *)(m->arena_host + d->b_off) : NULL,
+                                    (int8_t *)(m->arena_host + off));
+            if (j > i + 3) {
+                const mars_op_t moved = *d;
+                memmove(&m->ops[i + 4], &m->ops[i + 3], sizeof(mars_op_t) * (size_t)(j - i - 3));
+                m->ops[i + 3] = moved;
+            }
+            a->split_chain = side;
+            a->chain_w_off = off;
+            break;
+        }
+        i += 2; /* (B and C carry no split_next) */
+    }
+    free(readers);
+}
+
 /* Ragged pixel rows of graph outputs (the 255-channel YOLO heads) are kept at a 16-byte-aligned pitch on the device:
  * the producing convolution then takes the aligned epilogue (16-byte stores straight from registers, every launch
  * form) instead of the LDS-staged copy-out with 8+4+2+1-byte row tails.  Only tensors nothing in the graph reads:
@@ -1875,6 +1940,11 @@ void plan_check(mars_model_ext_t *m) {
                                    !m->ops[i + 1].pair_next || m->ops[i + 2].pair_next || m->ops[i + 1].n_in != 1 || m->ops[i + 2].n_in != 1 ||
                                    m->ops[i + 1].t_in[0] != o->t_out || m->ops[i + 2].t_in[0] != o->t_out || o->post_next || o->pair_next || o->pre || o->add_t))
             why = "split_next without its pair of 1x1s behind it";
+        else if (o->split_chain && (!o->split_next || i + 3 >= m->n_ops || !chain_mate_ok(&m->ops[i + 3], o) || (o->split_chain != 1 && o->split_chain != 2) ||
+                                    m->ops[i + 3].t_in[0] != m->ops[i + o->split_chain].t_out || m->ops[i + 3].t_out < 0 ||
+                                    m->ops[i + 3].t_out == m->ops[i + 1].t_out || m->ops[i + 3].t_out == m->ops[i + 2].t_out || m->ops[i + 3].t_out == o->t_out ||
+                                    m->mt[m->ops[i + 3].t_out].pix_stride || o->chain_w_off == NO_OFF))
+            why = "split_chain without its 1x1 behind the pair";
         for (int k = 0; !why && k < o->nseg; k++)
             if (!op_reads(o, o->seg_t[k])) why = "a seg_t is not among t_in";
         for (int k = 0; !why && k < o->vc_n; k++)

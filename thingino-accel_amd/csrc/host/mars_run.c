@@ -110,6 +110,16 @@ static void conv_i8_split_params(const mars_model_ext_t *m, const mars_op_t *op,
     }
 }
 
+/* ... + the 1x1 chained to one side of that pair (fuse_split_chain) */
+static void conv_i8_chain_params(const mars_model_ext_t *m, const mars_op_t *op, const mars_op_t *d, mhip_conv_i8_t *p) {
+    uint8_t *A = m->arena_dev;
+    p->chain_side = op->split_chain;
+    p->chain_w = (const int8_t *)(A + op->chain_w_off);
+    p->chain_lut2 = A + d->lut2_off;
+    p->chain_cs = d->cs;
+    p->chain_out = (int8_t *)tdev(m, d->t_out); p->chain_out_stride = tstride(m, d->t_out);
+}
+
 static void conv_f32_params(mars_model_ext_t *m, mars_op_t *op, mhip_conv_f32_t *p) {
     const int B = m->run_frames;
     uint8_t *A = m->arena_dev;
@@ -368,9 +378,11 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
         }
         mars_op_t *mate = (op->pair_next || op->post_next || op->split_next) && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
         mars_op_t *mate2 = op->split_next && i + 2 < m->n_ops ? &m->ops[i + 2] : NULL; /* (a fused pair: both mates' outputs are this launch's) */
+        mars_op_t *mate3 = op->split_next && op->split_chain && i + 3 < m->n_ops ? &m->ops[i + 3] : NULL; /* (... and the chained 1x1's) */
         if (wait_tail && ((op->t_out >= 0 && (m->mt[op->t_out].io_out || m->mt[op->t_out].tail_read)) ||
                           (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)) ||
-                          (mate2 && mate2->t_out >= 0 && (m->mt[mate2->t_out].io_out || m->mt[mate2->t_out].tail_read)))) {
+                          (mate2 && mate2->t_out >= 0 && (m->mt[mate2->t_out].io_out || m->mt[mate2->t_out].tail_read)) ||
+                          (mate3 && mate3->t_out >= 0 && (m->mt[mate3->t_out].io_out || m->mt[mate3->t_out].tail_read)))) {
             /* the previous batch's detection tail (auxiliary stream) still reads the graph
              * outputs (or the raw heads it decodes): order this launch behind it */
             mhip_stream_wait(sid, m->ev_tail_done);
@@ -389,11 +401,12 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
         if (op->split_next) { /* cv1 + cv2 inside this launch (conv_i8_patch<SPLIT>): the plan holds them only where this form runs */
             mhip_conv_i8_t pa;
             rc = -1;
-            if (mate && mate2) {
+            if (mate && mate2 && (mate3 || !op->split_chain)) {
                 conv_i8_split_params(m, op, mate, mate2, &pa);
+                if (mate3) conv_i8_chain_params(m, op, mate3, &pa);
                 rc = mhip_conv_i8(&pa);
             }
-            i += 2; /* both mates have run */
+            i += mate3 ? 3 : 2; /* both mates have run (and the chained 1x1) */
         } else if (mate && op->post_next) { /* cv3 inside this launch (conv_i8_patch<POST>): the plan holds it only where this form runs */
             mhip_conv_i8_t pa;
             conv_i8_post_params(m, op, mate, &pa);
@@ -423,8 +436,8 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             rc = launch_op(m, op);
         }
         { /* the relayout scratch's copy of a tensor dies with any write to that tensor */
-            const mars_op_t *w2[3] = {op, mate, mate2};
-            for (int q = 0; q < 3; q++)
+            const mars_op_t *w2[4] = {op, mate, mate2, mate3};
+            for (int q = 0; q < 4; q++)
                 if (w2[q] && op_writes(w2[q], m->scratch_t)) m->scratch_t = -1;
         }
         if (m->profiling) { /* level 2: one event per run of launches of the same kind (their sum lands on the last one) */
@@ -804,6 +817,7 @@ static mars_error_t autotune_model(mars_model_t *model, int reps) {
         if (op->pair_next || (i > 0 && m->ops[i - 1].pair_next)) continue; /* paired launches have one form */
         if (op->post_next || (i > 0 && m->ops[i - 1].post_next)) continue; /* ... and a fused cv3 goes with the launch its policy picks */
         if (op->split_next) continue;                                      /* ... as does a fused pair (its mates are a pair: skipped above) */
+        if (i >= 3 && m->ops[i - 3].split_chain) continue;                 /* ... and the 1x1 chained to it */
         mhip_conv_i8_t p;
         conv_i8_params(m, op, &p);
         int codes[32];

@@ -123,6 +123,15 @@ typedef struct {
     const uint8_t *split_lut2[2];
     float split_cs[2];
     int8_t *split_out[2];   size_t split_out_stride[2];
+    /* optional, with split_w only: a THIRD 1x1 stride-1 convolution with a fused SiLU table (the bottleneck's m.cv1, 32 -> 32 channels) that
+     * reads side chain_side - 1 (chain_side = 1 or 2, 0 = none), evaluated on that side's requantised tile row while it is still in
+     * registers.  Both sides are stored as without it.  chain_w = the image of mhip_conv_i8_chain_pack; its own half-step table, combined
+     * scale and output: a dense NHWC tensor of 32 channels */
+    int chain_side;
+    const int8_t *chain_w;
+    const uint8_t *chain_lut2;
+    float chain_cs;
+    int8_t *chain_out;      size_t chain_out_stride;
 } mhip_conv_i8_t;
 /* can the convolution described by *p take the pair of 1x1s behind it (split_* fields) in its launch?  (geometry only, at some tile height) */
 int mhip_conv_i8_split_ok(const mhip_conv_i8_t *p);
@@ -132,6 +141,13 @@ int mhip_conv_i8_split_ok(const mhip_conv_i8_t *p);
  * g * 8 + s * 4 + r of that side (mhip_conv_i8_split_row; tests) */
 size_t mhip_conv_i8_split_pack(const int8_t *packed0, const int32_t *bias0, const int8_t *packed1, const int32_t *bias1, int8_t *out);
 int mhip_conv_i8_split_row(int side, int oc);
+/* Bytes of, and (packed, out != NULL) the content of, the chained 1x1's image (chain_* fields): packed / bias = its packed weights
+ * [oc_pad = 32][k64 = 64] (input channels 0..31, then zeros) and bias rows as every conv_i8 launch reads them (bias NULL = zeros).
+ * 32 rows x 64 bytes in the kernel's LDS layout (chunk swizzle applied), then 32 bias rows; row mhip_conv_i8_split_row(0, oc) carries
+ * output channel oc; input channel c sits at K position (c >> 3) * 16 + (c & 7) -- a lane group's 8 bytes of one side, the upper 8 bytes
+ * of its 16-byte chunk are zero (mhip_conv_i8_chain_k; tests) */
+size_t mhip_conv_i8_chain_pack(const int8_t *packed, const int32_t *bias, int8_t *out);
+int mhip_conv_i8_chain_k(int c);
 /* can the convolution described by *p take a following 1x1 (post_* fields) in its launch?  (geometry only, at some tile height) */
 int mhip_conv_i8_post_ok(const mhip_conv_i8_t *p);
 /* Bytes of, and (packed, out != NULL) the content of, the 1x1's image for a fused launch of c = 32 / 64 channels: `packed` / `bias` = the
