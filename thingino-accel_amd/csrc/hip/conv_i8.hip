@@ -401,6 +401,32 @@ __device__ __forceinline__ void wait_vmcnt_at_most(int n) { // largest known-saf
 // [0, noc0) belong to the first, the rest to the second (`alt` = its output side).  The two workgroups that need a
 // pixel tile are neighbours in the XCD-aware block order, so the second one's input reads hit L2: the input is
 // read from HBM once instead of twice.
+// BOTH (BN == 128, sides of 64 channels): the same two convolutions in ONE 128-row tile.  Tile rows 0-63 are the first
+// convolution, rows 64-127 the second; with two waves along the channels the wave's column (wv / NWM) is its side, so
+// everything side-specific -- weight image, bias rows, scale, half-step table, output tensor -- is wave-uniform.  The
+// input K step is staged ONCE per ring stage for both sides (one address computation, one LDS-DMA), which also holds
+// for a never-materialised concat: the input comes from HBM once.  Weight rows are fetched in groups of 16, and a
+// wave fetches the row groups of its own side, so the source image is chosen per wave (no merged image on the host).
+// The second side's half-step table sits at LDS bytes 512..1023 (requant_pack_pre).
+// CHAIN (with BOTH): a 1x1 from 64 to 64 channels with a half-step table that reads side `side` - 1 (the bottleneck's m.cv1
+// behind cv1) is evaluated in that side's waves.  The 16 bytes a lane has just packed for a pixel subtile -- 16
+// consecutive channels of one pixel -- ARE the B operand of the 1x1's only K step; its 64 x 64 weights (the layer's own
+// packed image), bias rows and table (LDS bytes 1024..1535) stay resident.  One pixel subtile at a time: 16 accumulator
+// registers.  Those waves issue one more store per subtile (or, `elide`: the side has no other reader and is not
+// stored, the same number); the other side's waves store as before -- younger[] counts per wave.
+struct conv_chain_t {
+    const int8_t *w;
+    const int32_t *bias;
+    const uint8_t *lut2;
+    int8_t *out;
+    size_t out_stride;
+    unsigned out_bytes;
+    float cs;
+    int side, elide;
+};
+#define CHAIN_W_OFF (3 * LUTB)          // LDS: [table A][table B][table D][D's weights 64 x 64][D's bias rows][ring ...]
+#define CHAIN_B_OFF (CHAIN_W_OFF + 4096)
+#define CHAIN_LDS (LUTB + 4096 + 256)   // what CHAIN adds
 struct conv_out_side_t {
     int8_t *out;
     size_t out_stride;
@@ -411,30 +437,34 @@ struct conv_out_side_t {
     float cs;
     unsigned out_bytes;
 };
-template <int BPX, int BN, int STAGES, bool HAS_LUT, bool SEG = false, bool PAIR = false>
+template <int BPX, int BN, int STAGES, bool HAS_LUT, bool SEG = false, bool PAIR = false, bool BOTH = false, bool CHAIN = false>
 __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t pin, const unsigned total_pix, const int k64,
                                                             const int8_t *__restrict__ zeros, const unsigned noc,
                                                             const unsigned npt, const unsigned ngrp, const int lg_inc,
                                                             const unsigned kw_magic, const fastdiv_t dhw, const fastdiv_t dow,
                                                             const unsigned out_bytes_first, const conv_out_side_t alt,
                                                             const unsigned noc0, const int bufmode, const unsigned in_bytes,
-                                                            const int wres) {
+                                                            const int wres, const conv_chain_t ch) {
     // wres (host: 2-stage ring only): the weights of this workgroup's channel tile, all K steps, are fetched ONCE
     // into LDS behind the ring and stay there while the workgroup walks its pixel tiles; the ring then carries pixel
     // tiles only -- for 1x1 layers that halves the LDS-DMA bytes per tile
     ANAT_BEGIN();
     const int STAGE = wres ? BPX * BK : (BPX + BN) * BK;
-    constexpr int NWN = BN == 128 ? 2 : 1;
+    constexpr int NWN = BN >= 128 ? 2 : 1;
     constexpr int NWM = 4 / NWN;
     constexpr int WPX = BPX / NWM / 16;
     constexpr int WOC = BN / NWN / 16;
     constexpr int XI = BPX / 64;
-    constexpr int LW = BN >= 128 ? 2 : 1;
+    constexpr int LW = BN >= 128 ? BN / 64 : 1;
     constexpr int L = XI + LW;  // vector-memory instructions per wave per stage
-    constexpr int NST = WPX;    // ... and per tile epilogue
+    constexpr int NST = WPX * (WOC == 8 ? 2 : 1); // ... and per tile epilogue (WOC == 8: two 16-byte runs per pixel)
+    static_assert(!BOTH || ((BN == 128 || BN == 256) && HAS_LUT && !PAIR), "BOTH: two sides of 64 (128) channels with half-step tables in one 128 (256) row tile");
+    static_assert(BOTH || BN <= 128, "the 256-row tile exists for two sides of 128 channels only");
+    static_assert(!CHAIN || BN == 128, "CHAIN: sides of 64 channels");
+    static_assert(!CHAIN || BOTH, "CHAIN: a 1x1 behind one side of a one-tile pair");
     extern __shared__ __attribute__((aligned(16))) int8_t dynlds[];
     uint8_t *slut = (uint8_t *)dynlds; // LDS byte address 0 (requant_pack LUT0)
-    int8_t *lds = dynlds + LUTB;
+    int8_t *lds = dynlds + (BOTH ? 2 : 1) * LUTB + (CHAIN ? CHAIN_LDS : 0);
     lds_base_must_be_zero(dynlds);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -444,8 +474,9 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
     unsigned ot = id - grp * noc;
     mhip_conv_i8_t p = pin; // uniform; the second convolution of a pair swaps in its output side
     unsigned out_bytes = out_bytes_first;
-    if (PAIR && ot >= noc0) {
-        ot -= noc0;
+    const bool second = BOTH ? wv >= NWM : (PAIR && ot >= noc0); // uniform: this wave works for the second convolution
+    if (PAIR && second) ot -= noc0;
+    if (second) {
         p.lut2 = alt.lut2; // its own half-step table (the two convolutions have different scales)
         p.out = alt.out; p.out_stride = alt.out_stride; p.w = alt.w; p.bias = alt.bias; p.lut = alt.lut;
         p.out_c = alt.out_c; p.relu = alt.relu; p.out_pix_stride = alt.out_pix_stride; p.out_ch_off = alt.out_ch_off;
@@ -459,6 +490,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
     const unsigned hw = (unsigned)(p.out_h * p.out_w);
     const int wm = wv % NWM, wn = wv / NWM;
     const int pxw = wm * (WPX * 16), ocw = wn * (WOC * 16);
+    const int ocs = BOTH ? 0 : ocw; // the wave's first channel in ITS convolution (BOTH: a side is one wave column wide)
 
     // BN == 16 (round 6: out_c <= 16 -- the yolov5n models' first C3 -- ran 32-row tiles, half of every MFMA and of the requantisation for
     // channels that do not exist): ONE channel subtile.  The host packed weight rows and bias for two subtiles (MFMA row 4 g + r of subtile
@@ -467,13 +499,24 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
     v4i bias[WOC];
 #pragma unroll
     for (int s = 0; s < WOC; s++)
-        bias[s] = p.bias ? *(const v4i *)(p.bias + (BN == 16 ? packed_row16((lane >> 4) * 4) : oc0 + ocw + s * 16 + (lane >> 4) * 4)) : (v4i){0, 0, 0, 0};
+        bias[s] = p.bias ? *(const v4i *)(p.bias + (BN == 16 ? packed_row16((lane >> 4) * 4) : oc0 + ocs + s * 16 + (lane >> 4) * 4)) : (v4i){0, 0, 0, 0};
     if (HAS_LUT) {
-        if (p.lut2) { if (tid < 128) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.lut2)[tid]; }
+        if (BOTH) { // both sides' half-step tables, the second behind the first (host: both exist)
+            if (tid < 128) {
+                ((uint32_t *)slut)[tid] = ((const uint32_t *)pin.lut2)[tid];
+                ((uint32_t *)slut)[128 + tid] = ((const uint32_t *)alt.lut2)[tid];
+                if (CHAIN) ((uint32_t *)slut)[256 + tid] = ((const uint32_t *)ch.lut2)[tid];
+            }
+            if (CHAIN && tid < 64) ((int32_t *)(dynlds + CHAIN_B_OFF))[tid] = ch.bias ? ch.bias[tid] : 0;
+        } else if (p.lut2) { if (tid < 128) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.lut2)[tid]; }
         else if (tid < 64) ((uint32_t *)slut)[tid] = ((const uint32_t *)p.lut)[tid];
         __syncthreads();
     }
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)out_bytes, 0x00020000);
+    const bool chw = CHAIN && wn == ch.side - 1; // uniform: this wave's side feeds the chained 1x1
+    const bool store_own = !(chw && ch.elide);
+    const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(ch.out, 0, CHAIN ? (int)ch.out_bytes : 0, 0x00020000);
+    const int nstw = NST * ((store_own ? 1 : 0) + (chw ? 1 : 0)); // stores this wave issues per tile
 
     const int schunk = (lane & 3) ^ (((lane >> 4) & 1) << 1);
     const int8_t *xwin[XI];
@@ -515,7 +558,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
 #pragma unroll
     for (int j = 0; j < LW; j++) {
         wq[j] = BN >= 64 ? wv * LW + j : (BN == 16 ? 0 : (wv & 1));
-        const int wrow = BN == 16 ? packed_row16(lane >> 2) : oc0 + wq[j] * 16 + (lane >> 2);
+        // (BOTH: this wave's row groups are its own side's -- wq / 4 == wv / NWM -- and p.w is that side's 64-row image)
+        const int wrow = BN == 16 ? packed_row16(lane >> 2) : oc0 + (BOTH ? wq[j] & (BN / 32 - 1) : wq[j]) * 16 + (lane >> 2);
         wsrc[j] = p.w + (size_t)wrow * k64 + schunk * 16;
         wvoff[j] = wrow * k64 + schunk * 16;
     }
@@ -528,15 +572,16 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
         int8_t *sb = lds + stage * STAGE;
         const unsigned pos = (unsigned)(ks * BK + schunk * 16);
         if (SEG) {
+            // (pin: the input side is the same for both convolutions of a launch, and the indexed reads stay loads from the kernel arguments)
             // owner of channel c: the last segment that starts at or before it (unused segments start at INT_MAX)
-            auto owner = [&](int c) { return (c >= p.seg_c0[1]) + (c >= p.seg_c0[2]) + (c >= p.seg_c0[3]); };
+            auto owner = [&](int c) { return (c >= pin.seg_c0[1]) + (c >= pin.seg_c0[2]) + (c >= pin.seg_c0[3]); };
             const int sa = owner(ks * BK), sb2 = owner(ks * BK + 32); // uniform
             const bool hi = schunk >= 2;
-            const int8_t *base = hi ? p.seg_in[sb2] : p.seg_in[sa];
-            const unsigned fstride = (unsigned)(hi ? p.seg_stride[sb2] : p.seg_stride[sa]);
-            const unsigned segc = (unsigned)(hi ? p.seg_c[sb2] : p.seg_c[sa]);
-            const unsigned coff = pos - (unsigned)(hi ? p.seg_c0[sb2] : p.seg_c0[sa]);
-            const bool up = ((p.seg_up >> (hi ? sb2 : sa)) & 1) != 0; // segment = 2x nearest upsample of its tensor
+            const int8_t *base = hi ? pin.seg_in[sb2] : pin.seg_in[sa];
+            const unsigned fstride = (unsigned)(hi ? pin.seg_stride[sb2] : pin.seg_stride[sa]);
+            const unsigned segc = (unsigned)(hi ? pin.seg_c[sb2] : pin.seg_c[sa]);
+            const unsigned coff = pos - (unsigned)(hi ? pin.seg_c0[sb2] : pin.seg_c0[sa]);
+            const bool up = ((pin.seg_up >> (hi ? sb2 : sa)) & 1) != 0; // segment = 2x nearest upsample of its tensor
             const bool kvalid = (int)pos < p.in_c;
 #pragma unroll
             for (int j = 0; j < XI; j++) {
@@ -579,6 +624,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
     // issue cursor over the (tile, k-step) stream; younger[i] = vector-memory instructions this wave has
     // issued after the i-th oldest stage still in the ring (a stage that was not issued counts as empty)
     int8_t *const wres_base = lds + STAGES * STAGE;
+    // the chained 1x1's weights: one DMA instruction per wave (16 rows each), older than every ring stage of every wave
+    if (CHAIN) glds16(ch.w + (size_t)(wv * 16 + (lane >> 2)) * BK + schunk * 16, dynlds + CHAIN_W_OFF + wv * 16 * BK);
     if (wres)
         for (int ks = 0; ks < nks; ks++)
 #pragma unroll
@@ -607,7 +654,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
     nstage = STAGES - 1;
 
     const int frow = lane & 15, fchunk = lane >> 4;
-    const int chan = ocw + (lane >> 4) * (4 * WOC);
+    const int chan = ocs + (lane >> 4) * (4 * WOC);
     const int pstride = p.out_pix_stride ? p.out_pix_stride : p.out_c;
     const int lo = p.relu ? 0 : -128;
     const uint8_t *lut128 = slut + 128;
@@ -617,7 +664,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
     for (unsigned tile = t0; tile < t1; tile++) {
         v4i acc[WOC][WPX];
         for (int ks = 0; ks < nks; ks++) {
-            wait_vmcnt_at_most<(STAGES - 2) * L, NST>(younger[0]);
+            if (CHAIN && younger[0] >= 2 * NST + (STAGES - 2) * L) wait_vmcnt<2 * NST + (STAGES - 2) * L>();
+            else wait_vmcnt_at_most<(STAGES - 2) * L, NST>(younger[0]);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             // all fragment reads of this step first, then the next stage's DMA (its address math hides the LDS
@@ -658,6 +706,15 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
 #ifdef ANATOMY
         if (tile + 1 == t1) ANAT_NOW(2); // (the last tile's epilogue has no next tile's K steps to hide behind)
 #endif
+        // CHAIN: the 1x1's operands once per tile, not per subtile (the table reads below are opaque to the compiler: it would not hoist them)
+        v4i wd[CHAIN ? 4 : 1], bd[CHAIN ? 4 : 1];
+        if (CHAIN && chw) {
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                wd[CHAIN ? s : 0] = *(const v4i *)(dynlds + CHAIN_W_OFF + lds_off(s * 16 + frow, fchunk));
+                bd[CHAIN ? s : 0] = *(const v4i *)(dynlds + CHAIN_B_OFF + (s * 16 + (lane >> 4) * 4) * 4);
+            }
+        }
 #pragma unroll
         for (int t = 0; t < WPX; t++) {
             const unsigned pix = tile * BPX + pxw + t * 16 + (lane & 15);
@@ -671,10 +728,44 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
             for (int s = 0; s < WOC; s++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) a[s * 4 + r] = acc[s][t][r];
-            if (HAS_LUT && p.lut2) requant_pack<WOC * 4, HAS_LUT, true, true, false, true>(a, p.cs, lo, lut128, pk);
+            if constexpr (BOTH && WOC == 8) {
+                // sides of 128 channels: the packed rows are ordered per group of 64 channels, so subtiles 0-3 give this lane channels
+                // 16 g .. 16 g + 15 and subtiles 4-7 channels 64 + 16 g ..: two 16-byte runs, two stores
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    int ah[16];
+                    uint32_t ph[4];
+#pragma unroll
+                    for (int q = 0; q < 16; q++) ah[q] = a[h * 16 + q];
+                    if (second) requant_pack_at<16, LUTB>(ah, p.cs, ph);
+                    else requant_pack_at<16, 0>(ah, p.cs, ph);
+                    const int vo = pix < total_pix ? (int)(f * (unsigned)p.out_stride + rem * (unsigned)pstride) + h * 64 + (lane >> 4) * 16 : -1;
+                    __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)ph[0], (int)ph[1], (int)ph[2], (int)ph[3]}, orsrc, vo, 0, 0);
+                }
+                continue;
+            } else if constexpr (BOTH) {
+                if (second) requant_pack_at<WOC * 4, LUTB>(a, p.cs, pk); // the table at LDS bytes 512..1023
+                else requant_pack<WOC * 4, HAS_LUT, true, true, false, true>(a, p.cs, lo, lut128, pk);
+            } else if (HAS_LUT && p.lut2) requant_pack<WOC * 4, HAS_LUT, true, true, false, true>(a, p.cs, lo, lut128, pk);
             else requant_pack<WOC * 4, HAS_LUT, true, true>(a, p.cs, lo, lut128, pk);
             const int voff = ok ? (int)off : -1; // 0xffffffff >= num_records: dropped by the buffer unit
-            if (WOC == 4)
+            if constexpr (CHAIN) {
+                if (store_own) __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]}, orsrc, voff, 0, 0);
+                if (chw) { // pk = this pixel's channels 16 g .. 16 g + 15 of the side: the 1x1's B operand, K in natural order
+                    const v4i xd = {(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
+                    int ad[16];
+#pragma unroll
+                    for (int s = 0; s < 4; s++) {
+                        const v4i r = __builtin_amdgcn_mfma_i32_16x16x64_i8(wd[s], xd, bd[s], 0, 0, 0);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) ad[s * 4 + e] = r[e];
+                    }
+                    uint32_t pd[4];
+                    requant_pack_at<16, 2 * LUTB>(ad, ch.cs, pd);
+                    const unsigned offd = f * (unsigned)ch.out_stride + rem * 64u + (unsigned)chan;
+                    __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)pd[0], (int)pd[1], (int)pd[2], (int)pd[3]}, drsrc, pix < total_pix ? (int)offd : -1, 0, 0);
+                }
+            } else if (WOC == 4)
                 __builtin_amdgcn_raw_buffer_store_b128((v4i){(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]}, orsrc, voff, 0, 0);
             else if (WOC == 2)
                 __builtin_amdgcn_raw_buffer_store_b64((v2i){(int)pk[0], (int)pk[WOC > 1 ? 1 : 0]}, orsrc, voff, 0, 0);
@@ -704,7 +795,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_i8_persist(const mhip_conv_i8_t
             }
         }
 #pragma unroll
-        for (int i = 0; i < STAGES - 1; i++) younger[i] += ragged ? NST * (WOC == 4 ? 5 : 4) : NST;
+        for (int i = 0; i < STAGES - 1; i++) younger[i] += CHAIN ? nstw : (ragged ? NST * (WOC == 4 ? 5 : 4) : NST);
     }
     ANAT_END(p);
 }
@@ -884,6 +975,8 @@ const tune_t &conv_i8_tune_state() {
         g_tune.few_wgs = env_int("MARS_HIP_FEW_WGS", 256);
         g_tune.patch_ring = env_int("MARS_HIP_PATCH_RING", 0);
         g_tune.patch_lds_kb = env_int("MARS_HIP_PATCH_LDS_KB", 80);
+        g_tune.both_bpx = env_int("MARS_HIP_BOTH_BPX", 0);
+        g_tune.both_wide = env_int("MARS_HIP_BOTH_WIDE", 0);
         g_tune.init = 1;
     }
     return g_tune;
@@ -894,7 +987,7 @@ static int tune_access(const char *key, int value, int *get) {
     (void)conv_i8_tune_state();
     struct { const char *k; int *v; } tab[] = {{"persist", &g_tune.persist}, {"persist_stages", &g_tune.persist_stages},
                                                {"persist_maxk", &g_tune.persist_maxk}, {"persist_slots", &g_tune.persist_slots}, {"wres", &g_tune.wres}, {"rgb_direct", &g_tune.rgb_direct}, {"small_batch", &g_tune.small_batch},
-                                               {"rows", &g_tune.rows}, {"few_wgs", &g_tune.few_wgs}, {"patch_ring", &g_tune.patch_ring}, {"patch_lds_kb", &g_tune.patch_lds_kb}, {"stages", &g_tune.stages}, {"bpx", &g_tune.bpx}, {"variant", &g_tune.variant}, {"bufmode", &g_tune.bufmode}};
+                                               {"rows", &g_tune.rows}, {"few_wgs", &g_tune.few_wgs}, {"patch_ring", &g_tune.patch_ring}, {"patch_lds_kb", &g_tune.patch_lds_kb}, {"both_bpx", &g_tune.both_bpx}, {"both_wide", &g_tune.both_wide}, {"stages", &g_tune.stages}, {"bpx", &g_tune.bpx}, {"variant", &g_tune.variant}, {"bufmode", &g_tune.bufmode}};
     for (auto &e : tab)
         if (key && !strcmp(key, e.k)) {
             if (get) *get = *e.v;
@@ -947,48 +1040,53 @@ static int launch_mfma(const mhip_conv_i8_t *p, long total_pix, int k64) {
 template <int BPX, int BN>
 static size_t wres_lds(int k64) { return LUTB + 2 * (size_t)BPX * BK + (size_t)(k64 / BK) * BN * BK; }
 
-template <int BPX, int BN, int STAGES, bool HAS_LUT, bool SEG = false, bool PAIR = false>
+// BOTH: `second` is the second side of the one-tile pair form (both sides: out_c = oc_pad = 64 with half-step tables,
+// mhip_conv_i8_both_ok); one channel tile, a second table in LDS
+template <int BPX, int BN, int STAGES, bool HAS_LUT, bool SEG = false, bool PAIR = false, bool BOTH = false, bool CHAIN = false>
 static int launch_persist_t(const mhip_conv_i8_t *p, long total_pix, int k64, int lg, unsigned magic,
-                            const mhip_conv_i8_t *second = nullptr, int wres = 0) {
+                            const mhip_conv_i8_t *second = nullptr, int wres = 0, const conv_chain_t *chain = nullptr) {
     if (BN == 16 && (p->out_c > 16 || p->oc_pad != 32 || (PAIR && (second->out_c > 16 || second->oc_pad != 32)))) return -1; // (one tile of 16 channels out of a 32-row image)
-    const unsigned noc0 = BN == 16 ? 1u : (unsigned)(p->oc_pad / BN);
+    const unsigned noc0 = BN == 16 || BOTH ? 1u : (unsigned)(p->oc_pad / BN);
     const unsigned npt = (unsigned)((total_pix + BPX - 1) / BPX), noc = noc0 + (PAIR ? (BN == 16 ? 1u : (unsigned)(second->oc_pad / BN)) : 0u);
     conv_out_side_t alt;
     memset(&alt, 0, sizeof(alt));
-    if (PAIR) {
+    if (PAIR || BOTH) {
         alt.out = second->out; alt.out_stride = second->out_stride; alt.w = second->w; alt.bias = second->bias;
         alt.lut = second->lut; alt.lut2 = second->lut2; alt.out_c = second->out_c; alt.relu = second->relu; alt.out_pix_stride = second->out_pix_stride;
         alt.out_ch_off = second->out_ch_off; alt.cs = second->cs;
     }
-    if (PAIR) alt.out_bytes = (unsigned)persist_out_bytes(second);
+    if (PAIR || BOTH) alt.out_bytes = (unsigned)persist_out_bytes(second);
     if (wres && STAGES != 2) return -1;
-    const size_t lds = wres ? wres_lds<BPX, BN>(k64) : LUTB + (size_t)STAGES * (BPX + BN) * BK;
+    conv_chain_t ch;
+    memset(&ch, 0, sizeof(ch));
+    if (CHAIN) ch = *chain;
+    const size_t lds = (BOTH ? LUTB : 0) + (CHAIN ? CHAIN_LDS : 0) + (wres ? wres_lds<BPX, BN>(k64) : LUTB + (size_t)STAGES * (BPX + BN) * BK);
     if (wres) { // its own occupancy (LDS differs per layer) and longer runs: the weight fetch must amortise
         static bool attr = false;
-        if (!attr && hipFuncSetAttribute((const void *)conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR>,
+        if (!attr && hipFuncSetAttribute((const void *)conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
             return mhip_check(hipErrorUnknown, "conv_i8_persist LDS attribute");
         attr = true;
         int occ = 0, dev = 0;
         hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR>, NTHREADS, lds) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>, NTHREADS, lds) != hipSuccess ||
             hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
             return mhip_check(hipErrorUnknown, "conv_i8_persist occupancy query");
         unsigned g = (unsigned)((occ > 0 ? occ : 1) * prop.multiProcessorCount) / noc;
         if (tune().persist_slots > 0) g = (unsigned)tune().persist_slots / noc;
         if (g < 1) g = 1;
         if (g > npt) g = npt;
-        hipLaunchKernelGGL((conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR>), dim3(noc * g), dim3(NTHREADS), lds,
+        hipLaunchKernelGGL((conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>), dim3(noc * g), dim3(NTHREADS), lds,
                            mhip_stream_native(), *p, (unsigned)total_pix, k64, (const int8_t *)mhip_zero_page(), noc, npt, g, lg,
                            magic, make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
-                           (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64), (unsigned)in_extent_bytes(p), 1);
+                           (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64), (unsigned)in_extent_bytes(p), 1, ch);
         return mhip_check(hipGetLastError(), "conv_i8_persist (resident weights) launch");
     }
     static int slots = 0; // workgroups of this instantiation the device holds at once
     if (!slots) {
         int occ = 0, dev = 0;
         hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR>, NTHREADS, lds) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>, NTHREADS, lds) != hipSuccess ||
             hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
             return mhip_check(hipErrorUnknown, "conv_i8_persist occupancy query");
         slots = (occ > 0 ? occ : 1) * prop.multiProcessorCount;
@@ -998,10 +1096,10 @@ static int launch_persist_t(const mhip_conv_i8_t *p, long total_pix, int k64, in
     unsigned ngrp = (unsigned)(tune().persist_slots > 0 ? tune().persist_slots : 4 * slots) / noc;
     if (ngrp < 1) ngrp = 1;
     if (ngrp > npt) ngrp = npt;
-    hipLaunchKernelGGL((conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR>), dim3(noc * ngrp), dim3(NTHREADS), lds,
+    hipLaunchKernelGGL((conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>), dim3(noc * ngrp), dim3(NTHREADS), lds,
                        mhip_stream_native(), *p, (unsigned)total_pix, k64, (const int8_t *)mhip_zero_page(), noc, npt, ngrp, lg,
                        magic, make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
-                       (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64), (unsigned)in_extent_bytes(p), 0);
+                       (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64), (unsigned)in_extent_bytes(p), 0, ch);
     return mhip_check(hipGetLastError(), "conv_i8_persist launch");
 }
 
@@ -1275,6 +1373,99 @@ extern "C" int mhip_conv_i8_pair(const mhip_conv_i8_t *a, const mhip_conv_i8_t *
     if (bn == 64) return launch_pair_t<128, 64>(a, b, total_pix, k64, lg, magic, wres);
     if (b16) return launch_pair_t<128, 16>(a, b, total_pix, k64, lg, magic, wres);
     return launch_pair_t<128, 32>(a, b, total_pix, k64, lg, magic, wres);
+}
+
+// The same two convolutions in ONE tile (conv_i8_persist<BOTH>): 1x1, stride 1, sides of exactly 64 channels with dense
+// 16-byte aligned rows, both with a half-step table; plain or never-materialised concat input.  Shape and batch only
+// (pointers may be dummies, but the two sides' outputs must differ).
+static bool both_shape_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b) {
+    if (!a || !b || !tune().persist) return false;
+    if (a->in_stride != b->in_stride || a->frames != b->frames || a->in_h != b->in_h || a->in_w != b->in_w || a->in_c != b->in_c ||
+        a->out_h != b->out_h || a->out_w != b->out_w || a->row_pad != b->row_pad || a->nseg != b->nseg || a->seg_up != b->seg_up)
+        return false;
+    for (const mhip_conv_i8_t *p : {a, b}) {
+        if (p->kh != 1 || p->kw != 1 || p->stride_h != 1 || p->stride_w != 1 || p->pad_top || p->pad_left || p->in_h != p->out_h ||
+            p->in_w != p->out_w || (p->out_c != 64 && !(p->out_c == 128 && tune().both_wide && (p->nseg > 1 || tune().both_wide > 1))) || p->oc_pad != p->out_c || p->out_c != a->out_c || p->out_pix_stride || p->out_ch_off || !p->lut || !p->lut2 ||
+            p->add || p->out_nchw || p->in_c < 64 || p->row_pad != p->in_c || !persist_eligible(p))
+            return false;
+        if (p->nseg > 1 && !seg_valid(p)) return false;
+    }
+    for (int i = 0; i < a->nseg; i++)
+        if (a->seg_c[i] != b->seg_c[i] || a->seg_stride[i] != b->seg_stride[i]) return false;
+    const long total_pix = (long)a->frames * a->out_h * a->out_w;
+    return total_pix > 0 && total_pix <= 0x7fffffffL - 256 && a->out != b->out;
+}
+extern "C" int mhip_conv_i8_both_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b) { return both_shape_ok(a, b) ? 1 : 0; }
+
+// pixels per tile and resident weights of the one-tile pair form.  Measured on the yolov5s twin at batch 256 (one stream, per launch):
+// 128 pixels win on the plain-input site (128 -> 64 + 64 at 80 x 80: 0.083 against 0.097 ms; 0.103 side by side) and tie on the concat
+// site (256 -> 64 + 64: 0.118 against 0.122 ms; 0.172 as two launches); with the chained 1x1 the 256-pixel tile is at the register
+// limit and loses (0.18 / 0.215 against 0.129 / 0.164 ms for the two sites).  So 128 is the default; MARS_HIP_BOTH_BPX / MARS_HIP_WRES
+// pin either (A / B)
+static void both_form(int rows, int nks, bool chain, int *bpx, int *wres) {
+    *bpx = tune().both_bpx == 128 || tune().both_bpx == 256 ? tune().both_bpx : 128;
+    *wres = tune().wres && 2 * LUTB + (chain ? CHAIN_LDS : 0) + 2 * (size_t)*bpx * BK + (size_t)nks * rows * BK <= 80 * 1024;
+}
+// ... with the 1x1 `d` (64 -> 64 channels, half-step table, dense rows) that reads side `side` - 1 evaluated in that side's waves
+static bool chain_shape_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const mhip_conv_i8_t *d, int side) {
+    if (!both_shape_ok(a, b) || a->out_c != 64 || !d || (side != 1 && side != 2)) return false;
+    return d->kh == 1 && d->kw == 1 && d->stride_h == 1 && d->stride_w == 1 && !d->pad_top && !d->pad_left && d->in_c == 64 && d->out_c == 64 &&
+           d->oc_pad == 64 && d->row_pad == 64 && d->frames == a->frames && d->in_h == a->out_h && d->in_w == a->out_w && d->out_h == a->out_h &&
+           d->out_w == a->out_w && !d->out_pix_stride && !d->out_ch_off && d->lut && d->lut2 && !d->add && !d->out_nchw && d->nseg <= 1 &&
+           persist_eligible(d) && d->out != a->out && d->out != b->out;
+}
+extern "C" int mhip_conv_i8_both_chain_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const mhip_conv_i8_t *d, int side) {
+    return chain_shape_ok(a, b, d, side) ? 1 : 0;
+}
+static int both_launch(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const conv_chain_t *ch);
+extern "C" int mhip_conv_i8_both_chain(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const mhip_conv_i8_t *d, int side, int elide) {
+    if (!chain_shape_ok(a, b, d, side) || !d->w || !d->out) return -2;
+    const mhip_conv_i8_t *src = side == 1 ? a : b;
+    const mhip_conv_i8_t *other = side == 1 ? b : a;
+    if (!other->out) return -2;
+    if (!elide && (!src->out || d->in != src->out || d->in_stride != src->out_stride)) return -2; // (elided: that side is never stored)
+    conv_chain_t ch;
+    ch.w = d->w; ch.bias = d->bias; ch.lut2 = d->lut2; ch.out = d->out; ch.out_stride = d->out_stride;
+    ch.out_bytes = (unsigned)persist_out_bytes(d); ch.cs = d->cs; ch.side = side; ch.elide = elide ? 1 : 0;
+    return both_launch(a, b, &ch);
+}
+extern "C" int mhip_conv_i8_both(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b) {
+    if (!a || !b || !a->out || !b->out) return -2;
+    return both_launch(a, b, nullptr);
+}
+static int both_launch(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const conv_chain_t *ch) {
+    // a launch variant forced from outside (tests, the tuner's knob): the plain pair steps aside like the side-by-side form, so that its members
+    // run as that variant; with a chained 1x1 this launch is the plan's only form (as the patch-staged fusions) and runs regardless
+    if (!both_shape_ok(a, b) || (tune().variant && !ch) || !mhip_zero_page()) return -2;
+    if (a->nseg > 1) {
+        for (int i = 0; i < a->nseg; i++)
+            if (a->seg_in[i] != b->seg_in[i]) return -2;
+    } else if (a->in != b->in) {
+        return -2;
+    }
+    const long total_pix = (long)a->frames * a->out_h * a->out_w;
+    const int k64 = (a->kh * a->row_pad + BK - 1) / BK * BK, nks = k64 / BK;
+    int lg = 0;
+    while ((1 << lg) < a->in_c) lg++;
+    int bpx, wres;
+    both_form(2 * a->out_c, nks, ch != nullptr, &bpx, &wres);
+    if (a->out_c == 128) { // sides of 128 channels: the 256-row tile at 128 pixels (128 accumulator registers), no chain
+        if (ch) return -2;
+        return a->nseg > 1 ? launch_persist_t<128, 256, 2, true, true, false, true>(a, total_pix, k64, lg, 65536u, b, wres)
+                           : launch_persist_t<128, 256, 2, true, false, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
+    }
+    if (ch) {
+        if (a->nseg > 1)
+            return bpx == 256 ? launch_persist_t<256, 128, 2, true, true, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch)
+                              : launch_persist_t<128, 128, 2, true, true, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch);
+        return bpx == 256 ? launch_persist_t<256, 128, 2, true, false, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch)
+                          : launch_persist_t<128, 128, 2, true, false, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch);
+    }
+    if (a->nseg > 1)
+        return bpx == 256 ? launch_persist_t<256, 128, 2, true, true, false, true>(a, total_pix, k64, lg, 65536u, b, wres)
+                          : launch_persist_t<128, 128, 2, true, true, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
+    return bpx == 256 ? launch_persist_t<256, 128, 2, true, false, false, true>(a, total_pix, k64, lg, 65536u, b, wres)
+                      : launch_persist_t<128, 128, 2, true, false, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
 }
 
 extern "C" int mhip_conv_i8_seg_ok(const mhip_conv_i8_t *p) {

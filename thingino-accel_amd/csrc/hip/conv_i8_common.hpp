@@ -182,9 +182,9 @@ __device__ __forceinline__ void lut4_fast(int q0, int q1, int q2, int q3, int &v
                  : "v"(q0), "v"(q1), "v"(q2), "v"(q3)
                  : "memory");
 }
-// the same half-step requantisation against a SECOND table at LDS bytes 512..1023 (the 1x1 stage of the fused bottleneck)
-template <int NV>
-__device__ __forceinline__ void requant_pack_pre(const int (&a)[NV], float cs, uint32_t (&pk)[NV / 4]) {
+// the same half-step requantisation of NV values against the table at LDS bytes TAB..TAB + 511
+template <int NV, int TAB>
+__device__ __forceinline__ void requant_pack_at(const int (&a)[NV], float cs, uint32_t (&pk)[NV / 4]) {
     const float cs2 = cs * 2.0f;
     const int klo = -256, khi = 255;
     int q[NV], v[NV];
@@ -195,15 +195,18 @@ __device__ __forceinline__ void requant_pack_pre(const int (&a)[NV], float cs, u
     }
 #pragma unroll
     for (int g = 0; g < NV / 4; g++)
-        asm volatile("ds_read_i8 %0, %4 offset:768\n\tds_read_i8 %1, %5 offset:768\n\t"
-                     "ds_read_i8 %2, %6 offset:768\n\tds_read_i8 %3, %7 offset:768"
+        asm volatile("ds_read_i8 %0, %4 offset:%8\n\tds_read_i8 %1, %5 offset:%8\n\t"
+                     "ds_read_i8 %2, %6 offset:%8\n\tds_read_i8 %3, %7 offset:%8"
                      : "=&v"(v[4 * g]), "=&v"(v[4 * g + 1]), "=&v"(v[4 * g + 2]), "=&v"(v[4 * g + 3])
-                     : "v"(q[4 * g]), "v"(q[4 * g + 1]), "v"(q[4 * g + 2]), "v"(q[4 * g + 3])
+                     : "v"(q[4 * g]), "v"(q[4 * g + 1]), "v"(q[4 * g + 2]), "v"(q[4 * g + 3]), "n"(TAB + 256)
                      : "memory");
     wait_lds_values<NV>(v);
 #pragma unroll
     for (int g = 0; g < NV / 4; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
+// ... against a SECOND table at LDS bytes 512..1023 (the 1x1 stage of the fused bottleneck)
+template <int NV>
+__device__ __forceinline__ void requant_pack_pre(const int (&a)[NV], float cs, uint32_t (&pk)[NV / 4]) { requant_pack_at<NV, 512>(a, cs, pk); }
 // ... of TWO results of 8 values each (the sides of a fused cv1 + cv2 pair): a[0..7] with cs0 through the table at LDS bytes 512..1023,
 // a[8..15] with cs1 through a third table at 1024..1535; one wait for all sixteen reads
 __device__ __forceinline__ void requant_pack_two(const int (&a)[16], float cs0, float cs1, uint32_t (&pk)[4]) {
@@ -234,26 +237,7 @@ __device__ __forceinline__ void requant_pack_two(const int (&a)[16], float cs0, 
     for (int g = 0; g < 4; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
 // ... of the 8 values of the 1x1 chained to one side of that pair, through a fourth table at LDS bytes 1536..2047
-__device__ __forceinline__ void requant_pack_chain(const int (&a)[8], float cs, uint32_t (&pk)[2]) {
-    const float cs2 = cs * 2.0f;
-    const int klo = -256, khi = 255;
-    int q[8], v[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int k = (int)((float)a[i] * cs2);
-        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(q[i]) : "v"(k), "v"(klo), "v"(khi));
-    }
-#pragma unroll
-    for (int g = 0; g < 2; g++)
-        asm volatile("ds_read_i8 %0, %4 offset:1792\n\tds_read_i8 %1, %5 offset:1792\n\t"
-                     "ds_read_i8 %2, %6 offset:1792\n\tds_read_i8 %3, %7 offset:1792"
-                     : "=&v"(v[4 * g]), "=&v"(v[4 * g + 1]), "=&v"(v[4 * g + 2]), "=&v"(v[4 * g + 3])
-                     : "v"(q[4 * g]), "v"(q[4 * g + 1]), "v"(q[4 * g + 2]), "v"(q[4 * g + 3])
-                     : "memory");
-    wait_lds_values<8>(v);
-#pragma unroll
-    for (int g = 0; g < 2; g++) pk[g] = pack4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
-}
+__device__ __forceinline__ void requant_pack_chain(const int (&a)[8], float cs, uint32_t (&pk)[2]) { requant_pack_at<8, 1536>(a, cs, pk); }
 template <int NV, bool HAS_LUT, bool SAFE, bool LUT0, bool ADD = false, bool FAST = false>
 __device__ __forceinline__ void requant_pack(const int (&a)[NV], float cs, int lo, const uint8_t *lut128, uint32_t (&pk)[NV / 4],
                                              const uint32_t *xw = nullptr, const add_args_t *ga = nullptr) {
@@ -521,6 +505,8 @@ struct tune_t {
     int rows;           // MARS_HIP_ROWS          1: the default policy may pick conv_i8_rows (variant 20) where it measured faster
     int patch_ring;     // MARS_HIP_PATCH_RING    0: auto, else at most this many patch buffers per workgroup of the patch-staged kernel (1..4)
     int patch_lds_kb;   // MARS_HIP_PATCH_LDS_KB  LDS budget of one patch-staged workgroup (default 80: two workgroups per CU)
+    int both_bpx;       // MARS_HIP_BOTH_BPX      0: auto, else pixels per tile of the one-tile pair form (128 | 256)
+    int both_wide;      // MARS_HIP_BOTH_WIDE     1: the one-tile pair form also takes sides of 128 channels over a concat (the 256-row tile), 2: over a tensor too
 };
 const tune_t &conv_i8_tune_state(); // conv_i8.hip
 

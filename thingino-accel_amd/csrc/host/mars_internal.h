@@ -81,6 +81,10 @@ typedef struct {
     int nseg, seg_t[4], seg_c[4], seg_up;
     int chain_n, chain_out[3]; /* OP_MAXPOOL heading a fused chain of stride-1 pools: every stage's output tensor */
     int pair_next; /* conv_i8: launched together with the NEXT op (same input, same geometry: C3's cv1 + cv2) */ /* conv_i8 reading a never-materialised concat: its segments (tensor, channels) */
+    int pair_both; /* ... in the ONE-TILE form (conv_i8_persist<BOTH>: sides of 64 channels, the input staged once for both; pair_convs) */
+    int both_chain; /* ... and the op behind the mate, a 1x1 from 64 to 64 channels that reads side both_chain - 1 (1 or 2, 0 = none: the bottleneck's
+                       m.cv1), is evaluated in that side's waves (fuse_both_chain; conv_i8_persist<CHAIN>); it stays in the plan, is not launched */
+    int both_elide; /* ... and that side has no other reader and is no graph output: it is not stored, its tensor is not allocated */
     int row_pad, oc_pad, c_pad;
     int ch_off, scale_h, scale_w, bn_n;
     int out_pix_stride, out_ch_off; /* producer writes a channel slice of a wider tensor (zero-copy concat) */
@@ -124,7 +128,7 @@ typedef struct {
 typedef struct {
     int fusion; /* MARS_HIP_FUSION, default 1 */
     unsigned no_fuse_lut : 1, no_nhwc_internal : 1, no_vconcat_q : 1, no_pair_f32 : 1, no_rec : 1, no_zero_tail : 1, no_vconcat_f32 : 1,
-        no_rowpad : 1, no_post : 1, no_split : 1, no_chain : 1; /* MARS_HIP_NO_*: set = that pass is off */
+        no_rowpad : 1, no_post : 1, no_split : 1, no_chain : 1, no_both : 1, no_both_chain : 1; /* MARS_HIP_NO_*: set = that pass is off */
     size_t rec_limit;        /* MARS_HIP_REC_LIMIT: bytes all frames of a tensor may span under 32-bit offsets (rec_pairs, virtual_concat_f32) */
     size_t vconcat_limit;    /* MARS_HIP_VCONCAT_LIMIT: ... the output of a segmented convolution (alloc_batch) */
     size_t bottleneck_limit; /* MARS_HIP_BOTTLENECK_LIMIT: largest batch that keeps fused bottlenecks, 0 = no limit (alloc_batch) */
@@ -141,6 +145,8 @@ typedef struct mars_model_ext {
     int no_post;       /* fused cv3 launches (fuse_post) switched off: one of them cannot launch at this batch (32-bit output offsets) */
     int no_split;      /* fused cv1 + cv2 launches (fuse_split) switched off: likewise */
     int no_chain;      /* the 1x1 chained to such a launch (fuse_split_chain) switched off: likewise */
+    int no_both;       /* one-tile pairs (pair_convs, pair_both) switched off: likewise */
+    int no_both_chain; /* the 1x1 chained to such a pair (fuse_both_chain) switched off: likewise */
     int rec_frames;    /* rec_pairs: the batch the record-format pairs were chosen for (0 = one frame); a pair whose tensors reach 4 GiB at that batch is left alone */
     int rec_skipped;   /* ... some pair was left alone for that reason (a smaller batch may take it) */
     size_t rec_max_frames; /* ... the largest batch every chosen pair still fits */
@@ -268,6 +274,9 @@ MARS_INTERNAL size_t planned_stride(const mtensor_t *t);
 MARS_INTERNAL void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p);
 MARS_INTERNAL int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t out_stride);
 MARS_INTERNAL int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames);
+MARS_INTERNAL int conv_i8_both_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames);
+MARS_INTERNAL int conv_i8_both_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *d, int side, int frames);
+MARS_INTERNAL void fuse_both_chain(mars_model_ext_t *m);
 MARS_INTERNAL int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames);
 MARS_INTERNAL int conv_i8_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, const mars_op_t *d, int side, int frames);
 /* ... the passes, in the order build_plan calls them (f32: 0 = the int8 form, 1 = the float32 form) */

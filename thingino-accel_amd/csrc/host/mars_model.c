@@ -48,6 +48,8 @@ void plan_switches_read(plan_switches_t *sw, int at_load) {
     sw->no_post = getenv("MARS_HIP_NO_POST") != NULL;
     sw->no_split = getenv("MARS_HIP_NO_SPLIT") != NULL;
     sw->no_chain = getenv("MARS_HIP_NO_CHAIN") != NULL;
+    sw->no_both = getenv("MARS_HIP_NO_BOTH") != NULL;
+    sw->no_both_chain = getenv("MARS_HIP_NO_BOTH_CHAIN") != NULL;
     /* (tests lower the limits to see the per-batch decisions with small tensors) */
     sw->rec_limit = (e = getenv("MARS_HIP_REC_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0xfffffff0u;
     sw->vconcat_limit = (e = getenv("MARS_HIP_VCONCAT_LIMIT")) ? (size_t)strtoull(e, NULL, 0) : (size_t)0x7fffffffu;
@@ -193,7 +195,8 @@ mars_error_t build_plan(mars_model_ext_t *m) {
         fuse_split(m);    /* after pairing: it takes whole pairs; an op carrying `pre` or `post_next` is left alone */
         fuse_split_chain(m); /* after fuse_split: it extends its launches; after fuse_bottleneck: a 1x1 folded into a 3x3 as `pre` is no op any more */
         pad_output_rows(m);
-        virtual_concat_q(m); /* last of the int8 passes: it splits a convolution in two launches over one output tensor */
+        virtual_concat_q(m); /* last of the passes that form int8 launches: it splits a convolution in two launches over one output tensor */
+        fuse_both_chain(m);  /* after every pass that marks mates or cuts a pair in row ranges: it takes whole one-tile pairs and free 1x1s only */
     } else {
         nhwc_internal(m); /* only resets what a plan at another level left in the tensors */
     }
@@ -240,8 +243,8 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
      * alone at a larger batch may fit now) */
     const int rec_replan = (size_t)n > m->rec_max_frames || (m->rec_skipped && n < m->rec_frames);
     m->rec_frames = n;
-    if (m->no_vconcat || m->no_bottleneck || m->no_post || m->no_split || m->no_chain || rec_replan) {
-        m->no_vconcat = m->no_bottleneck = m->no_post = m->no_split = m->no_chain = 0;
+    if (m->no_vconcat || m->no_bottleneck || m->no_post || m->no_split || m->no_chain || m->no_both || m->no_both_chain || rec_replan) {
+        m->no_vconcat = m->no_bottleneck = m->no_post = m->no_split = m->no_chain = m->no_both = m->no_both_chain = 0;
         mars_error_t e = build_plan(m);
         if (e == MARS_OK) e = upload_params(m);
         if (e != MARS_OK) return e;
@@ -310,6 +313,33 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
             if (op->kind != OP_CONV_I8 || !op->split_next) continue;
             if (!conv_i8_split_fits(m, op, op + 1, op + 2, n)) {
                 m->no_split = 1;
+                mars_error_t e = build_plan(m);
+                if (e == MARS_OK) e = upload_params(m);
+                if (e != MARS_OK) return e;
+                break;
+            }
+        }
+    /* the 1x1 chained to a one-tile pair likewise (its output's 31-bit offsets; an elided side has no launch of its own to fall back to); asked
+     * first: without it the pair may still fit.  Both behind the checks above: a re-plan without fuse_split frees pairs for this form */
+    if (!m->no_both_chain)
+        for (int i = 0; i + 2 < m->n_ops; i++) {
+            const mars_op_t *op = &m->ops[i];
+            if (op->kind != OP_CONV_I8 || !op->pair_both || !op->both_chain) continue;
+            if (!conv_i8_both_chain_fits(m, op, op + 1, op + 2, op->both_chain, n)) {
+                m->no_both_chain = 1;
+                mars_error_t e = build_plan(m);
+                if (e == MARS_OK) e = upload_params(m);
+                if (e != MARS_OK) return e;
+                break;
+            }
+        }
+    /* one-tile pairs likewise (either side's output, 31-bit offsets): a pair over a virtual concat exists for that form alone */
+    if (!m->no_both)
+        for (int i = 0; i + 1 < m->n_ops; i++) {
+            const mars_op_t *op = &m->ops[i];
+            if (op->kind != OP_CONV_I8 || !op->pair_both) continue;
+            if (!conv_i8_both_fits(m, op, op + 1, n)) {
+                m->no_both = 1;
                 mars_error_t e = build_plan(m);
                 if (e == MARS_OK) e = upload_params(m);
                 if (e != MARS_OK) return e;
@@ -485,6 +515,7 @@ static int describe_op_full(const mars_op_t *o, char *line, size_t cap, int k) {
     if (o->split_next) ADD(" %zd", (ssize_t)o->split_w_off);
     ADD(" split_chain %d", o->split_chain);
     if (o->split_chain) ADD(" %zd", (ssize_t)o->chain_w_off);
+    ADD(" pair_both %d both_chain %d both_elide %d", o->pair_both, o->both_chain, o->both_elide);
     ADD(" pre %d", o->pre);
     if (o->pre) ADD(" %zd %zd %zd %a", (ssize_t)o->pre_w_off, (ssize_t)o->pre_b_off, (ssize_t)o->pre_lut2_off, (double)o->pre_cs);
     ADD(" macs %a bytes %a prof_kind %d", o->macs, o->bytes, o->prof_kind);
@@ -513,7 +544,7 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
 #define FLAG(cond, ...) if (cond) k += snprintf(line + k, sizeof line - (size_t)k, __VA_ARGS__)
         FLAG(o->kind == OP_CONV_I8 || o->kind == OP_CONV_F32 || o->kind == OP_CONV_F32_VHEAD, " k%dx%d s%d c%d->%d", o->kh, o->kw, o->sw, o->in_c, o->out_c);
         FLAG(o->nchw, " relayout"); FLAG(o->out_nchw, " planar_store"); FLAG(o->lut_off != NO_OFF, " lut"); FLAG(o->add_t, " add=%d", o->add_t - 1);
-        FLAG(o->nseg, " seg=%d", o->nseg); FLAG(o->pair_next, " pair_next"); FLAG(o->post_next, " post_next"); FLAG(o->split_next, " split_next"); FLAG(o->pre, " pre"); FLAG(o->silu_f32, " silu");
+        FLAG(o->nseg, " seg=%d", o->nseg); FLAG(o->pair_next && !(o->pair_both && o->nseg), " pair_next"); /* (a pair over a concat exists in the one-tile form only: pair_both says it all) */ FLAG(o->pair_both, " pair_both"); FLAG(o->both_chain, " both_chain=%d", o->both_chain); FLAG(o->both_elide, " both_elide"); FLAG(o->post_next, " post_next"); FLAG(o->split_next, " split_next"); FLAG(o->pre, " pre"); FLAG(o->silu_f32, " silu");
         FLAG(o->k_limit, " k_limit=%d", o->k_limit); FLAG(o->in_rec, " in_rec=%d", o->in_rec); FLAG(o->out_rec, " out_rec");
         FLAG(o->vc_shift, " view=-%d", o->vc_shift); FLAG(o->vc_n, " vcat=%dx%d", o->vc_n, o->vc_run);
         FLAG(o->rows_only, " rows_only=%d", o->rows_only); FLAG(o->out_byte_off, " out_off=%zu", o->out_byte_off); FLAG(o->chain_n, " chain=%d", o->chain_n);
@@ -539,10 +570,10 @@ size_t mars_hip_describe_plan(const void *data, size_t size, unsigned flags, cha
     if (full) {
         const plan_switches_t *w = &m->sw;
         snprintf(line, sizeof line, "+plan n_ops %d arena_size %zu scratch_per_frame %zu blob_mirror_bytes %zu rec_max_frames %zu rec_skipped %d f32_mode %d | fusion %d"
-                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d no_post %d no_split %d no_chain %d rec_limit %zu"
+                 " no_fuse_lut %d no_nhwc_internal %d no_vconcat_q %d no_pair_f32 %d no_rec %d no_zero_tail %d no_vconcat_f32 %d no_rowpad %d no_post %d no_split %d no_chain %d no_both %d no_both_chain %d rec_limit %zu"
                  " vconcat_limit %zu bottleneck_limit %zu\n", m->n_ops, m->arena_size, m->scratch_per_frame, m->blob_mirror_bytes, m->rec_max_frames, m->rec_skipped,
                  m->plan_f32_mode, w->fusion, w->no_fuse_lut, w->no_nhwc_internal, w->no_vconcat_q, w->no_pair_f32, w->no_rec, w->no_zero_tail, w->no_vconcat_f32,
-                 w->no_rowpad, w->no_post, w->no_split, w->no_chain, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
+                 w->no_rowpad, w->no_post, w->no_split, w->no_chain, w->no_both, w->no_both_chain, w->rec_limit, w->vconcat_limit, w->bottleneck_limit);
         EMIT();
     }
 #undef EMIT

@@ -704,6 +704,51 @@ int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_
     return mhip_conv_i8_post_ok(&p);
 }
 
+/* the shape-only launch records of a one-tile pair (operands: any distinct non-null addresses) */
+static int both_records(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames, mhip_conv_i8_t p[2]) {
+    const mars_op_t *o[2] = {a, b};
+    if (a->t_out < 0 || b->t_out < 0 || a->lut2_off == NO_OFF || b->lut2_off == NO_OFF || a->nchw || b->nchw)
+        return 0;
+    for (int k = 0; k < 2; k++) {
+        conv_i8_geometry(o[k], frames, &p[k]);
+        p[k].in = (const int8_t *)m;
+        p[k].in_stride = o[k]->t_in[0] >= 0 ? planned_stride(&m->mt[o[k]->t_in[0]]) : 0;
+        p[k].out = (int8_t *)m + k; p[k].out_stride = planned_stride(&m->mt[o[k]->t_out]);
+        p[k].lut = p[k].lut2 = (const uint8_t *)m;
+        if (o[k]->add_t) p[k].add = (const int8_t *)m;
+        p[k].nseg = o[k]->nseg; p[k].seg_up = o[k]->seg_up;
+        int c0 = 0;
+        for (int q = 0; q < 4; q++) {
+            p[k].seg_c0[q] = 0x7fffffff;
+            if (q < o[k]->nseg) {
+                p[k].seg_in[q] = (const int8_t *)m;
+                p[k].seg_stride[q] = o[k]->seg_t[q] >= 0 ? planned_stride(&m->mt[o[k]->seg_t[q]]) : 0;
+                p[k].seg_c[q] = o[k]->seg_c[q];
+                p[k].seg_c0[q] = c0;
+                c0 += o[k]->seg_c[q];
+            }
+        }
+    }
+    return 1;
+}
+/* does the device code take the pair `a`, `b` (same input) in its one-tile form (pair_convs, pair_both), at this batch? */
+int conv_i8_both_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames) {
+    mhip_conv_i8_t p[2];
+    return both_records(m, a, b, frames, p) && mhip_conv_i8_both_ok(&p[0], &p[1]);
+}
+/* ... and with the 1 x 1 `d` behind them, which reads side `side` - 1, chained into that launch (fuse_both_chain)? */
+int conv_i8_both_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *d, int side, int frames) {
+    mhip_conv_i8_t p[2], pd;
+    if (d->t_out < 0 || d->lut2_off == NO_OFF || d->nchw || !both_records(m, a, b, frames, p)) return 0;
+    conv_i8_geometry(d, frames, &pd);
+    pd.in = (const int8_t *)m; pd.out = (int8_t *)m + 2;
+    pd.in_stride = planned_stride(&m->mt[(side == 1 ? a : b)->t_out]); pd.out_stride = planned_stride(&m->mt[d->t_out]);
+    pd.lut = pd.lut2 = (const uint8_t *)m;
+    if (d->add_t) pd.add = (const int8_t *)m;
+    pd.nseg = d->nseg;
+    return mhip_conv_i8_both_chain_ok(&p[0], &p[1], &pd, side);
+}
+
 /* does the device code take convolution `a` with the paired 1 x 1s `b` and `c` behind it evaluated in the same launch (fuse_split), at this batch? */
 int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames) {
     mhip_conv_i8_t p;
@@ -1396,6 +1441,58 @@ void fuse_split_chain(mars_model_ext_t *m) {
     free(readers);
 }
 
+/* The bottleneck's m.cv1 inside a one-tile pair: A carries pair_both with its mate B right behind it; D = a 1 x 1 SiLU convolution from 64 to 64
+ * channels that reads exactly A's or B's output over the same map.  The side's waves (conv_i8_persist<CHAIN>) hold its requantised bytes in
+ * registers the moment they store them: they are the B operand of D's only K step.  D's launch and its read of the side go.  Where D is the
+ * side's ONLY reader and the side is no graph output (the neck's C3: no shortcut), the side is not stored either and its tensor is not
+ * allocated (both_elide; as fuse_split's k x k result).  Same bytes: D sees exactly the int8 values its input tensor holds, or would hold.
+ * All three ops stay in the plan: A records the side (both_chain = 1 for its own, 2 for B's), D is moved up behind B under pair_up's rule and
+ * skipped by the run loop like B.  It reads D's own packed weights and bias rows: no second image.  Only where the device code takes it
+ * (conv_i8_both_chain_fits); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_both_chain). */
+static int both_chain_mate_ok(const mars_op_t *d, const mars_op_t *a) {
+    return d->kind == OP_CONV_I8 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && !d->pt && !d->pl && d->safe && !d->nchw && !d->out_nchw && !d->add_t &&
+           !d->chain_n && !d->store_c && !d->in_byte_off && !d->out_byte_off && !d->out_pix_stride && !d->out_ch_off && d->lut_off != NO_OFF &&
+           d->lut2_off != NO_OFF && !d->nseg && !d->pre && !d->pair_next && !d->post_next && !d->split_next && d->n_in == 1 && d->in_c == 64 && d->out_c == 64 &&
+           d->oc_pad == 64 && d->row_pad == 64 && d->in_h == a->out_h && d->in_w == a->out_w && d->out_h == a->out_h && d->out_w == a->out_w;
+}
+void fuse_both_chain(mars_model_ext_t *m) {
+    if (m->sw.no_both_chain || m->no_both_chain || m->sw.no_both || m->no_both) return;
+    int *readers, *writers;
+    if (!use_counts(m, &readers, &writers)) return;
+    for (int i = 0; i + 2 < m->n_ops; i++) {
+        mars_op_t *a = &m->ops[i];
+        if (a->kind != OP_CONV_I8 || !a->pair_both || a->both_chain || a->in_byte_off || a[1].in_byte_off || a->out_byte_off || a[1].out_byte_off) continue;
+        if (i > 0 && m->ops[i - 1].split_next) continue; /* (the pair is itself inside a launch) */
+        const int O0 = a->t_out, O1 = a[1].t_out;
+        for (int j = i + 2; j < m->n_ops && j <= i + 48; j++) {
+            const mars_op_t *d = &m->ops[j];
+            if (!both_chain_mate_ok(d, a) || m->ops[j - 1].pair_next || m->ops[j - 1].post_next || m->ops[j - 1].split_next ||
+                (j >= 2 && (m->ops[j - 2].split_next || m->ops[j - 2].both_chain)) || (j >= 3 && m->ops[j - 3].split_chain))
+                continue; /* (a mate of another launch is not D) */
+            const int side = d->t_in[0] == O0 ? 1 : (d->t_in[0] == O1 ? 2 : 0), O = d->t_out;
+            if (!side || O < 0 || O == O0 || O == O1 || writers[O] != 1 || m->mt[O].io_in || m->mt[O].is_weight || m->mt[O].pix_stride ||
+                op_reads(a, O) || op_reads(a + 1, O) || op_reads(d, O))
+                continue;
+            if (touched_between(m, i + 2, j, O, USE_READ | USE_WRITE) || touched_between(m, i + 2, j, d->t_in[0], USE_WRITE)) continue;
+            if (!conv_i8_both_chain_fits(m, a, a + 1, d, side, 1)) continue; /* one frame: alloc_batch asks again for its batch */
+            if (j > i + 2) {
+                const mars_op_t moved = *d;
+                memmove(&m->ops[i + 3], &m->ops[i + 2], sizeof(mars_op_t) * (size_t)(j - i - 2));
+                m->ops[i + 2] = moved;
+            }
+            a->both_chain = side;
+            const int S = side == 1 ? O0 : O1;
+            if (readers[S] == 1 && writers[S] == 1 && !m->mt[S].io_in && !m->mt[S].io_out && !m->mt[S].is_weight && !m->mt[S].tail_read) {
+                a->both_elide = 1;
+                m->mt[S].needed = 0;
+            }
+            break;
+        }
+        i += 1; /* (the mate carries no pair_both) */
+    }
+    free(readers);
+}
+
 /* Ragged pixel rows of graph outputs (the 255-channel YOLO heads) are kept at a 16-byte-aligned pitch on the device:
  * the producing convolution then takes the aligned epilogue (16-byte stores straight from registers, every launch
  * form) instead of the LDS-staged copy-out with 8+4+2+1-byte row tails.  Only tensors nothing in the graph reads:
@@ -1541,9 +1638,9 @@ static int same_conv_input(const mars_op_t *a, const mars_op_t *b) {
            a->row_pad == b->row_pad && a->oc_pad == b->oc_pad;
 }
 static int pairable(const mars_op_t *o) {
-    /* measured: pairs with a plain input gain 10-20 %, pairs reading a virtual concat lose (their single launches are
-     * tuned individually), so only the former are formed */
-    return o->kind == OP_CONV_I8 && !o->nchw && !o->out_nchw && !o->add_t && !o->nseg && o->safe && o->lut_off != NO_OFF && !o->pair_next &&
+    /* measured: side-by-side pairs with a plain input gain 10-20 %, those reading a virtual concat lose (their single launches are
+     * tuned individually), so a pair over a concat is formed only where it takes the one-tile form (pair_convs) */
+    return o->kind == OP_CONV_I8 && !o->nchw && !o->out_nchw && !o->add_t && o->safe && o->lut_off != NO_OFF && !o->pair_next &&
            (o->in_c & 15) == 0 && o->in_c > 4 && (o->out_c & 15) == 0 && !o->out_pix_stride;
 }
 /* the step both pairing passes share: op j becomes op i's mate (moved up right behind it) unless an op between them touches j's output or
@@ -1567,7 +1664,14 @@ void pair_convs(mars_model_ext_t *m) {
             mars_op_t *b = &m->ops[j];
             if (!pairable(b) || !same_conv_input(a, b) || b->t_out == a->t_out) continue;
             if (op_reads(b, b->t_out) || op_reads(b, a->t_out)) continue;
-            if (pair_up(m, i, j)) break;
+            /* the one-tile form (sides of 64 channels: the input is staged once for both) where the device code takes it at one frame; alloc_batch
+             * asks again for its batch (m->no_both).  MARS_HIP_NO_BOTH: the side-by-side form, and no pair over a concat */
+            const int both = !m->sw.no_both && !m->no_both && conv_i8_both_fits(m, a, b, 1);
+            if (a->nseg && !both) continue;
+            if (pair_up(m, i, j)) {
+                m->ops[i].pair_both = both;
+                break;
+            }
         }
     }
 }
@@ -1933,6 +2037,8 @@ void plan_check(mars_model_ext_t *m) {
         else if (o->add_t && !op_reads(o, o->add_t - 1)) why = "add_t is not among t_in";
         else if (o->chain_n && o->t_out != o->chain_out[o->chain_n - 1]) why = "t_out is not the chain's last stage";
         else if (o->pair_next && (i + 1 >= m->n_ops || m->ops[i + 1].kind != o->kind)) why = "pair_next without a mate of its kind";
+        else if (o->pair_both && (!o->pair_next || o->kind != OP_CONV_I8 || (o->out_c != 64 && o->out_c != 128) || m->ops[i + 1].out_c != o->out_c)) why = "pair_both without a pair of 64- or 128-channel sides";
+        else if (o->kind == OP_CONV_I8 && o->pair_next && o->nseg && !o->pair_both) why = "a side-by-side pair over a virtual concat";
         else if (o->post_next && (o->kind != OP_CONV_I8 || i + 1 >= m->n_ops || m->ops[i + 1].kind != OP_CONV_I8 || m->ops[i + 1].nseg != 2 ||
                                   m->ops[i + 1].seg_t[0] != o->t_out || !op_reads(o, m->ops[i + 1].seg_t[1])))
             why = "post_next without its 1x1 behind it, or y2 is not among t_in";
@@ -1945,6 +2051,12 @@ void plan_check(mars_model_ext_t *m) {
                                     m->ops[i + 3].t_out == m->ops[i + 1].t_out || m->ops[i + 3].t_out == m->ops[i + 2].t_out || m->ops[i + 3].t_out == o->t_out ||
                                     m->mt[m->ops[i + 3].t_out].pix_stride || o->chain_w_off == NO_OFF))
             why = "split_chain without its 1x1 behind the pair";
+        else if (o->both_chain && (!o->pair_both || i + 2 >= m->n_ops || !both_chain_mate_ok(&m->ops[i + 2], o) || (o->both_chain != 1 && o->both_chain != 2) ||
+                                   m->ops[i + 2].t_in[0] != m->ops[i + o->both_chain - 1].t_out || m->ops[i + 2].t_out < 0 ||
+                                   m->ops[i + 2].t_out == o->t_out || m->ops[i + 2].t_out == m->ops[i + 1].t_out))
+            why = "both_chain without its 1x1 behind the pair";
+        else if (o->both_elide && (!o->both_chain || m->mt[m->ops[i + o->both_chain - 1].t_out].needed || m->mt[m->ops[i + o->both_chain - 1].t_out].io_out))
+            why = "both_elide on a side that is kept";
         for (int k = 0; !why && k < o->nseg; k++)
             if (!op_reads(o, o->seg_t[k])) why = "a seg_t is not among t_in";
         for (int k = 0; !why && k < o->vc_n; k++)

@@ -377,7 +377,7 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             return (mars_error_t)op->err;
         }
         mars_op_t *mate = (op->pair_next || op->post_next || op->split_next) && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
-        mars_op_t *mate2 = op->split_next && i + 2 < m->n_ops ? &m->ops[i + 2] : NULL; /* (a fused pair: both mates' outputs are this launch's) */
+        mars_op_t *mate2 = (op->split_next || (op->pair_both && op->both_chain)) && i + 2 < m->n_ops ? &m->ops[i + 2] : NULL; /* (a fused pair: both mates' outputs are this launch's; a one-tile pair's chained 1x1) */
         mars_op_t *mate3 = op->split_next && op->split_chain && i + 3 < m->n_ops ? &m->ops[i + 3] : NULL; /* (... and the chained 1x1's) */
         if (wait_tail && ((op->t_out >= 0 && (m->mt[op->t_out].io_out || m->mt[op->t_out].tail_read)) ||
                           (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)) ||
@@ -426,7 +426,18 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             mhip_conv_i8_t pa, pb;
             conv_i8_params(m, op, &pa);
             conv_i8_params(m, mate, &pb);
-            rc = mhip_conv_i8_pair(&pa, &pb);
+            if (op->pair_both && op->both_chain) { /* ... and the 1x1 behind one side (conv_i8_persist<CHAIN>); the plan holds it only where this form runs */
+                mhip_conv_i8_t pd;
+                rc = -1;
+                if (mate2) {
+                    conv_i8_params(m, mate2, &pd);
+                    rc = mhip_conv_i8_both_chain(&pa, &pb, &pd, op->both_chain, op->both_elide);
+                    if (rc == -2) rc = -1; /* (alloc_batch asked for this batch) */
+                }
+                i++; /* the chained 1x1 has run */
+            } else {
+                rc = op->pair_both ? mhip_conv_i8_both(&pa, &pb) : mhip_conv_i8_pair(&pa, &pb); /* (one tile for both | two tiles side by side) */
+            }
             if (rc == -2) {
                 rc = launch_op(m, op);
                 if (!rc) rc = launch_op(m, mate);
@@ -818,6 +829,7 @@ static mars_error_t autotune_model(mars_model_t *model, int reps) {
         if (op->post_next || (i > 0 && m->ops[i - 1].post_next)) continue; /* ... and a fused cv3 goes with the launch its policy picks */
         if (op->split_next) continue;                                      /* ... as does a fused pair (its mates are a pair: skipped above) */
         if (i >= 3 && m->ops[i - 3].split_chain) continue;                 /* ... and the 1x1 chained to it */
+        if (i >= 2 && m->ops[i - 2].both_chain) continue;                  /* ... or to a one-tile pair */
         mhip_conv_i8_t p;
         conv_i8_params(m, op, &p);
         int codes[32];

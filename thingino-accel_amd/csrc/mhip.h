@@ -185,6 +185,16 @@ int mhip_conv_i8_seg_ok(const mhip_conv_i8_t *p);
 /* two convolutions over the same input in one launch (the second's input reads hit L2); -2 = not eligible as a
  * pair (launch them separately), else the launch result */
 int mhip_conv_i8_pair(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b);
+/* ... in ONE tile that carries both (conv_i8_persist<BOTH>): the input -- a never-materialised concat included -- is staged once
+ * for both.  1x1, stride 1, both sides out_c = oc_pad = 64 with dense rows and a half-step table.  _both_ok: do shape and batch
+ * allow it (pointers may be dummies; the sides' `out` must differ)?  _both: -2 = not eligible, else the launch result */
+int mhip_conv_i8_both_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b);
+int mhip_conv_i8_both(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b);
+/* ... and a 1x1 `d` from 64 to 64 channels (half-step table, dense rows, the layer's own packed weights and bias rows) that reads side
+ * `side` - 1 (1 | 2) evaluated in that side's waves on the bytes they have just packed (conv_i8_persist<CHAIN>): d's launch and its read
+ * of the side go.  elide: the side itself is not stored (its `out` is not touched and may be NULL) */
+int mhip_conv_i8_both_chain_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const mhip_conv_i8_t *d, int side);
+int mhip_conv_i8_both_chain(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const mhip_conv_i8_t *d, int side, int elide);
 /* does a layer with in_c bytes per pixel take the small-channel packing (every pixel widened to 4 bytes, 32-byte kernel rows)? */
 int mhip_conv_i8_small_c(int in_c, int kw, int out_c);
 /* packing geometry shared by host packer and kernel */
