@@ -819,10 +819,9 @@ int mars_yolo_keypoints(const int8_t *rows, int n, int K, int D, const int *gx, 
  *             w' = w * rx and h' = h * rx -- BOTH by rx, they lie along the box's own axes; the angle is unchanged.
  * Result.     mars_obb_t per kept box, in sorted order; pred = its prediction index (cells of the heads before its head + its cell).
  * Detections. The model's ordinary detection list is filled too, index-aligned with the obb records, so mars_hip_detect_results and the
- *             crop, label and track stages work unchanged: entry i = the ENCLOSING UPRIGHT RECTANGLE of obb record i -- same x, y, conf,
- *             cls;  w_e = (w * |cs|) + (h * |sn|);  h_e = (w * |sn|) + (h * |cs|), from the mapped w, h.
- * Not covered: the pipelined mars_hip_pipe_* path; rotated crops (the crop stage gets the enclosing rectangle); an exact polygon IoU; a
- *   file-level finder (callers name the angle tensors); float32 tensors; anchor-based obb heads. */
+ *             crop, label and track stages work unchanged ("Rotated crops" below cuts along the box's own axes instead): entry i = the
+ *             ENCLOSING UPRIGHT RECTANGLE of obb record i -- same x, y, conf, cls;  w_e = (w * |cs|) + (h * |sn|);  h_e = (w * |sn|) + (h * |cs|), from the mapped w, h.
+ * Not covered: the pipelined mars_hip_pipe_* path; an exact polygon IoU; a file-level finder (callers name the angle tensors); float32 tensors; anchor-based obb heads. */
 typedef struct { float x, y, w, h, conf; int cls; float angle; int pred; } mars_obb_t; /* 32 bytes */
 #define MARS_OBB_AGNOSTIC 1u /* boxes of different classes suppress each other too */
 /* Zero-initialise; zero means default in every field but the tensor indices. */
@@ -855,6 +854,60 @@ int mars_yolo_obb_nms(mars_obb_t *boxes, int n, float thresh, unsigned flags);
  *   corner 0 = (x - ux + vx, y - uy - vy);  1 = (x + ux + vx, y + uy - vy);  2 = (x + ux - vx, y + uy + vy);  3 = (x - ux - vx, y - uy + vy),
  * each sum left to right. */
 void mars_yolo_obb_corners(const mars_obb_t *box, float xy[8]);
+
+/* ------------------------------------------------------------ Rotated crops */
+/* The crop stage for ORIENTED boxes ("Oriented boxes" above): a plate, a line of text or a vehicle seen from above is cut out along its own
+ * axes and reaches the second model upright, without the background and the wrong aspect ratio of its enclosing rectangle.  Options
+ * (mars_hip_roi_opts_t), selection, the ROI table and the label / identify / track joins are those of "ROI crops"; the sampler differs.
+ * float32 with every operation rounded on its own, no fused multiply-add; integers wherever a pixel is touched:
+ *
+ * Box -> crop frame.  A mars_obb_t in source-frame pixels, frames of W x H; cs, sn = its angle's cosine and sine: in the device chain the decode
+ *   tables' entries the obb stage carries per box, in the host-pointer form cosf(angle), sinf(angle) of the host libm.
+ *     we = w * expand,  he = h * expand        (expand == 0 means 1.0, min_size == 0 means 2)
+ *   The box is SKIPPED when a float field (x, y, w, h, conf, angle) is not finite, w <= 0 or h <= 0, we < min_size or he < min_size,
+ *   we > 32768 or he > 32768, or the centre is outside the frame (x < 0, x > W, y < 0, y > H).  Behind this rule (and W, H <= 32767, which
+ *   the calls require) every conversion below is defined and every Q16 value fits an int32.
+ * Target geometry for a tw x th input.  Stretch: nw = tw, nh = th, px = py = 0.  MARS_ROI_KEEP_ASPECT: the integer rule of "ROI crops" with
+ *   cw = max(1, (int)rintf(we)), ch = max(1, (int)rintf(he)).  Pixels outside [px, px + nw) x [py, py + nh) are -17.
+ * Sample positions, Q16, per box (rintf = round to nearest even):
+ *     sx = we / (float)(2 * nw),  sy = he / (float)(2 * nh)
+ *     Ux = (int)rintf((sx * cs) * 65536.0f),     Uy = (int)rintf((sx * sn) * 65536.0f)
+ *     Vx = (int)rintf((-(sy * sn)) * 65536.0f),  Vy = (int)rintf((sy * cs) * 65536.0f)
+ *     X0 = (int)rintf((x - 0.5f) * 65536.0f),    Y0 = (int)rintf((y - 0.5f) * 65536.0f)
+ *   Output column i of [0, nw), row j of [0, nh), in int64:  a = 2 i + 1 - nw,  b = 2 j + 1 - nh,
+ *     PX = X0 + a * Ux + b * Vx,  PY = Y0 + a * Uy + b * Vy;   qx = PX >> 8 (arithmetic: floor), ix = qx >> 8, fx = qx & 255;  iy, fy alike.
+ * Taps and blend.  Taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1).  A tap with ix outside [0, W) or iy outside [0, H) is 111
+ *   in every channel (the grey, -17 after the - 128): a rotated box leaves the frame with a corner, and the corner is grey, not a smeared edge.
+ *   There is no clamp.  The blend is that of "ROI crops": top, bot, v = (top * (256 - fy) + bot * fy + 32768) >> 16, out = (int8)(v - 128);
+ *   the layout follows the destination's format tag.
+ * NV12 source.  Every in-frame tap is converted with the integer BT.601 formulas of "NV12 camera frames", the chroma pair taken at
+ *   (ix >> 1, iy >> 1), all MARS_NV12_* flags apply.  A rotated NV12 crop equals the rotated RGB crop of mars_yolo_nv12_to_rgb of the frame.
+ * Consequences.  Angle 0, nw == we, we and x - we / 2 integers (rows alike): Ux = Vy = 32768, Uy = Vx = 0, every fx = fy = 0: an exact copy
+ *   of the frame's pixels minus 128.  cs, sn of (float)(pi / 2): Ux rounds to 0 and the crop is an exact transposed copy (column i walks down
+ *   the frame, row j walks left).
+ * Selection (device chain).  The rules of "ROI crops" over the obb records in list order -- min_conf, class window, max_per_frame -- with
+ *   the skip rule above in the rectangle rule's place.
+ * ROI table.  frame and det as before; det indexes the obb records AND the detection list (they are index-aligned), so the label, identify
+ *   and track joins work unchanged.  x0 .. y1 is for the caller's information only, the enclosing rectangle of the expanded box clipped to the
+ *   frame:  ex = ((we * |cs|) + (he * |sn|)) * 0.5f,  ey = ((we * |sn|) + (he * |cs|)) * 0.5f,
+ *     x0 = (int)floorf(max(x - ex, 0)),  x1 = (int)ceilf(min(x + ex, (float)W)),  y0, y1 alike with ey, H.
+ *   A kept box has x1 > x0 and y1 > y0; a skipped box of the host-pointer form has all four zero (x1 == x0 marks it).
+ * Refused: what the calls of "ROI crops" refuse, W or H above 32767 (MARS_ERR_INVALID_FILE), and MARS_ERR_INVALID_TENSOR when det_model
+ *   holds no obb results (no mars_hip_detect_obb_device since its batch was set).
+ * Not covered: the pipelined mars_hip_pipe_* path; area averaging (a strong down-scale samples four taps per output pixel, as the upright
+ *   crop does); rotated crops of merged tile lists; boxes whose centre is off-frame (skipped). */
+/* mars_yolo_crop_boxes for oriented boxes: host pointers in and out, runs on the GPU.  Only the skip rule applies; a skipped box's crop is
+ * all -17 and rois[i].x1 == rois[i].x0 marks it (rois may be NULL). */
+mars_error_t mars_yolo_crop_obb(const unsigned char *frames, int n_frames, const mars_obb_t *boxes, const int *frame_of_box, int n_boxes,
+                                const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc, signed char *out, mars_roi_t *rois);
+/* mars_hip_crop_detections_device over the obb records and (cos, sin) pairs the last mars_hip_detect_obb_device of det_model left in HBM
+ * (decoded with src_w / src_h set: source-frame pixels).  Enqueues only; stream and event ordering are exactly those of
+ * mars_hip_crop_detections_device, and mars_hip_roi_results serves this call too. */
+mars_error_t mars_hip_crop_obb_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
+                                      const mars_hip_roi_opts_t *opts);
+/* The same with the frames in host memory: uploads them, crops, waits. */
+mars_error_t mars_hip_crop_obb(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
+                               const mars_hip_roi_opts_t *opts);
 
 /* --------------------------------------------------------- Tiled inference */
 /* Sliced inference for frames much larger than the graph input: a camera frame is cut into overlapping tiles, every tile is one frame of the

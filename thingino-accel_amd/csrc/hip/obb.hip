@@ -21,7 +21,8 @@
 //                        under MARS_OBB_AGNOSTIC) into an 8 KB bit matrix; wave 0 applies the rows greedily (suppressed boxes suppress
 //                        nothing) exactly as sort_nms_kernel does; the survivors are compacted in order by ballot prefix, mapped
 //                        through the letterbox, and written twice: the 32-byte record and the enclosing upright rectangle as a
-//                        24-byte detection, index-aligned.
+//                        24-byte detection, index-aligned; where the caller asks (csn_out), the kept box's (cos, sin) pair too, for the
+//                        rotated crops of roi.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -370,6 +371,7 @@ __global__ __launch_bounds__(OBB_NMS_THREADS) void obb_sort_nms_kernel(const mhi
                 k.h = __fmul_rn(k.h, p.rx); // both sides by rx: they lie along the box's own axes
             }
             out[slot] = k;
+            if (p.csn_out) ((float2 *)p.csn_out + (size_t)f * MAXD)[slot] = t;
             if (dets) {
                 const float ac = fabsf(t.x), as = fabsf(t.y);
                 obb_det e;

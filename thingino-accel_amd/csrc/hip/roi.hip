@@ -10,6 +10,8 @@
 //                             knows it: the kernel reads the kept count and its rectangle from device memory, builds the column table in
 //                             LDS, stages the source-row segments its rows touch in LDS (NV12: converted once per pixel while staging),
 //                             blends from LDS, puts the strip's bytes together in LDS and stores contiguous runs 16 bytes at a time.
+//   roi_rot_crop_kernel<FMT>  the same strip for an ORIENTED box ("Rotated crops"): samples along the box's axes from a staged bounding rectangle;
+//                             the select and rectangle kernels serve it through their ROT flag.
 // Nothing here uses atomics: a slot number is a function of the lists alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,10 +43,58 @@ __device__ __forceinline__ bool roi_rect(const roi_det_t d, const float expand, 
     return true;
 }
 
+// ---- "Rotated crops": the skip rule, the enclosing rectangle of the ROI table and the Q16 sample frame of an oriented box.  float32, every
+// operation rounded on its own; rintf is round-to-nearest-even on both sides; `/` is the correctly rounded division (hipcc's default)
+struct roi_obb_t { float x, y, w, h, conf; int cls; float angle; int pred; }; // mars_obb_t
+
+// false = skipped; we, he = the expanded sides.  Behind this rule every conversion below is defined: we, he <= 32768, the centre inside the frame
+__device__ __forceinline__ bool rot_sides(const roi_obb_t d, const float expand, const int min_size, const int W, const int H, float &we, float &he) {
+    we = he = 0.0f;
+    if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf) && isfinite(d.angle))) return false;
+    if (!(d.w > 0.0f) || !(d.h > 0.0f)) return false;
+    we = __fmul_rn(d.w, expand);
+    he = __fmul_rn(d.h, expand);
+    if (we < (float)min_size || he < (float)min_size || we > 32768.0f || he > 32768.0f) return false;
+    return !(d.x < 0.0f || d.x > (float)W || d.y < 0.0f || d.y > (float)H);
+}
+
+// the rule and, for a kept box, the integer rectangle around the expanded box, clipped to the frame (the ROI table's x0 .. y1: never read back here)
+__device__ __forceinline__ bool rot_rect(const roi_obb_t d, const float cs, const float sn, const float expand, const int min_size, const int W, const int H,
+                                         int &x0, int &y0, int &x1, int &y1) {
+    x0 = y0 = x1 = y1 = 0;
+    float we, he;
+    if (!rot_sides(d, expand, min_size, W, H, we, he)) return false;
+    const float ac = fabsf(cs), as = fabsf(sn);
+    const float ex = __fmul_rn(__fadd_rn(__fmul_rn(we, ac), __fmul_rn(he, as)), 0.5f), ey = __fmul_rn(__fadd_rn(__fmul_rn(we, as), __fmul_rn(he, ac)), 0.5f);
+    x0 = (int)floorf(fmaxf(__fsub_rn(d.x, ex), 0.0f)); x1 = (int)ceilf(fminf(__fadd_rn(d.x, ex), (float)W));
+    y0 = (int)floorf(fmaxf(__fsub_rn(d.y, ey), 0.0f)); y1 = (int)ceilf(fminf(__fadd_rn(d.y, ey), (float)H));
+    return true;
+}
+
+struct rot_geom_t { int X0, Y0, Ux, Uy, Vx, Vy, nw, nh, px, py; };
+__device__ __forceinline__ int rot_q16(const float v) { return (int)rintf(__fmul_rn(v, 65536.0f)); }
+__device__ __forceinline__ rot_geom_t rot_geom(const roi_obb_t d, const float we, const float he, const float cs, const float sn, const int tw, const int th,
+                                               const int keep_aspect) {
+    rot_geom_t g;
+    g.nw = tw; g.nh = th;
+    if (keep_aspect) {
+        const int cw = max(1, (int)rintf(we)), ch = max(1, (int)rintf(he));
+        if ((long long)cw * th >= (long long)ch * tw) g.nh = max(1, (int)(((long long)ch * tw + cw / 2) / cw));
+        else g.nw = max(1, (int)(((long long)cw * th + ch / 2) / ch));
+    }
+    g.px = (tw - g.nw) / 2; g.py = (th - g.nh) / 2;
+    const float sx = __fdiv_rn(we, (float)(2 * g.nw)), sy = __fdiv_rn(he, (float)(2 * g.nh));
+    g.Ux = rot_q16(__fmul_rn(sx, cs)); g.Uy = rot_q16(__fmul_rn(sx, sn));
+    g.Vx = rot_q16(-__fmul_rn(sy, sn)); g.Vy = rot_q16(__fmul_rn(sy, cs));
+    g.X0 = rot_q16(__fsub_rn(d.x, 0.5f)); g.Y0 = rot_q16(__fsub_rn(d.y, 0.5f));
+    return g;
+}
+
 // One wave per frame.  PHASE 0 counts the frame's kept boxes into frame_kept[f]; PHASE 1 (a second launch: it needs every frame's count) sums
 // the counts of the frames in front into the frame's first slot, walks the list again the same way and writes the table.  A box's rank inside
 // its frame = kept boxes in front of it in the list: the ballot of the 64 boxes in flight, masked below the lane, plus the chunks before.
-template <int PHASE>
+// ROT: the lists are oriented boxes (32-byte records and their (cos, sin) pairs) under the skip rule of "Rotated crops".
+template <int PHASE, int ROT>
 __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
     const int f = blockIdx.x, lane = threadIdx.x;
     int base = 0;
@@ -74,7 +124,12 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
         const int i = i0 + lane;
         bool ok = false;
         int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-        if (i < n) {
+        if (i < n && ROT) {
+            const size_t k = (size_t)f * p.det_cap + i;
+            const roi_obb_t d = ((const roi_obb_t *)p.dets)[k];
+            ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
+                 rot_rect(d, p.csn[2 * k], p.csn[2 * k + 1], p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
+        } else if (i < n) {
             const roi_det_t d = dets[i];
             ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
                  roi_rect(d, p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
@@ -96,6 +151,7 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
     if (PHASE == 0 && lane == 0) p.frame_kept[f] = kept;
 }
 
+template <int ROT>
 __global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i == 0) {
@@ -107,9 +163,14 @@ __global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
     r.frame = p.frame_of_box[i];
     r.det = -1;
     const bool ok = r.frame >= 0 && r.frame < p.n_frames;
-    const roi_det_t d = ((const roi_det_t *)p.boxes)[i];
     r.x0 = r.y0 = r.x1 = r.y1 = 0;
-    if (ok) roi_rect(d, p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
+    if (ROT) {
+        const roi_obb_t d = ((const roi_obb_t *)p.boxes)[i];
+        if (ok) rot_rect(d, p.csn[2 * i], p.csn[2 * i + 1], p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
+    } else {
+        const roi_det_t d = ((const roi_det_t *)p.boxes)[i];
+        if (ok) roi_rect(d, p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
+    }
     ((roi_rec_t *)p.rois)[i] = r;
 }
 
@@ -282,23 +343,165 @@ __global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const
         for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
 }
 
+// ---- the rotated crop.  A workgroup owns ROI_R output rows of one slot, as above; it walks them in chunks of cn columns x rn rows.  The taps of a
+// chunk lie in a parallelogram of the source; its bounding rectangle is staged in LDS as one dword per pixel (R | G << 8 | B << 16; NV12 is
+// converted once per staged pixel pair, pixels outside the frame are 111 in every channel) and the blend reads its four taps from there.
+// cn and rn are chosen per strip so that the rectangle fits ROT_PIX pixels: the whole strip for the boxes a second stage sees, a few columns
+// at strong down-scales or near 45 degrees, and in the end one pixel (2 x 2 taps always fit).  Positions are the int64 sums of the header;
+// the only floats are those of rot_sides / rot_geom, once per workgroup.
+#define ROT_PIX 4096 // staged pixels: 16 KB
+static size_t rot_lds(int tw) { return roi_lds_stage(tw) + (size_t)ROT_PIX * 4; }
+
+// columns (dx = Ux, Vx) or rows (dy = Uy, Vy) of the bounding rectangle of a cn x rn chunk, at most: the positions span
+// D = 2 (cn - 1) |U| + 2 (rn - 1) |V| of Q16, so their integer parts span at most (D >> 16) + 1, + 1 for the tap to the right, + 1 to count
+// both ends; NV12 starts at an even column and stages pairs
+__device__ __forceinline__ long long rot_extent(const int cn, const int rn, const int u, const int v, const int pad) {
+    return ((2LL * (cn - 1) * abs(u) + 2LL * (rn - 1) * abs(v)) >> 16) + 3 + pad;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, const int off_buf) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    const int tid = threadIdx.x;
+    const int slot = blockIdx.y, ys = blockIdx.x * ROI_R;
+    const int rows = min(ROI_R, p.th - ys), row_b = p.tw * 3;
+    int8_t *dst = p.out + (size_t)slot * p.out_stride;
+    // this slot's box, from device memory: entry (frame, det) of the lists, or the caller's box `slot`
+    bool live = slot < p.n_out[0];
+    roi_rec_t r = {0, 0, 0, 0, 0, 0};
+    if (live) r = ((const roi_rec_t *)p.rois)[slot];
+    live = live && r.x1 > r.x0 && r.frame >= 0 && r.frame < p.n_frames && (r.det < 0 ? p.boxes != nullptr : (p.dets != nullptr && r.det < p.det_cap));
+    rot_geom_t g = {0, 0, 0, 0, 0, 0, p.tw, p.th, 0, 0};
+    if (live) {
+        const size_t k = r.det < 0 ? (size_t)slot : (size_t)r.frame * p.det_cap + r.det;
+        const roi_obb_t d = ((const roi_obb_t *)(r.det < 0 ? p.boxes : p.dets))[k];
+        const float cs = p.csn[2 * k], sn = p.csn[2 * k + 1];
+        float we, he;
+        live = rot_sides(d, p.expand, p.min_size, p.w, p.h, we, he);
+        if (live) g = rot_geom(d, we, he, cs, sn, p.tw, p.th, p.keep_aspect);
+    }
+    const int nw = g.nw, nh = g.nh, px = g.px, py = g.py;
+    const int r_lo = max(py - ys, 0), r_hi = min(py + nh - ys, rows); // the strip's rows inside the resized crop
+    if (!live || r_hi <= r_lo) { // an empty slot, a skipped box or a pad band: grey, the source is not touched
+        if (p.nhwc) roi_fill_run(dst + (size_t)ys * row_b, rows * row_b, tid);
+        else
+            for (int c = 0; c < 3; c++) roi_fill_run(dst + ((size_t)c * p.th + ys) * p.tw, rows * p.tw, tid);
+        return;
+    }
+    int8_t *stage = (int8_t *)sm;
+    unsigned *buf = (unsigned *)(sm + off_buf);
+    const uint8_t *frame = p.frames + (size_t)r.frame * p.frame_stride;
+    // the strip's LDS image, grey first: as in roi_crop_kernel
+    int8_t *st[3];
+    const int chan = ((ROI_R * p.tw + 15) & ~15) + 16;
+    if (p.nhwc) st[0] = st[1] = st[2] = stage + ((uintptr_t)(dst + (size_t)ys * row_b) & 15);
+    else
+        for (int c = 0; c < 3; c++) st[c] = stage + c * chan + ((uintptr_t)(dst + ((size_t)c * p.th + ys) * p.tw) & 15);
+    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
+    // the chunk: columns first, then rows, halved until the bounding rectangle fits
+    const int pad = FMT ? 2 : 0;
+    int cn = nw, rn = r_hi - r_lo;
+    while (cn > 1 && rot_extent(cn, rn, g.Ux, g.Vx, pad) * rot_extent(cn, rn, g.Uy, g.Vy, 0) > ROT_PIX) cn = (cn + 1) >> 1;
+    while (rn > 1 && rot_extent(cn, rn, g.Ux, g.Vx, pad) * rot_extent(cn, rn, g.Uy, g.Vy, 0) > ROT_PIX) rn = (rn + 1) >> 1;
+    const nv12_coef_t kc = nv12_coef(p.nv12_flags);
+    const long long X0 = g.X0, Y0 = g.Y0;
+    for (int ra = r_lo; ra < r_hi; ra += rn) {
+        const int rb = min(ra + rn, r_hi);
+        const long long b0 = 2 * (ys + ra - py) + 1 - nh, b1 = 2 * (ys + rb - 1 - py) + 1 - nh;
+        for (int c0 = 0; c0 < nw; c0 += cn) {
+            const int c1 = min(c0 + cn, nw);
+            const long long a0 = 2 * c0 + 1 - nw, a1 = 2 * (c1 - 1) + 1 - nw;
+            // the positions are affine in (a, b): their extremes are at the chunk's corners
+            const long long xa = min(a0 * g.Ux, a1 * g.Ux), xb = max(a0 * g.Ux, a1 * g.Ux), xc = min(b0 * g.Vx, b1 * g.Vx), xd = max(b0 * g.Vx, b1 * g.Vx);
+            const long long ya = min(a0 * g.Uy, a1 * g.Uy), yb = max(a0 * g.Uy, a1 * g.Uy), yc = min(b0 * g.Vy, b1 * g.Vy), yd = max(b0 * g.Vy, b1 * g.Vy);
+            int bx0 = (int)((X0 + xa + xc) >> 16);
+            const int bx1 = (int)((X0 + xb + xd) >> 16) + 1, by0 = (int)((Y0 + ya + yc) >> 16), by1 = (int)((Y0 + yb + yd) >> 16) + 1;
+            if (FMT) bx0 &= ~1;
+            const int bw = FMT ? (bx1 - bx0 + 2) & ~1 : bx1 - bx0 + 1, bh = by1 - by0 + 1; // bw * bh <= ROT_PIX by the choice of cn, rn
+            if (FMT) { // pairs of pixels from an even column: two Y bytes and their chroma pair; the frame's sizes are even, so a pair is inside or outside as a whole
+                const int hw = bw >> 1;
+                for (int it = tid; it < hw * bh; it += 256) {
+                    const int s = it / hw, u = it - s * hw, sx = bx0 + 2 * u, sy = by0 + s;
+                    unsigned v0 = 0x6f6f6fu, v1 = 0x6f6f6fu;
+                    if (sx >= 0 && sx < p.w && sy >= 0 && sy < p.h) {
+                        const uint8_t *gy = frame + (size_t)sy * p.w + sx, *gc = frame + ((size_t)p.h + (size_t)(sy >> 1)) * p.w + sx;
+                        const unsigned yv = (unsigned)gy[0] | (unsigned)gy[1] << 8, cv = (unsigned)gc[0] | (unsigned)gc[1] << 8;
+                        int c[4][3];
+                        nv12_quad(kc, yv, cv, c);
+                        v0 = (unsigned)c[0][0] | (unsigned)c[0][1] << 8 | (unsigned)c[0][2] << 16;
+                        v1 = (unsigned)c[1][0] | (unsigned)c[1][1] << 8 | (unsigned)c[1][2] << 16;
+                    }
+                    buf[s * bw + 2 * u] = v0;
+                    buf[s * bw + 2 * u + 1] = v1;
+                }
+            } else {
+                for (int it = tid; it < bw * bh; it += 256) {
+                    const int s = it / bw, u = it - s * bw, sx = bx0 + u, sy = by0 + s;
+                    unsigned v = 0x6f6f6fu;
+                    if (sx >= 0 && sx < p.w && sy >= 0 && sy < p.h) {
+                        const uint8_t *gp = frame + ((size_t)sy * p.w + sx) * 3;
+                        v = (unsigned)gp[0] | (unsigned)gp[1] << 8 | (unsigned)gp[2] << 16;
+                    }
+                    buf[s * bw + u] = v;
+                }
+            }
+            __syncthreads(); // (the first time round also: the grey strip)
+            const int wc = c1 - c0;
+            for (int idx = tid; idx < (rb - ra) * wc; idx += 256) {
+                const int rr = idx / wc, i = c0 + idx - rr * wc, row = ra + rr;
+                const long long a = 2 * i + 1 - nw, b = 2 * (ys + row - py) + 1 - nh;
+                const long long PX = X0 + a * g.Ux + b * g.Vx, PY = Y0 + a * g.Uy + b * g.Vy;
+                const int qx = (int)(PX >> 8), qy = (int)(PY >> 8);
+                const int fx = qx & 255, fy = qy & 255;
+                const unsigned *t = buf + ((qy >> 8) - by0) * bw + ((qx >> 8) - bx0);
+                const unsigned t00 = t[0], t01 = t[1], t10 = t[bw], t11 = t[bw + 1];
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const int top = (int)((t00 >> (8 * c)) & 255u) * (256 - fx) + (int)((t01 >> (8 * c)) & 255u) * fx;
+                    const int bot = (int)((t10 >> (8 * c)) & 255u) * (256 - fx) + (int)((t11 >> (8 * c)) & 255u) * fx;
+                    const int v = (top * (256 - fy) + bot * fy + 32768) >> 16;
+                    const int8_t q = (int8_t)(v - 128);
+                    if (p.nhwc) st[0][row * row_b + (px + i) * 3 + c] = q;
+                    else st[c][row * p.tw + px + i] = q;
+                }
+            }
+            __syncthreads(); // the staged rectangle may be overwritten
+        }
+    }
+    if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
+    else
+        for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
+}
+
 static bool roi_common_ok(const mhip_roi_t *p) {
     return p && p->rois && p->n_out && p->w > 0 && p->h > 0 && p->n_frames > 0 && p->slots > 0 && p->expand > 0 && p->min_size >= 1 &&
            (p->fmt == 0 || (p->fmt == 1 && !(p->w & 1) && !(p->h & 1) && !(p->nv12_flags & ~3u)));
 }
 
-extern "C" int mhip_roi_select(const mhip_roi_t *p) {
-    if (!roi_common_ok(p) || !p->dets || !p->counts || !p->frame_kept || p->det_cap <= 0 || p->cls_count < 0 || p->max_per_frame < 0) return -1;
-    hipLaunchKernelGGL(roi_select_kernel<0>, dim3((unsigned)p->n_frames), dim3(64), 0, mhip_stream_native(), *p);
-    hipLaunchKernelGGL(roi_select_kernel<1>, dim3((unsigned)p->n_frames), dim3(64), 0, mhip_stream_native(), *p);
-    return mhip_check(hipGetLastError(), "roi select");
+static int roi_select(const mhip_roi_t *p, const bool rot) {
+    if (!roi_common_ok(p) || !p->dets || !p->counts || !p->frame_kept || p->det_cap <= 0 || p->cls_count < 0 || p->max_per_frame < 0 || rot != (p->csn != nullptr)) return -1;
+    const dim3 g((unsigned)p->n_frames);
+    if (rot) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, 1>), g, dim3(64), 0, mhip_stream_native(), *p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, 1>), g, dim3(64), 0, mhip_stream_native(), *p);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, 0>), g, dim3(64), 0, mhip_stream_native(), *p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, 0>), g, dim3(64), 0, mhip_stream_native(), *p);
+    }
+    return mhip_check(hipGetLastError(), rot ? "roi select (oriented)" : "roi select");
 }
+extern "C" int mhip_roi_select(const mhip_roi_t *p) { return roi_select(p, false); }
+extern "C" int mhip_roi_rot_select(const mhip_roi_t *p) { return roi_select(p, true); }
 
-extern "C" int mhip_roi_rects(const mhip_roi_t *p) {
-    if (!roi_common_ok(p) || !p->boxes || !p->frame_of_box || p->n_boxes <= 0 || p->n_boxes > p->slots) return -1;
-    hipLaunchKernelGGL(roi_rects_kernel, dim3((unsigned)((p->n_boxes + 255) / 256)), dim3(256), 0, mhip_stream_native(), *p);
-    return mhip_check(hipGetLastError(), "roi rects");
+static int roi_rects(const mhip_roi_t *p, const bool rot) {
+    if (!roi_common_ok(p) || !p->boxes || !p->frame_of_box || p->n_boxes <= 0 || p->n_boxes > p->slots || rot != (p->csn != nullptr)) return -1;
+    const dim3 g((unsigned)((p->n_boxes + 255) / 256));
+    if (rot) hipLaunchKernelGGL(roi_rects_kernel<1>, g, dim3(256), 0, mhip_stream_native(), *p);
+    else hipLaunchKernelGGL(roi_rects_kernel<0>, g, dim3(256), 0, mhip_stream_native(), *p);
+    return mhip_check(hipGetLastError(), rot ? "roi rects (oriented)" : "roi rects");
 }
+extern "C" int mhip_roi_rects(const mhip_roi_t *p) { return roi_rects(p, false); }
+extern "C" int mhip_roi_rot_rects(const mhip_roi_t *p) { return roi_rects(p, true); }
 
 extern "C" int mhip_roi_fits(int w, int tw, int fmt) {
     if (w <= 0 || tw <= 0) return 0;
@@ -315,4 +518,20 @@ extern "C" int mhip_roi_crop(const mhip_roi_t *p) {
     if (p->fmt) hipLaunchKernelGGL(roi_crop_kernel<1>, g, dim3(256), (size_t)off_rows + rowbuf, mhip_stream_native(), *p, off_meta, off_stage, off_rows, rowbuf);
     else hipLaunchKernelGGL(roi_crop_kernel<0>, g, dim3(256), (size_t)off_rows + rowbuf, mhip_stream_native(), *p, off_meta, off_stage, off_rows, rowbuf);
     return mhip_check(hipGetLastError(), p->fmt ? "roi crop (nv12)" : "roi crop");
+}
+
+extern "C" int mhip_roi_rot_fits(int w, int h, int tw) {
+    if (w <= 0 || h <= 0 || tw <= 0) return 0;
+    return w <= 32767 && h <= 32767 && rot_lds(tw) <= 64 * 1024; // (x - 0.5) * 65536 of a centre inside the frame fits an int
+}
+
+extern "C" int mhip_roi_rot_crop(const mhip_roi_t *p) {
+    if (!roi_common_ok(p) || !p->frames || !p->out || !p->csn || (!p->dets && !p->boxes) || (p->dets && p->det_cap <= 0) || (p->boxes && p->n_boxes < p->slots) ||
+        p->tw <= 0 || p->th <= 0 || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 || !mhip_roi_rot_fits(p->w, p->h, p->tw))
+        return -1;
+    const int off_buf = (int)roi_lds_stage(p->tw);
+    const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);
+    if (p->fmt) hipLaunchKernelGGL(roi_rot_crop_kernel<1>, g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
+    else hipLaunchKernelGGL(roi_rot_crop_kernel<0>, g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
+    return mhip_check(hipGetLastError(), p->fmt ? "rotated roi crop (nv12)" : "rotated roi crop");
 }

@@ -228,8 +228,9 @@ typedef struct mars_model_ext {
     void *ev_pose[2];   /* timing events around the keypoint stage's launches on the auxiliary stream */
     /* oriented boxes (mars_obb.c) */
     void *obb_dev;      /* one block on the device: the angle tables [4][768] x float, kept and candidate counts [frames] x int each, candidate
-                         * records [frames][MARS_YOLO_MAX_DET] x mars_obb_t, their (cos, sin) pairs, kept records [frames][MARS_YOLO_MAX_DET] x mars_obb_t */
-    size_t obb_bytes, obb_cnt_off, obb_out_off;
+                         * records [frames][MARS_YOLO_MAX_DET] x mars_obb_t, their (cos, sin) pairs, kept records [frames][MARS_YOLO_MAX_DET] x mars_obb_t,
+                         * the kept records' (cos, sin) pairs (mars_roi.c cuts rotated crops along them) */
+    size_t obb_bytes, obb_cnt_off, obb_out_off, obb_csn_off;
     int obb_frames;                   /* of the last obb call; 0: there was none */
     float obb_lut_scale[4];           /* the scales the block's angle tables were built from */
     int obb_lut_n;                    /* tables that are up (0: none) */

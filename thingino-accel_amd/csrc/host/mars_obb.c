@@ -119,10 +119,11 @@ mars_error_t mars_hip_detect_obb_device(mars_model_t *model, const mars_yolo_dfl
     if (e == MARS_OK) e = mars_dfl_prepare(m, &c.dfl);
     if (e != MARS_OK) return e;
     /* the block: angle tables (at its start: their place does not move with the batch), the kept counts, candidate records, their (cos, sin)
-     * pairs, kept records */
+     * pairs, kept records, the kept records' (cos, sin) pairs */
     const size_t B = (size_t)m->batch, rec_b = ALIGN_UP(B * MARS_YOLO_MAX_DET * sizeof(mars_obb_t), 256);
     const size_t cnt_off = OBB_TAB, cand_off = cnt_off + ALIGN_UP(2 * B * sizeof(int), 256), csn_off = cand_off + rec_b;
-    const size_t out_off = csn_off + ALIGN_UP(B * MARS_YOLO_MAX_DET * 2 * sizeof(float), 256), total = out_off + rec_b;
+    const size_t csn_b = ALIGN_UP(B * MARS_YOLO_MAX_DET * 2 * sizeof(float), 256);
+    const size_t out_off = csn_off + csn_b, kcsn_off = out_off + rec_b, total = kcsn_off + csn_b; /* ... and the kept boxes' (cos, sin) pairs */
     if (!m->obb_dev || m->obb_bytes < total) {
         if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: an earlier tail may still use the old block */
         if (m->obb_dev) mhip_free(m->obb_dev);
@@ -157,13 +158,14 @@ mars_error_t mars_hip_detect_obb_device(mars_model_t *model, const mars_yolo_dfl
     p->cand = blk + cand_off;
     p->csn = (float *)(blk + csn_off);
     p->out = blk + out_off;
+    p->csn_out = (float *)(blk + kcsn_off);
     /* behind the graph's event on the auxiliary stream; the next run's layers that write one of these buffers wait for it (tail_read) */
     for (int k = 0; k < c.dfl.n; k++) m->mt[c.dfl.box_buf[k]].tail_read = m->mt[c.dfl.cls_buf[k]].tail_read = m->mt[bufs[k]].tail_read = 1;
     m->obb_frames = 0;
     e = mars_tail_on_aux(m, obb_launch_cb, &c);
     if (e != MARS_OK) return e;
     m->det_mapped = c.dfl.map;
-    m->obb_cnt_off = cnt_off; m->obb_out_off = out_off;
+    m->obb_cnt_off = cnt_off; m->obb_out_off = out_off; m->obb_csn_off = kcsn_off;
     m->obb_frames = m->batch;
     return MARS_OK;
 }

@@ -1,5 +1,5 @@
 /*
- * mars_roi.c -- host side of the ROI crops (include/mars_hip.h, "ROI crops"): argument checks, the ROI table hung on the destination
+ * mars_roi.c -- host side of the ROI crops (include/mars_hip.h, "ROI crops" and "Rotated crops"): argument checks, the ROI table hung on the destination
  * model, stream ordering, and the launches of csrc/hip/roi.hip.  The reference stops at the boxes (src/mars/mars_yolo_test.c:132-214);
  * a second stage there would cut crops on the host.  There is no CPU pixel path here: without the device every entry point fails.
  */
@@ -36,19 +36,23 @@ static mars_error_t roi_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_
     return MARS_OK;
 }
 
-mars_error_t mars_yolo_crop_boxes(const unsigned char *frames, int n_frames, const mars_det_t *boxes, const int *frame_of_box, int n_boxes,
-                                  const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc, signed char *out, mars_roi_t *rois) {
-    mhip_roi_t p;
-    const mars_error_t e = roi_opts(opts, tw, th, &p);
+/* ... and what the rotated forms refuse on top */
+static mars_error_t rot_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_roi_t *p) {
+    const mars_error_t e = roi_opts(o, tw, th, p);
     if (e != MARS_OK) return e;
-    if (!frames || !boxes || !frame_of_box || !out || n_frames <= 0 || n_boxes <= 0 || n_boxes > 65535) return MARS_ERR_INVALID_FILE;
+    return mhip_roi_rot_fits(o->src_w, o->src_h, tw) ? MARS_OK : MARS_ERR_INVALID_FILE;
+}
+
+/* the host-pointer forms: boxes of box_b bytes each; csn != NULL: oriented boxes and their (cos, sin) pairs */
+static mars_error_t crop_host(const unsigned char *frames, int n_frames, const void *boxes, size_t box_b, const float *csn, const int *frame_of_box, int n_boxes,
+                              mhip_roi_t p, int nhwc, signed char *out, mars_roi_t *rois) {
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    const size_t in_b = p.frame_stride * (size_t)n_frames, out_b = (size_t)tw * th * 3;
-    /* one device block: [frames][boxes][frame_of_box][counters][rois][out] */
-    size_t off[6], total = 0;
-    const size_t sz[6] = {in_b, (size_t)n_boxes * sizeof(mars_det_t), (size_t)n_boxes * sizeof(int), 16, (size_t)n_boxes * sizeof(mars_roi_t),
-                          out_b * (size_t)n_boxes};
-    for (int i = 0; i < 6; i++) {
+    const size_t in_b = p.frame_stride * (size_t)n_frames, out_b = (size_t)p.tw * p.th * 3;
+    /* one device block: [frames][boxes][frame_of_box][counters][rois][out][(cos, sin) pairs] */
+    size_t off[7], total = 0;
+    const size_t sz[7] = {in_b, (size_t)n_boxes * box_b, (size_t)n_boxes * sizeof(int), 16, (size_t)n_boxes * sizeof(mars_roi_t),
+                          out_b * (size_t)n_boxes, csn ? (size_t)n_boxes * 2 * sizeof(float) : 0};
+    for (int i = 0; i < 7; i++) {
         off[i] = total;
         total += ALIGN_UP(sz[i], 256);
     }
@@ -58,16 +62,44 @@ mars_error_t mars_yolo_crop_boxes(const unsigned char *frames, int n_frames, con
     p.boxes = d + off[1]; p.frame_of_box = (const int *)(d + off[2]); p.n_boxes = n_boxes;
     p.n_out = (int *)(d + off[3]); p.rois = d + off[4];
     p.out = (int8_t *)(d + off[5]); p.out_stride = out_b; p.slots = n_boxes; p.nhwc = nhwc != 0;
+    if (csn) p.csn = (const float *)(d + off[6]);
     int rc = mhip_h2d_async(d, frames, in_b);
     if (!rc) rc = mhip_h2d_async(d + off[1], boxes, sz[1]);
     if (!rc) rc = mhip_h2d_async(d + off[2], frame_of_box, sz[2]);
-    if (!rc) rc = mhip_roi_rects(&p);
-    if (!rc) rc = mhip_roi_crop(&p);
+    if (!rc && csn) rc = mhip_h2d_async(d + off[6], csn, sz[6]);
+    if (!rc) rc = csn ? mhip_roi_rot_rects(&p) : mhip_roi_rects(&p);
+    if (!rc) rc = csn ? mhip_roi_rot_crop(&p) : mhip_roi_crop(&p);
     if (!rc) rc = mhip_d2h_async(out, p.out, sz[5]);
     if (!rc && rois) rc = mhip_d2h_async(rois, p.rois, sz[4]);
     if (mhip_sync()) rc = -1;
     mhip_free(d);
     return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
+}
+
+mars_error_t mars_yolo_crop_boxes(const unsigned char *frames, int n_frames, const mars_det_t *boxes, const int *frame_of_box, int n_boxes,
+                                  const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc, signed char *out, mars_roi_t *rois) {
+    mhip_roi_t p;
+    const mars_error_t e = roi_opts(opts, tw, th, &p);
+    if (e != MARS_OK) return e;
+    if (!frames || !boxes || !frame_of_box || !out || n_frames <= 0 || n_boxes <= 0 || n_boxes > 65535) return MARS_ERR_INVALID_FILE;
+    return crop_host(frames, n_frames, boxes, sizeof(mars_det_t), NULL, frame_of_box, n_boxes, p, nhwc, out, rois);
+}
+
+mars_error_t mars_yolo_crop_obb(const unsigned char *frames, int n_frames, const mars_obb_t *boxes, const int *frame_of_box, int n_boxes,
+                                const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc, signed char *out, mars_roi_t *rois) {
+    mhip_roi_t p;
+    const mars_error_t e = rot_opts(opts, tw, th, &p);
+    if (e != MARS_OK) return e;
+    if (!frames || !boxes || !frame_of_box || !out || n_frames <= 0 || n_boxes <= 0 || n_boxes > 65535) return MARS_ERR_INVALID_FILE;
+    float *csn = (float *)malloc((size_t)n_boxes * 2 * sizeof(float)); /* the host libm's, as mars_yolo_obb_nms takes them */
+    if (!csn) return MARS_ERR_ALLOC_FAILED;
+    for (int i = 0; i < n_boxes; i++) {
+        csn[2 * i] = cosf(boxes[i].angle);
+        csn[2 * i + 1] = sinf(boxes[i].angle);
+    }
+    const mars_error_t rc = crop_host(frames, n_frames, boxes, sizeof(mars_obb_t), csn, frame_of_box, n_boxes, p, nhwc, out, rois);
+    free(csn);
+    return rc;
 }
 
 void mars_roi_release(mars_model_ext_t *m) {
@@ -89,12 +121,13 @@ static int roi_table(mars_model_ext_t *m, int slots, int frames) {
     return 0;
 }
 
-mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
-                                             const mars_hip_roi_opts_t *opts) {
+/* the device chain; rot: over the oriented boxes of det_model's last obb call */
+static mars_error_t crop_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index, const mars_hip_roi_opts_t *opts,
+                                int rot) {
     if (!det_model || !dst_model || !frames_dev || !opts) return MARS_ERR_INVALID_FILE;
     { /* what can be said without looking at either model */
         mhip_roi_t q;
-        const mars_error_t e = roi_opts(opts, 1, 1, &q);
+        const mars_error_t e = rot ? rot_opts(opts, 1, 1, &q) : roi_opts(opts, 1, 1, &q);
         if (e != MARS_OK) return e;
     }
     if (det_model == dst_model) return MARS_ERR_INVALID_TENSOR;
@@ -110,13 +143,20 @@ mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void
     if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0 || !m->mt[tid].dev || m->mt[tid].stride < (size_t)tw * th * 3)
         return MARS_ERR_INVALID_TENSOR;
     if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    if (rot && (!det->obb_dev || det->obb_frames != det->batch)) return MARS_ERR_INVALID_TENSOR;            /* no obb results in HBM */
     mhip_roi_t p;
-    const mars_error_t e = roi_opts(opts, tw, th, &p);
+    const mars_error_t e = rot ? rot_opts(opts, tw, th, &p) : roi_opts(opts, tw, th, &p);
     if (e != MARS_OK) return e;
     if (m->batch > 65535) return MARS_ERR_INVALID_TENSOR;
     if (roi_table(m, m->batch, det->batch)) return MARS_ERR_ALLOC_FAILED;
     p.frames = (const uint8_t *)frames_dev; p.n_frames = det->batch;
-    p.dets = det->det_dev; p.counts = det->det_counts_dev; p.det_cap = MARS_YOLO_MAX_DET;
+    if (rot) { /* the kept records, their counts and their (cos, sin) pairs: index-aligned with the detection list */
+        const uint8_t *blk = (const uint8_t *)det->obb_dev;
+        p.dets = blk + det->obb_out_off; p.counts = (const int *)(blk + det->obb_cnt_off); p.csn = (const float *)(blk + det->obb_csn_off);
+    } else {
+        p.dets = det->det_dev; p.counts = det->det_counts_dev;
+    }
+    p.det_cap = MARS_YOLO_MAX_DET;
     p.n_out = (int *)m->roi_dev;
     p.rois = (uint8_t *)m->roi_dev + 16;
     p.frame_kept = (int *)((uint8_t *)m->roi_dev + 16 + (size_t)m->roi_cap_slots * sizeof(mars_roi_t));
@@ -130,17 +170,18 @@ mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void
         if (mhip_stream_wait(0, m->ev_label_done)) return MARS_ERR_LAYER_FAILED;
         m->label_pending = 0;
     }
-    if (mhip_roi_select(&p) || mhip_roi_crop(&p)) return MARS_ERR_LAYER_FAILED;
+    if (rot ? (mhip_roi_rot_select(&p) || mhip_roi_rot_crop(&p)) : (mhip_roi_select(&p) || mhip_roi_crop(&p))) return MARS_ERR_LAYER_FAILED;
     m->roi_slots = m->batch;
     m->roi_from = det;
     return MARS_OK;
 }
 
-mars_error_t mars_hip_crop_detections(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
-                                      const mars_hip_roi_opts_t *opts) {
+/* the same with the frames in host memory: upload, crop, wait */
+static mars_error_t crop_upload(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index, const mars_hip_roi_opts_t *opts,
+                                int rot) {
     if (!det_model || !dst_model || !frames || !opts) return MARS_ERR_INVALID_FILE;
     mhip_roi_t q;
-    mars_error_t e = roi_opts(opts, 1, 1, &q);
+    mars_error_t e = rot ? rot_opts(opts, 1, 1, &q) : roi_opts(opts, 1, 1, &q);
     if (e != MARS_OK) return e;
     if (det_model == dst_model) return MARS_ERR_INVALID_TENSOR;
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
@@ -151,10 +192,30 @@ mars_error_t mars_hip_crop_detections(mars_model_t *det_model, const unsigned ch
     if (!d) return MARS_ERR_ALLOC_FAILED;
     mhip_select_stream(0);
     if (mhip_h2d_async(d, frames, in_b)) e = MARS_ERR_LAYER_FAILED;
-    if (e == MARS_OK) e = mars_hip_crop_detections_device(det_model, d, dst_model, input_index, opts);
+    if (e == MARS_OK) e = crop_device(det_model, d, dst_model, input_index, opts, rot);
     if (mhip_sync() && e == MARS_OK) e = MARS_ERR_LAYER_FAILED;
     mhip_free(d);
     return e;
+}
+
+mars_error_t mars_hip_crop_detections_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
+                                             const mars_hip_roi_opts_t *opts) {
+    return crop_device(det_model, frames_dev, dst_model, input_index, opts, 0);
+}
+
+mars_error_t mars_hip_crop_detections(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
+                                      const mars_hip_roi_opts_t *opts) {
+    return crop_upload(det_model, frames, dst_model, input_index, opts, 0);
+}
+
+mars_error_t mars_hip_crop_obb_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
+                                      const mars_hip_roi_opts_t *opts) {
+    return crop_device(det_model, frames_dev, dst_model, input_index, opts, 1);
+}
+
+mars_error_t mars_hip_crop_obb(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
+                               const mars_hip_roi_opts_t *opts) {
+    return crop_upload(det_model, frames, dst_model, input_index, opts, 1);
 }
 
 mars_error_t mars_hip_roi_results(mars_model_t *dst_model, mars_roi_t *rois, int cap, int *n_kept, int *n_dropped) {

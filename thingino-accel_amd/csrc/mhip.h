@@ -428,11 +428,19 @@ typedef struct {
     int slots, tw, th, nhwc;
     void *rois; int *n_out;
     int *frame_kept;                            /* mhip_roi_select: scratch, [n_frames] */
+    const float *csn;                           /* the mhip_roi_rot_* calls only ("Rotated crops"): dets / boxes hold records of 32 bytes (mars_obb_t)
+                                                 * and csn the (cos, sin) pair of every one of them, index-aligned */
 } mhip_roi_t;
 int mhip_roi_select(const mhip_roi_t *p); /* the selection rules over the detection lists, frame-major, list order; two launches */
 int mhip_roi_rects(const mhip_roi_t *p);  /* the rectangle rule alone: slot i = box i (x1 == x0: skipped), n_out = {n_boxes, 0} */
 int mhip_roi_crop(const mhip_roi_t *p);   /* slots >= n_out[0], skipped slots and pad bands are filled with -17 */
 int mhip_roi_fits(int w, int tw, int fmt); /* 1: the crop kernel's LDS holds two source rows of such frames and a strip of such a target */
+/* the same three over oriented boxes: the skip rule of "Rotated crops" in the rectangle rule's place, x0 .. y1 = the enclosing rectangle (for the
+ * caller only), and a crop kernel that reads box (frame, det) of dets -- box `slot` of boxes where det < 0 -- and samples along its axes */
+int mhip_roi_rot_select(const mhip_roi_t *p);
+int mhip_roi_rot_rects(const mhip_roi_t *p);
+int mhip_roi_rot_crop(const mhip_roi_t *p);
+int mhip_roi_rot_fits(int w, int h, int tw); /* 1: positions of such frames fit the Q16 integers and a strip of such a target fits the LDS */
 
 /* ---- second-stage labels (classify.hip): int8 feature maps -> per-channel int32 sums -> ranked top-K entries; include/mars_hip.h
  * "Second-stage labels" states the arithmetic.  Every pointer is device memory. */
@@ -574,6 +582,7 @@ typedef struct {
     float *csn;             /* [frames][1000][2]: cos, sin of every candidate's angle (permuted with the records) */
     int *cand_counts;       /* [frames] candidates (the decode writes it; clamped to 0 .. 1000) */
     void *out;              /* [frames][1000] records: the kept boxes, mapped */
+    float *csn_out;         /* NULL, or [frames][1000][2]: cos, sin of every kept box, index-aligned with out (the rotated crops read them) */
     int *out_counts;        /* [frames] kept */
     void *dets;             /* NULL, or [frames][1000] records of 24 bytes: the enclosing upright rectangles, index-aligned with out */
     int *counts;            /* NULL, or [frames] kept (the detection list's) */

@@ -243,7 +243,7 @@ EXPORTS = {
                    "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks",
                    "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints",
                    "mars_hip_detect_obb_device", "mars_hip_obb_results", "mars_hip_detect_obb", "mars_hip_obb_ms", "mars_yolo_obb_nms",
-                   "mars_yolo_obb_corners",
+                   "mars_yolo_obb_corners", "mars_yolo_crop_obb", "mars_hip_crop_obb_device", "mars_hip_crop_obb",
                    "mars_tile_grid", "mars_hip_preprocess_tiles_device", "mars_hip_preprocess_tiles", "mars_hip_merge_tiles_device",
                    "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
@@ -328,6 +328,9 @@ def lib():
     L.mars_hip_crop_detections_device.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
     L.mars_hip_crop_detections.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
     L.mars_hip_roi_results.argtypes = [P(MarsModel), C.c_void_p, C.c_int, P(C.c_int), P(C.c_int)]
+    L.mars_yolo_crop_obb.argtypes = L.mars_yolo_crop_boxes.argtypes
+    L.mars_hip_crop_obb_device.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
+    L.mars_hip_crop_obb.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
     L.mars_yolo_classify_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P(ClsOpts), C.c_void_p, C.c_void_p]
     L.mars_hip_classify_device.argtypes = [P(MarsModel), P(ClsOpts)]
     L.mars_hip_classify_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int)]
@@ -507,24 +510,34 @@ def roi_opts(w, h, fmt=CAMERA_RGB, src_flags=0, expand=0.0, min_conf=0.0, min_si
     return o
 
 
-def crop_boxes(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
-    """mars_yolo_crop_boxes: frames (uint8, [n] frames of opts.src_w x opts.src_h, RGB or NV12) and boxes (DET_DTYPE records, box i in frame
-    frame_of_box[i]) -> (int8 crops [n_boxes][tw * th * 3], ROI_DTYPE records [n_boxes]; x1 == x0: skipped, its crop is all -17), on the GPU"""
+def _crop_host(fn, dtype, frames, boxes, frame_of_box, opts, tw, th, nhwc):
     a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
     fb = opts.src_w * opts.src_h * 3 // (2 if opts.src_format == CAMERA_NV12 else 1)
     if fb <= 0 or a.size % fb:
         raise ValueError("frames of %d x %d are %d bytes each, got %d" % (opts.src_w, opts.src_h, fb, a.size))
-    b = np.ascontiguousarray(boxes, dtype=DET_DTYPE).reshape(-1)
+    b = np.ascontiguousarray(boxes, dtype=dtype).reshape(-1)
     fo = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
     if fo.size != b.size:
         raise ValueError("one frame index per box")
     out = np.zeros((b.size, tw * th * 3), dtype=np.int8)
     rois = np.zeros(b.size, dtype=ROI_DTYPE)
-    rc = lib().mars_yolo_crop_boxes(a.ctypes.data, a.size // fb, b.ctypes.data, fo.ctypes.data, b.size, C.byref(opts), tw, th, int(bool(nhwc)),
-                                    out.ctypes.data, rois.ctypes.data)
+    rc = getattr(lib(), fn)(a.ctypes.data, a.size // fb, b.ctypes.data, fo.ctypes.data, b.size, C.byref(opts), tw, th, int(bool(nhwc)),
+                            out.ctypes.data, rois.ctypes.data)
     if rc != MARS_OK:
-        raise MarsError(rc, "mars_yolo_crop_boxes")
+        raise MarsError(rc, fn)
     return out, rois
+
+
+def crop_boxes(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
+    """mars_yolo_crop_boxes: frames (uint8, [n] frames of opts.src_w x opts.src_h, RGB or NV12) and boxes (DET_DTYPE records, box i in frame
+    frame_of_box[i]) -> (int8 crops [n_boxes][tw * th * 3], ROI_DTYPE records [n_boxes]; x1 == x0: skipped, its crop is all -17), on the GPU"""
+    return _crop_host("mars_yolo_crop_boxes", DET_DTYPE, frames, boxes, frame_of_box, opts, tw, th, nhwc)
+
+
+def crop_obb(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
+    """mars_yolo_crop_obb: crop_boxes for oriented boxes (OBB_DTYPE records), each cut along its own axes ("Rotated crops"); x0 .. y1 of the
+    ROI records = the enclosing rectangle"""
+    return _crop_host("mars_yolo_crop_obb", OBB_DTYPE, frames, boxes, frame_of_box, opts, tw, th, nhwc)
 
 
 def tile_grid(W, H, tile_w, tile_h, overlap_x=0, overlap_y=0):
@@ -1204,6 +1217,20 @@ class Model:
             rc = lib().mars_hip_crop_detections(det_model.p, a.ctypes.data, self.p, input_index, C.byref(opts))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_crop_detections")
+
+    def crop_obb_detections(self, det_model, frames, opts, input_index=0):
+        """crop_detections over the oriented boxes det_model's last detect_obb_device left in HBM, each cut along its own axes: frames =
+        uint8 host array, uploaded, the call waits (mars_hip_crop_obb)"""
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        rc = lib().mars_hip_crop_obb(det_model.p, a.ctypes.data, self.p, input_index, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_crop_obb")
+
+    def crop_obb_detections_device(self, det_model, frames_dev, opts, input_index=0):
+        """the same with frames_dev = a device address (DeviceBuffer.ptr); enqueues only (mars_hip_crop_obb_device)"""
+        rc = lib().mars_hip_crop_obb_device(det_model.p, C.c_void_p(frames_dev), self.p, input_index, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_crop_obb_device")
 
     def roi_results(self):
         """-> (ROI_DTYPE records of the crops the last crop_detections() wrote, frame k of the input <- rois[k]; boxes dropped for want of a frame)"""
