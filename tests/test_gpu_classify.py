@@ -128,6 +128,29 @@ def test_classify_through_a_model(gpu, C, nchw, fusion):
     m.close()
 
 
+def test_result_block_grows_and_is_reused(gpu):
+    """one model, top_k 1 -> 8 (the cap: the result block has to grow) -> 1 (the larger block is kept and holds the smaller layout): every
+    call's entries and sums are the restatement's, and nothing can be fetched before the first.  (The classify stage records no events of
+    its own: there is no device time to ask for)"""
+    C_, nchw = 10, False
+    d, mid, out = head_graph(C_, nchw)
+    m = gpu.Model(d, batch=3)
+    with pytest.raises(gpu.MarsError) as e:
+        m.classify_results(1)
+    assert e.value.code == gpu.MARS_ERR_INVALID_TENSOR
+    nb = m.input_view(0).shape[1]
+    for f in range(3):
+        m.input_view(0)[f] = lcg_frame(0xC1A60000 + 16 * C_ + f, nb)
+    m.run()
+    bytes_ = frames_of(m, out, 3)
+    want, want_sums = classify_np(bytes_, C_, 8, 8, not nchw, 0.37, 8, False)
+    for k in (1, 8, 1):
+        top, sums = m.classify(top_k=k, output_index=0)
+        same(sums, want_sums, ("growth", k, "sums"))
+        same(top, np.ascontiguousarray(want[:, :k]), ("growth", k))
+    m.close()
+
+
 # ---- the chain ---------------------------------------------------------------------------------------------------------------------------
 def out_geometry(d2, tout):
     """-> (C, H, W, nhwc, scale) of the second stage's output tensor"""

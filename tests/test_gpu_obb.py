@@ -79,6 +79,28 @@ def test_hand_built_graphs(gpu, nchw, S, batch, fusion):
     m.close()
 
 
+def test_result_block_follows_the_batch(gpu):
+    """one model at batch 1 -> 3 -> 1 (mars_hip_set_batch between the calls): the result block and the angle tables inside it are there for
+    every batch, every call's boxes are the restatement's, the stage's device time is there after each, and nothing can be fetched before
+    the first"""
+    S, nchw = 64, False
+    d, heads, angs, _, _ = obb_graph(nchw, S)
+    m = gpu.Model(d, batch=1)
+    with pytest.raises(gpu.MarsError) as e:
+        m.obb_results()
+    assert e.value.code == gpu.MARS_ERR_INVALID_TENSOR and m.obb_ms() < 0
+    for batch in (1, 3, 1):
+        m.set_batch(batch)
+        fill(m, 0x0BB00000 + S, zero_frame=1)
+        m.run()
+        got = m.detect_obb(gpu.obb_opts(angs), **DFL_KW)
+        want = model_expected(gpu, m, heads, angs, nchw, S, DFL_KW)
+        check(got, want, ("growth", batch))
+        assert len(want) == batch and len(want[0][0]) > 0
+        assert m.obb_ms() >= 0
+    m.close()
+
+
 def test_flags_and_overrides(gpu):
     """angle_scales overrides, MARS_OBB_AGNOSTIC on and off, src = 1280 x 720, nms_thresh 0.3 and 0.7: one graph, many calls"""
     S, nchw = 128, False

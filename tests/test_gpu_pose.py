@@ -155,6 +155,28 @@ def test_hand_built_graphs(gpu, K, D, nchw):
     m.close()
 
 
+def test_result_block_grows_and_is_reused(gpu):
+    """one model, max_per_frame 1 -> 256 (the cap: the result block has to grow, and the visibility tables inside it go up again) -> 1 (the
+    larger block is kept and holds the smaller layout): every call's boxes and keypoints are the restatement's, the stage's device time is
+    there after each, and nothing can be fetched before the first"""
+    S, K, D, nchw = 64, 17, 3, False
+    d, heads, kpts, _, _ = pose_graph(K, D, nchw, S)
+    m = gpu.Model(d, batch=3)
+    with pytest.raises(gpu.MarsError) as e:
+        m.pose_results()
+    assert e.value.code == gpu.MARS_ERR_INVALID_TENSOR and m.pose_ms() < 0
+    fill(m, GRAPH_SEED + K, zero_frame=1)
+    m.run()
+    for n in (1, 256, 1):
+        kw = dict(max_per_frame=n)
+        got = m.detect_pose(gpu.pose_opts(kpts, num_kpt=K, kpt_dim=D, **kw), **DFL_KW)
+        want = model_expected(gpu, m, heads, kpts, nchw, S, K, D, kw)
+        check(got, want, ("growth", n))
+        assert got[1].shape == (3, n) and got[2].shape == (3, n, K) and any(len(w[0]) > 1 for w in want)
+        assert m.pose_ms() >= 0
+    m.close()
+
+
 def many_kept_frames(rng, heads, K, D):
     """bytes for three frames of a 128 x 128 graph (336 cells): frame 0 -- every cell a candidate at one of two class-byte levels (the tail's
     tie-queue replay decides the order), every box distribution one sharp bin near the cell (small boxes: few are suppressed); frame 1 --

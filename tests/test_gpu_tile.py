@@ -327,6 +327,33 @@ def test_chain_through_a_model(gpu, nchw, batch):
         b.free()
 
 
+def test_merged_block_follows_the_batch(gpu):
+    """one model at batch 2 -> 4 -> 2 over the two-tile table (1, 2, 1 camera frames; mars_hip_set_batch between the calls): the merged
+    arrays are there for every batch, every merge is the restatement's, the merge's device time is there after each, and nothing can be
+    fetched before the first"""
+    tiles = MODEL_SHAPES[4]
+    d, tin, heads = tile_graph(False)
+    m = gpu.Model(d, batch=2)
+    with pytest.raises(gpu.MarsError) as e:
+        m.tile_results()
+    assert e.value.code == gpu.MARS_ERR_INVALID_TENSOR and m.tile_ms() < 0
+    o = gpu.tile_opts(CW, CH, tiles, merge_thresh=0.4)
+    dfl = dict(heads=[(b, c, s) for b, c, s in heads], reg_max=R, **DFL_KW)
+    for rnd, batch in enumerate((2, 4, 2)):
+        m.set_batch(batch)
+        cams = batch // len(tiles)
+        m.preprocess_tiles(camera_frames(cams, 0x711E3000 + 64 * rnd), o)
+        m.run_device(sync=False)
+        m.detect_dfl_device(**dfl)
+        m.merge_tiles(o)
+        got = m.tile_results()
+        lists = m.detect_results()
+        assert sum(len(l) > 0 for l in lists) >= cams, "the threshold leaves candidates in too few tiles"
+        same_merge(got, tileref.merge(*lists_to_arrays(lists), tiles, CW, CH, S, S, merge_thresh=0.4), ("growth", batch))
+        assert m.tile_ms() >= 0 and gpu.lib().mars_hip_tile_frames(m.p) == cams
+    m.close()
+
+
 def test_refusals_through_the_model(gpu):
     FILE, TENSOR = gpu.MARS_ERR_INVALID_FILE, gpu.MARS_ERR_INVALID_TENSOR
     d, tin, heads = tile_graph(True)

@@ -169,6 +169,27 @@ def test_hand_built_graphs(gpu, nm, nchw, fusion):
         m.close()
 
 
+def test_result_block_grows_and_is_reused(gpu):
+    """one model, max_per_frame 1 -> 64 (the cap: the result block has to grow) -> 1 (the larger block is kept and holds the smaller layout):
+    every call's boxes and masks are the restatement's, the stage's device time is there after each, and nothing can be fetched before the first"""
+    S, nm, nchw = 64, 4, False
+    d, heads, coefs, pr = seg_graph(nm, nchw, S)
+    m = gpu.Model(d, batch=3)
+    with pytest.raises(gpu.MarsError) as e:
+        m.mask_results()
+    assert e.value.code == gpu.MARS_ERR_INVALID_TENSOR and gpu.lib().mars_hip_mask_ms(m.p) < 0
+    fill(m, 0x5E600000 + S, zero_frame=1)
+    m.run()
+    for n in (1, 64, 1):
+        seg_kw = dict(max_per_frame=n)
+        got = m.detect_seg(gpu.seg_opts(coefs, pr, **seg_kw), **DFL_KW)
+        want = model_expected(gpu, m, heads, coefs, pr, nchw, S, seg_kw)
+        check(got, want, ("growth", n))
+        assert got[2].shape == (3, n, S // 4, 1) and len(want[0][0]) > 1
+        assert gpu.lib().mars_hip_mask_ms(m.p) >= 0
+    m.close()
+
+
 @pytest.mark.parametrize("nchw", [False, True])
 @pytest.mark.parametrize("nm", [4, 32])
 def test_chosen_bytes(gpu, nm, nchw):

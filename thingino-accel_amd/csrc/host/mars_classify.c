@@ -22,10 +22,10 @@ static mars_error_t cls_opts(const mars_hip_cls_opts_t *o, int *top_k, int *soft
     return MARS_OK;
 }
 
-static size_t cls_block(const mhip_classify_t *p, size_t *sums_off, size_t *top_off) {
-    *sums_off = ALIGN_UP((size_t)p->frames * p->nsplit * p->c * sizeof(int), 256);
-    *top_off = *sums_off + ALIGN_UP((size_t)p->frames * p->c * sizeof(int), 256);
-    return *top_off + ALIGN_UP((size_t)p->frames * p->top_k * sizeof(mars_cls_t), 256);
+/* the block of a classify call: [frames][nsplit][C] partial sums, [frames][C] sums, [frames][top_k] entries -> bytes */
+static size_t cls_block(const mhip_classify_t *p, size_t off[3]) {
+    const size_t sz[3] = {(size_t)p->frames * p->nsplit * p->c * sizeof(int), (size_t)p->frames * p->c * sizeof(int), (size_t)p->frames * p->top_k * sizeof(mars_cls_t)};
+    return mars_block_layout(sz, 3, off);
 }
 
 mars_error_t mars_yolo_classify_maps(const signed char *maps, int n, int c, int h, int w, int nhwc, float scale, const mars_hip_cls_opts_t *opts,
@@ -37,7 +37,7 @@ mars_error_t mars_yolo_classify_maps(const signed char *maps, int n, int c, int 
     if (!maps || !top || n <= 0 || c <= 0 || h <= 0 || w <= 0) return MARS_ERR_INVALID_FILE;
     if (c > MHIP_CLS_MAX_C || (long long)h * w > (1LL << 24) || n > 65535) return MARS_ERR_INVALID_TENSOR;
     p.scale = opts->scale != 0 ? opts->scale : scale;
-    if (!(p.scale > 0) || !isfinite(p.scale)) return MARS_ERR_INVALID_TENSOR;
+    if (!mars_scale_ok(p.scale)) return MARS_ERR_INVALID_TENSOR;
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     p.frames = n; p.c = c; p.hw = h * w;
     p.frame_stride = (size_t)c * p.hw;
@@ -48,14 +48,14 @@ mars_error_t mars_yolo_classify_maps(const signed char *maps, int n, int c, int 
     if (!d_in) return MARS_ERR_ALLOC_FAILED;
     p.base = d_in;
     p.nsplit = mhip_classify_split(&p);
-    size_t so, to;
-    const size_t total = cls_block(&p, &so, &to);
+    size_t off[3];
+    const size_t total = cls_block(&p, off);
     uint8_t *d = p.nsplit > 0 ? (uint8_t *)mhip_malloc(total) : NULL;
     if (!d) {
         mhip_free(d_in);
         return p.nsplit > 0 ? MARS_ERR_ALLOC_FAILED : MARS_ERR_INVALID_TENSOR;
     }
-    p.partial = (int *)d; p.sums = (int *)(d + so); p.top = d + to;
+    p.partial = (int *)d; p.sums = (int *)(d + off[1]); p.top = d + off[2];
     int rc = mhip_h2d_async(d_in, maps, in_b);
     if (!rc) rc = mhip_classify(&p);
     if (!rc) rc = mhip_d2h_async(top, p.top, (size_t)n * p.top_k * sizeof(mars_cls_t));
@@ -64,15 +64,6 @@ mars_error_t mars_yolo_classify_maps(const signed char *maps, int n, int c, int 
     mhip_free(d);
     mhip_free(d_in);
     return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
-}
-
-void mars_cls_release(mars_model_ext_t *m) {
-    if (m->cls_dev) mhip_free(m->cls_dev);
-    if (m->label_dev) mhip_free(m->label_dev);
-    m->cls_dev = m->label_dev = NULL;
-    m->cls_bytes = 0;
-    m->cls_frames = m->cls_c = m->cls_top_k = m->label_cap = m->label_frames = m->label_pending = 0;
-    mars_match_release(m);
 }
 
 static int cls_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, int *counts_dev) {
@@ -84,11 +75,10 @@ mars_error_t mars_hip_classify_device(mars_model_t *model, const mars_hip_cls_op
     mhip_classify_t p;
     memset(&p, 0, sizeof(p));
     if (!model) return MARS_ERR_INVALID_FILE;
-    const mars_error_t e = cls_opts(opts, &p.top_k, &p.softmax);
+    mars_error_t e = cls_opts(opts, &p.top_k, &p.softmax);
     if (e != MARS_OK) return e;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe) return MARS_ERR_INVALID_TENSOR; /* a pipe's slots own their buffers */
+    if ((e = mars_stage_guard(m)) != MARS_OK) return e;
     int T;
     if (opts->tensor > 0) T = opts->tensor;
     else if (opts->output_index < 0 || (uint32_t)opts->output_index >= model->header.num_outputs) return MARS_ERR_INVALID_TENSOR;
@@ -101,7 +91,7 @@ mars_error_t mars_hip_classify_device(mars_model_t *model, const mars_hip_cls_op
     if (c > MHIP_CLS_MAX_C || (long long)h * w > (1LL << 24) || m->batch > 65535) return MARS_ERR_INVALID_TENSOR;
     if (mars_locate_i8(m, T, c, h, w, 1, &buf, &off, &p.pix_step, &p.ch_step)) return MARS_ERR_INVALID_TENSOR;
     p.scale = opts->scale != 0 ? opts->scale : d->scale;
-    if (!(p.scale > 0) || !isfinite(p.scale)) return MARS_ERR_INVALID_TENSOR;
+    if (!mars_scale_ok(p.scale)) return MARS_ERR_INVALID_TENSOR;
     const mtensor_t *tb = &m->mt[buf];
     p.frames = m->batch; p.c = c; p.hw = h * w;
     p.base = (const int8_t *)tb->dev + off;
@@ -119,41 +109,29 @@ mars_error_t mars_hip_classify_device(mars_model_t *model, const mars_hip_cls_op
     }
     p.nsplit = mhip_classify_split(&p);
     if (p.nsplit <= 0) return MARS_ERR_INVALID_TENSOR;
-    size_t so, to;
-    const size_t total = cls_block(&p, &so, &to);
-    if (!m->cls_dev || m->cls_bytes < total) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: an earlier tail or scatter may still use the old block */
-        if (m->cls_dev) mhip_free(m->cls_dev);
-        m->cls_frames = 0; m->cls_bytes = 0;
-        m->cls_dev = mhip_malloc(total);
-        if (!m->cls_dev) return MARS_ERR_ALLOC_FAILED;
-        m->cls_bytes = total;
-    }
-    p.partial = (int *)m->cls_dev;
-    p.sums = (int *)((uint8_t *)m->cls_dev + so);
-    p.top = (uint8_t *)m->cls_dev + to;
+    size_t boff[3];
+    if ((e = mars_block_reserve(&m->cls, cls_block(&p, boff), 0, NULL)) != MARS_OK) return e;
+    p.partial = (int *)m->cls.dev;
+    p.sums = (int *)((uint8_t *)m->cls.dev + boff[1]);
+    p.top = (uint8_t *)m->cls.dev + boff[2];
     /* behind the graph's event on the auxiliary stream; the next run's layers that write the tensor's buffer wait for it (tail_read), the
      * rest of that run overlaps it.  An earlier label scatter reads the block from the same stream: it is in front */
     m->mt[buf].tail_read = 1;
-    m->cls_frames = 0;
-    const mars_error_t e2 = mars_tail_on_aux(m, cls_launch_cb, &p);
-    if (e2 != MARS_OK) return e2;
-    m->cls_sums_off = so; m->cls_top_off = to;
-    m->cls_frames = p.frames; m->cls_c = c; m->cls_top_k = p.top_k;
+    m->cls.frames = 0;
+    if ((e = mars_tail_on_aux(m, cls_launch_cb, &p)) != MARS_OK) return e;
+    m->cls_sums_off = boff[1]; m->cls_top_off = boff[2];
+    m->cls.frames = p.frames; m->cls_c = c; m->cls_top_k = p.top_k;
     return MARS_OK;
 }
 
 mars_error_t mars_hip_classify_results(mars_model_t *model, mars_cls_t *top, int *sums, int *channels) {
     if (!model || !top) return MARS_ERR_INVALID_FILE;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->cls_dev || m->cls_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no classify call yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    m->tail_pending = 0;
-    if (mhip_d2h_async(top, (uint8_t *)m->cls_dev + m->cls_top_off, (size_t)m->cls_frames * m->cls_top_k * sizeof(mars_cls_t)) ||
-        (sums && mhip_d2h_async(sums, (uint8_t *)m->cls_dev + m->cls_sums_off, (size_t)m->cls_frames * m->cls_c * sizeof(int))) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    if (channels) *channels = m->cls_c;
-    return MARS_OK;
+    const size_t F = (size_t)m->cls.frames;
+    const mars_block_part_t parts[2] = {{top, m->cls_top_off, F * m->cls_top_k * sizeof(mars_cls_t)}, {sums, m->cls_sums_off, F * m->cls_c * sizeof(int)}};
+    const mars_error_t e = mars_block_fetch(&m->cls, parts, 2, &m->tail_pending);
+    if (e == MARS_OK && channels) *channels = m->cls_c;
+    return e;
 }
 
 mars_error_t mars_hip_classify(mars_model_t *model, const mars_hip_cls_opts_t *opts, mars_cls_t *top, int *sums) {
@@ -164,48 +142,11 @@ mars_error_t mars_hip_classify(mars_model_t *model, const mars_hip_cls_opts_t *o
 
 mars_error_t mars_hip_label_detections_device(mars_model_t *det_model, mars_model_t *cls_model) {
     if (!det_model || !cls_model) return MARS_ERR_INVALID_FILE;
-    if (det_model == cls_model) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *det = (mars_model_ext_t *)det_model, *m = (mars_model_ext_t *)cls_model;
-    if (!m->act_dev || !det->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe || det->pipe) return MARS_ERR_INVALID_TENSOR;
-    if (!m->roi_dev || m->roi_slots <= 0 || m->roi_from != det) return MARS_ERR_INVALID_TENSOR;            /* no crop call out of det_model */
-    if (!m->cls_dev || m->cls_frames <= 0 || m->cls_frames < m->roi_slots) return MARS_ERR_INVALID_TENSOR; /* no classify results */
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
-    if (!det->label_dev || det->label_cap < det->batch) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight (own_det_buffers) */
-        if (det->label_dev) mhip_free(det->label_dev);
-        det->label_cap = det->label_frames = 0;
-        det->label_dev = mhip_malloc((size_t)det->batch * MARS_YOLO_MAX_DET * sizeof(mars_cls_t));
-        if (!det->label_dev) return MARS_ERR_ALLOC_FAILED;
-        det->label_cap = det->batch;
-    }
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_label_done) m->ev_label_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_label_done) return MARS_ERR_ALLOC_FAILED;
-    /* The auxiliary stream.  It carries every detection tail and every classify tail, so the scatter comes behind both models' tails and
-     * ahead of det_model's next detect call and cls_model's next classify call.  The ROI table is written on the main stream: the scatter
-     * waits for what that stream has been given so far, and the next crop call into cls_model waits for the scatter (ev_label_done) */
-    mhip_select_stream(0);
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc)
-        rc = mhip_label_scatter((uint8_t *)m->roi_dev + 16, (const int *)m->roi_dev, m->roi_slots, (uint8_t *)m->cls_dev + m->cls_top_off, m->cls_top_k,
-                                det->label_dev, det->batch, MARS_YOLO_MAX_DET);
-    if (!rc) rc = mhip_event_record(m->ev_label_done);
-    mhip_select_aux(0);
-    if (rc) return MARS_ERR_LAYER_FAILED;
-    m->label_pending = 1;
-    det->label_frames = det->batch;
-    return MARS_OK;
+    return mars_scatter_on_aux(det, m, &m->cls, m->cls_top_off, m->cls_top_k, &det->label);
 }
 
 mars_error_t mars_hip_label_results(mars_model_t *det_model, mars_cls_t *labels) {
     if (!det_model || !labels) return MARS_ERR_INVALID_FILE;
-    mars_model_ext_t *det = (mars_model_ext_t *)det_model;
-    if (!det->label_dev || det->label_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no scatter yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    if (mhip_d2h_async(labels, det->label_dev, (size_t)det->label_frames * MARS_YOLO_MAX_DET * sizeof(mars_cls_t)) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    return MARS_OK;
+    return mars_side_fetch(&((mars_model_ext_t *)det_model)->label, labels, sizeof(mars_cls_t));
 }

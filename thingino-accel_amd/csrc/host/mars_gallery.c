@@ -139,19 +139,16 @@ int mars_hip_match_chunk(int rows) { return mhip_match_chunk(rows); }
 /* the device block of a match of n queries: fills the pointers of p from `base` (NULL: sizes only); -> bytes */
 static size_t match_block(mhip_match_t *p, uint8_t *base, size_t *top_off, size_t *row_off) {
     const size_t n = (size_t)p->queries, chunks = ((size_t)p->n_rows + p->chunk - 1) / p->chunk;
-    size_t off = 0, o_q, o_qq, o_qinv, o_part, o_top, o_row;
-    o_q = off; off += ALIGN_UP(ALIGN_UP(n, 64) * p->cp, 256);
-    o_qq = off; off += ALIGN_UP(n * sizeof(int), 256);
-    o_qinv = off; off += ALIGN_UP(n * sizeof(float), 256);
-    o_part = off; off += ALIGN_UP(n * chunks * MHIP_MATCH_KEEP * sizeof(unsigned long long), 256);
-    o_top = off; off += ALIGN_UP(n * p->top_k * sizeof(mars_cls_t), 256);
-    o_row = off; off += ALIGN_UP(n * p->top_k * sizeof(int), 256);
+    const size_t sz[6] = {ALIGN_UP(n, 64) * p->cp, n * sizeof(int), n * sizeof(float), n * chunks * MHIP_MATCH_KEEP * sizeof(unsigned long long),
+                          n * p->top_k * sizeof(mars_cls_t), n * p->top_k * sizeof(int)};
+    size_t o[6];
+    const size_t total = mars_block_layout(sz, 6, o);
     if (base) {
-        p->q = (int8_t *)(base + o_q); p->qq = (int *)(base + o_qq); p->qinv = (float *)(base + o_qinv);
-        p->part = (unsigned long long *)(base + o_part); p->top = base + o_top; p->top_row = (int *)(base + o_row);
+        p->q = (int8_t *)(base + o[0]); p->qq = (int *)(base + o[1]); p->qinv = (float *)(base + o[2]);
+        p->part = (unsigned long long *)(base + o[3]); p->top = base + o[4]; p->top_row = (int *)(base + o[5]);
     }
-    *top_off = o_top; *row_off = o_row;
-    return off;
+    *top_off = o[4]; *row_off = o[5];
+    return total;
 }
 
 static void match_gallery(mhip_match_t *p, const mars_hip_gallery_t *g) {
@@ -186,61 +183,40 @@ mars_error_t mars_yolo_match_vectors(mars_hip_gallery_t *g, const int *vectors, 
     return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
 }
 
-void mars_match_release(mars_model_ext_t *m) {
-    if (m->match_dev) mhip_free(m->match_dev);
-    if (m->ident_dev) mhip_free(m->ident_dev);
-    m->match_dev = m->ident_dev = NULL;
-    m->match_bytes = 0;
-    m->match_frames = m->match_top_k = m->ident_cap = m->ident_frames = 0;
-}
-
 mars_error_t mars_hip_match_device(mars_model_t *cls_model, mars_hip_gallery_t *g, const mars_hip_match_opts_t *opts) {
     mhip_match_t p;
     memset(&p, 0, sizeof(p));
     if (!cls_model || !g) return MARS_ERR_INVALID_FILE;
-    const mars_error_t e = match_opts(opts, &p.top_k, &p.min_score);
+    mars_error_t e = match_opts(opts, &p.top_k, &p.min_score);
     if (e != MARS_OK) return e;
     mars_model_ext_t *m = (mars_model_ext_t *)cls_model;
-    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe) return MARS_ERR_INVALID_TENSOR;
-    if (!m->cls_dev || m->cls_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no classify results */
+    if ((e = mars_stage_guard(m)) != MARS_OK) return e;
+    if (!m->cls.dev || m->cls.frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no classify results */
     if (g->channels != m->cls_c || g->count <= 0) return MARS_ERR_INVALID_TENSOR;
-    p.queries = m->cls_frames;
-    p.vec = (const int *)((uint8_t *)m->cls_dev + m->cls_sums_off);
+    p.queries = m->cls.frames;
+    p.vec = (const int *)((uint8_t *)m->cls.dev + m->cls_sums_off);
     match_gallery(&p, g);
     size_t to, ro;
-    const size_t total = match_block(&p, NULL, &to, &ro);
-    if (!m->match_dev || m->match_bytes < total) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: an earlier match or scatter may still use the old block */
-        if (m->match_dev) mhip_free(m->match_dev);
-        m->match_frames = 0; m->match_bytes = 0;
-        m->match_dev = mhip_malloc(total);
-        if (!m->match_dev) return MARS_ERR_ALLOC_FAILED;
-        m->match_bytes = total;
-    }
-    match_block(&p, (uint8_t *)m->match_dev, &to, &ro);
+    if ((e = mars_block_reserve(&m->match, match_block(&p, NULL, &to, &ro), 0, NULL)) != MARS_OK) return e;
+    match_block(&p, (uint8_t *)m->match.dev, &to, &ro);
     /* The auxiliary stream: behind the classify tail that writes the sums, behind an earlier identity scatter that reads this block, and
      * ahead of the next classify tail that overwrites the sums */
-    m->match_frames = 0;
+    m->match.frames = 0;
     mhip_select_aux(1);
     const int rc = mhip_match(&p);
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;
     m->match_top_off = to; m->match_row_off = ro;
-    m->match_frames = p.queries; m->match_top_k = p.top_k;
+    m->match.frames = p.queries; m->match_top_k = p.top_k;
     return MARS_OK;
 }
 
 mars_error_t mars_hip_match_results(mars_model_t *cls_model, mars_cls_t *top, int *rows) {
     if (!cls_model || !top) return MARS_ERR_INVALID_FILE;
     mars_model_ext_t *m = (mars_model_ext_t *)cls_model;
-    if (!m->match_dev || m->match_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no match call yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    const size_t n = (size_t)m->match_frames * m->match_top_k;
-    if (mhip_d2h_async(top, (uint8_t *)m->match_dev + m->match_top_off, n * sizeof(mars_cls_t)) ||
-        (rows && mhip_d2h_async(rows, (uint8_t *)m->match_dev + m->match_row_off, n * sizeof(int))) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    return MARS_OK;
+    const size_t n = (size_t)m->match.frames * m->match_top_k;
+    const mars_block_part_t parts[2] = {{top, m->match_top_off, n * sizeof(mars_cls_t)}, {rows, m->match_row_off, n * sizeof(int)}};
+    return mars_block_fetch(&m->match, parts, 2, NULL);
 }
 
 mars_error_t mars_hip_match(mars_model_t *cls_model, mars_hip_gallery_t *g, const mars_hip_match_opts_t *opts, mars_cls_t *top, int *rows) {
@@ -251,47 +227,11 @@ mars_error_t mars_hip_match(mars_model_t *cls_model, mars_hip_gallery_t *g, cons
 
 mars_error_t mars_hip_identify_detections_device(mars_model_t *det_model, mars_model_t *cls_model) {
     if (!det_model || !cls_model) return MARS_ERR_INVALID_FILE;
-    if (det_model == cls_model) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *det = (mars_model_ext_t *)det_model, *m = (mars_model_ext_t *)cls_model;
-    if (!m->act_dev || !det->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe || det->pipe) return MARS_ERR_INVALID_TENSOR;
-    if (!m->roi_dev || m->roi_slots <= 0 || m->roi_from != det) return MARS_ERR_INVALID_TENSOR;                /* no crop call out of det_model */
-    if (!m->match_dev || m->match_frames <= 0 || m->match_frames < m->roi_slots) return MARS_ERR_INVALID_TENSOR; /* no match results */
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR;    /* no detections in HBM */
-    if (!det->ident_dev || det->ident_cap < det->batch) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
-        if (det->ident_dev) mhip_free(det->ident_dev);
-        det->ident_cap = det->ident_frames = 0;
-        det->ident_dev = mhip_malloc((size_t)det->batch * MARS_YOLO_MAX_DET * sizeof(mars_cls_t));
-        if (!det->ident_dev) return MARS_ERR_ALLOC_FAILED;
-        det->ident_cap = det->batch;
-    }
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_label_done) m->ev_label_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_label_done) return MARS_ERR_ALLOC_FAILED;
-    /* As the label scatter (mars_classify.c): the auxiliary stream carries every tail and every match, the ROI table is written on the main
-     * stream, and the next crop call into cls_model waits for ev_label_done -- recorded again here, behind both kinds of scatter */
-    mhip_select_stream(0);
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc)
-        rc = mhip_label_scatter((uint8_t *)m->roi_dev + 16, (const int *)m->roi_dev, m->roi_slots, (uint8_t *)m->match_dev + m->match_top_off,
-                                m->match_top_k, det->ident_dev, det->batch, MARS_YOLO_MAX_DET);
-    if (!rc) rc = mhip_event_record(m->ev_label_done);
-    mhip_select_aux(0);
-    if (rc) return MARS_ERR_LAYER_FAILED;
-    m->label_pending = 1;
-    det->ident_frames = det->batch;
-    return MARS_OK;
+    return mars_scatter_on_aux(det, m, &m->match, m->match_top_off, m->match_top_k, &det->ident);
 }
 
 mars_error_t mars_hip_identity_results(mars_model_t *det_model, mars_cls_t *idents) {
     if (!det_model || !idents) return MARS_ERR_INVALID_FILE;
-    mars_model_ext_t *det = (mars_model_ext_t *)det_model;
-    if (!det->ident_dev || det->ident_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no scatter yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    if (mhip_d2h_async(idents, det->ident_dev, (size_t)det->ident_frames * MARS_YOLO_MAX_DET * sizeof(mars_cls_t)) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    return MARS_OK;
+    return mars_side_fetch(&((mars_model_ext_t *)det_model)->ident, idents, sizeof(mars_cls_t));
 }

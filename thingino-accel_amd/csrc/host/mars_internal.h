@@ -7,6 +7,7 @@
 #ifndef MARS_INTERNAL_H
 #define MARS_INTERNAL_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -122,6 +123,18 @@ typedef struct {
     void *ev_start; /* profiling: the event that marks this launch's start = the previous launch's ev1 (own ev0 for the first) */
 } mars_op_t;
 
+/* ---- tail stages (mars_stage.c): the records every stage behind the detection tail hangs on a model */
+/* one result block on the device.  frames: those of the stage's last call, 0 = there was none (cleared before the launches, set after they
+ * were enqueued); ev: timing events around the stage's launches on the auxiliary stream, created on first use where the stage has any */
+typedef struct { void *dev; size_t bytes; int frames; void *ev[2]; } mars_block_t;
+typedef struct { void *dst; size_t off, bytes; } mars_block_part_t; /* mars_block_fetch: a host destination (NULL: skipped) and the part of the block it gets */
+/* one record per detection of THIS model: [cap][MARS_YOLO_MAX_DET] x record on the device; frames == 0: nothing has filled it yet */
+typedef struct { void *dev; int cap, frames; } mars_det_side_t;
+/* where the plan left an int8 activation tensor that a convolution wrote (mars_side_tensor) */
+typedef struct { int buf; const int8_t *base; size_t stride; int c, h, w, pix_step, ch_step; } mars_side_tensor_t;
+/* the (effective) scales the tables up on the device were built from, per head; n: tables that are up (0: none) */
+typedef struct { float key[4][2]; int n; } mars_lut_cache_t;
+
 /* Every environment switch the planner and alloc_batch obey, read in ONE place (plan_switches_read, mars_model.c): a plan is a function of
  * (file, batch, f32_mfma mode, this record).  build_plan and alloc_batch refresh it when they start; `fusion` is read at load only
  * (mars_hip_set_fusion changes it afterwards). */
@@ -169,15 +182,12 @@ typedef struct mars_model_ext {
     int *det_counts_dev;
     float *det_lut_dev;
     int det_cap;
-    float det_lut_scale[4]; /* scales the uploaded decode LUTs were built for */
-    int det_lut_n;
+    mars_lut_cache_t det_lut; /* the output scales the uploaded decode LUTs were built for */
     int det_lut_mono[4];    /* value table of that segment strictly increasing (mhip_detect_t.mono) */
     float *heads_lut_dev;   /* raw-head decode: [head][256] sigmoid tables (mhip_heads_t.sig) */
-    float heads_lut_scale[4];
-    int heads_lut_n;
+    mars_lut_cache_t heads_lut;
     float *dfl_lut_dev;     /* DFL decode: [head][512] tables (mhip_dfl_heads_t.tab) */
-    float dfl_lut_scale[4][2]; /* effective (box, class) scales they were built for */
-    int dfl_lut_n;
+    mars_lut_cache_t dfl_lut; /* effective (box, class) scales they were built for */
     void *ev_graph_done, *ev_tail_done; /* main->aux and aux->main hand-offs */
     int tail_pending;
     int frame0, run_frames; /* frame range the launches being enqueued cover (a large batch runs as two halves on two streams) */
@@ -196,53 +206,42 @@ typedef struct mars_model_ext {
     int roi_slots;      /* slots of the last crop call (its batch then); 0 = there was none */
     struct mars_model_ext *roi_from; /* ... whose detections they were (compared, never followed: mars_free clears it) */
     /* second-stage labels (mars_classify.c) */
-    void *cls_dev;      /* pooled results of THIS model, one block on the device: [cls_frames][nsplit][C] partial sums, [cls_frames][C] sums, [cls_frames][top_k] entries */
-    size_t cls_bytes, cls_sums_off, cls_top_off;
-    int cls_frames, cls_c, cls_top_k; /* of the last classify call; cls_frames == 0: there was none */
+    mars_block_t cls;   /* pooled results of THIS model: [frames][nsplit][C] partial sums, [frames][C] sums, [frames][top_k] entries */
+    size_t cls_sums_off, cls_top_off;
+    int cls_c, cls_top_k; /* of the last classify call */
     void *ev_label_done; /* a label scatter (auxiliary stream) has read this model's ROI table and entries: the next crop call into it waits */
     int label_pending;
-    void *label_dev;    /* labels of THIS model's detections: [label_cap][MARS_YOLO_MAX_DET] x mars_cls_t on the device */
-    int label_cap, label_frames; /* label_frames == 0: no scatter yet */
+    mars_det_side_t label; /* labels of THIS model's detections: x mars_cls_t */
     /* gallery match (mars_gallery.c) */
-    void *match_dev;    /* match results of THIS model, one block on the device: quantised queries, qq, qinv, the chunks' lists, [match_frames][top_k] entries, their rows */
-    size_t match_bytes, match_top_off, match_row_off;
-    int match_frames, match_top_k; /* of the last match call; match_frames == 0: there was none */
-    void *ident_dev;    /* identities of THIS model's detections: [ident_cap][MARS_YOLO_MAX_DET] x mars_cls_t on the device */
-    int ident_cap, ident_frames; /* ident_frames == 0: no scatter yet */
+    mars_block_t match; /* match results of THIS model: quantised queries, qq, qinv, the chunks' lists, [frames][top_k] entries, their rows */
+    size_t match_top_off, match_row_off;
+    int match_top_k;    /* of the last match call */
+    mars_det_side_t ident; /* identities of THIS model's detections: x mars_cls_t */
     /* tracking (mars_track.c) */
-    void *track_dev;    /* track ids of THIS model's detections: [track_cap][MARS_YOLO_MAX_DET] x mars_track_t on the device */
-    int track_cap, track_frames; /* track_frames == 0: no track call yet */
+    mars_det_side_t track; /* track ids of THIS model's detections: x mars_track_t */
     /* instance masks (mars_seg.c) */
-    void *seg_dev;      /* one block on the device: candidate / kept prediction indices [frames][MARS_YOLO_MAX_DET] x int each, the kept boxes before the
-                         * letterbox mapping, [frames][seg_max] x mars_mask_t, [frames][seg_max][seg_ph][pitch] x uint32 */
-    size_t seg_bytes, seg_rec_off, seg_word_off;
-    int seg_frames, seg_max, seg_ph, seg_pw; /* of the last seg call; seg_frames == 0: there was none */
-    void *ev_seg[2];    /* timing events around the mask stage's launches on the auxiliary stream */
+    mars_block_t seg;   /* candidate / kept prediction indices [frames][MARS_YOLO_MAX_DET] x int each, the kept boxes before the letterbox mapping,
+                         * [frames][seg_max] x mars_mask_t, [frames][seg_max][seg_ph][pitch] x uint32 */
+    size_t seg_rec_off, seg_word_off;
+    int seg_max, seg_ph, seg_pw; /* of the last seg call */
     /* pose keypoints (mars_pose.c) */
-    void *pose_dev;     /* one block on the device: the visibility tables [4][256] x float, candidate / kept prediction indices
-                         * [frames][MARS_YOLO_MAX_DET] x int each, [frames][pose_max] x mars_pose_t, [frames][pose_max][pose_k] x mars_kpt_t */
-    size_t pose_bytes, pose_rec_off, pose_kpt_off;
-    int pose_frames, pose_max, pose_k; /* of the last pose call; pose_frames == 0: there was none */
-    float pose_lut_scale[4];           /* the scales the block's visibility tables were built from */
-    int pose_lut_n;                    /* tables that are up (0: none) */
-    void *ev_pose[2];   /* timing events around the keypoint stage's launches on the auxiliary stream */
+    mars_block_t pose;  /* the visibility tables [4][256] x float, candidate / kept prediction indices [frames][MARS_YOLO_MAX_DET] x int each,
+                         * [frames][pose_max] x mars_pose_t, [frames][pose_max][pose_k] x mars_kpt_t */
+    size_t pose_rec_off, pose_kpt_off;
+    int pose_max, pose_k; /* of the last pose call */
+    mars_lut_cache_t pose_lut; /* the block's visibility tables */
     /* oriented boxes (mars_obb.c) */
-    void *obb_dev;      /* one block on the device: the angle tables [4][768] x float, kept and candidate counts [frames] x int each, candidate
-                         * records [frames][MARS_YOLO_MAX_DET] x mars_obb_t, their (cos, sin) pairs, kept records [frames][MARS_YOLO_MAX_DET] x mars_obb_t,
+    mars_block_t obb;   /* the angle tables [4][768] x float, kept and candidate counts [frames] x int each, candidate records
+                         * [frames][MARS_YOLO_MAX_DET] x mars_obb_t, their (cos, sin) pairs, kept records [frames][MARS_YOLO_MAX_DET] x mars_obb_t,
                          * the kept records' (cos, sin) pairs (mars_roi.c cuts rotated crops along them) */
-    size_t obb_bytes, obb_cnt_off, obb_out_off, obb_csn_off;
-    int obb_frames;                   /* of the last obb call; 0: there was none */
-    float obb_lut_scale[4];           /* the scales the block's angle tables were built from */
-    int obb_lut_n;                    /* tables that are up (0: none) */
-    void *ev_obb[2];    /* timing events around the oriented stage's launches on the auxiliary stream */
+    size_t obb_cnt_off, obb_out_off, obb_csn_off;
+    mars_lut_cache_t obb_lut; /* the block's angle tables */
     /* tiled inference (mars_tile.c) */
     int det_mapped;     /* the last detection tail of THIS model mapped its lists into source-frame pixels (src_w > 0): the tile merge refuses them */
-    void *tile_roi_dev; /* tiles INTO this model: [slots, 0, ...] in 256 bytes, then [tile_roi_cap] x mars_roi_t, on the device */
-    int tile_roi_cap;
-    void *tile_dev;     /* merged lists of THIS model's detections, one block on the device: [tile_cap][MARS_YOLO_MAX_DET] x mars_det_t, the same of
-                         * mars_tile_src_t, [tile_cap] x int, [tile_cap] x mars_tile_stats_t */
-    int tile_cap, tile_cams; /* tile_cams == 0: no merge yet */
-    void *ev_tile[2];   /* timing events around the merge launch on the auxiliary stream */
+    mars_block_t tile_roi; /* tiles INTO this model: [slots, 0, ...] in 256 bytes, then [batch] x mars_roi_t */
+    mars_block_t tile;  /* merged lists of THIS model's detections: [frames][MARS_YOLO_MAX_DET] x mars_det_t, the same of mars_tile_src_t,
+                         * [frames] x int, [frames] x mars_tile_stats_t; frames = camera frames of the last merge */
+    size_t tile_off[4];
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -312,26 +311,33 @@ MARS_INTERNAL int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int fr
 /* mars_roi.c */
 MARS_INTERNAL void mars_roi_release(mars_model_ext_t *m); /* the ROI table of a model whose device state goes away */
 
-/* mars_classify.c */
-MARS_INTERNAL void mars_cls_release(mars_model_ext_t *m); /* the pooled results and labels of a model whose device state goes away */
-
-/* mars_gallery.c */
-MARS_INTERNAL void mars_match_release(mars_model_ext_t *m); /* the match results and identities of a model whose device state goes away (mars_cls_release calls it) */
-
-/* mars_track.c */
-MARS_INTERNAL void mars_track_release(mars_model_ext_t *m); /* the track results of a model whose device state goes away */
-
-/* mars_seg.c */
-MARS_INTERNAL void mars_seg_release(mars_model_ext_t *m); /* the mask results of a model whose device state goes away */
-
-/* mars_pose.c */
-MARS_INTERNAL void mars_pose_release(mars_model_ext_t *m); /* the keypoint results of a model whose device state goes away */
-
-/* mars_obb.c */
-MARS_INTERNAL void mars_obb_release(mars_model_ext_t *m); /* the oriented results of a model whose device state goes away */
-
-/* mars_tile.c */
-MARS_INTERNAL void mars_tile_release(mars_model_ext_t *m); /* the tile table and merged lists of a model whose device state goes away */
+/* mars_stage.c: tail stages.  A new stage's host side starts from a mars_block_t, mars_side_tensor and mars_tail_on_aux */
+static inline int mars_scale_ok(float s) { return s > 0 && isfinite(s); }
+/* the device is up and no pipe is open (a pipe's slots own their buffers) */
+static inline mars_error_t mars_stage_guard(const mars_model_ext_t *m) {
+    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
+    return m->pipe ? MARS_ERR_INVALID_TENSOR : MARS_OK;
+}
+MARS_INTERNAL size_t mars_block_layout(const size_t *sz, int n, size_t *off); /* parts of sz[i] bytes, each aligned to 256: their offsets -> the total */
+/* the block holds `total` bytes (grown: synchronises, *fresh = 1, what it held is gone) and, with_events, its two events exist */
+MARS_INTERNAL mars_error_t mars_block_reserve(mars_block_t *b, size_t total, int with_events, int *fresh);
+MARS_INTERNAL void mars_block_release(mars_block_t *b);
+MARS_INTERNAL float mars_block_ms(const mars_block_t *b); /* device time between the two events; -1: no call yet, or no events */
+/* synchronise, (tail_pending != NULL: clear it,) copy every part with a destination, synchronise; INVALID_TENSOR before the stage's first call */
+MARS_INTERNAL mars_error_t mars_block_fetch(const mars_block_t *b, const mars_block_part_t *parts, int n, int *tail_pending);
+MARS_INTERNAL mars_error_t mars_side_reserve(mars_det_side_t *s, int frames, size_t rec);
+MARS_INTERNAL void mars_side_release(mars_det_side_t *s);
+MARS_INTERNAL mars_error_t mars_side_fetch(const mars_det_side_t *s, void *dst, size_t rec);
+/* the entries [slot][top_k] at src + top_off of second-stage model m go through m's ROI table onto det's detections, into `side` of det */
+MARS_INTERNAL mars_error_t mars_scatter_on_aux(mars_model_ext_t *det, mars_model_ext_t *m, const mars_block_t *src, size_t top_off, int top_k,
+                                               mars_det_side_t *side);
+/* int8 activation tensor T of want_c channels on a want_h x want_w grid (0: any) whose bytes the plan keeps: where they are, and that every
+ * byte a kernel may touch lies inside the frame's stride */
+MARS_INTERNAL mars_error_t mars_side_tensor(const mars_model_ext_t *m, int T, int want_c, int want_h, int want_w, mars_side_tensor_t *out);
+MARS_INTERNAL int mars_lut_stale(const mars_lut_cache_t *c, int n, const float key[4][2]);
+/* tables of n heads built for `key` go up to dst (nothing where they are up already): synchronises around the upload; c->n == 0 if it fails */
+MARS_INTERNAL mars_error_t mars_lut_refresh(mars_lut_cache_t *c, void *dst, int n, const float key[4][2], const float *tab, size_t floats_per_head);
+MARS_INTERNAL void mars_stages_release(mars_model_ext_t *m); /* every record above and the ROI table, of a model whose device state goes away */
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

@@ -97,13 +97,7 @@ static void free_device_state(mars_model_ext_t *m) {
     m->det_counts_dev = NULL;
     m->det_cap = 0;
     m->tail_pending = 0;
-    mars_roi_release(m);
-    mars_cls_release(m);
-    mars_track_release(m);
-    mars_seg_release(m);
-    mars_pose_release(m);
-    mars_obb_release(m);
-    mars_tile_release(m);
+    mars_stages_release(m);
 }
 
 static void free_ops(mars_model_ext_t *m) {

@@ -18,39 +18,8 @@
 typedef struct {
     mars_dfl_cfg_t dfl;
     mhip_obb_t obb;
-    void *ev[2];
+    void *const *ev; /* the block's two timing events */
 } obb_call_t;
-
-void mars_obb_release(mars_model_ext_t *m) {
-    if (m->obb_dev) mhip_free(m->obb_dev);
-    m->obb_dev = NULL;
-    m->obb_bytes = 0;
-    m->obb_frames = m->obb_lut_n = 0;
-    for (int i = 0; i < 2; i++) {
-        if (m->ev_obb[i]) mhip_event_destroy(m->ev_obb[i]);
-        m->ev_obb[i] = NULL;
-    }
-}
-
-/* an int8 activation tensor of exactly 1 channel on a want_h x want_w grid whose bytes the plan keeps: where they are, and that every byte
- * the kernel may touch lies inside the frame's stride */
-static mars_error_t angle_tensor(const mars_model_ext_t *m, int T, int want_h, int want_w, int *buf, const int8_t **base, size_t *stride, int *pix_step) {
-    if (T < 0 || (uint32_t)T >= m->pub.header.num_tensors) return MARS_ERR_INVALID_TENSOR;
-    const mars_tensor_t *d = &m->pub.tensors[T].desc;
-    int c, h, w, off, ch_step;
-    if (d->dtype != MARS_DTYPE_INT8 || m->mt[T].is_weight || mars_tensor_chw(d, &c, &h, &w)) return MARS_ERR_INVALID_TENSOR;
-    if (c != 1 || h != want_h || w != want_w) return MARS_ERR_INVALID_TENSOR;
-    if (mars_locate_i8(m, T, c, h, w, 0, buf, &off, pix_step, &ch_step)) return MARS_ERR_INVALID_TENSOR;
-    const mtensor_t *tb = &m->mt[*buf];
-    if (!tb->dev || *pix_step <= 0) return MARS_ERR_INVALID_TENSOR;
-    const size_t last = (size_t)off + ((size_t)h * w - 1) * (size_t)*pix_step;
-    if (last >= tb->stride) return MARS_ERR_INVALID_TENSOR;
-    *base = (const int8_t *)tb->dev + off;
-    *stride = tb->stride;
-    return MARS_OK;
-}
-
-static int scale_ok(float s) { return s > 0 && isfinite(s); }
 
 /* ang, cs, sn of every byte under scale s: the sigmoid is the DFL class confidence's expression (mars_yolo.c) */
 static void angle_table(float s, float *tab) {
@@ -88,21 +57,24 @@ static int obb_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, i
 mars_error_t mars_hip_detect_obb_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_obb_opts_t *s) {
     if (!model || !s) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe) return MARS_ERR_INVALID_TENSOR; /* a pipe's slots own their buffers */
+    mars_error_t e = mars_stage_guard(m);
+    if (e != MARS_OK) return e;
     if ((s->flags & ~MARS_OBB_AGNOSTIC) || m->batch > 65535) return MARS_ERR_INVALID_TENSOR;
     obb_call_t c;
     memset(&c, 0, sizeof(c));
     mhip_obb_t *p = &c.obb;
-    mars_error_t e = mars_dfl_resolve(m, heads, &c.dfl);
+    e = mars_dfl_resolve(m, heads, &c.dfl);
     if (e != MARS_OK) return e;
     int bufs[4];
-    float scales[4] = {0, 0, 0, 0};
+    float scales[4][2] = {{0}};
     for (int k = 0; k < c.dfl.n; k++) {
-        e = angle_tensor(m, s->angle_tensors[k], c.dfl.h[k], c.dfl.w[k], &bufs[k], &p->ang[k], &p->ang_frame_stride[k], &p->ang_pix_step[k]);
+        mars_side_tensor_t t; /* exactly 1 channel: no channel step is taken */
+        e = mars_side_tensor(m, s->angle_tensors[k], 1, c.dfl.h[k], c.dfl.w[k], &t);
         if (e != MARS_OK) return e;
-        scales[k] = s->angle_scales[k] != 0 ? s->angle_scales[k] : model->tensors[s->angle_tensors[k]].desc.scale;
-        if (!scale_ok(scales[k])) return MARS_ERR_INVALID_TENSOR;
+        bufs[k] = t.buf;
+        p->ang[k] = t.base; p->ang_frame_stride[k] = t.stride; p->ang_pix_step[k] = t.pix_step;
+        scales[k][0] = s->angle_scales[k] != 0 ? s->angle_scales[k] : model->tensors[s->angle_tensors[k]].desc.scale;
+        if (!mars_scale_ok(scales[k][0])) return MARS_ERR_INVALID_TENSOR;
         p->h[k] = c.dfl.h[k]; p->w[k] = c.dfl.w[k]; p->nc[k] = c.dfl.nc[k];
         p->box_pix_step[k] = c.dfl.box_pix_step[k]; p->box_ch_step[k] = c.dfl.box_ch_step[k];
         p->cls_pix_step[k] = c.dfl.cls_pix_step[k]; p->cls_ch_step[k] = c.dfl.cls_ch_step[k];
@@ -118,69 +90,49 @@ mars_error_t mars_hip_detect_obb_device(mars_model_t *model, const mars_yolo_dfl
     e = mars_own_det_buffers(m);
     if (e == MARS_OK) e = mars_dfl_prepare(m, &c.dfl);
     if (e != MARS_OK) return e;
-    /* the block: angle tables (at its start: their place does not move with the batch), the kept counts, candidate records, their (cos, sin)
-     * pairs, kept records, the kept records' (cos, sin) pairs */
-    const size_t B = (size_t)m->batch, rec_b = ALIGN_UP(B * MARS_YOLO_MAX_DET * sizeof(mars_obb_t), 256);
-    const size_t cnt_off = OBB_TAB, cand_off = cnt_off + ALIGN_UP(2 * B * sizeof(int), 256), csn_off = cand_off + rec_b;
-    const size_t csn_b = ALIGN_UP(B * MARS_YOLO_MAX_DET * 2 * sizeof(float), 256);
-    const size_t out_off = csn_off + csn_b, kcsn_off = out_off + rec_b, total = kcsn_off + csn_b; /* ... and the kept boxes' (cos, sin) pairs */
-    if (!m->obb_dev || m->obb_bytes < total) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: an earlier tail may still use the old block */
-        if (m->obb_dev) mhip_free(m->obb_dev);
-        m->obb_frames = 0; m->obb_bytes = 0; m->obb_lut_n = 0;
-        m->obb_dev = mhip_malloc(total);
-        if (!m->obb_dev) return MARS_ERR_ALLOC_FAILED;
-        m->obb_bytes = total;
-    }
-    for (int i = 0; i < 2; i++) {
-        if (!m->ev_obb[i]) m->ev_obb[i] = mhip_event_create();
-        if (!m->ev_obb[i]) return MARS_ERR_ALLOC_FAILED;
-        c.ev[i] = m->ev_obb[i];
-    }
-    uint8_t *blk = (uint8_t *)m->obb_dev;
+    /* the block: angle tables (at its start: their place does not move with the batch), the kept and candidate counts, candidate records,
+     * their (cos, sin) pairs, kept records, the kept records' (cos, sin) pairs */
+    const size_t B = (size_t)m->batch, rec_b = B * MARS_YOLO_MAX_DET * sizeof(mars_obb_t), csn_b = B * MARS_YOLO_MAX_DET * 2 * sizeof(float);
+    const size_t sz[6] = {OBB_TAB, 2 * B * sizeof(int), rec_b, csn_b, rec_b, csn_b};
+    size_t off[6];
+    int fresh;
+    e = mars_block_reserve(&m->obb, mars_block_layout(sz, 6, off), 1, &fresh);
+    if (fresh) m->obb_lut.n = 0;
+    if (e != MARS_OK) return e;
+    c.ev = m->obb.ev;
+    uint8_t *blk = (uint8_t *)m->obb.dev;
     /* the tables depend only on the effective scales: built and uploaded once; synchronises when they change (mars_dfl_prepare's way) */
-    int stale = m->obb_lut_n != c.dfl.n;
-    for (int k = 0; k < c.dfl.n; k++)
-        if (memcmp(&m->obb_lut_scale[k], &scales[k], sizeof(float)) != 0) stale = 1;
-    if (stale) {
+    if (mars_lut_stale(&m->obb_lut, c.dfl.n, scales)) {
         float tab[4 * 768];
-        for (int k = 0; k < c.dfl.n; k++) angle_table(scales[k], tab + k * 768);
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
-        m->obb_lut_n = 0; /* (until the new tables are up) */
-        m->obb_frames = 0;
-        if (mhip_h2d_async(blk, tab, (size_t)c.dfl.n * 768 * sizeof(float)) || mhip_sync()) return MARS_ERR_LAYER_FAILED; /* `tab` is on this stack frame */
-        memcpy(m->obb_lut_scale, scales, sizeof(scales));
-        m->obb_lut_n = c.dfl.n;
+        for (int k = 0; k < c.dfl.n; k++) angle_table(scales[k][0], tab + k * 768);
+        m->obb.frames = 0;
+        e = mars_lut_refresh(&m->obb_lut, blk, c.dfl.n, scales, tab, 768); /* `tab` is on this stack frame */
+        if (e != MARS_OK) return e;
     }
     p->atab = (const float *)blk;
-    p->out_counts = (int *)(blk + cnt_off);
+    p->out_counts = (int *)(blk + off[1]);
     p->cand_counts = p->out_counts + B;
-    p->cand = blk + cand_off;
-    p->csn = (float *)(blk + csn_off);
-    p->out = blk + out_off;
-    p->csn_out = (float *)(blk + kcsn_off);
+    p->cand = blk + off[2];
+    p->csn = (float *)(blk + off[3]);
+    p->out = blk + off[4];
+    p->csn_out = (float *)(blk + off[5]);
     /* behind the graph's event on the auxiliary stream; the next run's layers that write one of these buffers wait for it (tail_read) */
     for (int k = 0; k < c.dfl.n; k++) m->mt[c.dfl.box_buf[k]].tail_read = m->mt[c.dfl.cls_buf[k]].tail_read = m->mt[bufs[k]].tail_read = 1;
-    m->obb_frames = 0;
+    m->obb.frames = 0;
     e = mars_tail_on_aux(m, obb_launch_cb, &c);
     if (e != MARS_OK) return e;
     m->det_mapped = c.dfl.map;
-    m->obb_cnt_off = cnt_off; m->obb_out_off = out_off; m->obb_csn_off = kcsn_off;
-    m->obb_frames = m->batch;
+    m->obb_cnt_off = off[1]; m->obb_out_off = off[4]; m->obb_csn_off = off[5];
+    m->obb.frames = m->batch;
     return MARS_OK;
 }
 
 mars_error_t mars_hip_obb_results(mars_model_t *model, mars_obb_t *boxes, int *counts) {
     if (!model) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->obb_dev || m->obb_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no obb call yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    m->tail_pending = 0;
-    const size_t F = (size_t)m->obb_frames;
-    if ((boxes && mhip_d2h_async(boxes, (uint8_t *)m->obb_dev + m->obb_out_off, F * MARS_YOLO_MAX_DET * sizeof(mars_obb_t))) ||
-        (counts && mhip_d2h_async(counts, (uint8_t *)m->obb_dev + m->obb_cnt_off, F * sizeof(int))) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    return MARS_OK;
+    const size_t F = (size_t)m->obb.frames;
+    const mars_block_part_t parts[2] = {{boxes, m->obb_out_off, F * MARS_YOLO_MAX_DET * sizeof(mars_obb_t)}, {counts, m->obb_cnt_off, F * sizeof(int)}};
+    return mars_block_fetch(&m->obb, parts, 2, &m->tail_pending);
 }
 
 mars_error_t mars_hip_detect_obb(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_obb_opts_t *s, mars_det_t *dets, int *counts,
@@ -191,11 +143,7 @@ mars_error_t mars_hip_detect_obb(mars_model_t *model, const mars_yolo_dfl_heads_
     return e != MARS_OK ? e : mars_hip_obb_results(model, boxes, NULL);
 }
 
-float mars_hip_obb_ms(mars_model_t *model) {
-    mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m || !m->obb_dev || m->obb_frames <= 0 || !m->ev_obb[0] || !m->ev_obb[1]) return -1.0f;
-    return mhip_event_elapsed_ms(m->ev_obb[0], m->ev_obb[1]);
-}
+float mars_hip_obb_ms(mars_model_t *model) { return model ? mars_block_ms(&((mars_model_ext_t *)model)->obb) : -1.0f; }
 
 int mars_yolo_obb_nms(mars_obb_t *boxes, int n, float thresh, unsigned flags) {
     if (n < 0 || n > MARS_YOLO_MAX_DET || (flags & ~MARS_OBB_AGNOSTIC) || !(thresh >= 0) || !isfinite(thresh)) return -1;
@@ -204,9 +152,10 @@ int mars_yolo_obb_nms(mars_obb_t *boxes, int n, float thresh, unsigned flags) {
     for (int i = 0; i < n; i++)
         if (!(boxes[i].conf >= 0) || signbit(boxes[i].conf)) return -1; /* NaN or negative (-0 too): the bit pattern would not order it */
     if (!nna_is_ready() && nna_init() != NNA_SUCCESS) return -1;
-    const size_t rec_b = ALIGN_UP((size_t)n * sizeof(mars_obb_t), 256), csn_b = ALIGN_UP((size_t)n * 2 * sizeof(float), 256);
-    const size_t o_csn = rec_b, o_out = o_csn + csn_b, o_cnt = o_out + rec_b;
-    uint8_t *d = (uint8_t *)mhip_malloc(o_cnt + 256);
+    /* one scratch block: [candidates][their (cos, sin) pairs][kept][kept count, candidate count] */
+    const size_t sz[4] = {(size_t)n * sizeof(mars_obb_t), (size_t)n * 2 * sizeof(float), (size_t)n * sizeof(mars_obb_t), 2 * sizeof(int)};
+    size_t off[4];
+    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 4, off));
     if (!d) return -1;
     float csn[2 * MARS_YOLO_MAX_DET];
     for (int i = 0; i < n; i++) {
@@ -218,11 +167,11 @@ int mars_yolo_obb_nms(mars_obb_t *boxes, int n, float thresh, unsigned flags) {
     p.frames = 1;
     p.e_thresh = e_of(thresh != 0 ? thresh : 0.45f);
     p.agnostic = (flags & MARS_OBB_AGNOSTIC) != 0;
-    p.cand = d; p.csn = (float *)(d + o_csn); p.out = d + o_out;
-    p.out_counts = (int *)(d + o_cnt); p.cand_counts = p.out_counts + 1;
+    p.cand = d; p.csn = (float *)(d + off[1]); p.out = d + off[2];
+    p.out_counts = (int *)(d + off[3]); p.cand_counts = p.out_counts + 1;
     int kept = -1;
-    int rc = mhip_h2d_async(p.cand, boxes, (size_t)n * sizeof(mars_obb_t));
-    if (!rc) rc = mhip_h2d_async(p.csn, csn, (size_t)n * 2 * sizeof(float));
+    int rc = mhip_h2d_async(p.cand, boxes, sz[0]);
+    if (!rc) rc = mhip_h2d_async(p.csn, csn, sz[1]);
     if (!rc) rc = mhip_h2d_async(p.cand_counts, &n, sizeof(int));
     if (!rc) rc = mhip_obb_nms(&p);
     if (!rc) rc = mhip_d2h_async(&kept, p.out_counts, sizeof(int));

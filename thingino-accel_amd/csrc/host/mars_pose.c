@@ -16,40 +16,8 @@
 typedef struct {
     mars_dfl_cfg_t dfl;
     mhip_pose_t pose;
-    void *ev[2];
+    void *const *ev; /* the block's two timing events */
 } pose_call_t;
-
-void mars_pose_release(mars_model_ext_t *m) {
-    if (m->pose_dev) mhip_free(m->pose_dev);
-    m->pose_dev = NULL;
-    m->pose_bytes = 0;
-    m->pose_frames = m->pose_max = m->pose_k = m->pose_lut_n = 0;
-    for (int i = 0; i < 2; i++) {
-        if (m->ev_pose[i]) mhip_event_destroy(m->ev_pose[i]);
-        m->ev_pose[i] = NULL;
-    }
-}
-
-/* an int8 activation tensor of `want_c` channels on a want_h x want_w grid whose bytes the plan keeps: where they are, and that every byte
- * the kernel may touch lies inside the frame's stride */
-static mars_error_t kpt_tensor(const mars_model_ext_t *m, int T, int want_c, int want_h, int want_w, int *buf, const int8_t **base, size_t *stride,
-                               int *pix_step, int *ch_step) {
-    if (T < 0 || (uint32_t)T >= m->pub.header.num_tensors) return MARS_ERR_INVALID_TENSOR;
-    const mars_tensor_t *d = &m->pub.tensors[T].desc;
-    int c, h, w, off;
-    if (d->dtype != MARS_DTYPE_INT8 || m->mt[T].is_weight || mars_tensor_chw(d, &c, &h, &w)) return MARS_ERR_INVALID_TENSOR;
-    if (c != want_c || h != want_h || w != want_w) return MARS_ERR_INVALID_TENSOR;
-    if (mars_locate_i8(m, T, c, h, w, 0, buf, &off, pix_step, ch_step)) return MARS_ERR_INVALID_TENSOR;
-    const mtensor_t *tb = &m->mt[*buf];
-    if (!tb->dev || *pix_step <= 0 || *ch_step <= 0) return MARS_ERR_INVALID_TENSOR;
-    const size_t last = (size_t)off + ((size_t)h * w - 1) * (size_t)*pix_step + (size_t)(c - 1) * (size_t)*ch_step;
-    if (last >= tb->stride) return MARS_ERR_INVALID_TENSOR;
-    *base = (const int8_t *)tb->dev + off;
-    *stride = tb->stride;
-    return MARS_OK;
-}
-
-static int scale_ok(float s) { return s > 0 && isfinite(s); }
 
 /* the visibility of every byte under scale s: the DFL class confidence's expression (mars_yolo.c), the host's expf */
 static void vis_table(float s, float *tab) {
@@ -72,8 +40,8 @@ static int pose_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, 
 mars_error_t mars_hip_detect_pose_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_pose_opts_t *s) {
     if (!model || !s) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe) return MARS_ERR_INVALID_TENSOR; /* a pipe's slots own their buffers */
+    mars_error_t e = mars_stage_guard(m);
+    if (e != MARS_OK) return e;
     pose_call_t c;
     memset(&c, 0, sizeof(c));
     mhip_pose_t *p = &c.pose;
@@ -81,17 +49,19 @@ mars_error_t mars_hip_detect_pose_device(mars_model_t *model, const mars_yolo_df
     if (s->max_per_frame < 0 || s->max_per_frame > MARS_POSE_MAX_PER_FRAME || !isfinite(s->min_conf) || K < 1 || K > MARS_POSE_MAX_KPT ||
         (D != 2 && D != 3) || m->batch > 65535)
         return MARS_ERR_INVALID_TENSOR;
-    mars_error_t e = mars_dfl_resolve(m, heads, &c.dfl);
+    e = mars_dfl_resolve(m, heads, &c.dfl);
     if (e != MARS_OK) return e;
     int bufs[4];
-    float scales[4] = {0, 0, 0, 0};
+    float scales[4][2] = {{0}};
     for (int k = 0; k < c.dfl.n; k++) {
-        e = kpt_tensor(m, s->kpt_tensors[k], K * D, c.dfl.h[k], c.dfl.w[k], &bufs[k], &p->kpt[k], &p->kpt_frame_stride[k], &p->kpt_pix_step[k],
-                       &p->kpt_ch_step[k]);
+        mars_side_tensor_t t;
+        e = mars_side_tensor(m, s->kpt_tensors[k], K * D, c.dfl.h[k], c.dfl.w[k], &t);
         if (e != MARS_OK) return e;
-        scales[k] = s->kpt_scales[k] != 0 ? s->kpt_scales[k] : model->tensors[s->kpt_tensors[k]].desc.scale;
-        if (!scale_ok(scales[k])) return MARS_ERR_INVALID_TENSOR;
-        p->scale[k] = scales[k];
+        bufs[k] = t.buf;
+        p->kpt[k] = t.base; p->kpt_frame_stride[k] = t.stride; p->kpt_pix_step[k] = t.pix_step; p->kpt_ch_step[k] = t.ch_step;
+        scales[k][0] = s->kpt_scales[k] != 0 ? s->kpt_scales[k] : model->tensors[s->kpt_tensors[k]].desc.scale;
+        if (!mars_scale_ok(scales[k][0])) return MARS_ERR_INVALID_TENSOR;
+        p->scale[k] = scales[k][0];
         p->cells[k] = c.dfl.h[k] * c.dfl.w[k];
         p->w[k] = c.dfl.w[k];
         p->stride[k] = c.dfl.stride[k];
@@ -110,68 +80,48 @@ mars_error_t mars_hip_detect_pose_device(mars_model_t *model, const mars_yolo_df
     /* the block: visibility tables (at its start: their place does not move with the batch), candidate origins, kept origins, records,
      * keypoints */
     const size_t B = (size_t)m->batch;
-    const size_t tab_off = 0, cand_off = 4 * 256 * sizeof(float), kept_off = cand_off + ALIGN_UP(B * MARS_YOLO_MAX_DET * sizeof(int), 256);
-    const size_t rec_off = kept_off + ALIGN_UP(B * MARS_YOLO_MAX_DET * sizeof(int), 256);
-    const size_t kpt_off = rec_off + ALIGN_UP(B * p->max_per_frame * sizeof(mars_pose_t), 256);
-    const size_t total = kpt_off + ALIGN_UP(B * p->max_per_frame * K * sizeof(mars_kpt_t), 256);
-    if (!m->pose_dev || m->pose_bytes < total) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: an earlier tail may still use the old block */
-        if (m->pose_dev) mhip_free(m->pose_dev);
-        m->pose_frames = 0; m->pose_bytes = 0; m->pose_lut_n = 0;
-        m->pose_dev = mhip_malloc(total);
-        if (!m->pose_dev) return MARS_ERR_ALLOC_FAILED;
-        m->pose_bytes = total;
-    }
-    for (int i = 0; i < 2; i++) {
-        if (!m->ev_pose[i]) m->ev_pose[i] = mhip_event_create();
-        if (!m->ev_pose[i]) return MARS_ERR_ALLOC_FAILED;
-        c.ev[i] = m->ev_pose[i];
-    }
-    uint8_t *blk = (uint8_t *)m->pose_dev;
+    const size_t sz[5] = {4 * 256 * sizeof(float), B * MARS_YOLO_MAX_DET * sizeof(int), B * MARS_YOLO_MAX_DET * sizeof(int),
+                          B * p->max_per_frame * sizeof(mars_pose_t), B * p->max_per_frame * K * sizeof(mars_kpt_t)};
+    size_t off[5];
+    int fresh;
+    e = mars_block_reserve(&m->pose, mars_block_layout(sz, 5, off), 1, &fresh);
+    if (fresh) m->pose_lut.n = 0;
+    if (e != MARS_OK) return e;
+    c.ev = m->pose.ev;
+    uint8_t *blk = (uint8_t *)m->pose.dev;
     /* the tables depend only on the effective scales: built and uploaded once; synchronises when they change (mars_dfl_prepare's way) */
-    int stale = m->pose_lut_n != c.dfl.n;
-    for (int k = 0; k < c.dfl.n; k++)
-        if (memcmp(&m->pose_lut_scale[k], &scales[k], sizeof(float)) != 0) stale = 1;
-    if (stale) {
+    if (mars_lut_stale(&m->pose_lut, c.dfl.n, scales)) {
         float tab[4 * 256];
-        for (int k = 0; k < c.dfl.n; k++) vis_table(scales[k], tab + k * 256);
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
-        m->pose_lut_n = 0; /* (until the new tables are up) */
-        m->pose_frames = 0;
-        if (mhip_h2d_async(blk + tab_off, tab, (size_t)c.dfl.n * 256 * sizeof(float)) || mhip_sync())
-            return MARS_ERR_LAYER_FAILED; /* `tab` is on this stack frame */
-        memcpy(m->pose_lut_scale, scales, sizeof(scales));
-        m->pose_lut_n = c.dfl.n;
+        for (int k = 0; k < c.dfl.n; k++) vis_table(scales[k][0], tab + k * 256);
+        m->pose.frames = 0;
+        e = mars_lut_refresh(&m->pose_lut, blk, c.dfl.n, scales, tab, 256); /* `tab` is on this stack frame */
+        if (e != MARS_OK) return e;
     }
-    c.dfl.cand_pred = (int *)(blk + cand_off);
-    c.dfl.kept_pred = (int *)(blk + kept_off);
+    c.dfl.cand_pred = (int *)(blk + off[1]);
+    c.dfl.kept_pred = (int *)(blk + off[2]);
     p->pred = c.dfl.kept_pred;
-    p->vis = (const float *)(blk + tab_off);
-    p->recs = blk + rec_off;
-    p->kpts = blk + kpt_off;
+    p->vis = (const float *)blk;
+    p->recs = blk + off[3];
+    p->kpts = blk + off[4];
     /* behind the graph's event on the auxiliary stream; the next run's layers that write one of these buffers wait for it (tail_read) */
     for (int k = 0; k < c.dfl.n; k++) m->mt[c.dfl.box_buf[k]].tail_read = m->mt[c.dfl.cls_buf[k]].tail_read = m->mt[bufs[k]].tail_read = 1;
-    m->pose_frames = 0;
+    m->pose.frames = 0;
     e = mars_tail_on_aux(m, pose_launch_cb, &c);
     if (e != MARS_OK) return e;
     m->det_mapped = c.dfl.map;
-    m->pose_rec_off = rec_off; m->pose_kpt_off = kpt_off;
-    m->pose_frames = m->batch; m->pose_max = p->max_per_frame; m->pose_k = K;
+    m->pose_rec_off = off[3]; m->pose_kpt_off = off[4];
+    m->pose.frames = m->batch; m->pose_max = p->max_per_frame; m->pose_k = K;
     return MARS_OK;
 }
 
 mars_error_t mars_hip_pose_results(mars_model_t *model, mars_pose_t *recs, mars_kpt_t *kpts, int *num_kpt) {
     if (!model) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->pose_dev || m->pose_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no pose call yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    m->tail_pending = 0;
-    const size_t slots = (size_t)m->pose_frames * m->pose_max;
-    if ((recs && mhip_d2h_async(recs, (uint8_t *)m->pose_dev + m->pose_rec_off, slots * sizeof(mars_pose_t))) ||
-        (kpts && mhip_d2h_async(kpts, (uint8_t *)m->pose_dev + m->pose_kpt_off, slots * m->pose_k * sizeof(mars_kpt_t))) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    if (num_kpt) *num_kpt = m->pose_k;
-    return MARS_OK;
+    const size_t slots = (size_t)m->pose.frames * m->pose_max;
+    const mars_block_part_t parts[2] = {{recs, m->pose_rec_off, slots * sizeof(mars_pose_t)}, {kpts, m->pose_kpt_off, slots * m->pose_k * sizeof(mars_kpt_t)}};
+    const mars_error_t e = mars_block_fetch(&m->pose, parts, 2, &m->tail_pending);
+    if (e == MARS_OK && num_kpt) *num_kpt = m->pose_k;
+    return e;
 }
 
 mars_error_t mars_hip_detect_pose(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_pose_opts_t *s, mars_det_t *dets, int *counts,
@@ -182,21 +132,18 @@ mars_error_t mars_hip_detect_pose(mars_model_t *model, const mars_yolo_dfl_heads
     return e != MARS_OK ? e : mars_hip_pose_results(model, recs, kpts, NULL);
 }
 
-float mars_hip_pose_ms(mars_model_t *model) {
-    mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m || !m->pose_dev || m->pose_frames <= 0 || !m->ev_pose[0] || !m->ev_pose[1]) return -1.0f;
-    return mhip_event_elapsed_ms(m->ev_pose[0], m->ev_pose[1]);
-}
+float mars_hip_pose_ms(mars_model_t *model) { return model ? mars_block_ms(&((mars_model_ext_t *)model)->pose) : -1.0f; }
 
 int mars_yolo_keypoints(const int8_t *rows, int n, int K, int D, const int *gx, const int *gy, const int *stride, float s, mars_kpt_t *kpts) {
-    if (n < 0 || n > MARS_POSE_MAX_PER_FRAME || K < 1 || K > MARS_POSE_MAX_KPT || (D != 2 && D != 3) || !scale_ok(s)) return -1;
+    if (n < 0 || n > MARS_POSE_MAX_PER_FRAME || K < 1 || K > MARS_POSE_MAX_KPT || (D != 2 && D != 3) || !mars_scale_ok(s)) return -1;
     if (n == 0) return 0;
     if (!rows || !gx || !gy || !stride || !kpts) return -1;
     if (!nna_is_ready() && nna_init() != NNA_SUCCESS) return -1;
-    const size_t row_b = (size_t)n * K * D, idx_b = (size_t)n * sizeof(int), grid_b = 3 * idx_b, kpt_b = (size_t)n * K * sizeof(mars_kpt_t);
-    const size_t o_cnt = ALIGN_UP(row_b, 256), o_pred = o_cnt + 256, o_grid = o_pred + ALIGN_UP(idx_b, 256), o_tab = o_grid + ALIGN_UP(grid_b, 256);
-    const size_t o_rec = o_tab + 256 * sizeof(float), o_kpt = o_rec + ALIGN_UP((size_t)n * sizeof(mars_pose_t), 256);
-    uint8_t *d = (uint8_t *)mhip_malloc(o_kpt + kpt_b);
+    /* one scratch block: [rows][count][pred][grid][table][recs][kpts] */
+    const size_t sz[7] = {(size_t)n * K * D, sizeof(int), (size_t)n * sizeof(int), (size_t)n * 3 * sizeof(int), 256 * sizeof(float),
+                          (size_t)n * sizeof(mars_pose_t), (size_t)n * K * sizeof(mars_kpt_t)};
+    size_t off[7];
+    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 7, off));
     if (!d) return -1;
     int pred[MARS_POSE_MAX_PER_FRAME], grid[3 * MARS_POSE_MAX_PER_FRAME];
     float tab[256];
@@ -209,19 +156,19 @@ int mars_yolo_keypoints(const int8_t *rows, int n, int K, int D, const int *gx, 
     memset(&p, 0, sizeof(p));
     p.kpt[0] = (const int8_t *)d; p.kpt_pix_step[0] = K * D; p.kpt_ch_step[0] = 1; p.cells[0] = n; p.w[0] = n; p.stride[0] = 1; p.scale[0] = s;
     p.nheads = 1;
-    p.vis = (const float *)(d + o_tab);
+    p.vis = (const float *)(d + off[4]);
     p.num_kpt = K; p.dim = D;
     p.frames = 1;
-    p.counts = (const int *)(d + o_cnt); p.pred = (const int *)(d + o_pred); p.grid = (const int *)(d + o_grid); p.det_cap = n;
+    p.counts = (const int *)(d + off[1]); p.pred = (const int *)(d + off[2]); p.grid = (const int *)(d + off[3]); p.det_cap = n;
     p.select_all = 1; p.max_per_frame = n;
-    p.recs = d + o_rec; p.kpts = d + o_kpt;
-    int rc = mhip_h2d_async(d, rows, row_b);
-    if (!rc) rc = mhip_h2d_async(d + o_cnt, &n, sizeof(int));
-    if (!rc) rc = mhip_h2d_async(d + o_pred, pred, idx_b);
-    if (!rc) rc = mhip_h2d_async(d + o_grid, grid, grid_b);
-    if (!rc) rc = mhip_h2d_async(d + o_tab, tab, sizeof(tab));
+    p.recs = d + off[5]; p.kpts = d + off[6];
+    int rc = mhip_h2d_async(d, rows, sz[0]);
+    if (!rc) rc = mhip_h2d_async(d + off[1], &n, sizeof(int));
+    if (!rc) rc = mhip_h2d_async(d + off[2], pred, sz[2]);
+    if (!rc) rc = mhip_h2d_async(d + off[3], grid, sz[3]);
+    if (!rc) rc = mhip_h2d_async(d + off[4], tab, sizeof(tab));
     if (!rc) rc = mhip_pose(&p);
-    if (!rc) rc = mhip_d2h_async(kpts, p.kpts, kpt_b);
+    if (!rc) rc = mhip_d2h_async(kpts, p.kpts, sz[6]);
     if (mhip_sync()) rc = -1; /* (`n`, `pred`, `grid` and `tab` are on this stack frame) */
     mhip_free(d);
     return rc ? -1 : 0;

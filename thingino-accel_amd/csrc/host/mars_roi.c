@@ -49,14 +49,10 @@ static mars_error_t crop_host(const unsigned char *frames, int n_frames, const v
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     const size_t in_b = p.frame_stride * (size_t)n_frames, out_b = (size_t)p.tw * p.th * 3;
     /* one device block: [frames][boxes][frame_of_box][counters][rois][out][(cos, sin) pairs] */
-    size_t off[7], total = 0;
+    size_t off[7];
     const size_t sz[7] = {in_b, (size_t)n_boxes * box_b, (size_t)n_boxes * sizeof(int), 16, (size_t)n_boxes * sizeof(mars_roi_t),
                           out_b * (size_t)n_boxes, csn ? (size_t)n_boxes * 2 * sizeof(float) : 0};
-    for (int i = 0; i < 7; i++) {
-        off[i] = total;
-        total += ALIGN_UP(sz[i], 256);
-    }
-    uint8_t *d = (uint8_t *)mhip_malloc(total);
+    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 7, off));
     if (!d) return MARS_ERR_ALLOC_FAILED;
     p.frames = d; p.n_frames = n_frames;
     p.boxes = d + off[1]; p.frame_of_box = (const int *)(d + off[2]); p.n_boxes = n_boxes;
@@ -143,7 +139,7 @@ static mars_error_t crop_device(mars_model_t *det_model, const void *frames_dev,
     if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0 || !m->mt[tid].dev || m->mt[tid].stride < (size_t)tw * th * 3)
         return MARS_ERR_INVALID_TENSOR;
     if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
-    if (rot && (!det->obb_dev || det->obb_frames != det->batch)) return MARS_ERR_INVALID_TENSOR;            /* no obb results in HBM */
+    if (rot && (!det->obb.dev || det->obb.frames != det->batch)) return MARS_ERR_INVALID_TENSOR;            /* no obb results in HBM */
     mhip_roi_t p;
     const mars_error_t e = rot ? rot_opts(opts, tw, th, &p) : roi_opts(opts, tw, th, &p);
     if (e != MARS_OK) return e;
@@ -151,7 +147,7 @@ static mars_error_t crop_device(mars_model_t *det_model, const void *frames_dev,
     if (roi_table(m, m->batch, det->batch)) return MARS_ERR_ALLOC_FAILED;
     p.frames = (const uint8_t *)frames_dev; p.n_frames = det->batch;
     if (rot) { /* the kept records, their counts and their (cos, sin) pairs: index-aligned with the detection list */
-        const uint8_t *blk = (const uint8_t *)det->obb_dev;
+        const uint8_t *blk = (const uint8_t *)det->obb.dev;
         p.dets = blk + det->obb_out_off; p.counts = (const int *)(blk + det->obb_cnt_off); p.csn = (const float *)(blk + det->obb_csn_off);
     } else {
         p.dets = det->det_dev; p.counts = det->det_counts_dev;

@@ -109,14 +109,16 @@ mars_error_t mars_yolo_tile_frames(const unsigned char *frames, int n_frames, co
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     const int slots = n_frames * p.n_tiles;
     const size_t in_b = r.frame_stride * (size_t)n_frames, out_b = (size_t)tw * th * 3;
-    const size_t o_cnt = ALIGN_UP(in_b, 256), o_roi = o_cnt + 256, o_out = o_roi + ALIGN_UP((size_t)slots * sizeof(mars_roi_t), 256);
-    uint8_t *d = (uint8_t *)mhip_malloc(o_out + out_b * (size_t)slots);
+    /* one device block: [frames][counters][rois][out] */
+    const size_t sz[4] = {in_b, 256, (size_t)slots * sizeof(mars_roi_t), out_b * (size_t)slots};
+    size_t off[4];
+    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 4, off));
     if (!d) return MARS_ERR_ALLOC_FAILED;
     p.cams = n_frames;
-    p.n_out = (int *)(d + o_cnt); p.rois = d + o_roi;
+    p.n_out = (int *)(d + off[1]); p.rois = d + off[2];
     r.frames = d; r.n_frames = n_frames;
     r.n_out = p.n_out; r.rois = p.rois;
-    r.out = (int8_t *)(d + o_out); r.out_stride = out_b; r.slots = slots; r.nhwc = nhwc != 0;
+    r.out = (int8_t *)(d + off[3]); r.out_stride = out_b; r.slots = slots; r.nhwc = nhwc != 0;
     int rc = mhip_h2d_async(d, frames, in_b);
     if (!rc) rc = mhip_tile_rois(&p);
     if (!rc) rc = mhip_roi_crop(&r);
@@ -126,17 +128,6 @@ mars_error_t mars_yolo_tile_frames(const unsigned char *frames, int n_frames, co
     return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
 }
 
-void mars_tile_release(mars_model_ext_t *m) {
-    if (m->tile_roi_dev) mhip_free(m->tile_roi_dev);
-    if (m->tile_dev) mhip_free(m->tile_dev);
-    m->tile_roi_dev = m->tile_dev = NULL;
-    m->tile_roi_cap = m->tile_cap = m->tile_cams = 0;
-    for (int i = 0; i < 2; i++) {
-        if (m->ev_tile[i]) mhip_event_destroy(m->ev_tile[i]);
-        m->ev_tile[i] = NULL;
-    }
-}
-
 mars_error_t mars_hip_preprocess_tiles_device(mars_model_t *model, int input_index, const void *frames_dev, const mars_hip_tile_opts_t *opts) {
     if (!model || !frames_dev || !opts) return MARS_ERR_INVALID_FILE;
     mhip_tile_t p;
@@ -144,8 +135,7 @@ mars_error_t mars_hip_preprocess_tiles_device(mars_model_t *model, int input_ind
     mars_error_t e = tile_opts(opts, 1, 1, &p); /* what can be said without looking at the model */
     if (e != MARS_OK) return e;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe) return MARS_ERR_INVALID_TENSOR; /* a pipe's slots own their buffers */
+    if ((e = mars_stage_guard(m)) != MARS_OK) return e;
     if (input_index < 0 || (uint32_t)input_index >= model->header.num_inputs) return MARS_ERR_INVALID_TENSOR;
     const uint32_t tid = model->header.input_tensor_ids[input_index];
     if (tid >= model->header.num_tensors) return MARS_ERR_INVALID_TENSOR;
@@ -158,16 +148,10 @@ mars_error_t mars_hip_preprocess_tiles_device(mars_model_t *model, int input_ind
     e = tile_opts(opts, tw, th, &p);
     if (e == MARS_OK) e = tile_roi(opts, tw, th, &r);
     if (e != MARS_OK) return e;
-    if (!m->tile_roi_dev || m->tile_roi_cap < m->batch) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: a crop queued earlier may still read the old table */
-        if (m->tile_roi_dev) mhip_free(m->tile_roi_dev);
-        m->tile_roi_cap = 0;
-        m->tile_roi_dev = mhip_malloc(256 + (size_t)m->batch * sizeof(mars_roi_t));
-        if (!m->tile_roi_dev) return MARS_ERR_ALLOC_FAILED;
-        m->tile_roi_cap = m->batch;
-    }
+    /* (a re-allocation synchronises: a crop queued earlier may still read the old table) */
+    if ((e = mars_block_reserve(&m->tile_roi, 256 + (size_t)m->batch * sizeof(mars_roi_t), 0, NULL)) != MARS_OK) return e;
     p.cams = m->batch / p.n_tiles;
-    p.n_out = (int *)m->tile_roi_dev; p.rois = (uint8_t *)m->tile_roi_dev + 256;
+    p.n_out = (int *)m->tile_roi.dev; p.rois = (uint8_t *)m->tile_roi.dev + 256;
     r.frames = (const uint8_t *)frames_dev; r.n_frames = p.cams;
     r.n_out = p.n_out; r.rois = p.rois;
     r.out = (int8_t *)m->mt[tid].dev; r.out_stride = m->mt[tid].stride; r.slots = m->batch; r.nhwc = nhwc;
@@ -204,14 +188,10 @@ mars_error_t mars_yolo_merge_tiles(const mars_det_t *dets, const int *counts, in
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     const size_t lists = (size_t)n_frames * p.n_tiles, C = (size_t)n_frames;
     /* one device block: [dets][counts][out][out_counts][origins][stats] */
-    size_t off[6], total = 0;
+    size_t off[6];
     const size_t sz[6] = {lists * max_det * sizeof(mars_det_t), lists * sizeof(int), C * MARS_YOLO_MAX_DET * sizeof(mars_det_t), C * sizeof(int),
                           C * MARS_YOLO_MAX_DET * sizeof(mars_tile_src_t), C * sizeof(mars_tile_stats_t)};
-    for (int i = 0; i < 6; i++) {
-        off[i] = total;
-        total += ALIGN_UP(sz[i], 256);
-    }
-    uint8_t *d = (uint8_t *)mhip_malloc(total);
+    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 6, off));
     if (!d) return MARS_ERR_ALLOC_FAILED;
     p.cams = n_frames; p.max_det = max_det;
     p.dets = d; p.counts = (const int *)(d + off[1]);
@@ -229,15 +209,9 @@ mars_error_t mars_yolo_merge_tiles(const mars_det_t *dets, const int *counts, in
 }
 
 /* the merged arrays of C camera frames, one block: [dets][origins][counts][stats] */
-static size_t tile_block(size_t C, size_t off[4]) {
-    const size_t sz[4] = {C * MARS_YOLO_MAX_DET * sizeof(mars_det_t), C * MARS_YOLO_MAX_DET * sizeof(mars_tile_src_t), C * sizeof(int),
-                          C * sizeof(mars_tile_stats_t)};
-    size_t total = 0;
-    for (int i = 0; i < 4; i++) {
-        off[i] = total;
-        total += ALIGN_UP(sz[i], 256);
-    }
-    return total;
+static void tile_parts(size_t C, size_t sz[4]) {
+    sz[0] = C * MARS_YOLO_MAX_DET * sizeof(mars_det_t); sz[1] = C * MARS_YOLO_MAX_DET * sizeof(mars_tile_src_t);
+    sz[2] = C * sizeof(int); sz[3] = C * sizeof(mars_tile_stats_t);
 }
 
 mars_error_t mars_hip_merge_tiles_device(mars_model_t *model, const mars_hip_tile_opts_t *opts) {
@@ -246,8 +220,7 @@ mars_error_t mars_hip_merge_tiles_device(mars_model_t *model, const mars_hip_til
     mars_error_t e = tile_opts(opts, 1, 1, &p);
     if (e != MARS_OK) return e;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (m->pipe) return MARS_ERR_INVALID_TENSOR;
+    if ((e = mars_stage_guard(m)) != MARS_OK) return e;
     if (m->batch % opts->n_tiles) return MARS_ERR_INVALID_TENSOR;
     if (!m->det_dev || !m->det_counts_dev || m->det_cap < m->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
     if (m->det_mapped) return MARS_ERR_INVALID_TENSOR; /* the lists are in source-frame pixels already */
@@ -258,57 +231,40 @@ mars_error_t mars_hip_merge_tiles_device(mars_model_t *model, const mars_hip_til
     if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0) return MARS_ERR_INVALID_TENSOR;
     if ((e = tile_opts(opts, tw, th, &p)) != MARS_OK) return e;
     const int C = m->batch / p.n_tiles;
-    size_t off[4];
-    if (!m->tile_dev || m->tile_cap < C) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
-        if (m->tile_dev) mhip_free(m->tile_dev);
-        m->tile_cap = m->tile_cams = 0;
-        m->tile_dev = mhip_malloc(tile_block((size_t)C, off));
-        if (!m->tile_dev) return MARS_ERR_ALLOC_FAILED;
-        m->tile_cap = C;
-    }
-    for (int i = 0; i < 2; i++) {
-        if (!m->ev_tile[i]) m->ev_tile[i] = mhip_event_create();
-        if (!m->ev_tile[i]) return MARS_ERR_ALLOC_FAILED;
-    }
-    tile_block((size_t)m->tile_cap, off);
-    uint8_t *blk = (uint8_t *)m->tile_dev;
+    size_t sz[4], off[4];
+    tile_parts((size_t)C, sz);
+    if ((e = mars_block_reserve(&m->tile, mars_block_layout(sz, 4, off), 1, NULL)) != MARS_OK) return e;
+    uint8_t *blk = (uint8_t *)m->tile.dev;
     p.cams = C; p.max_det = MARS_YOLO_MAX_DET;
     p.dets = m->det_dev; p.counts = m->det_counts_dev;
     p.out = blk + off[0]; p.origins = blk + off[1]; p.out_counts = (int *)(blk + off[2]); p.stats = blk + off[3];
     /* The auxiliary stream, as mars_hip_track_device: it carries every detection tail, so this comes behind the tail that wrote the lists and
      * ahead of the model's next detect call.  Nothing on the main stream reads or writes what the kernel touches */
-    m->tile_cams = 0;
+    m->tile.frames = 0;
     mhip_select_aux(1);
-    int rc = mhip_event_record(m->ev_tile[0]);
+    int rc = mhip_event_record(m->tile.ev[0]);
     if (!rc) rc = mhip_tile_merge(&p);
-    if (!rc) rc = mhip_event_record(m->ev_tile[1]);
+    if (!rc) rc = mhip_event_record(m->tile.ev[1]);
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;
-    m->tile_cams = C;
+    memcpy(m->tile_off, off, sizeof(off));
+    m->tile.frames = C;
     return MARS_OK;
 }
 
 mars_error_t mars_hip_tile_results(mars_model_t *model, mars_det_t *dets, int *counts, mars_tile_src_t *origins, mars_tile_stats_t *stats) {
     if (!model) return MARS_ERR_INVALID_FILE;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m->tile_dev || m->tile_cams <= 0) return MARS_ERR_INVALID_TENSOR; /* no merge yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    size_t off[4];
-    tile_block((size_t)m->tile_cap, off);
-    const uint8_t *blk = (const uint8_t *)m->tile_dev;
-    const size_t C = (size_t)m->tile_cams;
-    if ((dets && mhip_d2h_async(dets, blk + off[0], C * MARS_YOLO_MAX_DET * sizeof(mars_det_t))) ||
-        (origins && mhip_d2h_async(origins, blk + off[1], C * MARS_YOLO_MAX_DET * sizeof(mars_tile_src_t))) ||
-        (counts && mhip_d2h_async(counts, blk + off[2], C * sizeof(int))) ||
-        (stats && mhip_d2h_async(stats, blk + off[3], C * sizeof(mars_tile_stats_t))) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    return MARS_OK;
+    size_t sz[4];
+    tile_parts((size_t)m->tile.frames, sz);
+    const mars_block_part_t parts[4] = {{dets, m->tile_off[0], sz[0]}, {origins, m->tile_off[1], sz[1]}, {counts, m->tile_off[2], sz[2]},
+                                        {stats, m->tile_off[3], sz[3]}};
+    return mars_block_fetch(&m->tile, parts, 4, NULL);
 }
 
 int mars_hip_tile_frames(mars_model_t *model) {
     const mars_model_ext_t *m = (const mars_model_ext_t *)model;
-    return m && m->tile_dev && m->tile_cams > 0 ? m->tile_cams : 0;
+    return m && m->tile.dev && m->tile.frames > 0 ? m->tile.frames : 0;
 }
 
 mars_error_t mars_hip_merge_tiles(mars_model_t *model, const mars_hip_tile_opts_t *opts, mars_det_t *dets, int *counts, mars_tile_src_t *origins,
@@ -317,8 +273,4 @@ mars_error_t mars_hip_merge_tiles(mars_model_t *model, const mars_hip_tile_opts_
     return e != MARS_OK ? e : mars_hip_tile_results(model, dets, counts, origins, stats);
 }
 
-float mars_hip_tile_ms(mars_model_t *model) {
-    mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (!m || !m->tile_dev || m->tile_cams <= 0 || !m->ev_tile[0] || !m->ev_tile[1]) return -1.0f;
-    return mhip_event_elapsed_ms(m->ev_tile[0], m->ev_tile[1]);
-}
+float mars_hip_tile_ms(mars_model_t *model) { return model ? mars_block_ms(&((mars_model_ext_t *)model)->tile) : -1.0f; }

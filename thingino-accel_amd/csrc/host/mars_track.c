@@ -124,30 +124,26 @@ mars_error_t mars_yolo_track_lists(mars_hip_tracker_t *t, const mars_det_t *dets
     if ((e = track_map(&p, t, frames)) != MARS_OK) return e;
     if (!t->states || !t->hdr || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     const size_t n = (size_t)frames * max_det;
-    const size_t det_b = ALIGN_UP(n * sizeof(mars_det_t), 256), cnt_b = ALIGN_UP((size_t)frames * sizeof(int), 256), rec_b = ALIGN_UP(n * 8, 256);
     const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
-    uint8_t *d = (uint8_t *)mhip_malloc(det_b + cnt_b + rec_b * (carry ? 2 : 1));
+    /* one scratch block: [dets][counts][tracks][identities, where they are carried] */
+    const size_t sz[4] = {n * sizeof(mars_det_t), (size_t)frames * sizeof(int), n * sizeof(mars_track_t), carry ? n * sizeof(mars_cls_t) : 0};
+    size_t off[4];
+    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 4, off));
     if (!d) return MARS_ERR_ALLOC_FAILED;
     p.max_det = max_det;
     p.dets = d;
-    p.counts = (const int *)(d + det_b);
-    p.out = d + det_b + cnt_b;
-    p.idents = carry ? d + det_b + cnt_b + rec_b : NULL;
+    p.counts = (const int *)(d + off[1]);
+    p.out = d + off[2];
+    p.idents = carry ? d + off[3] : NULL;
     /* on the main stream: behind whatever the auxiliary stream still does to this tracker's tables, hence the wait first */
     int rc = mhip_sync();
-    if (!rc) rc = mhip_h2d_async(d, dets, n * sizeof(mars_det_t)) || mhip_h2d_async(d + det_b, counts, (size_t)frames * sizeof(int));
-    if (!rc && carry) rc = mhip_h2d_async(d + det_b + cnt_b + rec_b, idents, n * sizeof(mars_cls_t));
+    if (!rc) rc = mhip_h2d_async(d, dets, sz[0]) || mhip_h2d_async(d + off[1], counts, sz[1]);
+    if (!rc && carry) rc = mhip_h2d_async(d + off[3], idents, sz[3]);
     if (!rc) rc = mhip_track(&p);
-    if (!rc) rc = mhip_d2h_async(out, p.out, n * sizeof(mars_track_t));
+    if (!rc) rc = mhip_d2h_async(out, p.out, sz[2]);
     if (mhip_sync()) rc = -1;
     mhip_free(d);
     return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
-}
-
-void mars_track_release(mars_model_ext_t *m) {
-    if (m->track_dev) mhip_free(m->track_dev);
-    m->track_dev = NULL;
-    m->track_cap = m->track_frames = 0;
 }
 
 mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts) {
@@ -161,40 +157,29 @@ mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *
     if (det->pipe) return MARS_ERR_INVALID_TENSOR;
     if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
     const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
-    if (carry && (!det->ident_dev || det->ident_frames < det->batch)) return MARS_ERR_INVALID_TENSOR;      /* no identity scatter */
+    if (carry && (!det->ident.dev || det->ident.frames < det->batch)) return MARS_ERR_INVALID_TENSOR;      /* no identity scatter */
     if ((e = track_map(&p, t, det->batch)) != MARS_OK) return e;
-    if (!det->track_dev || det->track_cap < det->batch) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
-        mars_track_release(det);
-        det->track_dev = mhip_malloc((size_t)det->batch * MARS_YOLO_MAX_DET * sizeof(mars_track_t));
-        if (!det->track_dev) return MARS_ERR_ALLOC_FAILED;
-        det->track_cap = det->batch;
-    }
+    if ((e = mars_side_reserve(&det->track, det->batch, sizeof(mars_track_t))) != MARS_OK) return e;
     p.max_det = MARS_YOLO_MAX_DET;
     p.dets = det->det_dev;
     p.counts = det->det_counts_dev;
-    p.idents = carry ? det->ident_dev : NULL;
-    p.out = det->track_dev;
+    p.idents = carry ? det->ident.dev : NULL;
+    p.out = det->track.dev;
     /* The auxiliary stream, as the label scatter: it carries every detection tail and every scatter, so this comes behind the tail that
      * wrote the lists and the scatter that wrote the identities, and ahead of det_model's next detect call.  Nothing on the main stream
      * reads or writes what the kernel touches, so nothing there waits for it */
-    det->track_frames = 0;
+    det->track.frames = 0;
     mhip_select_aux(1);
     const int rc = mhip_track(&p);
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;
-    det->track_frames = det->batch;
+    det->track.frames = det->batch;
     return MARS_OK;
 }
 
 mars_error_t mars_hip_track_results(mars_model_t *det_model, mars_track_t *tracks) {
     if (!det_model || !tracks) return MARS_ERR_INVALID_FILE;
-    mars_model_ext_t *det = (mars_model_ext_t *)det_model;
-    if (!det->track_dev || det->track_frames <= 0) return MARS_ERR_INVALID_TENSOR; /* no track call yet */
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* both streams */
-    if (mhip_d2h_async(tracks, det->track_dev, (size_t)det->track_frames * MARS_YOLO_MAX_DET * sizeof(mars_track_t)) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED;
-    return MARS_OK;
+    return mars_side_fetch(&((mars_model_ext_t *)det_model)->track, tracks, sizeof(mars_track_t));
 }
 
 mars_error_t mars_hip_track(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts, mars_track_t *tracks) {

@@ -50,25 +50,19 @@ mars_error_t mars_detect_prepare(mars_model_ext_t *m, const int *output_indices,
     if (!output_indices || n_outputs <= 0 || n_outputs > 4) return MARS_ERR_INVALID_TENSOR;
     if (!m->det_lut_dev) m->det_lut_dev = (float *)mhip_malloc(4 * 768 * sizeof(float));
     if (!m->det_lut_dev) return MARS_ERR_ALLOC_FAILED;
-    int lut_stale = m->det_lut_n != n_outputs;
+    float key[4][2] = {{0}};
     for (int s = 0; s < n_outputs; s++) {
         mars_runtime_tensor_t *t = mars_get_output(model, output_indices[s]);
         if (!t || t->desc.dtype != MARS_DTYPE_INT8) return MARS_ERR_INVALID_TENSOR;
-        if (memcmp(&m->det_lut_scale[s], &t->desc.scale, sizeof(float)) != 0) lut_stale = 1;
+        key[s][0] = t->desc.scale;
     }
-    if (!lut_stale) return MARS_OK;
+    if (!mars_lut_stale(&m->det_lut, n_outputs, key)) return MARS_OK;
     float lut[4 * 768];
     for (int s = 0; s < n_outputs; s++) {
-        float sc = mars_get_output(model, output_indices[s])->desc.scale;
-        build_decode_lut(sc, lut + s * 768);
-        m->det_lut_scale[s] = sc;
+        build_decode_lut(key[s][0], lut + s * 768);
         m->det_lut_mono[s] = lut_increasing(lut + s * 768);
     }
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
-    if (mhip_h2d_async(m->det_lut_dev, lut, (size_t)n_outputs * 768 * sizeof(float)) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED; /* `lut` is on this stack frame */
-    m->det_lut_n = n_outputs;
-    return MARS_OK;
+    return mars_lut_refresh(&m->det_lut, m->det_lut_dev, n_outputs, key, lut, 768); /* `lut` is on this stack frame */
 }
 
 /* decode + NMS of the current batch on the CURRENT stream, from the output tensors' current device buffers into
@@ -105,7 +99,7 @@ mars_error_t mars_hip_detect_device(mars_model_t *model, const int *output_indic
     if (m->det_cap < m->batch || !m->det_dev) {
         if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
         if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
-        m->det_lut_n = 0;
+        m->det_lut.n = 0;
     }
     for (int s = 0; s < n_outputs; s++) {
         if (!mars_get_output(model, output_indices[s])) return MARS_ERR_INVALID_TENSOR;
@@ -334,22 +328,15 @@ mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h,
 mars_error_t mars_heads_prepare(mars_model_ext_t *m, const mars_heads_cfg_t *c) {
     if (!m->heads_lut_dev) m->heads_lut_dev = (float *)mhip_malloc(4 * 256 * sizeof(float));
     if (!m->heads_lut_dev) return MARS_ERR_ALLOC_FAILED;
-    int stale = m->heads_lut_n != c->n;
-    for (int k = 0; k < c->n; k++)
-        if (memcmp(&m->heads_lut_scale[k], &m->pub.tensors[c->ti[k]].desc.scale, sizeof(float)) != 0) stale = 1;
-    if (!stale) return MARS_OK;
+    float key[4][2] = {{0}};
+    for (int k = 0; k < c->n; k++) key[k][0] = m->pub.tensors[c->ti[k]].desc.scale;
+    if (!mars_lut_stale(&m->heads_lut, c->n, key)) return MARS_OK;
     float lut[4 * 256], tab[768];
     for (int k = 0; k < c->n; k++) {
-        const float sc = m->pub.tensors[c->ti[k]].desc.scale;
-        build_decode_lut(sc, tab); /* its obj(q) = 1 / (1 + expf(-q * scale)): the sigmoid of every head byte */
+        build_decode_lut(key[k][0], tab); /* its obj(q) = 1 / (1 + expf(-q * scale)): the sigmoid of every head byte */
         memcpy(lut + k * 256, tab + 256, 256 * sizeof(float));
-        m->heads_lut_scale[k] = sc;
     }
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
-    if (mhip_h2d_async(m->heads_lut_dev, lut, (size_t)c->n * 256 * sizeof(float)) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED; /* `lut` is on this stack frame */
-    m->heads_lut_n = c->n;
-    return MARS_OK;
+    return mars_lut_refresh(&m->heads_lut, m->heads_lut_dev, c->n, key, lut, 256); /* `lut` is on this stack frame */
 }
 
 int mars_heads_launch(mars_model_ext_t *m, const mars_heads_cfg_t *c, void *dets_dev, int *counts_dev) {
@@ -382,7 +369,7 @@ static mars_error_t own_det_buffers(mars_model_ext_t *m) {
     if (m->det_cap >= m->batch && m->det_dev) return MARS_OK;
     if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
     if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
-    m->det_lut_n = 0;
+    m->det_lut.n = 0;
     return MARS_OK;
 }
 
@@ -610,24 +597,16 @@ mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *
 mars_error_t mars_dfl_prepare(mars_model_ext_t *m, const mars_dfl_cfg_t *c) {
     if (!m->dfl_lut_dev) m->dfl_lut_dev = (float *)mhip_malloc(4 * 512 * sizeof(float));
     if (!m->dfl_lut_dev) return MARS_ERR_ALLOC_FAILED;
-    int stale = m->dfl_lut_n != c->n;
-    for (int k = 0; k < c->n; k++)
-        if (memcmp(&m->dfl_lut_scale[k][0], &c->box_scale[k], sizeof(float)) != 0 || memcmp(&m->dfl_lut_scale[k][1], &c->cls_scale[k], sizeof(float)) != 0)
-            stale = 1;
-    if (!stale) return MARS_OK;
+    float key[4][2] = {{0}};
+    for (int k = 0; k < c->n; k++) { key[k][0] = c->box_scale[k]; key[k][1] = c->cls_scale[k]; }
+    if (!mars_lut_stale(&m->dfl_lut, c->n, key)) return MARS_OK;
     float lut[4 * 512], tab[768];
     for (int k = 0; k < c->n; k++) {
         for (int d = 0; d < 256; d++) lut[k * 512 + d] = expf(-((float)d * c->box_scale[k]));
         build_decode_lut(c->cls_scale[k], tab);
         memcpy(lut + k * 512 + 256, tab + 256, 256 * sizeof(float));
     }
-    if (mhip_sync()) return MARS_ERR_LAYER_FAILED;
-    m->dfl_lut_n = 0; /* (until the new tables are up) */
-    if (mhip_h2d_async(m->dfl_lut_dev, lut, (size_t)c->n * 512 * sizeof(float)) || mhip_sync())
-        return MARS_ERR_LAYER_FAILED; /* `lut` is on this stack frame */
-    for (int k = 0; k < c->n; k++) { m->dfl_lut_scale[k][0] = c->box_scale[k]; m->dfl_lut_scale[k][1] = c->cls_scale[k]; }
-    m->dfl_lut_n = c->n;
-    return MARS_OK;
+    return mars_lut_refresh(&m->dfl_lut, m->dfl_lut_dev, c->n, key, lut, 512); /* `lut` is on this stack frame */
 }
 
 int mars_dfl_launch(mars_model_ext_t *m, const mars_dfl_cfg_t *c, void *dets_dev, int *counts_dev) {
