@@ -112,7 +112,7 @@ def disjoint_lists(T, per_tile, max_det):
 
 
 MERGE_CASES = ["t1", "t2", "t6_counts", "t6_edge0", "t6_edge4", "t6_ios", "t6_iou", "t6_agnostic", "t6_classes", "t6_thresh03", "t6_thresh07",
-               "t6_invalid", "t6_keep_aspect", "t16_quota", "t16_full", "t16_ties", "t16_disjoint", "t2_three_frames"]
+               "t6_invalid", "t6_keep_aspect", "t16_quota", "t16_full", "t16_ties", "t16_disjoint", "t2_three_frames", "t2_n64", "t2_n65", "t16_n1025"]
 
 
 def merge_case(name):
@@ -127,6 +127,9 @@ def merge_case(name):
         n_frames = 3 if name.endswith("frames") else 1
         parts = [synth_lists(0x7200 + c, W, H, tiles, [60 + c, 50], 64, 45) for c in range(n_frames)]
         dets, counts = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    elif name in ("t2_n64", "t2_n65"):  # candidate counts at the edge of the 64-row chunks of the suppression walk
+        W, H, tiles = TABLES[2]
+        dets, counts = synth_lists(0x7264, W, H, tiles, [32, int(name[4:]) - 32], 64, 45)
     elif name.startswith("t6"):
         W, H, tiles = TABLES[6]
         cnt = [0, 1, 63, 64, 65, 40] if name == "t6_counts" else [50, 64, 33, 65, 20, 47]
@@ -154,6 +157,8 @@ def merge_case(name):
             dets, counts = synth_lists(0x7161, W, H, tiles, [128] * 16, 128, 700, size=(5.0, 16.0))
         elif name == "t16_ties":
             dets, counts = synth_lists(0x7162, W, H, tiles, [60] * 16, 64, 300, levels=8)
+        elif name == "t16_n1025":  # one candidate behind 1024: a last chunk of one row, and the removed set's upper 16 words in use
+            dets, counts = synth_lists(0x7163, W, H, tiles, [64] * 15 + [65], 65, 300)
         else:
             dets, counts = disjoint_lists(16, 128, 128)
             bite = False
@@ -171,6 +176,8 @@ def merge_case(name):
         assert st[0]["suppressed"] == 0 and oc[0] == 70 and (org[0, :70]["det"] == order).all() and (out[0, :70]["conf"] == cand["conf"][order]).all()
     if name == "t6_counts":
         assert st[0]["candidates"] == sum([0, 1, 63, 64, 65, 40])
+    if name in ("t2_n64", "t2_n65", "t16_n1025"):
+        assert st[0]["candidates"] == int(name.split("_n")[1])
     if name == "t6_edge0":
         assert st[0]["edge"] == 0
     if name == "t6_edge4":

@@ -20,12 +20,10 @@
 
 #include "../expf_exact.h"
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
-
-struct cls_rec_t { int cls; float score; };            // mars_cls_t
-struct cls_roi_t { int frame, det, x0, y0, x1, y1; };  // mars_roi_t
 
 #define CLS_ONES 0x01010101
 
@@ -165,26 +163,26 @@ __global__ __launch_bounds__(64) void cls_finish_kernel(const mhip_classify_t p)
         int my = -1;
 #pragma unroll
         for (int k = 0; k < MHIP_CLS_MAX_TOPK; k++) my = lane == k ? cls[k] : my;
-        cls_rec_t r;
+        cls_t r;
         r.cls = my;
         r.score = 0.0f;
         if (my >= 0) r.score = p.softmax ? e[my] / den : ((float)s[my] / fhw) * p.scale;
-        ((cls_rec_t *)p.top)[(size_t)f * p.top_k + lane] = r;
+        ((cls_t *)p.top)[(size_t)f * p.top_k + lane] = r;
     }
 }
 
-__global__ __launch_bounds__(256) void cls_label_fill_kernel(cls_rec_t *labels, const size_t n) {
-    cls_rec_t none;
+__global__ __launch_bounds__(256) void cls_label_fill_kernel(cls_t *labels, const size_t n) {
+    cls_t none;
     none.cls = -1;
     none.score = 0.0f;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) labels[i] = none;
 }
 
-__global__ __launch_bounds__(256) void cls_label_scatter_kernel(const cls_roi_t *rois, const int *n_out, const int slots, const cls_rec_t *top, const int top_k,
-                                                                cls_rec_t *labels, const int det_frames, const int det_cap) {
+__global__ __launch_bounds__(256) void cls_label_scatter_kernel(const roi_t *rois, const int *n_out, const int slots, const cls_t *top, const int top_k,
+                                                                cls_t *labels, const int det_frames, const int det_cap) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= slots || k >= n_out[0]) return;
-    const cls_roi_t r = rois[k];
+    const roi_t r = rois[k];
     if (r.frame < 0 || r.frame >= det_frames || r.det < 0 || r.det >= det_cap) return; // (a caller's box: det = -1)
     labels[(size_t)r.frame * det_cap + r.det] = top[(size_t)k * top_k];
 }
@@ -258,8 +256,8 @@ extern "C" int mhip_label_scatter(const void *rois, const int *n_out, int slots,
     const size_t n = (size_t)det_frames * det_cap;
     const unsigned fill = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     hipStream_t st = mhip_stream_native();
-    hipLaunchKernelGGL(cls_label_fill_kernel, dim3(fill), dim3(256), 0, st, (cls_rec_t *)labels, n);
-    hipLaunchKernelGGL(cls_label_scatter_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (const cls_roi_t *)rois, n_out, slots,
-                       (const cls_rec_t *)top, top_k, (cls_rec_t *)labels, det_frames, det_cap);
+    hipLaunchKernelGGL(cls_label_fill_kernel, dim3(fill), dim3(256), 0, st, (cls_t *)labels, n);
+    hipLaunchKernelGGL(cls_label_scatter_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (const roi_t *)rois, n_out, slots,
+                       (const cls_t *)top, top_k, (cls_t *)labels, det_frames, det_cap);
     return mhip_check(hipGetLastError(), "label scatter");
 }

@@ -24,14 +24,13 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
 typedef int gm_v4i __attribute__((ext_vector_type(4)));
 typedef unsigned long long gm_word_t;
-
-struct gm_rec_t { int cls; float score; }; // mars_cls_t
 
 #define GM_QT 64        // queries per workgroup
 #define GM_KEEP MHIP_MATCH_KEEP
@@ -216,7 +215,7 @@ __global__ __launch_bounds__(64) void gm_merge_kernel(const mhip_match_t p, cons
         else prev = 0;
     }
     if (lane < p.top_k) {
-        gm_rec_t r;
+        cls_t r;
         r.cls = -1;
         r.score = 0.0f;
         int row = -1;
@@ -228,7 +227,7 @@ __global__ __launch_bounds__(64) void gm_merge_kernel(const mhip_match_t p, cons
                 r.score = score;
             }
         }
-        ((gm_rec_t *)p.top)[(size_t)n * p.top_k + lane] = r;
+        ((cls_t *)p.top)[(size_t)n * p.top_k + lane] = r;
         p.top_row[(size_t)n * p.top_k + lane] = row;
     }
 }

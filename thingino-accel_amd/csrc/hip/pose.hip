@@ -16,20 +16,10 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
-
-struct ps_det {
-    float x, y, w, h, conf;
-    int cls;
-};
-struct ps_rec {
-    int det, head, cell;
-};
-struct ps_kpt {
-    float x, y, v;
-};
 
 #define POSE_SEL_THREADS 64
 #define POSE_THREADS 256
@@ -37,9 +27,9 @@ struct ps_kpt {
 __global__ __launch_bounds__(POSE_SEL_THREADS) void pose_select_kernel(const mhip_pose_t p) {
     const int f = blockIdx.x, lane = threadIdx.x;
     const int M = p.max_per_frame;
-    const ps_det *dets = (const ps_det *)p.dets + (size_t)f * p.det_cap;
+    const det_t *dets = (const det_t *)p.dets + (size_t)f * p.det_cap;
     const int *pred = p.pred + (size_t)f * p.det_cap;
-    ps_rec *recs = (ps_rec *)p.recs + (size_t)f * M;
+    pose_t *recs = (pose_t *)p.recs + (size_t)f * M;
     int n = p.counts[f];
     n = n < 0 ? 0 : n > p.det_cap ? p.det_cap : n;
     int taken = 0;
@@ -51,7 +41,7 @@ __global__ __launch_bounds__(POSE_SEL_THREADS) void pose_select_kernel(const mhi
         const unsigned long long m = __ballot(ok);
         const int slot = taken + __popcll(m & ((1ull << lane) - 1ull));
         if (ok && slot < M) {
-            ps_rec r = {i, -1, -1};
+            pose_t r = {i, -1, -1};
             int pr = pred[i]; // (never read beyond the count)
 #pragma unroll
             for (int k = 0; k < 4; k++) // constant indices into the kernel arguments
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(POSE_SEL_THREADS) void pose_select_kernel(const mhi
         taken += __popcll(m);
     }
     if (taken > M) taken = M;
-    for (int slot = taken + lane; slot < M; slot += POSE_SEL_THREADS) recs[slot] = ps_rec{-1, -1, -1};
+    for (int slot = taken + lane; slot < M; slot += POSE_SEL_THREADS) recs[slot] = pose_t{-1, -1, -1};
 }
 
 __global__ __launch_bounds__(POSE_THREADS) void pose_kpt_kernel(const mhip_pose_t p) {
@@ -72,8 +62,8 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_kpt_kernel(const mhip_pose_
     const int K = p.num_kpt, D = p.dim, M = p.max_per_frame;
     if (t >= M * K) return;
     const int slot = t / K, j = t - slot * K;
-    const ps_rec r = ((const ps_rec *)p.recs)[(size_t)f * M + slot];
-    ps_kpt o = {0.0f, 0.0f, 0.0f};
+    const pose_t r = ((const pose_t *)p.recs)[(size_t)f * M + slot];
+    kpt_t o = {0.0f, 0.0f, 0.0f};
     if (r.det >= 0 && r.head >= 0) {
         const int8_t *b = nullptr;
         size_t fs = 0;
@@ -104,7 +94,7 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_kpt_kernel(const mhip_pose_
             o.y = __fmul_rn(__fsub_rn(o.y, (float)p.py), p.ry);
         }
     }
-    ((ps_kpt *)p.kpts)[(size_t)f * M * K + t] = o;
+    ((kpt_t *)p.kpts)[(size_t)f * M * K + t] = o;
 }
 
 extern "C" int mhip_pose(const mhip_pose_t *p) {

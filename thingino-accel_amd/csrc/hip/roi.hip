@@ -18,16 +18,14 @@
 
 #include "../mhip.h"
 #include "nv12.hpp"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-struct roi_rec_t { int frame, det, x0, y0, x1, y1; };   // mars_roi_t
-struct roi_det_t { float x, y, w, h, conf; int cls; };  // mars_det_t
-
 // box -> source rectangle; false = skipped (the rectangle is then all zeros).  float32, every operation rounded on its own (-ffp-contract=off).
 // The two clamps in front of the conversions keep far-away boxes inside the int range and change no decision: x0f > W + 1 means x0 > x1 anyway
-__device__ __forceinline__ bool roi_rect(const roi_det_t d, const float expand, const int min_size, const int W, const int H, int &x0, int &y0,
+__device__ __forceinline__ bool roi_rect(const det_t d, const float expand, const int min_size, const int W, const int H, int &x0, int &y0,
                                          int &x1, int &y1) {
     x0 = y0 = x1 = y1 = 0;
     if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf))) return false;
@@ -45,10 +43,9 @@ __device__ __forceinline__ bool roi_rect(const roi_det_t d, const float expand, 
 
 // ---- "Rotated crops": the skip rule, the enclosing rectangle of the ROI table and the Q16 sample frame of an oriented box.  float32, every
 // operation rounded on its own; rintf is round-to-nearest-even on both sides; `/` is the correctly rounded division (hipcc's default)
-struct roi_obb_t { float x, y, w, h, conf; int cls; float angle; int pred; }; // mars_obb_t
 
 // false = skipped; we, he = the expanded sides.  Behind this rule every conversion below is defined: we, he <= 32768, the centre inside the frame
-__device__ __forceinline__ bool rot_sides(const roi_obb_t d, const float expand, const int min_size, const int W, const int H, float &we, float &he) {
+__device__ __forceinline__ bool rot_sides(const obb_t d, const float expand, const int min_size, const int W, const int H, float &we, float &he) {
     we = he = 0.0f;
     if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf) && isfinite(d.angle))) return false;
     if (!(d.w > 0.0f) || !(d.h > 0.0f)) return false;
@@ -59,7 +56,7 @@ __device__ __forceinline__ bool rot_sides(const roi_obb_t d, const float expand,
 }
 
 // the rule and, for a kept box, the integer rectangle around the expanded box, clipped to the frame (the ROI table's x0 .. y1: never read back here)
-__device__ __forceinline__ bool rot_rect(const roi_obb_t d, const float cs, const float sn, const float expand, const int min_size, const int W, const int H,
+__device__ __forceinline__ bool rot_rect(const obb_t d, const float cs, const float sn, const float expand, const int min_size, const int W, const int H,
                                          int &x0, int &y0, int &x1, int &y1) {
     x0 = y0 = x1 = y1 = 0;
     float we, he;
@@ -73,7 +70,7 @@ __device__ __forceinline__ bool rot_rect(const roi_obb_t d, const float cs, cons
 
 struct rot_geom_t { int X0, Y0, Ux, Uy, Vx, Vy, nw, nh, px, py; };
 __device__ __forceinline__ int rot_q16(const float v) { return (int)rintf(__fmul_rn(v, 65536.0f)); }
-__device__ __forceinline__ rot_geom_t rot_geom(const roi_obb_t d, const float we, const float he, const float cs, const float sn, const int tw, const int th,
+__device__ __forceinline__ rot_geom_t rot_geom(const obb_t d, const float we, const float he, const float cs, const float sn, const int tw, const int th,
                                                const int keep_aspect) {
     rot_geom_t g;
     g.nw = tw; g.nh = th;
@@ -117,8 +114,8 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
         }
     }
     const int n = min(max(p.counts[f], 0), p.det_cap);
-    const roi_det_t *dets = (const roi_det_t *)p.dets + (size_t)f * p.det_cap;
-    roi_rec_t *rois = (roi_rec_t *)p.rois;
+    const det_t *dets = (const det_t *)p.dets + (size_t)f * p.det_cap;
+    roi_t *rois = (roi_t *)p.rois;
     int kept = 0;
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + lane;
@@ -126,11 +123,11 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
         int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
         if (i < n && ROT) {
             const size_t k = (size_t)f * p.det_cap + i;
-            const roi_obb_t d = ((const roi_obb_t *)p.dets)[k];
+            const obb_t d = ((const obb_t *)p.dets)[k];
             ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
                  rot_rect(d, p.csn[2 * k], p.csn[2 * k + 1], p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
         } else if (i < n) {
-            const roi_det_t d = dets[i];
+            const det_t d = dets[i];
             ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
                  roi_rect(d, p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
         }
@@ -138,7 +135,7 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
         const int rank = kept + __popcll(mask & ((1ull << lane) - 1ull));
         if (p.max_per_frame > 0 && rank >= p.max_per_frame) ok = false;
         if (PHASE == 1 && ok && base + rank < p.slots) {
-            roi_rec_t r;
+            roi_t r;
             r.frame = f; r.det = i; r.x0 = x0; r.y0 = y0; r.x1 = x1; r.y1 = y1;
             rois[base + rank] = r;
         }
@@ -159,19 +156,19 @@ __global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
         p.n_out[1] = 0;
     }
     if (i >= p.n_boxes || i >= p.slots) return;
-    roi_rec_t r;
+    roi_t r;
     r.frame = p.frame_of_box[i];
     r.det = -1;
     const bool ok = r.frame >= 0 && r.frame < p.n_frames;
     r.x0 = r.y0 = r.x1 = r.y1 = 0;
     if (ROT) {
-        const roi_obb_t d = ((const roi_obb_t *)p.boxes)[i];
+        const obb_t d = ((const obb_t *)p.boxes)[i];
         if (ok) rot_rect(d, p.csn[2 * i], p.csn[2 * i + 1], p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
     } else {
-        const roi_det_t d = ((const roi_det_t *)p.boxes)[i];
+        const det_t d = ((const det_t *)p.boxes)[i];
         if (ok) roi_rect(d, p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
     }
-    ((roi_rec_t *)p.rois)[i] = r;
+    ((roi_t *)p.rois)[i] = r;
 }
 
 #define ROI_R 8 // output rows of a strip
@@ -220,8 +217,8 @@ __global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const
     int8_t *dst = p.out + (size_t)slot * p.out_stride;
     // this slot's geometry, from device memory
     bool live = slot < p.n_out[0];
-    roi_rec_t r = {0, 0, 0, 0, 0, 0};
-    if (live) r = ((const roi_rec_t *)p.rois)[slot];
+    roi_t r = {0, 0, 0, 0, 0, 0};
+    if (live) r = ((const roi_t *)p.rois)[slot];
     const int cw = r.x1 - r.x0, ch = r.y1 - r.y0;
     live = live && cw > 0 && ch > 0 && r.frame >= 0 && r.frame < p.n_frames && r.x0 >= 0 && r.y0 >= 0 && r.x1 <= p.w && r.y1 <= p.h;
     int nw = p.tw, nh = p.th;
@@ -368,13 +365,13 @@ __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, c
     int8_t *dst = p.out + (size_t)slot * p.out_stride;
     // this slot's box, from device memory: entry (frame, det) of the lists, or the caller's box `slot`
     bool live = slot < p.n_out[0];
-    roi_rec_t r = {0, 0, 0, 0, 0, 0};
-    if (live) r = ((const roi_rec_t *)p.rois)[slot];
+    roi_t r = {0, 0, 0, 0, 0, 0};
+    if (live) r = ((const roi_t *)p.rois)[slot];
     live = live && r.x1 > r.x0 && r.frame >= 0 && r.frame < p.n_frames && (r.det < 0 ? p.boxes != nullptr : (p.dets != nullptr && r.det < p.det_cap));
     rot_geom_t g = {0, 0, 0, 0, 0, 0, p.tw, p.th, 0, 0};
     if (live) {
         const size_t k = r.det < 0 ? (size_t)slot : (size_t)r.frame * p.det_cap + r.det;
-        const roi_obb_t d = ((const roi_obb_t *)(r.det < 0 ? p.boxes : p.dets))[k];
+        const obb_t d = ((const obb_t *)(r.det < 0 ? p.boxes : p.dets))[k];
         const float cs = p.csn[2 * k], sn = p.csn[2 * k + 1];
         float we, he;
         live = rot_sides(d, p.expand, p.min_size, p.w, p.h, we, he);

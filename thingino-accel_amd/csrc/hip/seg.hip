@@ -26,19 +26,12 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
 typedef int sg_v4i __attribute__((ext_vector_type(4)));
-
-struct sg_det {
-    float x, y, w, h, conf;
-    int cls;
-};
-struct sg_rec {
-    int det, x0, y0, x1, y1, area;
-};
 
 #define SEG_SEL_THREADS 64
 #define SEG_THREADS 256
@@ -55,22 +48,22 @@ __device__ __forceinline__ int sg_edge(float v, int hi, bool up) {
 __global__ __launch_bounds__(SEG_SEL_THREADS) void seg_select_kernel(const mhip_seg_t p) {
     const int f = blockIdx.x, lane = threadIdx.x;
     const int M = p.max_per_frame;
-    const sg_det *dets = (const sg_det *)p.boxes + (size_t)f * p.det_cap;
-    sg_rec *recs = (sg_rec *)p.recs + (size_t)f * M;
+    const det_t *dets = (const det_t *)p.boxes + (size_t)f * p.det_cap;
+    mask_t *recs = (mask_t *)p.recs + (size_t)f * M;
     int n = p.counts[f];
     n = n < 0 ? 0 : n > p.det_cap ? p.det_cap : n;
     const float fx = __fdiv_rn((float)p.pw, (float)p.in_w), fy = __fdiv_rn((float)p.ph, (float)p.in_h);
     int taken = 0;
     for (int base = 0; base < n && taken < M; base += SEG_SEL_THREADS) {
         const int i = base + lane;
-        sg_det d = {0, 0, 0, 0, 0, 0};
+        det_t d = {0, 0, 0, 0, 0, 0};
         if (i < n) d = dets[i];
         const bool ok = i < n && (p.select_all || d.conf >= p.min_conf);
         const unsigned long long m = __ballot(ok);
         const int slot = taken + __popcll(m & ((1ull << lane) - 1ull));
         if (ok && slot < M) {
             const float hw = __fmul_rn(d.w, 0.5f), hh = __fmul_rn(d.h, 0.5f);
-            sg_rec r;
+            mask_t r;
             r.det = i;
             r.x0 = sg_edge(__fmul_rn(__fsub_rn(d.x, hw), fx), p.pw, false);
             r.x1 = sg_edge(__fmul_rn(__fadd_rn(d.x, hw), fx), p.pw, true);
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(SEG_SEL_THREADS) void seg_select_kernel(const mhip_
         taken += __popcll(m);
     }
     if (taken > M) taken = M;
-    for (int slot = taken + lane; slot < M; slot += SEG_SEL_THREADS) recs[slot] = sg_rec{-1, 0, 0, 0, 0, 0};
+    for (int slot = taken + lane; slot < M; slot += SEG_SEL_THREADS) recs[slot] = mask_t{-1, 0, 0, 0, 0, 0};
 }
 
 // the 16 bytes of channels kb .. kb + 15 (zero from nm on) of the pixel / cell whose channel 0 is at q
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_mask_kernel(const mhip_seg_t 
     __shared__ int nsel_s;
     const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int M = p.max_per_frame, pitch = (p.pw + 31) >> 5, units = p.ph * pitch;
-    sg_rec *recs = (sg_rec *)p.recs + (size_t)f * M;
+    mask_t *recs = (mask_t *)p.recs + (size_t)f * M;
     uint32_t *words = p.words + (size_t)f * M * units;
     if (tid < 64) {
         int det = -1, head = -1, cell = 0, x0 = 0, y0 = 0, x1 = 0, y1 = 0;

@@ -4,14 +4,15 @@
 // include/mars_hip.h ("Tiled inference") states the arithmetic.  The reference has no batch and no such step; nothing here restates it.
 //   tile_rois_kernel   slot c * T + t of the ROI table = tile t's rectangle in camera frame c.  The front-end is then roi_crop_kernel itself:
 //                      the bytes of a tile are the bytes of a crop of that rectangle, by construction.
-//   tile_merge_kernel  one workgroup per camera frame, sort_nms_kernel (yolo_tail.hip) in shape:
+//   tile_merge_kernel  one workgroup per camera frame, sort_nms_kernel (yolo_tail.hip) in shape; sort, buckets, walk and compaction are
+//                      tail_core.hpp's:
 //                      gather  the first `quota` entries of every tile's list, validity, map and edge rule applied, into LDS by an ordered
-//                              block-wide count (wave ballots + a scan over the waves), so that slot k is candidate k of the header's numbering;
+//                              block-wide count (block_rank), so that slot k is candidate k of the header's numbering;
 //                      sort    bitonic over a 64-bit key (confidence in its order-preserving integer form, 2047 - k): confidence descending,
 //                              k ascending, a strict total order -- no tie replay as in the tail, the exchange-sort permutation is not part of
 //                              this contract;
-//                      pairs   "different tiles, same class (or agnostic), m > t" 64 rows at a time inside class buckets into a 64 x 2048 bit
-//                              matrix; wave 0 walks the rows greedily (a removed candidate removes nothing), 32 lanes holding the removed set;
+//                      pairs   "different tiles, same class (or agnostic), m > t" inside class buckets into a 64 x 2048 bit matrix
+//                              (greedy_suppress<32>: 32 lanes hold the removed set);
 //                      output  survivors compacted in sorted order, the first 1000 written, the slots behind them zeroed, the counters.
 // LDS: 2048 x {x, y, w, h, conf, class: 24 bytes, list index: 2, tile: 1, sorted slot -> k: 2, bucket list: 2} = 62 KB, the bit matrix (the
 // sort's keys before it is needed) 16 KB, bucket and scan words 1.5 KB: 81464 bytes, under 80 KB so that two workgroups share a CU and the
@@ -20,22 +21,16 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-struct tile_det_t { float x, y, w, h, conf; int cls; };   // mars_det_t
-struct tile_src_t { int tile, det; };                     // mars_tile_src_t
-struct tile_roi_t { int frame, det, x0, y0, x1, y1; };    // mars_roi_t
-struct tile_stats_t { int candidates, overflow, invalid, edge, suppressed, truncated; }; // mars_tile_stats_t
-
-#define TM_THREADS 512
-#define TM_WAVES (TM_THREADS / 64)
+#define TM_THREADS NMS_THREADS
+#define TM_WAVES NMS_WAVES
 #define TM_CAND MHIP_TILE_MAX_CAND
-#define TM_CHUNK 64
-#define TM_SUBS (TM_THREADS / TM_CHUNK) // threads that share a row's bucket
-#define TM_BUCKETS 128
-#define TM_MAXD 1000
+#define TM_CHUNK NMS_CHUNK
+#define TM_BUCKETS NMS_BUCKETS
 #define TM_WORDS (TM_CAND / 32)         // 32-bit words of a matrix row
 
 // byte offsets of the kernel's LDS arrays
@@ -74,10 +69,10 @@ __global__ __launch_bounds__(256) void tile_rois_kernel(const mhip_tile_t p) {
     }
     if (i >= slots) return;
     const int c = i / p.n_tiles, t = i - c * p.n_tiles;
-    tile_roi_t r;
+    roi_t r;
     r.frame = c; r.det = t;
     r.x0 = p.tiles[t].x0; r.y0 = p.tiles[t].y0; r.x1 = p.tiles[t].x1; r.y1 = p.tiles[t].y1;
-    ((tile_roi_t *)p.rois)[i] = r;
+    ((roi_t *)p.rois)[i] = r;
 }
 
 __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const mhip_tile_t p) {
@@ -93,11 +88,11 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const mhip_tile_
     int *bstart = (int *)(sm + TM_OFF_BSTART), *bfill = (int *)(sm + TM_OFF_BFILL), *tstart = (int *)(sm + TM_OFF_TSTART);
     int *wave_cnt = (int *)(sm + TM_OFF_WAVE), *stat = (int *)(sm + TM_OFF_STAT);
 
-    const int cam = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int cam = blockIdx.x, tid = threadIdx.x;
     const int T = p.n_tiles;
-    const tile_det_t *lists = (const tile_det_t *)p.dets + (size_t)cam * T * p.max_det;
-    tile_det_t *out = (tile_det_t *)p.out + (size_t)cam * TM_MAXD;
-    tile_src_t *org = (tile_src_t *)p.origins + (size_t)cam * TM_MAXD;
+    const det_t *lists = (const det_t *)p.dets + (size_t)cam * T * p.max_det;
+    det_t *out = (det_t *)p.out + (size_t)cam * MAXD;
+    tile_src_t *org = (tile_src_t *)p.origins + (size_t)cam * MAXD;
 
     // ---- quota: the gather slots [tstart[t], tstart[t + 1]) are the first entries of tile t's list
     if (tid == 0) {
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const mhip_tile_
         if (s < M) {
             while (tstart[t + 1] <= s) t++; // (empty tiles are stepped over; t < T because s < tstart[T])
             i = s - tstart[t];
-            const tile_det_t d = lists[(size_t)t * p.max_det + i];
+            const det_t d = lists[(size_t)t * p.max_det + i];
             const mhip_tile_geom_t g = p.tiles[t];
             if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf)) || !(d.w > 0.0f) || !(d.h > 0.0f)) {
                 atomicAdd(&stat[1], 1);
@@ -145,23 +140,19 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const mhip_tile_
                 }
             }
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wv] = __popcll(m);
-        __syncthreads();
-        int off = n;
-        for (int w = 0; w < wv; w++) off += wave_cnt[w];
-        const int k = off + __popcll(m & ((1ull << lane) - 1ull));
+        int step;
+        const int k = n + block_rank<TM_WAVES>(keep, wave_cnt, step);
         if (keep) { // k < TM_CAND: at most M entries are kept
             bx[k] = X; by[k] = Y; bw[k] = Wd; bh[k] = Hd; bconf[k] = conf; bc[k] = cls;
             bdet[k] = (unsigned short)i; btile[k] = (unsigned char)t;
         }
-        for (int w = 0; w < TM_WAVES; w++) n += wave_cnt[w];
-        __syncthreads();
+        n += step;
+        __syncthreads(); // wave_cnt is rewritten by the next step
     }
     if (n == 0) { // uniform
-        const tile_det_t zd = {0, 0, 0, 0, 0, 0};
+        const det_t zd = {0, 0, 0, 0, 0, 0};
         const tile_src_t zs = {0, 0};
-        for (int j = tid; j < TM_MAXD; j += TM_THREADS) { out[j] = zd; org[j] = zs; }
+        for (int j = tid; j < MAXD; j += TM_THREADS) { out[j] = zd; org[j] = zs; }
         if (tid == 0) {
             const tile_stats_t st = {0, stat[0], stat[1], stat[2], 0, 0};
             ((tile_stats_t *)p.stats)[cam] = st;
@@ -176,126 +167,51 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const mhip_tile_
         for (int r = tid; r < P; r += TM_THREADS)
             keys[r] = r < n ? ((unsigned long long)tile_ord(bconf[r]) << 11) | (unsigned)(TM_CAND - 1 - r) : 0ull;
         __syncthreads();
-        for (int k = 2; k <= P; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < (P >> 1); t += TM_THREADS) {
-                    const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                    const unsigned long long a = keys[lo], b = keys[hi];
-                    const bool desc = (lo & k) == 0;
-                    if (desc ? a < b : a > b) { keys[lo] = b; keys[hi] = a; }
-                }
-                __syncthreads();
-            }
+        bitonic_sort_desc(keys, P);
         for (int r = tid; r < n; r += TM_THREADS) perm[r] = (unsigned short)(TM_CAND - 1 - (int)(keys[r] & (TM_CAND - 1)));
     }
     if (tid < TM_BUCKETS) bfill[tid] = 0;
     __syncthreads();
-    // ---- class buckets over the sorted slots (class & 127, the exact class is still compared); one bucket when every pair counts
-    for (int j = tid; j < n; j += TM_THREADS) atomicAdd(&bfill[p.agnostic ? 0 : (unsigned)bc[perm[j]] & (TM_BUCKETS - 1)], 1);
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int b = 0; b < TM_BUCKETS; b++) { bstart[b] = acc; acc += bfill[b]; bfill[b] = 0; }
-        bstart[TM_BUCKETS] = acc;
-    }
-    __syncthreads();
-    for (int j = tid; j < n; j += TM_THREADS) {
-        const int b = p.agnostic ? 0 : (unsigned)bc[perm[j]] & (TM_BUCKETS - 1);
-        blist[bstart[b] + atomicAdd(&bfill[b], 1)] = (unsigned short)j;
-    }
-    __syncthreads();
-    const int nw = (n + 63) >> 6;
-    unsigned long long removed = 0; // wave 0: lane w (< 32) holds word w of the removed set
-    for (int i0 = 0; i0 < n; i0 += TM_CHUNK) {
-        const int rows = n - i0 < TM_CHUNK ? n - i0 : TM_CHUNK;
-        for (int k = tid; k < TM_CHUNK * TM_WORDS; k += TM_THREADS) mask[k] = 0;
-        __syncthreads();
-        {
-            const int r = tid / TM_SUBS, sub = tid % TM_SUBS, i = i0 + r;
-            if (r < rows) {
-                const int a = perm[i];
-                const float xi = bx[a], yi = by[a], wi = bw[a], hi = bh[a];
-                const int ci = bc[a], ti = btile[a];
-                const float ax1 = xi - wi / 2, ay1 = yi - hi / 2, ax2 = xi + wi / 2, ay2 = yi + hi / 2;
-                const float aarea = wi * hi;
-                const int b = p.agnostic ? 0 : (unsigned)ci & (TM_BUCKETS - 1);
-                for (int e = bstart[b] + sub; e < bstart[b + 1]; e += TM_SUBS) {
-                    const int j = blist[e];
-                    if (j <= i) continue;
-                    const int q = perm[j];
-                    if (btile[q] == ti || (!p.agnostic && bc[q] != ci)) continue;
-                    const float xj = bx[q], yj = by[q], wj = bw[q], hj = bh[q];
-                    float x1 = fmaxf(ax1, xj - wj / 2);
-                    float y1 = fmaxf(ay1, yj - hj / 2);
-                    float x2 = fminf(ax2, xj + wj / 2);
-                    float y2 = fminf(ay2, yj + hj / 2);
-                    float iw = fmaxf(0.0f, x2 - x1), ih = fmaxf(0.0f, y2 - y1);
-                    float inter = iw * ih;
-                    float barea = wj * hj;
-                    float den;
-                    if (p.ios) den = fminf(aarea, barea);
-                    else {
-                        den = aarea + barea;
-                        den = den - inter;
-                    }
-                    den = den + 1e-6f;
-                    if (inter / den > p.thresh) atomicOr(&mask[r * TM_WORDS + (j >> 5)], 1u << (j & 31));
-                }
+    // ---- class buckets over the sorted slots (the exact class is still compared); one bucket when every pair counts
+    const auto bucket_of = [&](const int j) { return p.agnostic ? 0 : class_bucket(bc[perm[j]]); };
+    class_buckets(n, bstart, bfill, blist, bucket_of);
+    // ---- pairs: different tiles, same class (or agnostic), IoU or IoS above the threshold
+    struct row_t { box_edges_t box; int cls, tile; };
+    greedy_suppress<TM_CAND / 64>(
+        n, mask, bstart, blist, removed_s, bucket_of,
+        [&](const int i) {
+            const int a = perm[i];
+            return row_t{box_edges(bx[a], by[a], bw[a], bh[a]), bc[a], btile[a]};
+        },
+        [&](const row_t &a, const int j) {
+            const int q = perm[j];
+            if (btile[q] == a.tile || (!p.agnostic && bc[q] != a.cls)) return false;
+            float inter, barea, den;
+            box_iou_terms(a.box, bx[q], by[q], bw[q], bh[q], inter, barea);
+            if (p.ios) den = fminf(a.box.area, barea);
+            else {
+                den = a.box.area + barea;
+                den = den - inter;
             }
-        }
-        __syncthreads();
-        if (tid < 64) {
-            // the greedy walk: a dependent chain of `rows` steps whose matrix rows do not depend on it, so they are fetched 16 at a time ahead of
-            // the steps that use them, and a removed row is skipped by a select, not a branch (sort_nms_kernel's walk, 32 words wide)
-            const int wl = tid < 32 ? tid : 31, c = i0 >> 6; // rows i0.. live in word c of the removed set
-            for (int r0 = 0; r0 < rows; r0 += 16) {
-                unsigned long long mrow[16];
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int r = r0 + k < TM_CHUNK ? r0 + k : TM_CHUNK - 1;
-                    mrow[k] = *(const unsigned long long *)&mask[r * TM_WORDS + 2 * wl];
-                }
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int r = r0 + k;
-                    const unsigned half = r < 32 ? __builtin_amdgcn_readlane((unsigned)removed, c) : __builtin_amdgcn_readlane((unsigned)(removed >> 32), c);
-                    const bool dead = (half >> (r & 31)) & 1u; // a removed candidate removes nothing
-                    removed |= (dead || tid >= nw || r >= rows) ? 0ull : mrow[k];
-                }
-            }
-        }
-        __syncthreads(); // the next chunk overwrites the bit matrix
-    }
-    if (tid < 32) removed_s[tid] = tid < nw ? removed : ~0ull;
-    __syncthreads();
-    // ---- the survivors in sorted order, the first 1000 of them
-    int total = 0;
-    for (int base = 0; base < n; base += TM_THREADS) {
-        const int idx = base + tid;
-        const bool keep = idx < n && !((removed_s[idx >> 6] >> (idx & 63)) & 1ull);
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wv] = __popcll(m);
-        __syncthreads();
-        int off = total;
-        for (int w = 0; w < wv; w++) off += wave_cnt[w];
-        const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && slot < TM_MAXD) {
-            const int a = perm[idx];
-            tile_det_t d;
-            d.x = bx[a]; d.y = by[a]; d.w = bw[a]; d.h = bh[a]; d.conf = bconf[a]; d.cls = bc[a];
-            out[slot] = d;
-            tile_src_t o;
-            o.tile = btile[a]; o.det = bdet[a];
-            org[slot] = o;
-        }
-        for (int w = 0; w < TM_WAVES; w++) total += wave_cnt[w];
-        __syncthreads();
-    }
-    const int kept = min(total, TM_MAXD);
+            den = den + 1e-6f;
+            return inter / den > p.thresh;
+        });
+    // ---- the survivors in sorted order, the first 1000 of them (the count goes on: the stats need it)
+    const int total = compact_survivors(n, removed_s, wave_cnt, [&](const int idx, const int slot) {
+        if (slot >= MAXD) return;
+        const int a = perm[idx];
+        det_t d;
+        d.x = bx[a]; d.y = by[a]; d.w = bw[a]; d.h = bh[a]; d.conf = bconf[a]; d.cls = bc[a];
+        out[slot] = d;
+        tile_src_t o;
+        o.tile = btile[a]; o.det = bdet[a];
+        org[slot] = o;
+    });
+    const int kept = min(total, MAXD);
     {
-        const tile_det_t zd = {0, 0, 0, 0, 0, 0};
+        const det_t zd = {0, 0, 0, 0, 0, 0};
         const tile_src_t zs = {0, 0};
-        for (int j = kept + tid; j < TM_MAXD; j += TM_THREADS) { out[j] = zd; org[j] = zs; }
+        for (int j = kept + tid; j < MAXD; j += TM_THREADS) { out[j] = zd; org[j] = zs; }
     }
     if (tid == 0) {
         const tile_stats_t st = {n, stat[0], stat[1], stat[2], n - total, total - kept};
@@ -321,7 +237,7 @@ extern "C" int mhip_tile_rois(const mhip_tile_t *p) {
 
 extern "C" int mhip_tile_merge(const mhip_tile_t *p) {
     if (!tile_table_ok(p) || !p->dets || !p->counts || !p->out || !p->out_counts || !p->origins || !p->stats) return -1;
-    if (p->max_det < 1 || p->max_det > TM_MAXD || p->quota < 1 || (long long)p->n_tiles * p->quota > TM_CAND) return -1;
+    if (p->max_det < 1 || p->max_det > MAXD || p->quota < 1 || (long long)p->n_tiles * p->quota > TM_CAND) return -1;
     if (!(p->thresh >= 0.0f) || !(p->edge_margin >= 0.0f)) return -1;
     static bool attr = false;
     if (!attr) {

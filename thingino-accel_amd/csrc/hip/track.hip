@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 #pragma clang fp contract(off)
 
@@ -31,30 +32,11 @@ extern "C" int mhip_check(hipError_t e, const char *what);
 #define TK_THREADS 512
 #define TK_WAVES (TK_THREADS / 64)
 
-struct tk_det_t { float x, y, w, h, conf; int cls; };                                          // mars_det_t
-struct tk_cls_t { int cls; float score; };                                                     // mars_cls_t
-struct tk_out_t { int id, hits; };                                                             // mars_track_t
-struct tk_state_t { int id, cls, hits, miss; float x, y, w, h, vx, vy; tk_cls_t ident; };      // mars_track_state_t
-static_assert(sizeof(tk_det_t) == 24 && sizeof(tk_out_t) == 8 && sizeof(tk_state_t) == 48, "record sizes of include/mars_hip.h");
+struct tk_out_t { int id, hits; };                                                        // mars_track_t
+struct tk_state_t { int id, cls, hits, miss; float x, y, w, h, vx, vy; cls_t ident; };    // mars_track_state_t
+static_assert(sizeof(tk_out_t) == 8 && sizeof(tk_state_t) == 48, "record sizes of include/mars_hip.h");
 
 __device__ __forceinline__ bool tk_finite(const float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// the suppress loop's expression of yolo_tail.hip: a = the track at its prediction, b = the detection
-__device__ __forceinline__ float tk_iou(const float ax, const float ay, const float aw, const float ah, const float bx, const float by,
-                                        const float bw, const float bh) {
-    const float ax1 = ax - aw / 2, ay1 = ay - ah / 2, ax2 = ax + aw / 2, ay2 = ay + ah / 2;
-    const float x1 = fmaxf(ax1, bx - bw / 2);
-    const float y1 = fmaxf(ay1, by - bh / 2);
-    const float x2 = fminf(ax2, bx + bw / 2);
-    const float y2 = fminf(ay2, by + bh / 2);
-    const float iw = fmaxf(0.0f, x2 - x1), ih = fmaxf(0.0f, y2 - y1);
-    const float inter = iw * ih;
-    const float aarea = aw * ah, barea = bw * bh;
-    float uni = aarea + barea;
-    uni = uni - inter;
-    uni = uni + 1e-6f;
-    return inter / uni;
-}
 
 struct tk_lds_t {
     // the table, one array per field
@@ -81,32 +63,19 @@ struct tk_lds_t {
 
 // rank of this thread among the threads with `flag`, in thread order, and their number.  Every thread of the workgroup calls it.
 __device__ __forceinline__ int tk_scan(const bool flag, int *wsum, int &total) {
-    const unsigned long long b = __ballot(flag);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
     __syncthreads(); // (the previous call's readers of wsum are through; what the caller wrote before is visible after)
-    if (lane == 0) wsum[w] = __popcll(b);
-    __syncthreads();
-    int base = 0, t = 0;
-#pragma unroll
-    for (int k = 0; k < TK_WAVES; k++) {
-        const int c = wsum[k];
-        base += k < w ? c : 0;
-        t += c;
-    }
-    total = t;
-    return base + before;
+    return block_rank<TK_WAVES>(flag, wsum, total);
 }
 
 // the first TK_CAND members of a set into the candidate arrays, in index order; -> their number.  low: the set L, otherwise H
-__device__ int tk_candidates(tk_lds_t &s, const mhip_track_t &p, const tk_det_t *d, const int n, const bool low) {
+__device__ int tk_candidates(tk_lds_t &s, const mhip_track_t &p, const det_t *d, const int n, const bool low) {
     const int tid = threadIdx.x;
     if (tid < TK_CAND) s.cfree[tid] = 0;
     int running = 0;
     for (int c0 = 0; c0 < n; c0 += TK_THREADS) { // (n is the same in every thread)
         const int i = c0 + tid;
         bool in = false;
-        tk_det_t v;
+        det_t v;
         if (i < n) {
             v = d[i];
             const bool gate = p.cls_count == 0 || (v.cls >= p.cls_first && (long long)v.cls < (long long)p.cls_first + p.cls_count);
@@ -139,12 +108,12 @@ __device__ void tk_associate(tk_lds_t &s, const int nc, const float thresh, cons
         if (track_side) {
             int pick = -1;
             if (s.tfree[me]) {
-                const float ax = s.px[me], ay = s.py[me], aw = s.w[me], ah = s.h[me];
+                const box_edges_t a = box_edges(s.px[me], s.py[me], s.w[me], s.h[me]); // the track at its prediction
                 const int acls = s.cls[me];
                 float best = 0.0f;
                 for (int j = 0; j < nc; j++) {
                     if (!s.cfree[j] || !(any_class || s.ccls[j] == acls)) continue;
-                    const float iou = tk_iou(ax, ay, aw, ah, s.cx[j], s.cy[j], s.cw[j], s.ch[j]);
+                    const float iou = box_iou(a, s.cx[j], s.cy[j], s.cw[j], s.ch[j]);
                     if (iou >= thresh && (pick < 0 || iou > best)) { best = iou; pick = j; } // ties: the lower index stays
                 }
             }
@@ -157,7 +126,7 @@ __device__ void tk_associate(tk_lds_t &s, const int nc, const float thresh, cons
                 float best = 0.0f;
                 for (int t = 0; t < TK_SLOTS; t++) {
                     if (!s.tfree[t] || !(any_class || s.cls[t] == bcls)) continue;
-                    const float iou = tk_iou(s.px[t], s.py[t], s.w[t], s.h[t], bx, by, bw, bh);
+                    const float iou = box_iou(box_edges(s.px[t], s.py[t], s.w[t], s.h[t]), bx, by, bw, bh);
                     if (iou >= thresh && (pick < 0 || iou > best)) { best = iou; pick = t; } // ties: the lower slot stays
                 }
             }
@@ -203,8 +172,8 @@ __global__ __launch_bounds__(TK_THREADS) void track_kernel(const mhip_track_t p)
     __syncthreads();
     for (int t = 0; t < p.steps; t++) {
         const size_t f = p.stream_major ? (size_t)b * p.steps + t : (size_t)t * p.streams + b;
-        const tk_det_t *d = (const tk_det_t *)p.dets + f * p.max_det;
-        const tk_cls_t *idn = p.idents ? (const tk_cls_t *)p.idents + f * p.max_det : nullptr;
+        const det_t *d = (const det_t *)p.dets + f * p.max_det;
+        const cls_t *idn = p.idents ? (const cls_t *)p.idents + f * p.max_det : nullptr;
         tk_out_t *o = (tk_out_t *)p.out + f * p.max_det;
         int n = p.counts[f];
         n = n < 0 ? 0 : n > p.max_det ? p.max_det : n;
@@ -235,7 +204,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_kernel(const mhip_track_t p)
         if (live) {
             const int i = s.det[tid];
             if (i >= 0) {
-                const tk_det_t v = d[i];
+                const det_t v = d[i];
                 const float dx = v.x - s.x[tid], dy = v.y - s.y[tid];
                 if (s.hits[tid] == 1) { s.vx[tid] = dx; s.vy[tid] = dy; }
                 else { s.vx[tid] = (s.vx[tid] + dx) * 0.5f; s.vy[tid] = (s.vy[tid] + dy) * 0.5f; }
@@ -243,7 +212,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_kernel(const mhip_track_t p)
                 s.hits[tid] += 1;
                 s.miss[tid] = 0;
                 if (idn) {
-                    const tk_cls_t e = idn[i];
+                    const cls_t e = idn[i];
                     if (e.cls >= 0 && (s.icls[tid] < 0 || e.score >= s.iscore[tid])) { s.icls[tid] = e.cls; s.iscore[tid] = e.score; }
                 }
                 o[i] = tk_out_t{s.id[tid], s.hits[tid]}; // (behind the {-1, 0} of the loop above: the scans' barriers lie between)
@@ -264,11 +233,11 @@ __global__ __launch_bounds__(TK_THREADS) void track_kernel(const mhip_track_t p)
         const int fits = nborn < nfree ? nborn : nfree;
         if (wants && bi < fits) {
             const int slot = s.freelist[bi], i = s.hidx[tid];
-            const tk_det_t v = d[i];
+            const det_t v = d[i];
             const int id = (int)((unsigned)s.next_id + 1u + (unsigned)bi);
             s.id[slot] = id; s.cls[slot] = v.cls; s.hits[slot] = 1; s.miss[slot] = 0;
             s.x[slot] = v.x; s.y[slot] = v.y; s.w[slot] = v.w; s.h[slot] = v.h; s.vx[slot] = 0.0f; s.vy[slot] = 0.0f;
-            tk_cls_t e = tk_cls_t{-1, 0.0f};
+            cls_t e = cls_t{-1, 0.0f};
             if (idn) e = idn[i];
             s.icls[slot] = e.cls; s.iscore[slot] = e.score;
             o[i] = tk_out_t{id, 1};

@@ -26,29 +26,22 @@
 #include <string.h>
 
 #include "../mhip.h"
+#include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-#define MAXD 1000
 #define ROW 85
 #define NCLS 80
 #define CONF_MIN 0.25f
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-struct det_rec {
-    float x, y, w, h, conf;
-    int cls;
-};
 
 // ------------------------------------------------------------------ decode
 __global__ __launch_bounds__(256) void decode_kernel(const mhip_detect_t p) {
     __shared__ int wave_cnt[4];
     __shared__ int run_total;
     const int f = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    det_rec *dets = (det_rec *)p.dets + (size_t)f * MAXD;
+    const int tid = threadIdx.x;
+    det_t *dets = (det_t *)p.dets + (size_t)f * MAXD;
     if (tid == 0) run_total = 0;
     __syncthreads();
     int total = 0;
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const mhip_detect_t p) {
         for (int base = 0; base < np && total < MAXD; base += 256) {
             const int r = base + tid;
             bool cand = false;
-            det_rec d;
+            det_t d;
             if (r < np) {
                 // padded pixel rows (the model wrote its 255-channel rows at a 256-byte pitch): prediction r is anchor
                 // r % apx of pixel r / apx; a channel count that is no multiple of 85 takes the per-byte mapping
@@ -118,17 +111,11 @@ __global__ __launch_bounds__(256) void decode_kernel(const mhip_detect_t p) {
                     }
                 }
             }
-            unsigned long long m = __ballot(cand);
-            int before = __popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_cnt[wv] = __popcll(m);
-            __syncthreads();
-            int off = total;
-            for (int w = 0; w < wv; w++) off += wave_cnt[w];
-            int slot = off + before;
+            int step;
+            const int slot = total + block_rank<4>(cand, wave_cnt, step);
             if (cand && slot < MAXD) dets[slot] = d;
-            int step = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
             total += step;
-            __syncthreads();
+            __syncthreads(); // wave_cnt is rewritten by the next step
         }
     }
     if (total > MAXD) total = MAXD;
@@ -166,14 +153,10 @@ __global__ __launch_bounds__(256) void decode_kernel(const mhip_detect_t p) {
 // evaluated 64 rows at a time, inside class buckets, into an 8 KB bit matrix; wave 0 then walks those rows
 // greedily OR-ing them into the removed set (suppressed boxes suppress nothing) -- exactly the reference's
 // double loop.  The float expression order of the IoU is the reference's.
-#define NMS_THREADS 512
-#define NMS_SUBS (NMS_THREADS / NMS_CHUNK) // threads that share a row's bucket
-#define NMS_CHUNK 64
-#define NMS_BUCKETS 128
 // cand_pred / kept_pred (both or neither; NULL = nothing is written): the origin of every record.  cand_pred[f][r] is the prediction index
 // of candidate r as the decode wrote it; the compaction writes kept_pred[f][slot] = cand_pred[f][sperm[j]] for survivor j of the sorted
 // order -- sperm[] is final on every path of the sort (bitonic, tie-queue replay, the NaN loop) and nothing overwrites it afterwards.
-__global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int *counts, float thresh, const int *cand_pred, int *kept_pred) {
+__global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_t *all, int *counts, float thresh, const int *cand_pred, int *kept_pred) {
     __shared__ float bx[1024], by[1024], bw[1024], bh[1024], bconf[1024];
     __shared__ int bc[1024];
     __shared__ unsigned short blist[1024];              // box indices grouped by class bucket
@@ -184,8 +167,8 @@ __global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int
     __shared__ unsigned short sperm[1024];              // sorted slot -> original index
     __shared__ int flags[2];                            // [0] a NaN confidence in this frame, [1] a tie in this frame
 
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    det_rec *dets = all + (size_t)f * MAXD;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    det_t *dets = all + (size_t)f * MAXD;
     int n = counts[f];
     if (n > MAXD) n = MAXD;
     if (n <= 0) return;
@@ -224,16 +207,7 @@ __global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int
             __syncthreads();
             for (int r = tid; r < n; r += NMS_THREADS) sperm[r] = (unsigned short)(1023 - (int)(keys[r] & 1023));
         } else {
-            for (int k = 2; k <= P; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int t = tid; t < (P >> 1); t += NMS_THREADS) {
-                        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                        const unsigned long long a = keys[lo], b = keys[hi];
-                        const bool desc = (lo & k) == 0;
-                        if (desc ? a < b : a > b) { keys[lo] = b; keys[hi] = a; }
-                    }
-                    __syncthreads();
-                }
+            bitonic_sort_desc(keys, P);
             // slots of untied elements are final; tie groups are replayed below
             bool member[2] = {false, false};
             for (int q = 0, r = tid; r < n; r += NMS_THREADS, q++) {
@@ -297,108 +271,31 @@ __global__ __launch_bounds__(NMS_THREADS) void sort_nms_kernel(det_rec *all, int
     }
     if (tid < NMS_BUCKETS) bfill[tid] = 0;
     for (int j = tid; j < n; j += NMS_THREADS) { // in the sorted order
-        det_rec d = dets[sperm[j]];
+        det_t d = dets[sperm[j]];
         bx[j] = d.x; by[j] = d.y; bw[j] = d.w; bh[j] = d.h; bc[j] = d.cls; bconf[j] = d.conf;
     }
     __syncthreads();
     // Only boxes of the same class can suppress each other (reference :118), so the pair relation is evaluated
-    // inside class buckets (class & 127; the exact class is still compared): ~n^2/160 IoUs instead of n^2/2 compares.
-    for (int j = tid; j < n; j += NMS_THREADS) atomicAdd(&bfill[(unsigned)bc[j] & (NMS_BUCKETS - 1)], 1);
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int b = 0; b < NMS_BUCKETS; b++) { bstart[b] = acc; acc += bfill[b]; bfill[b] = 0; }
-        bstart[NMS_BUCKETS] = acc;
-    }
-    __syncthreads();
-    for (int j = tid; j < n; j += NMS_THREADS) {
-        const int b = (unsigned)bc[j] & (NMS_BUCKETS - 1);
-        blist[bstart[b] + atomicAdd(&bfill[b], 1)] = (unsigned short)j;
-    }
-    __syncthreads();
-    const int nw = (n + 63) >> 6;
-    unsigned long long removed = 0; // wave 0: lane w (< 16) holds word w of the removed set
-    for (int i0 = 0; i0 < n; i0 += NMS_CHUNK) {
-        const int rows = n - i0 < NMS_CHUNK ? n - i0 : NMS_CHUNK;
-        for (int k = tid; k < NMS_CHUNK * 32; k += NMS_THREADS) ((unsigned int *)mask)[k] = 0;
-        __syncthreads();
-        {
-            const int r = tid / NMS_SUBS, sub = tid % NMS_SUBS, i = i0 + r;
-            if (r < rows) {
-                const float xi = bx[i], yi = by[i], wi = bw[i], hi = bh[i];
-                const int ci = bc[i];
-                const float ax1 = xi - wi / 2, ay1 = yi - hi / 2, ax2 = xi + wi / 2, ay2 = yi + hi / 2;
-                const float aarea = wi * hi;
-                const int b = (unsigned)ci & (NMS_BUCKETS - 1);
-                for (int e = bstart[b] + sub; e < bstart[b + 1]; e += NMS_SUBS) {
-                    const int j = blist[e];
-                    if (j <= i || bc[j] != ci) continue;
-                    const float xj = bx[j], yj = by[j], wj = bw[j], hj = bh[j];
-                    float x1 = fmaxf(ax1, xj - wj / 2);
-                    float y1 = fmaxf(ay1, yj - hj / 2);
-                    float x2 = fminf(ax2, xj + wj / 2);
-                    float y2 = fminf(ay2, yj + hj / 2);
-                    float iw = fmaxf(0.0f, x2 - x1), ih = fmaxf(0.0f, y2 - y1);
-                    float inter = iw * ih;
-                    float barea = wj * hj;
-                    float uni = aarea + barea;
-                    uni = uni - inter;
-                    uni = uni + 1e-6f;
-                    if (inter / uni > thresh) atomicOr(&mask[r][j >> 5], 1u << (j & 31));
-                }
-            }
-        }
-        __syncthreads();
-        if (tid < 64) {
-            // the greedy walk is a dependent chain of `rows` steps; its matrix rows do not depend on it, so they are fetched
-            // 16 at a time ahead of the steps that use them (one LDS latency per 16 rows instead of one per row) and a
-            // suppressed row is skipped by a select, not a branch
-            const int wl = tid < 16 ? tid : 15, c = i0 >> 6; // lane w holds word w of the removed set; rows i0.. live in word c
-            for (int r0 = 0; r0 < rows; r0 += 16) {
-                unsigned long long mrow[16];
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int r = r0 + k < NMS_CHUNK ? r0 + k : NMS_CHUNK - 1;
-                    mrow[k] = *(const unsigned long long *)&mask[r][2 * wl];
-                }
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int r = r0 + k; // bit r of word c: rows >= `rows` hold an all-zero matrix row
-                    const unsigned half = r < 32 ? __builtin_amdgcn_readlane((unsigned)removed, c) : __builtin_amdgcn_readlane((unsigned)(removed >> 32), c);
-                    const bool dead = (half >> (r & 31)) & 1u; // suppressed boxes suppress nothing
-                    removed |= (dead || tid >= nw || r >= rows) ? 0ull : mrow[k];
-                }
-            }
-        }
-        __syncthreads(); // the next chunk overwrites the bit matrix
-    }
-    if (tid < 16) removed_s[tid] = tid < nw ? removed : ~0ull;
-    __syncthreads();
-    // compact the survivors in order (a record only ever moves to a lower slot, 256 at a time)
-    int total = 0;
-    for (int base = 0; base < n; base += NMS_THREADS) {
-        const int idx = base + tid;
-        const bool keep = idx < n && !((removed_s[idx >> 6] >> (idx & 63)) & 1ull);
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wv] = __popcll(m);
-        __syncthreads();
-        int off = total;
-        for (int w = 0; w < wv; w++) off += wave_cnt[w];
-        const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep) {
-            det_rec k;
-            k.x = bx[idx]; k.y = by[idx]; k.w = bw[idx]; k.h = bh[idx]; k.conf = bconf[idx]; k.cls = bc[idx];
-            dets[slot] = k;
-            if (kept_pred) kept_pred[(size_t)f * MAXD + slot] = cand_pred[(size_t)f * MAXD + sperm[idx]];
-        }
-        for (int w = 0; w < NMS_THREADS / 64; w++) total += wave_cnt[w];
-        __syncthreads();
-    }
+    // inside class buckets (the exact class is still compared): ~n^2/160 IoUs instead of n^2/2 compares.
+    const auto bucket_of = [&](const int j) { return class_bucket(bc[j]); };
+    class_buckets(n, bstart, bfill, blist, bucket_of);
+    struct row_t { box_edges_t box; int cls; };
+    greedy_suppress<16>(
+        n, &mask[0][0], bstart, blist, removed_s, bucket_of,
+        [&](const int i) { return row_t{box_edges(bx[i], by[i], bw[i], bh[i]), bc[i]}; },
+        [&](const row_t &a, const int j) { return bc[j] == a.cls && box_iou(a.box, bx[j], by[j], bw[j], bh[j]) > thresh; });
+    // compact the survivors in order (a record only ever moves to a lower slot)
+    const int total = compact_survivors(n, removed_s, wave_cnt, [&](const int idx, const int slot) {
+        det_t k;
+        k.x = bx[idx]; k.y = by[idx]; k.w = bw[idx]; k.h = bh[idx]; k.conf = bconf[idx]; k.cls = bc[idx];
+        dets[slot] = k;
+        if (kept_pred) kept_pred[(size_t)f * MAXD + slot] = cand_pred[(size_t)f * MAXD + sperm[idx]];
+    });
     if (tid == 0) counts[f] = total;
 }
 
 extern "C" void mhip_tail_release(void) {} // (the systolic sort's permutation buffer lived here until round 3)
-static int launch_sort_nms(det_rec *dets, int *counts, int frames, float thresh, const int *cand_pred = nullptr, int *kept_pred = nullptr) {
+static int launch_sort_nms(det_t *dets, int *counts, int frames, float thresh, const int *cand_pred = nullptr, int *kept_pred = nullptr) {
     if (!cand_pred || !kept_pred) cand_pred = nullptr, kept_pred = nullptr;
     hipLaunchKernelGGL(sort_nms_kernel, dim3(frames), dim3(NMS_THREADS), 0, mhip_stream_native(), dets, counts, thresh, cand_pred, kept_pred);
     return mhip_check(hipGetLastError(), "sort + nms");
@@ -411,12 +308,12 @@ extern "C" int mhip_detect(const mhip_detect_t *p) {
     hipLaunchKernelGGL(decode_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), *p);
     int rc = mhip_check(hipGetLastError(), "decode");
     if (rc || !p->do_nms) return rc;
-    return launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
+    return launch_sort_nms((det_t *)p->dets, p->counts, p->frames, p->nms_thresh);
 }
 
 extern "C" int mhip_nms_only(void *dets_dev, int *count_dev, int n, float thresh) {
     if (!dets_dev || !count_dev || n < 0 || n > MAXD) return -1;
-    return launch_sort_nms((det_rec *)dets_dev, count_dev, 1, thresh);
+    return launch_sort_nms((det_t *)dets_dev, count_dev, 1, thresh);
 }
 
 // ------------------------------------------------------------ anchor heads
@@ -439,7 +336,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void heads_decode_kernel(const mhip_
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (int i = tid; i < p.nheads * 256; i += HEADS_THREADS) sig_s[i >> 8][i & 255] = p.sig[i];
     __syncthreads();
-    det_rec *dets = (det_rec *)p.dets + (size_t)f * MAXD;
+    det_t *dets = (det_t *)p.dets + (size_t)f * MAXD;
     const float conf = p.conf;
     int total = 0;
     for (int hd = 0; hd < p.nheads && total < MAXD; hd++) {
@@ -521,7 +418,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void heads_decode_kernel(const mhip_
                         const int8_t *row = ab + (size_t)cell * ps;
                         const float s0 = sg[row[0] + 128], s1 = sg[row[cs] + 128];
                         const float s2 = __fmul_rn(sg[row[2 * cs] + 128], 2.0f), s3 = __fmul_rn(sg[row[3 * cs] + 128], 2.0f);
-                        det_rec d;
+                        det_t d;
                         d.x = __fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(s0, 2.0f), 0.5f), (float)gx), fstride);
                         d.y = __fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(s1, 2.0f), 0.5f), (float)gy), fstride);
                         d.w = __fmul_rn(__fmul_rn(s2, s2), aw);
@@ -546,12 +443,12 @@ __global__ __launch_bounds__(HEADS_THREADS) void heads_decode_kernel(const mhip_
 
 // the kept boxes back through the letterbox of the image front-end (after NMS: suppression sees the network's coordinates)
 // pre != NULL: the records as they were before the mapping (graph-input pixels) are kept in pre[frame][i] (the mask stage cuts by them)
-__global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int *counts, float px, float py, float rx, float ry, det_rec *pre) {
-    det_rec *d = all + (size_t)blockIdx.x * MAXD;
+__global__ __launch_bounds__(256) void heads_map_kernel(det_t *all, const int *counts, float px, float py, float rx, float ry, det_t *pre) {
+    det_t *d = all + (size_t)blockIdx.x * MAXD;
     int n = counts[blockIdx.x];
     if (n > MAXD) n = MAXD;
     for (int i = threadIdx.x; i < n; i += 256) {
-        det_rec r = d[i];
+        det_t r = d[i];
         if (pre) pre[(size_t)blockIdx.x * MAXD + i] = r;
         r.x = __fmul_rn(__fsub_rn(r.x, px), rx);
         r.y = __fmul_rn(__fsub_rn(r.y, py), ry);
@@ -579,34 +476,6 @@ __global__ __launch_bounds__(256) void heads_map_kernel(det_rec *all, const int 
 #define DFL_THREADS 256
 #define DFL_CELLS 4
 
-// the first maximum of 16 int8 bytes (classes c0 .. c0 + 15) folded into (bq, arg)
-__device__ __forceinline__ void dfl_argmax16(const v4i w, const int c0, int &bq, int &arg) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int d = w[j];
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int q = (d << (24 - 8 * b)) >> 24;
-            const bool gt = q > bq;
-            bq = gt ? q : bq;
-            arg = gt ? c0 + 4 * j + b : arg;
-        }
-    }
-}
-
-// one box side from its R bytes at q[i * cs]
-__device__ __forceinline__ float dfl_side(const int8_t *q, const int R, const int cs, const float *E) {
-    int m = -128;
-    for (int i = 0; i < R; i++) m = max(m, (int)q[(size_t)i * cs]);
-    float den = E[m - q[0]], num = 0.0f; // 0 * e_0 adds nothing to 0.0f
-    for (int i = 1; i < R; i++) {
-        const float e = E[m - q[(size_t)i * cs]];
-        den = __fadd_rn(den, e);
-        num = __fadd_rn(num, __fmul_rn((float)i, e));
-    }
-    return __fdiv_rn(num, den);
-}
-
 // ... reg_max 16 in a pixel row: the side is one 16-byte load
 __device__ __forceinline__ float dfl_side16(const int8_t *q, const float *E) {
     v4i w;
@@ -630,10 +499,10 @@ __device__ __forceinline__ float dfl_side16(const int8_t *q, const float *E) {
 __global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_heads_t p) {
     __shared__ float tab_s[4][512];
     __shared__ int wave_cnt[DFL_CELLS][DFL_THREADS / 64];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int f = blockIdx.x, tid = threadIdx.x;
     for (int i = tid; i < p.nheads * 512; i += DFL_THREADS) tab_s[i >> 9][i & 511] = p.tab[i];
     __syncthreads();
-    det_rec *dets = (det_rec *)p.dets + (size_t)f * MAXD;
+    det_t *dets = (det_t *)p.dets + (size_t)f * MAXD;
     const float conf = p.conf;
     const int R = p.reg_max;
     int total = 0, pred0 = 0; // pred0: the prediction index of this head's cell 0
@@ -648,71 +517,21 @@ __global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_
             int bq[DFL_CELLS], arg[DFL_CELLS];
             const int8_t *row[DFL_CELLS]; // a cell past the end reads the last cell's bytes and is dropped below
 #pragma unroll
-            for (int k = 0; k < DFL_CELLS; k++) {
-                bq[k] = -129;
-                arg[k] = 0;
-                row[k] = cb + (size_t)min(base + k * DFL_THREADS + tid, npix - 1) * cps;
-            }
-            if (ccs == 1 && nc == 80) {
-                v4i w[DFL_CELLS][5]; // 20 loads of 16 bytes in flight (any alignment is served)
-#pragma unroll
-                for (int k = 0; k < DFL_CELLS; k++)
-#pragma unroll
-                    for (int j = 0; j < 5; j++) __builtin_memcpy(&w[k][j], row[k] + 16 * j, 16);
-#pragma unroll
-                for (int k = 0; k < DFL_CELLS; k++)
-#pragma unroll
-                    for (int j = 0; j < 5; j++) dfl_argmax16(w[k][j], 16 * j, bq[k], arg[k]);
-            } else if (ccs == 1) {
-                const int n16 = nc >> 4; // whole 16-byte runs inside the row, then its last bytes one by one
-                for (int j = 0; j < n16; j++) {
-                    v4i w[DFL_CELLS];
-#pragma unroll
-                    for (int k = 0; k < DFL_CELLS; k++) __builtin_memcpy(&w[k], row[k] + 16 * j, 16);
-#pragma unroll
-                    for (int k = 0; k < DFL_CELLS; k++) dfl_argmax16(w[k], 16 * j, bq[k], arg[k]);
-                }
-                for (int c = n16 << 4; c < nc; c++) {
-                    int q[DFL_CELLS];
-#pragma unroll
-                    for (int k = 0; k < DFL_CELLS; k++) q[k] = row[k][c];
-#pragma unroll
-                    for (int k = 0; k < DFL_CELLS; k++)
-                        if (q[k] > bq[k]) { bq[k] = q[k]; arg[k] = c; }
-                }
-            } else {
-#pragma unroll 4
-                for (int c = 0; c < nc; c++) { // planes: a wave reads 64 consecutive bytes of plane c per load
-                    int q[DFL_CELLS];
-#pragma unroll
-                    for (int k = 0; k < DFL_CELLS; k++) q[k] = row[k][(size_t)c * ccs];
-#pragma unroll
-                    for (int k = 0; k < DFL_CELLS; k++)
-                        if (q[k] > bq[k]) { bq[k] = q[k]; arg[k] = c; }
-                }
-            }
-            // slots: candidates are numbered in cell order = (k, thread); one count per (k, wave)
+            for (int k = 0; k < DFL_CELLS; k++) row[k] = cb + (size_t)min(base + k * DFL_THREADS + tid, npix - 1) * cps;
+            dfl_class_walk<DFL_CELLS, true>(row, nc, ccs, bq, arg);
+            // slots: candidates are numbered in cell order = (k, thread)
             bool cand[DFL_CELLS];
             float cf[DFL_CELLS];
-            int before[DFL_CELLS];
+            int rank[DFL_CELLS], step;
 #pragma unroll
             for (int k = 0; k < DFL_CELLS; k++) {
                 cf[k] = sg[bq[k] + 128];
                 cand[k] = base + k * DFL_THREADS + tid < npix && cf[k] >= conf;
-                const unsigned long long m = __ballot(cand[k]);
-                before[k] = __popcll(m & ((1ull << lane) - 1ull));
-                if (lane == 0) wave_cnt[k][wv] = __popcll(m);
             }
-            __syncthreads();
+            block_rank<DFL_THREADS / 64, DFL_CELLS>(cand, wave_cnt, rank, step);
 #pragma unroll
             for (int k = 0; k < DFL_CELLS; k++) {
-                int slot = total + before[k];
-#pragma unroll
-                for (int w = 0; w < DFL_THREADS / 64; w++) {
-                    const int c = wave_cnt[k][w];
-                    if (w < wv) slot += c;
-                    total += c;
-                }
+                const int slot = total + rank[k];
                 if (!cand[k] || slot >= MAXD) continue;
                 const int cell = base + k * DFL_THREADS + tid, gy = cell / W, gx = cell - gy * W;
                 const int8_t *q = bb + (size_t)cell * bps;
@@ -725,7 +544,7 @@ __global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_
                 }
                 const float ax = __fadd_rn((float)gx, 0.5f), ay = __fadd_rn((float)gy, 0.5f);
                 const float x1 = __fsub_rn(ax, dist[0]), y1 = __fsub_rn(ay, dist[1]), x2 = __fadd_rn(ax, dist[2]), y2 = __fadd_rn(ay, dist[3]);
-                det_rec d;
+                det_t d;
                 d.x = __fmul_rn(__fmul_rn(__fadd_rn(x1, x2), 0.5f), fstride);
                 d.y = __fmul_rn(__fmul_rn(__fadd_rn(y1, y2), 0.5f), fstride);
                 d.w = __fmul_rn(__fsub_rn(x2, x1), fstride);
@@ -735,6 +554,7 @@ __global__ __launch_bounds__(DFL_THREADS) void dfl_decode_kernel(const mhip_dfl_
                 dets[slot] = d;
                 if (p.cand_pred) p.cand_pred[(size_t)f * MAXD + slot] = pred0 + cell;
             }
+            total += step;
             __syncthreads(); // wave_cnt is rewritten by the next step
         }
     }
@@ -751,10 +571,10 @@ extern "C" int mhip_detect_heads(const mhip_heads_t *p) {
         if (!p->base[k] || p->h[k] <= 0 || p->w[k] <= 0 || p->nc[k] < 1 || p->pix_step[k] <= 0 || p->ch_step[k] <= 0) return -1;
     hipLaunchKernelGGL(heads_decode_kernel, dim3(p->frames), dim3(HEADS_THREADS), 0, mhip_stream_native(), *p);
     int rc = mhip_check(hipGetLastError(), "decode heads");
-    if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh);
+    if (!rc) rc = launch_sort_nms((det_t *)p->dets, p->counts, p->frames, p->nms_thresh);
     if (rc || !p->map) return rc;
-    hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,
-                       (float)p->py, p->rx, p->ry, (det_rec *)nullptr);
+    hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_t *)p->dets, p->counts, (float)p->px,
+                       (float)p->py, p->rx, p->ry, (det_t *)nullptr);
     return mhip_check(hipGetLastError(), "letterbox mapping");
 }
 
@@ -768,9 +588,9 @@ extern "C" int mhip_detect_dfl(const mhip_dfl_heads_t *p) {
     if (!q.cand_pred || !q.kept_pred) q.cand_pred = q.kept_pred = nullptr; // both or neither
     hipLaunchKernelGGL(dfl_decode_kernel, dim3(p->frames), dim3(DFL_THREADS), 0, mhip_stream_native(), q);
     int rc = mhip_check(hipGetLastError(), "decode DFL heads");
-    if (!rc) rc = launch_sort_nms((det_rec *)p->dets, p->counts, p->frames, p->nms_thresh, p->cand_pred, p->kept_pred);
+    if (!rc) rc = launch_sort_nms((det_t *)p->dets, p->counts, p->frames, p->nms_thresh, p->cand_pred, p->kept_pred);
     if (rc || !p->map) return rc;
-    hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_rec *)p->dets, p->counts, (float)p->px,
-                       (float)p->py, p->rx, p->ry, (det_rec *)p->premap);
+    hipLaunchKernelGGL(heads_map_kernel, dim3(p->frames), dim3(256), 0, mhip_stream_native(), (det_t *)p->dets, p->counts, (float)p->px,
+                       (float)p->py, p->rx, p->ry, (det_t *)p->premap);
     return mhip_check(hipGetLastError(), "letterbox mapping");
 }
