@@ -415,22 +415,43 @@ mars_error_t mars_hip_preprocess_nv12_device(mars_model_t *model, int input_inde
  * NV12 source.  The four taps are converted with the integer BT.601 formulas of "NV12 camera frames" above, the chroma pair taken at
  *   (x >> 1, y >> 1) in FRAME coordinates, all MARS_NV12_* flags apply; then the blend.  An NV12 crop equals the RGB crop of
  *   mars_yolo_nv12_to_rgb of that frame, bit for bit.
+ * Area averaging (MARS_ROI_AREA).  Four taps skip most of the source at strong down-scales; with the flag an axis that has more source
+ *   samples than outputs is box-filtered instead.  Box -> rectangle, the target geometry, the -17 bands, the layouts, the selection and the
+ *   ROI table do not change.  Per axis, with n_in source samples (cw or ch) and n_out outputs (nw or nh), output sample i has a list of
+ *   (source index, weight) taps and a denominator D:
+ *     flag clear, or n_in <= n_out:  D = 256; the taps are (i0, 256 - f) and (i1, f) from pos, exactly as under "Resize";
+ *     flag set and n_in > n_out:     D = n_in.  In units of 1 / n_out of a source sample, output i covers [i * n_in, (i + 1) * n_in) and
+ *       source sample s covers [s * n_out, (s + 1) * n_out):  w(i, s) = min((s + 1) * n_out, (i + 1) * n_in) - max(s * n_out, i * n_in)
+ *       for s from (i * n_in) / n_out to ((i + 1) * n_in + n_out - 1) / n_out - 1 (/ is floor).  Every such weight is positive, the weights
+ *       of one output sum to n_in, there are at most (n_in + n_out - 1) / n_out + 1 of them, and a source sample feeds at most two
+ *       outputs.  7 -> 3: weights (3, 3, 1), (2, 3, 2), (1, 3, 3) over the sources 0..2, 2..4, 4..6.
+ *   Per pixel and channel, p = the crop's pixel, 0 .. 255, over 64-bit integers (S passes 2^32 once both axes are averaged and
+ *   cw * ch > 16 843 009), both / floor:
+ *     S = sum over the y taps of wy * (sum over the x taps of wx * p);  v = (S + (Dx * Dy) / 2) / (Dx * Dy);  out = (int8)(v - 128)
+ *   With both axes interpolated this is the formula under "Resize" (Dx * Dy = 65536).  The axes are independent: a flat wide box is averaged
+ *   along x and interpolated along y.  So: with the flag and no down-scaled axis the bytes are those without it; cw = k * nw, ch = l * nh
+ *   gives the rounded mean of every k x l block; a constant crop gives a constant output.  NV12: every tap is converted to RGB first, as
+ *   above, then weighted; an NV12 area crop equals the RGB area crop of mars_yolo_nv12_to_rgb of that frame, bit for bit.
+ *   The rotated calls ("Rotated crops") refuse the flag.
  * Selection (the detection forms).  Boxes are visited by ascending frame, inside a frame in the order the tail left them.  A box is kept when
  *   conf >= min_conf, cls_count == 0 or cls_first <= cls < cls_first + cls_count, the rectangle rule does not skip it, and fewer than
  *   max_per_frame boxes of its frame are kept already (0: no limit).  Kept boxes fill the destination's frames 0, 1, ... in visiting
  *   order up to its current batch; the boxes beyond are counted as dropped.  Destination frames behind the last crop are filled with -17. */
 typedef struct { int frame, det, x0, y0, x1, y1; } mars_roi_t; /* 24 bytes; det = index inside its frame's list (-1: a caller's box) */
 #define MARS_ROI_KEEP_ASPECT 1u
+#define MARS_ROI_AREA 4u /* "Area averaging"; not for the rotated calls */
 /* Zero-initialise; zero means default in every field but the frame size. */
 typedef struct {
     int src_w, src_h, src_format; unsigned src_flags; /* frames: MARS_HIP_CAMERA_RGB / _NV12, MARS_NV12_* (NV12 only) */
     float expand, min_conf; int min_size;
     int cls_first, cls_count, max_per_frame;
-    unsigned flags;                                    /* MARS_ROI_KEEP_ASPECT */
+    unsigned flags;                                    /* MARS_ROI_KEEP_ASPECT | MARS_ROI_AREA */
 } mars_hip_roi_opts_t;
 /* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL pointer, a non-positive size, an unknown
  * format or flag bit, odd NV12 sizes, a negative or non-finite expand / min_conf / min_size / cls_count / max_per_frame, frames or targets
- * too wide for the crop kernel's on-chip buffers (about 5000 pixels).  MARS_ERR_INVALID_TENSOR: det_model == dst_model, a destination input
+ * too wide for the crop kernel's on-chip buffers (about 5000 pixels; with MARS_ROI_AREA also a target wider than 1280 pixels, or frames too
+ * wide for the area kernel's buffers beside the target: about 4700 pixels at 1280, more at narrower targets -- frames up to 3840 wide into
+ * targets up to 1280 wide always pass).  MARS_ERR_INVALID_TENSOR: det_model == dst_model, a destination input
  * that is not int8 with 3 channels, no detections in HBM, a model with an open pipe. */
 /* The mars_yolo_letterbox of this feature: host pointers in and out, runs on the GPU.  `frames` = n_frames frames of opts->src_w x src_h,
  * densely packed; box i lies in frame frame_of_box[i].  Only the rectangle rule applies.  out = [n_boxes][tw * th * 3] int8 ([th][tw][3] with
@@ -894,8 +915,8 @@ void mars_yolo_obb_corners(const mars_obb_t *box, float xy[8]);
  *   A kept box has x1 > x0 and y1 > y0; a skipped box of the host-pointer form has all four zero (x1 == x0 marks it).
  * Refused: what the calls of "ROI crops" refuse, W or H above 32767 (MARS_ERR_INVALID_FILE), and MARS_ERR_INVALID_TENSOR when det_model
  *   holds no obb results (no mars_hip_detect_obb_device since its batch was set).
- * Not covered: the pipelined mars_hip_pipe_* path; area averaging (a strong down-scale samples four taps per output pixel, as the upright
- *   crop does); rotated crops of merged tile lists; boxes whose centre is off-frame (skipped). */
+ * Not covered: the pipelined mars_hip_pipe_* path; area averaging (a strong down-scale samples four taps per output pixel; the upright
+ *   crop has MARS_ROI_AREA for it, and the calls below refuse that flag with MARS_ERR_INVALID_FILE before anything else); rotated crops of merged tile lists; boxes whose centre is off-frame (skipped). */
 /* mars_yolo_crop_boxes for oriented boxes: host pointers in and out, runs on the GPU.  Only the skip rule applies; a skipped box's crop is
  * all -17 and rois[i].x1 == rois[i].x0 marks it (rois may be NULL). */
 mars_error_t mars_yolo_crop_obb(const unsigned char *frames, int n_frames, const mars_obb_t *boxes, const int *frame_of_box, int n_boxes,
@@ -924,7 +945,9 @@ mars_error_t mars_hip_crop_obb(mars_model_t *det_model, const unsigned char *fra
  * Front-end.  Tile t of camera frame c is written into model frame c * T + t by the rules of "ROI crops" above: the crop rectangle is the
  *             tile's rectangle (no box arithmetic); the target geometry is stretch, or MARS_TILE_KEEP_ASPECT with the integer nw, nh, px, py
  *             rule and -17 bands; the "Resize" and "NV12 source" paragraphs apply; the layout is the one the input's format tag asks for.
- *             A tile whose size equals the input's gives pos = i * 256: an exact copy, pixel - 128.
+ *             A tile whose size equals the input's gives pos = i * 256: an exact copy, pixel - 128.  MARS_TILE_AREA: the tile is resized by
+ *             "Area averaging" of "ROI crops" (a whole-frame tile of 1920 x 1080 into 640 x 640 is a 3 x down-scale); a tile no larger than
+ *             its target keeps its bytes, the exact copy included.  The merge calls accept the bit and ignore it.
  * Quota.      Tile t contributes the first q entries of its list, q = max_per_tile, or by default min(MARS_YOLO_MAX_DET,
  *             MARS_TILE_MAX_CAND / n_tiles); n_tiles * q <= MARS_TILE_MAX_CAND.  The entries beyond q are counted in `overflow`.
  * Validity.   An entry is dropped, and counted in `invalid`, when one of x, y, w, h, conf is not finite, or w <= 0, or h <= 0.
@@ -963,6 +986,7 @@ typedef struct { int candidates, overflow, invalid, edge, suppressed, truncated;
 #define MARS_TILE_KEEP_ASPECT 1u
 #define MARS_TILE_MATCH_IOS 2u
 #define MARS_TILE_AGNOSTIC 4u
+#define MARS_TILE_AREA 16u /* front-end: "Area averaging" of "ROI crops" */
 /* Pure host code.  Writes the first min(count, cap) tiles (tiles may be NULL with cap 0) and returns the count, also when it exceeds cap;
  * -1: a non-positive size, a negative overlap, or overlap >= tile. */
 int mars_tile_grid(int W, int H, int tile_w, int tile_h, int overlap_x, int overlap_y, mars_tile_t *tiles, int cap);
@@ -970,7 +994,7 @@ int mars_tile_grid(int W, int H, int tile_w, int tile_h, int overlap_x, int over
 typedef struct {
     int src_w, src_h, src_format; unsigned src_flags;   /* camera frames, as mars_hip_roi_opts_t */
     int n_tiles; const mars_tile_t *tiles;              /* per camera frame, 1 .. MARS_TILE_MAX_TILES; copied by every call */
-    unsigned flags;                                     /* MARS_TILE_KEEP_ASPECT | MARS_TILE_MATCH_IOS | MARS_TILE_AGNOSTIC */
+    unsigned flags;                                     /* MARS_TILE_KEEP_ASPECT | MARS_TILE_MATCH_IOS | MARS_TILE_AGNOSTIC | MARS_TILE_AREA */
     float merge_thresh;                                 /* 0: 0.5 */
     float edge_margin;                                  /* source pixels; 0: no edge rule */
     int max_per_tile;                                   /* 0: min(MARS_YOLO_MAX_DET, MARS_TILE_MAX_CAND / n_tiles) */
@@ -978,7 +1002,7 @@ typedef struct {
 /* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL table or pointer; n_tiles outside
  * 1 .. MARS_TILE_MAX_TILES; a tile that is empty or not inside [0, src_w) x [0, src_h); a non-positive frame or input size, an unknown format
  * or flag bit, odd NV12 sizes; a negative or non-finite merge_thresh or edge_margin, merge_thresh > 1; a negative max_per_tile, or n_tiles *
- * max_per_tile > MARS_TILE_MAX_CAND; (front-end) a frame or target too wide for the crop kernel; (host-pointer forms) a non-positive n_frames,
+ * max_per_tile > MARS_TILE_MAX_CAND; (front-end) a frame or target too wide for the crop kernel (the limits of "ROI crops", those of MARS_ROI_AREA under MARS_TILE_AREA); (host-pointer forms) a non-positive n_frames,
  * n_frames * n_tiles > 65535, max_det outside 1 .. MARS_YOLO_MAX_DET.  MARS_ERR_INVALID_TENSOR: a batch that is no
  * multiple of n_tiles; an input that is not int8 with 3 channels; no detections in HBM; lists mapped with src_w > 0; *_results before any
  * merge; a model with an open pipe. */

@@ -10,6 +10,7 @@
 //                             knows it: the kernel reads the kept count and its rectangle from device memory, builds the column table in
 //                             LDS, stages the source-row segments its rows touch in LDS (NV12: converted once per pixel while staging),
 //                             blends from LDS, puts the strip's bytes together in LDS and stores contiguous runs 16 bytes at a time.
+//   roi_area_crop_kernel      the crop under MARS_ROI_AREA / MARS_TILE_AREA: down-scaled axes are box-filtered; a strip streams over its source rows;
 //   roi_rot_crop_kernel<FMT>  the same strip for an ORIENTED box ("Rotated crops"): samples along the box's axes from a staged bounding rectangle;
 //                             the select and rectangle kernels serve it through their ROT flag.
 // Nothing here uses atomics: a slot number is a function of the lists alone.
@@ -208,6 +209,43 @@ static size_t roi_rowbuf(int w, int fmt) {
     return all < 32 * 1024 ? all : (2 * pm > 32 * 1024 ? 2 * pm : 32 * 1024);
 }
 
+// Unit u of the staged image of source row sy for the area kernel, laid out as roi_crop_kernel stages it: a staged row holds the pixels
+// [xe, x1) of a source row as RGB bytes (xe = x0, NV12: x0 & ~1).  RGB: 16 bytes of the segment; NV12: four pixels converted from an even
+// column, 12 bytes, each stored on its own (packed into dwords inside a helper like this one, the bytes came out wrong: profiles/HISTORY.md,
+// "Area-averaged crops")
+template <int FMT>
+__device__ __forceinline__ void area_stage_unit(const mhip_roi_t &p, const nv12_coef_t &kc, const uint8_t *frame, const int x0, const int xe, const int cw,
+                                               const int sy, const int u, unsigned char *row) {
+    if (FMT) { // Y bytes of pixels xe + 4 u .. + 3 and, at the same byte offset of chroma row sy >> 1, their two chroma pairs
+        const int x = xe + 4 * u;
+        const uint8_t *gy = frame + (size_t)sy * p.w + x, *gc = frame + ((size_t)p.h + (size_t)(sy >> 1)) * p.w + x;
+        unsigned yv, cv;
+        if (x + 4 <= p.w) {
+            __builtin_memcpy(&yv, gy, 4);
+            __builtin_memcpy(&cv, gc, 4);
+        } else { // w % 4 == 2: the row's last two pixels and their one pair; nothing is read beyond either row
+            yv = (unsigned)gy[0] | (unsigned)gy[1] << 8;
+            cv = (unsigned)gc[0] | (unsigned)gc[1] << 8;
+        }
+        int c[4][3];
+        nv12_quad(kc, yv, cv, c);
+        unsigned char *o = row + u * 12;
+#pragma unroll
+        for (int k = 0; k < 12; k++) o[k] = (unsigned char)c[k / 3][k % 3];
+    } else { // 16 bytes of the segment [x0 * 3, x1 * 3) of the row; the last piece byte by byte: nothing is read beyond the segment
+        const uint8_t *g = frame + ((size_t)sy * p.w + x0) * 3 + (size_t)u * 16;
+        unsigned v[4] = {0u, 0u, 0u, 0u};
+        const int left = cw * 3 - u * 16;
+        if (left >= 16) __builtin_memcpy(v, g, 16);
+        else {
+#pragma unroll
+            for (int b = 0; b < 15; b++) // (register indices fixed by the unrolling)
+                if (b < left) v[b >> 2] |= (unsigned)g[b] << (8 * (b & 3));
+        }
+        *(uint4 *)(row + u * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+}
+
 template <int FMT>
 __global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const int off_meta, const int off_stage, const int off_rows, const int rowbuf_bytes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
@@ -335,6 +373,193 @@ __global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const
         __syncthreads(); // the rows and the group record may be overwritten
         r_cur = r_end;
     }
+    if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
+    else
+        for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
+}
+
+// ---- the area-averaging crop ("Area averaging" in include/mars_hip.h): an axis with more source samples than outputs is box-filtered, the
+// other one keeps the bilinear taps.  A strip of output rows covers a contiguous range of source rows, too many to hold at strong
+// down-scales, so the kernel streams: it stages a window of the next source rows (as many as the row buffer holds), and for each output row
+// walks that row's source rows.  Thread t owns the (column, channel) pairs q = t + 256 k: for a source row it reduces the row's x taps into
+// h[q] (<= 255 Dx) once, keeps it in its own LDS entry of a two-row cache indexed by the row's parity -- consecutive output rows share their
+// boundary row (averaged) or both rows (interpolated) -- and adds wy * h[q] to the accumulator of the current output row, a register.  Only
+// the row window is shared between threads: two barriers per window, none per row.  Accumulators are 32 bits wide where 255.5 Dx Dy fits,
+// else 64; the slot's geometry decides, so a workgroup takes one path.  The quotient is the exact unsigned division of that width.
+#define AREA_MAX_TW 1280          // 15 pairs per thread
+#define AREA_ACC32_MAX 16000000u  // Dx * Dy up to here: 255.5 * Dx * Dy < 2^32
+static int area_rows(int tw) { return tw <= 640 ? ROI_R : ROI_R / 2; } // output rows of a strip
+// LDS: [column table, 4 bytes a column][h cache: 2 rows x (tw * 3) dwords][strip bytes][source-row window]
+static size_t area_lds_col(int tw) { return roi_r16((size_t)tw * 4); }
+static size_t area_lds_hs(int tw) { return 2 * roi_r16((size_t)tw * 12); }
+static size_t area_lds_stage(int tw) { return 3 * (roi_r16((size_t)area_rows(tw) * tw) + 16); }
+static size_t area_rowbuf(int w, int tw, int fmt) { // 0: the widest source row does not fit beside the rest
+    const size_t rest = area_lds_col(tw) + area_lds_hs(tw) + area_lds_stage(tw), pm = roi_pitch_max(w, fmt);
+    if (rest + pm > 64 * 1024) return 0;
+    const size_t want = pm > 16 * 1024 ? pm : 16 * 1024, room = 64 * 1024 - rest;
+    return want < room ? want : room;
+}
+
+struct area_geom_t {
+    const uint8_t *frame;
+    int x0, y0, xe, cw, ch, nw, nh, px, py, ys, r_lo, r_hi, ax, ay; // ax, ay: the axis is averaged
+    int units, pitch, cap_rows, np3, hs_pitch;
+    const unsigned *coltab; // averaged x: first tap's pixel in a staged row | taps << 16; else: left tap's pixel | (distance to the right tap) << 16 | fx << 24
+    unsigned *hs;
+    unsigned char *rowbuf;
+    int8_t *stage, *st0;  // the strip's LDS image: planar, channel c at stage + c * chan + ((lo + c * plane) & 15); nhwc: st0
+    int chan;
+    unsigned lo, plane;
+};
+
+// the source rows [sa, sb] of output row o and, on an interpolated axis, fy
+__device__ __forceinline__ void area_row_span(const int o, const int ch, const int nh, const int ay, int &sa, int &sb, int &fy) {
+    if (ay) {
+        sa = (int)(((long long)o * ch) / nh);
+        sb = (int)(((long long)(o + 1) * ch + nh - 1) / nh) - 1;
+        fy = 0;
+    } else {
+        const int pos = roi_pos(o, ch, nh);
+        sa = pos >> 8; sb = min(sa + 1, ch - 1); fy = pos & 255;
+    }
+}
+
+template <int FMT, int NP, typename ACC>
+__device__ __forceinline__ void area_strip(const mhip_roi_t &p, const area_geom_t &g, const int tid) {
+    const nv12_coef_t kc = nv12_coef(p.nv12_flags);
+    const ACC D = (ACC)(g.ax ? g.cw : 256) * (ACC)(g.ay ? g.ch : 256);
+    const int row_b = p.tw * 3;
+    int s_last, sa, sb, fy;
+    area_row_span(g.ys + g.r_hi - 1 - g.py, g.ch, g.nh, g.ay, sa, s_last, fy);
+    int tag0 = -1, tag1 = -1, b0 = 0, b1 = -1; // the cached rows, the staged window [b0, b1]
+    for (int row = g.r_lo; row < g.r_hi; row++) {
+        const int o = g.ys + row - g.py;
+        area_row_span(o, g.ch, g.nh, g.ay, sa, sb, fy);
+        ACC acc[NP];
+#pragma unroll
+        for (int k = 0; k < NP; k++) acc[k] = 0;
+        for (int s = sa; s <= sb; s++) {
+            const int wy = g.ay ? (int)(min((long long)(s + 1) * g.nh, (long long)(o + 1) * g.ch) - max((long long)s * g.nh, (long long)o * g.ch))
+                                : (sb == sa ? 256 : (s == sa ? 256 - fy : fy));
+            unsigned *hrow = g.hs + (s & 1) * g.hs_pitch;
+            if ((s & 1 ? tag1 : tag0) != s) { // (uniform: every thread walks the same rows)
+                if (s < b0 || s > b1) {
+                    __syncthreads(); // the old window is read no more (the first time round: the column table and the grey strip)
+                    b0 = s; b1 = min(s + g.cap_rows - 1, s_last);
+                    for (int it = tid; it < (b1 - b0 + 1) * g.units; it += 256) {
+                        const int sr = it / g.units, u = it - sr * g.units;
+                        area_stage_unit<FMT>(p, kc, g.frame, g.x0, g.xe, g.cw, g.y0 + b0 + sr, u, g.rowbuf + sr * g.pitch);
+                    }
+                    __syncthreads();
+                }
+                const unsigned char *rp = g.rowbuf + (s - b0) * g.pitch;
+                const int xo = g.x0 - g.xe;
+#pragma unroll
+                for (int k = 0; k < NP; k++) {
+                    const int q = tid + 256 * k;
+                    if (q < g.np3) {
+                        const int i = q / 3, c = q - 3 * i;
+                        const unsigned ct = g.coltab[i];
+                        const unsigned char *t = rp + (ct & 0xffffu) * 3 + c;
+                        unsigned h;
+                        if (g.ax) { // first and last tap by the overlap rule, nw for every one between
+                            const int n = (int)(ct >> 16), xa = (int)(ct & 0xffffu) - xo;
+                            const unsigned w0 = (unsigned)(min((xa + 1) * g.nw, (i + 1) * g.cw) - i * g.cw), w1 = (unsigned)((i + 1) * g.cw - (xa + n - 1) * g.nw);
+                            unsigned mid = 0;
+                            for (int x = 1; x < n - 1; x++) mid += t[3 * x];
+                            h = w0 * t[0] + (unsigned)g.nw * mid + w1 * t[3 * (n - 1)];
+                        } else {
+                            const unsigned fx = ct >> 24;
+                            h = (unsigned)t[0] * (256u - fx) + (unsigned)t[3 * ((ct >> 16) & 1u)] * fx;
+                        }
+                        hrow[q] = h;
+                    }
+                }
+                if (s & 1) tag1 = s; else tag0 = s;
+            }
+#pragma unroll
+            for (int k = 0; k < NP; k++) {
+                const int q = tid + 256 * k;
+                if (q < g.np3) acc[k] += (ACC)(unsigned)wy * (ACC)hrow[q]; // the thread's own entries: no barrier
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            const int q = tid + 256 * k;
+            if (q < g.np3) {
+                const int i = q / 3, c = q - 3 * i;
+                const int v = (int)((acc[k] + D / 2) / D);
+                const int8_t q8 = (int8_t)(v - 128);
+                if (p.nhwc) g.st0[row * row_b + (g.px + i) * 3 + c] = q8;
+                else g.stage[c * g.chan + ((g.lo + c * g.plane) & 15u) + row * p.tw + g.px + i] = q8; // channel c's image, at its run's offset inside a 16-byte line
+            }
+        }
+    }
+}
+
+template <int FMT, int NP>
+__global__ __launch_bounds__(256) void roi_area_crop_kernel(const mhip_roi_t p, const int ar, const int off_hs, const int off_stage, const int off_rows,
+                                                            const int rowbuf_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    const int tid = threadIdx.x;
+    const int slot = blockIdx.y, ys = blockIdx.x * ar;
+    const int rows = min(ar, p.th - ys), row_b = p.tw * 3;
+    int8_t *dst = p.out + (size_t)slot * p.out_stride;
+    // this slot's geometry, from device memory: as roi_crop_kernel
+    bool live = slot < p.n_out[0];
+    roi_t r = {0, 0, 0, 0, 0, 0};
+    if (live) r = ((const roi_t *)p.rois)[slot];
+    const int cw = r.x1 - r.x0, ch = r.y1 - r.y0;
+    live = live && cw > 0 && ch > 0 && r.frame >= 0 && r.frame < p.n_frames && r.x0 >= 0 && r.y0 >= 0 && r.x1 <= p.w && r.y1 <= p.h;
+    int nw = p.tw, nh = p.th;
+    if (live && p.keep_aspect) {
+        if ((long long)cw * p.th >= (long long)ch * p.tw) nh = max(1, (int)(((long long)ch * p.tw + cw / 2) / cw));
+        else nw = max(1, (int)(((long long)cw * p.th + ch / 2) / ch));
+    }
+    const int px = (p.tw - nw) / 2, py = (p.th - nh) / 2;
+    const int r_lo = max(py - ys, 0), r_hi = min(py + nh - ys, rows);
+    if (!live || r_hi <= r_lo) {
+        if (p.nhwc) roi_fill_run(dst + (size_t)ys * row_b, rows * row_b, tid);
+        else
+            for (int c = 0; c < 3; c++) roi_fill_run(dst + ((size_t)c * p.th + ys) * p.tw, rows * p.tw, tid);
+        return;
+    }
+    area_geom_t g;
+    unsigned *coltab = (unsigned *)sm;
+    int8_t *stage = (int8_t *)(sm + off_stage);
+    g.frame = p.frames + (size_t)r.frame * p.frame_stride;
+    g.x0 = r.x0; g.y0 = r.y0; g.xe = FMT ? (r.x0 & ~1) : r.x0;
+    g.cw = cw; g.ch = ch; g.nw = nw; g.nh = nh; g.px = px; g.py = py; g.ys = ys; g.r_lo = r_lo; g.r_hi = r_hi;
+    g.ax = cw > nw; g.ay = ch > nh;
+    g.units = FMT ? (r.x1 - g.xe + 3) >> 2 : (cw * 3 + 15) >> 4;
+    g.pitch = FMT ? (g.units * 12 + 15) & ~15 : g.units * 16;
+    g.cap_rows = rowbuf_bytes / g.pitch; // >= 1: the launcher sized the window for the widest box
+    g.np3 = nw * 3;
+    g.hs_pitch = (p.tw * 3 + 3) & ~3;
+    g.coltab = coltab; g.hs = (unsigned *)(sm + off_hs); g.rowbuf = sm + off_rows;
+    const int xo = r.x0 - g.xe;
+    for (int i = tid; i < nw; i += 256) {
+        if (g.ax) {
+            const int xa = (int)(((long long)i * cw) / nw), xb = (int)(((long long)(i + 1) * cw + nw - 1) / nw) - 1;
+            coltab[i] = (unsigned)(xa + xo) | (unsigned)(xb - xa + 1) << 16;
+        } else {
+            const int pos = roi_pos(i, cw, nw), i0 = pos >> 8, i1 = min(i0 + 1, cw - 1);
+            coltab[i] = (unsigned)(i0 + xo) | (unsigned)(i1 - i0) << 16 | (unsigned)(pos & 255) << 24;
+        }
+    }
+    // the strip's LDS image, grey first: as in roi_crop_kernel, ar rows deep
+    const int chan = ((ar * p.tw + 15) & ~15) + 16;
+    int8_t *st[3];
+    if (p.nhwc) st[0] = st[1] = st[2] = stage + ((uintptr_t)(dst + (size_t)ys * row_b) & 15);
+    else
+        for (int c = 0; c < 3; c++) st[c] = stage + c * chan + ((uintptr_t)(dst + ((size_t)c * p.th + ys) * p.tw) & 15);
+    g.stage = stage; g.st0 = st[0]; g.chan = chan;
+    g.lo = (unsigned)((uintptr_t)(dst + (size_t)ys * p.tw) & 15); g.plane = (unsigned)p.th * (unsigned)p.tw;
+    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
+    const unsigned long long DD = (unsigned long long)(g.ax ? cw : 256) * (unsigned long long)(g.ay ? ch : 256);
+    if (DD <= AREA_ACC32_MAX) area_strip<FMT, NP, unsigned>(p, g, tid);
+    else area_strip<FMT, NP, unsigned long long>(p, g, tid);
+    __syncthreads();
     if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
     else
         for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
@@ -505,10 +730,33 @@ extern "C" int mhip_roi_fits(int w, int tw, int fmt) {
     return roi_lds_col(tw) + ROI_META + roi_lds_stage(tw) + roi_rowbuf(w, fmt) <= 64 * 1024;
 }
 
+extern "C" int mhip_roi_area_fits(int w, int tw, int fmt) {
+    if (w <= 0 || tw <= 0) return 0;
+    return tw <= AREA_MAX_TW && w <= 65535 && area_rowbuf(w, tw, fmt) != 0;
+}
+
+template <int FMT>
+static void roi_area_launch(const mhip_roi_t *p) {
+    const int ar = area_rows(p->tw), off_hs = (int)area_lds_col(p->tw), off_stage = off_hs + (int)area_lds_hs(p->tw);
+    const int off_rows = off_stage + (int)area_lds_stage(p->tw), rowbuf = (int)area_rowbuf(p->w, p->tw, p->fmt);
+    const dim3 g((unsigned)((p->th + ar - 1) / ar), (unsigned)p->slots);
+    const size_t lds = (size_t)off_rows + rowbuf;
+    // pairs per thread: tw * 3 <= 256 NP
+    if (p->tw * 3 <= 512) hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_area_crop_kernel<FMT, 2>), g, dim3(256), lds, mhip_stream_native(), *p, ar, off_hs, off_stage, off_rows, rowbuf);
+    else if (p->tw * 3 <= 2048) hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_area_crop_kernel<FMT, 8>), g, dim3(256), lds, mhip_stream_native(), *p, ar, off_hs, off_stage, off_rows, rowbuf);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_area_crop_kernel<FMT, 15>), g, dim3(256), lds, mhip_stream_native(), *p, ar, off_hs, off_stage, off_rows, rowbuf);
+}
+
 extern "C" int mhip_roi_crop(const mhip_roi_t *p) {
     if (!roi_common_ok(p) || !p->frames || !p->out || p->tw <= 0 || p->th <= 0 || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 ||
         !mhip_roi_fits(p->w, p->tw, p->fmt))
         return -1;
+    if (p->area) {
+        if (!mhip_roi_area_fits(p->w, p->tw, p->fmt)) return -1;
+        if (p->fmt) roi_area_launch<1>(p);
+        else roi_area_launch<0>(p);
+        return mhip_check(hipGetLastError(), p->fmt ? "roi area crop (nv12)" : "roi area crop");
+    }
     const int off_meta = (int)roi_lds_col(p->tw), off_stage = off_meta + ROI_META, off_rows = off_stage + (int)roi_lds_stage(p->tw);
     const int rowbuf = (int)roi_rowbuf(p->w, p->fmt);
     const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);

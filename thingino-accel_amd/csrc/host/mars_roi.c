@@ -21,10 +21,11 @@ static mars_error_t roi_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_
     if (o->src_format != MARS_HIP_CAMERA_RGB && o->src_format != MARS_HIP_CAMERA_NV12) return MARS_ERR_INVALID_FILE;
     if (o->src_format == MARS_HIP_CAMERA_NV12 ? ((o->src_flags & ~NV12_FLAGS) || !mars_hip_nv12_frame_bytes(o->src_w, o->src_h)) : o->src_flags != 0)
         return MARS_ERR_INVALID_FILE;
-    if (o->flags & ~MARS_ROI_KEEP_ASPECT) return MARS_ERR_INVALID_FILE;
+    if (o->flags & ~(MARS_ROI_KEEP_ASPECT | MARS_ROI_AREA)) return MARS_ERR_INVALID_FILE;
     if (!isfinite(o->expand) || o->expand < 0 || !isfinite(o->min_conf) || o->min_size < 0 || o->cls_count < 0 || o->max_per_frame < 0)
         return MARS_ERR_INVALID_FILE;
     if (!mhip_roi_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
+    if ((o->flags & MARS_ROI_AREA) && !mhip_roi_area_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
     p->w = o->src_w; p->h = o->src_h; p->fmt = o->src_format; p->nv12_flags = o->src_flags;
     p->frame_stride = p->fmt ? mars_hip_nv12_frame_bytes(p->w, p->h) : (size_t)p->w * p->h * 3;
     p->expand = o->expand != 0 ? o->expand : 1.0f;
@@ -32,12 +33,14 @@ static mars_error_t roi_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_
     p->min_size = o->min_size ? o->min_size : 2;
     p->cls_first = o->cls_first; p->cls_count = o->cls_count; p->max_per_frame = o->max_per_frame;
     p->keep_aspect = (o->flags & MARS_ROI_KEEP_ASPECT) != 0;
+    p->area = (o->flags & MARS_ROI_AREA) != 0;
     p->tw = tw; p->th = th;
     return MARS_OK;
 }
 
 /* ... and what the rotated forms refuse on top */
 static mars_error_t rot_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_roi_t *p) {
+    if (o && (o->flags & MARS_ROI_AREA)) return MARS_ERR_INVALID_FILE; /* an area filter along a rotated box is another kernel */
     const mars_error_t e = roi_opts(o, tw, th, p);
     if (e != MARS_OK) return e;
     return mhip_roi_rot_fits(o->src_w, o->src_h, tw) ? MARS_OK : MARS_ERR_INVALID_FILE;

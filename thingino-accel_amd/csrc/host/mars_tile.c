@@ -17,7 +17,7 @@ _Static_assert(sizeof(mars_tile_t) == 16 && sizeof(mars_tile_src_t) == 8 && size
 _Static_assert(MARS_TILE_MAX_TILES == MHIP_TILE_MAX_TILES && MARS_TILE_MAX_CAND == MHIP_TILE_MAX_CAND, "the kernel's table and candidate sizes");
 
 #define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
-#define TILE_FLAGS (MARS_TILE_KEEP_ASPECT | MARS_TILE_MATCH_IOS | MARS_TILE_AGNOSTIC)
+#define TILE_FLAGS (MARS_TILE_KEEP_ASPECT | MARS_TILE_MATCH_IOS | MARS_TILE_AGNOSTIC | MARS_TILE_AREA)
 
 /* the number of starts of one axis: every k with k * step + tile < W, and the final one */
 static long long axis_starts(int W, int tile, int overlap) {
@@ -90,10 +90,12 @@ static mars_error_t tile_opts(const mars_hip_tile_opts_t *o, int tw, int th, mhi
 static mars_error_t tile_roi(const mars_hip_tile_opts_t *o, int tw, int th, mhip_roi_t *r) {
     memset(r, 0, sizeof(*r));
     if (!mhip_roi_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
+    if ((o->flags & MARS_TILE_AREA) && !mhip_roi_area_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
     r->w = o->src_w; r->h = o->src_h; r->fmt = o->src_format; r->nv12_flags = o->src_flags;
     r->frame_stride = r->fmt ? mars_hip_nv12_frame_bytes(r->w, r->h) : (size_t)r->w * r->h * 3;
     r->expand = 1.0f; r->min_size = 1;
     r->keep_aspect = (o->flags & MARS_TILE_KEEP_ASPECT) != 0;
+    r->area = (o->flags & MARS_TILE_AREA) != 0;
     r->tw = tw; r->th = th;
     return MARS_OK;
 }

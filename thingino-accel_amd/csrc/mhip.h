@@ -430,11 +430,13 @@ typedef struct {
     int *frame_kept;                            /* mhip_roi_select: scratch, [n_frames] */
     const float *csn;                           /* the mhip_roi_rot_* calls only ("Rotated crops"): dets / boxes hold records of 32 bytes (mars_obb_t)
                                                  * and csn the (cos, sin) pair of every one of them, index-aligned */
+    int area;                                   /* mhip_roi_crop only: box-filter the down-scaled axes ("Area averaging"); needs mhip_roi_area_fits */
 } mhip_roi_t;
 int mhip_roi_select(const mhip_roi_t *p); /* the selection rules over the detection lists, frame-major, list order; two launches */
 int mhip_roi_rects(const mhip_roi_t *p);  /* the rectangle rule alone: slot i = box i (x1 == x0: skipped), n_out = {n_boxes, 0} */
 int mhip_roi_crop(const mhip_roi_t *p);   /* slots >= n_out[0], skipped slots and pad bands are filled with -17 */
 int mhip_roi_fits(int w, int tw, int fmt); /* 1: the crop kernel's LDS holds two source rows of such frames and a strip of such a target */
+int mhip_roi_area_fits(int w, int tw, int fmt); /* 1: the area kernel takes such a target (<= 1280 wide) and its LDS holds one source row of such frames beside it */
 /* the same three over oriented boxes: the skip rule of "Rotated crops" in the rectangle rule's place, x0 .. y1 = the enclosing rectangle (for the
  * caller only), and a crop kernel that reads box (frame, det) of dets -- box `slot` of boxes where det < 0 -- and samples along its axes */
 int mhip_roi_rot_select(const mhip_roi_t *p);

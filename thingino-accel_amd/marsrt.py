@@ -99,7 +99,7 @@ class PipeOpts(C.Structure):
 
 CAMERA_RGB, CAMERA_NV12 = 0, 1        # MARS_HIP_CAMERA_*
 NV12_FULL_RANGE, NV12_VU = 1, 2       # MARS_NV12_*
-ROI_KEEP_ASPECT = 1                   # MARS_ROI_*
+ROI_KEEP_ASPECT, ROI_AREA = 1, 4      # MARS_ROI_*
 ROI_DTYPE = np.dtype([("frame", "<i4"), ("det", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4")])  # mars_roi_t
 
 
@@ -179,7 +179,7 @@ class ObbOpts(C.Structure):  # mars_hip_obb_opts_t: zero = default in every fiel
 
 
 TILE_MAX_TILES, TILE_MAX_CAND = 64, 2048                                 # MARS_TILE_*
-TILE_KEEP_ASPECT, TILE_MATCH_IOS, TILE_AGNOSTIC = 1, 2, 4
+TILE_KEEP_ASPECT, TILE_MATCH_IOS, TILE_AGNOSTIC, TILE_AREA = 1, 2, 4, 16
 TILE_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4")])  # mars_tile_t
 TILE_SRC_DTYPE = np.dtype([("tile", "<i4"), ("det", "<i4")])              # mars_tile_src_t
 TILE_STATS_DTYPE = np.dtype([("candidates", "<i4"), ("overflow", "<i4"), ("invalid", "<i4"), ("edge", "<i4"), ("suppressed", "<i4"),
@@ -500,13 +500,15 @@ def letterbox_nv12(nv12, w, h, tw, th, nhwc=True, flags=0):
     return out
 
 
-def roi_opts(w, h, fmt=CAMERA_RGB, src_flags=0, expand=0.0, min_conf=0.0, min_size=0, classes=None, max_per_frame=0, keep_aspect=False):
-    """mars_hip_roi_opts_t for frames of w x h.  classes = (first, count): the class window; zero means default everywhere else"""
+def roi_opts(w, h, fmt=CAMERA_RGB, src_flags=0, expand=0.0, min_conf=0.0, min_size=0, classes=None, max_per_frame=0, keep_aspect=False,
+             area=False):
+    """mars_hip_roi_opts_t for frames of w x h.  classes = (first, count): the class window; area: box-filter the down-scaled axes
+    (MARS_ROI_AREA; the rotated calls refuse it); zero means default everywhere else"""
     o = RoiOpts(int(w), int(h), int(fmt), int(src_flags), float(expand), float(min_conf), int(min_size))
     if classes is not None:
         o.cls_first, o.cls_count = int(classes[0]), int(classes[1])
     o.max_per_frame = int(max_per_frame)
-    o.flags = ROI_KEEP_ASPECT if keep_aspect else 0
+    o.flags = (ROI_KEEP_ASPECT if keep_aspect else 0) | (ROI_AREA if area else 0)
     return o
 
 
@@ -552,14 +554,14 @@ def tile_grid(W, H, tile_w, tile_h, overlap_x=0, overlap_y=0):
 
 
 def tile_opts(w, h, tiles, fmt=CAMERA_RGB, src_flags=0, keep_aspect=False, ios=False, agnostic=False, merge_thresh=0.0, edge_margin=0.0,
-              max_per_tile=0, flags=0):
+              max_per_tile=0, flags=0, area=False):
     """mars_hip_tile_opts_t for camera frames of w x h cut by `tiles` (TILE_DTYPE records, or rows of x0, y0, x1, y1); zero means default
-    everywhere else.  The table is copied and kept alive by the returned object"""
+    everywhere else; area: MARS_TILE_AREA, the front-end box-filters the down-scaled axes.  The table is copied and kept alive by the returned object"""
     t = np.ascontiguousarray(tiles)
     if t.dtype != TILE_DTYPE:
         t = np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 4)).view(TILE_DTYPE).reshape(-1)
     t = t.reshape(-1).copy()
-    f = int(flags) | (TILE_KEEP_ASPECT if keep_aspect else 0) | (TILE_MATCH_IOS if ios else 0) | (TILE_AGNOSTIC if agnostic else 0)
+    f = int(flags) | (TILE_KEEP_ASPECT if keep_aspect else 0) | (TILE_MATCH_IOS if ios else 0) | (TILE_AGNOSTIC if agnostic else 0) | (TILE_AREA if area else 0)
     o = TileOpts(int(w), int(h), int(fmt), int(src_flags), int(t.size), t.ctypes.data, f, float(merge_thresh), float(edge_margin), int(max_per_tile))
     o._table = t
     return o

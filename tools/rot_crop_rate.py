@@ -32,13 +32,14 @@ from roi_rate import Events  # noqa: E402
 CW, CH, TW, TH = 1280, 720, 160, 160
 
 
-class RoiLaunch(C.Structure):  # mhip_roi_t (csrc/mhip.h); `csn` is the last field, so a library without it reads a prefix
+class RoiLaunch(C.Structure):  # mhip_roi_t (csrc/mhip.h); `csn` and `area` are the last fields, so a library without them reads a prefix
     _fields_ = [("frames", C.c_void_p), ("frame_stride", C.c_size_t), ("n_frames", C.c_int), ("w", C.c_int), ("h", C.c_int), ("fmt", C.c_int),
                 ("nv12_flags", C.c_uint), ("dets", C.c_void_p), ("counts", C.c_void_p), ("det_cap", C.c_int),
                 ("boxes", C.c_void_p), ("frame_of_box", C.c_void_p), ("n_boxes", C.c_int), ("expand", C.c_float), ("min_conf", C.c_float),
                 ("min_size", C.c_int), ("cls_first", C.c_int), ("cls_count", C.c_int), ("max_per_frame", C.c_int), ("keep_aspect", C.c_int),
                 ("out", C.c_void_p), ("out_stride", C.c_size_t), ("slots", C.c_int), ("tw", C.c_int), ("th", C.c_int), ("nhwc", C.c_int),
-                ("rois", C.c_void_p), ("n_out", C.c_void_p), ("frame_kept", C.c_void_p), ("csn", C.c_void_p)]
+                ("rois", C.c_void_p), ("n_out", C.c_void_p), ("frame_kept", C.c_void_p), ("csn", C.c_void_p),
+                ("area", C.c_int)]
 
 
 def seeded_boxes(frames, per, seed=0x0B0C):
