@@ -765,8 +765,8 @@ int mars_yolo_masks(const int8_t *coefs, int n, int nm, const int8_t *proto, int
  * Limits.     1 <= K <= MARS_POSE_MAX_KPT, D = 2 or 3.  Keypoint tensors: int8, exactly K * D channels, on the grid of their head's box
  *             tensor, tensors whose bytes are addressable after a run as the DFL heads' (read where the plan left them: planes, pixel rows,
  *             a channel slice; no plan changes).  Anything else: MARS_ERR_INVALID_TENSOR.
- * Not covered: a file-level finder for pose heads (callers name the tensors); keypoints inside mars_hip_pipe_*; keypoints in the crop or
- *   track stages; OKS-based suppression (the boxes' NMS decides); float32 tensors; anchor-based pose heads. */
+ * Not covered: a file-level finder for pose heads (callers name the tensors); keypoints inside mars_hip_pipe_*; keypoints in the
+ *   track stages (the crop stage takes them: "Aligned crops" below); OKS-based suppression (the boxes' NMS decides); float32 tensors; anchor-based pose heads. */
 #define MARS_POSE_MAX_PER_FRAME 256
 #define MARS_POSE_MAX_KPT 32
 typedef struct { int det, head, cell; } mars_pose_t; /* 12 bytes */
@@ -929,6 +929,91 @@ mars_error_t mars_hip_crop_obb_device(mars_model_t *det_model, const void *frame
 /* The same with the frames in host memory: uploads them, crops, waits. */
 mars_error_t mars_hip_crop_obb(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
                                const mars_hip_roi_opts_t *opts);
+
+/* ------------------------------------------------------------ Aligned crops */
+/* The crop stage for POSE detections ("Pose keypoints" above): an embedder behind the gallery match is trained on ALIGNED inputs -- the
+ * five face landmarks, or shoulders and hips, moved onto fixed template positions by a similarity transform before the crop is taken.
+ * These calls fit that transform to a detection's keypoints by least squares and cut the crop with the sampler of "Rotated crops".
+ * Options (mars_hip_roi_opts_t), the ROI table and the label / identify / track joins are those of "ROI crops".  float32 with every
+ * operation rounded on its own (parentheses give the order), no fused multiply-add, division and square root correctly rounded:
+ *
+ * Inputs per box.  K keypoints mars_kpt_t {x, y, v} in source-frame pixels, frames of W x H.  A template of K points (u_j, v_j) in target
+ *   pixels, pixel centres at i + 0.5, the target tw x th.  A bit mask `use`: bit j set = keypoint j may take part; 0 means all K.  min_vis.
+ * Participating set.  P = the j, ascending, with bit j of `use` set and kpt[j].v >= min_vis (a NaN v does not pass).
+ * Skip rule.  The box is SKIPPED when |P| < 2, or when x, y or v of a participating keypoint is not finite.  A keypoint that does not
+ *   participate may hold anything, NaN included.
+ * Fit (template -> source; a complex least squares: no reflection is possible).  n = (float)|P|; every sum runs over P in ascending j and
+ *   starts from 0.0f:
+ *     qmx = (sum u_j) / n,  qmy = (sum v_j) / n,  pmx = (sum x_j) / n,  pmy = (sum y_j) / n
+ *     dqx = u_j - qmx,  dqy = v_j - qmy,  dpx = x_j - pmx,  dpy = y_j - pmy
+ *     A += (dqx * dpx) + (dqy * dpy);   B += (dqx * dpy) - (dqy * dpx);   D += (dqx * dqx) + (dqy * dqy)
+ *   SKIPPED unless D > 0.   a = A / D,  b = B / D;   SKIPPED unless both are finite.   The crop's centre:
+ *     ux = ((float)tw * 0.5f) - qmx,  uy = ((float)th * 0.5f) - qmy
+ *     cx = pmx + ((a * ux) - (b * uy)),  cy = pmy + ((b * ux) + (a * uy))
+ * Expand.  ae = a * expand,  be = b * expand  (expand == 0 means 1.0): the crop is scaled about its centre.
+ * Size rule.  s = sqrtf((ae * ae) + (be * be));   we = s * (float)tw,  he = s * (float)th.  SKIPPED when we < min_size, he < min_size
+ *   (min_size == 0 means 2), we > 32768, he > 32768, or the centre is outside the frame: unless 0 <= cx <= W and 0 <= cy <= H (a NaN centre
+ *   is outside).  Behind this rule (and W, H <= 32767, which the calls require) every Q16 value below fits an int32.
+ * Geometry, with q16(v) = (int)rintf(v * 65536.0f) (round to nearest even):
+ *     ha = ae * 0.5f,  hb = be * 0.5f
+ *     Ux = q16(ha),  Uy = q16(hb),  Vx = q16(-hb),  Vy = q16(ha),  X0 = q16(cx - 0.5f),  Y0 = q16(cy - 0.5f)
+ *     nw = tw,  nh = th,  px = py = 0
+ * Sampling.  From here the sample positions, the taps, the grey (111) taps outside the frame, the blend, the NV12 conversion and the layouts
+ *   are exactly those of "Rotated crops" with these six integers.
+ * Flags.  MARS_ROI_KEEP_ASPECT and MARS_ROI_AREA are refused (MARS_ERR_INVALID_FILE): the template fixes the geometry, the sampler has four taps.
+ * ROI table.  frame as before; det = the pose record's det, the index in the frame's detection list, so the label, identify and track joins
+ *   work unchanged (host-pointer form: -1).  x0 .. y1 is for the caller's information only, by the rule of "Rotated crops" around (cx, cy):
+ *     ca = |ae| / s,  sa = |be| / s,  ex = ((we * ca) + (he * sa)) * 0.5f,  ey = ((we * sa) + (he * ca)) * 0.5f,
+ *     x0 = (int)floorf(max(cx - ex, 0)),  x1 = (int)ceilf(min(cx + ex, (float)W)),  y0, y1 alike with cy, ey, H.
+ *   A skipped box of the host-pointer form has all four zero.
+ * Fit table.  Beside the ROI table one mars_align_t per slot: the six integers, used = the mask of P, n_used = |P|.  A skipped or empty slot
+ *   is all zeros (a kept one has n_used >= 2).  It lets a caller map crop pixels back into the frame (the position formula of "Rotated
+ *   crops") and see which keypoints carried the fit.
+ * Selection (device chain).  Frame by frame the pose slots of det_model's last pose call are walked in slot order; a slot with det == -1
+ *   ends its frame's list.  The slot's detection dets[f][det] must pass conf >= min_conf and the class window, and the box must not be
+ *   skipped; the kept boxes of a frame stop at max_per_frame (0: no limit).  Kept boxes fill the destination's frames 0, 1, ... up to its
+ *   batch, the rest are counted as dropped; destination frames behind the last crop are -17.  A function of the lists alone: no atomics.
+ * Consequences.  4 participating points, template coordinates multiples of 1/4 and kpt = template + an integer shift: every sum is exact,
+ *   a = 1 and b = 0 exactly, Ux = Vy = 32768, every fraction is 0 and the crop is an exact copy of the frame's pixels minus 128.  The same
+ *   template turned a quarter turn about an integer centre: Ux = 0, Uy = 32768 and the crop is an exact transposed copy.  Exactness needs sums
+ *   that are exact in float32; in general a is within rounding of 1 and the copy is not promised.
+ * Contract.  The pose call was made with src_w / src_h set, so that keypoints and boxes are in camera pixels: what the other crop calls ask.
+ * Refused.  MARS_ERR_INVALID_FILE, before any device work: what the calls of "Rotated crops" refuse about the options, the two flags, no
+ *   align options, num_kpt outside 1 .. MARS_POSE_MAX_KPT, a `use` bit at or above num_kpt, a template value (of the first num_kpt) or a
+ *   min_vis that is not finite.  MARS_ERR_INVALID_TENSOR: det_model holds no pose results (no mars_hip_detect_pose_device since its batch
+ *   was set), K of that call != num_kpt, and what mars_hip_crop_obb_device refuses about the two models.
+ * Not covered: the pipelined mars_hip_pipe_* path; affine or perspective fits; per-keypoint weights; area averaging; merged tile lists. */
+typedef struct {
+    int num_kpt;                            /* K: 1 .. MARS_POSE_MAX_KPT */
+    float tmpl[MARS_POSE_MAX_KPT][2];       /* (u_j, v_j), target pixels; the first K are read */
+    unsigned use;                           /* 0: all K */
+    float min_vis;
+} mars_hip_align_opts_t;
+typedef struct { int X0, Y0, Ux, Uy, Vx, Vy; unsigned used; int n_used; } mars_align_t; /* 32 bytes */
+/* Pure host code, no device: the fit of one keypoint set [K].  1 = kept (fit filled), 0 = skipped (fit zeroed), -1 = bad arguments (what is
+ * "Refused" above about the options, no kpts, no fit).  roi may be NULL; only its x0 .. y1 are written (zeros for a skipped box). */
+int mars_yolo_align_fit(const mars_kpt_t *kpts, const mars_hip_align_opts_t *align, const mars_hip_roi_opts_t *opts, int tw, int th,
+                        mars_align_t *fit, mars_roi_t *roi);
+/* The standard 5-point face template (the public ArcFace 112 x 112 positions: eyes, nose tip, mouth corners) scaled by tw / 112 and
+ * th / 112 into tmpl[0 .. 4]; returns K = 5, or -1 without tmpl or with a non-positive size. */
+int mars_yolo_align_template_face5(int tw, int th, float tmpl[][2]);
+/* mars_yolo_crop_boxes for keypoint sets: host pointers in and out, runs on the GPU.  kpts = [n_boxes][K].  Only the skip rule applies; a
+ * skipped box's crop is all -17, its ROI rectangle and its fit record are zeros.  rois and fits may be NULL. */
+mars_error_t mars_yolo_crop_aligned(const unsigned char *frames, int n_frames, const mars_kpt_t *kpts, const int *frame_of_box, int n_boxes,
+                                    const mars_hip_align_opts_t *align, const mars_hip_roi_opts_t *opts, int tw, int th, int nhwc,
+                                    signed char *out, mars_roi_t *rois, mars_align_t *fits);
+/* mars_hip_crop_detections_device over the keypoints the last mars_hip_detect_pose_device of det_model left in HBM.  Enqueues only; stream
+ * and event ordering are exactly those of mars_hip_crop_detections_device (the pose stage's kernels run in front of the event that call
+ * waits for), and mars_hip_roi_results serves this call too. */
+mars_error_t mars_hip_crop_pose_device(mars_model_t *det_model, const void *frames_dev, mars_model_t *dst_model, int input_index,
+                                       const mars_hip_roi_opts_t *opts, const mars_hip_align_opts_t *align);
+/* The same with the frames in host memory: uploads them, crops, waits. */
+mars_error_t mars_hip_crop_pose(mars_model_t *det_model, const unsigned char *frames, mars_model_t *dst_model, int input_index,
+                                const mars_hip_roi_opts_t *opts, const mars_hip_align_opts_t *align);
+/* Waits.  The fit table of the last aligned crop call into dst_model, beside mars_hip_roi_results: min(cap, the batch of that call)
+ * records, slot k beside ROI record k, zeros behind the kept ones.  MARS_ERR_INVALID_TENSOR unless the last crop call into dst_model was
+ * an aligned one. */
+mars_error_t mars_hip_align_results(mars_model_t *dst_model, mars_align_t *fits, int cap);
 
 /* --------------------------------------------------------- Tiled inference */
 /* Sliced inference for frames much larger than the graph input: a camera frame is cut into overlapping tiles, every tile is one frame of the

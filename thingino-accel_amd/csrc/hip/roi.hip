@@ -12,7 +12,9 @@
 //                             blends from LDS, puts the strip's bytes together in LDS and stores contiguous runs 16 bytes at a time.
 //   roi_area_crop_kernel      the crop under MARS_ROI_AREA / MARS_TILE_AREA: down-scaled axes are box-filtered; a strip streams over its source rows;
 //   roi_rot_crop_kernel<FMT>  the same strip for an ORIENTED box ("Rotated crops"): samples along the box's axes from a staged bounding rectangle;
-//                             the select and rectangle kernels serve it through their ROT flag.
+//                             the select and rectangle kernels serve it through their SRC_ROT list source.  With FIT the six integers of
+//                             its sample frame come from a table instead ("Aligned crops"): align_fit, a least-squares similarity of a
+//                             template onto pose keypoints, run by the select and rectangle kernels over their SRC_POSE list source.
 // Nothing here uses atomics: a slot number is a function of the lists alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,11 +90,70 @@ __device__ __forceinline__ rot_geom_t rot_geom(const obb_t d, const float we, co
     return g;
 }
 
+// ---- "Aligned crops": the least-squares similarity that carries the template onto a keypoint set -> the skip decision, the Q16 sample frame,
+// the mask of the keypoints that carried the fit and the enclosing rectangle.  float32, every operation rounded on its own, sums in ascending j
+struct align_t { int X0, Y0, Ux, Uy, Vx, Vy; unsigned used; int n_used; }; // mars_align_t
+static_assert(sizeof(align_t) == 32, "mars_align_t is 32 bytes");
+
+// false = skipped: `a` and the rectangle are then all zeros
+__device__ __forceinline__ bool align_fit(const kpt_t *kp, const mhip_roi_t &p, align_t &a, int &x0, int &y0, int &x1, int &y1) {
+    a = {0, 0, 0, 0, 0, 0, 0u, 0};
+    x0 = y0 = x1 = y1 = 0;
+    unsigned used = 0u;
+    float sqx = 0.0f, sqy = 0.0f, spx = 0.0f, spy = 0.0f;
+    for (int j = 0; j < p.num_kpt; j++) {
+        if (!((p.use >> j) & 1u)) continue;
+        const kpt_t k = kp[j];
+        if (!(k.v >= p.min_vis)) continue; // (a NaN visibility does not take part)
+        if (!(isfinite(k.x) && isfinite(k.y) && isfinite(k.v))) return false;
+        used |= 1u << j;
+        sqx = __fadd_rn(sqx, p.tmpl[j][0]); sqy = __fadd_rn(sqy, p.tmpl[j][1]);
+        spx = __fadd_rn(spx, k.x); spy = __fadd_rn(spy, k.y);
+    }
+    const int cnt = __popc(used);
+    if (cnt < 2) return false;
+    const float n = (float)cnt;
+    const float qmx = __fdiv_rn(sqx, n), qmy = __fdiv_rn(sqy, n), pmx = __fdiv_rn(spx, n), pmy = __fdiv_rn(spy, n);
+    float A = 0.0f, B = 0.0f, D = 0.0f;
+    for (int j = 0; j < p.num_kpt; j++) {
+        if (!((used >> j) & 1u)) continue;
+        const kpt_t k = kp[j];
+        const float dqx = __fsub_rn(p.tmpl[j][0], qmx), dqy = __fsub_rn(p.tmpl[j][1], qmy), dpx = __fsub_rn(k.x, pmx), dpy = __fsub_rn(k.y, pmy);
+        A = __fadd_rn(A, __fadd_rn(__fmul_rn(dqx, dpx), __fmul_rn(dqy, dpy)));
+        B = __fadd_rn(B, __fsub_rn(__fmul_rn(dqx, dpy), __fmul_rn(dqy, dpx)));
+        D = __fadd_rn(D, __fadd_rn(__fmul_rn(dqx, dqx), __fmul_rn(dqy, dqy)));
+    }
+    if (!(D > 0.0f)) return false;
+    const float fa = __fdiv_rn(A, D), fb = __fdiv_rn(B, D);
+    if (!(isfinite(fa) && isfinite(fb))) return false;
+    const float ux = __fsub_rn(__fmul_rn((float)p.tw, 0.5f), qmx), uy = __fsub_rn(__fmul_rn((float)p.th, 0.5f), qmy);
+    const float cx = __fadd_rn(pmx, __fsub_rn(__fmul_rn(fa, ux), __fmul_rn(fb, uy))), cy = __fadd_rn(pmy, __fadd_rn(__fmul_rn(fb, ux), __fmul_rn(fa, uy)));
+    const float ae = __fmul_rn(fa, p.expand), be = __fmul_rn(fb, p.expand);
+    const float s = __fsqrt_rn(__fadd_rn(__fmul_rn(ae, ae), __fmul_rn(be, be)));
+    const float we = __fmul_rn(s, (float)p.tw), he = __fmul_rn(s, (float)p.th);
+    if (!(we >= (float)p.min_size && he >= (float)p.min_size && we <= 32768.0f && he <= 32768.0f)) return false; // (a NaN side is skipped)
+    if (!(cx >= 0.0f && cx <= (float)p.w && cy >= 0.0f && cy <= (float)p.h)) return false;                       // (a NaN centre is outside)
+    const float ha = __fmul_rn(ae, 0.5f), hb = __fmul_rn(be, 0.5f);
+    a.Ux = rot_q16(ha); a.Uy = rot_q16(hb); a.Vx = rot_q16(-hb); a.Vy = rot_q16(ha);
+    a.X0 = rot_q16(__fsub_rn(cx, 0.5f)); a.Y0 = rot_q16(__fsub_rn(cy, 0.5f));
+    a.used = used; a.n_used = cnt;
+    const float ac = __fdiv_rn(fabsf(ae), s), as = __fdiv_rn(fabsf(be), s);
+    const float ex = __fmul_rn(__fadd_rn(__fmul_rn(we, ac), __fmul_rn(he, as)), 0.5f), ey = __fmul_rn(__fadd_rn(__fmul_rn(we, as), __fmul_rn(he, ac)), 0.5f);
+    x0 = (int)floorf(fmaxf(__fsub_rn(cx, ex), 0.0f)); x1 = (int)ceilf(fminf(__fadd_rn(cx, ex), (float)p.w));
+    y0 = (int)floorf(fmaxf(__fsub_rn(cy, ey), 0.0f)); y1 = (int)ceilf(fminf(__fadd_rn(cy, ey), (float)p.h));
+    return true;
+}
+
 // One wave per frame.  PHASE 0 counts the frame's kept boxes into frame_kept[f]; PHASE 1 (a second launch: it needs every frame's count) sums
 // the counts of the frames in front into the frame's first slot, walks the list again the same way and writes the table.  A box's rank inside
 // its frame = kept boxes in front of it in the list: the ballot of the 64 boxes in flight, masked below the lane, plus the chunks before.
-// ROT: the lists are oriented boxes (32-byte records and their (cos, sin) pairs) under the skip rule of "Rotated crops".
-template <int PHASE, int ROT>
+// SRC_ROT: the lists are oriented boxes (32-byte records and their (cos, sin) pairs) under the skip rule of "Rotated crops".
+// SRC_POSE: the lists are the frame's pose slots up to the first one with det == -1; a slot's detection passes min_conf and the class window,
+// its keypoints the fit of "Aligned crops", whose record goes beside the ROI entry (PHASE 0 clears the fit table first).
+#define SRC_BOX 0
+#define SRC_ROT 1
+#define SRC_POSE 2
+template <int PHASE, int SRC>
 __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
     const int f = blockIdx.x, lane = threadIdx.x;
     int base = 0;
@@ -114,15 +175,33 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
             p.n_out[1] = all - kept;
         }
     }
-    const int n = min(max(p.counts[f], 0), p.det_cap);
+    const int n_det = min(max(p.counts[f], 0), p.det_cap);
+    int n = SRC == SRC_POSE ? p.pose_max : n_det;
     const det_t *dets = (const det_t *)p.dets + (size_t)f * p.det_cap;
     roi_t *rois = (roi_t *)p.rois;
+    if (SRC == SRC_POSE && PHASE == 0) { // every slot of the fit table is zero before PHASE 1 (a later launch) writes the kept ones
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+        for (int i = f * 64 + lane; i < 2 * p.slots; i += 64 * (int)gridDim.x) ((uint4 *)p.fits)[i] = z;
+    }
     int kept = 0;
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + lane;
         bool ok = false;
         int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-        if (i < n && ROT) {
+        int det_i = i;
+        align_t fit;
+        if (SRC == SRC_POSE) {
+            const size_t k = (size_t)f * p.pose_max + min(i, n - 1);
+            const int di = ((const pose_t *)p.pose_recs)[k].det;
+            const unsigned long long ends = __ballot(i < n && di < 0); // the first such slot ends the list
+            if (ends) n = i0 + __ffsll((long long)ends) - 1;
+            if (i < n && di < n_det) { // (a det beyond the frame's list cannot come from the pose stage: not taken)
+                const det_t d = dets[di];
+                ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
+                     align_fit((const kpt_t *)p.pose_kpts + k * p.num_kpt, p, fit, x0, y0, x1, y1);
+                det_i = di;
+            }
+        } else if (i < n && SRC == SRC_ROT) {
             const size_t k = (size_t)f * p.det_cap + i;
             const obb_t d = ((const obb_t *)p.dets)[k];
             ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
@@ -137,8 +216,9 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
         if (p.max_per_frame > 0 && rank >= p.max_per_frame) ok = false;
         if (PHASE == 1 && ok && base + rank < p.slots) {
             roi_t r;
-            r.frame = f; r.det = i; r.x0 = x0; r.y0 = y0; r.x1 = x1; r.y1 = y1;
+            r.frame = f; r.det = SRC == SRC_POSE ? det_i : i; r.x0 = x0; r.y0 = y0; r.x1 = x1; r.y1 = y1;
             rois[base + rank] = r;
+            if (SRC == SRC_POSE) ((align_t *)p.fits)[base + rank] = fit;
         }
         kept += __popcll(mask);
         if (p.max_per_frame > 0 && kept >= p.max_per_frame) {
@@ -149,7 +229,7 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
     if (PHASE == 0 && lane == 0) p.frame_kept[f] = kept;
 }
 
-template <int ROT>
+template <int SRC>
 __global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i == 0) {
@@ -162,7 +242,11 @@ __global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
     r.det = -1;
     const bool ok = r.frame >= 0 && r.frame < p.n_frames;
     r.x0 = r.y0 = r.x1 = r.y1 = 0;
-    if (ROT) {
+    if (SRC == SRC_POSE) { // box i = the K keypoints at i * K; its fit record beside the ROI entry (zeros: skipped)
+        align_t fit = {0, 0, 0, 0, 0, 0, 0u, 0};
+        if (ok) align_fit((const kpt_t *)p.boxes + (size_t)i * p.num_kpt, p, fit, r.x0, r.y0, r.x1, r.y1);
+        ((align_t *)p.fits)[i] = fit;
+    } else if (SRC == SRC_ROT) {
         const obb_t d = ((const obb_t *)p.boxes)[i];
         if (ok) rot_rect(d, p.csn[2 * i], p.csn[2 * i + 1], p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
     } else {
@@ -581,7 +665,8 @@ __device__ __forceinline__ long long rot_extent(const int cn, const int rn, cons
     return ((2LL * (cn - 1) * abs(u) + 2LL * (rn - 1) * abs(v)) >> 16) + 3 + pad;
 }
 
-template <int FMT>
+// FIT: the six integers come from the slot's entry of the fit table ("Aligned crops") instead of the obb record and its (cos, sin) pair
+template <int FMT, int FIT>
 __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, const int off_buf) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int tid = threadIdx.x;
@@ -592,9 +677,16 @@ __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, c
     bool live = slot < p.n_out[0];
     roi_t r = {0, 0, 0, 0, 0, 0};
     if (live) r = ((const roi_t *)p.rois)[slot];
-    live = live && r.x1 > r.x0 && r.frame >= 0 && r.frame < p.n_frames && (r.det < 0 ? p.boxes != nullptr : (p.dets != nullptr && r.det < p.det_cap));
+    if (FIT) live = live && r.frame >= 0 && r.frame < p.n_frames;
+    else live = live && r.x1 > r.x0 && r.frame >= 0 && r.frame < p.n_frames && (r.det < 0 ? p.boxes != nullptr : (p.dets != nullptr && r.det < p.det_cap));
     rot_geom_t g = {0, 0, 0, 0, 0, 0, p.tw, p.th, 0, 0};
-    if (live) {
+    if (FIT) {
+        if (live) {
+            const align_t a = ((const align_t *)p.fits)[slot];
+            live = a.n_used > 0; // (zeros: a skipped box)
+            g.X0 = a.X0; g.Y0 = a.Y0; g.Ux = a.Ux; g.Uy = a.Uy; g.Vx = a.Vx; g.Vy = a.Vy;
+        }
+    } else if (live) {
         const size_t k = r.det < 0 ? (size_t)slot : (size_t)r.frame * p.det_cap + r.det;
         const obb_t d = ((const obb_t *)(r.det < 0 ? p.boxes : p.dets))[k];
         const float cs = p.csn[2 * k], sn = p.csn[2 * k + 1];
@@ -700,30 +792,46 @@ static bool roi_common_ok(const mhip_roi_t *p) {
            (p->fmt == 0 || (p->fmt == 1 && !(p->w & 1) && !(p->h & 1) && !(p->nv12_flags & ~3u)));
 }
 
-static int roi_select(const mhip_roi_t *p, const bool rot) {
-    if (!roi_common_ok(p) || !p->dets || !p->counts || !p->frame_kept || p->det_cap <= 0 || p->cls_count < 0 || p->max_per_frame < 0 || rot != (p->csn != nullptr)) return -1;
-    const dim3 g((unsigned)p->n_frames);
-    if (rot) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, 1>), g, dim3(64), 0, mhip_stream_native(), *p);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, 1>), g, dim3(64), 0, mhip_stream_native(), *p);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, 0>), g, dim3(64), 0, mhip_stream_native(), *p);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, 0>), g, dim3(64), 0, mhip_stream_native(), *p);
-    }
-    return mhip_check(hipGetLastError(), rot ? "roi select (oriented)" : "roi select");
+// what the align calls need on top: the fit table (16-byte aligned: it is cleared 16 bytes at a time), a template size and a mask inside it, a target
+static bool roi_align_ok(const mhip_roi_t *p) {
+    return p->fits && !((uintptr_t)p->fits & 15) && p->num_kpt >= 1 && p->num_kpt <= MHIP_POSE_MAX_KPT && p->use != 0 &&
+           (p->num_kpt == 32 || !(p->use >> p->num_kpt)) && p->tw > 0 && p->th > 0 && !p->csn;
 }
-extern "C" int mhip_roi_select(const mhip_roi_t *p) { return roi_select(p, false); }
-extern "C" int mhip_roi_rot_select(const mhip_roi_t *p) { return roi_select(p, true); }
 
-static int roi_rects(const mhip_roi_t *p, const bool rot) {
-    if (!roi_common_ok(p) || !p->boxes || !p->frame_of_box || p->n_boxes <= 0 || p->n_boxes > p->slots || rot != (p->csn != nullptr)) return -1;
-    const dim3 g((unsigned)((p->n_boxes + 255) / 256));
-    if (rot) hipLaunchKernelGGL(roi_rects_kernel<1>, g, dim3(256), 0, mhip_stream_native(), *p);
-    else hipLaunchKernelGGL(roi_rects_kernel<0>, g, dim3(256), 0, mhip_stream_native(), *p);
-    return mhip_check(hipGetLastError(), rot ? "roi rects (oriented)" : "roi rects");
+static int roi_select(const mhip_roi_t *p, const int src) {
+    if (!roi_common_ok(p) || !p->dets || !p->counts || !p->frame_kept || p->det_cap <= 0 || p->cls_count < 0 || p->max_per_frame < 0 ||
+        (src == SRC_ROT) != (p->csn != nullptr))
+        return -1;
+    if (src == SRC_POSE && (!roi_align_ok(p) || !p->pose_recs || !p->pose_kpts || p->pose_max <= 0)) return -1;
+    const dim3 g((unsigned)p->n_frames);
+    if (src == SRC_POSE) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, SRC_POSE>), g, dim3(64), 0, mhip_stream_native(), *p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, SRC_POSE>), g, dim3(64), 0, mhip_stream_native(), *p);
+    } else if (src == SRC_ROT) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, SRC_ROT>), g, dim3(64), 0, mhip_stream_native(), *p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, SRC_ROT>), g, dim3(64), 0, mhip_stream_native(), *p);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, SRC_BOX>), g, dim3(64), 0, mhip_stream_native(), *p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, SRC_BOX>), g, dim3(64), 0, mhip_stream_native(), *p);
+    }
+    return mhip_check(hipGetLastError(), src == SRC_POSE ? "roi select (aligned)" : src == SRC_ROT ? "roi select (oriented)" : "roi select");
 }
-extern "C" int mhip_roi_rects(const mhip_roi_t *p) { return roi_rects(p, false); }
-extern "C" int mhip_roi_rot_rects(const mhip_roi_t *p) { return roi_rects(p, true); }
+extern "C" int mhip_roi_select(const mhip_roi_t *p) { return roi_select(p, SRC_BOX); }
+extern "C" int mhip_roi_rot_select(const mhip_roi_t *p) { return roi_select(p, SRC_ROT); }
+extern "C" int mhip_roi_align_select(const mhip_roi_t *p) { return roi_select(p, SRC_POSE); }
+
+static int roi_rects(const mhip_roi_t *p, const int src) {
+    if (!roi_common_ok(p) || !p->boxes || !p->frame_of_box || p->n_boxes <= 0 || p->n_boxes > p->slots || (src == SRC_ROT) != (p->csn != nullptr)) return -1;
+    if (src == SRC_POSE && !roi_align_ok(p)) return -1;
+    const dim3 g((unsigned)((p->n_boxes + 255) / 256));
+    if (src == SRC_POSE) hipLaunchKernelGGL(roi_rects_kernel<SRC_POSE>, g, dim3(256), 0, mhip_stream_native(), *p);
+    else if (src == SRC_ROT) hipLaunchKernelGGL(roi_rects_kernel<SRC_ROT>, g, dim3(256), 0, mhip_stream_native(), *p);
+    else hipLaunchKernelGGL(roi_rects_kernel<SRC_BOX>, g, dim3(256), 0, mhip_stream_native(), *p);
+    return mhip_check(hipGetLastError(), src == SRC_POSE ? "roi rects (aligned)" : src == SRC_ROT ? "roi rects (oriented)" : "roi rects");
+}
+extern "C" int mhip_roi_rects(const mhip_roi_t *p) { return roi_rects(p, SRC_BOX); }
+extern "C" int mhip_roi_rot_rects(const mhip_roi_t *p) { return roi_rects(p, SRC_ROT); }
+extern "C" int mhip_roi_align_rects(const mhip_roi_t *p) { return roi_rects(p, SRC_POSE); }
 
 extern "C" int mhip_roi_fits(int w, int tw, int fmt) {
     if (w <= 0 || tw <= 0) return 0;
@@ -776,7 +884,18 @@ extern "C" int mhip_roi_rot_crop(const mhip_roi_t *p) {
         return -1;
     const int off_buf = (int)roi_lds_stage(p->tw);
     const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);
-    if (p->fmt) hipLaunchKernelGGL(roi_rot_crop_kernel<1>, g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
-    else hipLaunchKernelGGL(roi_rot_crop_kernel<0>, g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
+    if (p->fmt) hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<1, 0>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<0, 0>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
     return mhip_check(hipGetLastError(), p->fmt ? "rotated roi crop (nv12)" : "rotated roi crop");
+}
+
+extern "C" int mhip_roi_align_crop(const mhip_roi_t *p) {
+    if (!roi_common_ok(p) || !roi_align_ok(p) || !p->frames || !p->out || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 ||
+        !mhip_roi_rot_fits(p->w, p->h, p->tw))
+        return -1;
+    const int off_buf = (int)roi_lds_stage(p->tw);
+    const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);
+    if (p->fmt) hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<1, 1>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<0, 1>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
+    return mhip_check(hipGetLastError(), p->fmt ? "aligned roi crop (nv12)" : "aligned roi crop");
 }

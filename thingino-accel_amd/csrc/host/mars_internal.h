@@ -205,6 +205,8 @@ typedef struct mars_model_ext {
     int roi_cap_slots, roi_cap_frames;
     int roi_slots;      /* slots of the last crop call (its batch then); 0 = there was none */
     struct mars_model_ext *roi_from; /* ... whose detections they were (compared, never followed: mars_free clears it) */
+    void *roi_fit_dev;  /* "Aligned crops": [roi_cap_slots] x mars_align_t beside the table, from the first aligned crop call on; grown and released with it */
+    int roi_fit_slots;  /* roi_slots if the last crop call was an aligned one, else 0 */
     /* second-stage labels (mars_classify.c) */
     mars_block_t cls;   /* pooled results of THIS model: [frames][nsplit][C] partial sums, [frames][C] sums, [frames][top_k] entries */
     size_t cls_sums_off, cls_top_off;

@@ -431,6 +431,14 @@ typedef struct {
     const float *csn;                           /* the mhip_roi_rot_* calls only ("Rotated crops"): dets / boxes hold records of 32 bytes (mars_obb_t)
                                                  * and csn the (cos, sin) pair of every one of them, index-aligned */
     int area;                                   /* mhip_roi_crop only: box-filter the down-scaled axes ("Area averaging"); needs mhip_roi_area_fits */
+    /* the mhip_roi_align_* calls only ("Aligned crops"); at the end: the other calls' fields keep their places */
+    void *fits;                                 /* [slots] records of 32 bytes (mars_align_t): written by select / rects, read by the crop */
+    const void *pose_recs, *pose_kpts;          /* mhip_roi_align_select: [n_frames][pose_max] records of 12 bytes and [n_frames][pose_max][num_kpt]
+                                                 * keypoints of 12 bytes, as mhip_pose leaves them; mhip_roi_align_rects: `boxes` = [n_boxes][num_kpt] keypoints */
+    int pose_max, num_kpt;                      /* num_kpt: 1 .. 32 */
+    unsigned use;                               /* resolved: a non-empty mask below 1 << num_kpt */
+    float min_vis;
+    float tmpl[32][2];                          /* the template, target pixels */
 } mhip_roi_t;
 int mhip_roi_select(const mhip_roi_t *p); /* the selection rules over the detection lists, frame-major, list order; two launches */
 int mhip_roi_rects(const mhip_roi_t *p);  /* the rectangle rule alone: slot i = box i (x1 == x0: skipped), n_out = {n_boxes, 0} */
@@ -443,6 +451,13 @@ int mhip_roi_rot_select(const mhip_roi_t *p);
 int mhip_roi_rot_rects(const mhip_roi_t *p);
 int mhip_roi_rot_crop(const mhip_roi_t *p);
 int mhip_roi_rot_fits(int w, int h, int tw); /* 1: positions of such frames fit the Q16 integers and a strip of such a target fits the LDS */
+/* the same three for "Aligned crops": the lists are pose slots (select: slot order, det == -1 ends a frame's list, the slot's detection
+ * passes min_conf and the class window) or a caller's keypoint sets (rects); the least-squares fit of the template decides the skip and
+ * gives the six Q16 integers, written beside the ROI entry into `fits` (skipped and empty slots: zeros); the crop kernel is the rotated
+ * sampler reading its geometry from `fits`.  mhip_roi_rot_fits is the size check. */
+int mhip_roi_align_select(const mhip_roi_t *p);
+int mhip_roi_align_rects(const mhip_roi_t *p);
+int mhip_roi_align_crop(const mhip_roi_t *p);
 
 /* ---- second-stage labels (classify.hip): int8 feature maps -> per-channel int32 sums -> ranked top-K entries; include/mars_hip.h
  * "Second-stage labels" states the arithmetic.  Every pointer is device memory. */

@@ -169,6 +169,14 @@ class PoseOpts(C.Structure):  # mars_hip_pose_opts_t: zero = default in every fi
                 ("min_conf", C.c_float), ("max_per_frame", C.c_int)]
 
 
+ALIGN_DTYPE = np.dtype([("X0", "<i4"), ("Y0", "<i4"), ("Ux", "<i4"), ("Uy", "<i4"), ("Vx", "<i4"), ("Vy", "<i4"), ("used", "<u4"),
+                        ("n_used", "<i4")])                              # mars_align_t
+
+
+class AlignOpts(C.Structure):  # mars_hip_align_opts_t: zero = default in every field but num_kpt and the template
+    _fields_ = [("num_kpt", C.c_int), ("tmpl", (C.c_float * 2) * POSE_MAX_KPT), ("use", C.c_uint), ("min_vis", C.c_float)]
+
+
 OBB_AGNOSTIC = 1                                                        # MARS_OBB_AGNOSTIC
 OBB_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("conf", "<f4"), ("cls", "<i4"), ("angle", "<f4"),
                       ("pred", "<i4")])                                  # mars_obb_t
@@ -195,6 +203,7 @@ assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
 assert TILE_DTYPE.itemsize == 16 and TILE_SRC_DTYPE.itemsize == 8 and TILE_STATS_DTYPE.itemsize == 24 and C.sizeof(TileOpts) == 48
 assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
 assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
+assert ALIGN_DTYPE.itemsize == 32 and C.sizeof(AlignOpts) == 268
 assert C.sizeof(MaskRec) == MASK_DTYPE.itemsize == 24 and C.sizeof(SegOpts) == 52
 assert C.sizeof(TrackRec) == TRACK_DTYPE.itemsize == 8 and C.sizeof(TrackState) == TRACK_STATE_DTYPE.itemsize == 48
 
@@ -244,6 +253,8 @@ EXPORTS = {
                    "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints",
                    "mars_hip_detect_obb_device", "mars_hip_obb_results", "mars_hip_detect_obb", "mars_hip_obb_ms", "mars_yolo_obb_nms",
                    "mars_yolo_obb_corners", "mars_yolo_crop_obb", "mars_hip_crop_obb_device", "mars_hip_crop_obb",
+                   "mars_yolo_align_fit", "mars_yolo_align_template_face5", "mars_yolo_crop_aligned", "mars_hip_crop_pose_device",
+                   "mars_hip_crop_pose", "mars_hip_align_results",
                    "mars_tile_grid", "mars_hip_preprocess_tiles_device", "mars_hip_preprocess_tiles", "mars_hip_merge_tiles_device",
                    "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
@@ -331,6 +342,13 @@ def lib():
     L.mars_yolo_crop_obb.argtypes = L.mars_yolo_crop_boxes.argtypes
     L.mars_hip_crop_obb_device.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
     L.mars_hip_crop_obb.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts)]
+    L.mars_yolo_align_fit.argtypes = [C.c_void_p, P(AlignOpts), P(RoiOpts), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.mars_yolo_align_template_face5.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.mars_yolo_crop_aligned.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, P(AlignOpts), P(RoiOpts), C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_crop_pose_device.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts), P(AlignOpts)]
+    L.mars_hip_crop_pose.argtypes = [P(MarsModel), C.c_void_p, P(MarsModel), C.c_int, P(RoiOpts), P(AlignOpts)]
+    L.mars_hip_align_results.argtypes = [P(MarsModel), C.c_void_p, C.c_int]
     L.mars_yolo_classify_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P(ClsOpts), C.c_void_p, C.c_void_p]
     L.mars_hip_classify_device.argtypes = [P(MarsModel), P(ClsOpts)]
     L.mars_hip_classify_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int)]
@@ -540,6 +558,63 @@ def crop_obb(frames, boxes, frame_of_box, opts, tw, th, nhwc=True):
     """mars_yolo_crop_obb: crop_boxes for oriented boxes (OBB_DTYPE records), each cut along its own axes ("Rotated crops"); x0 .. y1 of the
     ROI records = the enclosing rectangle"""
     return _crop_host("mars_yolo_crop_obb", OBB_DTYPE, frames, boxes, frame_of_box, opts, tw, th, nhwc)
+
+
+def align_opts(tmpl, use=0, min_vis=0.0):
+    """mars_hip_align_opts_t ("Aligned crops"): tmpl = K template points (u, v) in target pixels; use = the mask of the keypoints that may take
+    part (0: all K); min_vis = the visibility a keypoint needs.  More than POSE_MAX_KPT points give num_kpt = their number, which the
+    library refuses"""
+    t = np.asarray(tmpl, dtype=np.float32).reshape(-1, 2)
+    o = AlignOpts()
+    o.num_kpt = len(t)
+    for j in range(min(len(t), POSE_MAX_KPT)):
+        o.tmpl[j][0], o.tmpl[j][1] = float(t[j, 0]), float(t[j, 1])
+    o.use, o.min_vis = int(use), float(min_vis)
+    return o
+
+
+def align_template_face5(tw, th):
+    """mars_yolo_align_template_face5: the public 5-point face template scaled to a tw x th target -> float32 [5][2]"""
+    t = np.zeros((5, 2), dtype=np.float32)
+    if lib().mars_yolo_align_template_face5(int(tw), int(th), t.ctypes.data) != 5:
+        raise ValueError("mars_yolo_align_template_face5 refuses this size")
+    return t
+
+
+def align_fit(kpts, align, opts, tw, th):
+    """mars_yolo_align_fit, pure host code: one keypoint set (KPT_DTYPE [K]) -> (kept, one ALIGN_DTYPE record, (x0, y0, x1, y1)); ValueError
+    where the library returns -1"""
+    k = np.ascontiguousarray(kpts, dtype=KPT_DTYPE).reshape(-1)
+    if k.size < align.num_kpt:
+        raise ValueError("%d keypoints for a template of %d" % (k.size, align.num_kpt))
+    fit = np.zeros((), dtype=ALIGN_DTYPE)
+    roi = np.zeros((), dtype=ROI_DTYPE)
+    rc = lib().mars_yolo_align_fit(k.ctypes.data, C.byref(align), C.byref(opts), int(tw), int(th), fit.ctypes.data, roi.ctypes.data)
+    if rc < 0:
+        raise ValueError("mars_yolo_align_fit refuses these arguments")
+    return bool(rc), fit, (int(roi["x0"]), int(roi["y0"]), int(roi["x1"]), int(roi["y1"]))
+
+
+def crop_aligned(frames, kpts, frame_of_box, align, opts, tw, th, nhwc=True):
+    """mars_yolo_crop_aligned: crop_boxes for keypoint sets (KPT_DTYPE [n_boxes][K]), each fitted to the template of `align` and cut with the
+    rotated sampler ("Aligned crops") -> (int8 crops, ROI_DTYPE records, ALIGN_DTYPE records); a skipped box: -17, zeros, zeros"""
+    a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    fb = opts.src_w * opts.src_h * 3 // (2 if opts.src_format == CAMERA_NV12 else 1)
+    if fb <= 0 or a.size % fb:
+        raise ValueError("frames of %d x %d are %d bytes each, got %d" % (opts.src_w, opts.src_h, fb, a.size))
+    K = max(int(align.num_kpt), 1)
+    k = np.ascontiguousarray(kpts, dtype=KPT_DTYPE).reshape(-1, K)
+    fo = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
+    if fo.size != len(k):
+        raise ValueError("one frame index per keypoint set")
+    out = np.zeros((len(k), tw * th * 3), dtype=np.int8)
+    rois = np.zeros(len(k), dtype=ROI_DTYPE)
+    fits = np.zeros(len(k), dtype=ALIGN_DTYPE)
+    rc = lib().mars_yolo_crop_aligned(a.ctypes.data, a.size // fb, k.ctypes.data, fo.ctypes.data, len(k), C.byref(align), C.byref(opts), tw, th,
+                                      int(bool(nhwc)), out.ctypes.data, rois.ctypes.data, fits.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_crop_aligned")
+    return out, rois, fits
 
 
 def tile_grid(W, H, tile_w, tile_h, overlap_x=0, overlap_y=0):
@@ -1233,6 +1308,30 @@ class Model:
         rc = lib().mars_hip_crop_obb_device(det_model.p, C.c_void_p(frames_dev), self.p, input_index, C.byref(opts))
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_crop_obb_device")
+
+    def crop_pose_detections(self, det_model, frames, opts, align, input_index=0):
+        """crop_detections over the keypoints det_model's last detect_pose_device left in HBM, each set fitted to the template of `align`
+        (align_opts(...)) and cut aligned: frames = uint8 host array, uploaded, the call waits (mars_hip_crop_pose)"""
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        rc = lib().mars_hip_crop_pose(det_model.p, a.ctypes.data, self.p, input_index, C.byref(opts), C.byref(align) if align is not None else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_crop_pose")
+
+    def crop_pose_detections_device(self, det_model, frames_dev, opts, align, input_index=0):
+        """the same with frames_dev = a device address (DeviceBuffer.ptr); enqueues only (mars_hip_crop_pose_device)"""
+        rc = lib().mars_hip_crop_pose_device(det_model.p, C.c_void_p(frames_dev), self.p, input_index, C.byref(opts),
+                                             C.byref(align) if align is not None else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_crop_pose_device")
+
+    def align_results(self):
+        """-> ALIGN_DTYPE [batch]: the fit records of the last aligned crop call, record k beside roi_results()[0][k], zeros behind the kept
+        ones (mars_hip_align_results); waits"""
+        fits = np.zeros(self.batch, dtype=ALIGN_DTYPE)
+        rc = lib().mars_hip_align_results(self.p, fits.ctypes.data, self.batch)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_align_results")
+        return fits
 
     def roi_results(self):
         """-> (ROI_DTYPE records of the crops the last crop_detections() wrote, frame k of the input <- rois[k]; boxes dropped for want of a frame)"""
