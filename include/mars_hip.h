@@ -705,8 +705,9 @@ mars_error_t mars_hip_track(mars_model_t *det_model, mars_hip_tracker_t *t, cons
  * Limits.     1 <= nm <= MARS_SEG_MAX_NM.  Coefficient tensors: int8, nm channels, on the grid of their head's box tensor.  Prototype tensor:
  *             int8, nm channels.  All of them tensors whose bytes are addressable after a run, as the DFL heads' (read where the plan left
  *             them: planes, pixel rows, a channel slice; no plan changes).  Anything else: MARS_ERR_INVALID_TENSOR.
- * Not covered: a file-level finder for seg heads (no shipped file has one: callers name the tensors); masks at input or camera resolution
- *   (upsampling); masks inside mars_hip_pipe_*; masks in the crop or track stages; nm > 64; float32 tensors; anchor-based seg heads. */
+ * Not covered: a file-level finder for seg heads (no shipped file has one: callers name the tensors); masks inside mars_hip_pipe_*; masks
+ *   in the crop or track stages; nm > 64; float32 tensors; anchor-based seg heads.  (Masks at input or camera resolution: "Instance masks in
+ *   frame pixels" below.) */
 #define MARS_SEG_MAX_PER_FRAME 64
 #define MARS_SEG_MAX_NM 64
 typedef struct { int det, x0, y0, x1, y1, area; } mars_mask_t; /* 24 bytes */
@@ -738,6 +739,64 @@ float mars_hip_mask_ms(mars_model_t *model);
  * [n][ph][(pw + 31) / 32].  0, or -1: an argument out of range, no device, or a failed launch. */
 int mars_yolo_masks(const int8_t *coefs, int n, int nm, const int8_t *proto, int ph, int pw, const mars_det_t *boxes, int in_w, int in_h,
                     float s, float logit_min, mars_mask_t *recs, uint32_t *words);
+
+/* ------------------------------------------- Instance masks in frame pixels */
+/* The masks of "Instance masks" on the grid of the frame the caller sent: the letterbox undone, the prototype-size dots up-sampled (bilinear,
+ * pixel centres aligned, weights in 1/256) and cut to the box, on the device.  Integers up to the one float32 product and compare of
+ * "Instance masks": everything is defined to the bit.
+ *
+ * Grid.       out_w x out_h.  0 / 0 in the options: src_w x src_h of the DFL options when they map through the letterbox, otherwise the graph
+ *             input in_w x in_h.  1 <= out_w, out_h <= MARS_MASK_NATIVE_MAX, and out_h * ((out_w + 31) / 32) <= 2^24 as for the prototype masks.
+ * Geometry.   With the letterbox mapping (src_w > 0) (nw, nh, px, py) are the integers of the boxes' letterbox rule for src_w x src_h frames:
+ *             scale = fminf((float)in_w / src_w, (float)in_h / src_h); nw = (int)(src_w * scale); nh = (int)(src_h * scale); px = (in_w - nw) / 2;
+ *             py = (in_h - nh) / 2.  Without it nw = in_w, nh = in_h, px = py = 0.
+ * Taps.       int64, exact.  Output column X: the centre of the pixel carried through the letterbox into prototype coordinates is u = N / D,
+ *               N = (2X + 1) * nw * PW + 2 * out_w * px * PW - out_w * in_w;   D = 2 * out_w * in_w
+ *             (the source frame's width cancels: the grid spans the letterboxed content).  i0 = floor(N / D), a true floor (N may be negative);
+ *             r = N - i0 * D;  w1 = (r * 256) / D, in 0 .. 255;  w0 = 256 - w1;  ia = clamp(i0, 0, PW - 1);  ib = clamp(i0 + 1, 0, PW - 1).
+ *             Output row Y alike with nh, py, PH, in_h and out_h.
+ * Value.      With dot(x, y) the int32 dot of "Instance masks":
+ *               S = wy0 * (wx0 * dot(ia, ja) + wx1 * dot(ib, ja)) + wy1 * (wx0 * dot(ia, jb) + wx1 * dot(ib, jb)),  int64, |S| <= 2^36.
+ * Bit.        bit = ((float)S * s16 > logit_min).  (float)S rounds to nearest even; s16 = s * 1.52587890625e-05f (2^-16), ONE float32 product
+ *             of the product scale s of "Instance masks".  The options mean what they mean there.
+ * Rectangle.  From the record mars_hip_detect_results returns -- frame pixels under the mapping, graph-input pixels otherwise: the BASE grid
+ *             base_w x base_h = src_w x src_h or in_w x in_h -- by the rule of "Instance masks" with fx = (float)out_w / (float)base_w, fy =
+ *             (float)out_h / (float)base_h and the bounds clamped to 0 .. out_w and 0 .. out_h (the same floorf / ceilf, the same NaN rule).
+ * Cut, selection, output.  As in "Instance masks": slot j holds a mars_mask_t in OUTPUT pixels and out_h rows of (out_w + 31) / 32 words,
+ *             padding bits 0; unused slots {-1, 0, 0, 0, 0, 0} and all-zero words.
+ * Refused.    Down-scaling: out_w * in_w < nw * PW or out_h * in_h < nh * PH.  A size out of range; an axis beyond 2^20 (in_w, in_h, PW, PH:
+ *             the int64 terms stay exact below it); a set flag bit; everything mars_hip_detect_seg_device refuses.  MARS_ERR_INVALID_TENSOR.
+ * Consequence.  Identity geometry and out = PW x PH: N / D = X exactly, w1 = 0, S = 65536 * dot, and every bit is the prototype mask's bit.
+ * Not covered: down-scaled masks (area averaging is another feature); masks inside mars_hip_pipe_*; masks in the crop, tile-merge or track
+ *   stages; run-length or box-relative output; float32 tensors; nm > 64. */
+#define MARS_MASK_NATIVE_MAX 8192
+/* Zero-initialise; there are no flags yet. */
+typedef struct { int out_w, out_h; unsigned flags; } mars_hip_mask_native_opts_t;
+typedef struct { int in_w, in_h, nw, nh, px, py, base_w, base_h, out_w, out_h; } mars_mask_geom_t; /* 40 bytes */
+/* mars_hip_detect_seg_device with the masks on the output grid: DFL decode + NMS, the selection, the masks, on the auxiliary stream; the
+ * ordering and the waits of the next run are those of mars_hip_detect_seg_device.  The results live in a block of their own: the
+ * prototype-size results of an earlier mars_hip_detect_seg_device on the same model stay fetchable, and this call produces none.  native ==
+ * NULL: every default.  Every refusal comes before anything is allocated or uploaded.  The first call, and every call whose geometry (frame
+ * size, output grid, prototype size) differs from the call before, uploads the tap tables and WAITS for the device twice around that upload
+ * (an earlier call may still read the old tables); calls that repeat the geometry only enqueue. */
+mars_error_t mars_hip_detect_seg_native_device(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_seg_opts_t *seg,
+                                               const mars_hip_mask_native_opts_t *native);
+/* Waits.  recs = [batch][max_per_frame]; words = [batch][max_per_frame][out_h][pitch]; any pointer may be NULL.  MARS_ERR_INVALID_TENSOR before
+ * any native seg call on this model. */
+mars_error_t mars_hip_mask_native_results(mars_model_t *model, mars_mask_t *recs, uint32_t *words, int *out_h, int *out_w, int *pitch_words);
+/* mars_hip_detect_seg_native_device + mars_hip_detect_results + mars_hip_mask_native_results. */
+mars_error_t mars_hip_detect_seg_native(mars_model_t *model, const mars_yolo_dfl_heads_t *heads, const mars_hip_seg_opts_t *seg,
+                                        const mars_hip_mask_native_opts_t *native, mars_det_t *dets, int *counts, mars_mask_t *recs, uint32_t *words);
+/* Device time (ms) of the stage alone (selection + masks) of the last mars_hip_detect_seg_native_device call; waits for it.  < 0: not available. */
+float mars_hip_mask_native_ms(mars_model_t *model);
+/* Host only, no device: the tap table of one axis.  out_n output pixels over the n_content letterboxed pixels that start at `pad` inside an
+ * in_n wide graph input, prototypes P wide: ia, ib, w1 = [out_n] each.  0, or -1: out_n outside 1 .. 8192, in_n or P outside 1 .. 2^20,
+ * n_content < 1, pad < 0, pad + n_content > in_n, a NULL table, or down-scaling (out_n * in_n < n_content * P). */
+int mars_yolo_mask_taps(int out_n, int in_n, int n_content, int pad, int P, int *ia, int *ib, int *w1);
+/* Host pointers in and out, one frame, the same kernel on the GPU; waits.  As mars_yolo_masks, with the boxes in pixels of the geometry's base
+ * grid: recs = [n], words = [n][out_h][(out_w + 31) / 32].  0, or -1: what mars_yolo_masks answers -1 to, or a geometry "Refused" above. */
+int mars_yolo_masks_native(const int8_t *coefs, int n, int nm, const int8_t *proto, int ph, int pw, const mars_det_t *boxes,
+                           const mars_mask_geom_t *geom, float s, float logit_min, mars_mask_t *recs, uint32_t *words);
 
 /* ----------------------------------------------------------- Pose keypoints */
 /* The "-pose" sibling of the anchor-free DFL head (YOLOv8-pose style): beside the box and class convolutions every scale has a KEYPOINT

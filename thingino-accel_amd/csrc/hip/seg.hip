@@ -26,24 +26,16 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "seg_common.hpp"
 #include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-typedef int sg_v4i __attribute__((ext_vector_type(4)));
-
 #define SEG_SEL_THREADS 64
 #define SEG_THREADS 256
 #define SEG_WAVE_UNITS 16                                 // word units a wavefront walks
 #define SEG_WG_UNITS (SEG_WAVE_UNITS * SEG_THREADS / 64)  // ... and a workgroup covers
-
-// floorf / ceilf of v clamped to 0 .. hi BEFORE the conversion (the same integers as clamp((int)..., 0, hi) wherever that is defined; a
-// value beyond the int range lands on the bound, a NaN on 0)
-__device__ __forceinline__ int sg_edge(float v, int hi, bool up) {
-    v = up ? ceilf(v) : floorf(v);
-    return (int)fminf(fmaxf(v, 0.0f), (float)hi);
-}
 
 __global__ __launch_bounds__(SEG_SEL_THREADS) void seg_select_kernel(const mhip_seg_t p) {
     const int f = blockIdx.x, lane = threadIdx.x;
@@ -76,23 +68,6 @@ __global__ __launch_bounds__(SEG_SEL_THREADS) void seg_select_kernel(const mhip_
     }
     if (taken > M) taken = M;
     for (int slot = taken + lane; slot < M; slot += SEG_SEL_THREADS) recs[slot] = mask_t{-1, 0, 0, 0, 0, 0};
-}
-
-// the 16 bytes of channels kb .. kb + 15 (zero from nm on) of the pixel / cell whose channel 0 is at q
-__device__ __forceinline__ sg_v4i sg_load16(const int8_t *q, const int kb, const int nm, const int ch_step) {
-    sg_v4i v = {0, 0, 0, 0};
-    if (kb >= nm) return v;
-    if (ch_step == 1 && kb + 16 <= nm) {
-        __builtin_memcpy(&v, q + kb, 16); // any alignment is served
-        return v;
-    }
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int c = kb + j;
-        const int b = c < nm ? (int)q[(size_t)c * ch_step] & 255 : 0;
-        v[j >> 2] |= b << (8 * (j & 3));
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(SEG_THREADS) void seg_mask_kernel(const mhip_seg_t p) {
@@ -190,6 +165,12 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_mask_kernel(const mhip_seg_t 
     }
 }
 
+// the selection alone, for a caller that has checked p (mhip_seg below; seg_native.hip, with the output grid in pw / ph and the base grid in in_w / in_h)
+extern "C" int mhip_seg_select(const mhip_seg_t *p) {
+    hipLaunchKernelGGL(seg_select_kernel, dim3(p->frames), dim3(SEG_SEL_THREADS), 0, mhip_stream_native(), *p);
+    return mhip_check(hipGetLastError(), "mask selection");
+}
+
 extern "C" int mhip_seg(const mhip_seg_t *p) {
     if (!p || p->nheads <= 0 || p->nheads > 4 || p->frames <= 0 || p->frames > 65535 || !p->proto || !p->boxes || !p->counts || !p->pred ||
         !p->recs || !p->words || p->det_cap <= 0 || p->nm < 1 || p->nm > MHIP_SEG_MAX_NM || p->ph <= 0 || p->pw <= 0 || p->in_w <= 0 ||
@@ -198,8 +179,7 @@ extern "C" int mhip_seg(const mhip_seg_t *p) {
         return -1;
     for (int k = 0; k < p->nheads; k++)
         if (!p->coef[k] || p->cells[k] <= 0 || p->coef_pix_step[k] <= 0 || p->coef_ch_step[k] <= 0) return -1;
-    hipLaunchKernelGGL(seg_select_kernel, dim3(p->frames), dim3(SEG_SEL_THREADS), 0, mhip_stream_native(), *p);
-    int rc = mhip_check(hipGetLastError(), "mask selection");
+    int rc = mhip_seg_select(p);
     if (rc) return rc;
     const int units = p->ph * ((p->pw + 31) / 32);
     hipLaunchKernelGGL(seg_mask_kernel, dim3((units + SEG_WG_UNITS - 1) / SEG_WG_UNITS, p->frames), dim3(SEG_THREADS), 0, mhip_stream_native(), *p);

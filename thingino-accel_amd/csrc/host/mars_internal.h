@@ -226,6 +226,12 @@ typedef struct mars_model_ext {
                          * [frames][seg_max] x mars_mask_t, [frames][seg_max][seg_ph][pitch] x uint32 */
     size_t seg_rec_off, seg_word_off;
     int seg_max, seg_ph, seg_pw; /* of the last seg call */
+    /* instance masks in frame pixels (mars_seg.c): a block of its own, so the prototype-size results above stay fetchable */
+    mars_block_t segn;  /* the tap tables 6 x [MARS_MASK_NATIVE_MAX] x int (at its start: their place does not move with the batch), candidate /
+                         * kept prediction indices, [frames][segn_max] x mars_mask_t, [frames][segn_max][segn_oh][pitch] x uint32 */
+    size_t segn_rec_off, segn_word_off;
+    int segn_max, segn_oh, segn_ow; /* of the last native seg call */
+    int segn_key[10];   /* what the block's tap tables were built for: the mars_mask_geom_t's axes fields and PH, PW; segn_key[8] == 0: none */
     /* pose keypoints (mars_pose.c) */
     mars_block_t pose;  /* the visibility tables [4][256] x float, candidate / kept prediction indices [frames][MARS_YOLO_MAX_DET] x int each,
                          * [frames][pose_max] x mars_pose_t, [frames][pose_max][pose_k] x mars_kpt_t */
@@ -378,6 +384,7 @@ typedef struct {
     float conf, nms;
     int map, px, py;
     float rx, ry;
+    int nw, nh;   /* with map: the letterboxed content's size inside the graph input (the integers px, py, rx and ry come from) */
     int internal; /* some buffer is not a graph output's: one buffer for every batch in flight */
     int *cand_pred, *kept_pred; /* device, or NULL (mars_dfl_resolve leaves NULL): mhip_dfl_heads_t's origin arrays */
     void *premap;               /* device, or NULL: mhip_dfl_heads_t.premap */

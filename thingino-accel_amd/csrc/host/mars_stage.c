@@ -154,11 +154,13 @@ mars_error_t mars_lut_refresh(mars_lut_cache_t *c, void *dst, int n, const float
 /* ---- everything a model holds for these stages, when its device state goes away */
 void mars_stages_release(mars_model_ext_t *m) {
     mars_roi_release(m);
-    mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->pose, &m->obb, &m->tile_roi, &m->tile};
+    mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->segn, &m->pose, &m->obb, &m->tile_roi, &m->tile};
     mars_det_side_t *sides[] = {&m->label, &m->ident, &m->track};
     for (size_t i = 0; i < sizeof(blocks) / sizeof(blocks[0]); i++) mars_block_release(blocks[i]);
     for (size_t i = 0; i < sizeof(sides) / sizeof(sides[0]); i++) mars_side_release(sides[i]);
     m->cls_c = m->cls_top_k = m->match_top_k = m->label_pending = 0;
     m->seg_max = m->seg_ph = m->seg_pw = m->pose_max = m->pose_k = 0;
+    m->segn_max = m->segn_oh = m->segn_ow = 0;
+    memset(m->segn_key, 0, sizeof(m->segn_key)); /* (those tables lived inside the block) */
     m->pose_lut.n = m->obb_lut.n = 0; /* (those tables lived inside the blocks) */
 }

@@ -260,7 +260,7 @@ int mars_find_heads(const mars_model_ext_t *m, int *tensor_ids, int *strides, in
 
 /* the letterbox of mars_preproc.c (the reference's load_image, mars_yolo_test.c:47-49) of w x hs frames for a tw x th graph input, as
  * the mapping of the kept boxes back into the frame */
-static mars_error_t letterbox_of(int w, int hs, int tw, int th, int *map, int *px, int *py, float *rx, float *ry) {
+static mars_error_t letterbox_of(int w, int hs, int tw, int th, int *map, int *px, int *py, float *rx, float *ry, int *nw_out, int *nh_out) {
     if (w <= 0 || hs <= 0) return MARS_ERR_INVALID_TENSOR;
     const float scale = fminf((float)tw / w, (float)th / hs);
     const int nw = (int)(w * scale), nh = (int)(hs * scale);
@@ -270,6 +270,8 @@ static mars_error_t letterbox_of(int w, int hs, int tw, int th, int *map, int *p
     *py = (th - nh) / 2;
     *rx = (float)w / (float)nw;
     *ry = (float)hs / (float)nh;
+    if (nw_out) *nw_out = nw;
+    if (nh_out) *nh_out = nh;
     return MARS_OK;
 }
 
@@ -320,7 +322,7 @@ mars_error_t mars_heads_resolve(mars_model_ext_t *m, const mars_yolo_heads_t *h,
     else return MARS_ERR_INVALID_TENSOR; /* no default anchors for a fourth head */
     c->conf = h->conf_thresh != 0 ? h->conf_thresh : 0.25f;
     c->nms = h->nms_thresh != 0 ? h->nms_thresh : 0.45f;
-    if (h->src_w || h->src_h) return letterbox_of(h->src_w, h->src_h, iw, ih, &c->map, &c->px, &c->py, &c->rx, &c->ry);
+    if (h->src_w || h->src_h) return letterbox_of(h->src_w, h->src_h, iw, ih, &c->map, &c->px, &c->py, &c->rx, &c->ry, NULL, NULL);
     return MARS_OK;
 }
 
@@ -588,7 +590,7 @@ mars_error_t mars_dfl_resolve(mars_model_ext_t *m, const mars_yolo_dfl_heads_t *
     }
     c->conf = h->conf_thresh != 0 ? h->conf_thresh : 0.25f;
     c->nms = h->nms_thresh != 0 ? h->nms_thresh : 0.45f;
-    if (h->src_w || h->src_h) return letterbox_of(h->src_w, h->src_h, iw, ih, &c->map, &c->px, &c->py, &c->rx, &c->ry);
+    if (h->src_w || h->src_h) return letterbox_of(h->src_w, h->src_h, iw, ih, &c->map, &c->px, &c->py, &c->rx, &c->ry, &c->nw, &c->nh);
     return MARS_OK;
 }
 

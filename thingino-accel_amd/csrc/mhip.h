@@ -549,6 +549,20 @@ typedef struct {
     uint32_t *words;        /* [frames][max_per_frame][ph][(pw + 31) / 32] */
 } mhip_seg_t;
 int mhip_seg(const mhip_seg_t *p);
+int mhip_seg_select(const mhip_seg_t *p); /* the selection launch alone; p is not checked */
+
+/* ---- instance masks in frame pixels (seg_native.hip): the same lists, tensors and selection, the masks on an out_w x out_h grid by the
+ * exact rule of include/mars_hip.h ("Instance masks in frame pixels").  Two launches: the selection of seg.hip with the output grid in the
+ * prototype size's place, then one workgroup per (span of 64 rows, slot, frame), walked in tiles of 16 rows x 8 words. */
+#define MHIP_SEGN_MAX_OUT 8192
+typedef struct {
+    mhip_seg_t seg;         /* as mhip_seg takes it, but: in_w / in_h = the BASE grid the boxes are in, scale[k] = the product scale * 2^-16,
+                             * words = [frames][max_per_frame][out_h][(out_w + 31) / 32]; ph / pw stay the prototype tensor's */
+    int out_w, out_h;       /* 1 .. MHIP_SEGN_MAX_OUT */
+    const int *taps;        /* [ia][ib][w1] of out_w ints each, then the same of out_h for the rows (mars_yolo_mask_taps): up-scaling tables,
+                             * ia <= ib <= ia + 1, non-decreasing, inside the prototype tensor */
+} mhip_seg_native_t;
+int mhip_seg_native(const mhip_seg_native_t *p);
 
 /* ---- pose keypoints (pose.hip): kept detections + their prediction indices -> per frame up to max_per_frame records {det, head, cell} and K
  * keypoints {x, y, v} each, gathered from the origin cell of the heads' keypoint tensors by the exact rule of include/mars_hip.h ("Pose

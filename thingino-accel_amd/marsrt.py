@@ -159,6 +159,18 @@ class SegOpts(C.Structure):  # mars_hip_seg_opts_t: zero = default in every fiel
                 ("logit_min", C.c_float), ("min_conf", C.c_float), ("max_per_frame", C.c_int)]
 
 
+MASK_NATIVE_MAX = 8192                                                  # MARS_MASK_NATIVE_MAX
+MASK_GEOM_FIELDS = ("in_w", "in_h", "nw", "nh", "px", "py", "base_w", "base_h", "out_w", "out_h")
+
+
+class MaskNativeOpts(C.Structure):  # mars_hip_mask_native_opts_t: zero = default in every field
+    _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("flags", C.c_uint)]
+
+
+class MaskGeom(C.Structure):  # mars_mask_geom_t
+    _fields_ = [(n, C.c_int) for n in MASK_GEOM_FIELDS]
+
+
 POSE_MAX_PER_FRAME, POSE_MAX_KPT = 256, 32                              # MARS_POSE_*
 POSE_DTYPE = np.dtype([("det", "<i4"), ("head", "<i4"), ("cell", "<i4")])  # mars_pose_t
 KPT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("v", "<f4")])          # mars_kpt_t
@@ -205,6 +217,7 @@ assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
 assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
 assert ALIGN_DTYPE.itemsize == 32 and C.sizeof(AlignOpts) == 268
 assert C.sizeof(MaskRec) == MASK_DTYPE.itemsize == 24 and C.sizeof(SegOpts) == 52
+assert C.sizeof(MaskNativeOpts) == 12 and C.sizeof(MaskGeom) == 40
 assert C.sizeof(TrackRec) == TRACK_DTYPE.itemsize == 8 and C.sizeof(TrackState) == TRACK_STATE_DTYPE.itemsize == 48
 
 
@@ -250,6 +263,8 @@ EXPORTS = {
                    "mars_hip_tracker_create", "mars_hip_tracker_reset", "mars_hip_tracker_free", "mars_hip_tracker_read",
                    "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track",
                    "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks",
+                   "mars_hip_detect_seg_native_device", "mars_hip_mask_native_results", "mars_hip_detect_seg_native", "mars_hip_mask_native_ms",
+                   "mars_yolo_mask_taps", "mars_yolo_masks_native",
                    "mars_hip_detect_pose_device", "mars_hip_pose_results", "mars_hip_detect_pose", "mars_hip_pose_ms", "mars_yolo_keypoints",
                    "mars_hip_detect_obb_device", "mars_hip_obb_results", "mars_hip_detect_obb", "mars_hip_obb_ms", "mars_yolo_obb_nms",
                    "mars_yolo_obb_corners", "mars_yolo_crop_obb", "mars_hip_crop_obb_device", "mars_hip_crop_obb",
@@ -385,6 +400,15 @@ def lib():
     L.mars_hip_mask_ms.argtypes = [P(MarsModel)]
     L.mars_yolo_masks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
                                   C.c_void_p, C.c_void_p]
+    L.mars_hip_detect_seg_native_device.argtypes = [P(MarsModel), P(YoloDflHeads), P(SegOpts), P(MaskNativeOpts)]
+    L.mars_hip_mask_native_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int)]
+    L.mars_hip_detect_seg_native.argtypes = [P(MarsModel), P(YoloDflHeads), P(SegOpts), P(MaskNativeOpts), C.c_void_p, P(C.c_int), C.c_void_p,
+                                             C.c_void_p]
+    L.mars_hip_mask_native_ms.restype = C.c_float
+    L.mars_hip_mask_native_ms.argtypes = [P(MarsModel)]
+    L.mars_yolo_mask_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_yolo_masks_native.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, P(MaskGeom), C.c_float, C.c_float,
+                                         C.c_void_p, C.c_void_p]
     L.mars_hip_detect_pose_device.argtypes = [P(MarsModel), P(YoloDflHeads), P(PoseOpts)]
     L.mars_hip_pose_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int)]
     L.mars_hip_detect_pose.argtypes = [P(MarsModel), P(YoloDflHeads), P(PoseOpts), C.c_void_p, P(C.c_int), C.c_void_p, C.c_void_p]
@@ -1014,6 +1038,50 @@ def masks(coefs, proto, boxes, in_w, in_h, s, logit_min=0.0):
     return recs, words
 
 
+def mask_native_opts(out_w=0, out_h=0, flags=0):
+    """mars_hip_mask_native_opts_t: 0 / 0 = the frame the DFL options map into (src), otherwise the graph input"""
+    o = MaskNativeOpts()
+    o.out_w, o.out_h, o.flags = int(out_w), int(out_h), int(flags)
+    return o
+
+
+def mask_geom(in_w, in_h, out_w, out_h, nw=None, nh=None, px=0, py=0, base_w=None, base_h=None):
+    """mars_mask_geom_t: the letterboxed content nw x nh at (px, py) inside the in_w x in_h graph input (default: all of it), the grid the
+    boxes are in (default: the graph input) and the output grid"""
+    g = MaskGeom()
+    g.in_w, g.in_h, g.out_w, g.out_h, g.px, g.py = int(in_w), int(in_h), int(out_w), int(out_h), int(px), int(py)
+    g.nw, g.nh = int(in_w if nw is None else nw), int(in_h if nh is None else nh)
+    g.base_w, g.base_h = int(in_w if base_w is None else base_w), int(in_h if base_h is None else base_h)
+    return g
+
+
+def mask_taps(out_n, in_n, n_content, pad, P):
+    """mars_yolo_mask_taps (host only): the tap table of one axis -> (ia, ib, w1) int32 [out_n]; ValueError where it refuses"""
+    n = max(int(out_n), 0)
+    ia, ib, w1 = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    if lib().mars_yolo_mask_taps(int(out_n), int(in_n), int(n_content), int(pad), int(P), ia.ctypes.data, ib.ctypes.data, w1.ctypes.data) != 0:
+        raise ValueError("mars_yolo_mask_taps refused its arguments")
+    return ia, ib, w1
+
+
+def masks_native(coefs, proto, boxes, geom, s, logit_min=0.0):
+    """mars_yolo_masks_native: as masks(), the boxes in pixels of geom's base grid, geom a mask_geom() -> (records MASK_DTYPE [n], words uint32
+    [n][out_h][pitch]); host arrays in and out, runs on the GPU"""
+    a = np.ascontiguousarray(coefs, dtype=np.int8)
+    pr = np.ascontiguousarray(proto, dtype=np.int8)
+    bx = np.ascontiguousarray(boxes, dtype=DET_DTYPE)
+    nm, ph, pw = pr.shape
+    n = len(bx)
+    assert a.shape == (n, nm) or (n == 0 and a.size == 0)
+    recs = np.zeros(n, dtype=MASK_DTYPE)
+    words = np.zeros((n, max(geom.out_h, 0), (max(geom.out_w, 0) + 31) // 32), dtype=np.uint32)
+    rc = lib().mars_yolo_masks_native(a.ctypes.data, n, nm, pr.ctypes.data, ph, pw, bx.ctypes.data, C.byref(geom), float(s), float(logit_min),
+                                      recs.ctypes.data, words.ctypes.data)
+    if rc != 0:
+        raise ValueError("mars_yolo_masks_native refused its arguments or failed (%d)" % rc)
+    return recs, words
+
+
 def unpack_masks(words, pw):
     """uint32 [..., PH, pitch] mask words -> bool [..., PH, pw]: pixel x is bit x & 31 of word x >> 5"""
     w = np.ascontiguousarray(words, dtype="<u4")
@@ -1129,6 +1197,7 @@ class Model:
         L = lib()
         self._bytes = np.frombuffer(bytes(file_bytes), dtype=np.uint8).copy()
         self.p = C.POINTER(MarsModel)()
+        self._segn_max = 16  # slots per frame of the last detect_seg_native_device (before one, the C call refuses the fetch)
         rc = L.mars_hip_load_memory_ex(self._bytes.ctypes.data, self._bytes.size, flags, C.byref(self.p))
         if rc != MARS_OK:
             self.p = None
@@ -1574,6 +1643,34 @@ class Model:
         """detect_seg_device + detect_results + mask_results (mars_hip_detect_seg): (a record array per frame, records, words, PW)"""
         self.detect_seg_device(seg, heads, **kw)
         return (self.detect_results(),) + self.mask_results()
+
+    def detect_seg_native_device(self, seg, native=None, heads=None, **kw):
+        """DFL decode + NMS + instance masks in frame pixels, results stay in HBM (mars_hip_detect_seg_native_device).  seg: seg_opts();
+        native: mask_native_opts() or None (every default); heads and the keywords as for yolo_dfl_heads()"""
+        rc = lib().mars_hip_detect_seg_native_device(self.p, C.byref(yolo_dfl_heads(heads, **kw)), C.byref(seg) if seg is not None else None,
+                                                     C.byref(native) if native is not None else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_detect_seg_native_device")
+        self._segn_max = seg.max_per_frame or 16
+
+    def mask_native_results(self):
+        """the masks the last detect_seg_native_device left in HBM (mars_hip_mask_native_results): (records MASK_DTYPE [batch][max_per_frame],
+        words uint32 [batch][max_per_frame][out_h][pitch], out_w); unpack_masks(words, out_w) gives the pixels"""
+        oh, ow, pitch = C.c_int(), C.c_int(), C.c_int()
+        rc = lib().mars_hip_mask_native_results(self.p, None, None, C.byref(oh), C.byref(ow), C.byref(pitch))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_mask_native_results")
+        recs = np.zeros((self.batch, self._segn_max), dtype=MASK_DTYPE)
+        words = np.zeros((self.batch, self._segn_max, oh.value, pitch.value), dtype=np.uint32)
+        rc = lib().mars_hip_mask_native_results(self.p, recs.ctypes.data, words.ctypes.data, None, None, None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_mask_native_results")
+        return recs, words, ow.value
+
+    def detect_seg_native(self, seg, native=None, heads=None, **kw):
+        """detect_seg_native_device + detect_results + mask_native_results: (a record array per frame, records, words, out_w)"""
+        self.detect_seg_native_device(seg, native, heads, **kw)
+        return (self.detect_results(),) + self.mask_native_results()
 
     def detect_pose_device(self, pose, heads=None, **kw):
         """DFL decode + NMS + pose keypoints, results stay in HBM (mars_hip_detect_pose_device).  pose: pose_opts(); heads and the keywords
