@@ -634,8 +634,8 @@ mars_error_t mars_hip_identity_results(mars_model_t *det_model, mars_cls_t *iden
  *   Output.  out[f][i] = {id, hits}, the values after the update, for every matched or born detection; every other entry up to the array's
  *     width is {-1, 0}.
  * Not covered: the pipelined mars_hip_pipe_* path; optimal (Hungarian) assignment; Kalman covariance (the motion model is the velocity
- *   average above); an appearance cost in the association (the identity rides on the track, it does not steer it); more than
- *   MARS_TRACK_SLOTS tracks per stream. */
+ *   average above); more than MARS_TRACK_SLOTS tracks per stream.  (An appearance term in the association: "Appearance in tracking"
+ *   below.) */
 #define MARS_TRACK_SLOTS 256          /* tracks per stream */
 #define MARS_TRACK_MAX_CAND 256       /* candidates per frame and pass */
 typedef struct { int id, hits; } mars_track_t;                       /* 8 bytes; {-1, 0}: no track */
@@ -678,6 +678,84 @@ mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *
 mars_error_t mars_hip_track_results(mars_model_t *det_model, mars_track_t *tracks);
 /* mars_hip_track_device + mars_hip_track_results. */
 mars_error_t mars_hip_track(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts, mars_track_t *tracks);
+
+/* --------------------------------------------------- Appearance in tracking */
+/* The second stage's embedding steers the association: two people cross, a box jumps after an occlusion, the frame rate drops -- the IoU
+ * alone loses the track, and with it the identity it carried.  A tracker made by mars_hip_tracker_create_app holds an int8 embedding per
+ * slot beside the tables; the calls below take an embedding per detection, compare every live track with every candidate of the high set
+ * by cosine similarity on the int8 matrix unit, and let a high cosine stand in for a low IoU (the BoT-SORT / DeepSORT step).  Everything is
+ * defined to the bit; "Tracking" above holds wherever this section does not say otherwise:
+ *
+ * Embeddings.  A detection's embedding is the int8 vector q[0 .. C) with qq = sum_c q[c]^2: the "Gallery match" quantisation of a C-vector
+ *   of int32, 1 <= C <= 4096.  qq == 0 (a null vector), or no vector at all, means the detection has NONE.  A track slot holds e[0 .. C)
+ *   int8 and ee; ee == 0 means the slot has none.
+ * Cosine of slot s and detection i, defined only when ee_s > 0 and qq_i > 0.  dot = sum_c q[c] * e[c], an exact int32;
+ *     cos = ((float)dot * einv) * qinv,   einv = 1.0f / sqrtf((float)ee),  qinv = 1.0f / sqrtf((float)qq)
+ *   float32, every operation rounded on its own, no fused multiply-add: the arithmetic of "Gallery match" with the track where the gallery
+ *   row stands.  It may exceed 1 by an ulp and is not clamped.
+ * Pass 1, in the place of "Association" for pass 1 only.  iou = the IoU of the predicted track and the detection, as above.
+ *     app = both have an embedding && cos >= app_thresh && iou >= app_min_iou
+ *   A pair is ELIGIBLE when the classes are equal or MARS_TRACK_ANY_CLASS is set, and (iou >= iou_thresh || app).
+ *     key = app ? fmaxf(iou, cos) : iou
+ *   Eligible pairs are visited by (key descending, slot ascending, detection index ascending); a pair is taken when both its track and its
+ *   detection are still free.  A strict total order in which a pair's key depends on that pair alone.  A NaN iou fails every comparison,
+ *   app_min_iou's too: never eligible.
+ * Pass 2 (the low set) is unchanged: IoU only.
+ * Update.  The steps of "Tracking", and:
+ *   A slot matched, in either pass, to a detection that has an embedding takes it: e = q, ee = qq.  With MARS_TRACK_APP_SMOOTH, when the
+ *     slot already has one: v[c] = 3 * e[c] + q[c] in int32, and e, ee = the "Gallery match" quantisation of v (an all-zero v leaves the
+ *     slot without an embedding).
+ *   A slot matched to a detection without an embedding keeps what it has; so does a coasting slot.
+ *   A slot that dies loses its embedding: ee = 0, bytes zeroed.
+ *   A birth takes the detection's embedding, or none: never the previous occupant's.
+ * Invariants.  With no detection carrying an embedding every output and every state is that of "Tracking".  One call over 2 T steps leaves
+ *   exactly the state, embeddings included, and the outputs of two calls over T steps each.
+ * Not covered: appearance in pass 2; association with no spatial gate at all (app_min_iou == 0 means 0.1); EMA weights other than 3 : 1;
+ *   float32 embeddings; the pipelined mars_hip_pipe_* path; optimal (Hungarian) assignment. */
+#define MARS_TRACK_APP_SMOOTH 1u
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    float app_thresh;      /* 0: 0.75 */
+    float app_min_iou;     /* 0: 0.1 */
+    unsigned flags;        /* MARS_TRACK_APP_SMOOTH */
+} mars_hip_track_app_opts_t;
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: what "Tracking" refuses so; no appearance options, one of
+ * them negative, non-finite or above 1, an unknown flag bit; non-positive channels, nt or nc; a negative n_vectors, or vectors / emb_index
+ * NULL with n_vectors > 0; a negative cap.  MARS_ERR_INVALID_TENSOR: what "Tracking" refuses so; channels above 4096; nt or nc above 256;
+ * a tracker without an embedding plane; a cosine asked of a side without an embedding; and, for the model forms, what
+ * mars_hip_identify_detections_device refuses so (det_model == cls_model, an open pipe, no crop call into cls_model out of this det_model,
+ * no classify results on cls_model, no detections in HBM) and classify results whose C differs from the tracker's channels. */
+/* The rule's two pieces on the host, no device needed.  The cosine of a detection's (q, qq) and a slot's (e, ee), both C bytes. */
+mars_error_t mars_yolo_track_cosine(const signed char *q, int qq, const signed char *e, int ee, int c, float *cos);
+/* The MARS_TRACK_APP_SMOOTH update of a slot holding (e, ee) matched to a detection with (q, qq): -> out[0 .. C), *out_ee.  qq == 0: the
+ * slot keeps (e, ee); ee == 0: it takes (q, qq).  e and q may be NULL where their sum of squares is 0. */
+mars_error_t mars_yolo_embed_blend(const signed char *e, int ee, const signed char *q, int qq, int c, signed char *out, int *out_ee);
+/* A tracker with an embedding plane: the tables of mars_hip_tracker_create plus [streams][MARS_TRACK_SLOTS][C rounded up to 64] int8 and
+ * [streams][MARS_TRACK_SLOTS] int32 in HBM.  mars_hip_tracker_reset clears the plane too.  mars_yolo_track_lists and mars_hip_track_device
+ * stay legal on it: they run this section's rule with no embedding supplied, so deaths and births keep the plane consistent. */
+mars_error_t mars_hip_tracker_create_app(int streams, int channels, mars_hip_tracker_t **out);
+/* Waits.  The embeddings of the live tracks of one stream by ascending slot, aligned with mars_hip_tracker_read: q = [cap][C] int8,
+ * ee = [cap] (both may be NULL with cap 0); *n_live as there. */
+mars_error_t mars_hip_tracker_read_embeddings(mars_hip_tracker_t *t, int stream, signed char *q, int *ee, int cap, int *n_live);
+/* mars_yolo_track_lists with embeddings: vectors = [n_vectors][C] int32 (NULL with n_vectors == 0), quantised on the device with the bits
+ * of mars_yolo_embed_quantise; emb_index = [frames][max_det] (may be NULL with n_vectors == 0): detection (f, i) uses row emb_index[f][i],
+ * any value outside 0 .. n_vectors - 1 means none. */
+mars_error_t mars_yolo_track_lists_app(mars_hip_tracker_t *t, const mars_det_t *dets, const int *counts, const mars_cls_t *idents, const int *vectors,
+                                       int n_vectors, const int *emb_index, int frames, int max_det, const mars_hip_track_opts_t *opts,
+                                       const mars_hip_track_app_opts_t *app, mars_track_t *out);
+/* mars_hip_track_device with embeddings: takes the [frames][C] sums the last mars_hip_classify_device of cls_model left in HBM and the ROI
+ * table of the crop call from det_model into cls_model; on the auxiliary stream it quantises the rows, gives row k < kept to detection
+ * (roi.frame, roi.det), and tracks.  Enqueues only, with the identity scatter's ordering; MARS_TRACK_CARRY_IDENTITY works as before and
+ * mars_hip_track_results returns the ids. */
+mars_error_t mars_hip_track_app_device(mars_model_t *det_model, mars_model_t *cls_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts,
+                                       const mars_hip_track_app_opts_t *app);
+/* mars_hip_track_app_device + mars_hip_track_results. */
+mars_error_t mars_hip_track_app(mars_model_t *det_model, mars_model_t *cls_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts,
+                                const mars_hip_track_app_opts_t *app, mars_track_t *tracks);
+/* Test hook: the tracking kernel's own matrix routine on the GPU, ungated.  track_q = [nt][C] int8 and track_ee = [nt] stand where slots
+ * 0 .. nt - 1 would; vectors = [nc][C] int32 are quantised as above; out = [nt][nc] cosines, 0 where a side has no embedding.
+ * 1 <= nt, nc <= 256.  Waits. */
+mars_error_t mars_yolo_track_cosine_matrix(const signed char *track_q, const int *track_ee, const int *vectors, int nt, int nc, int c, float *out);
 
 /* ---------------------------------------------------------- Instance masks */
 /* The "-seg" sibling of the anchor-free DFL head (YOLOv8-seg style): beside the box and class convolutions every scale has a COEFFICIENT

@@ -221,6 +221,8 @@ typedef struct mars_model_ext {
     mars_det_side_t ident; /* identities of THIS model's detections: x mars_cls_t */
     /* tracking (mars_track.c) */
     mars_det_side_t track; /* track ids of THIS model's detections: x mars_track_t */
+    mars_block_t track_app; /* "Appearance in tracking", of THIS model's detections: the quantised rows [slots][cp], their qq [slots], the row
+                             * index of every detection [frames][MARS_YOLO_MAX_DET] x int */
     /* instance masks (mars_seg.c) */
     mars_block_t seg;   /* candidate / kept prediction indices [frames][MARS_YOLO_MAX_DET] x int each, the kept boxes before the letterbox mapping,
                          * [frames][seg_max] x mars_mask_t, [frames][seg_max][seg_ph][pitch] x uint32 */

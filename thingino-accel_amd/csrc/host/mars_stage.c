@@ -154,7 +154,7 @@ mars_error_t mars_lut_refresh(mars_lut_cache_t *c, void *dst, int n, const float
 /* ---- everything a model holds for these stages, when its device state goes away */
 void mars_stages_release(mars_model_ext_t *m) {
     mars_roi_release(m);
-    mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->segn, &m->pose, &m->obb, &m->tile_roi, &m->tile};
+    mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->segn, &m->pose, &m->obb, &m->tile_roi, &m->tile, &m->track_app};
     mars_det_side_t *sides[] = {&m->label, &m->ident, &m->track};
     for (size_t i = 0; i < sizeof(blocks) / sizeof(blocks[0]); i++) mars_block_release(blocks[i]);
     for (size_t i = 0; i < sizeof(sides) / sizeof(sides[0]); i++) mars_side_release(sides[i]);

@@ -524,6 +524,34 @@ typedef struct {
 } mhip_track_t;
 int mhip_track(const mhip_track_t *p); /* one launch */
 
+/* ---- appearance in tracking (track_app.hip): the same walk on a tracker that holds an int8 embedding per slot, by the exact rule of
+ * include/mars_hip.h ("Appearance in tracking").  A kernel of its own: mhip_track above keeps its instructions.  Per stream and step the
+ * cosines of the 256 slots against the high set's candidates are computed on the int8 matrix unit into `cosm`, twice (slot-major and
+ * candidate-major: the two halves of the workgroup walk it along different axes), and pass 1 reads them.  Every pointer is device memory. */
+#define MHIP_TRACK_APP_MAX_C 4096
+#define MHIP_TRACK_APP_COS_FLOATS (2 * MHIP_TRACK_SLOTS * MHIP_TRACK_CAND) /* per stream of a launch: 512 KB */
+#define MHIP_TRACK_APP_CHUNK 512    /* streams per launch: the launcher walks the streams in chunks over ONE block of at most 256 MB */
+typedef struct {
+    mhip_track_t t;         /* the lists, the tables and the resolved options, as for mhip_track */
+    int c, cp;              /* channels; cp = c rounded up to a multiple of 64: the pitch of every int8 row */
+    int8_t *plane;          /* [streams][MHIP_TRACK_SLOTS][cp]: the slots' embeddings, pad channels zero, a slot without one all zero */
+    int *plane_ee;          /* [streams][MHIP_TRACK_SLOTS]; 0: the slot has none */
+    const int *vec;         /* [n_vec][c] int32 embeddings of this call's detections, or NULL with n_vec == 0 */
+    int n_vec;
+    int8_t *q; int *qq;     /* [n_vec][cp], [n_vec]: written by the quantise launch (the rule of gallery.hip); NULL with n_vec == 0 */
+    const int *emb_index;   /* [frames][max_det]: detection (f, i) uses row emb_index[f][i]; outside 0 .. n_vec - 1: none.  NULL: none has one */
+    float *cosm;            /* [min(streams, MHIP_TRACK_APP_CHUNK)][MHIP_TRACK_APP_COS_FLOATS]; NULL only where emb_index is NULL */
+    float app_thresh, app_min_iou; /* resolved: never 0 */
+    int smooth;
+} mhip_track_app_t;
+int mhip_track_app(const mhip_track_app_t *p); /* the quantise launch (n_vec > 0), then one launch per chunk of streams */
+/* emb_index [det_frames][det_cap]: every entry -1, then entry (roi.frame, roi.det) of crop k < min(n_out[0], slots) = k */
+int mhip_track_app_index(const void *rois, const int *n_out, int slots, int *emb_index, int det_frames, int det_cap);
+/* test hook: plane [256][cp] / plane_ee [256] against the quantised vec [nc][c] -> out [nt][nc], the slot-major matrix of the kernel's own
+ * routine; *bad (device) is raised where the candidate-major copy differs from it.  q, qq as above; cosm: MHIP_TRACK_APP_COS_FLOATS floats */
+int mhip_track_app_matrix(const int8_t *plane, const int *plane_ee, const int *vec, int nt, int nc, int c, int cp, int8_t *q, int *qq, float *cosm,
+                          float *out, int *bad);
+
 /* ---- instance masks (seg.hip): kept detections + their prediction indices -> per frame up to max_per_frame records and bit masks at the
  * prototype tensor's size, by the exact rule of include/mars_hip.h ("Instance masks").  Every pointer is device memory.  Two launches: the
  * selection (records, rectangles), then the masks (int8 MFMA of the selected cells' coefficient rows against the prototype pixels). */

@@ -146,6 +146,14 @@ class TrackOpts(C.Structure):  # mars_hip_track_opts_t: zero = default in every 
                 ("max_miss", C.c_int), ("cls_first", C.c_int), ("cls_count", C.c_int), ("flags", C.c_uint)]
 
 
+TRACK_APP_SMOOTH = 1                                                     # MARS_TRACK_APP_*
+TRACK_APP_MAX_C = 4096
+
+
+class TrackAppOpts(C.Structure):  # mars_hip_track_app_opts_t: zero = default in every field
+    _fields_ = [("app_thresh", C.c_float), ("app_min_iou", C.c_float), ("flags", C.c_uint)]
+
+
 SEG_MAX_PER_FRAME, SEG_MAX_NM = 64, 64                                  # MARS_SEG_*
 MASK_DTYPE = np.dtype([("det", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("area", "<i4")])  # mars_mask_t
 
@@ -262,6 +270,8 @@ EXPORTS = {
                    "mars_hip_identity_results",
                    "mars_hip_tracker_create", "mars_hip_tracker_reset", "mars_hip_tracker_free", "mars_hip_tracker_read",
                    "mars_yolo_track_lists", "mars_hip_track_device", "mars_hip_track_results", "mars_hip_track",
+                   "mars_yolo_track_cosine", "mars_yolo_embed_blend", "mars_hip_tracker_create_app", "mars_hip_tracker_read_embeddings",
+                   "mars_yolo_track_lists_app", "mars_hip_track_app_device", "mars_hip_track_app", "mars_yolo_track_cosine_matrix",
                    "mars_hip_detect_seg_device", "mars_hip_mask_results", "mars_hip_detect_seg", "mars_hip_mask_ms", "mars_yolo_masks",
                    "mars_hip_detect_seg_native_device", "mars_hip_mask_native_results", "mars_hip_detect_seg_native", "mars_hip_mask_native_ms",
                    "mars_yolo_mask_taps", "mars_yolo_masks_native",
@@ -393,6 +403,15 @@ def lib():
     L.mars_hip_track_device.argtypes = [P(MarsModel), C.c_void_p, P(TrackOpts)]
     L.mars_hip_track_results.argtypes = [P(MarsModel), C.c_void_p]
     L.mars_hip_track.argtypes = [P(MarsModel), C.c_void_p, P(TrackOpts), C.c_void_p]
+    L.mars_yolo_track_cosine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, P(C.c_float)]
+    L.mars_yolo_embed_blend.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, P(C.c_int)]
+    L.mars_hip_tracker_create_app.argtypes = [C.c_int, C.c_int, P(C.c_void_p)]
+    L.mars_hip_tracker_read_embeddings.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, P(C.c_int)]
+    L.mars_yolo_track_lists_app.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            P(TrackOpts), P(TrackAppOpts), C.c_void_p]
+    L.mars_hip_track_app_device.argtypes = [P(MarsModel), P(MarsModel), C.c_void_p, P(TrackOpts), P(TrackAppOpts)]
+    L.mars_hip_track_app.argtypes = [P(MarsModel), P(MarsModel), C.c_void_p, P(TrackOpts), P(TrackAppOpts), C.c_void_p]
+    L.mars_yolo_track_cosine_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.mars_hip_detect_seg_device.argtypes = [P(MarsModel), P(YoloDflHeads), P(SegOpts)]
     L.mars_hip_mask_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int)]
     L.mars_hip_detect_seg.argtypes = [P(MarsModel), P(YoloDflHeads), P(SegOpts), C.c_void_p, P(C.c_int), C.c_void_p, C.c_void_p]
@@ -812,16 +831,38 @@ def track_opts(min_conf=0.0, low_conf=0.0, iou_thresh=0.0, iou_thresh_low=0.0, m
     return TrackOpts(float(min_conf), float(low_conf), float(iou_thresh), float(iou_thresh_low), int(max_miss), int(first), int(count), flags)
 
 
-class Tracker:
-    """mars_hip_tracker_t: the track tables of `streams` camera streams, TRACK_SLOTS slots each, held on the device between calls"""
+def track_app_opts(app_thresh=0.0, app_min_iou=0.0, smooth=False):
+    """mars_hip_track_app_opts_t; zero means default (cosine threshold 0.75, spatial gate 0.1, a matched slot takes the detection's
+    embedding as it is); smooth: MARS_TRACK_APP_SMOOTH, the 3 : 1 blend"""
+    return TrackAppOpts(float(app_thresh), float(app_min_iou), TRACK_APP_SMOOTH if smooth else 0)
 
-    def __init__(self, streams):
+
+class Tracker:
+    """mars_hip_tracker_t: the track tables of `streams` camera streams, TRACK_SLOTS slots each, held on the device between calls;
+    channels > 0: with an int8 embedding of that many channels per slot ("Appearance in tracking", mars_hip_tracker_create_app)"""
+
+    def __init__(self, streams, channels=0):
         self.streams = int(streams)
+        self.channels = int(channels)
         self.p = C.c_void_p()
-        rc = lib().mars_hip_tracker_create(self.streams, C.byref(self.p))
+        if self.channels:
+            rc, what = lib().mars_hip_tracker_create_app(self.streams, self.channels, C.byref(self.p)), "mars_hip_tracker_create_app"
+        else:
+            rc, what = lib().mars_hip_tracker_create(self.streams, C.byref(self.p)), "mars_hip_tracker_create"
         if rc != MARS_OK:
             self.p = C.c_void_p()
-            raise MarsError(rc, "mars_hip_tracker_create")
+            raise MarsError(rc, what)
+
+    def read_embeddings(self, stream):
+        """-> (int8 [live][channels], int32 [live]): the embeddings of the live tracks of one stream by ascending slot, aligned with read();
+        ee == 0: the track has none.  Waits"""
+        q = np.zeros((TRACK_SLOTS, max(self.channels, 1)), dtype=np.int8)
+        ee = np.zeros(TRACK_SLOTS, dtype=np.int32)
+        n = C.c_int(0)
+        rc = lib().mars_hip_tracker_read_embeddings(self.p, int(stream), q.ctypes.data, ee.ctypes.data, TRACK_SLOTS, C.byref(n))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_tracker_read_embeddings")
+        return q[:n.value].copy(), ee[:n.value].copy()
 
     def reset(self):
         """every table empty, the next id 1, the counters 0"""
@@ -863,6 +904,80 @@ def track_lists(tracker, dets, counts, opts=None, idents=None):
                                      C.byref(o), out.ctypes.data)
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_track_lists")
+    return out
+
+
+def track_lists_app(tracker, dets, counts, vectors=None, emb_index=None, opts=None, app=None, idents=None):
+    """mars_yolo_track_lists_app: track_lists on a Tracker(streams, channels) with embeddings: vectors = int32 [n_vectors][channels] or None,
+    emb_index = int [frames][max_det], the row of vectors detection (f, i) uses (anything outside 0 .. n_vectors - 1: none)"""
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if d.ndim != 2 or d.shape[0] != c.size:
+        raise ValueError("dets must be [frames][max_det] with one count per frame")
+    i = None
+    if idents is not None:
+        i = np.ascontiguousarray(idents, dtype=CLS_DTYPE)
+        if i.shape != d.shape:
+            raise ValueError("idents must have the shape of dets")
+    v, nv, e = None, 0, None
+    if vectors is not None and np.size(vectors):
+        v = np.ascontiguousarray(vectors, dtype=np.int32).reshape(-1)
+        if not tracker.channels or v.size % tracker.channels:
+            raise ValueError("embeddings of %d values, got %d values" % (tracker.channels, v.size))
+        nv = v.size // tracker.channels
+    if emb_index is not None:
+        e = np.ascontiguousarray(emb_index, dtype=np.int32)
+        if e.shape != d.shape:
+            raise ValueError("emb_index must have the shape of dets")
+    o = opts if opts is not None else track_opts()
+    a = app if app is not None else track_app_opts()
+    out = np.zeros(d.shape, dtype=TRACK_DTYPE)
+    rc = lib().mars_yolo_track_lists_app(tracker.p, d.ctypes.data, c.ctypes.data, i.ctypes.data if i is not None else None,
+                                         v.ctypes.data if v is not None else None, nv, e.ctypes.data if e is not None else None, d.shape[0],
+                                         d.shape[1], C.byref(o), C.byref(a), out.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_track_lists_app")
+    return out
+
+
+def track_cosine(q, qq, e, ee):
+    """mars_yolo_track_cosine: the cosine of a detection's (q, qq) and a slot's (e, ee), int8 vectors of one length -> np.float32; host only"""
+    a, b = np.ascontiguousarray(q, dtype=np.int8).reshape(-1), np.ascontiguousarray(e, dtype=np.int8).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("two vectors of one length")
+    out = C.c_float(0)
+    rc = lib().mars_yolo_track_cosine(a.ctypes.data, int(qq), b.ctypes.data, int(ee), int(a.size), C.byref(out))
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_track_cosine")
+    return np.float32(out.value)
+
+
+def embed_blend(e, ee, q, qq):
+    """mars_yolo_embed_blend: the MARS_TRACK_APP_SMOOTH update of a slot holding (e, ee) matched to a detection with (q, qq) ->
+    (int8 [channels], ee); host only"""
+    a, b = np.ascontiguousarray(e, dtype=np.int8).reshape(-1), np.ascontiguousarray(q, dtype=np.int8).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("two vectors of one length")
+    out = np.zeros(a.size, dtype=np.int8)
+    oe = C.c_int(0)
+    rc = lib().mars_yolo_embed_blend(a.ctypes.data, int(ee), b.ctypes.data, int(qq), int(a.size), out.ctypes.data, C.byref(oe))
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_embed_blend")
+    return out, int(oe.value)
+
+
+def track_cosine_matrix(track_q, track_ee, vectors):
+    """mars_yolo_track_cosine_matrix, a test hook: int8 [nt][channels] and int32 [nt] standing where slots would, int32 vectors
+    [nc][channels] -> float32 [nt][nc], the ungated cosines of the tracking kernel's own matrix routine (0 where a side has no embedding)"""
+    tq = np.ascontiguousarray(track_q, dtype=np.int8)
+    te = np.ascontiguousarray(track_ee, dtype=np.int32).reshape(-1)
+    v = np.ascontiguousarray(vectors, dtype=np.int32)
+    if tq.ndim != 2 or v.ndim != 2 or tq.shape[1] != v.shape[1] or tq.shape[0] != te.size:
+        raise ValueError("track_q [nt][channels], track_ee [nt], vectors [nc][channels]")
+    out = np.zeros((tq.shape[0], v.shape[0]), dtype=np.float32)
+    rc = lib().mars_yolo_track_cosine_matrix(tq.ctypes.data, te.ctypes.data, v.ctypes.data, tq.shape[0], v.shape[0], tq.shape[1], out.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_track_cosine_matrix")
     return out
 
 
@@ -1520,6 +1635,25 @@ class Model:
         rc = lib().mars_hip_track_results(self.p, tracks.ctypes.data)
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_track_results")
+        return tracks
+
+    def track_app_device(self, cls_model, tracker, opts=None, app=None, **kw):
+        """track_device with the embeddings of the second stage: the sums cls_model's last classify_device left and the ROI table of the crop
+        call from this model into it steer the association (mars_hip_track_app_device); enqueues only.  app = track_app_opts(...)"""
+        o = opts if opts is not None else track_opts(**kw)
+        a = app if app is not None else track_app_opts()
+        rc = lib().mars_hip_track_app_device(self.p, cls_model.p, tracker.p, C.byref(o), C.byref(a))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_track_app_device")
+
+    def track_app(self, cls_model, tracker, opts=None, app=None, **kw):
+        """track_app_device + track_results (mars_hip_track_app)"""
+        o = opts if opts is not None else track_opts(**kw)
+        a = app if app is not None else track_app_opts()
+        tracks = np.zeros((self.batch, MAX_DET), dtype=TRACK_DTYPE)
+        rc = lib().mars_hip_track_app(self.p, cls_model.p, tracker.p, C.byref(o), C.byref(a), tracks.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_track_app")
         return tracks
 
     def track(self, tracker, opts=None, **kw):
