@@ -102,6 +102,12 @@ def test_crop_aligned_geometries(gpu, src):
                 o = gpu.roi_opts(W, H, fmt=fmt, src_flags=flags, expand=expand)
                 got, rois, fits = gpu.crop_aligned(raw, kp, fo, gpu.align_opts(tmpl, min_vis=MIN_VIS), o, tw, th, nhwc)
                 check_tables(rois, fits, fo, rects, wfits)
+                if (tw, th) == (32, 32):  # the device and mars_yolo_align_fit compile one text (csrc/align_fit.h): they compute the same bits too
+                    for i in range(len(kp)):
+                        kept, hfit, hrect = gpu.align_fit(kp[i], gpu.align_opts(tmpl, min_vis=MIN_VIS), o, tw, th)
+                        assert kept == (int(fits[i]["n_used"]) > 0), i
+                        assert [int(hfit[k]) for k in FIT_KEYS] == [int(fits[i][k]) for k in FIT_KEYS], i
+                        assert hrect == (int(rois[i]["x0"]), int(rois[i]["y0"]), int(rois[i]["x1"]), int(rois[i]["y1"])), i
                 assert int((fits["n_used"] > 0).sum()) == n_kept and int((rois["x1"] > rois["x0"]).sum()) == n_kept
                 assert int((fits["n_used"] == 0).sum()) == len(kp) - n_kept
                 w = want if nhwc else want.reshape(-1, th, tw, 3).transpose(0, 3, 1, 2).reshape(len(kp), -1)

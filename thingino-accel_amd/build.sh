@@ -20,7 +20,7 @@ pids=()
 for f in "$SRC"/hip/*.hip; do
   o="$OBJ/$(basename "$f" .hip).hip.o"
   stale=0
-  for h in "$SRC"/mhip.h "$SRC"/expf_exact.h "$SRC"/hip/*.hpp; do  # every header a kernel file may include
+  for h in "$SRC"/*.h "$SRC"/hip/*.hpp; do  # every header a kernel file may include
     [ -f "$h" ] && [ "$h" -nt "$o" ] && stale=1
   done
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ $stale = 1 ]; then

@@ -6,19 +6,28 @@
 //   roi_select_kernel<0 / 1>  the selection rules over the detection lists a tail left in HBM: per-frame kept counts by wave ballots in list
 //                             order, slot offsets by a sum over the frames in front, the ROI table and the kept / dropped counters;
 //   roi_rects_kernel          the rectangle rule alone over a caller's boxes (mars_yolo_crop_boxes), box i -> slot i;
-//   roi_crop_kernel<FMT>      a workgroup owns ROI_R output rows of one destination slot.  The geometry differs per box and only the device
-//                             knows it: the kernel reads the kept count and its rectangle from device memory, builds the column table in
-//                             LDS, stages the source-row segments its rows touch in LDS (NV12: converted once per pixel while staging),
-//                             blends from LDS, puts the strip's bytes together in LDS and stores contiguous runs 16 bytes at a time.
+//   roi_crop_kernel<FMT>      the bilinear crop.  The geometry differs per box and only the device knows it: the kernel reads the kept count
+//                             and its rectangle from device memory, builds the column table in LDS, stages the source-row segments its
+//                             rows touch in LDS (NV12: converted once per pixel while staging) and blends from LDS;
 //   roi_area_crop_kernel      the crop under MARS_ROI_AREA / MARS_TILE_AREA: down-scaled axes are box-filtered; a strip streams over its source rows;
-//   roi_rot_crop_kernel<FMT>  the same strip for an ORIENTED box ("Rotated crops"): samples along the box's axes from a staged bounding rectangle;
+//   roi_rot_crop_kernel<FMT>  the crop of an ORIENTED box ("Rotated crops"): samples along the box's axes from a staged bounding rectangle;
 //                             the select and rectangle kernels serve it through their SRC_ROT list source.  With FIT the six integers of
 //                             its sample frame come from a table instead ("Aligned crops"): align_fit, a least-squares similarity of a
 //                             template onto pose keypoints, run by the select and rectangle kernels over their SRC_POSE list source.
+// What the three crop kernels share is written once:
+//   strip_t      a workgroup owns R output rows of one destination slot.  The strip says where they lie in the destination, fills them grey
+//                when there is nothing to sample, keeps their bytes together in an LDS image and stores that image as contiguous runs,
+//                16 bytes at a time;
+//   slot_geom    an upright slot's rectangle -> live, the resized size (keep_aspect_size, the rotated geometry's rule too) and its place;
+//   stage_unit   one unit of a staged source row of the two upright kernels; blend4, the four-tap blend of the two samplers;
+//   align_fit    csrc/align_fit.h, the text the host's mars_yolo_align_fit compiles too, with the enclosing rectangle of a rotated box.
 // Nothing here uses atomics: a slot number is a function of the lists alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "../align_fit.h"
 #include "../mhip.h"
 #include "nv12.hpp"
 #include "tail_core.hpp"
@@ -26,11 +35,11 @@
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-// box -> source rectangle; false = skipped (the rectangle is then all zeros).  float32, every operation rounded on its own (-ffp-contract=off).
-// The two clamps in front of the conversions keep far-away boxes inside the int range and change no decision: x0f > W + 1 means x0 > x1 anyway
-__device__ __forceinline__ bool roi_rect(const det_t d, const float expand, const int min_size, const int W, const int H, int &x0, int &y0,
-                                         int &x1, int &y1) {
-    x0 = y0 = x1 = y1 = 0;
+// box -> source rectangle q = {x0, y0, x1, y1}; false = skipped (the rectangle is then all zeros).  float32, every operation rounded on its own
+// (-ffp-contract=off).  The two clamps in front of the conversions keep far-away boxes inside the int range and change no decision:
+// x0f > W + 1 means x0 > x1 anyway
+__device__ __forceinline__ bool roi_rect(const det_t d, const float expand, const int min_size, const int W, const int H, int q[4]) {
+    q[0] = q[1] = q[2] = q[3] = 0;
     if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf))) return false;
     if (!(d.w > 0.0f) || !(d.h > 0.0f)) return false;
     const float hw = (d.w * expand) * 0.5f, hh = (d.h * expand) * 0.5f;
@@ -40,8 +49,14 @@ __device__ __forceinline__ bool roi_rect(const det_t d, const float expand, cons
     y0f = fminf(y0f, (float)(H + 1)); y1f = fmaxf(y1f, -1.0f);
     const int ax0 = (int)floorf(x0f), ax1 = (int)ceilf(x1f), ay0 = (int)floorf(y0f), ay1 = (int)ceilf(y1f);
     if (ax1 - ax0 < min_size || ay1 - ay0 < min_size) return false;
-    x0 = ax0; y0 = ay0; x1 = ax1; y1 = ay1;
+    q[0] = ax0; q[1] = ay0; q[2] = ax1; q[3] = ay1;
     return true;
+}
+
+// the resized size of a cw x ch source inside a tw x th target under MARS_ROI_KEEP_ASPECT: the longer side fills its axis, the other is rounded, >= 1
+__device__ __forceinline__ void keep_aspect_size(const int cw, const int ch, const int tw, const int th, int &nw, int &nh) {
+    if ((long long)cw * th >= (long long)ch * tw) nh = max(1, (int)(((long long)ch * tw + cw / 2) / cw));
+    else nw = max(1, (int)(((long long)cw * th + ch / 2) / ch));
 }
 
 // ---- "Rotated crops": the skip rule, the enclosing rectangle of the ROI table and the Q16 sample frame of an oriented box.  float32, every
@@ -60,28 +75,20 @@ __device__ __forceinline__ bool rot_sides(const obb_t d, const float expand, con
 
 // the rule and, for a kept box, the integer rectangle around the expanded box, clipped to the frame (the ROI table's x0 .. y1: never read back here)
 __device__ __forceinline__ bool rot_rect(const obb_t d, const float cs, const float sn, const float expand, const int min_size, const int W, const int H,
-                                         int &x0, int &y0, int &x1, int &y1) {
-    x0 = y0 = x1 = y1 = 0;
+                                         int q[4]) {
+    q[0] = q[1] = q[2] = q[3] = 0;
     float we, he;
     if (!rot_sides(d, expand, min_size, W, H, we, he)) return false;
-    const float ac = fabsf(cs), as = fabsf(sn);
-    const float ex = __fmul_rn(__fadd_rn(__fmul_rn(we, ac), __fmul_rn(he, as)), 0.5f), ey = __fmul_rn(__fadd_rn(__fmul_rn(we, as), __fmul_rn(he, ac)), 0.5f);
-    x0 = (int)floorf(fmaxf(__fsub_rn(d.x, ex), 0.0f)); x1 = (int)ceilf(fminf(__fadd_rn(d.x, ex), (float)W));
-    y0 = (int)floorf(fmaxf(__fsub_rn(d.y, ey), 0.0f)); y1 = (int)ceilf(fminf(__fadd_rn(d.y, ey), (float)H));
+    rot_enclose(d.x, d.y, we, he, fabsf(cs), fabsf(sn), W, H, q);
     return true;
 }
 
 struct rot_geom_t { int X0, Y0, Ux, Uy, Vx, Vy, nw, nh, px, py; };
-__device__ __forceinline__ int rot_q16(const float v) { return (int)rintf(__fmul_rn(v, 65536.0f)); }
 __device__ __forceinline__ rot_geom_t rot_geom(const obb_t d, const float we, const float he, const float cs, const float sn, const int tw, const int th,
                                                const int keep_aspect) {
     rot_geom_t g;
     g.nw = tw; g.nh = th;
-    if (keep_aspect) {
-        const int cw = max(1, (int)rintf(we)), ch = max(1, (int)rintf(he));
-        if ((long long)cw * th >= (long long)ch * tw) g.nh = max(1, (int)(((long long)ch * tw + cw / 2) / cw));
-        else g.nw = max(1, (int)(((long long)cw * th + ch / 2) / ch));
-    }
+    if (keep_aspect) keep_aspect_size(max(1, (int)rintf(we)), max(1, (int)rintf(he)), tw, th, g.nw, g.nh);
     g.px = (tw - g.nw) / 2; g.py = (th - g.nh) / 2;
     const float sx = __fdiv_rn(we, (float)(2 * g.nw)), sy = __fdiv_rn(he, (float)(2 * g.nh));
     g.Ux = rot_q16(__fmul_rn(sx, cs)); g.Uy = rot_q16(__fmul_rn(sx, sn));
@@ -90,58 +97,9 @@ __device__ __forceinline__ rot_geom_t rot_geom(const obb_t d, const float we, co
     return g;
 }
 
-// ---- "Aligned crops": the least-squares similarity that carries the template onto a keypoint set -> the skip decision, the Q16 sample frame,
-// the mask of the keypoints that carried the fit and the enclosing rectangle.  float32, every operation rounded on its own, sums in ascending j
-struct align_t { int X0, Y0, Ux, Uy, Vx, Vy; unsigned used; int n_used; }; // mars_align_t
-static_assert(sizeof(align_t) == 32, "mars_align_t is 32 bytes");
-
-// false = skipped: `a` and the rectangle are then all zeros
-__device__ __forceinline__ bool align_fit(const kpt_t *kp, const mhip_roi_t &p, align_t &a, int &x0, int &y0, int &x1, int &y1) {
-    a = {0, 0, 0, 0, 0, 0, 0u, 0};
-    x0 = y0 = x1 = y1 = 0;
-    unsigned used = 0u;
-    float sqx = 0.0f, sqy = 0.0f, spx = 0.0f, spy = 0.0f;
-    for (int j = 0; j < p.num_kpt; j++) {
-        if (!((p.use >> j) & 1u)) continue;
-        const kpt_t k = kp[j];
-        if (!(k.v >= p.min_vis)) continue; // (a NaN visibility does not take part)
-        if (!(isfinite(k.x) && isfinite(k.y) && isfinite(k.v))) return false;
-        used |= 1u << j;
-        sqx = __fadd_rn(sqx, p.tmpl[j][0]); sqy = __fadd_rn(sqy, p.tmpl[j][1]);
-        spx = __fadd_rn(spx, k.x); spy = __fadd_rn(spy, k.y);
-    }
-    const int cnt = __popc(used);
-    if (cnt < 2) return false;
-    const float n = (float)cnt;
-    const float qmx = __fdiv_rn(sqx, n), qmy = __fdiv_rn(sqy, n), pmx = __fdiv_rn(spx, n), pmy = __fdiv_rn(spy, n);
-    float A = 0.0f, B = 0.0f, D = 0.0f;
-    for (int j = 0; j < p.num_kpt; j++) {
-        if (!((used >> j) & 1u)) continue;
-        const kpt_t k = kp[j];
-        const float dqx = __fsub_rn(p.tmpl[j][0], qmx), dqy = __fsub_rn(p.tmpl[j][1], qmy), dpx = __fsub_rn(k.x, pmx), dpy = __fsub_rn(k.y, pmy);
-        A = __fadd_rn(A, __fadd_rn(__fmul_rn(dqx, dpx), __fmul_rn(dqy, dpy)));
-        B = __fadd_rn(B, __fsub_rn(__fmul_rn(dqx, dpy), __fmul_rn(dqy, dpx)));
-        D = __fadd_rn(D, __fadd_rn(__fmul_rn(dqx, dqx), __fmul_rn(dqy, dqy)));
-    }
-    if (!(D > 0.0f)) return false;
-    const float fa = __fdiv_rn(A, D), fb = __fdiv_rn(B, D);
-    if (!(isfinite(fa) && isfinite(fb))) return false;
-    const float ux = __fsub_rn(__fmul_rn((float)p.tw, 0.5f), qmx), uy = __fsub_rn(__fmul_rn((float)p.th, 0.5f), qmy);
-    const float cx = __fadd_rn(pmx, __fsub_rn(__fmul_rn(fa, ux), __fmul_rn(fb, uy))), cy = __fadd_rn(pmy, __fadd_rn(__fmul_rn(fb, ux), __fmul_rn(fa, uy)));
-    const float ae = __fmul_rn(fa, p.expand), be = __fmul_rn(fb, p.expand);
-    const float s = __fsqrt_rn(__fadd_rn(__fmul_rn(ae, ae), __fmul_rn(be, be)));
-    const float we = __fmul_rn(s, (float)p.tw), he = __fmul_rn(s, (float)p.th);
-    if (!(we >= (float)p.min_size && he >= (float)p.min_size && we <= 32768.0f && he <= 32768.0f)) return false; // (a NaN side is skipped)
-    if (!(cx >= 0.0f && cx <= (float)p.w && cy >= 0.0f && cy <= (float)p.h)) return false;                       // (a NaN centre is outside)
-    const float ha = __fmul_rn(ae, 0.5f), hb = __fmul_rn(be, 0.5f);
-    a.Ux = rot_q16(ha); a.Uy = rot_q16(hb); a.Vx = rot_q16(-hb); a.Vy = rot_q16(ha);
-    a.X0 = rot_q16(__fsub_rn(cx, 0.5f)); a.Y0 = rot_q16(__fsub_rn(cy, 0.5f));
-    a.used = used; a.n_used = cnt;
-    const float ac = __fdiv_rn(fabsf(ae), s), as = __fdiv_rn(fabsf(be), s);
-    const float ex = __fmul_rn(__fadd_rn(__fmul_rn(we, ac), __fmul_rn(he, as)), 0.5f), ey = __fmul_rn(__fadd_rn(__fmul_rn(we, as), __fmul_rn(he, ac)), 0.5f);
-    x0 = (int)floorf(fmaxf(__fsub_rn(cx, ex), 0.0f)); x1 = (int)ceilf(fminf(__fadd_rn(cx, ex), (float)p.w));
-    y0 = (int)floorf(fmaxf(__fsub_rn(cy, ey), 0.0f)); y1 = (int)ceilf(fminf(__fadd_rn(cy, ey), (float)p.h));
-    return true;
+// conf >= min_conf and the class window: what the three list sources of the selection ask of a detection before their own rule
+__device__ __forceinline__ bool roi_wanted(const mhip_roi_t &p, const float conf, const int cls) {
+    return conf >= p.min_conf && (p.cls_count == 0 || ((long long)cls >= p.cls_first && (long long)cls < (long long)p.cls_first + p.cls_count));
 }
 
 // One wave per frame.  PHASE 0 counts the frame's kept boxes into frame_kept[f]; PHASE 1 (a second launch: it needs every frame's count) sums
@@ -187,7 +145,7 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + lane;
         bool ok = false;
-        int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+        int q[4] = {0, 0, 0, 0};
         int det_i = i;
         align_t fit;
         if (SRC == SRC_POSE) {
@@ -197,26 +155,23 @@ __global__ __launch_bounds__(64) void roi_select_kernel(const mhip_roi_t p) {
             if (ends) n = i0 + __ffsll((long long)ends) - 1;
             if (i < n && di < n_det) { // (a det beyond the frame's list cannot come from the pose stage: not taken)
                 const det_t d = dets[di];
-                ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
-                     align_fit((const kpt_t *)p.pose_kpts + k * p.num_kpt, p, fit, x0, y0, x1, y1);
+                ok = roi_wanted(p, d.conf, d.cls) && align_fit((const align_kpt_t *)p.pose_kpts + k * p.num_kpt, &p, &fit, q);
                 det_i = di;
             }
         } else if (i < n && SRC == SRC_ROT) {
             const size_t k = (size_t)f * p.det_cap + i;
             const obb_t d = ((const obb_t *)p.dets)[k];
-            ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
-                 rot_rect(d, p.csn[2 * k], p.csn[2 * k + 1], p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
+            ok = roi_wanted(p, d.conf, d.cls) && rot_rect(d, p.csn[2 * k], p.csn[2 * k + 1], p.expand, p.min_size, p.w, p.h, q);
         } else if (i < n) {
             const det_t d = dets[i];
-            ok = d.conf >= p.min_conf && (p.cls_count == 0 || ((long long)d.cls >= p.cls_first && (long long)d.cls < (long long)p.cls_first + p.cls_count)) &&
-                 roi_rect(d, p.expand, p.min_size, p.w, p.h, x0, y0, x1, y1);
+            ok = roi_wanted(p, d.conf, d.cls) && roi_rect(d, p.expand, p.min_size, p.w, p.h, q);
         }
         const unsigned long long mask = __ballot(ok);
         const int rank = kept + __popcll(mask & ((1ull << lane) - 1ull));
         if (p.max_per_frame > 0 && rank >= p.max_per_frame) ok = false;
         if (PHASE == 1 && ok && base + rank < p.slots) {
             roi_t r;
-            r.frame = f; r.det = SRC == SRC_POSE ? det_i : i; r.x0 = x0; r.y0 = y0; r.x1 = x1; r.y1 = y1;
+            r.frame = f; r.det = SRC == SRC_POSE ? det_i : i; r.x0 = q[0]; r.y0 = q[1]; r.x1 = q[2]; r.y1 = q[3];
             rois[base + rank] = r;
             if (SRC == SRC_POSE) ((align_t *)p.fits)[base + rank] = fit;
         }
@@ -241,37 +196,113 @@ __global__ __launch_bounds__(256) void roi_rects_kernel(const mhip_roi_t p) {
     r.frame = p.frame_of_box[i];
     r.det = -1;
     const bool ok = r.frame >= 0 && r.frame < p.n_frames;
-    r.x0 = r.y0 = r.x1 = r.y1 = 0;
+    int q[4] = {0, 0, 0, 0};
     if (SRC == SRC_POSE) { // box i = the K keypoints at i * K; its fit record beside the ROI entry (zeros: skipped)
         align_t fit = {0, 0, 0, 0, 0, 0, 0u, 0};
-        if (ok) align_fit((const kpt_t *)p.boxes + (size_t)i * p.num_kpt, p, fit, r.x0, r.y0, r.x1, r.y1);
+        if (ok) align_fit((const align_kpt_t *)p.boxes + (size_t)i * p.num_kpt, &p, &fit, q);
         ((align_t *)p.fits)[i] = fit;
     } else if (SRC == SRC_ROT) {
         const obb_t d = ((const obb_t *)p.boxes)[i];
-        if (ok) rot_rect(d, p.csn[2 * i], p.csn[2 * i + 1], p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
+        if (ok) rot_rect(d, p.csn[2 * i], p.csn[2 * i + 1], p.expand, p.min_size, p.w, p.h, q);
     } else {
         const det_t d = ((const det_t *)p.boxes)[i];
-        if (ok) roi_rect(d, p.expand, p.min_size, p.w, p.h, r.x0, r.y0, r.x1, r.y1);
+        if (ok) roi_rect(d, p.expand, p.min_size, p.w, p.h, q);
     }
+    r.x0 = q[0]; r.y0 = q[1]; r.x1 = q[2]; r.y1 = q[3];
     ((roi_t *)p.rois)[i] = r;
 }
 
 #define ROI_R 8 // output rows of a strip
 
-// n bytes of -17 at o, any alignment: bytes up to the first 16-byte boundary, 16-byte stores, bytes behind the last one
+// n bytes of -17 at o, any alignment: bytes up to the first 16-byte boundary, 16-byte stores, bytes behind the last one (fewer than 16 at
+// either end: a thread each)
 __device__ __forceinline__ void roi_fill_run(int8_t *o, const int n, const int tid) {
     const int head = min(n, (int)((16u - (unsigned)((uintptr_t)o & 15)) & 15u)), body = (n - head) & ~15;
     const unsigned g = 0xefefefefu; // (int8) -17
-    for (int i = tid; i < head; i += 256) o[i] = (int8_t)-17;
+    if (tid < head) o[tid] = (int8_t)-17;
     for (int i = tid * 16; i < body; i += 256 * 16) *(uint4 *)(o + head + i) = make_uint4(g, g, g, g);
-    for (int i = head + body + tid; i < n; i += 256) o[i] = (int8_t)-17;
+    if (head + body + tid < n) o[head + body + tid] = (int8_t)-17;
 }
 // n bytes from LDS to o; l and o are congruent mod 16, so the 16-byte runs are aligned on both sides
 __device__ __forceinline__ void roi_store_run(int8_t *o, const int8_t *l, const int n, const int tid) {
     const int head = min(n, (int)((16u - (unsigned)((uintptr_t)o & 15)) & 15u)), body = (n - head) & ~15;
-    for (int i = tid; i < head; i += 256) o[i] = l[i];
+    if (tid < head) o[tid] = l[tid];
     for (int i = tid * 16; i < body; i += 256 * 16) *(uint4 *)(o + head + i) = *(const uint4 *)(l + head + i);
-    for (int i = head + body + tid; i < n; i += 256) o[i] = l[i];
+    if (head + body + tid < n) o[head + body + tid] = l[head + body + tid];
+}
+
+// ---- the strip: the R output rows of one destination slot that a workgroup owns.  In the destination it is one contiguous run of bytes
+// (planar: one run per channel, `plane` bytes apart).  Its bytes are put together in LDS and stored in the end: the image of a run starts
+// at the same offset inside a 16-byte line as the run does in memory (planar: each channel in a region of its own, a multiple of 16 bytes)
+struct strip_t {
+    int8_t *run;        // row ys of the slot in the destination (planar: of channel 0)
+    int ys, rows;       // the strip's first row in the target and its rows (the last strip may be short)
+    int r_lo, r_hi;     // its rows inside the resized crop (strip_cover)
+    int n_run;          // runs of rows * pitch bytes: nhwc 1, planar 3
+    int pitch, step;    // bytes from row to row and from column to column of one channel: nhwc tw * 3 and 3, planar tw and 1
+    unsigned plane, lo; // bytes from run to run (nhwc: 0); the offset of `run` inside a 16-byte line
+    int8_t *img;        // the LDS image (strip_image); channel c of a pixel lies strip_base(c) + strip_pix(row, column) into it
+    int cs;             // bytes from channel to channel in the image: nhwc 1, planar a channel region
+};
+__device__ __forceinline__ strip_t strip_open(const mhip_roi_t &p, const int slot, const int ys, const int R) {
+    strip_t s;
+    s.ys = ys; s.rows = min(R, p.th - ys);
+    s.r_lo = s.r_hi = 0;
+    s.n_run = p.nhwc ? 1 : 3;
+    s.pitch = p.nhwc ? p.tw * 3 : p.tw; s.step = p.nhwc ? 3 : 1;
+    s.plane = p.nhwc ? 0u : (unsigned)p.th * (unsigned)p.tw;
+    s.run = p.out + (size_t)slot * p.out_stride + (size_t)ys * s.pitch;
+    s.lo = (unsigned)((uintptr_t)s.run & 15);
+    s.img = nullptr; s.cs = 1;
+    return s;
+}
+// the strip's rows inside a resized crop of nh rows that starts at row py of the target; false: none of them (a pad band)
+__device__ __forceinline__ bool strip_cover(strip_t &s, const int py, const int nh) {
+    s.r_lo = max(py - s.ys, 0); s.r_hi = min(py + nh - s.ys, s.rows);
+    return s.r_hi > s.r_lo;
+}
+// an empty slot, a skipped box or a pad band: grey, the source is not touched
+__device__ __forceinline__ void strip_grey(const strip_t &s, const int tid) {
+    for (int c = 0; c < s.n_run; c++) roi_fill_run(s.run + (size_t)c * s.plane, s.rows * s.pitch, tid);
+}
+// the image in `stage` (3 channel regions of an R-row strip: roi_lds_stage), grey first: the bands left / right of the crop and the rows outside it stay so
+__device__ __forceinline__ void strip_image(strip_t &s, int8_t *stage, const int R, const int tw, const int tid) {
+    const int chan = ((R * tw + 15) & ~15) + 16; // bytes per channel region: a multiple of 16, so every region starts on a 16-byte line
+    s.img = stage; s.cs = s.n_run == 1 ? 1 : chan;
+    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
+}
+// uniform: with c a constant of an unrolled loop it is scalar work outside the pixel loop
+__device__ __forceinline__ int strip_base(const strip_t &s, const int c) { return c * s.cs + (int)((s.lo + (unsigned)c * s.plane) & 15u); }
+__device__ __forceinline__ int strip_pix(const strip_t &s, const int row, const int col) { return row * s.pitch + col * s.step; }
+__device__ __forceinline__ void strip_put(const strip_t &s, const int pix, const int c, const int8_t v) { s.img[strip_base(s, c) + pix] = v; }
+// after a barrier behind the last strip_put
+__device__ __forceinline__ void strip_store(const strip_t &s, const int tid) {
+    for (int c = 0; c < s.n_run; c++) roi_store_run(s.run + (size_t)c * s.plane, s.img + strip_base(s, c), s.rows * s.pitch, tid);
+}
+
+// ---- an upright slot, from device memory: the kept count and the slot's rectangle -> whether there is anything to sample, the source
+// rectangle, the resized size inside the target and where it starts
+struct slot_geom_t {
+    bool live;
+    int frame, x0, y0, cw, ch, nw, nh, px, py;
+};
+__device__ __forceinline__ slot_geom_t slot_geom(const mhip_roi_t &p, const int slot) {
+    slot_geom_t g;
+    bool live = slot < p.n_out[0];
+    roi_t r = {0, 0, 0, 0, 0, 0};
+    if (live) r = ((const roi_t *)p.rois)[slot];
+    g.frame = r.frame; g.x0 = r.x0; g.y0 = r.y0; g.cw = r.x1 - r.x0; g.ch = r.y1 - r.y0;
+    g.live = live && g.cw > 0 && g.ch > 0 && r.frame >= 0 && r.frame < p.n_frames && r.x0 >= 0 && r.y0 >= 0 && r.x1 <= p.w && r.y1 <= p.h;
+    g.nw = p.tw; g.nh = p.th;
+    if (g.live && p.keep_aspect) keep_aspect_size(g.cw, g.ch, p.tw, p.th, g.nw, g.nh);
+    g.px = (p.tw - g.nw) / 2; g.py = (p.th - g.nh) / 2;
+    return g;
+}
+
+// the four taps of one channel, fx and fy in 1/256 -> the int8 the crops write
+__device__ __forceinline__ int8_t blend4(const int t00, const int t01, const int t10, const int t11, const int fx, const int fy) {
+    const int top = t00 * (256 - fx) + t01 * fx, bot = t10 * (256 - fx) + t11 * fx;
+    return (int8_t)(((top * (256 - fy) + bot * fy + 32768) >> 16) - 128);
 }
 
 // position of output sample i of n_out over n_in source samples, half-pixel centres, 8 fractional bits, clamped to the source
@@ -293,15 +324,24 @@ static size_t roi_rowbuf(int w, int fmt) {
     return all < 32 * 1024 ? all : (2 * pm > 32 * 1024 ? 2 * pm : 32 * 1024);
 }
 
-// Unit u of the staged image of source row sy for the area kernel, laid out as roi_crop_kernel stages it: a staged row holds the pixels
-// [xe, x1) of a source row as RGB bytes (xe = x0, NV12: x0 & ~1).  RGB: 16 bytes of the segment; NV12: four pixels converted from an even
-// column, 12 bytes, each stored on its own (packed into dwords inside a helper like this one, the bytes came out wrong: profiles/HISTORY.md,
-// "Area-averaged crops")
+// ---- staged source rows of the two upright kernels.  A staged row holds the pixels [xe, x0 + cw) of a source row as RGB bytes (xe = x0,
+// NV12: x0 & ~1), `units` units in `pitch` bytes: 16-byte pieces of the segment, NV12: quads of pixels converted from an even column
+struct stage_rows_t { int xe, units, pitch; };
 template <int FMT>
-__device__ __forceinline__ void area_stage_unit(const mhip_roi_t &p, const nv12_coef_t &kc, const uint8_t *frame, const int x0, const int xe, const int cw,
-                                               const int sy, const int u, unsigned char *row) {
+__device__ __forceinline__ stage_rows_t stage_rows(const slot_geom_t &g) {
+    stage_rows_t sr;
+    sr.xe = FMT ? (g.x0 & ~1) : g.x0;
+    sr.units = FMT ? (g.x0 + g.cw - sr.xe + 3) >> 2 : (g.cw * 3 + 15) >> 4;
+    sr.pitch = FMT ? (sr.units * 12 + 15) & ~15 : sr.units * 16;
+    return sr;
+}
+// Unit u of the staged image `row` of source row sy.  RGB: 16 bytes of the segment; NV12: four pixels, 12 bytes, each stored on its own
+// (packed into dwords inside a helper like this one, the bytes came out wrong: profiles/HISTORY.md, "Area-averaged crops")
+template <int FMT>
+__device__ __forceinline__ void stage_unit(const mhip_roi_t &p, const nv12_coef_t &kc, const uint8_t *frame, const slot_geom_t &g, const stage_rows_t &sr,
+                                          const int sy, const int u, unsigned char *row) {
     if (FMT) { // Y bytes of pixels xe + 4 u .. + 3 and, at the same byte offset of chroma row sy >> 1, their two chroma pairs
-        const int x = xe + 4 * u;
+        const int x = sr.xe + 4 * u;
         const uint8_t *gy = frame + (size_t)sy * p.w + x, *gc = frame + ((size_t)p.h + (size_t)(sy >> 1)) * p.w + x;
         unsigned yv, cv;
         if (x + 4 <= p.w) {
@@ -317,76 +357,51 @@ __device__ __forceinline__ void area_stage_unit(const mhip_roi_t &p, const nv12_
 #pragma unroll
         for (int k = 0; k < 12; k++) o[k] = (unsigned char)c[k / 3][k % 3];
     } else { // 16 bytes of the segment [x0 * 3, x1 * 3) of the row; the last piece byte by byte: nothing is read beyond the segment
-        const uint8_t *g = frame + ((size_t)sy * p.w + x0) * 3 + (size_t)u * 16;
+        const uint8_t *gp = frame + ((size_t)sy * p.w + g.x0) * 3 + (size_t)u * 16;
         unsigned v[4] = {0u, 0u, 0u, 0u};
-        const int left = cw * 3 - u * 16;
-        if (left >= 16) __builtin_memcpy(v, g, 16);
+        const int left = g.cw * 3 - u * 16;
+        if (left >= 16) __builtin_memcpy(v, gp, 16);
         else {
 #pragma unroll
             for (int b = 0; b < 15; b++) // (register indices fixed by the unrolling)
-                if (b < left) v[b >> 2] |= (unsigned)g[b] << (8 * (b & 3));
+                if (b < left) v[b >> 2] |= (unsigned)gp[b] << (8 * (b & 3));
         }
         *(uint4 *)(row + u * 16) = make_uint4(v[0], v[1], v[2], v[3]);
     }
 }
 
+// A workgroup owns ROI_R output rows of one slot: it builds the column table, then takes its rows in groups of as many as the row buffer
+// holds source rows for: stage those, blend the group's pixels from them into the strip's image
 template <int FMT>
 __global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const int off_meta, const int off_stage, const int off_rows, const int rowbuf_bytes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int tid = threadIdx.x;
-    const int slot = blockIdx.y, ys = blockIdx.x * ROI_R;
-    const int rows = min(ROI_R, p.th - ys), row_b = p.tw * 3;
-    int8_t *dst = p.out + (size_t)slot * p.out_stride;
-    // this slot's geometry, from device memory
-    bool live = slot < p.n_out[0];
-    roi_t r = {0, 0, 0, 0, 0, 0};
-    if (live) r = ((const roi_t *)p.rois)[slot];
-    const int cw = r.x1 - r.x0, ch = r.y1 - r.y0;
-    live = live && cw > 0 && ch > 0 && r.frame >= 0 && r.frame < p.n_frames && r.x0 >= 0 && r.y0 >= 0 && r.x1 <= p.w && r.y1 <= p.h;
-    int nw = p.tw, nh = p.th;
-    if (live && p.keep_aspect) {
-        if ((long long)cw * p.th >= (long long)ch * p.tw) nh = max(1, (int)(((long long)ch * p.tw + cw / 2) / cw));
-        else nw = max(1, (int)(((long long)cw * p.th + ch / 2) / ch));
-    }
-    const int px = (p.tw - nw) / 2, py = (p.th - nh) / 2;
-    const int r_lo = max(py - ys, 0), r_hi = min(py + nh - ys, rows); // the strip's rows inside the resized crop
-    if (!live || r_hi <= r_lo) { // an empty slot, a skipped box or a pad band: grey, the source is not touched
-        if (p.nhwc) roi_fill_run(dst + (size_t)ys * row_b, rows * row_b, tid);
-        else
-            for (int c = 0; c < 3; c++) roi_fill_run(dst + ((size_t)c * p.th + ys) * p.tw, rows * p.tw, tid);
+    strip_t s = strip_open(p, blockIdx.y, blockIdx.x * ROI_R, ROI_R);
+    const slot_geom_t g = slot_geom(p, blockIdx.y);
+    if (!g.live || !strip_cover(s, g.py, g.nh)) {
+        strip_grey(s, tid);
         return;
     }
-    int2 *coltab = (int2 *)sm;                       // [nw] {byte offset of the left tap in a staged row, fx | (distance to the right tap) << 8}
-    int *meta = (int *)(sm + off_meta);              // [0] end of the group of rows, [1] staged source rows; [4 ..) their numbers; [32 ..) per strip row {slot a, slot b, fy, -}
-    int8_t *stage = (int8_t *)(sm + off_stage);
+    int2 *coltab = (int2 *)sm;          // [nw] {byte offset of the left tap in a staged row, fx | (distance to the right tap) << 8}
+    int *meta = (int *)(sm + off_meta); // [0] end of the group of rows, [1] staged source rows; [4 ..) their numbers; [32 ..) per strip row {slot a, slot b, fy, -}
     unsigned char *rowbuf = sm + off_rows;
-    const uint8_t *frame = p.frames + (size_t)r.frame * p.frame_stride;
-    // a staged row holds the pixels [xe, x1) of a source row as RGB bytes; NV12 rows are converted four pixels at a time from an even column
-    const int xe = FMT ? (r.x0 & ~1) : r.x0;
-    const int units = FMT ? (r.x1 - xe + 3) >> 2 : (cw * 3 + 15) >> 4; // quads of pixels / 16-byte pieces per staged row
-    const int pitch = FMT ? (units * 12 + 15) & ~15 : units * 16;
-    const int cap_rows = rowbuf_bytes / pitch; // >= 2: the launcher sized the buffer for the widest box
-    for (int i = tid; i < nw; i += 256) {
-        const int pos = roi_pos(i, cw, nw), i0 = pos >> 8, i1 = min(i0 + 1, cw - 1);
-        coltab[i] = make_int2((i0 + r.x0 - xe) * 3, (pos & 255) | ((i1 - i0) * 3) << 8);
+    const uint8_t *frame = p.frames + (size_t)g.frame * p.frame_stride;
+    const stage_rows_t sr = stage_rows<FMT>(g);
+    const int cap_rows = rowbuf_bytes / sr.pitch; // >= 2: the launcher sized the buffer for the widest box
+    for (int i = tid; i < g.nw; i += 256) {
+        const int pos = roi_pos(i, g.cw, g.nw), i0 = pos >> 8, i1 = min(i0 + 1, g.cw - 1);
+        coltab[i] = make_int2((i0 + g.x0 - sr.xe) * 3, (pos & 255) | ((i1 - i0) * 3) << 8);
     }
-    // the strip's bytes: grey first (bands left / right of the crop, rows outside it).  The strip (planar: each channel's rows) is one contiguous
-    // run of the destination; its LDS image starts at the same offset inside a 16-byte line as the run does in memory
-    int8_t *st[3];
-    const int chan = ((ROI_R * p.tw + 15) & ~15) + 16; // bytes per channel region: a multiple of 16, so every region starts on a 16-byte line
-    if (p.nhwc) st[0] = st[1] = st[2] = stage + ((uintptr_t)(dst + (size_t)ys * row_b) & 15);
-    else
-        for (int c = 0; c < 3; c++) st[c] = stage + c * chan + ((uintptr_t)(dst + ((size_t)c * p.th + ys) * p.tw) & 15);
-    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
+    strip_image(s, (int8_t *)(sm + off_stage), ROI_R, p.tw, tid);
     const nv12_coef_t kc = nv12_coef(p.nv12_flags);
-    int r_cur = r_lo;
-    while (r_cur < r_hi) {
+    int r_cur = s.r_lo;
+    while (r_cur < s.r_hi) {
         // the next group of rows: as many as the row buffer holds source rows for.  Source rows only grow along the strip, so a row that is
         // already staged is one of the last two
         if (tid == 0) {
             int n_st = 0, rr = r_cur;
-            for (; rr < r_hi; rr++) {
-                const int pos = roi_pos(ys + rr - py, ch, nh), j0 = pos >> 8, j1 = min(j0 + 1, ch - 1);
+            for (; rr < s.r_hi; rr++) {
+                const int pos = roi_pos(s.ys + rr - g.py, g.ch, g.nh), j0 = pos >> 8, j1 = min(j0 + 1, g.ch - 1);
                 int a = -1, b = -1;
                 for (int k = max(n_st - 2, 0); k < n_st; k++) {
                     if (meta[4 + k] == j0) a = k;
@@ -403,63 +418,26 @@ __global__ __launch_bounds__(256) void roi_crop_kernel(const mhip_roi_t p, const
         }
         __syncthreads(); // (the first time round also: the column table and the grey strip)
         const int r_end = meta[0], n_st = meta[1];
-        for (int it = tid; it < n_st * units; it += 256) {
-            const int s = it / units, u = it - s * units;
-            const int sy = r.y0 + meta[4 + s];
-            if (FMT) { // Y bytes of pixels xe + 4 u .. + 3 and, at the same byte offset of chroma row sy >> 1, their two chroma pairs
-                const int x = xe + 4 * u;
-                const uint8_t *gy = frame + (size_t)sy * p.w + x, *gc = frame + ((size_t)p.h + (size_t)(sy >> 1)) * p.w + x;
-                unsigned yv, cv;
-                if (x + 4 <= p.w) {
-                    __builtin_memcpy(&yv, gy, 4);
-                    __builtin_memcpy(&cv, gc, 4);
-                } else { // w % 4 == 2: the row's last two pixels and their one pair; nothing is read beyond either row
-                    yv = (unsigned)gy[0] | (unsigned)gy[1] << 8;
-                    cv = (unsigned)gc[0] | (unsigned)gc[1] << 8;
-                }
-                int c[4][3];
-                nv12_quad(kc, yv, cv, c);
-                unsigned *o = (unsigned *)(rowbuf + s * pitch + u * 12);
-                o[0] = (unsigned)c[0][0] | (unsigned)c[0][1] << 8 | (unsigned)c[0][2] << 16 | (unsigned)c[1][0] << 24;
-                o[1] = (unsigned)c[1][1] | (unsigned)c[1][2] << 8 | (unsigned)c[2][0] << 16 | (unsigned)c[2][1] << 24;
-                o[2] = (unsigned)c[2][2] | (unsigned)c[3][0] << 8 | (unsigned)c[3][1] << 16 | (unsigned)c[3][2] << 24;
-            } else { // 16 bytes of the segment [x0 * 3, x1 * 3) of the row; the last piece byte by byte: nothing is read beyond the segment
-                const uint8_t *g = frame + ((size_t)sy * p.w + r.x0) * 3 + (size_t)u * 16;
-                unsigned v[4] = {0u, 0u, 0u, 0u};
-                const int left = cw * 3 - u * 16;
-                if (left >= 16) __builtin_memcpy(v, g, 16);
-                else {
-#pragma unroll
-                    for (int b = 0; b < 15; b++) // (register indices fixed by the unrolling)
-                        if (b < left) v[b >> 2] |= (unsigned)g[b] << (8 * (b & 3));
-                }
-                *(uint4 *)(rowbuf + s * pitch + u * 16) = make_uint4(v[0], v[1], v[2], v[3]);
-            }
+        for (int it = tid; it < n_st * sr.units; it += 256) {
+            const int st = it / sr.units, u = it - st * sr.units;
+            stage_unit<FMT>(p, kc, frame, g, sr, g.y0 + meta[4 + st], u, rowbuf + st * sr.pitch);
         }
         __syncthreads();
-        const int npix = (r_end - r_cur) * nw;
+        const int npix = (r_end - r_cur) * g.nw;
         for (int idx = tid; idx < npix; idx += 256) {
-            const int rr = idx / nw, i = idx - rr * nw, row = r_cur + rr;
+            const int rr = idx / g.nw, i = idx - rr * g.nw, row = r_cur + rr;
             const int4 rt = *(const int4 *)(meta + 32 + 4 * row);
-            const unsigned char *ra = rowbuf + rt.x * pitch, *rb = rowbuf + rt.y * pitch;
+            const unsigned char *ra = rowbuf + rt.x * sr.pitch, *rb = rowbuf + rt.y * sr.pitch;
             const int2 ct = coltab[i];
             const int o0 = ct.x, o1 = ct.x + (ct.y >> 8), fx = ct.y & 255, fy = rt.z;
+            const int pix = strip_pix(s, row, g.px + i);
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const int top = (int)ra[o0 + c] * (256 - fx) + (int)ra[o1 + c] * fx;
-                const int bot = (int)rb[o0 + c] * (256 - fx) + (int)rb[o1 + c] * fx;
-                const int v = (top * (256 - fy) + bot * fy + 32768) >> 16;
-                const int8_t q = (int8_t)(v - 128);
-                if (p.nhwc) st[0][row * row_b + (px + i) * 3 + c] = q;
-                else st[c][row * p.tw + px + i] = q;
-            }
+            for (int c = 0; c < 3; c++) strip_put(s, pix, c, blend4(ra[o0 + c], ra[o1 + c], rb[o0 + c], rb[o1 + c], fx, fy));
         }
         __syncthreads(); // the rows and the group record may be overwritten
         r_cur = r_end;
     }
-    if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
-    else
-        for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
+    strip_store(s, tid);
 }
 
 // ---- the area-averaging crop ("Area averaging" in include/mars_hip.h): an axis with more source samples than outputs is box-filtered, the
@@ -486,14 +464,12 @@ static size_t area_rowbuf(int w, int tw, int fmt) { // 0: the widest source row 
 
 struct area_geom_t {
     const uint8_t *frame;
-    int x0, y0, xe, cw, ch, nw, nh, px, py, ys, r_lo, r_hi, ax, ay; // ax, ay: the axis is averaged
-    int units, pitch, cap_rows, np3, hs_pitch;
+    stage_rows_t sr;
+    int ax, ay; // the axis is averaged
+    int cap_rows, np3, hs_pitch;
     const unsigned *coltab; // averaged x: first tap's pixel in a staged row | taps << 16; else: left tap's pixel | (distance to the right tap) << 16 | fx << 24
     unsigned *hs;
     unsigned char *rowbuf;
-    int8_t *stage, *st0;  // the strip's LDS image: planar, channel c at stage + c * chan + ((lo + c * plane) & 15); nhwc: st0
-    int chan;
-    unsigned lo, plane;
 };
 
 // the source rows [sa, sb] of output row o and, on an interpolated axis, fy
@@ -509,44 +485,43 @@ __device__ __forceinline__ void area_row_span(const int o, const int ch, const i
 }
 
 template <int FMT, int NP, typename ACC>
-__device__ __forceinline__ void area_strip(const mhip_roi_t &p, const area_geom_t &g, const int tid) {
+__device__ __forceinline__ void area_strip(const mhip_roi_t &p, const slot_geom_t &g, const area_geom_t &a, const strip_t &s, const int tid) {
     const nv12_coef_t kc = nv12_coef(p.nv12_flags);
-    const ACC D = (ACC)(g.ax ? g.cw : 256) * (ACC)(g.ay ? g.ch : 256);
-    const int row_b = p.tw * 3;
+    const ACC D = (ACC)(a.ax ? g.cw : 256) * (ACC)(a.ay ? g.ch : 256);
     int s_last, sa, sb, fy;
-    area_row_span(g.ys + g.r_hi - 1 - g.py, g.ch, g.nh, g.ay, sa, s_last, fy);
+    area_row_span(s.ys + s.r_hi - 1 - g.py, g.ch, g.nh, a.ay, sa, s_last, fy);
     int tag0 = -1, tag1 = -1, b0 = 0, b1 = -1; // the cached rows, the staged window [b0, b1]
-    for (int row = g.r_lo; row < g.r_hi; row++) {
-        const int o = g.ys + row - g.py;
-        area_row_span(o, g.ch, g.nh, g.ay, sa, sb, fy);
+    for (int row = s.r_lo; row < s.r_hi; row++) {
+        const int o = s.ys + row - g.py;
+        area_row_span(o, g.ch, g.nh, a.ay, sa, sb, fy);
         ACC acc[NP];
 #pragma unroll
         for (int k = 0; k < NP; k++) acc[k] = 0;
-        for (int s = sa; s <= sb; s++) {
-            const int wy = g.ay ? (int)(min((long long)(s + 1) * g.nh, (long long)(o + 1) * g.ch) - max((long long)s * g.nh, (long long)o * g.ch))
-                                : (sb == sa ? 256 : (s == sa ? 256 - fy : fy));
-            unsigned *hrow = g.hs + (s & 1) * g.hs_pitch;
-            if ((s & 1 ? tag1 : tag0) != s) { // (uniform: every thread walks the same rows)
-                if (s < b0 || s > b1) {
+        for (int sy = sa; sy <= sb; sy++) {
+            const int wy = a.ay ? (int)(min((long long)(sy + 1) * g.nh, (long long)(o + 1) * g.ch) - max((long long)sy * g.nh, (long long)o * g.ch))
+                                : (sb == sa ? 256 : (sy == sa ? 256 - fy : fy));
+            unsigned *hrow = a.hs + (sy & 1) * a.hs_pitch;
+            if ((sy & 1 ? tag1 : tag0) != sy) { // (uniform: every thread walks the same rows)
+                if (sy < b0 || sy > b1) {
                     __syncthreads(); // the old window is read no more (the first time round: the column table and the grey strip)
-                    b0 = s; b1 = min(s + g.cap_rows - 1, s_last);
-                    for (int it = tid; it < (b1 - b0 + 1) * g.units; it += 256) {
-                        const int sr = it / g.units, u = it - sr * g.units;
-                        area_stage_unit<FMT>(p, kc, g.frame, g.x0, g.xe, g.cw, g.y0 + b0 + sr, u, g.rowbuf + sr * g.pitch);
+                    b0 = sy; b1 = min(sy + a.cap_rows - 1, s_last);
+                    for (int it = tid; it < (b1 - b0 + 1) * a.sr.units; it += 256) {
+                        const int st = it / a.sr.units, u = it - st * a.sr.units;
+                        stage_unit<FMT>(p, kc, a.frame, g, a.sr, g.y0 + b0 + st, u, a.rowbuf + st * a.sr.pitch);
                     }
                     __syncthreads();
                 }
-                const unsigned char *rp = g.rowbuf + (s - b0) * g.pitch;
-                const int xo = g.x0 - g.xe;
+                const unsigned char *rp = a.rowbuf + (sy - b0) * a.sr.pitch;
+                const int xo = g.x0 - a.sr.xe;
 #pragma unroll
                 for (int k = 0; k < NP; k++) {
                     const int q = tid + 256 * k;
-                    if (q < g.np3) {
+                    if (q < a.np3) {
                         const int i = q / 3, c = q - 3 * i;
-                        const unsigned ct = g.coltab[i];
+                        const unsigned ct = a.coltab[i];
                         const unsigned char *t = rp + (ct & 0xffffu) * 3 + c;
                         unsigned h;
-                        if (g.ax) { // first and last tap by the overlap rule, nw for every one between
+                        if (a.ax) { // first and last tap by the overlap rule, nw for every one between
                             const int n = (int)(ct >> 16), xa = (int)(ct & 0xffffu) - xo;
                             const unsigned w0 = (unsigned)(min((xa + 1) * g.nw, (i + 1) * g.cw) - i * g.cw), w1 = (unsigned)((i + 1) * g.cw - (xa + n - 1) * g.nw);
                             unsigned mid = 0;
@@ -559,23 +534,21 @@ __device__ __forceinline__ void area_strip(const mhip_roi_t &p, const area_geom_
                         hrow[q] = h;
                     }
                 }
-                if (s & 1) tag1 = s; else tag0 = s;
+                if (sy & 1) tag1 = sy; else tag0 = sy;
             }
 #pragma unroll
             for (int k = 0; k < NP; k++) {
                 const int q = tid + 256 * k;
-                if (q < g.np3) acc[k] += (ACC)(unsigned)wy * (ACC)hrow[q]; // the thread's own entries: no barrier
+                if (q < a.np3) acc[k] += (ACC)(unsigned)wy * (ACC)hrow[q]; // the thread's own entries: no barrier
             }
         }
 #pragma unroll
         for (int k = 0; k < NP; k++) {
             const int q = tid + 256 * k;
-            if (q < g.np3) {
+            if (q < a.np3) {
                 const int i = q / 3, c = q - 3 * i;
                 const int v = (int)((acc[k] + D / 2) / D);
-                const int8_t q8 = (int8_t)(v - 128);
-                if (p.nhwc) g.st0[row * row_b + (g.px + i) * 3 + c] = q8;
-                else g.stage[c * g.chan + ((g.lo + c * g.plane) & 15u) + row * p.tw + g.px + i] = q8; // channel c's image, at its run's offset inside a 16-byte line
+                strip_put(s, strip_pix(s, row, g.px + i), c, (int8_t)(v - 128));
             }
         }
     }
@@ -586,70 +559,40 @@ __global__ __launch_bounds__(256) void roi_area_crop_kernel(const mhip_roi_t p, 
                                                             const int rowbuf_bytes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int tid = threadIdx.x;
-    const int slot = blockIdx.y, ys = blockIdx.x * ar;
-    const int rows = min(ar, p.th - ys), row_b = p.tw * 3;
-    int8_t *dst = p.out + (size_t)slot * p.out_stride;
-    // this slot's geometry, from device memory: as roi_crop_kernel
-    bool live = slot < p.n_out[0];
-    roi_t r = {0, 0, 0, 0, 0, 0};
-    if (live) r = ((const roi_t *)p.rois)[slot];
-    const int cw = r.x1 - r.x0, ch = r.y1 - r.y0;
-    live = live && cw > 0 && ch > 0 && r.frame >= 0 && r.frame < p.n_frames && r.x0 >= 0 && r.y0 >= 0 && r.x1 <= p.w && r.y1 <= p.h;
-    int nw = p.tw, nh = p.th;
-    if (live && p.keep_aspect) {
-        if ((long long)cw * p.th >= (long long)ch * p.tw) nh = max(1, (int)(((long long)ch * p.tw + cw / 2) / cw));
-        else nw = max(1, (int)(((long long)cw * p.th + ch / 2) / ch));
-    }
-    const int px = (p.tw - nw) / 2, py = (p.th - nh) / 2;
-    const int r_lo = max(py - ys, 0), r_hi = min(py + nh - ys, rows);
-    if (!live || r_hi <= r_lo) {
-        if (p.nhwc) roi_fill_run(dst + (size_t)ys * row_b, rows * row_b, tid);
-        else
-            for (int c = 0; c < 3; c++) roi_fill_run(dst + ((size_t)c * p.th + ys) * p.tw, rows * p.tw, tid);
+    strip_t s = strip_open(p, blockIdx.y, blockIdx.x * ar, ar);
+    const slot_geom_t g = slot_geom(p, blockIdx.y);
+    if (!g.live || !strip_cover(s, g.py, g.nh)) {
+        strip_grey(s, tid);
         return;
     }
-    area_geom_t g;
+    area_geom_t a;
     unsigned *coltab = (unsigned *)sm;
-    int8_t *stage = (int8_t *)(sm + off_stage);
-    g.frame = p.frames + (size_t)r.frame * p.frame_stride;
-    g.x0 = r.x0; g.y0 = r.y0; g.xe = FMT ? (r.x0 & ~1) : r.x0;
-    g.cw = cw; g.ch = ch; g.nw = nw; g.nh = nh; g.px = px; g.py = py; g.ys = ys; g.r_lo = r_lo; g.r_hi = r_hi;
-    g.ax = cw > nw; g.ay = ch > nh;
-    g.units = FMT ? (r.x1 - g.xe + 3) >> 2 : (cw * 3 + 15) >> 4;
-    g.pitch = FMT ? (g.units * 12 + 15) & ~15 : g.units * 16;
-    g.cap_rows = rowbuf_bytes / g.pitch; // >= 1: the launcher sized the window for the widest box
-    g.np3 = nw * 3;
-    g.hs_pitch = (p.tw * 3 + 3) & ~3;
-    g.coltab = coltab; g.hs = (unsigned *)(sm + off_hs); g.rowbuf = sm + off_rows;
-    const int xo = r.x0 - g.xe;
-    for (int i = tid; i < nw; i += 256) {
-        if (g.ax) {
-            const int xa = (int)(((long long)i * cw) / nw), xb = (int)(((long long)(i + 1) * cw + nw - 1) / nw) - 1;
+    a.frame = p.frames + (size_t)g.frame * p.frame_stride;
+    a.sr = stage_rows<FMT>(g);
+    a.ax = g.cw > g.nw; a.ay = g.ch > g.nh;
+    a.cap_rows = rowbuf_bytes / a.sr.pitch; // >= 1: the launcher sized the window for the widest box
+    a.np3 = g.nw * 3;
+    a.hs_pitch = (p.tw * 3 + 3) & ~3;
+    a.coltab = coltab; a.hs = (unsigned *)(sm + off_hs); a.rowbuf = sm + off_rows;
+    const int xo = g.x0 - a.sr.xe;
+    for (int i = tid; i < g.nw; i += 256) {
+        if (a.ax) {
+            const int xa = (int)(((long long)i * g.cw) / g.nw), xb = (int)(((long long)(i + 1) * g.cw + g.nw - 1) / g.nw) - 1;
             coltab[i] = (unsigned)(xa + xo) | (unsigned)(xb - xa + 1) << 16;
         } else {
-            const int pos = roi_pos(i, cw, nw), i0 = pos >> 8, i1 = min(i0 + 1, cw - 1);
+            const int pos = roi_pos(i, g.cw, g.nw), i0 = pos >> 8, i1 = min(i0 + 1, g.cw - 1);
             coltab[i] = (unsigned)(i0 + xo) | (unsigned)(i1 - i0) << 16 | (unsigned)(pos & 255) << 24;
         }
     }
-    // the strip's LDS image, grey first: as in roi_crop_kernel, ar rows deep
-    const int chan = ((ar * p.tw + 15) & ~15) + 16;
-    int8_t *st[3];
-    if (p.nhwc) st[0] = st[1] = st[2] = stage + ((uintptr_t)(dst + (size_t)ys * row_b) & 15);
-    else
-        for (int c = 0; c < 3; c++) st[c] = stage + c * chan + ((uintptr_t)(dst + ((size_t)c * p.th + ys) * p.tw) & 15);
-    g.stage = stage; g.st0 = st[0]; g.chan = chan;
-    g.lo = (unsigned)((uintptr_t)(dst + (size_t)ys * p.tw) & 15); g.plane = (unsigned)p.th * (unsigned)p.tw;
-    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
-    const unsigned long long DD = (unsigned long long)(g.ax ? cw : 256) * (unsigned long long)(g.ay ? ch : 256);
-    if (DD <= AREA_ACC32_MAX) area_strip<FMT, NP, unsigned>(p, g, tid);
-    else area_strip<FMT, NP, unsigned long long>(p, g, tid);
+    strip_image(s, (int8_t *)(sm + off_stage), ar, p.tw, tid);
+    const unsigned long long DD = (unsigned long long)(a.ax ? g.cw : 256) * (unsigned long long)(a.ay ? g.ch : 256);
+    if (DD <= AREA_ACC32_MAX) area_strip<FMT, NP, unsigned>(p, g, a, s, tid);
+    else area_strip<FMT, NP, unsigned long long>(p, g, a, s, tid);
     __syncthreads();
-    if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
-    else
-        for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
+    strip_store(s, tid);
 }
 
-// ---- the rotated crop.  A workgroup owns ROI_R output rows of one slot, as above; it walks them in chunks of cn columns x rn rows.  The taps of a
+// ---- the rotated crop.  A workgroup owns a strip of ROI_R output rows of one slot, as above; it walks them in chunks of cn columns x rn rows.  The taps of a
 // chunk lie in a parallelogram of the source; its bounding rectangle is staged in LDS as one dword per pixel (R | G << 8 | B << 16; NV12 is
 // converted once per staged pixel pair, pixels outside the frame are 111 in every channel) and the blend reads its four taps from there.
 // cn and rn are chosen per strip so that the rectangle fits ROT_PIX pixels: the whole strip for the boxes a second stage sees, a few columns
@@ -671,8 +614,7 @@ __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, c
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int tid = threadIdx.x;
     const int slot = blockIdx.y, ys = blockIdx.x * ROI_R;
-    const int rows = min(ROI_R, p.th - ys), row_b = p.tw * 3;
-    int8_t *dst = p.out + (size_t)slot * p.out_stride;
+    strip_t s = strip_open(p, slot, ys, ROI_R);
     // this slot's box, from device memory: entry (frame, det) of the lists, or the caller's box `slot`
     bool live = slot < p.n_out[0];
     roi_t r = {0, 0, 0, 0, 0, 0};
@@ -695,23 +637,14 @@ __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, c
         if (live) g = rot_geom(d, we, he, cs, sn, p.tw, p.th, p.keep_aspect);
     }
     const int nw = g.nw, nh = g.nh, px = g.px, py = g.py;
-    const int r_lo = max(py - ys, 0), r_hi = min(py + nh - ys, rows); // the strip's rows inside the resized crop
-    if (!live || r_hi <= r_lo) { // an empty slot, a skipped box or a pad band: grey, the source is not touched
-        if (p.nhwc) roi_fill_run(dst + (size_t)ys * row_b, rows * row_b, tid);
-        else
-            for (int c = 0; c < 3; c++) roi_fill_run(dst + ((size_t)c * p.th + ys) * p.tw, rows * p.tw, tid);
+    if (!live || !strip_cover(s, py, nh)) {
+        strip_grey(s, tid);
         return;
     }
-    int8_t *stage = (int8_t *)sm;
+    const int r_lo = s.r_lo, r_hi = s.r_hi;
     unsigned *buf = (unsigned *)(sm + off_buf);
     const uint8_t *frame = p.frames + (size_t)r.frame * p.frame_stride;
-    // the strip's LDS image, grey first: as in roi_crop_kernel
-    int8_t *st[3];
-    const int chan = ((ROI_R * p.tw + 15) & ~15) + 16;
-    if (p.nhwc) st[0] = st[1] = st[2] = stage + ((uintptr_t)(dst + (size_t)ys * row_b) & 15);
-    else
-        for (int c = 0; c < 3; c++) st[c] = stage + c * chan + ((uintptr_t)(dst + ((size_t)c * p.th + ys) * p.tw) & 15);
-    for (int i = tid * 4; i < 3 * chan; i += 1024) *(unsigned *)(stage + i) = 0xefefefefu;
+    strip_image(s, (int8_t *)sm, ROI_R, p.tw, tid);
     // the chunk: columns first, then rows, halved until the bounding rectangle fits
     const int pad = FMT ? 2 : 0;
     int cn = nw, rn = r_hi - r_lo;
@@ -769,22 +702,15 @@ __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, c
                 const int fx = qx & 255, fy = qy & 255;
                 const unsigned *t = buf + ((qy >> 8) - by0) * bw + ((qx >> 8) - bx0);
                 const unsigned t00 = t[0], t01 = t[1], t10 = t[bw], t11 = t[bw + 1];
+                const int pix = strip_pix(s, row, px + i);
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const int top = (int)((t00 >> (8 * c)) & 255u) * (256 - fx) + (int)((t01 >> (8 * c)) & 255u) * fx;
-                    const int bot = (int)((t10 >> (8 * c)) & 255u) * (256 - fx) + (int)((t11 >> (8 * c)) & 255u) * fx;
-                    const int v = (top * (256 - fy) + bot * fy + 32768) >> 16;
-                    const int8_t q = (int8_t)(v - 128);
-                    if (p.nhwc) st[0][row * row_b + (px + i) * 3 + c] = q;
-                    else st[c][row * p.tw + px + i] = q;
-                }
+                for (int c = 0; c < 3; c++)
+                    strip_put(s, pix, c, blend4((t00 >> (8 * c)) & 255u, (t01 >> (8 * c)) & 255u, (t10 >> (8 * c)) & 255u, (t11 >> (8 * c)) & 255u, fx, fy));
             }
             __syncthreads(); // the staged rectangle may be overwritten
         }
     }
-    if (p.nhwc) roi_store_run(dst + (size_t)ys * row_b, st[0], rows * row_b, tid);
-    else
-        for (int c = 0; c < 3; c++) roi_store_run(dst + ((size_t)c * p.th + ys) * p.tw, st[c], rows * p.tw, tid);
+    strip_store(s, tid);
 }
 
 static bool roi_common_ok(const mhip_roi_t *p) {
@@ -798,23 +724,27 @@ static bool roi_align_ok(const mhip_roi_t *p) {
            (p->num_kpt == 32 || !(p->use >> p->num_kpt)) && p->tw > 0 && p->th > 0 && !p->csn;
 }
 
+// f(the list source as a compile-time constant) for a run-time src: the one place the three sources are spelled out, with their names in the checks
+template <typename F>
+static void with_src(const int src, F f) {
+    if (src == SRC_POSE) f(std::integral_constant<int, SRC_POSE>());
+    else if (src == SRC_ROT) f(std::integral_constant<int, SRC_ROT>());
+    else f(std::integral_constant<int, SRC_BOX>());
+}
+static const char *const ROI_SELECT_NAME[3] = {"roi select", "roi select (oriented)", "roi select (aligned)"};
+static const char *const ROI_RECTS_NAME[3] = {"roi rects", "roi rects (oriented)", "roi rects (aligned)"};
+
 static int roi_select(const mhip_roi_t *p, const int src) {
     if (!roi_common_ok(p) || !p->dets || !p->counts || !p->frame_kept || p->det_cap <= 0 || p->cls_count < 0 || p->max_per_frame < 0 ||
         (src == SRC_ROT) != (p->csn != nullptr))
         return -1;
     if (src == SRC_POSE && (!roi_align_ok(p) || !p->pose_recs || !p->pose_kpts || p->pose_max <= 0)) return -1;
     const dim3 g((unsigned)p->n_frames);
-    if (src == SRC_POSE) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, SRC_POSE>), g, dim3(64), 0, mhip_stream_native(), *p);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, SRC_POSE>), g, dim3(64), 0, mhip_stream_native(), *p);
-    } else if (src == SRC_ROT) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, SRC_ROT>), g, dim3(64), 0, mhip_stream_native(), *p);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, SRC_ROT>), g, dim3(64), 0, mhip_stream_native(), *p);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, SRC_BOX>), g, dim3(64), 0, mhip_stream_native(), *p);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, SRC_BOX>), g, dim3(64), 0, mhip_stream_native(), *p);
-    }
-    return mhip_check(hipGetLastError(), src == SRC_POSE ? "roi select (aligned)" : src == SRC_ROT ? "roi select (oriented)" : "roi select");
+    with_src(src, [&](auto S) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<0, decltype(S)::value>), g, dim3(64), 0, mhip_stream_native(), *p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_select_kernel<1, decltype(S)::value>), g, dim3(64), 0, mhip_stream_native(), *p);
+    });
+    return mhip_check(hipGetLastError(), ROI_SELECT_NAME[src]);
 }
 extern "C" int mhip_roi_select(const mhip_roi_t *p) { return roi_select(p, SRC_BOX); }
 extern "C" int mhip_roi_rot_select(const mhip_roi_t *p) { return roi_select(p, SRC_ROT); }
@@ -824,10 +754,8 @@ static int roi_rects(const mhip_roi_t *p, const int src) {
     if (!roi_common_ok(p) || !p->boxes || !p->frame_of_box || p->n_boxes <= 0 || p->n_boxes > p->slots || (src == SRC_ROT) != (p->csn != nullptr)) return -1;
     if (src == SRC_POSE && !roi_align_ok(p)) return -1;
     const dim3 g((unsigned)((p->n_boxes + 255) / 256));
-    if (src == SRC_POSE) hipLaunchKernelGGL(roi_rects_kernel<SRC_POSE>, g, dim3(256), 0, mhip_stream_native(), *p);
-    else if (src == SRC_ROT) hipLaunchKernelGGL(roi_rects_kernel<SRC_ROT>, g, dim3(256), 0, mhip_stream_native(), *p);
-    else hipLaunchKernelGGL(roi_rects_kernel<SRC_BOX>, g, dim3(256), 0, mhip_stream_native(), *p);
-    return mhip_check(hipGetLastError(), src == SRC_POSE ? "roi rects (aligned)" : src == SRC_ROT ? "roi rects (oriented)" : "roi rects");
+    with_src(src, [&](auto S) { hipLaunchKernelGGL(roi_rects_kernel<decltype(S)::value>, g, dim3(256), 0, mhip_stream_native(), *p); });
+    return mhip_check(hipGetLastError(), ROI_RECTS_NAME[src]);
 }
 extern "C" int mhip_roi_rects(const mhip_roi_t *p) { return roi_rects(p, SRC_BOX); }
 extern "C" int mhip_roi_rot_rects(const mhip_roi_t *p) { return roi_rects(p, SRC_ROT); }
@@ -878,24 +806,24 @@ extern "C" int mhip_roi_rot_fits(int w, int h, int tw) {
     return w <= 32767 && h <= 32767 && rot_lds(tw) <= 64 * 1024; // (x - 0.5) * 65536 of a centre inside the frame fits an int
 }
 
-extern "C" int mhip_roi_rot_crop(const mhip_roi_t *p) {
-    if (!roi_common_ok(p) || !p->frames || !p->out || !p->csn || (!p->dets && !p->boxes) || (p->dets && p->det_cap <= 0) || (p->boxes && p->n_boxes < p->slots) ||
-        p->tw <= 0 || p->th <= 0 || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 || !mhip_roi_rot_fits(p->w, p->h, p->tw))
+// the rotated sampler over the obb records (fit 0) or the fit table (fit 1), behind the checks both forms share
+static int rot_crop(const mhip_roi_t *p, const int fit) {
+    if (!p->frames || !p->out || p->tw <= 0 || p->th <= 0 || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 ||
+        !mhip_roi_rot_fits(p->w, p->h, p->tw))
         return -1;
-    const int off_buf = (int)roi_lds_stage(p->tw);
+    static const char *const name[2][2] = {{"rotated roi crop", "rotated roi crop (nv12)"}, {"aligned roi crop", "aligned roi crop (nv12)"}};
+    const auto k = fit ? (p->fmt ? roi_rot_crop_kernel<1, 1> : roi_rot_crop_kernel<0, 1>) : (p->fmt ? roi_rot_crop_kernel<1, 0> : roi_rot_crop_kernel<0, 0>);
     const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);
-    if (p->fmt) hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<1, 0>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<0, 0>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
-    return mhip_check(hipGetLastError(), p->fmt ? "rotated roi crop (nv12)" : "rotated roi crop");
+    hipLaunchKernelGGL(k, g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, (int)roi_lds_stage(p->tw));
+    return mhip_check(hipGetLastError(), name[fit][p->fmt]);
+}
+
+extern "C" int mhip_roi_rot_crop(const mhip_roi_t *p) {
+    if (!roi_common_ok(p) || !p->csn || (!p->dets && !p->boxes) || (p->dets && p->det_cap <= 0) || (p->boxes && p->n_boxes < p->slots)) return -1;
+    return rot_crop(p, 0);
 }
 
 extern "C" int mhip_roi_align_crop(const mhip_roi_t *p) {
-    if (!roi_common_ok(p) || !roi_align_ok(p) || !p->frames || !p->out || p->slots > 65535 || p->out_stride < (size_t)p->tw * p->th * 3 ||
-        !mhip_roi_rot_fits(p->w, p->h, p->tw))
-        return -1;
-    const int off_buf = (int)roi_lds_stage(p->tw);
-    const dim3 g((unsigned)((p->th + ROI_R - 1) / ROI_R), (unsigned)p->slots);
-    if (p->fmt) hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<1, 1>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(roi_rot_crop_kernel<0, 1>), g, dim3(256), rot_lds(p->tw), mhip_stream_native(), *p, off_buf);
-    return mhip_check(hipGetLastError(), p->fmt ? "aligned roi crop (nv12)" : "aligned roi crop");
+    if (!roi_common_ok(p) || !roi_align_ok(p)) return -1;
+    return rot_crop(p, 1);
 }

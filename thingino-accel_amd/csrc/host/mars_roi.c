@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../align_fit.h"
 #include "../mhip.h"
 #include "mars_hip.h"
 #include "mars_internal.h"
@@ -63,60 +64,14 @@ static mars_error_t align_opts(const mars_hip_roi_opts_t *o, const mars_hip_alig
     return MARS_OK;
 }
 
-/* "Aligned crops" on the host, step for step what align_fit of csrc/hip/roi.hip does (this file is built with -ffp-contract=off); 0 = skipped */
-static int q16(float v) { return (int)rintf(v * 65536.0f); }
-static int align_fit(const mars_kpt_t *kp, const mhip_roi_t *p, mars_align_t *a, int r[4]) {
-    memset(a, 0, sizeof(*a));
-    r[0] = r[1] = r[2] = r[3] = 0;
-    unsigned used = 0u;
-    int cnt = 0;
-    float sqx = 0.0f, sqy = 0.0f, spx = 0.0f, spy = 0.0f;
-    for (int j = 0; j < p->num_kpt; j++) {
-        if (!((p->use >> j) & 1u) || !(kp[j].v >= p->min_vis)) continue;
-        if (!(isfinite(kp[j].x) && isfinite(kp[j].y) && isfinite(kp[j].v))) return 0;
-        used |= 1u << j;
-        cnt++;
-        sqx = sqx + p->tmpl[j][0]; sqy = sqy + p->tmpl[j][1];
-        spx = spx + kp[j].x; spy = spy + kp[j].y;
-    }
-    if (cnt < 2) return 0;
-    const float n = (float)cnt;
-    const float qmx = sqx / n, qmy = sqy / n, pmx = spx / n, pmy = spy / n;
-    float A = 0.0f, B = 0.0f, D = 0.0f;
-    for (int j = 0; j < p->num_kpt; j++) {
-        if (!((used >> j) & 1u)) continue;
-        const float dqx = p->tmpl[j][0] - qmx, dqy = p->tmpl[j][1] - qmy, dpx = kp[j].x - pmx, dpy = kp[j].y - pmy;
-        A = A + ((dqx * dpx) + (dqy * dpy));
-        B = B + ((dqx * dpy) - (dqy * dpx));
-        D = D + ((dqx * dqx) + (dqy * dqy));
-    }
-    if (!(D > 0.0f)) return 0;
-    const float fa = A / D, fb = B / D;
-    if (!(isfinite(fa) && isfinite(fb))) return 0;
-    const float ux = (float)p->tw * 0.5f - qmx, uy = (float)p->th * 0.5f - qmy;
-    const float cx = pmx + ((fa * ux) - (fb * uy)), cy = pmy + ((fb * ux) + (fa * uy));
-    const float ae = fa * p->expand, be = fb * p->expand;
-    const float s = sqrtf((ae * ae) + (be * be));
-    const float we = s * (float)p->tw, he = s * (float)p->th;
-    if (!(we >= (float)p->min_size && he >= (float)p->min_size && we <= 32768.0f && he <= 32768.0f)) return 0;
-    if (!(cx >= 0.0f && cx <= (float)p->w && cy >= 0.0f && cy <= (float)p->h)) return 0; /* (a NaN centre is outside) */
-    const float ha = ae * 0.5f, hb = be * 0.5f;
-    a->Ux = q16(ha); a->Uy = q16(hb); a->Vx = q16(-hb); a->Vy = q16(ha);
-    a->X0 = q16(cx - 0.5f); a->Y0 = q16(cy - 0.5f);
-    a->used = used; a->n_used = cnt;
-    const float ac = fabsf(ae) / s, as = fabsf(be) / s;
-    const float ex = ((we * ac) + (he * as)) * 0.5f, ey = ((we * as) + (he * ac)) * 0.5f;
-    r[0] = (int)floorf(fmaxf(cx - ex, 0.0f)); r[2] = (int)ceilf(fminf(cx + ex, (float)p->w));
-    r[1] = (int)floorf(fmaxf(cy - ey, 0.0f)); r[3] = (int)ceilf(fminf(cy + ey, (float)p->h));
-    return 1;
-}
-
+/* "Aligned crops" on the host: align_fit of csrc/align_fit.h, the text the device compiles too; 0 = skipped */
+_Static_assert(sizeof(align_kpt_t) == sizeof(mars_kpt_t) && sizeof(align_t) == sizeof(mars_align_t), "align_fit.h restates mars_kpt_t and mars_align_t");
 int mars_yolo_align_fit(const mars_kpt_t *kpts, const mars_hip_align_opts_t *align, const mars_hip_roi_opts_t *opts, int tw, int th, mars_align_t *fit,
                         mars_roi_t *roi) {
     mhip_roi_t p;
     if (!kpts || !fit || align_opts(opts, align, tw, th, &p) != MARS_OK) return -1;
     int r[4];
-    const int kept = align_fit(kpts, &p, fit, r);
+    const int kept = align_fit((const align_kpt_t *)kpts, &p, (align_t *)fit, r);
     if (roi) { roi->x0 = r[0]; roi->y0 = r[1]; roi->x1 = r[2]; roi->y1 = r[3]; }
     return kept;
 }
