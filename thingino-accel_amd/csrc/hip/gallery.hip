@@ -29,7 +29,6 @@
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-typedef int gm_v4i __attribute__((ext_vector_type(4)));
 typedef unsigned long long gm_word_t;
 
 #define GM_QT 64        // queries per workgroup
@@ -69,9 +68,7 @@ __device__ __forceinline__ gm_word_t gm_shfl_xor(const gm_word_t v, const int ma
     return ((gm_word_t)hi << 32) | lo;
 }
 
-__device__ __forceinline__ unsigned gm_abs(const int v) { return v < 0 ? 0u - (unsigned)v : (unsigned)v; } // (|INT32_MIN| = 2^31 fits)
-
-// grid: queries rounded up to GM_QT, one wavefront each
+// grid: queries rounded up to GM_QT, one wavefront each: tail_core.hpp's quantise_row, its qinv, and the pad rows
 __global__ __launch_bounds__(64) void gm_quantise_kernel(const mhip_match_t p) {
     const int n = blockIdx.x, lane = threadIdx.x;
     int8_t *out = p.q + (size_t)n * p.cp;
@@ -80,21 +77,7 @@ __global__ __launch_bounds__(64) void gm_quantise_kernel(const mhip_match_t p) {
         return;
     }
     const int *v = p.vec + (size_t)n * p.c;
-    unsigned m = 0;
-    for (int c = lane; c < p.c; c += 64) m = max(m, gm_abs(v[c]));
-    for (int s = 32; s > 0; s >>= 1) m = max(m, (unsigned)__shfl_xor(m, s, 64));
-    int qq = 0;
-    for (int c = lane; c < p.cp; c += 64) {
-        int q = 0;
-        if (c < p.c && m) {
-            const int x = v[c];
-            const int mag = (int)(((unsigned long long)gm_abs(x) * 127u + (m >> 1)) / m);
-            q = x < 0 ? -mag : mag;
-        }
-        out[c] = (int8_t)q;
-        qq += q * q;
-    }
-    for (int s = 32; s > 0; s >>= 1) qq += __shfl_xor(qq, s, 64);
+    const int qq = quantise_row(out, p.c, p.cp, [v](const int c) { return v[c]; });
     if (lane == 0) {
         p.qq[n] = qq;
         p.qinv[n] = qq ? 1.0f / sqrtf((float)qq) : 0.0f;
@@ -119,30 +102,30 @@ __global__ __launch_bounds__(256) void gm_match_kernel(const mhip_match_t p, con
 #pragma unroll
         for (int i = 0; i < GM_KEEP; i++) list[u][i] = 0;
     }
-    gm_v4i b[4];
+    v4i b[4];
     if (ONE) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) b[u] = *(const gm_v4i *)(qp + (size_t)u * 16 * cp);
+        for (int u = 0; u < 4; u++) b[u] = *(const v4i *)(qp + (size_t)u * 16 * cp);
     }
     const int8_t *ap = p.rows + (size_t)(r0 + frow) * cp + fchunk * 16;
-    gm_v4i a_next = (gm_v4i){0, 0, 0, 0};
-    if (ONE && w < nsub) a_next = *(const gm_v4i *)(ap + (size_t)w * 16 * cp);
+    v4i a_next = (v4i){0, 0, 0, 0};
+    if (ONE && w < nsub) a_next = *(const v4i *)(ap + (size_t)w * 16 * cp);
     for (int s = w; s < nsub; s += 4) {
         const int row0 = r0 + s * 16;
-        gm_v4i acc[4];
+        v4i acc[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) acc[u] = (gm_v4i){0, 0, 0, 0};
+        for (int u = 0; u < 4; u++) acc[u] = (v4i){0, 0, 0, 0};
         if (ONE) {
-            const gm_v4i a = a_next;
-            if (s + 4 < nsub) a_next = *(const gm_v4i *)(ap + (size_t)(s + 4) * 16 * cp); // the next subtile's rows, under this one's arithmetic
+            const v4i a = a_next;
+            if (s + 4 < nsub) a_next = *(const v4i *)(ap + (size_t)(s + 4) * 16 * cp); // the next subtile's rows, under this one's arithmetic
 #pragma unroll
             for (int u = 0; u < 4; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[u], acc[u], 0, 0, 0);
         } else {
             const int8_t *as = ap + (size_t)s * 16 * cp;
             for (int ks = 0; ks < ksteps; ks++) {
-                const gm_v4i a = *(const gm_v4i *)(as + ks * 64);
+                const v4i a = *(const v4i *)(as + ks * 64);
 #pragma unroll
-                for (int u = 0; u < 4; u++) b[u] = *(const gm_v4i *)(qp + (size_t)u * 16 * cp + ks * 64);
+                for (int u = 0; u < 4; u++) b[u] = *(const v4i *)(qp + (size_t)u * 16 * cp + ks * 64);
 #pragma unroll
                 for (int u = 0; u < 4; u++) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[u], acc[u], 0, 0, 0);
             }

@@ -1,6 +1,7 @@
 // tail_core.hpp -- what the detection-tail kernels share, device-only and inlined: the mirrors of the public records, the ordered
 // block-wide rank, and the sort / class buckets / greedy suppression / compaction core of the three NMS kernels (sort_nms_kernel of
-// yolo_tail.hip, obb_sort_nms_kernel of obb.hip, tile_merge_kernel of tile.hip), the reference's upright IoU and the DFL head helpers.
+// yolo_tail.hip, obb_sort_nms_kernel of obb.hip, tile_merge_kernel of tile.hip), the reference's upright IoU, the int8 quantisation of an
+// embedding row (gallery.hip's queries, track_app.hip's vectors and its blend) and the DFL head helpers.
 // No kernels and no launchers here.  Every helper that contains a barrier says so; all of those are called by EVERY thread of the
 // workgroup under uniform control flow (a kernel's early returns stay ahead of them).
 #pragma once
@@ -89,6 +90,34 @@ __device__ __forceinline__ float box_iou(const box_edges_t &a, const float bx, c
     uni = uni - inter;
     uni = uni + 1e-6f;
     return inter / uni;
+}
+
+// -------------------------------------------------------- int8 embedding rows
+__device__ __forceinline__ unsigned abs_u32(const int v) { return v < 0 ? 0u - (unsigned)v : (unsigned)v; } // (|INT32_MIN| = 2^31 fits)
+
+// The gallery's quantisation rule (include/mars_hip.h, "Gallery match") on one row, by one wavefront, every lane calling: m = max |v| by
+// shuffles, out[k] = sign * ((|v| * 127 + m / 2) / m) in 64-bit integers for k < c, zero for the pad channels c .. cp - 1 and where m is 0;
+// -> qq = sum out^2 (the same in every lane).  value(k), k < c, is channel k's integer; a lane reads value(k) before it writes out[k] and
+// touches no other lane's channels, so value may read the row it writes.
+template <class Value>
+__device__ __forceinline__ int quantise_row(int8_t *out, const int c, const int cp, const Value value) {
+    const int lane = threadIdx.x & 63;
+    unsigned m = 0;
+    for (int k = lane; k < c; k += 64) m = max(m, abs_u32(value(k)));
+    for (int s = 32; s > 0; s >>= 1) m = max(m, (unsigned)__shfl_xor(m, s, 64));
+    int qq = 0;
+    for (int k = lane; k < cp; k += 64) {
+        int o = 0;
+        if (k < c && m) {
+            const int x = value(k);
+            const int mag = (int)(((unsigned long long)abs_u32(x) * 127u + (m >> 1)) / m);
+            o = x < 0 ? -mag : mag;
+        }
+        out[k] = (int8_t)o;
+        qq += o * o;
+    }
+    for (int s = 32; s > 0; s >>= 1) qq += __shfl_xor(qq, s, 64);
+    return qq;
 }
 
 // ------------------------------------------- sort, buckets, suppress, compact

@@ -1,9 +1,9 @@
 // track_app.hip -- tracking with an appearance term on gfx950: the walk of track.hip on a tracker whose slots hold an int8 embedding each,
 // the cosines of slots against candidates on v_mfma_i32_16x16x64_i8, and the embedding plane's update.
 //
-// include/mars_hip.h ("Appearance in tracking") states the arithmetic.  A kernel of its own, not a template shared with track.hip: the plain
-// kernel on a tracker without a plane keeps its instructions (profiles/HISTORY.md records what shared staging did to roi.hip), at the price
-// of the walk being written twice.  What differs from track.hip, per stream and step:
+// include/mars_hip.h ("Appearance in tracking") states the arithmetic.  The records, the LDS table, the scans, the candidates' compaction
+// and the rounds are track_core.hpp's, one source for this file and track.hip; the per-step body is this kernel's own, track.hip's with
+// the plane's steps worked in (track_core.hpp says why the body is not shared).  What the plane adds, per stream and step:
 //   candidates   the high set's compaction also notes each candidate's embedding row (emb_index -> q, qq), or none;
 //   cosines      between the compaction and pass 1 the eight wavefronts compute slots x candidates: a wavefront takes two of the sixteen
 //                16-slot tiles as the MFMA's A operand and walks the candidates' 16-tiles four at a time as B operands (gallery.hip's operand
@@ -14,69 +14,24 @@
 //                LDS; the scratch is written and read by one workgroup between two of its barriers and stays in L2.  A step in which no
 //                live slot or no candidate has an embedding skips the products and runs pass 1 on the IoU alone;
 //   association  pass 1 reads cos where both sides have an embedding and recomputes the IoU as before; a pair's key depends on the pair
-//                alone, so the mutual-best-pick rounds stay a valid evaluation of the greedy order.  Pass 2 is track.hip's;
+//                alone, so the mutual-best-pick rounds stay a valid evaluation of the greedy order.  Pass 2 is the plain one;
 //   embeddings   the update and the births leave one action per slot (take row r, blend with row r, clear, nothing); a wavefront per slot
-//                row then writes the plane in HBM, the 3:1 blend re-quantised by the rule of gallery.hip.
+//                row then writes the plane in HBM, the 3:1 blend re-quantised by the gallery's rule (tail_core.hpp's quantise_row, which
+//                gallery.hip's and this file's quantise launches call too).
 // The streams of a call run in chunks of MHIP_TRACK_APP_CHUNK over one scratch block, so the scratch is bounded by 256 MB whatever the
-// number of streams.  LDS: about 28 KB (track.hip's 25 KB + four int arrays of 256).
+// number of streams.  LDS: about 28 KB (the plain table's 25 KB + four int arrays of 256).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../mhip.h"
-#include "tail_core.hpp"
+#include "track_core.hpp"
 
 #pragma clang fp contract(off)
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-#define TA_SLOTS MHIP_TRACK_SLOTS
-#define TA_CAND MHIP_TRACK_CAND
-#define TA_THREADS 512
-#define TA_WAVES (TA_THREADS / 64)
-#define TA_TAKE_NONE (-1)
-#define TA_CLEAR (-2)
-static_assert(TA_SLOTS == 256 && TA_CAND == 256 && TA_WAVES == 8, "the tile walk below: sixteen 16-slot tiles over eight wavefronts");
-
-struct ta_out_t { int id, hits; };                                                        // mars_track_t
-struct ta_state_t { int id, cls, hits, miss; float x, y, w, h, vx, vy; cls_t ident; };    // mars_track_state_t
-static_assert(sizeof(ta_out_t) == 8 && sizeof(ta_state_t) == 48, "record sizes of include/mars_hip.h");
-
-__device__ __forceinline__ bool ta_finite(const float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ unsigned ta_abs(const int v) { return v < 0 ? 0u - (unsigned)v : (unsigned)v; } // (|INT32_MIN| = 2^31 fits)
-
-struct ta_lds_t {
-    // the table, one array per field
-    int id[TA_SLOTS], cls[TA_SLOTS], hits[TA_SLOTS], miss[TA_SLOTS];
-    float x[TA_SLOTS], y[TA_SLOTS], w[TA_SLOTS], h[TA_SLOTS], vx[TA_SLOTS], vy[TA_SLOTS];
-    int icls[TA_SLOTS];
-    float iscore[TA_SLOTS];
-    int ee[TA_SLOTS];                 // the slot's embedding: its sum of squares, 0 = none (the bytes live in HBM)
-    float px[TA_SLOTS], py[TA_SLOTS]; // the prediction of this step
-    int det[TA_SLOTS];                // the detection index this step's passes gave the slot, or -1
-    int take[TA_SLOTS];               // this step's embedding action: the row of q to take, TA_TAKE_NONE or TA_CLEAR
-    // the candidates of the running pass
-    float cx[TA_CAND], cy[TA_CAND], cw[TA_CAND], ch[TA_CAND];
-    int ccls[TA_CAND];
-    int crow[TA_CAND], cqq[TA_CAND];  // pass 1: the candidate's row of q and its qq; -1 and 0: it has no embedding
-    short cidx[TA_CAND], cslot[TA_CAND]; // index in the frame's list; the slot that took it, or -1
-    short tpick[TA_SLOTS], cpick[TA_CAND];
-    unsigned char tfree[TA_SLOTS], cfree[TA_CAND]; // still in the game
-    unsigned char blend[TA_SLOTS];    // the row taken is blended 3:1 into what the slot holds
-    // the high set after pass 1, for the births
-    short hidx[TA_CAND];
-    unsigned char hfree[TA_CAND];
-    short freelist[TA_SLOTS];
-    int wsum[TA_WAVES];
-    long long counters[4];
-    int next_id;
-};
-
-// rank of this thread among the threads with `flag`, in thread order, and their number.  Every thread of the workgroup calls it.
-__device__ __forceinline__ int ta_scan(const bool flag, int *wsum, int &total) {
-    __syncthreads(); // (the previous call's readers of wsum are through; what the caller wrote before is visible after)
-    return block_rank<TA_WAVES>(flag, wsum, total);
-}
+static_assert(TK_SLOTS == 256 && TK_CAND == 256 && TK_WAVES == 8, "the tile walk below: sixteen 16-slot tiles over eight wavefronts");
 
 // detection i of a frame -> its row of q, or -1: no index array, an index outside the rows, a null vector
 __device__ __forceinline__ int ta_row_of(const mhip_track_app_t &p, const int *idx, const int i, int &qq) {
@@ -88,52 +43,14 @@ __device__ __forceinline__ int ta_row_of(const mhip_track_app_t &p, const int *i
     return qq > 0 ? r : -1;
 }
 
-// the first TA_CAND members of a set into the candidate arrays, in index order; -> their number.  low: the set L, otherwise H (with rows)
-__device__ int ta_candidates(ta_lds_t &s, const mhip_track_app_t &pa, const det_t *d, const int *idx, const int n, const bool low) {
-    const mhip_track_t &p = pa.t;
-    const int tid = threadIdx.x;
-    if (tid < TA_CAND) { s.cfree[tid] = 0; s.crow[tid] = -1; s.cqq[tid] = 0; }
-    int running = 0;
-    for (int c0 = 0; c0 < n; c0 += TA_THREADS) { // (n is the same in every thread)
-        const int i = c0 + tid;
-        bool in = false;
-        det_t v;
-        if (i < n) {
-            v = d[i];
-            const bool gate = p.cls_count == 0 || (v.cls >= p.cls_first && (long long)v.cls < (long long)p.cls_first + p.cls_count);
-            const bool valid = ta_finite(v.x) && ta_finite(v.y) && ta_finite(v.w) && ta_finite(v.h) && ta_finite(v.conf) && v.w > 0.0f && v.h > 0.0f && gate;
-            in = valid && (low ? (v.conf >= p.low_conf && v.conf < p.min_conf) : v.conf >= p.min_conf);
-        }
-        int total;
-        const int pos = running + ta_scan(in, s.wsum, total); // (its barriers lie behind the clearing above)
-        if (in && pos < TA_CAND) {
-            s.cx[pos] = v.x; s.cy[pos] = v.y; s.cw[pos] = v.w; s.ch[pos] = v.h;
-            s.ccls[pos] = v.cls;
-            s.cidx[pos] = (short)i;
-            s.cslot[pos] = -1;
-            s.cfree[pos] = 1;
-            if (!low) {
-                int qq;
-                s.crow[pos] = ta_row_of(pa, idx, i, qq);
-                s.cqq[pos] = qq;
-            }
-        }
-        running += total;
-    }
-    const int nc = running < TA_CAND ? running : TA_CAND;
-    if (tid == 0) s.counters[2] += running - nc;
-    __syncthreads();
-    return nc;
-}
-
-// The cosines of the TA_SLOTS rows of `plane` (ee[t] == 0: none) against candidates 0 .. nc - 1 (crow[c] < 0: none): sm[t][c] and cm[c][t],
+// The cosines of the TK_SLOTS rows of `plane` (ee[t] == 0: none) against candidates 0 .. nc - 1 (crow[c] < 0: none): sm[t][c] and cm[c][t],
 // pitch 256, for every t and every c below nc rounded up to 16; 0.0f where a side has no embedding.  Every thread of the workgroup calls
 // it; no barrier inside: the caller has made ee, crow and cqq (LDS) and the rows (HBM) visible, and puts a barrier before the readers.
 __device__ void ta_matrix(const int8_t *plane, const int *ee, const int8_t *q, const int *crow, const int *cqq, const int nc, const int cp,
                           float *sm, float *cm) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, frow = lane & 15, fchunk = lane >> 4;
     const int ntile = (nc + 15) >> 4, ksteps = cp >> 6;
-    for (int tt = w; tt < TA_SLOTS / 16; tt += TA_WAVES) {
+    for (int tt = w; tt < TK_SLOTS / 16; tt += TK_WAVES) {
         const int t0 = tt * 16, tb = t0 + 4 * fchunk; // this lane's four slots: tb .. tb + 3
         float einv[4];
 #pragma unroll
@@ -178,85 +95,11 @@ __device__ void ta_matrix(const int8_t *plane, const int *ee, const int8_t *q, c
                 for (int e = 0; e < 4; e++) {
                     const float k = (float)acc[u][e] * einv[e]; // two roundings, then a third: no contraction in this file
                     v[e] = (einv[e] != 0.0f && qinv[u] != 0.0f) ? k * qinv[u] : 0.0f;
-                    sm[(size_t)(tb + e) * TA_CAND + c] = v[e];
+                    sm[(size_t)(tb + e) * TK_CAND + c] = v[e];
                 }
-                *(float4 *)(cm + (size_t)c * TA_SLOTS + tb) = make_float4(v[0], v[1], v[2], v[3]);
+                *(float4 *)(cm + (size_t)c * TK_SLOTS + tb) = make_float4(v[0], v[1], v[2], v[3]);
             }
         }
-    }
-}
-
-// one pass: the tracks with tfree set against the nc candidates.  Leaves det[slot] and cslot[candidate] of the pairs taken.  APP: pass 1
-// with the cosines of ta_matrix (sm, cm)
-template <bool APP>
-__device__ void ta_associate(ta_lds_t &s, const int nc, const float thresh, const bool any_class, const float app_thresh, const float app_min_iou,
-                             const float *sm, const float *cm) {
-    const int tid = threadIdx.x;
-    const bool track_side = tid < TA_SLOTS;
-    const int me = track_side ? tid : tid - TA_SLOTS;
-    for (;;) {
-        if (track_side) {
-            int pick = -1;
-            if (s.tfree[me]) {
-                const box_edges_t a = box_edges(s.px[me], s.py[me], s.w[me], s.h[me]); // the track at its prediction
-                const int acls = s.cls[me];
-                const bool mine = APP && s.ee[me] > 0;
-                float best = 0.0f;
-                for (int j = 0; j < nc; j++) {
-                    if (!s.cfree[j] || !(any_class || s.ccls[j] == acls)) continue;
-                    const float iou = box_iou(a, s.cx[j], s.cy[j], s.cw[j], s.ch[j]);
-                    float key = iou;
-                    bool ok = iou >= thresh;
-                    if (APP && mine && s.cqq[j] > 0) {
-                        const float cs = cm[(size_t)j * TA_SLOTS + me];
-                        if (cs >= app_thresh && iou >= app_min_iou) { key = fmaxf(iou, cs); ok = true; }
-                    }
-                    if (ok && (pick < 0 || key > best)) { best = key; pick = j; } // ties: the lower index stays
-                }
-            }
-            s.tpick[me] = (short)pick;
-        } else {
-            int pick = -1;
-            if (me < nc && s.cfree[me]) {
-                const float bx = s.cx[me], by = s.cy[me], bw = s.cw[me], bh = s.ch[me];
-                const int bcls = s.ccls[me];
-                const bool mine = APP && s.cqq[me] > 0;
-                float best = 0.0f;
-                for (int t = 0; t < TA_SLOTS; t++) {
-                    if (!s.tfree[t] || !(any_class || s.cls[t] == bcls)) continue;
-                    const float iou = box_iou(box_edges(s.px[t], s.py[t], s.w[t], s.h[t]), bx, by, bw, bh);
-                    float key = iou;
-                    bool ok = iou >= thresh;
-                    if (APP && mine && s.ee[t] > 0) {
-                        const float cs = sm[(size_t)t * TA_CAND + me];
-                        if (cs >= app_thresh && iou >= app_min_iou) { key = fmaxf(iou, cs); ok = true; }
-                    }
-                    if (ok && (pick < 0 || key > best)) { best = key; pick = t; } // ties: the lower slot stays
-                }
-            }
-            s.cpick[me] = (short)pick;
-        }
-        __syncthreads();
-        int took = 0;
-        if (track_side) {
-            if (s.tfree[me]) {
-                const int j = s.tpick[me];
-                if (j < 0) s.tfree[me] = 0; // nothing eligible is left for it, and nothing will be
-                else if (s.cpick[j] == me) {
-                    s.det[me] = s.cidx[j];
-                    s.tfree[me] = 0;
-                    took = 1;
-                }
-            }
-        } else if (me < nc && s.cfree[me]) {
-            const int t = s.cpick[me];
-            if (t < 0) s.cfree[me] = 0;
-            else if (s.tpick[t] == me) {
-                s.cslot[me] = (short)t;
-                s.cfree[me] = 0;
-            }
-        }
-        if (!__syncthreads_or(took)) break; // every round with a free eligible pair takes the best of them: at most 256 rounds and one
     }
 }
 
@@ -271,37 +114,22 @@ __device__ int ta_row_update(int8_t *row, const int ee, const int8_t *src, const
         for (int c = lane; c < cp; c += 64) row[c] = src[c]; // (the pad channels of q are zero)
         return src_qq;
     }
-    // v = 3 e + q, |v| <= 508: the rule's 64-bit products fit 32 bits here
-    unsigned m = 0;
-    for (int c = lane; c < cp; c += 64) m = max(m, ta_abs(3 * (int)row[c] + (int)src[c]));
-    for (int sft = 32; sft > 0; sft >>= 1) m = max(m, (unsigned)__shfl_xor(m, sft, 64));
-    int qq = 0;
-    for (int c = lane; c < cp; c += 64) {
-        int o = 0;
-        if (m) {
-            const int v = 3 * (int)row[c] + (int)src[c];
-            const int mag = (int)((ta_abs(v) * 127u + (m >> 1)) / m);
-            o = v < 0 ? -mag : mag;
-        }
-        row[c] = (int8_t)o; // (this lane's own bytes: read above, by this lane alone)
-        qq += o * o;
-    }
-    for (int sft = 32; sft > 0; sft >>= 1) qq += __shfl_xor(qq, sft, 64);
-    return qq;
+    // v = 3 e + q over all cp channels (the pads of both rows are zero, and stay so); a lane's own bytes, read before it writes them
+    return quantise_row(row, cp, cp, [row, src](const int c) { return 3 * (int)row[c] + (int)src[c]; });
 }
 
 // grid: the streams of one chunk; b0: the first of them
-__global__ __launch_bounds__(TA_THREADS) void track_app_kernel(const mhip_track_app_t pa, const int b0) {
-    __shared__ ta_lds_t s;
+__global__ __launch_bounds__(TK_THREADS) void track_app_kernel(const mhip_track_app_t pa, const int b0) {
+    __shared__ tk_lds_t<true> s;
     const mhip_track_t &p = pa.t;
     const int tid = threadIdx.x, b = b0 + blockIdx.x;
-    ta_state_t *table = (ta_state_t *)p.states + (size_t)b * TA_SLOTS;
-    int8_t *plane = pa.plane + (size_t)b * TA_SLOTS * pa.cp;
-    int *plane_ee = pa.plane_ee + (size_t)b * TA_SLOTS;
-    float *sm = pa.cosm ? pa.cosm + (size_t)blockIdx.x * MHIP_TRACK_APP_COS_FLOATS : nullptr, *cm = sm ? sm + TA_SLOTS * TA_CAND : nullptr;
+    tk_state_t *table = (tk_state_t *)p.states + (size_t)b * TK_SLOTS;
+    int8_t *plane = pa.plane + (size_t)b * TK_SLOTS * pa.cp;
+    int *plane_ee = pa.plane_ee + (size_t)b * TK_SLOTS;
+    float *sm = pa.cosm ? pa.cosm + (size_t)blockIdx.x * MHIP_TRACK_APP_COS_FLOATS : nullptr, *cm = sm ? sm + TK_SLOTS * TK_CAND : nullptr;
     const bool with_vectors = pa.emb_index && pa.n_vec > 0 && sm;
-    if (tid < TA_SLOTS) {
-        const ta_state_t v = table[tid];
+    if (tid < TK_SLOTS) {
+        const tk_state_t v = table[tid];
         s.id[tid] = v.id; s.cls[tid] = v.cls; s.hits[tid] = v.hits; s.miss[tid] = v.miss;
         s.x[tid] = v.x; s.y[tid] = v.y; s.w[tid] = v.w; s.h[tid] = v.h; s.vx[tid] = v.vx; s.vy[tid] = v.vy;
         s.icls[tid] = v.ident.cls; s.iscore[tid] = v.ident.score;
@@ -315,40 +143,40 @@ __global__ __launch_bounds__(TA_THREADS) void track_app_kernel(const mhip_track_
         const det_t *d = (const det_t *)p.dets + f * p.max_det;
         const cls_t *idn = p.idents ? (const cls_t *)p.idents + f * p.max_det : nullptr;
         const int *idx = with_vectors ? pa.emb_index + f * p.max_det : nullptr;
-        ta_out_t *o = (ta_out_t *)p.out + f * p.max_det;
+        tk_out_t *o = (tk_out_t *)p.out + f * p.max_det;
         int n = p.counts[f];
         n = n < 0 ? 0 : n > p.max_det ? p.max_det : n;
-        for (int i = tid; i < p.max_det; i += TA_THREADS) o[i] = ta_out_t{-1, 0};
-        const bool live = tid < TA_SLOTS && s.hits[tid] > 0;
-        if (tid < TA_SLOTS) {
+        for (int i = tid; i < p.max_det; i += TK_THREADS) o[i] = tk_out_t{-1, 0};
+        const bool live = tid < TK_SLOTS && s.hits[tid] > 0;
+        if (tid < TK_SLOTS) {
             s.px[tid] = s.x[tid] + s.vx[tid];
             s.py[tid] = s.y[tid] + s.vy[tid];
             s.det[tid] = -1;
-            s.take[tid] = TA_TAKE_NONE;
+            s.take[tid] = TK_TAKE_NONE;
             s.blend[tid] = 0;
             s.tfree[tid] = live;
         }
         // pass 1: every live track against H, with the cosines where both sides of some pair have an embedding
-        const int nh = ta_candidates(s, pa, d, idx, n, false);
-        const int some_c = __syncthreads_or(tid < nh && s.cqq[tid < TA_CAND ? tid : 0] > 0);
-        const int some_t = __syncthreads_or(live && s.ee[tid < TA_SLOTS ? tid : 0] > 0);
+        const int nh = tk_candidates<true>(s, pa, d, idx, n, false);
+        const int some_c = __syncthreads_or(tid < nh && s.cqq[tid < TK_CAND ? tid : 0] > 0);
+        const int some_t = __syncthreads_or(live && s.ee[tid < TK_SLOTS ? tid : 0] > 0);
         if (idx && some_c && some_t) {
             ta_matrix(plane, s.ee, pa.q, s.crow, s.cqq, nh, pa.cp, sm, cm);
             __syncthreads(); // the matrix in HBM, written and read by this workgroup alone
-            ta_associate<true>(s, nh, p.iou, p.any_class != 0, pa.app_thresh, pa.app_min_iou, sm, cm);
+            tk_associate<true>(s, nh, p.iou, p.any_class != 0, pa.app_thresh, pa.app_min_iou, sm, cm);
         } else {
-            ta_associate<false>(s, nh, p.iou, p.any_class != 0, 0.0f, 0.0f, nullptr, nullptr);
+            tk_associate<false>(s, nh, p.iou, p.any_class != 0, 0.0f, 0.0f, nullptr, nullptr);
         }
-        if (tid < TA_CAND) {
+        if (tid < TK_CAND) {
             s.hidx[tid] = s.cidx[tid];
             s.hfree[tid] = tid < nh && s.cslot[tid] < 0;
         }
         __syncthreads();
         // pass 2: the tracks it left against L, on the IoU alone
         if (p.low_conf > 0.0f) {
-            if (tid < TA_SLOTS) s.tfree[tid] = live && s.det[tid] < 0;
-            const int nl = ta_candidates(s, pa, d, idx, n, true);
-            ta_associate<false>(s, nl, p.iou_low, p.any_class != 0, 0.0f, 0.0f, nullptr, nullptr);
+            if (tid < TK_SLOTS) s.tfree[tid] = live && s.det[tid] < 0;
+            const int nl = tk_candidates<true>(s, pa, d, idx, n, true);
+            tk_associate<false>(s, nl, p.iou_low, p.any_class != 0, 0.0f, 0.0f, nullptr, nullptr);
         }
         // update
         bool died = false;
@@ -369,21 +197,21 @@ __global__ __launch_bounds__(TA_THREADS) void track_app_kernel(const mhip_track_
                 int qq;
                 const int r = ta_row_of(pa, idx, i, qq);
                 if (r >= 0) { s.take[tid] = r; s.blend[tid] = pa.smooth && s.ee[tid] > 0; }
-                o[i] = ta_out_t{s.id[tid], s.hits[tid]}; // (behind the {-1, 0} of the loop above: the scans' barriers lie between)
+                o[i] = tk_out_t{s.id[tid], s.hits[tid]}; // (behind the {-1, 0} of the loop above: the scans' barriers lie between)
             } else {
                 s.x[tid] = s.px[tid]; s.y[tid] = s.py[tid];
                 s.miss[tid] += 1;
-                if (s.miss[tid] > p.max_miss) { s.hits[tid] = 0; died = true; s.take[tid] = TA_CLEAR; }
+                if (s.miss[tid] > p.max_miss) { s.hits[tid] = 0; died = true; s.take[tid] = TK_CLEAR; }
             }
         }
         int deaths, nfree, nborn;
-        ta_scan(died, s.wsum, deaths);
+        tk_scan(died, s.wsum, deaths);
         // births: free slot r and unmatched H member r meet
-        const bool is_free = tid < TA_SLOTS && s.hits[tid] == 0;
-        const int r = ta_scan(is_free, s.wsum, nfree);
+        const bool is_free = tid < TK_SLOTS && s.hits[tid] == 0;
+        const int r = tk_scan(is_free, s.wsum, nfree);
         if (is_free) s.freelist[r] = (short)tid;
-        const bool wants = tid < TA_CAND && s.hfree[tid];
-        const int bi = ta_scan(wants, s.wsum, nborn); // (its barriers publish the free list, and the actions of the update)
+        const bool wants = tid < TK_CAND && s.hfree[tid];
+        const int bi = tk_scan(wants, s.wsum, nborn); // (its barriers publish the free list, and the actions of the update)
         const int fits = nborn < nfree ? nborn : nfree;
         if (wants && bi < fits) {
             const int slot = s.freelist[bi], i = s.hidx[tid];
@@ -396,8 +224,8 @@ __global__ __launch_bounds__(TA_THREADS) void track_app_kernel(const mhip_track_
             s.icls[slot] = e.cls; s.iscore[slot] = e.score;
             int qq;
             const int row = ta_row_of(pa, idx, i, qq);
-            if (row >= 0) s.take[slot] = row; // the detection's, never the previous occupant's: a slot freed in this step stays at TA_CLEAR
-            o[i] = ta_out_t{id, 1};           // otherwise, one free for longer holds zeros already
+            if (row >= 0) s.take[slot] = row; // the detection's, never the previous occupant's: a slot freed in this step stays at TK_CLEAR
+            o[i] = tk_out_t{id, 1};           // otherwise, one free for longer holds zeros already
         }
         __syncthreads();
         if (tid == 0) {
@@ -407,17 +235,17 @@ __global__ __launch_bounds__(TA_THREADS) void track_app_kernel(const mhip_track_
             s.counters[3] += nborn - fits;
         }
         // embeddings: a wavefront per slot row
-        for (int slot = tid >> 6; slot < TA_SLOTS; slot += TA_WAVES) {
+        for (int slot = tid >> 6; slot < TK_SLOTS; slot += TK_WAVES) {
             const int a = s.take[slot]; // (the same in every lane)
-            if (a == TA_TAKE_NONE) continue;
+            if (a == TK_TAKE_NONE) continue;
             const int ee = ta_row_update(plane + (size_t)slot * pa.cp, s.ee[slot], a >= 0 ? pa.q + (size_t)a * pa.cp : nullptr, a >= 0 ? pa.qq[a] : 0,
-                                         a == TA_CLEAR, s.blend[slot] != 0, pa.cp);
+                                         a == TK_CLEAR, s.blend[slot] != 0, pa.cp);
             if ((tid & 63) == 0) s.ee[slot] = ee;
         }
         __syncthreads(); // the next step's products read the rows and ee
     }
-    if (tid < TA_SLOTS) {
-        ta_state_t v;
+    if (tid < TK_SLOTS) {
+        tk_state_t v;
         v.id = s.id[tid]; v.cls = s.cls[tid]; v.hits = s.hits[tid]; v.miss = s.miss[tid];
         v.x = s.x[tid]; v.y = s.y[tid]; v.w = s.w[tid]; v.h = s.h[tid]; v.vx = s.vx[tid]; v.vy = s.vy[tid];
         v.ident.cls = s.icls[tid]; v.ident.score = s.iscore[tid];
@@ -430,25 +258,10 @@ __global__ __launch_bounds__(TA_THREADS) void track_app_kernel(const mhip_track_
 
 // grid: rows, one wavefront each: gallery.hip's quantise launch without its qinv
 __global__ __launch_bounds__(64) void ta_quantise_kernel(const int *vec, const int c, const int cp, int8_t *q, int *qq_out) {
-    const int n = blockIdx.x, lane = threadIdx.x;
-    int8_t *out = q + (size_t)n * cp;
+    const int n = blockIdx.x;
     const int *v = vec + (size_t)n * c;
-    unsigned m = 0;
-    for (int k = lane; k < c; k += 64) m = max(m, ta_abs(v[k]));
-    for (int s = 32; s > 0; s >>= 1) m = max(m, (unsigned)__shfl_xor(m, s, 64));
-    int qq = 0;
-    for (int k = lane; k < cp; k += 64) {
-        int o = 0;
-        if (k < c && m) {
-            const int x = v[k];
-            const int mag = (int)(((unsigned long long)ta_abs(x) * 127u + (m >> 1)) / m);
-            o = x < 0 ? -mag : mag;
-        }
-        out[k] = (int8_t)o;
-        qq += o * o;
-    }
-    for (int s = 32; s > 0; s >>= 1) qq += __shfl_xor(qq, s, 64);
-    if (lane == 0) qq_out[n] = qq;
+    const int qq = quantise_row(q + (size_t)n * cp, c, cp, [v](const int k) { return v[k]; });
+    if (threadIdx.x == 0) qq_out[n] = qq;
 }
 
 __global__ __launch_bounds__(256) void ta_index_fill_kernel(int *idx, const size_t n) {
@@ -465,26 +278,26 @@ __global__ __launch_bounds__(256) void ta_index_scatter_kernel(const roi_t *rois
 }
 
 // the test hook: one workgroup runs ta_matrix as the tracking kernel does, every candidate j using row j
-__global__ __launch_bounds__(TA_THREADS) void ta_matrix_hook_kernel(const int8_t *plane, const int *plane_ee, const int8_t *q, const int *qq, const int nt,
+__global__ __launch_bounds__(TK_THREADS) void ta_matrix_hook_kernel(const int8_t *plane, const int *plane_ee, const int8_t *q, const int *qq, const int nt,
                                                                     const int nc, const int cp, float *cosm, float *out, int *bad) {
-    __shared__ int ee[TA_SLOTS], crow[TA_CAND], cqq[TA_CAND];
+    __shared__ int ee[TK_SLOTS], crow[TK_CAND], cqq[TK_CAND];
     const int tid = threadIdx.x;
-    if (tid < TA_SLOTS) {
+    if (tid < TK_SLOTS) {
         ee[tid] = plane_ee[tid];
         const int v = tid < nc ? qq[tid] : 0;
         crow[tid] = v > 0 ? tid : -1;
         cqq[tid] = v > 0 ? v : 0;
     }
     __syncthreads();
-    float *sm = cosm, *cm = cosm + TA_SLOTS * TA_CAND;
+    float *sm = cosm, *cm = cosm + TK_SLOTS * TK_CAND;
     ta_matrix(plane, ee, q, crow, cqq, nc, cp, sm, cm);
     __syncthreads();
     int differs = 0;
-    for (int i = tid; i < nt * nc; i += TA_THREADS) {
+    for (int i = tid; i < nt * nc; i += TK_THREADS) {
         const int t = i / nc, c = i % nc;
-        const float v = sm[(size_t)t * TA_CAND + c];
+        const float v = sm[(size_t)t * TK_CAND + c];
         out[i] = v;
-        differs |= __float_as_uint(v) != __float_as_uint(cm[(size_t)c * TA_SLOTS + t]);
+        differs |= __float_as_uint(v) != __float_as_uint(cm[(size_t)c * TK_SLOTS + t]);
     }
     if (differs) *bad = 1;
 }
@@ -493,11 +306,8 @@ __global__ __launch_bounds__(TA_THREADS) void ta_matrix_hook_kernel(const int8_t
 static bool ta_rows_ok(const int c, const int cp) { return c >= 1 && c <= MHIP_TRACK_APP_MAX_C && cp == ((c + 63) & ~63); }
 
 extern "C" int mhip_track_app(const mhip_track_app_t *pa) {
-    if (!pa) return -1;
+    if (!pa || !tk_args_ok(&pa->t) || !pa->plane || !pa->plane_ee) return -1;
     const mhip_track_t *p = &pa->t;
-    if (!p->dets || !p->counts || !p->out || !p->states || !p->hdr || !pa->plane || !pa->plane_ee) return -1;
-    if (p->streams < 1 || p->streams > 65535 || p->steps < 1 || p->max_det < 1 || p->max_det > 1000) return -1;
-    if (!(p->min_conf > 0.0f) || !(p->low_conf >= 0.0f) || !(p->iou > 0.0f) || !(p->iou_low > 0.0f) || p->max_miss < 1 || p->cls_count < 0) return -1;
     if (!ta_rows_ok(pa->c, pa->cp) || pa->n_vec < 0) return -1;
     if (pa->n_vec > 0 && (!pa->vec || !pa->q || !pa->qq || !pa->emb_index || !pa->cosm)) return -1;
     if (!(pa->app_thresh > 0.0f) || !(pa->app_thresh <= 1.0f) || !(pa->app_min_iou > 0.0f) || !(pa->app_min_iou <= 1.0f)) return -1;
@@ -505,7 +315,7 @@ extern "C" int mhip_track_app(const mhip_track_app_t *pa) {
     if (pa->n_vec > 0) hipLaunchKernelGGL(ta_quantise_kernel, dim3((unsigned)pa->n_vec), dim3(64), 0, st, pa->vec, pa->c, pa->cp, pa->q, pa->qq);
     for (int b0 = 0; b0 < p->streams; b0 += MHIP_TRACK_APP_CHUNK) { // stream order keeps one chunk's scratch from the next
         const int nb = p->streams - b0 < MHIP_TRACK_APP_CHUNK ? p->streams - b0 : MHIP_TRACK_APP_CHUNK;
-        hipLaunchKernelGGL(track_app_kernel, dim3((unsigned)nb), dim3(TA_THREADS), 0, st, *pa, b0);
+        hipLaunchKernelGGL(track_app_kernel, dim3((unsigned)nb), dim3(TK_THREADS), 0, st, *pa, b0);
     }
     return mhip_check(hipGetLastError(), "track with appearance");
 }
@@ -524,9 +334,9 @@ extern "C" int mhip_track_app_index(const void *rois, const int *n_out, int slot
 extern "C" int mhip_track_app_matrix(const int8_t *plane, const int *plane_ee, const int *vec, int nt, int nc, int c, int cp, int8_t *q, int *qq,
                                      float *cosm, float *out, int *bad) {
     if (!plane || !plane_ee || !vec || !q || !qq || !cosm || !out || !bad) return -1;
-    if (nt < 1 || nt > TA_SLOTS || nc < 1 || nc > TA_CAND || !ta_rows_ok(c, cp)) return -1;
+    if (nt < 1 || nt > TK_SLOTS || nc < 1 || nc > TK_CAND || !ta_rows_ok(c, cp)) return -1;
     hipStream_t st = mhip_stream_native();
     hipLaunchKernelGGL(ta_quantise_kernel, dim3((unsigned)nc), dim3(64), 0, st, vec, c, cp, q, qq);
-    hipLaunchKernelGGL(ta_matrix_hook_kernel, dim3(1), dim3(TA_THREADS), 0, st, plane, plane_ee, (const int8_t *)q, (const int *)qq, nt, nc, cp, cosm, out, bad);
+    hipLaunchKernelGGL(ta_matrix_hook_kernel, dim3(1), dim3(TK_THREADS), 0, st, plane, plane_ee, (const int8_t *)q, (const int *)qq, nt, nc, cp, cosm, out, bad);
     return mhip_check(hipGetLastError(), "track cosine matrix");
 }

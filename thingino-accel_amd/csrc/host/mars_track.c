@@ -241,26 +241,29 @@ mars_error_t mars_hip_tracker_read_embeddings(mars_hip_tracker_t *t, int stream,
     return rc;
 }
 
-mars_error_t mars_yolo_track_lists_app(mars_hip_tracker_t *t, const mars_det_t *dets, const int *counts, const mars_cls_t *idents, const int *vectors,
-                                       int n_vectors, const int *emb_index, int frames, int max_det, const mars_hip_track_opts_t *opts,
-                                       const mars_hip_track_app_opts_t *app, mars_track_t *out) {
+/* Both list forms: the checks in the order the error codes are pinned to, one scratch block, the uploads, the launch, the fetch.  app_form:
+ * mars_yolo_track_lists_app, which needs a tracker with a plane and brings `app` and the vectors; the plain form passes none of them */
+static mars_error_t track_lists(mars_hip_tracker_t *t, const mars_det_t *dets, const int *counts, const mars_cls_t *idents, const int *vectors,
+                                int n_vectors, const int *emb_index, int frames, int max_det, const mars_hip_track_opts_t *opts, int app_form,
+                                const mars_hip_track_app_opts_t *app, mars_track_t *out) {
     mhip_track_app_t a;
     memset(&a, 0, sizeof(a));
     mars_error_t e = track_opts(opts, &a.t);
     if (e != MARS_OK) return e;
-    if ((e = track_app_opts(app, &a)) != MARS_OK) return e;
+    if (app_form && (e = track_app_opts(app, &a)) != MARS_OK) return e;
     if (!t || !dets || !counts || !out || frames <= 0 || max_det <= 0) return MARS_ERR_INVALID_FILE;
     if (n_vectors < 0 || (n_vectors > 0 && (!vectors || !emb_index))) return MARS_ERR_INVALID_FILE;
     if ((opts->flags & MARS_TRACK_CARRY_IDENTITY) && !idents) return MARS_ERR_INVALID_FILE;
     if (max_det > MARS_YOLO_MAX_DET || n_vectors > MHIP_MATCH_MAX_ROWS) return MARS_ERR_INVALID_TENSOR;
     if ((e = track_map(&a.t, t, frames)) != MARS_OK) return e;
-    if (!t->plane) return MARS_ERR_INVALID_TENSOR; /* a tracker of mars_hip_tracker_create */
-    if (!t->states || !t->hdr || !t->plane_ee || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    track_app_plane(&a, t);
+    if (app_form && !t->plane) return MARS_ERR_INVALID_TENSOR; /* a tracker of mars_hip_tracker_create */
+    if (!t->states || !t->hdr || (app_form && !t->plane_ee) || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
+    if (app_form) track_app_plane(&a, t);
     if (n_vectors > 0 && (e = track_app_scratch(t, &a)) != MARS_OK) return e;
     const size_t n = (size_t)frames * max_det, nv = (size_t)n_vectors;
     const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
-    /* one scratch block: [dets][counts][tracks][identities, where they are carried][vectors][their int8 rows][their qq][the row indices] */
+    /* one scratch block: [dets][counts][tracks][identities, where they are carried], and where vectors come
+     * [vectors][their int8 rows][their qq][the row indices] */
     const size_t sz[8] = {n * sizeof(mars_det_t), (size_t)frames * sizeof(int), n * sizeof(mars_track_t), carry ? n * sizeof(mars_cls_t) : 0,
                           nv * t->channels * sizeof(int), nv * t->cp, nv * sizeof(int), nv ? n * sizeof(int) : 0};
     size_t off[8];
@@ -283,11 +286,17 @@ mars_error_t mars_yolo_track_lists_app(mars_hip_tracker_t *t, const mars_det_t *
     if (!rc) rc = mhip_h2d_async(d, dets, sz[0]) || mhip_h2d_async(d + off[1], counts, sz[1]);
     if (!rc && carry) rc = mhip_h2d_async(d + off[3], idents, sz[3]);
     if (!rc && nv) rc = mhip_h2d_async(d + off[4], vectors, sz[4]) || mhip_h2d_async(d + off[7], emb_index, sz[7]);
-    if (!rc) rc = mhip_track_app(&a);
+    if (!rc) rc = app_form ? mhip_track_app(&a) : track_launch(t, &a.t);
     if (!rc) rc = mhip_d2h_async(out, a.t.out, sz[2]);
     if (mhip_sync()) rc = -1;
     mhip_free(d);
     return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
+}
+
+mars_error_t mars_yolo_track_lists_app(mars_hip_tracker_t *t, const mars_det_t *dets, const int *counts, const mars_cls_t *idents, const int *vectors,
+                                       int n_vectors, const int *emb_index, int frames, int max_det, const mars_hip_track_opts_t *opts,
+                                       const mars_hip_track_app_opts_t *app, mars_track_t *out) {
+    return track_lists(t, dets, counts, idents, vectors, n_vectors, emb_index, frames, max_det, opts, 1, app, out);
 }
 
 mars_error_t mars_yolo_track_cosine_matrix(const signed char *track_q, const int *track_ee, const int *vectors, int nt, int nc, int c, float *out) {
@@ -325,36 +334,24 @@ mars_error_t mars_yolo_track_cosine_matrix(const signed char *track_q, const int
 
 mars_error_t mars_yolo_track_lists(mars_hip_tracker_t *t, const mars_det_t *dets, const int *counts, const mars_cls_t *idents, int frames,
                                    int max_det, const mars_hip_track_opts_t *opts, mars_track_t *out) {
-    mhip_track_t p;
-    memset(&p, 0, sizeof(p));
-    mars_error_t e = track_opts(opts, &p);
-    if (e != MARS_OK) return e;
-    if (!t || !dets || !counts || !out || frames <= 0 || max_det <= 0) return MARS_ERR_INVALID_FILE;
-    if ((opts->flags & MARS_TRACK_CARRY_IDENTITY) && !idents) return MARS_ERR_INVALID_FILE;
-    if (max_det > MARS_YOLO_MAX_DET) return MARS_ERR_INVALID_TENSOR;
-    if ((e = track_map(&p, t, frames)) != MARS_OK) return e;
-    if (!t->states || !t->hdr || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    const size_t n = (size_t)frames * max_det;
+    return track_lists(t, dets, counts, idents, NULL, 0, NULL, frames, max_det, opts, 0, NULL, out);
+}
+
+/* The detector's side of a device call, the same with and without a second model: its lists in HBM, the identities where they are carried,
+ * the frame -> stream map, room for the results, and the mhip_track_t part of the launch record filled */
+static mars_error_t track_from_detector(mars_model_ext_t *det, const mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts, mhip_track_t *p) {
+    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
     const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
-    /* one scratch block: [dets][counts][tracks][identities, where they are carried] */
-    const size_t sz[4] = {n * sizeof(mars_det_t), (size_t)frames * sizeof(int), n * sizeof(mars_track_t), carry ? n * sizeof(mars_cls_t) : 0};
-    size_t off[4];
-    uint8_t *d = (uint8_t *)mhip_malloc(mars_block_layout(sz, 4, off));
-    if (!d) return MARS_ERR_ALLOC_FAILED;
-    p.max_det = max_det;
-    p.dets = d;
-    p.counts = (const int *)(d + off[1]);
-    p.out = d + off[2];
-    p.idents = carry ? d + off[3] : NULL;
-    /* on the main stream: behind whatever the auxiliary stream still does to this tracker's tables, hence the wait first */
-    int rc = mhip_sync();
-    if (!rc) rc = mhip_h2d_async(d, dets, sz[0]) || mhip_h2d_async(d + off[1], counts, sz[1]);
-    if (!rc && carry) rc = mhip_h2d_async(d + off[3], idents, sz[3]);
-    if (!rc) rc = track_launch(t, &p);
-    if (!rc) rc = mhip_d2h_async(out, p.out, sz[2]);
-    if (mhip_sync()) rc = -1;
-    mhip_free(d);
-    return rc ? MARS_ERR_LAYER_FAILED : MARS_OK;
+    if (carry && (!det->ident.dev || det->ident.frames < det->batch)) return MARS_ERR_INVALID_TENSOR;      /* no identity scatter */
+    mars_error_t e = track_map(p, t, det->batch);
+    if (e != MARS_OK) return e;
+    if ((e = mars_side_reserve(&det->track, det->batch, sizeof(mars_track_t))) != MARS_OK) return e;
+    p->max_det = MARS_YOLO_MAX_DET;
+    p->dets = det->det_dev;
+    p->counts = det->det_counts_dev;
+    p->idents = carry ? det->ident.dev : NULL;
+    p->out = det->track.dev;
+    return MARS_OK;
 }
 
 mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts) {
@@ -366,16 +363,7 @@ mars_error_t mars_hip_track_device(mars_model_t *det_model, mars_hip_tracker_t *
     mars_model_ext_t *det = (mars_model_ext_t *)det_model;
     if (!det->act_dev || !t->states || !t->hdr || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     if (det->pipe) return MARS_ERR_INVALID_TENSOR;
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
-    const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
-    if (carry && (!det->ident.dev || det->ident.frames < det->batch)) return MARS_ERR_INVALID_TENSOR;      /* no identity scatter */
-    if ((e = track_map(&p, t, det->batch)) != MARS_OK) return e;
-    if ((e = mars_side_reserve(&det->track, det->batch, sizeof(mars_track_t))) != MARS_OK) return e;
-    p.max_det = MARS_YOLO_MAX_DET;
-    p.dets = det->det_dev;
-    p.counts = det->det_counts_dev;
-    p.idents = carry ? det->ident.dev : NULL;
-    p.out = det->track.dev;
+    if ((e = track_from_detector(det, t, opts, &p)) != MARS_OK) return e;
     /* The auxiliary stream, as the label scatter: it carries every detection tail and every scatter, so this comes behind the tail that
      * wrote the lists and the scatter that wrote the identities, and ahead of det_model's next detect call.  Nothing on the main stream
      * reads or writes what the kernel touches, so nothing there waits for it */
@@ -415,11 +403,7 @@ mars_error_t mars_hip_track_app_device(mars_model_t *det_model, mars_model_t *cl
     if (!m->roi_dev || m->roi_slots <= 0 || m->roi_from != det) return MARS_ERR_INVALID_TENSOR;             /* no crop call out of det_model */
     if (!m->cls.dev || m->cls.frames <= 0 || m->cls.frames < m->roi_slots) return MARS_ERR_INVALID_TENSOR;  /* no classify results */
     if (m->cls_c != t->channels) return MARS_ERR_INVALID_TENSOR;
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
-    const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
-    if (carry && (!det->ident.dev || det->ident.frames < det->batch)) return MARS_ERR_INVALID_TENSOR;      /* no identity scatter */
-    if ((e = track_map(&a.t, t, det->batch)) != MARS_OK) return e;
-    if ((e = mars_side_reserve(&det->track, det->batch, sizeof(mars_track_t))) != MARS_OK) return e;
+    if ((e = track_from_detector(det, t, opts, &a.t)) != MARS_OK) return e;
     const size_t nv = (size_t)m->roi_slots;
     const size_t sz[3] = {nv * t->cp, nv * sizeof(int), (size_t)det->batch * MARS_YOLO_MAX_DET * sizeof(int)};
     size_t off[3];
@@ -430,11 +414,6 @@ mars_error_t mars_hip_track_app_device(mars_model_t *det_model, mars_model_t *cl
     if (!m->ev_label_done) m->ev_label_done = mhip_event_create_sync();
     if (!m->ev_graph_done || !m->ev_label_done) return MARS_ERR_ALLOC_FAILED;
     uint8_t *blk = (uint8_t *)det->track_app.dev;
-    a.t.max_det = MARS_YOLO_MAX_DET;
-    a.t.dets = det->det_dev;
-    a.t.counts = det->det_counts_dev;
-    a.t.idents = carry ? det->ident.dev : NULL;
-    a.t.out = det->track.dev;
     a.vec = (const int *)((uint8_t *)m->cls.dev + m->cls_sums_off);
     a.n_vec = m->roi_slots; /* every slot's row is quantised; the index below names those below `kept` only */
     a.q = (int8_t *)blk; a.qq = (int *)(blk + off[1]);

@@ -525,9 +525,10 @@ typedef struct {
 int mhip_track(const mhip_track_t *p); /* one launch */
 
 /* ---- appearance in tracking (track_app.hip): the same walk on a tracker that holds an int8 embedding per slot, by the exact rule of
- * include/mars_hip.h ("Appearance in tracking").  A kernel of its own: mhip_track above keeps its instructions.  Per stream and step the
- * cosines of the 256 slots against the high set's candidates are computed on the int8 matrix unit into `cosm`, twice (slot-major and
- * candidate-major: the two halves of the workgroup walk it along different axes), and pass 1 reads them.  Every pointer is device memory. */
+ * include/mars_hip.h ("Appearance in tracking").  Both kernels take records, table, scans, compaction and rounds from hip/track_core.hpp;
+ * mhip_track's kernel has none of what the plane adds.  Per stream and step the cosines of the 256 slots against the high set's candidates
+ * are computed on the int8 matrix unit into `cosm`, twice (slot-major and candidate-major: the two halves of the workgroup walk it along
+ * different axes), and pass 1 reads them.  Every pointer is device memory. */
 #define MHIP_TRACK_APP_MAX_C 4096
 #define MHIP_TRACK_APP_COS_FLOATS (2 * MHIP_TRACK_SLOTS * MHIP_TRACK_CAND) /* per stream of a launch: 512 KB */
 #define MHIP_TRACK_APP_CHUNK 512    /* streams per launch: the launcher walks the streams in chunks over ONE block of at most 256 MB */
