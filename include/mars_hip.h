@@ -846,7 +846,7 @@ int mars_yolo_masks(const int8_t *coefs, int n, int nm, const int8_t *proto, int
  *             the int64 terms stay exact below it); a set flag bit; everything mars_hip_detect_seg_device refuses.  MARS_ERR_INVALID_TENSOR.
  * Consequence.  Identity geometry and out = PW x PH: N / D = X exactly, w1 = 0, S = 65536 * dot, and every bit is the prototype mask's bit.
  * Not covered: down-scaled masks (area averaging is another feature); masks inside mars_hip_pipe_*; masks in the crop, tile-merge or track
- *   stages; run-length or box-relative output; float32 tensors; nm > 64. */
+ *   stages; run-length or box-relative output; float32 tensors; nm > 64.  ("Redaction" below consumes these masks on the device.) */
 #define MARS_MASK_NATIVE_MAX 8192
 /* Zero-initialise; there are no flags yet. */
 typedef struct { int out_w, out_h; unsigned flags; } mars_hip_mask_native_opts_t;
@@ -1256,6 +1256,90 @@ mars_error_t mars_yolo_tile_frames(const unsigned char *frames, int n_frames, co
  * origins and stats may be NULL. */
 mars_error_t mars_yolo_merge_tiles(const mars_det_t *dets, const int *counts, int n_frames, int max_det, const mars_hip_tile_opts_t *opts,
                                    int tw, int th, mars_det_t *out, int *out_counts, mars_tile_src_t *origins, mars_tile_stats_t *stats);
+
+/* --------------------------------------------------------------- Redaction */
+/* Everything above reads camera frames; this writes them.  The first thing a camera deployment does with a person, face or plate detector is
+ * hide what it found before a frame is encoded, stored or streamed.  The frames, the detections in frame pixels (mars_hip_detect_*_device
+ * with src_w / src_h set), optionally the per-detection masks on the frame's own grid ("Instance masks in frame pixels") and the identity
+ * hung on each detection ("Gallery match") are all in HBM after a batch; the calls below mosaic or fill the detected regions there, one
+ * sparse pass over the pixels that change.  All integers except the rectangle rule, which is float32 and stated under "ROI crops".
+ *
+ * Frames.     F frames of W x H, densely packed (no row pitch): RGB [H][W][3] uint8, or NV12 as in "NV12 camera frames" (W, H even).
+ *             src_format and src_flags mean what they mean in mars_hip_roi_opts_t.  Of the NV12 flags only MARS_NV12_VU matters, and only
+ *             for the fill colour; MARS_NV12_FULL_RANGE is accepted and ignored: nothing is converted.
+ * Regions.    Every selected detection gives one region.  Its rectangle R = (x0, y0, x1, y1) is "Box -> source rectangle" of "ROI crops"
+ *             with the options' expand (0 means 1.0).  The region is SKIPPED when a float field is not finite, w <= 0, h <= 0, cw < 1 or
+ *             ch < 1: there is no min_size here.  A region without a mask is all of R.  A region with a mask is the pixels of R whose bit
+ *             is set in that detection's mask words: pixel x is bit x & 31 of word x >> 5 of its row, pitch = (W + 31) / 32 words, as in
+ *             "Instance masks in frame pixels".  Bits outside R are ignored.
+ * Union.      U(f) is the union of the regions of frame f.  A pixel is redacted iff it is in U; overlapping regions make no difference
+ *             beyond that.
+ * Cells.      cell = B in {2, 4, 8, 16, 32, 64}; 0 means 16.  Cell (cx, cy) is the pixels [cx * B, min(W, (cx + 1) * B)) x [cy * B,
+ *             min(H, (cy + 1) * B)), anchored at the frame's origin, not at the box; n is its pixel count (edge cells are clipped).
+ * Mosaic (mode MARS_REDACT_MOSAIC = 0, the default), RGB.  Per channel: S = the sum of the ORIGINAL bytes over the whole cell, whether or not
+ *             those pixels are redacted; v = (S + n / 2) / n, floor -- the rounding of "Area averaging".  Every redacted pixel of the cell
+ *             becomes v; every other byte keeps its value.
+ * Mosaic, NV12.  The luma plane follows the RGB rule with one channel.  Chroma sample (i, j) covers the pixels (2i .. 2i + 1, 2j .. 2j + 1)
+ *             and is redacted iff any of those four pixels is in U.  Its value is the rounded mean, by the same formula, of the original
+ *             samples of its cell: cell (cx, cy) holds the chroma samples [cx * B / 2, ...) x [cy * B / 2, ...), clipped to the plane, n
+ *             their count.  U and V are averaged separately.
+ * Fill (mode MARS_REDACT_FILL = 1).  RGB: redacted pixels become fill[0 .. 2] = R, G, B.  NV12: redacted luma becomes fill[0], redacted
+ *             chroma samples the pair U = fill[1], V = fill[2], stored V, U under MARS_NV12_VU.
+ * Output.     In place (dst NULL or == the frames) or into a second buffer of the same size, of which every byte is written (unredacted
+ *             bytes are copied).  A dst that overlaps the source without being equal to it is refused.  Either way the result is a function
+ *             of the original frames alone.
+ * Selection (device form).  Every listed detection is visited and every selected one counts; there is no cap below MARS_YOLO_MAX_DET.
+ *             Selected: conf >= min_conf (0: all); cls_count == 0 or cls_first <= cls < cls_first + cls_count, as in "ROI crops"; under
+ *             MARS_REDACT_SPARE_IDENTIFIED not the detections whose identity entry (mars_hip_identify_detections_device) has cls >= 0 and
+ *             score >= ident_min -- "hide everyone who is not enrolled"; the flag needs identity results of this batch on the model.
+ *             Under MARS_REDACT_USE_MASKS a selected detection that has a slot among the native mask results -- the mars_mask_t.det entries
+ *             of the last mars_hip_detect_seg_native_device, whose grid must be W x H -- uses its mask; one without a slot falls back to
+ *             its rectangle: the privacy-safe side is to hide more.
+ * Statistics. Per frame {regions, masked, skipped, pixels}: the regions formed, how many of them used a mask, the selected detections
+ *             the rectangle rule skipped, |U|.
+ * Not covered: Gaussian blur; mask dilation; "only the identified"; selection by track id; oriented or keypoint-shaped regions; the merged
+ *   lists of "Tiled inference"; the mars_hip_pipe_* path; frames with a row pitch. */
+#define MARS_REDACT_MOSAIC 0
+#define MARS_REDACT_FILL 1
+#define MARS_REDACT_USE_MASKS 1u
+#define MARS_REDACT_SPARE_IDENTIFIED 2u
+/* Zero-initialise; zero means default in every field but the frame size. */
+typedef struct {
+    int src_w, src_h, src_format; unsigned src_flags; /* frames: MARS_HIP_CAMERA_RGB / _NV12, MARS_NV12_* (NV12 only) */
+    int mode, cell; unsigned char fill[3];
+    float expand, min_conf, ident_min;
+    int cls_first, cls_count;
+    unsigned flags;                                    /* MARS_REDACT_USE_MASKS | MARS_REDACT_SPARE_IDENTIFIED (the device form) */
+} mars_hip_redact_opts_t;
+typedef struct { int regions, masked, skipped, pixels; } mars_redact_stats_t; /* 16 bytes */
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: no options or a NULL pointer where one is needed, a
+ * non-positive size, an unknown format, mode or flag bit, odd NV12 sizes, a cell outside the set, a negative or non-finite expand, min_conf
+ * or ident_min, ident_min > 1, a negative cls_count, a dst that overlaps the source in part.  MARS_ERR_INVALID_TENSOR: W or H above 8192, no
+ * detections in HBM, a model with an open pipe, MARS_REDACT_USE_MASKS without native mask results of this batch or with a mask grid that is
+ * not W x H, MARS_REDACT_SPARE_IDENTIFIED without identity results of this batch. */
+/* Host pointers in and out, the same kernels on the GPU; waits.  `frames` = n_frames frames of opts->src_w x src_h; box i lies in frame
+ * frame_of_box[i] (a box whose index names no frame is left out).  Every box is taken: only the rectangle rule applies, opts->flags are not
+ * looked at beyond the check.  mask_of_box = NULL, or [n_boxes]: an index into mask_words[.][H][(W + 31) / 32], or -1 for the rectangle alone.
+ * n_boxes may be 0 (0 .. 65535, n_frames 1 .. 65535).  out = the redacted frames; out == frames runs the in-place form.  stats = [n_frames],
+ * or NULL. */
+mars_error_t mars_yolo_redact_frames(const unsigned char *frames, int n_frames, const mars_det_t *boxes, const int *frame_of_box, int n_boxes,
+                                     const uint32_t *mask_words, const int *mask_of_box, const mars_hip_redact_opts_t *opts, unsigned char *out,
+                                     mars_redact_stats_t *stats);
+/* The device form.  Reads the detections the last mars_hip_detect_*_device of det_model left in HBM (in frame pixels) and redacts det_model's
+ * batch of frames at frames_dev into dst_dev (NULL or == frames_dev: in place).  Enqueues only, on the auxiliary stream: behind the detection
+ * tail, the native masks and the identity scatter, which that stream carries.  Ordering against the main stream, both ways: the redaction
+ * first waits for an event recorded on the main stream at the call, so crops the library enqueued EARLIER from the same frames
+ * (mars_hip_crop_*_device, mars_hip_preprocess*_device) read the original pixels; and it records an event the main stream waits for, so
+ * library work enqueued LATER, and every *_results call, sees the redacted frames.  Work of the caller's own on other streams is the
+ * caller's to order (mars_hip_sync). */
+mars_error_t mars_hip_redact_device(mars_model_t *det_model, void *frames_dev, void *dst_dev, const mars_hip_redact_opts_t *opts);
+/* Waits.  stats = [batch] of the last mars_hip_redact_device call (may be NULL: only waits).  MARS_ERR_INVALID_TENSOR before any such call. */
+mars_error_t mars_hip_redact_results(mars_model_t *det_model, mars_redact_stats_t *stats);
+/* The same with the frames in host memory, in place: uploads them, redacts, downloads them, waits. */
+mars_error_t mars_hip_redact(mars_model_t *det_model, unsigned char *frames, const mars_hip_redact_opts_t *opts, mars_redact_stats_t *stats);
+/* Device time (ms) of the last mars_hip_redact_device call (selection + pixels), from events on the auxiliary stream; waits for it.  < 0: not
+ * available. */
+float mars_hip_redact_ms(mars_model_t *det_model);
 
 #ifdef __cplusplus
 }

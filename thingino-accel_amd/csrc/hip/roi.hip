@@ -35,23 +35,7 @@
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-// box -> source rectangle q = {x0, y0, x1, y1}; false = skipped (the rectangle is then all zeros).  float32, every operation rounded on its own
-// (-ffp-contract=off).  The two clamps in front of the conversions keep far-away boxes inside the int range and change no decision:
-// x0f > W + 1 means x0 > x1 anyway
-__device__ __forceinline__ bool roi_rect(const det_t d, const float expand, const int min_size, const int W, const int H, int q[4]) {
-    q[0] = q[1] = q[2] = q[3] = 0;
-    if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf))) return false;
-    if (!(d.w > 0.0f) || !(d.h > 0.0f)) return false;
-    const float hw = (d.w * expand) * 0.5f, hh = (d.h * expand) * 0.5f;
-    float x0f = fmaxf(d.x - hw, 0.0f), x1f = fminf(d.x + hw, (float)W);
-    float y0f = fmaxf(d.y - hh, 0.0f), y1f = fminf(d.y + hh, (float)H);
-    x0f = fminf(x0f, (float)(W + 1)); x1f = fmaxf(x1f, -1.0f);
-    y0f = fminf(y0f, (float)(H + 1)); y1f = fmaxf(y1f, -1.0f);
-    const int ax0 = (int)floorf(x0f), ax1 = (int)ceilf(x1f), ay0 = (int)floorf(y0f), ay1 = (int)ceilf(y1f);
-    if (ax1 - ax0 < min_size || ay1 - ay0 < min_size) return false;
-    q[0] = ax0; q[1] = ay0; q[2] = ax1; q[3] = ay1;
-    return true;
-}
+// (roi_rect, the box -> source rectangle rule, lives in tail_core.hpp: redact.hip forms its regions by it too)
 
 // the resized size of a cw x ch source inside a tw x th target under MARS_ROI_KEEP_ASPECT: the longer side fills its axis, the other is rounded, >= 1
 __device__ __forceinline__ void keep_aspect_size(const int cw, const int ch, const int tw, const int th, int &nw, int &nh) {

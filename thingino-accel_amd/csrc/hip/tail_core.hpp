@@ -1,7 +1,7 @@
 // tail_core.hpp -- what the detection-tail kernels share, device-only and inlined: the mirrors of the public records, the ordered
 // block-wide rank, and the sort / class buckets / greedy suppression / compaction core of the three NMS kernels (sort_nms_kernel of
-// yolo_tail.hip, obb_sort_nms_kernel of obb.hip, tile_merge_kernel of tile.hip), the reference's upright IoU, the int8 quantisation of an
-// embedding row (gallery.hip's queries, track_app.hip's vectors and its blend) and the DFL head helpers.
+// yolo_tail.hip, obb_sort_nms_kernel of obb.hip, tile_merge_kernel of tile.hip), the reference's upright IoU, the box -> source rectangle rule of the
+// crops and the redaction (roi.hip, redact.hip), the int8 quantisation of an embedding row (gallery.hip's queries, track_app.hip's vectors and its blend) and the DFL head helpers.
 // No kernels and no launchers here.  Every helper that contains a barrier says so; all of those are called by EVERY thread of the
 // workgroup under uniform control flow (a kernel's early returns stay ahead of them).
 #pragma once
@@ -90,6 +90,26 @@ __device__ __forceinline__ float box_iou(const box_edges_t &a, const float bx, c
     uni = uni - inter;
     uni = uni + 1e-6f;
     return inter / uni;
+}
+
+// ------------------------------------------------ box -> source rectangle
+// "ROI crops" of include/mars_hip.h, shared by the crop selection (roi.hip) and the regions of "Redaction" (redact.hip).
+// box -> source rectangle q = {x0, y0, x1, y1}; false = skipped (the rectangle is then all zeros).  float32, every operation rounded on its own
+// (-ffp-contract=off).  The two clamps in front of the conversions keep far-away boxes inside the int range and change no decision:
+// x0f > W + 1 means x0 > x1 anyway
+__device__ __forceinline__ bool roi_rect(const det_t d, const float expand, const int min_size, const int W, const int H, int q[4]) {
+    q[0] = q[1] = q[2] = q[3] = 0;
+    if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.w) && isfinite(d.h) && isfinite(d.conf))) return false;
+    if (!(d.w > 0.0f) || !(d.h > 0.0f)) return false;
+    const float hw = (d.w * expand) * 0.5f, hh = (d.h * expand) * 0.5f;
+    float x0f = fmaxf(d.x - hw, 0.0f), x1f = fminf(d.x + hw, (float)W);
+    float y0f = fmaxf(d.y - hh, 0.0f), y1f = fminf(d.y + hh, (float)H);
+    x0f = fminf(x0f, (float)(W + 1)); x1f = fmaxf(x1f, -1.0f);
+    y0f = fminf(y0f, (float)(H + 1)); y1f = fmaxf(y1f, -1.0f);
+    const int ax0 = (int)floorf(x0f), ax1 = (int)ceilf(x1f), ay0 = (int)floorf(y0f), ay1 = (int)ceilf(y1f);
+    if (ax1 - ax0 < min_size || ay1 - ay0 < min_size) return false;
+    q[0] = ax0; q[1] = ay0; q[2] = ax1; q[3] = ay1;
+    return true;
 }
 
 // -------------------------------------------------------- int8 embedding rows

@@ -252,6 +252,11 @@ typedef struct mars_model_ext {
     mars_block_t tile;  /* merged lists of THIS model's detections: [frames][MARS_YOLO_MAX_DET] x mars_det_t, the same of mars_tile_src_t,
                          * [frames] x int, [frames] x mars_tile_stats_t; frames = camera frames of the last merge */
     size_t tile_off[4];
+    /* redaction (mars_redact.c) */
+    mars_block_t redact; /* of THIS model's detections: the region table [frames][MARS_YOLO_MAX_DET] x 5 int, its counts [frames] x int,
+                          * [frames] x mars_redact_stats_t */
+    size_t redact_stats_off;
+    void *ev_redact_done; /* the redaction (auxiliary stream) has written the frames: the main stream waits for it */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 

@@ -2,7 +2,7 @@
  * mars_stage.c -- what the stages behind the detection tail share on the host (mars_internal.h, "tail stages"): the result block hung on a
  * model, the per-detection side arrays hung on a detector and the scatter that fills two of them, where the plan left an int8 side tensor,
  * and the scale-keyed tables.  No launch of its own but the scatter's; the stage files (mars_seg.c, mars_pose.c, mars_obb.c, mars_tile.c,
- * mars_classify.c, mars_gallery.c, mars_track.c) and the table functions of mars_yolo.c are written on top of it.
+ * mars_redact.c, mars_classify.c, mars_gallery.c, mars_track.c) and the table functions of mars_yolo.c are written on top of it.
  */
 #include <stdint.h>
 #include <string.h>
@@ -154,7 +154,7 @@ mars_error_t mars_lut_refresh(mars_lut_cache_t *c, void *dst, int n, const float
 /* ---- everything a model holds for these stages, when its device state goes away */
 void mars_stages_release(mars_model_ext_t *m) {
     mars_roi_release(m);
-    mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->segn, &m->pose, &m->obb, &m->tile_roi, &m->tile, &m->track_app};
+    mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->segn, &m->pose, &m->obb, &m->tile_roi, &m->tile, &m->track_app, &m->redact};
     mars_det_side_t *sides[] = {&m->label, &m->ident, &m->track};
     for (size_t i = 0; i < sizeof(blocks) / sizeof(blocks[0]); i++) mars_block_release(blocks[i]);
     for (size_t i = 0; i < sizeof(sides) / sizeof(sides[0]); i++) mars_side_release(sides[i]);
@@ -163,4 +163,6 @@ void mars_stages_release(mars_model_ext_t *m) {
     m->segn_max = m->segn_oh = m->segn_ow = 0;
     memset(m->segn_key, 0, sizeof(m->segn_key)); /* (those tables lived inside the block) */
     m->pose_lut.n = m->obb_lut.n = 0; /* (those tables lived inside the blocks) */
+    if (m->ev_redact_done) mhip_event_destroy(m->ev_redact_done);
+    m->ev_redact_done = NULL;
 }

@@ -678,6 +678,35 @@ typedef struct {
 int mhip_tile_rois(const mhip_tile_t *p);  /* one launch: the ROI table of C camera frames */
 int mhip_tile_merge(const mhip_tile_t *p); /* one launch, one workgroup per camera frame */
 
+/* ---- redaction (redact.hip): detections -> per frame a table of regions {x0, y0, x1, y1, mask slot or -1} -> the frames with the union of
+ * the regions mosaicked or filled, by the exact rule of include/mars_hip.h ("Redaction").  Every pointer is device memory.  Two launches:
+ * mhip_redact_select (one workgroup per frame: the selection, the rectangle rule of "ROI crops", the table, the counts), then mhip_redact
+ * (one workgroup per 64 x 64 pixel tile and frame; it adds the frame's `pixels`). */
+#define MHIP_REDACT_MAX_DIM 8192
+typedef struct {
+    const uint8_t *frames; uint8_t *dst;        /* [n_frames] RGB [h][w][3] (fmt 0) or NV12 (fmt 1) frames; dst == frames: in place, else a second such buffer */
+    size_t frame_stride;
+    int n_frames, w, h, fmt;
+    unsigned nv12_flags;                        /* MARS_NV12_* (only VU matters: the fill colour's order) */
+    const void *dets; const int *counts;        /* frame f's list: counts[f] records of 24 bytes from record list_off[f] on (list_off == NULL: */
+    const int *list_off; int det_cap;           /* f * det_cap, and counts[f] is clamped to 0 .. det_cap) */
+    int select_all;                             /* != 0: every listed record is selected (the host-pointer form) */
+    float expand, min_conf, ident_min;          /* resolved: expand > 0 */
+    int cls_first, cls_count;
+    const void *idents;                         /* NULL, or records of 8 bytes {cls, score} index-aligned with dets: cls >= 0 and score >= ident_min spares */
+    const void *mask_recs; int mask_max;        /* NULL, or [n_frames][mask_max] records of 24 bytes whose det field names a list index: that
+                                                 * detection's mask is slot f * mask_max + j; mask_max <= 64 */
+    const int *mask_of;                         /* NULL, or a slot (or < 0: none) per record, index-aligned with dets (the host-pointer form) */
+    const uint32_t *mask_words;                 /* [slot][h][(w + 31) / 32] */
+    int mode, cell_log2;                        /* 0 mosaic, 1 fill; cell = 1 << cell_log2: 2 .. 64 */
+    unsigned char fill[3];
+    int *table;                                 /* 5 ints per record, at the place of the frame's list: the first table_n[f] of them are regions */
+    int *table_n;                               /* [n_frames] */
+    int *stats;                                 /* [n_frames][4]: regions, masked, skipped, pixels */
+} mhip_redact_t;
+int mhip_redact_select(const mhip_redact_t *p);
+int mhip_redact(const mhip_redact_t *p);
+
 #ifdef __cplusplus
 }
 #endif

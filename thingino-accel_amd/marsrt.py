@@ -219,7 +219,20 @@ class TileOpts(C.Structure):  # mars_hip_tile_opts_t: zero = default in every fi
                 ("tiles", C.c_void_p), ("flags", C.c_uint), ("merge_thresh", C.c_float), ("edge_margin", C.c_float), ("max_per_tile", C.c_int)]
 
 
+REDACT_MOSAIC, REDACT_FILL = 0, 1                                        # MARS_REDACT_*
+REDACT_USE_MASKS, REDACT_SPARE_IDENTIFIED = 1, 2
+REDACT_MAX_DIM = 8192
+REDACT_STATS_DTYPE = np.dtype([("regions", "<i4"), ("masked", "<i4"), ("skipped", "<i4"), ("pixels", "<i4")])  # mars_redact_stats_t
+
+
+class RedactOpts(C.Structure):  # mars_hip_redact_opts_t: zero = default in every field but the frame size
+    _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("src_format", C.c_int), ("src_flags", C.c_uint), ("mode", C.c_int), ("cell", C.c_int),
+                ("fill", C.c_ubyte * 3), ("expand", C.c_float), ("min_conf", C.c_float), ("ident_min", C.c_float), ("cls_first", C.c_int),
+                ("cls_count", C.c_int), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert REDACT_STATS_DTYPE.itemsize == 16 and C.sizeof(RedactOpts) == 52
 assert TILE_DTYPE.itemsize == 16 and TILE_SRC_DTYPE.itemsize == 8 and TILE_STATS_DTYPE.itemsize == 24 and C.sizeof(TileOpts) == 48
 assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
 assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
@@ -281,7 +294,8 @@ EXPORTS = {
                    "mars_yolo_align_fit", "mars_yolo_align_template_face5", "mars_yolo_crop_aligned", "mars_hip_crop_pose_device",
                    "mars_hip_crop_pose", "mars_hip_align_results",
                    "mars_tile_grid", "mars_hip_preprocess_tiles_device", "mars_hip_preprocess_tiles", "mars_hip_merge_tiles_device",
-                   "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles"],
+                   "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles",
+                   "mars_yolo_redact_frames", "mars_hip_redact_device", "mars_hip_redact_results", "mars_hip_redact", "mars_hip_redact_ms"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -454,6 +468,13 @@ def lib():
     L.mars_yolo_tile_frames.argtypes = [C.c_void_p, C.c_int, P(TileOpts), C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.mars_yolo_merge_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(TileOpts), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]
+    L.mars_yolo_redact_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, P(RedactOpts), C.c_void_p,
+                                          C.c_void_p]
+    L.mars_hip_redact_device.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(RedactOpts)]
+    L.mars_hip_redact_results.argtypes = [P(MarsModel), C.c_void_p]
+    L.mars_hip_redact.argtypes = [P(MarsModel), C.c_void_p, P(RedactOpts), C.c_void_p]
+    L.mars_hip_redact_ms.restype = C.c_float
+    L.mars_hip_redact_ms.argtypes = [P(MarsModel)]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -721,6 +742,56 @@ def merge_tiles(dets, counts, opts, tw, th):
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_merge_tiles")
     return out, oc, org, st
+
+
+def redact_opts(w, h, fmt=CAMERA_RGB, src_flags=0, mode=REDACT_MOSAIC, cell=0, fill=(0, 0, 0), expand=0.0, min_conf=0.0, ident_min=0.0,
+                classes=None, use_masks=False, spare_identified=False, flags=None):
+    """mars_hip_redact_opts_t for frames of w x h.  mode: REDACT_MOSAIC / REDACT_FILL; cell: 2 .. 64, a power of two (0: 16); fill = (R, G, B)
+    or (Y, U, V); classes = (first, count): the class window; use_masks / spare_identified: the device form's flags (flags overrides both);
+    zero means default everywhere else"""
+    o = RedactOpts(int(w), int(h), int(fmt), int(src_flags), int(mode), int(cell))
+    o.fill[:] = [int(v) for v in fill]
+    o.expand, o.min_conf, o.ident_min = float(expand), float(min_conf), float(ident_min)
+    if classes is not None:
+        o.cls_first, o.cls_count = int(classes[0]), int(classes[1])
+    o.flags = int(flags) if flags is not None else (REDACT_USE_MASKS if use_masks else 0) | (REDACT_SPARE_IDENTIFIED if spare_identified else 0)
+    return o
+
+
+def redact_frame_bytes(opts):
+    return opts.src_w * opts.src_h * 3 // (2 if opts.src_format == CAMERA_NV12 else 1)
+
+
+def redact_frames(frames, boxes, frame_of_box, opts, mask_words=None, mask_of_box=None, inplace=False):
+    """mars_yolo_redact_frames: frames (uint8, [n] frames of opts.src_w x opts.src_h, RGB or NV12) with the regions of boxes (DET_DTYPE records,
+    box i in frame frame_of_box[i]) mosaicked or filled, on the GPU -> (the redacted frames, uint8 [n][frame bytes]; REDACT_STATS_DTYPE [n]).
+    mask_words = uint32 [n_masks][h][(w + 31) / 32] and mask_of_box = [n_boxes] indices into it (-1: the rectangle alone), or both None.
+    inplace: the in-place kernels run (on a copy: the caller's array is left alone)"""
+    a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    fb = redact_frame_bytes(opts)
+    if fb <= 0 or a.size == 0 or a.size % fb:
+        raise ValueError("frames of %d x %d are %d bytes each, got %d" % (opts.src_w, opts.src_h, fb, a.size))
+    b = np.ascontiguousarray(boxes, dtype=DET_DTYPE).reshape(-1)
+    fo = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
+    if fo.size != b.size:
+        raise ValueError("one frame index per box")
+    mw = mo = None
+    if mask_of_box is not None:
+        mo = np.ascontiguousarray(mask_of_box, dtype=np.int32).reshape(-1)
+        pitch = (opts.src_w + 31) // 32
+        mw = np.ascontiguousarray(mask_words if mask_words is not None else np.zeros(0), dtype=np.uint32).reshape(-1)
+        if mo.size != b.size or mw.size % (opts.src_h * pitch) or (mo.size and int(mo.max()) >= mw.size // (opts.src_h * pitch)):
+            raise ValueError("mask_of_box: one index per box, inside mask_words [.][%d][%d]" % (opts.src_h, pitch))
+    n = a.size // fb
+    out = a.copy() if inplace else np.zeros_like(a)
+    src = out if inplace else a
+    stats = np.zeros(n, dtype=REDACT_STATS_DTYPE)
+    rc = lib().mars_yolo_redact_frames(src.ctypes.data, n, b.ctypes.data if b.size else None, fo.ctypes.data if b.size else None, b.size,
+                                       mw.ctypes.data if mw is not None and mw.size else None, mo.ctypes.data if mo is not None and mo.size else None,
+                                       C.byref(opts), out.ctypes.data, stats.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_redact_frames")
+    return out.reshape(n, fb), stats
 
 
 def cls_opts(output_index=0, tensor=0, top_k=0, scale=0.0, softmax=False):
@@ -1619,6 +1690,39 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_identity_results")
         return idents
+
+    def redact_device(self, frames_dev, opts, dst_dev=None):
+        """THIS model is the detector: its batch of frames at the device address frames_dev with the regions of the detections its last
+        detect_*_device left in HBM mosaicked or filled, in place or (dst_dev: a second device address) into another buffer; enqueues only
+        (mars_hip_redact_device)"""
+        rc = lib().mars_hip_redact_device(self.p, C.c_void_p(frames_dev), C.c_void_p(dst_dev) if dst_dev else None, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_redact_device")
+
+    def redact_results(self):
+        """-> REDACT_STATS_DTYPE [batch] of the last redact_device() (mars_hip_redact_results); waits"""
+        stats = np.zeros(self.batch, dtype=REDACT_STATS_DTYPE)
+        rc = lib().mars_hip_redact_results(self.p, stats.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_redact_results")
+        return stats
+
+    def redact(self, frames, opts):
+        """redact_device on frames in host memory (uint8, this model's batch of them): -> (the redacted frames, the statistics); the caller's
+        array is left alone (mars_hip_redact works in place on a copy); waits"""
+        a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1).copy()
+        fb = redact_frame_bytes(opts)
+        if fb <= 0 or a.size != fb * self.batch:
+            raise ValueError("%d frames of %d bytes each, got %d bytes" % (self.batch, fb, a.size))
+        stats = np.zeros(self.batch, dtype=REDACT_STATS_DTYPE)
+        rc = lib().mars_hip_redact(self.p, a.ctypes.data, C.byref(opts), stats.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_redact")
+        return a.reshape(self.batch, fb), stats
+
+    def redact_ms(self):
+        """device time (ms) of the last redact_device() (mars_hip_redact_ms); < 0: not available"""
+        return float(lib().mars_hip_redact_ms(self.p))
 
     def track_device(self, tracker, opts=None, **kw):
         """THIS model is the detector: the detections its last detect_*_device call left in HBM (and, with carry_identity, the identities
