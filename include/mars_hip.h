@@ -1341,6 +1341,92 @@ mars_error_t mars_hip_redact(mars_model_t *det_model, unsigned char *frames, con
  * available. */
 float mars_hip_redact_ms(mars_model_t *det_model);
 
+/* --------------------------------------------------------------- Motion */
+/* The first question a camera deployment asks of a frame: did anything move, and where?  The frames are in HBM for the front-end, the crops
+ * and the redaction; the calls below read each of them once more (the Y plane of an NV12 frame, every byte of an RGB frame) and keep a
+ * background per camera stream on the device, like the trackers keep their tables.  They tell a parked car from a moving one, idle streams
+ * and tiles from busy ones, and count motion inside intrusion zones.  All integers except the rectangle rule, which is float32 and stated
+ * under "ROI crops".
+ *
+ * Detector.   mars_hip_motion_t is made for S streams (1 .. 65535) of W x H frames (each at most 8192, as in "Redaction"), a format
+ *             (MARS_HIP_CAMERA_RGB or _NV12; NV12 sizes are even; nothing is converted, so no NV12 flag matters) and a cell size B in
+ *             {4, 8, 16, 32, 64}; 0 means 16.  Frames are densely packed, as in "Redaction".
+ * Grid.       gw = (W + B - 1) / B, gh alike.  Cell (cx, cy) is the pixels [cx * B, min(W, (cx + 1) * B)) x [cy * B, min(H, (cy + 1) * B)),
+ *             anchored at the frame's origin; n is its pixel count (edge cells are clipped).  Per stream the detector holds in HBM
+ *             bg[gh][gw] as uint16 and an `initialised` flag.
+ * Luma.       NV12: the Y byte.  RGB: (77 R + 150 G + 29 B + 128) >> 8, which is 0 .. 255.
+ * Cell mean.  S = the sum of luma over the cell; m = (256 * S + n / 2) / n, floor: 8.8 fixed point, 0 .. 65280.
+ * Frames -> streams.  The rule of "Tracking": F % S == 0; by default frame f is stream f % S, step f / S; with MARS_MOTION_STREAM_MAJOR
+ *             stream f / (F / S), step f % (F / S).  A stream's steps are processed in ascending order; streams and cells are independent.
+ *             One call over 2T steps leaves exactly the state and the outputs of two calls over T steps each.
+ * Step, per cell.  Not initialised: bg = m, raw = 0 and the frame's `first` is 1; the stream is initialised after the step.  Initialised:
+ *             delta = m - bg, raw = |delta| > 256 * threshold (1 .. 255; 0 means 8).  Then k = raw ? learn_active : learn (1 .. 16 each; 0
+ *             means 4 and 8) and bg += sign(delta) * (|delta| >> k): an active cell is absorbed slowly.  A shift of 16 freezes the cell,
+ *             since |delta| < 65536.  The shift truncates toward zero, so bg stalls within 2^k - 1 of m; this is by design.  Under
+ *             MARS_MOTION_FRAME_DIFF bg = m after the comparison and the shifts are not looked at: plain frame differencing.
+ * Filter.     active(cx, cy) = raw && (the number of raw cells among the up to 8 neighbours inside the grid >= min_neighbors); 0 .. 8, 0
+ *             means no filter.  The background update uses raw, not active.
+ * Map.        Per frame gh rows of pitch = (gw + 31) / 32 uint32 words; cell cx is bit cx & 31 of word cx >> 5, as in "Instance masks in
+ *             frame pixels".  Bits at cx >= gw are zero.
+ * Statistics. Per frame {active, x0, y0, x1, y1, first}: the number of active cells and their bounding box in pixels, x0 = min cx * B,
+ *             x1 = min(W, (max cx + 1) * B), y alike; all four 0 without an active cell.
+ * Zones.      Up to MARS_MOTION_MAX_ZONES rectangles of mars_tile_t ("Tiled inference"): half-open source pixels, not empty, inside the
+ *             frame, so a tile table can be passed as it is.  zone_counts[f][z] = the number of active cells with cx in
+ *             [x0 / B, (x1 - 1) / B] and cy in [y0 / B, (y1 - 1) / B]: the cells whose pixels meet the zone.
+ * Detections. For frame f of a detection list and the map of frame f of the last motion call: the box's rectangle is "Box -> source
+ *             rectangle" of "ROI crops" with expand (0 means 1.0) and min_size 1, its cells are those the zone rule gives for that
+ *             rectangle, and the result is mars_motion_det_t {active, cells}.  A box the rule skips, and every entry behind the list, is
+ *             {0, 0}.  The caller decides what share of the cells means "moving".
+ * Not covered: device-side gating or compaction of the model batch; per-pixel models (MOG, ViBe); adaptive thresholds; camera-shake
+ *   compensation; frames with a row pitch; the mars_hip_pipe_* path; the merged lists of "Tiled inference". */
+#define MARS_MOTION_MAX_ZONES 64
+#define MARS_MOTION_STREAM_MAJOR 1u
+#define MARS_MOTION_FRAME_DIFF 2u
+typedef struct mars_hip_motion mars_hip_motion_t; /* opaque */
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int threshold, learn, learn_active, min_neighbors;
+    unsigned flags;                                    /* MARS_MOTION_STREAM_MAJOR | MARS_MOTION_FRAME_DIFF */
+    int n_zones; const mars_tile_t *zones;             /* 0 .. MARS_MOTION_MAX_ZONES; copied by every call */
+} mars_hip_motion_opts_t;
+typedef struct { int active, x0, y0, x1, y1, first; } mars_motion_stats_t; /* 24 bytes */
+typedef struct { int active, cells; } mars_motion_det_t;                   /* 8 bytes */
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: NULL where a pointer is needed; a non-positive size, stream or
+ * frame count; a cell outside the set; a threshold, shift, min_neighbors or zone count out of range; an unknown flag or format; odd NV12
+ * sizes; a zone that is empty or not inside the frame; a negative or non-finite expand.  MARS_ERR_INVALID_TENSOR: W or H above 8192, more
+ * than 65535 streams, F % S != 0, a stream out of range, *_results with nothing pending, no detections in HBM, a batch different from the
+ * last motion call's F, a model with an open pipe.  A refused call leaves the detector's state as it was. */
+mars_error_t mars_hip_motion_create(int streams, int w, int h, int format, int cell, mars_hip_motion_t **out);
+mars_error_t mars_hip_motion_reset(mars_hip_motion_t *m, int stream);   /* that stream not initialised again; -1: all of them; waits */
+void         mars_hip_motion_free(mars_hip_motion_t *m);                /* waits for the device first */
+/* Pure host code: the grid of W x H frames at that cell size.  Any pointer may be NULL. */
+mars_error_t mars_hip_motion_grid(int w, int h, int cell, int *gw, int *gh, int *pitch);
+/* Waits.  bg = [gh][gw] of that stream (meaningless until it is initialised), *initialised = its flag; either may be NULL. */
+mars_error_t mars_hip_motion_read(mars_hip_motion_t *m, int stream, uint16_t *bg, int *initialised);
+/* Host pointers in and out, the same kernels on the GPU; waits.  frames = n_frames frames; maps = [n_frames][gh][pitch], stats = [n_frames],
+ * zone_counts = [n_frames][n_zones]; any of the three may be NULL. */
+mars_error_t mars_yolo_motion_frames(mars_hip_motion_t *m, const unsigned char *frames, int n_frames, const mars_hip_motion_opts_t *opts,
+                                     uint32_t *maps, mars_motion_stats_t *stats, int *zone_counts);
+/* The device form: n_frames frames at frames_dev.  Enqueues only, on the library's current stream, like mars_hip_preprocess_device.  A
+ * redaction enqueued LATER on the same frames first waits for that stream, so motion has read the original pixels; one enqueued EARLIER has
+ * made that stream wait for it, so motion sees the redacted ones. */
+mars_error_t mars_hip_motion_device(mars_hip_motion_t *m, const void *frames_dev, int n_frames, const mars_hip_motion_opts_t *opts);
+/* Waits.  The arrays of the last mars_hip_motion_device call, as in mars_yolo_motion_frames; any pointer may be NULL. */
+mars_error_t mars_hip_motion_results(mars_hip_motion_t *m, uint32_t *maps, mars_motion_stats_t *stats, int *zone_counts);
+/* Reads the lists the last mars_hip_detect_*_device of det_model left in HBM, boxes taken as frame pixels, against the maps of m's last
+ * call, whose F must equal the batch.  Enqueues only, on the auxiliary stream with the label scatter's ordering: behind the detection tail
+ * and behind the motion kernels the main stream has been given, ahead of the model's next detect call; m's next motion call waits for it.
+ * The result array lives on det_model beside the tracks. */
+mars_error_t mars_hip_motion_detections_device(mars_model_t *det_model, mars_hip_motion_t *m, float expand);
+/* Waits.  out = [batch][MARS_YOLO_MAX_DET]: entry i of frame f belongs to detection i of mars_hip_detect_results. */
+mars_error_t mars_hip_motion_det_results(mars_model_t *det_model, mars_motion_det_t *out);
+/* The host-list form, against the maps of m's last call; waits.  Box i lies in frame frame_of_box[i]; one whose index names no frame gives
+ * {0, 0}.  out = [n_boxes]. */
+mars_error_t mars_yolo_motion_boxes(mars_hip_motion_t *m, const mars_det_t *boxes, const int *frame_of_box, int n_boxes, float expand,
+                                    mars_motion_det_t *out);
+/* Device time (ms) of the last mars_hip_motion_device call's two kernels, from events on its stream; waits for it.  < 0: not available. */
+float mars_hip_motion_ms(mars_hip_motion_t *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,6 +257,8 @@ typedef struct mars_model_ext {
                           * [frames] x mars_redact_stats_t */
     size_t redact_stats_off;
     void *ev_redact_done; /* the redaction (auxiliary stream) has written the frames: the main stream waits for it */
+    /* motion (mars_motion.c) */
+    mars_det_side_t motion; /* moved cells of THIS model's detections: x mars_motion_det_t */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 

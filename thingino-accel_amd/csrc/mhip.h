@@ -707,6 +707,43 @@ typedef struct {
 int mhip_redact_select(const mhip_redact_t *p);
 int mhip_redact(const mhip_redact_t *p);
 
+/* ---- motion maps (motion.hip): camera frames -> per frame a bit map of the grid cells whose mean luma left the stream's background, by the
+ * exact rule of include/mars_hip.h ("Motion").  Every pointer is device memory.  Two launches per call: mhip_motion_cells (one workgroup
+ * per 64 x 64 pixel tile and STREAM, which walks that stream's steps in order: cell means, the compare, the background update, one raw byte
+ * per cell and the frames' `first`), then mhip_motion_map (one workgroup per frame: the neighbour filter, the packed words, the statistics,
+ * the zone counts; it marks the frame's stream initialised).  mhip_motion_dets counts a box list's cells against the maps. */
+#define MHIP_MOTION_MAX_DIM 8192
+#define MHIP_MOTION_MAX_ZONES 64
+typedef struct {
+    const uint8_t *frames;                      /* [n_frames] RGB [h][w][3] (fmt 0) or NV12 (fmt 1: only the Y plane is read) */
+    size_t frame_stride;
+    int n_frames, streams, steps, stream_major; /* n_frames = streams * steps; frame of (stream s, step t) = stream_major ? s * steps + t : t * streams + s */
+    int w, h, fmt, cell_log2, gw, gh, pitch;    /* cell = 1 << cell_log2: 4 .. 64; gw, gh = the grid; pitch = (gw + 31) / 32 words */
+    int threshold, learn, learn_active;         /* resolved: 1 .. 255, 1 .. 16, 1 .. 16 */
+    int min_neighbors, frame_diff;              /* 0 .. 8; != 0: bg = m after the comparison */
+    uint16_t *bg;                               /* [streams][gh][gw] */
+    int *init;                                  /* [streams]: != 0 once a step has run */
+    uint8_t *raw;                               /* [n_frames][gh][32 * pitch]: scratch between the two launches, 16-byte aligned; cells >= gw are never written */
+    uint32_t *maps;                             /* [n_frames][gh][pitch] */
+    int *stats;                                 /* [n_frames][6]: active, x0, y0, x1, y1, first */
+    int *zone_counts;                           /* [n_frames][n_zones]; may be NULL with n_zones == 0 */
+    int n_zones;
+    int zones[MHIP_MOTION_MAX_ZONES][4];        /* the zones' CELL ranges, inclusive: cx0, cy0, cx1, cy1, inside the grid */
+} mhip_motion_t;
+int mhip_motion_cells(const mhip_motion_t *p);
+int mhip_motion_map(const mhip_motion_t *p);
+typedef struct {
+    const uint32_t *maps; int n_frames, gw, gh, pitch, cell_log2, w, h;
+    const void *dets;       /* records of 24 bytes */
+    const int *counts;      /* device form: [n_frames] list lengths, clamped to 0 .. det_cap; entry e is record e % det_cap of frame e / det_cap */
+    int det_cap;
+    const int *frame_of;    /* list form (counts == NULL): the frame of entry e; one that names no frame gives {0, 0} */
+    int n_entries;          /* device form: n_frames * det_cap */
+    float expand;           /* resolved: > 0 */
+    void *out;              /* [n_entries] records of 8 bytes {active, cells} */
+} mhip_motion_dets_t;
+int mhip_motion_dets(const mhip_motion_dets_t *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,7 +231,19 @@ class RedactOpts(C.Structure):  # mars_hip_redact_opts_t: zero = default in ever
                 ("cls_count", C.c_int), ("flags", C.c_uint)]
 
 
+MOTION_STREAM_MAJOR, MOTION_FRAME_DIFF = 1, 2                             # MARS_MOTION_*
+MOTION_MAX_ZONES = 64
+MOTION_STATS_DTYPE = np.dtype([("active", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("first", "<i4")])  # mars_motion_stats_t
+MOTION_DET_DTYPE = np.dtype([("active", "<i4"), ("cells", "<i4")])        # mars_motion_det_t
+
+
+class MotionOpts(C.Structure):  # mars_hip_motion_opts_t: zero = default in every field
+    _fields_ = [("threshold", C.c_int), ("learn", C.c_int), ("learn_active", C.c_int), ("min_neighbors", C.c_int), ("flags", C.c_uint),
+                ("n_zones", C.c_int), ("zones", C.c_void_p)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert MOTION_STATS_DTYPE.itemsize == 24 and MOTION_DET_DTYPE.itemsize == 8 and C.sizeof(MotionOpts) == 32
 assert REDACT_STATS_DTYPE.itemsize == 16 and C.sizeof(RedactOpts) == 52
 assert TILE_DTYPE.itemsize == 16 and TILE_SRC_DTYPE.itemsize == 8 and TILE_STATS_DTYPE.itemsize == 24 and C.sizeof(TileOpts) == 48
 assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
@@ -295,7 +307,10 @@ EXPORTS = {
                    "mars_hip_crop_pose", "mars_hip_align_results",
                    "mars_tile_grid", "mars_hip_preprocess_tiles_device", "mars_hip_preprocess_tiles", "mars_hip_merge_tiles_device",
                    "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles",
-                   "mars_yolo_redact_frames", "mars_hip_redact_device", "mars_hip_redact_results", "mars_hip_redact", "mars_hip_redact_ms"],
+                   "mars_yolo_redact_frames", "mars_hip_redact_device", "mars_hip_redact_results", "mars_hip_redact", "mars_hip_redact_ms",
+                   "mars_hip_motion_create", "mars_hip_motion_reset", "mars_hip_motion_free", "mars_hip_motion_grid", "mars_hip_motion_read",
+                   "mars_yolo_motion_frames", "mars_hip_motion_device", "mars_hip_motion_results", "mars_hip_motion_detections_device",
+                   "mars_hip_motion_det_results", "mars_yolo_motion_boxes", "mars_hip_motion_ms"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -475,6 +490,20 @@ def lib():
     L.mars_hip_redact.argtypes = [P(MarsModel), C.c_void_p, P(RedactOpts), C.c_void_p]
     L.mars_hip_redact_ms.restype = C.c_float
     L.mars_hip_redact_ms.argtypes = [P(MarsModel)]
+    L.mars_hip_motion_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_void_p)]
+    L.mars_hip_motion_reset.argtypes = [C.c_void_p, C.c_int]
+    L.mars_hip_motion_free.argtypes = [C.c_void_p]
+    L.mars_hip_motion_free.restype = None
+    L.mars_hip_motion_grid.argtypes = [C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
+    L.mars_hip_motion_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, P(C.c_int)]
+    L.mars_yolo_motion_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, P(MotionOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_motion_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, P(MotionOpts)]
+    L.mars_hip_motion_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_motion_detections_device.argtypes = [P(MarsModel), C.c_void_p, C.c_float]
+    L.mars_hip_motion_det_results.argtypes = [P(MarsModel), C.c_void_p]
+    L.mars_yolo_motion_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    L.mars_hip_motion_ms.restype = C.c_float
+    L.mars_hip_motion_ms.argtypes = [C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -792,6 +821,115 @@ def redact_frames(frames, boxes, frame_of_box, opts, mask_words=None, mask_of_bo
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_redact_frames")
     return out.reshape(n, fb), stats
+
+
+def motion_grid(w, h, cell=0):
+    """mars_hip_motion_grid: (gw, gh, pitch) of w x h frames at that cell size (0: 16); host only"""
+    gw, gh, pitch = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().mars_hip_motion_grid(int(w), int(h), int(cell), C.byref(gw), C.byref(gh), C.byref(pitch))
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_hip_motion_grid")
+    return gw.value, gh.value, pitch.value
+
+
+def motion_opts(threshold=0, learn=0, learn_active=0, min_neighbors=0, stream_major=False, frame_diff=False, zones=None, flags=None):
+    """mars_hip_motion_opts_t.  threshold: luma levels, 1 .. 255 (0: 8); learn / learn_active: the background's shifts, 1 .. 16 (0: 4 and 8);
+    min_neighbors: 0 .. 8; zones: TILE_DTYPE records or rows of (x0, y0, x1, y1), at most MOTION_MAX_ZONES (the record keeps them alive);
+    flags overrides stream_major and frame_diff"""
+    o = MotionOpts(int(threshold), int(learn), int(learn_active), int(min_neighbors))
+    o.flags = int(flags) if flags is not None else (MOTION_STREAM_MAJOR if stream_major else 0) | (MOTION_FRAME_DIFF if frame_diff else 0)
+    if zones is not None and len(zones):
+        z = np.asarray(zones)
+        o._zones = np.ascontiguousarray(z if z.dtype == TILE_DTYPE else np.asarray(zones, dtype=np.int32).reshape(-1, 4)).reshape(-1).view(np.int32)
+        o.n_zones, o.zones = o._zones.size // 4, o._zones.ctypes.data
+    return o
+
+
+class Motion:
+    """mars_hip_motion_t: the background grids of `streams` camera streams of w x h frames (fmt: CAMERA_RGB / CAMERA_NV12) at one cell size,
+    held on the device between calls"""
+
+    def __init__(self, streams, w, h, fmt=CAMERA_RGB, cell=0):
+        self.p = C.c_void_p()
+        rc = lib().mars_hip_motion_create(int(streams), int(w), int(h), int(fmt), int(cell), C.byref(self.p))
+        if rc != MARS_OK:
+            self.p = None
+            raise MarsError(rc, "mars_hip_motion_create")
+        self.streams, self.w, self.h, self.fmt, self.cell = int(streams), int(w), int(h), int(fmt), int(cell) or 16
+        self.gw, self.gh, self.pitch = motion_grid(w, h, cell)
+        self.frame_bytes = self.w * self.h * 3 // (2 if self.fmt == CAMERA_NV12 else 1)
+        self._frames = self._zones = 0
+
+    def _arrays(self, n, nz):
+        return (np.zeros((n, self.gh, self.pitch), dtype=np.uint32), np.zeros(n, dtype=MOTION_STATS_DTYPE), np.zeros((n, nz), dtype=np.int32))
+
+    def frames(self, frames, opts=None, **kw):
+        """mars_yolo_motion_frames: frames (uint8, [n] frames in host memory) go through the detector, on the GPU -> (maps uint32
+        [n][gh][pitch], MOTION_STATS_DTYPE [n], zone counts int32 [n][n_zones]); waits.  opts = motion_opts(...), or its keywords"""
+        o = opts if opts is not None else motion_opts(**kw)
+        a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+        if a.size == 0 or a.size % self.frame_bytes:
+            raise ValueError("frames of %d x %d are %d bytes each, got %d" % (self.w, self.h, self.frame_bytes, a.size))
+        n = a.size // self.frame_bytes
+        maps, stats, zc = self._arrays(n, o.n_zones)
+        rc = lib().mars_yolo_motion_frames(self.p, a.ctypes.data, n, C.byref(o), maps.ctypes.data, stats.ctypes.data, zc.ctypes.data if o.n_zones else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_yolo_motion_frames")
+        self._frames, self._zones = n, o.n_zones
+        return maps, stats, zc
+
+    def device(self, frames_dev, n_frames, opts=None, **kw):
+        """mars_hip_motion_device: n_frames frames at device address frames_dev; enqueues only"""
+        o = opts if opts is not None else motion_opts(**kw)
+        rc = lib().mars_hip_motion_device(self.p, C.c_void_p(frames_dev), int(n_frames), C.byref(o))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_motion_device")
+        self._frames, self._zones = int(n_frames), o.n_zones
+
+    def results(self):
+        """-> (maps, stats, zone counts) of the last device() (mars_hip_motion_results); waits"""
+        maps, stats, zc = self._arrays(self._frames, self._zones)
+        rc = lib().mars_hip_motion_results(self.p, maps.ctypes.data if self._frames else None, stats.ctypes.data if self._frames else None,
+                                           zc.ctypes.data if zc.size else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_motion_results")
+        return maps, stats, zc
+
+    def boxes(self, boxes, frame_of_box, expand=0.0):
+        """mars_yolo_motion_boxes: DET_DTYPE records, box i in frame frame_of_box[i] of the last call -> MOTION_DET_DTYPE [n]; waits"""
+        b = np.ascontiguousarray(boxes, dtype=DET_DTYPE).reshape(-1)
+        fo = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
+        if fo.size != b.size:
+            raise ValueError("one frame index per box")
+        out = np.zeros(b.size, dtype=MOTION_DET_DTYPE)
+        rc = lib().mars_yolo_motion_boxes(self.p, b.ctypes.data if b.size else None, fo.ctypes.data if b.size else None, b.size, float(expand),
+                                          out.ctypes.data if b.size else None)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_yolo_motion_boxes")
+        return out
+
+    def read(self, stream):
+        """-> (bg uint16 [gh][gw], initialised) of that stream (mars_hip_motion_read); waits"""
+        bg = np.zeros((self.gh, self.gw), dtype=np.uint16)
+        init = C.c_int()
+        rc = lib().mars_hip_motion_read(self.p, int(stream), bg.ctypes.data, C.byref(init))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_motion_read")
+        return bg, bool(init.value)
+
+    def reset(self, stream=-1):
+        rc = lib().mars_hip_motion_reset(self.p, int(stream))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_motion_reset")
+
+    def ms(self):
+        """device time (ms) of the last device() call's kernels (mars_hip_motion_ms); < 0: not available"""
+        return float(lib().mars_hip_motion_ms(self.p))
+
+    def close(self):
+        if self.p:
+            lib().mars_hip_motion_free(self.p)
+            self.p = None
 
 
 def cls_opts(output_index=0, tensor=0, top_k=0, scale=0.0, softmax=False):
@@ -1723,6 +1861,21 @@ class Model:
     def redact_ms(self):
         """device time (ms) of the last redact_device() (mars_hip_redact_ms); < 0: not available"""
         return float(lib().mars_hip_redact_ms(self.p))
+
+    def motion_detections_device(self, motion, expand=0.0):
+        """THIS model is the detector: the detections its last detect_*_device call left in HBM are counted against the maps of motion's
+        last call (mars_hip_motion_detections_device); enqueues only"""
+        rc = lib().mars_hip_motion_detections_device(self.p, motion.p, float(expand))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_motion_detections_device")
+
+    def motion_det_results(self):
+        """-> MOTION_DET_DTYPE [batch][MAX_DET]: entry i of frame f belongs to detect_results()[f][i] (mars_hip_motion_det_results); waits"""
+        out = np.zeros((self.batch, MAX_DET), dtype=MOTION_DET_DTYPE)
+        rc = lib().mars_hip_motion_det_results(self.p, out.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_motion_det_results")
+        return out
 
     def track_device(self, tracker, opts=None, **kw):
         """THIS model is the detector: the detections its last detect_*_device call left in HBM (and, with carry_identity, the identities
