@@ -51,7 +51,9 @@ def test_grid_and_refusals_without_a_device(marsrt):
     p = C.c_void_p()
     bad = [((1, 0, 8, 0, 16), FILE), ((1, 8, -1, 0, 16), FILE), ((0, 8, 8, 0, 16), FILE), ((1, 8, 8, 2, 16), FILE), ((1, 8, 8, 0, 2), FILE),
            ((1, 8, 8, 0, 24), FILE), ((1, 8, 8, 0, 128), FILE), ((1, 9, 8, 1, 16), FILE), ((1, 8, 9, 1, 16), FILE), ((1, 8193, 8, 0, 16), TENSOR),
-           ((1, 8, 8194, 1, 16), TENSOR), ((65536, 8, 8, 0, 16), TENSOR)]
+           ((1, 8, 8194, 1, 16), TENSOR), ((65536, 8, 8, 0, 16), TENSOR),
+           # two faults of different codes: the format before the grid, the grid before the evenness, the evenness before the stream count
+           ((1, 8195, 8, 1, 16), TENSOR), ((1, 8193, 8, 2, 16), FILE), ((65536, 9, 8, 1, 16), FILE)]
     for args, code in bad:
         assert L.mars_hip_motion_create(*args, C.byref(p)) == code and not p.value, args
     assert L.mars_hip_motion_create(1, 8, 8, 0, 16, None) == FILE

@@ -249,7 +249,8 @@ def test_redact_bad_arguments_are_refused_up_front(marsrt):
            marsrt.redact_opts(6, 4, expand=-1.0), marsrt.redact_opts(6, 4, expand=float("nan")), marsrt.redact_opts(6, 4, expand=float("inf")),
            marsrt.redact_opts(6, 4, min_conf=-0.5), marsrt.redact_opts(6, 4, min_conf=float("nan")),
            marsrt.redact_opts(6, 4, ident_min=-0.5), marsrt.redact_opts(6, 4, ident_min=float("nan")), marsrt.redact_opts(6, 4, ident_min=1.5),
-           marsrt.redact_opts(6, 4, classes=(0, -1))]
+           marsrt.redact_opts(6, 4, classes=(0, -1)),
+           marsrt.redact_opts(8193, 3, fmt=nv), marsrt.redact_opts(8193, 4, cell=3)]              # two faults: these come before the size limit
     P = C.POINTER(marsrt.MarsModel)
     a = marsrt.MarsModel()  # never looked into: the refusals come first
     for o in bad:

@@ -5,7 +5,7 @@
 //   motion_cells_kernel    one workgroup of 256 threads per 64 x 64 pixel tile and STREAM.  A tile is cell-aligned for every legal cell
 //                          (4 .. 64) and holds at most 256 cells: thread t owns cell t of the tile and keeps its background in a register
 //                          across the stream's steps of the call -- loaded once, stored once.  Per step the tile's rows (the Y plane of an
-//                          NV12 frame) go to LDS with the row moves of redact.hip, four threads on a row reduce 16 pixels each to luma and to
+//                          NV12 frame) go to LDS (tile_rows_to_lds of frame_tile.hpp), four threads on a row reduce 16 pixels each to luma and to
 //                          their cells' parts of the row, the owning thread adds the rows, compares, updates and stores one raw byte.
 //   motion_map_kernel      one workgroup per frame, a thread per 32 cells of a grid row (raw rows are padded to whole words, so the 32 bytes
 //                          come as two aligned 16-byte loads): the three rows' raw bits in registers, the neighbour count by popcounts,
@@ -21,17 +21,16 @@
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "frame_tile.hpp"
 #include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-#define MO_TILE 64     // pixels per tile side
-#define MO_THREADS 256
-#define MO_PITCH 208   // LDS bytes per staged row: 64 x 3 + the shift of at most 3, a multiple of 16 (the word reads below end at byte 196)
 #define MO_CELLS 16    // cells per tile side at most (cell 4)
 
-// 16 pixels of C bytes from byte `o` of an LDS row (any alignment) -> their luma; pixels from `valid` on give 0
+// 16 pixels of C bytes from byte `o` of an LDS row (any alignment) -> their luma; pixels from `valid` on give 0.  The word reads end at byte
+// 196 of the row at most (o <= 3 + 144, thirteen words from o & ~3): inside FT_PITCH
 template <int C>
 __device__ __forceinline__ void luma16(const uint8_t *row, const int o, const int valid, int y[16]) {
     const uint32_t *w = (const uint32_t *)(row + (o & ~3));
@@ -60,13 +59,13 @@ __device__ __forceinline__ void luma16(const uint8_t *row, const int o, const in
 }
 
 template <int C>
-__global__ __launch_bounds__(MO_THREADS) void motion_cells_kernel(const mhip_motion_t p) {
-    __shared__ __attribute__((aligned(16))) uint8_t pix[MO_TILE * MO_PITCH];
-    __shared__ unsigned short part[MO_TILE * MO_CELLS]; // [row][cell column of the tile]: the row's part of the cell's sum, <= 64 * 255
+__global__ __launch_bounds__(FT_THREADS) void motion_cells_kernel(const mhip_motion_t p) {
+    __shared__ __attribute__((aligned(16))) uint8_t pix[FT_TILE * FT_PITCH];
+    __shared__ unsigned short part[FT_TILE * MO_CELLS]; // [row][cell column of the tile]: the row's part of the cell's sum, <= 64 * 255
     const int tid = threadIdx.x, row = tid >> 2, sub = tid & 3; // four threads on a row
-    const int s = blockIdx.z, X0 = blockIdx.x * MO_TILE, Y0 = blockIdx.y * MO_TILE;
+    const int s = blockIdx.z, X0 = blockIdx.x * FT_TILE, Y0 = blockIdx.y * FT_TILE;
     const int W = p.w, H = p.h, bl = p.cell_log2, B = 1 << bl;
-    const int tw = min(MO_TILE, W - X0), th = min(MO_TILE, H - Y0);
+    const int tw = min(FT_TILE, W - X0), th = min(FT_TILE, H - Y0);
     const int ncx = (tw + B - 1) >> bl, ncy = (th + B - 1) >> bl;
     const size_t pitch = (size_t)W * C;
     const int nb = tw * C;
@@ -86,29 +85,13 @@ __global__ __launch_bounds__(MO_THREADS) void motion_cells_kernel(const mhip_mot
         const size_t f = p.stream_major ? (size_t)s * p.steps + t : (size_t)t * p.streams + s;
         const uint8_t *src = p.frames + f * p.frame_stride + ((size_t)Y0 * W + X0) * C;
         const bool wide = !(((uintptr_t)src | pitch | (size_t)nb) & 15);
-        // ---- the tile's rows -> LDS, row r at pix + r * MO_PITCH + (its address & 3); nothing is read behind a row's last byte
-        int sh = 0;
-        if (row < th) {
-            const uint8_t *g = src + (size_t)row * pitch;
-            if (wide) {
-                uint8_t *l = pix + row * MO_PITCH;
-                for (int j = sub; j < (nb >> 4); j += 4) *(uint4 *)(l + 16 * j) = *(const uint4 *)(g + 16 * j);
-            } else {
-                sh = (int)((uintptr_t)g & 3);
-                const int head = min(nb, (4 - sh) & 3), nd = (nb - head) >> 2;
-                uint8_t *l = pix + row * MO_PITCH + sh;
-                if (sub == 0)
-                    for (int k = 0; k < head; k++) l[k] = g[k];
-                for (int j = sub; j < nd; j += 4) *(uint32_t *)(l + head + 4 * j) = *(const uint32_t *)(g + head + 4 * j);
-                if (sub == 3)
-                    for (int k = head + 4 * nd; k < nb; k++) l[k] = g[k];
-            }
-        }
+        // ---- the tile's rows -> LDS, row r at pix + r * FT_PITCH + (its address & 3); nothing is read behind a row's last byte
+        const int sh = tile_rows_to_lds(src, pitch, nb, th, pix, wide);
         __syncthreads();
         // ---- pixels 16 sub .. 16 sub + 15 of the row -> luma -> the row's parts of the cells they lie in
         int y[16];
         if (row < th) {
-            luma16<C>(pix + row * MO_PITCH, sh + 16 * sub * C, tw - 16 * sub, y);
+            luma16<C>(pix + row * FT_PITCH, sh + 16 * sub * C, tw - 16 * sub, y);
         } else {
 #pragma unroll
             for (int x = 0; x < 16; x++) y[x] = 0;
@@ -174,7 +157,7 @@ __device__ __forceinline__ unsigned long long raw_bits(const uint8_t *raw, const
     return out;
 }
 
-__global__ __launch_bounds__(MO_THREADS) void motion_map_kernel(const mhip_motion_t p) {
+__global__ __launch_bounds__(FT_THREADS) void motion_map_kernel(const mhip_motion_t p) {
     __shared__ int acc[5];                    // active, min cx, min cy, max cx, max cy
     __shared__ int zc[MHIP_MOTION_MAX_ZONES];
     const int f = blockIdx.x, tid = threadIdx.x;
@@ -185,7 +168,7 @@ __global__ __launch_bounds__(MO_THREADS) void motion_map_kernel(const mhip_motio
     const uint8_t *raw = p.raw + (size_t)f * gh * rp;
     uint32_t *map = p.maps + (size_t)f * gh * p.pitch;
     const int words = gh * p.pitch; // <= 2048 * 64
-    for (int i = tid; i < words; i += MO_THREADS) {
+    for (int i = tid; i < words; i += FT_THREADS) {
         const int cy = i / p.pitch, c0 = (i - cy * p.pitch) << 5;
         const unsigned long long mid = raw_bits(raw, rp, gw, gh, cy, c0);
         uint32_t bits = (uint32_t)(mid >> 1);
@@ -210,7 +193,7 @@ __global__ __launch_bounds__(MO_THREADS) void motion_map_kernel(const mhip_motio
             for (int z = 0; z < p.n_zones; z++) {
                 const int lo = max(p.zones[z][0], c0), hi = min(p.zones[z][2], c0 + 31); // inclusive
                 if (cy < p.zones[z][1] || cy > p.zones[z][3] || hi < lo) continue;
-                const uint32_t m = (hi - lo == 31 ? ~0u : (1u << (hi - lo + 1)) - 1u) << (lo - c0);
+                const uint32_t m = span_mask(lo - c0, hi - c0);
                 if (bits & m) atomicAdd(&zc[z], __popc(bits & m));
             }
         }
@@ -231,8 +214,8 @@ __global__ __launch_bounds__(MO_THREADS) void motion_map_kernel(const mhip_motio
     if (tid < p.n_zones) p.zone_counts[(size_t)f * p.n_zones + tid] = zc[tid];
 }
 
-__global__ __launch_bounds__(MO_THREADS) void motion_dets_kernel(const mhip_motion_dets_t p) {
-    const int e = blockIdx.x * MO_THREADS + threadIdx.x;
+__global__ __launch_bounds__(FT_THREADS) void motion_dets_kernel(const mhip_motion_dets_t p) {
+    const int e = blockIdx.x * FT_THREADS + threadIdx.x;
     if (e >= p.n_entries) return;
     int f, act = 0, cells = 0;
     bool listed;
@@ -252,8 +235,7 @@ __global__ __launch_bounds__(MO_THREADS) void motion_dets_kernel(const mhip_moti
         for (int cy = cy0; cy <= cy1; cy++)
             for (int wi = cx0 >> 5; wi <= cx1 >> 5; wi++) {
                 const int c0 = wi << 5, lo = max(cx0, c0), hi = min(cx1, c0 + 31);
-                const uint32_t m = (hi - lo == 31 ? ~0u : (1u << (hi - lo + 1)) - 1u) << (lo - c0);
-                act += __popc(map[(size_t)cy * p.pitch + wi] & m);
+                act += __popc(map[(size_t)cy * p.pitch + wi] & span_mask(lo - c0, hi - c0));
             }
     }
     int *o = (int *)p.out + 2 * (size_t)e;
@@ -262,12 +244,12 @@ __global__ __launch_bounds__(MO_THREADS) void motion_dets_kernel(const mhip_moti
 
 static bool motion_ok(const mhip_motion_t *p) {
     if (!p || !p->frames || !p->bg || !p->init || !p->raw || !p->maps || !p->stats) return false;
-    if (p->w <= 0 || p->h <= 0 || p->w > MHIP_MOTION_MAX_DIM || p->h > MHIP_MOTION_MAX_DIM || p->cell_log2 < 2 || p->cell_log2 > 6) return false;
-    if (p->fmt != 0 && !(p->fmt == 1 && !((p->w | p->h) & 1))) return false;
+    if (p->w > MHIP_MOTION_MAX_DIM || p->h > MHIP_MOTION_MAX_DIM || p->cell_log2 < 2 || p->cell_log2 > 6) return false;
+    const size_t fb = mhip_frame_bytes(p->w, p->h, p->fmt);
+    if (!mhip_frame_format_ok(p->fmt, 0) || !fb || p->frame_stride < fb) return false; // (no NV12 flag matters: only the Y plane is read)
     const int B = 1 << p->cell_log2;
     if (p->gw != (p->w + B - 1) / B || p->gh != (p->h + B - 1) / B || p->pitch != (p->gw + 31) / 32) return false;
     if (p->streams <= 0 || p->streams > 65535 || p->steps <= 0 || (long long)p->streams * p->steps != p->n_frames) return false;
-    if (p->frame_stride < (size_t)p->w * p->h * (p->fmt ? 3 : 6) / 2) return false;
     if (p->threshold < 1 || p->threshold > 255 || p->learn < 1 || p->learn > 16 || p->learn_active < 1 || p->learn_active > 16) return false;
     if (p->min_neighbors < 0 || p->min_neighbors > 8 || p->n_zones < 0 || p->n_zones > MHIP_MOTION_MAX_ZONES || (p->n_zones && !p->zone_counts)) return false;
     for (int z = 0; z < p->n_zones; z++)
@@ -279,15 +261,15 @@ static bool motion_ok(const mhip_motion_t *p) {
 
 extern "C" int mhip_motion_cells(const mhip_motion_t *p) {
     if (!motion_ok(p)) return -1;
-    const dim3 g((unsigned)((p->w + MO_TILE - 1) / MO_TILE), (unsigned)((p->h + MO_TILE - 1) / MO_TILE), (unsigned)p->streams);
-    if (p->fmt == 0) hipLaunchKernelGGL(motion_cells_kernel<3>, g, dim3(MO_THREADS), 0, mhip_stream_native(), *p);
-    else hipLaunchKernelGGL(motion_cells_kernel<1>, g, dim3(MO_THREADS), 0, mhip_stream_native(), *p);
+    const dim3 g((unsigned)((p->w + FT_TILE - 1) / FT_TILE), (unsigned)((p->h + FT_TILE - 1) / FT_TILE), (unsigned)p->streams);
+    if (p->fmt == 0) hipLaunchKernelGGL(motion_cells_kernel<3>, g, dim3(FT_THREADS), 0, mhip_stream_native(), *p);
+    else hipLaunchKernelGGL(motion_cells_kernel<1>, g, dim3(FT_THREADS), 0, mhip_stream_native(), *p);
     return mhip_check(hipGetLastError(), "motion cells");
 }
 
 extern "C" int mhip_motion_map(const mhip_motion_t *p) {
     if (!motion_ok(p)) return -1;
-    hipLaunchKernelGGL(motion_map_kernel, dim3((unsigned)p->n_frames), dim3(MO_THREADS), 0, mhip_stream_native(), *p);
+    hipLaunchKernelGGL(motion_map_kernel, dim3((unsigned)p->n_frames), dim3(FT_THREADS), 0, mhip_stream_native(), *p);
     return mhip_check(hipGetLastError(), "motion map");
 }
 
@@ -297,6 +279,6 @@ extern "C" int mhip_motion_dets(const mhip_motion_dets_t *p) {
         p->cell_log2 > 6 || p->gw != ((p->w - 1) >> p->cell_log2) + 1 || p->gh != ((p->h - 1) >> p->cell_log2) + 1 || p->pitch != (p->gw + 31) / 32 ||
         !(p->expand > 0) || (p->counts && (long long)p->n_frames * p->det_cap != p->n_entries))
         return -1;
-    hipLaunchKernelGGL(motion_dets_kernel, dim3((unsigned)((p->n_entries + MO_THREADS - 1) / MO_THREADS)), dim3(MO_THREADS), 0, mhip_stream_native(), *p);
+    hipLaunchKernelGGL(motion_dets_kernel, dim3((unsigned)((p->n_entries + FT_THREADS - 1) / FT_THREADS)), dim3(FT_THREADS), 0, mhip_stream_native(), *p);
     return mhip_check(hipGetLastError(), "motion dets");
 }

@@ -16,23 +16,22 @@
 // the original frame alone, in place as out of place.  A workgroup whose tile meets no region leaves at once and, in place, touches no pixel.
 // Rows of 3 * W bytes have any alignment: a row is moved as 16-byte units where the tile's rows are all 16-byte aligned on both sides,
 // else as bytes up to the first 4-byte boundary, 4-byte units and bytes behind the last one; its LDS copy is shifted by the row's address
-// & 3, so both sides of every 4-byte move are aligned.  All stores are plain vector stores from C++.
+// & 3, so both sides of every 4-byte move are aligned (in: tile_rows_to_lds of frame_tile.hpp; out: below).  All stores are plain vector
+// stores from C++.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../mhip.h"
+#include "frame_tile.hpp"
 #include "tail_core.hpp"
 
 extern "C" hipStream_t mhip_stream_native(void);
 extern "C" int mhip_check(hipError_t e, const char *what);
 
-#define RD_TILE 64     // pixels per tile side
-#define RD_THREADS 256
-#define RD_PITCH 208   // LDS bytes per staged row: 64 x 3 + the shift of at most 3, a multiple of 16
 #define RD_CELLS 32    // cells per tile side at most (cell 2; a chroma tile at cell 2 has 32 cells of one sample)
 
-__global__ __launch_bounds__(RD_THREADS) void redact_select_kernel(const mhip_redact_t p) {
-    __shared__ int wave_cnt[RD_THREADS / 64];
+__global__ __launch_bounds__(FT_THREADS) void redact_select_kernel(const mhip_redact_t p) {
+    __shared__ int wave_cnt[FT_THREADS / 64];
     __shared__ int slot_det[64]; // the list index each mask slot of this frame belongs to, -1: none
     __shared__ int cnt[2];       // masked, skipped
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(RD_THREADS) void redact_select_kernel(const mhip_re
     __syncthreads();
     const det_t *dets = (const det_t *)p.dets + base;
     int kept = 0;
-    for (int i0 = 0; i0 < n; i0 += RD_THREADS) {
+    for (int i0 = 0; i0 < n; i0 += FT_THREADS) {
         const int i = i0 + tid;
         bool ok = false, skip = false;
         int q[4] = {0, 0, 0, 0}, slot = -1;
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(RD_THREADS) void redact_select_kernel(const mhip_re
             }
         }
         int total;
-        const int rank = block_rank<RD_THREADS / 64>(ok, wave_cnt, total);
+        const int rank = block_rank<FT_THREADS / 64>(ok, wave_cnt, total);
         if (ok) {
             int *t = p.table + (base + (size_t)(kept + rank)) * 5;
             t[0] = q[0]; t[1] = q[1]; t[2] = q[2]; t[3] = q[3]; t[4] = slot;
@@ -97,37 +96,23 @@ __device__ __forceinline__ void redact_plane(const uint8_t *src, uint8_t *dst, c
     const int nb = tw * C;
     const bool wide = !(((uintptr_t)src | (uintptr_t)dst | pitch | (size_t)nb) & 15);
     const bool same4 = !(((uintptr_t)src ^ (uintptr_t)dst) & 3);
-    // ---- the tile's rows -> LDS, row r at pix + r * RD_PITCH + (its address & 3)
-    if (row < th) {
-        const uint8_t *g = src + (size_t)row * pitch;
-        if (wide) {
-            uint8_t *l = pix + row * RD_PITCH;
-            for (int j = sub; j < (nb >> 4); j += 4) *(uint4 *)(l + 16 * j) = *(const uint4 *)(g + 16 * j);
-        } else {
-            const int sh = (int)((uintptr_t)g & 3), head = min(nb, (4 - sh) & 3), nd = (nb - head) >> 2;
-            uint8_t *l = pix + row * RD_PITCH + sh;
-            if (sub == 0)
-                for (int k = 0; k < head; k++) l[k] = g[k];
-            for (int j = sub; j < nd; j += 4) *(uint32_t *)(l + head + 4 * j) = *(const uint32_t *)(g + head + 4 * j);
-            if (sub == 3)
-                for (int k = head + 4 * nd; k < nb; k++) l[k] = g[k];
-        }
-    }
+    // ---- the tile's rows -> LDS, row r at pix + r * FT_PITCH + (its address & 3); wide here: the stores below go the same way
+    (void)tile_rows_to_lds(src, pitch, nb, th, pix, wide);
     __syncthreads(); // every byte of the tile has been read: from here on it may be written
     if (any) {
         const int B = 1 << bl, ncx = (tw + B - 1) >> bl, ncy = (th + B - 1) >> bl;
         if (mode == 0) {
             // the sums of the ORIGINAL bytes: a row's part of every cell, then the cells
-            for (int it = tid; it < th * ncx * C; it += RD_THREADS) {
+            for (int it = tid; it < th * ncx * C; it += FT_THREADS) {
                 const int c = it % C, t2 = it / C, cx = t2 % ncx, r = t2 / ncx;
-                const uint8_t *l = pix + r * RD_PITCH + (int)((uintptr_t)(src + (size_t)r * pitch) & 3);
+                const uint8_t *l = pix + r * FT_PITCH + (int)((uintptr_t)(src + (size_t)r * pitch) & 3);
                 const int x1 = min(tw, (cx + 1) << bl);
                 int s = 0;
                 for (int x = cx << bl; x < x1; x++) s += l[x * C + c];
                 rowsum[(r * RD_CELLS + cx) * C + c] = (unsigned short)s; // <= 64 * 255
             }
             __syncthreads();
-            for (int it = tid; it < ncy * ncx * C; it += RD_THREADS) {
+            for (int it = tid; it < ncy * ncx * C; it += FT_THREADS) {
                 const int c = it % C, t2 = it / C, cx = t2 % ncx, cy = t2 / ncx;
                 const int r1 = min(th, (cy + 1) << bl);
                 int s = 0;
@@ -137,10 +122,10 @@ __device__ __forceinline__ void redact_plane(const uint8_t *src, uint8_t *dst, c
             }
             __syncthreads();
         }
-        for (int s = tid; s < RD_TILE * RD_TILE; s += RD_THREADS) {
+        for (int s = tid; s < FT_TILE * FT_TILE; s += FT_THREADS) {
             const int r = s >> 6, x = s & 63;
             if (r < th && x < tw && ((cov[r] >> x) & 1ull)) {
-                uint8_t *l = pix + r * RD_PITCH + (int)((uintptr_t)(src + (size_t)r * pitch) & 3) + x * C;
+                uint8_t *l = pix + r * FT_PITCH + (int)((uintptr_t)(src + (size_t)r * pitch) & 3) + x * C;
                 const uint8_t *v = val + ((r >> bl) * RD_CELLS + (x >> bl)) * C;
 #pragma unroll
                 for (int c = 0; c < C; c++) l[c] = mode ? (uint8_t)(fill >> (8 * c)) : v[c];
@@ -158,7 +143,7 @@ __device__ __forceinline__ void redact_plane(const uint8_t *src, uint8_t *dst, c
         };
         uint8_t *g = dst + (size_t)row * pitch;
         const int sh = (int)((uintptr_t)(src + (size_t)row * pitch) & 3);
-        const uint8_t *l = pix + row * RD_PITCH + sh;
+        const uint8_t *l = pix + row * FT_PITCH + sh;
         if (inplace && !cr) {
             // nothing of this row changes
         } else if (wide) {
@@ -182,31 +167,31 @@ __device__ __forceinline__ void redact_plane(const uint8_t *src, uint8_t *dst, c
     __syncthreads();
 }
 
-__global__ __launch_bounds__(RD_THREADS) void redact_kernel(const mhip_redact_t p) {
-    __shared__ __attribute__((aligned(16))) uint8_t pix[RD_TILE * RD_PITCH];
-    __shared__ unsigned short rowsum[RD_TILE * RD_CELLS * 3];
+__global__ __launch_bounds__(FT_THREADS) void redact_kernel(const mhip_redact_t p) {
+    __shared__ __attribute__((aligned(16))) uint8_t pix[FT_TILE * FT_PITCH];
+    __shared__ unsigned short rowsum[FT_TILE * RD_CELLS * 3];
     __shared__ uint8_t val[RD_CELLS * RD_CELLS * 3];
-    __shared__ unsigned long long cov[RD_TILE], ccov[RD_TILE / 2];
-    __shared__ unsigned covh[2][2 * RD_TILE];
-    __shared__ int hits[RD_THREADS][5];
+    __shared__ unsigned long long cov[FT_TILE], ccov[FT_TILE / 2];
+    __shared__ unsigned covh[2][2 * FT_TILE];
+    __shared__ int hits[FT_THREADS][5];
     __shared__ int nhits;
-    const int tid = threadIdx.x, f = blockIdx.z, X0 = blockIdx.x * RD_TILE, Y0 = blockIdx.y * RD_TILE;
-    const int W = p.w, H = p.h, tw = min(RD_TILE, W - X0), th = min(RD_TILE, H - Y0);
+    const int tid = threadIdx.x, f = blockIdx.z, X0 = blockIdx.x * FT_TILE, Y0 = blockIdx.y * FT_TILE;
+    const int W = p.w, H = p.h, tw = min(FT_TILE, W - X0), th = min(FT_TILE, H - Y0);
     const bool inplace = p.dst == p.frames;
     const int n = p.table_n[f];
     const int *tab = p.table + (p.list_off ? (size_t)p.list_off[f] : (size_t)f * p.det_cap) * 5;
     const size_t mpitch = (size_t)((W + 31) >> 5);
     // ---- the frame's regions against this tile: thread (half, row, word) ORs every second hit into its 32 pixels of the coverage map
-    const int row = (tid >> 1) & (RD_TILE - 1), word = tid & 1, half = tid >> 7;
+    const int row = (tid >> 1) & (FT_TILE - 1), word = tid & 1, half = tid >> 7;
     unsigned acc = 0;
     bool any = false;
-    for (int i0 = 0; i0 < n; i0 += RD_THREADS) {
+    for (int i0 = 0; i0 < n; i0 += FT_THREADS) {
         if (tid == 0) nhits = 0;
         __syncthreads();
         if (i0 + tid < n) {
             const int *t = tab + (size_t)(i0 + tid) * 5;
             const int x0 = t[0], y0 = t[1], x1 = t[2], y1 = t[3];
-            if (x0 < X0 + RD_TILE && x1 > X0 && y0 < Y0 + RD_TILE && y1 > Y0) {
+            if (x0 < X0 + FT_TILE && x1 > X0 && y0 < Y0 + FT_TILE && y1 > Y0) {
                 int *h = hits[atomicAdd(&nhits, 1)]; // in any order: the union does not depend on it
                 h[0] = x0; h[1] = y0; h[2] = x1; h[3] = y1; h[4] = t[4];
             }
@@ -219,7 +204,7 @@ __global__ __launch_bounds__(RD_THREADS) void redact_kernel(const mhip_redact_t 
             const int *h = hits[e];
             const int lo = max(h[0], px) - px, hi = min(h[2], px + 32) - px;
             if (y < h[1] || y >= h[3] || hi <= lo) continue;
-            unsigned bits = (hi - lo == 32 ? ~0u : (1u << (hi - lo)) - 1u) << lo;
+            unsigned bits = span_mask(lo, hi - 1);
             if (h[4] >= 0) bits &= p.mask_words[((size_t)h[4] * H + y) * mpitch + (px >> 5)]; // y < y1 <= H; px < x1 <= W
             acc |= bits;
         }
@@ -228,7 +213,7 @@ __global__ __launch_bounds__(RD_THREADS) void redact_kernel(const mhip_redact_t 
     if (inplace && !any) return; // nothing of this tile changes: no pixel is touched
     covh[half][2 * row + word] = acc;
     __syncthreads();
-    if (tid < RD_TILE) {
+    if (tid < FT_TILE) {
         const unsigned long long c = (unsigned long long)(covh[0][2 * tid] | covh[1][2 * tid]) |
                                      ((unsigned long long)(covh[0][2 * tid + 1] | covh[1][2 * tid + 1]) << 32);
         cov[tid] = c;
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(RD_THREADS) void redact_kernel(const mhip_redact_t 
         redact_plane<3>(sf + o, df + o, (size_t)W * 3, tw, th, p.cell_log2, p.mode, f0 | (f1 << 8) | (f2 << 16), cov, any, inplace, pix, rowsum, val);
         return;
     }
-    if (tid < RD_TILE / 2) { // a chroma sample is redacted iff any of its four pixels is: the even bits of the two rows' OR, packed
+    if (tid < FT_TILE / 2) { // a chroma sample is redacted iff any of its four pixels is: the even bits of the two rows' OR, packed
         unsigned long long m = cov[2 * tid] | cov[2 * tid + 1];
         m = (m | (m >> 1)) & 0x5555555555555555ull;
         m = (m | (m >> 1)) & 0x3333333333333333ull;
@@ -263,23 +248,23 @@ __global__ __launch_bounds__(RD_THREADS) void redact_kernel(const mhip_redact_t 
 }
 
 static bool redact_ok(const mhip_redact_t *p) {
-    return p && p->frames && p->dst && p->table && p->table_n && p->stats && p->dets && p->counts && p->n_frames > 0 && p->n_frames <= 65535 &&
-           p->w > 0 && p->h > 0 && p->w <= MHIP_REDACT_MAX_DIM && p->h <= MHIP_REDACT_MAX_DIM &&
-           (p->fmt == 0 || (p->fmt == 1 && !(p->w & 1) && !(p->h & 1) && !(p->nv12_flags & ~3u))) &&
-           p->frame_stride >= (size_t)p->w * p->h * (p->fmt ? 3 : 6) / 2 && (p->list_off || p->det_cap > 0) && p->expand > 0 && p->cls_count >= 0 &&
+    const size_t fb = p ? mhip_frame_bytes(p->w, p->h, p->fmt) : 0;
+    return fb && p->frames && p->dst && p->table && p->table_n && p->stats && p->dets && p->counts && p->n_frames > 0 && p->n_frames <= 65535 &&
+           p->w <= MHIP_REDACT_MAX_DIM && p->h <= MHIP_REDACT_MAX_DIM && mhip_frame_format_ok(p->fmt, p->nv12_flags) && p->frame_stride >= fb &&
+           (p->list_off || p->det_cap > 0) && p->expand > 0 && p->cls_count >= 0 &&
            (p->mode == 0 || p->mode == 1) && p->cell_log2 >= 1 && p->cell_log2 <= 6 && (!p->mask_recs || (p->mask_max > 0 && p->mask_max <= 64)) &&
            ((!p->mask_recs && !p->mask_of) || p->mask_words);
 }
 
 extern "C" int mhip_redact_select(const mhip_redact_t *p) {
     if (!redact_ok(p)) return -1;
-    hipLaunchKernelGGL(redact_select_kernel, dim3((unsigned)p->n_frames), dim3(RD_THREADS), 0, mhip_stream_native(), *p);
+    hipLaunchKernelGGL(redact_select_kernel, dim3((unsigned)p->n_frames), dim3(FT_THREADS), 0, mhip_stream_native(), *p);
     return mhip_check(hipGetLastError(), "redact select");
 }
 
 extern "C" int mhip_redact(const mhip_redact_t *p) {
     if (!redact_ok(p)) return -1;
-    const dim3 g((unsigned)((p->w + RD_TILE - 1) / RD_TILE), (unsigned)((p->h + RD_TILE - 1) / RD_TILE), (unsigned)p->n_frames);
-    hipLaunchKernelGGL(redact_kernel, g, dim3(RD_THREADS), 0, mhip_stream_native(), *p);
+    const dim3 g((unsigned)((p->w + FT_TILE - 1) / FT_TILE), (unsigned)((p->h + FT_TILE - 1) / FT_TILE), (unsigned)p->n_frames);
+    hipLaunchKernelGGL(redact_kernel, g, dim3(FT_THREADS), 0, mhip_stream_native(), *p);
     return mhip_check(hipGetLastError(), "redact");
 }

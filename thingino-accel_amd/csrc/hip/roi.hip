@@ -698,8 +698,8 @@ __global__ __launch_bounds__(256) void roi_rot_crop_kernel(const mhip_roi_t p, c
 }
 
 static bool roi_common_ok(const mhip_roi_t *p) {
-    return p && p->rois && p->n_out && p->w > 0 && p->h > 0 && p->n_frames > 0 && p->slots > 0 && p->expand > 0 && p->min_size >= 1 &&
-           (p->fmt == 0 || (p->fmt == 1 && !(p->w & 1) && !(p->h & 1) && !(p->nv12_flags & ~3u)));
+    return p && p->rois && p->n_out && p->n_frames > 0 && p->slots > 0 && p->expand > 0 && p->min_size >= 1 &&
+           mhip_frame_format_ok(p->fmt, p->nv12_flags) && mhip_frame_bytes(p->w, p->h, p->fmt);
 }
 
 // what the align calls need on top: the fit table (16-byte aligned: it is cleared 16 bytes at a time), a template size and a mask inside it, a target

@@ -328,13 +328,26 @@ MARS_INTERNAL int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int fr
 /* mars_roi.c */
 MARS_INTERNAL void mars_roi_release(mars_model_ext_t *m); /* the ROI table of a model whose device state goes away */
 
-/* mars_stage.c: tail stages.  A new stage's host side starts from a mars_block_t, mars_side_tensor and mars_tail_on_aux */
+/* mars_stage.c: tail stages.  A new stage's host side starts from a mars_block_t, mars_side_tensor and mars_tail_on_aux; one that reads or
+ * writes camera frames from mhip_frame_format_ok / mhip_frame_bytes (csrc/mhip.h), mars_pixel_input and mars_aux_behind_current */
 static inline int mars_scale_ok(float s) { return s > 0 && isfinite(s); }
 /* the device is up and no pipe is open (a pipe's slots own their buffers) */
 static inline mars_error_t mars_stage_guard(const mars_model_ext_t *m) {
     if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     return m->pipe ? MARS_ERR_INVALID_TENSOR : MARS_OK;
 }
+/* a detection tail has left lists for the current batch in HBM */
+static inline int mars_has_dets(const mars_model_ext_t *m) { return m->det_dev && m->det_counts_dev && m->det_cap >= m->batch; }
+/* graph input `input_index` as the target of int8 pixels: three channels, [th][tw][3] (nhwc) or [3][th][tw], dev + frame * stride */
+typedef struct { int tid, nhwc, tw, th; int8_t *dev; size_t stride; } mars_pixel_input_t;
+/* INVALID_TENSOR: no such input, not three int8 channels of a positive size, or (unless geometry_only, which leaves dev and stride alone)
+ * no device buffer whose stride holds a frame */
+MARS_INTERNAL mars_error_t mars_pixel_input(const mars_model_ext_t *m, int input_index, int geometry_only, mars_pixel_input_t *out);
+/* What the selected stream has been given so far -> the auxiliary stream: *ev (created where the slot is empty) is recorded on the selected
+ * stream, then the auxiliary stream is selected and waits for it.  On a failure nothing was enqueued behind the record and the auxiliary
+ * stream is not selected: ALLOC_FAILED (no event: nothing at all was enqueued) or LAYER_FAILED.  After MARS_OK the caller enqueues and
+ * ends with mhip_select_aux(0) */
+MARS_INTERNAL mars_error_t mars_aux_behind_current(void **ev);
 MARS_INTERNAL size_t mars_block_layout(const size_t *sz, int n, size_t *off); /* parts of sz[i] bytes, each aligned to 256: their offsets -> the total */
 /* the block holds `total` bytes (grown: synchronises, *fresh = 1, what it held is gone) and, with_events, its two events exist */
 MARS_INTERNAL mars_error_t mars_block_reserve(mars_block_t *b, size_t total, int with_events, int *fresh);

@@ -53,18 +53,18 @@ mars_error_t mars_hip_motion_grid(int w, int h, int cell, int *gw, int *gh, int 
 
 mars_error_t mars_hip_motion_create(int streams, int w, int h, int format, int cell, mars_hip_motion_t **out) {
     if (!out || streams <= 0) return MARS_ERR_INVALID_FILE;
-    if (format != MARS_HIP_CAMERA_RGB && format != MARS_HIP_CAMERA_NV12) return MARS_ERR_INVALID_FILE;
+    if (!mhip_frame_format_ok(format, 0)) return MARS_ERR_INVALID_FILE; /* (nothing is converted: there are no NV12 flags to give) */
     int gw, gh, pitch;
     const mars_error_t e = mars_hip_motion_grid(w, h, cell, &gw, &gh, &pitch);
     if (e != MARS_OK) return e;
-    if (format == MARS_HIP_CAMERA_NV12 && ((w | h) & 1)) return MARS_ERR_INVALID_FILE;
+    if (!mhip_frame_bytes(w, h, format)) return MARS_ERR_INVALID_FILE; /* an odd NV12 size: the grid call has seen to the rest */
     if (streams > 65535) return MARS_ERR_INVALID_TENSOR;
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     mars_hip_motion_t *m = (mars_hip_motion_t *)calloc(1, sizeof(*m));
     if (!m) return MARS_ERR_ALLOC_FAILED;
     m->streams = streams; m->w = w; m->h = h; m->fmt = format == MARS_HIP_CAMERA_NV12;
     m->cell_log2 = cell_log2(cell); m->gw = gw; m->gh = gh; m->pitch = pitch;
-    m->frame_bytes = (size_t)w * h * (m->fmt ? 3 : 6) / 2;
+    m->frame_bytes = mhip_frame_bytes(w, h, format);
     m->bg = (uint16_t *)mhip_malloc((size_t)streams * gh * gw * sizeof(uint16_t));
     m->init = (int *)mhip_malloc((size_t)streams * sizeof(int));
     m->ev_read_done = mhip_event_create_sync();
@@ -222,11 +222,9 @@ mars_error_t mars_hip_motion_detections_device(mars_model_t *det_model, mars_hip
     mars_error_t e = mars_stage_guard(det);
     if (e != MARS_OK) return e;
     const int B = det->batch;
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < B) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    if (!mars_has_dets(det)) return MARS_ERR_INVALID_TENSOR;                                     /* no detections in HBM */
     if (!m->res.dev || m->res.frames <= 0 || m->res.frames != B) return MARS_ERR_INVALID_TENSOR;    /* no motion call, or one over other frames */
     if ((e = mars_side_reserve(&det->motion, B, sizeof(mars_motion_det_t))) != MARS_OK) return e;
-    if (!det->ev_graph_done) det->ev_graph_done = mhip_event_create_sync();
-    if (!det->ev_graph_done) return MARS_ERR_ALLOC_FAILED;
     mhip_motion_dets_t q;
     dets_record(m, expand, &q);
     q.dets = det->det_dev; q.counts = det->det_counts_dev; q.det_cap = MARS_YOLO_MAX_DET; q.n_entries = B * MARS_YOLO_MAX_DET;
@@ -236,10 +234,8 @@ mars_error_t mars_hip_motion_detections_device(mars_model_t *det_model, mars_hip
      * been given so far, and the detector's next motion call waits for the count (ev_read_done) before it rewrites them */
     det->motion.frames = 0;
     mhip_select_stream(0);
-    if (mhip_event_record(det->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, det->ev_graph_done);
-    if (!rc) rc = mhip_motion_dets(&q);
+    if ((e = mars_aux_behind_current(&det->ev_graph_done)) != MARS_OK) return e;
+    int rc = mhip_motion_dets(&q);
     if (!rc) rc = mhip_event_record(m->ev_read_done);
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;

@@ -288,12 +288,7 @@ static int run_letterbox(const geom_t *g, const uint8_t *rgb_dev, size_t rgb_str
 }
 
 /* ---- NV12 camera frames (include/mars_hip.h: "NV12 camera frames"): Y plane, then interleaved chroma at half resolution, w * h * 3 / 2 bytes */
-#define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
-
-size_t mars_hip_nv12_frame_bytes(int w, int h) {
-    if (w <= 0 || h <= 0 || (w & 1) || (h & 1)) return 0;
-    return (size_t)w * (size_t)h / 2 * 3;
-}
+size_t mars_hip_nv12_frame_bytes(int w, int h) { return mhip_frame_bytes(w, h, MARS_HIP_CAMERA_NV12); }
 
 /* the RGB frames of the two-pass route (mhip_letterbox_nv12 converts into them where the strip kernel is not offered): bytes needed, 0 = none */
 static size_t nv12_scratch_bytes(const geom_t *g, int frames) {
@@ -328,7 +323,7 @@ static uint8_t *nv12_scratch(size_t bytes) {
 /* one NV12 frame -> uint8 RGB [h][w][3]; host pointers, runs on the GPU */
 int mars_yolo_nv12_to_rgb(const unsigned char *nv12, int w, int h, unsigned flags, unsigned char *rgb) {
     const size_t in_b = mars_hip_nv12_frame_bytes(w, h), out_b = in_b * 2;
-    if (!nv12 || !rgb || !in_b || (flags & ~NV12_FLAGS) || !mhip_ready()) return -1;
+    if (!nv12 || !rgb || !in_b || !mhip_frame_format_ok(MARS_HIP_CAMERA_NV12, flags) || !mhip_ready()) return -1;
     const size_t in_pad = (in_b + 255) & ~(size_t)255;
     uint8_t *d = (uint8_t *)mhip_malloc(in_pad + out_b);
     if (!d) return -1;
@@ -343,7 +338,7 @@ int mars_yolo_nv12_to_rgb(const unsigned char *nv12, int w, int h, unsigned flag
 /* mars_yolo_letterbox on one NV12 frame */
 int mars_yolo_letterbox_nv12(const unsigned char *nv12, int w, int h, int tw, int th, int nhwc, unsigned flags, signed char *out) {
     const size_t in_b = mars_hip_nv12_frame_bytes(w, h);
-    if (!nv12 || !out || !in_b || tw <= 0 || th <= 0 || (flags & ~NV12_FLAGS) || !mhip_ready()) return -1;
+    if (!nv12 || !out || !in_b || tw <= 0 || th <= 0 || !mhip_frame_format_ok(MARS_HIP_CAMERA_NV12, flags) || !mhip_ready()) return -1;
     geom_t *g;
     if (geometry(w, h, tw, th, &g)) return -1;
     const size_t in_pad = (in_b + 255) & ~(size_t)255, out_b = (size_t)tw * th * 3, out_pad = (out_b + 255) & ~(size_t)255;
@@ -397,22 +392,12 @@ static mars_error_t preproc_target(mars_model_t *model, int input_index, int w, 
     if (!model || w <= 0 || h <= 0 || frames <= 0 || first_frame < 0) return MARS_ERR_INVALID_FILE;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     if (!m->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
-    if (input_index < 0 || (uint32_t)input_index >= model->header.num_inputs || first_frame + frames > m->batch)
-        return MARS_ERR_INVALID_TENSOR;
-    const uint32_t tid = model->header.input_tensor_ids[input_index]; /* an index, as in mars_get_input() */
-    if (tid >= model->header.num_tensors) return MARS_ERR_INVALID_TENSOR;
-    const int ti = (int)tid;
-    const mars_tensor_t *t = &model->tensors[ti].desc;
-    const int nhwc = t->format == MARS_FORMAT_NHWC;
-    const int th = nhwc ? t->shape[1] : t->shape[2], tw = nhwc ? t->shape[2] : t->shape[3];
-    const int ch = nhwc ? t->shape[3] : t->shape[1];
-    if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0 || !m->mt[ti].dev ||
-        m->mt[ti].stride < (size_t)tw * th * 3)
-        return MARS_ERR_INVALID_TENSOR;
-    if (geometry(w, h, tw, th, g)) return MARS_ERR_LAYER_FAILED;
-    *dst = (int8_t *)m->mt[ti].dev + (size_t)first_frame * m->mt[ti].stride;
-    *dst_stride = m->mt[ti].stride;
-    *nhwc_out = nhwc;
+    mars_pixel_input_t in;
+    if (first_frame + frames > m->batch || mars_pixel_input(m, input_index, 0, &in) != MARS_OK) return MARS_ERR_INVALID_TENSOR;
+    if (geometry(w, h, in.tw, in.th, g)) return MARS_ERR_LAYER_FAILED;
+    *dst = in.dev + (size_t)first_frame * in.stride;
+    *dst_stride = in.stride;
+    *nhwc_out = in.nhwc;
     return MARS_OK;
 }
 
@@ -455,7 +440,7 @@ mars_error_t mars_hip_preprocess_device(mars_model_t *model, int input_index, co
 /* ---- the same two calls for NV12 frames: same checks and error codes; odd sizes and unknown flag bits are refused before any device work */
 mars_error_t mars_hip_preprocess_nv12(mars_model_t *model, int input_index, const unsigned char *nv12_frames, int w, int h, unsigned flags,
                                       int first_frame, int frames) {
-    if (!nv12_frames || (flags & ~NV12_FLAGS) || (w > 0 && h > 0 && !mars_hip_nv12_frame_bytes(w, h))) return MARS_ERR_INVALID_FILE;
+    if (!nv12_frames || !mhip_frame_format_ok(MARS_HIP_CAMERA_NV12, flags) || (w > 0 && h > 0 && !mars_hip_nv12_frame_bytes(w, h))) return MARS_ERR_INVALID_FILE;
     geom_t *g;
     int8_t *dst;
     size_t dst_stride;
@@ -475,7 +460,7 @@ mars_error_t mars_hip_preprocess_nv12(mars_model_t *model, int input_index, cons
 
 mars_error_t mars_hip_preprocess_nv12_device(mars_model_t *model, int input_index, const void *nv12_dev, int w, int h, unsigned flags,
                                              int first_frame, int frames) {
-    if (!nv12_dev || (flags & ~NV12_FLAGS) || (w > 0 && h > 0 && !mars_hip_nv12_frame_bytes(w, h))) return MARS_ERR_INVALID_FILE;
+    if (!nv12_dev || !mhip_frame_format_ok(MARS_HIP_CAMERA_NV12, flags) || (w > 0 && h > 0 && !mars_hip_nv12_frame_bytes(w, h))) return MARS_ERR_INVALID_FILE;
     geom_t *g;
     int8_t *dst;
     size_t dst_stride;

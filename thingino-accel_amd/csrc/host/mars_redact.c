@@ -13,16 +13,13 @@
 #include "mars_hip.h"
 #include "mars_internal.h"
 
-#define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
 #define REDACT_FLAGS (MARS_REDACT_USE_MASKS | MARS_REDACT_SPARE_IDENTIFIED)
 
 /* the checks that need no device and no model, and the defaults resolved into the launch record */
 static mars_error_t redact_opts(const mars_hip_redact_opts_t *o, mhip_redact_t *p) {
     memset(p, 0, sizeof(*p));
     if (!o || o->src_w <= 0 || o->src_h <= 0) return MARS_ERR_INVALID_FILE;
-    if (o->src_format != MARS_HIP_CAMERA_RGB && o->src_format != MARS_HIP_CAMERA_NV12) return MARS_ERR_INVALID_FILE;
-    if (o->src_format == MARS_HIP_CAMERA_NV12 ? ((o->src_flags & ~NV12_FLAGS) || ((o->src_w | o->src_h) & 1)) : o->src_flags != 0)
-        return MARS_ERR_INVALID_FILE;
+    if (!mhip_frame_format_ok(o->src_format, o->src_flags) || !mhip_frame_bytes(o->src_w, o->src_h, o->src_format)) return MARS_ERR_INVALID_FILE;
     if ((o->mode != MARS_REDACT_MOSAIC && o->mode != MARS_REDACT_FILL) || (o->flags & ~REDACT_FLAGS)) return MARS_ERR_INVALID_FILE;
     const int cell = o->cell ? o->cell : 16;
     int lg = 0;
@@ -33,7 +30,7 @@ static mars_error_t redact_opts(const mars_hip_redact_opts_t *o, mhip_redact_t *
         return MARS_ERR_INVALID_FILE;
     if (o->src_w > MHIP_REDACT_MAX_DIM || o->src_h > MHIP_REDACT_MAX_DIM) return MARS_ERR_INVALID_TENSOR;
     p->w = o->src_w; p->h = o->src_h; p->fmt = o->src_format; p->nv12_flags = o->src_flags;
-    p->frame_stride = (size_t)p->w * p->h * (p->fmt ? 3 : 6) / 2;
+    p->frame_stride = mhip_frame_bytes(p->w, p->h, p->fmt);
     p->expand = o->expand != 0 ? o->expand : 1.0f;
     p->min_conf = o->min_conf; p->ident_min = o->ident_min;
     p->cls_first = o->cls_first; p->cls_count = o->cls_count;
@@ -123,7 +120,7 @@ mars_error_t mars_hip_redact_device(mars_model_t *det_model, void *frames_dev, v
     if (!dst_dev) dst_dev = frames_dev;
     const int B = m->batch;
     if (partial_overlap(frames_dev, dst_dev, p.frame_stride * (size_t)B)) return MARS_ERR_INVALID_FILE;
-    if (!m->det_dev || !m->det_counts_dev || m->det_cap < B || B > 65535) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    if (!mars_has_dets(m) || B > 65535) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
     if (opts->flags & MARS_REDACT_USE_MASKS) { /* the native mask results of this batch, on the frames' own grid */
         if (!m->segn.dev || m->segn.frames != B || m->segn_ow != p.w || m->segn_oh != p.h) return MARS_ERR_INVALID_TENSOR;
         p.mask_recs = (const uint8_t *)m->segn.dev + m->segn_rec_off;
@@ -139,9 +136,7 @@ mars_error_t mars_hip_redact_device(mars_model_t *det_model, void *frames_dev, v
     size_t off[3];
     e = mars_block_reserve(&m->redact, mars_block_layout(sz, 3, off), 1, NULL);
     if (e != MARS_OK) return e;
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_redact_done) m->ev_redact_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_redact_done) return MARS_ERR_ALLOC_FAILED;
+    if (!m->ev_redact_done && !(m->ev_redact_done = mhip_event_create_sync())) return MARS_ERR_ALLOC_FAILED;
     uint8_t *blk = (uint8_t *)m->redact.dev;
     p.frames = (const uint8_t *)frames_dev; p.dst = (uint8_t *)dst_dev; p.n_frames = B;
     p.dets = m->det_dev; p.counts = m->det_counts_dev; p.det_cap = MARS_YOLO_MAX_DET;
@@ -152,10 +147,8 @@ mars_error_t mars_hip_redact_device(mars_model_t *det_model, void *frames_dev, v
      * stream has been given so far, and the main stream then waits for the redaction, so that whatever the library enqueues later sees the
      * redacted frames */
     mhip_select_stream(0);
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc) rc = mhip_event_record(m->redact.ev[0]);
+    if ((e = mars_aux_behind_current(&m->ev_graph_done)) != MARS_OK) return e;
+    int rc = mhip_event_record(m->redact.ev[0]);
     if (!rc) rc = mhip_redact_select(&p);
     if (!rc) rc = mhip_redact(&p);
     if (!rc) rc = mhip_event_record(m->redact.ev[1]);

@@ -13,22 +13,18 @@
 #include "mars_hip.h"
 #include "mars_internal.h"
 
-#define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
-
 /* the checks that need no device and no model, and the defaults resolved into the launch record */
 static mars_error_t roi_opts(const mars_hip_roi_opts_t *o, int tw, int th, mhip_roi_t *p) {
     memset(p, 0, sizeof(*p));
     if (!o || o->src_w <= 0 || o->src_h <= 0 || tw <= 0 || th <= 0) return MARS_ERR_INVALID_FILE;
-    if (o->src_format != MARS_HIP_CAMERA_RGB && o->src_format != MARS_HIP_CAMERA_NV12) return MARS_ERR_INVALID_FILE;
-    if (o->src_format == MARS_HIP_CAMERA_NV12 ? ((o->src_flags & ~NV12_FLAGS) || !mars_hip_nv12_frame_bytes(o->src_w, o->src_h)) : o->src_flags != 0)
-        return MARS_ERR_INVALID_FILE;
+    if (!mhip_frame_format_ok(o->src_format, o->src_flags) || !mhip_frame_bytes(o->src_w, o->src_h, o->src_format)) return MARS_ERR_INVALID_FILE;
     if (o->flags & ~(MARS_ROI_KEEP_ASPECT | MARS_ROI_AREA)) return MARS_ERR_INVALID_FILE;
     if (!isfinite(o->expand) || o->expand < 0 || !isfinite(o->min_conf) || o->min_size < 0 || o->cls_count < 0 || o->max_per_frame < 0)
         return MARS_ERR_INVALID_FILE;
     if (!mhip_roi_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
     if ((o->flags & MARS_ROI_AREA) && !mhip_roi_area_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
     p->w = o->src_w; p->h = o->src_h; p->fmt = o->src_format; p->nv12_flags = o->src_flags;
-    p->frame_stride = p->fmt ? mars_hip_nv12_frame_bytes(p->w, p->h) : (size_t)p->w * p->h * 3;
+    p->frame_stride = mhip_frame_bytes(p->w, p->h, p->fmt);
     p->expand = o->expand != 0 ? o->expand : 1.0f;
     p->min_conf = o->min_conf;
     p->min_size = o->min_size ? o->min_size : 2;
@@ -206,20 +202,14 @@ static mars_error_t crop_device(mars_model_t *det_model, const void *frames_dev,
     mars_model_ext_t *det = (mars_model_ext_t *)det_model, *m = (mars_model_ext_t *)dst_model;
     if (!m->act_dev || !det->act_dev || !mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     if (m->pipe || det->pipe) return MARS_ERR_INVALID_TENSOR; /* a pipe's slots own their buffers */
-    if (input_index < 0 || (uint32_t)input_index >= dst_model->header.num_inputs) return MARS_ERR_INVALID_TENSOR;
-    const uint32_t tid = dst_model->header.input_tensor_ids[input_index];
-    if (tid >= dst_model->header.num_tensors) return MARS_ERR_INVALID_TENSOR;
-    const mars_tensor_t *t = &dst_model->tensors[tid].desc;
-    const int nhwc = t->format == MARS_FORMAT_NHWC;
-    const int th = nhwc ? t->shape[1] : t->shape[2], tw = nhwc ? t->shape[2] : t->shape[3], ch = nhwc ? t->shape[3] : t->shape[1];
-    if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0 || !m->mt[tid].dev || m->mt[tid].stride < (size_t)tw * th * 3)
-        return MARS_ERR_INVALID_TENSOR;
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    mars_pixel_input_t in;
+    if (mars_pixel_input(m, input_index, 0, &in) != MARS_OK) return MARS_ERR_INVALID_TENSOR;
+    if (!mars_has_dets(det)) return MARS_ERR_INVALID_TENSOR;                                                /* no detections in HBM */
     if (rot && (!det->obb.dev || det->obb.frames != det->batch)) return MARS_ERR_INVALID_TENSOR;            /* no obb results in HBM */
     if (mode == MODE_ALIGN && (!det->pose.dev || det->pose.frames != det->batch || det->pose_k != align->num_kpt))
         return MARS_ERR_INVALID_TENSOR;                                                                     /* no pose results in HBM, or of another K */
     mhip_roi_t p;
-    const mars_error_t e = mode_opts(mode, opts, align, tw, th, &p);
+    const mars_error_t e = mode_opts(mode, opts, align, in.tw, in.th, &p);
     if (e != MARS_OK) return e;
     if (m->batch > 65535) return MARS_ERR_INVALID_TENSOR;
     if (roi_table(m, m->batch, det->batch, mode == MODE_ALIGN)) return MARS_ERR_ALLOC_FAILED;
@@ -239,7 +229,7 @@ static mars_error_t crop_device(mars_model_t *det_model, const void *frames_dev,
     p.n_out = (int *)m->roi_dev;
     p.rois = (uint8_t *)m->roi_dev + 16;
     p.frame_kept = (int *)((uint8_t *)m->roi_dev + 16 + (size_t)m->roi_cap_slots * sizeof(mars_roi_t));
-    p.out = (int8_t *)m->mt[tid].dev; p.out_stride = m->mt[tid].stride; p.slots = m->batch; p.nhwc = nhwc;
+    p.out = in.dev; p.out_stride = in.stride; p.slots = m->batch; p.nhwc = in.nhwc;
     /* The main stream.  It carries every run of dst_model (the parts of a large batch join it again), so the crops come behind an earlier
      * graph that still reads the input and ahead of the next one.  The detections come from the auxiliary stream: wait for the event the
      * tail recorded there -- the one the next run's head-writing layers of det_model wait for */

@@ -1,8 +1,10 @@
 /*
  * mars_stage.c -- what the stages behind the detection tail share on the host (mars_internal.h, "tail stages"): the result block hung on a
  * model, the per-detection side arrays hung on a detector and the scatter that fills two of them, where the plan left an int8 side tensor,
- * and the scale-keyed tables.  No launch of its own but the scatter's; the stage files (mars_seg.c, mars_pose.c, mars_obb.c, mars_tile.c,
- * mars_redact.c, mars_motion.c, mars_classify.c, mars_gallery.c, mars_track.c) and the table functions of mars_yolo.c are written on top of it.
+ * the scale-keyed tables, the graph input that takes int8 pixels, and the hand-off from the selected stream to the auxiliary one.  No launch
+ * of its own but the scatter's; the stage files (mars_seg.c, mars_pose.c, mars_obb.c, mars_tile.c, mars_redact.c, mars_motion.c, mars_roi.c,
+ * mars_classify.c, mars_gallery.c, mars_track.c), the front-end's target (mars_preproc.c) and the tails and table functions of mars_yolo.c
+ * are written on top of it.
  */
 #include <stdint.h>
 #include <string.h>
@@ -91,22 +93,17 @@ mars_error_t mars_scatter_on_aux(mars_model_ext_t *det, mars_model_ext_t *m, con
     if (m->pipe || det->pipe) return MARS_ERR_INVALID_TENSOR;
     if (!m->roi_dev || m->roi_slots <= 0 || m->roi_from != det) return MARS_ERR_INVALID_TENSOR;             /* no crop call out of det_model */
     if (!src->dev || src->frames <= 0 || src->frames < m->roi_slots) return MARS_ERR_INVALID_TENSOR;        /* no classify / match results */
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
-    const mars_error_t e = mars_side_reserve(side, det->batch, sizeof(mars_cls_t));
+    if (!mars_has_dets(det)) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    mars_error_t e = mars_side_reserve(side, det->batch, sizeof(mars_cls_t));
     if (e != MARS_OK) return e;
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_label_done) m->ev_label_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_label_done) return MARS_ERR_ALLOC_FAILED;
+    if (!m->ev_label_done && !(m->ev_label_done = mhip_event_create_sync())) return MARS_ERR_ALLOC_FAILED;
     /* The auxiliary stream.  It carries every detection tail, every classify tail and every match, so the scatter comes behind both models'
      * tails and ahead of det_model's next detect call and cls_model's next classify call.  The ROI table is written on the main stream: the
      * scatter waits for what that stream has been given so far, and the next crop call into cls_model waits for the scatter (ev_label_done,
      * recorded again by every scatter of either kind) */
     mhip_select_stream(0);
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc)
-        rc = mhip_label_scatter((uint8_t *)m->roi_dev + 16, (const int *)m->roi_dev, m->roi_slots, (const uint8_t *)src->dev + top_off, top_k, side->dev,
+    if ((e = mars_aux_behind_current(&m->ev_graph_done)) != MARS_OK) return e;
+    int rc = mhip_label_scatter((uint8_t *)m->roi_dev + 16, (const int *)m->roi_dev, m->roi_slots, (const uint8_t *)src->dev + top_off, top_k, side->dev,
                                 det->batch, MARS_YOLO_MAX_DET);
     if (!rc) rc = mhip_event_record(m->ev_label_done);
     mhip_select_aux(0);
@@ -134,6 +131,34 @@ mars_error_t mars_side_tensor(const mars_model_ext_t *m, int T, int want_c, int 
     o->base = (const int8_t *)tb->dev + off;
     o->stride = tb->stride;
     return MARS_OK;
+}
+
+/* ---- the graph input that takes int8 pixels (the front-end, the crops, the tiles) */
+_Static_assert(MARS_HIP_CAMERA_RGB == 0 && MARS_HIP_CAMERA_NV12 == 1 && (MARS_NV12_FULL_RANGE | MARS_NV12_VU) == 3u, "mhip_frame_format_ok of csrc/mhip.h");
+mars_error_t mars_pixel_input(const mars_model_ext_t *m, int input_index, int geometry_only, mars_pixel_input_t *o) {
+    if (input_index < 0 || (uint32_t)input_index >= m->pub.header.num_inputs) return MARS_ERR_INVALID_TENSOR;
+    const uint32_t tid = m->pub.header.input_tensor_ids[input_index]; /* an index, as in mars_get_input() */
+    if (tid >= m->pub.header.num_tensors) return MARS_ERR_INVALID_TENSOR;
+    const mars_tensor_t *t = &m->pub.tensors[tid].desc;
+    o->tid = (int)tid;
+    o->nhwc = t->format == MARS_FORMAT_NHWC;
+    o->th = o->nhwc ? t->shape[1] : t->shape[2]; o->tw = o->nhwc ? t->shape[2] : t->shape[3];
+    const int ch = o->nhwc ? t->shape[3] : t->shape[1];
+    if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || o->tw <= 0 || o->th <= 0) return MARS_ERR_INVALID_TENSOR;
+    if (geometry_only) return MARS_OK;
+    if (!m->mt[tid].dev || m->mt[tid].stride < (size_t)o->tw * o->th * 3) return MARS_ERR_INVALID_TENSOR;
+    o->dev = (int8_t *)m->mt[tid].dev; o->stride = m->mt[tid].stride;
+    return MARS_OK;
+}
+
+/* ---- the hand-off to the auxiliary stream */
+mars_error_t mars_aux_behind_current(void **ev) {
+    if (!*ev && !(*ev = mhip_event_create_sync())) return MARS_ERR_ALLOC_FAILED;
+    if (mhip_event_record(*ev)) return MARS_ERR_LAYER_FAILED;
+    mhip_select_aux(1);
+    if (!mhip_stream_wait(1, *ev)) return MARS_OK;
+    mhip_select_aux(0);
+    return MARS_ERR_LAYER_FAILED;
 }
 
 /* ---- scale-keyed tables */

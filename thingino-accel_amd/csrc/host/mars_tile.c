@@ -16,7 +16,6 @@
 _Static_assert(sizeof(mars_tile_t) == 16 && sizeof(mars_tile_src_t) == 8 && sizeof(mars_tile_stats_t) == 24, "the records tile.hip reads and writes");
 _Static_assert(MARS_TILE_MAX_TILES == MHIP_TILE_MAX_TILES && MARS_TILE_MAX_CAND == MHIP_TILE_MAX_CAND, "the kernel's table and candidate sizes");
 
-#define NV12_FLAGS (MARS_NV12_FULL_RANGE | MARS_NV12_VU)
 #define TILE_FLAGS (MARS_TILE_KEEP_ASPECT | MARS_TILE_MATCH_IOS | MARS_TILE_AGNOSTIC | MARS_TILE_AREA)
 
 /* the number of starts of one axis: every k with k * step + tile < W, and the final one */
@@ -49,9 +48,7 @@ static mars_error_t tile_opts(const mars_hip_tile_opts_t *o, int tw, int th, mhi
     memset(p, 0, sizeof(*p));
     if (!o || !o->tiles || o->src_w <= 0 || o->src_h <= 0 || tw <= 0 || th <= 0) return MARS_ERR_INVALID_FILE;
     if (o->n_tiles < 1 || o->n_tiles > MARS_TILE_MAX_TILES) return MARS_ERR_INVALID_FILE;
-    if (o->src_format != MARS_HIP_CAMERA_RGB && o->src_format != MARS_HIP_CAMERA_NV12) return MARS_ERR_INVALID_FILE;
-    if (o->src_format == MARS_HIP_CAMERA_NV12 ? ((o->src_flags & ~NV12_FLAGS) || !mars_hip_nv12_frame_bytes(o->src_w, o->src_h)) : o->src_flags != 0)
-        return MARS_ERR_INVALID_FILE;
+    if (!mhip_frame_format_ok(o->src_format, o->src_flags) || !mhip_frame_bytes(o->src_w, o->src_h, o->src_format)) return MARS_ERR_INVALID_FILE;
     if (o->flags & ~TILE_FLAGS) return MARS_ERR_INVALID_FILE;
     if (!isfinite(o->merge_thresh) || o->merge_thresh < 0 || o->merge_thresh > 1 || !isfinite(o->edge_margin) || o->edge_margin < 0)
         return MARS_ERR_INVALID_FILE;
@@ -92,7 +89,7 @@ static mars_error_t tile_roi(const mars_hip_tile_opts_t *o, int tw, int th, mhip
     if (!mhip_roi_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
     if ((o->flags & MARS_TILE_AREA) && !mhip_roi_area_fits(o->src_w, tw, o->src_format)) return MARS_ERR_INVALID_FILE;
     r->w = o->src_w; r->h = o->src_h; r->fmt = o->src_format; r->nv12_flags = o->src_flags;
-    r->frame_stride = r->fmt ? mars_hip_nv12_frame_bytes(r->w, r->h) : (size_t)r->w * r->h * 3;
+    r->frame_stride = mhip_frame_bytes(r->w, r->h, r->fmt);
     r->expand = 1.0f; r->min_size = 1;
     r->keep_aspect = (o->flags & MARS_TILE_KEEP_ASPECT) != 0;
     r->area = (o->flags & MARS_TILE_AREA) != 0;
@@ -138,17 +135,11 @@ mars_error_t mars_hip_preprocess_tiles_device(mars_model_t *model, int input_ind
     if (e != MARS_OK) return e;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     if ((e = mars_stage_guard(m)) != MARS_OK) return e;
-    if (input_index < 0 || (uint32_t)input_index >= model->header.num_inputs) return MARS_ERR_INVALID_TENSOR;
-    const uint32_t tid = model->header.input_tensor_ids[input_index];
-    if (tid >= model->header.num_tensors) return MARS_ERR_INVALID_TENSOR;
-    const mars_tensor_t *t = &model->tensors[tid].desc;
-    const int nhwc = t->format == MARS_FORMAT_NHWC;
-    const int th = nhwc ? t->shape[1] : t->shape[2], tw = nhwc ? t->shape[2] : t->shape[3], ch = nhwc ? t->shape[3] : t->shape[1];
-    if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0 || !m->mt[tid].dev || m->mt[tid].stride < (size_t)tw * th * 3)
-        return MARS_ERR_INVALID_TENSOR;
+    mars_pixel_input_t in;
+    if ((e = mars_pixel_input(m, input_index, 0, &in)) != MARS_OK) return e;
     if (m->batch % opts->n_tiles || m->batch > 65535) return MARS_ERR_INVALID_TENSOR;
-    e = tile_opts(opts, tw, th, &p);
-    if (e == MARS_OK) e = tile_roi(opts, tw, th, &r);
+    e = tile_opts(opts, in.tw, in.th, &p);
+    if (e == MARS_OK) e = tile_roi(opts, in.tw, in.th, &r);
     if (e != MARS_OK) return e;
     /* (a re-allocation synchronises: a crop queued earlier may still read the old table) */
     if ((e = mars_block_reserve(&m->tile_roi, 256 + (size_t)m->batch * sizeof(mars_roi_t), 0, NULL)) != MARS_OK) return e;
@@ -156,7 +147,7 @@ mars_error_t mars_hip_preprocess_tiles_device(mars_model_t *model, int input_ind
     p.n_out = (int *)m->tile_roi.dev; p.rois = (uint8_t *)m->tile_roi.dev + 256;
     r.frames = (const uint8_t *)frames_dev; r.n_frames = p.cams;
     r.n_out = p.n_out; r.rois = p.rois;
-    r.out = (int8_t *)m->mt[tid].dev; r.out_stride = m->mt[tid].stride; r.slots = m->batch; r.nhwc = nhwc;
+    r.out = in.dev; r.out_stride = in.stride; r.slots = m->batch; r.nhwc = in.nhwc;
     /* the current stream, as mars_hip_preprocess_device: the table first, then the crops that read it */
     return mhip_tile_rois(&p) || mhip_roi_crop(&r) ? MARS_ERR_LAYER_FAILED : MARS_OK;
 }
@@ -169,8 +160,7 @@ mars_error_t mars_hip_preprocess_tiles(mars_model_t *model, int input_index, con
     if (!mhip_ready()) return MARS_ERR_NNA_INIT_FAILED;
     const int B = mars_hip_get_batch(model);
     if (B <= 0 || B % opts->n_tiles) return MARS_ERR_INVALID_TENSOR;
-    const size_t fb = opts->src_format ? mars_hip_nv12_frame_bytes(opts->src_w, opts->src_h) : (size_t)opts->src_w * opts->src_h * 3;
-    const size_t in_b = fb * (size_t)(B / opts->n_tiles);
+    const size_t in_b = mhip_frame_bytes(opts->src_w, opts->src_h, opts->src_format) * (size_t)(B / opts->n_tiles);
     uint8_t *d = (uint8_t *)mhip_malloc(in_b);
     if (!d) return MARS_ERR_ALLOC_FAILED;
     if (mhip_h2d_async(d, frames, in_b)) e = MARS_ERR_LAYER_FAILED;
@@ -224,14 +214,11 @@ mars_error_t mars_hip_merge_tiles_device(mars_model_t *model, const mars_hip_til
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     if ((e = mars_stage_guard(m)) != MARS_OK) return e;
     if (m->batch % opts->n_tiles) return MARS_ERR_INVALID_TENSOR;
-    if (!m->det_dev || !m->det_counts_dev || m->det_cap < m->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
-    if (m->det_mapped) return MARS_ERR_INVALID_TENSOR; /* the lists are in source-frame pixels already */
-    if (model->header.num_inputs < 1 || model->header.input_tensor_ids[0] >= model->header.num_tensors) return MARS_ERR_INVALID_TENSOR;
-    const mars_tensor_t *t = &model->tensors[model->header.input_tensor_ids[0]].desc;
-    const int nhwc = t->format == MARS_FORMAT_NHWC;
-    const int th = nhwc ? t->shape[1] : t->shape[2], tw = nhwc ? t->shape[2] : t->shape[3], ch = nhwc ? t->shape[3] : t->shape[1];
-    if (ch != 3 || t->dtype != MARS_DTYPE_INT8 || tw <= 0 || th <= 0) return MARS_ERR_INVALID_TENSOR;
-    if ((e = tile_opts(opts, tw, th, &p)) != MARS_OK) return e;
+    if (!mars_has_dets(m)) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    if (m->det_mapped) return MARS_ERR_INVALID_TENSOR;   /* the lists are in source-frame pixels already */
+    mars_pixel_input_t in; /* the geometry the tiles were cut for: input 0's */
+    if ((e = mars_pixel_input(m, 0, 1, &in)) != MARS_OK) return e;
+    if ((e = tile_opts(opts, in.tw, in.th, &p)) != MARS_OK) return e;
     const int C = m->batch / p.n_tiles;
     size_t sz[4], off[4];
     tile_parts((size_t)C, sz);

@@ -340,7 +340,7 @@ mars_error_t mars_yolo_track_lists(mars_hip_tracker_t *t, const mars_det_t *dets
 /* The detector's side of a device call, the same with and without a second model: its lists in HBM, the identities where they are carried,
  * the frame -> stream map, room for the results, and the mhip_track_t part of the launch record filled */
 static mars_error_t track_from_detector(mars_model_ext_t *det, const mars_hip_tracker_t *t, const mars_hip_track_opts_t *opts, mhip_track_t *p) {
-    if (!det->det_dev || !det->det_counts_dev || det->det_cap < det->batch) return MARS_ERR_INVALID_TENSOR; /* no detections in HBM */
+    if (!mars_has_dets(det)) return MARS_ERR_INVALID_TENSOR;                                               /* no detections in HBM */
     const int carry = (opts->flags & MARS_TRACK_CARRY_IDENTITY) != 0;
     if (carry && (!det->ident.dev || det->ident.frames < det->batch)) return MARS_ERR_INVALID_TENSOR;      /* no identity scatter */
     mars_error_t e = track_map(p, t, det->batch);
@@ -410,9 +410,7 @@ mars_error_t mars_hip_track_app_device(mars_model_t *det_model, mars_model_t *cl
     if ((e = mars_block_reserve(&det->track_app, mars_block_layout(sz, 3, off), 0, NULL)) != MARS_OK) return e;
     track_app_plane(&a, t);
     if ((e = track_app_scratch(t, &a)) != MARS_OK) return e;
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_label_done) m->ev_label_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_label_done) return MARS_ERR_ALLOC_FAILED;
+    if (!m->ev_label_done && !(m->ev_label_done = mhip_event_create_sync())) return MARS_ERR_ALLOC_FAILED;
     uint8_t *blk = (uint8_t *)det->track_app.dev;
     a.vec = (const int *)((uint8_t *)m->cls.dev + m->cls_sums_off);
     a.n_vec = m->roi_slots; /* every slot's row is quantised; the index below names those below `kept` only */
@@ -423,10 +421,8 @@ mars_error_t mars_hip_track_app_device(mars_model_t *det_model, mars_model_t *cl
      * scatter waits for what that stream has been given so far, and the next crop call into cls_model waits for this call (ev_label_done) */
     det->track.frames = 0;
     mhip_select_stream(0);
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc) rc = mhip_track_app_index((uint8_t *)m->roi_dev + 16, (const int *)m->roi_dev, m->roi_slots, (int *)(blk + off[2]), det->batch, MARS_YOLO_MAX_DET);
+    if ((e = mars_aux_behind_current(&m->ev_graph_done)) != MARS_OK) return e;
+    int rc = mhip_track_app_index((uint8_t *)m->roi_dev + 16, (const int *)m->roi_dev, m->roi_slots, (int *)(blk + off[2]), det->batch, MARS_YOLO_MAX_DET);
     if (!rc) rc = mhip_track_app(&a);
     if (!rc) rc = mhip_event_record(m->ev_label_done);
     mhip_select_aux(0);

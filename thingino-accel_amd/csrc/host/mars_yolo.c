@@ -93,37 +93,29 @@ int mars_detect_launch(mars_model_ext_t *m, const int *output_indices, int n_out
     return mhip_detect(&p);
 }
 
+typedef struct { const int *output_indices; int n_outputs; float nms_thresh; } detect_cfg_t;
+static int detect_launch_cb(mars_model_ext_t *m, const void *cfg, void *dets_dev, int *counts_dev) {
+    const detect_cfg_t *c = (const detect_cfg_t *)cfg;
+    return mars_detect_launch(m, c->output_indices, c->n_outputs, c->nms_thresh, dets_dev, counts_dev);
+}
+
 mars_error_t mars_hip_detect_device(mars_model_t *model, const int *output_indices, int n_outputs, float nms_thresh) {
     if (!model || !output_indices || n_outputs <= 0 || n_outputs > 4) return MARS_ERR_INVALID_TENSOR;
     mars_model_ext_t *m = (mars_model_ext_t *)model;
-    if (m->det_cap < m->batch || !m->det_dev) {
-        if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
-        if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
-        m->det_lut.n = 0;
-    }
+    mars_error_t e = mars_own_det_buffers(m);
+    if (e != MARS_OK) return e;
     for (int s = 0; s < n_outputs; s++) {
         if (!mars_get_output(model, output_indices[s])) return MARS_ERR_INVALID_TENSOR;
         uint32_t ti = model->header.output_tensor_ids[output_indices[s]];
         if (!m->mt[ti].dev) return MARS_ERR_INVALID_TENSOR;
     }
-    mars_error_t e = mars_detect_prepare(m, output_indices, n_outputs);
-    if (e != MARS_OK) return e;
+    if ((e = mars_detect_prepare(m, output_indices, n_outputs)) != MARS_OK) return e;
     /* The tail runs on the auxiliary stream: it starts when the graph launches enqueued so far
      * have finished, and the NEXT run's output-writing layers wait for it (mars_hip_run_device_async),
      * so decode/sort/NMS of batch k overlap the convolutions of batch k+1. */
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_tail_done) m->ev_tail_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_tail_done) return MARS_ERR_ALLOC_FAILED;
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc) rc = mars_detect_launch(m, output_indices, n_outputs, nms_thresh, m->det_dev, m->det_counts_dev);
-    if (!rc) rc = mhip_event_record(m->ev_tail_done);
-    mhip_select_aux(0);
-    if (rc) return MARS_ERR_LAYER_FAILED;
-    m->tail_pending = 1;
-    m->det_mapped = 0;
-    return MARS_OK;
+    const detect_cfg_t c = {output_indices, n_outputs, nms_thresh};
+    if ((e = mars_tail_on_aux(m, detect_launch_cb, &c)) == MARS_OK) m->det_mapped = 0;
+    return e;
 }
 
 mars_error_t mars_hip_detect(mars_model_t *model, const int *output_indices, int n_outputs, float nms_thresh,
@@ -367,7 +359,7 @@ int mars_heads_launch(mars_model_ext_t *m, const mars_heads_cfg_t *c, void *dets
 }
 
 /* the model's own detection buffers, large enough for the current batch */
-static mars_error_t own_det_buffers(mars_model_ext_t *m) {
+mars_error_t mars_own_det_buffers(mars_model_ext_t *m) {
     if (m->det_cap >= m->batch && m->det_dev) return MARS_OK;
     if (mhip_sync()) return MARS_ERR_LAYER_FAILED; /* re-allocation: nothing may be in flight */
     if (ensure_det_buffers(m, m->batch)) return MARS_ERR_ALLOC_FAILED;
@@ -375,19 +367,14 @@ static mars_error_t own_det_buffers(mars_model_ext_t *m) {
     return MARS_OK;
 }
 
-mars_error_t mars_own_det_buffers(mars_model_ext_t *m) { return own_det_buffers(m); }
-
-/* as mars_hip_detect_device: a raw-head decode (launch(m, cfg, dets, counts) on the current stream) runs on the auxiliary stream behind the
- * graph, and the next run's layers that write a tensor it reads wait for it (tail_read, set by the caller) -- the heads of the shipped
- * files are internal tensors, not graph outputs */
+/* a tail (launch(m, cfg, dets, counts) on the current stream: the decode of graph outputs, of raw heads, a later stage's) runs on the
+ * auxiliary stream behind whatever the SELECTED stream has been given (no stream is selected here: the caller's stays), and the next
+ * run's layers that write a tensor it reads wait for it (graph outputs; tail_read, set by the caller, where the heads are internal tensors) */
 mars_error_t mars_tail_on_aux(mars_model_ext_t *m, int (*launch)(mars_model_ext_t *, const void *, void *, int *), const void *cfg) {
-    if (!m->ev_graph_done) m->ev_graph_done = mhip_event_create_sync();
-    if (!m->ev_tail_done) m->ev_tail_done = mhip_event_create_sync();
-    if (!m->ev_graph_done || !m->ev_tail_done) return MARS_ERR_ALLOC_FAILED;
-    if (mhip_event_record(m->ev_graph_done)) return MARS_ERR_LAYER_FAILED;
-    mhip_select_aux(1);
-    int rc = mhip_stream_wait(1, m->ev_graph_done);
-    if (!rc) rc = launch(m, cfg, m->det_dev, m->det_counts_dev);
+    if (!m->ev_tail_done && !(m->ev_tail_done = mhip_event_create_sync())) return MARS_ERR_ALLOC_FAILED;
+    const mars_error_t e = mars_aux_behind_current(&m->ev_graph_done);
+    if (e != MARS_OK) return e;
+    int rc = launch(m, cfg, m->det_dev, m->det_counts_dev);
     if (!rc) rc = mhip_event_record(m->ev_tail_done);
     mhip_select_aux(0);
     if (rc) return MARS_ERR_LAYER_FAILED;
@@ -404,7 +391,7 @@ mars_error_t mars_hip_detect_heads_device(mars_model_t *model, const mars_yolo_h
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     mars_heads_cfg_t c;
     mars_error_t e = mars_heads_resolve(m, heads, &c);
-    if (e == MARS_OK) e = own_det_buffers(m);
+    if (e == MARS_OK) e = mars_own_det_buffers(m);
     if (e == MARS_OK) e = mars_heads_prepare(m, &c);
     if (e != MARS_OK) return e;
     for (int k = 0; k < c.n; k++) m->mt[c.ti[k]].tail_read = 1;
@@ -648,7 +635,7 @@ mars_error_t mars_hip_detect_dfl_device(mars_model_t *model, const mars_yolo_dfl
     mars_model_ext_t *m = (mars_model_ext_t *)model;
     mars_dfl_cfg_t c;
     mars_error_t e = mars_dfl_resolve(m, heads, &c);
-    if (e == MARS_OK) e = own_det_buffers(m);
+    if (e == MARS_OK) e = mars_own_det_buffers(m);
     if (e == MARS_OK) e = mars_dfl_prepare(m, &c);
     if (e != MARS_OK) return e;
     for (int k = 0; k < c.n; k++) m->mt[c.box_buf[k]].tail_read = m->mt[c.cls_buf[k]].tail_read = 1;

@@ -390,6 +390,15 @@ typedef struct {
 } mhip_dfl_heads_t;
 int mhip_detect_dfl(const mhip_dfl_heads_t *p);
 
+/* ---- camera frames, as every stage that reads or writes them takes them (host checks and launchers alike): fmt 0 = RGB [h][w][3], fmt 1 =
+ * NV12 (MARS_HIP_CAMERA_* of include/mars_hip.h; mars_stage.c asserts the values), flags = MARS_NV12_* (bits 0 and 1), legal with NV12 only */
+static inline int mhip_frame_format_ok(int fmt, unsigned flags) { return fmt == 0 ? flags == 0 : fmt == 1 && !(flags & ~3u); }
+/* bytes of one w x h frame; 0: a non-positive size, or an odd one of an NV12 frame */
+static inline size_t mhip_frame_bytes(int w, int h, int fmt) {
+    if (w <= 0 || h <= 0 || (fmt && ((w | h) & 1))) return 0;
+    return fmt ? (size_t)w * (size_t)h / 2 * 3 : (size_t)w * (size_t)h * 3;
+}
+
 /* ---- image front-end (preproc.hip): letterbox resize + (px - 128); tables from csrc/host/mars_preproc.c */
 typedef struct {
     const uint8_t *rgb; size_t rgb_stride;   /* [frames][h][w][3] uint8 on the device (mhip_letterbox_nv12: [frames] NV12 frames) */
