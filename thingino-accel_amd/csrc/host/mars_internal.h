@@ -262,6 +262,65 @@ typedef struct mars_model_ext {
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
+/* ---- launch groups: several planned ops that run as ONE launch.  The flags in mars_op_t are the stored truth (the dump prints them); these
+ * helpers are the only place that reads them for grouping.  Derived on every call, never stored: passes move ops.  Host-only (tests/c/plan_groups.c).
+ * A new form: the enum with its span in form_span and its flags in op_form, its case in conv_i8_group_records / conv_i8_group_fits and in
+ * enqueue_range's switch, one row of alloc_batch's table, one plan_check clause, its pass ("Launch groups"). */
+enum {
+    FORM_PLAIN = 0,   /* {op} */
+    FORM_PAIR,        /* {a, b}: side by side (pair_next; conv_i8_persist<PAIR>) */
+    FORM_BOTH,        /* {a, b}: one tile (pair_both) */
+    FORM_BOTH_CHAIN,  /* {a, b, d}: ... + the 1x1 behind side both_chain */
+    FORM_POST,        /* {a, cv3} (post_next) */
+    FORM_SPLIT,       /* {a, cv1, cv2} (split_next; cv1 keeps its pair_next) */
+    FORM_SPLIT_CHAIN, /* {a, cv1, cv2, d}: ... + the 1x1 behind side split_chain */
+    FORM_PAIR_F32,    /* {a, b}: conv_f32_split's pair form */
+    FORM_BAD,         /* the flags of op i ask for mates beyond n_ops: an error wherever it is met (plan_check lets no such plan through) */
+    FORM_COUNT
+};
+/* members of a form (FORM_BAD has what the plan has left: op_form); a form without an entry has none, so nothing indexes by it */
+static inline int form_span(int form) {
+    static const int span[FORM_COUNT] = {[FORM_PLAIN] = 1, [FORM_PAIR] = 2, [FORM_BOTH] = 2, [FORM_BOTH_CHAIN] = 3, [FORM_POST] = 2, [FORM_SPLIT] = 3,
+                                         [FORM_SPLIT_CHAIN] = 4, [FORM_PAIR_F32] = 2, [FORM_BAD] = 1};
+    return form >= 0 && form < FORM_COUNT ? span[form] : 0;
+}
+/* the form of the launch that STARTS at op i (i is taken to be a head); g[]: its members in plan order, -1 behind them.  FORM_BAD: the ops left */
+static inline int op_form(const mars_model_ext_t *m, int i, int g[4]) {
+    const mars_op_t *o = &m->ops[i];
+    int form = FORM_PLAIN;
+    if (o->split_next) form = o->split_chain ? FORM_SPLIT_CHAIN : FORM_SPLIT;
+    else if (o->post_next) form = FORM_POST;
+    else if (o->pair_next) form = o->kind == OP_CONV_F32 ? FORM_PAIR_F32 : !o->pair_both ? FORM_PAIR : o->both_chain ? FORM_BOTH_CHAIN : FORM_BOTH;
+    int span = form_span(form);
+    if (i + span > m->n_ops) { form = FORM_BAD; span = m->n_ops - i; }
+    for (int k = 0; k < 4; k++) g[k] = k < span ? i + k : -1;
+    return form;
+}
+static inline int op_span(const mars_model_ext_t *m, int i) {
+    int g[4], n = 0;
+    op_form(m, i, g);
+    while (n < 4 && g[n] >= 0) n++;
+    return n;
+}
+/* the head of the launch that owns op i: groups are laid out from op 0 on, so a flag on a mate (cv1 of a split group keeps pair_next) starts nothing */
+static inline int op_head(const mars_model_ext_t *m, int i) {
+    int h = 0;
+    for (int s; h + (s = op_span(m, h)) <= i; h += s) {}
+    return h;
+}
+static inline int op_is_mate(const mars_model_ext_t *m, int i) { return op_head(m, i) != i; }
+/* op i's own flags ask for no mate (not op_span == 1: flags that ask for mates behind the plan's end span the ops left, which may be one) */
+static inline int op_plain(const mars_model_ext_t *m, int i) {
+    int g[4];
+    return op_form(m, i, g) == FORM_PLAIN;
+}
+/* device address of tensor ti for the first frame of the range being enqueued (weights: one copy for every frame), and its frame stride */
+static inline uint8_t *tdev(const mars_model_ext_t *m, int ti) {
+    if (ti < 0 || !m->mt[ti].dev) return NULL;
+    return m->mt[ti].dev + (m->mt[ti].is_weight ? 0 : (size_t)m->frame0 * m->mt[ti].stride);
+}
+static inline size_t tstride(const mars_model_ext_t *m, int ti) { return ti >= 0 ? m->mt[ti].stride : 0; }
+
 
 /* ---- shared between mars_model.c (loader), mars_plan.c (planner) and mars_run.c (run paths); hidden from the library's ABI */
 #define MARS_INTERNAL __attribute__((visibility("hidden")))
@@ -288,14 +347,12 @@ MARS_INTERNAL void blob_read(const mars_model_ext_t *m, size_t off, size_t n, vo
 MARS_INTERNAL int op_reads(const mars_op_t *o, int t);  /* t is one of t_in[0 .. n_in) */
 MARS_INTERNAL int op_writes(const mars_op_t *o, int t); /* t is t_out or one of chain_out[0 .. chain_n) */
 MARS_INTERNAL size_t planned_stride(const mtensor_t *t);
-MARS_INTERNAL void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p);
 MARS_INTERNAL int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t out_stride);
-MARS_INTERNAL int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames);
-MARS_INTERNAL int conv_i8_both_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames);
-MARS_INTERNAL int conv_i8_both_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *d, int side, int frames);
+/* the launch records of a group, for the question "does the device code take it" (live = 0: stand-in addresses, planned strides; the members
+ * are candidates, their flags need not be set yet) and for the launch itself (live = 1: device addresses of the frame range being enqueued) */
+MARS_INTERNAL void conv_i8_group_records(const mars_model_ext_t *m, int form, const mars_op_t *g[4], int side, int frames, int live, mhip_conv_i8_t *p);
+MARS_INTERNAL int conv_i8_group_fits(const mars_model_ext_t *m, int form, const mars_op_t *g[4], int side, int frames);
 MARS_INTERNAL void fuse_both_chain(mars_model_ext_t *m);
-MARS_INTERNAL int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames);
-MARS_INTERNAL int conv_i8_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, const mars_op_t *d, int side, int frames);
 /* ... the passes, in the order build_plan calls them (f32: 0 = the int8 form, 1 = the float32 form) */
 MARS_INTERNAL void plan_layer(mars_model_ext_t *m, int li);
 MARS_INTERNAL void fold_silu(mars_model_ext_t *m, int f32);
@@ -319,8 +376,6 @@ MARS_INTERNAL void pair_convs_f32(mars_model_ext_t *m);
 MARS_INTERNAL void rec_pairs(mars_model_ext_t *m);
 MARS_INTERNAL void virtual_concat_f32(mars_model_ext_t *m);
 MARS_INTERNAL void plan_check(mars_model_ext_t *m);
-/* mars_run.c */
-MARS_INTERNAL void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8_t *p);
 /* mars_preproc.c */
 MARS_INTERNAL int mars_preproc_prepare(int w, int h, int tw, int th); /* gather tables of a letterbox geometry, cached */
 MARS_INTERNAL int mars_preproc_prepare_nv12(int w, int h, int tw, int th, int frames); /* the same + the conversion scratch, where NV12 frames need one */

@@ -223,6 +223,29 @@ mars_error_t upload_params(mars_model_ext_t *m) {
     return MARS_OK;
 }
 
+static mars_error_t replan(mars_model_ext_t *m) {
+    const mars_error_t e = build_plan(m);
+    return e == MARS_OK ? upload_params(m) : e;
+}
+
+/* The fusions alloc_batch takes back for a batch they do not fit, in the order it asks: {the model flag that switches the pass off, how to ask,
+ * the form asked about, the chained form whose launches are asked as that form too}.  The order matters: a chained 1x1 is asked before the
+ * launch it extends (without it the pair may still fit), and the one-tile rows stand behind fuse_split's (a re-plan without it frees pairs
+ * for that form). */
+enum { ASK_VCONCAT, ASK_PRE, ASK_GROUP };
+typedef struct { size_t flag; int ask, form, chained; } take_back_t;
+#define FLAG(f) offsetof(mars_model_ext_t, f)
+static const take_back_t TAKE_BACK[] = {
+    {FLAG(no_vconcat), ASK_VCONCAT, 0, 0},
+    {FLAG(no_bottleneck), ASK_PRE, 0, 0}, /* (level 2) */
+    {FLAG(no_post), ASK_GROUP, FORM_POST, FORM_POST},
+    {FLAG(no_chain), ASK_GROUP, FORM_SPLIT_CHAIN, FORM_SPLIT_CHAIN},
+    {FLAG(no_split), ASK_GROUP, FORM_SPLIT, FORM_SPLIT_CHAIN},
+    {FLAG(no_both_chain), ASK_GROUP, FORM_BOTH_CHAIN, FORM_BOTH_CHAIN},
+    {FLAG(no_both), ASK_GROUP, FORM_BOTH, FORM_BOTH_CHAIN},
+};
+#undef FLAG
+
 mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
     const uint32_t nt = m->pub.header.num_tensors;
     if (m->pipe) mars_hip_pipe_close(&m->pub); /* its slots were sized for the old batch */
@@ -239,107 +262,39 @@ mars_error_t alloc_batch(mars_model_ext_t *m, int n) {
     m->rec_frames = n;
     if (m->no_vconcat || m->no_bottleneck || m->no_post || m->no_split || m->no_chain || m->no_both || m->no_both_chain || rec_replan) {
         m->no_vconcat = m->no_bottleneck = m->no_post = m->no_split = m->no_chain = m->no_both = m->no_both_chain = 0;
-        mars_error_t e = build_plan(m);
-        if (e == MARS_OK) e = upload_params(m);
+        const mars_error_t e = replan(m);
         if (e != MARS_OK) return e;
     }
-    /* segmented (virtual concat) convolutions address their output with 32-bit buffer offsets: if this batch makes
-     * an output tensor of one of them 2 GiB or more, plan again with materialised concats */
-    if (!m->no_vconcat) /* deferred (descriptor-only) ranks take the same decision: it depends on shapes and batch only */
+    /* Every fusion below was accepted on shapes alone (one frame), and its launch has no other form to fall back to: the mates are not launched
+     * on their own, a folded 1x1 has left the plan.  The launchers' limits also depend on the batch (31- / 32-bit output offsets, tile counts):
+     * ask every such launch again for THIS batch and plan again without the fusion if one does not fit.  Each row sees the plan the rows
+     * before it left (deferred, descriptor-only ranks take the same decisions: they depend on shapes and batch only) */
+    for (size_t r = 0; r < sizeof TAKE_BACK / sizeof *TAKE_BACK; r++) {
+        const take_back_t *tb = &TAKE_BACK[r];
+        int *off = (int *)((char *)m + tb->flag);
+        if (*off || (tb->ask == ASK_PRE && m->sw.fusion < 2)) continue;
         for (int i = 0; i < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || op->nseg < 2 || op->t_out < 0) continue;
-            if (planned_stride(&m->mt[op->t_out]) * (size_t)n > vlim) {
-                m->no_vconcat = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
+            const mars_op_t *op = &m->ops[i], *mem[4] = {op, NULL, NULL, NULL};
+            int g[4], fits = 1;
+            if (op->kind != OP_CONV_I8) continue;
+            if (tb->ask == ASK_VCONCAT) { /* segmented convolutions address their output with 32-bit buffer offsets */
+                fits = op->nseg < 2 || op->t_out < 0 || planned_stride(&m->mt[op->t_out]) * (size_t)n <= vlim;
+            } else if (tb->ask == ASK_PRE) {
+                const size_t in_stride = op->t_in[0] >= 0 ? planned_stride(&m->mt[op->t_in[0]]) : 0;
+                fits = !op->pre || op->t_out < 0 || (conv_i8_pre_fits(op, n, in_stride, planned_stride(&m->mt[op->t_out])) && !(blim && (size_t)n > blim));
+            } else {
+                const int form = op_form(m, i, g);
+                if (form != tb->form && form != tb->chained) continue;
+                for (int q = 1; q < form_span(tb->form); q++) mem[q] = &m->ops[g[q]];
+                fits = conv_i8_group_fits(m, tb->form, mem, tb->form == FORM_SPLIT_CHAIN ? op->split_chain : op->both_chain, n);
             }
+            if (fits) continue;
+            *off = 1;
+            const mars_error_t e = replan(m);
+            if (e != MARS_OK) return e;
+            break;
         }
-    /* fused bottlenecks were accepted on geometry alone (one frame, no strides): the launcher's limits also depend on the
-     * batch (32-bit output offsets, tile count).  The 1x1 has left the plan, so a launch that fails would have no
-     * fallback: check every fused launch against THIS batch and plan again without the fusion if one does not fit */
-    if (m->sw.fusion >= 2 && !m->no_bottleneck)
-        for (int i = 0; i < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || !op->pre || op->t_out < 0) continue;
-            const size_t in_stride = op->t_in[0] >= 0 ? planned_stride(&m->mt[op->t_in[0]]) : 0;
-            if (!conv_i8_pre_fits(op, n, in_stride, planned_stride(&m->mt[op->t_out])) || (blim && (size_t)n > blim)) {
-                m->no_bottleneck = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
-            }
-        }
-    /* fused cv3 launches were accepted for one frame: cv3's output is addressed with 31-bit offsets, and the 1x1 is not launched on its own, so a
-     * launch that fails would have no fallback: check every one against THIS batch and plan again without the fusion if one does not fit */
-    if (!m->no_post)
-        for (int i = 0; i + 1 < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || !op->post_next) continue;
-            if (!conv_i8_post_fits(m, op, op + 1, n)) {
-                m->no_post = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
-            }
-        }
-    /* the 1x1 chained to a fused cv1 + cv2 launch likewise (its output's 31-bit offsets); asked first: without it the pair may still fit */
-    if (!m->no_chain)
-        for (int i = 0; i + 3 < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || !op->split_next || !op->split_chain) continue;
-            if (!conv_i8_chain_fits(m, op, op + 1, op + 2, op + 3, op->split_chain, n)) {
-                m->no_chain = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
-            }
-        }
-    /* fused cv1 + cv2 launches likewise: either side's output is addressed with 31-bit offsets */
-    if (!m->no_split)
-        for (int i = 0; i + 2 < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || !op->split_next) continue;
-            if (!conv_i8_split_fits(m, op, op + 1, op + 2, n)) {
-                m->no_split = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
-            }
-        }
-    /* the 1x1 chained to a one-tile pair likewise (its output's 31-bit offsets; an elided side has no launch of its own to fall back to); asked
-     * first: without it the pair may still fit.  Both behind the checks above: a re-plan without fuse_split frees pairs for this form */
-    if (!m->no_both_chain)
-        for (int i = 0; i + 2 < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || !op->pair_both || !op->both_chain) continue;
-            if (!conv_i8_both_chain_fits(m, op, op + 1, op + 2, op->both_chain, n)) {
-                m->no_both_chain = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
-            }
-        }
-    /* one-tile pairs likewise (either side's output, 31-bit offsets): a pair over a virtual concat exists for that form alone */
-    if (!m->no_both)
-        for (int i = 0; i + 1 < m->n_ops; i++) {
-            const mars_op_t *op = &m->ops[i];
-            if (op->kind != OP_CONV_I8 || !op->pair_both) continue;
-            if (!conv_i8_both_fits(m, op, op + 1, n)) {
-                m->no_both = 1;
-                mars_error_t e = build_plan(m);
-                if (e == MARS_OK) e = upload_params(m);
-                if (e != MARS_OK) return e;
-                break;
-            }
-        }
+    }
     free_device_state(m);
     size_t per_frame = 0;
     for (uint32_t i = 0; i < nt; i++) {

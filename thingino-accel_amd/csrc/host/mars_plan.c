@@ -668,8 +668,8 @@ static void lut2_from_lut(mars_model_ext_t *m, mars_op_t *c, const int8_t *tab) 
     if (c->lut2_off != NO_OFF) memcpy(m->arena_host + c->lut2_off, tab2, 512);
 }
 
-/* the geometry half of a conv_i8 launch record (conv_i8_params adds addresses, strides and the epilogue's operands) */
-void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p) {
+/* the geometry half of a conv_i8 launch record (conv_i8_record adds addresses, strides and the epilogue's operands) */
+static void conv_i8_geometry(const mars_op_t *op, int frames, mhip_conv_i8_t *p) {
     memset(p, 0, sizeof(*p));
     p->frames = frames;
     p->in_c = op->in_c; p->in_h = op->in_h; p->in_w = op->in_w;
@@ -689,90 +689,112 @@ int conv_i8_pre_fits(const mars_op_t *op, int frames, size_t in_stride, size_t o
     return mhip_conv_i8_pre_ok(&p);
 }
 
-/* does the device code take convolution `a` with the 1 x 1 `b` behind it evaluated in the same launch (fuse_post), at this batch?  Geometry and
- * the planned frame strides only: the operands only need to be non-null */
-int conv_i8_post_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames) {
-    mhip_conv_i8_t p;
-    if (a->t_in[0] < 0 || a->t_out < 0 || b->t_out < 0) return 0;
-    conv_i8_geometry(a, frames, &p);
-    p.in_stride = planned_stride(&m->mt[a->t_in[0]]); p.out_stride = planned_stride(&m->mt[a->t_out]);
-    p.lut = p.lut2 = p.post_lut2 = (const uint8_t *)a;
-    p.post_w = p.post_in = (const int8_t *)a; p.post_out = (int8_t *)m;
-    if (a->add_t) p.add = (const int8_t *)a;
-    p.post_out_stride = planned_stride(&m->mt[b->t_out]);
-    p.post_out_pix_stride = b->out_pix_stride; p.post_out_ch_off = b->out_ch_off;
-    return mhip_conv_i8_post_ok(&p);
+/* ---- the launch records of a group, built in ONE place for the question "does the device code take it at this batch?" (shape-only) and for the
+ * launch itself (live), so that the record asked about is the record launched.  Shape-only: an operand's address is a stand-in -- non-null,
+ * another one for another tensor (the queries compare outputs) -- and its stride the one alloc_batch will give. */
+typedef struct { const mars_model_ext_t *m; int frames, live; } rec_ctx_t;
+static uint8_t *rec_addr(const rec_ctx_t *c, int ti) {
+    if (c->live) return tdev(c->m, ti);
+    return ti >= 0 ? (uint8_t *)c->m->mt + ti : NULL;
 }
-
-/* the shape-only launch records of a one-tile pair (operands: any distinct non-null addresses) */
-static int both_records(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames, mhip_conv_i8_t p[2]) {
-    const mars_op_t *o[2] = {a, b};
-    if (a->t_out < 0 || b->t_out < 0 || a->lut2_off == NO_OFF || b->lut2_off == NO_OFF || a->nchw || b->nchw)
-        return 0;
-    for (int k = 0; k < 2; k++) {
-        conv_i8_geometry(o[k], frames, &p[k]);
-        p[k].in = (const int8_t *)m;
-        p[k].in_stride = o[k]->t_in[0] >= 0 ? planned_stride(&m->mt[o[k]->t_in[0]]) : 0;
-        p[k].out = (int8_t *)m + k; p[k].out_stride = planned_stride(&m->mt[o[k]->t_out]);
-        p[k].lut = p[k].lut2 = (const uint8_t *)m;
-        if (o[k]->add_t) p[k].add = (const int8_t *)m;
-        p[k].nseg = o[k]->nseg; p[k].seg_up = o[k]->seg_up;
-        int c0 = 0;
-        for (int q = 0; q < 4; q++) {
-            p[k].seg_c0[q] = 0x7fffffff;
-            if (q < o[k]->nseg) {
-                p[k].seg_in[q] = (const int8_t *)m;
-                p[k].seg_stride[q] = o[k]->seg_t[q] >= 0 ? planned_stride(&m->mt[o[k]->seg_t[q]]) : 0;
-                p[k].seg_c[q] = o[k]->seg_c[q];
-                p[k].seg_c0[q] = c0;
-                c0 += o[k]->seg_c[q];
-            }
+static size_t rec_stride(const rec_ctx_t *c, int ti) { return c->live ? tstride(c->m, ti) : ti >= 0 ? planned_stride(&c->m->mt[ti]) : 0; }
+/* an entry of the parameter arena; `image`: one of the fused forms' weight images, which a candidate has not reserved yet */
+static const uint8_t *rec_param(const rec_ctx_t *c, size_t off, int image) {
+    if (!c->live) return image || off != NO_OFF ? (const uint8_t *)c->m->mt : NULL;
+    return off != NO_OFF ? c->m->arena_dev + off : NULL;
+}
+/* one member's own record; unwritten: its result never reaches memory (the head of a post / split launch), so its tensor has no buffer */
+static void conv_i8_record(const rec_ctx_t *c, const mars_op_t *op, int unwritten, mhip_conv_i8_t *p) {
+    conv_i8_geometry(op, c->frames, p);
+    p->in = (const int8_t *)rec_addr(c, op->t_in[0]); p->in_stride = rec_stride(c, op->t_in[0]);
+    p->out = (int8_t *)rec_addr(c, op->t_out); p->out_stride = rec_stride(c, op->t_out);
+    if (c->live && p->in) p->in += op->in_byte_off;   /* (a row range of the tensors: virtual_concat_q) */
+    if (c->live && p->out) p->out += op->out_byte_off;
+    p->w = (const int8_t *)rec_param(c, op->w_off, 0);
+    p->bias = (const int32_t *)rec_param(c, op->b_off, 0);
+    p->lut = rec_param(c, op->lut_off, 0);
+    p->lut2 = op->lut_off != NO_OFF ? rec_param(c, op->lut2_off, 0) : NULL;
+    p->w_rgb = !op->w2_rows ? (const int8_t *)rec_param(c, op->w2_off, 0) : NULL;
+    p->w_rows = op->w2_rows ? (const int8_t *)rec_param(c, op->w2_off, 0) : NULL;
+    if (op->pre) {
+        p->pre_w = (const int8_t *)rec_param(c, op->pre_w_off, 0);
+        p->pre_bias = (const int32_t *)rec_param(c, op->pre_b_off, 0);
+        p->pre_lut2 = rec_param(c, op->pre_lut2_off, 0);
+        p->pre_cs = op->pre_cs;
+    }
+    p->cs = op->cs; p->relu = op->relu; p->out_nchw = op->out_nchw;
+    p->variant = op->variant;
+    if (unwritten && op->t_out >= 0) p->out_stride = planned_stride(&c->m->mt[op->t_out]); /* (never allocated: the Add's operand has its layout) */
+    if (op->add_t && (!c->live || rec_stride(c, op->add_t - 1) == p->out_stride)) { /* (the planner guarantees equal strides: launch_op) */
+        p->add = (const int8_t *)rec_addr(c, op->add_t - 1);
+        p->add_s_conv = op->add_s_conv; p->add_s_other = op->add_s_other; p->add_inv = op->add_inv;
+    }
+    p->nseg = op->nseg;
+    p->seg_up = op->seg_up;
+    int c0 = 0;
+    for (int k = 0; k < 4; k++) {
+        p->seg_c0[k] = 0x7fffffff;
+        if (k < op->nseg) {
+            p->seg_in[k] = (const int8_t *)rec_addr(c, op->seg_t[k]);
+            p->seg_stride[k] = rec_stride(c, op->seg_t[k]);
+            p->seg_c[k] = op->seg_c[k];
+            p->seg_c0[k] = c0;
+            c0 += op->seg_c[k];
         }
     }
-    return 1;
+    if (op->nseg > 1) p->in = p->seg_in[0];
 }
-/* does the device code take the pair `a`, `b` (same input) in its one-tile form (pair_convs, pair_both), at this batch? */
-int conv_i8_both_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, int frames) {
-    mhip_conv_i8_t p[2];
-    return both_records(m, a, b, frames, p) && mhip_conv_i8_both_ok(&p[0], &p[1]);
+/* g[]: the members (candidates: their flags need not be set), side: the chained 1x1's (FORM_SPLIT_CHAIN).  The tile walkers' forms (pair, one
+ * tile, + chain) get a record per member, p[k] for g[k]; the patch-staged ones (post, split, + chain) one record, p[0], that carries the mates */
+void conv_i8_group_records(const mars_model_ext_t *m, int form, const mars_op_t *g[4], int side, int frames, int live, mhip_conv_i8_t *p) {
+    const rec_ctx_t c = {m, frames, live};
+    const int patch = form == FORM_POST || form == FORM_SPLIT || form == FORM_SPLIT_CHAIN;
+    conv_i8_record(&c, g[0], patch, &p[0]);
+    if (!patch) {
+        for (int k = 1; k < form_span(form); k++) conv_i8_record(&c, g[k], 0, &p[k]);
+        return;
+    }
+    if (form == FORM_POST) {
+        const mars_op_t *cv3 = g[1];
+        p->post_w = (const int8_t *)rec_param(&c, g[0]->post_w_off, 1);
+        p->post_lut2 = rec_param(&c, cv3->lut2_off, 0);
+        p->post_cs = cv3->cs;
+        p->post_in = (const int8_t *)rec_addr(&c, cv3->seg_t[1]); p->post_in_stride = rec_stride(&c, cv3->seg_t[1]);
+        p->post_out = (int8_t *)rec_addr(&c, cv3->t_out); p->post_out_stride = rec_stride(&c, cv3->t_out);
+        if (live && p->post_out) p->post_out += cv3->out_byte_off;
+        p->post_out_pix_stride = cv3->out_pix_stride; p->post_out_ch_off = cv3->out_ch_off;
+        return;
+    }
+    p->split_w = (const int8_t *)rec_param(&c, g[0]->split_w_off, 1);
+    for (int k = 0; k < 2; k++) {
+        p->split_lut2[k] = rec_param(&c, g[1 + k]->lut2_off, 0);
+        p->split_cs[k] = g[1 + k]->cs;
+        p->split_out[k] = (int8_t *)rec_addr(&c, g[1 + k]->t_out); p->split_out_stride[k] = rec_stride(&c, g[1 + k]->t_out);
+    }
+    if (form == FORM_SPLIT_CHAIN) {
+        p->chain_side = side;
+        p->chain_w = (const int8_t *)rec_param(&c, g[0]->chain_w_off, 1);
+        p->chain_lut2 = rec_param(&c, g[3]->lut2_off, 0);
+        p->chain_cs = g[3]->cs;
+        p->chain_out = (int8_t *)rec_addr(&c, g[3]->t_out); p->chain_out_stride = rec_stride(&c, g[3]->t_out);
+    }
 }
-/* ... and with the 1 x 1 `d` behind them, which reads side `side` - 1, chained into that launch (fuse_both_chain)? */
-int conv_i8_both_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *d, int side, int frames) {
-    mhip_conv_i8_t p[2], pd;
-    if (d->t_out < 0 || d->lut2_off == NO_OFF || d->nchw || !both_records(m, a, b, frames, p)) return 0;
-    conv_i8_geometry(d, frames, &pd);
-    pd.in = (const int8_t *)m; pd.out = (int8_t *)m + 2;
-    pd.in_stride = planned_stride(&m->mt[(side == 1 ? a : b)->t_out]); pd.out_stride = planned_stride(&m->mt[d->t_out]);
-    pd.lut = pd.lut2 = (const uint8_t *)m;
-    if (d->add_t) pd.add = (const int8_t *)m;
-    pd.nseg = d->nseg;
-    return mhip_conv_i8_both_chain_ok(&p[0], &p[1], &pd, side);
-}
-
-/* does the device code take convolution `a` with the paired 1 x 1s `b` and `c` behind it evaluated in the same launch (fuse_split), at this batch? */
-int conv_i8_split_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, int frames) {
-    mhip_conv_i8_t p;
-    if (a->t_in[0] < 0 || a->t_out < 0 || b->t_out < 0 || c->t_out < 0) return 0;
-    conv_i8_geometry(a, frames, &p);
-    p.in_stride = planned_stride(&m->mt[a->t_in[0]]); p.out_stride = planned_stride(&m->mt[a->t_out]);
-    p.lut = p.lut2 = p.split_lut2[0] = p.split_lut2[1] = (const uint8_t *)a;
-    p.split_w = (const int8_t *)a; p.split_out[0] = p.split_out[1] = (int8_t *)m;
-    p.split_out_stride[0] = planned_stride(&m->mt[b->t_out]); p.split_out_stride[1] = planned_stride(&m->mt[c->t_out]);
-    return mhip_conv_i8_split_ok(&p);
-}
-
-/* ... and with the 1 x 1 `d` behind them, which reads side `side` - 1 of the pair, chained into that launch as well (fuse_split_chain)? */
-int conv_i8_chain_fits(const mars_model_ext_t *m, const mars_op_t *a, const mars_op_t *b, const mars_op_t *c, const mars_op_t *d, int side, int frames) {
-    mhip_conv_i8_t p;
-    if (a->t_in[0] < 0 || a->t_out < 0 || b->t_out < 0 || c->t_out < 0 || d->t_out < 0 || (side != 1 && side != 2)) return 0;
-    conv_i8_geometry(a, frames, &p);
-    p.in_stride = planned_stride(&m->mt[a->t_in[0]]); p.out_stride = planned_stride(&m->mt[a->t_out]);
-    p.lut = p.lut2 = p.split_lut2[0] = p.split_lut2[1] = p.chain_lut2 = (const uint8_t *)a;
-    p.split_w = p.chain_w = (const int8_t *)a;
-    p.split_out[0] = (int8_t *)m; p.split_out[1] = (int8_t *)m + 1; p.chain_out = (int8_t *)m + 2; /* (three tensors: any three addresses) */
-    p.split_out_stride[0] = planned_stride(&m->mt[b->t_out]); p.split_out_stride[1] = planned_stride(&m->mt[c->t_out]);
-    p.chain_side = side; p.chain_out_stride = planned_stride(&m->mt[d->t_out]);
-    return mhip_conv_i8_split_ok(&p);
+/* does the device code take the group in this form at this batch?  The passes ask for one frame before they set a flag, alloc_batch asks
+ * again for its batch.  (The side-by-side pair has no query: its launch steps aside at run time.) */
+int conv_i8_group_fits(const mars_model_ext_t *m, int form, const mars_op_t *g[4], int side, int frames) {
+    mhip_conv_i8_t p[3];
+    const int tile = form == FORM_BOTH || form == FORM_BOTH_CHAIN;
+    for (int k = 0; k < form_span(form); k++)
+        if (g[k]->t_out < 0 || (tile && g[k]->nchw)) return 0;
+    if ((!tile && g[0]->t_in[0] < 0) || ((form == FORM_BOTH_CHAIN || form == FORM_SPLIT_CHAIN) && side != 1 && side != 2)) return 0;
+    conv_i8_group_records(m, form, g, side, frames, 0, p);
+    switch (form) {
+        case FORM_POST: return mhip_conv_i8_post_ok(&p[0]);
+        case FORM_SPLIT: case FORM_SPLIT_CHAIN: return mhip_conv_i8_split_ok(&p[0]);
+        case FORM_BOTH: return mhip_conv_i8_both_ok(&p[0], &p[1]);
+        case FORM_BOTH_CHAIN: return mhip_conv_i8_both_chain_ok(&p[0], &p[1], &p[2], side);
+        default: return 0;
+    }
 }
 
 /* ------------------------------------------------------------------ fusion
@@ -1136,8 +1158,9 @@ void virtual_concat_q(mars_model_ext_t *m) {
         }
         if (bad || r <= i || nr < 1 || nr > 2) continue;
         /* one reader, or the two of a paired launch (a head C3's cv1 + cv2: both are split, both halves stay pairs) */
-        const int np = m->ops[r].pair_next ? 2 : 1;
-        if (nr != np || (r > 0 && m->ops[r - 1].pair_next) || (np == 2 && (r + 1 >= m->n_ops || m->ops[r + 1].t_in[0] != T || m->ops[r + 1].pair_next))) continue;
+        int g[4];
+        const int form = op_form(m, r, g), np = op_span(m, r);
+        if ((form != FORM_PLAIN && form != FORM_PAIR && form != FORM_BOTH) || nr != np || op_is_mate(m, r) || (np == 2 && m->ops[r + 1].t_in[0] != T)) continue;
         int ok = 1;
         for (int q = 0; q < np && ok; q++) {
             const mars_op_t *cv = &m->ops[r + q];
@@ -1277,8 +1300,7 @@ void fuse_bottleneck(mars_model_ext_t *m) {
         if (a->kh != 1 || a->kw != 1 || a->sh != 1 || a->sw != 1 || a->nchw || b->nchw || a->out_nchw || b->out_nchw || !a->safe || !b->safe || a->nseg || b->nseg ||
             a->add_t || a->n_in != 1 || a->out_pix_stride || a->relu || a->lut2_off == NO_OFF || b->lut2_off == NO_OFF ||
             a->in_c != a->out_c || a->out_c != b->in_c || (a->in_c != 32 && a->in_c != 64) || b->sh != 1 || b->sw != 1 ||
-            a->in_h != b->in_h || a->in_w != b->in_w || a->b_off == NO_OFF || a->pair_next || b->pair_next ||
-            (i > 0 && m->ops[i - 1].pair_next))
+            a->in_h != b->in_h || a->in_w != b->in_w || a->b_off == NO_OFF || !op_plain(m, i) || !op_plain(m, i + 1) || op_is_mate(m, i))
             continue;
         const int X = a->t_in[0];
         if (X < 0 || X == b->t_out || m->mt[X].is_weight) continue;
@@ -1308,9 +1330,7 @@ void fuse_post(mars_model_ext_t *m) {
     if (!use_counts(m, &readers, &writers)) return;
     for (int i = 0; i + 1 < m->n_ops; i++) {
         mars_op_t *a = &m->ops[i], *b = &m->ops[i + 1];
-        if (a->kind != OP_CONV_I8 || b->kind != OP_CONV_I8 || a->pre || b->pre || a->post_next || b->post_next || a->pair_next || b->pair_next ||
-            (i > 0 && (m->ops[i - 1].pair_next || m->ops[i - 1].post_next)))
-            continue;
+        if (a->kind != OP_CONV_I8 || b->kind != OP_CONV_I8 || a->pre || b->pre || !op_plain(m, i) || !op_plain(m, i + 1) || op_is_mate(m, i)) continue;
         const int c = a->out_c, T = a->t_out, O = b->t_out;
         if ((c != 32 && c != 64) || a->oc_pad != c || a->kh * a->kw < 2 || a->sh != 1 || a->sw != 1 || !a->safe || a->nchw || a->out_nchw || a->nseg ||
             a->out_pix_stride || a->out_ch_off || a->store_c || a->chain_n || a->in_byte_off || a->out_byte_off || a->lut_off == NO_OFF ||
@@ -1326,7 +1346,8 @@ void fuse_post(mars_model_ext_t *m) {
             m->mt[T].is_weight || m->mt[T].tail_read || m->mt[Y].is_weight || m->mt[Y].pix_stride ||
             m->mt[Y].bytes != (size_t)a->out_h * a->out_w * c || op_reads(a, O) || op_reads(a, Y))
             continue;
-        if (!conv_i8_post_fits(m, a, b, 1)) continue; /* one frame: alloc_batch asks again for its batch */
+        const mars_op_t *g[4] = {a, b};
+        if (!conv_i8_group_fits(m, FORM_POST, g, 0, 1)) continue;
         const size_t bytes = mhip_conv_i8_post_pack(c, NULL, NULL, NULL);
         const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
         if (off == NO_OFF) break;
@@ -1350,11 +1371,13 @@ void fuse_post(mars_model_ext_t *m) {
  * carries split_next and is launched, B (which keeps pair_next) and C are skipped.  B and C write dense tensors: pair_convs forms no pair that
  * writes a channel slice, and one that has been given a byte offset or padded rows is declined here.  Only where the device code takes it
  * (mhip_conv_i8_split_ok); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_split). */
-static int split_mate_ok(const mars_op_t *b, const mars_op_t *a, int T) {
-    return b->kind == OP_CONV_I8 && b->kh == 1 && b->kw == 1 && b->sh == 1 && b->sw == 1 && !b->pt && !b->pl && b->safe && !b->nchw && !b->out_nchw && !b->add_t &&
-           !b->chain_n && !b->store_c && !b->in_byte_off && !b->out_byte_off && !b->out_pix_stride && !b->out_ch_off && b->lut_off != NO_OFF &&
-           b->lut2_off != NO_OFF && !b->nseg && !b->pre && !b->post_next && !b->split_next && b->n_in == 1 && b->t_in[0] == T && b->in_c == 64 &&
-           b->out_c == 32 && b->oc_pad == 32 && b->row_pad == 64 && b->in_h == a->out_h && b->in_w == a->out_w && b->out_h == a->out_h && b->out_w == a->out_w;
+/* the mate every fused 1x1 form takes: a plain SiLU 1 x 1 from in_c to out_c channels over a's output map, dense on both sides, with a half-step
+ * table.  Shape only: whether d is free (no head, no mate of another launch) and which tensor it reads is the caller's question */
+static int free_1x1_ok(const mars_op_t *d, const mars_op_t *a, int in_c, int out_c) {
+    return d->kind == OP_CONV_I8 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && !d->pt && !d->pl && d->safe && !d->nchw && !d->out_nchw && !d->add_t &&
+           !d->chain_n && !d->store_c && !d->in_byte_off && !d->out_byte_off && !d->out_pix_stride && !d->out_ch_off && d->lut_off != NO_OFF &&
+           d->lut2_off != NO_OFF && !d->nseg && !d->pre && d->n_in == 1 && d->in_c == in_c && d->out_c == out_c && d->oc_pad == out_c && d->row_pad == in_c &&
+           d->in_h == a->out_h && d->in_w == a->out_w && d->out_h == a->out_h && d->out_w == a->out_w;
 }
 void fuse_split(mars_model_ext_t *m) {
     if (m->sw.no_split || m->no_split) return;
@@ -1362,20 +1385,20 @@ void fuse_split(mars_model_ext_t *m) {
     if (!use_counts(m, &readers, &writers)) return;
     for (int i = 0; i + 2 < m->n_ops; i++) {
         mars_op_t *a = &m->ops[i], *b = &m->ops[i + 1], *c = &m->ops[i + 2];
-        if (a->kind != OP_CONV_I8 || a->pre || a->post_next || a->split_next || a->pair_next || !b->pair_next || c->pair_next ||
-            (i > 0 && (m->ops[i - 1].pair_next || m->ops[i - 1].post_next)))
-            continue;
+        int gi[4];
+        if (a->kind != OP_CONV_I8 || a->pre || !op_plain(m, i) || op_form(m, i + 1, gi) != FORM_PAIR || !op_plain(m, i + 2) || op_is_mate(m, i)) continue;
         const int T = a->t_out;
         if (a->out_c != 64 || a->oc_pad != 64 || a->kh * a->kw < 2 || (a->sh != 1 && a->sh != 2) || a->sw != a->sh || !a->safe || a->nchw || a->out_nchw ||
             a->nseg || a->out_pix_stride || a->out_ch_off || a->store_c || a->chain_n || a->in_byte_off || a->out_byte_off || a->add_t ||
             a->lut_off == NO_OFF || a->lut2_off == NO_OFF || a->n_in != 1)
             continue;
-        if (T < 0 || !split_mate_ok(b, a, T) || !split_mate_ok(c, a, T)) continue;
+        if (T < 0 || !free_1x1_ok(b, a, 64, 32) || !free_1x1_ok(c, a, 64, 32) || b->t_in[0] != T || c->t_in[0] != T) continue;
         const int O0 = b->t_out, O1 = c->t_out;
         if (O0 < 0 || O1 < 0 || O0 == O1 || O0 == T || O1 == T || readers[T] != 2 || writers[T] != 1 || m->mt[T].io_in || m->mt[T].io_out ||
             m->mt[T].is_weight || m->mt[T].tail_read || m->mt[O0].pix_stride || m->mt[O1].pix_stride || op_reads(a, O0) || op_reads(a, O1))
             continue;
-        if (!conv_i8_split_fits(m, a, b, c, 1)) continue; /* one frame: alloc_batch asks again for its batch */
+        const mars_op_t *g[4] = {a, b, c};
+        if (!conv_i8_group_fits(m, FORM_SPLIT, g, 0, 1)) continue;
         const size_t bytes = mhip_conv_i8_split_pack(NULL, NULL, NULL, NULL, NULL);
         const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
         if (off == NO_OFF) break;
@@ -1390,53 +1413,64 @@ void fuse_split(mars_model_ext_t *m) {
     free(readers);
 }
 
+/* op `from` moves up to position `to` (<= from); the ops in between move one down */
+static void move_up(mars_model_ext_t *m, int to, int from) {
+    const mars_op_t moved = m->ops[from];
+    memmove(&m->ops[to + 1], &m->ops[to], sizeof(mars_op_t) * (size_t)(from - to));
+    m->ops[to] = moved;
+}
+
+/* The search both chain passes share.  The launch at i has the members of `form` but the last; its two sides are the last two of them.  D = the
+ * first free 1 x 1 from c to c channels, at most 48 ops behind i, that reads exactly one side, writes a plain tensor of its own that only it
+ * writes, may move up behind the members under pair_up's rule (nothing in between touches its output or writes its input), and with which the
+ * device code takes the form at one frame.  -> D's index and *side = the side it reads (1 | 2); -1 = there is none.  Nothing is changed: the
+ * caller reserves what the form needs, then moves D up (move_up) and sets its flag */
+static int find_chained_1x1(const mars_model_ext_t *m, int i, int form, int c, const int *writers, int *side_out) {
+    const int n = form_span(form) - 1, O0 = m->ops[i + n - 2].t_out, O1 = m->ops[i + n - 1].t_out;
+    const mars_op_t *a = &m->ops[i], *g[4] = {a, a + 1, a + 2, NULL};
+    for (int j = i + n; j < m->n_ops && j <= i + 48; j++) {
+        const mars_op_t *d = &m->ops[j];
+        if (!free_1x1_ok(d, a, c, c) || !op_plain(m, j) || op_is_mate(m, j)) continue; /* (a head or a mate of another launch is not D) */
+        const int side = d->t_in[0] == O0 ? 1 : (d->t_in[0] == O1 ? 2 : 0), O = d->t_out;
+        if (!side || O < 0 || O == O0 || O == O1 || O == a->t_out || writers[O] != 1 || m->mt[O].io_in || m->mt[O].is_weight || m->mt[O].pix_stride || op_reads(d, O))
+            continue;
+        int reads = 0;
+        for (int k = 0; k < n; k++) reads |= op_reads(&a[k], O);
+        if (reads || touched_between(m, i + n, j, O, USE_READ | USE_WRITE) || touched_between(m, i + n, j, d->t_in[0], USE_WRITE)) continue;
+        g[n] = d;
+        if (!conv_i8_group_fits(m, form, g, side, 1)) continue;
+        *side_out = side;
+        return j;
+    }
+    return -1;
+}
+
 /* The bottleneck's m.cv1 inside the launch that already runs cv1 + cv2: A carries split_next with mates B and C; D = a 1 x 1 SiLU convolution from 32
  * to 32 channels that reads exactly B's or C's output over the same map.  A's launch (conv_i8_patch<CHAIN>) holds that side's requantised tile row
  * in registers the moment it stores it: it is the B operand of D's only K step.  D's input is still written (other ops read it: cv1's tensor is the
  * bottleneck's shortcut), only D's read of it and D's launch go.  Same bytes: D sees exactly the int8 values its input tensor holds.  All four ops
  * stay in the plan: A records the side (split_chain = 1 for B's, 2 for C's) and the image, D is skipped by the run loop like B and C.  D is moved up
  * behind C under pair_up's rule (nothing in between touches its output or writes its input); the first op that qualifies is taken.  Only where the
- * device code takes it (conv_i8_chain_fits); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_chain). */
-static int chain_mate_ok(const mars_op_t *d, const mars_op_t *a) {
-    return d->kind == OP_CONV_I8 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && !d->pt && !d->pl && d->safe && !d->nchw && !d->out_nchw && !d->add_t &&
-           !d->chain_n && !d->store_c && !d->in_byte_off && !d->out_byte_off && !d->out_pix_stride && !d->out_ch_off && d->lut_off != NO_OFF &&
-           d->lut2_off != NO_OFF && !d->nseg && !d->pre && !d->pair_next && !d->post_next && !d->split_next && d->n_in == 1 && d->in_c == 32 && d->out_c == 32 &&
-           d->oc_pad == 32 && d->row_pad == 32 && d->in_h == a->out_h && d->in_w == a->out_w && d->out_h == a->out_h && d->out_w == a->out_w;
-}
+ * device code takes it (conv_i8_group_fits); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_chain). */
 void fuse_split_chain(mars_model_ext_t *m) {
     if (m->sw.no_chain || m->no_chain || m->sw.no_split || m->no_split) return;
-    int *readers, *writers;
+    int *readers, *writers, g[4];
     if (!use_counts(m, &readers, &writers)) return;
-    for (int i = 0; i + 3 < m->n_ops; i++) {
+    for (int i = 0; i + 3 < m->n_ops; i += op_span(m, i)) {
         mars_op_t *a = &m->ops[i];
-        if (a->kind != OP_CONV_I8 || !a->split_next || a->split_chain) continue;
-        const int O0 = a[1].t_out, O1 = a[2].t_out;
-        for (int j = i + 3; j < m->n_ops && j <= i + 48; j++) {
-            const mars_op_t *d = &m->ops[j];
-            if (!chain_mate_ok(d, a) || m->ops[j - 1].pair_next || m->ops[j - 1].post_next || m->ops[j - 1].split_next ||
-                (j >= 2 && m->ops[j - 2].split_next))
-                continue; /* (a mate of another launch is not D) */
-            const int side = d->t_in[0] == O0 ? 1 : (d->t_in[0] == O1 ? 2 : 0), O = d->t_out;
-            if (!side || O < 0 || O == O0 || O == O1 || O == a->t_out || writers[O] != 1 || m->mt[O].io_in || m->mt[O].is_weight || m->mt[O].pix_stride ||
-                op_reads(a, O) || op_reads(d, O))
-                continue;
-            if (touched_between(m, i + 3, j, O, USE_READ | USE_WRITE) || touched_between(m, i + 3, j, d->t_in[0], USE_WRITE)) continue;
-            if (!conv_i8_chain_fits(m, a, a + 1, a + 2, d, side, 1)) continue; /* one frame: alloc_batch asks again for its batch */
-            const size_t bytes = mhip_conv_i8_chain_pack(NULL, NULL, NULL);
-            const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
-            if (off == NO_OFF) { free(readers); return; }
-            mhip_conv_i8_chain_pack((const int8_t *)(m->arena_host + d->w_off), d->b_off != NO_OFF ? (const int32_t *)(m->arena_host + d->b_off) : NULL,
-                                    (int8_t *)(m->arena_host + off));
-            if (j > i + 3) {
-                const mars_op_t moved = *d;
-                memmove(&m->ops[i + 4], &m->ops[i + 3], sizeof(mars_op_t) * (size_t)(j - i - 3));
-                m->ops[i + 3] = moved;
-            }
-            a->split_chain = side;
-            a->chain_w_off = off;
-            break;
-        }
-        i += 2; /* (B and C carry no split_next) */
+        if (a->kind != OP_CONV_I8 || op_form(m, i, g) != FORM_SPLIT) continue;
+        int side;
+        const int j = find_chained_1x1(m, i, FORM_SPLIT_CHAIN, 32, writers, &side);
+        if (j < 0) continue;
+        const size_t bytes = mhip_conv_i8_chain_pack(NULL, NULL, NULL);
+        const size_t off = arena_reserve(m, bytes); /* (may move the arena: pointers are taken afterwards) */
+        if (off == NO_OFF) break;
+        move_up(m, i + 3, j);
+        const mars_op_t *d = &m->ops[i + 3];
+        mhip_conv_i8_chain_pack((const int8_t *)(m->arena_host + d->w_off), d->b_off != NO_OFF ? (const int32_t *)(m->arena_host + d->b_off) : NULL,
+                                (int8_t *)(m->arena_host + off));
+        a->split_chain = side;
+        a->chain_w_off = off;
     }
     free(readers);
 }
@@ -1448,47 +1482,24 @@ void fuse_split_chain(mars_model_ext_t *m) {
  * allocated (both_elide; as fuse_split's k x k result).  Same bytes: D sees exactly the int8 values its input tensor holds, or would hold.
  * All three ops stay in the plan: A records the side (both_chain = 1 for its own, 2 for B's), D is moved up behind B under pair_up's rule and
  * skipped by the run loop like B.  It reads D's own packed weights and bias rows: no second image.  Only where the device code takes it
- * (conv_i8_both_chain_fits); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_both_chain). */
-static int both_chain_mate_ok(const mars_op_t *d, const mars_op_t *a) {
-    return d->kind == OP_CONV_I8 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && !d->pt && !d->pl && d->safe && !d->nchw && !d->out_nchw && !d->add_t &&
-           !d->chain_n && !d->store_c && !d->in_byte_off && !d->out_byte_off && !d->out_pix_stride && !d->out_ch_off && d->lut_off != NO_OFF &&
-           d->lut2_off != NO_OFF && !d->nseg && !d->pre && !d->pair_next && !d->post_next && !d->split_next && d->n_in == 1 && d->in_c == 64 && d->out_c == 64 &&
-           d->oc_pad == 64 && d->row_pad == 64 && d->in_h == a->out_h && d->in_w == a->out_w && d->out_h == a->out_h && d->out_w == a->out_w;
-}
+ * (conv_i8_group_fits); alloc_batch takes the decision back for a batch whose output offsets leave 31 bits (m->no_both_chain). */
 void fuse_both_chain(mars_model_ext_t *m) {
     if (m->sw.no_both_chain || m->no_both_chain || m->sw.no_both || m->no_both) return;
-    int *readers, *writers;
+    int *readers, *writers, g[4];
     if (!use_counts(m, &readers, &writers)) return;
-    for (int i = 0; i + 2 < m->n_ops; i++) {
+    for (int i = 0; i + 2 < m->n_ops; i += op_span(m, i)) {
         mars_op_t *a = &m->ops[i];
-        if (a->kind != OP_CONV_I8 || !a->pair_both || a->both_chain || a->in_byte_off || a[1].in_byte_off || a->out_byte_off || a[1].out_byte_off) continue;
-        if (i > 0 && m->ops[i - 1].split_next) continue; /* (the pair is itself inside a launch) */
-        const int O0 = a->t_out, O1 = a[1].t_out;
-        for (int j = i + 2; j < m->n_ops && j <= i + 48; j++) {
-            const mars_op_t *d = &m->ops[j];
-            if (!both_chain_mate_ok(d, a) || m->ops[j - 1].pair_next || m->ops[j - 1].post_next || m->ops[j - 1].split_next ||
-                (j >= 2 && (m->ops[j - 2].split_next || m->ops[j - 2].both_chain)) || (j >= 3 && m->ops[j - 3].split_chain))
-                continue; /* (a mate of another launch is not D) */
-            const int side = d->t_in[0] == O0 ? 1 : (d->t_in[0] == O1 ? 2 : 0), O = d->t_out;
-            if (!side || O < 0 || O == O0 || O == O1 || writers[O] != 1 || m->mt[O].io_in || m->mt[O].is_weight || m->mt[O].pix_stride ||
-                op_reads(a, O) || op_reads(a + 1, O) || op_reads(d, O))
-                continue;
-            if (touched_between(m, i + 2, j, O, USE_READ | USE_WRITE) || touched_between(m, i + 2, j, d->t_in[0], USE_WRITE)) continue;
-            if (!conv_i8_both_chain_fits(m, a, a + 1, d, side, 1)) continue; /* one frame: alloc_batch asks again for its batch */
-            if (j > i + 2) {
-                const mars_op_t moved = *d;
-                memmove(&m->ops[i + 3], &m->ops[i + 2], sizeof(mars_op_t) * (size_t)(j - i - 2));
-                m->ops[i + 2] = moved;
-            }
-            a->both_chain = side;
-            const int S = side == 1 ? O0 : O1;
-            if (readers[S] == 1 && writers[S] == 1 && !m->mt[S].io_in && !m->mt[S].io_out && !m->mt[S].is_weight && !m->mt[S].tail_read) {
-                a->both_elide = 1;
-                m->mt[S].needed = 0;
-            }
-            break;
+        if (a->kind != OP_CONV_I8 || op_form(m, i, g) != FORM_BOTH || a->in_byte_off || a[1].in_byte_off || a->out_byte_off || a[1].out_byte_off) continue;
+        int side;
+        const int j = find_chained_1x1(m, i, FORM_BOTH_CHAIN, 64, writers, &side);
+        if (j < 0) continue;
+        move_up(m, i + 2, j);
+        a->both_chain = side;
+        const int S = a[side - 1].t_out;
+        if (readers[S] == 1 && writers[S] == 1 && !m->mt[S].io_in && !m->mt[S].io_out && !m->mt[S].is_weight && !m->mt[S].tail_read) {
+            a->both_elide = 1;
+            m->mt[S].needed = 0;
         }
-        i += 1; /* (the mate carries no pair_both) */
     }
     free(readers);
 }
@@ -1640,7 +1651,7 @@ static int same_conv_input(const mars_op_t *a, const mars_op_t *b) {
 static int pairable(const mars_op_t *o) {
     /* measured: side-by-side pairs with a plain input gain 10-20 %, those reading a virtual concat lose (their single launches are
      * tuned individually), so a pair over a concat is formed only where it takes the one-tile form (pair_convs) */
-    return o->kind == OP_CONV_I8 && !o->nchw && !o->out_nchw && !o->add_t && o->safe && o->lut_off != NO_OFF && !o->pair_next &&
+    return o->kind == OP_CONV_I8 && !o->nchw && !o->out_nchw && !o->add_t && o->safe && o->lut_off != NO_OFF &&
            (o->in_c & 15) == 0 && o->in_c > 4 && (o->out_c & 15) == 0 && !o->out_pix_stride;
 }
 /* the step both pairing passes share: op j becomes op i's mate (moved up right behind it) unless an op between them touches j's output or
@@ -1650,23 +1661,22 @@ static int pair_up(mars_model_ext_t *m, int i, int j) {
     if (touched_between(m, i + 1, j, b->t_out, USE_READ | USE_WRITE)) return 0;
     for (int k = 0; k < b->n_in; k++)
         if (touched_between(m, i + 1, j, b->t_in[k], USE_WRITE)) return 0;
-    const mars_op_t moved = *b;
-    memmove(&m->ops[i + 2], &m->ops[i + 1], sizeof(mars_op_t) * (size_t)(j - i - 1));
-    m->ops[i + 1] = moved;
+    move_up(m, i + 1, j);
     m->ops[i].pair_next = 1;
     return 1;
 }
 void pair_convs(mars_model_ext_t *m) {
     for (int i = 0; i + 1 < m->n_ops; i++) {
         mars_op_t *a = &m->ops[i];
-        if (!pairable(a) || (i > 0 && m->ops[i - 1].pair_next)) continue;
+        if (!pairable(a) || !op_plain(m, i) || op_is_mate(m, i)) continue;
         for (int j = i + 1; j < m->n_ops && j <= i + 48; j++) {
             mars_op_t *b = &m->ops[j];
-            if (!pairable(b) || !same_conv_input(a, b) || b->t_out == a->t_out) continue;
+            if (!pairable(b) || !op_plain(m, j) || !same_conv_input(a, b) || b->t_out == a->t_out) continue;
             if (op_reads(b, b->t_out) || op_reads(b, a->t_out)) continue;
             /* the one-tile form (sides of 64 channels: the input is staged once for both) where the device code takes it at one frame; alloc_batch
              * asks again for its batch (m->no_both).  MARS_HIP_NO_BOTH: the side-by-side form, and no pair over a concat */
-            const int both = !m->sw.no_both && !m->no_both && conv_i8_both_fits(m, a, b, 1);
+            const mars_op_t *g[4] = {a, b};
+            const int both = !m->sw.no_both && !m->no_both && conv_i8_group_fits(m, FORM_BOTH, g, 0, 1);
             if (a->nseg && !both) continue;
             if (pair_up(m, i, j)) {
                 m->ops[i].pair_both = both;
@@ -1681,17 +1691,17 @@ void pair_convs(mars_model_ext_t *m) {
  * they are bound by exactly those bytes.  Formed where both take conv_f32_split (a weight image packed under f32_mfma = 3 / 4 at load),
  * neither has a folded Add; the second is moved up next to the first when nothing in between touches its tensors (as pair_convs). */
 static int pairable_f32(const mars_op_t *o) {
-    return o->kind == OP_CONV_F32 && !o->add_t && o->n_in == 1 && o->w2_off != NO_OFF && o->w3_off == NO_OFF && !o->pair_next && !o->in_rec && !o->out_rec &&
+    return o->kind == OP_CONV_F32 && !o->add_t && o->n_in == 1 && o->w2_off != NO_OFF && o->w3_off == NO_OFF && !o->in_rec && !o->out_rec &&
            o->kh == 1 && o->kw == 1;
 }
 void pair_convs_f32(mars_model_ext_t *m) {
     if (m->sw.no_pair_f32) return;
     for (int i = 0; i + 1 < m->n_ops; i++) {
         mars_op_t *a = &m->ops[i];
-        if (!pairable_f32(a) || (i > 0 && m->ops[i - 1].pair_next)) continue;
+        if (!pairable_f32(a) || !op_plain(m, i) || op_is_mate(m, i)) continue;
         for (int j = i + 1; j < m->n_ops && j <= i + 48; j++) {
             mars_op_t *b = &m->ops[j];
-            if (!pairable_f32(b) || b->t_in[0] != a->t_in[0] || b->t_out == a->t_out || b->t_out < 0 || a->t_out < 0) continue;
+            if (!pairable_f32(b) || !op_plain(m, j) || b->t_in[0] != a->t_in[0] || b->t_out == a->t_out || b->t_out < 0 || a->t_out < 0) continue;
             if (a->in_h != b->in_h || a->in_w != b->in_w || a->in_c != b->in_c || a->out_h != b->out_h || a->out_w != b->out_w || a->out_c != b->out_c ||
                 a->sh != b->sh || a->sw != b->sw || a->pt != b->pt || a->pl != b->pl || a->silu_f32 != b->silu_f32 || a->f32_exact != b->f32_exact)
                 continue;
@@ -1699,7 +1709,7 @@ void pair_convs_f32(mars_model_ext_t *m) {
             if (a->w2_planes != b->w2_planes) continue;
             int ok = b->t_in[0] != b->t_out && b->t_in[0] != a->t_out;
             for (int q = i + 1; q < j && ok; q++)
-                if (m->ops[q].pair_next) ok = 0; /* (this pass does not move an op past a pair; pair_convs does: kept as it was) */
+                if (m->ops[q].pair_next) ok = 0; /* (this pass does not move an op past a pair; pair_convs does: kept as it was.  The flag, not op_span: only pairs stop it, no other group) */
             if (ok && pair_up(m, i, j)) break;
         }
     }
@@ -1769,7 +1779,7 @@ void rec_pairs(mars_model_ext_t *m) {
         if (i < 0) continue;
         mars_op_t *pr = &m->ops[i];
         if (pr->kind != OP_CONV_F32 || pr->add_t || pr->out_rec || (pr->out_c & 7) || pr->kh > 32 || pr->kw > 32) continue;
-        if (pr->pair_next || (i > 0 && m->ops[i - 1].pair_next)) continue; /* (a paired launch writes plain floats) */
+        if (!op_plain(m, i) || op_is_mate(m, i)) continue; /* (a paired launch writes plain floats) */
         if (pr->out_c != x->in_c || pr->out_h != x->in_h || pr->out_w != x->in_w) continue;
         if (!(pr->w2_off != NO_OFF || (pr->w3_off != NO_OFF && pr->w3_stem))) continue; /* conv_f32_split or conv_f32_stem writes it */
         /* a weight image alone does not mean conv_f32_split takes the shape (stride 2 with an odd kernel width and pad > 1, maps
@@ -1912,8 +1922,9 @@ void virtual_concat_f32(mars_model_ext_t *m) {
                 }
         }
         if (!ok || r1 < 0 || nr > 2) continue;
-        const int paired = m->ops[r1].pair_next ? 1 : 0;
-        if (nr != 1 + paired || (r1 > 0 && m->ops[r1 - 1].pair_next) || (paired && (r1 + 1 >= m->n_ops || m->ops[r1 + 1].t_in[0] != T))) continue;
+        int g[4];
+        const int paired = op_form(m, r1, g) == FORM_PAIR_F32;
+        if (nr != 1 + paired || op_is_mate(m, r1) || (paired && m->ops[r1 + 1].t_in[0] != T)) continue;
         const int rl = r1 + paired; /* the last reader */
         size_t km = 0, worst = 0;
         for (int j = r1; j <= rl && ok; j++) {
@@ -2032,30 +2043,32 @@ void plan_check(mars_model_ext_t *m) {
     for (int i = 0; i < m->n_ops; i++) {
         const mars_op_t *o = &m->ops[i];
         const char *why = NULL;
+        const mars_op_t *M[4];
+        int g[4], gg[4];
+        op_form(m, i, g);
+        for (int k = 0; k < 4; k++) M[k] = g[k] >= 0 ? &m->ops[g[k]] : NULL;
         if (o->kind == -1) why = "a dead op is left";
         else if (o->n_in < 0 || o->n_in > 4 || o->nseg < 0 || o->nseg > 4 || o->chain_n < 0 || o->chain_n > 3 || o->vc_n < 0 || o->vc_n > 3) why = "an operand count is out of range";
         else if (o->add_t && !op_reads(o, o->add_t - 1)) why = "add_t is not among t_in";
         else if (o->chain_n && o->t_out != o->chain_out[o->chain_n - 1]) why = "t_out is not the chain's last stage";
-        else if (o->pair_next && (i + 1 >= m->n_ops || m->ops[i + 1].kind != o->kind)) why = "pair_next without a mate of its kind";
-        else if (o->pair_both && (!o->pair_next || o->kind != OP_CONV_I8 || (o->out_c != 64 && o->out_c != 128) || m->ops[i + 1].out_c != o->out_c)) why = "pair_both without a pair of 64- or 128-channel sides";
+        /* the launch group o heads (or, for cv1 of a split group, would head): M[k] = its k-th member, NULL where the plan ends before it.  The flags
+         * themselves are read here and only here: this is where their coherence is checked */
+        else if (o->pair_next && (!M[1] || M[1]->kind != o->kind)) why = "pair_next without a mate of its kind";
+        else if (o->pair_both && (!o->pair_next || o->kind != OP_CONV_I8 || (o->out_c != 64 && o->out_c != 128) || M[1]->out_c != o->out_c)) why = "pair_both without a pair of 64- or 128-channel sides";
         else if (o->kind == OP_CONV_I8 && o->pair_next && o->nseg && !o->pair_both) why = "a side-by-side pair over a virtual concat";
-        else if (o->post_next && (o->kind != OP_CONV_I8 || i + 1 >= m->n_ops || m->ops[i + 1].kind != OP_CONV_I8 || m->ops[i + 1].nseg != 2 ||
-                                  m->ops[i + 1].seg_t[0] != o->t_out || !op_reads(o, m->ops[i + 1].seg_t[1])))
+        else if (o->post_next && (o->kind != OP_CONV_I8 || !M[1] || M[1]->kind != OP_CONV_I8 || M[1]->nseg != 2 || M[1]->seg_t[0] != o->t_out || !op_reads(o, M[1]->seg_t[1])))
             why = "post_next without its 1x1 behind it, or y2 is not among t_in";
-        else if (o->split_next && (o->kind != OP_CONV_I8 || i + 2 >= m->n_ops || m->ops[i + 1].kind != OP_CONV_I8 || m->ops[i + 2].kind != OP_CONV_I8 ||
-                                   !m->ops[i + 1].pair_next || m->ops[i + 2].pair_next || m->ops[i + 1].n_in != 1 || m->ops[i + 2].n_in != 1 ||
-                                   m->ops[i + 1].t_in[0] != o->t_out || m->ops[i + 2].t_in[0] != o->t_out || o->post_next || o->pair_next || o->pre || o->add_t))
+        else if (o->split_next && (o->kind != OP_CONV_I8 || !M[2] || M[1]->kind != OP_CONV_I8 || M[2]->kind != OP_CONV_I8 || op_form(m, g[1], gg) != FORM_PAIR || !op_plain(m, g[2]) ||
+                                   M[1]->n_in != 1 || M[2]->n_in != 1 || M[1]->t_in[0] != o->t_out || M[2]->t_in[0] != o->t_out || o->post_next || o->pair_next || o->pre || o->add_t))
             why = "split_next without its pair of 1x1s behind it";
-        else if (o->split_chain && (!o->split_next || i + 3 >= m->n_ops || !chain_mate_ok(&m->ops[i + 3], o) || (o->split_chain != 1 && o->split_chain != 2) ||
-                                    m->ops[i + 3].t_in[0] != m->ops[i + o->split_chain].t_out || m->ops[i + 3].t_out < 0 ||
-                                    m->ops[i + 3].t_out == m->ops[i + 1].t_out || m->ops[i + 3].t_out == m->ops[i + 2].t_out || m->ops[i + 3].t_out == o->t_out ||
-                                    m->mt[m->ops[i + 3].t_out].pix_stride || o->chain_w_off == NO_OFF))
+        else if (o->split_chain && (!o->split_next || !M[3] || !free_1x1_ok(M[3], o, 32, 32) || !op_plain(m, g[3]) || (o->split_chain != 1 && o->split_chain != 2) ||
+                                    M[3]->t_in[0] != M[o->split_chain]->t_out || M[3]->t_out < 0 || M[3]->t_out == M[1]->t_out || M[3]->t_out == M[2]->t_out ||
+                                    M[3]->t_out == o->t_out || m->mt[M[3]->t_out].pix_stride || o->chain_w_off == NO_OFF))
             why = "split_chain without its 1x1 behind the pair";
-        else if (o->both_chain && (!o->pair_both || i + 2 >= m->n_ops || !both_chain_mate_ok(&m->ops[i + 2], o) || (o->both_chain != 1 && o->both_chain != 2) ||
-                                   m->ops[i + 2].t_in[0] != m->ops[i + o->both_chain - 1].t_out || m->ops[i + 2].t_out < 0 ||
-                                   m->ops[i + 2].t_out == o->t_out || m->ops[i + 2].t_out == m->ops[i + 1].t_out))
+        else if (o->both_chain && (!o->pair_both || !M[2] || !free_1x1_ok(M[2], o, 64, 64) || !op_plain(m, g[2]) || (o->both_chain != 1 && o->both_chain != 2) ||
+                                   M[2]->t_in[0] != M[o->both_chain - 1]->t_out || M[2]->t_out < 0 || M[2]->t_out == o->t_out || M[2]->t_out == M[1]->t_out))
             why = "both_chain without its 1x1 behind the pair";
-        else if (o->both_elide && (!o->both_chain || m->mt[m->ops[i + o->both_chain - 1].t_out].needed || m->mt[m->ops[i + o->both_chain - 1].t_out].io_out))
+        else if (o->both_elide && (!o->both_chain || m->mt[M[o->both_chain - 1]->t_out].needed || m->mt[M[o->both_chain - 1]->t_out].io_out))
             why = "both_elide on a side that is kept";
         for (int k = 0; !why && k < o->nseg; k++)
             if (!op_reads(o, o->seg_t[k])) why = "a seg_t is not among t_in";

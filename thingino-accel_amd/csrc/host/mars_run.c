@@ -35,89 +35,10 @@ static int g_dual_ways = 2; /* parts (= streams) such a batch is cut into: 2..4 
  * other is in the deep matrix-bound ones from then on: 4.45-4.50 ms per batch at every offset against 4.43 joined, 2.47
  * against 2.37 at batch 128.  The aligned start of the two halves is worth more than the bubble at the join costs.) */
 /* ------------------------------------------------------------------ running */
-/* device address of the first frame of the range being enqueued (weights: one copy for every frame) */
-static uint8_t *tdev(const mars_model_ext_t *m, int ti) {
-    if (ti < 0 || !m->mt[ti].dev) return NULL;
-    return m->mt[ti].dev + (m->mt[ti].is_weight ? 0 : (size_t)m->frame0 * m->mt[ti].stride);
-}
-static size_t tstride(const mars_model_ext_t *m, int ti) { return ti >= 0 ? m->mt[ti].stride : 0; }
-
-void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8_t *p) {
-    uint8_t *A = m->arena_dev;
-    conv_i8_geometry(op, m->run_frames, p);
-    p->in = (const int8_t *)tdev(m, op->t_in[0]); p->in_stride = tstride(m, op->t_in[0]);
-    p->out = (int8_t *)tdev(m, op->t_out); p->out_stride = tstride(m, op->t_out);
-    if (p->in) p->in += op->in_byte_off;   /* (a row range of the tensors: virtual_concat_q) */
-    if (p->out) p->out += op->out_byte_off;
-    p->w = (const int8_t *)(A + op->w_off);
-    p->bias = op->b_off != NO_OFF ? (const int32_t *)(A + op->b_off) : NULL;
-    p->lut = op->lut_off != NO_OFF ? A + op->lut_off : NULL;
-    p->lut2 = op->lut_off != NO_OFF && op->lut2_off != NO_OFF ? A + op->lut2_off : NULL;
-    p->w_rgb = op->w2_off != NO_OFF && !op->w2_rows ? (const int8_t *)(A + op->w2_off) : NULL;
-    p->w_rows = op->w2_off != NO_OFF && op->w2_rows ? (const int8_t *)(A + op->w2_off) : NULL;
-    if (op->pre) {
-        p->pre_w = (const int8_t *)(A + op->pre_w_off);
-        p->pre_bias = (const int32_t *)(A + op->pre_b_off);
-        p->pre_lut2 = A + op->pre_lut2_off;
-        p->pre_cs = op->pre_cs;
-    }
-    p->cs = op->cs; p->relu = op->relu; p->out_nchw = op->out_nchw;
-    p->variant = op->variant;
-    if ((op->post_next || op->split_next) && op->t_out >= 0) p->out_stride = planned_stride(&m->mt[op->t_out]); /* (never written, so never allocated: the Add's operand has its layout) */
-    if (op->add_t && tstride(m, op->add_t - 1) == p->out_stride) {
-        p->add = (const int8_t *)tdev(m, op->add_t - 1);
-        p->add_s_conv = op->add_s_conv; p->add_s_other = op->add_s_other; p->add_inv = op->add_inv;
-    }
-    p->nseg = op->nseg;
-    p->seg_up = op->seg_up;
-    int c0 = 0;
-    for (int k = 0; k < 4; k++) {
-        p->seg_c0[k] = 0x7fffffff;
-        if (k < op->nseg) {
-            p->seg_in[k] = (const int8_t *)tdev(m, op->seg_t[k]);
-            p->seg_stride[k] = tstride(m, op->seg_t[k]);
-            p->seg_c[k] = op->seg_c[k];
-            p->seg_c0[k] = c0;
-            c0 += op->seg_c[k];
-        }
-    }
-    if (op->nseg > 1) p->in = p->seg_in[0];
-}
-
-/* a launch that carries post_next: its own record + the 1x1 behind it (fuse_post) */
-static void conv_i8_post_params(const mars_model_ext_t *m, const mars_op_t *op, const mars_op_t *cv3, mhip_conv_i8_t *p) {
-    uint8_t *A = m->arena_dev;
-    conv_i8_params(m, op, p);
-    p->post_w = (const int8_t *)(A + op->post_w_off);
-    p->post_lut2 = A + cv3->lut2_off;
-    p->post_cs = cv3->cs;
-    p->post_in = (const int8_t *)tdev(m, cv3->seg_t[1]); p->post_in_stride = tstride(m, cv3->seg_t[1]);
-    p->post_out = (int8_t *)tdev(m, cv3->t_out); p->post_out_stride = tstride(m, cv3->t_out);
-    if (p->post_out) p->post_out += cv3->out_byte_off;
-    p->post_out_pix_stride = cv3->out_pix_stride; p->post_out_ch_off = cv3->out_ch_off;
-}
-
-/* a launch that carries split_next: its own record + the pair of 1x1s behind it (fuse_split) */
-static void conv_i8_split_params(const mars_model_ext_t *m, const mars_op_t *op, const mars_op_t *cv1, const mars_op_t *cv2, mhip_conv_i8_t *p) {
-    uint8_t *A = m->arena_dev;
-    const mars_op_t *side[2] = {cv1, cv2};
-    conv_i8_params(m, op, p);
-    p->split_w = (const int8_t *)(A + op->split_w_off);
-    for (int k = 0; k < 2; k++) {
-        p->split_lut2[k] = A + side[k]->lut2_off;
-        p->split_cs[k] = side[k]->cs;
-        p->split_out[k] = (int8_t *)tdev(m, side[k]->t_out); p->split_out_stride[k] = tstride(m, side[k]->t_out);
-    }
-}
-
-/* ... + the 1x1 chained to one side of that pair (fuse_split_chain) */
-static void conv_i8_chain_params(const mars_model_ext_t *m, const mars_op_t *op, const mars_op_t *d, mhip_conv_i8_t *p) {
-    uint8_t *A = m->arena_dev;
-    p->chain_side = op->split_chain;
-    p->chain_w = (const int8_t *)(A + op->chain_w_off);
-    p->chain_lut2 = A + d->lut2_off;
-    p->chain_cs = d->cs;
-    p->chain_out = (int8_t *)tdev(m, d->t_out); p->chain_out_stride = tstride(m, d->t_out);
+/* the live record of one op launched on its own (the groups': conv_i8_group_records, mars_plan.c) */
+static void conv_i8_params(const mars_model_ext_t *m, const mars_op_t *op, mhip_conv_i8_t *p) {
+    const mars_op_t *g[4] = {op};
+    conv_i8_group_records(m, FORM_PLAIN, g, 0, m->run_frames, 1, p);
 }
 
 static void conv_f32_params(mars_model_ext_t *m, mars_op_t *op, mhip_conv_f32_t *p) {
@@ -376,13 +297,13 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             fprintf(stderr, "Mars: Layer %d execution failed\n", op->layer);
             return (mars_error_t)op->err;
         }
-        mars_op_t *mate = (op->pair_next || op->post_next || op->split_next) && i + 1 < m->n_ops ? &m->ops[i + 1] : NULL;
-        mars_op_t *mate2 = (op->split_next || (op->pair_both && op->both_chain)) && i + 2 < m->n_ops ? &m->ops[i + 2] : NULL; /* (a fused pair: both mates' outputs are this launch's; a one-tile pair's chained 1x1) */
-        mars_op_t *mate3 = op->split_next && op->split_chain && i + 3 < m->n_ops ? &m->ops[i + 3] : NULL; /* (... and the chained 1x1's) */
-        if (wait_tail && ((op->t_out >= 0 && (m->mt[op->t_out].io_out || m->mt[op->t_out].tail_read)) ||
-                          (mate && mate->t_out >= 0 && (m->mt[mate->t_out].io_out || m->mt[mate->t_out].tail_read)) ||
-                          (mate2 && mate2->t_out >= 0 && (m->mt[mate2->t_out].io_out || m->mt[mate2->t_out].tail_read)) ||
-                          (mate3 && mate3->t_out >= 0 && (m->mt[mate3->t_out].io_out || m->mt[mate3->t_out].tail_read)))) {
+        int g[4];
+        const int form = op_form(m, i, g), span = op_span(m, i); /* the launch that starts here: its members' outputs are this launch's */
+        const mars_op_t *mem[4] = {op, NULL, NULL, NULL};
+        for (int q = 1; q < span; q++) mem[q] = &m->ops[g[q]];
+        for (int q = 0; q < span && wait_tail; q++) {
+            const int t = mem[q]->t_out;
+            if (t < 0 || !(m->mt[t].io_out || m->mt[t].tail_read)) continue;
             /* the previous batch's detection tail (auxiliary stream) still reads the graph
              * outputs (or the raw heads it decodes): order this launch behind it */
             mhip_stream_wait(sid, m->ev_tail_done);
@@ -398,59 +319,38 @@ static mars_error_t enqueue_range(mars_model_ext_t *m, int sid, int wait_tail) {
             op->ev_start = prof_last;
         }
         int rc;
-        if (op->split_next) { /* cv1 + cv2 inside this launch (conv_i8_patch<SPLIT>): the plan holds them only where this form runs */
-            mhip_conv_i8_t pa;
-            rc = -1;
-            if (mate && mate2 && (mate3 || !op->split_chain)) {
-                conv_i8_split_params(m, op, mate, mate2, &pa);
-                if (mate3) conv_i8_chain_params(m, op, mate3, &pa);
-                rc = mhip_conv_i8(&pa);
+        switch (form) {
+            case FORM_POST: case FORM_SPLIT: case FORM_SPLIT_CHAIN: { /* the mates inside this launch (conv_i8_patch<POST | SPLIT | CHAIN>): the plan holds them only where this form runs */
+                mhip_conv_i8_t p;
+                conv_i8_group_records(m, form, mem, op->split_chain, m->run_frames, 1, &p);
+                rc = mhip_conv_i8(&p);
+                break;
             }
-            i += mate3 ? 3 : 2; /* both mates have run (and the chained 1x1) */
-        } else if (mate && op->post_next) { /* cv3 inside this launch (conv_i8_patch<POST>): the plan holds it only where this form runs */
-            mhip_conv_i8_t pa;
-            conv_i8_post_params(m, op, mate, &pa);
-            rc = mhip_conv_i8(&pa);
-            i++; /* the mate has run */
-        } else if (mate && op->kind == OP_CONV_F32) { /* one grid for both (conv_f32_split's pair form); -2: one after the other */
-            mhip_conv_f32_t pa, pb;
-            conv_f32_params(m, op, &pa);
-            conv_f32_params(m, mate, &pb);
-            rc = mhip_conv_f32_pair(&pa, &pb);
-            if (rc == -2) {
-                rc = launch_op(m, op);
-                if (!rc) rc = launch_op(m, mate);
+            case FORM_PAIR_F32: { /* one grid for both (conv_f32_split's pair form); -2: one after the other */
+                mhip_conv_f32_t pa, pb;
+                conv_f32_params(m, op, &pa);
+                conv_f32_params(m, &m->ops[g[1]], &pb);
+                rc = mhip_conv_f32_pair(&pa, &pb);
+                break;
             }
-            i++;
-        } else if (mate) { /* one grid for both (conv_i8_persist<PAIR>); -2 = not possible at this batch: one after the other */
-            mhip_conv_i8_t pa, pb;
-            conv_i8_params(m, op, &pa);
-            conv_i8_params(m, mate, &pb);
-            if (op->pair_both && op->both_chain) { /* ... and the 1x1 behind one side (conv_i8_persist<CHAIN>); the plan holds it only where this form runs */
-                mhip_conv_i8_t pd;
-                rc = -1;
-                if (mate2) {
-                    conv_i8_params(m, mate2, &pd);
-                    rc = mhip_conv_i8_both_chain(&pa, &pb, &pd, op->both_chain, op->both_elide);
-                    if (rc == -2) rc = -1; /* (alloc_batch asked for this batch) */
-                }
-                i++; /* the chained 1x1 has run */
-            } else {
-                rc = op->pair_both ? mhip_conv_i8_both(&pa, &pb) : mhip_conv_i8_pair(&pa, &pb); /* (one tile for both | two tiles side by side) */
+            case FORM_PAIR: case FORM_BOTH: case FORM_BOTH_CHAIN: { /* one grid for both: two tiles side by side (conv_i8_persist<PAIR>) | one tile (<BOTH>) | + the 1x1 behind one side (<CHAIN>) */
+                mhip_conv_i8_t p[3];
+                conv_i8_group_records(m, form, mem, op->both_chain, m->run_frames, 1, p);
+                rc = form == FORM_PAIR ? mhip_conv_i8_pair(&p[0], &p[1]) : form == FORM_BOTH ? mhip_conv_i8_both(&p[0], &p[1])
+                                       : mhip_conv_i8_both_chain(&p[0], &p[1], &p[2], op->both_chain, op->both_elide);
+                if (form == FORM_BOTH_CHAIN && rc == -2) rc = -1; /* (the plan holds the chained 1x1 only where this form runs: alloc_batch asked for this batch) */
+                break;
             }
-            if (rc == -2) {
-                rc = launch_op(m, op);
-                if (!rc) rc = launch_op(m, mate);
-            }
-            i++; /* the mate has run */
-        } else {
+            case FORM_BAD: rc = -1; break; /* mates beyond the plan's end */
+            default: rc = launch_op(m, op);
+        }
+        if (rc == -2 && (form == FORM_PAIR || form == FORM_BOTH || form == FORM_PAIR_F32)) { /* a pair that is not possible at this batch: one after the other */
             rc = launch_op(m, op);
+            if (!rc) rc = launch_op(m, &m->ops[g[1]]);
         }
-        { /* the relayout scratch's copy of a tensor dies with any write to that tensor */
-            const mars_op_t *w2[4] = {op, mate, mate2, mate3};
-            for (int q = 0; q < 4; q++)
-                if (w2[q] && op_writes(w2[q], m->scratch_t)) m->scratch_t = -1;
-        }
+        i += span - 1; /* the mates have run */
+        for (int q = 0; q < span; q++) /* the relayout scratch's copy of a tensor dies with any write to that tensor */
+            if (op_writes(mem[q], m->scratch_t)) m->scratch_t = -1;
         if (m->profiling) { /* level 2: one event per run of launches of the same kind (their sum lands on the last one) */
             const int nx = i + 1;
             const int end = m->profiling != 2 || nx >= m->n_ops || m->ops[nx].prof_kind != op->prof_kind;
@@ -825,11 +725,8 @@ static mars_error_t autotune_model(mars_model_t *model, int reps) {
     for (int i = 0; i < m->n_ops && err == MARS_OK; i++) {
         mars_op_t *op = &m->ops[i];
         if (op->kind != OP_CONV_I8 || op->nchw) continue;
-        if (op->pair_next || (i > 0 && m->ops[i - 1].pair_next)) continue; /* paired launches have one form */
-        if (op->post_next || (i > 0 && m->ops[i - 1].post_next)) continue; /* ... and a fused cv3 goes with the launch its policy picks */
-        if (op->split_next) continue;                                      /* ... as does a fused pair (its mates are a pair: skipped above) */
-        if (i >= 3 && m->ops[i - 3].split_chain) continue;                 /* ... and the 1x1 chained to it */
-        if (i >= 2 && m->ops[i - 2].both_chain) continue;                  /* ... or to a one-tile pair */
+        int g[4];
+        if (op_is_mate(m, i) || op_form(m, i, g) != FORM_PLAIN) continue; /* a group has one form: its members go with the launch its policy picks */
         mhip_conv_i8_t p;
         conv_i8_params(m, op, &p);
         int codes[32];
