@@ -1341,6 +1341,147 @@ mars_error_t mars_hip_redact(mars_model_t *det_model, unsigned char *frames, con
  * available. */
 float mars_hip_redact_ms(mars_model_t *det_model);
 
+/* --------------------------------------------------------------- Overlay */
+/* The counterpart of "Redaction": not hiding what was found but showing it -- box, label, track id, mask tint and keypoints painted into
+ * the frame before it is encoded, stored or streamed.  Everything it draws is in HBM next to the frames after a batch: the detections in
+ * frame pixels, the track ids ("Tracking"), the masks on the frame's own grid ("Instance masks in frame pixels") and the keypoints ("Pose
+ * keypoints").  The reference draws on the host only, with PIL in a test script (mgk-decompiler/test_yolo_inference.py, draw_detections: a
+ * rectangle and a text per box).  Everything that touches a pixel is integer arithmetic; the only float32 steps are the rectangle rule, the
+ * confidence percentage and the keypoint floorf.
+ *
+ * Frames.     As in "Redaction": F frames of W x H (each at most 8192), densely packed, RGB [H][W][3] or NV12 (W, H even); src_format and
+ *             src_flags as there.
+ * Output.     In place (dst NULL or == the frames) or into a second buffer of the same size, of which every byte is written.  A dst that
+ *             overlaps the source without being equal to it is refused.  Either way the result is a function of the original frames alone.
+ * Palette.    P entries of RGB, 1 <= P <= 256, the caller's; palette == NULL: the built-in table of 16 (mars_overlay_default_palette):
+ *               (255,64,64) (64,200,64) (64,128,255) (255,200,0) (255,0,255) (0,220,220) (255,128,0) (128,64,255)
+ *               (160,255,64) (255,128,192) (0,128,128) (128,0,0) (0,0,160) (128,128,0) (192,192,192) (96,96,96)
+ * NV12 colours.  For NV12 frames the host converts every colour once (mars_overlay_rgb_to_yuv; >> is an arithmetic shift, results clamped
+ *             to 0 .. 255) and uploads the converted table; the kernels are format-blind about colour.  Limited range (the default):
+ *               Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16, U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128, V = ((112 R - 94 G - 18 B + 128) >> 8) + 128;
+ *             MARS_NV12_FULL_RANGE:
+ *               Y = (77 R + 150 G + 29 B + 128) >> 8, U = ((-43 R - 85 G + 128 B + 128) >> 8) + 128, V = ((128 R - 107 G - 21 B + 128) >> 8) + 128.
+ *             MARS_NV12_VU swaps the stored chroma pair.
+ * Colour of a detection.  color_by = MARS_OVERLAY_BY_CLASS (0: key = cls), _BY_TRACK (key = the track id) or _FIXED (key = 0).  key >= 0:
+ *             palette[key % P]; key < 0: the options' no_key colour.  The host-pointer form takes a key per box instead where it is given
+ *             one; without keys, _BY_TRACK there gives every box the key -1.
+ * Text colour.  Black where the luma (77 R + 150 G + 29 B + 128) >> 8 of the RGB colour under it is >= 128, else white.
+ * Selection (device form).  conf >= min_conf (0: all) and the class window cls_first / cls_count, as in "Redaction"; with
+ *             MARS_OVERLAY_TRACKED_ONLY only detections whose track entry has id >= 0 and hits >= min_hits (0 means 1).
+ * Elements.   Every selected detection gives one element.  Its rectangle R = (x0, y0, x1, y1) is "Box -> source rectangle" of "ROI crops"
+ *             with expand 1.0 and min_size 1.  A selected detection the rectangle rule skips counts in `skipped` and paints nothing.
+ *             Elements keep the list's order; the element index below is the rank among the frame's elements.
+ * Layers.     layers is a bit set of MARS_OVERLAY_MASKS, _BOXES, _KEYPOINTS, _LABELS; 0 means _BOXES | _LABELS.  Within a layer a pixel
+ *             that several elements cover belongs to the one with the lowest element index -- for markers the lowest (element index,
+ *             keypoint index); lists are sorted by confidence, so the most confident is on top.  Across layers: LABELS over KEYPOINTS over
+ *             BOXES over MASKS over the source pixel.
+ * MASKS (tint).  The pixels of R whose bit is set in the element's frame-pixel mask: the words of "Instance masks in frame pixels", pitch
+ *             (W + 31) / 32.  An element without a mask slot has no tint.  Per channel out = (src * (256 - a) + col * a + 128) >> 8, a =
+ *             alpha in 1 .. 256 (0 means 96), col the element's colour.
+ * BOXES (outline).  The pixels of R that are not in (x0 + t, y0 + t, x1 - t, y1 - t); t = thickness in 1 .. 16 (0 means 2).  An empty
+ *             inner rectangle makes all of R outline.  Opaque, the element's colour.
+ * KEYPOINTS (markers).  Every keypoint j of an element that has a pose slot, with x and y finite and v >= kpt_min_v (0 means 0.5):
+ *             cx = floorf(x), cy = floorf(y); the marker is dropped, before any conversion to int, when cx < -8.0f, cx > (float)(W + 8),
+ *             cy < -8.0f or cy > (float)(H + 8); otherwise it is the square [cx - r, cx + r] x [cy - r, cy + r] cut to the frame (it may
+ *             be empty then), r = radius in 1 .. 8 (0 means 2).  Opaque, colour palette[j % P].
+ * LABELS.     A strip per element whose text has n > 0 bytes.  s = scale in 1 .. 8 (0 means 2); Wl = s * (6 n + 1), Hl = 9 s; lx = x0;
+ *             ly = y0 - Hl where that is >= 0, else y0 (inside the box's top).  The strip [lx, lx + Wl) x [ly, ly + Hl) is cut to the
+ *             frame.  For its pixel (x, y): u = x - lx - s, v = y - ly - s.  The pixel has the text colour when u >= 0, 0 <= v < 7 s,
+ *             k = u / (6 s) < n, u % (6 s) < 5 s and bit 4 - (u % (6 s)) / s of row v / s of the glyph of byte k is set; every other pixel
+ *             of the strip has the element's colour.  Opaque.
+ * Font.       5 x 7, drawn for this project: 64 glyphs for the bytes 32 .. 95, seven row bytes each from the top, bit 4 the left column,
+ *             bits 5 .. 7 clear (mars_overlay_glyph).  Bytes 96 .. 126 show the glyph of byte - 32 (lowercase shows as uppercase); every
+ *             other byte shows as '?'.
+ * Text (device form).  The parts that `text` chooses (MARS_OVERLAY_TEXT_CLASS | _TRACK | _CONF; 0 means _CLASS | _CONF), in that order,
+ *             joined by one space; the first MARS_OVERLAY_TEXT_MAX bytes are kept.  CLASS: the bytes of names[cls] up to the first NUL
+ *             where names is set, 0 <= cls < n_names and names[cls] is not empty, else the decimal of cls ('-' in front of a negative
+ *             one).  names = n_names x MARS_OVERLAY_NAME_LEN bytes, NUL-padded (a name of exactly that length has no NUL), copied by
+ *             every call.  TRACK: '#' and the decimal id; left out when id < 0.  CONF: p = (int)(conf * 100.0f + 0.5f), the two float32
+ *             operations rounded on their own (no FMA), clamped to 0 .. 100 (a NaN gives 0); its decimal and '%'.  The device composes
+ *             these bytes in the selection kernel; mars_overlay_text composes the same bytes on the host, with the same code.  The
+ *             host-pointer form takes the label of a box from texts (up to the first NUL, at most MARS_OVERLAY_TEXT_MAX bytes) where it
+ *             is given them, else composes it with id = -1.
+ * NV12.       Luma is painted per pixel as above with the Y of every colour.  Chroma sample (i, j) follows pixel (2i, 2j): the chroma pair
+ *             of the opaque element that owns that pixel, if any; else the tint's blend of both samples, if that pixel is tinted; else
+ *             unchanged.
+ * Statistics. Per frame {boxes, masked, labels, markers, skipped, pixels}: the elements; those with a mask slot (MASKS on); those with a
+ *             text (LABELS on); the markers formed (KEYPOINTS on, dropped ones not counted); the selected detections the rectangle rule
+ *             skipped; the frame pixels (luma positions) that any layer covers.
+ * Not covered: skeleton limbs and any line drawing; oriented outlines; anti-aliasing; caller fonts and glyphs beyond the table; names of
+ *   gallery identities; the mars_hip_pipe_* path; the merged lists of "Tiled inference"; frames with a row pitch. */
+#define MARS_OVERLAY_MASKS 1u
+#define MARS_OVERLAY_BOXES 2u
+#define MARS_OVERLAY_KEYPOINTS 4u
+#define MARS_OVERLAY_LABELS 8u
+#define MARS_OVERLAY_BY_CLASS 0
+#define MARS_OVERLAY_BY_TRACK 1
+#define MARS_OVERLAY_FIXED 2
+#define MARS_OVERLAY_TEXT_CLASS 1u
+#define MARS_OVERLAY_TEXT_TRACK 2u
+#define MARS_OVERLAY_TEXT_CONF 4u
+#define MARS_OVERLAY_TRACKED_ONLY 1u
+#define MARS_OVERLAY_TEXT_MAX 24
+#define MARS_OVERLAY_NAME_LEN 16
+#define MARS_OVERLAY_MAX_NAMES 4096
+/* Zero-initialise; zero means default in every field but the frame size. */
+typedef struct {
+    int src_w, src_h, src_format; unsigned src_flags; /* frames: MARS_HIP_CAMERA_RGB / _NV12, MARS_NV12_* (NV12 only) */
+    unsigned layers;                                   /* MARS_OVERLAY_MASKS | _BOXES | _KEYPOINTS | _LABELS */
+    int color_by;                                      /* MARS_OVERLAY_BY_CLASS / _BY_TRACK / _FIXED */
+    unsigned text;                                     /* MARS_OVERLAY_TEXT_CLASS | _TRACK | _CONF */
+    int thickness, radius, scale, alpha;
+    unsigned char no_key[3];                           /* R, G, B of a negative key */
+    float min_conf, kpt_min_v;
+    int cls_first, cls_count, min_hits;
+    unsigned flags;                                    /* MARS_OVERLAY_TRACKED_ONLY (the device form) */
+    int n_palette; const unsigned char *palette;       /* [n_palette][3] R, G, B; NULL (n_palette 0): the built-in table */
+    int n_names; const char *names;                    /* [n_names][MARS_OVERLAY_NAME_LEN]; NULL (n_names 0): classes show as numbers */
+} mars_hip_overlay_opts_t;
+typedef struct { int boxes, masked, labels, markers, skipped, pixels; } mars_overlay_stats_t; /* 24 bytes */
+/* Pure host code.  The built-in palette -> rgb = [16][3]; returns 16. */
+int mars_overlay_default_palette(unsigned char *rgb);
+/* Pure host code.  rgb = R, G, B -> yuv = Y and the chroma pair in its stored order (U, V; V, U under MARS_NV12_VU), by the formulas above;
+ * flags = MARS_NV12_*. */
+void mars_overlay_rgb_to_yuv(const unsigned char *rgb, unsigned flags, unsigned char *yuv);
+/* Pure host code.  The seven rows of the glyph that `byte` shows as (any int: what is not 32 .. 126 shows as '?'). */
+void mars_overlay_glyph(int byte, unsigned char rows[7]);
+/* Pure host code.  The label of a detection as the device form composes it -> the number of bytes; out = MARS_OVERLAY_TEXT_MAX bytes, zero
+ * behind the text.  text = MARS_OVERLAY_TEXT_* (0 means CLASS | CONF); names may be NULL; track_id < 0: untracked. */
+int mars_overlay_text(unsigned text, const char *names, int n_names, int cls, int track_id, float conf, char *out);
+/* Refused before any device work by every call below, in the order of "Redaction".  MARS_ERR_INVALID_FILE: no options or a NULL pointer
+ * where one is needed, a non-positive size, an unknown format, layer, text, colour or flag bit, odd NV12 sizes, a thickness above 16, a
+ * radius or scale above 8, an alpha above 256, any of them negative, a negative or non-finite min_conf or kpt_min_v, a negative cls_count
+ * or min_hits, a palette of more than 256 or fewer than 1 entries or a count without a table, more than MARS_OVERLAY_MAX_NAMES names or a
+ * count without a table, more than MARS_POSE_MAX_KPT keypoints a box, a dst that overlaps the source in part.  MARS_ERR_INVALID_TENSOR: W
+ * or H above 8192, no detections in HBM, a model with an open pipe; where the options ask for them (MARS_OVERLAY_TRACKED_ONLY, _BY_TRACK or
+ * _TEXT_TRACK; _MASKS; _KEYPOINTS): no track results of this batch, no native mask results of this batch or a mask grid that is not W x H,
+ * no pose results of this batch. */
+/* Host pointers in and out, the same kernels on the GPU; waits.  `frames` = n_frames frames of opts->src_w x src_h; box i lies in frame
+ * frame_of_box[i] (a box whose index names no frame is left out).  Every box is taken: min_conf, the class window and opts->flags are not
+ * looked at beyond the check.  Each of these may be NULL: keys = [n_boxes] colour keys; texts = [n_boxes][MARS_OVERLAY_TEXT_MAX] labels;
+ * mask_of_box = [n_boxes] indices into mask_words[.][H][(W + 31) / 32], or -1 for no tint; kpts = [n_boxes][num_kpt] keypoints in frame
+ * pixels (a box without any: v = 0).  n_boxes 0 .. 65535, n_frames 1 .. 65535.  out = the painted frames; out == frames runs the in-place
+ * form.  stats = [n_frames], or NULL. */
+mars_error_t mars_yolo_overlay_frames(const unsigned char *frames, int n_frames, const mars_det_t *boxes, const int *frame_of_box, int n_boxes,
+                                      const int *keys, const char *texts, const uint32_t *mask_words, const int *mask_of_box, const mars_kpt_t *kpts,
+                                      int num_kpt, const mars_hip_overlay_opts_t *opts, unsigned char *out, mars_overlay_stats_t *stats);
+/* The device form.  Reads the detections the last mars_hip_detect_*_device of det_model left in HBM (in frame pixels) and paints det_model's
+ * batch of frames at frames_dev into dst_dev (NULL or == frames_dev: in place).  Where the options ask for them it also reads the track
+ * side array (mars_hip_track_device), the native mask results (mars_hip_detect_seg_native_device, whose grid must be W x H) and the pose
+ * results (mars_hip_detect_pose_device with src_w / src_h set, so that the keypoints are in frame pixels); each must belong to this batch.
+ * Enqueues only, on the auxiliary stream, with the redaction's event protocol in both directions: crops, front-end and motion the library
+ * enqueued EARLIER have read the original pixels; library work enqueued LATER, and every *_results call, sees the painted ones.  An overlay
+ * enqueued after a redaction paints over the redacted pixels.  The palette and the names are copied by the call: a call whose palette and
+ * names differ from those of det_model's last overlay call waits for the device around their upload, every other call only enqueues. */
+mars_error_t mars_hip_overlay_device(mars_model_t *det_model, void *frames_dev, void *dst_dev, const mars_hip_overlay_opts_t *opts);
+/* Waits.  stats = [batch] of the last mars_hip_overlay_device call (may be NULL: only waits).  MARS_ERR_INVALID_TENSOR before any such call. */
+mars_error_t mars_hip_overlay_results(mars_model_t *det_model, mars_overlay_stats_t *stats);
+/* The same with the frames in host memory, in place: uploads them, paints, downloads them, waits. */
+mars_error_t mars_hip_overlay(mars_model_t *det_model, unsigned char *frames, const mars_hip_overlay_opts_t *opts, mars_overlay_stats_t *stats);
+/* Device time (ms) of the last mars_hip_overlay_device call (selection + pixels), from events on the auxiliary stream; waits for it.  < 0:
+ * not available. */
+float mars_hip_overlay_ms(mars_model_t *det_model);
+
 /* --------------------------------------------------------------- Motion */
 /* The first question a camera deployment asks of a frame: did anything move, and where?  The frames are in HBM for the front-end, the crops
  * and the redaction; the calls below read each of them once more (the Y plane of an NV12 frame, every byte of an RGB frame) and keep a

@@ -1,5 +1,5 @@
-// frame_tile.hpp -- what the kernels that walk camera frames tile by tile share (redact.hip, motion.hip): the tile's shape, the move of a
-// tile's rows into LDS, and the mask of a span of bits.  What a kernel does with the staged rows, and its barriers, are its own.
+// frame_tile.hpp -- what the kernels that walk camera frames tile by tile share (redact.hip, motion.hip, overlay.hip): the tile's shape, the move of a
+// tile's rows into LDS and, for the kernels that write frames, back, and the mask of a span of bits.  What a kernel does with the staged rows, and its barriers, are its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +32,48 @@ __device__ __forceinline__ int tile_rows_to_lds(const uint8_t *src, const size_t
     if (sub == 3)
         for (int k = head + 4 * nd; k < nb; k++) l[k] = g[k];
     return sh;
+}
+
+// LDS -> the destination, the way back.  Called by every thread behind the caller's barrier: thread t is one of the four on row t >> 2.  The
+// staged rows are those tile_rows_to_lds(src, pitch, nb, rows, pix, wide) left (src gives every row's shift); row r goes to dst + r * pitch.
+// C = bytes per sample, bit x of cov[r] = sample (x, r) has changed.  Out of place every unit is stored; in place only the units that hold a
+// changed sample.  wide must also cover dst (both sides multiples of 16): 16-byte units; else, where src and dst agree in their low two
+// address bits, bytes up to the first 4-byte boundary, 4-byte units and bytes behind the last one; else bytes.  No store reaches over a row's
+// ends.  All plain vector stores.  No barrier: the caller's.
+template <int C>
+__device__ __forceinline__ void tile_rows_from_lds(const uint8_t *src, uint8_t *dst, const size_t pitch, const int nb, const int rows, const uint8_t *pix,
+                                                   const bool wide, const unsigned long long *cov, const bool inplace) {
+    const int row = threadIdx.x >> 2, sub = threadIdx.x & 3;
+    if (row >= rows) return;
+    const bool same4 = !(((uintptr_t)src ^ (uintptr_t)dst) & 3);
+    const unsigned long long cr = cov[row];
+    const auto want = [&](const int b0, const int b1) { // bytes b0 .. b1 of the row hold a changed sample
+        if (!inplace) return true;
+        const int s0 = b0 / C, s1 = b1 / C;
+        return ((cr >> s0) & ((2ull << (s1 - s0)) - 1ull)) != 0ull;
+    };
+    uint8_t *g = dst + (size_t)row * pitch;
+    const int sh = (int)((uintptr_t)(src + (size_t)row * pitch) & 3);
+    const uint8_t *l = pix + row * FT_PITCH + sh;
+    if (inplace && !cr) {
+        // nothing of this row changes
+    } else if (wide) {
+        for (int j = sub; j < (nb >> 4); j += 4)
+            if (want(16 * j, 16 * j + 15)) *(uint4 *)(g + 16 * j) = *(const uint4 *)(l + 16 * j);
+    } else if (same4) {
+        const int head = min(nb, (4 - sh) & 3), nd = (nb - head) >> 2;
+        if (sub == 0)
+            for (int k = 0; k < head; k++)
+                if (want(k, k)) g[k] = l[k];
+        for (int j = sub; j < nd; j += 4)
+            if (want(head + 4 * j, head + 4 * j + 3)) *(uint32_t *)(g + head + 4 * j) = *(const uint32_t *)(l + head + 4 * j);
+        if (sub == 3)
+            for (int k = head + 4 * nd; k < nb; k++)
+                if (want(k, k)) g[k] = l[k];
+    } else { // the two buffers differ in their alignment: bytes
+        for (int k = sub; k < nb; k += 4)
+            if (want(k, k)) g[k] = l[k];
+    }
 }
 
 // bits lo .. hi (inclusive, 0 <= lo <= hi <= 31) of a 32-bit word

@@ -16,7 +16,7 @@
 // the original frame alone, in place as out of place.  A workgroup whose tile meets no region leaves at once and, in place, touches no pixel.
 // Rows of 3 * W bytes have any alignment: a row is moved as 16-byte units where the tile's rows are all 16-byte aligned on both sides,
 // else as bytes up to the first 4-byte boundary, 4-byte units and bytes behind the last one; its LDS copy is shifted by the row's address
-// & 3, so both sides of every 4-byte move are aligned (in: tile_rows_to_lds of frame_tile.hpp; out: below).  All stores are plain vector
+// & 3, so both sides of every 4-byte move are aligned (tile_rows_to_lds and tile_rows_from_lds of frame_tile.hpp).  All stores are plain vector
 // stores from C++.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -92,10 +92,9 @@ template <int C>
 __device__ __forceinline__ void redact_plane(const uint8_t *src, uint8_t *dst, const size_t pitch, const int tw, const int th, const int bl, const int mode,
                                              const unsigned fill /* byte c: channel c's fill value */, const unsigned long long *cov, const bool any, const bool inplace, uint8_t *pix,
                                              unsigned short *rowsum, uint8_t *val) {
-    const int tid = threadIdx.x, row = tid >> 2, sub = tid & 3; // four threads on a row
+    const int tid = threadIdx.x;
     const int nb = tw * C;
     const bool wide = !(((uintptr_t)src | (uintptr_t)dst | pitch | (size_t)nb) & 15);
-    const bool same4 = !(((uintptr_t)src ^ (uintptr_t)dst) & 3);
     // ---- the tile's rows -> LDS, row r at pix + r * FT_PITCH + (its address & 3); wide here: the stores below go the same way
     (void)tile_rows_to_lds(src, pitch, nb, th, pix, wide);
     __syncthreads(); // every byte of the tile has been read: from here on it may be written
@@ -133,37 +132,8 @@ __device__ __forceinline__ void redact_plane(const uint8_t *src, uint8_t *dst, c
         }
         __syncthreads();
     }
-    // ---- LDS -> the destination: everything out of place, in place the units that hold a redacted sample
-    if (row < th) {
-        const unsigned long long cr = cov[row];
-        const auto want = [&](const int b0, const int b1) { // bytes b0 .. b1 of the row hold a redacted sample
-            if (!inplace) return true;
-            const int s0 = b0 / C, s1 = b1 / C;
-            return ((cr >> s0) & ((2ull << (s1 - s0)) - 1ull)) != 0ull;
-        };
-        uint8_t *g = dst + (size_t)row * pitch;
-        const int sh = (int)((uintptr_t)(src + (size_t)row * pitch) & 3);
-        const uint8_t *l = pix + row * FT_PITCH + sh;
-        if (inplace && !cr) {
-            // nothing of this row changes
-        } else if (wide) {
-            for (int j = sub; j < (nb >> 4); j += 4)
-                if (want(16 * j, 16 * j + 15)) *(uint4 *)(g + 16 * j) = *(const uint4 *)(l + 16 * j);
-        } else if (same4) {
-            const int head = min(nb, (4 - sh) & 3), nd = (nb - head) >> 2;
-            if (sub == 0)
-                for (int k = 0; k < head; k++)
-                    if (want(k, k)) g[k] = l[k];
-            for (int j = sub; j < nd; j += 4)
-                if (want(head + 4 * j, head + 4 * j + 3)) *(uint32_t *)(g + head + 4 * j) = *(const uint32_t *)(l + head + 4 * j);
-            if (sub == 3)
-                for (int k = head + 4 * nd; k < nb; k++)
-                    if (want(k, k)) g[k] = l[k];
-        } else { // the two buffers differ in their alignment: bytes
-            for (int k = sub; k < nb; k += 4)
-                if (want(k, k)) g[k] = l[k];
-        }
-    }
+    // ---- LDS -> the destination: everything out of place, in place the units that hold a redacted sample (frame_tile.hpp)
+    tile_rows_from_lds<C>(src, dst, pitch, nb, th, pix, wide, cov, inplace);
     __syncthreads();
 }
 

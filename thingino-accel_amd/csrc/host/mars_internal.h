@@ -257,6 +257,13 @@ typedef struct mars_model_ext {
                           * [frames] x mars_redact_stats_t */
     size_t redact_stats_off;
     void *ev_redact_done; /* the redaction (auxiliary stream) has written the frames: the main stream waits for it */
+    /* overlay (mars_overlay.c) */
+    mars_block_t overlay; /* of THIS model's detections: the element table [frames][MARS_YOLO_MAX_DET] x 12 int, the marker table
+                           * [frames][markers] x 4 int, both counts [frames] x int, [frames] x mars_overlay_stats_t, the packed palette [256] x
+                           * uint32, the names */
+    size_t overlay_stats_off;
+    void *overlay_img;    /* host copy of the palette and names that are up in the block: a call with the same ones uploads nothing */
+    size_t overlay_img_bytes;
     /* motion (mars_motion.c) */
     mars_det_side_t motion; /* moved cells of THIS model's detections: x mars_motion_det_t */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */

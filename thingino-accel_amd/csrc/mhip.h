@@ -716,6 +716,57 @@ typedef struct {
 int mhip_redact_select(const mhip_redact_t *p);
 int mhip_redact(const mhip_redact_t *p);
 
+/* ---- overlay (overlay.hip): detections, track ids, masks and keypoints -> the frames with boxes, labels, tints and markers painted in, by
+ * the exact rule of include/mars_hip.h ("Overlay").  Every pointer is device memory.  Two launches: mhip_overlay_select (one workgroup per
+ * frame: the selection, the rectangle rule, colours, label texts, mask and pose slots, the frame's element table and marker table, the
+ * counts), then mhip_overlay (one workgroup per 64 x 64 pixel tile and frame; it adds the frame's `pixels`).
+ * A colour is packed as c0 | c1 << 8 | c2 << 16 | white << 24: R, G, B, or Y and the chroma pair in its stored order -- the host converts,
+ * the kernels are format-blind; white = the text on it is white, from the RGB colour. */
+#define MHIP_OVERLAY_MAX_DIM 8192
+#define MHIP_OVERLAY_MAX_KPT 32
+#define MHIP_OVERLAY_REC_INTS 12 /* an element: x0, y0, x1, y1, mask slot or -1, colour | text length << 25, 24 text bytes */
+#define MHIP_OVERLAY_MASKS 1u
+#define MHIP_OVERLAY_BOXES 2u
+#define MHIP_OVERLAY_KEYPOINTS 4u
+#define MHIP_OVERLAY_LABELS 8u
+typedef struct {
+    const uint8_t *frames; uint8_t *dst;        /* as in mhip_redact_t */
+    size_t frame_stride;
+    int n_frames, w, h, fmt;
+    const void *dets; const int *counts;        /* the lists, as in mhip_redact_t */
+    const int *list_off; int det_cap;
+    int select_all;                             /* != 0: every listed record is selected (the host-pointer form) */
+    float min_conf;
+    int cls_first, cls_count;
+    const void *tracks;                         /* NULL, or records of 8 bytes {id, hits} index-aligned with dets */
+    int tracked_only, min_hits;                 /* != 0: only records with id >= 0 and hits >= min_hits (resolved: >= 1) */
+    int color_by;                               /* 0 class, 1 track id, 2 fixed */
+    const int *keys;                            /* NULL, or the colour key of every record, index-aligned with dets: overrides color_by */
+    unsigned text;                              /* MHIP_OVERLAY_TEXT_* of csrc/overlay_rule.h, resolved: not 0 */
+    const char *texts;                          /* NULL, or [.][24] bytes index-aligned with dets: the label of a record, up to the first NUL */
+    const char *names; int n_names;             /* NULL, or [n_names][16] */
+    const void *mask_recs; int mask_max;        /* as in mhip_redact_t */
+    const int *mask_of;
+    const uint32_t *mask_words;
+    const void *pose_recs; int pose_max;        /* NULL, or [n_frames][pose_max] records of 12 bytes whose det field names a list index: that
+                                                 * detection's keypoints are row f * pose_max + j of kpts; pose_max <= 256 */
+    int kpt_rows;                               /* != 0 (the host-pointer form): record i's keypoints are row i of kpts, index-aligned with dets */
+    const void *kpts; int num_kpt;              /* [row][num_kpt] records of 12 bytes {x, y, v}; num_kpt 1 .. 32 */
+    float kpt_min_v;                            /* resolved */
+    unsigned layers;                            /* MHIP_OVERLAY_*, resolved: not 0 */
+    int thick, radius, scale, alpha;            /* resolved: 1 .. 16, 1 .. 8, 1 .. 8, 1 .. 256 */
+    const uint32_t *palette; int n_palette;     /* packed colours, 1 .. 256 of them */
+    uint32_t no_key, text_col[2];               /* packed: the colour of a negative key; black and white */
+    int *table;                                 /* MHIP_OVERLAY_REC_INTS per record, at the place of the frame's list: the first table_n[f] are elements */
+    int *table_n;                               /* [n_frames] */
+    int *marks;                                 /* 4 ints per marker {cx, cy, element * 32 + keypoint, 0}: frame f's from marker list_off[f] * */
+    size_t mark_stride;                         /* num_kpt on (list_off != NULL), else from f * mark_stride on; in no order: the key orders them */
+    int *marks_n;                               /* [n_frames] */
+    int *stats;                                 /* [n_frames][6]: boxes, masked, labels, markers, skipped, pixels */
+} mhip_overlay_t;
+int mhip_overlay_select(const mhip_overlay_t *p);
+int mhip_overlay(const mhip_overlay_t *p);
+
 /* ---- motion maps (motion.hip): camera frames -> per frame a bit map of the grid cells whose mean luma left the stream's background, by the
  * exact rule of include/mars_hip.h ("Motion").  Every pointer is device memory.  Two launches per call: mhip_motion_cells (one workgroup
  * per 64 x 64 pixel tile and STREAM, which walks that stream's steps in order: cell means, the compare, the background update, one raw byte

@@ -231,6 +231,23 @@ class RedactOpts(C.Structure):  # mars_hip_redact_opts_t: zero = default in ever
                 ("cls_count", C.c_int), ("flags", C.c_uint)]
 
 
+OVERLAY_MASKS, OVERLAY_BOXES, OVERLAY_KEYPOINTS, OVERLAY_LABELS = 1, 2, 4, 8  # MARS_OVERLAY_*
+OVERLAY_BY_CLASS, OVERLAY_BY_TRACK, OVERLAY_FIXED = 0, 1, 2
+OVERLAY_TEXT_CLASS, OVERLAY_TEXT_TRACK, OVERLAY_TEXT_CONF = 1, 2, 4
+OVERLAY_TRACKED_ONLY = 1
+OVERLAY_TEXT_MAX, OVERLAY_NAME_LEN, OVERLAY_MAX_NAMES = 24, 16, 4096
+OVERLAY_STATS_DTYPE = np.dtype([("boxes", "<i4"), ("masked", "<i4"), ("labels", "<i4"), ("markers", "<i4"), ("skipped", "<i4"),
+                                ("pixels", "<i4")])  # mars_overlay_stats_t
+
+
+class OverlayOpts(C.Structure):  # mars_hip_overlay_opts_t: zero = default in every field but the frame size
+    _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("src_format", C.c_int), ("src_flags", C.c_uint), ("layers", C.c_uint),
+                ("color_by", C.c_int), ("text", C.c_uint), ("thickness", C.c_int), ("radius", C.c_int), ("scale", C.c_int), ("alpha", C.c_int),
+                ("no_key", C.c_ubyte * 3), ("min_conf", C.c_float), ("kpt_min_v", C.c_float), ("cls_first", C.c_int), ("cls_count", C.c_int),
+                ("min_hits", C.c_int), ("flags", C.c_uint), ("n_palette", C.c_int), ("palette", C.c_void_p), ("n_names", C.c_int),
+                ("names", C.c_void_p)]
+
+
 MOTION_STREAM_MAJOR, MOTION_FRAME_DIFF = 1, 2                             # MARS_MOTION_*
 MOTION_MAX_ZONES = 64
 MOTION_STATS_DTYPE = np.dtype([("active", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("first", "<i4")])  # mars_motion_stats_t
@@ -245,6 +262,7 @@ class MotionOpts(C.Structure):  # mars_hip_motion_opts_t: zero = default in ever
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
 assert MOTION_STATS_DTYPE.itemsize == 24 and MOTION_DET_DTYPE.itemsize == 8 and C.sizeof(MotionOpts) == 32
 assert REDACT_STATS_DTYPE.itemsize == 16 and C.sizeof(RedactOpts) == 52
+assert OVERLAY_STATS_DTYPE.itemsize == 24 and C.sizeof(OverlayOpts) == 104
 assert TILE_DTYPE.itemsize == 16 and TILE_SRC_DTYPE.itemsize == 8 and TILE_STATS_DTYPE.itemsize == 24 and C.sizeof(TileOpts) == 48
 assert OBB_DTYPE.itemsize == 32 and C.sizeof(ObbOpts) == 36
 assert POSE_DTYPE.itemsize == KPT_DTYPE.itemsize == 12 and C.sizeof(PoseOpts) == 48
@@ -308,6 +326,8 @@ EXPORTS = {
                    "mars_tile_grid", "mars_hip_preprocess_tiles_device", "mars_hip_preprocess_tiles", "mars_hip_merge_tiles_device",
                    "mars_hip_tile_results", "mars_hip_tile_frames", "mars_hip_merge_tiles", "mars_hip_tile_ms", "mars_yolo_tile_frames", "mars_yolo_merge_tiles",
                    "mars_yolo_redact_frames", "mars_hip_redact_device", "mars_hip_redact_results", "mars_hip_redact", "mars_hip_redact_ms",
+                   "mars_overlay_default_palette", "mars_overlay_rgb_to_yuv", "mars_overlay_glyph", "mars_overlay_text", "mars_yolo_overlay_frames",
+                   "mars_hip_overlay_device", "mars_hip_overlay_results", "mars_hip_overlay", "mars_hip_overlay_ms",
                    "mars_hip_motion_create", "mars_hip_motion_reset", "mars_hip_motion_free", "mars_hip_motion_grid", "mars_hip_motion_read",
                    "mars_yolo_motion_frames", "mars_hip_motion_device", "mars_hip_motion_results", "mars_hip_motion_detections_device",
                    "mars_hip_motion_det_results", "mars_yolo_motion_boxes", "mars_hip_motion_ms"],
@@ -490,6 +510,19 @@ def lib():
     L.mars_hip_redact.argtypes = [P(MarsModel), C.c_void_p, P(RedactOpts), C.c_void_p]
     L.mars_hip_redact_ms.restype = C.c_float
     L.mars_hip_redact_ms.argtypes = [P(MarsModel)]
+    L.mars_overlay_default_palette.argtypes = [C.c_void_p]
+    L.mars_overlay_rgb_to_yuv.restype = None
+    L.mars_overlay_rgb_to_yuv.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
+    L.mars_overlay_glyph.restype = None
+    L.mars_overlay_glyph.argtypes = [C.c_int, C.c_void_p]
+    L.mars_overlay_text.argtypes = [C.c_uint, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
+    L.mars_yolo_overlay_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int, P(OverlayOpts), C.c_void_p, C.c_void_p]
+    L.mars_hip_overlay_device.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, P(OverlayOpts)]
+    L.mars_hip_overlay_results.argtypes = [P(MarsModel), C.c_void_p]
+    L.mars_hip_overlay.argtypes = [P(MarsModel), C.c_void_p, P(OverlayOpts), C.c_void_p]
+    L.mars_hip_overlay_ms.restype = C.c_float
+    L.mars_hip_overlay_ms.argtypes = [P(MarsModel)]
     L.mars_hip_motion_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_void_p)]
     L.mars_hip_motion_reset.argtypes = [C.c_void_p, C.c_int]
     L.mars_hip_motion_free.argtypes = [C.c_void_p]
@@ -820,6 +853,121 @@ def redact_frames(frames, boxes, frame_of_box, opts, mask_words=None, mask_of_bo
                                        C.byref(opts), out.ctypes.data, stats.ctypes.data)
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_redact_frames")
+    return out.reshape(n, fb), stats
+
+
+def overlay_default_palette():
+    """mars_overlay_default_palette: the built-in palette, uint8 [16][3] R, G, B; host only"""
+    out = np.zeros((16, 3), dtype=np.uint8)
+    assert lib().mars_overlay_default_palette(out.ctypes.data) == 16
+    return out
+
+
+def rgb_to_yuv(rgb, flags=0):
+    """mars_overlay_rgb_to_yuv: (R, G, B) -> (Y, first stored chroma byte, second), flags = NV12_*; host only"""
+    a = np.array([int(v) for v in rgb], dtype=np.uint8)
+    out = np.zeros(3, dtype=np.uint8)
+    lib().mars_overlay_rgb_to_yuv(a.ctypes.data, int(flags), out.ctypes.data)
+    return tuple(int(v) for v in out)
+
+
+def overlay_glyph(byte):
+    """mars_overlay_glyph: the seven row bytes of the glyph that `byte` (any int) shows as; host only"""
+    out = np.zeros(7, dtype=np.uint8)
+    lib().mars_overlay_glyph(int(byte), out.ctypes.data)
+    return out
+
+
+def overlay_names(names):
+    """a list of str / bytes -> the NUL-padded table uint8 [n][OVERLAY_NAME_LEN] (longer names are cut)"""
+    t = np.zeros((len(names), OVERLAY_NAME_LEN), dtype=np.uint8)
+    for i, s in enumerate(names):
+        b = (s.encode("latin-1") if isinstance(s, str) else bytes(s))[:OVERLAY_NAME_LEN]
+        t[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+    return t
+
+
+def overlay_text(cls, conf, track_id=-1, text=0, names=None):
+    """mars_overlay_text: the label bytes the device form composes for a detection; names: None, a list, or an overlay_names() table; host only"""
+    t = None
+    if names is not None:
+        t = names if isinstance(names, np.ndarray) else overlay_names(names)
+        t = np.ascontiguousarray(t, dtype=np.uint8).reshape(-1, OVERLAY_NAME_LEN)
+    out = np.zeros(OVERLAY_TEXT_MAX, dtype=np.uint8)
+    n = lib().mars_overlay_text(int(text), t.ctypes.data if t is not None and len(t) else None, len(t) if t is not None else 0, int(cls),
+                                int(track_id), C.c_float(float(conf)), out.ctypes.data)
+    return out[:n].tobytes()
+
+
+def overlay_opts(w, h, fmt=CAMERA_RGB, src_flags=0, layers=0, color_by=OVERLAY_BY_CLASS, text=0, thickness=0, radius=0, scale=0, alpha=0,
+                 no_key=(0, 0, 0), min_conf=0.0, kpt_min_v=0.0, classes=None, min_hits=0, tracked_only=False, flags=None, palette=None, names=None):
+    """mars_hip_overlay_opts_t for frames of w x h.  layers: OVERLAY_MASKS | _BOXES | _KEYPOINTS | _LABELS (0: boxes and labels); color_by:
+    OVERLAY_BY_CLASS / _BY_TRACK / _FIXED; text: OVERLAY_TEXT_* (0: class and confidence); palette: uint8 [P][3] (None: the built-in one); names:
+    a list or an overlay_names() table; classes = (first, count): the class window; zero means default everywhere else.  The returned record
+    keeps the palette and names arrays alive"""
+    o = OverlayOpts(int(w), int(h), int(fmt), int(src_flags), int(layers), int(color_by), int(text), int(thickness), int(radius), int(scale),
+                    int(alpha))
+    o.no_key[:] = [int(v) for v in no_key]
+    o.min_conf, o.kpt_min_v, o.min_hits = float(min_conf), float(kpt_min_v), int(min_hits)
+    if classes is not None:
+        o.cls_first, o.cls_count = int(classes[0]), int(classes[1])
+    o.flags = int(flags) if flags is not None else (OVERLAY_TRACKED_ONLY if tracked_only else 0)
+    if palette is not None:
+        o._palette = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 3)
+        o.n_palette, o.palette = len(o._palette), o._palette.ctypes.data
+    if names is not None:
+        o._names = np.ascontiguousarray(names if isinstance(names, np.ndarray) else overlay_names(names), dtype=np.uint8).reshape(-1, OVERLAY_NAME_LEN)
+        o.n_names, o.names = len(o._names), o._names.ctypes.data
+    return o
+
+
+def overlay_frames(frames, boxes, frame_of_box, opts, keys=None, texts=None, mask_words=None, mask_of_box=None, kpts=None, inplace=False):
+    """mars_yolo_overlay_frames: frames (uint8, [n] frames of opts.src_w x opts.src_h, RGB or NV12) with the boxes (DET_DTYPE records, box i in
+    frame frame_of_box[i]) painted in on the GPU -> (the painted frames, uint8 [n][frame bytes]; OVERLAY_STATS_DTYPE [n]).  keys = int32
+    [n_boxes] colour keys; texts = a list of bytes / str or uint8 [n_boxes][OVERLAY_TEXT_MAX]; mask_words / mask_of_box as in redact_frames;
+    kpts = KPT_DTYPE [n_boxes][K]; each may be None.  inplace: the in-place kernels run (on a copy: the caller's array is left alone)"""
+    a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    fb = redact_frame_bytes(opts)
+    if fb <= 0 or a.size == 0 or a.size % fb:
+        raise ValueError("frames of %d x %d are %d bytes each, got %d" % (opts.src_w, opts.src_h, fb, a.size))
+    b = np.ascontiguousarray(boxes, dtype=DET_DTYPE).reshape(-1)
+    fo = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
+    if fo.size != b.size:
+        raise ValueError("one frame index per box")
+    ky = tx = kp = mw = mo = None
+    K = 0
+    if keys is not None:
+        ky = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+        if ky.size != b.size:
+            raise ValueError("one key per box")
+    if texts is not None:
+        if isinstance(texts, np.ndarray):
+            tx = np.ascontiguousarray(texts, dtype=np.uint8).reshape(-1, OVERLAY_TEXT_MAX)
+        else:
+            tx = np.zeros((len(texts), OVERLAY_TEXT_MAX), dtype=np.uint8)
+            for i, s in enumerate(texts):
+                t = (s.encode("latin-1") if isinstance(s, str) else bytes(s))[:OVERLAY_TEXT_MAX]
+                tx[i, :len(t)] = np.frombuffer(t, dtype=np.uint8)
+        if len(tx) != b.size:
+            raise ValueError("one text per box")
+    if kpts is not None and b.size:
+        kp = np.ascontiguousarray(kpts, dtype=KPT_DTYPE).reshape(b.size, -1)
+        K = kp.shape[1]
+    if mask_of_box is not None:
+        mo = np.ascontiguousarray(mask_of_box, dtype=np.int32).reshape(-1)
+        pitch = (opts.src_w + 31) // 32
+        mw = np.ascontiguousarray(mask_words if mask_words is not None else np.zeros(0), dtype=np.uint32).reshape(-1)
+        if mo.size != b.size or mw.size % (opts.src_h * pitch) or (mo.size and int(mo.max()) >= mw.size // (opts.src_h * pitch)):
+            raise ValueError("mask_of_box: one index per box, inside mask_words [.][%d][%d]" % (opts.src_h, pitch))
+    n = a.size // fb
+    out = a.copy() if inplace else np.zeros_like(a)
+    src = out if inplace else a
+    stats = np.zeros(n, dtype=OVERLAY_STATS_DTYPE)
+    ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+    rc = lib().mars_yolo_overlay_frames(src.ctypes.data, n, ptr(b), ptr(fo) if b.size else None, b.size, ptr(ky), ptr(tx), ptr(mw), ptr(mo), ptr(kp), K,
+                                        C.byref(opts), out.ctypes.data, stats.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_overlay_frames")
     return out.reshape(n, fb), stats
 
 
@@ -1861,6 +2009,39 @@ class Model:
     def redact_ms(self):
         """device time (ms) of the last redact_device() (mars_hip_redact_ms); < 0: not available"""
         return float(lib().mars_hip_redact_ms(self.p))
+
+    def overlay_device(self, frames_dev, opts, dst_dev=None):
+        """paint the detections the last detect*(device=True) left in HBM -- and, where opts asks for them, this batch's track ids, native
+        masks and keypoints -- into this model's batch of frames at device pointer frames_dev (overlay_opts(); dst_dev None: in place);
+        enqueues only (mars_hip_overlay_device)"""
+        rc = lib().mars_hip_overlay_device(self.p, C.c_void_p(frames_dev), C.c_void_p(dst_dev) if dst_dev else None, C.byref(opts))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_overlay_device")
+
+    def overlay_results(self):
+        """-> OVERLAY_STATS_DTYPE [batch] of the last overlay_device() (mars_hip_overlay_results); waits"""
+        stats = np.zeros(self.batch, dtype=OVERLAY_STATS_DTYPE)
+        rc = lib().mars_hip_overlay_results(self.p, stats.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_overlay_results")
+        return stats
+
+    def overlay(self, frames, opts):
+        """overlay_device on frames in host memory (uint8, this model's batch of them): -> (the painted frames, the statistics); the caller's
+        array is left alone (mars_hip_overlay works in place on a copy); waits"""
+        a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1).copy()
+        fb = redact_frame_bytes(opts)
+        if a.size != fb * self.batch:
+            raise ValueError("%d frames of %d bytes, got %d bytes" % (self.batch, fb, a.size))
+        stats = np.zeros(self.batch, dtype=OVERLAY_STATS_DTYPE)
+        rc = lib().mars_hip_overlay(self.p, a.ctypes.data, C.byref(opts), stats.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_overlay")
+        return a.reshape(self.batch, fb), stats
+
+    def overlay_ms(self):
+        """device time (ms) of the last overlay_device() (mars_hip_overlay_ms); < 0: not available"""
+        return float(lib().mars_hip_overlay_ms(self.p))
 
     def motion_detections_device(self, motion, expand=0.0):
         """THIS model is the detector: the detections its last detect_*_device call left in HBM are counted against the maps of motion's
