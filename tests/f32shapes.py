@@ -49,8 +49,10 @@ def shape_id(fam, shape):
     return fam + ":" + "x".join(str(q) for q in shape)
 
 
-def _conv_chain(rng, h, w, ic, oc, k, st, pad, silu, add):
-    """conv (+ SIGMOID / MUL) (+ ADD with a second graph input) on NCHW floats -> (file bytes, output tensor, out_h, out_w)"""
+def _conv_chain(rng, h, w, ic, oc, k, st, pad, silu, add, weights=None, bias=None):
+    """conv (+ SIGMOID / MUL) (+ ADD with a second graph input) on NCHW floats -> (file bytes, output tensor, out_h, out_w).
+    `weights` ([oc][ic][k][k]) / `bias` ([oc]) replace the random ones (tests/f32edges.py); left out, the byte stream is the one
+    golden.json "conv_f32_family" was made from."""
     G = marsfile.Graph()
     F, N = marsfile.F32, marsfile.NCHW
     if pad == "same":
@@ -60,8 +62,14 @@ def _conv_chain(rng, h, w, ic, oc, k, st, pad, silu, add):
     x = G.tensor([1, ic, h, w], dtype=F, fmt=N)
     a = G.tensor([1, oc, oh, ow], dtype=F, fmt=N)
     amp = 1.7 / (k * k * ic) ** 0.5
-    wt = G.tensor([oc, ic, k, k], dtype=F, fmt=marsfile.OIHW, data=((rng.random((oc, ic, k, k), dtype=np.float32) * 2 - 1) * amp).astype(np.float32))
-    b = G.tensor([oc], dtype=F, fmt=marsfile.D1, data=((rng.random(oc, dtype=np.float32) * 2 - 1) * 0.1).astype(np.float32))
+    wd = ((rng.random((oc, ic, k, k), dtype=np.float32) * 2 - 1) * amp).astype(np.float32)
+    bd = ((rng.random(oc, dtype=np.float32) * 2 - 1) * 0.1).astype(np.float32)
+    if weights is not None:
+        wd = np.ascontiguousarray(weights, dtype=np.float32).reshape(oc, ic, k, k)
+    if bias is not None:
+        bd = np.ascontiguousarray(bias, dtype=np.float32).reshape(oc)
+    wt = G.tensor([oc, ic, k, k], dtype=F, fmt=marsfile.OIHW, data=wd)
+    b = G.tensor([oc], dtype=F, fmt=marsfile.D1, data=bd)
     G.conv(x, a, wt, b, (k, k), (st, st), pad=marsfile.PAD_SAME if pad == "same" else marsfile.PAD_VALID)
     out = a
     if silu:
@@ -79,31 +87,69 @@ def _conv_chain(rng, h, w, ic, oc, k, st, pad, silu, add):
     return G.serialise(ins, [out]), out, oh, ow
 
 
-def split_case(shape):
-    """-> dict(d, out, B, xs = input frames (float32 arrays, frame f takes xs[f % len(xs)]), rs = None)"""
-    h, w, ic, oc, k, st, pad, B, silu = shape
+def _given(case, frames, resid, batch):
+    """the optional arguments of the three builders below: `frames` / `resid` replace the random input / residual frames (lists of float32
+    arrays), `batch` the shape's batch"""
+    if frames is not None:
+        case["xs"] = [np.ascontiguousarray(q, dtype=np.float32).reshape(-1) for q in frames]
+    if resid is not None and case["rs"] is not None:
+        case["rs"] = [np.ascontiguousarray(q, dtype=np.float32).reshape(-1) for q in resid]
+    if batch is not None:
+        case["B"] = batch
+    return case
+
+
+def split_case(shape, weights=None, bias=None, frames=None, silu=None, batch=None):
+    """-> dict(d, out, B, xs = input frames (float32 arrays, frame f takes xs[f % len(xs)]), rs = None).  The optional arguments
+    (weights, bias, input frames, SiLU on / off, batch) are tests/f32edges.py's; without them: the graph and frames of golden.json"""
+    h, w, ic, oc, k, st, pad, B, silu_ = shape
     rng = np.random.default_rng(h * 1000 + w * 10 + k)
-    d, out, oh, ow = _conv_chain(rng, h, w, ic, oc, k, st, pad, silu, False)
+    d, out, oh, ow = _conv_chain(rng, h, w, ic, oc, k, st, pad, silu_ if silu is None else silu, False, weights, bias)
     xs = [(rng.random(ic * h * w, dtype=np.float32) * 2 - 1).astype(np.float32) for _ in range(min(B, 4))]
-    return dict(d=d, out=out, B=B, xs=xs, rs=None, oh=oh, ow=ow)
+    return _given(dict(d=d, out=out, B=B, xs=xs, rs=None, oh=oh, ow=ow), frames, None, batch)
 
 
-def patch_case(shape):
-    h, w, ic, oc, k, st, B, silu, add = shape
+def patch_case(shape, weights=None, bias=None, frames=None, resid=None, silu=None, batch=None):
+    h, w, ic, oc, k, st, B, silu_, add = shape
     rng = np.random.default_rng(h * 1000 + w * 10 + k + st)
-    d, out, oh, ow = _conv_chain(rng, h, w, ic, oc, k, st, "same", silu, add)
+    d, out, oh, ow = _conv_chain(rng, h, w, ic, oc, k, st, "same", silu_ if silu is None else silu, add, weights, bias)
     nx = min(B, 4)
     xs = [(rng.random(ic * h * w, dtype=np.float32) * 2 - 1).astype(np.float32) for _ in range(nx)]
     rs = [(rng.random(oc * oh * ow, dtype=np.float32) * 2 - 1).astype(np.float32) for _ in range(nx)]
-    return dict(d=d, out=out, B=B, xs=xs, rs=rs if add else None, oh=oh, ow=ow)
+    return _given(dict(d=d, out=out, B=B, xs=xs, rs=rs if add else None, oh=oh, ow=ow), frames, resid, batch)
 
 
-def stem_case(shape):
-    h, w, ic, oc, k, B, silu = shape
+def stem_case(shape, weights=None, bias=None, frames=None, silu=None, batch=None):
+    h, w, ic, oc, k, B, silu_ = shape
     rng = np.random.default_rng(h * 1000 + w * 10 + k + ic)
-    d, out, oh, ow = _conv_chain(rng, h, w, ic, oc, k, 2, "same", silu, False)
+    d, out, oh, ow = _conv_chain(rng, h, w, ic, oc, k, 2, "same", silu_ if silu is None else silu, False, weights, bias)
     xs = [(rng.random(ic * h * w, dtype=np.float32) * 2 - 1).astype(np.float32) for _ in range(min(B, 3))]
-    return dict(d=d, out=out, B=B, xs=xs, rs=None, oh=oh, ow=ow)
+    return _given(dict(d=d, out=out, B=B, xs=xs, rs=None, oh=oh, ow=ow), frames, None, batch)
+
+
+# the virtual concat of tests/test_gpu_f32_edges.py (checked against the oracle in tests/test_f32_edges_cpu.py)
+VC = (20, 20, 32, 40, 3)  # h, w, channels of each concat input, reader's channels, batch
+
+
+def vcat_graph(wa, wb, wr, br):
+    """a 1 x 1 convolution over a CONCAT of two maps, each a 1 x 1 convolution of the ONE-channel graph input (weights wa, wb, no bias): under
+    f32_mfma 3 / 4 the planner never materialises the concat (virtual_concat_f32) -> (file bytes, the concat tensor)"""
+    h, w, c, oc, B = VC
+    G = marsfile.Graph()
+    F, N = marsfile.F32, marsfile.NCHW
+    x = G.tensor([1, 1, h, w], dtype=F, fmt=N)
+    ins = []
+    for wd in (wa, wb):
+        a = G.tensor([1, c, h, w], dtype=F, fmt=N)
+        G.conv(x, a, G.tensor([c, 1, 1, 1], dtype=F, fmt=marsfile.OIHW, data=np.ascontiguousarray(wd, dtype=np.float32).reshape(c, 1, 1, 1)),
+               G.tensor([c], dtype=F, fmt=marsfile.D1, data=np.zeros(c, dtype=np.float32)), (1, 1), (1, 1))
+        ins.append(a)
+    cat = G.tensor([1, 2 * c, h, w], dtype=F, fmt=N)
+    G.concat(ins, cat, axis=1)
+    o = G.tensor([1, oc, h, w], dtype=F, fmt=N)
+    G.conv(cat, o, G.tensor([oc, 2 * c, 1, 1], dtype=F, fmt=marsfile.OIHW, data=np.ascontiguousarray(wr, dtype=np.float32).reshape(oc, 2 * c, 1, 1)),
+           G.tensor([oc], dtype=F, fmt=marsfile.D1, data=np.ascontiguousarray(br, dtype=np.float32)), (1, 1), (1, 1))
+    return G.serialise([x], [o]), cat
 
 
 FAMILIES = (("split", SPLIT, split_case), ("patch", PATCH, patch_case), ("stem", STEM, stem_case))

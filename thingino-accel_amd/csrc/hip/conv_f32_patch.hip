@@ -117,26 +117,28 @@ struct fpatch_geom_t {
 };
 
 __device__ __forceinline__ int pa_lds_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 2)) << 4); }
-__device__ __forceinline__ float psilu_fast(float v) { // as conv_f32_split's three-product mode: v_exp_f32 / v_rcp_f32
+__device__ __forceinline__ float psilu_fast(float v) { // as conv_f32_split's three-product mode (silu_fast there: why the halves)
     const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
+    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
 }
 
 // N floats (one pixel, N consecutive channels) -> N / 2 dwords of hi, N / 2 of mid.  hi = bf16(x) (round to nearest even), mid = bf16(x - hi);
-// the subtraction is exact.  Not finite (hi = +-inf or NaN, i.e. |x| >= 2^128 - 2^119 or x not finite): mid = 0, so that the product sums
-// see the inf / NaN once instead of the NaN an inf - inf residual would be
+// the subtraction is exact.  hi SATURATES at the largest bf16 (one v_med3_f32): for |x| >= 2^128 - 2^119 or x = +-inf, where bf16(x) would be
+// +-inf, hi stays finite and the residual -- mid -- is the infinity.  The mid plane meets only the weights' hi plane, so the product sums see
+// inf * w.hi once and give sign(w) * inf as the reference does; in the hi plane the infinity also met w.mid -- inf * 0, or inf times a residual
+// of the other sign -- and came out NaN (ADVICE r4 asked for no inf - inf residual; conv_f32_split.hip splitn has the same rule).  FLT_MAX
+// still gives inf: hi + mid = 2^128.
 template <int N>
 __device__ __forceinline__ void psplit(const float (&x)[N], int (&hi)[N / 2], int (&mid)[N / 2]) {
 #pragma unroll
     for (int i = 0; i < N / 2; i++) {
         const f32x2 v = {x[2 * i], x[2 * i + 1]};
-        const int h = __builtin_bit_cast(int, __builtin_convertvector(v, bf16x2));
+        const f32x2 vh = {__builtin_amdgcn_fmed3f(v[0], -0x1.fep+127f, 0x1.fep+127f), __builtin_amdgcn_fmed3f(v[1], -0x1.fep+127f, 0x1.fep+127f)};
+        const int h = __builtin_bit_cast(int, __builtin_convertvector(vh, bf16x2));
         const float h0 = __int_as_float(h << 16), h1 = __int_as_float(h & (int)0xffff0000);
         f32x2 r; // two plain subtractions (left to itself the compiler packs them into a v_pk_add_f32 behind two register moves)
         asm("v_sub_f32 %0, %1, %2" : "=v"(r[0]) : "v"(v[0]), "v"(h0));
         asm("v_sub_f32 %0, %1, %2" : "=v"(r[1]) : "v"(v[1]), "v"(h1));
-        r[0] = __builtin_isfinite(h0) ? r[0] : 0.0f;
-        r[1] = __builtin_isfinite(h1) ? r[1] : 0.0f;
         hi[i] = h;
         mid[i] = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
     }

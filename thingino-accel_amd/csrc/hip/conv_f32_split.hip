@@ -80,9 +80,13 @@ __device__ __forceinline__ float silu_split(float v) { // as conv_f32.hip: the e
 }
 // three piece products (relative error per product up to 2^-16) do not need libm's last bit: v_exp_f32 and v_rcp_f32, 1 ulp each --
 // the exact form above is double-precision arithmetic and a table, a fifth of the kernel's time on every layer
+// v / (1 + e) as (v / 2) * rcp((1 + e) / 2): v_rcp_f32 returns 0 where its result would be a denormal, i.e. for 1 + e > 2^126 (v <
+// -87.34, a true value of up to 1.0e-36 came out as -0); halved, the operand stays below 2^127 until v = -88.03, where the true value
+// is 5.2e-37.  No larger factor: v / 2 is exact down to |v| = 2^-125 and the product never exceeds |v|, so nothing changes at tiny or
+// huge v (a factor 2^-32 made v 2^-32 a denormal below |v| = 2^-94 and lost its bits).  The fma rounds once, like the addition it replaces.
 __device__ __forceinline__ float silu_fast(float v) {
-    const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f); // exp(-v); +inf for v << 0: rcp -> 0, v * 0 = -0
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
+    const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f); // exp(-v)
+    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
 }
 __device__ __forceinline__ int a_lds_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 2)) << 4); }
 __device__ __forceinline__ int b_lds_off(int r, int chunk) { // pixel r of the tile, 16-byte chunk (8 taps) of its 64-byte row
@@ -110,23 +114,42 @@ static sdiv_t make_sdiv(unsigned d) {
 // two at a time): hi = bf16(x), mid = bf16(x - hi), lo = x - hi - mid.  Every subtraction is exact (x - hi has at most 16
 // significant bits, x - hi - mid at most 8, a bf16 value), so x == hi + mid + lo exactly; with two planes |x - hi - mid| <=
 // 2^-17 |x|, errors of either sign.
+// A value bf16 would round to +-inf (x = +-inf, or |x| >= 2^128 - 2^119) keeps a FINITE hi and the LAST plane carries the infinity: the
+// last plane of the input meets only the weights' hi plane (mid * hi, lo * hi), so the sum sees inf * w.hi once and gives sign(w) * inf
+// as the reference does.  With the infinity in the hi plane it also met w.mid and w.lo -- inf * 0, or inf times a residual of the other
+// sign -- and inf - inf as its own residual: NaN.  Two planes: hi saturates at the largest bf16 (two packed 16-bit minima per PAIR of
+// elements: this is the K loop), the residual is then +-inf by itself; FLT_MAX still comes out as inf (hi + mid = 2^128).  Three
+// planes (not the benchmark's mode): hi = mid = 0 and lo = bf16(x).  A NaN ends as a NaN piece either way.
+#define NONFINITE_BF16 0x1.ffp+127f // 2^128 - 2^119: from here on bf16 rounding gives inf
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 template <int N, int NPL>
 __device__ __forceinline__ void splitn(const float (&x)[N], int (&hi)[N / 2], int (&mid)[N / 2], int (&lo)[N / 2]) {
 #pragma unroll
     for (int i = 0; i < N / 2; i++) { // (element 2i, element 2i + 1) -> one dword per plane, element 2i in the low half
         const f32x2 v = {x[2 * i], x[2 * i + 1]};
-        const int h = __builtin_bit_cast(int, __builtin_convertvector(v, bf16x2));
+        const bool f0 = __builtin_fabsf(v[0]) < NONFINITE_BF16, f1 = __builtin_fabsf(v[1]) < NONFINITE_BF16; // (false for a NaN; NPL == 3 only)
+        const f32x2 vh = {NPL == 3 && !f0 ? 0.0f : v[0], NPL == 3 && !f1 ? 0.0f : v[1]};
+        int h = __builtin_bit_cast(int, __builtin_convertvector(vh, bf16x2));
+        if (NPL == 2) { // saturate both halves at once: +inf / +NaN (0x7f80 ..) -> 0x7f7f as signed, -inf / -NaN (0xff80 ..) -> 0xff7f as unsigned
+            h = __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(s16x2, h), (s16x2){0x7f7f, 0x7f7f}));
+            h = __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(u16x2, h), (u16x2){0xff7f, 0xff7f}));
+        }
         const f32x2 hf = {__int_as_float(h << 16), __int_as_float(h & (int)0xffff0000)};
-        const f32x2 r = v - hf;
-        const int m = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
+        const f32x2 r = v - hf; // (+-inf: itself)
         hi[i] = h;
-        mid[i] = m;
         if (NPL == 3) {
+            const f32x2 rm = {f0 ? r[0] : 0.0f, f1 ? r[1] : 0.0f};
+            const int m = __builtin_bit_cast(int, __builtin_convertvector(rm, bf16x2));
             const f32x2 mf = {__int_as_float(m << 16), __int_as_float(m & (int)0xffff0000)};
+            mid[i] = m;
             lo[i] = __builtin_bit_cast(int, __builtin_convertvector(r - mf, bf16x2)); // exact
-        } else lo[i] = 0;
+        } else {
+            mid[i] = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
+            lo[i] = 0;
+        }
     }
 }
 
@@ -494,12 +517,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
 #pragma unroll
                     for (int j = 0; j < 4; j++) x[j] = p.silu ? silu_fast(acc[a][c][j]) : acc[a][c][j];
                     int hi[2], mid[2], lo_[2];
-                    splitn<4, 2>(x, hi, mid, lo_);
-#pragma unroll
-                    for (int i = 0; i < 2; i++) { // no residual of a non-finite hi (as the weights' packer and conv_f32_patch's split)
-                        const float h0 = __int_as_float(hi[i] << 16), h1 = __int_as_float(hi[i] & (int)0xffff0000);
-                        mid[i] = (__builtin_isfinite(h0) ? mid[i] & 0xffff : 0) | (__builtin_isfinite(h1) ? mid[i] & (int)0xffff0000 : 0);
-                    }
+                    splitn<4, 2>(x, hi, mid, lo_); // (an infinite result: a finite hi, the infinity in mid -- splitn's rule)
                     const auto s0 = __builtin_amdgcn_permlane16_swap((unsigned)mid[0], (unsigned)hi[0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap((unsigned)mid[1], (unsigned)hi[1], false, false);
                     const int chunk = (oc0 + wm * TM + a * 16) / 8 + (fc >> 1);

@@ -49,22 +49,22 @@ struct stem_geom_t {
     unsigned ntiles, in_bytes, per;
 };
 
-__device__ __forceinline__ float stem_silu(float v) {
+__device__ __forceinline__ float stem_silu(float v) { // (conv_f32_split.hip silu_fast: why the halves)
     const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
+    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
 }
-// 8 floats -> 4 dwords hi, 4 dwords mid (as conv_f32_patch.hip: round to nearest, exact residual, no residual of a non-finite hi)
+// 8 floats -> 4 dwords hi, 4 dwords mid (as conv_f32_patch.hip: round to nearest, exact residual; hi saturates at the largest bf16,
+// so that an infinity is carried by the mid piece alone)
 __device__ __forceinline__ void stem_split8(const float (&x)[8], v4i &hi, v4i &mid) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const f32x2 v = {x[2 * i], x[2 * i + 1]};
-        const int h = __builtin_bit_cast(int, __builtin_convertvector(v, bf16x2));
+        const f32x2 vh = {__builtin_amdgcn_fmed3f(v[0], -0x1.fep+127f, 0x1.fep+127f), __builtin_amdgcn_fmed3f(v[1], -0x1.fep+127f, 0x1.fep+127f)};
+        const int h = __builtin_bit_cast(int, __builtin_convertvector(vh, bf16x2));
         const float h0 = __int_as_float(h << 16), h1 = __int_as_float(h & (int)0xffff0000);
         f32x2 r;
         asm("v_sub_f32 %0, %1, %2" : "=v"(r[0]) : "v"(v[0]), "v"(h0));
         asm("v_sub_f32 %0, %1, %2" : "=v"(r[1]) : "v"(v[1]), "v"(h1));
-        r[0] = __builtin_isfinite(h0) ? r[0] : 0.0f;
-        r[1] = __builtin_isfinite(h1) ? r[1] : 0.0f;
         hi[i] = h;
         mid[i] = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
     }

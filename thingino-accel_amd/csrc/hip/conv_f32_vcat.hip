@@ -29,9 +29,9 @@ struct vcat_args_t {
     int hw, planes;        // pixels per plane, planes summed (L / HW + 1)
 };
 
-__device__ __forceinline__ float vcat_silu(float v) {
+__device__ __forceinline__ float vcat_silu(float v) { // (conv_f32_split.hip silu_fast: why the halves)
     const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
+    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
 }
 // bf16, round to nearest even (a NaN stays one): as mhip_conv_f32_split_pack and mars_hip_write_tensor cut records
 __device__ __forceinline__ unsigned vcat_bf16(float x) {
@@ -110,9 +110,9 @@ __global__ __launch_bounds__(256) void conv_f32_vcat_head(const mhip_conv_f32_t 
         for (int k = 0; k < 4; k++) v += red[k][wv * VC_PX + i][lane];
         if (p.silu) v = vcat_silu(v);
         if (p.out_rec) { // the two pieces of this channel in the record of pixel px (conv_f32_split.hip says what a record is)
-            const unsigned h = vcat_bf16(v);
+            const unsigned h = vcat_bf16(__builtin_amdgcn_fmed3f(v, -0x1.fep+127f, 0x1.fep+127f)); // hi saturates: an infinity is carried by mid alone (conv_f32_split.hip splitn)
             const float hv = __uint_as_float(h << 16);
-            const float r = hv - hv == 0.0f ? v - hv : 0.0f; // no residual of a non-finite hi
+            const float r = v - hv;
             unsigned short *rec = (unsigned short *)((char *)p.out + (size_t)f * p.out_stride + ((size_t)(oc >> 3) * a.hw + px) * 32u);
             rec[oc & 7] = (unsigned short)h;
             rec[8 + (oc & 7)] = (unsigned short)vcat_bf16(r);

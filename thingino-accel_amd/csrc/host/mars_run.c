@@ -857,10 +857,12 @@ mars_error_t mars_hip_write_tensor(mars_model_t *model, int ti, int frame, const
                 memcpy(&x, &f[(size_t)c * t->rec_hw + px], 4);
                 uint32_t b;
                 memcpy(&b, &x, 4);
-                const uint16_t h = (b & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((b >> 16) | 0x40u) : (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
+                /* hi saturates at the largest bf16: a value bf16 rounds to +-inf keeps a finite hi, the mid piece carries the infinity (conv_f32_split.hip splitn) */
+                const uint16_t h = (b & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((b >> 16) | 0x40u)
+                                   : (b & 0x7fffffffu) >= 0x7f7f8000u ? (uint16_t)((b >> 16 & 0x8000u) | 0x7f7fu) : (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
                 const uint32_t hb = (uint32_t)h << 16;
                 memcpy(&hv, &hb, 4);
-                r = hv - hv == 0.0f ? x - hv : 0.0f;
+                r = x - hv;
                 memcpy(&b, &r, 4);
                 const uint16_t md = (b & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((b >> 16) | 0x40u) : (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
                 uint8_t *q = raw + ((size_t)(c >> 3) * t->rec_hw + px) * 32 + (size_t)(c & 7) * 2;
