@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import cases
+import eltref
 import marsfile
 from conftest import lcg_frame
 from test_oracle import LAYER_KINDS, _layer_graph, model_bytes, model_input
@@ -137,9 +138,8 @@ def test_single_layer_graphs(gpu, orc, kind, exact_f32):
                 assert not g.tensor(ti).any()  # tensor no layer writes: not materialised on the device
                 continue
             want = g.tensor(ti)
-            if t["dtype"] == 0 and kind == "f32_chain":
-                a, b = got.view(np.float32), want.view(np.float32)
-                assert np.all(np.abs(a - b) <= 1e-4 * np.maximum(1, np.abs(b)))
+            if t["dtype"] == 0 and kind == "f32_chain":  # nothing in that graph is approximate: bit for bit, NaN for NaN (tests/eltref.py)
+                eltref.assert_same("f32_chain tensor %d" % ti, got, want, "f32")
             else:
                 assert np.array_equal(got, want), "tensor %d" % ti
     m.close()

@@ -461,4 +461,6 @@ def record_vs_reference(R, marsrt):
     rec["letterbox_sweep"] = obs_letterbox_sweep(R)
     for key, gen, opts, seed in GENERATED:
         rec["generated/" + key] = obs_generated(R, generated_graphs(gen, opts, seed))
+    import test_elt_cpu  # the element-wise and batch-norm cases of tests/eltref.py ("elt/...")
+    rec.update(test_elt_cpu.record(R))
     return {k: fold(v) for k, v in rec.items()}
