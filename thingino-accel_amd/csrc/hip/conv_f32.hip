@@ -19,25 +19,7 @@
 // mars_hip_set_tuning("f32_mfma", 2) uses them everywhere (tolerance verified on the config-5 output), 0 nowhere; 3 / 4 (round 4) =
 // everywhere AND on the bf16 matrix cores with every operand split into two / three bf16 pieces, three / six piece products per
 // product (conv_f32_split.hip); 3 is the config-5 benchmark.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
-#include "../expf_exact.h"
-#include "../mhip.h"
-
-extern "C" hipStream_t mhip_stream_native(void);
-extern "C" int mhip_check(hipError_t e, const char *what);
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-// fused SiLU as the exporter writes it (conv -> SIGMOID -> MUL, reference mars_runtime.c:742-749 and :807-816 float forms):
-// s = 1.0f / (1.0f + expf(-v)); out = v * s -- every step rounded as the reference rounds it, expf as this image's libm
-// (expf_exact.h), so folding the two element-wise layers into the convolution's epilogue changes no bit
-__device__ __forceinline__ float silu_f32(float v) {
-    const float s = 1.0f / (1.0f + expf_exact(-v, expf_exact_tab));
-    return v * s;
-}
+#include "conv_f32_common.hpp"
 
 __global__ __launch_bounds__(256) void conv_f32_kernel(const mhip_conv_f32_t p) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
@@ -65,7 +47,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const mhip_conv_f32_t p) 
         }
     }
     const size_t oi = ((size_t)oc * p.out_h + oy) * p.out_w + ox;
-    const float r = p.silu ? silu_f32(acc) : acc;
+    const float r = p.silu ? silu_exact(acc) : acc;
     out[oi] = p.add ? r + ((const float *)((const char *)p.add + (size_t)f * p.add_stride))[oi] : r;
 }
 
@@ -82,22 +64,6 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const mhip_conv_f32_t p) 
 #define F_BK 16
 #define F_APITCH 80   // floats per k-row of the weight tile  ([k][m], m contiguous): 64 + 16
 #define F_BPITCH 144  // floats per k-row of the input tile   ([k][n], n contiguous): 128 + 16
-struct fdiv_t {
-    unsigned m, s1, s2;
-};
-__device__ __forceinline__ unsigned fdivf(unsigned n, const fdiv_t d) {
-    const unsigned q = __umulhi(d.m, n);
-    return (q + ((n - q) >> d.s1)) >> d.s2;
-}
-static fdiv_t make_fdiv(unsigned d) {
-    fdiv_t r;
-    unsigned l = 0;
-    while ((1ull << l) < d) l++;
-    r.m = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-    r.s1 = l < 1 ? l : 1;
-    r.s2 = l > 0 ? l - 1 : 0;
-    return r;
-}
 
 __global__ __launch_bounds__(256) void conv_f32_mfma(const mhip_conv_f32_t p, const unsigned total_pix, const int K, const int nks,
                                                      const unsigned npt, const fdiv_t dhw, const fdiv_t dow, const fdiv_t dtaps,
@@ -126,8 +92,8 @@ __global__ __launch_bounds__(256) void conv_f32_mfma(const mhip_conv_f32_t p, co
     for (int e = 0; e < 8; e++) {
         const unsigned px = p0 + (unsigned)(nb + e);
         const bool valid = px < total_pix;
-        const unsigned f = fdivf(valid ? px : 0u, dhw), rem = (valid ? px : 0u) - f * hw;
-        const int oy = (int)fdivf(rem, dow), ox = (int)rem - oy * p.out_w;
+        const unsigned f = fdiv(valid ? px : 0u, dhw), rem = (valid ? px : 0u) - f * hw;
+        const int oy = (int)fdiv(rem, dow), ox = (int)rem - oy * p.out_w;
         iy0[e] = valid ? oy * p.stride_h - p.pad_top : -(1 << 28); // invalid pixels fail every bounds test
         ix0[e] = ox * p.stride_w - p.pad_left;
         fbase[e] = (const float *)((const char *)p.in + (size_t)f * p.in_stride);
@@ -146,8 +112,8 @@ __global__ __launch_bounds__(256) void conv_f32_mfma(const mhip_conv_f32_t p, co
         }
         const int k = ks * F_BK + kb;
         const bool kok = k < K;
-        const unsigned ic = fdivf((unsigned)(kok ? k : 0), dtaps), r = (unsigned)(kok ? k : 0) - ic * (unsigned)taps;
-        const int ky = (int)fdivf(r, dkw), kx = (int)r - ky * p.kw;
+        const unsigned ic = fdiv((unsigned)(kok ? k : 0), dtaps), r = (unsigned)(kok ? k : 0) - ic * (unsigned)taps;
+        const int ky = (int)fdiv(r, dkw), kx = (int)r - ky * p.kw;
         const size_t coff = (size_t)ic * plane;
 #pragma unroll
         for (int e = 0; e < 8; e++) {
@@ -207,7 +173,7 @@ __global__ __launch_bounds__(256) void conv_f32_mfma(const mhip_conv_f32_t p, co
     for (int c = 0; c < 4; c++) {
         const unsigned px = p0 + (unsigned)(wn * 64 + c * 16 + fm);
         if (px >= total_pix) continue;
-        const unsigned f = fdivf(px, dhw), rem = px - f * hw;
+        const unsigned f = fdiv(px, dhw), rem = px - f * hw;
         float *out = (float *)((char *)p.out + (size_t)f * p.out_stride);
         const float *addp = p.add ? (const float *)((const char *)p.add + (size_t)f * p.add_stride) : nullptr;
 #pragma unroll
@@ -216,7 +182,7 @@ __global__ __launch_bounds__(256) void conv_f32_mfma(const mhip_conv_f32_t p, co
             for (int j = 0; j < 4; j++) {
                 const int oc = oc0 + wm * 32 + a * 16 + (lane >> 4) * 4 + j;
                 if (oc < p.out_c) {
-                    const float r = p.silu ? silu_f32(acc[a][c][j]) : acc[a][c][j];
+                    const float r = p.silu ? silu_exact(acc[a][c][j]) : acc[a][c][j];
                     out[(size_t)oc * hw + rem] = addp ? r + addp[(size_t)oc * hw + rem] : r;
                 }
             }

@@ -26,21 +26,7 @@
 // Everything index-shaped (geometry, unit table, schedule, weight order) is host code shared with the packer and checked on
 // the CPU against a direct convolution by an emulation of this kernel's addressing (tests/test_host_pack.py).
 // Results: inside north_star's 1e-4 (same three piece products as conv_f32_split; the K order differs, so not bit-equal to it).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../mhip.h"
-
-extern "C" hipStream_t mhip_stream_native(void);
-extern "C" int mhip_check(hipError_t e, const char *what);
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "conv_f32_common.hpp"
 
 #define P_NT 512   // threads per workgroup
 #define P_NB 2     // patch ring slots (chunks)
@@ -55,16 +41,6 @@ extern "C" int mhip_fpatch_stamps(unsigned long long *out, int reset) {
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(fpatch_stamp_sums), z, sizeof z) != hipSuccess) return -1;
     return 0;
 }
-#define STAMP(i)                                                                  \
-    do {                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                        \
-        const unsigned long long t_ = __builtin_readcyclecounter();              \
-        st_acc[i] += t_ - st_last;                                                \
-        st_last = t_;                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                        \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
 #endif
 #ifndef FPATCH_PRIO // experiment: 1 = the staging phase runs at raised wave priority (its few instructions ahead of the mate's MFMAs)
 #define FPATCH_PRIO 0
@@ -72,27 +48,6 @@ extern "C" int mhip_fpatch_stamps(unsigned long long *out, int reset) {
 #ifndef FPATCH_ABL // timing-only ablations (tools/stamps_build.sh fpabl N; wrong results): 1 no MFMAs, 2 no split / LDS writes of the
 #define FPATCH_ABL 0 // patch, 4 no patch loads, 8 no fragment reads; conv_f32_prec: 16 no DMA waits, 32 no patch DMA
 #endif
-
-struct pdiv_t {
-    unsigned m, s1, s2;
-};
-__host__ __device__ __forceinline__ unsigned pdiv(unsigned n, const pdiv_t d) {
-#ifdef __HIP_DEVICE_COMPILE__
-    const unsigned q = __umulhi(d.m, n);
-#else
-    const unsigned q = (unsigned)(((unsigned long long)d.m * n) >> 32);
-#endif
-    return (q + ((n - q) >> d.s1)) >> d.s2;
-}
-static pdiv_t make_pdiv(unsigned d) {
-    pdiv_t r;
-    unsigned l = 0;
-    while ((1ull << l) < d) l++;
-    r.m = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-    r.s1 = l < 1 ? l : 1;
-    r.s2 = l > 0 ? l - 1 : 0;
-    return r;
-}
 
 // geometry of one layer (host-derived; the ints before the dividers are also what mhip_conv_f32_patch_geom reports)
 struct fpatch_geom_t {
@@ -113,34 +68,30 @@ struct fpatch_geom_t {
     int woff, poff, lds_bytes; // LDS byte offsets of the weight stages and the patch ring, total
     int nb, rec, ndma;         // patch ring slots (2; 2 | 4 for record input); input in record format; 1 KB LDS-DMA blocks per slot
     unsigned total_pix, ntiles, nsegs, in_bytes, per, out_bytes;
-    pdiv_t dSW, dHo, dHV, dNS, dgrp, dPWP;
+    fdiv_t dSW, dHo, dHV, dNS, dgrp, dPWP;
 };
 
-__device__ __forceinline__ int pa_lds_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 2)) << 4); }
-__device__ __forceinline__ float psilu_fast(float v) { // as conv_f32_split's three-product mode (silu_fast there: why the halves)
-    const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
-    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
+// ---- what conv_f32_patch and conv_f32_prec share of the tile walk (P_BN = pixels per tile).  Plain functions over explicit operands:
+// conv_f32_prec's scalar state (its DMA ages) must not be captured by anything.  (The record-position decode, the pbase / output-offset
+// decode, the fragment reads, the table copy and the tile run are the same text in both kernels and stay there: hoisted, each changed the code of
+// the 128-channel instantiations -- profiles/f32_common_refactor.md.)
+// first virtual row of tile t
+template <int P_BN>
+__device__ __forceinline__ int fpatch_tile_v0(const fpatch_geom_t &g, const unsigned t) {
+    const unsigned R0 = fdiv(t * P_BN, g.dSW), seg0 = fdiv(R0, g.dHo);
+    return (int)(seg0 * (unsigned)g.HV + (R0 - seg0 * (unsigned)g.H_out) * (unsigned)g.s);
 }
-
-// N floats (one pixel, N consecutive channels) -> N / 2 dwords of hi, N / 2 of mid.  hi = bf16(x) (round to nearest even), mid = bf16(x - hi);
-// the subtraction is exact.  hi SATURATES at the largest bf16 (one v_med3_f32): for |x| >= 2^128 - 2^119 or x = +-inf, where bf16(x) would be
-// +-inf, hi stays finite and the residual -- mid -- is the infinity.  The mid plane meets only the weights' hi plane, so the product sums see
-// inf * w.hi once and give sign(w) * inf as the reference does; in the hi plane the infinity also met w.mid -- inf * 0, or inf times a residual
-// of the other sign -- and came out NaN (ADVICE r4 asked for no inf - inf residual; conv_f32_split.hip splitn has the same rule).  FLT_MAX
-// still gives inf: hi + mid = 2^128.
-template <int N>
-__device__ __forceinline__ void psplit(const float (&x)[N], int (&hi)[N / 2], int (&mid)[N / 2]) {
-#pragma unroll
-    for (int i = 0; i < N / 2; i++) {
-        const f32x2 v = {x[2 * i], x[2 * i + 1]};
-        const f32x2 vh = {__builtin_amdgcn_fmed3f(v[0], -0x1.fep+127f, 0x1.fep+127f), __builtin_amdgcn_fmed3f(v[1], -0x1.fep+127f, 0x1.fep+127f)};
-        const int h = __builtin_bit_cast(int, __builtin_convertvector(vh, bf16x2));
-        const float h0 = __int_as_float(h << 16), h1 = __int_as_float(h & (int)0xffff0000);
-        f32x2 r; // two plain subtractions (left to itself the compiler packs them into a v_pk_add_f32 behind two register moves)
-        asm("v_sub_f32 %0, %1, %2" : "=v"(r[0]) : "v"(v[0]), "v"(h0));
-        asm("v_sub_f32 %0, %1, %2" : "=v"(r[1]) : "v"(v[1]), "v"(h1));
-        hi[i] = h;
-        mid[i] = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
+// source of every patch row of tile t (threads < PR) into row table t & 1: (row byte offset | ~0, first column x_al); esz = bytes per
+// input position (4: a float of a plane; 32: a record)
+template <int P_BN>
+__device__ __forceinline__ void fpatch_fill_rowtab(const mhip_conv_f32_t &p, const fpatch_geom_t &g, int2 *rowtab, const int tid, const unsigned t, const unsigned esz) {
+    if (tid < g.PR) {
+        const unsigned V = (unsigned)fpatch_tile_v0<P_BN>(g, t) + (unsigned)tid;
+        const unsigned seg = fdiv(V, g.dHV), f = fdiv(seg, g.dNS), st = seg - f * (unsigned)g.nstrips;
+        const int iy = (int)(V - seg * (unsigned)g.HV) - g.pad;
+        const bool ok = t < g.ntiles && seg < g.nsegs && iy >= 0 && iy < g.H_in;
+        rowtab[(t & 1) * P_PRCAP + tid] = make_int2(ok ? (int)(f * (unsigned)p.in_stride + (unsigned)(iy * g.W_in) * esz) : -1,
+                                                    (int)st * g.SW * g.s - g.pad - g.dx);
     }
 }
 
@@ -185,7 +136,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
     constexpr int NSUB = 8 / CPI; // items per (row, column group)
     const bool has_item = tid < g.nitems;
     const int icell = tid / NSUB, ich = tid % NSUB;
-    const int ir = (int)pdiv((unsigned)icell, g.dgrp), igq = icell - ir * g.ngrp;
+    const int ir = (int)fdiv((unsigned)icell, g.dgrp), igq = icell - ir * g.ngrp;
     // A pixel's record in the ring: 32 bytes = [8 x hi | 8 x mid] at pixel * 32, NO bank swizzle: the reader's address is then one
     // add per fragment (patch pixel of the lane's row + the unit's offset, both pre-multiplied), the mid half an immediate offset;
     // the two lane groups of a 16-byte read that meet in a bank (pixels 8 apart) cost LDS cycles the staging phase has, where the
@@ -198,21 +149,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
         aitem[i] = patch + (ir * g.PWP + (g.s == 2 ? (v >> 1) + (v & 1) * g.PWH : v)) * 32 + ich * (CPI * 2);
     }
     const int slot_bytes = g.slotpix * 32;
-    // first virtual row of tile t
-    auto tile_v0 = [&](unsigned t) __attribute__((always_inline)) {
-        const unsigned R0 = pdiv(t * P_BN, g.dSW), seg0 = pdiv(R0, g.dHo);
-        return (int)(seg0 * (unsigned)g.HV + (R0 - seg0 * (unsigned)g.H_out) * (unsigned)g.s);
-    };
-    auto fill_rowtab = [&](unsigned t) __attribute__((always_inline)) { // source of every patch row of tile t (threads < PR)
-        if (tid < g.PR) {
-            const unsigned V = (unsigned)tile_v0(t) + (unsigned)tid;
-            const unsigned seg = pdiv(V, g.dHV), f = pdiv(seg, g.dNS), st = seg - f * (unsigned)g.nstrips;
-            const int iy = (int)(V - seg * (unsigned)g.HV) - g.pad;
-            const bool ok = t < g.ntiles && seg < g.nsegs && iy >= 0 && iy < g.H_in;
-            rowtab[(t & 1) * P_PRCAP + tid] = make_int2(ok ? (int)(f * (unsigned)p.in_stride + (unsigned)(iy * g.W_in) * (RECIN ? 32u : 4u)) : -1,
-                                                        (int)st * g.SW * g.s - g.pad - g.dx);
-        }
-    };
+    auto fill_rowtab = [&](unsigned t) __attribute__((always_inline)) { fpatch_fill_rowtab<P_BN>(p, g, rowtab, tid, t, RECIN ? 32u : 4u); };
     // RECIN: item q of this thread = half record tid + 512 q of the slot (patch position / 2, hi | mid); its byte offset for the tile being
     // fetched lives in rvo[] (recomputed when the fetch stream moves on to the next tile, as in conv_f32_prec)
     constexpr int NRI = RECIN ? RECIN : 1;
@@ -223,7 +160,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
 #pragma unroll
         for (int q = 0; q < NRI; q++) {
             const unsigned it = (unsigned)(tid + q * P_NT), pos = it >> 1;
-            const unsigned r = pdiv(pos, g.dPWP);
+            const unsigned r = fdiv(pos, g.dPWP);
             const int cp = (int)(pos - r * (unsigned)g.PWP);
             const int v = g.s == 2 ? (cp < g.PWH ? 2 * cp : 2 * (cp - g.PWH) + 1) : cp;
             const bool in = (int)r < g.PR;
@@ -277,7 +214,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
 #pragma unroll
                 for (int j = 0; j < CPI; j++) x[j] = __int_as_float(breg[j][i]);
                 int hi[CPI / 2], mid[CPI / 2];
-                psplit<CPI>(x, hi, mid);
+                split2<CPI>(x, hi, mid);
                 int8_t *a = aitem[i] + slot * slot_bytes;
                 if (CPI == 8) {
                     *(v4i *)a = (v4i){hi[0], hi[1 % (CPI / 2)], hi[2 % (CPI / 2)], hi[3 % (CPI / 2)]};
@@ -293,49 +230,31 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
         }
     };
 
-    // ---- weights: row oc0 + tid / ATPR of both planes, elements (tid % ATPR) * AE .. of the step (as conv_f32_split)
+    // ---- weights: row oc0 + tid / ATPR of both planes, elements (tid % ATPR) * AE .. of the step, through registers (wstage_fetch / wstage_commit)
     const int arow = tid / ATPR, akc = (tid % ATPR) * AE;
-    // (buffer loads: a 32-bit per-lane offset, the (plane, step) part in the scalar offset: no 64-bit row pointer and address arithmetic per load)
     const unsigned wplane = (unsigned)g.oc_pad * (unsigned)g.kp * 2u;
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wpl, 0, (int)(2u * wplane), 0x00020000);
     const unsigned wvoff = ((unsigned)(oc0 + arow) * (unsigned)g.kp + (unsigned)akc) * 2u;
     int aregs[2][2][AD];
-    auto fetch_w = [&](int ks, int (&areg)[2][AD]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int pl = 0; pl < 2; pl++) {
-            const unsigned so = (unsigned)pl * wplane + (unsigned)ks * 64u;
-            if (AE == 8) { const v4i t = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, so, 0)); areg[pl][0] = t[0]; areg[pl][1 % AD] = t[1]; areg[pl][2 % AD] = t[2]; areg[pl][3 % AD] = t[3]; }
-            else if (AE == 4) { const auto t = __builtin_amdgcn_raw_buffer_load_b64(wrs, wvoff, so, 0); areg[pl][0] = (int)t[0]; areg[pl][1 % AD] = (int)t[1]; }
-            else areg[pl][0] = (int)__builtin_amdgcn_raw_buffer_load_b32(wrs, wvoff, so, 0);
-        }
-    };
-    auto commit_w = [&](int buf, const int (&areg)[2][AD]) __attribute__((always_inline)) {
-        int8_t *st = wst + buf * WSTAGE;
-        const int aoff = pa_lds_off(arow, akc >> 3) + (akc & 7) * 2;
-#pragma unroll
-        for (int pl = 0; pl < 2; pl++) {
-            if (AE == 8) *(v4i *)(st + pl * APLANE + aoff) = (v4i){areg[pl][0], areg[pl][1 % AD], areg[pl][2 % AD], areg[pl][3 % AD]};
-            else if (AE == 4) *(int2 *)(st + pl * APLANE + aoff) = make_int2(areg[pl][0], areg[pl][1 % AD]);
-            else *(int *)(st + pl * APLANE + aoff) = areg[pl][0];
-        }
-    };
+    auto fetch_w = [&](int ks, int (&areg)[2][AD]) __attribute__((always_inline)) { wstage_fetch<AE>(wrs, wvoff, wplane, ks, areg); };
+    auto commit_w = [&](int buf, const int (&areg)[2][AD]) __attribute__((always_inline)) { wstage_commit<AE, APLANE>(wst + buf * WSTAGE, arow, akc, areg); };
 
     // ---- the compute side's view of a tile: patch pixel of tap (0, 0) of this lane's A rows, output offsets of its D rows
     const int8_t *pbase[NI]; // LDS address of the record of tap (0, 0), slot 0, of the lane's A rows
     unsigned ooff[NI]; // byte offset (frame + position inside a channel plane) of the lane's 4 result pixels, ~0 = none
     auto tile_setup = [&](unsigned t) __attribute__((always_inline)) {
-        const int V0 = tile_v0(t);
+        const int V0 = fpatch_tile_v0<P_BN>(g, t);
 #pragma unroll
         for (int n = 0; n < NI; n++) {
             const unsigned q = t * P_BN + (unsigned)(wn * TN + n * 16 + fr); // A operand: pixel fr of MFMA tile n
-            const unsigned R = pdiv(q, g.dSW), xs = q - R * (unsigned)g.SW;
-            const unsigned seg = pdiv(R, g.dHo), y = R - seg * (unsigned)g.H_out;
+            const unsigned R = fdiv(q, g.dSW), xs = q - R * (unsigned)g.SW;
+            const unsigned seg = fdiv(R, g.dHo), y = R - seg * (unsigned)g.H_out;
             const int prow = (int)(seg * (unsigned)g.HV + y * (unsigned)g.s) - V0;
             pbase[n] = patch + (q < g.total_pix ? prow * g.PWP + (int)xs : 0) * 32;
             const unsigned q4 = t * P_BN + (unsigned)(wn * TN + n * 16 + fc * 4); // D: pixels 4 fc .. + 3 of tile n, channel fr
-            const unsigned R4 = pdiv(q4, g.dSW), xs4 = q4 - R4 * (unsigned)g.SW;
-            const unsigned seg4 = pdiv(R4, g.dHo), y4 = R4 - seg4 * (unsigned)g.H_out;
-            const unsigned f4 = pdiv(seg4, g.dNS), st4 = seg4 - f4 * (unsigned)g.nstrips;
+            const unsigned R4 = fdiv(q4, g.dSW), xs4 = q4 - R4 * (unsigned)g.SW;
+            const unsigned seg4 = fdiv(R4, g.dHo), y4 = R4 - seg4 * (unsigned)g.H_out;
+            const unsigned f4 = fdiv(seg4, g.dNS), st4 = seg4 - f4 * (unsigned)g.nstrips;
             ooff[n] = q4 < g.total_pix ? f4 * (unsigned)p.out_stride + (y4 * (unsigned)g.W_out + st4 * (unsigned)g.SW + xs4) * 4u : 0xffffffffu;
         }
     };
@@ -377,27 +296,19 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
         }
 #pragma unroll
         for (int a = 0; a < MI; a++) {
-            const int o = pa_lds_off(wm * TM + a * 16 + fr, fc);
+            const int o = a_lds_off(wm * TM + a * 16 + fr, fc);
             if (FPATCH_ABL & 8) { wh[a] = __builtin_bit_cast(bf16x8, (v4i){o, a, t, lane}); wmid[a] = wh[a]; continue; }
             wh[a] = __builtin_bit_cast(bf16x8, *(const v4i *)(ap + o));
             wmid[a] = __builtin_bit_cast(bf16x8, *(const v4i *)(ap + APLANE + o));
         }
     };
-    auto phase_m = [&]() __attribute__((always_inline)) {
+    auto phase_m = [&]() __attribute__((always_inline)) { // pixels are the A operand: a lane ends with 4 consecutive pixels of one channel
+        if (FPATCH_ABL & 1) {
 #pragma unroll
-        for (int a = 0; a < MI; a++)
+            for (int a = 0; a < MI; a++)
 #pragma unroll
-            for (int c = 0; c < NI; c++) { // pixels are the A operand: a lane ends with 4 consecutive pixels of one channel
-                if (FPATCH_ABL & 1) { asm volatile("" ::"v"(xm[c]), "v"(xh[c]), "v"(wh[a]), "v"(wmid[a])); continue; }
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xm[c], wh[a], acc[a][c], 0, 0, 0);   // mid * hi
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[c], wmid[a], acc[a][c], 0, 0, 0); // hi * mid
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[c], wh[a], acc[a][c], 0, 0, 0);   // hi * hi
-            }
-    };
-    auto barrier_lds = [&]() __attribute__((always_inline)) { // this wave's LDS operations done (loads in flight stay in flight), then the barrier
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+                for (int c = 0; c < NI; c++) asm volatile("" ::"v"(xm[c]), "v"(xh[c]), "v"(wh[a]), "v"(wmid[a]));
+        } else mfma3<MI, NI>(acc, xh, xm, wh, wmid);
     };
     // top of R(t): commit the chunk the schedule names (its loads were issued >= 2 steps ago); the next chunk's loads are issued AFTER
     // the step's weight loads (vmcnt is in order: the weights, consumed one step later, must not queue behind them).  The schedule
@@ -535,7 +446,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
                         v4f r = acc[a][c];
                         if (p.silu) {
 #pragma unroll
-                            for (int j = 0; j < 4; j++) r[j] = psilu_fast(r[j]);
+                            for (int j = 0; j < 4; j++) r[j] = silu_fast(r[j]);
                         }
                         *(v4f *)((char *)p.out + (size_t)ooff[c] + (size_t)oc * hw * 4u) = r + addv[a][c];
                     }
@@ -550,7 +461,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_patch(const mhip_conv_f32_t 
                         v4f r = acc[a][c];
                         if (p.silu) {
 #pragma unroll
-                            for (int j = 0; j < 4; j++) r[j] = psilu_fast(r[j]);
+                            for (int j = 0; j < 4; j++) r[j] = silu_fast(r[j]);
                         }
                         *(v4f *)((char *)p.out + (size_t)ooff[c] + (size_t)oc * hw * 4u) = r;
                     }
@@ -642,29 +553,12 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_prec(const mhip_conv_f32_t p
     const int arow = tid / ATPR, akc = (tid % ATPR) * AE;
     // (buffer loads: a 32-bit per-lane offset and the (plane, step) part in the scalar offset -- a 64-bit row pointer and its per-load address
     // arithmetic cost the registers whose spill put a reload, and with it an s_waitcnt vmcnt(0), in front of the K loop)
-    const unsigned wplane_b = (unsigned)g.oc_pad * (unsigned)g.kp * 2u;
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wpl, 0, (int)(2u * wplane_b), 0x00020000);
+    const unsigned wplane = (unsigned)g.oc_pad * (unsigned)g.kp * 2u;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wpl, 0, (int)(2u * wplane), 0x00020000);
     const unsigned wvoff = ((unsigned)(oc0 + arow) * (unsigned)g.kp + (unsigned)akc) * 2u;
     int aregs[2][2][AD];
-    auto fetch_w = [&](int ks, int (&areg)[2][AD]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int pl = 0; pl < 2; pl++) {
-            const unsigned so = (unsigned)pl * wplane_b + (unsigned)ks * 64u;
-            if (AE == 8) { const v4i t = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, so, 0)); areg[pl][0] = t[0]; areg[pl][1 % AD] = t[1]; areg[pl][2 % AD] = t[2]; areg[pl][3 % AD] = t[3]; }
-            else if (AE == 4) { const auto t = __builtin_amdgcn_raw_buffer_load_b64(wrs, wvoff, so, 0); areg[pl][0] = (int)t[0]; areg[pl][1 % AD] = (int)t[1]; }
-            else areg[pl][0] = (int)__builtin_amdgcn_raw_buffer_load_b32(wrs, wvoff, so, 0);
-        }
-    };
-    auto commit_w = [&](int buf, const int (&areg)[2][AD]) __attribute__((always_inline)) {
-        int8_t *st = wst + buf * WSTAGE;
-        const int aoff = pa_lds_off(arow, akc >> 3) + (akc & 7) * 2;
-#pragma unroll
-        for (int pl = 0; pl < 2; pl++) {
-            if (AE == 8) *(v4i *)(st + pl * APLANE + aoff) = (v4i){areg[pl][0], areg[pl][1 % AD], areg[pl][2 % AD], areg[pl][3 % AD]};
-            else if (AE == 4) *(int2 *)(st + pl * APLANE + aoff) = make_int2(areg[pl][0], areg[pl][1 % AD]);
-            else *(int *)(st + pl * APLANE + aoff) = areg[pl][0];
-        }
-    };
+    auto fetch_w = [&](int ks, int (&areg)[2][AD]) __attribute__((always_inline)) { wstage_fetch<AE>(wrs, wvoff, wplane, ks, areg); };
+    auto commit_w = [&](int buf, const int (&areg)[2][AD]) __attribute__((always_inline)) { wstage_commit<AE, APLANE>(wst + buf * WSTAGE, arow, akc, areg); };
 
     // ---- patch: instruction j of this wave fills block j * 8 + wv of a slot = patch positions (j * 8 + wv) * 32 + lane / 2, the lane's
     // half record (lane & 1: hi | mid).  The lane's byte offsets for the tile whose chunks are being issued live in registers (vo[]):
@@ -672,20 +566,8 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_prec(const mhip_conv_f32_t p
     // the next tile, once per tile.  (Read from the row table at every issue, the LDS round trip beside the other waves' fragment
     // reads cost ~1500 cycles per issue: stamps.)
     const int ndw = g.ndma > wv ? (g.ndma - wv + 7) >> 3 : 0;
-    auto tile_v0 = [&](unsigned t) __attribute__((always_inline)) {
-        const unsigned R0 = pdiv(t * P_BN, g.dSW), seg0 = pdiv(R0, g.dHo);
-        return (int)(seg0 * (unsigned)g.HV + (R0 - seg0 * (unsigned)g.H_out) * (unsigned)g.s);
-    };
-    auto fill_rowtab = [&](unsigned t) __attribute__((always_inline)) {
-        if (tid < g.PR) {
-            const unsigned V = (unsigned)tile_v0(t) + (unsigned)tid;
-            const unsigned seg = pdiv(V, g.dHV), f = pdiv(seg, g.dNS), st = seg - f * (unsigned)g.nstrips;
-            const int iy = (int)(V - seg * (unsigned)g.HV) - g.pad;
-            const bool ok = t < g.ntiles && seg < g.nsegs && iy >= 0 && iy < g.H_in;
-            rowtab[(t & 1) * P_PRCAP + tid] = make_int2(ok ? (int)(f * (unsigned)p.in_stride + (unsigned)(iy * g.W_in) * 32u) : -1,
-                                                        (int)st * g.SW * g.s - g.pad - g.dx);
-        }
-    };
+    auto tile_v0 = [&](unsigned t) __attribute__((always_inline)) { return fpatch_tile_v0<P_BN>(g, t); };
+    auto fill_rowtab = [&](unsigned t) __attribute__((always_inline)) { fpatch_fill_rowtab<P_BN>(p, g, rowtab, tid, t, 32u); };
     unsigned vo[NDW];
     auto tile_vo = [&](unsigned t) __attribute__((always_inline)) {
         const int2 *rtab = rowtab + (t & 1u) * P_PRCAP;
@@ -693,7 +575,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_prec(const mhip_conv_f32_t p
         for (int j = 0; j < NDW; j++)
             if (j < ndw) {
                 const unsigned pos = (unsigned)((j * 8 + wv) * 32 + (lane >> 1));
-                const unsigned r = pdiv(pos, g.dPWP);
+                const unsigned r = fdiv(pos, g.dPWP);
                 const int cp = (int)(pos - r * (unsigned)g.PWP);
                 const int v = g.s == 2 ? (cp < g.PWH ? 2 * cp : 2 * (cp - g.PWH) + 1) : cp;
                 const bool in = (int)r < g.PR;
@@ -726,17 +608,17 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_prec(const mhip_conv_f32_t p
 #pragma unroll
         for (int n = 0; n < NI; n++) {
             const unsigned q = t * P_BN + (unsigned)(wn * TN + n * 16 + fr);
-            const unsigned R = pdiv(q, g.dSW), xs = q - R * (unsigned)g.SW;
-            const unsigned seg = pdiv(R, g.dHo), y = R - seg * (unsigned)g.H_out;
+            const unsigned R = fdiv(q, g.dSW), xs = q - R * (unsigned)g.SW;
+            const unsigned seg = fdiv(R, g.dHo), y = R - seg * (unsigned)g.H_out;
             const int prow = (int)(seg * (unsigned)g.HV + y * (unsigned)g.s) - V0;
             pbase[n] = patch + (q < g.total_pix ? prow * g.PWP + (int)xs : 0) * 32;
         }
     };
     auto out_off = [&](unsigned t, int n) __attribute__((always_inline)) { // byte offset (frame + position inside a channel plane) of the lane's 4 result pixels of MFMA tile n, ~0 = none
         const unsigned q4 = t * P_BN + (unsigned)(wn * TN + n * 16 + fc * 4);
-        const unsigned R4 = pdiv(q4, g.dSW), xs4 = q4 - R4 * (unsigned)g.SW;
-        const unsigned seg4 = pdiv(R4, g.dHo), y4 = R4 - seg4 * (unsigned)g.H_out;
-        const unsigned f4 = pdiv(seg4, g.dNS), st4 = seg4 - f4 * (unsigned)g.nstrips;
+        const unsigned R4 = fdiv(q4, g.dSW), xs4 = q4 - R4 * (unsigned)g.SW;
+        const unsigned seg4 = fdiv(R4, g.dHo), y4 = R4 - seg4 * (unsigned)g.H_out;
+        const unsigned f4 = fdiv(seg4, g.dNS), st4 = seg4 - f4 * (unsigned)g.nstrips;
         return q4 < g.total_pix ? f4 * (unsigned)p.out_stride + (y4 * (unsigned)g.W_out + st4 * (unsigned)g.SW + xs4) * 4u : 0xffffffffu;
     };
     v4f acc[MI][NI];
@@ -761,31 +643,12 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_prec(const mhip_conv_f32_t p
         }
 #pragma unroll
         for (int a = 0; a < MI; a++) {
-            const int o = pa_lds_off(wm * TM + a * 16 + fr, fc);
+            const int o = a_lds_off(wm * TM + a * 16 + fr, fc);
             wh[a] = __builtin_bit_cast(bf16x8, *(const v4i *)(ap + o));
             wmid[a] = __builtin_bit_cast(bf16x8, *(const v4i *)(ap + APLANE + o));
         }
     };
-    auto phase_m = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int a = 0; a < MI; a++)
-#pragma unroll
-            for (int c = 0; c < NI; c++) {
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xm[c], wh[a], acc[a][c], 0, 0, 0);   // mid * hi
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[c], wmid[a], acc[a][c], 0, 0, 0); // hi * mid
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[c], wh[a], acc[a][c], 0, 0, 0);   // hi * hi
-            }
-    };
-    auto barrier_lds = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto barrier_raw = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto phase_m = [&]() __attribute__((always_inline)) { mfma3<MI, NI>(acc, xh, xm, wh, wmid); };
 
     // ---- prologue: tables, the row table and DMA offsets of the first tile, what the previous tile's steps would have issued for
     // it (the schedule entries that name a chunk of the NEXT tile), the first three weight stages; everything landed
@@ -919,7 +782,7 @@ __global__ __launch_bounds__(P_NT, 2) void conv_f32_prec(const mhip_conv_f32_t p
                     v4f r = acc[a][c];
                     if (p.silu) {
 #pragma unroll
-                        for (int j = 0; j < 4; j++) r[j] = psilu_fast(r[j]);
+                        for (int j = 0; j < 4; j++) r[j] = silu_fast(r[j]);
                     }
                     if (p.add) r += addv[a][c];
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, r), ors, vso(a, c), 0, 0);
@@ -1063,8 +926,8 @@ static int fpatch_geom(const mhip_conv_f32_t *p, fpatch_geom_t *g, int frames, i
     g->nsegs = (unsigned)(frames * g->nstrips);
     g->in_bytes = (unsigned)in_bytes;
     g->out_bytes = (unsigned)((size_t)(frames - 1) * p->out_stride + (size_t)p->out_c * p->out_h * p->out_w * 4);
-    g->dSW = make_pdiv((unsigned)g->SW); g->dHo = make_pdiv((unsigned)g->H_out); g->dHV = make_pdiv((unsigned)g->HV);
-    g->dNS = make_pdiv((unsigned)g->nstrips); g->dgrp = make_pdiv((unsigned)g->ngrp); g->dPWP = make_pdiv((unsigned)g->PWP);
+    g->dSW = make_fdiv((unsigned)g->SW); g->dHo = make_fdiv((unsigned)g->H_out); g->dHV = make_fdiv((unsigned)g->HV);
+    g->dNS = make_fdiv((unsigned)g->nstrips); g->dgrp = make_fdiv((unsigned)g->ngrp); g->dPWP = make_fdiv((unsigned)g->PWP);
     return 1;
 }
 
@@ -1074,26 +937,6 @@ static int fpatch_toff(const fpatch_geom_t *g, int c, int tap) {
     return (c % g->nb) * g->slotpix + ky * g->PWP + (g->s == 2 ? (v >> 1) + (v & 1) * g->PWH : v);
 }
 
-static uint16_t pbf16_rn(float x) {
-    uint32_t b;
-    memcpy(&b, &x, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((b >> 16) | 0x40u);
-    return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
-}
-static float pbf16_val(uint16_t h) {
-    const uint32_t b = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-}
-
-static void shape_of(mhip_conv_f32_t *p, int out_c, int in_c, int kh, int kw, int stride, int pad, int in_h, int in_w, int out_h, int out_w) {
-    memset(p, 0, sizeof(*p));
-    p->out_c = out_c; p->in_c = in_c; p->kh = kh; p->kw = kw; p->stride_h = p->stride_w = stride; p->pad_top = p->pad_left = pad;
-    p->in_h = in_h; p->in_w = in_w; p->out_h = out_h; p->out_w = out_w;
-    p->in_stride = (size_t)in_c * in_h * in_w * 4; p->out_stride = (size_t)out_c * out_h * out_w * 4; p->frames = 1;
-}
-
 // Bytes of, and (w, out != NULL) the content of, the image conv_f32_patch reads: [nsteps][4] unit offsets (bytes into the patch ring, -1 = dummy), [nsteps] schedule, then
 // two planes (hi, mid) of bf16 [oc_pad][kp] in the kernel's K order: element 8 u + j of a row = channel 8 c + j, tap of unit u =
 // (chunk c, tap) (dummy units and the slack: zeros).  0 = not a shape this kernel takes.
@@ -1101,7 +944,7 @@ static void shape_of(mhip_conv_f32_t *p, int out_c, int in_c, int kh, int kw, in
 extern "C" size_t mhip_conv_f32_patch_pack2(int out_c, int in_c, int kh, int kw, int stride, int pad, int in_h, int in_w, int out_h, int out_w,
                                             int rec, const float *w, void *out) {
     mhip_conv_f32_t p;
-    shape_of(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
+    conv_f32_shape(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
     fpatch_geom_t g;
     if (out_c <= 0 || !fpatch_geom(&p, &g, 1, rec != 0)) return 0;
     const size_t tabb = ((size_t)g.tab_ints * 4 + 255) & ~(size_t)255, planeb = (size_t)g.oc_pad * g.kp * 2;
@@ -1119,11 +962,11 @@ extern "C" size_t mhip_conv_f32_patch_pack2(int out_c, int in_c, int kh, int kw,
             const int c = u / g.U, tap = u - c * g.U, ky = tap / kw, kx = tap - ky * kw;
             for (int j = 0; j < 8; j++) {
                 const float x = w[((size_t)(oc * (size_t)in_c + c * 8 + j) * kh + ky) * kw + kx];
-                const uint16_t h = pbf16_rn(x);
-                const float hv = pbf16_val(h);
+                const uint16_t h = bf16_rn(x);
+                const float hv = bf16_val(h);
                 const size_t k = (size_t)oc * g.kp + (size_t)u * 8 + j;
                 hi[k] = h;
-                mid[k] = (hv - hv == 0.0f) ? pbf16_rn(x - hv) : 0; // (x - hi exact; hi not finite: no residual)
+                mid[k] = (hv - hv == 0.0f) ? bf16_rn(x - hv) : 0; // (x - hi exact; hi not finite: no residual)
             }
         }
     return bytes;
@@ -1139,7 +982,7 @@ extern "C" size_t mhip_conv_f32_patch_pack(int out_c, int in_c, int kh, int kw, 
 extern "C" int mhip_conv_f32_patch_geom2(int out_c, int in_c, int kh, int kw, int stride, int pad, int in_h, int in_w, int out_h, int out_w, int rec,
                                          int *outv, int cap) {
     mhip_conv_f32_t p;
-    shape_of(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
+    conv_f32_shape(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
     fpatch_geom_t g;
     if (out_c <= 0 || !fpatch_geom(&p, &g, 1, rec != 0)) return 0;
     const int n = 35;
@@ -1155,7 +998,7 @@ extern "C" int mhip_conv_f32_patch_geom(int out_c, int in_c, int kh, int kw, int
 // packed with rec = 1), 2 conv_f32_patch<..., RECIN> (two slots, through registers; the plain image)
 extern "C" int mhip_conv_f32_patch_rec_form(int out_c, int in_c, int kh, int kw, int stride, int pad, int in_h, int in_w, int out_h, int out_w) {
     mhip_conv_f32_t p;
-    shape_of(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
+    conv_f32_shape(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
     fpatch_geom_t g;
     if (out_c <= 0) return 0;
     if (fpatch_geom(&p, &g, 1, 1)) return 1;

@@ -27,26 +27,13 @@
 //    outside by an out-of-range offset the buffer unit turns into zeros.  GATHER 0 (any other geometry): one dword per tap.
 //    A fetch ONLY issues loads (a scheduler fence follows it; left alone the compiler sinks the loads to the end of the step);
 //    shifts and masks are applied by the commit one step later from a per-lane `meta` word;
-//  * LDS: A rows as in the int8 kernels (64-byte rows, chunk swizzle).  B rows (pixels) are dealt over four 64-row blocks
+//  * LDS: A rows as in the int8 kernels (64-byte rows, chunk swizzle: a_lds_off).  B rows (pixels) are dealt over four 64-row blocks
 //    (pixel r -> block r % 4, row r / 4) with the 16-byte chunk XOR-ed by (block ^ row / 4 % 4), laid out so that the
 //    4-pixel-per-lane writes and the 16-pixel fragment reads spread over the banks (SQ counters: 22 % of the LDS cycles are
 //    still conflicts -- LDS is busy a fifth of the time, not the bound);
 //  * two stages, two register sets: step ks + 2's loads are in flight while step ks multiplies and step ks + 1's operands
 //    are split and written (sched_group_barrier interleaves them with the MFMAs: two vector instructions fit in an MFMA's shadow).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../expf_exact.h"
-#include "../mhip.h"
-
-extern "C" hipStream_t mhip_stream_native(void);
-extern "C" int mhip_check(hipError_t e, const char *what);
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "conv_f32_common.hpp"
 
 #define S_BN 256  // pixels per workgroup
 #define S_BK 32   // taps per K step = one v_mfma_f32_16x16x32_bf16
@@ -59,98 +46,13 @@ extern "C" int mhip_split_stamps(unsigned long long *out, int reset) {
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(split_stamp_sums), z, sizeof z) != hipSuccess) return -1;
     return 0;
 }
-#define STAMP(i)                                                                  \
-    do {                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                        \
-        const unsigned long long t_ = __builtin_readcyclecounter();              \
-        st_acc[i] += t_ - st_last;                                                \
-        st_last = t_;                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                        \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
 #endif
 #ifndef SPLIT_ABL // timing-only ablations (tools/stamps_build.sh split N; wrong results): 1 no MFMAs, 2 no gather loads, 4 no
 #define SPLIT_ABL 0 // split / LDS writes of the input, 8 no fragment reads, 16 plain stores (no SiLU), 32 no stores, 64 aligned gathers
 #endif
 
-__device__ __forceinline__ float silu_split(float v) { // as conv_f32.hip: the exporter's SiLU with the reference's roundings
-    const float s = 1.0f / (1.0f + expf_exact(-v, expf_exact_tab));
-    return v * s;
-}
-// three piece products (relative error per product up to 2^-16) do not need libm's last bit: v_exp_f32 and v_rcp_f32, 1 ulp each --
-// the exact form above is double-precision arithmetic and a table, a fifth of the kernel's time on every layer
-// v / (1 + e) as (v / 2) * rcp((1 + e) / 2): v_rcp_f32 returns 0 where its result would be a denormal, i.e. for 1 + e > 2^126 (v <
-// -87.34, a true value of up to 1.0e-36 came out as -0); halved, the operand stays below 2^127 until v = -88.03, where the true value
-// is 5.2e-37.  No larger factor: v / 2 is exact down to |v| = 2^-125 and the product never exceeds |v|, so nothing changes at tiny or
-// huge v (a factor 2^-32 made v 2^-32 a denormal below |v| = 2^-94 and lost its bits).  The fma rounds once, like the addition it replaces.
-__device__ __forceinline__ float silu_fast(float v) {
-    const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f); // exp(-v)
-    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
-}
-__device__ __forceinline__ int a_lds_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 2)) << 4); }
 __device__ __forceinline__ int b_lds_off(int r, int chunk) { // pixel r of the tile, 16-byte chunk (8 taps) of its 64-byte row
     return ((((r & 3) << 6) + (r >> 2)) << 6) + (((chunk ^ r ^ (r >> 4)) & 3) << 4);
-}
-
-struct sdiv_t {
-    unsigned m, s1, s2;
-};
-__device__ __forceinline__ unsigned sdiv(unsigned n, const sdiv_t d) {
-    const unsigned q = __umulhi(d.m, n);
-    return (q + ((n - q) >> d.s1)) >> d.s2;
-}
-static sdiv_t make_sdiv(unsigned d) {
-    sdiv_t r;
-    unsigned l = 0;
-    while ((1ull << l) < d) l++;
-    r.m = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-    r.s1 = l < 1 ? l : 1;
-    r.s2 = l > 0 ? l - 1 : 0;
-    return r;
-}
-
-// N floats -> N bf16 in each of NPL planes (N / 2 dwords each), round-to-nearest split (v_cvt_pk_bf16_f32 converts and packs
-// two at a time): hi = bf16(x), mid = bf16(x - hi), lo = x - hi - mid.  Every subtraction is exact (x - hi has at most 16
-// significant bits, x - hi - mid at most 8, a bf16 value), so x == hi + mid + lo exactly; with two planes |x - hi - mid| <=
-// 2^-17 |x|, errors of either sign.
-// A value bf16 would round to +-inf (x = +-inf, or |x| >= 2^128 - 2^119) keeps a FINITE hi and the LAST plane carries the infinity: the
-// last plane of the input meets only the weights' hi plane (mid * hi, lo * hi), so the sum sees inf * w.hi once and gives sign(w) * inf
-// as the reference does.  With the infinity in the hi plane it also met w.mid and w.lo -- inf * 0, or inf times a residual of the other
-// sign -- and inf - inf as its own residual: NaN.  Two planes: hi saturates at the largest bf16 (two packed 16-bit minima per PAIR of
-// elements: this is the K loop), the residual is then +-inf by itself; FLT_MAX still comes out as inf (hi + mid = 2^128).  Three
-// planes (not the benchmark's mode): hi = mid = 0 and lo = bf16(x).  A NaN ends as a NaN piece either way.
-#define NONFINITE_BF16 0x1.ffp+127f // 2^128 - 2^119: from here on bf16 rounding gives inf
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-template <int N, int NPL>
-__device__ __forceinline__ void splitn(const float (&x)[N], int (&hi)[N / 2], int (&mid)[N / 2], int (&lo)[N / 2]) {
-#pragma unroll
-    for (int i = 0; i < N / 2; i++) { // (element 2i, element 2i + 1) -> one dword per plane, element 2i in the low half
-        const f32x2 v = {x[2 * i], x[2 * i + 1]};
-        const bool f0 = __builtin_fabsf(v[0]) < NONFINITE_BF16, f1 = __builtin_fabsf(v[1]) < NONFINITE_BF16; // (false for a NaN; NPL == 3 only)
-        const f32x2 vh = {NPL == 3 && !f0 ? 0.0f : v[0], NPL == 3 && !f1 ? 0.0f : v[1]};
-        int h = __builtin_bit_cast(int, __builtin_convertvector(vh, bf16x2));
-        if (NPL == 2) { // saturate both halves at once: +inf / +NaN (0x7f80 ..) -> 0x7f7f as signed, -inf / -NaN (0xff80 ..) -> 0xff7f as unsigned
-            h = __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(s16x2, h), (s16x2){0x7f7f, 0x7f7f}));
-            h = __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(u16x2, h), (u16x2){0xff7f, 0xff7f}));
-        }
-        const f32x2 hf = {__int_as_float(h << 16), __int_as_float(h & (int)0xffff0000)};
-        const f32x2 r = v - hf; // (+-inf: itself)
-        hi[i] = h;
-        if (NPL == 3) {
-            const f32x2 rm = {f0 ? r[0] : 0.0f, f1 ? r[1] : 0.0f};
-            const int m = __builtin_bit_cast(int, __builtin_convertvector(rm, bf16x2));
-            const f32x2 mf = {__int_as_float(m << 16), __int_as_float(m & (int)0xffff0000)};
-            mid[i] = m;
-            lo[i] = __builtin_bit_cast(int, __builtin_convertvector(r - mf, bf16x2)); // exact
-        } else {
-            mid[i] = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
-            lo[i] = 0;
-        }
-    }
 }
 
 struct split_args_t {
@@ -160,7 +62,7 @@ struct split_args_t {
     int nks;     // K steps: roundup64(K) / 32 (even)
     int kwp;     // kernel row length in the packed K space (kw, or kw + 1 for GATHER 2 with an odd kw)
     int oc_pad;  // rows of a weight plane
-    sdiv_t dhw, dow, dtaps, dkwp;
+    fdiv_t dhw, dow, dtaps, dkwp;
     // a PAIR of convolutions over the same input in one grid (mhip_conv_f32_pair: C3's cv1 + cv2 -- same geometry, same out_c): channel tiles
     // blockIdx.y >= noc1 belong to the second one (its weight planes, bias and output); the two workgroups of a pixel run walk the same
     // tiles side by side, the second one's input reads hit L2.  noc1 == 0: one convolution
@@ -171,9 +73,8 @@ struct split_args_t {
 };
 
 // BM = output channels per workgroup (128 | 64 | 32); waves: WM along channels x WN along pixels, WM * WN == 8
-// RECOUT (mhip_conv_f32_t.out_rec, two pieces only): the results leave as RECORDS -- [out_c / 8][H][W] x 32 bytes = [8 x bf16 hi | 8 x bf16 mid] of
-// 8 consecutive channels of one pixel -- for the one k x k convolution that reads them (conv_f32_prec in conv_f32_patch.hip: its staging
-// phase is then plain LDS-DMA).  The MFMA operands change places (D = W X^T), so a lane ends with 4 consecutive CHANNELS of one pixel.
+// RECOUT (mhip_conv_f32_t.out_rec, two pieces only): the results leave as RECORDS (conv_f32_common.hpp: the format, record_half) for the
+// one k x k convolution that reads them.  The MFMA operands change places (D = W X^T), so a lane ends with 4 consecutive CHANNELS of one pixel.
 template <int BM, int WM, int WN, int GATHER, int NPL, bool RECOUT = false>
 __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void conv_f32_split(const mhip_conv_f32_t p_, const split_args_t g) {
     mhip_conv_f32_t p = p_;
@@ -222,8 +123,8 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
     auto setup = [&](unsigned pt) __attribute__((always_inline)) { // the fetch side's view of pixel tile pt (beyond the last: nothing valid)
         const unsigned px = pt * S_BN + (unsigned)(pl_ * PPL);
         const bool valid = pt < g.npt && px < g.total_pix; // (GATHER 1 / 2: out_w % PPL == 0, so the lane's pixels share row, frame and validity)
-        const unsigned f = sdiv(valid ? px : 0u, g.dhw), rem = (valid ? px : 0u) - f * hw;
-        const int oy = (int)sdiv(rem, g.dow), ox = (int)rem - oy * p.out_w;
+        const unsigned f = fdiv(valid ? px : 0u, g.dhw), rem = (valid ? px : 0u) - f * hw;
+        const int oy = (int)fdiv(rem, g.dow), ox = (int)rem - oy * p.out_w;
         const int iy0 = oy * p.stride_h - p.pad_top;
         ix0 = ox * p.stride_w - p.pad_left;
         vbase = (unsigned)(f * (unsigned)p.in_stride) + (unsigned)((iy0 * p.in_w + ix0) * 4);
@@ -263,9 +164,9 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
         meta = 0; smeta = 0;
         // the lane's taps of this step: (ic, ky, kx) carried from the first one (wave-uniform: scalar registers)
         const int k0 = ks * S_BK + tg * TPL;
-        int ic = (int)sdiv((unsigned)(k0 < K ? k0 : 0), g.dtaps);
+        int ic = (int)fdiv((unsigned)(k0 < K ? k0 : 0), g.dtaps);
         const int t0 = (k0 < K ? k0 : 0) - ic * taps;
-        int ky = (int)sdiv((unsigned)t0, g.dkwp), kx = t0 - ky * kwp;
+        int ky = (int)fdiv((unsigned)t0, g.dkwp), kx = t0 - ky * kwp;
         int soff = (ic * plane + ky * p.in_w + kx) * 4; // byte offset of tap (ic, ky, kx) relative to the window origin
         constexpr int STEP = GATHER == 2 ? 2 : 1;       // taps per load
 #pragma unroll
@@ -359,13 +260,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
                 if (NPL == 3) *(v4i *)(bp + 2 * BPLANE + off) = (v4i){lo[0], lo[1], lo[2], lo[3]};
             }
         }
-        const int aoff = a_lds_off(arow, akc >> 3) + (akc & 7) * 2; // AE bf16 = AE * 2 bytes inside the 16-byte chunk
-#pragma unroll
-        for (int pl = 0; pl < NPL; pl++) {
-            if (AE == 8) *(v4i *)(st + pl * APLANE + aoff) = (v4i){areg[pl][0], areg[pl][1 % AD], areg[pl][2 % AD], areg[pl][3 % AD]};
-            else if (AE == 4) *(int2 *)(st + pl * APLANE + aoff) = make_int2(areg[pl][0], areg[pl][1 % AD]);
-            else *(int *)(st + pl * APLANE + aoff) = areg[pl][0];
-        }
+        wstage_commit<AE, APLANE, NPL>(st, arow, akc, areg);
     };
 
     // accumulators start at the bias.  The MFMA takes the PIXELS as its A operand and the weights as B (D = X W^T), so a lane holds
@@ -433,15 +328,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
                     acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[NPL - 1][c], af[0][a], acc[a][c], 0, 0, 0); // hi * lo
                     acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[1][c], af[1][a], acc[a][c], 0, 0, 0);       // mid * mid
                 }
-                if (RECOUT) { // (NPL == 2) weights are the A operand: rows = channels
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][a], bf[1][c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1][a], bf[0][c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][a], bf[0][c], acc[a][c], 0, 0, 0);
-                    continue;
-                }
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[1][c], af[0][a], acc[a][c], 0, 0, 0); // hi * mid
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0][c], af[1][a], acc[a][c], 0, 0, 0); // mid * hi
-                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0][c], af[0][a], acc[a][c], 0, 0, 0); // hi * hi
+                mfma3_tile<RECOUT>(acc[a][c], bf[0][c], bf[1][c], af[0][a], af[1][a]); // (RECOUT: the weights are the A operand)
             }
         commit(buf ^ 1, breg, areg, meta, smeta);
 #pragma unroll
@@ -501,27 +388,22 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
         const unsigned p0 = pt * S_BN;
         const bool vec4 = (hw & 3u) == 0u;
         if (RECOUT) {
-            // a lane holds channels 4 fc .. + 3 (of channel tile a) of pixel fr (of pixel tile c): its two hi dwords and two mid dwords.
-            // v_permlane16_swap between lane rows fc, fc ^ 1 (every lane takes part: before any branch): the even row ends with the
-            // mid pieces of all 8 channels of the record, the odd row with the hi pieces -- one 16-byte store per lane, 32 contiguous
-            // bytes per pixel, 512 per chunk and instruction
+            // a lane holds channels 4 fc .. + 3 (of channel tile a) of pixel fr (of pixel tile c): half a record (record_half), 512
+            // contiguous bytes per chunk and instruction
 #pragma unroll
             for (int c = 0; c < NI; c++) {
                 const unsigned px = p0 + (unsigned)(wn * TN + c * 16 + fr);
                 const bool pok = px < g.total_pix;
-                const unsigned f = sdiv(pok ? px : 0u, g.dhw), rem = (pok ? px : 0u) - f * hw;
+                const unsigned f = fdiv(pok ? px : 0u, g.dhw), rem = (pok ? px : 0u) - f * hw;
                 char *ob = (char *)p.out + (size_t)f * p.out_stride + (size_t)rem * 32u + ((fc & 1) ? 0u : 16u);
 #pragma unroll
                 for (int a = 0; a < MI; a++) {
                     float x[4];
 #pragma unroll
                     for (int j = 0; j < 4; j++) x[j] = p.silu ? silu_fast(acc[a][c][j]) : acc[a][c][j];
-                    int hi[2], mid[2], lo_[2];
-                    splitn<4, 2>(x, hi, mid, lo_); // (an infinite result: a finite hi, the infinity in mid -- splitn's rule)
-                    const auto s0 = __builtin_amdgcn_permlane16_swap((unsigned)mid[0], (unsigned)hi[0], false, false);
-                    const auto s1 = __builtin_amdgcn_permlane16_swap((unsigned)mid[1], (unsigned)hi[1], false, false);
+                    const v4i rec = record_half<false>(x);
                     const int chunk = (oc0 + wm * TM + a * 16) / 8 + (fc >> 1);
-                    if (pok && chunk * 8 < p.out_c) *(v4i *)(ob + (size_t)chunk * hw * 32u) = (v4i){(int)s0[0], (int)s1[0], (int)s0[1], (int)s1[1]};
+                    if (pok && chunk * 8 < p.out_c) *(v4i *)(ob + (size_t)chunk * hw * 32u) = rec;
                     acc[a][c] = bias4[a];
                 }
             }
@@ -532,7 +414,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
             const unsigned px = p0 + (unsigned)(wn * TN + c * 16 + fc * 4);
             if (vec4) {
                 if (px < g.total_pix) { // (total_pix % 4 == 0 here: all four pixels or none)
-                    const unsigned f = sdiv(px, g.dhw), rem = px - f * hw;
+                    const unsigned f = fdiv(px, g.dhw), rem = px - f * hw;
                     float *out = (float *)((char *)p.out + (size_t)f * p.out_stride);
                     const float *addp = p.add ? (const float *)((const char *)p.add + (size_t)f * p.add_stride) : nullptr;
                     float *out2v = fz ? (float *)((char *)g.out2 + (size_t)f * p.out_stride) - (size_t)(BM / 2) * hw : out; // channel oc of the second = plane oc - BM / 2
@@ -544,7 +426,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
                             v4f r = acc[a][c];
                             if (p.silu && !(SPLIT_ABL & 16)) {
 #pragma unroll
-                                for (int j = 0; j < 4; j++) r[j] = NPL == 2 ? silu_fast(r[j]) : silu_split(r[j]);
+                                for (int j = 0; j < 4; j++) r[j] = NPL == 2 ? silu_fast(r[j]) : silu_exact(r[j]);
                             }
                             if (addp) r += *(const v4f *)(addp + (size_t)oc * hw + rem);
                             *(v4f *)((fz && wm * TM + a * 16 >= BM / 2 ? out2v : out) + (size_t)oc * hw + rem) = r;
@@ -555,7 +437,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     if (px + j >= g.total_pix) continue;
-                    const unsigned f = sdiv(px + j, g.dhw), rem = px + j - f * hw;
+                    const unsigned f = fdiv(px + j, g.dhw), rem = px + j - f * hw;
                     float *out = (float *)((char *)p.out + (size_t)f * p.out_stride);
                     const float *addp = p.add ? (const float *)((const char *)p.add + (size_t)f * p.add_stride) : nullptr;
                     float *out2v = fz ? (float *)((char *)g.out2 + (size_t)f * p.out_stride) - (size_t)(BM / 2) * hw : out;
@@ -564,7 +446,7 @@ __global__ __launch_bounds__(S_NT, BM == 32 && NPL == 2 && !RECOUT ? 4 : 2) void
                         const int oc = oc0 + wm * TM + a * 16 + fr;
                         if (SPLIT_ABL & 32) asm volatile("" ::"v"(acc[a][c][j]));
                         else if (oc < out_c_eff) {
-                            const float r = p.silu && !(SPLIT_ABL & 16) ? (NPL == 2 ? silu_fast(acc[a][c][j]) : silu_split(acc[a][c][j])) : acc[a][c][j];
+                            const float r = p.silu && !(SPLIT_ABL & 16) ? (NPL == 2 ? silu_fast(acc[a][c][j]) : silu_exact(acc[a][c][j])) : acc[a][c][j];
                             (fz && wm * TM + a * 16 >= BM / 2 ? out2v : out)[(size_t)oc * hw + rem] = addp ? r + addp[(size_t)oc * hw + rem] : r;
                         }
                     }
@@ -676,7 +558,7 @@ static int try_split(const mhip_conv_f32_t *p, const mhip_conv_f32_t *q) {
     split_args_t g;
     g.total_pix = (unsigned)total; g.npt = (unsigned)((total + S_BN - 1) / S_BN); g.in_bytes = (unsigned)in_bytes;
     g.K = (int)Kl; g.kp = (int)((K + 63) / 64 * 64) + 64; g.nks = (int)((Kl + 63) / 64 * 64) / 32; g.kwp = kwp; g.oc_pad = (p->out_c + 127) / 128 * 128;
-    g.dhw = make_sdiv((unsigned)hw); g.dow = make_sdiv((unsigned)p->out_w); g.dtaps = make_sdiv((unsigned)(p->kh * kwp)); g.dkwp = make_sdiv((unsigned)kwp);
+    g.dhw = make_fdiv((unsigned)hw); g.dow = make_fdiv((unsigned)p->out_w); g.dtaps = make_fdiv((unsigned)(p->kh * kwp)); g.dkwp = make_fdiv((unsigned)kwp);
     // a pair: in ONE channel tile where both fit one (2 * out_c = 32 | 64 | 128: the wave tiles then split between the two at a multiple of
     // 16 channels), else as two runs of channel tiles (the launcher fills in the count)
     const bool one_tile = q && (p->out_c == 16 || p->out_c == 32 || (p->out_c == 64 && p->use_mfma == 3));
@@ -700,18 +582,6 @@ extern "C" int mhip_conv_f32_split_takes(int out_c, int in_c, int kh, int kw, in
     return kwp != kw ? -1 : 0;
 }
 
-static uint16_t bf16_rn(float x) { // round to nearest even (NaN kept a NaN)
-    uint32_t b;
-    memcpy(&b, &x, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((b >> 16) | 0x40u);
-    return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
-}
-static float bf16_val(uint16_t h) {
-    const uint32_t b = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-}
 extern "C" size_t mhip_conv_f32_split_pack(int out_c, int in_c, int kh, int kw, int stride_w, int planes, const float *w, void *out) {
     if (out_c <= 0 || in_c <= 0 || kh <= 0 || kw <= 0 || planes < 2 || planes > 3) return 0;
     const int kwp = split_kwp(kw, stride_w);

@@ -17,21 +17,7 @@
 //     SIMD's two waves overlap.
 // Bound: HBM -- 4.9 MB in + 13.1 MB out per 640 x 640 frame.  Takes in_c <= 4, out_c <= 32, even kernel width <= 8 and kh * kw / 2 <= 20,
 // stride 2, even equal pads, output maps that are multiples of 16 x 32.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../mhip.h"
-
-extern "C" hipStream_t mhip_stream_native(void);
-extern "C" int mhip_check(hipError_t e, const char *what);
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "conv_f32_common.hpp"
 
 #define ST_TH 16
 #define ST_TW 32
@@ -49,30 +35,17 @@ struct stem_geom_t {
     unsigned ntiles, in_bytes, per;
 };
 
-__device__ __forceinline__ float stem_silu(float v) { // (conv_f32_split.hip silu_fast: why the halves)
-    const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
-    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
-}
-// 8 floats -> 4 dwords hi, 4 dwords mid (as conv_f32_patch.hip: round to nearest, exact residual; hi saturates at the largest bf16,
-// so that an infinity is carried by the mid piece alone)
+// 8 floats -> 4 dwords hi, 4 dwords mid (split2)
 __device__ __forceinline__ void stem_split8(const float (&x)[8], v4i &hi, v4i &mid) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const f32x2 v = {x[2 * i], x[2 * i + 1]};
-        const f32x2 vh = {__builtin_amdgcn_fmed3f(v[0], -0x1.fep+127f, 0x1.fep+127f), __builtin_amdgcn_fmed3f(v[1], -0x1.fep+127f, 0x1.fep+127f)};
-        const int h = __builtin_bit_cast(int, __builtin_convertvector(vh, bf16x2));
-        const float h0 = __int_as_float(h << 16), h1 = __int_as_float(h & (int)0xffff0000);
-        f32x2 r;
-        asm("v_sub_f32 %0, %1, %2" : "=v"(r[0]) : "v"(v[0]), "v"(h0));
-        asm("v_sub_f32 %0, %1, %2" : "=v"(r[1]) : "v"(v[1]), "v"(h1));
-        hi[i] = h;
-        mid[i] = __builtin_bit_cast(int, __builtin_convertvector(r, bf16x2));
-    }
+    int h[4], m[4];
+    split2<8>(x, h, m);
+    hi = (v4i){h[0], h[1], h[2], h[3]};
+    mid = (v4i){m[0], m[1], m[2], m[3]};
 }
 
 // RECOUT (mhip_conv_f32_t.out_rec): the results leave in record format for the one k x k convolution that reads them (layer 3 of the
-// yolov5 twins; conv_f32_split.hip says what a record is): the MFMA operands change places, a lane ends with 4 consecutive channels of
-// one pixel, v_permlane16_swap pairs them into 16-byte halves of a record.
+// yolov5 twins; conv_f32_common.hpp says what a record is): the MFMA operands change places, a lane ends with 4 consecutive channels of
+// one pixel, record_half pairs them into 16-byte halves of a record.
 template <bool RECOUT>
 __global__ __launch_bounds__(ST_NT, 2) void conv_f32_stem(const mhip_conv_f32_t p, const stem_geom_t g, const int8_t *__restrict__ wpl) {
     constexpr int MI = 2, NI = 4; // 32 channels x 64 pixels per wave
@@ -196,44 +169,26 @@ __global__ __launch_bounds__(ST_NT, 2) void conv_f32_stem(const mhip_conv_f32_t 
                 xh[n] = __builtin_bit_cast(bf16x8, *(const v4i *)a);
                 xm[n] = __builtin_bit_cast(bf16x8, *(const v4i *)(a + 16));
             }
-#pragma unroll
-            for (int a = 0; a < MI; a++)
-#pragma unroll
-                for (int n = 0; n < NI; n++) {
-                    if (RECOUT) { // weights are the A operand: rows = channels
-                        acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][a], xm[n], acc[a][n], 0, 0, 0);
-                        acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm[ks][a], xh[n], acc[a][n], 0, 0, 0);
-                        acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][a], xh[n], acc[a][n], 0, 0, 0);
-                        continue;
-                    }
-                    acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xm[n], wh[ks][a], acc[a][n], 0, 0, 0);
-                    acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[n], wm[ks][a], acc[a][n], 0, 0, 0);
-                    acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[n], wh[ks][a], acc[a][n], 0, 0, 0);
-                }
+            mfma3<MI, NI, RECOUT>(acc, xh, xm, wh[ks], wm[ks]); // (RECOUT: the weights are the A operand, rows = channels)
         }
     };
     auto epilogue = [&](unsigned t) __attribute__((always_inline)) { // tile t's results: 4 consecutive pixels of a channel row per store
         unsigned f;
         int oy0, ox0;
         tile_origin(t, f, oy0, ox0);
-        if (RECOUT) { // lane = pixel fr of tile n, channels 4 fc .. + 3 of channel tile a; lane rows fc, fc ^ 1 trade pieces (every lane: no branch)
+        if (RECOUT) { // lane = pixel fr of tile n, channels 4 fc .. + 3 of channel tile a (record_half: every lane, no branch)
 #pragma unroll
             for (int n = 0; n < NI; n++) {
                 const unsigned pos = (unsigned)((oy0 + 2 * wv + (n >> 1)) * g.W_out + ox0 + (n & 1) * 16 + fr);
                 char *ob = (char *)p.out + (size_t)f * p.out_stride + (size_t)pos * 32u + ((fc & 1) ? 0u : 16u);
 #pragma unroll
                 for (int a = 0; a < MI; a++) {
-                    float x[8];
+                    float x[4];
 #pragma unroll
-                    for (int j = 0; j < 4; j++) x[j] = p.silu ? stem_silu(acc[a][n][j]) : acc[a][n][j];
-#pragma unroll
-                    for (int j = 4; j < 8; j++) x[j] = 0.f;
-                    v4i hi, mid;
-                    stem_split8(x, hi, mid);
-                    const auto s0 = __builtin_amdgcn_permlane16_swap((unsigned)mid[0], (unsigned)hi[0], false, false);
-                    const auto s1 = __builtin_amdgcn_permlane16_swap((unsigned)mid[1], (unsigned)hi[1], false, false);
+                    for (int j = 0; j < 4; j++) x[j] = p.silu ? silu_fast(acc[a][n][j]) : acc[a][n][j];
+                    const v4i rec = record_half<true>(x);
                     const int chunk = 2 * a + (fc >> 1);
-                    if (chunk * 8 < p.out_c) *(v4i *)(ob + (size_t)chunk * hw * 32u) = (v4i){(int)s0[0], (int)s1[0], (int)s0[1], (int)s1[1]};
+                    if (chunk * 8 < p.out_c) *(v4i *)(ob + (size_t)chunk * hw * 32u) = rec;
                     acc[a][n] = bias4[a];
                 }
             }
@@ -249,7 +204,7 @@ __global__ __launch_bounds__(ST_NT, 2) void conv_f32_stem(const mhip_conv_f32_t 
                     v4f r = acc[a][n];
                     if (p.silu) {
 #pragma unroll
-                        for (int j = 0; j < 4; j++) r[j] = stem_silu(r[j]);
+                        for (int j = 0; j < 4; j++) r[j] = silu_fast(r[j]);
                     }
                     const size_t o = (size_t)f * p.out_stride + ((size_t)oc * hw + pos) * 4u;
                     if (p.add) r += *(const v4f *)((const char *)p.add + o);
@@ -258,11 +213,6 @@ __global__ __launch_bounds__(ST_NT, 2) void conv_f32_stem(const mhip_conv_f32_t 
                 acc[a][n] = bias4[a];
             }
         }
-    };
-    auto barrier_lds = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
     };
 
     const unsigned t0 = blockIdx.x * g.per;
@@ -322,32 +272,13 @@ static int stem_geom(const mhip_conv_f32_t *p, stem_geom_t *g, int frames) {
     return 1;
 }
 
-static uint16_t sbf16_rn(float x) {
-    uint32_t b;
-    memcpy(&b, &x, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((b >> 16) | 0x40u);
-    return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
-}
-static float sbf16_val(uint16_t h) {
-    const uint32_t b = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-}
-static void stem_shape(mhip_conv_f32_t *p, int out_c, int in_c, int kh, int kw, int stride, int pad, int in_h, int in_w, int out_h, int out_w) {
-    memset(p, 0, sizeof(*p));
-    p->out_c = out_c; p->in_c = in_c; p->kh = kh; p->kw = kw; p->stride_h = p->stride_w = stride; p->pad_top = p->pad_left = pad;
-    p->in_h = in_h; p->in_w = in_w; p->out_h = out_h; p->out_w = out_w;
-    p->in_stride = (size_t)in_c * in_h * in_w * 4; p->out_stride = (size_t)out_c * out_h * out_w * 4; p->frames = 1;
-}
-
 // Bytes of, and (w, out != NULL) the content of, the weight image conv_f32_stem loads into registers: two planes (hi, mid) of bf16
 // [32 channels][20 units][8]: element par * 4 + ch of unit (ky, j) = w[oc][ch][ky][2 j + par] (channel slots >= in_c, units >=
 // kh * kw / 2, channels >= out_c: zeros).  0 = not a shape this kernel takes.
 extern "C" size_t mhip_conv_f32_stem_pack(int out_c, int in_c, int kh, int kw, int stride, int pad, int in_h, int in_w, int out_h, int out_w,
                                           const float *w, void *out) {
     mhip_conv_f32_t p;
-    stem_shape(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
+    conv_f32_shape(&p, out_c, in_c, kh, kw, stride, pad, in_h, in_w, out_h, out_w);
     stem_geom_t g;
     if (!stem_geom(&p, &g, 1)) return 0;
     const size_t rowe = (size_t)ST_NS * 4 * 8, planee = 32 * rowe, bytes = 2 * planee * 2;
@@ -359,11 +290,11 @@ extern "C" size_t mhip_conv_f32_stem_pack(int out_c, int in_c, int kh, int kw, i
             for (int kx = 0; kx < kw; kx++)
                 for (int ch = 0; ch < in_c; ch++) {
                     const float x = w[((size_t)(oc * (size_t)in_c + ch) * kh + ky) * kw + kx];
-                    const uint16_t h = sbf16_rn(x);
-                    const float hv = sbf16_val(h);
+                    const uint16_t h = bf16_rn(x);
+                    const float hv = bf16_val(h);
                     const size_t k = (size_t)oc * rowe + (size_t)(ky * (kw / 2) + kx / 2) * 8 + (size_t)(kx & 1) * 4 + ch;
                     hi[k] = h;
-                    mid[k] = (hv - hv == 0.0f) ? sbf16_rn(x - hv) : 0;
+                    mid[k] = (hv - hv == 0.0f) ? bf16_rn(x - hv) : 0;
                 }
     return bytes;
 }

@@ -13,14 +13,7 @@
 // holds the tail of in_last's data (the launch stopped one plane early).  This kernel recomputes those s pixels (20 - 60 of 400 - 25 600)
 // from their true operands, in float32 with fused multiply-adds, and overwrites them: same stream, after the main launch.
 // Bound: nothing -- out_c * s * (L / HW + 1) multiply-adds per frame, a few microseconds.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
-#include "../mhip.h"
-
-extern "C" hipStream_t mhip_stream_native(void);
-extern "C" int mhip_check(hipError_t e, const char *what);
+#include "conv_f32_common.hpp"
 
 struct vcat_args_t {
     const float *first[3]; // the concat's inputs but the last
@@ -28,17 +21,6 @@ struct vcat_args_t {
     int n_first, run, s;   // their count, floats per run, s = n_first * run
     int hw, planes;        // pixels per plane, planes summed (L / HW + 1)
 };
-
-__device__ __forceinline__ float vcat_silu(float v) { // (conv_f32_split.hip silu_fast: why the halves)
-    const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
-    return (v * 0.5f) * __builtin_amdgcn_rcpf(__builtin_fmaf(e, 0.5f, 0.5f));
-}
-// bf16, round to nearest even (a NaN stays one): as mhip_conv_f32_split_pack and mars_hip_write_tensor cut records
-__device__ __forceinline__ unsigned vcat_bf16(float x) {
-    const unsigned b = __float_as_uint(x);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return (b >> 16) | 0x40u;
-    return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-}
 
 // One workgroup (4 waves): 256 output channels x VC_PX consecutive head pixels of one frame.  A lane owns 4 channels x VC_PX pixels; the weights
 // come TRANSPOSED ([plane][oc_pitch], packed by the planner: mhip_conv_f32_vcat_pack), so a step is ONE 16-byte weight load and two 16-byte operand
@@ -108,14 +90,13 @@ __global__ __launch_bounds__(256) void conv_f32_vcat_head(const mhip_conv_f32_t 
         float v = bias;
 #pragma unroll
         for (int k = 0; k < 4; k++) v += red[k][wv * VC_PX + i][lane];
-        if (p.silu) v = vcat_silu(v);
-        if (p.out_rec) { // the two pieces of this channel in the record of pixel px (conv_f32_split.hip says what a record is)
-            const unsigned h = vcat_bf16(__builtin_amdgcn_fmed3f(v, -0x1.fep+127f, 0x1.fep+127f)); // hi saturates: an infinity is carried by mid alone (conv_f32_split.hip splitn)
-            const float hv = __uint_as_float(h << 16);
-            const float r = v - hv;
-            unsigned short *rec = (unsigned short *)((char *)p.out + (size_t)f * p.out_stride + ((size_t)(oc >> 3) * a.hw + px) * 32u);
-            rec[oc & 7] = (unsigned short)h;
-            rec[8 + (oc & 7)] = (unsigned short)vcat_bf16(r);
+        if (p.silu) v = silu_fast(v);
+        if (p.out_rec) { // the two pieces of this channel in the record of pixel px (conv_f32_common.hpp says what a record is)
+            const uint16_t h = bf16_rn(__builtin_amdgcn_fmed3f(v, -0x1.fep+127f, 0x1.fep+127f)); // hi saturates: an infinity is carried by mid alone (split2's rule, scalar)
+            const float r = v - bf16_val(h);
+            uint16_t *rec = (uint16_t *)((char *)p.out + (size_t)f * p.out_stride + ((size_t)(oc >> 3) * a.hw + px) * 32u);
+            rec[oc & 7] = h;
+            rec[8 + (oc & 7)] = bf16_rn(r);
         } else {
             ((float *)((char *)p.out + (size_t)f * p.out_stride))[(size_t)oc * a.hw + px] = v;
         }

@@ -857,7 +857,7 @@ mars_error_t mars_hip_write_tensor(mars_model_t *model, int ti, int frame, const
                 memcpy(&x, &f[(size_t)c * t->rec_hw + px], 4);
                 uint32_t b;
                 memcpy(&b, &x, 4);
-                /* hi saturates at the largest bf16: a value bf16 rounds to +-inf keeps a finite hi, the mid piece carries the infinity (conv_f32_split.hip splitn) */
+                /* hi saturates at the largest bf16: a value bf16 rounds to +-inf keeps a finite hi, the mid piece carries the infinity.  The rule's home is hip/conv_f32_common.hpp (bf16_rn, split2 / splitn, the record format); this is its copy in C */
                 const uint16_t h = (b & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((b >> 16) | 0x40u)
                                    : (b & 0x7fffffffu) >= 0x7f7f8000u ? (uint16_t)((b >> 16 & 0x8000u) | 0x7f7fu) : (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
                 const uint32_t hb = (uint32_t)h << 16;
