@@ -958,46 +958,68 @@ static int env_int(const char *name, int dflt) {
     const char *e = getenv(name);
     return e ? atoi(e) : dflt;
 }
+// the launch-policy knobs (tune_t, conv_i8_common.hpp): key of mhip_conv_i8_tune(), environment name, default
+static const struct {
+    const char *key, *env;
+    int dflt;
+    int tune_t::*member;
+} KNOBS[] = {
+    {"persist", "MARS_HIP_PERSIST", 1, &tune_t::persist},
+    {"persist_stages", "MARS_HIP_PSTAGES", 2, &tune_t::persist_stages},
+    {"persist_maxk", "MARS_HIP_PERSIST_MAXK", 8, &tune_t::persist_maxk}, // measured: deeper K loops gain nothing from walking tiles
+    {"persist_slots", "MARS_HIP_PSLOTS", 0, &tune_t::persist_slots},
+    {"stages", "MARS_HIP_STAGES", 0, &tune_t::stages},
+    {"bpx", "MARS_HIP_BPX", 0, &tune_t::bpx},
+    {"variant", "MARS_HIP_VARIANT", 0, &tune_t::variant},
+    {"bufmode", "MARS_HIP_BUFMODE", 1, &tune_t::bufmode},
+    {"wres", "MARS_HIP_WRES", 3, &tune_t::wres},
+    {"rgb_direct", "MARS_HIP_RGB_DIRECT", 1, &tune_t::rgb_direct},
+    {"small_batch", "MARS_HIP_SMALL_BATCH", 1, &tune_t::small_batch},
+    {"rows", "MARS_HIP_ROWS", 1, &tune_t::rows},
+    {"few_wgs", "MARS_HIP_FEW_WGS", 256, &tune_t::few_wgs},
+    {"patch_ring", "MARS_HIP_PATCH_RING", 0, &tune_t::patch_ring},
+    {"patch_lds_kb", "MARS_HIP_PATCH_LDS_KB", 80, &tune_t::patch_lds_kb},
+    {"both_bpx", "MARS_HIP_BOTH_BPX", 0, &tune_t::both_bpx},
+    {"both_wide", "MARS_HIP_BOTH_WIDE", 0, &tune_t::both_wide},
+};
 const tune_t &conv_i8_tune_state() {
     if (!g_tune.init) {
-        g_tune.persist = env_int("MARS_HIP_PERSIST", 1);
-        g_tune.persist_stages = env_int("MARS_HIP_PSTAGES", 2);
-        g_tune.persist_maxk = env_int("MARS_HIP_PERSIST_MAXK", 8); // measured: deeper K loops gain nothing from walking tiles
-        g_tune.persist_slots = env_int("MARS_HIP_PSLOTS", 0);
-        g_tune.stages = env_int("MARS_HIP_STAGES", 0);
-        g_tune.bpx = env_int("MARS_HIP_BPX", 0);
-        g_tune.variant = env_int("MARS_HIP_VARIANT", 0);
-        g_tune.bufmode = env_int("MARS_HIP_BUFMODE", 1);
-        g_tune.wres = env_int("MARS_HIP_WRES", 3);
-        g_tune.rgb_direct = env_int("MARS_HIP_RGB_DIRECT", 1);
-        g_tune.small_batch = env_int("MARS_HIP_SMALL_BATCH", 1);
-        g_tune.rows = env_int("MARS_HIP_ROWS", 1);
-        g_tune.few_wgs = env_int("MARS_HIP_FEW_WGS", 256);
-        g_tune.patch_ring = env_int("MARS_HIP_PATCH_RING", 0);
-        g_tune.patch_lds_kb = env_int("MARS_HIP_PATCH_LDS_KB", 80);
-        g_tune.both_bpx = env_int("MARS_HIP_BOTH_BPX", 0);
-        g_tune.both_wide = env_int("MARS_HIP_BOTH_WIDE", 0);
+        for (const auto &k : KNOBS) g_tune.*k.member = env_int(k.env, k.dflt);
         g_tune.init = 1;
     }
     return g_tune;
 }
 static inline const tune_t &tune() { return conv_i8_tune_state(); }
-// value == NULL-safe accessor pair: set (get == nullptr) or read (get != nullptr) one launch-policy knob
+// set (get == nullptr) or read (get != nullptr) one launch-policy knob
 static int tune_access(const char *key, int value, int *get) {
     (void)conv_i8_tune_state();
-    struct { const char *k; int *v; } tab[] = {{"persist", &g_tune.persist}, {"persist_stages", &g_tune.persist_stages},
-                                               {"persist_maxk", &g_tune.persist_maxk}, {"persist_slots", &g_tune.persist_slots}, {"wres", &g_tune.wres}, {"rgb_direct", &g_tune.rgb_direct}, {"small_batch", &g_tune.small_batch},
-                                               {"rows", &g_tune.rows}, {"few_wgs", &g_tune.few_wgs}, {"patch_ring", &g_tune.patch_ring}, {"patch_lds_kb", &g_tune.patch_lds_kb}, {"both_bpx", &g_tune.both_bpx}, {"both_wide", &g_tune.both_wide}, {"stages", &g_tune.stages}, {"bpx", &g_tune.bpx}, {"variant", &g_tune.variant}, {"bufmode", &g_tune.bufmode}};
-    for (auto &e : tab)
-        if (key && !strcmp(key, e.k)) {
-            if (get) *get = *e.v;
-            else *e.v = value;
+    for (const auto &k : KNOBS)
+        if (key && !strcmp(key, k.key)) {
+            if (get) *get = g_tune.*k.member;
+            else g_tune.*k.member = value;
             return 0;
         }
     return -1;
 }
 extern "C" int mhip_conv_i8_tune(const char *key, int value) { return tune_access(key, value, nullptr); }
 extern "C" int mhip_conv_i8_tune_get(const char *key, int *value) { return value ? tune_access(key, 0, value) : -1; }
+
+// ---- launch arithmetic every form shares
+// channels per tile: the widest of 128 / 64 / 32 that divides oc_pad
+static int chan_tile(int oc_pad) { return oc_pad % 128 == 0 ? 128 : (oc_pad % 64 == 0 ? 64 : 32); }
+// shift-based K position: log2 of in_c (a power of two) and the 16-bit reciprocal of kw
+static int log2_of(int in_c) {
+    int lg = 0;
+    while ((1 << lg) < in_c) lg++;
+    return lg;
+}
+static unsigned kw_magic(int kw) { return (65536u + (unsigned)kw - 1u) / (unsigned)kw; }
+// workgroups of the launch under its large-batch tiling (256 pixels x 128 channels): the "few workgroups" tests compare this
+static long large_tile_wgs(const mhip_conv_i8_t *p) { return ((long)p->frames * p->out_h * p->out_w + 255) / 256 * ((p->oc_pad + 127) / 128); }
+// LDS of the weights-resident tile walker: table + 2 pixel-tile stages + every K step of one channel tile (`bn` rows), + `extra`
+// bytes (the one-tile pair form's second table, its chained 1x1); a workgroup may take WRES_LDS_MAX (two per CU)
+#define WRES_LDS_MAX (80 * 1024)
+static size_t wres_lds(int bpx, int bn, int nks, size_t extra = 0) { return LUTB + extra + 2 * (size_t)bpx * BK + (size_t)nks * bn * BK; }
 
 // buffer-addressed K loop: a 64-byte step inside one tap (in_c >= 64, power of two), 31-bit offsets, tap masks
 static int buf_mode(const mhip_conv_i8_t *p, int k64) {
@@ -1022,23 +1044,25 @@ static int launch_mfma(const mhip_conv_i8_t *p, long total_pix, int k64) {
         attr = true;
     }
     // in_c a power of two and tap/kw small enough for the 16-bit reciprocal: shift-based K position
-    int lg = -1;
-    if ((p->in_c & (p->in_c - 1)) == 0 && (long)p->kh * p->kw * (p->kw - 1) < 65536) {
-        lg = 0;
-        while ((1 << lg) < p->in_c) lg++;
-    }
-    const unsigned magic = ((65536u + (unsigned)p->kw - 1u) / (unsigned)p->kw);
+    const int lg = (p->in_c & (p->in_c - 1)) == 0 && (long)p->kh * p->kw * (p->kw - 1) < 65536 ? log2_of(p->in_c) : -1;
     hipLaunchKernelGGL((conv_i8_mfma<BPX, BN, STAGES, KS, NW>), dim3(nblk), dim3(NW * 64), lds, mhip_stream_native(), *p, total_pix,
-                       k64, (const int8_t *)mhip_zero_page(), noc, nblk, lg, magic,
+                       k64, (const int8_t *)mhip_zero_page(), noc, nblk, lg, kw_magic(p->kw),
                        make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
                        lg >= 0 ? buf_mode(p, k64) : 0, (unsigned)in_extent_bytes(p));
     return mhip_check(hipGetLastError(), "conv_i8_mfma launch");
 }
 
 
-// LDS of the weights-resident form: LUT + 2 pixel-tile stages + every K step of one channel tile
-template <int BPX, int BN>
-static size_t wres_lds(int k64) { return LUTB + 2 * (size_t)BPX * BK + (size_t)(k64 / BK) * BN * BK; }
+// workgroups of `kern` the device holds at once with `lds` bytes each, 0 = the query failed
+template <class K>
+static int device_slots(K kern, size_t lds) {
+    int occ = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NTHREADS, lds) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+        hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return 0;
+    return (occ > 0 ? occ : 1) * prop.multiProcessorCount;
+}
 
 // BOTH: `second` is the second side of the one-tile pair form (both sides: out_c = oc_pad = 64 with half-step tables,
 // mhip_conv_i8_both_ok); one channel tile, a second table in LDS
@@ -1060,84 +1084,83 @@ static int launch_persist_t(const mhip_conv_i8_t *p, long total_pix, int k64, in
     conv_chain_t ch;
     memset(&ch, 0, sizeof(ch));
     if (CHAIN) ch = *chain;
-    const size_t lds = (BOTH ? LUTB : 0) + (CHAIN ? CHAIN_LDS : 0) + (wres ? wres_lds<BPX, BN>(k64) : LUTB + (size_t)STAGES * (BPX + BN) * BK);
+    const auto kern = conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>;
+    const size_t extra = (BOTH ? LUTB : 0) + (CHAIN ? CHAIN_LDS : 0);
+    const size_t lds = wres ? wres_lds(BPX, BN, k64 / BK, extra) : extra + LUTB + (size_t)STAGES * (BPX + BN) * BK;
+    int slots; // workgroups the device holds at once
     if (wres) { // its own occupancy (LDS differs per layer) and longer runs: the weight fetch must amortise
         static bool attr = false;
-        if (!attr && hipFuncSetAttribute((const void *)conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
+        if (!attr && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WRES_LDS_MAX) != hipSuccess)
             return mhip_check(hipErrorUnknown, "conv_i8_persist LDS attribute");
         attr = true;
-        int occ = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>, NTHREADS, lds) != hipSuccess ||
-            hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-            return mhip_check(hipErrorUnknown, "conv_i8_persist occupancy query");
-        unsigned g = (unsigned)((occ > 0 ? occ : 1) * prop.multiProcessorCount) / noc;
-        if (tune().persist_slots > 0) g = (unsigned)tune().persist_slots / noc;
-        if (g < 1) g = 1;
-        if (g > npt) g = npt;
-        hipLaunchKernelGGL((conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>), dim3(noc * g), dim3(NTHREADS), lds,
-                           mhip_stream_native(), *p, (unsigned)total_pix, k64, (const int8_t *)mhip_zero_page(), noc, npt, g, lg,
-                           magic, make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
-                           (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64), (unsigned)in_extent_bytes(p), 1, ch);
-        return mhip_check(hipGetLastError(), "conv_i8_persist (resident weights) launch");
+        slots = device_slots(kern, lds);
+    } else {
+        static int cached = 0; // (of this instantiation: its LDS is fixed)
+        if (!cached) cached = device_slots(kern, lds);
+        // 4 workgroups per device slot: short enough runs that a workgroup which has to wait for a slot (the detection
+        // tail of the previous batch shares the CUs) costs little, long enough to keep the cross-tile prefetch (measured)
+        slots = 4 * cached;
     }
-    static int slots = 0; // workgroups of this instantiation the device holds at once
-    if (!slots) {
-        int occ = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>, NTHREADS, lds) != hipSuccess ||
-            hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-            return mhip_check(hipErrorUnknown, "conv_i8_persist occupancy query");
-        slots = (occ > 0 ? occ : 1) * prop.multiProcessorCount;
-    }
-    // 4 workgroups per device slot: short enough runs that a workgroup which has to wait for a slot (the detection
-    // tail of the previous batch shares the CUs) costs little, long enough to keep the cross-tile prefetch (measured)
-    unsigned ngrp = (unsigned)(tune().persist_slots > 0 ? tune().persist_slots : 4 * slots) / noc;
+    if (!slots) return mhip_check(hipErrorUnknown, "conv_i8_persist occupancy query");
+    unsigned ngrp = (unsigned)(tune().persist_slots > 0 ? tune().persist_slots : slots) / noc;
     if (ngrp < 1) ngrp = 1;
     if (ngrp > npt) ngrp = npt;
-    hipLaunchKernelGGL((conv_i8_persist<BPX, BN, STAGES, HAS_LUT, SEG, PAIR, BOTH, CHAIN>), dim3(noc * ngrp), dim3(NTHREADS), lds,
-                       mhip_stream_native(), *p, (unsigned)total_pix, k64, (const int8_t *)mhip_zero_page(), noc, npt, ngrp, lg,
-                       magic, make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
-                       (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64), (unsigned)in_extent_bytes(p), 0, ch);
-    return mhip_check(hipGetLastError(), "conv_i8_persist launch");
+    hipLaunchKernelGGL(kern, dim3(noc * ngrp), dim3(NTHREADS), lds, mhip_stream_native(), *p, (unsigned)total_pix, k64,
+                       (const int8_t *)mhip_zero_page(), noc, npt, ngrp, lg, magic, make_fastdiv((unsigned)(p->out_h * p->out_w)),
+                       make_fastdiv((unsigned)p->out_w), (unsigned)persist_out_bytes(p), alt, noc0, SEG ? 0 : buf_mode(p, k64),
+                       (unsigned)in_extent_bytes(p), wres ? 1 : 0, ch);
+    return mhip_check(hipGetLastError(), wres ? "conv_i8_persist (resident weights) launch" : "conv_i8_persist launch");
 }
 
-// 1 = launched (rc in *rc), 0 = this layer is not eligible for the persistent kernel
 // ---- launch variants of the in_c % 16 == 0 kernels.  A variant = (form, pixels per workgroup, ring depth); every
 // variant computes the same bytes.  p->variant == 0 takes the measured default policy below; the host can pin a
 // variant per layer after timing the candidates on the device (mars_hip_autotune).
-//   code = 1 + persist + 2*(bpx == 256) + 4*(stages == 3)
-//   code = 9 / 10 / 11: patch-staged kernel with 8 / 16 / 4 tile rows
-//   code = 12: one tile per workgroup, 128 pixels, 2 ring stages of 128 K bytes each (even number of K steps)
-//   code = 13: one 256 x 128 tile per 8-wave workgroup, 3 stages
-//   code = 14 / 15: tile walker with the weights of its channel tile resident in LDS, 128 / 256 pixels
-//   code = 18 / 19: 128-byte K steps (whole-line DMA requests), 128 x 128 tile on 4 waves / 256 x 128 tile on 8 waves
-//   code = 20: conv_i8_rows (round 4): whole-row tiles, patch-staged input, streamed weights, persistent, deep 3x3 stride 1
-#define NVARIANTS 20 // 16, 17 were measured-and-dropped forms (round 2), 6 / 8 = the three-stage tile walker (pruned in round 4)
 struct variant_t {
     int persist, bpx, stages, patch, ks2, w8, wres, r128, rows;
 };
+#define NVARIANTS 20 // the highest code (callers size arrays with it); codes without a row (6, 8, 16, 17) are retired forms
+static const variant_t NO_VARIANT = {-1, 0, 0, 0, 0, 0, 0, 0, 0};
+static const struct {
+    int code;
+    variant_t v;
+} VARIANTS[] = {
+    {1, {0, 128, 2, 0, 0, 0, 0, 0, 0}},  // one tile per workgroup, 128 pixels, 2 ring stages
+    {2, {1, 128, 2, 0, 0, 0, 0, 0, 0}},  // tile walker (persistent), 128 pixels, 2 ring stages
+    {3, {0, 256, 2, 0, 0, 0, 0, 0, 0}},  // one tile per workgroup, 256 pixels, 2 ring stages
+    {4, {1, 256, 2, 0, 0, 0, 0, 0, 0}},  // tile walker, 256 pixels, 2 ring stages
+    {5, {0, 128, 3, 0, 0, 0, 0, 0, 0}},  // one tile per workgroup, 128 pixels, 3 ring stages
+    {7, {0, 256, 3, 0, 0, 0, 0, 0, 0}},  // one tile per workgroup, 256 pixels, 3 ring stages
+    {9, {0, 0, 0, 8, 0, 0, 0, 0, 0}},    // patch-staged kernel, 8 tile rows
+    {10, {0, 0, 0, 16, 0, 0, 0, 0, 0}},  // patch-staged kernel, 16 tile rows
+    {11, {0, 0, 0, 4, 0, 0, 0, 0, 0}},   // patch-staged kernel, 4 tile rows
+    {12, {0, 128, 2, 0, 1, 0, 0, 0, 0}}, // one tile per workgroup, 128 pixels, 2 ring stages of 128 K bytes each (even number of K steps)
+    {13, {0, 256, 3, 0, 0, 1, 0, 0, 0}}, // one 256 x 128 tile per 8-wave workgroup, 3 stages
+    {14, {1, 128, 2, 0, 0, 0, 1, 0, 0}}, // tile walker with the weights of its channel tile resident in LDS, 128 pixels
+    {15, {1, 256, 2, 0, 0, 0, 1, 0, 0}}, // ... 256 pixels
+    {18, {0, 0, 0, 0, 0, 0, 0, 1, 0}},   // 128-byte K steps (whole-line DMA requests), 128 x 128 tile on 4 waves
+    {19, {0, 0, 0, 0, 0, 0, 0, 2, 0}},   // ... 256 x 128 tile on 8 waves
+    {20, {0, 0, 0, 0, 0, 0, 0, 0, 1}},   // conv_i8_rows: whole-row tiles, patch-staged input, streamed weights, persistent, deep 3x3 stride 1
+};
+// the code of what launch_variant() runs `v` as: it tells 256 pixels from any other count (the "bpx" knob may hold anything); 0 = none
 static int variant_code(const variant_t &v) {
-    if (v.rows) return 20;
-    if (v.r128) return 17 + v.r128;
-    if (v.wres) return v.bpx == 256 ? 15 : 14;
-    if (v.w8) return 13;
-    if (v.ks2) return 12;
-    if (v.patch) return v.patch == 16 ? 10 : (v.patch == 8 ? 9 : 11);
-    return 1 + (v.persist ? 1 : 0) + (v.bpx == 256 ? 2 : 0) + (v.stages == 3 ? 4 : 0);
+    for (const auto &e : VARIANTS)
+        if (e.v.persist == v.persist && (e.v.bpx == 256) == (v.bpx == 256) && e.v.stages == v.stages && e.v.patch == v.patch &&
+            e.v.ks2 == v.ks2 && e.v.w8 == v.w8 && e.v.wres == v.wres && e.v.r128 == v.r128 && e.v.rows == v.rows)
+            return e.code;
+    return 0;
 }
-static variant_t variant_of(int code) {
-    if (code == 20) return variant_t{0, 0, 0, 0, 0, 0, 0, 0, 1};
-    if (code == 18 || code == 19) return variant_t{0, 0, 0, 0, 0, 0, 0, code - 17, 0};
-    if (code == 14 || code == 15) return variant_t{1, code == 15 ? 256 : 128, 2, 0, 0, 0, 1, 0, 0};
-    if (code == 13) return variant_t{0, 256, 3, 0, 0, 1, 0, 0, 0};
-    if (code == 12) return variant_t{0, 128, 2, 0, 1, 0, 0, 0, 0};
-    if (code >= 9 && code <= 11) return variant_t{0, 0, 0, code == 10 ? 16 : (code == 9 ? 8 : 4), 0, 0, 0, 0, 0};
-    if (code > 8 || code == 6 || code == 8) return variant_t{-1, 0, 0, 0, 0, 0, 0, 0, 0}; // 6, 8, 16, 17: retired codes
-    const int c = code - 1;
-    return variant_t{c & 1, (c & 2) ? 256 : 128, (c & 4) ? 3 : 2, 0, 0, 0, 0, 0, 0};
+static variant_t variant_of(int code) { // NO_VARIANT: not a code (launch_variant refuses it, no layer lists it)
+    for (const auto &e : VARIANTS)
+        if (e.code == code) return e.v;
+    return NO_VARIANT;
 }
+// patch-staged kernel: tile rows <-> code (0 = not one of its heights / codes)
+static int patch_code(int th) {
+    variant_t v{};
+    v.patch = th;
+    return variant_code(v);
+}
+static int patch_rows(int code) { return variant_of(code).patch; }
 
 // ---- 128-byte K steps (conv_i8_r128): eligibility, launch
 static bool r128_ok(const mhip_conv_i8_t *p) {
@@ -1155,11 +1178,8 @@ static int launch_r128_t(const mhip_conv_i8_t *p, long total_pix) {
     if (!attr && hipFuncSetAttribute((const void *)conv_i8_r128<BPX, BN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return mhip_check(hipErrorUnknown, "conv_i8_r128 LDS attribute");
     attr = true;
-    int lg = 0;
-    while ((1 << lg) < p->in_c) lg++;
-    const unsigned magic = ((65536u + (unsigned)p->kw - 1u) / (unsigned)p->kw);
     hipLaunchKernelGGL((conv_i8_r128<BPX, BN, NW>), dim3(npt * noc), dim3(NW * 64), lds, mhip_stream_native(), *p, total_pix, k128, noc,
-                       npt * noc, lg, magic, make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
+                       npt * noc, log2_of(p->in_c), kw_magic(p->kw), make_fastdiv((unsigned)(p->out_h * p->out_w)), make_fastdiv((unsigned)p->out_w),
                        (unsigned)in_extent_bytes(p));
     return mhip_check(hipGetLastError(), "conv_i8_r128 launch");
 }
@@ -1192,21 +1212,15 @@ static bool persist_eligible(const mhip_conv_i8_t *p) {
 }
 static bool wres_default(const mhip_conv_i8_t *p, int nks, int *bpx) {
     if (!tune().wres || p->kh * p->kw != 1 || p->in_c < 64 || p->out_h * p->out_w > 6400) return false;
-    const int bn = p->oc_pad % 128 == 0 ? 128 : (p->oc_pad % 64 == 0 ? 64 : 32);
+    const int bn = chan_tile(p->oc_pad);
     const int px = (bn == 64 && p->out_h * p->out_w >= 6400) ? 256 : 128;
-    if (LUTB + 2 * (size_t)px * BK + (size_t)nks * bn * BK > 80 * 1024) return false;
+    if (wres_lds(px, bn, nks) > WRES_LDS_MAX) return false;
     *bpx = px;
     return true;
 }
 
 static variant_t default_variant(const mhip_conv_i8_t *p, int nks) {
-    variant_t v;
-    v.patch = 0;
-    v.ks2 = 0;
-    v.w8 = 0;
-    v.wres = 0;
-    v.r128 = 0;
-    v.rows = 0;
+    variant_t v{};
     // wide, shallow k x k layers: the patch-staged kernel wins wherever its double-buffered form fits (measured on the
     // 160x160 and 80x80 layers of yolov5s: 1.25-1.9x over the implicit-GEMM forms)
     int ring = 0;
@@ -1215,15 +1229,14 @@ static variant_t default_variant(const mhip_conv_i8_t *p, int nks) {
     // step: 4-row patches, the 128 x 128 tile with 128-byte K steps for deep K loops (half the barriers per MAC, four
     // waves), the plain two-stage tile walker without the up-front weight fetch for 1 x 1 layers.  These are the
     // autotuner's choices at batch 1 (yolov5s twin, 640 x 640: 0.62 -> 0.53 ms per frame).
-    const long wg_large = ((long)p->frames * p->out_h * p->out_w + 255) / 256 * ((p->oc_pad + 127) / 128);
-    const bool few = wg_large < tune().few_wgs && tune().persist && !tune().bpx && !tune().stages && tune().small_batch;
+    const bool few = large_tile_wgs(p) < tune().few_wgs && tune().persist && !tune().bpx && !tune().stages && tune().small_batch;
     if (few) {
         if (conv_i8_patch_ok(p, 4, &ring)) {
-            v.persist = 0; v.bpx = 0; v.stages = 0; v.patch = 4;
+            v.patch = 4;
             return v;
         }
         if (nks >= 8 && r128_ok(p)) {
-            v.persist = 0; v.bpx = 0; v.stages = 0; v.r128 = 1;
+            v.r128 = 1;
             return v;
         }
         v.bpx = 128;
@@ -1236,18 +1249,18 @@ static variant_t default_variant(const mhip_conv_i8_t *p, int nks) {
     // measured 70.8 vs 77.7 us (3x3 256->256 @20x20) and 204 vs 252 us (512->512) at batch 256; on 40-wide maps with 128
     // channels (two chunks per tile: the in-line epilogue is a fifth of a tile) it loses, 81.5 vs 79.2 us
     if (tune().persist && !tune().bpx && !tune().stages && tune().rows && p->out_w <= 20 && p->in_c >= 256 && conv_i8_rows_ok(p)) {
-        v.persist = 0; v.bpx = 0; v.stages = 0; v.rows = 1;
+        v.rows = 1;
         return v;
     }
     if (tune().persist && !tune().bpx && !tune().stages) {
         // 16 output rows per workgroup wherever that patch fits at all (single-buffered included: the taller patch
         // re-reads fewer halo rows, measured 5-40 % over 8 rows on the 160x160 / 80x80 layers), else 8 rows
         if (conv_i8_patch_ok(p, 16, &ring)) {
-            v.persist = 0; v.bpx = 0; v.stages = 0; v.patch = 16;
+            v.patch = 16;
             return v;
         }
         if (conv_i8_patch_ok(p, 8, &ring) && ring >= 2) {
-            v.persist = 0; v.bpx = 0; v.stages = 0; v.patch = 8;
+            v.patch = 8;
             return v;
         }
     }
@@ -1280,10 +1293,9 @@ template <int BPX, int BN>
 static int launch_variant_t(const mhip_conv_i8_t *p, long total_pix, int k64, const variant_t &v) {
     if (v.persist) {
         if (!persist_eligible(p)) return -1;
-        int lg = 0;
-        while ((1 << lg) < p->in_c) lg++;
-        const unsigned magic = ((65536u + (unsigned)p->kw - 1u) / (unsigned)p->kw);
-        if (v.wres && wres_lds<BPX, BN>(k64) > 80 * 1024) return -1;
+        const int lg = log2_of(p->in_c);
+        const unsigned magic = kw_magic(p->kw);
+        if (v.wres && wres_lds(BPX, BN, k64 / BK) > WRES_LDS_MAX) return -1;
         if (p->nseg > 1) // never-materialised concat input: the two-stage tile walker only
             return p->lut ? launch_persist_t<BPX, BN, 2, true, true>(p, total_pix, k64, lg, magic, nullptr, v.wres)
                           : launch_persist_t<BPX, BN, 2, false, true>(p, total_pix, k64, lg, magic, nullptr, v.wres);
@@ -1293,7 +1305,7 @@ static int launch_variant_t(const mhip_conv_i8_t *p, long total_pix, int k64, co
         if (v.stages == 2)
             return p->lut ? launch_persist_t<BPX, BN, 2, true>(p, total_pix, k64, lg, magic)
                           : launch_persist_t<BPX, BN, 2, false>(p, total_pix, k64, lg, magic);
-        return -1; // the three-stage tile walker (variants 6 / 8) is retired: round 4 pruning, never picked by the policy or the tuner
+        return -1; // (no three-stage tile walker)
     }
     if constexpr (BN == 16) {
         return -1; // (the 16-channel tile exists in the tile walker only)
@@ -1309,23 +1321,25 @@ static bool bn16_ok(const mhip_conv_i8_t *p) {
     return !off && p->out_c <= 16 && p->oc_pad == 32 && p->nseg <= 1;
 }
 
+// the (pixels, channels) tile instantiation of a launcher: `launch` takes the two sizes as integral constants.  256 or 128
+// pixels; the channel tile of oc_pad, with `b16` the 16-channel tile in place of the 32-channel one
+template <class F>
+static int with_tile(int bpx, int oc_pad, bool b16, F launch) {
+#define TILE(P, N) launch(std::integral_constant<int, P>{}, std::integral_constant<int, N>{})
+    const int bn = chan_tile(oc_pad);
+    if (bpx == 256) return bn == 128 ? TILE(256, 128) : (bn == 64 ? TILE(256, 64) : (b16 ? TILE(256, 16) : TILE(256, 32)));
+    return bn == 128 ? TILE(128, 128) : (bn == 64 ? TILE(128, 64) : (b16 ? TILE(128, 16) : TILE(128, 32)));
+#undef TILE
+}
+
 static int launch_variant(const mhip_conv_i8_t *p, long total_pix, int k64, const variant_t &v) {
-    if (v.persist < 0) return -1; // a retired variant code
+    if (v.persist < 0) return -1; // NO_VARIANT
     if (v.rows) return conv_i8_launch_rows(p);
     if (v.r128) return launch_r128(p, total_pix, v.r128);
     if (v.patch) return conv_i8_launch_patch(p, k64, v.patch);
-    const int bn = p->oc_pad % 128 == 0 ? 128 : (p->oc_pad % 64 == 0 ? 64 : 32);
-    const bool b16 = v.persist && v.stages == 2 && bn16_ok(p);
-    if (v.bpx == 256) {
-        if (bn == 128) return launch_variant_t<256, 128>(p, total_pix, k64, v);
-        if (bn == 64) return launch_variant_t<256, 64>(p, total_pix, k64, v);
-        if (b16) return launch_variant_t<256, 16>(p, total_pix, k64, v);
-        return launch_variant_t<256, 32>(p, total_pix, k64, v);
-    }
-    if (bn == 128) return launch_variant_t<128, 128>(p, total_pix, k64, v);
-    if (bn == 64) return launch_variant_t<128, 64>(p, total_pix, k64, v);
-    if (b16) return launch_variant_t<128, 16>(p, total_pix, k64, v);
-    return launch_variant_t<128, 32>(p, total_pix, k64, v);
+    return with_tile(v.bpx, p->oc_pad, v.persist && v.stages == 2 && bn16_ok(p), [&](auto bpx, auto bn) {
+        return launch_variant_t<decltype(bpx)::value, decltype(bn)::value>(p, total_pix, k64, v);
+    });
 }
 
 // Two convolutions over the same input in one launch (conv_i8_persist<PAIR>).  -2 = the pair is not eligible (the
@@ -1351,28 +1365,15 @@ extern "C" int mhip_conv_i8_pair(const mhip_conv_i8_t *a, const mhip_conv_i8_t *
         return -2;
     if (a->nseg > 1 && (!seg_valid(a) || !seg_valid(b))) return -2;
     if (!persist_eligible(a) || !persist_eligible(b)) return -2;
-    const int bn = a->oc_pad % 128 == 0 ? 128 : (a->oc_pad % 64 == 0 ? 64 : 32);
-    const int bnb = b->oc_pad % 128 == 0 ? 128 : (b->oc_pad % 64 == 0 ? 64 : 32);
-    if (bn != bnb || !mhip_zero_page()) return -2;
+    if (chan_tile(a->oc_pad) != chan_tile(b->oc_pad) || !mhip_zero_page()) return -2;
     const long total_pix = (long)a->frames * a->out_h * a->out_w;
-    const int k64 = (a->kh * a->row_pad + BK - 1) / BK * BK, nks = k64 / BK;
+    const int k64 = conv_i8_k64(a);
     if (total_pix <= 0 || total_pix > 0x7fffffffL) return -2;
-    int lg = 0;
-    while ((1 << lg) < a->in_c) lg++;
-    const unsigned magic = ((65536u + (unsigned)a->kw - 1u) / (unsigned)a->kw);
-    const variant_t dv = default_variant(a, nks);
-    const int bpx = dv.bpx ? dv.bpx : 128, wres = dv.persist && dv.wres && (tune().wres & 2);
-    const bool b16 = bn16_ok(a) && bn16_ok(b);
-    if (bpx == 256) {
-        if (bn == 128) return launch_pair_t<256, 128>(a, b, total_pix, k64, lg, magic, wres);
-        if (bn == 64) return launch_pair_t<256, 64>(a, b, total_pix, k64, lg, magic, wres);
-        if (b16) return launch_pair_t<256, 16>(a, b, total_pix, k64, lg, magic, wres);
-        return launch_pair_t<256, 32>(a, b, total_pix, k64, lg, magic, wres);
-    }
-    if (bn == 128) return launch_pair_t<128, 128>(a, b, total_pix, k64, lg, magic, wres);
-    if (bn == 64) return launch_pair_t<128, 64>(a, b, total_pix, k64, lg, magic, wres);
-    if (b16) return launch_pair_t<128, 16>(a, b, total_pix, k64, lg, magic, wres);
-    return launch_pair_t<128, 32>(a, b, total_pix, k64, lg, magic, wres);
+    const variant_t dv = default_variant(a, k64 / BK);
+    const int wres = dv.persist && dv.wres && (tune().wres & 2);
+    return with_tile(dv.bpx, a->oc_pad, bn16_ok(a) && bn16_ok(b), [&](auto bpx, auto bn) {
+        return launch_pair_t<decltype(bpx)::value, decltype(bn)::value>(a, b, total_pix, k64, log2_of(a->in_c), kw_magic(a->kw), wres);
+    });
 }
 
 // The same two convolutions in ONE tile (conv_i8_persist<BOTH>): 1x1, stride 1, sides of exactly 64 channels with dense
@@ -1404,7 +1405,7 @@ extern "C" int mhip_conv_i8_both_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_
 // pin either (A / B)
 static void both_form(int rows, int nks, bool chain, int *bpx, int *wres) {
     *bpx = tune().both_bpx == 128 || tune().both_bpx == 256 ? tune().both_bpx : 128;
-    *wres = tune().wres && 2 * LUTB + (chain ? CHAIN_LDS : 0) + 2 * (size_t)*bpx * BK + (size_t)nks * rows * BK <= 80 * 1024;
+    *wres = tune().wres && wres_lds(*bpx, rows, nks, LUTB + (chain ? CHAIN_LDS : 0)) <= WRES_LDS_MAX;
 }
 // ... with the 1x1 `d` (64 -> 64 channels, half-step table, dense rows) that reads side `side` - 1 evaluated in that side's waves
 static bool chain_shape_ok(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const mhip_conv_i8_t *d, int side) {
@@ -1433,6 +1434,16 @@ extern "C" int mhip_conv_i8_both(const mhip_conv_i8_t *a, const mhip_conv_i8_t *
     if (!a || !b || !a->out || !b->out) return -2;
     return both_launch(a, b, nullptr);
 }
+// the instantiations of the one-tile pair form: plain / never-materialised concat input x with / without the chained 1x1 at 256 or
+// 128 pixels, and (WIDE, sides of 128 channels) the 256-row tile at 128 pixels (128 accumulator registers), which has no chain
+template <bool SEG, bool CHAIN, bool WIDE = false>
+static int both_launch_t(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, long total_pix, int k64, int bpx, int wres, const conv_chain_t *ch) {
+    const int lg = log2_of(a->in_c);
+    if constexpr (WIDE) return launch_persist_t<128, 256, 2, true, SEG, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
+    else
+        return bpx == 256 ? launch_persist_t<256, 128, 2, true, SEG, false, true, CHAIN>(a, total_pix, k64, lg, 65536u, b, wres, ch)
+                          : launch_persist_t<128, 128, 2, true, SEG, false, true, CHAIN>(a, total_pix, k64, lg, 65536u, b, wres, ch);
+}
 static int both_launch(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const conv_chain_t *ch) {
     // a launch variant forced from outside (tests, the tuner's knob): the plain pair steps aside like the side-by-side form, so that its members
     // run as that variant; with a chained 1x1 this launch is the plan's only form (as the patch-staged fusions) and runs regardless
@@ -1444,92 +1455,104 @@ static int both_launch(const mhip_conv_i8_t *a, const mhip_conv_i8_t *b, const c
         return -2;
     }
     const long total_pix = (long)a->frames * a->out_h * a->out_w;
-    const int k64 = (a->kh * a->row_pad + BK - 1) / BK * BK, nks = k64 / BK;
-    int lg = 0;
-    while ((1 << lg) < a->in_c) lg++;
+    const int k64 = conv_i8_k64(a);
+    const bool seg = a->nseg > 1;
     int bpx, wres;
-    both_form(2 * a->out_c, nks, ch != nullptr, &bpx, &wres);
-    if (a->out_c == 128) { // sides of 128 channels: the 256-row tile at 128 pixels (128 accumulator registers), no chain
-        if (ch) return -2;
-        return a->nseg > 1 ? launch_persist_t<128, 256, 2, true, true, false, true>(a, total_pix, k64, lg, 65536u, b, wres)
-                           : launch_persist_t<128, 256, 2, true, false, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
-    }
-    if (ch) {
-        if (a->nseg > 1)
-            return bpx == 256 ? launch_persist_t<256, 128, 2, true, true, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch)
-                              : launch_persist_t<128, 128, 2, true, true, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch);
-        return bpx == 256 ? launch_persist_t<256, 128, 2, true, false, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch)
-                          : launch_persist_t<128, 128, 2, true, false, false, true, true>(a, total_pix, k64, lg, 65536u, b, wres, ch);
-    }
-    if (a->nseg > 1)
-        return bpx == 256 ? launch_persist_t<256, 128, 2, true, true, false, true>(a, total_pix, k64, lg, 65536u, b, wres)
-                          : launch_persist_t<128, 128, 2, true, true, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
-    return bpx == 256 ? launch_persist_t<256, 128, 2, true, false, false, true>(a, total_pix, k64, lg, 65536u, b, wres)
-                      : launch_persist_t<128, 128, 2, true, false, false, true>(a, total_pix, k64, lg, 65536u, b, wres);
+    both_form(2 * a->out_c, k64 / BK, ch != nullptr, &bpx, &wres);
+#define BOTH(CHAIN, WIDE) \
+    (seg ? both_launch_t<true, CHAIN, WIDE>(a, b, total_pix, k64, bpx, wres, ch) : both_launch_t<false, CHAIN, WIDE>(a, b, total_pix, k64, bpx, wres, ch))
+    if (a->out_c == 128) return ch ? -2 : BOTH(false, true);
+    return ch ? BOTH(true, false) : BOTH(false, false);
+#undef BOTH
 }
 
 extern "C" int mhip_conv_i8_seg_ok(const mhip_conv_i8_t *p) {
     return p && (p->in_c % 16) == 0 && !mhip_conv_i8_small_c(p->in_c, p->kw, p->out_c) && seg_valid(p) && persist_eligible(p);
 }
 
+// ---- which variant a layer runs
+// the default policy's code: default_variant() for plain layers; a never-materialised concat runs on the tile walker only, with
+// the default's pixel count and resident weights (codes 2 / 4 / 14 / 15)
+static int default_code(const mhip_conv_i8_t *p, int nks) {
+    const variant_t dv = default_variant(p, nks);
+    if (p->nseg <= 1) return variant_code(dv);
+    return dv.persist && dv.wres ? (dv.bpx == 256 ? 15 : 14) : (dv.bpx == 256 ? 4 : 2);
+}
+
 // candidate variant codes of a layer (0 when the layer is not served by these kernels), default first
 extern "C" int mhip_conv_i8_variants(const mhip_conv_i8_t *p, int *codes, int max) {
     if (!p || (p->in_c % 16) != 0 || mhip_conv_i8_small_c(p->in_c, p->kw, p->out_c)) return 0;
-    const int k64 = (p->kh * p->row_pad + BK - 1) / BK * BK, nks = k64 / BK;
+    const int nks = conv_i8_k64(p) / BK;
     int n = 0;
-    if (p->pre_w) { // fused bottleneck: the patch-staged kernel at 16 / 8 / 4 tile rows
-        const int first = conv_i8_pre_tile_rows(p);
-        for (int th : {first, 16, 8, 4})
-            if (th && n < max && conv_i8_patch_ok(p, th, nullptr)) {
-                const int code = th == 16 ? 10 : (th == 8 ? 9 : 11);
-                bool seen = false;
-                for (int i = 0; i < n; i++) seen |= codes[i] == code;
-                if (!seen) codes[n++] = code;
-            }
+    const auto add = [&](int code) {
+        for (int i = 0; i < n; i++)
+            if (codes[i] == code) return;
+        if (n < max) codes[n++] = code;
+    };
+    if (p->pre_w || p->post_w || p->split_w) { // fused forms: the patch-staged kernel at the heights that fit, tallest first; the fused
+                                               // bottleneck's first is the tallest with two patch buffers (conv_i8_tile_rows)
+        for (int th : {p->pre_w ? conv_i8_tile_rows(p, true) : 0, 16, 8, 4})
+            if (th && conv_i8_patch_ok(p, th, nullptr)) add(patch_code(th));
         return n;
     }
-    if (p->post_w) { // fused cv3: the patch-staged kernel at the heights that fit
-        for (int th : {16, 8, 4})
-            if (n < max && conv_i8_patch_ok(p, th, nullptr)) codes[n++] = th == 16 ? 10 : (th == 8 ? 9 : 11);
-        return n;
-    }
-    if (p->split_w) { // fused cv1 + cv2 pair: likewise
-        for (int th : {16, 8, 4})
-            if (n < max && conv_i8_patch_ok(p, th, nullptr)) codes[n++] = th == 16 ? 10 : (th == 8 ? 9 : 11);
-        return n;
-    }
+    add(default_code(p, nks));
+    const int bn = chan_tile(p->oc_pad);
     if (p->nseg > 1) { // the tile walker only: plain, or with resident weights where they fit
-        const int bn = p->oc_pad % 128 == 0 ? 128 : (p->oc_pad % 64 == 0 ? 64 : 32);
-        const variant_t dv = default_variant(p, nks);
-        const int dflt = dv.persist && dv.wres ? (dv.bpx == 256 ? 15 : 14) : (dv.bpx == 256 ? 4 : 2);
-        if (n < max) codes[n++] = dflt;
-        if (n < max && dflt != 2) codes[n++] = 2;
-        if (n < max && dflt != 4) codes[n++] = 4;
-        if (n < max && dflt != 14 && LUTB + 2 * (size_t)128 * BK + (size_t)nks * bn * BK <= 80 * 1024) codes[n++] = 14;
-        if (n < max && dflt != 15 && LUTB + 2 * (size_t)256 * BK + (size_t)nks * bn * BK <= 80 * 1024) codes[n++] = 15;
+        add(2);
+        add(4);
+        if (wres_lds(128, bn, nks) <= WRES_LDS_MAX) add(14);
+        if (wres_lds(256, bn, nks) <= WRES_LDS_MAX) add(15);
         return n;
     }
-    const int dflt = variant_code(default_variant(p, nks));
-    if (n < max) codes[n++] = dflt;
-    for (int code = 1; code <= NVARIANTS; code++) {
-        const variant_t v = variant_of(code);
-        if (code == dflt) continue;
+    for (const auto &e : VARIANTS) {
+        const variant_t &v = e.v;
         if (v.patch && !conv_i8_patch_ok(p, v.patch, nullptr)) continue;
         if (v.persist && !persist_eligible(p)) continue;
         if (v.ks2 && ((nks & 1) || nks < 4 || p->oc_pad % 64 != 0)) continue;
         if (v.w8 && (p->oc_pad % 128 != 0 || nks < 3)) continue;
-        if (v.persist < 0) continue; // retired codes
         if (v.r128 && !r128_ok(p)) continue;
         if (v.rows && !conv_i8_rows_ok(p)) continue;
-        if (v.wres) {
-            const int bn = p->oc_pad % 128 == 0 ? 128 : (p->oc_pad % 64 == 0 ? 64 : 32);
-            if (LUTB + 2 * (size_t)v.bpx * BK + (size_t)nks * bn * BK > 80 * 1024) continue;
-        }
+        if (v.wres && wres_lds(v.bpx, bn, nks) > WRES_LDS_MAX) continue;
         if (!v.persist && v.stages == 3 && nks <= 2) continue; // identical to the 2-stage launch
-        if (n < max) codes[n++] = code;
+        add(e.code);
     }
     return n;
 }
+
+// The fused forms (pre / post / split) run on the patch-staged kernel only: a forced height where it fits, 4 rows when
+// workgroups are few, else `tallest`.  few_limit: post and split pass the few_wgs knob; the fused bottleneck (pre) predates
+// that knob and keeps its constant 256 (nor does it test in_c % 16, see resolve_code)
+static int fused_code(const mhip_conv_i8_t *p, int tallest, long few_limit) {
+    const int want = patch_rows(p->variant ? p->variant : tune().variant);
+    int th = tallest;
+    if (want) { // forced (autotuner / tests)
+        if (conv_i8_patch_ok(p, want, nullptr)) th = want;
+    } else if (tune().small_batch && conv_i8_patch_ok(p, 4, nullptr) && large_tile_wgs(p) < few_limit) {
+        th = 4;
+    }
+    return patch_code(th);
+}
+
+// The variant code mhip_conv_i8 runs `p` with: p->variant, else the "variant" knob where this layer has that variant, else the
+// default policy.  0 = the stem / generic kernels serve the layer, -1 = no kernel takes it as described.  Pure host arithmetic.
+static int resolve_code(const mhip_conv_i8_t *p, int k64) {
+    if (p->in_planar || mhip_conv_i8_small_c(p->in_c, p->kw, p->out_c)) return 0;
+    if (p->pre_w) return mhip_conv_i8_pre_ok(p) ? fused_code(p, conv_i8_tile_rows(p, true), 256) : -1;
+    if (p->post_w) return (p->in_c % 16) == 0 && mhip_conv_i8_post_ok(p) ? fused_code(p, conv_i8_tile_rows(p, false), tune().few_wgs) : -1;
+    if (p->split_w) return (p->in_c % 16) == 0 && mhip_conv_i8_split_ok(p) ? fused_code(p, conv_i8_tile_rows(p, false), tune().few_wgs) : -1;
+    if ((p->in_c % 16) != 0) return 0;
+    if (p->variant < 0 || p->variant > NVARIANTS || (p->nseg > 1 && (!seg_valid(p) || !persist_eligible(p)))) return -1;
+    int code = p->variant;
+    if (!code && tune().variant) { // forced from outside: only where this layer has that variant
+        int codes[NVARIANTS];
+        const int n = mhip_conv_i8_variants(p, codes, NVARIANTS);
+        for (int i = 0; i < n; i++)
+            if (codes[i] == tune().variant) code = codes[i];
+    }
+    if (!code) return default_code(p, k64 / BK);
+    return p->nseg <= 1 || code == 4 || code == 14 || code == 15 ? code : 2;
+}
+extern "C" int mhip_conv_i8_code(const mhip_conv_i8_t *p) { return p ? resolve_code(p, conv_i8_k64(p)) : -1; }
 
 template <int BN>
 static int launch_generic(const mhip_conv_i8_t *p, long total_pix, int k64) {
@@ -1555,7 +1578,7 @@ extern "C" int mhip_conv_i8(const mhip_conv_i8_t *p) {
                    mhip_conv_i8_small_c(p->in_c, p->kw, p->out_c) || p->nseg > 1))
         return -1;
     const long total_pix = (long)p->frames * p->out_h * p->out_w;
-    const int k64 = (p->kh * p->row_pad + BK - 1) / BK * BK;
+    const int k64 = conv_i8_k64(p);
     if (total_pix <= 0 || total_pix > 0x7fffffffL || (total_pix + BP - 1) / BP * (oc_pad / 32) > 0x7fffffffL) return -1;
     if (p->in_planar) { // planes [c][H][W] instead of pixels: only the patch-widening small-channel kernel reads them (it interleaves while staging)
         if (p->in_planar > 4 || p->in_c != 4 || p->in_w < 4 || p->stride_h < 1 || p->stride_w < 1 || p->add || p->nseg > 1 ||
@@ -1574,74 +1597,9 @@ extern "C" int mhip_conv_i8(const mhip_conv_i8_t *p) {
         if (oc_pad % 64 == 0) return launch_generic<64>(p, total_pix, k64);
         return launch_generic<32>(p, total_pix, k64);
     }
-    if (p->pre_w) { // fused bottleneck: the patch-staged kernel at the tallest tile that fits (4 rows for few workgroups)
-        if (!mhip_zero_page() || !mhip_conv_i8_pre_ok(p)) return -1;
-        int th = conv_i8_pre_tile_rows(p);
-        const int code = p->variant ? p->variant : tune().variant;
-        if (code >= 9 && code <= 11) { // forced (autotuner / tests): that height if it fits
-            const int want = code == 10 ? 16 : (code == 9 ? 8 : 4);
-            if (conv_i8_patch_ok(p, want, nullptr)) th = want;
-        } else if (tune().small_batch && conv_i8_patch_ok(p, 4, nullptr) &&
-                   ((long)p->frames * p->out_h * p->out_w + 255) / 256 * ((p->oc_pad + 127) / 128) < 256) {
-            th = 4;
-        }
-        return conv_i8_launch_patch(p, k64, th);
-    }
-    if (p->post_w) { // fused cv3: the patch-staged kernel at the tallest tile that fits (4 rows for few workgroups); no other form runs it
-        if (!mhip_zero_page() || (p->in_c % 16) != 0 || !mhip_conv_i8_post_ok(p)) return -1;
-        int th = conv_i8_post_tile_rows(p);
-        const int code = p->variant ? p->variant : tune().variant;
-        if (code >= 9 && code <= 11) { // forced (tests): that height if it fits
-            const int want = code == 10 ? 16 : (code == 9 ? 8 : 4);
-            if (conv_i8_patch_ok(p, want, nullptr)) th = want;
-        } else if (tune().small_batch && conv_i8_patch_ok(p, 4, nullptr) &&
-                   ((long)p->frames * p->out_h * p->out_w + 255) / 256 * ((p->oc_pad + 127) / 128) < tune().few_wgs) {
-            th = 4;
-        }
-        return conv_i8_launch_patch(p, k64, th);
-    }
-    if (p->split_w) { // fused cv1 + cv2 pair: the same policy, the same single form
-        if (!mhip_zero_page() || (p->in_c % 16) != 0 || !mhip_conv_i8_split_ok(p)) return -1;
-        int th = conv_i8_split_tile_rows(p);
-        const int code = p->variant ? p->variant : tune().variant;
-        if (code >= 9 && code <= 11) { // forced (tests): that height if it fits
-            const int want = code == 10 ? 16 : (code == 9 ? 8 : 4);
-            if (conv_i8_patch_ok(p, want, nullptr)) th = want;
-        } else if (tune().small_batch && conv_i8_patch_ok(p, 4, nullptr) &&
-                   ((long)p->frames * p->out_h * p->out_w + 255) / 256 * ((p->oc_pad + 127) / 128) < tune().few_wgs) {
-            th = 4;
-        }
-        return conv_i8_launch_patch(p, k64, th);
-    }
-    if ((p->in_c % 16) == 0) {
-        if (!mhip_zero_page()) return -1;
-        const int nks = k64 / BK;
-        if (p->variant < 0 || p->variant > NVARIANTS) return -1;
-        int code = p->variant;
-        if (p->nseg > 1) {
-            if (!seg_valid(p) || !persist_eligible(p)) return -1;
-            if (!code && tune().variant) { // forced from outside, as below
-                int codes[NVARIANTS];
-                const int n = mhip_conv_i8_variants(p, codes, NVARIANTS);
-                for (int i = 0; i < n; i++)
-                    if (codes[i] == tune().variant) code = codes[i];
-            }
-            variant_t v = variant_of(code == 4 || code == 14 || code == 15 ? code : 2);
-            if (!code) {
-                const variant_t dv = default_variant(p, nks);
-                v.bpx = dv.bpx ? dv.bpx : 128;
-                v.wres = dv.persist && dv.wres;
-            }
-            return launch_variant(p, total_pix, k64, v);
-        }
-        if (!code && tune().variant) { // forced from outside: only where this layer has that variant
-            int codes[NVARIANTS];
-            const int n = mhip_conv_i8_variants(p, codes, NVARIANTS);
-            for (int i = 0; i < n; i++)
-                if (codes[i] == tune().variant) code = codes[i];
-        }
-        return launch_variant(p, total_pix, k64, code ? variant_of(code) : default_variant(p, nks));
-    }
+    const int code = resolve_code(p, k64);
+    if (code < 0 || (code && !mhip_zero_page())) return -1;
+    if (code) return launch_variant(p, total_pix, k64, variant_of(code));
     if (oc_pad % 64 == 0) return launch_generic<64>(p, total_pix, k64);
     return launch_generic<32>(p, total_pix, k64);
 }

@@ -524,14 +524,17 @@ static inline long persist_out_bytes(const mhip_conv_i8_t *p) {
 static inline bool conv_i8_direct_rows(const mhip_conv_i8_t *p) { // NHWC rows stored straight from registers (as epilogue())
     return !p->out_nchw && ((p->out_c | p->out_pix_stride | p->out_ch_off) & 15) == 0;
 }
+static inline int conv_i8_k64(const mhip_conv_i8_t *p) { // bytes of one packed weight row: the K loop's length, whole 64-byte steps
+    return (p->kh * p->row_pad + BK - 1) / BK * BK;
+}
 
 // conv_i8_patch.hip: can the patch-staged kernel take this layer with `th` (4 | 8 | 16) tile rows?  *ring = patch buffers
 // per workgroup it would run with (1 = the next tile's patch is not prefetched)
 bool conv_i8_patch_ok(const mhip_conv_i8_t *p, int th, int *ring);
 int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th); // -1: not eligible
-int conv_i8_pre_tile_rows(const mhip_conv_i8_t *p);                 // fused bottleneck: tallest tile that fits, 0 = none
-int conv_i8_post_tile_rows(const mhip_conv_i8_t *p);                // fused cv3 (post_* fields): likewise
-int conv_i8_split_tile_rows(const mhip_conv_i8_t *p);               // fused cv1 + cv2 pair (split_* fields): likewise
+// fused forms (pre_* / post_* / split_* fields): tallest tile that fits, 0 = none; need_ring2 (the fused bottleneck): tiles above
+// 4 rows count only with two patch buffers
+int conv_i8_tile_rows(const mhip_conv_i8_t *p, bool need_ring2);
 // conv_i8_rows.hip: whole-row tiles, patch-staged input, streamed weights, one persistent workgroup per CU (variant 20)
 bool conv_i8_rows_ok(const mhip_conv_i8_t *p);
 int conv_i8_launch_rows(const mhip_conv_i8_t *p); // -1: not eligible

@@ -730,8 +730,7 @@ static bool patch_geom(const mhip_conv_i8_t *p, int th, patch_geom_t *g) {
     if (!direct || !p->safe || (C != 16 && C != 32 && C != 64 && C != 128) || (C == 16 && (no_c16 || p->pre_w)) || (s != 1 && s != 2) || p->stride_h != s ||
         p->kh > 7 || p->kw > 7 || p->kh * p->kw < 2 || p->row_pad != p->kw * C || persist_out_bytes(p) > 0x7fffffffL)
         return false;
-    const int k64 = (p->kh * p->row_pad + BK - 1) / BK * BK;
-    g->nks = k64 / BK;
+    g->nks = conv_i8_k64(p) / BK;
     g->bn = p->oc_pad % 64 == 0 ? 64 : 32;
     g->tiles_x = (p->out_w + PT_TW - 1) / PT_TW;
     g->tiles_y = (p->out_h + th - 1) / th;
@@ -883,28 +882,22 @@ int conv_i8_launch_patch(const mhip_conv_i8_t *p, int k64, int th) {
 #undef PATCH
 }
 
-// fused bottleneck (pre_* fields): only the patch-staged kernel evaluates it; some tile height must fit
-int conv_i8_pre_tile_rows(const mhip_conv_i8_t *p) {
+// fused forms (pre_* / post_* / split_* fields): only the patch-staged kernel evaluates them, and the launch has no other form: the tallest
+// tile that fits.  need_ring2 (the fused bottleneck): tiles above 4 rows count only with two patch buffers
+int conv_i8_tile_rows(const mhip_conv_i8_t *p, bool need_ring2) {
     patch_geom_t g;
     for (int th : {16, 8, 4})
-        if (patch_geom(p, th, &g) && (th == 4 || g.ring >= 2)) return th;
+        if (patch_geom(p, th, &g) && (!need_ring2 || th == 4 || g.ring >= 2)) return th;
     return 0;
 }
 extern "C" int mhip_conv_i8_pre_ok(const mhip_conv_i8_t *p) {
     if (!p || !p->pre_w || p->nseg > 1 || p->out_nchw) return 0;
-    return conv_i8_pre_tile_rows(p) != 0;
+    return conv_i8_tile_rows(p, true) != 0;
 }
 
-// fused cv3 (post_* fields): only the patch-staged kernel evaluates it, and the launch has no other form: the tallest tile that fits
-int conv_i8_post_tile_rows(const mhip_conv_i8_t *p) {
-    patch_geom_t g;
-    for (int th : {16, 8, 4})
-        if (patch_geom(p, th, &g)) return th;
-    return 0;
-}
 extern "C" int mhip_conv_i8_post_ok(const mhip_conv_i8_t *p) {
     if (!p || !p->post_w || p->pre_w || p->nseg > 1 || p->out_nchw) return 0;
-    return conv_i8_post_tile_rows(p) != 0;
+    return conv_i8_tile_rows(p, false) != 0;
 }
 extern "C" int mhip_conv_i8_post_k(int c, int k) {
     if (c == 64) return k;
@@ -931,16 +924,9 @@ extern "C" size_t mhip_conv_i8_post_pack(int c, const int8_t *packed, const int3
     return bytes;
 }
 
-// fused cv1 + cv2 pair (split_* fields): only the patch-staged kernel evaluates it, and the launch has no other form: the tallest tile that fits
-int conv_i8_split_tile_rows(const mhip_conv_i8_t *p) {
-    patch_geom_t g;
-    for (int th : {16, 8, 4})
-        if (patch_geom(p, th, &g)) return th;
-    return 0;
-}
 extern "C" int mhip_conv_i8_split_ok(const mhip_conv_i8_t *p) {
     if (!p || !p->split_w || p->pre_w || p->post_w || p->add || p->nseg > 1 || p->out_nchw) return 0;
-    return conv_i8_split_tile_rows(p) != 0;
+    return conv_i8_tile_rows(p, false) != 0;
 }
 extern "C" int mhip_conv_i8_split_row(int side, int oc) {
     const int g = oc >> 3, rem = oc & 7; // a lane group's 8 consecutive channels of one side

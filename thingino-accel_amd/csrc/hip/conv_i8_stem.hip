@@ -574,7 +574,7 @@ static inline const tune_t &tune() { return conv_i8_tune_state(); }
 // operand-direct RGB stem (conv_i8_rgb): -2 = not a shape it takes
 template <int WOC>
 static int try_rgb(const mhip_conv_i8_t *p, int k64) {
-    const bool direct = !p->out_nchw && ((p->out_c | p->out_pix_stride | p->out_ch_off) & 15) == 0; // as epilogue()
+    const bool direct = conv_i8_direct_rows(p);
     const bool rgb_ok = direct && p->in_c == 3 && p->safe && !p->add && (p->lut2 || !p->lut);
     // operand-direct form: 32-bit offsets, stride 2 x even, 16 stored channels per lane, the class shift inside the K slot
     const long in_ext = in_extent_bytes(p), out_ext = persist_out_bytes(p);
@@ -612,7 +612,7 @@ static int launch_smallc(const mhip_conv_i8_t *p, int k64) {
     const int gpr = (PW + 3) / 4;
     if ((long)PH * gpr > 2 * NTHREADS || ntiles > 0x7fffffffL) return -1;
     constexpr int BN = WOC * 16;
-    const bool direct = !p->out_nchw && ((p->out_c | p->out_pix_stride | p->out_ch_off) & 15) == 0; // as epilogue()
+    const bool direct = conv_i8_direct_rows(p);
     const size_t tile_bytes = direct ? 0 : (size_t)SC_BP * (BN + OPAD);
     const size_t lds = (size_t)BN * k64 + 2 * ((((size_t)PH + 1) * PWp * 4 + 15) & ~(size_t)15) + tile_bytes + LUTB +
                        (size_t)SC_BP * 8 + (size_t)BN * 4;

@@ -180,6 +180,9 @@ int mhip_conv_i8_tune(const char *key, int value); /* launch-policy knobs, see m
 int mhip_conv_i8_tune_get(const char *key, int *value);
 /* launch variants that can run this layer (same bytes out, different speed), the default first; 0 if none */
 int mhip_conv_i8_variants(const mhip_conv_i8_t *p, int *codes, int max);
+/* the variant code mhip_conv_i8 runs *p with under p->variant, the "variant" knob and the default policy; 0 = the stem / generic
+ * kernels serve the layer, -1 = no kernel takes it as described.  Pure host arithmetic: no device call, pointers may be dummies */
+int mhip_conv_i8_code(const mhip_conv_i8_t *p);
 /* can this (shape-only: pointers may be dummies) segmented convolution run?  frames/out_stride as they will be */
 int mhip_conv_i8_seg_ok(const mhip_conv_i8_t *p);
 /* two convolutions over the same input in one launch (the second's input reads hit L2); -2 = not eligible as a
