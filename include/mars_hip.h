@@ -1568,6 +1568,115 @@ mars_error_t mars_yolo_motion_boxes(mars_hip_motion_t *m, const mars_det_t *boxe
 /* Device time (ms) of the last mars_hip_motion_device call's two kernels, from events on its stream; waits for it.  < 0: not available. */
 float mars_hip_motion_ms(mars_hip_motion_t *m);
 
+/* --------------------------------------------------------------- Events */
+/* What a deployment does with a track id: count objects over a line in each direction, know who is inside a zone, and raise an event when
+ * something enters, leaves or stays too long.  "Motion" has zones but counts cells without memory; "Tracking" has memory but no geometry.
+ * An events object holds, per camera stream and in HBM like the trackers' tables, the stream's rules, a table of MARS_TRACK_SLOTS slots, a
+ * step counter that starts at 0 and running totals.  A call reads a batch's detection lists and track ids and leaves a record per
+ * detection and counts per frame.  float32 appears only in the anchor, every operation rounded on its own, no fused multiply-add; from the
+ * quantised anchor on everything is integers, and everything is defined to the bit:
+ *
+ * Rules of a stream.  Up to MARS_EVENTS_MAX_LINES directed segments A -> B with A != B, and up to MARS_EVENTS_MAX_ZONES polygons of 3 ..
+ *   MARS_EVENTS_MAX_VERTS vertices each with a `dwell` step count (0: no dwell event).  Every coordinate is integer pixels in [-32768, 32768];
+ *   a polygon need not be convex or simple (the even-odd rule below decides).  Vertices are multiplied by 16 to meet the anchors.
+ * Slot.  {id, last_step, qx, qy, inside, dwelled, since[MARS_EVENTS_MAX_ZONES]}: the track id (0: the slot is free), the step it was last
+ *   seen at, its anchor then, the mask of the zones it was inside then, the mask of the zones whose dwell event has fired since it entered,
+ *   and per zone the step it entered at.
+ * Frames -> streams.  The rule of "Tracking": a call over F frames and an object of S streams needs F % S == 0.  Default: frame f is stream
+ *   f % S, step f / S.  MARS_EVENTS_STREAM_MAJOR: stream f / (F / S), step f % (F / S).  A stream's steps are processed in ascending order;
+ *   streams are independent.  State persists between calls: one call over 2 T steps leaves exactly the state and outputs of two calls over
+ *   T steps each.
+ * Participants of a frame with lists d[0 .. n), tr[0 .. n).  Entry i is a CANDIDATE when tr[i].id >= 1, tr[i].hits >= min_hits and d[i].x,
+ *   y, w, h are all finite.  A candidate whose id an earlier candidate (a lower index) of the frame brings too adds to `duplicates`; the
+ *   others are the PARTICIPANTS.  The first MARS_TRACK_MAX_CAND participants by index are used, the rest add to `overflow`.  The record of
+ *   every entry that is not a used participant, up to the array's width, is all zero.
+ * Anchor.  ax = x;  ay = y, or under MARS_EVENTS_ANCHOR_BOTTOM ay = y + h * 0.5f (one multiply, one add).  For a in (ax, ay):
+ *   c = fminf(fmaxf(a, -32768.0f), 32768.0f);  q = (int)floorf(c * 16.0f).  Q = (qx, qy), |q| <= 2^19.
+ * Step, in this order, `step` being the stream's counter:
+ *   1 Expiry.  Every used slot with step - last_step > max_gap is freed; `expired` grows by one and each zone of its `inside` adds one to
+ *     that zone's `lost`.
+ *   2 Lookup.  A used participant takes the slot that holds its id.  Those without one, by ascending index, take the free slots by ascending
+ *     slot (slots freed in 1 count as free).  With no free slot `dropped` grows by one and the record is all zero.
+ *   3 First sight (a slot just taken).  id = the participant's, qx, qy = Q, inside = zones(Q), since[z] = step for those zones, dwelled = 0;
+ *     `first` grows by one.  The record is {zones = inside, everything else 0}: no enter event and no crossing.
+ *   4 Seen again, P = (qx, qy) of the slot.  All products are int64 (the operands are below 2^21).  cross(u, v) = u.x * v.y - u.y * v.x.
+ *     Lines.  side(X) = cross(B - A, X - A) >= 0.  Line l is crossed when side(P) != side(Q) and
+ *       (cross(Q - P, A - P) >= 0) != (cross(Q - P, B - P) >= 0); it is `in` when side goes 0 -> 1 and `out` otherwise.  Both tests are
+ *       half-open: a point on the line is on the positive side, and a path through an end point counts for exactly one of two segments
+ *       that continue each other through it.  P == Q crosses nothing.
+ *     Zones, the even-odd crossing number.  For every edge (V, W) of the polygon in order, the last vertex closing back to the first: if
+ *       (V.y > Q.y) != (W.y > Q.y) then d = W.y - V.y, lhs = (Q.x - V.x) * d, rhs = (W.x - V.x) * (Q.y - V.y), and the parity toggles when
+ *       d > 0 ? lhs < rhs : lhs > rhs.  now = the mask of the zones with odd parity (this is zones(Q) of 3 as well).
+ *     Events.  entered = now & ~inside, exited = inside & ~now.  since[z] = step for the entered zones; the `dwelled` bits of entered and
+ *       exited zones are cleared.  For z in now with dwell[z] > 0, step - since[z] >= dwell[z] and the bit clear in `dwelled`: the dwell
+ *       event fires and the bit is set, so it fires once per stay.  Then inside = now, qx, qy = Q.  The record is {zones = now, entered,
+ *       exited, dwelled = the events fired in this step, lines_in, lines_out}.
+ *     A track seen again after a gap of at most max_gap steps is judged over the whole gap: P is where it was last seen.
+ *   5 last_step = step for every slot seen.  Then step += 1.
+ * Counts.  line_counts[f][l] = {in, out}: the number of the frame's records with bit l in lines_in, in lines_out.  zone_counts[f][z] =
+ *   {inside, entered, exited, dwelled}: likewise over zones, entered, exited, dwelled.  Both arrays are MARS_EVENTS_MAX_LINES and _ZONES
+ *   wide whatever the stream's rules hold; the rest is zero.
+ * Totals, per stream since the last reset, int64: per line {in, out}; per zone {entered, exited, dwelled, lost}; the counters {first,
+ *   expired, overflow, dropped, duplicates}.
+ * Not covered: the mars_hip_pipe_* path; the merged lists of "Tiled inference"; polylines as one rule (give one line per segment: the
+ *   half-open tests make them add up); zones from masks or oriented boxes; per-class rules; speed; an event queue (the caller reads the
+ *   records and the counts); more than 2^31 steps per stream. */
+#define MARS_EVENTS_MAX_LINES 32
+#define MARS_EVENTS_MAX_ZONES 32
+#define MARS_EVENTS_MAX_VERTS 8
+#define MARS_EVENTS_STREAM_MAJOR 1u
+#define MARS_EVENTS_ANCHOR_BOTTOM 2u
+typedef struct { int ax, ay, bx, by; } mars_event_line_t;                                                   /* 16 bytes */
+typedef struct { int n, dwell; int x[MARS_EVENTS_MAX_VERTS], y[MARS_EVENTS_MAX_VERTS]; } mars_event_zone_t;   /* 72 bytes */
+typedef struct {
+    int n_lines, n_zones;
+    mars_event_line_t lines[MARS_EVENTS_MAX_LINES];
+    mars_event_zone_t zones[MARS_EVENTS_MAX_ZONES];
+} mars_hip_event_rules_t;                                                                                   /* 2824 bytes */
+typedef struct { uint32_t zones, entered, exited, dwelled, lines_in, lines_out; } mars_event_t;             /* 24 bytes */
+typedef struct { int id, last_step, qx, qy; uint32_t inside, dwelled; int since[MARS_EVENTS_MAX_ZONES]; } mars_event_slot_t; /* 152 bytes */
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int max_gap;           /* 0: 30 */
+    int min_hits;          /* 0: 1 */
+    unsigned flags;        /* MARS_EVENTS_STREAM_MAJOR | MARS_EVENTS_ANCHOR_BOTTOM */
+} mars_hip_events_opts_t;
+typedef struct mars_hip_events mars_hip_events_t; /* opaque */
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: NULL where a pointer is needed; non-positive streams, frames
+ * or max_det; a negative option; an unknown flag; a line or zone count out of range; a vertex count outside 3 .. MARS_EVENTS_MAX_VERTS; a
+ * coordinate outside +-32768; a line with A == B; a negative dwell.  MARS_ERR_INVALID_TENSOR: streams above 65535, max_det above
+ * MARS_YOLO_MAX_DET, F % S != 0, a stream out of range, no detections or no track results in HBM, *_results with nothing pending, a model
+ * with an open pipe.  A refused call leaves the state as it was. */
+mars_error_t mars_hip_events_create(int streams, mars_hip_events_t **out);       /* 1 .. 65535; no rules on any stream */
+void         mars_hip_events_free(mars_hip_events_t *ev);                        /* waits for the device first */
+/* That stream's table empty, its step and totals zero, its rules kept; -1: all streams; waits. */
+mars_error_t mars_hip_events_reset(mars_hip_events_t *ev, int stream);
+/* Waits, copies the rules and resets that stream; -1: all streams. */
+mars_error_t mars_hip_events_set_rules(mars_hip_events_t *ev, int stream, const mars_hip_event_rules_t *rules);
+/* Waits.  The totals and counters of one stream, the number of used slots and the step counter; any pointer may be NULL. */
+mars_error_t mars_hip_events_read(mars_hip_events_t *ev, int stream, long long line_totals[MARS_EVENTS_MAX_LINES][2],
+                                  long long zone_totals[MARS_EVENTS_MAX_ZONES][4], long long counters[5], int *n_used, int *step);
+/* Waits.  The table of one stream, slots = [MARS_TRACK_SLOTS], in canonical form: a free slot is all zero, and since[z] is zero for every
+ * zone the slot is not inside (nothing reads those). */
+mars_error_t mars_hip_events_read_slots(mars_hip_events_t *ev, int stream, mars_event_slot_t *slots);
+/* The mars_yolo_track_lists of this feature: host pointers in and out, runs the same kernel on the GPU and waits.  dets, tracks and records
+ * are [frames][max_det], 1 <= max_det <= MARS_YOLO_MAX_DET; counts = [frames] (clamped to 0 .. max_det); line_counts =
+ * [frames][MARS_EVENTS_MAX_LINES][2] and zone_counts = [frames][MARS_EVENTS_MAX_ZONES][4], either may be NULL. */
+mars_error_t mars_yolo_event_lists(mars_hip_events_t *ev, const mars_det_t *dets, const mars_track_t *tracks, const int *counts, int frames, int max_det,
+                                   const mars_hip_events_opts_t *opts, mars_event_t *records, int *line_counts, int *zone_counts);
+/* Reads the detection lists and the track array the last mars_hip_track_device or mars_hip_track_app_device left on det_model in HBM (F =
+ * its batch).  Enqueues only, on the auxiliary stream with the label scatter's ordering: behind the tracker, ahead of the model's next
+ * detect call.  The record array lives on det_model beside the tracks and is freed with the model; the per-frame counts live on ev. */
+mars_error_t mars_hip_events_device(mars_model_t *det_model, mars_hip_events_t *ev, const mars_hip_events_opts_t *opts);
+/* Waits.  records = [batch of det_model][MARS_YOLO_MAX_DET]: entry i of frame f belongs to dets[f][i] of mars_hip_detect_results; the counts
+ * as in mars_yolo_event_lists.  Any of the three may be NULL.  ev must be the object of det_model's last mars_hip_events_device call. */
+mars_error_t mars_hip_events_results(mars_model_t *det_model, mars_hip_events_t *ev, mars_event_t *records, int *line_counts, int *zone_counts);
+/* mars_hip_events_device + mars_hip_events_results. */
+mars_error_t mars_hip_events(mars_model_t *det_model, mars_hip_events_t *ev, const mars_hip_events_opts_t *opts, mars_event_t *records,
+                             int *line_counts, int *zone_counts);
+/* Device time (ms) of the last call's kernel (either form), from events on its stream; waits for it.  < 0: not available. */
+float mars_hip_events_ms(mars_hip_events_t *ev);
+
 #ifdef __cplusplus
 }
 #endif

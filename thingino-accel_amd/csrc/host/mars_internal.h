@@ -266,6 +266,8 @@ typedef struct mars_model_ext {
     size_t overlay_img_bytes;
     /* motion (mars_motion.c) */
     mars_det_side_t motion; /* moved cells of THIS model's detections: x mars_motion_det_t */
+    /* events (mars_events.c) */
+    mars_det_side_t event;  /* event records of THIS model's detections: x mars_event_t */
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 

@@ -807,6 +807,40 @@ typedef struct {
 } mhip_motion_dets_t;
 int mhip_motion_dets(const mhip_motion_dets_t *p);
 
+/* ---- events (events.hip): detection lists and their track ids -> line crossings, zone entry, exit and dwell per detection, per frame and
+ * per stream, by the exact rule of include/mars_hip.h ("Events").  One workgroup per stream walks that stream's `steps` frames in order;
+ * thread s owns slot s of the stream's table.  Every pointer is device memory. */
+#define MHIP_EVENTS_LINES 32
+#define MHIP_EVENTS_ZONES 32
+#define MHIP_EVENTS_VERTS 8
+#define MHIP_EVENTS_TOTALS (2 * MHIP_EVENTS_LINES + 4 * MHIP_EVENTS_ZONES + 5)
+/* a stream's rules as the kernel reads them: every coordinate already multiplied by 16 */
+typedef struct {
+    int n_lines, n_zones;
+    int lines[MHIP_EVENTS_LINES][4];                                                    /* ax, ay, bx, by */
+    struct { int n, dwell, x[MHIP_EVENTS_VERTS], y[MHIP_EVENTS_VERTS]; } zones[MHIP_EVENTS_ZONES];
+} mhip_event_rules_t;
+/* a stream's step counter and running totals: [line][in, out], [zone][entered, exited, dwelled, lost], first, expired, overflow, dropped,
+ * duplicates */
+typedef struct { int step, pad; long long tot[MHIP_EVENTS_TOTALS]; } mhip_events_hdr_t;
+typedef struct {
+    int streams, steps;     /* frames = streams * steps */
+    int max_det;            /* row length of dets, tracks and records: 1 .. 1000 */
+    int stream_major;       /* frame of (stream b, step t): b * steps + t; otherwise t * streams + b */
+    const void *dets;       /* [frames][max_det] records of 24 bytes {float x, y, w, h, conf; int cls} */
+    const void *tracks;     /* [frames][max_det] records of 8 bytes {int id, hits} */
+    const int *counts;      /* [frames]; clamped to 0 .. max_det */
+    void *records;          /* [frames][max_det] records of 24 bytes (mars_event_t) */
+    int *line_counts;       /* [frames][MHIP_EVENTS_LINES][2] */
+    int *zone_counts;       /* [frames][MHIP_EVENTS_ZONES][4] */
+    void *slots;            /* [streams][MHIP_TRACK_SLOTS] records of 152 bytes (mars_event_slot_t); id == 0: a free slot */
+    mhip_events_hdr_t *hdr; /* [streams] */
+    const mhip_event_rules_t *rules; /* [streams] */
+    int max_gap, min_hits;  /* resolved: >= 1 */
+    int anchor_bottom;
+} mhip_events_t;
+int mhip_events(const mhip_events_t *p); /* one launch */
+
 #ifdef __cplusplus
 }
 #endif

@@ -259,7 +259,32 @@ class MotionOpts(C.Structure):  # mars_hip_motion_opts_t: zero = default in ever
                 ("n_zones", C.c_int), ("zones", C.c_void_p)]
 
 
+EVENTS_MAX_LINES, EVENTS_MAX_ZONES, EVENTS_MAX_VERTS = 32, 32, 8          # MARS_EVENTS_*
+EVENTS_STREAM_MAJOR, EVENTS_ANCHOR_BOTTOM = 1, 2
+EVENT_DTYPE = np.dtype([("zones", "<u4"), ("entered", "<u4"), ("exited", "<u4"), ("dwelled", "<u4"), ("lines_in", "<u4"),
+                        ("lines_out", "<u4")])                           # mars_event_t
+EVENT_SLOT_DTYPE = np.dtype([("id", "<i4"), ("last_step", "<i4"), ("qx", "<i4"), ("qy", "<i4"), ("inside", "<u4"), ("dwelled", "<u4"),
+                             ("since", "<i4", (EVENTS_MAX_ZONES,))])      # mars_event_slot_t
+
+
+class EventLine(C.Structure):  # mars_event_line_t
+    _fields_ = [("ax", C.c_int), ("ay", C.c_int), ("bx", C.c_int), ("by", C.c_int)]
+
+
+class EventZone(C.Structure):  # mars_event_zone_t
+    _fields_ = [("n", C.c_int), ("dwell", C.c_int), ("x", C.c_int * EVENTS_MAX_VERTS), ("y", C.c_int * EVENTS_MAX_VERTS)]
+
+
+class EventRules(C.Structure):  # mars_hip_event_rules_t
+    _fields_ = [("n_lines", C.c_int), ("n_zones", C.c_int), ("lines", EventLine * EVENTS_MAX_LINES), ("zones", EventZone * EVENTS_MAX_ZONES)]
+
+
+class EventsOpts(C.Structure):  # mars_hip_events_opts_t: zero = default in every field
+    _fields_ = [("max_gap", C.c_int), ("min_hits", C.c_int), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert EVENT_DTYPE.itemsize == 24 and EVENT_SLOT_DTYPE.itemsize == 152 and C.sizeof(EventRules) == 2824 and C.sizeof(EventsOpts) == 12
 assert MOTION_STATS_DTYPE.itemsize == 24 and MOTION_DET_DTYPE.itemsize == 8 and C.sizeof(MotionOpts) == 32
 assert REDACT_STATS_DTYPE.itemsize == 16 and C.sizeof(RedactOpts) == 52
 assert OVERLAY_STATS_DTYPE.itemsize == 24 and C.sizeof(OverlayOpts) == 104
@@ -330,7 +355,10 @@ EXPORTS = {
                    "mars_hip_overlay_device", "mars_hip_overlay_results", "mars_hip_overlay", "mars_hip_overlay_ms",
                    "mars_hip_motion_create", "mars_hip_motion_reset", "mars_hip_motion_free", "mars_hip_motion_grid", "mars_hip_motion_read",
                    "mars_yolo_motion_frames", "mars_hip_motion_device", "mars_hip_motion_results", "mars_hip_motion_detections_device",
-                   "mars_hip_motion_det_results", "mars_yolo_motion_boxes", "mars_hip_motion_ms"],
+                   "mars_hip_motion_det_results", "mars_yolo_motion_boxes", "mars_hip_motion_ms",
+                   "mars_hip_events_create", "mars_hip_events_free", "mars_hip_events_reset", "mars_hip_events_set_rules", "mars_hip_events_read",
+                   "mars_hip_events_read_slots", "mars_yolo_event_lists", "mars_hip_events_device", "mars_hip_events_results", "mars_hip_events",
+                   "mars_hip_events_ms"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -537,6 +565,20 @@ def lib():
     L.mars_yolo_motion_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
     L.mars_hip_motion_ms.restype = C.c_float
     L.mars_hip_motion_ms.argtypes = [C.c_void_p]
+    L.mars_hip_events_create.argtypes = [C.c_int, P(C.c_void_p)]
+    L.mars_hip_events_free.argtypes = [C.c_void_p]
+    L.mars_hip_events_free.restype = None
+    L.mars_hip_events_reset.argtypes = [C.c_void_p, C.c_int]
+    L.mars_hip_events_set_rules.argtypes = [C.c_void_p, C.c_int, P(EventRules)]
+    L.mars_hip_events_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int)]
+    L.mars_hip_events_read_slots.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mars_yolo_event_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(EventsOpts), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    L.mars_hip_events_device.argtypes = [P(MarsModel), C.c_void_p, P(EventsOpts)]
+    L.mars_hip_events_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_events.argtypes = [P(MarsModel), C.c_void_p, P(EventsOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mars_hip_events_ms.restype = C.c_float
+    L.mars_hip_events_ms.argtypes = [C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -1078,6 +1120,111 @@ class Motion:
         if self.p:
             lib().mars_hip_motion_free(self.p)
             self.p = None
+
+
+def event_rules(lines=(), zones=()):
+    """mars_hip_event_rules_t.  lines: rows of (ax, ay, bx, by), directed A -> B; zones: polygons, each a list of 3 .. EVENTS_MAX_VERTS
+    (x, y) vertices, or a pair (vertices, dwell steps).  Integer pixels in [-32768, 32768].  Counts beyond what the record holds raise
+    ValueError; everything else is left to the library's checks"""
+    lines, zones = list(lines), list(zones)
+    if len(lines) > EVENTS_MAX_LINES or len(zones) > EVENTS_MAX_ZONES:
+        raise ValueError("at most %d lines and %d zones" % (EVENTS_MAX_LINES, EVENTS_MAX_ZONES))
+    r = EventRules()
+    r.n_lines, r.n_zones = len(lines), len(zones)
+    for k, ln in enumerate(lines):
+        r.lines[k] = EventLine(*[int(v) for v in ln])
+    for k, z in enumerate(zones):
+        verts, dwell = (z[0], z[1]) if len(z) == 2 and not np.isscalar(z[0]) and np.isscalar(z[1]) else (z, 0)
+        if len(verts) > EVENTS_MAX_VERTS:
+            raise ValueError("at most %d vertices" % EVENTS_MAX_VERTS)
+        r.zones[k].n, r.zones[k].dwell = len(verts), int(dwell)
+        for v, (x, y) in enumerate(verts):
+            r.zones[k].x[v], r.zones[k].y[v] = int(x), int(y)
+    return r
+
+
+def event_opts(max_gap=0, min_hits=0, stream_major=False, anchor_bottom=False, flags=None):
+    """mars_hip_events_opts_t; zero means default everywhere (max_gap 30, min_hits 1, the anchor is the box centre).  flags overrides
+    stream_major and anchor_bottom"""
+    f = int(flags) if flags is not None else (EVENTS_STREAM_MAJOR if stream_major else 0) | (EVENTS_ANCHOR_BOTTOM if anchor_bottom else 0)
+    return EventsOpts(int(max_gap), int(min_hits), f)
+
+
+class Events:
+    """mars_hip_events_t: per camera stream the rules (lines and zones), a table of TRACK_SLOTS slots, a step counter and running totals,
+    held on the device between calls"""
+
+    def __init__(self, streams):
+        self.streams = int(streams)
+        self.p = C.c_void_p()
+        rc = lib().mars_hip_events_create(self.streams, C.byref(self.p))
+        if rc != MARS_OK:
+            self.p = C.c_void_p()
+            raise MarsError(rc, "mars_hip_events_create")
+
+    def set_rules(self, rules, stream=-1):
+        """the rules of one stream (-1: of all) are replaced and that stream is reset (mars_hip_events_set_rules); waits"""
+        rc = lib().mars_hip_events_set_rules(self.p, int(stream), C.byref(rules))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events_set_rules")
+
+    def reset(self, stream=-1):
+        """that stream's table empty, its step and totals zero, its rules kept (-1: all streams); waits"""
+        rc = lib().mars_hip_events_reset(self.p, int(stream))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events_reset")
+
+    def read(self, stream):
+        """-> (line totals int64 [EVENTS_MAX_LINES][in, out], zone totals int64 [EVENTS_MAX_ZONES][entered, exited, dwelled, lost], counters
+        int64 [first, expired, overflow, dropped, duplicates], used slots, step) of one stream (mars_hip_events_read); waits"""
+        lt = np.zeros((EVENTS_MAX_LINES, 2), dtype=np.int64)
+        zt = np.zeros((EVENTS_MAX_ZONES, 4), dtype=np.int64)
+        cnt = np.zeros(5, dtype=np.int64)
+        used, step = C.c_int(0), C.c_int(0)
+        rc = lib().mars_hip_events_read(self.p, int(stream), lt.ctypes.data, zt.ctypes.data, cnt.ctypes.data, C.byref(used), C.byref(step))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events_read")
+        return lt, zt, cnt, used.value, step.value
+
+    def read_slots(self, stream):
+        """-> EVENT_SLOT_DTYPE [TRACK_SLOTS], the table of one stream in canonical form (mars_hip_events_read_slots); waits"""
+        slots = np.zeros(TRACK_SLOTS, dtype=EVENT_SLOT_DTYPE)
+        rc = lib().mars_hip_events_read_slots(self.p, int(stream), slots.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events_read_slots")
+        return slots
+
+    def ms(self):
+        """device time (ms) of the last call's kernel (mars_hip_events_ms); < 0: not available"""
+        return float(lib().mars_hip_events_ms(self.p))
+
+    def close(self):
+        if self.p:
+            lib().mars_hip_events_free(self.p)
+            self.p = C.c_void_p()
+
+
+def _event_arrays(frames, max_det):
+    return (np.zeros((frames, max_det), dtype=EVENT_DTYPE), np.zeros((frames, EVENTS_MAX_LINES, 2), dtype=np.int32),
+            np.zeros((frames, EVENTS_MAX_ZONES, 4), dtype=np.int32))
+
+
+def event_lists(events, dets, tracks, counts, opts=None):
+    """mars_yolo_event_lists: dets = DET_DTYPE [frames][max_det], tracks = TRACK_DTYPE of that shape, counts = [frames] -> (EVENT_DTYPE
+    [frames][max_det], line counts int32 [frames][EVENTS_MAX_LINES][in, out], zone counts int32 [frames][EVENTS_MAX_ZONES][inside, entered,
+    exited, dwelled]), on the GPU; the object's tables move on by these frames"""
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    t = np.ascontiguousarray(tracks, dtype=TRACK_DTYPE)
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if d.ndim != 2 or d.shape[0] != c.size or t.shape != d.shape:
+        raise ValueError("dets and tracks must be [frames][max_det] with one count per frame")
+    o = opts if opts is not None else event_opts()
+    rec, lc, zc = _event_arrays(d.shape[0], d.shape[1])
+    rc = lib().mars_yolo_event_lists(events.p, d.ctypes.data, t.ctypes.data, c.ctypes.data, d.shape[0], d.shape[1], C.byref(o), rec.ctypes.data,
+                                     lc.ctypes.data, zc.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_event_lists")
+    return rec, lc, zc
 
 
 def cls_opts(output_index=0, tensor=0, top_k=0, scale=0.0, softmax=False):
@@ -2102,6 +2249,33 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_track")
         return tracks
+
+    def events_device(self, events, opts=None, **kw):
+        """THIS model is the detector: the detections its last detect_*_device call left in HBM and the track ids track_device or
+        track_app_device hung on them go through the events object, on the device (mars_hip_events_device); enqueues only.  opts =
+        event_opts(...), or its keywords"""
+        o = opts if opts is not None else event_opts(**kw)
+        rc = lib().mars_hip_events_device(self.p, events.p, C.byref(o))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events_device")
+
+    def events_results(self, events):
+        """-> (EVENT_DTYPE [batch][MAX_DET], line counts, zone counts) as event_lists gives them: entry i of frame f belongs to
+        detect_results()[f][i] (mars_hip_events_results); waits"""
+        rec, lc, zc = _event_arrays(self.batch, MAX_DET)
+        rc = lib().mars_hip_events_results(self.p, events.p, rec.ctypes.data, lc.ctypes.data, zc.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events_results")
+        return rec, lc, zc
+
+    def events(self, events, opts=None, **kw):
+        """events_device + events_results (mars_hip_events)"""
+        o = opts if opts is not None else event_opts(**kw)
+        rec, lc, zc = _event_arrays(self.batch, MAX_DET)
+        rc = lib().mars_hip_events(self.p, events.p, C.byref(o), rec.ctypes.data, lc.ctypes.data, zc.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_events")
+        return rec, lc, zc
 
     def write_tensor(self, idx, data, frame=0):
         """mars_hip_write_tensor: one frame of an activation tensor from host memory"""
