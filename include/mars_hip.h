@@ -1677,6 +1677,127 @@ mars_error_t mars_hip_events(mars_model_t *det_model, mars_hip_events_t *ev, con
 /* Device time (ms) of the last call's kernel (either form), from events on its stream; waits for it.  < 0: not available. */
 float mars_hip_events_ms(mars_hip_events_t *ev);
 
+/* ------------------------------------------------------------ Best shots */
+/* What a track looked like.  Every deployment that keeps track ids stores one picture per track: the frame in which the object was
+ * largest, sharpest and most confidently seen.  The crops (the second model's input, as the crop calls wrote it), the join from crop to
+ * detection (the ROI table) and the track ids are in HBM already; a shots object adds, per camera stream and in HBM, a table of `slots`
+ * entries, a pixel plane [slots][tw * th * 3] int8 in the crops' layout, a step counter that starts at 0 and counters.  A call measures
+ * every crop, keeps the best crop of every live track with its pixels, and hands a track's picture over once the track has ended.
+ * Everything is integer arithmetic apart from one float-to-int conversion of the confidence, and everything is defined to the byte:
+ *
+ * Crop.  tw * th * 3 int8 bytes as the crop kernels write them: the pixel minus 128, [th][tw][3] (nhwc) or [3][th][tw].  u = byte + 128,
+ *   0 .. 255, is the pixel.  ROI entry k = {frame, det, x0, y0, x1, y1} belongs to crop k; cw = x1 - x0, ch = y1 - y0 (differences and
+ *   every product below in int64).
+ * Content rectangle [px, px + nw) x [py, py + nh) of the target.  Without MARS_SHOT_KEEP_ASPECT the whole target: px = py = 0, nw = tw,
+ *   nh = th.  With it, the integer rule of "ROI crops", "Target geometry", / floor:
+ *     cw * th >= ch * tw:  nw = tw, nh = max(1, (ch * tw + cw / 2) / cw);   otherwise:  nh = th, nw = max(1, (cw * th + ch / 2) / ch);
+ *     px = (tw - nw) / 2, py = (th - nh) / 2.
+ *   A crop whose entry has x1 <= x0 or y1 <= y0, or a frame outside the call's frames, has NO CONTENT.
+ * Luma.  Y = (77 * R + 150 * G + 29 * B + 128) >> 8 of the pixel's u values, 0 .. 255.
+ * Metrics of a crop.  mean = (sum of Y over the content) / (nw * nh), / floor.  For every content pixel whose four neighbours lie inside
+ *   the content:  L = 4 * Y(x, y) - Y(x - 1, y) - Y(x + 1, y) - Y(x, y - 1) - Y(x, y + 1), |L| <= 1020;
+ *   sharp = (sum of L * L, int64) / ((nw - 2) * (nh - 2)), 0 when nw < 3 or nh < 3; sharp <= 1 040 400.  No content: mean = sharp = 0.
+ * Score, int64 factors.  a = min(cw * ch, tw * th): source pixels beyond the target's size add nothing.
+ *   c = (int)floorf(fminf(fmaxf(conf, 0.0f), 1.0f) * 1024.0f), the product rounded once, no fused multiply-add; a non-finite conf gives
+ *   c = 0.  score = a * (sharp + 1) * c < 2^52.
+ * Frames -> streams.  The rule of "Tracking": a call over F frames and an object of S streams needs F % S == 0.  Default: frame f is stream
+ *   f % S, step f / S.  MARS_SHOT_STREAM_MAJOR: stream f / (F / S), step f % (F / S).  Every frame is a step of its stream even when it has
+ *   no crop.  A stream's steps are processed in ascending order; streams are independent.  State persists between calls: one call over 2 T
+ *   steps leaves exactly the state, plane and outputs of two calls over T steps each.
+ * Candidates of a step.  Crops are visited by ascending crop index k.  Crop k is a CANDIDATE when k < kept (the number of crops written),
+ *   its frame maps to this step, it has content, track.id >= 1 and track.hits >= min_hits, min_mean <= mean <= max_mean (0 in both fields:
+ *   no window), sharp >= min_sharp and, under MARS_SHOT_INSIDE, its rectangle touches no border of the src_w x src_h frame: x0 > 0, y0 > 0,
+ *   x1 < src_w, y1 < src_h.  A candidate whose id a candidate with a lower index of the same step brings too adds to `duplicates`.  The
+ *   first MARS_TRACK_MAX_CAND of the remaining ones are the PARTICIPANTS, the others add to `overflow`.
+ * Step, in this order, `step` being the stream's counter:
+ *   1 Expiry.  Every LIVE slot with step - last_step > max_gap becomes DONE and keeps its shot; `finished` grows by one per slot.
+ *   2 Lookup.  A participant takes the LIVE slot that holds its id.  Those without one, by ascending index, each take the lowest FREE slot;
+ *     if there is none the lowest DONE slot (slots that 1 just finished included), whose shot is overwritten: `lost` grows by one; if there
+ *     is none of either `dropped` grows by one and the crop's record names slot -1.
+ *   3 First sight (a slot just taken).  The slot becomes LIVE: id, first_step = best_step = step, seen = taken = 1, the metrics, the
+ *     score, conf, cls and the rectangle of this crop, and its pixels.
+ *   4 Seen again.  seen += 1.  If score > the slot's score (strictly: a tie keeps the older shot) the slot takes this crop's metrics,
+ *     score, conf, cls, rectangle, best_step = step and pixels, and taken += 1.
+ *   5 last_step = step for every slot seen.  Then step += 1.
+ *   The counter `taken` grows by one for every crop 3 or 4 stored.
+ * Record per crop, mars_shot_t.  Every crop k < kept with content gets its metrics and its score, tracked or not; slot = the table slot of a
+ *   participant that found one, else -1; taken = 1 where 3 or 4 stored the crop.  Entries at k >= kept and crops without content are
+ *   {0, 0, 0, -1, 0}.
+ * Slot, mars_shot_slot_t.  state: 0 FREE, 1 LIVE, 2 DONE.  A FREE slot reads back all zero.  Only mars_hip_shots_collect and a reset free
+ *   a slot.
+ * Not covered: the mars_hip_pipe_* path; MARS_SHOT_KEEP_ASPECT behind a rotated or aligned crop call (those calls have their own geometry:
+ *   crop with stretch there); crops cut at a resolution of the shots object's own (the thumbnail is the second model's input); weights in
+ *   the score; pose or frontality terms in the score; more than one shot per track; a second-model input kept at a row pitch (refused); a
+ *   host write into the second model's input while a shots call is pending (wait first: only the crop calls wait by themselves); more than
+ *   2^31 steps per stream. */
+#define MARS_SHOT_STREAM_MAJOR 1u
+#define MARS_SHOT_KEEP_ASPECT 2u
+#define MARS_SHOT_INSIDE 4u
+#define MARS_SHOT_FREE 0
+#define MARS_SHOT_LIVE 1
+#define MARS_SHOT_DONE 2
+typedef struct { long long score; int sharp, mean, slot, taken; } mars_shot_t;                               /* 24 bytes */
+typedef struct {
+    int id, state, first_step, last_step, best_step, seen, taken, cls;
+    float conf;
+    int x0, y0, x1, y1, sharp, mean, pad;
+    long long score;
+} mars_shot_slot_t;                                                                                          /* 72 bytes */
+/* Zero-initialise; zero means default in every field. */
+typedef struct {
+    int max_gap;            /* 0: 30 */
+    int min_hits;           /* 0: 1 */
+    int min_mean, max_mean; /* 0 .. 255, min_mean <= max_mean; both 0: no window */
+    int min_sharp;
+    int src_w, src_h;       /* the frames' size: needed by MARS_SHOT_INSIDE only */
+    unsigned flags;         /* MARS_SHOT_STREAM_MAJOR | MARS_SHOT_KEEP_ASPECT | MARS_SHOT_INSIDE */
+} mars_hip_shot_opts_t;                                                                                      /* 32 bytes */
+typedef struct mars_hip_shots mars_hip_shots_t; /* opaque */
+/* Refused before any device work by every call below.  MARS_ERR_INVALID_FILE: NULL where a pointer is needed; non-positive streams, slots,
+ * sizes, crops or frames; a negative option; a mean outside 0 .. 255 or min_mean > max_mean; an unknown flag; MARS_SHOT_INSIDE without
+ * src_w and src_h; a negative cap.  MARS_ERR_INVALID_TENSOR: streams above 65535, slots above MARS_TRACK_SLOTS, tw or th above 1280, more
+ * than 65535 crops, F % S != 0, a stream or slot out of range, the pixels of a FREE slot, det_model == src_model, a model with an open
+ * pipe, no detections or no track results in HBM, no crop call into src_model out of this det_model, an input that is not int8 with 3
+ * channels, is kept at a row pitch (mars_hip_tensor_row_pitch), or whose size or layout is not the shots object's; *_results with nothing
+ * pending.  A refused call leaves the state as it was. */
+mars_error_t mars_hip_shots_create(int streams, int slots, int tw, int th, int nhwc, mars_hip_shots_t **out);
+void         mars_hip_shots_free(mars_hip_shots_t *sh);                            /* waits for the device first */
+/* That stream's table empty, its step and counters zero; -1: all streams; waits. */
+mars_error_t mars_hip_shots_reset(mars_hip_shots_t *sh, int stream);
+/* The end of a stream: waits, turns every LIVE slot DONE and adds them to `finished`; -1: all streams.  The step counter stays. */
+mars_error_t mars_hip_shots_flush(mars_hip_shots_t *sh, int stream);
+/* Waits.  counters = {finished, lost, dropped, overflow, duplicates, taken} of one stream, its LIVE and DONE slots and its step counter;
+ * any pointer may be NULL. */
+mars_error_t mars_hip_shots_read(mars_hip_shots_t *sh, int stream, long long counters[6], int *n_live, int *n_done, int *step);
+/* Waits.  The table of one stream, slots = [the object's slots], in canonical form. */
+mars_error_t mars_hip_shots_read_slots(mars_hip_shots_t *sh, int stream, mars_shot_slot_t *slots);
+/* Waits.  The picture of a LIVE or DONE slot: rgb = uint8 [th][tw][3], byte + 128 with the layout undone. */
+mars_error_t mars_hip_shots_read_pixels(mars_hip_shots_t *sh, int stream, int slot, unsigned char *rgb);
+/* How a deployment receives a finished track's picture.  Waits, copies the DONE slots by ascending slot, up to `cap`, into slots_out =
+ * [cap] with their pictures in rgb_out = [cap][th][tw][3] (either may be NULL with cap 0), and frees exactly those it copied.  *n = the
+ * number of DONE slots there were. */
+mars_error_t mars_hip_shots_collect(mars_hip_shots_t *sh, int stream, mars_shot_slot_t *slots_out, unsigned char *rgb_out, int cap, int *n);
+/* The mars_yolo_event_lists of this feature: host pointers in and out, runs the same kernels on the GPU and waits.  One entry of each
+ * array belongs to one crop: crops = [n_crops][tw * th * 3] int8 in the object's layout, rois, confs, cls, tracks and records = [n_crops];
+ * every crop counts as written (kept = n_crops, at most 65535).  A crop whose rois[k].frame lies outside [0, frames) has no content. */
+mars_error_t mars_yolo_shot_lists(mars_hip_shots_t *sh, const signed char *crops, const mars_roi_t *rois, const float *confs, const int *cls,
+                                  const mars_track_t *tracks, int n_crops, int frames, const mars_hip_shot_opts_t *opts, mars_shot_t *records);
+/* The device-only chain.  Reads the crops in input `input_index` of src_model and its ROI table as the last crop call out of det_model
+ * left them, and det_model's detection lists and the track array of its last mars_hip_track_device / _track_app_device (F = det_model's
+ * batch).  Enqueues only, on the auxiliary stream: behind the crop call (the main stream as given so far) and the tracker, ahead of
+ * det_model's next detect call and, through an event of its own, ahead of the next crop call into src_model.  The record array lives on
+ * src_model and is freed with it. */
+mars_error_t mars_hip_shots_device(mars_model_t *det_model, mars_model_t *src_model, int input_index, mars_hip_shots_t *sh,
+                                   const mars_hip_shot_opts_t *opts);
+/* Waits.  records = [batch of src_model]: entry k belongs to rois[k] of mars_hip_roi_results.  sh must be the object of the last
+ * mars_hip_shots_device call over src_model. */
+mars_error_t mars_hip_shots_results(mars_model_t *src_model, mars_hip_shots_t *sh, mars_shot_t *records);
+/* mars_hip_shots_device + mars_hip_shots_results. */
+mars_error_t mars_hip_shots(mars_model_t *det_model, mars_model_t *src_model, int input_index, mars_hip_shots_t *sh,
+                            const mars_hip_shot_opts_t *opts, mars_shot_t *records);
+/* Device time (ms) of the last call's three kernels (either form), from events on its stream; waits for it.  < 0: not available. */
+float mars_hip_shots_ms(mars_hip_shots_t *sh);
+
 #ifdef __cplusplus
 }
 #endif

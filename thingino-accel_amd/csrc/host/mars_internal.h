@@ -268,6 +268,10 @@ typedef struct mars_model_ext {
     mars_det_side_t motion; /* moved cells of THIS model's detections: x mars_motion_det_t */
     /* events (mars_events.c) */
     mars_det_side_t event;  /* event records of THIS model's detections: x mars_event_t */
+    /* best shots (mars_shots.c) */
+    mars_block_t shot;      /* shot records of the crops in THIS model's input: [batch] x mars_shot_t */
+    void *ev_shot_done;     /* a shots call (auxiliary stream) has read this model's input and ROI table: the next crop call into it waits */
+    int shot_pending;
     struct mars_model_ext *live_next; /* every loaded model, newest first (mars_live_models): a process-wide mode change re-plans the float ones */
 } mars_model_ext_t;
 
@@ -432,6 +436,13 @@ MARS_INTERNAL int mars_lut_stale(const mars_lut_cache_t *c, int n, const float k
 /* tables of n heads built for `key` go up to dst (nothing where they are up already): synchronises around the upload; c->n == 0 if it fails */
 MARS_INTERNAL mars_error_t mars_lut_refresh(mars_lut_cache_t *c, void *dst, int n, const float key[4][2], const float *tab, size_t floats_per_head);
 MARS_INTERNAL void mars_stages_release(mars_model_ext_t *m); /* every record above and the ROI table, of a model whose device state goes away */
+
+/* mars_shots.c: its parts that need no device (tests/c/shots_host.c drives them under the sanitizers) */
+MARS_INTERNAL mars_error_t mars_shots_opts(const mars_hip_shot_opts_t *o, mhip_shots_t *p); /* the checks, the defaults resolved into the launch record */
+MARS_INTERNAL mars_error_t mars_shots_map(int streams, int frames, int *steps);             /* F % S == 0 -> the steps of every stream */
+MARS_INTERNAL int mars_shots_frame(int streams, int steps, int stream_major, int stream, int step); /* the frame that is (stream, step) */
+/* a stored crop, int8 [th][tw][3] or [3][th][tw], -> uint8 [th][tw][3]: byte + 128, the layout undone */
+MARS_INTERNAL void mars_shots_relayout(const int8_t *src, int tw, int th, int nhwc, unsigned char *rgb);
 
 /* mars_yolo.c, shared with mars_classify.c */
 MARS_INTERNAL int mars_tensor_chw(const mars_tensor_t *d, int *c, int *h, int *w);

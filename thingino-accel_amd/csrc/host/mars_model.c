@@ -133,6 +133,7 @@ void mars_free(mars_model_t *model) {
     if (m->ev_graph_done) mhip_event_destroy(m->ev_graph_done);
     if (m->ev_tail_done) mhip_event_destroy(m->ev_tail_done);
     if (m->ev_label_done) mhip_event_destroy(m->ev_label_done);
+    if (m->ev_shot_done) mhip_event_destroy(m->ev_shot_done);
     if (m->ev_fork) mhip_event_destroy(m->ev_fork);
     for (int k = 0; k < 3; k++)
         if (m->ev_join[k]) mhip_event_destroy(m->ev_join[k]);

@@ -239,6 +239,10 @@ static mars_error_t crop_device(mars_model_t *det_model, const void *frames_dev,
         if (mhip_stream_wait(0, m->ev_label_done)) return MARS_ERR_LAYER_FAILED;
         m->label_pending = 0;
     }
+    if (m->shot_pending) { /* ... or a shots call (mars_hip_shots_device, auxiliary stream) still reads the input and the table */
+        if (mhip_stream_wait(0, m->ev_shot_done)) return MARS_ERR_LAYER_FAILED;
+        m->shot_pending = 0;
+    }
     if (mode == MODE_ALIGN ? (mhip_roi_align_select(&p) || mhip_roi_align_crop(&p))
                            : rot ? (mhip_roi_rot_select(&p) || mhip_roi_rot_crop(&p)) : (mhip_roi_select(&p) || mhip_roi_crop(&p)))
         return MARS_ERR_LAYER_FAILED;

@@ -2,7 +2,7 @@
  * mars_stage.c -- what the stages behind the detection tail share on the host (mars_internal.h, "tail stages"): the result block hung on a
  * model, the per-detection side arrays hung on a detector and the scatter that fills two of them, where the plan left an int8 side tensor,
  * the scale-keyed tables, the graph input that takes int8 pixels, and the hand-off from the selected stream to the auxiliary one.  No launch
- * of its own but the scatter's; the stage files (mars_seg.c, mars_pose.c, mars_obb.c, mars_tile.c, mars_redact.c, mars_overlay.c, mars_motion.c, mars_events.c, mars_roi.c,
+ * of its own but the scatter's; the stage files (mars_seg.c, mars_pose.c, mars_obb.c, mars_tile.c, mars_redact.c, mars_overlay.c, mars_motion.c, mars_events.c, mars_shots.c, mars_roi.c,
  * mars_classify.c, mars_gallery.c, mars_track.c), the front-end's target (mars_preproc.c) and the tails and table functions of mars_yolo.c
  * are written on top of it.
  */
@@ -181,11 +181,11 @@ mars_error_t mars_lut_refresh(mars_lut_cache_t *c, void *dst, int n, const float
 void mars_stages_release(mars_model_ext_t *m) {
     mars_roi_release(m);
     mars_block_t *blocks[] = {&m->cls, &m->match, &m->seg, &m->segn, &m->pose, &m->obb, &m->tile_roi, &m->tile, &m->track_app, &m->redact,
-                            &m->overlay};
+                            &m->overlay, &m->shot};
     mars_det_side_t *sides[] = {&m->label, &m->ident, &m->track, &m->motion, &m->event};
     for (size_t i = 0; i < sizeof(blocks) / sizeof(blocks[0]); i++) mars_block_release(blocks[i]);
     for (size_t i = 0; i < sizeof(sides) / sizeof(sides[0]); i++) mars_side_release(sides[i]);
-    m->cls_c = m->cls_top_k = m->match_top_k = m->label_pending = 0;
+    m->cls_c = m->cls_top_k = m->match_top_k = m->label_pending = m->shot_pending = 0;
     m->seg_max = m->seg_ph = m->seg_pw = m->pose_max = m->pose_k = 0;
     m->segn_max = m->segn_oh = m->segn_ow = 0;
     memset(m->segn_key, 0, sizeof(m->segn_key)); /* (those tables lived inside the block) */

@@ -841,6 +841,48 @@ typedef struct {
 } mhip_events_t;
 int mhip_events(const mhip_events_t *p); /* one launch */
 
+/* ---- best shots (shots.hip): the crops in a second model's input, their ROI table and the track ids -> a quality measure per crop and, per
+ * stream, a table that keeps the best crop of every live track with its pixels, by the exact rule of include/mars_hip.h ("Best shots").
+ * Three launches: the metrics of every crop (band partials), the walk (one workgroup per stream, its steps in order), the copy of each
+ * slot's final winner into the plane.  Every pointer is device memory. */
+#define MHIP_SHOTS_COUNTERS 6
+#define MHIP_SHOTS_LDS 40960 /* bytes of staged rows and luma a metrics workgroup may hold: decides the band height */
+/* a stream's step counter and counters: finished, lost, dropped, overflow, duplicates, taken */
+typedef struct { int step, pad; long long cnt[MHIP_SHOTS_COUNTERS]; } mhip_shots_hdr_t;
+typedef struct {
+    int streams, steps;      /* frames = streams * steps */
+    int slots;               /* table slots per stream: 1 .. MHIP_TRACK_SLOTS */
+    int n_crops;             /* entries of crops, rois, partials, cand and records */
+    int tw, th, nhwc;        /* a crop: tw * th * 3 int8, [th][tw][3] or [3][th][tw] */
+    int band_rows, bands;    /* rows a metrics workgroup owns (mhip_shots_band_rows), and ceil(th / band_rows) */
+    int stream_major, keep_aspect, inside, src_w, src_h;
+    int max_gap, min_hits;   /* resolved: >= 1 */
+    int min_mean, max_mean, min_sharp; /* min_mean == max_mean == 0: no window */
+    const int8_t *crops;     /* crop k at crops + k * crop_stride */
+    size_t crop_stride;
+    const void *rois;        /* [n_crops] records of 24 bytes (mars_roi_t) */
+    const int *kept;         /* the number of crops written, clamped to 0 .. n_crops; NULL: n_crops */
+    /* det_cap == 0: one entry per crop.  det_cap > 0: lists of det_cap entries per frame, crop k's entry is [rois[k].frame][rois[k].det] */
+    int det_cap;
+    const float *confs;      /* det_cap == 0: [n_crops] */
+    const int *cls;          /* det_cap == 0: [n_crops] */
+    const void *dets;        /* det_cap > 0: [frames][det_cap] records of 24 bytes (mars_det_t) */
+    const void *tracks;      /* [n_crops] or [frames][det_cap] records of 8 bytes {int id, hits} */
+    long long *partials;     /* scratch: [n_crops][bands][2], the bands' sums of Y and of L * L */
+    int *cand;               /* scratch: [n_crops], the id a crop brings as a candidate of its step, 0: none */
+    void *records;           /* [n_crops] records of 24 bytes (mars_shot_t) */
+    void *table;             /* [streams][slots] records of 72 bytes (mars_shot_slot_t) */
+    mhip_shots_hdr_t *hdr;   /* [streams] */
+    int8_t *plane;           /* [streams][slots] crops at a pitch of plane_stride bytes, in the crops' layout */
+    size_t plane_stride;     /* a multiple of 16 */
+    int *last;               /* [streams][slots]: the crop the walk stored last in that slot in this call, or -1 */
+} mhip_shots_t;
+static inline int mhip_shots_band_rows(int tw) { /* 16 rows, fewer where 4 bytes a pixel of band and halo rows would not fit */
+    const int fit = MHIP_SHOTS_LDS / (tw * 4) - 2;
+    return fit > 16 ? 16 : fit < 1 ? 1 : fit;
+}
+int mhip_shots(const mhip_shots_t *p); /* the three launches */
+
 #ifdef __cplusplus
 }
 #endif

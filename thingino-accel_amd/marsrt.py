@@ -283,7 +283,21 @@ class EventsOpts(C.Structure):  # mars_hip_events_opts_t: zero = default in ever
     _fields_ = [("max_gap", C.c_int), ("min_hits", C.c_int), ("flags", C.c_uint)]
 
 
+SHOT_STREAM_MAJOR, SHOT_KEEP_ASPECT, SHOT_INSIDE = 1, 2, 4                # MARS_SHOT_*
+SHOT_FREE, SHOT_LIVE, SHOT_DONE = 0, 1, 2
+SHOT_DTYPE = np.dtype([("score", "<i8"), ("sharp", "<i4"), ("mean", "<i4"), ("slot", "<i4"), ("taken", "<i4")])  # mars_shot_t
+SHOT_SLOT_DTYPE = np.dtype([("id", "<i4"), ("state", "<i4"), ("first_step", "<i4"), ("last_step", "<i4"), ("best_step", "<i4"), ("seen", "<i4"),
+                            ("taken", "<i4"), ("cls", "<i4"), ("conf", "<f4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"),
+                            ("sharp", "<i4"), ("mean", "<i4"), ("pad", "<i4"), ("score", "<i8")])  # mars_shot_slot_t
+
+
+class ShotOpts(C.Structure):  # mars_hip_shot_opts_t: zero = default in every field
+    _fields_ = [("max_gap", C.c_int), ("min_hits", C.c_int), ("min_mean", C.c_int), ("max_mean", C.c_int), ("min_sharp", C.c_int),
+                ("src_w", C.c_int), ("src_h", C.c_int), ("flags", C.c_uint)]
+
+
 assert C.sizeof(MarsHeader) == 76 and C.sizeof(MarsTensorDesc) == 124
+assert SHOT_DTYPE.itemsize == 24 and SHOT_SLOT_DTYPE.itemsize == 72 and C.sizeof(ShotOpts) == 32
 assert EVENT_DTYPE.itemsize == 24 and EVENT_SLOT_DTYPE.itemsize == 152 and C.sizeof(EventRules) == 2824 and C.sizeof(EventsOpts) == 12
 assert MOTION_STATS_DTYPE.itemsize == 24 and MOTION_DET_DTYPE.itemsize == 8 and C.sizeof(MotionOpts) == 32
 assert REDACT_STATS_DTYPE.itemsize == 16 and C.sizeof(RedactOpts) == 52
@@ -358,7 +372,10 @@ EXPORTS = {
                    "mars_hip_motion_det_results", "mars_yolo_motion_boxes", "mars_hip_motion_ms",
                    "mars_hip_events_create", "mars_hip_events_free", "mars_hip_events_reset", "mars_hip_events_set_rules", "mars_hip_events_read",
                    "mars_hip_events_read_slots", "mars_yolo_event_lists", "mars_hip_events_device", "mars_hip_events_results", "mars_hip_events",
-                   "mars_hip_events_ms"],
+                   "mars_hip_events_ms",
+                   "mars_hip_shots_create", "mars_hip_shots_free", "mars_hip_shots_reset", "mars_hip_shots_flush", "mars_hip_shots_read",
+                   "mars_hip_shots_read_slots", "mars_hip_shots_read_pixels", "mars_hip_shots_collect", "mars_yolo_shot_lists",
+                   "mars_hip_shots_device", "mars_hip_shots_results", "mars_hip_shots", "mars_hip_shots_ms"],
     "mars_compile.h": ["mars_compile_onnx", "mars_compile_file", "mars_compile_last_error"],
 }
 
@@ -579,6 +596,22 @@ def lib():
     L.mars_hip_events.argtypes = [P(MarsModel), C.c_void_p, P(EventsOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.mars_hip_events_ms.restype = C.c_float
     L.mars_hip_events_ms.argtypes = [C.c_void_p]
+    L.mars_hip_shots_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_void_p)]
+    L.mars_hip_shots_free.argtypes = [C.c_void_p]
+    L.mars_hip_shots_free.restype = None
+    L.mars_hip_shots_reset.argtypes = [C.c_void_p, C.c_int]
+    L.mars_hip_shots_flush.argtypes = [C.c_void_p, C.c_int]
+    L.mars_hip_shots_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int)]
+    L.mars_hip_shots_read_slots.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mars_hip_shots_read_pixels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.mars_hip_shots_collect.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, P(C.c_int)]
+    L.mars_yolo_shot_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(ShotOpts),
+                                       C.c_void_p]
+    L.mars_hip_shots_device.argtypes = [P(MarsModel), P(MarsModel), C.c_int, C.c_void_p, P(ShotOpts)]
+    L.mars_hip_shots_results.argtypes = [P(MarsModel), C.c_void_p, C.c_void_p]
+    L.mars_hip_shots.argtypes = [P(MarsModel), P(MarsModel), C.c_int, C.c_void_p, P(ShotOpts), C.c_void_p]
+    L.mars_hip_shots_ms.restype = C.c_float
+    L.mars_hip_shots_ms.argtypes = [C.c_void_p]
     L.mars_hip_set_profiling.argtypes = [P(MarsModel), C.c_int]
     L.mars_hip_set_profiling.restype = None
     L.mars_hip_tensor_device.restype = C.c_void_p
@@ -1225,6 +1258,110 @@ def event_lists(events, dets, tracks, counts, opts=None):
     if rc != MARS_OK:
         raise MarsError(rc, "mars_yolo_event_lists")
     return rec, lc, zc
+
+
+def shot_opts(max_gap=0, min_hits=0, min_mean=0, max_mean=0, min_sharp=0, src=None, stream_major=False, keep_aspect=False, inside=False,
+              flags=None):
+    """mars_hip_shot_opts_t; zero means default everywhere (max_gap 30, min_hits 1, no mean window, stretch geometry).  src = (w, h) of
+    the frames, needed by inside only.  flags overrides stream_major, keep_aspect and inside"""
+    f = int(flags) if flags is not None else ((SHOT_STREAM_MAJOR if stream_major else 0) | (SHOT_KEEP_ASPECT if keep_aspect else 0) |
+                                              (SHOT_INSIDE if inside else 0))
+    w, h = src if src is not None else (0, 0)
+    return ShotOpts(int(max_gap), int(min_hits), int(min_mean), int(max_mean), int(min_sharp), int(w), int(h), f)
+
+
+class Shots:
+    """mars_hip_shots_t: per camera stream a table of `slots` entries with the best crop of every live track, its pixels in a plane of
+    tw x th x 3 int8 crops, a step counter and counters, held on the device between calls"""
+
+    def __init__(self, streams, slots, tw, th, nhwc=True):
+        self.streams, self.slots, self.tw, self.th, self.nhwc = int(streams), int(slots), int(tw), int(th), bool(nhwc)
+        self.p = C.c_void_p()
+        rc = lib().mars_hip_shots_create(self.streams, self.slots, self.tw, self.th, int(self.nhwc), C.byref(self.p))
+        if rc != MARS_OK:
+            self.p = C.c_void_p()
+            raise MarsError(rc, "mars_hip_shots_create")
+
+    def reset(self, stream=-1):
+        """that stream's table empty, its step and counters zero (-1: all streams); waits"""
+        rc = lib().mars_hip_shots_reset(self.p, int(stream))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_reset")
+
+    def flush(self, stream=-1):
+        """the end of a stream: every LIVE slot becomes DONE and adds to `finished` (mars_hip_shots_flush); waits"""
+        rc = lib().mars_hip_shots_flush(self.p, int(stream))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_flush")
+
+    def read(self, stream):
+        """-> (counters int64 [finished, lost, dropped, overflow, duplicates, taken], LIVE slots, DONE slots, step) of one stream
+        (mars_hip_shots_read); waits"""
+        cnt = np.zeros(6, dtype=np.int64)
+        live, done, step = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = lib().mars_hip_shots_read(self.p, int(stream), cnt.ctypes.data, C.byref(live), C.byref(done), C.byref(step))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_read")
+        return cnt, live.value, done.value, step.value
+
+    def read_slots(self, stream):
+        """-> SHOT_SLOT_DTYPE [slots], the table of one stream in canonical form (mars_hip_shots_read_slots); waits"""
+        slots = np.zeros(self.slots, dtype=SHOT_SLOT_DTYPE)
+        rc = lib().mars_hip_shots_read_slots(self.p, int(stream), slots.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_read_slots")
+        return slots
+
+    def pixels(self, stream, slot):
+        """-> uint8 [th][tw][3], the picture of a LIVE or DONE slot (mars_hip_shots_read_pixels); waits"""
+        rgb = np.zeros((self.th, self.tw, 3), dtype=np.uint8)
+        rc = lib().mars_hip_shots_read_pixels(self.p, int(stream), int(slot), rgb.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_read_pixels")
+        return rgb
+
+    def collect(self, stream, cap):
+        """-> (SHOT_SLOT_DTYPE [k], uint8 [k][th][tw][3], DONE slots there were): the first k = min(cap, DONE) finished shots by ascending
+        slot with their pictures; those k slots are FREE afterwards (mars_hip_shots_collect); waits"""
+        cap = int(cap)
+        slots = np.zeros(max(cap, 1), dtype=SHOT_SLOT_DTYPE)
+        rgb = np.zeros((max(cap, 1), self.th, self.tw, 3), dtype=np.uint8)
+        n = C.c_int(0)
+        rc = lib().mars_hip_shots_collect(self.p, int(stream), slots.ctypes.data, rgb.ctypes.data, cap, C.byref(n))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_collect")
+        k = max(min(cap, n.value), 0)
+        return slots[:k].copy(), rgb[:k].copy(), n.value
+
+    def ms(self):
+        """device time (ms) of the last call's kernels (mars_hip_shots_ms); < 0: not available"""
+        return float(lib().mars_hip_shots_ms(self.p))
+
+    def close(self):
+        if self.p:
+            lib().mars_hip_shots_free(self.p)
+            self.p = C.c_void_p()
+
+
+def shot_lists(shots, crops, rois, confs, cls, tracks, frames, opts=None):
+    """mars_yolo_shot_lists: crops = int8 [n][tw * th * 3] in the object's layout, rois = ROI_DTYPE [n], confs = float32 [n], cls = int32
+    [n], tracks = TRACK_DTYPE [n], one entry per crop, over `frames` frames -> SHOT_DTYPE [n], on the GPU; the object's tables move on
+    by these frames"""
+    x = np.ascontiguousarray(crops, dtype=np.int8)
+    r = np.ascontiguousarray(rois, dtype=ROI_DTYPE).reshape(-1)
+    n = r.size
+    cf = np.ascontiguousarray(confs, dtype=np.float32).reshape(-1)
+    cl = np.ascontiguousarray(cls, dtype=np.int32).reshape(-1)
+    t = np.ascontiguousarray(tracks, dtype=TRACK_DTYPE).reshape(-1)
+    if x.size != n * shots.tw * shots.th * 3 or cf.size != n or cl.size != n or t.size != n:
+        raise ValueError("one crop of tw * th * 3 bytes, one ROI, confidence, class and track per crop")
+    o = opts if opts is not None else shot_opts()
+    rec = np.zeros(n, dtype=SHOT_DTYPE)
+    rc = lib().mars_yolo_shot_lists(shots.p, x.ctypes.data, r.ctypes.data, cf.ctypes.data, cl.ctypes.data, t.ctypes.data, n, int(frames),
+                                    C.byref(o), rec.ctypes.data)
+    if rc != MARS_OK:
+        raise MarsError(rc, "mars_yolo_shot_lists")
+    return rec
 
 
 def cls_opts(output_index=0, tensor=0, top_k=0, scale=0.0, softmax=False):
@@ -2276,6 +2413,32 @@ class Model:
         if rc != MARS_OK:
             raise MarsError(rc, "mars_hip_events")
         return rec, lc, zc
+
+    def shots_device(self, det_model, shots, opts=None, input_index=0, **kw):
+        """THIS model is the second stage: the crops the last crop call out of det_model wrote into its input, its ROI table, and
+        det_model's detection lists and track ids go through the shots object, on the device (mars_hip_shots_device); enqueues only.
+        opts = shot_opts(...), or its keywords"""
+        o = opts if opts is not None else shot_opts(**kw)
+        rc = lib().mars_hip_shots_device(det_model.p, self.p, int(input_index), shots.p, C.byref(o))
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_device")
+
+    def shots_results(self, shots):
+        """-> SHOT_DTYPE [batch]: entry k belongs to roi_results()[0][k] (mars_hip_shots_results); waits"""
+        rec = np.zeros(self.batch, dtype=SHOT_DTYPE)
+        rc = lib().mars_hip_shots_results(self.p, shots.p, rec.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots_results")
+        return rec
+
+    def shots(self, det_model, shots, opts=None, input_index=0, **kw):
+        """shots_device + shots_results (mars_hip_shots)"""
+        o = opts if opts is not None else shot_opts(**kw)
+        rec = np.zeros(self.batch, dtype=SHOT_DTYPE)
+        rc = lib().mars_hip_shots(det_model.p, self.p, int(input_index), shots.p, C.byref(o), rec.ctypes.data)
+        if rc != MARS_OK:
+            raise MarsError(rc, "mars_hip_shots")
+        return rec
 
     def write_tensor(self, idx, data, frame=0):
         """mars_hip_write_tensor: one frame of an activation tensor from host memory"""
